@@ -205,6 +205,25 @@ def roofline_block(key, kernel, launch_ms, kernel_ms_median, cnt, alg_bytes):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21  # 2M pixels: 32 MB of channels + 16 MB of indices
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the RGBA8 frame a caller of the timed path receives ((H, W) uint32, 4 bytes R G B A per pixel) as
+    out_dir/rgba8.npy, float32 (H, W, 4) holding the channel values 0..255.  When that exceeds DUMP_MAX_BYTES (c5: 3840x2160) it is
+    a fixed seeded sample of pixels instead: rgba8.npy (n, 4) and rgba8_pixel_index.npy (n,), their row-major indices (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    H, W = frame.shape
+    px = np.ascontiguousarray(frame).view(np.uint8).reshape(H * W, 4).astype(np.float32)
+    if px.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "rgba8.npy"), px.reshape(H, W, 4))
+        return
+    idx = np.sort(np.random.default_rng(0).choice(H * W, size=DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "rgba8.npy"), px[idx])
+    np.save(os.path.join(out_dir, "rgba8_pixel_index.npy"), idx.astype(np.float64))
+
+
 def default_policy(world, multi, path, inflight=0, batch=0):
     """(launches in flight, frames per launch) of the timed region: see the module docstring.  0 = default."""
     n_fly = inflight if inflight > 0 else (4 if multi else 1)
@@ -244,7 +263,11 @@ def main():
     ap.add_argument("--same-device", action="store_true", help="every rank renders on GPU 0 (rehearsal with --backend gloo)")
     ap.add_argument("--rendezvous-only", action="store_true", help="the ranks meet, add up their ranks and leave: checks the launch path "
                     "without a GPU (tests/test_tiling.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the frame the last timed step "
+                    "rendered to DIR/rgba8.npy (see dump_outputs), so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     launched = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if args.gpus > 1 and not launched:
@@ -616,6 +639,8 @@ def main():
             line["frame_rows_checked"] = int(len(rows))
             if not ok:
                 line["frame_mismatching_pixels"] = int((last_frame[rows] != ref[rows]).sum())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_frame)
         print(json.dumps(line), flush=True)
     if multi:
         dist.barrier()

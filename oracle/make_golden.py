@@ -13,8 +13,10 @@ a tool linked against the reference's CRT* sources compiled in place (oracle/Mak
   tests/golden/dragon.crtscene           the same scene DATA re-serialised from the reference's parsed
                                          values (float32 printed with 9 significant digits round-trips
                                          exactly) so the GPU box, which has no /root/reference, can load it.
+  tests/golden/dragon_original.crtscene  the shipped scene file itself, byte for byte (a data fixture: the parser reads
+                                         its CRLF / tab layout in tests/test_scene_layer.py)
 """
-import json, os, subprocess, sys
+import json, os, shutil, subprocess, sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -51,6 +53,7 @@ def main():
     }
     with open(os.path.join(gold, "dragon.crtscene"), "w") as f:
         json.dump(scene, f, separators=(",", ":"))
+    shutil.copyfile(REF_SCENE, os.path.join(gold, "dragon_original.crtscene"))
 
     # 2) known answers (drop the bulky raw geometry: it lives in the scene file above)
     for m in d["meshes"]:

@@ -6,9 +6,6 @@ import os
 import numpy as np
 import pytest
 
-REF_DRAGON = "/root/reference/DirectX-RayTracer/DirectX-RayTracer/Scenes/Dragon.crtscene"
-
-
 @pytest.fixture(scope="module")
 def gold(golden_dir):
     return json.load(open(os.path.join(golden_dir, "dragon_scene_layer.json")))
@@ -90,10 +87,10 @@ def test_python_vertex_normals_helper_matches(scenes, dragon, gold):
     np.testing.assert_allclose(n, np.array(gold["meshes"][1]["vertex_normals"], dtype=np.float32), rtol=0, atol=1e-6)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_DRAGON), reason="reference tree not mounted (GPU box)")
-def test_original_scene_file_parses_to_the_same_data(pkg, scene):
-    """The reference's shipped Dragon.crtscene, read in place, gives the same arrays as the re-serialised fixture."""
-    orig = pkg.Scene(REF_DRAGON)
+def test_original_scene_file_parses_to_the_same_data(pkg, scene, golden_dir):
+    """The reference's shipped Dragon.crtscene (byte for byte: tests/golden/dragon_original.crtscene, CRLF and tabs as shipped)
+    gives the same arrays as the re-serialised fixture."""
+    orig = pkg.Scene(os.path.join(golden_dir, "dragon_original.crtscene"))
     assert orig.mesh_count == scene.mesh_count
     for i in range(orig.mesh_count):
         a, b = orig.mesh(i), scene.mesh(i)
