@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "crt_scene_camera_get", "crt_scene_camera_set", "crt_scene_camera_rotate", "crt_scene_camera_zoom",
     "crt_scene_camera_move_forward", "crt_scene_camera_move_right", "crt_scene_camera_pan", "crt_scene_camera_tilt",
     "crt_scene_camera_roll", "crt_scene_camera_pan_around_target", "crt_upload_scene_from", "crt_set_camera_from",
+    "crt_set_accumulation", "crt_reset_accumulation", "crt_accumulated_samples",
 ]
 
 
@@ -190,6 +191,9 @@ def lib():
         "crt_scene_camera_pan_around_target": (C.c_int, [vp, f32, vp]),
         "crt_upload_scene_from": (C.c_int, [vp, vp]),
         "crt_set_camera_from": (C.c_int, [vp, vp]),
+        "crt_set_accumulation": (C.c_int, [vp, u32]),
+        "crt_reset_accumulation": (C.c_int, [vp]),
+        "crt_accumulated_samples": (C.c_int, [vp, C.POINTER(u32)]),
     }
     assert set(sig) == set(ABI_SYMBOLS)
     for name, (res, args) in sig.items():
@@ -582,6 +586,20 @@ class Renderer:
 
     def set_option(self, name, value):
         self._ok(lib().crt_set_option(self.h, name.encode(), int(value)), "crt_set_option")
+
+    def set_accumulation(self, max_samples):
+        """mode 200: frames add their samples to per-pixel sums while the view holds still, up to max_samples per pixel
+        (0 = off); always starts over (include/crt_hip.h)"""
+        self._ok(lib().crt_set_accumulation(self.h, int(max_samples)), "crt_set_accumulation")
+
+    def reset_accumulation(self):
+        self._ok(lib().crt_reset_accumulation(self.h), "crt_reset_accumulation")
+
+    def accumulated_samples(self):
+        """samples per pixel in the current sums (0 when accumulation is off or was reset)"""
+        n = C.c_uint32()
+        self._ok(lib().crt_accumulated_samples(self.h, C.byref(n)), "crt_accumulated_samples")
+        return n.value
 
     def read_counters(self):
         buf = np.zeros(32, dtype=np.uint64)

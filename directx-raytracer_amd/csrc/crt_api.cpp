@@ -172,6 +172,24 @@ struct crt_ctx {
     // scratch frame buffers for the host-output path, grown on demand
     void* dFrame[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
     size_t dFrameBytes[5] = { 0, 0, 0, 0, 0 };
+
+    // progressive accumulation (crt_set_accumulation): mode-200 frames add their samples to per-pixel sums while the key holds.
+    // Everything a frame's samples depend on is in the key; spp, counting and the tuning options are not (results never depend
+    // on them).  Floats are compared bitwise: a viewer that sets the same pose every tick keeps accumulating.
+    struct AccKey {
+        float pos[3], rot[9], miss[3];
+        uint32_t mode, bounces, seed, sceneSerial, textureSerial, width, height, kind, rank, nRanks;
+    };
+    uint32_t textureSerial = 0;     // bumped by crt_set_textures
+    uint32_t accMax = 0;            // samples per pixel the sums may reach; 0 = off
+    uint32_t accSamples = 0;        // samples per pixel in the sums
+    AccKey accKey{};                // what the sums belong to (meaningful while accSamples > 0)
+    void* dAccum = nullptr;         // float4 per output index of the RGBA8 store (pixel, or staging index of a tile share)
+    size_t accumBytes = 0;
+    // consecutive accumulating frames depend on each other through the sums: the next one waits (on the GPU) for the last one
+    hipEvent_t evAccum = nullptr;
+    hipStream_t accumStream = nullptr;
+    bool accumPending = false;
 };
 
 namespace {
@@ -274,6 +292,25 @@ void fillParams(const crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_
     p.stack_entries = c->tuneStackEntries ? c->tuneStackEntries : 16u;
     p.n_batch = 1;
     p.units_per_frame = crt::renderUnitCount(p);
+}
+
+// a frame that uses the sums runs after the last one that did, even when issued on another stream (crt_set_stream)
+int orderAccum(crt_ctx* c)
+{
+    if (!c->evAccum) HIP_TRY(c, hipEventCreateWithFlags(&c->evAccum, hipEventDisableTiming));
+    if (c->accumPending && c->accumStream != c->stream && hipEventQuery(c->evAccum) != hipSuccess)
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evAccum, 0));
+    return CRT_OK;
+}
+
+// after the launch: the sums now hold acc_total samples
+int commitAccum(crt_ctx* c, const RenderParams& p)
+{
+    HIP_TRY(c, hipEventRecord(c->evAccum, c->stream));
+    c->accumStream = c->stream;
+    c->accumPending = true;
+    c->accSamples = p.acc_total;
+    return CRT_OK;
 }
 
 // enqueue one frame; when stats != nullptr, bracket with events, synchronise and fill the timers/counters
@@ -428,6 +465,10 @@ int runRender(crt_ctx* c, RenderParams& p, crt_frame_stats* stats)
     // (a wait is only enqueued when it can matter: not for an event that has already completed, not for a frame that ran on
     // this same stream -- every barrier packet costs the stream a few microseconds)
     if (c->sortPending[slot] && hipEventQuery(c->evSort[slot]) != hipSuccess) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evSort[slot], 0));
+    if (p.acc_sum) {
+        const int ro = orderAccum(c);
+        if (ro) return ro;
+    }
     if (c->renderPending[slot] && c->slotStream[slot] != c->stream && hipEventQuery(c->evRender[slot]) != hipSuccess)
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evRender[slot], 0));
     c->sortPending[slot] = false;
@@ -443,6 +484,10 @@ int runRender(crt_ctx* c, RenderParams& p, crt_frame_stats* stats)
     if (arena) {
         HIP_TRY(c, hipEventRecord(arena->lastUse, c->stream));
         arena->pending = true;
+    }
+    if (p.acc_sum) {
+        const int ra = commitAccum(c, p);
+        if (ra) return ra;
     }
     if (feedback) {
         hipStream_t ss = c->sideStream;
@@ -480,6 +525,83 @@ int runRender(crt_ctx* c, RenderParams& p, crt_frame_stats* stats)
         }
     }
     return CRT_OK;
+}
+
+enum { kAccFrame = 1u, kAccTiles = 2u }; // the entry-point kinds whose frames accumulate (part of the key)
+
+// Mode 200 with accumulation on: start the sums over when the key changed, make room for them, and choose the samples this call
+// traces: acc_base .. acc_base + spp - 1, at most up to the limit.  p.spp = 0 afterwards: the sums are at the limit and the call
+// only resolves them (runAccumResolve).  Other modes leave p and the sums alone.
+int beginAccum(crt_ctx* c, RenderParams& p, uint32_t kind)
+{
+    if (c->accMax == 0u || p.mode < 200u) return CRT_OK;
+    crt_ctx::AccKey k;
+    std::memset(&k, 0, sizeof(k));
+    crt::copyBytes(k.pos, p.pos, sizeof(k.pos));
+    crt::copyBytes(k.rot, p.rot, sizeof(k.rot));
+    crt::copyBytes(k.miss, p.miss, sizeof(k.miss));
+    k.mode = p.mode;
+    k.bounces = p.max_bounces;
+    k.seed = p.seed;
+    k.sceneSerial = c->sceneSerial;
+    k.textureSerial = c->textureSerial;
+    k.width = p.width;
+    k.height = p.height;
+    k.kind = kind;
+    k.rank = p.rank;
+    k.nRanks = p.n_ranks;
+    if (c->accSamples == 0u || std::memcmp(&k, &c->accKey, sizeof(k)) != 0) {
+        c->accSamples = 0u;
+        c->accKey = k;
+    }
+    const size_t outputs = kind == kAccTiles ? static_cast<size_t>(crt_tile_slots(p.width, p.height, p.n_ranks)) * crt::kTile * crt::kTile
+                                             : static_cast<size_t>(p.width) * p.height;
+    const size_t need = outputs * 4u * sizeof(float);
+    if (c->accumBytes < need) { // (a larger frame: the key has changed, nothing in the old sums is kept)
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipDeviceSynchronize()); // frames of other streams may still use the old buffer
+        if (c->dAccum) (void)hipFree(c->dAccum);
+        c->dAccum = nullptr;
+        c->accumBytes = 0;
+        HIP_TRY(c, hipMalloc(&c->dAccum, need));
+        c->accumBytes = need;
+    }
+    const uint32_t traced = std::min(p.spp, c->accMax - c->accSamples);
+    p.acc_sum = c->dAccum;
+    p.acc_base = c->accSamples;
+    p.acc_total = c->accSamples + traced;
+    p.spp = traced;
+    return CRT_OK;
+}
+
+// accumulation at its limit: the stored sums resolved once more, no ray traced (stats: zero rays)
+int runAccumResolve(crt_ctx* c, const RenderParams& p, crt_frame_stats* stats)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = orderAccum(c);
+    if (rc) return rc;
+    if (c->counting) HIP_TRY(c, hipMemsetAsync(c->dCounters, 0, 32 * sizeof(unsigned long long), c->stream));
+    if (stats) HIP_TRY(c, hipEventRecord(c->evStart, c->stream));
+    rc = crt::launchPathAccumResolve(p, c->stream);
+    if (rc != 0) return fail(c, CRT_EHIP, "resolve kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+    if (stats) HIP_TRY(c, hipEventRecord(c->evStop, c->stream));
+    if ((rc = commitAccum(c, p)) != CRT_OK) return rc;
+    if (stats) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->evStart, c->evStop));
+        std::memset(stats, 0, sizeof(*stats));
+        stats->kernel_ms = ms;
+    }
+    return CRT_OK;
+}
+
+// one frame of an entry point that accumulates (kind: kAccFrame / kAccTiles)
+int runFrame(crt_ctx* c, RenderParams& p, crt_frame_stats* stats, uint32_t kind)
+{
+    const int rc = beginAccum(c, p, kind);
+    if (rc) return rc;
+    return p.acc_sum && p.spp == 0u ? runAccumResolve(c, p, stats) : runRender(c, p, stats);
 }
 
 int checkRenderable(crt_ctx* c, uint32_t w, uint32_t h)
@@ -576,6 +698,8 @@ void crt_destroy(crt_ctx* c)
     }
     if (c->sideStream) (void)hipStreamDestroy(c->sideStream);
     if (c->dTimeline) (void)hipFree(c->dTimeline);
+    if (c->dAccum) (void)hipFree(c->dAccum);
+    if (c->evAccum) (void)hipEventDestroy(c->evAccum);
     if (c->evStart) (void)hipEventDestroy(c->evStart);
     if (c->evStop) (void)hipEventDestroy(c->evStop);
     if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
@@ -744,6 +868,7 @@ int crt_set_textures(crt_ctx* c, const crt_texture* textures, uint32_t n)
     if (c->dTexels) (void)hipFree(c->dTexels);
     c->dTextures = c->dTexels = nullptr;
     c->nTextures = 0;
+    c->textureSerial++; // accumulated sums of the old textures are stale
     HIP_TRY(c, hipMalloc(&c->dTextures, sizeof(crt::TextureRec) * (n + 1)));
     HIP_TRY(c, hipMalloc(&c->dTexels, pool.size() + 16));
     if (n) HIP_TRY(c, hipMemcpy(c->dTextures, recs.data(), sizeof(crt::TextureRec) * n, hipMemcpyHostToDevice));
@@ -962,6 +1087,36 @@ int crt_synchronize(crt_ctx* c)
     return CRT_OK;
 }
 
+int crt_set_accumulation(crt_ctx* c, uint32_t max_samples)
+{
+    if (!c) return CRT_EINVAL;
+    if (max_samples > (1u << 24)) return fail(c, CRT_EINVAL, "crt_set_accumulation: max_samples %u above 2^24", max_samples);
+    c->accMax = max_samples;
+    c->accSamples = 0u;
+    if (max_samples == 0u && c->dAccum) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipDeviceSynchronize()); // frames in flight may still use the sums
+        (void)hipFree(c->dAccum);
+        c->dAccum = nullptr;
+        c->accumBytes = 0;
+    }
+    return CRT_OK;
+}
+
+int crt_reset_accumulation(crt_ctx* c)
+{
+    if (!c) return CRT_EINVAL;
+    c->accSamples = 0u;
+    return CRT_OK;
+}
+
+int crt_accumulated_samples(const crt_ctx* c, uint32_t* samples)
+{
+    if (!c || !samples) return CRT_EINVAL;
+    *samples = c->accMax ? c->accSamples : 0u;
+    return CRT_OK;
+}
+
 int crt_render_frame_device(crt_ctx* c, uint32_t w, uint32_t h, void* d_rgba8, void* d_hit_inst, void* d_hit_prim,
                             void* d_hit_t, void* d_rgb_f32, crt_frame_stats* stats)
 {
@@ -976,7 +1131,7 @@ int crt_render_frame_device(crt_ctx* c, uint32_t w, uint32_t h, void* d_rgba8, v
     p.hit_prim = static_cast<uint32_t*>(d_hit_prim);
     p.hit_t = static_cast<float*>(d_hit_t);
     p.rgb_f32 = static_cast<float*>(d_rgb_f32);
-    rc = runRender(c, p, stats);
+    rc = runFrame(c, p, stats, kAccFrame);
     if (rc) return rc;
     if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CRT_OK;
@@ -1003,10 +1158,11 @@ int crt_render_frame(crt_ctx* c, uint32_t w, uint32_t h, uint8_t* rgba8, uint32_
     p.hit_t = host[3] ? static_cast<float*>(c->dFrame[3]) : nullptr;
     p.rgb_f32 = host[4] ? static_cast<float*>(c->dFrame[4]) : nullptr;
     crt_frame_stats local;
-    rc = runRender(c, p, stats ? stats : &local); // synchronous like the reference's renderFrame
+    rc = runFrame(c, p, stats ? stats : &local, kAccFrame); // synchronous like the reference's renderFrame
     if (rc) return rc;
+    const bool traced = !(p.acc_sum && p.spp == 0u); // a frame at the accumulation limit writes no hit outputs
     for (int i = 0; i < 5; i++)
-        if (host[i]) HIP_TRY(c, hipMemcpyAsync(host[i], c->dFrame[i], bytes[i], hipMemcpyDeviceToHost, c->stream));
+        if (host[i] && (traced || i == 0 || i == 4)) HIP_TRY(c, hipMemcpyAsync(host[i], c->dFrame[i], bytes[i], hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CRT_OK;
@@ -1030,7 +1186,7 @@ int crt_render_tiles_device(crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, u
     fillParams(c, w, h, rank, n_ranks, p);
     p.staging = 1;
     p.rgba8 = static_cast<uint32_t*>(d_staging);
-    rc = runRender(c, p, stats);
+    rc = runFrame(c, p, stats, kAccTiles);
     if (rc) return rc;
     if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CRT_OK;
@@ -1047,6 +1203,8 @@ int runBatch(crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_t n_ranks
     if (!d_out || n_ranks == 0 || rank >= n_ranks) return fail(c, CRT_EINVAL, "bad batch arguments (rank %u of %u)", rank, n_ranks);
     for (uint32_t f = 0; f < n_frames; f++)
         if (!d_out[f]) return fail(c, CRT_EINVAL, "output pointer of frame %u is NULL", f);
+    if (c->accMax != 0u && c->mode >= 200u)
+        return fail(c, CRT_EINVAL, "batch entry points do not accumulate (their frames have different cameras): turn accumulation off for mode %u", c->mode);
     const auto t0 = std::chrono::steady_clock::now();
     RenderParams p;
     fillParams(c, w, h, rank, n_ranks, p);

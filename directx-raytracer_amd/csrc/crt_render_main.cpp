@@ -36,6 +36,9 @@ static void usage()
                  "                       rotate YAW PITCH | forward D | right D | zoom A | pan DEG | tilt DEG | roll DEG | mode M\n"
                  "   [--mode-at FRAME:MODE]...  switch the shading mode from that frame on\n"
                  "   [--spp N] [--bounces N] [--seed N]   mode 200 (path tracing)\n"
+                 "   [--accumulate MAX]   mode 200: frames add their samples to running per-pixel sums (up to MAX samples) while the\n"
+                 "                        camera holds still and start over when it moves; each frame written is the running mean;\n"
+                 "                        with --ranks every rank accumulates its own tiles\n"
                  "   [--phong KS_PERMILLE:EXPONENT]       mode 100 specular term\n"
                  "   [--out prefix] [--png] [--count]      frames as prefix_N.ppm, or prefix_N.png with --png\n"
                  "   [--ranks N [--device-base D] [--id-file PATH]]   N processes / GPUs, RCCL gather per frame\n"
@@ -48,7 +51,7 @@ struct Args {
     std::string scene, out, pathFile, idFile;
     uint32_t mode = 0, w = 1920, h = 1080;
     int frames = 1, device = 0, deviceBase = 0, ranks = 0, rank = -1;
-    int spp = -1, bounces = -1, seed = -1, phongKs = -1, phongExp = -1;
+    int spp = -1, bounces = -1, seed = -1, phongKs = -1, phongExp = -1, accumulate = -1;
     float orbit = 0.f, pitch = 0.f, forward = 0.f, right = 0.f, zoom = 0.f;
     bool count = false, png = false, hostExchange = false, sameDevice = false;
     unsigned long long nonce = 0; // names the launch in the id file (set by the --ranks parent)
@@ -91,6 +94,7 @@ int runRank(const Args& a)
     if (a.seed >= 0) renderer.setOption("seed", a.seed);
     if (a.phongKs >= 0) renderer.setOption("phong_ks", a.phongKs);
     if (a.phongExp >= 0) renderer.setOption("phong_exponent", a.phongExp);
+    if (a.accumulate >= 0) renderer.setAccumulation(static_cast<uint32_t>(a.accumulate));
     if (a.ranks > 0 && a.hostExchange) renderer.joinRanksThroughHostMemory(static_cast<uint32_t>(a.rank), static_cast<uint32_t>(a.ranks), a.nonce);
     else if (a.ranks > 0) renderer.joinRanks(static_cast<uint32_t>(a.rank), static_cast<uint32_t>(a.ranks), a.idFile, a.nonce);
     const bool talk = a.ranks <= 0 || a.rank == 0;
@@ -123,6 +127,7 @@ int runRank(const Args& a)
         const double rays = static_cast<double>(st.rays_primary + st.rays_shadow);
         std::printf("frame %d: kernel %.3f ms, call %.3f ms, %.1f Mray/s", f, st.kernel_ms, st.total_ms, rays / st.kernel_ms * 1e-3);
         if (a.ranks > 0) std::printf(" (rank 0's tile share of %d ranks)", a.ranks);
+        if (a.accumulate > 0) std::printf(", %u samples accumulated", renderer.getAccumulatedSamples());
         if (a.count) std::printf(", nodes %llu, tris %llu, shadow rays %llu", (unsigned long long)st.nodes_visited,
                                  (unsigned long long)st.tris_tested, (unsigned long long)st.rays_shadow);
         std::printf("\n");
@@ -246,6 +251,7 @@ int main(int argc, char** argv)
         else if (s == "--spp") a.spp = std::atoi(next("--spp"));
         else if (s == "--bounces") a.bounces = std::atoi(next("--bounces"));
         else if (s == "--seed") a.seed = std::atoi(next("--seed"));
+        else if (s == "--accumulate") { if ((a.accumulate = std::atoi(next("--accumulate"))) < 0) { usage(); return 2; } }
         else if (s == "--phong") { if (std::sscanf(next("--phong"), "%d:%d", &a.phongKs, &a.phongExp) != 2) { usage(); return 2; } }
         else if (s == "--out") a.out = next("--out");
         else if (s == "--count") a.count = true;

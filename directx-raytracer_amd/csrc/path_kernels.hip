@@ -371,7 +371,17 @@ __device__ __forceinline__ void streamShade(const RenderParams& p, const float4*
 // the tile: 5120 regions instead of 130 560 at 3840x2160 (3.9 GB -> 152 MB at 4 spp), and a workgroup that finishes a cheap
 // tile goes on with the next one instead of leaving its wave slot to a fresh launch.  Every wavefront reaches the exit: the
 // counter only grows, and a value >= n_work ends the loop.
-template <bool COUNT, class L>
+//
+// ACC (progressive accumulation, crt_set_accumulation): the call's samples are acc_base .. acc_base + spp - 1 of a longer run.
+// The first pass starts from the stored per-pixel sum (acc_sum, indexed like the RGBA8 store) instead of zero, the last one
+// stores the new sum and divides by acc_total.  ACC = false is the kernel without the feature (same registers, spills, scratch).
+__device__ __forceinline__ size_t accIndex(const RenderParams& p, uint32_t tile_x, uint32_t tile_y, uint32_t lx, uint32_t ly, uint32_t px, uint32_t py)
+{
+    return p.staging ? static_cast<size_t>((tile_y * p.tiles_x + tile_x) / p.n_ranks) * (kTile * kTile) + ly * kTile + lx
+                     : static_cast<size_t>(py) * p.width + px;
+}
+
+template <bool COUNT, class L, bool ACC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_PATH_WAVES_PER_EU, 8))) void pathKernel(const RenderParams p)
 {
     extern __shared__ int s_stack[];
@@ -472,7 +482,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_PATH_WAV
                 uint32_t rng = 0;
                 if (active) {
                     const uint32_t pixId = py * p.width + px;
-                    rng = pcgHash(pixId ^ pcgHash((s0 + sl) + pcgHash(p.seed)));
+                    rng = pcgHash(pixId ^ pcgHash((ACC ? p.acc_base + s0 + sl : s0 + sl) + pcgHash(p.seed)));
                     const float jx = rngNext(rng), jy = rngNext(rng);
                     r = makeRay(f3(camPos[0], camPos[1], camPos[2]), rayDirJ(camRot, px, py, jx, jy, static_cast<float>(p.width), static_cast<float>(p.height)));
                     if (COUNT) cntClosest++;
@@ -481,7 +491,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_PATH_WAV
                     // radiance so far: a miss ends the path with throughput (1) x miss colour; a hit starts from nothing, throughput 1
                     q.done[id] = isHit ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(fmaf(1.0f, miss.x, 0.0f), fmaf(1.0f, miss.y, 0.0f), fmaf(1.0f, miss.z, 0.0f), 0.0f);
                     if (isHit) q.thr[id] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-                    if (s0 + sl == 0u && frame == 0u) { // the hit outputs report sample 0's camera ray
+                    if (s0 + sl == 0u && frame == 0u) { // the hit outputs report the call's first camera sample
                         const size_t pix = static_cast<size_t>(py) * p.width + px;
                         uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
                         if (isHit) {
@@ -528,6 +538,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_PATH_WAV
                 if (s0 != 0u) {
                     const float4 a = q.accum[pl];
                     acc = f3(a.x, a.y, a.z);
+                } else if (ACC && p.acc_base != 0u) { // samples of earlier calls
+                    const float4 a = static_cast<const float4*>(p.acc_sum)[accIndex(p, tile_x, tile_y, lx, ly, px, py)];
+                    acc = f3(a.x, a.y, a.z);
                 }
                 for (uint32_t sl = 0; sl < nS; sl++) {
                     const float4 Ls = q.done[sl * tilePixels + pl];
@@ -536,7 +549,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_PATH_WAV
                 if (!last) {
                     q.accum[pl] = make_float4(acc.x, acc.y, acc.z, 0.0f);
                 } else {
-                    const float inv = 1.0f / static_cast<float>(p.spp);
+                    if (ACC) static_cast<float4*>(p.acc_sum)[accIndex(p, tile_x, tile_y, lx, ly, px, py)] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+                    const float inv = 1.0f / static_cast<float>(ACC ? p.acc_total : p.spp);
                     const F3 col = f3(acc.x * inv, acc.y * inv, acc.z * inv);
                     const uint32_t packed = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xFF000000u;
                     const size_t pix = static_cast<size_t>(py) * p.width + px;
@@ -673,7 +687,7 @@ __device__ __forceinline__ void wfCount(const RenderParams& p, uint32_t cntNodes
 #define CRT_WF_TRACE_WAVES 7
 #endif
 
-template <bool COUNT, class L>
+template <bool COUNT, class L, bool ACC> // ACC: the call's samples start at acc_base (see pathKernel)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WF_CAMERA_WAVES, 8))) void pathCameraKernel(const RenderParams p)
 {
     extern __shared__ int s_stack[];
@@ -718,7 +732,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WF_CAMER
             uint32_t rng = 0;
             if (active) {
                 const uint32_t pixId = py * p.width + px;
-                rng = pcgHash(pixId ^ pcgHash((p.wf_s0 + sl) + pcgHash(p.seed)));
+                rng = pcgHash(pixId ^ pcgHash((ACC ? p.acc_base + p.wf_s0 + sl : p.wf_s0 + sl) + pcgHash(p.seed)));
                 const float jx = rngNext(rng), jy = rngNext(rng);
                 r = makeRay(f3(camPos[0], camPos[1], camPos[2]), rayDirJ(camRot, px, py, jx, jy, static_cast<float>(p.width), static_cast<float>(p.height)));
                 if (COUNT) cntClosest++;
@@ -727,7 +741,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WF_CAMER
                 // radiance so far: a miss ends the path with throughput (1) x miss colour; a hit starts from nothing, throughput 1
                 q.done[id] = isHit ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(fmaf(1.0f, miss.x, 0.0f), fmaf(1.0f, miss.y, 0.0f), fmaf(1.0f, miss.z, 0.0f), 0.0f);
                 if (isHit) q.thr[id] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-                if (p.wf_s0 + sl == 0u && w.frame == 0u) { // the hit outputs report sample 0's camera ray
+                if (p.wf_s0 + sl == 0u && w.frame == 0u) { // the hit outputs report the call's first camera sample
                     const size_t pix = static_cast<size_t>(py) * p.width + px;
                     uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
                     if (isHit) {
@@ -787,7 +801,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WF_TRACE
 }
 
 // one wavefront per work item of the pass: this pass's samples join the running sums in sample order; after the last pass the
-// average is quantised and stored
+// average is quantised and stored (ACC: the first pass starts from the stored sums, the last one stores them; see pathKernel)
+template <bool ACC>
 __global__ __launch_bounds__(64) void pathResolveKernel(const RenderParams p)
 {
     const uint32_t lane = threadIdx.x & 63u, local = blockIdx.x;
@@ -797,9 +812,14 @@ __global__ __launch_bounds__(64) void pathResolveKernel(const RenderParams p)
     if ((px >= p.width) | (py >= p.height)) return;
     const uint32_t nS = min(p.path_samples, p.spp - p.wf_s0);
     const bool last = p.wf_s0 + nS >= p.spp;
+    const uint32_t mx = w.tile_x >> 1, my = w.tile_y >> 1; // 16x16 tile of the frame, pixel inside it
+    const uint32_t lx = (w.tile_x & 1u) * 8u + (lane & 7u), ly = (w.tile_y & 1u) * 8u + (lane >> 3);
     F3 acc = f3(0.0f, 0.0f, 0.0f);
     if (p.wf_s0 != 0u) {
         const float4 a = static_cast<const float4*>(p.wf_accum)[local * 64u + lane];
+        acc = f3(a.x, a.y, a.z);
+    } else if (ACC && p.acc_base != 0u) { // samples of earlier calls
+        const float4 a = static_cast<const float4*>(p.acc_sum)[accIndex(p, mx, my, lx, ly, px, py)];
         acc = f3(a.x, a.y, a.z);
     }
     for (uint32_t sl = 0; sl < nS; sl++) {
@@ -810,19 +830,48 @@ __global__ __launch_bounds__(64) void pathResolveKernel(const RenderParams p)
         static_cast<float4*>(p.wf_accum)[local * 64u + lane] = make_float4(acc.x, acc.y, acc.z, 0.0f);
         return;
     }
-    const float inv = 1.0f / static_cast<float>(p.spp);
+    if (ACC) static_cast<float4*>(p.acc_sum)[accIndex(p, mx, my, lx, ly, px, py)] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+    const float inv = 1.0f / static_cast<float>(ACC ? p.acc_total : p.spp);
     const F3 col = f3(acc.x * inv, acc.y * inv, acc.z * inv);
     const uint32_t packed = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xFF000000u;
     uint32_t* outRgba8 = w.frame ? p.batch_rgba8[w.frame - 1u] : p.rgba8;
     const size_t pix = static_cast<size_t>(py) * p.width + px;
     if (p.staging) {
-        const uint32_t mx = w.tile_x >> 1, my = w.tile_y >> 1; // 16x16 tile of the frame, pixel inside it
-        const uint32_t lx = (w.tile_x & 1u) * 8u + (lane & 7u), ly = (w.tile_y & 1u) * 8u + (lane >> 3);
         outRgba8[static_cast<size_t>((my * p.tiles_x + mx) / p.n_ranks) * (kTile * kTile) + ly * kTile + lx] = packed;
     } else {
         outRgba8[pix] = packed;
     }
     if (p.rgb_f32 && w.frame == 0u) {
+        p.rgb_f32[3 * pix + 0] = col.x;
+        p.rgb_f32[3 * pix + 1] = col.y;
+        p.rgb_f32[3 * pix + 2] = col.z;
+    }
+}
+
+// accumulation at its limit: no sample is traced, the stored sums are resolved again with the same multiply and quantisation as
+// the last pass of a frame.  One thread per output index of the RGBA8 store: pixel of a whole frame, or staging index of a tile
+// share (slot j of this rank = macro tile j * n_ranks + rank; indices outside the frame are left untouched, as a frame leaves them).
+__global__ __launch_bounds__(256) void pathAccumResolveKernel(const RenderParams p)
+{
+    const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    uint32_t px, py;
+    if (p.staging) {
+        if (i >= static_cast<size_t>(p.n_local_tiles) * (kTile * kTile)) return;
+        const uint32_t k = static_cast<uint32_t>(i / (kTile * kTile)) * p.n_ranks + p.rank, within = static_cast<uint32_t>(i % (kTile * kTile));
+        px = (k % p.tiles_x) * kTile + within % kTile;
+        py = (k / p.tiles_x) * kTile + within / kTile;
+        if ((px >= p.width) | (py >= p.height)) return;
+    } else {
+        if (i >= static_cast<size_t>(p.width) * p.height) return;
+        px = static_cast<uint32_t>(i % p.width);
+        py = static_cast<uint32_t>(i / p.width);
+    }
+    const float4 a = static_cast<const float4*>(p.acc_sum)[i];
+    const float inv = 1.0f / static_cast<float>(p.acc_total);
+    const F3 col = f3(a.x * inv, a.y * inv, a.z * inv);
+    p.rgba8[i] = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xFF000000u;
+    if (p.rgb_f32 && !p.staging) {
+        const size_t pix = static_cast<size_t>(py) * p.width + px;
         p.rgb_f32[3 * pix + 0] = col.x;
         p.rgb_f32[3 * pix + 1] = col.y;
         p.rgb_f32[3 * pix + 2] = col.z;
@@ -852,7 +901,7 @@ uint32_t pathGridSize(const RenderParams& p)
         hipDeviceProp_t prop;
         const size_t lds = static_cast<size_t>(kStackEntries) * 64u * sizeof(int); // worst case LDS: the grid must fit any stack_entries
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, reinterpret_cast<const void*>(&pathKernel<false, LayLegacy>), 64, lds) != hipSuccess || perCu <= 0) {
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, reinterpret_cast<const void*>(&pathKernel<false, LayLegacy, false>), 64, lds) != hipSuccess || perCu <= 0) {
             perCu = 16;
             cus = 256;
         } else {
@@ -925,7 +974,7 @@ uint32_t residentGroups(const void* kernel, int& cache, uint32_t stackEntries)
 uint32_t wfResident(int which, uint32_t stackEntries) // 0 camera, 1 shade, 2 trace; the LDS part of the stacks decides with the registers
 {
     static int cache[3][kStackEntries + 1] = {};
-    const void* k[3] = { reinterpret_cast<const void*>(&pathCameraKernel<false, LayLegacy>), reinterpret_cast<const void*>(&pathShadeKernel<false, LayLegacy>),
+    const void* k[3] = { reinterpret_cast<const void*>(&pathCameraKernel<false, LayLegacy, false>), reinterpret_cast<const void*>(&pathShadeKernel<false, LayLegacy>),
                          reinterpret_cast<const void*>(&pathTraceKernel<false, LayLegacy>) };
     const uint32_t e = stackEntries > kStackEntries ? kStackEntries : stackEntries;
     return residentGroups(k[which], cache[which][e], e);
@@ -949,8 +998,13 @@ int launchPathWavefront(const RenderParams& p0, bool counting, ihipStream_t* str
             if (e != hipSuccess) return static_cast<int>(e);
             const uint32_t maxWaves = p.wf_items * perItem / 64u; // no stage has more entries than the pass has paths
             const uint32_t camGrid = p.wf_items < wfResident(0, p.stack_entries) ? p.wf_items : wfResident(0, p.stack_entries);
-            if (counting) hipLaunchKernelGGL((pathCameraKernel<true, LayLegacy>), dim3(camGrid), block, lds, stream, p);
-            else hipLaunchKernelGGL((pathCameraKernel<false, LayLegacy>), dim3(camGrid), block, lds, stream, p);
+            if (p.acc_sum) {
+                if (counting) hipLaunchKernelGGL((pathCameraKernel<true, LayLegacy, true>), dim3(camGrid), block, lds, stream, p);
+                else hipLaunchKernelGGL((pathCameraKernel<false, LayLegacy, true>), dim3(camGrid), block, lds, stream, p);
+            } else {
+                if (counting) hipLaunchKernelGGL((pathCameraKernel<true, LayLegacy, false>), dim3(camGrid), block, lds, stream, p);
+                else hipLaunchKernelGGL((pathCameraKernel<false, LayLegacy, false>), dim3(camGrid), block, lds, stream, p);
+            }
             for (uint32_t b = 0; b <= p.max_bounces; b++) {
                 p.wf_queue = 2u * b;
                 const uint32_t sg = maxWaves < wfResident(1, p.stack_entries) ? maxWaves : wfResident(1, p.stack_entries);
@@ -962,7 +1016,8 @@ int launchPathWavefront(const RenderParams& p0, bool counting, ihipStream_t* str
                 if (counting) hipLaunchKernelGGL((pathTraceKernel<true, LayLegacy>), dim3(tg), block, lds, stream, p);
                 else hipLaunchKernelGGL((pathTraceKernel<false, LayLegacy>), dim3(tg), block, lds, stream, p);
             }
-            hipLaunchKernelGGL(pathResolveKernel, dim3(p.wf_items), block, 0, stream, p);
+            if (p.acc_sum) hipLaunchKernelGGL(pathResolveKernel<true>, dim3(p.wf_items), block, 0, stream, p);
+            else hipLaunchKernelGGL(pathResolveKernel<false>, dim3(p.wf_items), block, 0, stream, p);
             e = hipGetLastError();
             if (e != hipSuccess) return static_cast<int>(e);
         }
@@ -979,8 +1034,13 @@ int launchPath(const RenderParams& p, bool counting, ihipStream_t* stream)
     const dim3 grid(pathGridSize(p)), block(64);
     const size_t lds = static_cast<size_t>(p.stack_entries) * 64u * sizeof(int);
 #define CRT_LAUNCH(LAY)                                                                                \
-    if (counting) hipLaunchKernelGGL((pathKernel<true, LAY>), grid, block, lds, stream, p);            \
-    else hipLaunchKernelGGL((pathKernel<false, LAY>), grid, block, lds, stream, p);
+    if (p.acc_sum) {                                                                                   \
+        if (counting) hipLaunchKernelGGL((pathKernel<true, LAY, true>), grid, block, lds, stream, p);     \
+        else hipLaunchKernelGGL((pathKernel<false, LAY, true>), grid, block, lds, stream, p);             \
+    } else {                                                                                           \
+        if (counting) hipLaunchKernelGGL((pathKernel<true, LAY, false>), grid, block, lds, stream, p);        \
+        else hipLaunchKernelGGL((pathKernel<false, LAY, false>), grid, block, lds, stream, p);                \
+    }
 #if CRT_PACKED_LAYOUTS
     if (p.layout == 8u) { CRT_LAUNCH(LayPacked<8>) }
     else if (p.layout == 4u) { CRT_LAUNCH(LayPacked<4>) }
@@ -988,6 +1048,15 @@ int launchPath(const RenderParams& p, bool counting, ihipStream_t* stream)
 #endif
     { CRT_LAUNCH(LayLegacy) }
 #undef CRT_LAUNCH
+    return static_cast<int>(hipGetLastError());
+}
+
+int launchPathAccumResolve(const RenderParams& p, ihipStream_t* stream)
+{
+    if (!p.acc_sum || p.acc_total == 0u) return static_cast<int>(hipErrorInvalidValue);
+    const size_t n = p.staging ? static_cast<size_t>(p.n_local_tiles) * (kTile * kTile) : static_cast<size_t>(p.width) * p.height;
+    if (n == 0u) return static_cast<int>(hipSuccess);
+    hipLaunchKernelGGL(pathAccumResolveKernel, dim3(static_cast<uint32_t>((n + 255u) / 256u)), dim3(256), 0, stream, p);
     return static_cast<int>(hipGetLastError());
 }
 

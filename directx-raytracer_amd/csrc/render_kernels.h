@@ -89,6 +89,10 @@ struct RenderParams {
     uint32_t wf_queue;            // queue a shade / trace launch consumes (it fills wf_queue + 1)
     uint32_t wf_s0;               // first sample of this pass
     unsigned long long* timeline; // counting variant only, nullable: per workgroup {start, end} of s_memrealtime (100 MHz) + XCC id
+    // mode 200, progressive accumulation (crt_set_accumulation); acc_sum null = off
+    void* acc_sum;                // float4 per output index of the RGBA8 store (pixel of a frame, staging index of a tile share): running sums
+    uint32_t acc_base;            // global index of the call's first sample = samples already in the sums
+    uint32_t acc_total;           // acc_base + spp: what the sums are divided by
 };
 
 // Enqueue the fused rayGen -> traverse -> shade -> store kernel. counting selects the instrumented variant.
@@ -97,6 +101,8 @@ int launchRender(const RenderParams& p, bool counting, ihipStream_t* stream);
 uint32_t renderUnitCount(const RenderParams& p);
 // mode 200 (path_kernels.hip): the wavefront-private path pipeline; launchRender forwards to launchPath
 int launchPath(const RenderParams& p, bool counting, ihipStream_t* stream);
+// mode 200 with accumulation at its limit: the stored sums resolved to RGBA8 (and f32 rgb) without tracing
+int launchPathAccumResolve(const RenderParams& p, ihipStream_t* stream);
 // mode 200 scratch sizing
 size_t pathRegionBytes(uint32_t tile, uint32_t samples_per_pass);
 uint32_t pathWorkgroupCount(const RenderParams& p);

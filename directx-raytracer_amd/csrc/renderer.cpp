@@ -103,6 +103,19 @@ void Renderer::setOption(const char* name, int value)
     check(crt_set_option(ctx, name, value), name);
 }
 
+void Renderer::setAccumulation(uint32_t maxSamples)
+{
+    if (!ctx) throw std::runtime_error("setAccumulation before prepareForRendering");
+    check(crt_set_accumulation(ctx, maxSamples), "crt_set_accumulation");
+}
+
+uint32_t Renderer::getAccumulatedSamples() const
+{
+    uint32_t n = 0;
+    if (ctx) check(crt_accumulated_samples(ctx, &n), "crt_accumulated_samples");
+    return n;
+}
+
 // The id file holds {nonce, communicator id}.  The nonce names the launch (crt_render --ranks draws a fresh one per run): a file
 // left behind by an earlier run, or by another launch that was given the same path, carries a different nonce and is waited out
 // like a file that is not there yet instead of being taken for this run's id (ranks joining a dead communicator block for good).

@@ -44,6 +44,9 @@ public:
     const crt_frame_stats& getLastFrameStats() const { return stats; }
     void setCounting(bool on);
     void setOption(const char* name, int value); // crt_set_option: "spp", "max_bounces", "seed", "phong_ks", "phong_exponent", ...
+    // crt_set_accumulation: mode-200 frames add their samples to running sums while the camera holds still (0 = off)
+    void setAccumulation(uint32_t maxSamples);
+    uint32_t getAccumulatedSamples() const; // crt_accumulated_samples
 
     // N GPUs, one process each (no reference counterpart): join the RCCL communicator of an N-rank run.  Rank 0 creates the
     // 128-byte id and publishes it as `idFile` (written under a temporary name, then renamed); the other ranks wait for the

@@ -285,6 +285,33 @@ void crt_free(void* p);
 void* crt_host_alloc(size_t bytes);
 void crt_host_free(void* p);
 
+/* ---- progressive accumulation (no reference counterpart: the reference's idle tick renders every frame from scratch,
+ * R/DXRTApp.cpp:109-120).  While the view holds still, mode-200 frames add their samples to per-pixel sums, and the image
+ * converges instead of showing the same noise on every tick.
+ * - Only mode 200 accumulates.  With accumulation on, a mode-200 call traces samples n .. n+spp-1, n = the samples already in
+ *   the sums, adds them to per-pixel fp32 sums in sample order and outputs the mean of all n+spp samples (sum * (1.0f / total),
+ *   to RGBA8 and, where asked for, f32 rgb).  K calls of S spp therefore equal, bit for bit, one call of K*S spp; spp may
+ *   change between calls (4 + 1 + 3 spp = the 8-spp frame).  Other modes ignore the setting: their frames are those rendered
+ *   with it off, and they leave the sums untouched.
+ * - Limit: a call that would pass max_samples traces only the remainder.  Once the sums hold max_samples, a call traces
+ *   nothing: it writes the stored mean again (RGBA8 / f32 rgb; no hit outputs) and its crt_frame_stats report zero rays.
+ * - Automatic reset: a mode-200 call starts over at sample 0 when any of these differ from what the sums were made with:
+ *   camera pose (compared bitwise: setting the same pose again keeps accumulating), shading mode, miss colour, max_bounces,
+ *   seed, the uploaded scene, the textures, width x height, and the entry point kind with its (rank, n_ranks).  spp,
+ *   counting and the tuning options (path_pipeline, path_tile, path_ranges, path_pass_paths, ...) do not reset: results never
+ *   depend on them.  Mode 200 -> 3 -> 200 with nothing else changed continues the sums.
+ * - Hit outputs report the call's first camera sample (global index n; sample 0 after a reset, as without accumulation).
+ * - crt_render_frame, crt_render_frame_device and crt_render_tiles_device accumulate, and so does crt_render_frame_distributed
+ *   (each rank sums its own tile slots; the gather moves resolved RGBA8 only).  The batch entry points return CRT_EINVAL in
+ *   mode 200 with accumulation on and render nothing: their frames have different cameras.
+ * - Consecutive accumulating calls run in issue order on the GPU even when issued on different streams (crt_set_stream).
+ * The sums are one float4 per output pixel (staging slot pixel for tile shares), owned by the context: allocated by the first
+ * accumulating frame (33 MB at 1920x1080, 133 MB at 3840x2160), freed by crt_set_accumulation(ctx, 0) or crt_destroy. */
+int crt_set_accumulation(crt_ctx* ctx, uint32_t max_samples); /* 0 = off (default); 1..2^24 = on, up to that many samples per pixel
+                                                                  (2^24: every count is exact in fp32); always starts over */
+int crt_reset_accumulation(crt_ctx* ctx);                      /* drop the sums; the next frame starts at sample 0 */
+int crt_accumulated_samples(const crt_ctx* ctx, uint32_t* samples); /* samples per pixel in the current sums (0 when off or reset) */
+
 /* ---------------------------------------------------------------------------------------------------
  * Scene layer: stands in for CRTScene / CRTSceneParser / CRTCamera (kept API surface, host only, no GPU)
  * ------------------------------------------------------------------------------------------------- */
