@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "crt_scene_camera_move_forward", "crt_scene_camera_move_right", "crt_scene_camera_pan", "crt_scene_camera_tilt",
     "crt_scene_camera_roll", "crt_scene_camera_pan_around_target", "crt_upload_scene_from", "crt_set_camera_from",
     "crt_set_accumulation", "crt_reset_accumulation", "crt_accumulated_samples",
+    "crt_trace_rays_device", "crt_occluded_rays_device", "crt_trace_rays", "crt_occluded_rays",
 ]
 
 
@@ -194,6 +195,10 @@ def lib():
         "crt_set_accumulation": (C.c_int, [vp, u32]),
         "crt_reset_accumulation": (C.c_int, [vp]),
         "crt_accumulated_samples": (C.c_int, [vp, C.POINTER(u32)]),
+        "crt_trace_rays_device": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp]),
+        "crt_occluded_rays_device": (C.c_int, [vp, u32, vp, vp, vp]),
+        "crt_trace_rays": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp]),
+        "crt_occluded_rays": (C.c_int, [vp, u32, vp, vp, vp]),
     }
     assert set(sig) == set(ABI_SYMBOLS)
     for name, (res, args) in sig.items():
@@ -208,6 +213,24 @@ def _f32(a, n=None):
     a = np.ascontiguousarray(a, dtype=np.float32)
     assert n is None or a.size == n
     return a
+
+
+def make_rays(origins, directions, tmin=0.0, tmax=np.inf):
+    """(N, 8) float32 ray records {ox, oy, oz, tmin, dx, dy, dz, tmax} for Renderer.trace_rays / occluded.  origins and
+    directions are (N, 3) or (3,) (broadcast against each other); tmin / tmax are scalars or length-N arrays."""
+    o = np.asarray(origins, dtype=np.float32)
+    d = np.asarray(directions, dtype=np.float32)
+    if o.shape[-1:] != (3,) or d.shape[-1:] != (3,) or o.ndim > 2 or d.ndim > 2:
+        raise ValueError("origins and directions must be (N, 3) or (3,)")
+    n = max(o.reshape(-1, 3).shape[0], d.reshape(-1, 3).shape[0])
+    o = np.broadcast_to(o.reshape(-1, 3), (n, 3))
+    d = np.broadcast_to(d.reshape(-1, 3), (n, 3))
+    out = np.empty((n, 8), dtype=np.float32)
+    out[:, 0:3] = o
+    out[:, 3] = np.broadcast_to(np.asarray(tmin, dtype=np.float32), (n,))
+    out[:, 4:7] = d
+    out[:, 7] = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,))
+    return out
 
 
 def tile_count(w, h):
@@ -600,6 +623,49 @@ class Renderer:
         n = C.c_uint32()
         self._ok(lib().crt_accumulated_samples(self.h, C.byref(n)), "crt_accumulated_samples")
         return n.value
+
+    # ---- batched ray queries (include/crt_hip.h): records of 8 floats {ox, oy, oz, tmin, dx, dy, dz, tmax}, see make_rays
+    def trace_rays(self, rays, want=("t", "uv", "inst", "prim")):
+        """closest hit of every ray (host buffers, synchronous).  Returns a dict of the wanted arrays -- t (N,) float32, uv (N, 2)
+        float32, inst / prim (N,) uint32 (MISS on a miss, t = the ray's tmax) -- plus 'stats'."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = len(r)
+        out = {}
+        if "t" in want:
+            out["t"] = np.zeros(n, dtype=np.float32)
+        if "uv" in want:
+            out["uv"] = np.zeros((n, 2), dtype=np.float32)
+        if "inst" in want:
+            out["inst"] = np.zeros(n, dtype=np.uint32)
+        if "prim" in want:
+            out["prim"] = np.zeros(n, dtype=np.uint32)
+        st = FrameStats()
+
+        def p(k):
+            return out[k].ctypes.data if k in out else None
+        self._ok(lib().crt_trace_rays(self.h, n, r.ctypes.data, p("t"), p("uv"), p("inst"), p("prim"), C.byref(st)), "crt_trace_rays")
+        out["stats"] = st.as_dict()
+        return out
+
+    def occluded(self, rays):
+        """occlusion of every ray on (tmin, tmax): bool array (host buffers, synchronous)"""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        out = np.zeros(len(r), dtype=np.bool_)
+        self._ok(lib().crt_occluded_rays(self.h, len(r), r.ctypes.data, out.ctypes.data, None), "crt_occluded_rays")
+        return out
+
+    def trace_rays_device(self, n, d_rays, d_t=None, d_uv=None, d_inst=None, d_prim=None, stats=False):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_trace_rays_device(self.h, int(n), d_rays, d_t, d_uv, d_inst, d_prim, C.byref(st) if stats else None),
+                 "crt_trace_rays_device")
+        return st.as_dict() if stats else None
+
+    def occluded_device(self, n, d_rays, d_occluded, stats=False):
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_occluded_rays_device(self.h, int(n), d_rays, d_occluded, C.byref(st) if stats else None),
+                 "crt_occluded_rays_device")
+        return st.as_dict() if stats else None
 
     def read_counters(self):
         buf = np.zeros(32, dtype=np.uint64)

@@ -190,6 +190,25 @@ struct crt_ctx {
     hipEvent_t evAccum = nullptr;
     hipStream_t accumStream = nullptr;
     bool accumPending = false;
+
+    // batched ray queries (crt_trace_rays* / crt_occluded_rays*): per arena the launch's cursor, counters and the stack spill
+    // arena of the persistent query kernel.  Arenas belong to queries alone (never to a frame) and, like the path arenas, to the
+    // stream that last used one: queries on one stream run one after the other and share an arena, queries on different streams
+    // (up to kRing in flight) get arenas of their own.
+    struct RayArena {
+        unsigned char* mem = nullptr;
+        size_t bytes = 0;
+        hipStream_t stream = nullptr;
+        bool used = false;
+        hipEvent_t lastUse = nullptr;
+        bool pending = false;
+        uint32_t serial = 0;
+    } rayArena[kRing];
+    uint32_t raySerial = 0;
+    uint32_t rayResident[2] = {};        // resident workgroups of the closest-hit / occlusion query kernel on this device ...
+    uint32_t rayResidentEntries[2] = {}; // ... for this many LDS stack entries
+    void* dRayStage = nullptr; // the host entry points' rays and outputs, grown on demand
+    size_t rayStageBytes = 0;
 };
 
 namespace {
@@ -700,6 +719,11 @@ void crt_destroy(crt_ctx* c)
     if (c->dTimeline) (void)hipFree(c->dTimeline);
     if (c->dAccum) (void)hipFree(c->dAccum);
     if (c->evAccum) (void)hipEventDestroy(c->evAccum);
+    for (int i = 0; i < crt_ctx::kRing; i++) {
+        if (c->rayArena[i].mem) (void)hipFree(c->rayArena[i].mem);
+        if (c->rayArena[i].lastUse) (void)hipEventDestroy(c->rayArena[i].lastUse);
+    }
+    if (c->dRayStage) (void)hipFree(c->dRayStage);
     if (c->evStart) (void)hipEventDestroy(c->evStart);
     if (c->evStop) (void)hipEventDestroy(c->evStop);
     if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
@@ -1115,6 +1139,223 @@ int crt_accumulated_samples(const crt_ctx* c, uint32_t* samples)
     if (!c || !samples) return CRT_EINVAL;
     *samples = c->accMax ? c->accSamples : 0u;
     return CRT_OK;
+}
+
+namespace {
+
+// Batched ray queries.  Outputs of a closest-hit query: t, uv, inst, prim (any may be NULL); of an occlusion query: occluded.
+struct RayOutputs {
+    void* t = nullptr;
+    void* uv = nullptr;
+    void* inst = nullptr;
+    void* prim = nullptr;
+    void* occluded = nullptr;
+};
+
+// what every query entry point checks before anything is launched
+int checkQuery(crt_ctx* c, const char* what)
+{
+    if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
+    if (!c->haveScene) return fail(c, CRT_ESTATE, "%s: no scene uploaded: call crt_upload_scene first", what);
+    if (c->bvh.width != 0u) return fail(c, CRT_EINVAL, "%s: ray queries traverse the legacy 4-wide tree only (option bvh_width 0)", what);
+    return CRT_OK;
+}
+
+int checkDeviceOutputs(crt_ctx* c, const char* what, const void* rays, const RayOutputs& o, bool occlusion)
+{
+    if (!rays) return fail(c, CRT_EINVAL, "%s: ray buffer is NULL", what);
+    if (reinterpret_cast<uintptr_t>(rays) & 15u) return fail(c, CRT_EINVAL, "%s: ray buffer %p is not 16-byte aligned", what, rays);
+    if (occlusion) {
+        if (!o.occluded) return fail(c, CRT_EINVAL, "%s: occlusion output is NULL", what);
+        return CRT_OK;
+    }
+    if (!o.t && !o.uv && !o.inst && !o.prim) return fail(c, CRT_EINVAL, "%s: every output is NULL", what);
+    if ((reinterpret_cast<uintptr_t>(o.t) | reinterpret_cast<uintptr_t>(o.inst) | reinterpret_cast<uintptr_t>(o.prim)) & 3u)
+        return fail(c, CRT_EINVAL, "%s: t / inst / prim outputs must be 4-byte aligned", what);
+    if (reinterpret_cast<uintptr_t>(o.uv) & 7u) return fail(c, CRT_EINVAL, "%s: uv output must be 8-byte aligned", what);
+    return CRT_OK;
+}
+
+// Enqueue one query of n > 0 rays (device pointers) on the context's stream; with stats, time it, synchronise and fill them.
+int runRayQuery(crt_ctx* c, uint32_t n, const void* d_rays, const RayOutputs& o, bool occlusion, crt_frame_stats* stats)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    crt::RayQueryParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.nodes = c->dNodes;
+    q.tris = c->dTris;
+    q.n_nodes = c->bvh.nNodes4;
+    q.rays = d_rays;
+    q.n = n;
+    q.t = static_cast<float*>(o.t);
+    q.uv = static_cast<float*>(o.uv);
+    q.inst = static_cast<uint32_t*>(o.inst);
+    q.prim = static_cast<uint32_t*>(o.prim);
+    q.occluded = static_cast<unsigned char*>(o.occluded);
+    q.stack_entries = c->tuneStackEntries ? c->tuneStackEntries : 16u; // as fillParams
+    const uint32_t deepest = 3u * c->bvh.depth4 + 1u;                 // as runRender
+    q.spill_stride = deepest > q.stack_entries ? deepest - q.stack_entries : 1u;
+    q.inner_min = occlusion ? c->tuneInnerMinAny : c->tuneInnerMin;
+    const int kind = occlusion ? 1 : 0;
+    if (c->rayResident[kind] == 0u || c->rayResidentEntries[kind] != q.stack_entries) {
+        c->rayResident[kind] = crt::rayQueryResident(occlusion, q.stack_entries);
+        c->rayResidentEntries[kind] = q.stack_entries;
+        if (c->rayResident[kind] == 0u) return fail(c, CRT_EHIP, "ray query kernel: occupancy query failed");
+    }
+    uint32_t grid = 0;
+    crt::rayQueryLayout(n, c->rayResident[kind], q.chunk, grid);
+
+    // the arena this stream used last; else an unused one; else the least recently used one of another stream, once the
+    // query that used it last is done
+    crt_ctx::RayArena* arena = nullptr;
+    for (auto& a : c->rayArena)
+        if (a.used && a.stream == c->stream) arena = &a;
+    if (!arena) {
+        for (auto& a : c->rayArena)
+            if (!arena || (!a.used && arena->used) || (a.used == arena->used && a.serial < arena->serial)) arena = &a;
+        if (arena->pending && hipEventQuery(arena->lastUse) != hipSuccess) HIP_TRY(c, hipStreamWaitEvent(c->stream, arena->lastUse, 0));
+        arena->stream = c->stream;
+        arena->used = true;
+    }
+    constexpr size_t kHead = 256; // cursor at 0, counters at 64
+    const size_t need = kHead + static_cast<size_t>(grid) * 64u * q.spill_stride * sizeof(int);
+    if (arena->bytes < need) {
+        HIP_TRY(c, hipDeviceSynchronize()); // (the arena may still be in use by a query on its stream)
+        if (arena->mem) (void)hipFree(arena->mem);
+        arena->mem = nullptr;
+        arena->bytes = 0;
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&arena->mem), need));
+        arena->bytes = need;
+    }
+    if (!arena->lastUse) HIP_TRY(c, hipEventCreateWithFlags(&arena->lastUse, hipEventDisableTiming));
+    arena->serial = ++c->raySerial;
+    q.cursor = reinterpret_cast<uint32_t*>(arena->mem);
+    q.counters = reinterpret_cast<unsigned long long*>(arena->mem + 64);
+    q.spill = reinterpret_cast<int*>(arena->mem + kHead);
+    HIP_TRY(c, hipMemsetAsync(arena->mem, 0, kHead, c->stream));
+
+    const bool counting = c->counting;
+    if (stats) HIP_TRY(c, hipEventRecord(c->evStart, c->stream));
+    const int rc = crt::launchRayQuery(q, occlusion, counting, grid, c->stream);
+    if (rc != 0) return fail(c, CRT_EHIP, "ray query kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+    if (stats) HIP_TRY(c, hipEventRecord(c->evStop, c->stream));
+    HIP_TRY(c, hipEventRecord(arena->lastUse, c->stream));
+    arena->pending = true;
+    if (stats) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->evStart, c->evStop));
+        std::memset(stats, 0, sizeof(*stats));
+        stats->kernel_ms = ms;
+        if (occlusion) stats->rays_shadow = n;
+        else stats->rays_primary = n;
+        if (counting) {
+            unsigned long long host[2] = { 0, 0 };
+            HIP_TRY(c, hipMemcpy(host, q.counters, sizeof(host), hipMemcpyDeviceToHost));
+            stats->nodes_visited = host[0];
+            stats->tris_tested = host[1];
+        }
+    }
+    return CRT_OK;
+}
+
+void zeroStats(crt_frame_stats* stats, std::chrono::steady_clock::time_point t0)
+{
+    if (!stats) return;
+    std::memset(stats, 0, sizeof(*stats));
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int queryDevice(crt_ctx* c, const char* what, uint32_t n, const void* d_rays, const RayOutputs& o, bool occlusion, crt_frame_stats* stats)
+{
+    int rc = checkQuery(c, what);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n == 0u) { // nothing to look at, nothing launched
+        zeroStats(stats, t0);
+        return CRT_OK;
+    }
+    if ((rc = checkDeviceOutputs(c, what, d_rays, o, occlusion)) != CRT_OK) return rc;
+    if ((rc = runRayQuery(c, n, d_rays, o, occlusion, stats)) != CRT_OK) return rc;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+// host buffers: staged through the context's device buffer {rays | t | uv | inst | prim | occluded}; synchronous
+int queryHost(crt_ctx* c, const char* what, uint32_t n, const float* rays, const RayOutputs& host, bool occlusion, crt_frame_stats* stats)
+{
+    int rc = checkQuery(c, what);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n == 0u) {
+        zeroStats(stats, t0);
+        return CRT_OK;
+    }
+    if (!rays) return fail(c, CRT_EINVAL, "%s: ray buffer is NULL", what);
+    if (occlusion ? !host.occluded : (!host.t && !host.uv && !host.inst && !host.prim)) return fail(c, CRT_EINVAL, "%s: every output is NULL", what);
+    const size_t nn = n;
+    auto up = [](size_t b) { return (b + 255u) & ~static_cast<size_t>(255u); };
+    const size_t bytes[5] = { occlusion ? 0u : (host.t ? nn * 4u : 0u), occlusion ? 0u : (host.uv ? nn * 8u : 0u),
+                              occlusion ? 0u : (host.inst ? nn * 4u : 0u), occlusion ? 0u : (host.prim ? nn * 4u : 0u),
+                              occlusion ? nn : 0u };
+    size_t off[5], total = up(nn * 32u);
+    for (int i = 0; i < 5; i++) {
+        off[i] = total;
+        total += up(bytes[i]);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->rayStageBytes < total) {
+        HIP_TRY(c, hipDeviceSynchronize());
+        if (c->dRayStage) (void)hipFree(c->dRayStage);
+        c->dRayStage = nullptr;
+        c->rayStageBytes = 0;
+        HIP_TRY(c, hipMalloc(&c->dRayStage, total));
+        c->rayStageBytes = total;
+    }
+    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
+    RayOutputs d;
+    void* const hostPtr[5] = { host.t, host.uv, host.inst, host.prim, host.occluded };
+    void* devPtr[5];
+    for (int i = 0; i < 5; i++) devPtr[i] = bytes[i] ? base + off[i] : nullptr;
+    d.t = devPtr[0]; d.uv = devPtr[1]; d.inst = devPtr[2]; d.prim = devPtr[3]; d.occluded = devPtr[4];
+    HIP_TRY(c, hipMemcpyAsync(base, rays, nn * 32u, hipMemcpyHostToDevice, c->stream));
+    crt_frame_stats local;
+    if ((rc = runRayQuery(c, n, base, d, occlusion, stats ? stats : &local)) != CRT_OK) return rc;
+    for (int i = 0; i < 5; i++)
+        if (bytes[i]) HIP_TRY(c, hipMemcpyAsync(hostPtr[i], devPtr[i], bytes[i], hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+} // namespace
+
+int crt_trace_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_t, void* d_uv, void* d_inst, void* d_prim, crt_frame_stats* stats)
+{
+    RayOutputs o;
+    o.t = d_t; o.uv = d_uv; o.inst = d_inst; o.prim = d_prim;
+    return queryDevice(c, "crt_trace_rays_device", n, d_rays, o, false, stats);
+}
+
+int crt_occluded_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_occluded, crt_frame_stats* stats)
+{
+    RayOutputs o;
+    o.occluded = d_occluded;
+    return queryDevice(c, "crt_occluded_rays_device", n, d_rays, o, true, stats);
+}
+
+int crt_trace_rays(crt_ctx* c, uint32_t n, const float* rays, float* t, float* uv, uint32_t* inst, uint32_t* prim, crt_frame_stats* stats)
+{
+    RayOutputs o;
+    o.t = t; o.uv = uv; o.inst = inst; o.prim = prim;
+    return queryHost(c, "crt_trace_rays", n, rays, o, false, stats);
+}
+
+int crt_occluded_rays(crt_ctx* c, uint32_t n, const float* rays, uint8_t* occluded, crt_frame_stats* stats)
+{
+    RayOutputs o;
+    o.occluded = occluded;
+    return queryHost(c, "crt_occluded_rays", n, rays, o, true, stats);
 }
 
 int crt_render_frame_device(crt_ctx* c, uint32_t w, uint32_t h, void* d_rgba8, void* d_hit_inst, void* d_hit_prim,

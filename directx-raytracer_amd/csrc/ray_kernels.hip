@@ -1,0 +1,222 @@
+// HIP kernel for gfx950 (MI355X): batched ray queries on caller-supplied rays (crt_trace_rays* / crt_occluded_rays*) -- the
+// DXR TraceRay of any ray, which the reference only issues from its own rayGen shader (R/HLSL/ray_tracing_shaders.hlsl:21-69).
+//
+// A ray record is 8 floats {ox, oy, oz, tmin, dx, dy, dz, tmax} (32 B, two dwordx4 loads).  User rays are arbitrary: one may be
+// a node step long, its neighbour a grazing ray hundreds of steps long, so a wavefront that traced a fixed chunk of 64 would run
+// as long as its slowest ray.  Here the grid is persistent (what the chip holds at once) and every lane holds one ray: a lane
+// whose traversal has ended retires its ray (writes the requested outputs) and takes the next record as soon as CRT_REFILL_MIN
+// lanes are idle -- the streamClosest idea of path_kernels.hip applied to a user buffer.  Records are handed out from a global
+// cursor in chunks of `chunk` rays per atomic.  Every ray is still traced by one lane in its own fixed order with the per-lane
+// tmin / tmax of its record, so results and fetch counts are those of the oracle's traversal of the same ray, whatever the
+// order of the buffer, the refill timing or the wave scheduling.
+//
+// Arithmetic contract: identical, operation for operation, to oracle/crt_oracle.c (compiled with -ffp-contract=off).
+#include "traversal.hip.h"
+
+namespace crt {
+namespace {
+
+#ifndef CRT_REFILL_MIN
+#define CRT_REFILL_MIN 16
+#endif
+
+__device__ __forceinline__ uint32_t lanesBelow(unsigned long long m)
+{
+    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
+}
+
+// The box-cull bound of a ray whose current bound (tmax, then the best hit) is b.  Slab distances and the Moeller-Trumbore t
+// round differently, so boxes are culled against b widened by 2^-18 of |b| (traversal.hip.h kCullPad): b * (1 + 2^-18) for
+// b >= 0, as the frames do, and b * (1 - 2^-18) for b < 0, where the frames' factor would narrow the bound instead and reject
+// boxes holding triangles strictly inside (tmin, tmax).  Frames never see a negative bound (tmin = 0.001).
+constexpr float kCullPadNeg = 0.999996185302734375f; // 1 - 2^-18
+__device__ __forceinline__ float cullBound(float b) { return b * (b >= 0.0f ? kCullPad : kCullPadNeg); }
+
+__device__ __forceinline__ uint32_t waveTotal(uint32_t v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// A wavefront's window [next, end) on the ray buffer.  The first chunk is the wavefront's own (chunk number blockIdx.x, no
+// atomic); later ones come from the cursor, which counts the chunks behind the grid's own.  Everything here is wave-uniform.
+struct RayTap {
+    uint32_t next, end;
+    bool dry; // the cursor has passed the end of the buffer
+    __device__ __forceinline__ void begin(uint32_t n, uint32_t chunk)
+    {
+        const uint64_t first = static_cast<uint64_t>(blockIdx.x) * chunk;
+        next = static_cast<uint32_t>(first < n ? first : n);
+        end = static_cast<uint32_t>(first + chunk < n ? first + chunk : n);
+        dry = false;
+    }
+    __device__ __forceinline__ bool more() const { return (next < end) | !dry; }
+    // records for the lanes of `mask` (call in wave-uniform control flow); a lane's record is valid if `valid`
+    __device__ __forceinline__ uint32_t take(uint32_t* cursor, uint32_t n, uint32_t chunk, unsigned long long mask, bool& valid)
+    {
+        const uint32_t want = static_cast<uint32_t>(__popcll(mask)), avail = end - next;
+        uint32_t nb = 0u, nbEnd = 0u;
+        if ((want > avail) & !dry) {
+            uint32_t k = 0u;
+            if ((threadIdx.x & 63u) == 0u) k = atomicAdd(cursor, 1u);
+            const uint64_t start = (static_cast<uint64_t>(gridDim.x) + __builtin_amdgcn_readfirstlane(k)) * chunk;
+            if (start >= n) dry = true;
+            else {
+                nb = static_cast<uint32_t>(start);
+                nbEnd = static_cast<uint32_t>(start + chunk < n ? start + chunk : n);
+            }
+        }
+        const uint32_t pre = lanesBelow(mask);
+        const uint32_t idx = pre < avail ? next + pre : nb + (pre - avail);
+        valid = (pre < avail) | (idx < nbEnd);
+        if (want > avail) {
+            next = nbEnd ? min(nb + (want - avail), nbEnd) : end;
+            end = nbEnd ? nbEnd : end;
+        } else {
+            next += want;
+        }
+        return idx;
+    }
+};
+
+// OCCL = false: closest hit (t, uv, inst, prim, each optional); true: any hit in (tmin, tmax), one byte per ray.  Output
+// pointers are kernel arguments, so their null tests are scalar branches.  The generic octant loop (OCT = 8): refilled lanes
+// mix direction octants.
+// Register budget: the closest-hit form is given 6 wavefronts per SIMD (76 VGPRs, nothing spilled); at the frames' 7 it spilled
+// 4 VGPRs inside the loop and ran 9 / 8 / 15 % slower on the camera / AO / random legs of tools/ray_query_bench.py.
+constexpr int kRayWavesClosest = 6;
+// Resident wavefronts per SIMD the persistent grid is sized for: at most 7.  The occlusion form fits 8 (60 VGPRs), but with
+// 8 its random leg took 0.56 ms against 0.46 with 7 (incoherent rays: more concurrent traversals, more cache misses).
+constexpr int kRayMaxWavesPerSimd = 7;
+
+template <bool COUNT, bool OCCL, class L>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCCL ? L::kWavesPerEu : kRayWavesClosest, 8))) void rayQueryKernel(const RayQueryParams q)
+{
+    extern __shared__ int s_stack[]; // stack_entries x 64 dwords
+    const uint32_t lane = threadIdx.x & 63u;
+    const float4* nodes = reinterpret_cast<const float4*>(q.nodes);
+    const float4* tris = reinterpret_cast<const float4*>(q.tris);
+    const float4* rays = reinterpret_cast<const float4*>(q.rays);
+    Stack stack;
+    stack.lds = s_stack + lane;
+    stack.spill = q.spill + (static_cast<size_t>(blockIdx.x) * 64u + lane) * q.spill_stride;
+    stack.cap = static_cast<int>(q.stack_entries);
+    stack.sp = 0;
+    const int innerMin = static_cast<int>(q.inner_min);
+
+    Ray r = makeRay(f3(0.0f, 0.0f, 0.0f), f3(0.0f, 0.0f, 1.0f));
+    float tmin = 0.0f, tmax = 0.0f, tcull = 0.0f;
+    Hit h;
+    h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.gid = 0;
+    bool occluded = false;
+    int cur = L::kDone;
+    bool have = false; // this lane holds a record (being traced, or finished and not yet retired)
+    uint32_t my = 0;   // its index in the buffer
+    uint32_t iters = 0, cntNodes = 0, cntTris = 0;
+    RayTap tap;
+    tap.begin(q.n, q.chunk);
+    const unsigned long long all = __ballot(true);
+    for (;;) {
+        const bool idle = cur == L::kDone;
+        const unsigned long long idleMask = __ballot(idle);
+        if (idleMask == all || (tap.more() && static_cast<uint32_t>(__popcll(idleMask)) >= static_cast<uint32_t>(CRT_REFILL_MIN))) {
+            // retire the finished rays ...
+            if (idle & have) {
+                if (OCCL) {
+                    q.occluded[my] = occluded ? 1u : 0u;
+                } else {
+                    const bool hit = h.t < tmax;
+                    if (q.t) q.t[my] = h.t; // a miss keeps tmax
+                    if (q.uv) reinterpret_cast<float2*>(q.uv)[my] = make_float2(h.u, h.v);
+                    if (q.inst || q.prim) {
+                        uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
+                        if (hit) { // (an empty scene has no triangle record to read)
+                            const uint32_t* T = reinterpret_cast<const uint32_t*>(L::triPtr(tris, h.tri));
+                            inst = T[3]; // v0.w = mesh ordinal
+                            prim = T[7]; // e1.w = triangle of the mesh
+                        }
+                        if (q.inst) q.inst[my] = inst;
+                        if (q.prim) q.prim[my] = prim;
+                    }
+                }
+            }
+            // ... and hand the next records to the idle lanes
+            bool valid = false;
+            const uint32_t idx = tap.take(q.cursor, q.n, q.chunk, idleMask, valid);
+            if (idle) {
+                have = valid;
+                if (valid) {
+                    my = idx;
+                    const float4 a = rays[2u * static_cast<size_t>(idx)], b = rays[2u * static_cast<size_t>(idx) + 1u];
+                    r = makeRay(f3(a.x, a.y, a.z), f3(b.x, b.y, b.z));
+                    tmin = a.w;
+                    tmax = b.w;
+                    h.t = tmax; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.gid = 0;
+                    occluded = false;
+                    tcull = cullBound(tmax);
+                    stack.sp = 0;
+                    // a record with a NaN or an empty interval is not traced: it reports a miss
+                    const bool ok = (a.x == a.x) & (a.y == a.y) & (a.z == a.z) & (b.x == b.x) & (b.y == b.y) & (b.z == b.z) & (tmin < tmax);
+                    cur = (ok & (q.n_nodes != 0u)) ? L::kRoot : L::kDone;
+                }
+            }
+            if (__ballot(have) == 0ull && !tap.more()) break; // buffer exhausted and every ray retired
+        }
+        if (OCCL) anyIteration<COUNT, L, 8>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris);
+        else {
+            closestIteration<COUNT, L, 8>(nodes, tris, r, tmin, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris);
+            tcull = cullBound(h.t); // (closestIteration sets t * kCullPad on an accepted hit: the same value for t >= 0)
+        }
+    }
+    if (COUNT) {
+        const uint32_t a = waveTotal(cntNodes), c = waveTotal(cntTris);
+        if (lane == 0) {
+            atomicAdd(&q.counters[0], static_cast<unsigned long long>(a));
+            atomicAdd(&q.counters[1], static_cast<unsigned long long>(c));
+        }
+    }
+}
+
+} // namespace
+
+// resident workgroups of a persistent query kernel: what the occupancy calculator allows per CU for this LDS stack x CUs of
+// the current device (the closest-hit and the occlusion kernel hold different numbers of wavefronts).  The caller caches it.
+uint32_t rayQueryResident(bool occlusion, uint32_t stack_entries)
+{
+    int dev = 0, cus = 0, perCu = 0;
+    const size_t lds = static_cast<size_t>(stack_entries) * 64u * sizeof(int);
+    const void* k = occlusion ? reinterpret_cast<const void*>(&rayQueryKernel<false, true, LayLegacy>)
+                              : reinterpret_cast<const void*>(&rayQueryKernel<false, false, LayLegacy>);
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k, 64, lds) != hipSuccess || perCu <= 0 || cus <= 0)
+        return 0u;
+    const int most = 4 * kRayMaxWavesPerSimd; // one wavefront per workgroup, four SIMDs per CU
+    return static_cast<uint32_t>(perCu > most ? most : perCu) * static_cast<uint32_t>(cus);
+}
+
+void rayQueryLayout(uint32_t n, uint32_t resident, uint32_t& chunk, uint32_t& grid)
+{
+    // about four reservations per wavefront, of 64 to 1024 records: one atomic on one address costs the whole device a few ns
+    uint64_t c = (static_cast<uint64_t>(n) / (4u * static_cast<uint64_t>(resident)) + 63u) & ~static_cast<uint64_t>(63u);
+    chunk = static_cast<uint32_t>(c < 64u ? 64u : (c > 1024u ? 1024u : c));
+    const uint64_t chunks = (static_cast<uint64_t>(n) + chunk - 1u) / chunk;
+    grid = static_cast<uint32_t>(chunks < resident ? chunks : resident);
+}
+
+int launchRayQuery(const RayQueryParams& q, bool occlusion, bool counting, uint32_t grid, ihipStream_t* stream)
+{
+    if (q.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
+    const size_t lds = static_cast<size_t>(q.stack_entries) * 64u * sizeof(int);
+    const dim3 g(grid), block(64);
+    if (occlusion) {
+        if (counting) hipLaunchKernelGGL((rayQueryKernel<true, true, LayLegacy>), g, block, lds, stream, q);
+        else hipLaunchKernelGGL((rayQueryKernel<false, true, LayLegacy>), g, block, lds, stream, q);
+    } else {
+        if (counting) hipLaunchKernelGGL((rayQueryKernel<true, false, LayLegacy>), g, block, lds, stream, q);
+        else hipLaunchKernelGGL((rayQueryKernel<false, false, LayLegacy>), g, block, lds, stream, q);
+    }
+    return static_cast<int>(hipGetLastError());
+}
+
+} // namespace crt

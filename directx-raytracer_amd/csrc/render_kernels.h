@@ -119,6 +119,33 @@ int launchSortUnits(const uint32_t* cost, uint32_t* order, uint32_t n, bool xcdA
 int launchUntile(const uint32_t* gathered, uint32_t* frame, uint32_t width, uint32_t height, uint32_t n_ranks,
                  uint32_t rank_stride, uint32_t first_slot, ihipStream_t* stream);
 
+// batched ray queries (ray_kernels.hip; crt_trace_rays* / crt_occluded_rays*): n caller-supplied records of 8 floats
+// {ox, oy, oz, tmin, dx, dy, dz, tmax}, closest hit or occlusion, over the legacy 4-wide tree
+struct RayQueryParams {
+    const void* nodes;            // as RenderParams::nodes / tris (layout 0 only)
+    const void* tris;
+    uint32_t n_nodes;
+    const void* rays;             // n x 32 bytes, 16-byte aligned
+    uint32_t n;
+    float* t;                     // closest hit, each nullable: t, {u, v} (8-byte aligned), mesh ordinal, triangle of the mesh
+    float* uv;
+    uint32_t* inst;
+    uint32_t* prim;
+    unsigned char* occluded;      // occlusion: one byte per ray
+    uint32_t* cursor;             // chunks handed out behind the grid's own (zeroed on the stream before the launch)
+    unsigned long long* counters; // counting variant: [0] nodes fetched, [1] triangles fetched
+    int* spill;                   // stack spill arena: grid x 64 lanes x spill_stride ints
+    uint32_t spill_stride;
+    uint32_t stack_entries;       // per-lane stack entries kept in LDS
+    uint32_t inner_min;           // tune_inner_min (closest hit) or tune_inner_min_any (occlusion)
+    uint32_t chunk;               // records per cursor reservation (rayQueryLayout)
+};
+// workgroups of the closest-hit / occlusion query kernel the current device holds at once (0: unknown)
+uint32_t rayQueryResident(bool occlusion, uint32_t stack_entries);
+// records per reservation and grid (persistent: at most `resident` workgroups) of a query of n rays
+void rayQueryLayout(uint32_t n, uint32_t resident, uint32_t& chunk, uint32_t& grid);
+int launchRayQuery(const RayQueryParams& q, bool occlusion, bool counting, uint32_t grid, ihipStream_t* stream);
+
 // device-side texture record (crt_texture with the pixel pointer replaced by an offset into the texel pool)
 struct TextureRec {
     uint32_t type;

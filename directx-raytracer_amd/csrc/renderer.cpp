@@ -116,6 +116,25 @@ uint32_t Renderer::getAccumulatedSamples() const
     return n;
 }
 
+void Renderer::traceRays(const float* rays, size_t n, RayHit* out)
+{
+    if (!ctx) throw std::runtime_error("traceRays before prepareForRendering");
+    if (n > UINT32_MAX) throw std::runtime_error("traceRays: more than 2^32 - 1 rays");
+    if (n == 0) return;
+    const uint32_t m = static_cast<uint32_t>(n);
+    std::vector<float> t(n), uv(2 * n);
+    std::vector<uint32_t> inst(n), prim(n);
+    check(crt_trace_rays(ctx, m, rays, t.data(), uv.data(), inst.data(), prim.data(), nullptr), "crt_trace_rays");
+    for (size_t i = 0; i < n; i++) out[i] = RayHit{ t[i], uv[2 * i], uv[2 * i + 1], inst[i], prim[i] };
+}
+
+void Renderer::occluded(const float* rays, size_t n, uint8_t* out)
+{
+    if (!ctx) throw std::runtime_error("occluded before prepareForRendering");
+    if (n > UINT32_MAX) throw std::runtime_error("occluded: more than 2^32 - 1 rays");
+    check(crt_occluded_rays(ctx, static_cast<uint32_t>(n), rays, out, nullptr), "crt_occluded_rays");
+}
+
 // The id file holds {nonce, communicator id}.  The nonce names the launch (crt_render --ranks draws a fresh one per run): a file
 // left behind by an earlier run, or by another launch that was given the same path, carries a different nonce and is waited out
 // like a file that is not there yet instead of being taken for this run's id (ranks joining a dead communicator block for good).

@@ -48,6 +48,15 @@ public:
     void setAccumulation(uint32_t maxSamples);
     uint32_t getAccumulatedSamples() const; // crt_accumulated_samples
 
+    // batched ray queries on the uploaded scene (crt_trace_rays / crt_occluded_rays, synchronous): n records of 8 floats
+    // {ox, oy, oz, tmin, dx, dy, dz, tmax}.  A miss reports inst = prim = CRT_MISS, t = the ray's tmax, u = v = 0.
+    struct RayHit {
+        float t, u, v;
+        uint32_t inst, prim;
+    };
+    void traceRays(const float* rays, size_t n, RayHit* out);
+    void occluded(const float* rays, size_t n, uint8_t* out); // 1 = some triangle lies in (tmin, tmax)
+
     // N GPUs, one process each (no reference counterpart): join the RCCL communicator of an N-rank run.  Rank 0 creates the
     // 128-byte id and publishes it as `idFile` (written under a temporary name, then renamed); the other ranks wait for the
     // file.  Afterwards renderFrame() renders this rank's tiles, gathers and de-interleaves: every rank holds the frame.

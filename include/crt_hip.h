@@ -312,6 +312,48 @@ int crt_set_accumulation(crt_ctx* ctx, uint32_t max_samples); /* 0 = off (defaul
 int crt_reset_accumulation(crt_ctx* ctx);                      /* drop the sums; the next frame starts at sample 0 */
 int crt_accumulated_samples(const crt_ctx* ctx, uint32_t* samples); /* samples per pixel in the current sums (0 when off or reset) */
 
+/* ---- batched ray queries (DXR offers TraceRay on any ray; the reference only traces its own camera rays,
+ * R/HLSL/ray_tracing_shaders.hlsl:21-69).  The caller hands over rays and asks what they hit: picking, visibility / ambient
+ * occlusion rays, sensor casts.
+ * - Ray record: 8 floats (32 B) {ox, oy, oz, tmin, dx, dy, dz, tmax}; the buffer holds n records, contiguous.  The direction
+ *   need not be normalised: t is in units of |d|.  A hit is a triangle with tmin < t < tmax, by the frames' Moeller-Trumbore
+ *   test (two sided, no culling).  tmin may be 0 or negative, tmax may be +inf.  A record containing a NaN, or with
+ *   !(tmin < tmax), is not traced and reports a miss / not occluded; a zero direction is a miss.
+ * - Closest hit (crt_trace_rays*), per ray, each output optional: t (float), uv (2 floats: u = weight of v1, v = weight of
+ *   v2, the frames' barycentrics), inst (uint32 mesh ordinal in upload order), prim (uint32 triangle of that mesh).  Equal t
+ *   goes to the lower global triangle id, as in the frames.  Miss: inst = prim = CRT_MISS, t = the ray's tmax, u = v = 0.
+ * - Occlusion (crt_occluded_rays*): one byte per ray (the layout of torch.bool / np.bool_), 1 if any triangle lies in
+ *   (tmin, tmax): the any-hit traversal with early exit.
+ * - Results do not depend on the order of the rays in the buffer, on scheduling or on the tuning options inner_min /
+ *   inner_min_any.  The box cull is the frames' (boxes are tested against the best t so far widened by 2^-18 of its
+ *   magnitude), so for a ray whose tmax and hit are >= 0 the results and fetch counts are bit for bit the CPU oracle's
+ *   traversal of that ray.  For a negative bound the widening keeps its direction (the oracle's and the frames' factor would
+ *   narrow it): a triangle strictly inside (tmin, tmax) is found, and ties at t < 0 go to the lower global id, as at t > 0.
+ * - Limit (boundary rays): the slab test and the triangle test round differently, so a triangle whose hit lies where the ray
+ *   runs within rounding of a box face can be rejected with its box.  This concerns a ray lying in an axis-aligned face of
+ *   the boxes (an axis-aligned direction through the plane of axis-aligned geometry, or through a shared edge of such quads)
+ *   and a ray starting on a surface whose own hit is at t ~ tmin.  Such a ray may then report a miss, or a farther hit,
+ *   although a triangle lies in (tmin, tmax); the result is still the oracle's traversal of the same tree, but it can differ
+ *   between the host SAH tree and the gpu_build tree.  Every other ray gives the same result over either tree.
+ * - Layout: queries traverse the default 64-byte 4-wide tree.  With the experimental packed layouts (option bvh_width 4 / 8,
+ *   diagnostic builds only) every query returns CRT_EINVAL.
+ * - A query needs an uploaded scene (CRT_ESTATE otherwise).  It reads the tree, the triangles and the options inner_min /
+ *   inner_min_any, nothing else: camera, mode, accumulation sums, launch-order state and frame outputs are untouched, and a frame
+ *   rendered after any number of queries equals the frame rendered without them (accumulating mode-200 runs included).
+ * - n = 0 returns CRT_OK and launches nothing (the buffers are not looked at).  Offsets are 64-bit: n up to 2^32 - 1.
+ * - stats (may be NULL): kernel_ms = the query kernel (HIP events), total_ms = wall time of the call, rays_primary = n for a
+ *   closest-hit query, rays_shadow = n for an occlusion query; nodes_visited / tris_tested with crt_set_counting(ctx, 1), counted
+ *   as the frames count them.
+ * *_device: device pointers.  The ray buffer must be 16-byte aligned, t / inst / prim 4-byte, uv 8-byte aligned (CRT_EINVAL
+ * otherwise).  Any closest-hit output may be NULL, not all four.  Asynchronous on the context's stream (crt_set_stream) unless
+ * stats != NULL.  Host variants: synchronous, staged through a context-owned device buffer that grows on demand. */
+int crt_trace_rays_device(crt_ctx* ctx, uint32_t n, const void* d_rays, void* d_t, void* d_uv, void* d_inst, void* d_prim,
+                          crt_frame_stats* stats);
+int crt_occluded_rays_device(crt_ctx* ctx, uint32_t n, const void* d_rays, void* d_occluded, crt_frame_stats* stats);
+int crt_trace_rays(crt_ctx* ctx, uint32_t n, const float* rays, float* t, float* uv, uint32_t* inst, uint32_t* prim,
+                   crt_frame_stats* stats);
+int crt_occluded_rays(crt_ctx* ctx, uint32_t n, const float* rays, uint8_t* occluded, crt_frame_stats* stats);
+
 /* ---------------------------------------------------------------------------------------------------
  * Scene layer: stands in for CRTScene / CRTSceneParser / CRTCamera (kept API surface, host only, no GPU)
  * ------------------------------------------------------------------------------------------------- */
