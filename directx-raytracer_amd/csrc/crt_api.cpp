@@ -184,7 +184,7 @@ struct crt_ctx {
     uint32_t accMax = 0;            // samples per pixel the sums may reach; 0 = off
     uint32_t accSamples = 0;        // samples per pixel in the sums
     AccKey accKey{};                // what the sums belong to (meaningful while accSamples > 0)
-    void* dAccum = nullptr;         // float4 per output index of the RGBA8 store (pixel, or staging index of a tile share)
+    void* dAccum = nullptr;         // 4 doubles per output index of the RGBA8 store (pixel, or staging index of a tile share)
     size_t accumBytes = 0;
     // consecutive accumulating frames depend on each other through the sums: the next one waits (on the GPU) for the last one
     hipEvent_t evAccum = nullptr;
@@ -575,7 +575,7 @@ int beginAccum(crt_ctx* c, RenderParams& p, uint32_t kind)
     }
     const size_t outputs = kind == kAccTiles ? static_cast<size_t>(crt_tile_slots(p.width, p.height, p.n_ranks)) * crt::kTile * crt::kTile
                                              : static_cast<size_t>(p.width) * p.height;
-    const size_t need = outputs * 4u * sizeof(float);
+    const size_t need = outputs * 4u * sizeof(double); // float64 sums {x, y}, {z, 0} (path_kernels.hip loadSum)
     if (c->accumBytes < need) { // (a larger frame: the key has changed, nothing in the old sums is kept)
         HIP_TRY(c, hipSetDevice(c->device));
         HIP_TRY(c, hipDeviceSynchronize()); // frames of other streams may still use the old buffer

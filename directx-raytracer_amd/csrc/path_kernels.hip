@@ -21,6 +21,8 @@ namespace {
 // chunks, no atomics, no cross-wavefront traffic, no kernel boundary, and the queues are streamed with coalesced dwordx4
 // accesses (record i of a queue = one float4 per plane at index i).  Per path the arithmetic -- RNG stream, radiance
 // updates, their order -- is the oracle's, so frames stay bit-exact; the sample average runs in sample order at the end.
+// Per-pixel sample sums are float64 in sample order (loadSum / storeSum): a float32 running sum drifts by several RGBA8 steps long before
+// the 2^24 samples accumulation allows, a float64 one stays within 1 ulp of float.
 // Samples beyond `path_samples` are further passes of the same wavefront over the same scratch.
 constexpr uint32_t kShadePlanes = 3, kTracePlanes = 2;
 constexpr uint32_t kPathCounterStride = 16; // dwords between the work counters of two ranges (one 64-byte line each)
@@ -30,7 +32,7 @@ struct PathScratch {
     float4* trace;   // kTracePlanes x B: {o, rng} {d, id | bounce << 16}
     float4* done;    // B, by path id (sample-in-pass * tile pixels + pixel-in-tile): the path's radiance so far, final when it ends
     float4* thr;     // B, by path id: its throughput (only the shade stage changes it; the queues carry the ray, not this)
-    float4* accum;   // 256: running sum over the samples of earlier passes
+    double2* accum;  // 2 x 256: running sum over the samples of earlier passes (loadSum layout)
     uint32_t B;      // plane stride of the queues
     uint32_t* take;  // GLOBAL queues only: cursor of the queue a stream consumes ...
     uint32_t* put;   // ... and length of the queue it fills
@@ -51,6 +53,29 @@ __device__ __forceinline__ uint32_t waveReserve(uint32_t* counter, uint32_t n)
     uint32_t base = 0;
     if ((threadIdx.x & 63u) == 0u) base = atomicAdd(counter, n);
     return __builtin_amdgcn_readfirstlane(base);
+}
+
+// Sample sums of one pixel: float64 {x, y}, {z, 0} (two 16-byte words per pixel, index i -> words 2i, 2i + 1), one sample
+// added at a time in sample order, resolved once as (float)(sum / total).  oracle_render sums and divides the same way.
+struct D3 { double x, y, z; };
+__device__ __forceinline__ D3 loadSum(const void* sums, size_t i)
+{
+    const double2 a = static_cast<const double2*>(sums)[2u * i], b = static_cast<const double2*>(sums)[2u * i + 1u];
+    return D3{ a.x, a.y, b.x };
+}
+__device__ __forceinline__ void storeSum(void* sums, size_t i, const D3& a)
+{
+    static_cast<double2*>(sums)[2u * i] = make_double2(a.x, a.y);
+    static_cast<double2*>(sums)[2u * i + 1u] = make_double2(a.z, 0.0);
+}
+__device__ __forceinline__ D3 addSample(const D3& a, const float4& s)
+{
+    return D3{ a.x + static_cast<double>(s.x), a.y + static_cast<double>(s.y), a.z + static_cast<double>(s.z) };
+}
+__device__ __forceinline__ F3 sumMean(const D3& a, uint32_t total)
+{
+    const double n = static_cast<double>(total);
+    return f3(static_cast<float>(a.x / n), static_cast<float>(a.y / n), static_cast<float>(a.z / n));
 }
 
 __device__ __forceinline__ uint32_t lanePrefix(unsigned long long m)
@@ -374,7 +399,7 @@ __device__ __forceinline__ void streamShade(const RenderParams& p, const float4*
 //
 // ACC (progressive accumulation, crt_set_accumulation): the call's samples are acc_base .. acc_base + spp - 1 of a longer run.
 // The first pass starts from the stored per-pixel sum (acc_sum, indexed like the RGBA8 store) instead of zero, the last one
-// stores the new sum and divides by acc_total.  ACC = false is the kernel without the feature (same registers, spills, scratch).
+// stores the new sum and divides by acc_total (float64 sums, loadSum layout).  ACC = false is the kernel without the feature (same registers, spills, scratch).
 __device__ __forceinline__ size_t accIndex(const RenderParams& p, uint32_t tile_x, uint32_t tile_y, uint32_t lx, uint32_t ly, uint32_t px, uint32_t py)
 {
     return p.staging ? static_cast<size_t>((tile_y * p.tiles_x + tile_x) / p.n_ranks) * (kTile * kTile) + ly * kTile + lx
@@ -407,7 +432,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_PATH_WAV
         q.trace = q.shade + static_cast<size_t>(kShadePlanes) * q.B;
         q.done = q.trace + static_cast<size_t>(kTracePlanes) * q.B;
         q.thr = q.done + q.B;
-        q.accum = q.thr + q.B;
+        q.accum = reinterpret_cast<double2*>(q.thr + q.B);
         q.take = q.put = nullptr;
         q.chunk = 0u;
     }
@@ -534,24 +559,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_PATH_WAV
             const uint32_t px = tile_x * kTile + lx, py = tile_y * kTile + ly;
             if ((px < p.width) & (py < p.height)) {
                 const uint32_t pl = sb * 64u + lane;
-                F3 acc = f3(0.0f, 0.0f, 0.0f);
-                if (s0 != 0u) {
-                    const float4 a = q.accum[pl];
-                    acc = f3(a.x, a.y, a.z);
-                } else if (ACC && p.acc_base != 0u) { // samples of earlier calls
-                    const float4 a = static_cast<const float4*>(p.acc_sum)[accIndex(p, tile_x, tile_y, lx, ly, px, py)];
-                    acc = f3(a.x, a.y, a.z);
-                }
-                for (uint32_t sl = 0; sl < nS; sl++) {
-                    const float4 Ls = q.done[sl * tilePixels + pl];
-                    acc = f3(acc.x + Ls.x, acc.y + Ls.y, acc.z + Ls.z);
-                }
+                D3 acc{ 0.0, 0.0, 0.0 };
+                if (s0 != 0u) acc = loadSum(q.accum, pl);
+                else if (ACC && p.acc_base != 0u) acc = loadSum(p.acc_sum, accIndex(p, tile_x, tile_y, lx, ly, px, py)); // samples of earlier calls
+                for (uint32_t sl = 0; sl < nS; sl++) acc = addSample(acc, q.done[sl * tilePixels + pl]);
                 if (!last) {
-                    q.accum[pl] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+                    storeSum(q.accum, pl, acc);
                 } else {
-                    if (ACC) static_cast<float4*>(p.acc_sum)[accIndex(p, tile_x, tile_y, lx, ly, px, py)] = make_float4(acc.x, acc.y, acc.z, 0.0f);
-                    const float inv = 1.0f / static_cast<float>(ACC ? p.acc_total : p.spp);
-                    const F3 col = f3(acc.x * inv, acc.y * inv, acc.z * inv);
+                    if (ACC) storeSum(p.acc_sum, accIndex(p, tile_x, tile_y, lx, ly, px, py), acc);
+                    const F3 col = sumMean(acc, ACC ? p.acc_total : p.spp);
                     const uint32_t packed = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xFF000000u;
                     const size_t pix = static_cast<size_t>(py) * p.width + px;
                     if (p.staging) outRgba8[static_cast<size_t>((tile_y * p.tiles_x + tile_x) / p.n_ranks) * (kTile * kTile) + ly * kTile + lx] = packed;
@@ -646,7 +662,7 @@ __device__ __forceinline__ PathScratch wfScratch(const RenderParams& p)
     q.trace = static_cast<float4*>(p.wf_trace_q);
     q.done = static_cast<float4*>(p.wf_done);
     q.thr = static_cast<float4*>(p.wf_thr);
-    q.accum = static_cast<float4*>(p.wf_accum);
+    q.accum = static_cast<double2*>(p.wf_accum);
     q.take = nullptr;
     q.put = nullptr;
     return q;
@@ -814,25 +830,17 @@ __global__ __launch_bounds__(64) void pathResolveKernel(const RenderParams p)
     const bool last = p.wf_s0 + nS >= p.spp;
     const uint32_t mx = w.tile_x >> 1, my = w.tile_y >> 1; // 16x16 tile of the frame, pixel inside it
     const uint32_t lx = (w.tile_x & 1u) * 8u + (lane & 7u), ly = (w.tile_y & 1u) * 8u + (lane >> 3);
-    F3 acc = f3(0.0f, 0.0f, 0.0f);
-    if (p.wf_s0 != 0u) {
-        const float4 a = static_cast<const float4*>(p.wf_accum)[local * 64u + lane];
-        acc = f3(a.x, a.y, a.z);
-    } else if (ACC && p.acc_base != 0u) { // samples of earlier calls
-        const float4 a = static_cast<const float4*>(p.acc_sum)[accIndex(p, mx, my, lx, ly, px, py)];
-        acc = f3(a.x, a.y, a.z);
-    }
-    for (uint32_t sl = 0; sl < nS; sl++) {
-        const float4 Ls = static_cast<const float4*>(p.wf_done)[local * (64u * p.path_samples) + sl * 64u + lane];
-        acc = f3(acc.x + Ls.x, acc.y + Ls.y, acc.z + Ls.z);
-    }
+    D3 acc{ 0.0, 0.0, 0.0 };
+    if (p.wf_s0 != 0u) acc = loadSum(p.wf_accum, local * 64u + lane);
+    else if (ACC && p.acc_base != 0u) acc = loadSum(p.acc_sum, accIndex(p, mx, my, lx, ly, px, py)); // samples of earlier calls
+    for (uint32_t sl = 0; sl < nS; sl++)
+        acc = addSample(acc, static_cast<const float4*>(p.wf_done)[local * (64u * p.path_samples) + sl * 64u + lane]);
     if (!last) {
-        static_cast<float4*>(p.wf_accum)[local * 64u + lane] = make_float4(acc.x, acc.y, acc.z, 0.0f);
+        storeSum(p.wf_accum, local * 64u + lane, acc);
         return;
     }
-    if (ACC) static_cast<float4*>(p.acc_sum)[accIndex(p, mx, my, lx, ly, px, py)] = make_float4(acc.x, acc.y, acc.z, 0.0f);
-    const float inv = 1.0f / static_cast<float>(ACC ? p.acc_total : p.spp);
-    const F3 col = f3(acc.x * inv, acc.y * inv, acc.z * inv);
+    if (ACC) storeSum(p.acc_sum, accIndex(p, mx, my, lx, ly, px, py), acc);
+    const F3 col = sumMean(acc, ACC ? p.acc_total : p.spp);
     const uint32_t packed = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xFF000000u;
     uint32_t* outRgba8 = w.frame ? p.batch_rgba8[w.frame - 1u] : p.rgba8;
     const size_t pix = static_cast<size_t>(py) * p.width + px;
@@ -848,7 +856,7 @@ __global__ __launch_bounds__(64) void pathResolveKernel(const RenderParams p)
     }
 }
 
-// accumulation at its limit: no sample is traced, the stored sums are resolved again with the same multiply and quantisation as
+// accumulation at its limit: no sample is traced, the stored sums are resolved again with the same division and quantisation as
 // the last pass of a frame.  One thread per output index of the RGBA8 store: pixel of a whole frame, or staging index of a tile
 // share (slot j of this rank = macro tile j * n_ranks + rank; indices outside the frame are left untouched, as a frame leaves them).
 __global__ __launch_bounds__(256) void pathAccumResolveKernel(const RenderParams p)
@@ -866,9 +874,7 @@ __global__ __launch_bounds__(256) void pathAccumResolveKernel(const RenderParams
         px = static_cast<uint32_t>(i % p.width);
         py = static_cast<uint32_t>(i / p.width);
     }
-    const float4 a = static_cast<const float4*>(p.acc_sum)[i];
-    const float inv = 1.0f / static_cast<float>(p.acc_total);
-    const F3 col = f3(a.x * inv, a.y * inv, a.z * inv);
+    const F3 col = sumMean(loadSum(p.acc_sum, i), p.acc_total);
     p.rgba8[i] = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xFF000000u;
     if (p.rgb_f32 && !p.staging) {
         const size_t pix = static_cast<size_t>(py) * p.width + px;
@@ -887,7 +893,7 @@ namespace { uint32_t wfResident(int which, uint32_t stackEntries); } // resident
 size_t pathRegionBytes(uint32_t tile, uint32_t samples_per_pass)
 {
     const size_t pixels = static_cast<size_t>(tile) * tile, B = pixels * samples_per_pass;
-    return (kShadePlanes + kTracePlanes + 2u) * B * sizeof(float4) + pixels * sizeof(float4); // queues + radiance + throughput, + cross-pass sums
+    return (kShadePlanes + kTracePlanes + 2u) * B * sizeof(float4) + pixels * 2u * sizeof(double2); // queues + radiance + throughput, + cross-pass sums
 }
 uint32_t pathWorkgroupCount(const RenderParams& p) { return renderUnitCount(p) / (p.path_tile == 16u ? 4u : 1u) * (p.n_batch ? p.n_batch : 1u); }
 
@@ -947,7 +953,7 @@ size_t pathWavefrontBytes(const RenderParams& p, uint32_t items)
     pathWavefrontLayout(p, items, chunk, stride);
     const size_t paths = static_cast<size_t>(items) * 64u * p.path_samples;
     size_t bytes = kWfHeadBytes + (static_cast<size_t>(stride) * (kShadePlanes + kTracePlanes) + paths * 2u) * sizeof(float4);
-    if (p.spp > p.path_samples) bytes += static_cast<size_t>(items) * 64u * sizeof(float4);
+    if (p.spp > p.path_samples) bytes += static_cast<size_t>(items) * 64u * 2u * sizeof(double2); // cross-pass float64 sums
     return bytes;
 }
 

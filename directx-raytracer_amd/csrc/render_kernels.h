@@ -81,7 +81,7 @@ struct RenderParams {
     void* wf_trace_q;         // 2 planes x wf_paths
     void* wf_done;            // wf_paths: a path's radiance so far
     void* wf_thr;             // wf_paths: its throughput
-    void* wf_accum;           // nullable: 64 per work item of a pass, sums of earlier passes (spp > path_samples)
+    void* wf_accum;           // nullable: 64 x 2 double2 per work item of a pass, float64 sums of earlier passes (spp > path_samples)
     uint32_t* wf_counts;          // kWfHeadBytes: work counters of the camera launch, then {length, cursor} per queue
     uint32_t wf_paths;            // capacity of a pass in paths = plane stride (pathWavefrontPassItems() x 64 x path_samples)
     uint32_t wf_stride, wf_chunk; // the queues' capacity in entries (= plane stride) and the entries a wavefront reserves per atomic (pathWavefrontLayout)
@@ -90,7 +90,7 @@ struct RenderParams {
     uint32_t wf_s0;               // first sample of this pass
     unsigned long long* timeline; // counting variant only, nullable: per workgroup {start, end} of s_memrealtime (100 MHz) + XCC id
     // mode 200, progressive accumulation (crt_set_accumulation); acc_sum null = off
-    void* acc_sum;                // float4 per output index of the RGBA8 store (pixel of a frame, staging index of a tile share): running sums
+    void* acc_sum;                // 2 double2 {x, y}, {z, 0} per output index of the RGBA8 store (pixel of a frame, staging index of a tile share): float64 running sums
     uint32_t acc_base;            // global index of the call's first sample = samples already in the sums
     uint32_t acc_total;           // acc_base + spp: what the sums are divided by
 };

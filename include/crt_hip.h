@@ -289,7 +289,7 @@ void crt_host_free(void* p);
  * R/DXRTApp.cpp:109-120).  While the view holds still, mode-200 frames add their samples to per-pixel sums, and the image
  * converges instead of showing the same noise on every tick.
  * - Only mode 200 accumulates.  With accumulation on, a mode-200 call traces samples n .. n+spp-1, n = the samples already in
- *   the sums, adds them to per-pixel fp32 sums in sample order and outputs the mean of all n+spp samples (sum * (1.0f / total),
+ *   the sums, adds them to per-pixel float64 sums in sample order and outputs the mean of all n+spp samples ((float)(sum / total),
  *   to RGBA8 and, where asked for, f32 rgb).  K calls of S spp therefore equal, bit for bit, one call of K*S spp; spp may
  *   change between calls (4 + 1 + 3 spp = the 8-spp frame).  Other modes ignore the setting: their frames are those rendered
  *   with it off, and they leave the sums untouched.
@@ -305,10 +305,11 @@ void crt_host_free(void* p);
  *   (each rank sums its own tile slots; the gather moves resolved RGBA8 only).  The batch entry points return CRT_EINVAL in
  *   mode 200 with accumulation on and render nothing: their frames have different cameras.
  * - Consecutive accumulating calls run in issue order on the GPU even when issued on different streams (crt_set_stream).
- * The sums are one float4 per output pixel (staging slot pixel for tile shares), owned by the context: allocated by the first
- * accumulating frame (33 MB at 1920x1080, 133 MB at 3840x2160), freed by crt_set_accumulation(ctx, 0) or crt_destroy. */
+ * The sums are four doubles per output pixel (staging slot pixel for tile shares), owned by the context: allocated by the first
+ * accumulating frame (66 MB at 1920x1080, 265 MB at 3840x2160), freed by crt_set_accumulation(ctx, 0) or crt_destroy.  A pixel
+ * whose samples are all equal resolves to that value exactly at any count up to the limit. */
 int crt_set_accumulation(crt_ctx* ctx, uint32_t max_samples); /* 0 = off (default); 1..2^24 = on, up to that many samples per pixel
-                                                                  (2^24: every count is exact in fp32); always starts over */
+                                                                  (2^24: every count is exact in fp32, the sums are float64); always starts over */
 int crt_reset_accumulation(crt_ctx* ctx);                      /* drop the sums; the next frame starts at sample 0 */
 int crt_accumulated_samples(const crt_ctx* ctx, uint32_t* samples); /* samples per pixel in the current sums (0 when off or reset) */
 

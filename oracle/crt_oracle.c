@@ -1418,17 +1418,19 @@ int oracle_render(const oracle_scene* s, const float pos[3], const float rot[9],
             hit_rec hr;
             const size_t pix = (size_t)py * w + px;
             if (mode >= ORACLE_MODE_PATH) {
-                /* path tracing: spp jittered samples averaged; hit outputs report sample 0's camera ray */
-                v3 acc = v3_make(0.0f, 0.0f, 0.0f);
+                /* path tracing: spp jittered samples averaged; hit outputs report sample 0's camera ray.  The sum is float64,
+                 * one sample added at a time in sample order, resolved once as (float)(sum / spp) -- the kernels' loadSum /
+                 * sumMean (a float32 running sum is off by several RGBA8 steps at 2^22 samples of one value) */
+                double ax = 0.0, ay = 0.0, az = 0.0;
                 hit_rec h0;
                 memset(&h0, 0, sizeof(h0));
                 for (uint32_t sm = 0; sm < g_path_spp; sm++) {
                     v3 Ls = trace_path(s, rot, o, px, py, width, height, (uint32_t)pix, sm, miss, brute_force, &c, &n_closest, &n_shadow,
                                        sm == 0 ? &h0 : NULL);
-                    acc = v3_make(acc.x + Ls.x, acc.y + Ls.y, acc.z + Ls.z);
+                    ax += (double)Ls.x; ay += (double)Ls.y; az += (double)Ls.z;
                 }
-                const float inv = 1.0f / (float)g_path_spp;
-                v3 col = v3_make(acc.x * inv, acc.y * inv, acc.z * inv);
+                const double n = (double)g_path_spp;
+                v3 col = v3_make((float)(ax / n), (float)(ay / n), (float)(az / n));
                 if (rgba8) {
                     rgba8[4 * pix + 0] = oracle_unorm8(col.x); rgba8[4 * pix + 1] = oracle_unorm8(col.y);
                     rgba8[4 * pix + 2] = oracle_unorm8(col.z); rgba8[4 * pix + 3] = 255;

@@ -2,7 +2,7 @@
 """Cost of progressive accumulation (crt_set_accumulation) on the C5 workload (BASELINE.json configs[4]: 5M triangles,
 3840x2160, mode 200, 4 spp, 3 bounces).  In one process, three legs alternate round by round:
   off        accumulation off: the plain frame (what bench.py --config c5 measures)
-  on         accumulation on, far from the limit: every frame reads and writes the per-pixel sums (one float4 each, 133 MB)
+  on         accumulation on, far from the limit: every frame reads and writes the per-pixel sums (four doubles each, 265 MB)
   saturated  accumulation at its limit: no ray traced, the stored sums resolved to RGBA8 (resolve-only kernel)
 Frames are issued back to back on one stream (crt_render_frame_device) after a warm-up; ms/frame = HIP events around the leg's
 frames / frames.  Prints one JSON object (and writes it to --out when given).
