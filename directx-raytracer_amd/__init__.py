@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
     "crt_set_shading_mode", "crt_set_miss_color", "crt_set_counting", "crt_set_option", "crt_debug_read_timeline", "crt_debug_read_counters", "crt_render_frame", "crt_render_frame_device",
     "crt_tile_count", "crt_tile_slots", "crt_render_tiles_device", "crt_render_frames_batch_device", "crt_render_tiles_batch_device",
     "crt_untile_device", "crt_untile_batch_device", "crt_set_stream", "crt_reset_stream",
-    "crt_synchronize", "crt_bvh_info", "crt_bvh_export", "crt_bvh_build_host", "crt_free", "crt_host_alloc", "crt_host_free", "crt_bvh_info4", "crt_bvh_export4", "crt_bvh_export4q", "crt_bvh_quantize4", "crt_comm_unique_id", "crt_comm_init", "crt_comm_init_host", "crt_comm_destroy", "crt_comm_info", "crt_render_frame_distributed", "crt_bvh_build_host4", "crt_build_stats",
+    "crt_synchronize", "crt_bvh_info", "crt_bvh_export", "crt_bvh_build_host", "crt_free", "crt_host_alloc", "crt_host_free", "crt_bvh_info4", "crt_bvh_export4", "crt_bvh_export4q", "crt_bvh_export_planes4q", "crt_bvh_quantize4", "crt_comm_unique_id", "crt_comm_init", "crt_comm_init_host", "crt_comm_destroy", "crt_comm_info", "crt_render_frame_distributed", "crt_bvh_build_host4", "crt_build_stats",
     "crt_scene_load", "crt_scene_save", "crt_scene_new", "crt_scene_free", "crt_scene_add_mesh", "crt_scene_add_light",
     "crt_scene_add_material", "crt_scene_mesh_count", "crt_scene_mesh", "crt_scene_light_count", "crt_scene_light",
     "crt_scene_material_count", "crt_scene_material", "crt_scene_texture_count", "crt_scene_texture_color", "crt_scene_add_texture",
@@ -157,6 +157,7 @@ def lib():
         "crt_build_stats": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "crt_bvh_export4": (C.c_int, [vp, vp]),
         "crt_bvh_export4q": (C.c_int, [vp, vp]),
+        "crt_bvh_export_planes4q": (C.c_int, [vp, vp]),
         "crt_comm_unique_id": (C.c_int, [vp]),
         "crt_comm_init": (C.c_int, [vp, u32, u32, vp]),
         "crt_comm_init_host": (C.c_int, [vp, u32, u32, C.c_char_p]),
@@ -749,6 +750,14 @@ class Renderer:
         q = np.zeros(a.value, dtype=NODE4Q_DTYPE)
         self._ok(lib().crt_bvh_export4q(self.h, q.ctypes.data), "crt_bvh_export4q")
         return q
+
+    def bvh_export_planes4q(self):
+        """the decoded plane table (legacy layout): one row of 32 floats per quantised node, float(q) of its 24 plane bytes + 8 zeros"""
+        a = C.c_uint32()
+        self._ok(lib().crt_bvh_info4(self.h, C.byref(a), None), "crt_bvh_info4")
+        p = np.zeros((a.value, 32), dtype=np.float32)
+        self._ok(lib().crt_bvh_export_planes4q(self.h, p.ctypes.data), "crt_bvh_export_planes4q")
+        return p
 
     def pinned_frame(self, w, h):
         """RGBA8 frame buffer in page-locked host memory (crt_host_alloc), reused across calls of render_frame(pinned=True)."""

@@ -12,6 +12,7 @@
 // option (option "gpu_build": 8.7 ms against 360 ms at 1M triangles), not the default.
 #include "bvh_build.h"
 #include "bvh_wide.h"
+#include "render_kernels.h"
 
 #include <hip/hip_runtime.h>
 #include "gpu_sort.hip.h"
@@ -420,6 +421,17 @@ __global__ __launch_bounds__(256) void wideEmitKernel(const WideTmp* __restrict_
     nodes4q[id[t]] = Q;
 }
 
+// the decoded plane table (render_kernels.h, kPlaneStride): one thread per float of it.  Plane byte k of a record (qlo_x ..
+// qhi_z, child j = byte j of each little-endian word) is float k of its row; the row's last 8 floats are zero.
+__global__ __launch_bounds__(256) void decodePlanesKernel(const unsigned char* __restrict__ nodes, uint32_t n, float* __restrict__ planes)
+{
+    const size_t t = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x;
+    if (t >= static_cast<size_t>(n) * kPlaneStride) return;
+    const size_t node = t / kPlaneStride;
+    const uint32_t k = static_cast<uint32_t>(t % kPlaneStride);
+    planes[t] = k < 24u ? static_cast<float>(nodes[node * sizeof(crt_bvh_node4q) + offsetof(crt_bvh_node4q, qlo_x) + k]) : 0.0f;
+}
+
 struct DevBuf {
     void* p = nullptr;
     explicit DevBuf(size_t bytes) { GPU_TRY(hipMalloc(&p, bytes ? bytes : 16)); }
@@ -678,6 +690,16 @@ void buildBvhGpu(const crt_mesh_view* meshes, uint32_t n_meshes, Bvh& out, ihipS
     out.devTris = dTris.release();
     out.devShade = dShade.release();
     out.devUvs = anyUvs ? dUvs.release() : nullptr;
+}
+
+int launchDecodePlanes(const void* nodes4q, uint32_t n, float* planes, ihipStream_t* stream)
+{
+    static_assert(sizeof(crt_bvh_node4q) == 64 && offsetof(crt_bvh_node4q, qlo_x) == 24 && offsetof(crt_bvh_node4q, ref) == 48, "record layout");
+    if (n == 0) return 0;
+    const size_t total = static_cast<size_t>(n) * kPlaneStride;
+    hipLaunchKernelGGL(decodePlanesKernel, dim3(static_cast<uint32_t>((total + 255) / 256)), dim3(256), 0, stream,
+                       static_cast<const unsigned char*>(nodes4q), n, planes);
+    return static_cast<int>(hipGetLastError());
 }
 
 } // namespace crt

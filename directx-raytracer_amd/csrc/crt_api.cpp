@@ -59,6 +59,7 @@ struct crt_ctx {
 
     crt::Bvh bvh; // host copy of what sits in HBM
     void* dNodes = nullptr;     // quantised wide nodes: what the kernels traverse
+    void* dPlanes = nullptr;    // legacy layout: their decoded plane table (render_kernels.h kPlaneStride), rebuilt at every upload
     void* dBinNodes = nullptr;  // gpu_build only: the binary tree and the full-precision wide tree as the builder left them in
     void* dWideNodes = nullptr; // HBM (no host copy exists; crt_bvh_export* read them back)
     void* dTris = nullptr;
@@ -235,7 +236,7 @@ int fail(crt_ctx* ctx, int code, const char* fmt, ...)
 
 void freeScene(crt_ctx* c)
 {
-    void** ptrs[] = { &c->dNodes, &c->dBinNodes, &c->dWideNodes, &c->dTris, &c->dShade, &c->dLights, &c->dMats, &c->dUvs };
+    void** ptrs[] = { &c->dNodes, &c->dPlanes, &c->dBinNodes, &c->dWideNodes, &c->dTris, &c->dShade, &c->dLights, &c->dMats, &c->dUvs };
     for (void** p : ptrs) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
@@ -260,6 +261,7 @@ void fillParams(const crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_
 {
     std::memset(&p, 0, sizeof(p));
     p.nodes = c->dNodes;
+    p.planes = static_cast<const float*>(c->dPlanes);
     p.tris = c->bvh.width ? c->dNodes : c->dTris;
     p.shade = c->dShade;
     p.lights = c->dLights;
@@ -828,6 +830,11 @@ int crt_upload_scene(crt_ctx* c, const crt_mesh_view* meshes, uint32_t n_meshes,
     if (!c->dNodes) { // (a tree collapsed on the device is already there)
         HIP_TRY(c, hipMalloc(&c->dNodes, nb + 128));
         if (nb) HIP_TRY(c, hipMemcpy(c->dNodes, c->bvh.nodes4q.data(), nb, hipMemcpyHostToDevice));
+    }
+    if (!packed && c->bvh.nNodes4 > 0) { // from the records in HBM, so a tree built on the device gets its table the same way
+        HIP_TRY(c, hipMalloc(&c->dPlanes, sizeof(float) * crt::kPlaneStride * c->bvh.nNodes4));
+        HIP_TRY(c, static_cast<hipError_t>(crt::launchDecodePlanes(c->dNodes, c->bvh.nNodes4, static_cast<float*>(c->dPlanes), nullptr)));
+        HIP_TRY(c, hipDeviceSynchronize());
     }
     if (!recordsOnDevice) {
         if (!packed) HIP_TRY(c, hipMalloc(&c->dTris, tb + 64));
@@ -1542,6 +1549,15 @@ int crt_bvh_export4q(const crt_ctx* c, crt_bvh_node4q* nodes4q)
         if (!c->dWideNodes) crt::copyBytes(nodes4q, c->bvh.nodes4q.data(), sizeof(crt_bvh_node4q) * c->bvh.nodes4q.size());
         else if (hipMemcpy(nodes4q, c->dNodes, sizeof(crt_bvh_node4q) * c->bvh.nNodes4, hipMemcpyDeviceToHost) != hipSuccess) return CRT_EHIP;
     }
+    return CRT_OK;
+}
+
+int crt_bvh_export_planes4q(const crt_ctx* c, float* planes)
+{
+    if (!c || !c->haveScene || c->bvh.width != 0) return CRT_ESTATE;
+    if (planes && c->bvh.nNodes4 > 0 &&
+        hipMemcpy(planes, c->dPlanes, sizeof(float) * crt::kPlaneStride * c->bvh.nNodes4, hipMemcpyDeviceToHost) != hipSuccess)
+        return CRT_EHIP;
     return CRT_OK;
 }
 

@@ -10,11 +10,16 @@ namespace crt {
 constexpr int kMaxBatch = 4;       // frames per launch (crt_render_tiles_batch_device)
 constexpr int kTile = 16;          // macro tile edge: one 256-thread workgroup = 4 wavefronts of 8x8 pixels
 constexpr int kStackEntries = 32;  // upper bound of the per-lane LDS traversal stack = kMaxDepth of the builder
+// Decoded plane table (legacy layout): row i = float(q) of the 24 plane bytes of node i (bytes 24..47 of its record, in
+// order: qlo_x qhi_x qlo_y qhi_y qlo_z qhi_z, child k in byte k of each word), 8 floats of zero padding: 128 bytes per
+// node, so that a row is one s_load_dwordx16 + one s_load_dwordx8 on 64-byte boundaries.  Read by scalar-path node steps only.
+constexpr uint32_t kPlaneStride = 32;
 
 struct RenderParams {
     // scene (HBM)
     const void* nodes;   // crt_bvh_node4q[n_nodes], 64 B (the quantised wide tree); layout 4 / 8: the packed buffer (bvh_pack.h)
     const void* tris;    // crt_bvh_tri[n_tris], 48 B; layout 4 / 8: the same packed buffer
+    const float* planes; // layout 0: the decoded plane table, kPlaneStride floats per node (launchDecodePlanes); else null
     uint32_t layout;     // 0: legacy 64-byte 4-wide nodes + triangle array; 4 / 8: packed wide tree of that width
     const void* shade;   // crt_bvh_shade[n_tris], 48 B
     const void* lights;  // crt_light[n_lights]
@@ -113,6 +118,8 @@ uint32_t pathWavefrontPassItems(const RenderParams& p, uint32_t max_paths);
 void pathWavefrontLayout(const RenderParams& p, uint32_t items, uint32_t& chunk, uint32_t& stride);
 size_t pathWavefrontBytes(const RenderParams& p, uint32_t items);
 uint32_t pathGridSize(const RenderParams& p); // workgroups the persistent path kernel starts: min(work items, what the chip holds at once)
+// the decoded plane table of n quantised nodes (crt_bvh_node4q) into planes[n * kPlaneStride] (bvh_gpu.hip)
+int launchDecodePlanes(const void* nodes4q, uint32_t n, float* planes, ihipStream_t* stream);
 // unit_cost -> unit_order (descending)
 int launchSortUnits(const uint32_t* cost, uint32_t* order, uint32_t n, bool xcdAffine, ihipStream_t* stream);
 // tile-major gathered buffer -> row-major frame

@@ -164,6 +164,15 @@ struct Stack {
     uint32_t itNode = 0, itLeaf = 0, lanesNode = 0, lanesLeaf = 0;
     // divergent (per-lane fetched) steps: how many, lanes in them, runs of consecutive lanes on the same record, distinct records
     uint32_t dvN = 0, dvNLanes = 0, dvNRuns = 0, dvNDistinct = 0, dvL = 0, dvLLanes = 0, dvLRuns = 0, dvLDistinct = 0, unN = 0, unL = 0;
+    // wave-level node steps by kind [0 closest hit, 1 any hit]: scalar path (record through the scalar cache), divergent first
+    // step of a scheduling decision, follow-on steps (early-fetched, per lane); lane-steps on the scalar path.  Counted once
+    // per wavefront (by its first active lane), so a sum over lanes counts wavefront steps.
+    uint32_t wsU[2] = { 0, 0 }, wsD[2] = { 0, 0 }, wsF[2] = { 0, 0 }, lsU[2] = { 0, 0 };
+    __device__ __forceinline__ void stepStat(uint32_t* ws, int kind)
+    {
+        const uint32_t lane = threadIdx.x & 63u;
+        if (lane == static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(lane))) ws[kind]++;
+    }
     __device__ __forceinline__ void divStats(int cur, uint32_t& steps, uint32_t& lanes, uint32_t& runs, uint32_t& distinct)
     {
         const unsigned long long act = __ballot(true);
@@ -267,9 +276,18 @@ struct LayLegacy {
     static constexpr int kRoot = 0;
     static constexpr int kStackPerLevel = 3;
     static constexpr int kWavesPerEu = CRT_WAVES_PER_EU;
+    static constexpr bool kPlaneTable = true; // the kernels may pass the decoded plane table (kPlaneStride) beside the nodes
     struct Node {
         float4 q0, q1, q2;
         int4 refs;
+    };
+    // A record fetched through the scalar cache together with its row of the plane table: the 24 plane bytes as floats, so
+    // that each plane is one v_fma_f32 with a scalar operand instead of a v_cvt_f32_ubyte (half rate) and the fma.
+    struct NodeU {
+        float4 q0;  // lo.xyz, s.x
+        float sy, sz;
+        int4 refs;
+        float p[24]; // float(q): qlo_x[4] qhi_x[4] qlo_y[4] qhi_y[4] qlo_z[4] qhi_z[4] -- bytes 24..47 of the record, in order
     };
     static __device__ __forceinline__ bool inner(int c) { return c >= 0; }
     static __device__ __forceinline__ bool leaf(int c) { return (c < 0) & (c != kDone); }
@@ -289,6 +307,19 @@ struct LayLegacy {
         nd.q0 = quadOf(a); nd.q1 = quadOf(b); nd.q2 = quadOf(c);
         nd.refs = make_int4(__float_as_int(g.x), __float_as_int(g.y), __float_as_int(g.z), __float_as_int(g.w));
         return nd;
+    }
+    static __device__ __forceinline__ NodeU loadUniformDecoded(const float4* nodes, const float* planes, int ref)
+    {
+        const Node nd = loadUniform(nodes, ref);
+        ConstQuadPtr P = (ConstQuadPtr)(reinterpret_cast<uintptr_t>(planes + kPlaneStride * static_cast<size_t>(ref)));
+        NodeU u;
+        u.q0 = nd.q0; u.sy = nd.q1.x; u.sz = nd.q1.y; u.refs = nd.refs;
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            const f4v v = P[k];
+            u.p[4 * k + 0] = v.x; u.p[4 * k + 1] = v.y; u.p[4 * k + 2] = v.z; u.p[4 * k + 3] = v.w;
+        }
+        return u;
     }
     // leaf reference -> first triangle and count; triangle i of the leaf: its record and the id kept in Hit::tri
     static __device__ __forceinline__ void leafRange(int c, uint32_t& first, uint32_t& cnt)
@@ -312,6 +343,26 @@ struct LayLegacy {
 #pragma unroll
         for (int j = 0; j < 2; j++) slabPair<OCT>(lx, hx, ly, hy, lz, hz, j, r, ax, ay, az, bx, by, bz, tmin, tcull, tn + 2 * j, hit + 2 * j);
     }
+    // the same slab tests on a scalar record with decoded planes: the octant names the near / far plane of every axis at
+    // compile time, and fmaf(float(q), a, b) is the value slabPair computes (float(q) is exact for q <= 255).  Known octants
+    // only: the mixed-octant form would pick between two scalar planes per lane, two moves and a select on this ISA (one
+    // scalar operand per vector instruction), which costs more than the conversion it replaces; it keeps the record (Node).
+    template <int OCT>
+    static __device__ __forceinline__ void slab(const NodeU& nd, const Ray& r, float tmin, float tcull, float tn[4], bool hit[4])
+    {
+        static_assert(OCT < 8, "decoded planes: octant-specialised steps only");
+        const float ax = nd.q0.w * r.idir.x, ay = nd.sy * r.idir.y, az = nd.sz * r.idir.z;
+        const float bx = fmaf(nd.q0.x, r.idir.x, r.noid.x), by = fmaf(nd.q0.y, r.idir.y, r.noid.y), bz = fmaf(nd.q0.z, r.idir.z, r.noid.z);
+        constexpr int nx = (OCT & 1) ? 4 : 0, ny = (OCT & 2) ? 12 : 8, nz = (OCT & 4) ? 20 : 16; // near member of each pair
+        constexpr int fx = 4 - nx, fy = 20 - ny, fz = 36 - nz;                                   // far member
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const float t_n = fmaxf(fmaxf(fmaf(nd.p[nx + k], ax, bx), fmaf(nd.p[ny + k], ay, by)), fmaxf(fmaf(nd.p[nz + k], az, bz), tmin));
+            const float t_f = fminf(fminf(fmaf(nd.p[fx + k], ax, bx), fmaf(nd.p[fy + k], ay, by)), fminf(fmaf(nd.p[fz + k], az, bz), tcull));
+            tn[k] = t_n;
+            hit[k] = t_n <= t_f;
+        }
+    }
 
     // closest hit: visit the hit children nearest first.  Order key = (bits(t_near) & 0x7FFFFFFC) | slot: t_near >= 0 so its
     // bit pattern orders like the float, the two low bits hold the slot (keys are unique, order is total and identical in
@@ -325,8 +376,9 @@ struct LayLegacy {
     // 0.2803 vs 0.2854 ms, icosphere soup 0.246 vs 0.255, but primary rays only 0.201 vs 0.192 and the 5M-triangle frame
     // 0.368 vs 0.361: the network runs under the early fetch, off the step's dependent chain, so removing it frees issue
     // slots nobody was waiting for.)
-    template <bool COUNT, int OCT, bool EARLY>
-    static __device__ __forceinline__ void closestStep(const Node& nd, const Ray& r, float tmin, float tcull, Stack& stack,
+    // (N: Node, or NodeU on the scalar path with the plane table)
+    template <bool COUNT, int OCT, bool EARLY, class N>
+    static __device__ __forceinline__ void closestStep(const N& nd, const Ray& r, float tmin, float tcull, Stack& stack,
                                                        int& cur, uint32_t& cntNodes, const float4* __restrict__ nodes, Node& ndNext)
     {
         const int4 refs = nd.refs;
@@ -355,8 +407,8 @@ struct LayLegacy {
     }
 
     // any hit: order independent, children taken in slot order
-    template <bool COUNT, int OCT, bool EARLY>
-    static __device__ __forceinline__ void anyStep(const Node& nd, const Ray& r, float tmin, float tcull, Stack& stack,
+    template <bool COUNT, int OCT, bool EARLY, class N>
+    static __device__ __forceinline__ void anyStep(const N& nd, const Ray& r, float tmin, float tcull, Stack& stack,
                                                    int& cur, uint32_t& cntNodes, const float4* __restrict__ nodes, Node& ndNext)
     {
         const int4 refs = nd.refs;
@@ -398,6 +450,7 @@ struct LayPacked {
 #define CRT_WAVES_PER_EU_W8 5
 #endif
     static constexpr int kWavesPerEu = W == 8 ? CRT_WAVES_PER_EU_W8 : CRT_WAVES_PER_EU;
+    static constexpr bool kPlaneTable = false;
     static constexpr uint32_t kQuads = F::kGranuleBytes / 16u;             // float4 per granule
     static constexpr uint32_t kPayload = (1u << F::kPayloadBits) - 1u;     // low key bits that carry a child designator
     typedef PackedNode<W> Node;
@@ -562,6 +615,16 @@ struct LayPacked {
 
 #endif // CRT_PACKED_LAYOUTS
 
+// The record of a scalar-path step: with the plane table (DEC, layouts with kPlaneTable) and a known octant its planes come
+// decoded (LayLegacy::NodeU), otherwise it is the plain record.  Per-lane steps always fetch the plain 64-byte record: a
+// second fetch per lane costs more than the conversions it would save (section 5 of DESIGN.md).
+template <class L, int OCT, bool DEC>
+__device__ __forceinline__ auto loadUniformStep(const float4* nodes, const float* planes, int ref)
+{
+    if constexpr (DEC && OCT < 8) return L::loadUniformDecoded(nodes, planes, ref);
+    else return L::loadUniform(nodes, ref);
+}
+
 // Uniform descent: the rays of an 8x8 packet start at the root and usually agree on the first few nodes.  While every
 // active lane stands on the SAME inner node its record is fetched once through the scalar cache (the node address is
 // wave-uniform, so the loads become s_load) instead of 64 identical per-lane vector fetches; each lane still runs its own
@@ -572,17 +635,24 @@ struct LayPacked {
         const int c0 = __builtin_amdgcn_readfirstlane(cur);                                                                    \
         if (!L::inner(c0) || __ballot(cur != c0) != 0ull) break;                                                               \
         typename L::Node ndUnused;                                                                                             \
-        L::template STEP<COUNT, OCT, false>(L::loadUniform(nodes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndUnused);  \
+        CRT_UNIFORM_STEP_STAT(STEP)                                                                                            \
+        L::template STEP<COUNT, OCT, false>(loadUniformStep<L, OCT, DEC>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndUnused); \
     }
 #else
 #define CRT_UNIFORM_DESCENT(STEP)
 #endif
+#define CRT_STEP_KIND_closestStep 0
+#define CRT_STEP_KIND_anyStep 1
 #if CRT_PROF
 #define CRT_DIV_STATS_NODE stack.divStats(cur, stack.dvN, stack.dvNLanes, stack.dvNRuns, stack.dvNDistinct);
 #define CRT_DIV_STATS_LEAF stack.divStats(cur, stack.dvL, stack.dvLLanes, stack.dvLRuns, stack.dvLDistinct);
+#define CRT_STEP_STAT(WS, STEP) stack.stepStat(stack.WS, CRT_STEP_KIND_##STEP);
+#define CRT_UNIFORM_STEP_STAT(STEP) CRT_STEP_STAT(wsU, STEP) stack.lsU[CRT_STEP_KIND_##STEP]++;
 #else
 #define CRT_DIV_STATS_NODE
 #define CRT_DIV_STATS_LEAF
+#define CRT_STEP_STAT(WS, STEP)
+#define CRT_UNIFORM_STEP_STAT(STEP)
 #endif
 // One node step of the lanes standing on inner nodes (called with exactly those lanes active): through the scalar cache
 // when they all stand on the same node, per lane otherwise.
@@ -598,9 +668,11 @@ struct LayPacked {
     {                                                                                                                          \
         const int c0 = __builtin_amdgcn_readfirstlane(cur);                                                                    \
         if (__ballot(cur != c0) == 0ull) {                                                                                     \
-            L::template STEP<COUNT, OCT, EARLY>(L::loadUniform(nodes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
+            CRT_UNIFORM_STEP_STAT(STEP)                                                                                        \
+            L::template STEP<COUNT, OCT, EARLY>(loadUniformStep<L, OCT, DEC>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
         } else {                                                                                                               \
             CRT_DIV_STATS_NODE                                                                                                 \
+            CRT_STEP_STAT(wsD, STEP)                                                                                           \
             L::template STEP<COUNT, OCT, EARLY>(L::load(nodes, cur), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);      \
         }                                                                                                                      \
     }
@@ -614,6 +686,7 @@ struct LayPacked {
         CRT_FIRST_NODE_STEP(STEP, (NODE_STEPS > 1))                                                                            \
         _Pragma("unroll") for (int rep = 1; rep < NODE_STEPS; rep++) {                                                         \
             if (L::inner(cur)) {                                                                                               \
+                CRT_STEP_STAT(wsF, STEP)                                                                                       \
                 const typename L::Node ndCur = ndNext;                                                                         \
                 if (rep + 1 < NODE_STEPS) L::template STEP<COUNT, OCT, true>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);   \
                 else L::template STEP<COUNT, OCT, false>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);           \
@@ -646,10 +719,12 @@ __device__ __forceinline__ void loadTriUniform(const float4* T, float4& a, float
 // on inner nodes, or the leaf step of the lanes waiting at leaves.  Per-lane state (cur, stack, h, tcull) lives in the
 // caller, so a caller may retire finished rays and start new ones between two calls (streamClosest).  Returns false when
 // no lane has anything left to do.
-template <bool COUNT, class L, int OCT>
+// DEC / planes: scalar-path steps read the decoded plane table (kPlaneStride floats per node, render_kernels.h) -- the render kernel's
+// traversals; the others keep the default (no table).
+template <bool COUNT, class L, int OCT, bool DEC = false>
 __device__ __forceinline__ bool closestIteration(const float4* __restrict__ nodes, const float4* __restrict__ tris, const Ray& r, float tmin,
                                                  float& tcull, Stack& stack, int innerMin, Hit& h, int& cur, uint32_t& iters,
-                                                 uint32_t& cntNodes, uint32_t& cntTris)
+                                                 uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
 {
     const unsigned long long innerMask = __ballot(L::inner(cur));
     const unsigned long long leafMask = __ballot(L::leaf(cur));
@@ -753,24 +828,24 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
     return true;
 }
 
-template <bool COUNT, class L, int OCT>
+template <bool COUNT, class L, int OCT, bool DEC>
 __device__ __forceinline__ void traceClosestOct(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                              uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
-                                             Hit& h, uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris)
+                                             Hit& h, uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes)
 {
     h.t = tmax; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.gid = 0;
     int cur = n_nodes ? L::kRoot : L::kDone;
     stack.sp = 0;
     float tcull = tmax * kCullPad; // boxes are culled against best_t * pad; changes only when a hit is accepted
     CRT_UNIFORM_DESCENT(closestStep)
-    while (closestIteration<COUNT, L, OCT>(nodes, tris, r, tmin, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris)) {}
+    while (closestIteration<COUNT, L, OCT, DEC>(nodes, tris, r, tmin, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris, planes)) {}
 }
 
 // One scheduling decision of the any-hit traversal (see closestIteration); tmax / tcull / occluded are per-lane state of the caller
-template <bool COUNT, class L, int OCT>
+template <bool COUNT, class L, int OCT, bool DEC = false>
 __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, const float4* __restrict__ tris, const Ray& r, float tmin, float tmax,
                                              float tcull, Stack& stack, int innerMin, bool& occluded, int& cur, uint32_t& iters,
-                                             uint32_t& cntNodes, uint32_t& cntTris)
+                                             uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
 {
     const unsigned long long innerMask = __ballot(L::inner(cur));
     const unsigned long long leafMask = __ballot(L::leaf(cur));
@@ -834,17 +909,17 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
     return true;
 }
 
-template <bool COUNT, class L, int OCT>
+template <bool COUNT, class L, int OCT, bool DEC>
 __device__ __forceinline__ bool traceAnyOct(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                          uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
-                                         uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris)
+                                         uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes)
 {
     bool occluded = false;
     int cur = n_nodes ? L::kRoot : L::kDone;
     stack.sp = 0;
     const float tcull = tmax * kCullPad;
     CRT_UNIFORM_DESCENT(anyStep)
-    while (anyIteration<COUNT, L, OCT>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris)) {}
+    while (anyIteration<COUNT, L, OCT, DEC>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris, planes)) {}
     return occluded;
 }
 
@@ -855,42 +930,42 @@ __device__ __forceinline__ uint32_t octantOf(const Ray& r)
     return (__float_as_uint(r.d.x) >> 31) | ((__float_as_uint(r.d.y) >> 31) << 1) | ((__float_as_uint(r.d.z) >> 31) << 2);
 }
 
-template <bool COUNT, class L>
+template <bool COUNT, class L, bool DEC = false>
 __device__ __forceinline__ void traceClosest(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                              uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
-                                             Hit& h, uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris)
+                                             Hit& h, uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
 {
 #if OCTANT_SPECIALISE
     const uint32_t oct = octantOf(r);
     const uint32_t o0 = __builtin_amdgcn_readfirstlane(oct);
     if (__ballot(oct != o0) == 0ull) {
         switch (o0) {
-#define CRT_CASE(k) case k: traceClosestOct<COUNT, L, k>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris); return;
+#define CRT_CASE(k) case k: traceClosestOct<COUNT, L, k, DEC>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes); return;
             CRT_CASE(0) CRT_CASE(1) CRT_CASE(2) CRT_CASE(3) CRT_CASE(4) CRT_CASE(5) CRT_CASE(6) CRT_CASE(7)
 #undef CRT_CASE
         }
     }
 #endif
-    traceClosestOct<COUNT, L, 8>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris);
+    traceClosestOct<COUNT, L, 8, DEC>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes);
 }
 
-template <bool COUNT, class L>
+template <bool COUNT, class L, bool DEC = false>
 __device__ __forceinline__ bool traceAny(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                          uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
-                                         uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris)
+                                         uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
 {
 #if OCTANT_SPECIALISE
     const uint32_t oct = octantOf(r);
     const uint32_t o0 = __builtin_amdgcn_readfirstlane(oct);
     if (__ballot(oct != o0) == 0ull) {
         switch (o0) {
-#define CRT_CASE(k) case k: return traceAnyOct<COUNT, L, k>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris);
+#define CRT_CASE(k) case k: return traceAnyOct<COUNT, L, k, DEC>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
             CRT_CASE(0) CRT_CASE(1) CRT_CASE(2) CRT_CASE(3) CRT_CASE(4) CRT_CASE(5) CRT_CASE(6) CRT_CASE(7)
 #undef CRT_CASE
         }
     }
 #endif
-    return traceAnyOct<COUNT, L, 8>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris);
+    return traceAnyOct<COUNT, L, 8, DEC>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
 }
 
 } // namespace

@@ -269,6 +269,10 @@ int crt_bvh_info4(const crt_ctx* ctx, uint32_t* n_nodes4, uint32_t* depth4);
 int crt_bvh_export4(const crt_ctx* ctx, crt_bvh_node4* nodes4);
 /* the same nodes in the 64-byte quantised form the kernels fetch (count = n_nodes4) */
 int crt_bvh_export4q(const crt_ctx* ctx, crt_bvh_node4q* nodes4q);
+/* the decoded plane table beside those nodes (legacy layout only; CRT_ESTATE for the packed ones): n_nodes4 rows of 32 floats,
+ * row i = float(q) of plane byte k of node i (qlo_x .. qhi_z, child j = byte j of each word) for k < 24, then 8 zeros.  The
+ * kernels' node steps read it when a whole wavefront stands on one node. */
+int crt_bvh_export_planes4q(const crt_ctx* ctx, float* planes);
 /* host-only BVH build, no device needed (used by crt_upload_scene; exposed for tests and tooling) */
 int crt_bvh_build_host(const crt_mesh_view* meshes, uint32_t n_meshes,
                        crt_bvh_node** nodes, uint32_t* n_nodes,

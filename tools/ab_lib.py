@@ -39,6 +39,11 @@ def main():
                 if rnd: res[(path, v)].append(statistics.median(ms))
     for (path, v) in res:
         print("%-32s %-18s median %.4f ms  min %.4f ms" % (os.path.basename(path), "" if v is None else "%s=%d" % (oname, v), statistics.median(res[(path, v)]), min(res[(path, v)])), flush=True)
+    # each context is destroyed by the library that made it (pkg._lib is global: left to __del__ at exit, every context would go
+    # to the last library's crt_destroy, which reads another build's context layout)
+    for path, L, r in rs:
+        pkg._lib = L
+        r.close()
 
 
 if __name__ == "__main__":

@@ -56,6 +56,11 @@ def main():
         if d[4] > 0:
             print("   divergent leaf steps %d: %.1f lanes, %.1f runs, %.1f distinct leaves each" % (d[4], d[5] / d[4], d[6] / d[4], d[7] / d[4]))
         print("   node fetches %d  tri fetches %d -> per node phase %.1f lane-steps, per leaf phase %.1f tri tests" % (c[0], c[1], c[0] / itn, c[1] / itl))
+        for k, name in enumerate(("closest-hit (primary) rays", "any-hit (shadow) rays")):
+            u, dv, fo, lu = c[19 + k], c[21 + k], c[23 + k], c[25 + k]
+            if u + dv + fo > 0:  # wavefront node steps: scalar path (decoded planes) / divergent first step / follow-on step
+                print("   %-27s wavefront node steps %d: scalar path %d (%.1f%%, %.1f lanes), divergent first %d (%.1f%%), follow-on %d (%.1f%%)" % (
+                    name, u + dv + fo, u, 100 * u / (u + dv + fo), lu / max(u, 1), dv, 100 * dv / (u + dv + fo), fo, 100 * fo / (u + dv + fo)))
 
 
 if __name__ == "__main__":
