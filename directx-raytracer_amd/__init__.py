@@ -752,7 +752,7 @@ class Renderer:
         return q
 
     def bvh_export_planes4q(self):
-        """the decoded plane table (legacy layout): one row of 32 floats per quantised node, float(q) of its 24 plane bytes + 8 zeros"""
+        """the decoded plane table: one row of 32 floats per quantised node, float(q) of its 24 plane bytes + 8 zeros"""
         a = C.c_uint32()
         self._ok(lib().crt_bvh_info4(self.h, C.byref(a), None), "crt_bvh_info4")
         p = np.zeros((a.value, 32), dtype=np.float32)

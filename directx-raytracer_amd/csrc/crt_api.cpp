@@ -59,7 +59,7 @@ struct crt_ctx {
 
     crt::Bvh bvh; // host copy of what sits in HBM
     void* dNodes = nullptr;     // quantised wide nodes: what the kernels traverse
-    void* dPlanes = nullptr;    // legacy layout: their decoded plane table (render_kernels.h kPlaneStride), rebuilt at every upload
+    void* dPlanes = nullptr;    // their decoded plane table (render_kernels.h kPlaneStride), rebuilt at every upload
     void* dBinNodes = nullptr;  // gpu_build only: the binary tree and the full-precision wide tree as the builder left them in
     void* dWideNodes = nullptr; // HBM (no host copy exists; crt_bvh_export* read them back)
     void* dTris = nullptr;
@@ -73,7 +73,6 @@ struct crt_ctx {
     uint32_t nLights = 0, nMats = 0;
     bool haveScene = false;
     bool gpuBuild = false;      // option "gpu_build": LBVH on the device instead of the host SAH builder
-    uint32_t bvhWidth = 0;      // option "bvh_width": 0 = legacy 64-byte 4-wide nodes, 4 / 8 = packed wide tree (bvh_pack.h), at the next upload
     double buildMs = 0.0;       // wall time of the last crt_upload_scene (build + upload)
     double buildDeviceMs = 0.0; // of which GPU kernels (gpu_build only)
     uint32_t sceneSerial = 0;
@@ -262,7 +261,7 @@ void fillParams(const crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_
     std::memset(&p, 0, sizeof(p));
     p.nodes = c->dNodes;
     p.planes = static_cast<const float*>(c->dPlanes);
-    p.tris = c->bvh.width ? c->dNodes : c->dTris;
+    p.tris = c->dTris;
     p.shade = c->dShade;
     p.lights = c->dLights;
     p.mats = c->dMats;
@@ -270,8 +269,7 @@ void fillParams(const crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_
     p.textures = c->dTextures;
     p.texels = static_cast<const unsigned char*>(c->dTexels);
     p.n_textures = c->nTextures;
-    p.layout = c->bvh.width;
-    p.n_nodes = c->bvh.width ? c->bvh.nWide : c->bvh.nNodes4;
+    p.n_nodes = c->bvh.nNodes4;
     p.n_tris = c->bvh.nTris;
     p.n_lights = c->nLights;
     p.n_mats = c->nMats;
@@ -354,13 +352,13 @@ int runRender(crt_ctx* c, RenderParams& p, crt_frame_stats* stats)
     const uint32_t slot = c->frameSerial++ % crt_ctx::kRing;
     {
         // deepest stack a ray can build: three pending siblings per wide level; what does not fit the LDS part spills
-        const uint32_t deepest = c->bvh.width ? (c->bvh.width - 1u) * c->bvh.depthWide + 1u : 3u * c->bvh.depth4 + 1u;
+        const uint32_t deepest = 3u * c->bvh.depth4 + 1u;
         p.spill_stride = deepest > p.stack_entries ? deepest - p.stack_entries : 1u;
         // (mode 200: one slice per resident workgroup of the persistent kernel)
         if (p.mode >= 200u) {
             p.path_tile = c->tunePathTile ? c->tunePathTile : 8u;
             // the stages as separate launches over global queues (8x8 work items, 64-byte nodes), or one persistent kernel
-            p.path_wavefront = (c->tunePathPipeline == 1u && p.path_tile == 8u && c->bvh.width == 0u) ? 1u : 0u;
+            p.path_wavefront = (c->tunePathPipeline == 1u && p.path_tile == 8u) ? 1u : 0u;
         }
         // (+ 64 slices for each of the four wavefronts of a split packet)
         const size_t groups = p.mode >= 200u ? static_cast<size_t>(crt::pathGridSize(p))
@@ -784,7 +782,7 @@ int crt_upload_scene(crt_ctx* c, const crt_mesh_view* meshes, uint32_t n_meshes,
             HIP_TRY(c, hipSetDevice(c->device));
             crt::buildBvhGpu(meshes, n_meshes, built, c->stream, &deviceMs);
         } else {
-            crt::buildBvh(meshes, n_meshes, built, static_cast<int>(c->bvhWidth));
+            crt::buildBvh(meshes, n_meshes, built);
         }
     } catch (const std::bad_alloc&) {
         return fail(c, CRT_ENOMEM, "out of host memory while building the BVH");
@@ -820,26 +818,20 @@ int crt_upload_scene(crt_ctx* c, const crt_mesh_view* meshes, uint32_t n_meshes,
     const size_t nb = sizeof(crt_bvh_node4q) * c->bvh.nodes4q.size(); // the quantised wide tree is what the kernels traverse
     const size_t tb = sizeof(crt_bvh_tri) * c->bvh.nTris;
     const size_t sb = sizeof(crt_bvh_shade) * c->bvh.nTris;
-    const bool packed = c->bvh.width != 0;
     // +64 bytes of slack so that a speculative wide load of the last record stays inside the allocation
-    if (packed && !c->dNodes) { // nodes and triangles in one buffer: dTris stays empty, the kernels get dNodes for both
-        const size_t pb = c->bvh.packed.size() * sizeof(uint32_t);
-        HIP_TRY(c, hipMalloc(&c->dNodes, pb + 128));
-        if (pb) HIP_TRY(c, hipMemcpy(c->dNodes, c->bvh.packed.data(), pb, hipMemcpyHostToDevice));
-    }
     if (!c->dNodes) { // (a tree collapsed on the device is already there)
         HIP_TRY(c, hipMalloc(&c->dNodes, nb + 128));
         if (nb) HIP_TRY(c, hipMemcpy(c->dNodes, c->bvh.nodes4q.data(), nb, hipMemcpyHostToDevice));
     }
-    if (!packed && c->bvh.nNodes4 > 0) { // from the records in HBM, so a tree built on the device gets its table the same way
+    if (c->bvh.nNodes4 > 0) { // from the records in HBM, so a tree built on the device gets its table the same way
         HIP_TRY(c, hipMalloc(&c->dPlanes, sizeof(float) * crt::kPlaneStride * c->bvh.nNodes4));
         HIP_TRY(c, static_cast<hipError_t>(crt::launchDecodePlanes(c->dNodes, c->bvh.nNodes4, static_cast<float*>(c->dPlanes), nullptr)));
         HIP_TRY(c, hipDeviceSynchronize());
     }
     if (!recordsOnDevice) {
-        if (!packed) HIP_TRY(c, hipMalloc(&c->dTris, tb + 64));
+        HIP_TRY(c, hipMalloc(&c->dTris, tb + 64));
         HIP_TRY(c, hipMalloc(&c->dShade, sb + 64));
-        if (tb && !packed) HIP_TRY(c, hipMemcpy(c->dTris, c->bvh.tris.data(), tb, hipMemcpyHostToDevice));
+        if (tb) HIP_TRY(c, hipMemcpy(c->dTris, c->bvh.tris.data(), tb, hipMemcpyHostToDevice));
         if (sb) HIP_TRY(c, hipMemcpy(c->dShade, c->bvh.shade.data(), sb, hipMemcpyHostToDevice));
         if (!c->bvh.uvs.empty()) {
             const size_t ub = sizeof(crt_bvh_uv) * c->bvh.uvs.size();
@@ -854,7 +846,7 @@ int crt_upload_scene(crt_ctx* c, const crt_mesh_view* meshes, uint32_t n_meshes,
     c->nLights = n_lights;
     c->nMats = n_materials;
     for (int a = 0; a < 3; a++) c->sceneLo[a] = c->sceneHi[a] = 0.0f;
-    if (c->bvh.width == 0 && c->bvh.nNodes4 > 0) { // the root record as it sits in HBM (built here or on the device alike)
+    if (c->bvh.nNodes4 > 0) { // the root record as it sits in HBM (built here or on the device alike)
         crt_bvh_node4q root;
         HIP_TRY(c, hipMemcpy(&root, c->dNodes, sizeof(root), hipMemcpyDeviceToHost));
         for (int a = 0; a < 3; a++) {
@@ -959,16 +951,8 @@ int crt_set_option(crt_ctx* c, const char* name, int value)
         c->gpuBuild = value != 0;
         return CRT_OK;
     }
-#if defined(CRT_PACKED_LAYOUTS) && CRT_PACKED_LAYOUTS
-    // round-3 experiment (tools/variant_build.sh packed "-DCRT_PACKED_LAYOUTS=1", tools/width_ab.py): 0 = the product's 64-byte
-    // 4-wide nodes, 4 / 8 = packed wide tree (bvh_pack.h), taken at the next crt_upload_scene; host build only
-    if (std::strcmp(name, "bvh_width") == 0 && (value == 0 || value == 4 || value == 8)) {
-        c->bvhWidth = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-#else
+    // the 64-byte 4-wide tree is the only layout: 0 names it, any other width is rejected below
     if (std::strcmp(name, "bvh_width") == 0 && value == 0) return CRT_OK;
-#endif
     if (std::strcmp(name, "spp") == 0 && value >= 1 && value <= 65536) {
         c->pathSpp = static_cast<uint32_t>(value);
         c->viewSerial++;
@@ -1164,7 +1148,6 @@ int checkQuery(crt_ctx* c, const char* what)
 {
     if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
     if (!c->haveScene) return fail(c, CRT_ESTATE, "%s: no scene uploaded: call crt_upload_scene first", what);
-    if (c->bvh.width != 0u) return fail(c, CRT_EINVAL, "%s: ray queries traverse the legacy 4-wide tree only (option bvh_width 0)", what);
     return CRT_OK;
 }
 
@@ -1554,7 +1537,7 @@ int crt_bvh_export4q(const crt_ctx* c, crt_bvh_node4q* nodes4q)
 
 int crt_bvh_export_planes4q(const crt_ctx* c, float* planes)
 {
-    if (!c || !c->haveScene || c->bvh.width != 0) return CRT_ESTATE;
+    if (!c || !c->haveScene) return CRT_ESTATE;
     if (planes && c->bvh.nNodes4 > 0 &&
         hipMemcpy(planes, c->dPlanes, sizeof(float) * crt::kPlaneStride * c->bvh.nNodes4, hipMemcpyDeviceToHost) != hipSuccess)
         return CRT_EHIP;

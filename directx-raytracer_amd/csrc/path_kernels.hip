@@ -988,7 +988,7 @@ uint32_t wfResident(int which, uint32_t stackEntries) // 0 camera, 1 shade, 2 tr
 
 int launchPathWavefront(const RenderParams& p0, bool counting, ihipStream_t* stream)
 {
-    if (!p0.wf_counts || !p0.wf_shade_q || p0.wf_paths == 0u || p0.path_tile != 8u || p0.layout != 0u) return static_cast<int>(hipErrorInvalidValue);
+    if (!p0.wf_counts || !p0.wf_shade_q || p0.wf_paths == 0u || p0.path_tile != 8u) return static_cast<int>(hipErrorInvalidValue);
     const uint32_t total = pathWorkgroupCount(p0), perItem = 64u * p0.path_samples;
     const uint32_t passItems = p0.wf_paths / perItem;
     if (passItems == 0u || p0.max_bounces > 64u || p0.wf_paths > (1u << 25)) return static_cast<int>(hipErrorInvalidValue);
@@ -1039,21 +1039,13 @@ int launchPath(const RenderParams& p, bool counting, ihipStream_t* stream)
     if (!p.path_counter || p.path_work_items == 0) return static_cast<int>(hipErrorInvalidValue);
     const dim3 grid(pathGridSize(p)), block(64);
     const size_t lds = static_cast<size_t>(p.stack_entries) * 64u * sizeof(int);
-#define CRT_LAUNCH(LAY)                                                                                \
-    if (p.acc_sum) {                                                                                   \
-        if (counting) hipLaunchKernelGGL((pathKernel<true, LAY, true>), grid, block, lds, stream, p);     \
-        else hipLaunchKernelGGL((pathKernel<false, LAY, true>), grid, block, lds, stream, p);             \
-    } else {                                                                                           \
-        if (counting) hipLaunchKernelGGL((pathKernel<true, LAY, false>), grid, block, lds, stream, p);        \
-        else hipLaunchKernelGGL((pathKernel<false, LAY, false>), grid, block, lds, stream, p);                \
+    if (p.acc_sum) {
+        if (counting) hipLaunchKernelGGL((pathKernel<true, LayLegacy, true>), grid, block, lds, stream, p);
+        else hipLaunchKernelGGL((pathKernel<false, LayLegacy, true>), grid, block, lds, stream, p);
+    } else {
+        if (counting) hipLaunchKernelGGL((pathKernel<true, LayLegacy, false>), grid, block, lds, stream, p);
+        else hipLaunchKernelGGL((pathKernel<false, LayLegacy, false>), grid, block, lds, stream, p);
     }
-#if CRT_PACKED_LAYOUTS
-    if (p.layout == 8u) { CRT_LAUNCH(LayPacked<8>) }
-    else if (p.layout == 4u) { CRT_LAUNCH(LayPacked<4>) }
-    else
-#endif
-    { CRT_LAUNCH(LayLegacy) }
-#undef CRT_LAUNCH
     return static_cast<int>(hipGetLastError());
 }
 

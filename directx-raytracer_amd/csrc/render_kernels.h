@@ -10,17 +10,16 @@ namespace crt {
 constexpr int kMaxBatch = 4;       // frames per launch (crt_render_tiles_batch_device)
 constexpr int kTile = 16;          // macro tile edge: one 256-thread workgroup = 4 wavefronts of 8x8 pixels
 constexpr int kStackEntries = 32;  // upper bound of the per-lane LDS traversal stack = kMaxDepth of the builder
-// Decoded plane table (legacy layout): row i = float(q) of the 24 plane bytes of node i (bytes 24..47 of its record, in
+// Decoded plane table: row i = float(q) of the 24 plane bytes of node i (bytes 24..47 of its record, in
 // order: qlo_x qhi_x qlo_y qhi_y qlo_z qhi_z, child k in byte k of each word), 8 floats of zero padding: 128 bytes per
 // node, so that a row is one s_load_dwordx16 + one s_load_dwordx8 on 64-byte boundaries.  Read by scalar-path node steps only.
 constexpr uint32_t kPlaneStride = 32;
 
 struct RenderParams {
     // scene (HBM)
-    const void* nodes;   // crt_bvh_node4q[n_nodes], 64 B (the quantised wide tree); layout 4 / 8: the packed buffer (bvh_pack.h)
-    const void* tris;    // crt_bvh_tri[n_tris], 48 B; layout 4 / 8: the same packed buffer
-    const float* planes; // layout 0: the decoded plane table, kPlaneStride floats per node (launchDecodePlanes); else null
-    uint32_t layout;     // 0: legacy 64-byte 4-wide nodes + triangle array; 4 / 8: packed wide tree of that width
+    const void* nodes;   // crt_bvh_node4q[n_nodes], 64 B (the quantised wide tree)
+    const void* tris;    // crt_bvh_tri[n_tris], 48 B
+    const float* planes; // the decoded plane table, kPlaneStride floats per node (launchDecodePlanes)
     const void* shade;   // crt_bvh_shade[n_tris], 48 B
     const void* lights;  // crt_light[n_lights]
     const void* mats;    // crt_material[n_mats] (28 B)
@@ -127,9 +126,9 @@ int launchUntile(const uint32_t* gathered, uint32_t* frame, uint32_t width, uint
                  uint32_t rank_stride, uint32_t first_slot, ihipStream_t* stream);
 
 // batched ray queries (ray_kernels.hip; crt_trace_rays* / crt_occluded_rays*): n caller-supplied records of 8 floats
-// {ox, oy, oz, tmin, dx, dy, dz, tmax}, closest hit or occlusion, over the legacy 4-wide tree
+// {ox, oy, oz, tmin, dx, dy, dz, tmax}, closest hit or occlusion, over the 4-wide tree
 struct RayQueryParams {
-    const void* nodes;            // as RenderParams::nodes / tris (layout 0 only)
+    const void* nodes;            // as RenderParams::nodes / tris
     const void* tris;
     uint32_t n_nodes;
     const void* rays;             // n x 32 bytes, 16-byte aligned

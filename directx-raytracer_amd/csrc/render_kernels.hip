@@ -153,7 +153,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SPLIT ? 5 : 
             const F3 o = f3(camPos[0], camPos[1], camPos[2]);
             const Ray r = makeRay(o, rayDir(camRot, px, py, static_cast<float>(p.width), static_cast<float>(p.height)));
             if (COUNT) cntClosest++;
-            traceClosest<COUNT, L, L::kPlaneTable>(nodes, tris, p.n_nodes, r, kTMin, kTMax, stack, static_cast<int>(p.tune_inner_min), h, iters, cntNodes, cntTris, p.planes);
+            traceClosest<COUNT, L, true>(nodes, tris, p.n_nodes, r, kTMin, kTMax, stack, static_cast<int>(p.tune_inner_min), h, iters, cntNodes, cntTris, p.planes);
             col = f3(p.miss[0], p.miss[1], p.miss[2]); // miss shader (hlsl:72-76)
             if (h.t < kTMax) {
                 const float4* T = L::triPtr(tris, h.tri);
@@ -278,20 +278,13 @@ int launchRender(const RenderParams& p, bool counting, ihipStream_t* stream)
         const dim3 grid((n * 4u + extra) * (p.n_batch ? p.n_batch : 1u));
         const bool phong = p.mode >= 100u && p.phong_ks > 0.0f;
         const bool split = p.unit_order && p.split_units > 0u;
-#define CRT_LAUNCH2(LAY, SPL)                                                                                          \
-        if (counting && phong) hipLaunchKernelGGL((renderKernel<true, true, LAY, SPL>), grid, block, lds, stream, p);  \
-        else if (counting) hipLaunchKernelGGL((renderKernel<true, false, LAY, SPL>), grid, block, lds, stream, p);     \
-        else if (phong) hipLaunchKernelGGL((renderKernel<false, true, LAY, SPL>), grid, block, lds, stream, p);        \
-        else hipLaunchKernelGGL((renderKernel<false, false, LAY, SPL>), grid, block, lds, stream, p);
-#define CRT_LAUNCH(LAY) if (split) { CRT_LAUNCH2(LAY, true) } else { CRT_LAUNCH2(LAY, false) }
-#if CRT_PACKED_LAYOUTS
-        if (p.layout == 8u) { CRT_LAUNCH(LayPacked<8>) }
-        else if (p.layout == 4u) { CRT_LAUNCH(LayPacked<4>) }
-        else
-#endif
-        { CRT_LAUNCH(LayLegacy) }
+#define CRT_LAUNCH(SPL)                                                                                                    \
+        if (counting && phong) hipLaunchKernelGGL((renderKernel<true, true, LayLegacy, SPL>), grid, block, lds, stream, p);  \
+        else if (counting) hipLaunchKernelGGL((renderKernel<true, false, LayLegacy, SPL>), grid, block, lds, stream, p);     \
+        else if (phong) hipLaunchKernelGGL((renderKernel<false, true, LayLegacy, SPL>), grid, block, lds, stream, p);        \
+        else hipLaunchKernelGGL((renderKernel<false, false, LayLegacy, SPL>), grid, block, lds, stream, p);
+        if (split) { CRT_LAUNCH(true) } else { CRT_LAUNCH(false) }
 #undef CRT_LAUNCH
-#undef CRT_LAUNCH2
     }
     return static_cast<int>(hipGetLastError());
 }

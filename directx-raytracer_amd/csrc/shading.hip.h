@@ -114,8 +114,7 @@ __device__ __forceinline__ Surface surfaceAt(const RenderParams& p, const float4
     Surface sf;
     const float4* T = L::triPtr(tris, h.tri);
     const float4 tb = T[1], tc = T[2];
-    const uint32_t rec = L::shadeIndex(h.tri, __float_as_uint(tc.w)); // shading / uv record: leaf order, or input order (packed tree)
-    const float* S = reinterpret_cast<const float*>(p.shade) + 12 * static_cast<size_t>(rec);
+    const float* S = reinterpret_cast<const float*>(p.shade) + 12 * static_cast<size_t>(h.tri); // shading / uv record: leaf order
     const uint32_t material = __float_as_uint(S[9]);
     sf.P = f3(r.o.x + r.d.x * h.t, r.o.y + r.d.y * h.t, r.o.z + r.d.z * h.t);
     sf.albedo = f3(1.0f, 1.0f, 1.0f);
@@ -136,7 +135,7 @@ __device__ __forceinline__ Surface surfaceAt(const RenderParams& p, const float4
                 tu = 0.0f;
                 tv = 0.0f;
                 if (p.uvs) {
-                    const float* U = reinterpret_cast<const float*>(p.uvs) + 6 * static_cast<size_t>(rec);
+                    const float* U = reinterpret_cast<const float*>(p.uvs) + 6 * static_cast<size_t>(h.tri);
                     const float w = 1.0f - h.u - h.v;
                     tu = fmaf(U[4], h.v, fmaf(U[2], h.u, U[0] * w));
                     tv = fmaf(U[5], h.v, fmaf(U[3], h.u, U[1] * w));
@@ -200,7 +199,7 @@ __device__ __forceinline__ F3 directLight(const RenderParams& p, const float4* n
         if (cosv > 0.0f) {
             const Ray sr = makeRay(Po, Ld);
             if (COUNT) cntShadow++;
-            const bool occluded = traceAny<COUNT, L, L::kPlaneTable>(nodes, tris, p.n_nodes, sr, 0.0f, dist, stack, static_cast<int>(p.tune_inner_min_any), iters, cntNodes, cntTris, p.planes);
+            const bool occluded = traceAny<COUNT, L, true>(nodes, tris, p.n_nodes, sr, 0.0f, dist, stack, static_cast<int>(p.tune_inner_min_any), iters, cntNodes, cntTris, p.planes);
             if (!occluded) {
                 const float k = (Lt.intensity / (kFourPi * r2)) * cosv;
                 rgb.x = fmaf(albedo.x, k, rgb.x);

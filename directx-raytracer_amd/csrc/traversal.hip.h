@@ -7,7 +7,6 @@
 #pragma once
 
 #include "render_kernels.h"
-#include "bvh_pack.h"
 
 #include <hip/hip_runtime.h>
 
@@ -206,7 +205,7 @@ struct Stack {
 
 struct Hit {
     float t, u, v;
-    uint32_t tri; // triangle record: leaf-order index (legacy layout) or granule address in the packed buffer
+    uint32_t tri; // triangle record: leaf-order index into the triangle array, also the shading / uv record
     uint32_t gid;
 };
 
@@ -223,16 +222,14 @@ __device__ __forceinline__ int pick4(const int4& v, uint32_t i) // v[i], i in 0.
 }
 
 // =====================================================================================================================
-// Tree layouts.  A layout says what a reference is, how a node record is fetched and how one node step turns it into the
-// next current reference plus pushes; everything else (wave-level scheduling, leaves, the octant dispatch) is shared.
+// Tree layout.  The layout (LayLegacy) says what a reference is, how a node record is fetched and how one node step turns
+// it into the next current reference plus pushes; the wave-level scheduling, leaves and the octant dispatch use only that.
 //
-// ---- LayLegacy: 4-wide, node = crt_bvh_node4q, 64 bytes = four dwordx4 loads:
+// LayLegacy: 4-wide, node = crt_bvh_node4q, 64 bytes = four dwordx4 loads:
 //   {lo.x lo.y lo.z s.x} {s.y s.z qlo_x qhi_x} {qlo_y qhi_y qlo_z qhi_z} {ref[4]}
 // separate triangle array; references are signed (>= 0 node index, < 0 leaf ~((first << 3) | count)).
-// ---- LayPacked<W>: the packed wide tree of bvh_pack.h, W = 4 (48-byte nodes, three loads) or 8 (80 bytes, five): nodes
-// and triangles in ONE buffer, a node's children back to back, references (address << 3) | kind.
 //
-// In both the child planes are 8-bit offsets from the node's own minimum corner: plane = fma(q, s, lo).  A per-lane fetch
+// The child planes are 8-bit offsets from the node's own minimum corner: plane = fma(q, s, lo).  A per-lane fetch
 // request costs this kernel far more than vector arithmetic does (24 / 48 extra dependent VALU per step measured +9 % /
 // +21 %, one extra 4-byte touch per pushed child +29 %), so records are kept to as few requests per lane as possible and
 // decoded in registers.  The decode is folded into the slab test: t(q) = fma(q, s * idir, fma(lo, idir, -o * idir)),
@@ -276,7 +273,6 @@ struct LayLegacy {
     static constexpr int kRoot = 0;
     static constexpr int kStackPerLevel = 3;
     static constexpr int kWavesPerEu = CRT_WAVES_PER_EU;
-    static constexpr bool kPlaneTable = true; // the kernels may pass the decoded plane table (kPlaneStride) beside the nodes
     struct Node {
         float4 q0, q1, q2;
         int4 refs;
@@ -330,8 +326,6 @@ struct LayLegacy {
     }
     static __device__ __forceinline__ uint32_t triId(uint32_t first, uint32_t i) { return first + i; }
     static __device__ __forceinline__ const float4* triPtr(const float4* __restrict__ tris, uint32_t id) { return tris + 3 * static_cast<size_t>(id); }
-    // shading / uv record of a hit: leaf order
-    static __device__ __forceinline__ uint32_t shadeIndex(uint32_t id, uint32_t) { return id; }
 
     template <int OCT>
     static __device__ __forceinline__ void slab(const Node& nd, const Ray& r, float tmin, float tcull, float tn[4], bool hit[4])
@@ -428,194 +422,7 @@ struct LayLegacy {
     }
 };
 
-// The packed layouts are an experiment of round 3 that lost (48-byte 4-wide nodes +6 %, 80-byte 8-wide nodes
-// +34 % on the 1M-triangle frame): compiled only with -DCRT_PACKED_LAYOUTS=1 (tools/variant_build.sh packed ...), host build only.
-#ifndef CRT_PACKED_LAYOUTS
-#define CRT_PACKED_LAYOUTS 0
-#endif
-#if CRT_PACKED_LAYOUTS
-template <int W> struct PackedNode;
-template <> struct PackedNode<4> { float4 q0, q1, q2; };
-template <> struct PackedNode<8> { float4 q0, q1, q2, q3, q4; };
-
-template <int W>
-struct LayPacked {
-    typedef PackFmt<W> F;
-    static constexpr int kWidth = W;
-    static constexpr int kDone = static_cast<int>(kRefDone);
-    static constexpr int kRoot = static_cast<int>(kRefInner); // the root's record sits at address 0
-    static constexpr int kStackPerLevel = W - 1;
-    // register budget of the primary / shadow-ray kernel: an 8-wide node in flight is 20 registers, and the early fetch holds two
-#ifndef CRT_WAVES_PER_EU_W8
-#define CRT_WAVES_PER_EU_W8 5
-#endif
-    static constexpr int kWavesPerEu = W == 8 ? CRT_WAVES_PER_EU_W8 : CRT_WAVES_PER_EU;
-    static constexpr bool kPlaneTable = false;
-    static constexpr uint32_t kQuads = F::kGranuleBytes / 16u;             // float4 per granule
-    static constexpr uint32_t kPayload = (1u << F::kPayloadBits) - 1u;     // low key bits that carry a child designator
-    typedef PackedNode<W> Node;
-    static __device__ __forceinline__ bool inner(int c) { return (static_cast<uint32_t>(c) & 7u) == kRefInner; }
-    static __device__ __forceinline__ bool leaf(int c) { return ((static_cast<uint32_t>(c) & 7u) != kRefInner) & (c != kDone); }
-    static __device__ __forceinline__ const float4* at(const float4* buf, uint32_t address) { return buf + static_cast<size_t>(address) * kQuads; }
-    static __device__ __forceinline__ Node load(const float4* __restrict__ nodes, int ref)
-    {
-        const float4* N = at(nodes, static_cast<uint32_t>(ref) >> 3);
-        Node nd;
-        nd.q0 = N[0]; nd.q1 = N[1]; nd.q2 = N[2];
-        if constexpr (W == 8) { nd.q3 = N[3]; nd.q4 = N[4]; }
-        return nd;
-    }
-    static __device__ __forceinline__ Node loadUniform(const float4* nodes, int ref)
-    {
-        ConstQuadPtr C = (ConstQuadPtr)(reinterpret_cast<uintptr_t>(at(nodes, static_cast<uint32_t>(ref) >> 3)));
-        Node nd;
-        nd.q0 = quadOf(C[0]); nd.q1 = quadOf(C[1]); nd.q2 = quadOf(C[2]);
-        if constexpr (W == 8) { nd.q3 = quadOf(C[3]); nd.q4 = quadOf(C[4]); }
-        return nd;
-    }
-    static __device__ __forceinline__ void leafRange(int c, uint32_t& first, uint32_t& cnt)
-    {
-        first = static_cast<uint32_t>(c) >> 3;
-        cnt = static_cast<uint32_t>(c) & 7u;
-    }
-    static __device__ __forceinline__ uint32_t triId(uint32_t first, uint32_t i) { return first + i * F::kTriGranules; }
-    static __device__ __forceinline__ const float4* triPtr(const float4* __restrict__ tris, uint32_t id) { return at(tris, id); }
-    // shading / uv record of a hit: input order, by the gid the triangle record carries
-    static __device__ __forceinline__ uint32_t shadeIndex(uint32_t, uint32_t gid) { return gid; }
-
-    template <int OCT>
-    static __device__ __forceinline__ void slab(const Node& nd, const Ray& r, float tmin, float tcull, float tn[W], bool hit[W])
-    {
-        const uint32_t sc = __float_as_uint(nd.q1.x);
-        const float sx = __uint_as_float((sc & 0x3FFu) << 21), sy = __uint_as_float(((sc >> 10) & 0x3FFu) << 21), sz = __uint_as_float(sc & 0x7FE00000u);
-        const float ax = sx * r.idir.x, ay = sy * r.idir.y, az = sz * r.idir.z;
-        const float bx = fmaf(nd.q0.x, r.idir.x, r.noid.x), by = fmaf(nd.q0.y, r.idir.y, r.noid.y), bz = fmaf(nd.q0.z, r.idir.z, r.noid.z);
-        if constexpr (W == 4) {
-            const uint32_t lx = __float_as_uint(nd.q1.z), hx = __float_as_uint(nd.q1.w), ly = __float_as_uint(nd.q2.x), hy = __float_as_uint(nd.q2.y),
-                           lz = __float_as_uint(nd.q2.z), hz = __float_as_uint(nd.q2.w);
-#pragma unroll
-            for (int j = 0; j < 2; j++) slabPair<OCT>(lx, hx, ly, hy, lz, hz, j, r, ax, ay, az, bx, by, bz, tmin, tcull, tn + 2 * j, hit + 2 * j);
-        } else {
-#pragma unroll
-            for (int half = 0; half < 2; half++) {
-                const uint32_t lx = __float_as_uint(half ? nd.q2.y : nd.q2.x), hx = __float_as_uint(half ? nd.q2.w : nd.q2.z);
-                const uint32_t ly = __float_as_uint(half ? nd.q3.y : nd.q3.x), hy = __float_as_uint(half ? nd.q3.w : nd.q3.z);
-                const uint32_t lz = __float_as_uint(half ? nd.q4.y : nd.q4.x), hz = __float_as_uint(half ? nd.q4.w : nd.q4.z);
-#pragma unroll
-                for (int j = 0; j < 2; j++)
-                    slabPair<OCT>(lx, hx, ly, hy, lz, hz, j, r, ax, ay, az, bx, by, bz, tmin, tcull, tn + 4 * half + 2 * j, hit + 4 * half + 2 * j);
-            }
-        }
-    }
-    // the child designators m_k = (offset << 3) | kind, each in the low bits of a register (upper bits: whatever follows)
-    static __device__ __forceinline__ void designators(const Node& nd, uint32_t m[W])
-    {
-        if constexpr (W == 4) {
-            const uint32_t w = __float_as_uint(nd.q1.y);
-            m[0] = w; m[1] = w >> 8; m[2] = w >> 16; m[3] = w >> 24;
-        } else {
-            const uint32_t a = __float_as_uint(nd.q1.y), b = __float_as_uint(nd.q1.z), c = __float_as_uint(nd.q1.w);
-            m[0] = a; m[1] = a >> 10; m[2] = a >> 20; m[3] = b; m[4] = b >> 10; m[5] = b >> 20; m[6] = c; m[7] = c >> 10;
-        }
-    }
-
-    // closest hit: visit the hit children nearest first.  Order key = (bits(t_near) & ~payload) | m_k: t_near >= 0 so its bit
-    // pattern orders like the float; the low bits hold the child's designator, which makes keys unique AND is all a push
-    // needs: reference = base8 + (key & payload) -- the ordering network carries the children, nothing is looked up by slot
-    // afterwards.  Misses get 0xFFFFFFFF.  EARLY: see LayLegacy::closestStep.
-    template <bool COUNT, int OCT, bool EARLY>
-    static __device__ __forceinline__ void closestStep(const Node& nd, const Ray& r, float tmin, float tcull, Stack& stack,
-                                                       int& cur, uint32_t& cntNodes, const float4* __restrict__ nodes, Node& ndNext)
-    {
-        if (COUNT) cntNodes++;
-        float tn[W];
-        bool hit[W];
-        slab<OCT>(nd, r, tmin, tcull, tn, hit);
-        uint32_t m[W], key[W];
-        designators(nd, m);
-#pragma unroll
-        for (int k = 0; k < W; k++)
-            key[k] = hit[k] ? ((__float_as_uint(tn[k]) & ~kPayload) | (m[k] & kPayload)) : 0xFFFFFFFFu;
-        uint32_t nearest = min(min(key[0], key[1]), min(key[2], key[3]));
-        if constexpr (W == 8) nearest = min(nearest, min(min(key[4], key[5]), min(key[6], key[7])));
-        const bool any = nearest != 0xFFFFFFFFu;
-        const uint32_t base8 = __float_as_uint(nd.q0.w);
-        cur = any ? static_cast<int>(base8 + (nearest & kPayload)) : (stack.sp == 0 ? kDone : stack.pop()); // a lane pops or pushes, never both
-        if (EARLY) {
-            if (inner(cur)) ndNext = load(nodes, cur);
-        }
-#define CRT_CSWAP(a, b) { const uint32_t lo = min(key[a], key[b]), hi = max(key[a], key[b]); key[a] = lo; key[b] = hi; }
-        if constexpr (W == 4) {
-            CRT_CSWAP(0, 1) CRT_CSWAP(2, 3) CRT_CSWAP(0, 2) CRT_CSWAP(1, 3) CRT_CSWAP(1, 2)
-            if (key[1] != 0xFFFFFFFFu) {
-                if (key[3] != 0xFFFFFFFFu) stack.push(static_cast<int>(base8 + (key[3] & kPayload))); // farthest first: the nearest pending child pops first
-                if (key[2] != 0xFFFFFFFFu) stack.push(static_cast<int>(base8 + (key[2] & kPayload)));
-                stack.push(static_cast<int>(base8 + (key[1] & kPayload)));
-            }
-        } else {
-            // Batcher's odd-even merge sort for eight keys: 19 compare-exchanges
-            CRT_CSWAP(0, 1) CRT_CSWAP(2, 3) CRT_CSWAP(4, 5) CRT_CSWAP(6, 7)
-            CRT_CSWAP(0, 2) CRT_CSWAP(1, 3) CRT_CSWAP(4, 6) CRT_CSWAP(5, 7)
-            CRT_CSWAP(1, 2) CRT_CSWAP(5, 6)
-            CRT_CSWAP(0, 4) CRT_CSWAP(1, 5) CRT_CSWAP(2, 6) CRT_CSWAP(3, 7)
-            CRT_CSWAP(2, 4) CRT_CSWAP(3, 5)
-            CRT_CSWAP(1, 2) CRT_CSWAP(3, 4) CRT_CSWAP(5, 6)
-            if (key[1] != 0xFFFFFFFFu) {
-                if (key[2] != 0xFFFFFFFFu) {
-                    if (key[3] != 0xFFFFFFFFu) {
-                        if (key[4] != 0xFFFFFFFFu) {
-                            if (key[7] != 0xFFFFFFFFu) stack.push(static_cast<int>(base8 + (key[7] & kPayload)));
-                            if (key[6] != 0xFFFFFFFFu) stack.push(static_cast<int>(base8 + (key[6] & kPayload)));
-                            if (key[5] != 0xFFFFFFFFu) stack.push(static_cast<int>(base8 + (key[5] & kPayload)));
-                            stack.push(static_cast<int>(base8 + (key[4] & kPayload)));
-                        }
-                        stack.push(static_cast<int>(base8 + (key[3] & kPayload)));
-                    }
-                    stack.push(static_cast<int>(base8 + (key[2] & kPayload)));
-                }
-                stack.push(static_cast<int>(base8 + (key[1] & kPayload)));
-            }
-        }
-#undef CRT_CSWAP
-    }
-
-    // any hit: order independent, children taken in slot order: the first hit slot becomes current, later hit slots are
-    // pushed, last slot first
-    template <bool COUNT, int OCT, bool EARLY>
-    static __device__ __forceinline__ void anyStep(const Node& nd, const Ray& r, float tmin, float tcull, Stack& stack,
-                                                   int& cur, uint32_t& cntNodes, const float4* __restrict__ nodes, Node& ndNext)
-    {
-        if (COUNT) cntNodes++;
-        float tn[W];
-        bool hit[W];
-        slab<OCT>(nd, r, tmin, tcull, tn, hit);
-        uint32_t m[W];
-        designators(nd, m);
-        const uint32_t base8 = __float_as_uint(nd.q0.w);
-        uint32_t first = 0;
-        bool any = false;
-#pragma unroll
-        for (int k = W - 1; k >= 0; k--) {
-            first = hit[k] ? m[k] : first;
-            any |= hit[k];
-        }
-        cur = any ? static_cast<int>(base8 + (first & kPayload)) : (stack.sp == 0 ? kDone : stack.pop());
-        if (EARLY) {
-            if (inner(cur)) ndNext = load(nodes, cur);
-        }
-        bool before[W]; // some slot below k was hit
-        before[0] = false;
-#pragma unroll
-        for (int k = 1; k < W; k++) before[k] = before[k - 1] | hit[k - 1];
-#pragma unroll
-        for (int k = W - 1; k >= 1; k--)
-            if (hit[k] & before[k]) stack.push(static_cast<int>(base8 + (m[k] & kPayload)));
-    }
-};
-
-#endif // CRT_PACKED_LAYOUTS
-
-// The record of a scalar-path step: with the plane table (DEC, layouts with kPlaneTable) and a known octant its planes come
+// The record of a scalar-path step: with the plane table (DEC) and a known octant its planes come
 // decoded (LayLegacy::NodeU), otherwise it is the plain record.  Per-lane steps always fetch the plain 64-byte record: a
 // second fetch per lane costs more than the conversions it would save (section 5 of DESIGN.md).
 template <class L, int OCT, bool DEC>

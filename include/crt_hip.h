@@ -269,7 +269,7 @@ int crt_bvh_info4(const crt_ctx* ctx, uint32_t* n_nodes4, uint32_t* depth4);
 int crt_bvh_export4(const crt_ctx* ctx, crt_bvh_node4* nodes4);
 /* the same nodes in the 64-byte quantised form the kernels fetch (count = n_nodes4) */
 int crt_bvh_export4q(const crt_ctx* ctx, crt_bvh_node4q* nodes4q);
-/* the decoded plane table beside those nodes (legacy layout only; CRT_ESTATE for the packed ones): n_nodes4 rows of 32 floats,
+/* the decoded plane table beside those nodes: n_nodes4 rows of 32 floats,
  * row i = float(q) of plane byte k of node i (qlo_x .. qhi_z, child j = byte j of each word) for k < 24, then 8 zeros.  The
  * kernels' node steps read it when a whole wavefront stands on one node. */
 int crt_bvh_export_planes4q(const crt_ctx* ctx, float* planes);
@@ -340,8 +340,7 @@ int crt_accumulated_samples(const crt_ctx* ctx, uint32_t* samples); /* samples p
  *   and a ray starting on a surface whose own hit is at t ~ tmin.  Such a ray may then report a miss, or a farther hit,
  *   although a triangle lies in (tmin, tmax); the result is still the oracle's traversal of the same tree, but it can differ
  *   between the host SAH tree and the gpu_build tree.  Every other ray gives the same result over either tree.
- * - Layout: queries traverse the default 64-byte 4-wide tree.  With the experimental packed layouts (option bvh_width 4 / 8,
- *   diagnostic builds only) every query returns CRT_EINVAL.
+ * - Layout: queries traverse the 64-byte 4-wide tree the frames traverse.
  * - A query needs an uploaded scene (CRT_ESTATE otherwise).  It reads the tree, the triangles and the options inner_min /
  *   inner_min_any, nothing else: camera, mode, accumulation sums, launch-order state and frame outputs are untouched, and a frame
  *   rendered after any number of queries equals the frame rendered without them (accumulating mode-200 runs included).

@@ -399,6 +399,8 @@ def test_scheduling_knobs_never_change_results(pkg, oracle, scenes, dragon, rend
     speed knobs only: every setting must give the oracle's frame bit for bit (and the same fetch counters)."""
     sc = _with_normals(scenes, dragon)
     cam = sc["camera"]
+    # bvh_width 0 names the one tree layout there is: accepted, and the upload and frames below are the oracle's
+    assert pkg.lib().crt_set_option(renderer.h, b"bvh_width", 0) == 0  # CRT_OK
     renderer.upload(sc["meshes"], sc["lights"], sc["materials"])
     renderer.set_camera(cam["position"], cam["matrix"])
     renderer.change_shading_mode(100)
@@ -432,6 +434,8 @@ def test_scheduling_knobs_never_change_results(pkg, oracle, scenes, dragon, rend
             renderer.set_option("no_such_option", 1)
         with pytest.raises(pkg.CrtError):
             renderer.set_option("stack_entries", 33)
+        for width in (4, 8):  # no other tree layout exists
+            assert pkg.lib().crt_set_option(renderer.h, b"bvh_width", width) == 1  # CRT_EINVAL
     finally:
         renderer.set_counting(False)
         for name, v in defaults.items():

@@ -31,6 +31,6 @@ for pass in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_REQ_sum" \
   i=$((i+1))
   # each pass under its own timeout: a profiler that aborts (error 38: a group one pass cannot collect) can leave its finaliser
   # stuck, which must cost seconds, not the rest of the call
-  timeout -k 5 240 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $OUT/pmc_$i -- $B --steps $PSTEPS --warmup 2 > $OUT/bench_pmc_$i.log 2>&1 || echo "pmc pass $i FAILED ($pass): see $OUT/bench_pmc_$i.log"
+  timeout -k 5 240 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $OUT/pmc_$i -- $B --steps $PSTEPS --warmup 2 > $OUT/bench_pmc_$i.log 2>&1 || { echo "pmc pass $i FAILED ($pass): see $OUT/bench_pmc_$i.log"; exit 1; }
   echo "pmc pass $i done ($pass)"
 done
