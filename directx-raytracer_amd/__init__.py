@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "crt_scene_camera_roll", "crt_scene_camera_pan_around_target", "crt_upload_scene_from", "crt_set_camera_from",
     "crt_set_accumulation", "crt_reset_accumulation", "crt_accumulated_samples",
     "crt_trace_rays_device", "crt_occluded_rays_device", "crt_trace_rays", "crt_occluded_rays",
+    "crt_update_vertices", "crt_update_vertices_device", "crt_set_mesh_transform", "crt_refit", "crt_mesh_vertices",
 ]
 
 
@@ -200,6 +201,11 @@ def lib():
         "crt_occluded_rays_device": (C.c_int, [vp, u32, vp, vp, vp]),
         "crt_trace_rays": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp]),
         "crt_occluded_rays": (C.c_int, [vp, u32, vp, vp, vp]),
+        "crt_update_vertices": (C.c_int, [vp, u32, u32, vp, vp]),
+        "crt_update_vertices_device": (C.c_int, [vp, u32, u32, vp, vp]),
+        "crt_set_mesh_transform": (C.c_int, [vp, u32, vp]),
+        "crt_refit": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "crt_mesh_vertices": (C.c_int, [vp, u32, vp, vp]),
     }
     assert set(sig) == set(ABI_SYMBOLS)
     for name, (res, args) in sig.items():
@@ -565,7 +571,9 @@ class Renderer:
         self._ok(lib().crt_bvh_export_uv(self.h, uv.ctypes.data, C.byref(has)), "crt_bvh_export_uv")
         return uv if has.value else None
 
-    def upload(self, meshes, lights=(), materials=(), textures=None):
+    def upload(self, meshes, lights=(), materials=(), textures=None, dynamic=False):
+        """dynamic=True keeps what update_vertices / set_mesh_transform / refit need (include/crt_hip.h, dynamic geometry)"""
+        self.set_option("dynamic", int(bool(dynamic)))
         keep = []
         mv = _mesh_views(meshes, keep)
         larr = (Light * max(1, len(lights)))()
@@ -580,10 +588,72 @@ class Renderer:
             marr[i].ior = float(m.get("ior", 1.0))
             marr[i].texture = int(m.get("texture", -1))
         self._ok(lib().crt_upload_scene(self.h, mv, len(meshes), larr, len(lights), marr, len(materials)), "crt_upload_scene")
+        self._mesh_shapes = [(int(mv[i].n_vertices), bool(mv[i].normals)) for i in range(len(meshes))]
         self.set_textures(list(textures) if textures else [])
 
-    def upload_scene(self, scene):
+    def upload_scene(self, scene, dynamic=False):
+        self.set_option("dynamic", int(bool(dynamic)))
         self._ok(lib().crt_upload_scene_from(self.h, scene.h), "crt_upload_scene_from")
+        shapes = []
+        for i in range(scene.mesh_count):
+            mv = MeshView()
+            self._ok(lib().crt_scene_mesh(scene.h, i, C.byref(mv)), "crt_scene_mesh")
+            shapes.append((int(mv.n_vertices), bool(mv.normals)))
+        self._mesh_shapes = shapes
+
+    # ---- dynamic geometry (include/crt_hip.h): scenes uploaded with dynamic=True
+    def update_vertices(self, mesh, xyz, normals=None):
+        """new rest vertices (and normals) of a mesh: numpy arrays (host), or contiguous float32 torch tensors on the GPU (device
+        form; made ready on the current stream first).  Applied by the next refit."""
+        try:
+            import torch
+            on_device = isinstance(xyz, torch.Tensor) and xyz.is_cuda
+        except ImportError:
+            on_device = False
+        if on_device:
+            for a in (xyz, normals):
+                if a is not None and (a.dtype != torch.float32 or not a.is_contiguous() or not a.is_cuda or a.numel() % 3):
+                    raise ValueError("update_vertices: device arrays must be contiguous float32 CUDA tensors of n x 3 floats")
+            torch.cuda.current_stream().synchronize()
+            self._ok(lib().crt_update_vertices_device(self.h, int(mesh), xyz.numel() // 3, xyz.data_ptr(),
+                                                      normals.data_ptr() if normals is not None else None), "crt_update_vertices_device")
+            return
+        v = _f32(xyz).reshape(-1, 3)
+        n = _f32(normals).reshape(-1, 3) if normals is not None else None
+        self._ok(lib().crt_update_vertices(self.h, int(mesh), len(v), v.ctypes.data, n.ctypes.data if n is not None else None),
+                 "crt_update_vertices")
+
+    def set_mesh_transform(self, mesh, m):
+        """m: 3x4 row-major, or 4x4 whose last row is 0 0 0 1; None = identity"""
+        if m is None:
+            self._ok(lib().crt_set_mesh_transform(self.h, int(mesh), None), "crt_set_mesh_transform")
+            return
+        a = np.asarray(m, dtype=np.float32)
+        if a.shape == (4, 4):
+            if not np.array_equal(a[3], np.float32([0, 0, 0, 1])):
+                raise ValueError("set_mesh_transform: a 4x4 matrix must end in the row 0 0 0 1")
+            a = a[:3]
+        if a.shape != (3, 4):
+            raise ValueError("set_mesh_transform: 3x4 or 4x4 matrix expected, got %s" % (a.shape,))
+        a = np.ascontiguousarray(a)
+        self._ok(lib().crt_set_mesh_transform(self.h, int(mesh), a.ctypes.data), "crt_set_mesh_transform")
+
+    def refit(self):
+        """apply pending updates now; returns the refit's device time in ms (0 when nothing was pending)"""
+        ms = C.c_double()
+        self._ok(lib().crt_refit(self.h, C.byref(ms)), "crt_refit")
+        return ms.value
+
+    def mesh_vertices(self, mesh):
+        """(xyz, normals or None): world-space vertices of a mesh as they are traced, float32 (n, 3)"""
+        shapes = getattr(self, "_mesh_shapes", [])
+        if not 0 <= int(mesh) < len(shapes):
+            raise CrtError("mesh_vertices: mesh %d out of range" % int(mesh))
+        nv, has_n = shapes[int(mesh)]
+        xyz = np.zeros((nv, 3), dtype=np.float32)
+        nrm = np.zeros((nv, 3), dtype=np.float32) if has_n else None
+        self._ok(lib().crt_mesh_vertices(self.h, int(mesh), xyz.ctypes.data, nrm.ctypes.data if has_n else None), "crt_mesh_vertices")
+        return xyz, nrm
 
     def set_camera(self, pos, rot):
         p, r = _f32(pos, 3), _f32(rot, 9)

@@ -5,6 +5,7 @@
 
 #include "../../include/crt_hip.h"
 
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -52,6 +53,10 @@ void flattenUvs(const crt_mesh_view* meshes, uint32_t n_meshes, std::vector<crt_
 void reorderUvs(const std::vector<crt_bvh_uv>& inUv, Bvh& bvh);
 // binary -> wide collapse (DESIGN.md "BVH4"); called by both builders
 void collapseBvh4(Bvh& bvh);
+// the same collapse + quantisation on the device (bvh_gpu.hip), shared by the GPU builder and the refit of a dynamic scene
+size_t collapseScratchBytes(uint32_t nBinary);
+void collapseWideGpu(const crt_bvh_node* nodes, uint32_t nBinary, void* scratch, void** nodes4, void** nodes4q, struct ihipStream_t* stream,
+                     uint32_t* nWide, uint32_t* depth4, uint32_t* maxDepth);
 // (the collapse and quantisation rules themselves: bvh_wide.h, shared with the GPU builder)
 
 } // namespace crt

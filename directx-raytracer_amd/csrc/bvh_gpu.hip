@@ -12,6 +12,7 @@
 // option (option "gpu_build": 8.7 ms against 360 ms at 1M triangles), not the default.
 #include "bvh_build.h"
 #include "bvh_wide.h"
+#include "mesh_table.hip.h"
 #include "render_kernels.h"
 
 #include <hip/hip_runtime.h>
@@ -229,23 +230,6 @@ __global__ __launch_bounds__(256) void emitKernel(const KNode* __restrict__ K, c
     out[rank[i]] = N;
 }
 
-// One entry per mesh (plus a terminator holding the totals): where its triangles and vertices start in the concatenated arrays
-struct MeshEntry {
-    uint32_t triStart, vertStart, nVerts, material;
-    uint32_t hasNormals, hasUvs, pad0, pad1;
-};
-
-__device__ __forceinline__ uint32_t meshOf(const MeshEntry* __restrict__ table, uint32_t n_meshes, uint32_t g)
-{
-    uint32_t lo = 0, hi = n_meshes; // largest m with triStart[m] <= g (meshes without triangles are skipped by the <=)
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (table[mid].triStart <= g) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ float minSel(float a, float b) { return a < b ? a : b; }
 __device__ __forceinline__ float maxSel(float a, float b) { return a > b ? a : b; }
 
@@ -444,6 +428,73 @@ struct DevBuf {
 
 } // namespace
 
+size_t collapseScratchBytes(uint32_t nBinary)
+{
+    const size_t n = nBinary ? nBinary : 1u;
+    return sizeof(WideTmp) * n + sizeof(uint32_t) * (2 * n + 4 * n + 4); // tmp, size + id, two frontiers, scalars
+}
+
+// Binary -> 4-wide collapse + quantisation of the nBinary nodes at `nodes` (the rules: bvh_wide.h).  Scratch: collapseScratchBytes.
+// *nodes4 / *nodes4q: buffers of at least nBinary records (a wide node absorbs one binary node at least), or NULL: then buffers of
+// exactly the wide node count (+128 bytes of slack behind the quantised ones) are allocated here and handed to the caller.
+// Synchronises the stream once per wide level (the next level's count decides the next launch).
+void collapseWideGpu(const crt_bvh_node* nodes, uint32_t nBinary, void* scratch, void** nodes4, void** nodes4q, ihipStream_t* stream,
+                     uint32_t* nWideOut, uint32_t* depth4Out, uint32_t* maxDepthOut)
+{
+    const size_t n = nBinary ? nBinary : 1u;
+    WideTmp* dTmp = static_cast<WideTmp*>(scratch);
+    uint32_t* dSize = reinterpret_cast<uint32_t*>(dTmp + n);
+    uint32_t* dId = dSize + n;
+    uint32_t* dFrontA = dId + n;
+    uint32_t* dFrontB = dFrontA + 2 * n;
+    uint32_t* dScalars = dFrontB + 2 * n; // [0] next count, [1] max depth
+    const dim3 blk(256);
+    std::vector<std::pair<uint32_t, uint32_t>> levels; // {first temporary index, count}
+    {
+        const uint32_t rootEntry[2] = { 0u, 0u };
+        GPU_TRY(hipMemcpyAsync(dFrontA, rootEntry, sizeof(rootEntry), hipMemcpyHostToDevice, stream));
+        GPU_TRY(hipMemsetAsync(dScalars, 0, sizeof(uint32_t) * 2, stream));
+        uint32_t base = 0, count = 1;
+        uint32_t* cur = dFrontA;
+        uint32_t* nxt = dFrontB;
+        while (count) {
+            if (static_cast<uint64_t>(base) + count > nBinary) throw std::runtime_error("wide collapse: more wide nodes than binary nodes");
+            levels.emplace_back(base, count);
+            GPU_TRY(hipMemsetAsync(dScalars, 0, sizeof(uint32_t), stream));
+            hipLaunchKernelGGL(wideExpandKernel, dim3((count + 255) / 256), blk, 0, stream, nodes, cur, count, base, base + count, dTmp, nxt,
+                               dScalars, dScalars + 1);
+            GPU_TRY(hipGetLastError());
+            uint32_t nextCount = 0;
+            GPU_TRY(hipMemcpyAsync(&nextCount, dScalars, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            GPU_TRY(hipStreamSynchronize(stream));
+            base += count;
+            count = nextCount;
+            std::swap(cur, nxt);
+        }
+    }
+    const uint32_t nWide = levels.back().first + levels.back().second;
+    for (size_t L = levels.size(); L-- > 0;)
+        hipLaunchKernelGGL(wideSizeKernel, dim3((levels[L].second + 255) / 256), blk, 0, stream, dTmp, levels[L].first, levels[L].second, dSize);
+    GPU_TRY(hipMemsetAsync(dId, 0, sizeof(uint32_t), stream)); // the root's id
+    for (size_t L = 0; L < levels.size(); L++)
+        hipLaunchKernelGGL(wideIdKernel, dim3((levels[L].second + 255) / 256), blk, 0, stream, dTmp, levels[L].first, levels[L].second, dSize, dId);
+    GPU_TRY(hipGetLastError());
+    if (!*nodes4) {
+        DevBuf a(sizeof(crt_bvh_node4) * nWide), b(sizeof(crt_bvh_node4q) * nWide + 128);
+        *nodes4 = a.release();
+        *nodes4q = b.release();
+    }
+    hipLaunchKernelGGL(wideEmitKernel, dim3((nWide + 255) / 256), blk, 0, stream, dTmp, nWide, dId, static_cast<crt_bvh_node4*>(*nodes4),
+                       static_cast<crt_bvh_node4q*>(*nodes4q));
+    GPU_TRY(hipGetLastError());
+    uint32_t maxDepth = 0;
+    GPU_TRY(hipMemcpyAsync(&maxDepth, dScalars + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    GPU_TRY(hipStreamSynchronize(stream));
+    *nWideOut = nWide;
+    *depth4Out = static_cast<uint32_t>(levels.size());
+    if (maxDepthOut) *maxDepthOut = maxDepth;
+}
+
 void buildBvhGpu(const crt_mesh_view* meshes, uint32_t n_meshes, Bvh& out, ihipStream_t* stream, double* device_ms)
 {
     const bool timing = std::getenv("CRT_BUILD_TIMING") != nullptr;
@@ -634,44 +685,11 @@ void buildBvhGpu(const crt_mesh_view* meshes, uint32_t n_meshes, Bvh& out, ihipS
     if (timing) { GPU_TRY(hipStreamSynchronize(stream)); }
     lap("device build");
     // ---- collapse to the 4-wide tree and quantise, still on the device
-    DevBuf dTmp(sizeof(WideTmp) * nKept), dSize(sizeof(uint32_t) * nKept), dId(sizeof(uint32_t) * nKept);
-    DevBuf dFrontA(sizeof(uint32_t) * 2 * nKept), dFrontB(sizeof(uint32_t) * 2 * nKept), dScalars(sizeof(uint32_t) * 2); // [0] next count, [1] max depth
-    std::vector<std::pair<uint32_t, uint32_t>> levels; // {first temporary index, count}
-    {
-        const uint32_t rootEntry[2] = { 0u, 0u };
-        GPU_TRY(hipMemcpyAsync(dFrontA.p, rootEntry, sizeof(rootEntry), hipMemcpyHostToDevice, stream));
-        GPU_TRY(hipMemsetAsync(dScalars.p, 0, sizeof(uint32_t) * 2, stream));
-        uint32_t base = 0, count = 1;
-        uint32_t* cur = dFrontA.as<uint32_t>();
-        uint32_t* nxt = dFrontB.as<uint32_t>();
-        while (count) {
-            if (static_cast<uint64_t>(base) + count > nKept) throw std::runtime_error("wide collapse: more wide nodes than binary nodes");
-            levels.emplace_back(base, count);
-            GPU_TRY(hipMemsetAsync(dScalars.p, 0, sizeof(uint32_t), stream));
-            hipLaunchKernelGGL(wideExpandKernel, dim3((count + 255) / 256), blk, 0, stream, dNodes.as<crt_bvh_node>(), cur, count, base, base + count,
-                               dTmp.as<WideTmp>(), nxt, dScalars.as<uint32_t>(), dScalars.as<uint32_t>() + 1);
-            GPU_TRY(hipGetLastError());
-            uint32_t nextCount = 0;
-            GPU_TRY(hipMemcpyAsync(&nextCount, dScalars.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            GPU_TRY(hipStreamSynchronize(stream));
-            base += count;
-            count = nextCount;
-            std::swap(cur, nxt);
-        }
-    }
-    const uint32_t nWide = levels.back().first + levels.back().second;
-    for (size_t L = levels.size(); L-- > 0;)
-        hipLaunchKernelGGL(wideSizeKernel, dim3((levels[L].second + 255) / 256), blk, 0, stream, dTmp.as<WideTmp>(), levels[L].first, levels[L].second, dSize.as<uint32_t>());
-    GPU_TRY(hipMemsetAsync(dId.p, 0, sizeof(uint32_t), stream)); // the root's id
-    for (size_t L = 0; L < levels.size(); L++)
-        hipLaunchKernelGGL(wideIdKernel, dim3((levels[L].second + 255) / 256), blk, 0, stream, dTmp.as<WideTmp>(), levels[L].first, levels[L].second, dSize.as<uint32_t>(),
-                           dId.as<uint32_t>());
-    DevBuf dNodes4(sizeof(crt_bvh_node4) * nWide), dNodes4q(sizeof(crt_bvh_node4q) * nWide + 128);
-    hipLaunchKernelGGL(wideEmitKernel, dim3((nWide + 255) / 256), blk, 0, stream, dTmp.as<WideTmp>(), nWide, dId.as<uint32_t>(), dNodes4.as<crt_bvh_node4>(),
-                       dNodes4q.as<crt_bvh_node4q>());
-    GPU_TRY(hipGetLastError());
-    uint32_t maxDepth = 0;
-    GPU_TRY(hipMemcpyAsync(&maxDepth, dScalars.as<uint32_t>() + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    DevBuf dScratch(collapseScratchBytes(nKept));
+    uint32_t nWide = 0, depth4 = 0, maxDepth = 0;
+    void* wide[2] = { nullptr, nullptr }; // allocated by the collapse at their exact size
+    struct Owned { void** p; ~Owned() { for (int i = 0; i < 2; i++) if (p[i]) (void)hipFree(p[i]); } } owned{ wide };
+    collapseWideGpu(dNodes.as<crt_bvh_node>(), nKept, dScratch.p, &wide[0], &wide[1], stream, &nWide, &depth4, &maxDepth);
     GPU_TRY(hipEventRecord(e1, stream));
     GPU_TRY(hipStreamSynchronize(stream));
     float ms = 0.f;
@@ -679,12 +697,13 @@ void buildBvhGpu(const crt_mesh_view* meshes, uint32_t n_meshes, Bvh& out, ihipS
     if (device_ms) *device_ms = ms;
     lap("device collapse + quantise");
     out.maxDepth = maxDepth;
-    out.depth4 = static_cast<uint32_t>(levels.size());
+    out.depth4 = depth4;
     out.nNodes = nKept;
     out.nNodes4 = nWide;
     out.devNodes = dNodes.release();
-    out.devNodes4 = dNodes4.release();
-    out.devNodes4q = dNodes4q.release();
+    out.devNodes4 = wide[0];
+    out.devNodes4q = wide[1];
+    wide[0] = wide[1] = nullptr;
     // the leaf-ordered records stay in HBM: the caller adopts the buffers (and copies them out only if someone asks)
     out.nTris = n;
     out.devTris = dTris.release();

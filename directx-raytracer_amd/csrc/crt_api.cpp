@@ -6,6 +6,7 @@
 
 #include "bvh_build.h"
 #include "bvh_wide.h"
+#include "refit.h"
 #include "render_kernels.h"
 #include "scene.h"
 
@@ -22,6 +23,7 @@
 #include <atomic>
 #include <cerrno>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -76,6 +78,10 @@ struct crt_ctx {
     double buildMs = 0.0;       // wall time of the last crt_upload_scene (build + upload)
     double buildDeviceMs = 0.0; // of which GPU kernels (gpu_build only)
     uint32_t sceneSerial = 0;
+    // option "dynamic": the next upload keeps what a refit needs (refit.h); dyn = that state for the current scene, else NULL.
+    // A dynamic scene's tree and records exist in HBM only: the host copies in bvh are dropped and the exports read the device.
+    bool dynamicOpt = false;
+    crt::DynamicScene* dyn = nullptr;
     float sceneLo[3] = { 0.f, 0.f, 0.f }, sceneHi[3] = { 0.f, 0.f, 0.f }; // box of the tree's root: where split rays are cut into segments
 
     float pos[3] = { 0.f, 0.f, 0.f };
@@ -240,7 +246,107 @@ void freeScene(crt_ctx* c)
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
+    delete c->dyn;
+    c->dyn = nullptr;
     c->haveScene = false;
+}
+
+// the root record as it sits in HBM: where split rays are cut into segments
+int readSceneBox(crt_ctx* c)
+{
+    for (int a = 0; a < 3; a++) c->sceneLo[a] = c->sceneHi[a] = 0.0f;
+    if (c->bvh.nNodes4 > 0) {
+        crt_bvh_node4q root;
+        HIP_TRY(c, hipMemcpy(&root, c->dNodes, sizeof(root), hipMemcpyDeviceToHost));
+        for (int a = 0; a < 3; a++) {
+            c->sceneLo[a] = root.lo[a];
+            c->sceneHi[a] = crt::decodePlane(255u, root.s[a], root.lo[a]);
+        }
+    }
+    return CRT_OK;
+}
+
+// a device buffer of `used` valid bytes moved into one of `bytes` (>= used)
+int regrow(crt_ctx* c, void*& p, size_t used, size_t bytes)
+{
+    void* q = nullptr;
+    HIP_TRY(c, hipMalloc(&q, bytes));
+    if (p && used) {
+        const hipError_t e = hipMemcpy(q, p, used, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(q);
+            return fail(c, CRT_EHIP, "hipMemcpy failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (p) (void)hipFree(p);
+    p = q;
+    return CRT_OK;
+}
+
+// Upload with option "dynamic": the binary tree goes to (or stays in) HBM, the wide tree, its quantised form and the plane table get
+// room for one node per binary inner node (a refit may collapse to more wide nodes than the build did), and the meshes are kept.
+int setupDynamic(crt_ctx* c, const crt_mesh_view* meshes, uint32_t n_meshes)
+{
+    const uint32_t nBin = c->bvh.nNodes, cap = nBin ? nBin : 1u, n4 = c->bvh.nNodes4;
+    const bool hostTree = !c->dBinNodes;
+    if (hostTree) {
+        HIP_TRY(c, hipMalloc(&c->dBinNodes, sizeof(crt_bvh_node) * cap));
+        if (nBin) HIP_TRY(c, hipMemcpy(c->dBinNodes, c->bvh.nodes.data(), sizeof(crt_bvh_node) * nBin, hipMemcpyHostToDevice));
+    }
+    if (!c->dWideNodes) {
+        HIP_TRY(c, hipMalloc(&c->dWideNodes, sizeof(crt_bvh_node4) * cap));
+        if (n4) HIP_TRY(c, hipMemcpy(c->dWideNodes, c->bvh.nodes4.data(), sizeof(crt_bvh_node4) * n4, hipMemcpyHostToDevice));
+    } else if (int rc = regrow(c, c->dWideNodes, sizeof(crt_bvh_node4) * n4, sizeof(crt_bvh_node4) * cap)) {
+        return rc;
+    }
+    if (int rc = regrow(c, c->dNodes, sizeof(crt_bvh_node4q) * n4, sizeof(crt_bvh_node4q) * cap + 128)) return rc;
+    if (int rc = regrow(c, c->dPlanes, sizeof(float) * crt::kPlaneStride * n4, sizeof(float) * crt::kPlaneStride * cap)) return rc;
+    c->dyn = new (std::nothrow) crt::DynamicScene();
+    if (!c->dyn) return fail(c, CRT_ENOMEM, "out of host memory");
+    try {
+        crt::dynamicInit(*c->dyn, meshes, n_meshes, hostTree ? c->bvh.nodes.data() : nullptr, static_cast<const crt_bvh_node*>(c->dBinNodes), nBin,
+                         c->stream);
+    } catch (const std::bad_alloc&) {
+        return fail(c, CRT_ENOMEM, "out of host memory while keeping the dynamic scene");
+    } catch (const std::exception& ex) {
+        return fail(c, CRT_EHIP, "dynamic scene: %s", ex.what());
+    }
+    std::vector<crt_bvh_node>().swap(c->bvh.nodes);
+    std::vector<crt_bvh_node4>().swap(c->bvh.nodes4);
+    std::vector<crt_bvh_node4q>().swap(c->bvh.nodes4q);
+    std::vector<crt_bvh_tri>().swap(c->bvh.tris);
+    std::vector<crt_bvh_shade>().swap(c->bvh.shade);
+    return CRT_OK;
+}
+
+// Apply the pending updates of a dynamic scene (crt_update_vertices*, crt_set_mesh_transform) before anything reads the tree or the
+// records.  A refit changes the scene as a re-upload does: new sceneSerial (accumulated sums and launch orders are stale), new root
+// box, and the wide tree's node count and depth may differ.
+int applyRefit(crt_ctx* c, double* device_ms)
+{
+    if (device_ms) *device_ms = 0.0;
+    if (!c->dyn || !c->dyn->pending) return CRT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipDeviceSynchronize()); // frames in flight on any stream the caller used still read the records and the tree
+    crt::RefitTargets t;
+    t.binNodes = static_cast<crt_bvh_node*>(c->dBinNodes);
+    t.tris = static_cast<crt_bvh_tri*>(c->dTris);
+    t.shade = static_cast<crt_bvh_shade*>(c->dShade);
+    t.nodes4 = c->dWideNodes;
+    t.nodes4q = c->dNodes;
+    t.planes = static_cast<float*>(c->dPlanes);
+    uint32_t nWide = 0, depth4 = 0;
+    try {
+        crt::dynamicRefit(*c->dyn, t, c->stream, &nWide, &depth4, device_ms);
+    } catch (const std::exception& ex) {
+        return fail(c, CRT_EHIP, "refit failed: %s", ex.what());
+    }
+    c->bvh.nNodes4 = nWide;
+    c->bvh.depth4 = depth4;
+    if (int rc = readSceneBox(c)) return rc;
+    c->sceneSerial++;
+    for (uint64_t& k : c->orderKey) k = 0;
+    return CRT_OK;
 }
 
 int ensureFrame(crt_ctx* c, int slot, size_t bytes)
@@ -628,7 +734,7 @@ int checkRenderable(crt_ctx* c, uint32_t w, uint32_t h)
     if (!c) return CRT_EINVAL;
     if (!c->haveScene) return fail(c, CRT_ESTATE, "no scene uploaded: call crt_upload_scene first");
     if (w == 0 || h == 0 || w > 65536 || h > 65536) return fail(c, CRT_EINVAL, "bad frame size %ux%u", w, h);
-    return CRT_OK;
+    return applyRefit(c, nullptr);
 }
 
 } // namespace
@@ -845,13 +951,11 @@ int crt_upload_scene(crt_ctx* c, const crt_mesh_view* meshes, uint32_t n_meshes,
     if (n_materials) HIP_TRY(c, hipMemcpy(c->dMats, materials, sizeof(crt_material) * n_materials, hipMemcpyHostToDevice));
     c->nLights = n_lights;
     c->nMats = n_materials;
-    for (int a = 0; a < 3; a++) c->sceneLo[a] = c->sceneHi[a] = 0.0f;
-    if (c->bvh.nNodes4 > 0) { // the root record as it sits in HBM (built here or on the device alike)
-        crt_bvh_node4q root;
-        HIP_TRY(c, hipMemcpy(&root, c->dNodes, sizeof(root), hipMemcpyDeviceToHost));
-        for (int a = 0; a < 3; a++) {
-            c->sceneLo[a] = root.lo[a];
-            c->sceneHi[a] = crt::decodePlane(255u, root.s[a], root.lo[a]);
+    if (int rc = readSceneBox(c)) return rc; // (built here or on the device alike)
+    if (c->dynamicOpt) {
+        if (int rc = setupDynamic(c, meshes, n_meshes)) {
+            freeScene(c);
+            return rc;
         }
     }
     c->buildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
@@ -949,6 +1053,10 @@ int crt_set_option(crt_ctx* c, const char* name, int value)
     if (!c || !name) return CRT_EINVAL;
     if (std::strcmp(name, "gpu_build") == 0) {
         c->gpuBuild = value != 0;
+        return CRT_OK;
+    }
+    if (std::strcmp(name, "dynamic") == 0) {
+        c->dynamicOpt = value != 0;
         return CRT_OK;
     }
     // the 64-byte 4-wide tree is the only layout: 0 names it, any other width is rejected below
@@ -1148,7 +1256,7 @@ int checkQuery(crt_ctx* c, const char* what)
 {
     if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
     if (!c->haveScene) return fail(c, CRT_ESTATE, "%s: no scene uploaded: call crt_upload_scene first", what);
-    return CRT_OK;
+    return applyRefit(c, nullptr);
 }
 
 int checkDeviceOutputs(crt_ctx* c, const char* what, const void* rays, const RayOutputs& o, bool occlusion)
@@ -1493,6 +1601,7 @@ int crt_untile_device(crt_ctx* c, uint32_t w, uint32_t h, uint32_t n_ranks, cons
 int crt_bvh_info(const crt_ctx* c, uint32_t* n_nodes, uint32_t* n_tris, uint32_t* max_depth)
 {
     if (!c || !c->haveScene) return CRT_ESTATE;
+    if (int rc = applyRefit(const_cast<crt_ctx*>(c), nullptr)) return rc; // (pending updates of a dynamic scene)
     if (n_nodes) *n_nodes = c->bvh.nNodes;
     if (n_tris) *n_tris = c->bvh.nTris;
     if (max_depth) *max_depth = c->bvh.maxDepth;
@@ -1510,6 +1619,7 @@ int crt_build_stats(const crt_ctx* c, double* upload_ms, double* device_build_ms
 int crt_bvh_info4(const crt_ctx* c, uint32_t* n_nodes4, uint32_t* depth4)
 {
     if (!c || !c->haveScene) return CRT_ESTATE;
+    if (int rc = applyRefit(const_cast<crt_ctx*>(c), nullptr)) return rc; // (pending updates of a dynamic scene)
     if (n_nodes4) *n_nodes4 = c->bvh.nNodes4;
     if (depth4) *depth4 = c->bvh.depth4;
     return CRT_OK;
@@ -1518,6 +1628,7 @@ int crt_bvh_info4(const crt_ctx* c, uint32_t* n_nodes4, uint32_t* depth4)
 int crt_bvh_export4(const crt_ctx* c, crt_bvh_node4* nodes4)
 {
     if (!c || !c->haveScene) return CRT_ESTATE;
+    if (int rc = applyRefit(const_cast<crt_ctx*>(c), nullptr)) return rc; // (pending updates of a dynamic scene)
     if (nodes4) {
         if (!c->dWideNodes) crt::copyBytes(nodes4, c->bvh.nodes4.data(), sizeof(crt_bvh_node4) * c->bvh.nodes4.size());
         else if (hipMemcpy(nodes4, c->dWideNodes, sizeof(crt_bvh_node4) * c->bvh.nNodes4, hipMemcpyDeviceToHost) != hipSuccess) return CRT_EHIP;
@@ -1528,6 +1639,7 @@ int crt_bvh_export4(const crt_ctx* c, crt_bvh_node4* nodes4)
 int crt_bvh_export4q(const crt_ctx* c, crt_bvh_node4q* nodes4q)
 {
     if (!c || !c->haveScene) return CRT_ESTATE;
+    if (int rc = applyRefit(const_cast<crt_ctx*>(c), nullptr)) return rc; // (pending updates of a dynamic scene)
     if (nodes4q) {
         if (!c->dWideNodes) crt::copyBytes(nodes4q, c->bvh.nodes4q.data(), sizeof(crt_bvh_node4q) * c->bvh.nodes4q.size());
         else if (hipMemcpy(nodes4q, c->dNodes, sizeof(crt_bvh_node4q) * c->bvh.nNodes4, hipMemcpyDeviceToHost) != hipSuccess) return CRT_EHIP;
@@ -1538,6 +1650,7 @@ int crt_bvh_export4q(const crt_ctx* c, crt_bvh_node4q* nodes4q)
 int crt_bvh_export_planes4q(const crt_ctx* c, float* planes)
 {
     if (!c || !c->haveScene) return CRT_ESTATE;
+    if (int rc = applyRefit(const_cast<crt_ctx*>(c), nullptr)) return rc; // (pending updates of a dynamic scene)
     if (planes && c->bvh.nNodes4 > 0 &&
         hipMemcpy(planes, c->dPlanes, sizeof(float) * crt::kPlaneStride * c->bvh.nNodes4, hipMemcpyDeviceToHost) != hipSuccess)
         return CRT_EHIP;
@@ -1571,6 +1684,7 @@ int crt_bvh_build_host4(const crt_mesh_view* meshes, uint32_t n_meshes, crt_bvh_
 int crt_bvh_export(const crt_ctx* c, crt_bvh_node* nodes, crt_bvh_tri* tris, crt_bvh_shade* shade)
 {
     if (!c || !c->haveScene) return CRT_ESTATE;
+    if (int rc = applyRefit(const_cast<crt_ctx*>(c), nullptr)) return rc; // (pending updates of a dynamic scene)
     if (nodes) {
         if (!c->dBinNodes) crt::copyBytes(nodes, c->bvh.nodes.data(), sizeof(crt_bvh_node) * c->bvh.nodes.size());
         else if (hipMemcpy(nodes, c->dBinNodes, sizeof(crt_bvh_node) * c->bvh.nNodes, hipMemcpyDeviceToHost) != hipSuccess) return CRT_EHIP;
@@ -1588,6 +1702,106 @@ int crt_bvh_export(const crt_ctx* c, crt_bvh_node* nodes, crt_bvh_tri* tris, crt
     return CRT_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------- dynamic geometry (refit.h)
+namespace {
+
+int checkDynamic(const crt_ctx* c, uint32_t mesh, const char* what)
+{
+    if (!c->haveScene || !c->dyn) return fail(const_cast<crt_ctx*>(c), CRT_ESTATE, "%s: no scene uploaded with option \"dynamic\" = 1", what);
+    if (mesh >= c->dyn->meshes.size()) return fail(const_cast<crt_ctx*>(c), CRT_EINVAL, "%s: mesh %u out of range (%zu meshes)", what, mesh, c->dyn->meshes.size());
+    return CRT_OK;
+}
+
+int updateVertices(crt_ctx* c, uint32_t mesh, uint32_t n_vertices, const void* xyz, const void* normals, hipMemcpyKind kind, const char* what)
+{
+    if (!c) return CRT_EINVAL;
+    if (int rc = checkDynamic(c, mesh, what)) return rc;
+    crt::DynamicMesh& D = c->dyn->meshes[mesh];
+    if (n_vertices != D.nVerts) return fail(c, CRT_EINVAL, "%s: mesh %u has %u vertices, not %u (the topology is fixed)", what, mesh, D.nVerts, n_vertices);
+    if (!xyz) return fail(c, CRT_EINVAL, "%s: xyz is NULL", what);
+    if (normals && !D.hasNormals) return fail(c, CRT_EINVAL, "%s: mesh %u was uploaded without normals", what, mesh);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t off = 3 * static_cast<size_t>(D.vertStart), bytes = sizeof(float) * 3 * D.nVerts;
+    if (bytes) {
+        HIP_TRY(c, hipMemcpyAsync(c->dyn->dRestXyz + off, xyz, bytes, kind, c->stream));
+        if (normals) HIP_TRY(c, hipMemcpyAsync(c->dyn->dRestNormals + off, normals, bytes, kind, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream)); // the caller's buffers are read during the call
+    }
+    D.dirty = true;
+    c->dyn->pending = true;
+    c->accSamples = 0u; // the sums belong to the old geometry (the refit also gives the scene a new serial)
+    return CRT_OK;
+}
+
+} // namespace
+
+int crt_update_vertices(crt_ctx* c, uint32_t mesh, uint32_t n_vertices, const float* xyz, const float* normals)
+{
+    return updateVertices(c, mesh, n_vertices, xyz, normals, hipMemcpyHostToDevice, "crt_update_vertices");
+}
+
+int crt_update_vertices_device(crt_ctx* c, uint32_t mesh, uint32_t n_vertices, const void* d_xyz, const void* d_normals)
+{
+    return updateVertices(c, mesh, n_vertices, d_xyz, d_normals, hipMemcpyDeviceToDevice, "crt_update_vertices_device");
+}
+
+int crt_set_mesh_transform(crt_ctx* c, uint32_t mesh, const float m[12])
+{
+    if (!c) return CRT_EINVAL;
+    if (int rc = checkDynamic(c, mesh, "crt_set_mesh_transform")) return rc;
+    static const float kIdentity[12] = { 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f };
+    const float* M = m ? m : kIdentity;
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(M[i])) return fail(c, CRT_EINVAL, "crt_set_mesh_transform: entry %d is not finite", i);
+    crt::DynamicMesh& D = c->dyn->meshes[mesh];
+    float nm[9] = { 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f };
+    if (D.hasNormals) { // inverse transpose of the 3x3, in double, rounded to float once
+        const double a = M[0], b = M[1], cc = M[2], d = M[4], e = M[5], f = M[6], g = M[8], h = M[9], k = M[10];
+        const double A = e * k - f * h, B = -(d * k - f * g), C = d * h - e * g;
+        const double det = a * A + b * B + cc * C;
+        if (det == 0.0 || !std::isfinite(det)) return fail(c, CRT_EINVAL, "crt_set_mesh_transform: singular 3x3 on mesh %u, which has normals", mesh);
+        // inverse = adjugate / det; its transpose = cofactor matrix / det
+        const double cof[9] = { A, B, C, -(b * k - cc * h), a * k - cc * g, -(a * h - b * g), b * f - cc * e, -(a * f - cc * d), a * e - b * d };
+        for (int i = 0; i < 9; i++) {
+            nm[i] = static_cast<float>(cof[i] / det);
+            if (!std::isfinite(nm[i])) return fail(c, CRT_EINVAL, "crt_set_mesh_transform: the 3x3 of mesh %u is too close to singular", mesh);
+        }
+    }
+    std::memcpy(D.m, M, sizeof(D.m));
+    std::memcpy(D.nm, nm, sizeof(D.nm));
+    D.identity = std::memcmp(M, kIdentity, sizeof(kIdentity)) == 0; // bitwise: a -0.0 entry is not the identity
+    D.dirty = true;
+    c->dyn->pending = true;
+    c->accSamples = 0u; // the sums belong to the old geometry (the refit also gives the scene a new serial)
+    return CRT_OK;
+}
+
+int crt_refit(crt_ctx* c, double* device_ms)
+{
+    if (device_ms) *device_ms = 0.0;
+    if (!c) return CRT_EINVAL;
+    if (!c->haveScene || !c->dyn) return fail(c, CRT_ESTATE, "crt_refit: no scene uploaded with option \"dynamic\" = 1");
+    return applyRefit(c, device_ms);
+}
+
+int crt_mesh_vertices(const crt_ctx* cc, uint32_t mesh, float* xyz, float* normals)
+{
+    if (!cc) return CRT_EINVAL;
+    crt_ctx* c = const_cast<crt_ctx*>(cc); // a pending refit runs first
+    if (int rc = checkDynamic(c, mesh, "crt_mesh_vertices")) return rc;
+    const crt::DynamicMesh& D = c->dyn->meshes[mesh];
+    if (!xyz) return fail(c, CRT_EINVAL, "crt_mesh_vertices: xyz is NULL");
+    if (normals && !D.hasNormals) return fail(c, CRT_EINVAL, "crt_mesh_vertices: mesh %u was uploaded without normals", mesh);
+    if (int rc = applyRefit(c, nullptr)) return rc;
+    const size_t off = 3 * static_cast<size_t>(D.vertStart), bytes = sizeof(float) * 3 * D.nVerts;
+    if (bytes) {
+        HIP_TRY(c, hipMemcpyAsync(xyz, c->dyn->dWorldXyz + off, bytes, hipMemcpyDeviceToHost, c->stream));
+        if (normals) HIP_TRY(c, hipMemcpyAsync(normals, c->dyn->dWorldNormals + off, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return CRT_OK;
+}
 
 // ------------------------------------------------------------------------------------------- native RCCL gather
 // One process per GPU; every rank renders its macro tiles into a tile-major staging buffer, ONE ncclAllGather per frame moves

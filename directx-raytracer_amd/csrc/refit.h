@@ -1,0 +1,66 @@
+// Dynamic geometry (option "dynamic"): what a scene keeps in HBM so that moved vertices can be refitted into the uploaded tree
+// instead of rebuilding it (refit_kernels.hip; DESIGN.md "Dynamic geometry").  The topology -- triangles, indices, uvs,
+// materials, the binary tree's shape and leaf order -- is fixed at upload; a refit rewrites the vertices' world positions, the
+// leaf-ordered triangle and shading records, the binary boxes and, by collapsing again, the wide tree and its plane table.
+#pragma once
+
+#include "../../include/crt_hip.h"
+
+#include <cstdint>
+#include <vector>
+
+struct ihipStream_t;
+struct ihipEvent_t;
+
+namespace crt {
+
+struct DynamicMesh {
+    uint32_t vertStart = 0, nVerts = 0;
+    bool hasNormals = false;
+    bool identity = true; // transform bitwise equal to the identity: world data = rest data, no arithmetic
+    float m[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 }; // row-major 3x4
+    float nm[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };          // inverse transpose of its 3x3 (for normals), row-major
+    bool dirty = false;   // rest data or transform changed since the last refit
+};
+
+struct DynamicScene {
+    std::vector<DynamicMesh> meshes;
+    uint32_t nVerts = 0, nTris = 0, nBinary = 0;
+    void* dTable = nullptr;           // MeshEntry per mesh + terminator (mesh_table.hip.h)
+    float* dRestXyz = nullptr;        // 3 floats per vertex, all meshes back to back
+    float* dRestNormals = nullptr;    // idem (zeros for meshes without normals); NULL when no mesh has normals
+    float* dWorldXyz = nullptr;
+    float* dWorldNormals = nullptr;
+    uint32_t* dIdx = nullptr;         // 3 per triangle, mesh-local vertex indices
+    uint32_t* dLevelNodes = nullptr;  // binary inner nodes by depth: level k = dLevelNodes[levelStart[k] .. levelStart[k + 1])
+    std::vector<uint32_t> levelStart;
+    void* dScratch = nullptr;         // collapseWideGpu scratch
+    ihipEvent_t* ev0 = nullptr;
+    ihipEvent_t* ev1 = nullptr;
+    bool pending = false;             // some mesh is dirty
+
+    DynamicScene() = default;
+    DynamicScene(const DynamicScene&) = delete;
+    DynamicScene& operator=(const DynamicScene&) = delete;
+    ~DynamicScene();
+};
+
+// Everything a refit rewrites (all in HBM, capacities: nodes4 / nodes4q / planes hold one record per binary inner node)
+struct RefitTargets {
+    crt_bvh_node* binNodes;
+    crt_bvh_tri* tris;
+    crt_bvh_shade* shade;
+    void* nodes4;
+    void* nodes4q;
+    float* planes;
+};
+
+// At upload: copies the meshes (rest = world = as given) and the per-level lists of the binary tree (hostNodes, or read back
+// from binNodes when the tree exists on the device only).  Throws std::runtime_error on HIP errors.
+void dynamicInit(DynamicScene& d, const crt_mesh_view* meshes, uint32_t n_meshes, const crt_bvh_node* hostNodes, const crt_bvh_node* binNodes,
+                 uint32_t nBinary, ihipStream_t* stream);
+// The refit of all pending updates, on `stream`; returns when it is done.  *nWide / *depth4: the re-collapsed wide tree;
+// *device_ms: HIP-event time from the first transform to the plane table.  Throws std::runtime_error on HIP errors.
+void dynamicRefit(DynamicScene& d, const RefitTargets& t, ihipStream_t* stream, uint32_t* nWide, uint32_t* depth4, double* device_ms);
+
+} // namespace crt

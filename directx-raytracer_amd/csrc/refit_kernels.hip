@@ -1,0 +1,275 @@
+// Refit of a dynamic scene (refit.h; DESIGN.md "Dynamic geometry"): moved vertices go into the tree uploaded with them, with the
+// same bytes a fresh build of the moved meshes writes for every record whose place in the tree did not change.
+//   1. transformKernel: world = transform . rest, one thread per vertex, for meshes whose transform is not the identity
+//      (an identity mesh's world data is a copy of its rest data: no arithmetic, -0.0 stays -0.0)
+//   2. recordsKernel: the leaf-ordered triangle / shading records from the world vertices, as gatherKernel / flattenMeshes
+//   3. refitLevelKernel: the binary boxes bottom-up, one launch per depth level, deepest first -- the kernel boundary is the
+//      only synchronisation (no atomics, no hand-off between XCDs); a leaf's box from its triangles' vertices as triBoxKernel
+//      takes them, an inner node's from grow(left, right) with the selects of fitKernel / the oracle's aabb_grow
+//   4. collapseWideGpu (bvh_gpu.hip, shared with the GPU build) and the plane table (launchDecodePlanes)
+#include "refit.h"
+
+#include "bvh_build.h"
+#include "mesh_table.hip.h"
+#include "render_kernels.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+
+namespace crt {
+namespace {
+
+#define REFIT_TRY(expr)                                                                                        \
+    do {                                                                                                       \
+        hipError_t e_ = (expr);                                                                                \
+        if (e_ != hipSuccess) throw std::runtime_error(std::string(#expr " failed: ") + hipGetErrorString(e_)); \
+    } while (0)
+
+struct Xform {
+    float m[12];
+    float nm[9];
+};
+
+// x' = ((m0*x + m1*y) + m2*z) + m3 per row (the file is built with -ffp-contract=off: no fused multiply-add); normals by the
+// inverse transpose, no translation, not renormalised
+__global__ __launch_bounds__(256) void transformKernel(const float* __restrict__ rest, const float* __restrict__ restN, float* __restrict__ world,
+                                                       float* __restrict__ worldN, uint32_t n, Xform X)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float x = rest[3 * static_cast<size_t>(i)], y = rest[3 * static_cast<size_t>(i) + 1], z = rest[3 * static_cast<size_t>(i) + 2];
+    for (int r = 0; r < 3; r++) world[3 * static_cast<size_t>(i) + r] = ((X.m[4 * r] * x + X.m[4 * r + 1] * y) + X.m[4 * r + 2] * z) + X.m[4 * r + 3];
+    if (restN) {
+        const float a = restN[3 * static_cast<size_t>(i)], b = restN[3 * static_cast<size_t>(i) + 1], c = restN[3 * static_cast<size_t>(i) + 2];
+        for (int r = 0; r < 3; r++) worldN[3 * static_cast<size_t>(i) + r] = (X.nm[3 * r] * a + X.nm[3 * r + 1] * b) + X.nm[3 * r + 2] * c;
+    }
+}
+
+// leaf position i: the record's gid names the triangle; v0 / e1 / e2 and the vertex normals as gatherKernel writes them
+__global__ __launch_bounds__(256) void recordsKernel(const MeshEntry* __restrict__ table, uint32_t n_meshes, const float* __restrict__ xyz,
+                                                     const float* __restrict__ normals, const uint32_t* __restrict__ idx, uint32_t n,
+                                                     crt_bvh_tri* __restrict__ tris, crt_bvh_shade* __restrict__ shade)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t g = tris[i].gid;
+    const MeshEntry M = table[meshOf(table, n_meshes, g)];
+    const uint32_t v0 = M.vertStart + idx[3 * static_cast<size_t>(g)], v1 = M.vertStart + idx[3 * static_cast<size_t>(g) + 1],
+                   v2 = M.vertStart + idx[3 * static_cast<size_t>(g) + 2];
+    const float* A = xyz + 3 * static_cast<size_t>(v0);
+    const float* B = xyz + 3 * static_cast<size_t>(v1);
+    const float* C = xyz + 3 * static_cast<size_t>(v2);
+    for (int k = 0; k < 3; k++) {
+        tris[i].v0[k] = A[k];
+        tris[i].e1[k] = B[k] - A[k];
+        tris[i].e2[k] = C[k] - A[k];
+    }
+    if (M.hasNormals)
+        for (int k = 0; k < 3; k++) {
+            shade[i].n0[k] = normals[3 * static_cast<size_t>(v0) + k];
+            shade[i].n1[k] = normals[3 * static_cast<size_t>(v1) + k];
+            shade[i].n2[k] = normals[3 * static_cast<size_t>(v2) + k];
+        }
+}
+
+__device__ __forceinline__ float minSel(float a, float b) { return a < b ? a : b; }
+__device__ __forceinline__ float maxSel(float a, float b) { return a > b ? a : b; }
+
+struct Box6 { float mn[3], mx[3]; };
+
+// Every node of one depth level: both child boxes.  An inner child's box is the union of ITS two child boxes (written by the
+// launch of the level below); a leaf's the union of its triangles' boxes in leaf order.  Both builders fold boxes with the same
+// selects from +inf / -inf, and "a < b ? a : b" picks the last of equal values whichever way a fold is bracketed, so these are
+// the builders' boxes bit for bit.  The empty leaf beside a one-leaf root takes its sibling's box, as the builders give it.
+__global__ __launch_bounds__(256) void refitLevelKernel(const uint32_t* __restrict__ level, uint32_t count, crt_bvh_node* __restrict__ nodes,
+                                                        const crt_bvh_tri* __restrict__ tris, const MeshEntry* __restrict__ table, uint32_t n_meshes,
+                                                        const float* __restrict__ xyz, const uint32_t* __restrict__ idx)
+{
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= count) return;
+    const uint32_t b = level[t];
+    crt_bvh_node N = nodes[b];
+    Box6 box[2];
+    bool empty[2] = { false, false };
+    for (int c = 0; c < 2; c++) {
+        const int32_t ref = c == 0 ? N.left : N.right;
+        Box6& B = box[c];
+        if (ref >= 0) {
+            const crt_bvh_node C = nodes[ref];
+            B.mn[0] = minSel(C.lx0, C.rx0); B.mx[0] = maxSel(C.lx1, C.rx1);
+            B.mn[1] = minSel(C.ly0, C.ry0); B.mx[1] = maxSel(C.ly1, C.ry1);
+            B.mn[2] = minSel(C.lz0, C.rz0); B.mx[2] = maxSel(C.lz1, C.rz1);
+            continue;
+        }
+        const uint32_t leaf = static_cast<uint32_t>(~ref), first = leaf >> 3, cnt = leaf & 7u;
+        empty[c] = cnt == 0u;
+        for (int a = 0; a < 3; a++) { B.mn[a] = INFINITY; B.mx[a] = -INFINITY; }
+        for (uint32_t k = 0; k < cnt; k++) {
+            const uint32_t g = tris[first + k].gid;
+            const MeshEntry M = table[meshOf(table, n_meshes, g)];
+            const float* P = xyz + 3 * static_cast<size_t>(M.vertStart + idx[3 * static_cast<size_t>(g)]);
+            const float* Q = xyz + 3 * static_cast<size_t>(M.vertStart + idx[3 * static_cast<size_t>(g) + 1]);
+            const float* R = xyz + 3 * static_cast<size_t>(M.vertStart + idx[3 * static_cast<size_t>(g) + 2]);
+            for (int a = 0; a < 3; a++) {
+                B.mn[a] = minSel(B.mn[a], minSel(minSel(P[a], Q[a]), R[a]));
+                B.mx[a] = maxSel(B.mx[a], maxSel(maxSel(P[a], Q[a]), R[a]));
+            }
+        }
+    }
+    if (empty[1]) box[1] = box[0];
+    else if (empty[0]) box[0] = box[1];
+    N.lx0 = box[0].mn[0]; N.lx1 = box[0].mx[0]; N.ly0 = box[0].mn[1]; N.ly1 = box[0].mx[1]; N.lz0 = box[0].mn[2]; N.lz1 = box[0].mx[2];
+    N.rx0 = box[1].mn[0]; N.rx1 = box[1].mx[0]; N.ry0 = box[1].mn[1]; N.ry1 = box[1].mx[1]; N.rz0 = box[1].mn[2]; N.rz1 = box[1].mx[2];
+    nodes[b] = N;
+}
+
+} // namespace
+
+DynamicScene::~DynamicScene()
+{
+    void* ptrs[] = { dTable, dRestXyz, dRestNormals, dWorldXyz, dWorldNormals, dIdx, dLevelNodes, dScratch };
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+}
+
+void dynamicInit(DynamicScene& d, const crt_mesh_view* meshes, uint32_t n_meshes, const crt_bvh_node* hostNodes, const crt_bvh_node* binNodes,
+                 uint32_t nBinary, ihipStream_t* stream)
+{
+    uint64_t nv = 0, nt = 0;
+    bool anyNormals = false;
+    d.meshes.resize(n_meshes);
+    std::vector<MeshEntry> table(n_meshes + 1u);
+    for (uint32_t m = 0; m < n_meshes; m++) {
+        DynamicMesh& D = d.meshes[m];
+        D.vertStart = static_cast<uint32_t>(nv);
+        D.nVerts = meshes[m].n_vertices;
+        D.hasNormals = meshes[m].normals != nullptr;
+        anyNormals |= D.hasNormals && D.nVerts > 0;
+        MeshEntry& E = table[m];
+        E.triStart = static_cast<uint32_t>(nt); E.vertStart = static_cast<uint32_t>(nv); E.nVerts = D.nVerts;
+        E.material = static_cast<uint32_t>(meshes[m].material_index);
+        E.hasNormals = D.hasNormals ? 1u : 0u; E.hasUvs = meshes[m].uvs ? 1u : 0u; E.pad0 = E.pad1 = 0;
+        nv += meshes[m].n_vertices;
+        nt += meshes[m].n_triangles;
+    }
+    if (nv >= (1ull << 32)) throw std::runtime_error("too many vertices");
+    MeshEntry& E = table[n_meshes];
+    E.triStart = static_cast<uint32_t>(nt); E.vertStart = static_cast<uint32_t>(nv); E.nVerts = 0; E.material = 0; E.hasNormals = E.hasUvs = E.pad0 = E.pad1 = 0;
+    d.nVerts = static_cast<uint32_t>(nv);
+    d.nTris = static_cast<uint32_t>(nt);
+    d.nBinary = nBinary;
+    const size_t vb = sizeof(float) * 3 * (nv ? nv : 1);
+    REFIT_TRY(hipMalloc(&d.dTable, sizeof(MeshEntry) * table.size()));
+    REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dRestXyz), vb));
+    REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dWorldXyz), vb));
+    if (anyNormals) {
+        REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dRestNormals), vb));
+        REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dWorldNormals), vb));
+        REFIT_TRY(hipMemsetAsync(d.dRestNormals, 0, vb, stream));
+    }
+    REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dIdx), sizeof(uint32_t) * 3 * (nt ? nt : 1)));
+    REFIT_TRY(hipMemcpyAsync(d.dTable, table.data(), sizeof(MeshEntry) * table.size(), hipMemcpyHostToDevice, stream));
+    for (uint32_t m = 0; m < n_meshes; m++) {
+        const crt_mesh_view& M = meshes[m];
+        const size_t off = 3 * static_cast<size_t>(table[m].vertStart);
+        if (M.n_vertices && M.xyz) REFIT_TRY(hipMemcpyAsync(d.dRestXyz + off, M.xyz, sizeof(float) * 3 * M.n_vertices, hipMemcpyHostToDevice, stream));
+        if (M.n_vertices && M.normals)
+            REFIT_TRY(hipMemcpyAsync(d.dRestNormals + off, M.normals, sizeof(float) * 3 * M.n_vertices, hipMemcpyHostToDevice, stream));
+        if (M.n_triangles)
+            REFIT_TRY(hipMemcpyAsync(d.dIdx + 3 * static_cast<size_t>(table[m].triStart), M.idx, sizeof(uint32_t) * 3 * static_cast<size_t>(M.n_triangles),
+                                     hipMemcpyHostToDevice, stream));
+    }
+    REFIT_TRY(hipMemcpyAsync(d.dWorldXyz, d.dRestXyz, vb, hipMemcpyDeviceToDevice, stream));
+    if (anyNormals) REFIT_TRY(hipMemcpyAsync(d.dWorldNormals, d.dRestNormals, vb, hipMemcpyDeviceToDevice, stream));
+
+    // per-level lists of the binary inner nodes (the tree's shape never changes)
+    std::vector<crt_bvh_node> readBack;
+    if (!hostNodes && nBinary) {
+        readBack.resize(nBinary);
+        REFIT_TRY(hipMemcpyAsync(readBack.data(), binNodes, sizeof(crt_bvh_node) * nBinary, hipMemcpyDeviceToHost, stream));
+        REFIT_TRY(hipStreamSynchronize(stream));
+        hostNodes = readBack.data();
+    }
+    std::vector<uint32_t> order;
+    d.levelStart.clear();
+    if (nBinary) {
+        order.reserve(nBinary);
+        order.push_back(0);
+        size_t begin = 0;
+        while (begin < order.size()) {
+            const size_t end = order.size();
+            d.levelStart.push_back(static_cast<uint32_t>(begin));
+            for (size_t k = begin; k < end; k++) {
+                const crt_bvh_node& N = hostNodes[order[k]];
+                for (int32_t ch : { N.left, N.right })
+                    if (ch >= 0) {
+                        if (static_cast<uint32_t>(ch) >= nBinary || order.size() >= nBinary) throw std::runtime_error("binary tree: bad child reference");
+                        order.push_back(static_cast<uint32_t>(ch));
+                    }
+            }
+            begin = end;
+        }
+        d.levelStart.push_back(static_cast<uint32_t>(order.size()));
+    }
+    REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dLevelNodes), sizeof(uint32_t) * (order.empty() ? 1 : order.size())));
+    if (!order.empty())
+        REFIT_TRY(hipMemcpyAsync(d.dLevelNodes, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, stream));
+    REFIT_TRY(hipMalloc(&d.dScratch, collapseScratchBytes(nBinary)));
+    REFIT_TRY(hipEventCreate(&d.ev0));
+    REFIT_TRY(hipEventCreate(&d.ev1));
+    REFIT_TRY(hipStreamSynchronize(stream)); // the host arrays above die with this call
+}
+
+void dynamicRefit(DynamicScene& d, const RefitTargets& t, ihipStream_t* stream, uint32_t* nWide, uint32_t* depth4, double* device_ms)
+{
+    const dim3 blk(256);
+    REFIT_TRY(hipEventRecord(d.ev0, stream));
+    for (DynamicMesh& D : d.meshes) {
+        if (!D.dirty || D.nVerts == 0) continue;
+        const size_t off = 3 * static_cast<size_t>(D.vertStart), bytes = sizeof(float) * 3 * D.nVerts;
+        if (D.identity) {
+            REFIT_TRY(hipMemcpyAsync(d.dWorldXyz + off, d.dRestXyz + off, bytes, hipMemcpyDeviceToDevice, stream));
+            if (D.hasNormals) REFIT_TRY(hipMemcpyAsync(d.dWorldNormals + off, d.dRestNormals + off, bytes, hipMemcpyDeviceToDevice, stream));
+        } else {
+            Xform X;
+            std::memcpy(X.m, D.m, sizeof(X.m));
+            std::memcpy(X.nm, D.nm, sizeof(X.nm));
+            hipLaunchKernelGGL(transformKernel, dim3((D.nVerts + 255) / 256), blk, 0, stream, d.dRestXyz + off, D.hasNormals ? d.dRestNormals + off : nullptr,
+                               d.dWorldXyz + off, D.hasNormals ? d.dWorldNormals + off : nullptr, D.nVerts, X);
+        }
+    }
+    const uint32_t nMeshes = static_cast<uint32_t>(d.meshes.size());
+    const MeshEntry* table = static_cast<const MeshEntry*>(d.dTable);
+    if (d.nTris)
+        hipLaunchKernelGGL(recordsKernel, dim3((d.nTris + 255) / 256), blk, 0, stream, table, nMeshes, d.dWorldXyz, d.dWorldNormals, d.dIdx, d.nTris,
+                           t.tris, t.shade);
+    for (size_t L = d.levelStart.size() - (d.levelStart.empty() ? 0 : 1); L-- > 0;) {
+        const uint32_t first = d.levelStart[L], count = d.levelStart[L + 1] - first;
+        hipLaunchKernelGGL(refitLevelKernel, dim3((count + 255) / 256), blk, 0, stream, d.dLevelNodes + first, count, t.binNodes, t.tris, table,
+                           nMeshes, d.dWorldXyz, d.dIdx);
+    }
+    REFIT_TRY(hipGetLastError());
+    *nWide = 0;
+    *depth4 = 0;
+    if (d.nBinary) {
+        void* n4 = t.nodes4;
+        void* n4q = t.nodes4q;
+        collapseWideGpu(t.binNodes, d.nBinary, d.dScratch, &n4, &n4q, stream, nWide, depth4, nullptr);
+        REFIT_TRY(static_cast<hipError_t>(launchDecodePlanes(t.nodes4q, *nWide, t.planes, stream)));
+    }
+    REFIT_TRY(hipEventRecord(d.ev1, stream));
+    REFIT_TRY(hipStreamSynchronize(stream));
+    float ms = 0.f;
+    REFIT_TRY(hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    if (device_ms) *device_ms = ms;
+    for (DynamicMesh& D : d.meshes) D.dirty = false;
+    d.pending = false;
+}
+
+} // namespace crt

@@ -62,6 +62,7 @@ void Renderer::uploadScene()
         mats.push_back(crt_material{ { m.getAlbedo().getX(), m.getAlbedo().getY(), m.getAlbedo().getZ() },
                                      static_cast<uint32_t>(m.getType()), m.isSmoothShading() ? 1u : 0u, m.getIor(),
                                      m.isTexture() ? scene->textureIndexByName(m.getTextureName()) : -1 });
+    check(crt_set_option(ctx, "dynamic", dynamicGeometry ? 1 : 0), "crt_set_option");
     check(crt_upload_scene(ctx, meshes.data(), static_cast<uint32_t>(meshes.size()), lights.data(),
                            static_cast<uint32_t>(lights.size()), mats.data(), static_cast<uint32_t>(mats.size())),
           "crt_upload_scene");
@@ -95,6 +96,19 @@ void Renderer::renderFrame()
     frame.resize(static_cast<size_t>(width) * height * 4);
     if (nRanks) check(crt_render_frame_distributed(ctx, width, height, nullptr, frame.data(), &stats), "crt_render_frame_distributed");
     else check(crt_render_frame(ctx, width, height, frame.data(), nullptr, nullptr, nullptr, nullptr, &stats), "crt_render_frame");
+}
+
+void Renderer::setMeshTransform(uint32_t mesh, const float m[12])
+{
+    if (!ctx) throw std::runtime_error("setMeshTransform before prepareForRendering");
+    check(crt_set_mesh_transform(ctx, mesh, m), "crt_set_mesh_transform");
+}
+
+void Renderer::updateMeshVertices(uint32_t mesh, const float* xyz, size_t nVertices, const float* normals)
+{
+    if (!ctx) throw std::runtime_error("updateMeshVertices before prepareForRendering");
+    if (nVertices > UINT32_MAX) throw std::runtime_error("updateMeshVertices: more than 2^32 - 1 vertices");
+    check(crt_update_vertices(ctx, mesh, static_cast<uint32_t>(nVertices), xyz, normals), "crt_update_vertices");
 }
 
 void Renderer::setOption(const char* name, int value)

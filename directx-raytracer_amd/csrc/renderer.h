@@ -57,6 +57,12 @@ public:
     void traceRays(const float* rays, size_t n, RayHit* out);
     void occluded(const float* rays, size_t n, uint8_t* out); // 1 = some triangle lies in (tmin, tmax)
 
+    // dynamic geometry (crt_update_vertices / crt_set_mesh_transform, include/crt_hip.h): enable before prepareForRendering, whose
+    // upload then keeps what a refit needs.  Updates are applied before the next frame or ray query.
+    void setDynamicGeometry(bool on) { dynamicGeometry = on; }
+    void setMeshTransform(uint32_t mesh, const float m[12]);                                          // row-major 3x4; nullptr = identity
+    void updateMeshVertices(uint32_t mesh, const float* xyz, size_t nVertices, const float* normals = nullptr); // normals: nullptr = keep
+
     // N GPUs, one process each (no reference counterpart): join the RCCL communicator of an N-rank run.  Rank 0 creates the
     // 128-byte id and publishes it as `idFile` (written under a temporary name, then renamed); the other ranks wait for the
     // file.  Afterwards renderFrame() renders this rank's tiles, gathers and de-interleaves: every rank holds the frame.
@@ -75,6 +81,7 @@ private:
     std::vector<uint8_t> frame;
     crt_frame_stats stats{};
     uint32_t rank = 0, nRanks = 0; // nRanks = 0: single-GPU path (crt_render_frame)
+    bool dynamicGeometry = false;
     void uploadScene();
     void check(int rc, const char* what) const;
 };

@@ -131,8 +131,9 @@ uint32_t crt_abi_version(void);
 
 /* createVertexBuffers + createIndexBuffers + createAccelerationStructures
  * (R/DXRTRenderer.cpp:379-453, 302-376, 548-806): copies geometry, builds the BVH on the host (binned SAH)
- * and uploads nodes / leaf-ordered triangles / shading records to HBM. The scene is immutable afterwards
- * (the reference never refits either); a second call replaces it. */
+ * and uploads nodes / leaf-ordered triangles / shading records to HBM.  A second call replaces the scene.  Vertices and
+ * per-mesh transforms can change afterwards when option "dynamic" was set before the upload (crt_update_vertices and the
+ * functions beside it, below); triangles, indices, uvs and materials need a new upload. */
 int crt_upload_scene(crt_ctx* ctx, const crt_mesh_view* meshes, uint32_t n_meshes,
                      const crt_light* lights, uint32_t n_lights,
                      const crt_material* materials, uint32_t n_materials);
@@ -357,6 +358,34 @@ int crt_occluded_rays_device(crt_ctx* ctx, uint32_t n, const void* d_rays, void*
 int crt_trace_rays(crt_ctx* ctx, uint32_t n, const float* rays, float* t, float* uv, uint32_t* inst, uint32_t* prim,
                    crt_frame_stats* stats);
 int crt_occluded_rays(crt_ctx* ctx, uint32_t n, const float* rays, uint8_t* occluded, crt_frame_stats* stats);
+
+/* ---- dynamic geometry (DXR: acceleration-structure updates and D3D12_RAYTRACING_INSTANCE_DESC::Transform, which the reference
+ * fills with the identity for every mesh, R/DXRTRenderer.cpp:690-704).  Opt-in: crt_set_option(ctx, "dynamic", 1) before
+ * crt_upload_scene / crt_upload_scene_from; only then does the upload keep what a refit needs in HBM (the meshes' rest and world
+ * vertices and normals, indices, the binary tree, its per-level node lists, room for a wide tree of one node per binary inner
+ * node).  A context that never sets the option behaves, allocates and performs as without it.
+ * - Each mesh has rest vertices / normals (those uploaded, or the last ones given to crt_update_vertices*) and a transform, the
+ *   identity at upload.  World vertices = transform . rest.  A transform bitwise equal to the identity uses the rest data
+ *   unchanged (no arithmetic: -0.0 stays -0.0).  Otherwise, per row r of the row-major 3x4 m (DXR's Transform[3][4]):
+ *   x'_r = ((m[4r]*x + m[4r+1]*y) + m[4r+2]*z) + m[4r+3] in float, no fused multiply-add; normals are multiplied by the inverse
+ *   transpose of the 3x3, computed on the host in double and rounded to float once, and are not renormalised.
+ * - Updates are staged; one refit covers all of them.  It runs on the context's stream before the next call that reads the tree
+ *   or the records: every render entry point, crt_trace_rays* / crt_occluded_rays*, crt_bvh_info* / crt_bvh_export*,
+ *   crt_mesh_vertices; crt_refit forces it.  The refit keeps the tree's shape and leaf order and recomputes the leaf-ordered
+ *   triangle / shading records (each byte-equal to what a build of the moved meshes writes for that triangle), the binary boxes
+ *   bottom-up, the wide tree (whose node count and depth may change) and its plane table.  Like a re-upload it resets
+ *   accumulation and the stored launch orders.  A scene that moves far from where it was built traces slower than a rebuilt one.
+ * - Errors: NULL ctx -> CRT_EINVAL; no scene, or a scene uploaded without "dynamic" -> CRT_ESTATE; CRT_EINVAL for a bad mesh
+ *   index, n_vertices other than the uploaded count, xyz == NULL, normals for a mesh uploaded without normals, a non-finite
+ *   matrix entry, a singular 3x3 on a mesh that has normals.  A failed call changes nothing.
+ * - Several ranks (crt_comm_*): each rank's context applies the updates it is given; nothing is propagated between ranks. */
+int crt_update_vertices(crt_ctx* ctx, uint32_t mesh, uint32_t n_vertices, const float* xyz, const float* normals /* NULL = keep */);
+/* the same from device memory: the caller makes d_xyz / d_normals ready on the context's stream; they are read during the call */
+int crt_update_vertices_device(crt_ctx* ctx, uint32_t mesh, uint32_t n_vertices, const void* d_xyz, const void* d_normals);
+int crt_set_mesh_transform(crt_ctx* ctx, uint32_t mesh, const float m[12]); /* row-major 3x4; NULL = identity */
+int crt_refit(crt_ctx* ctx, double* device_ms /* may be NULL: HIP-event time of the refit, 0 when nothing was pending */);
+/* world-space vertices (and normals, may be NULL) of a mesh as they are traced, n_vertices * 3 floats each */
+int crt_mesh_vertices(const crt_ctx* ctx, uint32_t mesh, float* xyz, float* normals);
 
 /* ---------------------------------------------------------------------------------------------------
  * Scene layer: stands in for CRTScene / CRTSceneParser / CRTCamera (kept API surface, host only, no GPU)
