@@ -1188,6 +1188,25 @@ int crt_debug_read_counters(crt_ctx* c, unsigned long long out[32])
     return CRT_OK;
 }
 
+int crt_debug_check_rcp(int device_id, unsigned long long out[8])
+{
+    if (!out) return fail(nullptr, CRT_EINVAL, "crt_debug_check_rcp: out is NULL");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(nullptr, CRT_ENODEVICE, "no HIP device available");
+    if (device_id < 0 || device_id >= n) return fail(nullptr, CRT_EINVAL, "device_id %d out of range [0,%d)", device_id, n);
+    HIP_TRY(nullptr, hipSetDevice(device_id));
+    unsigned long long init[8] = { 0, 0, 0, 0, 0, 0, ~0ull, 0 };
+    unsigned long long* d = nullptr;
+    HIP_TRY(nullptr, hipMalloc(reinterpret_cast<void**>(&d), sizeof(init)));
+    hipError_t e = hipMemcpy(d, init, sizeof(init), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = static_cast<hipError_t>(crt::launchRcpCheck(d, nullptr));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d, sizeof(init), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(nullptr, CRT_EHIP, "crt_debug_check_rcp: %s", hipGetErrorString(e));
+    return CRT_OK;
+}
+
 int crt_set_stream(crt_ctx* c, void* hip_stream)
 {
     if (!c) return CRT_EINVAL;

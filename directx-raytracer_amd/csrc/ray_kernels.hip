@@ -178,6 +178,34 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCCL ? L::kW
     }
 }
 
+// Exhaustive check of rcpExact (traversal.hip.h) against the compiled correctly rounded 1.0f / d: wavefront w takes the
+// 64 * kRcpPerThread consecutive bit patterns from w * 64 * kRcpPerThread, 64 neighbouring patterns (one per lane) per
+// round.  out: [0] rcpExact mismatches, [1] inputs checked, [2..5] mismatches of the unguarded rcpNewton form among
+// the inputs with biased exponent 0 / 253..255 / 1..252 and an all-ones significand (the class Markstein's theorem leaves
+// out) / all others -- rcpFastOk accepts the last two, [6] smallest mismatching input of rcpExact (or ~0).  NaN results
+// match any NaN.
+constexpr uint32_t kRcpPerThread = 256;
+__device__ __forceinline__ bool sameRcp(float a, float b) { return (__float_as_uint(a) == __float_as_uint(b)) | ((a != a) & (b != b)); }
+
+__global__ void __launch_bounds__(256) rcpCheckKernel(unsigned long long* out)
+{
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    uint32_t bad = 0, badClass[4] = { 0, 0, 0, 0 }, first = 0xFFFFFFFFu;
+    for (uint32_t k = 0; k < kRcpPerThread; k++) {
+        const uint32_t bits = (wave * kRcpPerThread + k) * 64u + lane;
+        const float d = __uint_as_float(bits);
+        const float ref = 1.0f / d;
+        if (!sameRcp(rcpExact(d), ref)) { bad++; first = min(first, bits); }
+        const uint32_t e = (bits >> 23) & 0xFFu;
+        const int cls = e == 0u ? 0 : (e >= 253u ? 1 : ((bits & 0x7FFFFFu) == 0x7FFFFFu ? 2 : 3));
+        if (!sameRcp(rcpNewton(d), ref)) badClass[cls]++;
+    }
+    if (bad) { atomicAdd(&out[0], static_cast<unsigned long long>(bad)); atomicMin(&out[6], static_cast<unsigned long long>(first)); }
+    for (int c = 0; c < 4; c++)
+        if (badClass[c]) atomicAdd(&out[2 + c], static_cast<unsigned long long>(badClass[c]));
+    atomicAdd(&out[1], static_cast<unsigned long long>(kRcpPerThread));
+}
+
 } // namespace
 
 // resident workgroups of a persistent query kernel: what the occupancy calculator allows per CU for this LDS stack x CUs of
@@ -216,6 +244,14 @@ int launchRayQuery(const RayQueryParams& q, bool occlusion, bool counting, uint3
         if (counting) hipLaunchKernelGGL((rayQueryKernel<true, false, LayLegacy>), g, block, lds, stream, q);
         else hipLaunchKernelGGL((rayQueryKernel<false, false, LayLegacy>), g, block, lds, stream, q);
     }
+    return static_cast<int>(hipGetLastError());
+}
+
+int launchRcpCheck(unsigned long long* out, ihipStream_t* stream)
+{
+    // 2^32 inputs: 2^24 threads of kRcpPerThread inputs each
+    const uint32_t blocks = static_cast<uint32_t>((1ull << 32) / (256ull * kRcpPerThread));
+    hipLaunchKernelGGL(rcpCheckKernel, dim3(blocks), dim3(256), 0, stream, out);
     return static_cast<int>(hipGetLastError());
 }
 

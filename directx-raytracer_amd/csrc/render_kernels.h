@@ -151,6 +151,9 @@ uint32_t rayQueryResident(bool occlusion, uint32_t stack_entries);
 // records per reservation and grid (persistent: at most `resident` workgroups) of a query of n rays
 void rayQueryLayout(uint32_t n, uint32_t resident, uint32_t& chunk, uint32_t& grid);
 int launchRayQuery(const RayQueryParams& q, bool occlusion, bool counting, uint32_t grid, ihipStream_t* stream);
+// exhaustive check of the triangle test's reciprocal (ray_kernels.hip rcpCheckKernel) into out[0..6] (device memory, zeroed
+// except out[6] = ~0 by the caller)
+int launchRcpCheck(unsigned long long* out, ihipStream_t* stream);
 
 // device-side texture record (crt_texture with the pixel pointer replaced by an offset into the texel pool)
 struct TextureRec {

@@ -126,7 +126,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SPLIT ? 5 : 
     const unsigned long long tk0 = __builtin_amdgcn_s_memtime();
     unsigned long long pTNode = 0, pTLeaf = 0; uint32_t pItN = 0, pItL = 0, pLaN = 0, pLaL = 0;
     uint32_t pDv[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    uint32_t pSt[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    uint32_t pSt[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 #endif
     uint32_t iters = 0; // traversal-loop iterations of this wavefront = its critical path, fed back as next frame's cost
     if (split) {
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SPLIT ? 5 : 
         pTNode = stack.tNode; pTLeaf = stack.tLeaf; pItN = stack.itNode; pItL = stack.itLeaf; pLaN = stack.lanesNode; pLaL = stack.lanesLeaf;
         pDv[0] = stack.dvN; pDv[1] = stack.dvNLanes; pDv[2] = stack.dvNRuns; pDv[3] = stack.dvNDistinct;
         pDv[4] = stack.dvL; pDv[5] = stack.dvLLanes; pDv[6] = stack.dvLRuns; pDv[7] = stack.dvLDistinct;
-        for (int k = 0; k < 2; k++) { pSt[k] = stack.wsU[k]; pSt[2 + k] = stack.wsD[k]; pSt[4 + k] = stack.wsF[k]; pSt[6 + k] = stack.lsU[k]; }
+        for (int k = 0; k < 2; k++) { pSt[k] = stack.wsU[k]; pSt[2 + k] = stack.wsD[k]; pSt[4 + k] = stack.wsF[k]; pSt[6 + k] = stack.lsU[k]; pSt[8 + k] = stack.wsFA[k]; }
 #endif
         const uint32_t packed = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xFF000000u;
         // where the pixel goes: recomputed from a fresh lane index, so that nothing of it is held (it was spilled) during the traversal
@@ -212,8 +212,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SPLIT ? 5 : 
 #if CRT_PROF
     if (p.counters) {
         // node steps by kind (Stack::stepStat): [19 + k] scalar path, [21 + k] divergent first step, [23 + k] follow-on step,
-        // [25 + k] lane-steps on the scalar path; k = 0 closest hit, 1 any hit
-        for (int i = 0; i < 8; i++) {
+        // [25 + k] lane-steps on the scalar path, [27 + k] follow-on steps whose lanes all stand on one node; k = 0 closest
+        // hit, 1 any hit
+        for (int i = 0; i < 10; i++) {
             const uint32_t sum = waveSum(pSt[i]);
             if (lane == 0 && sum) atomicAdd(&p.counters[19 + i], static_cast<unsigned long long>(sum));
         }

@@ -133,14 +133,42 @@ __device__ __forceinline__ Ray makeRay(F3 o, F3 d)
     return r;
 }
 
+// Correctly rounded 1 / d without the IEEE division sequence (2 v_div_scale, v_rcp, 6 fma / mul, v_div_fmas, v_div_fixup):
+// v_rcp_f32 (1 ulp) and one Newton step written out, fmaf(-d, y, 1) then fmaf(e, y, y).  rcpFastOk names the inputs on
+// which that form is bit for bit the division: biased exponent 1..252 (no zero, denormal, inf or NaN, and |d| < 2^126, so
+// that 1 / d is normal).  Decided by comparing all 2^32 inputs with the device's 1.0f / d (crt_debug_check_rcp,
+// tests/test_rcp_exact.py): outside that range the Newton form differs, inside it never does -- the all-ones significands
+// included.  A wavefront with any lane outside the range takes the division for all its lanes: a
+// wave-uniform branch, not a per-lane select (which would run both forms).
+__device__ __forceinline__ bool rcpFastOk(float d)
+{
+    return (__float_as_uint(d) << 1) - 0x01000000u < 0xFC000000u;
+}
+__device__ __forceinline__ float rcpNewton(float d)
+{
+    const float y = __builtin_amdgcn_rcpf(d);
+    const float e = fmaf(-d, y, 1.0f);
+    return fmaf(e, y, y);
+}
+__device__ __forceinline__ float rcpExact(float d)
+{
+    // the division is the cold path: laid out away from the loops (inline, the icosphere soup frame lost 1.8 %)
+    if (__builtin_expect(__ballot(!rcpFastOk(d)) == 0ull, 1)) return rcpNewton(d);
+    return 1.0f / d;
+}
+
 // Moeller-Trumbore, two sided; u = weight of v1, v = weight of v2.  NaN/inf from det == 0 fail the compares.
+// SHORT: 1 / det by rcpExact or by the division.  Only the render kernel's closest-hit leaves (DEC) take the short form;
+// any-hit leaves, the path kernel and the ray queries keep the division (measured, DESIGN section 5: the short form gained
+// nothing there -- shadow rays: 5M-triangle frame +3 %, path tracing +0.9 %).
+template <bool SHORT>
 __device__ __forceinline__ bool triTest(const Ray& r, const float4 a, const float4 b, const float4 c, float tmin,
                                         float& t, float& u, float& v)
 {
     const F3 e1 = f3(b.x, b.y, b.z), e2 = f3(c.x, c.y, c.z);
     const F3 p = cross3(r.d, e2);
     const float det = dot3(e1, p);
-    const float inv = 1.0f / det;
+    const float inv = SHORT ? rcpExact(det) : 1.0f / det; // = 1.0f / det, bit for bit
     const F3 s = sub3(r.o, f3(a.x, a.y, a.z));
     u = dot3(s, p) * inv;
     const F3 q = cross3(s, e1);
@@ -167,6 +195,12 @@ struct Stack {
     // step of a scheduling decision, follow-on steps (early-fetched, per lane); lane-steps on the scalar path.  Counted once
     // per wavefront (by its first active lane), so a sum over lanes counts wavefront steps.
     uint32_t wsU[2] = { 0, 0 }, wsD[2] = { 0, 0 }, wsF[2] = { 0, 0 }, lsU[2] = { 0, 0 };
+    // follow-on steps whose active lanes all stand on one node (could take the scalar path)
+    uint32_t wsFA[2] = { 0, 0 };
+    __device__ __forceinline__ void agreeStat(int cur, int kind)
+    {
+        if (__ballot(cur != __builtin_amdgcn_readfirstlane(cur)) == 0ull) stepStat(wsFA, kind);
+    }
     __device__ __forceinline__ void stepStat(uint32_t* ws, int kind)
     {
         const uint32_t lane = threadIdx.x & 63u;
@@ -455,11 +489,13 @@ __device__ __forceinline__ auto loadUniformStep(const float4* nodes, const float
 #define CRT_DIV_STATS_LEAF stack.divStats(cur, stack.dvL, stack.dvLLanes, stack.dvLRuns, stack.dvLDistinct);
 #define CRT_STEP_STAT(WS, STEP) stack.stepStat(stack.WS, CRT_STEP_KIND_##STEP);
 #define CRT_UNIFORM_STEP_STAT(STEP) CRT_STEP_STAT(wsU, STEP) stack.lsU[CRT_STEP_KIND_##STEP]++;
+#define CRT_AGREE_STAT(STEP) stack.agreeStat(cur, CRT_STEP_KIND_##STEP);
 #else
 #define CRT_DIV_STATS_NODE
 #define CRT_DIV_STATS_LEAF
 #define CRT_STEP_STAT(WS, STEP)
 #define CRT_UNIFORM_STEP_STAT(STEP)
+#define CRT_AGREE_STAT(STEP)
 #endif
 // One node step of the lanes standing on inner nodes (called with exactly those lanes active): through the scalar cache
 // when they all stand on the same node, per lane otherwise.
@@ -494,6 +530,7 @@ __device__ __forceinline__ auto loadUniformStep(const float4* nodes, const float
         _Pragma("unroll") for (int rep = 1; rep < NODE_STEPS; rep++) {                                                         \
             if (L::inner(cur)) {                                                                                               \
                 CRT_STEP_STAT(wsF, STEP)                                                                                       \
+                CRT_AGREE_STAT(STEP)                                                                                           \
                 const typename L::Node ndCur = ndNext;                                                                         \
                 if (rep + 1 < NODE_STEPS) L::template STEP<COUNT, OCT, true>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);   \
                 else L::template STEP<COUNT, OCT, false>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);           \
@@ -571,7 +608,7 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
                 loadTriUniform(L::triPtr(tris, id), a, b, c);
                 if (COUNT) cntTris++;
                 float t, u, v;
-                if (triTest(r, a, b, c, tmin, t, u, v)) {
+                if (triTest<DEC>(r, a, b, c, tmin, t, u, v)) {
                     const uint32_t gid = __float_as_uint(c.w);
                     if ((t < h.t) | ((t == h.t) & (gid < h.gid))) {
                         h.t = t; h.u = u; h.v = v; h.tri = id; h.gid = gid;
@@ -594,14 +631,14 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
                 const float4 a1 = T1[0], b1 = T1[1], c1 = T1[2];
                 if (COUNT) cntTris += two ? 2u : 1u;
                 float t, u, v;
-                if (triTest(r, a, b, c, tmin, t, u, v)) {
+                if (triTest<DEC>(r, a, b, c, tmin, t, u, v)) {
                     const uint32_t gid = __float_as_uint(c.w);
                     if ((t < h.t) | ((t == h.t) & (gid < h.gid))) {
                         h.t = t; h.u = u; h.v = v; h.tri = id; h.gid = gid;
                         tcull = t * kCullPad;
                     }
                 }
-                if (two & triTest(r, a1, b1, c1, tmin, t, u, v)) {
+                if (two & triTest<DEC>(r, a1, b1, c1, tmin, t, u, v)) {
                     const uint32_t gid = __float_as_uint(c1.w);
                     if ((t < h.t) | ((t == h.t) & (gid < h.gid))) {
                         h.t = t; h.u = u; h.v = v; h.tri = id1; h.gid = gid;
@@ -616,7 +653,7 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
                 const float4 a = T[0], b = T[1], c = T[2];
                 if (COUNT) cntTris++;
                 float t, u, v;
-                if (triTest(r, a, b, c, tmin, t, u, v)) {
+                if (triTest<DEC>(r, a, b, c, tmin, t, u, v)) {
                     const uint32_t gid = __float_as_uint(c.w);
                     if ((t < h.t) | ((t == h.t) & (gid < h.gid))) {
                         h.t = t; h.u = u; h.v = v; h.tri = id; h.gid = gid;
@@ -690,7 +727,7 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
                 loadTriUniform(L::triPtr(tris, L::triId(ufirst, i)), a, b, c);
                 if (COUNT) cntTris++;
                 float t, u, v;
-                if (triTest(r, a, b, c, tmin, t, u, v) & (t < tmax)) {
+                if (triTest<false>(r, a, b, c, tmin, t, u, v) & (t < tmax)) {
                     occluded = true;
                     break;
                 }
@@ -702,7 +739,7 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
             const float4 a = T[0], b = T[1], c = T[2];
             if (COUNT) cntTris++;
             float t, u, v;
-            if (triTest(r, a, b, c, tmin, t, u, v) & (t < tmax)) {
+            if (triTest<false>(r, a, b, c, tmin, t, u, v) & (t < tmax)) {
                 occluded = true;
                 break;
             }

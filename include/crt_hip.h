@@ -249,6 +249,11 @@ int crt_debug_read_timeline(crt_ctx* ctx, unsigned long long* out, size_t max_wo
 /* raw device counters of the last counting render: [0] nodes [1] triangles [2] shadow rays [3] closest-hit rays; [4..31]
  * are filled only by the CRT_PROF diagnostic build of the kernels (tools/prof_build.sh, meanings in tools/prof_run.py) */
 int crt_debug_read_counters(crt_ctx* ctx, unsigned long long out[32]);
+/* self-check of the device arithmetic the triangle test relies on: its short reciprocal against the correctly rounded
+ * 1.0f / d for all 2^32 inputs, on device device_id.  out[0] mismatches (0 expected), [1] inputs checked (2^32), [2..5]
+ * mismatches of the unguarded Newton form by class (biased exponent 0 / 253..255 / all-ones significand / the rest), [6]
+ * smallest mismatching input or ~0.  Synchronous; a few milliseconds of GPU time. */
+int crt_debug_check_rcp(int device_id, unsigned long long out[8]);
 
 /* stream plumbing: run on an external hipStream_t (e.g. torch's current stream; NULL = HIP's default stream);
  * crt_reset_stream goes back to the context's private non-blocking stream */

@@ -61,6 +61,8 @@ def main():
             if u + dv + fo > 0:  # wavefront node steps: scalar path (decoded planes) / divergent first step / follow-on step
                 print("   %-27s wavefront node steps %d: scalar path %d (%.1f%%, %.1f lanes), divergent first %d (%.1f%%), follow-on %d (%.1f%%)" % (
                     name, u + dv + fo, u, 100 * u / (u + dv + fo), lu / max(u, 1), dv, 100 * dv / (u + dv + fo), fo, 100 * fo / (u + dv + fo)))
+                if fo > 0:  # follow-on steps whose lanes all stand on one node (the scalar path in octant-specialised loops)
+                    print("   %-27s follow-on steps on one node %d (%.1f%% of the follow-on steps)" % ("", c[27 + k], 100 * c[27 + k] / fo))
 
 
 if __name__ == "__main__":
