@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "crt_set_accumulation", "crt_reset_accumulation", "crt_accumulated_samples",
     "crt_trace_rays_device", "crt_occluded_rays_device", "crt_trace_rays", "crt_occluded_rays",
     "crt_update_vertices", "crt_update_vertices_device", "crt_set_mesh_transform", "crt_refit", "crt_mesh_vertices",
+    "crt_rebuild",
 ]
 
 
@@ -207,6 +208,7 @@ def lib():
         "crt_set_mesh_transform": (C.c_int, [vp, u32, vp]),
         "crt_refit": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "crt_mesh_vertices": (C.c_int, [vp, u32, vp, vp]),
+        "crt_rebuild": (C.c_int, [vp, C.POINTER(C.c_double)]),
     }
     assert set(sig) == set(ABI_SYMBOLS)
     for name, (res, args) in sig.items():
@@ -643,6 +645,13 @@ class Renderer:
         """apply pending updates now; returns the refit's device time in ms (0 when nothing was pending)"""
         ms = C.c_double()
         self._ok(lib().crt_refit(self.h, C.byref(ms)), "crt_refit")
+        return ms.value
+
+    def rebuild(self):
+        """apply pending updates and build a new tree on the GPU from the world vertices (builder: option "gpu_builder", 0 = LBVH,
+        1 = PLOC); returns the rebuild's device time in ms"""
+        ms = C.c_double()
+        self._ok(lib().crt_rebuild(self.h, C.byref(ms)), "crt_rebuild")
         return ms.value
 
     def mesh_vertices(self, mesh):

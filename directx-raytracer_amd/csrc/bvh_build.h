@@ -46,8 +46,31 @@ void buildBvh(const crt_mesh_view* meshes, uint32_t n_meshes, Bvh& out);
 // shared first step of both builders (see bvh_build.cpp)
 void flattenMeshes(const crt_mesh_view* meshes, uint32_t n_meshes, std::vector<crt_bvh_tri>& inTri, std::vector<crt_bvh_shade>& inShade,
                    std::vector<float>& boxCent);
-// LBVH on the GPU (bvh_gpu.hip): same output layout, lower quality, much faster; throws std::runtime_error on HIP errors
-void buildBvhGpu(const crt_mesh_view* meshes, uint32_t n_meshes, Bvh& out, struct ihipStream_t* stream, double* device_ms);
+// the GPU builders (option "gpu_builder"): Karras LBVH (bvh_gpu.hip) or PLOC (bvh_ploc.hip)
+constexpr int kGpuBuilderLbvh = 0;
+constexpr int kGpuBuilderPloc = 1;
+// GPU build (bvh_gpu.hip): same output layout as buildBvh, lower quality, much faster; throws std::runtime_error on HIP errors
+void buildBvhGpu(const crt_mesh_view* meshes, uint32_t n_meshes, Bvh& out, struct ihipStream_t* stream, double* device_ms,
+                 int builder = kGpuBuilderLbvh);
+// meshes already in HBM, as mesh_table.hip.h lays them out: the input of a rebuild (crt_rebuild)
+struct GpuMeshes {
+    const void* table = nullptr;     // MeshEntry per mesh + terminator
+    uint32_t nMeshes = 0, n = 0;     // meshes, triangles
+    const float* xyz = nullptr;      // 3 per vertex, world space
+    const uint32_t* idx = nullptr;   // 3 per triangle, mesh-local
+    const float* normals = nullptr;  // 3 per vertex or NULL
+    const float* uvsIn = nullptr;    // 3 per vertex (u, v, unused) or NULL: no uv records
+};
+// the same build from meshes in HBM (n > kLeafMax); out as buildBvhGpu leaves it
+void rebuildBvhGpu(const GpuMeshes& in, int builder, Bvh& out, struct ihipStream_t* stream, double* device_ms);
+// exclusive prefix sum of n uint32 counts on the device (gpu_sort.hip.h, whose kernels live in bvh_gpu.hip); tileSums holds
+// deviceScanScratchBytes(n); returns the first launch error (a hipError_t)
+int deviceExclusiveSum(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* tileSums, struct ihipStream_t* stream);
+size_t deviceScanScratchBytes(uint32_t n);
+// PLOC's tree (bvh_ploc.hip) from the Morton-sorted keys (gid in the low dword) and the per-gid triangle boxes (min xyz, max xyz):
+// the binary nodes in DFS pre-order at *nodes (hipMalloc'ed here, returned count) and the keys in leaf order at leafKeys[0..n)
+uint32_t plocBuildGpu(const unsigned long long* sortedKeys, const float* triBoxes, uint32_t n, unsigned long long* leafKeys, void** nodes,
+                      struct ihipStream_t* stream);
 // per-triangle uvs in input (gid) order, empty when no mesh has any; and their permutation to leaf order
 void flattenUvs(const crt_mesh_view* meshes, uint32_t n_meshes, std::vector<crt_bvh_uv>& inUv);
 void reorderUvs(const std::vector<crt_bvh_uv>& inUv, Bvh& bvh);

@@ -10,6 +10,8 @@
 // Cubic Morton cells and leaves of at most 2 triangles (per-axis scaling and the SAH builder's 4-triangle leaves measured +36 %
 // node fetches and +94 % triangle tests against the SAH tree on the 1M-triangle frame; now +18 % / -13 %).  It is the fast
 // option (option "gpu_build": 8.7 ms against 360 ms at 1M triangles), not the default.
+// Option "gpu_builder" = 1 swaps the Karras hierarchy for PLOC (bvh_ploc.hip) on the same sorted keys; buildFromDevice holds
+// both and starts from meshes already in HBM, so the rebuild of a dynamic scene (crt_rebuild) runs the same code as an upload.
 #include "bvh_build.h"
 #include "bvh_wide.h"
 #include "mesh_table.hip.h"
@@ -22,6 +24,7 @@
 #include <chrono>
 #include <climits>
 #include <cstring>
+#include <functional>
 #include <stdexcept>
 #include <string>
 
@@ -495,8 +498,121 @@ void collapseWideGpu(const crt_bvh_node* nodes, uint32_t nBinary, void* scratch,
     if (maxDepthOut) *maxDepthOut = maxDepth;
 }
 
-void buildBvhGpu(const crt_mesh_view* meshes, uint32_t n_meshes, Bvh& out, ihipStream_t* stream, double* device_ms)
+namespace {
+
+// Morton order, the builder's binary tree, the leaf-ordered records and the wide tree, from meshes already in HBM (n > kLeafMax)
+void buildFromDevice(const GpuMeshes& in, int builder, Bvh& out, ihipStream_t* stream, double* device_ms, const std::function<void(const char*)>& lap)
 {
+    const bool timing = std::getenv("CRT_BUILD_TIMING") != nullptr;
+    const uint32_t n = in.n, n_meshes = in.nMeshes, nInternal = n - 1;
+    const MeshEntry* table = static_cast<const MeshEntry*>(in.table);
+    DevBuf dBad(sizeof(int));
+    DevBuf dBox(sizeof(Box6) * n), dCent(sizeof(float) * 3 * n), dBounds(sizeof(int) * 6);
+    DevBuf dKeysIn(sizeof(unsigned long long) * n), dKeys(sizeof(unsigned long long) * n);
+    // the records the kernels will traverse (+64 bytes of slack for speculative wide loads of the last record)
+    DevBuf dTris(sizeof(crt_bvh_tri) * n + 64), dShade(sizeof(crt_bvh_shade) * n + 64), dUvs(in.uvsIn ? sizeof(crt_bvh_uv) * n + 64 : 0);
+    // scratch of the sort (digit counts per tile) and of the scan (tile sums); both written by this file's own kernels (gpu_sort.hip.h)
+    DevBuf dSortCounts(sizeof(uint32_t) * gpusort::sortScratchWords(n)), dScanSums(gpusort::scanScratchBytes(nInternal));
+    GPU_TRY(hipMemsetAsync(dBad.p, 0, sizeof(int), stream));
+
+    struct Events { // destroyed on every way out, exceptions included
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events()
+        {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+    } ev;
+    GPU_TRY(hipEventCreate(&ev.e0));
+    GPU_TRY(hipEventCreate(&ev.e1));
+    hipEvent_t e0 = ev.e0, e1 = ev.e1;
+    GPU_TRY(hipEventRecord(e0, stream));
+    const dim3 blk(256), grdN((n + 255) / 256), grdI((nInternal + 255) / 256);
+    hipLaunchKernelGGL(triBoxKernel, grdN, blk, 0, stream, table, n_meshes, in.xyz, in.idx, n, dBox.as<Box6>(), dCent.as<float>(), dBad.as<int>());
+    hipLaunchKernelGGL(initBoundsKernel, dim3(1), dim3(64), 0, stream, dBounds.as<int>());
+    hipLaunchKernelGGL(boundsKernel, dim3(kBoundsBlocks), blk, 0, stream, dCent.as<float>(), n, dBounds.as<int>());
+    // keys = Morton code << 32 | ordinal, written in ordinal order: a stable sort on the four bytes of the high dword orders the full keys;
+    // four passes ping-pong dKeys -> dKeysIn -> ... and end in dKeys
+    hipLaunchKernelGGL(mortonKernel, grdN, blk, 0, stream, dCent.as<float>(), n, dBounds.as<int>(), dKeys.as<unsigned long long>());
+    GPU_TRY(hipGetLastError()); // triBox / bounds / Morton launches
+    hipError_t sortStatus = hipSuccess;
+    unsigned long long* sorted = gpusort::sortKeysHigh(dKeys.as<unsigned long long>(), dKeysIn.as<unsigned long long>(), n, 4, dSortCounts.as<uint32_t>(), stream, &sortStatus);
+    GPU_TRY(sortStatus);
+    if (sorted != dKeys.as<unsigned long long>()) throw std::logic_error("sorted keys expected in the first buffer");
+    void* binNodes = nullptr; // the binary tree in DFS pre-order, handed to `out` at the end
+    struct OwnedNodes { void*& p; ~OwnedNodes() { if (p) (void)hipFree(p); } } ownedNodes{ binNodes };
+    uint32_t nKept = 0;
+    const unsigned long long* leafKeys = dKeys.as<unsigned long long>(); // leaf position -> key (gid in the low dword)
+    if (builder == kGpuBuilderPloc) {
+        int bad = 0;
+        GPU_TRY(hipMemcpyAsync(&bad, dBad.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        GPU_TRY(hipStreamSynchronize(stream));
+        if (bad) throw std::runtime_error("triangle index out of range");
+        nKept = plocBuildGpu(dKeys.as<unsigned long long>(), dBox.as<float>(), n, dKeysIn.as<unsigned long long>(), &binNodes, stream);
+        leafKeys = dKeysIn.as<unsigned long long>();
+    } else {
+        DevBuf dK(sizeof(KNode) * nInternal), dParI(sizeof(int) * nInternal), dParL(sizeof(int) * n);
+        DevBuf dNodeBox(sizeof(Box6) * nInternal), dFlags(sizeof(unsigned int) * nInternal);
+        DevBuf dKept(sizeof(uint32_t) * nInternal), dRank(sizeof(uint32_t) * nInternal);
+        hipLaunchKernelGGL(hierarchyKernel, grdI, blk, 0, stream, dKeys.as<unsigned long long>(), n, dK.as<KNode>(), dParI.as<int>(), dParL.as<int>());
+        GPU_TRY(hipMemsetAsync(dFlags.p, 0, sizeof(unsigned int) * nInternal, stream));
+        hipLaunchKernelGGL(fitKernel, grdN, blk, 0, stream, dK.as<KNode>(), dBox.as<Box6>(), dKeys.as<unsigned long long>(), n, dParI.as<int>(),
+                           dParL.as<int>(), dNodeBox.as<Box6>(), dFlags.as<unsigned int>());
+        hipLaunchKernelGGL(keptKernel, grdI, blk, 0, stream, dK.as<KNode>(), nInternal, dKept.as<uint32_t>());
+        GPU_TRY(hipGetLastError()); // hierarchy / fit / kept launches
+        GPU_TRY(gpusort::exclusiveSum(dKept.as<uint32_t>(), dRank.as<uint32_t>(), nInternal, dScanSums.as<uint32_t>(), stream));
+        uint32_t lastKept = 0, lastRank = 0;
+        int bad = 0;
+        GPU_TRY(hipMemcpyAsync(&lastKept, dKept.as<uint32_t>() + (nInternal - 1), 4, hipMemcpyDeviceToHost, stream));
+        GPU_TRY(hipMemcpyAsync(&lastRank, dRank.as<uint32_t>() + (nInternal - 1), 4, hipMemcpyDeviceToHost, stream));
+        GPU_TRY(hipMemcpyAsync(&bad, dBad.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        GPU_TRY(hipStreamSynchronize(stream));
+        if (bad) throw std::runtime_error("triangle index out of range");
+        nKept = lastKept + lastRank;
+        GPU_TRY(hipMalloc(&binNodes, sizeof(crt_bvh_node) * nKept));
+        hipLaunchKernelGGL(emitKernel, grdI, blk, 0, stream, dK.as<KNode>(), dKept.as<uint32_t>(), dRank.as<uint32_t>(), dNodeBox.as<Box6>(), dBox.as<Box6>(),
+                           dKeys.as<unsigned long long>(), nInternal, static_cast<crt_bvh_node*>(binNodes));
+        GPU_TRY(hipGetLastError());
+        GPU_TRY(hipStreamSynchronize(stream)); // the Karras scratch dies with this scope
+    }
+    hipLaunchKernelGGL(gatherKernel, grdN, blk, 0, stream, leafKeys, n, table, n_meshes, in.xyz, in.idx, in.normals, in.uvsIn, dTris.as<crt_bvh_tri>(),
+                       dShade.as<crt_bvh_shade>(), in.uvsIn ? dUvs.as<crt_bvh_uv>() : nullptr);
+    GPU_TRY(hipGetLastError());
+    if (timing) { GPU_TRY(hipStreamSynchronize(stream)); }
+    lap("device build");
+    // ---- collapse to the 4-wide tree and quantise, still on the device
+    DevBuf dScratch(collapseScratchBytes(nKept));
+    uint32_t nWide = 0, depth4 = 0, maxDepth = 0;
+    void* wide[2] = { nullptr, nullptr }; // allocated by the collapse at their exact size
+    struct Owned { void** p; ~Owned() { for (int i = 0; i < 2; i++) if (p[i]) (void)hipFree(p[i]); } } owned{ wide };
+    collapseWideGpu(static_cast<const crt_bvh_node*>(binNodes), nKept, dScratch.p, &wide[0], &wide[1], stream, &nWide, &depth4, &maxDepth);
+    GPU_TRY(hipEventRecord(e1, stream));
+    GPU_TRY(hipStreamSynchronize(stream));
+    float ms = 0.f;
+    GPU_TRY(hipEventElapsedTime(&ms, e0, e1));
+    if (device_ms) *device_ms = ms;
+    lap("device collapse + quantise");
+    out.maxDepth = maxDepth;
+    out.depth4 = depth4;
+    out.nNodes = nKept;
+    out.nNodes4 = nWide;
+    out.devNodes = binNodes;
+    binNodes = nullptr;
+    out.devNodes4 = wide[0];
+    out.devNodes4q = wide[1];
+    wide[0] = wide[1] = nullptr;
+    // the leaf-ordered records stay in HBM: the caller adopts the buffers (and copies them out only if someone asks)
+    out.nTris = n;
+    out.devTris = dTris.release();
+    out.devShade = dShade.release();
+    out.devUvs = in.uvsIn ? dUvs.release() : nullptr;
+}
+
+} // namespace
+
+void buildBvhGpu(const crt_mesh_view* meshes, uint32_t n_meshes, Bvh& out, ihipStream_t* stream, double* device_ms, int builder)
+{
+    if (builder != kGpuBuilderLbvh && builder != kGpuBuilderPloc) throw std::runtime_error("unknown GPU builder");
     const bool timing = std::getenv("CRT_BUILD_TIMING") != nullptr;
     auto tnow = [] { return std::chrono::steady_clock::now(); };
     auto tlast = tnow();
@@ -613,103 +729,41 @@ void buildBvhGpu(const crt_mesh_view* meshes, uint32_t n_meshes, Bvh& out, ihipS
     }
     lap("host concatenate");
 
-    const uint32_t nInternal = n - 1;
     DevBuf dTable(sizeof(MeshEntry) * table.size()), dXyz(sizeof(float) * hXyz.size()), dIdx(sizeof(uint32_t) * hIdx.size());
-    DevBuf dNormals(sizeof(float) * hNormals.size()), dUvsIn(sizeof(float) * hUvs.size()), dBad(sizeof(int));
-    DevBuf dBox(sizeof(Box6) * n), dCent(sizeof(float) * 3 * n), dBounds(sizeof(int) * 6);
-    DevBuf dKeysIn(sizeof(unsigned long long) * n), dKeys(sizeof(unsigned long long) * n);
-    DevBuf dK(sizeof(KNode) * nInternal), dParI(sizeof(int) * nInternal), dParL(sizeof(int) * n);
-    DevBuf dNodeBox(sizeof(Box6) * nInternal), dFlags(sizeof(unsigned int) * nInternal);
-    DevBuf dKept(sizeof(uint32_t) * nInternal), dRank(sizeof(uint32_t) * nInternal);
-    // the records the kernels will traverse (+64 bytes of slack for speculative wide loads of the last record)
-    DevBuf dTris(sizeof(crt_bvh_tri) * n + 64), dShade(sizeof(crt_bvh_shade) * n + 64), dUvs(anyUvs ? sizeof(crt_bvh_uv) * n + 64 : 0);
-    // scratch of the sort (digit counts per tile) and of the scan (tile sums); both written by this file's own kernels (gpu_sort.hip.h)
-    DevBuf dSortCounts(sizeof(uint32_t) * gpusort::sortScratchWords(n)), dScanSums(gpusort::scanScratchBytes(nInternal));
-
+    DevBuf dNormals(sizeof(float) * hNormals.size()), dUvsIn(sizeof(float) * hUvs.size());
     GPU_TRY(hipMemcpyAsync(dTable.p, table.data(), sizeof(MeshEntry) * table.size(), hipMemcpyHostToDevice, stream));
     GPU_TRY(hipMemcpyAsync(dXyz.p, hXyz.data(), sizeof(float) * hXyz.size(), hipMemcpyHostToDevice, stream));
     GPU_TRY(hipMemcpyAsync(dIdx.p, hIdx.data(), sizeof(uint32_t) * hIdx.size(), hipMemcpyHostToDevice, stream));
     if (anyNormals) GPU_TRY(hipMemcpyAsync(dNormals.p, hNormals.data(), sizeof(float) * hNormals.size(), hipMemcpyHostToDevice, stream));
     if (anyUvs) GPU_TRY(hipMemcpyAsync(dUvsIn.p, hUvs.data(), sizeof(float) * hUvs.size(), hipMemcpyHostToDevice, stream));
-    GPU_TRY(hipMemsetAsync(dBad.p, 0, sizeof(int), stream));
     if (timing) { GPU_TRY(hipStreamSynchronize(stream)); }
     lap("alloc + H2D meshes");
-
-    struct Events { // destroyed on every way out, exceptions included
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events()
-        {
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-        }
-    } ev;
-    GPU_TRY(hipEventCreate(&ev.e0));
-    GPU_TRY(hipEventCreate(&ev.e1));
-    hipEvent_t e0 = ev.e0, e1 = ev.e1;
-    GPU_TRY(hipEventRecord(e0, stream));
-    const dim3 blk(256), grdN((n + 255) / 256), grdI((nInternal + 255) / 256);
-    hipLaunchKernelGGL(triBoxKernel, grdN, blk, 0, stream, dTable.as<MeshEntry>(), n_meshes, dXyz.as<float>(), dIdx.as<uint32_t>(), n, dBox.as<Box6>(),
-                       dCent.as<float>(), dBad.as<int>());
-    hipLaunchKernelGGL(initBoundsKernel, dim3(1), dim3(64), 0, stream, dBounds.as<int>());
-    hipLaunchKernelGGL(boundsKernel, dim3(kBoundsBlocks), blk, 0, stream, dCent.as<float>(), n, dBounds.as<int>());
-    // keys = Morton code << 32 | ordinal, written in ordinal order: a stable sort on the four bytes of the high dword orders the full keys;
-    // four passes ping-pong dKeys -> dKeysIn -> ... and end in dKeys
-    hipLaunchKernelGGL(mortonKernel, grdN, blk, 0, stream, dCent.as<float>(), n, dBounds.as<int>(), dKeys.as<unsigned long long>());
-    GPU_TRY(hipGetLastError()); // triBox / bounds / Morton launches
-    hipError_t sortStatus = hipSuccess;
-    unsigned long long* sorted = gpusort::sortKeysHigh(dKeys.as<unsigned long long>(), dKeysIn.as<unsigned long long>(), n, 4, dSortCounts.as<uint32_t>(), stream, &sortStatus);
-    GPU_TRY(sortStatus);
-    if (sorted != dKeys.as<unsigned long long>()) throw std::logic_error("sorted keys expected in the first buffer");
-    hipLaunchKernelGGL(hierarchyKernel, grdI, blk, 0, stream, dKeys.as<unsigned long long>(), n, dK.as<KNode>(), dParI.as<int>(), dParL.as<int>());
-    GPU_TRY(hipMemsetAsync(dFlags.p, 0, sizeof(unsigned int) * nInternal, stream));
-    hipLaunchKernelGGL(fitKernel, grdN, blk, 0, stream, dK.as<KNode>(), dBox.as<Box6>(), dKeys.as<unsigned long long>(), n, dParI.as<int>(),
-                       dParL.as<int>(), dNodeBox.as<Box6>(), dFlags.as<unsigned int>());
-    hipLaunchKernelGGL(keptKernel, grdI, blk, 0, stream, dK.as<KNode>(), nInternal, dKept.as<uint32_t>());
-    GPU_TRY(hipGetLastError()); // hierarchy / fit / kept launches
-    GPU_TRY(gpusort::exclusiveSum(dKept.as<uint32_t>(), dRank.as<uint32_t>(), nInternal, dScanSums.as<uint32_t>(), stream));
-    uint32_t lastKept = 0, lastRank = 0;
-    int bad = 0;
-    GPU_TRY(hipMemcpyAsync(&lastKept, dKept.as<uint32_t>() + (nInternal - 1), 4, hipMemcpyDeviceToHost, stream));
-    GPU_TRY(hipMemcpyAsync(&lastRank, dRank.as<uint32_t>() + (nInternal - 1), 4, hipMemcpyDeviceToHost, stream));
-    GPU_TRY(hipMemcpyAsync(&bad, dBad.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-    GPU_TRY(hipStreamSynchronize(stream));
-    if (bad) throw std::runtime_error("triangle index out of range");
-    const uint32_t nKept = lastKept + lastRank;
-    DevBuf dNodes(sizeof(crt_bvh_node) * nKept);
-    hipLaunchKernelGGL(emitKernel, grdI, blk, 0, stream, dK.as<KNode>(), dKept.as<uint32_t>(), dRank.as<uint32_t>(), dNodeBox.as<Box6>(), dBox.as<Box6>(),
-                       dKeys.as<unsigned long long>(), nInternal, dNodes.as<crt_bvh_node>());
-    hipLaunchKernelGGL(gatherKernel, grdN, blk, 0, stream, dKeys.as<unsigned long long>(), n, dTable.as<MeshEntry>(), n_meshes, dXyz.as<float>(),
-                       dIdx.as<uint32_t>(), dNormals.as<float>(), dUvsIn.as<float>(), dTris.as<crt_bvh_tri>(), dShade.as<crt_bvh_shade>(),
-                       anyUvs ? dUvs.as<crt_bvh_uv>() : nullptr);
-    GPU_TRY(hipGetLastError());
-    if (timing) { GPU_TRY(hipStreamSynchronize(stream)); }
-    lap("device build");
-    // ---- collapse to the 4-wide tree and quantise, still on the device
-    DevBuf dScratch(collapseScratchBytes(nKept));
-    uint32_t nWide = 0, depth4 = 0, maxDepth = 0;
-    void* wide[2] = { nullptr, nullptr }; // allocated by the collapse at their exact size
-    struct Owned { void** p; ~Owned() { for (int i = 0; i < 2; i++) if (p[i]) (void)hipFree(p[i]); } } owned{ wide };
-    collapseWideGpu(dNodes.as<crt_bvh_node>(), nKept, dScratch.p, &wide[0], &wide[1], stream, &nWide, &depth4, &maxDepth);
-    GPU_TRY(hipEventRecord(e1, stream));
-    GPU_TRY(hipStreamSynchronize(stream));
-    float ms = 0.f;
-    GPU_TRY(hipEventElapsedTime(&ms, e0, e1));
-    if (device_ms) *device_ms = ms;
-    lap("device collapse + quantise");
-    out.maxDepth = maxDepth;
-    out.depth4 = depth4;
-    out.nNodes = nKept;
-    out.nNodes4 = nWide;
-    out.devNodes = dNodes.release();
-    out.devNodes4 = wide[0];
-    out.devNodes4q = wide[1];
-    wide[0] = wide[1] = nullptr;
-    // the leaf-ordered records stay in HBM: the caller adopts the buffers (and copies them out only if someone asks)
-    out.nTris = n;
-    out.devTris = dTris.release();
-    out.devShade = dShade.release();
-    out.devUvs = anyUvs ? dUvs.release() : nullptr;
+    GpuMeshes in;
+    in.table = dTable.p;
+    in.nMeshes = n_meshes;
+    in.n = n;
+    in.xyz = dXyz.as<float>();
+    in.idx = dIdx.as<uint32_t>();
+    in.normals = dNormals.as<float>();
+    in.uvsIn = anyUvs ? dUvsIn.as<float>() : nullptr;
+    buildFromDevice(in, builder, out, stream, device_ms, lap);
 }
+
+void rebuildBvhGpu(const GpuMeshes& in, int builder, Bvh& out, ihipStream_t* stream, double* device_ms)
+{
+    if (builder != kGpuBuilderLbvh && builder != kGpuBuilderPloc) throw std::runtime_error("unknown GPU builder");
+    if (in.n <= static_cast<uint32_t>(kLeafMax)) throw std::logic_error("rebuildBvhGpu: more than kLeafMax triangles expected");
+    out = Bvh();
+    if (device_ms) *device_ms = 0.0;
+    buildFromDevice(in, builder, out, stream, device_ms, [](const char*) {});
+}
+
+int deviceExclusiveSum(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* tileSums, ihipStream_t* stream)
+{
+    return static_cast<int>(gpusort::exclusiveSum(in, out, n, tileSums, stream));
+}
+
+size_t deviceScanScratchBytes(uint32_t n) { return gpusort::scanScratchBytes(n); }
 
 int launchDecodePlanes(const void* nodes4q, uint32_t n, float* planes, ihipStream_t* stream)
 {

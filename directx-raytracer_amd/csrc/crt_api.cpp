@@ -74,7 +74,8 @@ struct crt_ctx {
     uint32_t nTextures = 0;
     uint32_t nLights = 0, nMats = 0;
     bool haveScene = false;
-    bool gpuBuild = false;      // option "gpu_build": LBVH on the device instead of the host SAH builder
+    bool gpuBuild = false;      // option "gpu_build": a build on the device instead of the host SAH builder
+    int gpuBuilder = crt::kGpuBuilderLbvh; // option "gpu_builder": which one, for "gpu_build" uploads and crt_rebuild
     double buildMs = 0.0;       // wall time of the last crt_upload_scene (build + upload)
     double buildDeviceMs = 0.0; // of which GPU kernels (gpu_build only)
     uint32_t sceneSerial = 0;
@@ -886,7 +887,7 @@ int crt_upload_scene(crt_ctx* c, const crt_mesh_view* meshes, uint32_t n_meshes,
     try {
         if (c->gpuBuild) {
             HIP_TRY(c, hipSetDevice(c->device));
-            crt::buildBvhGpu(meshes, n_meshes, built, c->stream, &deviceMs);
+            crt::buildBvhGpu(meshes, n_meshes, built, c->stream, &deviceMs, c->gpuBuilder);
         } else {
             crt::buildBvh(meshes, n_meshes, built);
         }
@@ -1057,6 +1058,10 @@ int crt_set_option(crt_ctx* c, const char* name, int value)
     }
     if (std::strcmp(name, "dynamic") == 0) {
         c->dynamicOpt = value != 0;
+        return CRT_OK;
+    }
+    if (std::strcmp(name, "gpu_builder") == 0 && (value == crt::kGpuBuilderLbvh || value == crt::kGpuBuilderPloc)) {
+        c->gpuBuilder = value;
         return CRT_OK;
     }
     // the 64-byte 4-wide tree is the only layout: 0 names it, any other width is rejected below
@@ -1802,6 +1807,76 @@ int crt_refit(crt_ctx* c, double* device_ms)
     if (!c) return CRT_EINVAL;
     if (!c->haveScene || !c->dyn) return fail(c, CRT_ESTATE, "crt_refit: no scene uploaded with option \"dynamic\" = 1");
     return applyRefit(c, device_ms);
+}
+
+int crt_rebuild(crt_ctx* c, double* device_ms)
+{
+    if (device_ms) *device_ms = 0.0;
+    if (!c) return CRT_EINVAL;
+    if (!c->haveScene || !c->dyn) return fail(c, CRT_ESTATE, "crt_rebuild: no scene uploaded with option \"dynamic\" = 1");
+    if (c->dyn->nTris == 0) return applyRefit(c, device_ms); // no tree to build: the pending updates are all there is
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipDeviceSynchronize()); // frames in flight on any stream the caller used still read the records and the tree
+    crt::Bvh built;
+    struct DevRecords { // the new tree's buffers until the context adopts them
+        crt::Bvh& b;
+        ~DevRecords()
+        {
+            for (void** q : { &b.devTris, &b.devShade, &b.devUvs, &b.devNodes, &b.devNodes4, &b.devNodes4q }) {
+                if (*q) (void)hipFree(*q);
+                *q = nullptr;
+            }
+        }
+    } pending{ built };
+    try {
+        crt::dynamicRebuild(*c->dyn, c->gpuBuilder, static_cast<const crt_bvh_tri*>(c->dTris), c->dUvs, built, c->stream, device_ms);
+    } catch (const std::bad_alloc&) {
+        freeScene(c); // the world vertices may already be moved and the level lists half rewritten: as a failed upload, no scene
+        return fail(c, CRT_ENOMEM, "crt_rebuild: out of host memory");
+    } catch (const std::exception& ex) {
+        freeScene(c);
+        return fail(c, CRT_EHIP, "crt_rebuild failed: %s", ex.what());
+    }
+    // adopt the new tree and records; the wide tree, its quantised form and the plane table get room for one node per binary inner
+    // node, as at a dynamic upload (a refit may collapse to more wide nodes than the build did)
+    void** olds[] = { &c->dBinNodes, &c->dWideNodes, &c->dNodes, &c->dPlanes, &c->dTris, &c->dShade, &c->dUvs };
+    for (void** q : olds) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    c->dBinNodes = built.devNodes;
+    c->dWideNodes = built.devNodes4;
+    c->dNodes = built.devNodes4q;
+    c->dTris = built.devTris;
+    c->dShade = built.devShade;
+    c->dUvs = built.devUvs;
+    built.devNodes = built.devNodes4 = built.devNodes4q = built.devTris = built.devShade = built.devUvs = nullptr;
+    c->bvh.nNodes = built.nNodes;
+    c->bvh.nNodes4 = built.nNodes4;
+    c->bvh.depth4 = built.depth4;
+    c->bvh.maxDepth = built.maxDepth;
+    c->bvh.nTris = built.nTris;
+    const uint32_t cap = built.nNodes ? built.nNodes : 1u, n4 = built.nNodes4;
+    int rc = regrow(c, c->dWideNodes, sizeof(crt_bvh_node4) * n4, sizeof(crt_bvh_node4) * cap);
+    if (!rc) rc = regrow(c, c->dNodes, sizeof(crt_bvh_node4q) * n4, sizeof(crt_bvh_node4q) * cap + 128);
+    if (!rc) {
+        const hipError_t e = hipMalloc(&c->dPlanes, sizeof(float) * crt::kPlaneStride * cap);
+        if (e != hipSuccess) rc = fail(c, CRT_EHIP, "hipMalloc failed: %s", hipGetErrorString(e));
+    }
+    if (!rc) {
+        hipError_t e = static_cast<hipError_t>(crt::launchDecodePlanes(c->dNodes, n4, static_cast<float*>(c->dPlanes), c->stream));
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(c, CRT_EHIP, "plane table: %s", hipGetErrorString(e));
+    }
+    if (!rc) rc = readSceneBox(c);
+    if (rc) {
+        freeScene(c);
+        return rc;
+    }
+    c->sceneSerial++;
+    c->accSamples = 0u;
+    for (uint64_t& k : c->orderKey) k = 0;
+    return CRT_OK;
 }
 
 int crt_mesh_vertices(const crt_ctx* cc, uint32_t mesh, float* xyz, float* normals)

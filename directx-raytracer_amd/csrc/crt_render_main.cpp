@@ -40,6 +40,7 @@ static void usage()
                  "                        camera holds still and start over when it moves; each frame written is the running mean;\n"
                  "                        with --ranks every rank accumulates its own tiles\n"
                  "   [--phong KS_PERMILLE:EXPONENT]       mode 100 specular term\n"
+                 "   [--gpu-build lbvh|ploc]              build the acceleration structure on the GPU with that builder (default: host SAH)\n"
                  "   [--out prefix] [--png] [--count]      frames as prefix_N.ppm, or prefix_N.png with --png\n"
                  "   [--ranks N [--device-base D] [--id-file PATH]]   N processes / GPUs, RCCL gather per frame\n"
                  "   [--host-exchange [--same-device]]   with --ranks: tiles through shared host memory instead of RCCL; --same-device puts every\n"
@@ -52,6 +53,7 @@ struct Args {
     uint32_t mode = 0, w = 1920, h = 1080;
     int frames = 1, device = 0, deviceBase = 0, ranks = 0, rank = -1;
     int spp = -1, bounces = -1, seed = -1, phongKs = -1, phongExp = -1, accumulate = -1;
+    int gpuBuilder = -1; // --gpu-build: -1 = host SAH, 0 = LBVH, 1 = PLOC
     float orbit = 0.f, pitch = 0.f, forward = 0.f, right = 0.f, zoom = 0.f;
     bool count = false, png = false, hostExchange = false, sameDevice = false;
     unsigned long long nonce = 0; // names the launch in the id file (set by the --ranks parent)
@@ -85,6 +87,7 @@ int runRank(const Args& a)
 {
     crt::Renderer renderer;
     const int device = (a.ranks > 0 && !a.sameDevice) ? a.deviceBase + a.rank : a.device;
+    renderer.setGpuBuilder(a.gpuBuilder);
     renderer.prepareForRendering(a.scene, device);
     renderer.setFrameSize(a.w, a.h);
     renderer.changeShadingMode(a.mode);
@@ -255,6 +258,12 @@ int main(int argc, char** argv)
         else if (s == "--phong") { if (std::sscanf(next("--phong"), "%d:%d", &a.phongKs, &a.phongExp) != 2) { usage(); return 2; } }
         else if (s == "--out") a.out = next("--out");
         else if (s == "--count") a.count = true;
+        else if (s == "--gpu-build") {
+            const std::string b = next("--gpu-build");
+            if (b == "lbvh") a.gpuBuilder = 0;
+            else if (b == "ploc") a.gpuBuilder = 1;
+            else { usage(); return 2; }
+        }
         else if (s == "--png") a.png = true;
         else if (s == "--host-exchange") a.hostExchange = true;
         else if (s == "--same-device") a.sameDevice = true;

@@ -1,10 +1,12 @@
 // Dynamic geometry (option "dynamic"): what a scene keeps in HBM so that moved vertices can be refitted into the uploaded tree
-// instead of rebuilding it (refit_kernels.hip; DESIGN.md "Dynamic geometry").  The topology -- triangles, indices, uvs,
-// materials, the binary tree's shape and leaf order -- is fixed at upload; a refit rewrites the vertices' world positions, the
+// instead of rebuilding it (refit_kernels.hip; DESIGN.md "Dynamic geometry"), or a new tree built from them on the GPU
+// (dynamicRebuild).  The topology -- triangles, indices, uvs, materials -- is fixed at upload, the binary tree's
+// shape and leaf order until a rebuild; a refit rewrites the vertices' world positions, the
 // leaf-ordered triangle and shading records, the binary boxes and, by collapsing again, the wide tree and its plane table.
 #pragma once
 
 #include "../../include/crt_hip.h"
+#include "bvh_build.h"
 
 #include <cstdint>
 #include <vector>
@@ -62,5 +64,13 @@ void dynamicInit(DynamicScene& d, const crt_mesh_view* meshes, uint32_t n_meshes
 // The refit of all pending updates, on `stream`; returns when it is done.  *nWide / *depth4: the re-collapsed wide tree;
 // *device_ms: HIP-event time from the first transform to the plane table.  Throws std::runtime_error on HIP errors.
 void dynamicRefit(DynamicScene& d, const RefitTargets& t, ihipStream_t* stream, uint32_t* nWide, uint32_t* depth4, double* device_ms);
+
+// The rebuild (crt_rebuild; d.nTris > 0): the pending updates applied, then a new tree from the world vertices in HBM with the GPU
+// builder `builder` (bvh_build.h kGpuBuilder*).  out: the tree, its wide and quantised forms and the leaf-ordered records, all in HBM
+// (for <= kLeafMax triangles the builders' one-leaf tree is made on the host and uploaded here); whatever out holds belongs to the
+// caller, on success and on failure.  oldTris / oldUvs: the current leaf-ordered records; when oldUvs is set, out.devUvs holds the uv
+// records permuted to the new leaf order by gid.  The level lists and the collapse scratch follow the new tree.  Throws
+// std::runtime_error on HIP errors.
+void dynamicRebuild(DynamicScene& d, int builder, const crt_bvh_tri* oldTris, const void* oldUvs, Bvh& out, ihipStream_t* stream, double* device_ms);
 
 } // namespace crt

@@ -127,7 +127,86 @@ __global__ __launch_bounds__(256) void refitLevelKernel(const uint32_t* __restri
     nodes[b] = N;
 }
 
+// rebuild: the uv records follow their triangles -- scattered by gid from the old leaf order, gathered in the new one
+__global__ __launch_bounds__(256) void uvScatterKernel(const crt_bvh_tri* __restrict__ tris, const crt_bvh_uv* __restrict__ uvs, uint32_t n,
+                                                       crt_bvh_uv* __restrict__ byGid)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) byGid[tris[i].gid] = uvs[i];
+}
+
+__global__ __launch_bounds__(256) void uvGatherKernel(const crt_bvh_tri* __restrict__ tris, const crt_bvh_uv* __restrict__ byGid, uint32_t n,
+                                                      crt_bvh_uv* __restrict__ uvs)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) uvs[i] = byGid[tris[i].gid];
+}
+
 } // namespace
+
+// per-level lists of the binary inner nodes (the tree's shape changes only with a rebuild) and the collapse scratch for nBinary
+// nodes (hostNodes, or read back from binNodes when the tree exists on the device only)
+static void setLevels(DynamicScene& d, const crt_bvh_node* hostNodes, const crt_bvh_node* binNodes, uint32_t nBinary, ihipStream_t* stream)
+{
+    std::vector<crt_bvh_node> readBack;
+    if (!hostNodes && nBinary) {
+        readBack.resize(nBinary);
+        REFIT_TRY(hipMemcpyAsync(readBack.data(), binNodes, sizeof(crt_bvh_node) * nBinary, hipMemcpyDeviceToHost, stream));
+        REFIT_TRY(hipStreamSynchronize(stream));
+        hostNodes = readBack.data();
+    }
+    std::vector<uint32_t> order;
+    d.levelStart.clear();
+    if (nBinary) {
+        order.reserve(nBinary);
+        order.push_back(0);
+        size_t begin = 0;
+        while (begin < order.size()) {
+            const size_t end = order.size();
+            d.levelStart.push_back(static_cast<uint32_t>(begin));
+            for (size_t k = begin; k < end; k++) {
+                const crt_bvh_node& N = hostNodes[order[k]];
+                for (int32_t ch : { N.left, N.right })
+                    if (ch >= 0) {
+                        if (static_cast<uint32_t>(ch) >= nBinary || order.size() >= nBinary) throw std::runtime_error("binary tree: bad child reference");
+                        order.push_back(static_cast<uint32_t>(ch));
+                    }
+            }
+            begin = end;
+        }
+        d.levelStart.push_back(static_cast<uint32_t>(order.size()));
+    }
+    if (d.dLevelNodes) (void)hipFree(d.dLevelNodes);
+    d.dLevelNodes = nullptr;
+    if (d.dScratch) (void)hipFree(d.dScratch);
+    d.dScratch = nullptr;
+    d.nBinary = nBinary;
+    REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dLevelNodes), sizeof(uint32_t) * (order.empty() ? 1 : order.size())));
+    if (!order.empty())
+        REFIT_TRY(hipMemcpyAsync(d.dLevelNodes, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, stream));
+    REFIT_TRY(hipMalloc(&d.dScratch, collapseScratchBytes(nBinary)));
+    REFIT_TRY(hipStreamSynchronize(stream)); // the host arrays above die with this call
+}
+
+// world = transform . rest for every dirty mesh (step 1 of the refit and of the rebuild)
+static void applyTransforms(DynamicScene& d, ihipStream_t* stream)
+{
+    const dim3 blk(256);
+    for (DynamicMesh& D : d.meshes) {
+        if (!D.dirty || D.nVerts == 0) continue;
+        const size_t off = 3 * static_cast<size_t>(D.vertStart), bytes = sizeof(float) * 3 * D.nVerts;
+        if (D.identity) {
+            REFIT_TRY(hipMemcpyAsync(d.dWorldXyz + off, d.dRestXyz + off, bytes, hipMemcpyDeviceToDevice, stream));
+            if (D.hasNormals) REFIT_TRY(hipMemcpyAsync(d.dWorldNormals + off, d.dRestNormals + off, bytes, hipMemcpyDeviceToDevice, stream));
+        } else {
+            Xform X;
+            std::memcpy(X.m, D.m, sizeof(X.m));
+            std::memcpy(X.nm, D.nm, sizeof(X.nm));
+            hipLaunchKernelGGL(transformKernel, dim3((D.nVerts + 255) / 256), blk, 0, stream, d.dRestXyz + off, D.hasNormals ? d.dRestNormals + off : nullptr,
+                               d.dWorldXyz + off, D.hasNormals ? d.dWorldNormals + off : nullptr, D.nVerts, X);
+        }
+    }
+}
 
 DynamicScene::~DynamicScene()
 {
@@ -163,7 +242,6 @@ void dynamicInit(DynamicScene& d, const crt_mesh_view* meshes, uint32_t n_meshes
     E.triStart = static_cast<uint32_t>(nt); E.vertStart = static_cast<uint32_t>(nv); E.nVerts = 0; E.material = 0; E.hasNormals = E.hasUvs = E.pad0 = E.pad1 = 0;
     d.nVerts = static_cast<uint32_t>(nv);
     d.nTris = static_cast<uint32_t>(nt);
-    d.nBinary = nBinary;
     const size_t vb = sizeof(float) * 3 * (nv ? nv : 1);
     REFIT_TRY(hipMalloc(&d.dTable, sizeof(MeshEntry) * table.size()));
     REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dRestXyz), vb));
@@ -188,39 +266,7 @@ void dynamicInit(DynamicScene& d, const crt_mesh_view* meshes, uint32_t n_meshes
     REFIT_TRY(hipMemcpyAsync(d.dWorldXyz, d.dRestXyz, vb, hipMemcpyDeviceToDevice, stream));
     if (anyNormals) REFIT_TRY(hipMemcpyAsync(d.dWorldNormals, d.dRestNormals, vb, hipMemcpyDeviceToDevice, stream));
 
-    // per-level lists of the binary inner nodes (the tree's shape never changes)
-    std::vector<crt_bvh_node> readBack;
-    if (!hostNodes && nBinary) {
-        readBack.resize(nBinary);
-        REFIT_TRY(hipMemcpyAsync(readBack.data(), binNodes, sizeof(crt_bvh_node) * nBinary, hipMemcpyDeviceToHost, stream));
-        REFIT_TRY(hipStreamSynchronize(stream));
-        hostNodes = readBack.data();
-    }
-    std::vector<uint32_t> order;
-    d.levelStart.clear();
-    if (nBinary) {
-        order.reserve(nBinary);
-        order.push_back(0);
-        size_t begin = 0;
-        while (begin < order.size()) {
-            const size_t end = order.size();
-            d.levelStart.push_back(static_cast<uint32_t>(begin));
-            for (size_t k = begin; k < end; k++) {
-                const crt_bvh_node& N = hostNodes[order[k]];
-                for (int32_t ch : { N.left, N.right })
-                    if (ch >= 0) {
-                        if (static_cast<uint32_t>(ch) >= nBinary || order.size() >= nBinary) throw std::runtime_error("binary tree: bad child reference");
-                        order.push_back(static_cast<uint32_t>(ch));
-                    }
-            }
-            begin = end;
-        }
-        d.levelStart.push_back(static_cast<uint32_t>(order.size()));
-    }
-    REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dLevelNodes), sizeof(uint32_t) * (order.empty() ? 1 : order.size())));
-    if (!order.empty())
-        REFIT_TRY(hipMemcpyAsync(d.dLevelNodes, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, stream));
-    REFIT_TRY(hipMalloc(&d.dScratch, collapseScratchBytes(nBinary)));
+    setLevels(d, hostNodes, binNodes, nBinary, stream);
     REFIT_TRY(hipEventCreate(&d.ev0));
     REFIT_TRY(hipEventCreate(&d.ev1));
     REFIT_TRY(hipStreamSynchronize(stream)); // the host arrays above die with this call
@@ -230,20 +276,7 @@ void dynamicRefit(DynamicScene& d, const RefitTargets& t, ihipStream_t* stream, 
 {
     const dim3 blk(256);
     REFIT_TRY(hipEventRecord(d.ev0, stream));
-    for (DynamicMesh& D : d.meshes) {
-        if (!D.dirty || D.nVerts == 0) continue;
-        const size_t off = 3 * static_cast<size_t>(D.vertStart), bytes = sizeof(float) * 3 * D.nVerts;
-        if (D.identity) {
-            REFIT_TRY(hipMemcpyAsync(d.dWorldXyz + off, d.dRestXyz + off, bytes, hipMemcpyDeviceToDevice, stream));
-            if (D.hasNormals) REFIT_TRY(hipMemcpyAsync(d.dWorldNormals + off, d.dRestNormals + off, bytes, hipMemcpyDeviceToDevice, stream));
-        } else {
-            Xform X;
-            std::memcpy(X.m, D.m, sizeof(X.m));
-            std::memcpy(X.nm, D.nm, sizeof(X.nm));
-            hipLaunchKernelGGL(transformKernel, dim3((D.nVerts + 255) / 256), blk, 0, stream, d.dRestXyz + off, D.hasNormals ? d.dRestNormals + off : nullptr,
-                               d.dWorldXyz + off, D.hasNormals ? d.dWorldNormals + off : nullptr, D.nVerts, X);
-        }
-    }
+    applyTransforms(d, stream);
     const uint32_t nMeshes = static_cast<uint32_t>(d.meshes.size());
     const MeshEntry* table = static_cast<const MeshEntry*>(d.dTable);
     if (d.nTris)
@@ -268,6 +301,90 @@ void dynamicRefit(DynamicScene& d, const RefitTargets& t, ihipStream_t* stream, 
     float ms = 0.f;
     REFIT_TRY(hipEventElapsedTime(&ms, d.ev0, d.ev1));
     if (device_ms) *device_ms = ms;
+    for (DynamicMesh& D : d.meshes) D.dirty = false;
+    d.pending = false;
+}
+
+} // namespace crt
+
+namespace crt {
+
+void dynamicRebuild(DynamicScene& d, int builder, const crt_bvh_tri* oldTris, const void* oldUvs, Bvh& out, ihipStream_t* stream, double* device_ms)
+{
+    out = Bvh();
+    if (device_ms) *device_ms = 0.0;
+    if (d.nTris == 0) throw std::logic_error("dynamicRebuild: a scene without triangles");
+    REFIT_TRY(hipEventRecord(d.ev0, stream));
+    applyTransforms(d, stream);
+    const uint32_t nMeshes = static_cast<uint32_t>(d.meshes.size());
+    if (d.nTris > static_cast<uint32_t>(kLeafMax)) {
+        GpuMeshes in;
+        in.table = d.dTable;
+        in.nMeshes = nMeshes;
+        in.n = d.nTris;
+        in.xyz = d.dWorldXyz;
+        in.idx = d.dIdx;
+        in.normals = d.dWorldNormals;
+        rebuildBvhGpu(in, builder, out, stream, nullptr);
+    } else {
+        // a handful of triangles: the builders' one-leaf tree is made on the host (bvh_gpu.hip), from the world vertices read back
+        std::vector<MeshEntry> table(nMeshes + 1u);
+        std::vector<float> xyz(3 * static_cast<size_t>(d.nVerts)), nrm(d.dWorldNormals ? 3 * static_cast<size_t>(d.nVerts) : 0);
+        std::vector<uint32_t> idx(3 * static_cast<size_t>(d.nTris));
+        REFIT_TRY(hipMemcpyAsync(table.data(), d.dTable, sizeof(MeshEntry) * table.size(), hipMemcpyDeviceToHost, stream));
+        if (!xyz.empty()) REFIT_TRY(hipMemcpyAsync(xyz.data(), d.dWorldXyz, sizeof(float) * xyz.size(), hipMemcpyDeviceToHost, stream));
+        if (!nrm.empty()) REFIT_TRY(hipMemcpyAsync(nrm.data(), d.dWorldNormals, sizeof(float) * nrm.size(), hipMemcpyDeviceToHost, stream));
+        REFIT_TRY(hipMemcpyAsync(idx.data(), d.dIdx, sizeof(uint32_t) * idx.size(), hipMemcpyDeviceToHost, stream));
+        REFIT_TRY(hipStreamSynchronize(stream));
+        std::vector<crt_mesh_view> views(nMeshes);
+        for (uint32_t m = 0; m < nMeshes; m++) {
+            const MeshEntry& E = table[m];
+            crt_mesh_view& V = views[m];
+            std::memset(&V, 0, sizeof(V));
+            V.n_vertices = E.nVerts;
+            V.n_triangles = table[m + 1].triStart - E.triStart;
+            V.xyz = E.nVerts ? xyz.data() + 3 * static_cast<size_t>(E.vertStart) : nullptr;
+            V.idx = V.n_triangles ? idx.data() + 3 * static_cast<size_t>(E.triStart) : nullptr;
+            V.normals = E.hasNormals && E.nVerts ? nrm.data() + 3 * static_cast<size_t>(E.vertStart) : nullptr;
+            V.material_index = static_cast<int32_t>(E.material);
+        }
+        Bvh host;
+        buildBvhGpu(views.data(), nMeshes, host, stream, nullptr, builder);
+        REFIT_TRY(hipMalloc(&out.devNodes, sizeof(crt_bvh_node) * host.nodes.size()));
+        REFIT_TRY(hipMalloc(&out.devNodes4, sizeof(crt_bvh_node4) * host.nodes4.size()));
+        REFIT_TRY(hipMalloc(&out.devNodes4q, sizeof(crt_bvh_node4q) * host.nodes4q.size() + 128));
+        REFIT_TRY(hipMalloc(&out.devTris, sizeof(crt_bvh_tri) * host.tris.size() + 64));
+        REFIT_TRY(hipMalloc(&out.devShade, sizeof(crt_bvh_shade) * host.shade.size() + 64));
+        REFIT_TRY(hipMemcpyAsync(out.devNodes, host.nodes.data(), sizeof(crt_bvh_node) * host.nodes.size(), hipMemcpyHostToDevice, stream));
+        REFIT_TRY(hipMemcpyAsync(out.devNodes4, host.nodes4.data(), sizeof(crt_bvh_node4) * host.nodes4.size(), hipMemcpyHostToDevice, stream));
+        REFIT_TRY(hipMemcpyAsync(out.devNodes4q, host.nodes4q.data(), sizeof(crt_bvh_node4q) * host.nodes4q.size(), hipMemcpyHostToDevice, stream));
+        REFIT_TRY(hipMemcpyAsync(out.devTris, host.tris.data(), sizeof(crt_bvh_tri) * host.tris.size(), hipMemcpyHostToDevice, stream));
+        REFIT_TRY(hipMemcpyAsync(out.devShade, host.shade.data(), sizeof(crt_bvh_shade) * host.shade.size(), hipMemcpyHostToDevice, stream));
+        REFIT_TRY(hipStreamSynchronize(stream)); // (the host arrays die with this scope)
+        out.nNodes = static_cast<uint32_t>(host.nodes.size());
+        out.nNodes4 = static_cast<uint32_t>(host.nodes4.size());
+        out.depth4 = host.depth4;
+        out.maxDepth = host.maxDepth;
+        out.nTris = host.nTris;
+    }
+    if (oldUvs) {
+        const dim3 blk(256), grd((d.nTris + 255) / 256);
+        void* byGid = nullptr;
+        REFIT_TRY(hipMalloc(&byGid, sizeof(crt_bvh_uv) * d.nTris));
+        struct Owned { void*& p; ~Owned() { if (p) (void)hipFree(p); } } owned{ byGid };
+        REFIT_TRY(hipMalloc(&out.devUvs, sizeof(crt_bvh_uv) * d.nTris + 64));
+        hipLaunchKernelGGL(uvScatterKernel, grd, blk, 0, stream, oldTris, static_cast<const crt_bvh_uv*>(oldUvs), d.nTris, static_cast<crt_bvh_uv*>(byGid));
+        hipLaunchKernelGGL(uvGatherKernel, grd, blk, 0, stream, static_cast<const crt_bvh_tri*>(out.devTris), static_cast<const crt_bvh_uv*>(byGid), d.nTris,
+                           static_cast<crt_bvh_uv*>(out.devUvs));
+        REFIT_TRY(hipGetLastError());
+        REFIT_TRY(hipStreamSynchronize(stream)); // byGid dies with this scope
+    }
+    REFIT_TRY(hipEventRecord(d.ev1, stream));
+    REFIT_TRY(hipStreamSynchronize(stream));
+    float ms = 0.f;
+    REFIT_TRY(hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    if (device_ms) *device_ms = ms;
+    setLevels(d, nullptr, static_cast<const crt_bvh_node*>(out.devNodes), out.nNodes, stream);
     for (DynamicMesh& D : d.meshes) D.dirty = false;
     d.pending = false;
 }

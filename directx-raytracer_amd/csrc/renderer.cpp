@@ -63,6 +63,8 @@ void Renderer::uploadScene()
                                      static_cast<uint32_t>(m.getType()), m.isSmoothShading() ? 1u : 0u, m.getIor(),
                                      m.isTexture() ? scene->textureIndexByName(m.getTextureName()) : -1 });
     check(crt_set_option(ctx, "dynamic", dynamicGeometry ? 1 : 0), "crt_set_option");
+    check(crt_set_option(ctx, "gpu_build", gpuBuilder >= 0 ? 1 : 0), "crt_set_option");
+    check(crt_set_option(ctx, "gpu_builder", gpuBuilder >= 0 ? gpuBuilder : 0), "crt_set_option");
     check(crt_upload_scene(ctx, meshes.data(), static_cast<uint32_t>(meshes.size()), lights.data(),
                            static_cast<uint32_t>(lights.size()), mats.data(), static_cast<uint32_t>(mats.size())),
           "crt_upload_scene");
@@ -96,6 +98,14 @@ void Renderer::renderFrame()
     frame.resize(static_cast<size_t>(width) * height * 4);
     if (nRanks) check(crt_render_frame_distributed(ctx, width, height, nullptr, frame.data(), &stats), "crt_render_frame_distributed");
     else check(crt_render_frame(ctx, width, height, frame.data(), nullptr, nullptr, nullptr, nullptr, &stats), "crt_render_frame");
+}
+
+double Renderer::rebuild()
+{
+    if (!ctx) throw std::runtime_error("rebuild before prepareForRendering");
+    double ms = 0.0;
+    check(crt_rebuild(ctx, &ms), "crt_rebuild");
+    return ms;
 }
 
 void Renderer::setMeshTransform(uint32_t mesh, const float m[12])

@@ -62,6 +62,12 @@ public:
     void setDynamicGeometry(bool on) { dynamicGeometry = on; }
     void setMeshTransform(uint32_t mesh, const float m[12]);                                          // row-major 3x4; nullptr = identity
     void updateMeshVertices(uint32_t mesh, const float* xyz, size_t nVertices, const float* normals = nullptr); // normals: nullptr = keep
+    // crt_rebuild: pending updates applied and a new tree built on the GPU from the world vertices (builder: setGpuBuilder);
+    // returns the device ms
+    double rebuild();
+    // the acceleration structure of the next upload and of rebuild(): -1 = host SAH (the default; rebuild() then uses the LBVH),
+    // 0 = LBVH on the GPU, 1 = PLOC on the GPU (options "gpu_build" / "gpu_builder").  Set before prepareForRendering.
+    void setGpuBuilder(int builder) { gpuBuilder = builder; }
 
     // N GPUs, one process each (no reference counterpart): join the RCCL communicator of an N-rank run.  Rank 0 creates the
     // 128-byte id and publishes it as `idFile` (written under a temporary name, then renamed); the other ranks wait for the
@@ -82,6 +88,7 @@ private:
     crt_frame_stats stats{};
     uint32_t rank = 0, nRanks = 0; // nRanks = 0: single-GPU path (crt_render_frame)
     bool dynamicGeometry = false;
+    int gpuBuilder = -1;
     void uploadScene();
     void check(int rc, const char* what) const;
 };

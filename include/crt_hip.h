@@ -219,7 +219,9 @@ int crt_render_frame_distributed(crt_ctx* ctx, uint32_t width, uint32_t height, 
  * "phong_ks" = specular coefficient in thousandths (0 = off, the default; 300 = 0.3), "phong_exponent" = integer exponent
  * 1..65536 (default 32).  Per unoccluded light: rgb += ks * intensity / (4 pi r^2) * max(0, R . V)^n, R = light direction
  * mirrored about the shading normal, V = direction to the eye; white highlight, x^n by square and multiply.
- * "gpu_build" 0/1: acceleration structure built on the GPU (LBVH) at the next crt_upload_scene.
+ * "gpu_build" 0/1: acceleration structure built on the GPU at the next crt_upload_scene.  "gpu_builder" picks the GPU builder for
+ * those uploads and for crt_rebuild: 0 = LBVH (the default), 1 = PLOC (closer to the SAH tree in quality, slower to build); other
+ * values -> CRT_EINVAL.  It has no effect on host SAH uploads.
  * Rendering parameters of mode 200: "spp", "max_bounces", "seed". Tuning knobs (speed only, results never
  * change): "inner_min" / "inner_min_any" wave scheduling of the closest-hit / any-hit traversal loops (1..65: node steps while that
  * many lanes stand on inner nodes; -1..-8: while that many eighths of the wavefront's live lanes do; default -6), "xcd_group", "adaptive_order" (launch the most expensive 8x8
@@ -389,6 +391,18 @@ int crt_update_vertices(crt_ctx* ctx, uint32_t mesh, uint32_t n_vertices, const 
 int crt_update_vertices_device(crt_ctx* ctx, uint32_t mesh, uint32_t n_vertices, const void* d_xyz, const void* d_normals);
 int crt_set_mesh_transform(crt_ctx* ctx, uint32_t mesh, const float m[12]); /* row-major 3x4; NULL = identity */
 int crt_refit(crt_ctx* ctx, double* device_ms /* may be NULL: HIP-event time of the refit, 0 when nothing was pending */);
+/* Rebuild (DXR: BuildRaytracingAccelerationStructure without PERFORM_UPDATE): applies the pending updates, then builds a new tree
+ * on the GPU from the world vertices already in HBM, with the builder option "gpu_builder" names (0 = LBVH, the default; 1 = PLOC).
+ * Nothing is read back from the caller.
+ * - The tree and every record equal, byte for byte, what a "gpu_build" = 1 upload of the moved meshes with the same builder
+ *   produces; uv records follow their triangles.  Later refits refit the new tree.
+ * - Like a refit it gives the scene a new serial (accumulation and the stored launch orders restart) and updates the root box,
+ *   crt_bvh_info / crt_bvh_info4.  Synchronous; it works whether or not anything was pending.
+ * - Pick it over crt_refit when the meshes moved far from where the tree was built (a refitted tree keeps its shape and traces
+ *   slower the further the geometry moves); a refit is cheaper when the motion is small.
+ * - Errors: NULL ctx -> CRT_EINVAL; no scene, or a scene uploaded without "dynamic" -> CRT_ESTATE; HIP failures -> CRT_EHIP, after
+ *   which the context has no scene (as after a failed upload). */
+int crt_rebuild(crt_ctx* ctx, double* device_ms /* may be NULL: HIP-event time from the first transform to the collapsed tree */);
 /* world-space vertices (and normals, may be NULL) of a mesh as they are traced, n_vertices * 3 floats each */
 int crt_mesh_vertices(const crt_ctx* ctx, uint32_t mesh, float* xyz, float* normals);
 
