@@ -45,11 +45,12 @@ __device__ __forceinline__ void splitRange(float t0, float t1, uint32_t seg, uin
 // the part of (tmin, tmax) a ray spends inside the scene's box; a ray that misses it gets an empty interval at tmin
 __device__ __forceinline__ void sceneInterval(const Ray& r, const float* lo, const float* hi, float tmin, float tmax, float& t0, float& t1)
 {
-    const float x0 = fmaf(lo[0], r.idir.x, r.noid.x), x1 = fmaf(hi[0], r.idir.x, r.noid.x);
-    const float y0 = fmaf(lo[1], r.idir.y, r.noid.y), y1 = fmaf(hi[1], r.idir.y, r.noid.y);
-    const float z0 = fmaf(lo[2], r.idir.z, r.noid.z), z1 = fmaf(hi[2], r.idir.z, r.noid.z);
+    // the conservative slab test of the traversal (Ray): near distances from the near offset, far ones from the far offset
+    const float x0 = fmaf(lo[0], r.idir.x, r.noidn.x), x1 = fmaf(hi[0], r.idir.x, r.noidn.x);
+    const float y0 = fmaf(lo[1], r.idir.y, r.noidn.y), y1 = fmaf(hi[1], r.idir.y, r.noidn.y);
+    const float z0 = fmaf(lo[2], r.idir.z, r.noidn.z), z1 = fmaf(hi[2], r.idir.z, r.noidn.z);
     t0 = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), tmin));
-    t1 = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), tmax));
+    t1 = fminf(fminf(farOffset(fmaxf(x0, x1), r.noidn.x), farOffset(fmaxf(y0, y1), r.noidn.y)), fminf(farOffset(fmaxf(z0, z1), r.noidn.z), tmax));
     if (!(t0 <= t1)) t0 = t1 = tmin;
 }
 

@@ -20,6 +20,7 @@ constexpr float kTMin = 0.001f;   // hlsl:51
 constexpr float kTMax = 10000.0f; // hlsl:52
 constexpr float kDirEps = 1e-20f;
 constexpr float kCullPad = 1.00000381469726562f; // 1 + 2^-18, see oracle trace_closest
+constexpr float kSlabPad = 0x1p-21f;              // slab pads: near offsets 2^-21 |o * idir| down, far ones 2^-20 |noidn| up
 constexpr float kShadowBias = 1e-3f;
 constexpr float kFourPi = 12.566370614359172f;
 constexpr int kBlock = 256;
@@ -112,9 +113,15 @@ __device__ __forceinline__ float hashSin(float x, float k) { return frac1(sinCon
 
 __device__ __forceinline__ uint32_t unorm8(float c) { return static_cast<uint32_t>(saturate1(c) * 255.0f + 0.5f); }
 
+// noidn: -(o * idir) moved down by 2^-21 of its magnitude, the offset of the near slab distances of the ray.  A node step turns
+// it into the near offset bn = fma(lo, idir, noidn) and the far offset fma(|noidn|, 2^-20, bn) of each axis, so the far
+// distances sit about 2^-21 |o * idir| above the plain ones and the near distances as far below.  The rounding of
+// fma(plane, idir, -(o * idir)) has an absolute part of about 2^-23 |o * idir| that does not shrink with t; the pads cover it,
+// so that a box the ray enters is never culled however far from the origin it lies.  No register more
+// than the plain offset: the far pad is an fma operand with an absolute-value modifier.
 struct Ray {
     F3 o, d;
-    F3 idir, noid;
+    F3 idir, noidn;
 };
 
 __device__ __forceinline__ float safeRcp(float d)
@@ -123,13 +130,17 @@ __device__ __forceinline__ float safeRcp(float d)
     return 1.0f / ds;
 }
 
+// the far offset of a slab axis from its near offset bn: 2^-20 |noidn| higher (see Ray)
+__device__ __forceinline__ float farOffset(float bn, float noidn) { return fmaf(fabsf(noidn), 2.0f * kSlabPad, bn); }
+
 __device__ __forceinline__ Ray makeRay(F3 o, F3 d)
 {
     Ray r;
     r.o = o;
     r.d = d;
     r.idir = f3(safeRcp(d.x), safeRcp(d.y), safeRcp(d.z));
-    r.noid = f3(-(o.x * r.idir.x), -(o.y * r.idir.y), -(o.z * r.idir.z));
+    const F3 noid = f3(-(o.x * r.idir.x), -(o.y * r.idir.y), -(o.z * r.idir.z));
+    r.noidn = f3(noid.x - fabsf(noid.x) * kSlabPad, noid.y - fabsf(noid.y) * kSlabPad, noid.z - fabsf(noid.z) * kSlabPad);
     return r;
 }
 
@@ -266,7 +277,8 @@ __device__ __forceinline__ int pick4(const int4& v, uint32_t i) // v[i], i in 0.
 // The child planes are 8-bit offsets from the node's own minimum corner: plane = fma(q, s, lo).  A per-lane fetch
 // request costs this kernel far more than vector arithmetic does (24 / 48 extra dependent VALU per step measured +9 % /
 // +21 %, one extra 4-byte touch per pushed child +29 %), so records are kept to as few requests per lane as possible and
-// decoded in registers.  The decode is folded into the slab test: t(q) = fma(q, s * idir, fma(lo, idir, -o * idir)),
+// decoded in registers.  The decode is folded into the slab test: t(q) = fma(q, s * idir, b) with b = fma(lo, idir, noidn) in
+// the near distances and b = farOffset(that, noidn) in the far ones (Ray: three more fma per step, none per child);
 // monotonic in q with the sign of idir, so for a known direction octant (OCT < 8) the near plane of each axis is a fixed
 // member of the (qlo, qhi) pair and the min/max pairs of the generic form (OCT = 8) disappear -- bit for bit the same values.
 // An unused child slot is the leaf of no triangles with a point box (qlo = qhi = 0): the slab test rejects it, there is no
@@ -282,7 +294,8 @@ __device__ __forceinline__ int pick4(const int4& v, uint32_t i) // v[i], i in 0.
 // wavefront instruction -- so a conversion folded into a mixed-precision fma costs what the pair it replaces cost.)
 template <int OCT>
 __device__ __forceinline__ void slabPair(uint32_t lx, uint32_t hx, uint32_t ly, uint32_t hy, uint32_t lz, uint32_t hz, int pair, const Ray& r,
-                                         float ax, float ay, float az, float bx, float by, float bz, float tmin, float tcull, float tn[2], bool hit[2])
+                                         float ax, float ay, float az, float bxn, float byn, float bzn, float bxf, float byf, float bzf,
+                                         float tmin, float tcull, float tn[2], bool hit[2])
 {
     // near / far member of each (qlo, qhi) pair: fixed by the template octant, or picked per lane from the direction's sign
     // bits (mixed-octant wavefronts: bounce rays) -- six selects instead of the twelve min/max of the textbook form, and
@@ -294,8 +307,8 @@ __device__ __forceinline__ void slabPair(uint32_t lx, uint32_t hx, uint32_t ly, 
 #pragma unroll
     for (int i = 0; i < 2; i++) {
         const int byte = 2 * pair + i;
-        const float t_n = fmaxf(fmaxf(fmaf(ubyteToFloat(nxw, byte), ax, bx), fmaf(ubyteToFloat(nyw, byte), ay, by)), fmaxf(fmaf(ubyteToFloat(nzw, byte), az, bz), tmin));
-        const float t_f = fminf(fminf(fmaf(ubyteToFloat(fxw, byte), ax, bx), fmaf(ubyteToFloat(fyw, byte), ay, by)), fminf(fmaf(ubyteToFloat(fzw, byte), az, bz), tcull));
+        const float t_n = fmaxf(fmaxf(fmaf(ubyteToFloat(nxw, byte), ax, bxn), fmaf(ubyteToFloat(nyw, byte), ay, byn)), fmaxf(fmaf(ubyteToFloat(nzw, byte), az, bzn), tmin));
+        const float t_f = fminf(fminf(fmaf(ubyteToFloat(fxw, byte), ax, bxf), fmaf(ubyteToFloat(fyw, byte), ay, byf)), fminf(fmaf(ubyteToFloat(fzw, byte), az, bzf), tcull));
         tn[i] = t_n;
         hit[i] = t_n <= t_f;
     }
@@ -365,11 +378,12 @@ struct LayLegacy {
     static __device__ __forceinline__ void slab(const Node& nd, const Ray& r, float tmin, float tcull, float tn[4], bool hit[4])
     {
         const float ax = nd.q0.w * r.idir.x, ay = nd.q1.x * r.idir.y, az = nd.q1.y * r.idir.z;
-        const float bx = fmaf(nd.q0.x, r.idir.x, r.noid.x), by = fmaf(nd.q0.y, r.idir.y, r.noid.y), bz = fmaf(nd.q0.z, r.idir.z, r.noid.z);
+        const float bxn = fmaf(nd.q0.x, r.idir.x, r.noidn.x), byn = fmaf(nd.q0.y, r.idir.y, r.noidn.y), bzn = fmaf(nd.q0.z, r.idir.z, r.noidn.z);
+        const float bxf = farOffset(bxn, r.noidn.x), byf = farOffset(byn, r.noidn.y), bzf = farOffset(bzn, r.noidn.z);
         const uint32_t lx = __float_as_uint(nd.q1.z), hx = __float_as_uint(nd.q1.w), ly = __float_as_uint(nd.q2.x), hy = __float_as_uint(nd.q2.y),
                        lz = __float_as_uint(nd.q2.z), hz = __float_as_uint(nd.q2.w);
 #pragma unroll
-        for (int j = 0; j < 2; j++) slabPair<OCT>(lx, hx, ly, hy, lz, hz, j, r, ax, ay, az, bx, by, bz, tmin, tcull, tn + 2 * j, hit + 2 * j);
+        for (int j = 0; j < 2; j++) slabPair<OCT>(lx, hx, ly, hy, lz, hz, j, r, ax, ay, az, bxn, byn, bzn, bxf, byf, bzf, tmin, tcull, tn + 2 * j, hit + 2 * j);
     }
     // the same slab tests on a scalar record with decoded planes: the octant names the near / far plane of every axis at
     // compile time, and fmaf(float(q), a, b) is the value slabPair computes (float(q) is exact for q <= 255).  Known octants
@@ -380,13 +394,14 @@ struct LayLegacy {
     {
         static_assert(OCT < 8, "decoded planes: octant-specialised steps only");
         const float ax = nd.q0.w * r.idir.x, ay = nd.sy * r.idir.y, az = nd.sz * r.idir.z;
-        const float bx = fmaf(nd.q0.x, r.idir.x, r.noid.x), by = fmaf(nd.q0.y, r.idir.y, r.noid.y), bz = fmaf(nd.q0.z, r.idir.z, r.noid.z);
+        const float bxn = fmaf(nd.q0.x, r.idir.x, r.noidn.x), byn = fmaf(nd.q0.y, r.idir.y, r.noidn.y), bzn = fmaf(nd.q0.z, r.idir.z, r.noidn.z);
+        const float bxf = farOffset(bxn, r.noidn.x), byf = farOffset(byn, r.noidn.y), bzf = farOffset(bzn, r.noidn.z);
         constexpr int nx = (OCT & 1) ? 4 : 0, ny = (OCT & 2) ? 12 : 8, nz = (OCT & 4) ? 20 : 16; // near member of each pair
         constexpr int fx = 4 - nx, fy = 20 - ny, fz = 36 - nz;                                   // far member
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            const float t_n = fmaxf(fmaxf(fmaf(nd.p[nx + k], ax, bx), fmaf(nd.p[ny + k], ay, by)), fmaxf(fmaf(nd.p[nz + k], az, bz), tmin));
-            const float t_f = fminf(fminf(fmaf(nd.p[fx + k], ax, bx), fmaf(nd.p[fy + k], ay, by)), fminf(fmaf(nd.p[fz + k], az, bz), tcull));
+            const float t_n = fmaxf(fmaxf(fmaf(nd.p[nx + k], ax, bxn), fmaf(nd.p[ny + k], ay, byn)), fmaxf(fmaf(nd.p[nz + k], az, bzn), tmin));
+            const float t_f = fminf(fminf(fmaf(nd.p[fx + k], ax, bxf), fmaf(nd.p[fy + k], ay, byf)), fminf(fmaf(nd.p[fz + k], az, bzf), tcull));
             tn[k] = t_n;
             hit[k] = t_n <= t_f;
         }

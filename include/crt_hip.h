@@ -342,12 +342,15 @@ int crt_accumulated_samples(const crt_ctx* ctx, uint32_t* samples); /* samples p
  *   magnitude), so for a ray whose tmax and hit are >= 0 the results and fetch counts are bit for bit the CPU oracle's
  *   traversal of that ray.  For a negative bound the widening keeps its direction (the oracle's and the frames' factor would
  *   narrow it): a triangle strictly inside (tmin, tmax) is found, and ties at t < 0 go to the lower global id, as at t > 0.
- * - Limit (boundary rays): the slab test and the triangle test round differently, so a triangle whose hit lies where the ray
- *   runs within rounding of a box face can be rejected with its box.  This concerns a ray lying in an axis-aligned face of
- *   the boxes (an axis-aligned direction through the plane of axis-aligned geometry, or through a shared edge of such quads)
- *   and a ray starting on a surface whose own hit is at t ~ tmin.  Such a ray may then report a miss, or a farther hit,
- *   although a triangle lies in (tmin, tmax); the result is still the oracle's traversal of the same tree, but it can differ
- *   between the host SAH tree and the gpu_build tree.  Every other ray gives the same result over either tree.
+ * - Limit (boundary rays): the slab test is conservative against the absolute rounding that comes from the ray origin's
+ *   distance to the world origin.  Its near and far distances are padded by 2^-21 |o / d| per axis, so a
+ *   box the ray enters is not culled for that reason at any offset.  What remains is the relative rounding of the slab
+ *   distances, a few ulps of t.  A triangle whose hit lies where the ray runs within that of a box edge can still be rejected
+ *   with its box.  This concerns a ray lying in an axis-aligned face of the boxes (an axis-aligned direction through the
+ *   plane of axis-aligned geometry, or through a shared edge of such quads) and a ray starting on a surface whose own hit
+ *   is at t ~ tmin.  Such a ray may then report a miss, or a farther hit, although a triangle lies in (tmin, tmax).  The
+ *   result is still the oracle's traversal of the same tree, but it can differ between the host SAH tree and the gpu_build
+ *   tree.  Every other ray gives the same result over either tree, however far from the origin the scene lies.
  * - Layout: queries traverse the 64-byte 4-wide tree the frames traverse.
  * - A query needs an uploaded scene (CRT_ESTATE otherwise).  It reads the tree, the triangles and the options inner_min /
  *   inner_min_any, nothing else: camera, mode, accumulation sums, launch-order state and frame outputs are untouched, and a frame

@@ -40,6 +40,7 @@
 #define MAX_DEPTH 32      /* leaves at depth <= MAX_DEPTH  => traversal stack <= MAX_DEPTH entries */
 #define N_BINS 16
 #define C_TRAV 1.0f       /* SAH: cost of visiting an inner node, in triangle tests */
+#define SLAB_PAD 0x1p-21f /* slab pads: near offsets 2^-21 |o * idir| down, far ones 2^-20 |noidn| up */
 #define CULL_PAD 1.00000381469726562f /* 1 + 2^-18: boxes are culled against best_t * CULL_PAD (see trace_closest) */
 #define SHADOW_BIAS 1e-3f
 #define FOUR_PI 12.566370614359172f
@@ -736,7 +737,8 @@ uint32_t oracle_scene_max_depth(const oracle_scene* s) { return s->max_depth; }
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     v3 o, d;
-    v3 idir, noid; /* 1/d (clamped) and -(o * idir) for the fma slab test */
+    v3 idir;       /* 1/d (clamped) */
+    v3 noidn;      /* -(o * idir) moved down by SLAB_PAD of its magnitude: offset of the near slab distances */
 } ray;
 
 static inline float safe_rcp_dir(float d)
@@ -749,7 +751,8 @@ static inline void ray_setup(ray* r, v3 o, v3 d)
 {
     r->o = o; r->d = d;
     r->idir = v3_make(safe_rcp_dir(d.x), safe_rcp_dir(d.y), safe_rcp_dir(d.z));
-    r->noid = v3_make(-(o.x * r->idir.x), -(o.y * r->idir.y), -(o.z * r->idir.z));
+    const v3 noid = v3_make(-(o.x * r->idir.x), -(o.y * r->idir.y), -(o.z * r->idir.z));
+    r->noidn = v3_make(noid.x - fabsf(noid.x) * SLAB_PAD, noid.y - fabsf(noid.y) * SLAB_PAD, noid.z - fabsf(noid.z) * SLAB_PAD);
 }
 
 typedef struct { float t, u, v; uint32_t tri; /* leaf-order index */ uint32_t gid; int hit; } hit_rec;
@@ -775,14 +778,19 @@ static inline int tri_test(const ray* r, const oracle_tri* T, float tmin, float*
     return (uu >= 0.0f) & (vv >= 0.0f) & (uu + vv <= 1.0f) & (tt > tmin);
 }
 
+/* the far offset of a slab axis from its near offset bn: 2^-20 |noidn| higher */
+static inline float far_offset(float bn, float noidn) { return fmaf(fabsf(noidn), 2.0f * SLAB_PAD, bn); }
+
 static inline int box_test(float x0, float x1, float y0, float y1, float z0, float z1, const ray* r,
                            float tmin, float tmax, float* tnear)
 {
-    float ax = fmaf(x0, r->idir.x, r->noid.x), bx = fmaf(x1, r->idir.x, r->noid.x);
-    float ay = fmaf(y0, r->idir.y, r->noid.y), by = fmaf(y1, r->idir.y, r->noid.y);
-    float az = fmaf(z0, r->idir.z, r->noid.z), bz = fmaf(z1, r->idir.z, r->noid.z);
+    /* near distances from the near offset, far distances from the far offset: conservative */
+    float ax = fmaf(x0, r->idir.x, r->noidn.x), bx = fmaf(x1, r->idir.x, r->noidn.x);
+    float ay = fmaf(y0, r->idir.y, r->noidn.y), by = fmaf(y1, r->idir.y, r->noidn.y);
+    float az = fmaf(z0, r->idir.z, r->noidn.z), bz = fmaf(z1, r->idir.z, r->noidn.z);
     float tn = maxf_(maxf_(minf_(ax, bx), minf_(ay, by)), maxf_(minf_(az, bz), tmin));
-    float tf = minf_(minf_(maxf_(ax, bx), maxf_(ay, by)), minf_(maxf_(az, bz), tmax));
+    float tf = minf_(minf_(far_offset(maxf_(ax, bx), r->noidn.x), far_offset(maxf_(ay, by), r->noidn.y)),
+                     minf_(far_offset(maxf_(az, bz), r->noidn.z), tmax));
     *tnear = tn;
     return tn <= tf;
 }
@@ -882,7 +890,8 @@ static int trace_any2(const oracle_scene* s, const ray* r, float tmin, float tma
 static inline uint32_t f2u(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 
 /* the four slab tests of a quantised wide node in one SSE pass: lane k = child k.  Planes are decoded inside the test:
- * t(q) = fma(q, s * idir, fma(lo, idir, -o * idir)), the generic min/max form (the kernel's octant-specialised form picks
+ * t(q) = fma(q, s * idir, b), b = fma(lo, idir, noidn) for the near distances and b = far_offset(that) for the far ones,
+ * the generic min/max form (the kernel's octant-specialised form picks
  * the same members: t is monotonic in q).  _mm_min_ps(a, b) is exactly minf_(a, b) = a < b ? a : b (and max likewise),
  * _mm_fmadd_ps is fmaf per lane.  Returns the hit mask. */
 static inline __m128 q_bytes(uint32_t w) { return _mm_cvtepi32_ps(_mm_cvtepu8_epi32(_mm_cvtsi32_si128((int)w))); }
@@ -890,13 +899,18 @@ static inline __m128 q_bytes(uint32_t w) { return _mm_cvtepi32_ps(_mm_cvtepu8_ep
 static inline int slab4(const oracle_node4q* N, const ray* r, float tmin, float tcull, float tn_out[4])
 {
     const __m128 ax = _mm_set1_ps(N->s[0] * r->idir.x), ay = _mm_set1_ps(N->s[1] * r->idir.y), az = _mm_set1_ps(N->s[2] * r->idir.z);
-    const __m128 bx = _mm_set1_ps(fmaf(N->lo[0], r->idir.x, r->noid.x)), by = _mm_set1_ps(fmaf(N->lo[1], r->idir.y, r->noid.y)),
-                 bz = _mm_set1_ps(fmaf(N->lo[2], r->idir.z, r->noid.z));
-    const __m128 x0 = _mm_fmadd_ps(q_bytes(N->qlo_x), ax, bx), x1 = _mm_fmadd_ps(q_bytes(N->qhi_x), ax, bx);
-    const __m128 y0 = _mm_fmadd_ps(q_bytes(N->qlo_y), ay, by), y1 = _mm_fmadd_ps(q_bytes(N->qhi_y), ay, by);
-    const __m128 z0 = _mm_fmadd_ps(q_bytes(N->qlo_z), az, bz), z1 = _mm_fmadd_ps(q_bytes(N->qhi_z), az, bz);
-    const __m128 tn = _mm_max_ps(_mm_max_ps(_mm_min_ps(x0, x1), _mm_min_ps(y0, y1)), _mm_max_ps(_mm_min_ps(z0, z1), _mm_set1_ps(tmin)));
-    const __m128 tf = _mm_min_ps(_mm_min_ps(_mm_max_ps(x0, x1), _mm_max_ps(y0, y1)), _mm_min_ps(_mm_max_ps(z0, z1), _mm_set1_ps(tcull)));
+    const __m128 bxn = _mm_set1_ps(fmaf(N->lo[0], r->idir.x, r->noidn.x)), byn = _mm_set1_ps(fmaf(N->lo[1], r->idir.y, r->noidn.y)),
+                 bzn = _mm_set1_ps(fmaf(N->lo[2], r->idir.z, r->noidn.z));
+    const __m128 bxf = _mm_set1_ps(far_offset(fmaf(N->lo[0], r->idir.x, r->noidn.x), r->noidn.x)),
+                 byf = _mm_set1_ps(far_offset(fmaf(N->lo[1], r->idir.y, r->noidn.y), r->noidn.y)),
+                 bzf = _mm_set1_ps(far_offset(fmaf(N->lo[2], r->idir.z, r->noidn.z), r->noidn.z));
+    const __m128 qlx = q_bytes(N->qlo_x), qhx = q_bytes(N->qhi_x), qly = q_bytes(N->qlo_y), qhy = q_bytes(N->qhi_y);
+    const __m128 qlz = q_bytes(N->qlo_z), qhz = q_bytes(N->qhi_z);
+    const __m128 x0n = _mm_fmadd_ps(qlx, ax, bxn), x1n = _mm_fmadd_ps(qhx, ax, bxn), x0f = _mm_fmadd_ps(qlx, ax, bxf), x1f = _mm_fmadd_ps(qhx, ax, bxf);
+    const __m128 y0n = _mm_fmadd_ps(qly, ay, byn), y1n = _mm_fmadd_ps(qhy, ay, byn), y0f = _mm_fmadd_ps(qly, ay, byf), y1f = _mm_fmadd_ps(qhy, ay, byf);
+    const __m128 z0n = _mm_fmadd_ps(qlz, az, bzn), z1n = _mm_fmadd_ps(qhz, az, bzn), z0f = _mm_fmadd_ps(qlz, az, bzf), z1f = _mm_fmadd_ps(qhz, az, bzf);
+    const __m128 tn = _mm_max_ps(_mm_max_ps(_mm_min_ps(x0n, x1n), _mm_min_ps(y0n, y1n)), _mm_max_ps(_mm_min_ps(z0n, z1n), _mm_set1_ps(tmin)));
+    const __m128 tf = _mm_min_ps(_mm_min_ps(_mm_max_ps(x0f, x1f), _mm_max_ps(y0f, y1f)), _mm_min_ps(_mm_max_ps(z0f, z1f), _mm_set1_ps(tcull)));
     _mm_storeu_ps(tn_out, tn);
     return _mm_movemask_ps(_mm_cmple_ps(tn, tf)); /* unused slots are point boxes: no test of their own */
 }
@@ -1137,6 +1151,25 @@ int oracle_occluded(const oracle_scene* s, const float o[3], const float d[3], f
     ray_setup(&r, v3_make(o[0], o[1], o[2]), v3_make(d[0], d[1], d[2]));
     trav_count c = { 0, 0 };
     return brute ? brute_any(s, &r, tmin, tmax, &c) : trace_any(s, &r, tmin, tmax, &c);
+}
+
+/* closest hit of n ray records {ox, oy, oz, tmin, dx, dy, dz, tmax} (the layout of crt_trace_rays), over the tree or over every
+ * triangle (brute): t (the ray's tmax on a miss), inst / prim (ORACLE_MISS on a miss); each output may be NULL */
+void oracle_trace_rays(const oracle_scene* s, uint32_t n, const float* rays, int brute, float* t, uint32_t* inst, uint32_t* prim)
+{
+    #pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+        const float* q = rays + 8 * i;
+        ray r;
+        ray_setup(&r, v3_make(q[0], q[1], q[2]), v3_make(q[4], q[5], q[6]));
+        trav_count c = { 0, 0 };
+        hit_rec h;
+        if (brute) brute_closest(s, &r, q[3], q[7], &h, &c);
+        else trace_closest(s, &r, q[3], q[7], &h, &c);
+        if (t) t[i] = h.t;
+        if (inst) inst[i] = h.hit ? s->tris[h.tri].inst : ORACLE_MISS;
+        if (prim) prim[i] = h.hit ? s->tris[h.tri].prim : ORACLE_MISS;
+    }
 }
 
 int oracle_intersect_tri(const float o[3], const float d[3], const float v0[3], const float v1[3],

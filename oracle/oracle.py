@@ -119,6 +119,8 @@ def lib():
         L.oracle_unorm8.argtypes = [C.c_float]
         L.oracle_intersect_tri.restype = C.c_int
         L.oracle_intersect_tri.argtypes = [C.c_void_p] * 5 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oracle_trace_rays.restype = None
+        L.oracle_trace_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_max_threads.restype = C.c_int
         L.oracle_scene_set_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.oracle_scene_uvs.restype = C.c_void_p
@@ -301,6 +303,17 @@ def occluded(scene, o, d, tmin, tmax, brute_force=False):
     L.oracle_occluded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int]
     o, d = _f32(o, 3), _f32(d, 3)
     return int(L.oracle_occluded(scene.h, o.ctypes.data, d.ctypes.data, float(np.float32(tmin)), float(np.float32(tmax)), int(bool(brute_force))))
+
+
+def trace_rays(scene, rays, brute_force=False):
+    """closest hit of ray records {ox, oy, oz, tmin, dx, dy, dz, tmax} (the layout of the product's make_rays): dict of t (N,)
+    float32 (tmax on a miss), inst / prim (N,) uint32 (MISS on a miss)"""
+    r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+    n = len(r)
+    out = {"t": np.zeros(n, np.float32), "inst": np.zeros(n, np.uint32), "prim": np.zeros(n, np.uint32)}
+    lib().oracle_trace_rays(scene.h, n, r.ctypes.data, int(bool(brute_force)), out["t"].ctypes.data, out["inst"].ctypes.data,
+                            out["prim"].ctypes.data)
+    return out
 
 
 def ray_dir(rot, px, py, w, h):
