@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "crt_scene_camera_roll", "crt_scene_camera_pan_around_target", "crt_upload_scene_from", "crt_set_camera_from",
     "crt_set_accumulation", "crt_reset_accumulation", "crt_accumulated_samples",
     "crt_trace_rays_device", "crt_occluded_rays_device", "crt_trace_rays", "crt_occluded_rays",
+    "crt_closest_points_device", "crt_closest_points", "crt_count_hits_device", "crt_count_hits", "crt_occupancy_device", "crt_occupancy",
     "crt_update_vertices", "crt_update_vertices_device", "crt_set_mesh_transform", "crt_refit", "crt_mesh_vertices",
     "crt_rebuild",
 ]
@@ -203,6 +204,12 @@ def lib():
         "crt_occluded_rays_device": (C.c_int, [vp, u32, vp, vp, vp]),
         "crt_trace_rays": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp]),
         "crt_occluded_rays": (C.c_int, [vp, u32, vp, vp, vp]),
+        "crt_closest_points_device": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "crt_closest_points": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "crt_count_hits_device": (C.c_int, [vp, u32, vp, vp, vp]),
+        "crt_count_hits": (C.c_int, [vp, u32, vp, vp, vp]),
+        "crt_occupancy_device": (C.c_int, [vp, u32, vp, vp, vp]),
+        "crt_occupancy": (C.c_int, [vp, u32, vp, vp, vp]),
         "crt_update_vertices": (C.c_int, [vp, u32, u32, vp, vp]),
         "crt_update_vertices_device": (C.c_int, [vp, u32, u32, vp, vp]),
         "crt_set_mesh_transform": (C.c_int, [vp, u32, vp]),
@@ -240,6 +247,20 @@ def make_rays(origins, directions, tmin=0.0, tmax=np.inf):
     out[:, 3] = np.broadcast_to(np.asarray(tmin, dtype=np.float32), (n,))
     out[:, 4:7] = d
     out[:, 7] = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,))
+    return out
+
+
+def make_points(xyz, rmax=np.inf):
+    """(N, 4) float32 point records {x, y, z, rmax} for Renderer.closest_points / occupancy / signed_distance.  xyz is (N, 3)
+    or (3,); rmax is a scalar or a length-N array (the search radius of the closest-point query; occupancy ignores it)."""
+    p = np.asarray(xyz, dtype=np.float32)
+    if p.shape[-1:] != (3,) or p.ndim > 2:
+        raise ValueError("xyz must be (N, 3) or (3,)")
+    p = p.reshape(-1, 3)
+    n = p.shape[0]
+    out = np.empty((n, 4), dtype=np.float32)
+    out[:, 0:3] = p
+    out[:, 3] = np.broadcast_to(np.asarray(rmax, dtype=np.float32), (n,))
     return out
 
 
@@ -746,6 +767,66 @@ class Renderer:
         st = FrameStats() if stats else None
         self._ok(lib().crt_occluded_rays_device(self.h, int(n), d_rays, d_occluded, C.byref(st) if stats else None),
                  "crt_occluded_rays_device")
+        return st.as_dict() if stats else None
+
+    # ---- point queries (include/crt_hip.h): records of 4 floats {x, y, z, rmax}, see make_points
+    def closest_points(self, points, want=("dist", "point", "uv", "inst", "prim")):
+        """closest surface point of every point within its rmax (host buffers, synchronous).  Returns a dict of the wanted
+        arrays -- dist (N,) float32, point (N, 3) float32, uv (N, 2) float32, inst / prim (N,) uint32 (MISS on a miss, dist =
+        the record's rmax, point = the query point) -- plus 'stats'."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
+        n = len(pts)
+        shapes = {"dist": ((n,), np.float32), "point": ((n, 3), np.float32), "uv": ((n, 2), np.float32),
+                  "inst": ((n,), np.uint32), "prim": ((n,), np.uint32)}
+        out = {k: np.zeros(*shapes[k]) for k in shapes if k in want}
+        st = FrameStats()
+
+        def p(k):
+            return out[k].ctypes.data if k in out else None
+        self._ok(lib().crt_closest_points(self.h, n, pts.ctypes.data, p("dist"), p("point"), p("uv"), p("inst"), p("prim"), C.byref(st)),
+                 "crt_closest_points")
+        out["stats"] = st.as_dict()
+        return out
+
+    def count_hits(self, rays):
+        """number of triangles every ray crosses in (tmin, tmax): (N,) uint32 (host buffers, synchronous; rays as make_rays)"""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        out = np.zeros(len(r), dtype=np.uint32)
+        self._ok(lib().crt_count_hits(self.h, len(r), r.ctypes.data, out.ctypes.data, None), "crt_count_hits")
+        return out
+
+    def occupancy(self, points):
+        """inside / outside of every point (majority of three crossing parities): (N,) bool (host buffers, synchronous).
+        points: (N, 4) records (make_points) or (N, 3) coordinates."""
+        pts = np.asarray(points, dtype=np.float32)
+        pts = make_points(pts) if pts.shape[-1:] == (3,) else np.ascontiguousarray(pts).reshape(-1, 4)
+        out = np.zeros(len(pts), dtype=np.bool_)
+        self._ok(lib().crt_occupancy(self.h, len(pts), pts.ctypes.data, out.ctypes.data, None), "crt_occupancy")
+        return out
+
+    def signed_distance(self, points):
+        """distance to the closest surface point, negated where the point is inside (occupancy): (N,) float32.
+        points: (N, 4) records (make_points; rmax bounds the search) or (N, 3) coordinates (rmax = inf)."""
+        pts = np.asarray(points, dtype=np.float32)
+        pts = make_points(pts) if pts.shape[-1:] == (3,) else np.ascontiguousarray(pts).reshape(-1, 4)
+        d = self.closest_points(pts, want=("dist",))["dist"]
+        return np.where(self.occupancy(pts), -d, d).astype(np.float32)
+
+    def closest_points_device(self, n, d_points, d_dist=None, d_point=None, d_uv=None, d_inst=None, d_prim=None, stats=False):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_closest_points_device(self.h, int(n), d_points, d_dist, d_point, d_uv, d_inst, d_prim,
+                                                 C.byref(st) if stats else None), "crt_closest_points_device")
+        return st.as_dict() if stats else None
+
+    def count_hits_device(self, n, d_rays, d_count, stats=False):
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_count_hits_device(self.h, int(n), d_rays, d_count, C.byref(st) if stats else None), "crt_count_hits_device")
+        return st.as_dict() if stats else None
+
+    def occupancy_device(self, n, d_points, d_inside, stats=False):
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_occupancy_device(self.h, int(n), d_points, d_inside, C.byref(st) if stats else None), "crt_occupancy_device")
         return st.as_dict() if stats else None
 
     def read_counters(self):

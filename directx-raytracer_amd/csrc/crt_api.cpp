@@ -198,8 +198,8 @@ struct crt_ctx {
     hipStream_t accumStream = nullptr;
     bool accumPending = false;
 
-    // batched ray queries (crt_trace_rays* / crt_occluded_rays*): per arena the launch's cursor, counters and the stack spill
-    // arena of the persistent query kernel.  Arenas belong to queries alone (never to a frame) and, like the path arenas, to the
+    // batched ray and point queries (crt_trace_rays* / crt_occluded_rays*, crt_closest_points* / crt_count_hits* /
+    // crt_occupancy*): per arena the launch's cursor, counters and the stack spill arena of the persistent query kernel.  Arenas belong to queries alone (never to a frame) and, like the path arenas, to the
     // stream that last used one: queries on one stream run one after the other and share an arena, queries on different streams
     // (up to kRing in flight) get arenas of their own.
     struct RayArena {
@@ -212,9 +212,9 @@ struct crt_ctx {
         uint32_t serial = 0;
     } rayArena[kRing];
     uint32_t raySerial = 0;
-    uint32_t rayResident[2] = {};        // resident workgroups of the closest-hit / occlusion query kernel on this device ...
-    uint32_t rayResidentEntries[2] = {}; // ... for this many LDS stack entries
-    void* dRayStage = nullptr; // the host entry points' rays and outputs, grown on demand
+    uint32_t rayResident[5] = {};        // resident workgroups of each query kernel (QueryKind) on this device ...
+    uint32_t rayResidentEntries[5] = {}; // ... for this many LDS stack entries
+    void* dRayStage = nullptr; // the host entry points' records and outputs, grown on demand
     size_t rayStageBytes = 0;
 };
 
@@ -1266,14 +1266,35 @@ int crt_accumulated_samples(const crt_ctx* c, uint32_t* samples)
 
 namespace {
 
-// Batched ray queries.  Outputs of a closest-hit query: t, uv, inst, prim (any may be NULL); of an occlusion query: occluded.
-struct RayOutputs {
-    void* t = nullptr;
-    void* uv = nullptr;
-    void* inst = nullptr;
-    void* prim = nullptr;
-    void* occluded = nullptr;
+// Batched ray and point queries.  A query is n records of one kind (32-byte rays or 16-byte points) and up to five outputs
+// of a fixed size per record; every kind runs one persistent kernel (ray_kernels.hip, point_kernels.hip) over an arena of
+// the context.
+enum QueryKind { kQueryClosestHit = 0, kQueryOcclusion = 1, kQueryClosestPoint = 2, kQueryCount = 3, kQueryOccupancy = 4 };
+struct QueryOutput {
+    void* p = nullptr;
+    uint32_t bytes = 0; // per record
+    uint32_t align = 1; // of a device pointer
 };
+struct QuerySpec {
+    const char* what;
+    QueryKind kind;
+    uint32_t recordBytes;
+    const char* outputNames; // for the alignment message
+    QueryOutput out[5];      // the kind's outputs, in a fixed order; NULL = not wanted
+};
+
+QuerySpec rayQuerySpec(const char* what, bool occlusion, void* t, void* uv, void* inst, void* prim, void* occluded)
+{
+    QuerySpec s{ what, occlusion ? kQueryOcclusion : kQueryClosestHit, 32u, occlusion ? "occlusion" : "t / uv / inst / prim", {} };
+    if (occlusion) s.out[0] = { occluded, 1u, 1u };
+    else {
+        s.out[0] = { t, 4u, 4u };
+        s.out[1] = { uv, 8u, 8u };
+        s.out[2] = { inst, 4u, 4u };
+        s.out[3] = { prim, 4u, 4u };
+    }
+    return s;
+}
 
 // what every query entry point checks before anything is launched
 int checkQuery(crt_ctx* c, const char* what)
@@ -1283,49 +1304,59 @@ int checkQuery(crt_ctx* c, const char* what)
     return applyRefit(c, nullptr);
 }
 
-int checkDeviceOutputs(crt_ctx* c, const char* what, const void* rays, const RayOutputs& o, bool occlusion)
+int checkOutputs(crt_ctx* c, const QuerySpec& s)
 {
-    if (!rays) return fail(c, CRT_EINVAL, "%s: ray buffer is NULL", what);
-    if (reinterpret_cast<uintptr_t>(rays) & 15u) return fail(c, CRT_EINVAL, "%s: ray buffer %p is not 16-byte aligned", what, rays);
-    if (occlusion) {
-        if (!o.occluded) return fail(c, CRT_EINVAL, "%s: occlusion output is NULL", what);
-        return CRT_OK;
-    }
-    if (!o.t && !o.uv && !o.inst && !o.prim) return fail(c, CRT_EINVAL, "%s: every output is NULL", what);
-    if ((reinterpret_cast<uintptr_t>(o.t) | reinterpret_cast<uintptr_t>(o.inst) | reinterpret_cast<uintptr_t>(o.prim)) & 3u)
-        return fail(c, CRT_EINVAL, "%s: t / inst / prim outputs must be 4-byte aligned", what);
-    if (reinterpret_cast<uintptr_t>(o.uv) & 7u) return fail(c, CRT_EINVAL, "%s: uv output must be 8-byte aligned", what);
+    for (const QueryOutput& o : s.out)
+        if (o.p) return CRT_OK;
+    return fail(c, CRT_EINVAL, "%s: every output is NULL", s.what);
+}
+
+int checkDeviceOutputs(crt_ctx* c, const QuerySpec& s, const void* records)
+{
+    if (!records) return fail(c, CRT_EINVAL, "%s: record buffer is NULL", s.what);
+    if (reinterpret_cast<uintptr_t>(records) & 15u) return fail(c, CRT_EINVAL, "%s: record buffer %p is not 16-byte aligned", s.what, records);
+    if (const int rc = checkOutputs(c, s)) return rc;
+    for (const QueryOutput& o : s.out)
+        if (reinterpret_cast<uintptr_t>(o.p) & (o.align - 1u))
+            return fail(c, CRT_EINVAL, "%s: output %p (%s) is not %u-byte aligned", s.what, o.p, s.outputNames, o.align);
     return CRT_OK;
 }
 
-// Enqueue one query of n > 0 rays (device pointers) on the context's stream; with stats, time it, synchronise and fill them.
-int runRayQuery(crt_ctx* c, uint32_t n, const void* d_rays, const RayOutputs& o, bool occlusion, crt_frame_stats* stats)
+uint32_t queryResident(QueryKind kind, uint32_t stack_entries)
+{
+    switch (kind) {
+    case kQueryClosestHit: return crt::rayQueryResident(false, stack_entries);
+    case kQueryOcclusion: return crt::rayQueryResident(true, stack_entries);
+    case kQueryClosestPoint: return crt::pointQueryResident(crt::kPointClosest, stack_entries);
+    case kQueryCount: return crt::pointQueryResident(crt::kPointCount, stack_entries);
+    default: return crt::pointQueryResident(crt::kPointOccupancy, stack_entries);
+    }
+}
+
+// What a query kernel gets from its arena: grid, chunking, cursor, counters and the stack spill arena
+struct QueryLaunch {
+    uint32_t stack_entries, spill_stride, chunk, grid;
+    uint32_t* cursor;
+    unsigned long long* counters;
+    int* spill;
+    crt_ctx::RayArena* arena;
+};
+
+// One query of n > 0 records on the context's stream, in two halves around the kernel launch.  beginQuery sizes the persistent
+// grid, takes an arena and (with stats) starts the timer; entryWords = ints per stack entry.  endQuery takes the launch's HIP
+// error code and, with stats, synchronises and fills them.
+int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t entryWords, crt_frame_stats* stats, QueryLaunch& ql)
 {
     HIP_TRY(c, hipSetDevice(c->device));
-    crt::RayQueryParams q;
-    std::memset(&q, 0, sizeof(q));
-    q.nodes = c->dNodes;
-    q.tris = c->dTris;
-    q.n_nodes = c->bvh.nNodes4;
-    q.rays = d_rays;
-    q.n = n;
-    q.t = static_cast<float*>(o.t);
-    q.uv = static_cast<float*>(o.uv);
-    q.inst = static_cast<uint32_t*>(o.inst);
-    q.prim = static_cast<uint32_t*>(o.prim);
-    q.occluded = static_cast<unsigned char*>(o.occluded);
-    q.stack_entries = c->tuneStackEntries ? c->tuneStackEntries : 16u; // as fillParams
-    const uint32_t deepest = 3u * c->bvh.depth4 + 1u;                 // as runRender
-    q.spill_stride = deepest > q.stack_entries ? deepest - q.stack_entries : 1u;
-    q.inner_min = occlusion ? c->tuneInnerMinAny : c->tuneInnerMin;
-    const int kind = occlusion ? 1 : 0;
-    if (c->rayResident[kind] == 0u || c->rayResidentEntries[kind] != q.stack_entries) {
-        c->rayResident[kind] = crt::rayQueryResident(occlusion, q.stack_entries);
-        c->rayResidentEntries[kind] = q.stack_entries;
-        if (c->rayResident[kind] == 0u) return fail(c, CRT_EHIP, "ray query kernel: occupancy query failed");
+    ql.stack_entries = c->tuneStackEntries ? c->tuneStackEntries : 16u; // as fillParams
+    const uint32_t deepest = 3u * c->bvh.depth4 + 1u;                  // as runRender
+    ql.spill_stride = (deepest > ql.stack_entries ? deepest - ql.stack_entries : 1u) * entryWords;
+    if (c->rayResident[kind] == 0u || c->rayResidentEntries[kind] != ql.stack_entries) {
+        c->rayResident[kind] = queryResident(kind, ql.stack_entries);
+        c->rayResidentEntries[kind] = ql.stack_entries;
+        if (c->rayResident[kind] == 0u) return fail(c, CRT_EHIP, "query kernel: occupancy query failed");
     }
-    uint32_t grid = 0;
-    crt::rayQueryLayout(n, c->rayResident[kind], q.chunk, grid);
+    crt::rayQueryLayout(n, c->rayResident[kind], ql.chunk, ql.grid);
 
     // the arena this stream used last; else an unused one; else the least recently used one of another stream, once the
     // query that used it last is done
@@ -1340,7 +1371,7 @@ int runRayQuery(crt_ctx* c, uint32_t n, const void* d_rays, const RayOutputs& o,
         arena->used = true;
     }
     constexpr size_t kHead = 256; // cursor at 0, counters at 64
-    const size_t need = kHead + static_cast<size_t>(grid) * 64u * q.spill_stride * sizeof(int);
+    const size_t need = kHead + static_cast<size_t>(ql.grid) * 64u * ql.spill_stride * sizeof(int);
     if (arena->bytes < need) {
         HIP_TRY(c, hipDeviceSynchronize()); // (the arena may still be in use by a query on its stream)
         if (arena->mem) (void)hipFree(arena->mem);
@@ -1351,15 +1382,19 @@ int runRayQuery(crt_ctx* c, uint32_t n, const void* d_rays, const RayOutputs& o,
     }
     if (!arena->lastUse) HIP_TRY(c, hipEventCreateWithFlags(&arena->lastUse, hipEventDisableTiming));
     arena->serial = ++c->raySerial;
-    q.cursor = reinterpret_cast<uint32_t*>(arena->mem);
-    q.counters = reinterpret_cast<unsigned long long*>(arena->mem + 64);
-    q.spill = reinterpret_cast<int*>(arena->mem + kHead);
+    ql.cursor = reinterpret_cast<uint32_t*>(arena->mem);
+    ql.counters = reinterpret_cast<unsigned long long*>(arena->mem + 64);
+    ql.spill = reinterpret_cast<int*>(arena->mem + kHead);
     HIP_TRY(c, hipMemsetAsync(arena->mem, 0, kHead, c->stream));
-
-    const bool counting = c->counting;
+    ql.arena = arena;
     if (stats) HIP_TRY(c, hipEventRecord(c->evStart, c->stream));
-    const int rc = crt::launchRayQuery(q, occlusion, counting, grid, c->stream);
-    if (rc != 0) return fail(c, CRT_EHIP, "ray query kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+    return CRT_OK;
+}
+
+int endQuery(crt_ctx* c, QueryKind kind, uint32_t n, const QueryLaunch& ql, int rc, crt_frame_stats* stats)
+{
+    crt_ctx::RayArena* arena = ql.arena;
+    if (rc != 0) return fail(c, CRT_EHIP, "query kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
     if (stats) HIP_TRY(c, hipEventRecord(c->evStop, c->stream));
     HIP_TRY(c, hipEventRecord(arena->lastUse, c->stream));
     arena->pending = true;
@@ -1369,16 +1404,96 @@ int runRayQuery(crt_ctx* c, uint32_t n, const void* d_rays, const RayOutputs& o,
         HIP_TRY(c, hipEventElapsedTime(&ms, c->evStart, c->evStop));
         std::memset(stats, 0, sizeof(*stats));
         stats->kernel_ms = ms;
-        if (occlusion) stats->rays_shadow = n;
-        else stats->rays_primary = n;
-        if (counting) {
+        if (kind == kQueryOcclusion) stats->rays_shadow = n;
+        else stats->rays_primary = kind == kQueryOccupancy ? 3ull * n : n;
+        if (c->counting) {
             unsigned long long host[2] = { 0, 0 };
-            HIP_TRY(c, hipMemcpy(host, q.counters, sizeof(host), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(host, ql.counters, sizeof(host), hipMemcpyDeviceToHost));
             stats->nodes_visited = host[0];
             stats->tris_tested = host[1];
         }
     }
     return CRT_OK;
+}
+
+int runRayQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_rays, void* const d[5], crt_frame_stats* stats)
+{
+    const bool occlusion = s.kind == kQueryOcclusion;
+    crt::RayQueryParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.nodes = c->dNodes;
+    q.tris = c->dTris;
+    q.n_nodes = c->bvh.nNodes4;
+    q.rays = d_rays;
+    q.n = n;
+    if (occlusion) q.occluded = static_cast<unsigned char*>(d[0]);
+    else {
+        q.t = static_cast<float*>(d[0]);
+        q.uv = static_cast<float*>(d[1]);
+        q.inst = static_cast<uint32_t*>(d[2]);
+        q.prim = static_cast<uint32_t*>(d[3]);
+    }
+    q.inner_min = occlusion ? c->tuneInnerMinAny : c->tuneInnerMin;
+    QueryLaunch ql;
+    if (const int rc = beginQuery(c, s.kind, n, 1u, stats, ql)) return rc;
+    q.stack_entries = ql.stack_entries;
+    q.spill_stride = ql.spill_stride;
+    q.chunk = ql.chunk;
+    q.cursor = ql.cursor;
+    q.counters = ql.counters;
+    q.spill = ql.spill;
+    return endQuery(c, s.kind, n, ql, crt::launchRayQuery(q, occlusion, c->counting, ql.grid, c->stream), stats);
+}
+
+// the closest-point search's absolute pruning margin: 2^-18 x the diagonal of the root box, rounded up
+float pointPad(const crt_ctx* c)
+{
+    double dd = 0.0;
+    for (int a = 0; a < 3; a++) {
+        const double e = static_cast<double>(c->sceneHi[a]) - static_cast<double>(c->sceneLo[a]);
+        dd += e * e;
+    }
+    return static_cast<float>(std::sqrt(dd) * 0x1p-18 * (1.0 + 0x1p-20));
+}
+
+int runPointQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, void* const d[5], crt_frame_stats* stats)
+{
+    const crt::PointQueryKind pk = s.kind == kQueryClosestPoint ? crt::kPointClosest : (s.kind == kQueryCount ? crt::kPointCount : crt::kPointOccupancy);
+    crt::PointQueryParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.nodes = c->dNodes;
+    q.tris = c->dTris;
+    q.n_nodes = c->bvh.nNodes4;
+    q.records = d_records;
+    q.n = n;
+    if (pk == crt::kPointClosest) {
+        q.dist = static_cast<float*>(d[0]);
+        q.point = static_cast<float*>(d[1]);
+        q.uv = static_cast<float*>(d[2]);
+        q.inst = static_cast<uint32_t*>(d[3]);
+        q.prim = static_cast<uint32_t*>(d[4]);
+        q.pad = pointPad(c);
+    } else if (pk == crt::kPointCount) {
+        q.count = static_cast<uint32_t*>(d[0]);
+    } else {
+        q.inside = static_cast<unsigned char*>(d[0]);
+    }
+    q.inner_min = pk == crt::kPointClosest ? c->tuneInnerMin : c->tuneInnerMinAny;
+    QueryLaunch ql;
+    if (const int rc = beginQuery(c, s.kind, n, crt::pointQueryEntryWords(pk), stats, ql)) return rc;
+    q.stack_entries = ql.stack_entries;
+    q.spill_stride = ql.spill_stride;
+    q.chunk = ql.chunk;
+    q.cursor = ql.cursor;
+    q.counters = ql.counters;
+    q.spill = ql.spill;
+    return endQuery(c, s.kind, n, ql, crt::launchPointQuery(q, pk, c->counting, ql.grid, c->stream), stats);
+}
+
+int runKind(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, void* const d[5], crt_frame_stats* stats)
+{
+    if (s.kind == kQueryClosestHit || s.kind == kQueryOcclusion) return runRayQuery(c, s, n, d_records, d, stats);
+    return runPointQuery(c, s, n, d_records, d, stats);
 }
 
 void zeroStats(crt_frame_stats* stats, std::chrono::steady_clock::time_point t0)
@@ -1388,40 +1503,39 @@ void zeroStats(crt_frame_stats* stats, std::chrono::steady_clock::time_point t0)
     stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-int queryDevice(crt_ctx* c, const char* what, uint32_t n, const void* d_rays, const RayOutputs& o, bool occlusion, crt_frame_stats* stats)
+int queryDevice(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, crt_frame_stats* stats)
 {
-    int rc = checkQuery(c, what);
+    int rc = checkQuery(c, s.what);
     if (rc) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     if (n == 0u) { // nothing to look at, nothing launched
         zeroStats(stats, t0);
         return CRT_OK;
     }
-    if ((rc = checkDeviceOutputs(c, what, d_rays, o, occlusion)) != CRT_OK) return rc;
-    if ((rc = runRayQuery(c, n, d_rays, o, occlusion, stats)) != CRT_OK) return rc;
+    if ((rc = checkDeviceOutputs(c, s, d_records)) != CRT_OK) return rc;
+    void* const d[5] = { s.out[0].p, s.out[1].p, s.out[2].p, s.out[3].p, s.out[4].p };
+    if ((rc = runKind(c, s, n, d_records, d, stats)) != CRT_OK) return rc;
     if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CRT_OK;
 }
 
-// host buffers: staged through the context's device buffer {rays | t | uv | inst | prim | occluded}; synchronous
-int queryHost(crt_ctx* c, const char* what, uint32_t n, const float* rays, const RayOutputs& host, bool occlusion, crt_frame_stats* stats)
+// host buffers: staged through the context's device buffer {records | outputs in order}; synchronous
+int queryHost(crt_ctx* c, const QuerySpec& s, uint32_t n, const float* records, crt_frame_stats* stats)
 {
-    int rc = checkQuery(c, what);
+    int rc = checkQuery(c, s.what);
     if (rc) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     if (n == 0u) {
         zeroStats(stats, t0);
         return CRT_OK;
     }
-    if (!rays) return fail(c, CRT_EINVAL, "%s: ray buffer is NULL", what);
-    if (occlusion ? !host.occluded : (!host.t && !host.uv && !host.inst && !host.prim)) return fail(c, CRT_EINVAL, "%s: every output is NULL", what);
+    if (!records) return fail(c, CRT_EINVAL, "%s: record buffer is NULL", s.what);
+    if ((rc = checkOutputs(c, s)) != CRT_OK) return rc;
     const size_t nn = n;
     auto up = [](size_t b) { return (b + 255u) & ~static_cast<size_t>(255u); };
-    const size_t bytes[5] = { occlusion ? 0u : (host.t ? nn * 4u : 0u), occlusion ? 0u : (host.uv ? nn * 8u : 0u),
-                              occlusion ? 0u : (host.inst ? nn * 4u : 0u), occlusion ? 0u : (host.prim ? nn * 4u : 0u),
-                              occlusion ? nn : 0u };
-    size_t off[5], total = up(nn * 32u);
+    size_t bytes[5], off[5], total = up(nn * s.recordBytes);
     for (int i = 0; i < 5; i++) {
+        bytes[i] = s.out[i].p ? nn * s.out[i].bytes : 0u;
         off[i] = total;
         total += up(bytes[i]);
     }
@@ -1435,49 +1549,83 @@ int queryHost(crt_ctx* c, const char* what, uint32_t n, const float* rays, const
         c->rayStageBytes = total;
     }
     unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
-    RayOutputs d;
-    void* const hostPtr[5] = { host.t, host.uv, host.inst, host.prim, host.occluded };
     void* devPtr[5];
     for (int i = 0; i < 5; i++) devPtr[i] = bytes[i] ? base + off[i] : nullptr;
-    d.t = devPtr[0]; d.uv = devPtr[1]; d.inst = devPtr[2]; d.prim = devPtr[3]; d.occluded = devPtr[4];
-    HIP_TRY(c, hipMemcpyAsync(base, rays, nn * 32u, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(base, records, nn * s.recordBytes, hipMemcpyHostToDevice, c->stream));
     crt_frame_stats local;
-    if ((rc = runRayQuery(c, n, base, d, occlusion, stats ? stats : &local)) != CRT_OK) return rc;
+    if ((rc = runKind(c, s, n, base, devPtr, stats ? stats : &local)) != CRT_OK) return rc;
     for (int i = 0; i < 5; i++)
-        if (bytes[i]) HIP_TRY(c, hipMemcpyAsync(hostPtr[i], devPtr[i], bytes[i], hipMemcpyDeviceToHost, c->stream));
+        if (bytes[i]) HIP_TRY(c, hipMemcpyAsync(s.out[i].p, devPtr[i], bytes[i], hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CRT_OK;
 }
 
+QuerySpec closestPointSpec(const char* what, void* dist, void* point, void* uv, void* inst, void* prim)
+{
+    QuerySpec s{ what, kQueryClosestPoint, 16u, "dist / point / uv / inst / prim", {} };
+    s.out[0] = { dist, 4u, 4u };
+    s.out[1] = { point, 12u, 4u };
+    s.out[2] = { uv, 8u, 8u };
+    s.out[3] = { inst, 4u, 4u };
+    s.out[4] = { prim, 4u, 4u };
+    return s;
+}
+QuerySpec countSpec(const char* what, void* count) { return QuerySpec{ what, kQueryCount, 32u, "count", { { count, 4u, 4u } } }; }
+QuerySpec occupancySpec(const char* what, void* inside) { return QuerySpec{ what, kQueryOccupancy, 16u, "inside", { { inside, 1u, 1u } } }; }
+
 } // namespace
 
 int crt_trace_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_t, void* d_uv, void* d_inst, void* d_prim, crt_frame_stats* stats)
 {
-    RayOutputs o;
-    o.t = d_t; o.uv = d_uv; o.inst = d_inst; o.prim = d_prim;
-    return queryDevice(c, "crt_trace_rays_device", n, d_rays, o, false, stats);
+    return queryDevice(c, rayQuerySpec("crt_trace_rays_device", false, d_t, d_uv, d_inst, d_prim, nullptr), n, d_rays, stats);
 }
 
 int crt_occluded_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_occluded, crt_frame_stats* stats)
 {
-    RayOutputs o;
-    o.occluded = d_occluded;
-    return queryDevice(c, "crt_occluded_rays_device", n, d_rays, o, true, stats);
+    return queryDevice(c, rayQuerySpec("crt_occluded_rays_device", true, nullptr, nullptr, nullptr, nullptr, d_occluded), n, d_rays, stats);
 }
 
 int crt_trace_rays(crt_ctx* c, uint32_t n, const float* rays, float* t, float* uv, uint32_t* inst, uint32_t* prim, crt_frame_stats* stats)
 {
-    RayOutputs o;
-    o.t = t; o.uv = uv; o.inst = inst; o.prim = prim;
-    return queryHost(c, "crt_trace_rays", n, rays, o, false, stats);
+    return queryHost(c, rayQuerySpec("crt_trace_rays", false, t, uv, inst, prim, nullptr), n, rays, stats);
 }
 
 int crt_occluded_rays(crt_ctx* c, uint32_t n, const float* rays, uint8_t* occluded, crt_frame_stats* stats)
 {
-    RayOutputs o;
-    o.occluded = occluded;
-    return queryHost(c, "crt_occluded_rays", n, rays, o, true, stats);
+    return queryHost(c, rayQuerySpec("crt_occluded_rays", true, nullptr, nullptr, nullptr, nullptr, occluded), n, rays, stats);
+}
+
+int crt_closest_points_device(crt_ctx* c, uint32_t n, const void* d_points, void* d_dist, void* d_point, void* d_uv, void* d_inst,
+                              void* d_prim, crt_frame_stats* stats)
+{
+    return queryDevice(c, closestPointSpec("crt_closest_points_device", d_dist, d_point, d_uv, d_inst, d_prim), n, d_points, stats);
+}
+
+int crt_closest_points(crt_ctx* c, uint32_t n, const float* points, float* dist, float* point, float* uv, uint32_t* inst, uint32_t* prim,
+                       crt_frame_stats* stats)
+{
+    return queryHost(c, closestPointSpec("crt_closest_points", dist, point, uv, inst, prim), n, points, stats);
+}
+
+int crt_count_hits_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_count, crt_frame_stats* stats)
+{
+    return queryDevice(c, countSpec("crt_count_hits_device", d_count), n, d_rays, stats);
+}
+
+int crt_count_hits(crt_ctx* c, uint32_t n, const float* rays, uint32_t* count, crt_frame_stats* stats)
+{
+    return queryHost(c, countSpec("crt_count_hits", count), n, rays, stats);
+}
+
+int crt_occupancy_device(crt_ctx* c, uint32_t n, const void* d_points, void* d_inside, crt_frame_stats* stats)
+{
+    return queryDevice(c, occupancySpec("crt_occupancy_device", d_inside), n, d_points, stats);
+}
+
+int crt_occupancy(crt_ctx* c, uint32_t n, const float* points, uint8_t* inside, crt_frame_stats* stats)
+{
+    return queryHost(c, occupancySpec("crt_occupancy", inside), n, points, stats);
 }
 
 int crt_render_frame_device(crt_ctx* c, uint32_t w, uint32_t h, void* d_rgba8, void* d_hit_inst, void* d_hit_prim,

@@ -151,6 +151,35 @@ uint32_t rayQueryResident(bool occlusion, uint32_t stack_entries);
 // records per reservation and grid (persistent: at most `resident` workgroups) of a query of n rays
 void rayQueryLayout(uint32_t n, uint32_t resident, uint32_t& chunk, uint32_t& grid);
 int launchRayQuery(const RayQueryParams& q, bool occlusion, bool counting, uint32_t grid, ihipStream_t* stream);
+// point queries (point_kernels.hip; crt_closest_points* / crt_count_hits* / crt_occupancy*): n caller-supplied records, point
+// records of 4 floats {x, y, z, rmax} (closest point, occupancy) or ray records (hit counts), over the 4-wide tree
+enum PointQueryKind { kPointClosest = 0, kPointCount = 1, kPointOccupancy = 2 };
+struct PointQueryParams {
+    const void* nodes;            // as RayQueryParams
+    const void* tris;
+    uint32_t n_nodes;
+    const void* records;          // n x 16 bytes (points) or n x 32 bytes (rays), 16-byte aligned
+    uint32_t n;
+    float* dist;                  // closest point, each nullable: distance, point (3 floats), {u, v} (8-byte aligned), inst, prim
+    float* point;
+    float* uv;
+    uint32_t* inst;
+    uint32_t* prim;
+    uint32_t* count;              // hit counts: one uint32 per ray
+    unsigned char* inside;        // occupancy: one byte per point
+    float pad;                    // closest point: absolute pruning margin, 2^-18 x the root box's diagonal
+    uint32_t* cursor;             // as RayQueryParams
+    unsigned long long* counters;
+    int* spill;                   // stack spill arena: grid x 64 lanes x spill_stride ints
+    uint32_t spill_stride;
+    uint32_t stack_entries;
+    uint32_t inner_min;
+    uint32_t chunk;
+};
+// ints per stack entry of a point query kernel (the closest-point stack keeps each entry's box bound beside its reference)
+inline uint32_t pointQueryEntryWords(PointQueryKind kind) { return kind == kPointClosest ? 2u : 1u; }
+uint32_t pointQueryResident(PointQueryKind kind, uint32_t stack_entries);
+int launchPointQuery(const PointQueryParams& q, PointQueryKind kind, bool counting, uint32_t grid, ihipStream_t* stream);
 // exhaustive check of the triangle test's reciprocal (ray_kernels.hip rcpCheckKernel) into out[0..6] (device memory, zeroed
 // except out[6] = ~0 by the caller)
 int launchRcpCheck(unsigned long long* out, ihipStream_t* stream);

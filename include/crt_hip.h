@@ -369,6 +369,62 @@ int crt_trace_rays(crt_ctx* ctx, uint32_t n, const float* rays, float* t, float*
                    crt_frame_stats* stats);
 int crt_occluded_rays(crt_ctx* ctx, uint32_t n, const float* rays, uint8_t* occluded, crt_frame_stats* stats);
 
+/* ---- point queries: closest surface point, hit counts, occupancy (no reference counterpart; the set of Open3D's
+ * RaycastingScene: compute_closest_points / compute_distance / compute_signed_distance / compute_occupancy /
+ * count_intersections).  SDF and occupancy training data, collision margins, snapping a point to the surface.
+ * - Point record: 4 floats (16 B) {x, y, z, rmax}; the buffer holds n records, contiguous.
+ * - Closest point (crt_closest_points*): over every triangle's leaf-ordered record {v0, e1, e2} as traced (a = v0, ab = e1,
+ *   ac = e2), the triangle of smallest computed d2 among those with d2 <= rmax * rmax; equal d2 goes to the lower global
+ *   triangle id (upload ordinal), the frames' tie rule.  Outputs, each optional, not all NULL: dist = sqrtf(d2), point (3 floats,
+ *   the closest point), uv (2 floats: u = weight of v1, v = weight of v2, as in crt_trace_rays), inst, prim.  A miss (no
+ *   triangle within rmax, a record with a NaN, rmax < 0, an empty scene) reports dist = rmax, point = the query point, uv = 0,
+ *   inst = prim = CRT_MISS.  rmax = +inf is allowed.
+ * - Operation order (float, fused multiply-adds only where fmaf is written, / and sqrtf correctly rounded; dot(x, y) =
+ *   fmaf(x.z, y.z, fmaf(x.y, y.y, x.x * y.x))): Ericson's region method (Real-Time Collision Detection 5.1.5) on (a, ab, ac):
+ *     ap = p - a; bp = ap - ab; cp = ap - ac;  d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp),
+ *     d5 = dot(ab, cp), d6 = dot(ac, cp)  (each vector difference per component)
+ *     d1 <= 0 && d2 <= 0 -> (u, v) = (0, 0);  else d3 >= 0 && d4 <= d3 -> (1, 0);
+ *     else vc = d1*d4 - d3*d2; vc <= 0 && d1 >= 0 && d3 <= 0 && d1 - d3 > 0 -> (d1 / (d1 - d3), 0);
+ *     else d6 >= 0 && d5 <= d6 -> (0, 1);
+ *     else vb = d5*d2 - d1*d6; vb <= 0 && d2 >= 0 && d6 <= 0 && d2 - d6 > 0 -> (0, d2 / (d2 - d6));
+ *     else va = d3*d6 - d5*d4, e = d4 - d3, f = d5 - d6; va <= 0 && e >= 0 && f >= 0 && e + f > 0 -> w = e / (e + f), (1 - w, w);
+ *     else s = (va + vb) + vc; va > 0 && vb > 0 && vc > 0 && s < +inf -> (vb / s, vc / s) (the face), and when the triangle
+ *     is a sliver, s <= 2^-10 * (dot(ab, ab) * dot(ac, ac)), the nearer of that point and the edge candidates below (face
+ *     first on equal d2);
+ *     else (degenerate triangles, rounding at a region border) the nearest of the three edges: per edge (base, e) in the order
+ *     (a, ab), (a, ac), (b, ac - ab) with base offset g = ap, ap, bp: t = ee > 0 ? min(max(dot(g, e) / ee, 0), 1) : 0,
+ *     ee = dot(e, e), giving (t, 0), (0, t), (1 - t, t); each candidate's d2 as below, the first smallest one wins.
+ *   Then r = fmaf(-v, ac, fmaf(-u, ab, ap)) per component and d2 = dot(r, r); point = fmaf(v, ac, fmaf(u, ab, a)).  Every
+ *   division has a positive divisor, so no triangle -- zero area, collinear, all three vertices equal -- yields a NaN.
+ * - Hit count (crt_count_hits*): ray records of crt_trace_rays with their NaN and empty-interval rules; the number of
+ *   triangles that the ray queries' Moeller-Trumbore test accepts with tmin < t < tmax, every one of them (no early exit).
+ *   The "boundary rays" limit of the ray queries applies unchanged.
+ * - Occupancy (crt_occupancy*): one byte per point, 1 when at least two of the hit counts of the rays {p, tmin = 0,
+ *   CRT_OCCUPANCY_DIRk, tmax = +inf}, k = 0..2, are odd.  rmax is ignored.  The directions lie at least 16 degrees from
+ *   every axis plane and every cube diagonal, so that grid-sampled points over axis-aligned meshes do not hit edges and
+ *   vertices systematically.  Meaningful for closed meshes; undefined for points on a surface; for open geometry it is
+ *   the majority of three crossing parities, nothing more.  A point with a NaN coordinate is outside.
+ * - Results do not depend on the tree (host SAH, gpu_build LBVH or PLOC, refitted or rebuilt), on the order of the records
+ *   or on scheduling: the closest-point search prunes a box only when no triangle in it can produce a computed d2 <= the
+ *   best so far (the margin holds at any offset from the origin).
+ * - Common rules of the ray queries: pending refits are applied first; a query reads the tree and the triangle records,
+ *   nothing else (camera, mode, accumulation sums, launch orders, frame outputs are untouched); n = 0 returns CRT_OK and
+ *   launches nothing; CRT_ESTATE without a scene.  stats (may be NULL): kernel_ms, total_ms, rays_primary = records traced
+ *   (n; 3n for occupancy), nodes_visited / tris_tested with crt_set_counting(ctx, 1), counted as the frames count them.
+ * *_device: device pointers: points 16-byte, rays 16-byte, dist / point / inst / prim / count 4-byte, uv 8-byte aligned
+ * (CRT_EINVAL otherwise); asynchronous on the context's stream unless stats != NULL.  Host forms: synchronous, staged. */
+#define CRT_OCCUPANCY_DIR0 0x1.75de06p-1f, 0x1.2704acp-2f, 0x1.3d302ap-1f     /* ( 0.730209529,  0.288103759,  0.619508088) */
+#define CRT_OCCUPANCY_DIR1 -0x1.137b5p-1f, 0x1.84aca6p-1f, -0x1.7728acp-2f    /* (-0.538050175,  0.759129703, -0.366366088) */
+#define CRT_OCCUPANCY_DIR2 0x1.adef4p-2f, -0x1.69be36p-2f, -0x1.ac0a56p-1f    /* ( 0.419857979, -0.353264660, -0.836016357) */
+int crt_closest_points_device(crt_ctx* ctx, uint32_t n, const void* d_points, void* d_dist, void* d_point, void* d_uv,
+                              void* d_inst, void* d_prim, crt_frame_stats* stats);
+int crt_closest_points(crt_ctx* ctx, uint32_t n, const float* points, float* dist, float* point, float* uv,
+                       uint32_t* inst, uint32_t* prim, crt_frame_stats* stats);
+int crt_count_hits_device(crt_ctx* ctx, uint32_t n, const void* d_rays, void* d_count, crt_frame_stats* stats);
+int crt_count_hits(crt_ctx* ctx, uint32_t n, const float* rays, uint32_t* count, crt_frame_stats* stats);
+int crt_occupancy_device(crt_ctx* ctx, uint32_t n, const void* d_points, void* d_inside, crt_frame_stats* stats);
+int crt_occupancy(crt_ctx* ctx, uint32_t n, const float* points, uint8_t* inside, crt_frame_stats* stats);
+
 /* ---- dynamic geometry (DXR: acceleration-structure updates and D3D12_RAYTRACING_INSTANCE_DESC::Transform, which the reference
  * fills with the identity for every mesh, R/DXRTRenderer.cpp:690-704).  Opt-in: crt_set_option(ctx, "dynamic", 1) before
  * crt_upload_scene / crt_upload_scene_from; only then does the upload keep what a refit needs in HBM (the meshes' rest and world
