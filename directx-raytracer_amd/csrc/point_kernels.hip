@@ -383,9 +383,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LayLegacy::k
                         ok = (a.x == a.x) & (a.y == a.y) & (a.z == a.z);
                     } else {
                         const float4 a = recs[2u * static_cast<size_t>(idx)], b = recs[2u * static_cast<size_t>(idx) + 1u];
-                        r = makeRay(f3(a.x, a.y, a.z), f3(b.x, b.y, b.z));
-                        tmin = a.w;
-                        tmax = b.w;
+                        queryRay(a, b, r, tmin, tmax); // prescaled, as the ray queries
                         tcull = cullBound(tmax);
                         ok = (a.x == a.x) & (a.y == a.y) & (a.z == a.z) & (b.x == b.x) & (b.y == b.y) & (b.z == b.z) & (tmin < tmax);
                     }

@@ -10,6 +10,7 @@
 // tmin / tmax of its record, so results and fetch counts are those of the oracle's traversal of the same ray, whatever the
 // order of the buffer, the refill timing or the wave scheduling.
 //
+// A record is traced prescaled by a power of two (queryRay, traversal.hip.h): results do not depend on |d|.
 // Arithmetic contract: identical, operation for operation, to oracle/crt_oracle.c (compiled with -ffp-contract=off).
 #include "traversal.hip.h"
 
@@ -46,7 +47,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCCL ? L::kW
     const int innerMin = static_cast<int>(q.inner_min);
 
     Ray r = makeRay(f3(0.0f, 0.0f, 0.0f), f3(0.0f, 0.0f, 1.0f));
-    float tmin = 0.0f, tmax = 0.0f, tcull = 0.0f;
+    float tmin = 0.0f, tmax = 0.0f, tcull = 0.0f; // the prescaled interval (queryRay)
+    float tmaxRec = 0.0f;                         // the record's own tmax: a miss reports it
+    int e = 0;                                    // the record's scale exponent: a hit reports t * 2^-e
     Hit h;
     h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.gid = 0;
     bool occluded = false;
@@ -67,7 +70,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCCL ? L::kW
                     q.occluded[my] = occluded ? 1u : 0u;
                 } else {
                     const bool hit = h.t < tmax;
-                    if (q.t) q.t[my] = h.t; // a miss keeps tmax
+                    if (q.t) q.t[my] = hit ? __builtin_amdgcn_ldexpf(h.t, -e) : tmaxRec;
                     if (q.uv) reinterpret_cast<float2*>(q.uv)[my] = make_float2(h.u, h.v);
                     if (q.inst || q.prim) {
                         uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
@@ -89,9 +92,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCCL ? L::kW
                 if (valid) {
                     my = idx;
                     const float4 a = rays[2u * static_cast<size_t>(idx)], b = rays[2u * static_cast<size_t>(idx) + 1u];
-                    r = makeRay(f3(a.x, a.y, a.z), f3(b.x, b.y, b.z));
-                    tmin = a.w;
-                    tmax = b.w;
+                    e = queryRay(a, b, r, tmin, tmax);
+                    tmaxRec = b.w;
                     h.t = tmax; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.gid = 0;
                     occluded = false;
                     tcull = cullBound(tmax);

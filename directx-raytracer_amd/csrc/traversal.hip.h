@@ -844,6 +844,21 @@ __device__ __forceinline__ uint32_t lanesBelow(unsigned long long m)
 constexpr float kCullPadNeg = 0.999996185302734375f; // 1 - 2^-18
 __device__ __forceinline__ float cullBound(float b) { return b * (b >= 0.0f ? kCullPad : kCullPadNeg); }
 
+// The ray of a query record {ox, oy, oz, tmin} {dx, dy, dz, tmax} (crt_trace_rays*, crt_occluded_rays*, crt_count_hits*: any
+// direction magnitude), prescaled by a power of two as the oracle's query_setup does: (o, tmin 2^e, d 2^-e, tmax 2^e), e the
+// exponent of the largest |d_i|, which lands in [1, 2) (frexp's exponent is 0 for a zero or non-finite input: e = -1 there).
+// The scaling is exact, so every slab distance, pad, cull bound and Moeller-Trumbore value of the scaled ray is that of the
+// record scaled by 2^-e, the hit's t is t' 2^-e, and kDirEps clamps only components below 1e-20 of the largest instead of
+// every component below 1e-20.  The frames' rays have unit length and do not come through here.
+__device__ __forceinline__ int queryRay(const float4 a, const float4 b, Ray& r, float& tmin, float& tmax)
+{
+    const int e = __builtin_amdgcn_frexp_expf(fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fabsf(b.z))) - 1;
+    r = makeRay(f3(a.x, a.y, a.z), f3(__builtin_amdgcn_ldexpf(b.x, -e), __builtin_amdgcn_ldexpf(b.y, -e), __builtin_amdgcn_ldexpf(b.z, -e)));
+    tmin = __builtin_amdgcn_ldexpf(a.w, e);
+    tmax = __builtin_amdgcn_ldexpf(b.w, e);
+    return e;
+}
+
 __device__ __forceinline__ uint32_t waveTotal(uint32_t v)
 {
 #pragma unroll

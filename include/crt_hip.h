@@ -332,6 +332,13 @@ int crt_accumulated_samples(const crt_ctx* ctx, uint32_t* samples); /* samples p
  *   need not be normalised: t is in units of |d|.  A hit is a triangle with tmin < t < tmax, by the frames' Moeller-Trumbore
  *   test (two sided, no culling).  tmin may be 0 or negative, tmax may be +inf.  A record containing a NaN, or with
  *   !(tmin < tmax), is not traced and reports a miss / not occluded; a zero direction is a miss.
+ * - Direction magnitude: any finite non-zero largest component, 2^-149 .. FLT_MAX.  A record is traced as the same ray
+ *   prescaled by a power of two, (o, tmin 2^e, d 2^-e, tmax 2^e) with e the exponent of the largest |d_i|, and t is returned
+ *   as t' 2^-e.  The scaling is exact: a record and its 2^k multiple give the same hit, u, v and fetch counts, and t 2^k is
+ *   the unscaled t, wherever the scaled values stay normal floats.  Edges: tmin 2^e or tmax 2^e below 2^-126 in magnitude is
+ *   rounded; a t that leaves the float range is reported as +inf (still a hit) or as a subnormal; a component below 1e-20 of
+ *   the largest counts as +-1e-20 of it in the slab test (a boundary ray, below).  A zero direction, just outside the
+ *   range, hits nothing.
  * - Closest hit (crt_trace_rays*), per ray, each output optional: t (float), uv (2 floats: u = weight of v1, v = weight of
  *   v2, the frames' barycentrics), inst (uint32 mesh ordinal in upload order), prim (uint32 triangle of that mesh).  Equal t
  *   goes to the lower global triangle id, as in the frames.  Miss: inst = prim = CRT_MISS, t = the ray's tmax, u = v = 0.
@@ -339,9 +346,9 @@ int crt_accumulated_samples(const crt_ctx* ctx, uint32_t* samples); /* samples p
  *   (tmin, tmax): the any-hit traversal with early exit.
  * - Results do not depend on the order of the rays in the buffer, on scheduling or on the tuning options inner_min /
  *   inner_min_any.  The box cull is the frames' (boxes are tested against the best t so far widened by 2^-18 of its
- *   magnitude), so for a ray whose tmax and hit are >= 0 the results and fetch counts are bit for bit the CPU oracle's
- *   traversal of that ray.  For a negative bound the widening keeps its direction (the oracle's and the frames' factor would
- *   narrow it): a triangle strictly inside (tmin, tmax) is found, and ties at t < 0 go to the lower global id, as at t > 0.
+ *   magnitude), so the results and fetch counts are bit for bit the CPU oracle's traversal of that ray.  For a negative bound
+ *   the widening keeps its direction (the frames' factor would narrow it): a triangle strictly inside (tmin, tmax) is found,
+ *   and ties at t < 0 go to the lower global id, as at t > 0.
  * - Limit (boundary rays): the slab test is conservative against the absolute rounding that comes from the ray origin's
  *   distance to the world origin.  Its near and far distances are padded by 2^-21 |o / d| per axis, so a
  *   box the ray enters is not culled for that reason at any offset.  What remains is the relative rounding of the slab
@@ -396,8 +403,9 @@ int crt_occluded_rays(crt_ctx* ctx, uint32_t n, const float* rays, uint8_t* occl
  *     ee = dot(e, e), giving (t, 0), (0, t), (1 - t, t); each candidate's d2 as below, the first smallest one wins.
  *   Then r = fmaf(-v, ac, fmaf(-u, ab, ap)) per component and d2 = dot(r, r); point = fmaf(v, ac, fmaf(u, ab, a)).  Every
  *   division has a positive divisor, so no triangle -- zero area, collinear, all three vertices equal -- yields a NaN.
- * - Hit count (crt_count_hits*): ray records of crt_trace_rays with their NaN and empty-interval rules; the number of
- *   triangles that the ray queries' Moeller-Trumbore test accepts with tmin < t < tmax, every one of them (no early exit).
+ * - Hit count (crt_count_hits*): ray records of crt_trace_rays with their NaN and empty-interval rules and their direction
+ *   magnitude contract (prescaled the same way; counts do not depend on |d|); the number of triangles that the ray queries'
+ *   Moeller-Trumbore test accepts with tmin < t < tmax, every one of them (no early exit).
  *   The "boundary rays" limit of the ray queries applies unchanged.
  * - Occupancy (crt_occupancy*): one byte per point, 1 when at least two of the hit counts of the rays {p, tmin = 0,
  *   CRT_OCCUPANCY_DIRk, tmax = +inf}, k = 0..2, are odd.  rmax is ignored.  The directions lie at least 16 degrees from

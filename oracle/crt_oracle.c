@@ -755,6 +755,35 @@ static inline void ray_setup(ray* r, v3 o, v3 d)
     r->noidn = v3_make(noid.x - fabsf(noid.x) * SLAB_PAD, noid.y - fabsf(noid.y) * SLAB_PAD, noid.z - fabsf(noid.z) * SLAB_PAD);
 }
 
+/* Ray queries (crt_trace_rays / crt_occluded_rays / crt_count_hits: caller records of any direction magnitude) trace the
+ * record prescaled by a power of two: (o, tmin 2^e, d 2^-e, tmax 2^e), e the exponent of the largest |d_i| (it lands in
+ * [1, 2); e = -1 for a zero or non-finite largest component), and return t' 2^-e.  The scaling is exact, so every slab
+ * and Moeller-Trumbore value of the scaled ray is that of the record scaled by 2^-e, and DIR_EPS clamps only components
+ * below 1e-20 of the largest, where the unscaled setup clamped any component below 1e-20. */
+static inline int query_exp(v3 d)
+{
+    const float m = maxf_(maxf_(fabsf(d.x), fabsf(d.y)), fabsf(d.z));
+    int ex = 0;
+    if (m <= FLT_MAX) frexpf(m, &ex); /* m = f 2^ex, f in [0.5, 1); frexpf(0) gives 0 */
+    return ex - 1;
+}
+
+/* the scaled ray of a record {ox, oy, oz, tmin, dx, dy, dz, tmax} and its scaled interval; returns e */
+static inline int query_setup(ray* r, const float* q, float* tmin, float* tmax)
+{
+    const v3 d = v3_make(q[4], q[5], q[6]);
+    const int e = query_exp(d);
+    ray_setup(r, v3_make(q[0], q[1], q[2]), v3_make(ldexpf(d.x, -e), ldexpf(d.y, -e), ldexpf(d.z, -e)));
+    *tmin = ldexpf(q[3], e);
+    *tmax = ldexpf(q[7], e);
+    return e;
+}
+
+/* the box-cull bound of a current bound b (tmax, then the best hit): widened by 2^-18 of |b|, also when b < 0, where
+ * b * CULL_PAD would narrow it (traversal.hip.h cullBound).  The frames' bounds are never negative (tmin = 0.001). */
+#define CULL_PAD_NEG 0.999996185302734375f /* 1 - 2^-18 */
+static inline float cull_bound(float b) { return b * (b >= 0.0f ? CULL_PAD : CULL_PAD_NEG); }
+
 typedef struct { float t, u, v; uint32_t tri; /* leaf-order index */ uint32_t gid; int hit; } hit_rec;
 
 typedef struct { uint64_t nodes, tris; } trav_count;
@@ -806,7 +835,7 @@ static void trace_closest2(const oracle_scene* s, const ray* r, float tmin, floa
     int32_t stack[MAX_DEPTH + 1];
     int sp = 0;
     int32_t cur = 0;
-    float tcull = tmax * CULL_PAD;
+    float tcull = cull_bound(tmax);
     for (;;) {
         if (cur >= 0) {
             const oracle_node* N = &s->nodes[cur];
@@ -833,7 +862,7 @@ static void trace_closest2(const oracle_scene* s, const ray* r, float tmin, floa
                 if (tri_test(r, T, tmin, &t, &u, &v)) {
                     if ((t < h->t) | ((t == h->t) & (T->gid < h->gid))) {
                         h->t = t; h->u = u; h->v = v; h->tri = i; h->gid = T->gid; h->hit = 1;
-                        tcull = t * CULL_PAD;
+                        tcull = cull_bound(t);
                     }
                 }
             }
@@ -850,7 +879,7 @@ static int trace_any2(const oracle_scene* s, const ray* r, float tmin, float tma
     int32_t stack[MAX_DEPTH + 1];
     int sp = 0;
     int32_t cur = 0;
-    const float tcull = tmax * CULL_PAD;
+    const float tcull = cull_bound(tmax);
     for (;;) {
         if (cur >= 0) {
             const oracle_node* N = &s->nodes[cur];
@@ -944,7 +973,7 @@ static void trace_closest4(const oracle_scene* s, const ray* r, float tmin, floa
     int32_t stack[STACK4];
     int sp = 0;
     int32_t cur = 0;
-    float tcull = tmax * CULL_PAD;
+    float tcull = cull_bound(tmax);
     for (;;) {
         if (cur >= 0) {
             const oracle_node4q* N = &s->nodes4q[cur];
@@ -967,7 +996,7 @@ static void trace_closest4(const oracle_scene* s, const ray* r, float tmin, floa
                 if (tri_test(r, T, tmin, &t, &u, &v)) {
                     if ((t < h->t) | ((t == h->t) & (T->gid < h->gid))) {
                         h->t = t; h->u = u; h->v = v; h->tri = i; h->gid = T->gid; h->hit = 1;
-                        tcull = t * CULL_PAD;
+                        tcull = cull_bound(t);
                     }
                 }
             }
@@ -984,7 +1013,7 @@ static int trace_any4(const oracle_scene* s, const ray* r, float tmin, float tma
     int32_t stack[STACK4];
     int sp = 0;
     int32_t cur = 0;
-    const float tcull = tmax * CULL_PAD;
+    const float tcull = cull_bound(tmax);
     for (;;) {
         if (cur >= 0) {
             const oracle_node4q* N = &s->nodes4q[cur];
@@ -1144,43 +1173,70 @@ void oracle_shade_mode(uint32_t mode, uint32_t inst, uint32_t prim, float t, flo
     out_rgb[0] = c.x; out_rgb[1] = c.y; out_rgb[2] = c.z;
 }
 
-/* any-hit query on an arbitrary ray interval (tests: the segments of split packets, csrc/split_packet.hip.h) */
+/* any-hit query on an arbitrary ray interval (tests: the segments of split packets, csrc/split_packet.hip.h), prescaled as a
+ * ray query record (query_setup) */
 int oracle_occluded(const oracle_scene* s, const float o[3], const float d[3], float tmin, float tmax, int brute)
 {
-    ray r;
-    ray_setup(&r, v3_make(o[0], o[1], o[2]), v3_make(d[0], d[1], d[2]));
-    trav_count c = { 0, 0 };
-    return brute ? brute_any(s, &r, tmin, tmax, &c) : trace_any(s, &r, tmin, tmax, &c);
+    const float q[8] = { o[0], o[1], o[2], tmin, d[0], d[1], d[2], tmax };
+    uint8_t occ = 0;
+    oracle_query_rays(s, 1, q, brute, 1, NULL, NULL, NULL, NULL, &occ, NULL, NULL);
+    return occ;
 }
 
-/* closest hit of n ray records {ox, oy, oz, tmin, dx, dy, dz, tmax} (the layout of crt_trace_rays), over the tree or over every
- * triangle (brute): t (the ray's tmax on a miss), inst / prim (ORACLE_MISS on a miss); each output may be NULL */
-void oracle_trace_rays(const oracle_scene* s, uint32_t n, const float* rays, int brute, float* t, uint32_t* inst, uint32_t* prim)
+/* n ray records {ox, oy, oz, tmin, dx, dy, dz, tmax} (the layout of crt_trace_rays), each prescaled (query_setup), over the tree
+ * or over every triangle (brute).  occl = 0, closest hit: t (the record's tmax on a miss), uv (0, 0 on a miss), inst / prim
+ * (ORACLE_MISS on a miss); occl = 1: occ (1 if some triangle lies in (tmin, tmax)).  nodes / tris: the node records and
+ * triangles the query fetched.  A record with a NaN or an empty interval is not traced (a miss, no fetches), as in the query
+ * kernels.  Every output may be NULL. */
+void oracle_query_rays(const oracle_scene* s, uint32_t n, const float* rays, int brute, int occl, float* t, float* uv,
+                       uint32_t* inst, uint32_t* prim, uint8_t* occ, uint32_t* nodes, uint32_t* tris)
 {
-    #pragma omp parallel for schedule(dynamic, 64)
+    #pragma omp parallel for schedule(dynamic, 64) if (n > 64)
     for (int64_t i = 0; i < (int64_t)n; i++) {
         const float* q = rays + 8 * i;
         ray r;
-        ray_setup(&r, v3_make(q[0], q[1], q[2]), v3_make(q[4], q[5], q[6]));
+        float tmin, tmax;
+        const int e = query_setup(&r, q, &tmin, &tmax);
+        const int ok = (q[0] == q[0]) & (q[1] == q[1]) & (q[2] == q[2]) & (q[4] == q[4]) & (q[5] == q[5]) & (q[6] == q[6]) & (tmin < tmax);
         trav_count c = { 0, 0 };
         hit_rec h;
-        if (brute) brute_closest(s, &r, q[3], q[7], &h, &c);
-        else trace_closest(s, &r, q[3], q[7], &h, &c);
-        if (t) t[i] = h.t;
+        h.t = tmax; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.gid = 0; h.hit = 0;
+        int any = 0;
+        if (ok) {
+            if (occl) any = brute ? brute_any(s, &r, tmin, tmax, &c) : trace_any(s, &r, tmin, tmax, &c);
+            else if (brute) brute_closest(s, &r, tmin, tmax, &h, &c);
+            else trace_closest(s, &r, tmin, tmax, &h, &c);
+        }
+        if (t) t[i] = h.hit ? ldexpf(h.t, -e) : q[7];
+        if (uv) { uv[2 * i] = h.u; uv[2 * i + 1] = h.v; }
         if (inst) inst[i] = h.hit ? s->tris[h.tri].inst : ORACLE_MISS;
         if (prim) prim[i] = h.hit ? s->tris[h.tri].prim : ORACLE_MISS;
+        if (occ) occ[i] = (uint8_t)any;
+        if (nodes) nodes[i] = (uint32_t)c.nodes;
+        if (tris) tris[i] = (uint32_t)c.tris;
     }
 }
 
+/* closest hit of n ray records (oracle_query_rays): t, inst / prim; each output may be NULL */
+void oracle_trace_rays(const oracle_scene* s, uint32_t n, const float* rays, int brute, float* t, uint32_t* inst, uint32_t* prim)
+{
+    oracle_query_rays(s, n, rays, brute, 0, t, NULL, inst, prim, NULL, NULL, NULL);
+}
+
+/* one triangle, the ray queries' Moeller-Trumbore on the prescaled record (query_setup): 1 on a hit with t in (tmin, tmax) */
 int oracle_intersect_tri(const float o[3], const float d[3], const float v0[3], const float v1[3],
                          const float v2[3], float tmin, float tmax, float* t, float* u, float* v)
 {
+    const float q[8] = { o[0], o[1], o[2], tmin, d[0], d[1], d[2], tmax };
     ray r;
     oracle_tri T;
-    ray_setup(&r, v3_make(o[0], o[1], o[2]), v3_make(d[0], d[1], d[2]));
+    float lo, hi;
+    const int e = query_setup(&r, q, &lo, &hi);
     for (int k = 0; k < 3; k++) { T.v0[k] = v0[k]; T.e1[k] = v1[k] - v0[k]; T.e2[k] = v2[k] - v0[k]; }
     T.inst = T.prim = T.gid = 0;
-    return tri_test(&r, &T, tmin, t, u, v) & (*t < tmax);
+    const int hit = tri_test(&r, &T, lo, t, u, v) & (*t < hi);
+    *t = ldexpf(*t, -e);
+    return hit;
 }
 
 /* Surface at a closest hit, shared by mode 100 and the path tracer: hit point, shading normal (face normal, or the

@@ -170,6 +170,8 @@ uint8_t oracle_unorm8(float c);
 /* one triangle, Moeller-Trumbore as specified; returns 1 on hit with t in (tmin, tmax) */
 int oracle_occluded(const oracle_scene* s, const float o[3], const float d[3], float tmin, float tmax, int brute);
 void oracle_trace_rays(const oracle_scene* s, uint32_t n, const float* rays, int brute, float* t, uint32_t* inst, uint32_t* prim);
+void oracle_query_rays(const oracle_scene* s, uint32_t n, const float* rays, int brute, int occl, float* t, float* uv,
+                       uint32_t* inst, uint32_t* prim, uint8_t* occ, uint32_t* nodes, uint32_t* tris);
 int oracle_intersect_tri(const float o[3], const float d[3], const float v0[3], const float v1[3],
                          const float v2[3], float tmin, float tmax, float* t, float* u, float* v);
 int oracle_max_threads(void);

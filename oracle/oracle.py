@@ -121,6 +121,8 @@ def lib():
         L.oracle_intersect_tri.argtypes = [C.c_void_p] * 5 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_trace_rays.restype = None
         L.oracle_trace_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oracle_query_rays.restype = None
+        L.oracle_query_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
         L.oracle_max_threads.restype = C.c_int
         L.oracle_scene_set_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.oracle_scene_uvs.restype = C.c_void_p
@@ -306,13 +308,25 @@ def occluded(scene, o, d, tmin, tmax, brute_force=False):
 
 
 def trace_rays(scene, rays, brute_force=False):
-    """closest hit of ray records {ox, oy, oz, tmin, dx, dy, dz, tmax} (the layout of the product's make_rays): dict of t (N,)
-    float32 (tmax on a miss), inst / prim (N,) uint32 (MISS on a miss)"""
+    """closest hit of ray records {ox, oy, oz, tmin, dx, dy, dz, tmax} (the layout of the product's make_rays), each prescaled by
+    a power of two as the query kernels do: dict of t (N,) float32 (tmax on a miss), uv (N, 2) float32, inst / prim (N,) uint32
+    (MISS on a miss), nodes / tris (N,) uint32 (node records and triangles each query fetched)"""
     r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
     n = len(r)
-    out = {"t": np.zeros(n, np.float32), "inst": np.zeros(n, np.uint32), "prim": np.zeros(n, np.uint32)}
-    lib().oracle_trace_rays(scene.h, n, r.ctypes.data, int(bool(brute_force)), out["t"].ctypes.data, out["inst"].ctypes.data,
-                            out["prim"].ctypes.data)
+    out = {"t": np.zeros(n, np.float32), "uv": np.zeros((n, 2), np.float32), "inst": np.zeros(n, np.uint32),
+           "prim": np.zeros(n, np.uint32), "nodes": np.zeros(n, np.uint32), "tris": np.zeros(n, np.uint32)}
+    lib().oracle_query_rays(scene.h, n, r.ctypes.data, int(bool(brute_force)), 0, out["t"].ctypes.data, out["uv"].ctypes.data,
+                            out["inst"].ctypes.data, out["prim"].ctypes.data, None, out["nodes"].ctypes.data, out["tris"].ctypes.data)
+    return out
+
+
+def occluded_rays(scene, rays, brute_force=False):
+    """any hit of ray records (as trace_rays): dict of occluded (N,) uint8, nodes / tris (N,) uint32"""
+    r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+    n = len(r)
+    out = {"occluded": np.zeros(n, np.uint8), "nodes": np.zeros(n, np.uint32), "tris": np.zeros(n, np.uint32)}
+    lib().oracle_query_rays(scene.h, n, r.ctypes.data, int(bool(brute_force)), 1, None, None, None, None,
+                            out["occluded"].ctypes.data, out["nodes"].ctypes.data, out["tris"].ctypes.data)
     return out
 
 

@@ -143,14 +143,20 @@ static uint32_t countRay(const crt_bvh_tri* tris, uint32_t n_tris, f3 o, f3 d, f
     return c;
 }
 
-/* crt_count_hits: ray records of 8 floats */
+/* crt_count_hits: ray records of 8 floats, each prescaled as the query kernels do (traversal.hip.h queryRay): the ray
+ * (o, tmin 2^e, d 2^-e, tmax 2^e), e the exponent of the largest |d_i| (frexp's minus one; -1 for zero or non-finite) */
 void ref_count_hits(const crt_bvh_tri* tris, uint32_t n_tris, uint32_t n, const float* rays, uint32_t* count)
 {
     long i;
 #pragma omp parallel for schedule(dynamic, 64)
     for (i = 0; i < (long)n; i++) {
         const float* r = rays + 8 * i;
-        count[i] = countRay(tris, n_tris, mk(r[0], r[1], r[2]), mk(r[4], r[5], r[6]), r[3], r[7]);
+        const float m = fmaxf(fmaxf(fabsf(r[4]), fabsf(r[5])), fabsf(r[6]));
+        int ex = 0;
+        if (m <= 3.40282347e38f) frexpf(m, &ex);
+        const int e = ex - 1;
+        count[i] = countRay(tris, n_tris, mk(r[0], r[1], r[2]), mk(ldexpf(r[4], -e), ldexpf(r[5], -e), ldexpf(r[6], -e)),
+                            ldexpf(r[3], e), ldexpf(r[7], e));
     }
 }
 
