@@ -985,6 +985,7 @@ int crt_set_textures(crt_ctx* c, const crt_texture* textures, uint32_t n)
             if (!t.pixels || t.width == 0 || t.height == 0 || t.channels < 3)
                 return fail(c, CRT_EINVAL, "texture %u: bitmap needs pixels, width, height and >= 3 channels", i);
             const size_t bytes = static_cast<size_t>(t.width) * t.height * t.channels;
+            if (pool.size() + bytes > 0xFFFFFFFFull) return fail(c, CRT_EINVAL, "texture %u: more than 4 GiB of texels in one table", i);
             r.texel_offset = static_cast<uint32_t>(pool.size());
             r.width = t.width; r.height = t.height; r.channels = t.channels;
             pool.insert(pool.end(), t.pixels, t.pixels + bytes);

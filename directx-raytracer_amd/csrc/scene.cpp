@@ -4,6 +4,7 @@
 #include "image_decode.h"
 
 #include <iterator>
+#include <limits>
 
 #include <algorithm>
 #include <cmath>
@@ -187,15 +188,25 @@ uint32_t TextureDesc::typeCode() const
     return 0u;
 }
 
+// float -> int of the texture functions (include/crt_hip.h, "texture conversions"): truncation towards zero, saturated to
+// [INT_MIN, INT_MAX], NaN -> 0 -- what the device's conversion does; a plain cast is undefined outside the int range
+static int texInt(float x)
+{
+    if (x != x) return 0;
+    if (x >= 2147483648.0f) return std::numeric_limits<int>::max();
+    if (x <= -2147483648.0f) return std::numeric_limits<int>::min();
+    return static_cast<int>(x);
+}
+
 Vector TextureDesc::getColor(float u, float v) const
 {
     switch (typeCode()) {
     case 1u:
         return (u < scalar || v < scalar || (1 - u - v) < scalar) ? colorA : colorB;
     case 2u: {
-        const int n = static_cast<int>(1.f / scalar);
-        const int cu = static_cast<int>(std::floor(u * n)), cv = static_cast<int>(std::floor(v * n));
-        return ((cu + cv) % 2 == 0) ? colorA : colorB;
+        const int n = texInt(1.f / scalar);
+        const int cu = texInt(std::floor(u * n)), cv = texInt(std::floor(v * n));
+        return (((cu ^ cv) & 1) == 0) ? colorA : colorB; // parity of cu + cv without the signed overflow
     }
     case 3u: {
         if (pixels.empty() || channels < 3) return Vector(0.f, 0.f, 0.f);

@@ -83,10 +83,12 @@ __device__ __forceinline__ F3 textureColor(const TextureRec& t, const unsigned c
     const F3 A = f3(t.a[0], t.a[1], t.a[2]), B = f3(t.b[0], t.b[1], t.b[2]);
     if (t.type == 1u) return (u < t.scalar || v < t.scalar || (1.0f - u - v) < t.scalar) ? A : B; // edges
     if (t.type == 2u) { // checker
+        // float -> int as include/crt_hip.h states it ("texture conversions"): v_cvt_i32_f32 truncates, saturates and turns NaN
+        // into 0, which is the rule; the oracle and the host scene layer spell it out (tex_int / texInt)
         const int width = static_cast<int>(1.0f / t.scalar);
         const int u2 = static_cast<int>(floorf(u * static_cast<float>(width)));
         const int v2 = static_cast<int>(floorf(v * static_cast<float>(width)));
-        return ((u2 + v2) % 2 == 0) ? A : B;
+        return (((static_cast<uint32_t>(u2) + static_cast<uint32_t>(v2)) & 1u) == 0u) ? A : B; // parity of the wrapped sum (the CPU sides: (u2 ^ v2) & 1)
     }
     if (t.type == 3u) { // bitmap: nearest texel, v flipped
         if (t.channels < 3u || t.width == 0u) return f3(0.0f, 0.0f, 0.0f);

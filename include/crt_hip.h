@@ -69,7 +69,18 @@ typedef struct crt_material { float albedo[3]; uint32_t type; uint32_t smooth; f
     type = CRTMaterialType; texture = index into crt_set_textures' array when CRTMaterial::isTexture(), else -1 */
 /* R/CRTTexture*.h: type 0 albedo (color_a), 1 edges (color_a = edge colour, color_b = inner colour, scalar = edge width; evaluated
  * on the hit's barycentrics), 2 checker (color_a / color_b, scalar = square size), 3 bitmap (pixels: height x width x channels
- * bytes, channels >= 3, nearest texel, v flipped); 2 and 3 are evaluated on the mesh uvs interpolated at the hit */
+ * bytes, channels >= 3, nearest texel, v flipped); 2 and 3 are evaluated on the mesh uvs interpolated at the hit,
+ * uv0 * (1 - u - v) + uv1 * u + uv2 * v, and at (0, 0) when no mesh of the scene carries uvs (a mesh without uvs among meshes
+ * with them has zero uvs).  A material's texture replaces its albedo whatever its type, if 0 <= texture < n_textures;
+ * any other index leaves the material's own albedo.
+ * Texture conversions: wherever a texture function turns a float into an int (the checker's width = 1 / square_size and its
+ * cell numbers floor(u * width), floor(v * width); the bitmap's row (1 - v) * (height - 1) and column u * (width - 1) after u
+ * and v are clamped to [0, 1], NaN clamping to 0) the value is truncated towards zero, saturated to [INT_MIN, INT_MAX], and
+ * NaN becomes 0.  The checker shows color_a where the wrapped 32-bit sum of its two cell numbers is even ((cu ^ cv) & 1 == 0).
+ * So uvs and square sizes of any value, infinities and NaN included, give the same colour on the device, in the host scene
+ * layer (crt_scene_texture_color) and in the CPU oracle: square_size 0 (a scene file without the key) is width INT_MAX,
+ * square_size > 1 is width 0 (color_a everywhere), a negative one mirrors the cells.  The reference leaves these cases
+ * undefined (a plain C++ cast); inside the int range the rule is the reference's. */
 enum { CRT_TEX_ALBEDO = 0, CRT_TEX_EDGES = 1, CRT_TEX_CHECKER = 2, CRT_TEX_BITMAP = 3 };
 typedef struct crt_texture { uint32_t type; float color_a[3]; float color_b[3]; float scalar; const uint8_t* pixels; uint32_t width, height, channels; } crt_texture;
 

@@ -21,6 +21,7 @@
 #include "crt_oracle.h"
 
 #include <float.h>
+#include <limits.h>
 #include <immintrin.h>
 #include <math.h>
 #include <stdlib.h>
@@ -691,6 +692,16 @@ const oracle_uv* oracle_scene_uvs(const oracle_scene* s) { return s->uvs; }
 
 /* R/CRTTexture*.cpp getColor, operation for operation.  Bitmaps need >= 3 channels here (the reference reads the green
  * byte of 1-channel images from the next pixel: not reproduced). */
+/* float -> int of the texture functions (include/crt_hip.h, "texture conversions"): truncation towards zero, saturated to
+ * [INT_MIN, INT_MAX], NaN -> 0.  A plain C cast is undefined outside the int range (x86 gives INT_MIN for all of it). */
+static inline int tex_int(float x)
+{
+    if (x != x) return 0;
+    if (x >= 2147483648.0f) return INT_MAX;
+    if (x <= -2147483648.0f) return INT_MIN;
+    return (int)x;
+}
+
 static v3 texture_color(const oracle_texture* t, float u, float v)
 {
     const v3 A = v3_make(t->color_a[0], t->color_a[1], t->color_a[2]);
@@ -698,10 +709,10 @@ static v3 texture_color(const oracle_texture* t, float u, float v)
     if (t->type == 1u) /* R/CRTTextureEdges.cpp:9-15 */
         return (u < t->scalar || v < t->scalar || (1.0f - u - v) < t->scalar) ? A : Bc;
     if (t->type == 2u) { /* R/CRTTextureChecker.cpp:9-20 */
-        int width = (int)(1.0f / t->scalar);
-        int u2 = (int)floorf(u * (float)width);
-        int v2 = (int)floorf(v * (float)width);
-        return ((u2 + v2) % 2 == 0) ? A : Bc;
+        int width = tex_int(1.0f / t->scalar);
+        int u2 = tex_int(floorf(u * (float)width));
+        int v2 = tex_int(floorf(v * (float)width));
+        return (((u2 ^ v2) & 1) == 0) ? A : Bc; /* parity of u2 + v2 without the signed overflow */
     }
     if (t->type == 3u) { /* R/CRTTextureBitmap.cpp:12-36 */
         if (!t->pixels || t->channels < 3u) return v3_make(0.0f, 0.0f, 0.0f);

@@ -10,6 +10,10 @@ a tool linked against the reference's CRT* sources compiled in place (oracle/Mak
                                          (R/CRTCamera.cpp:9-130), CRTVector*CRTMatrix (R/CRTMatrix.cpp:26-38)
   tests/golden/texture_known_answers.json  getColor(u,v) of the reference's four texture classes (R/CRTTexture*.cpp) on a grid,
                                          the bitmap one reading tests/golden/tex7x5.ppm (written here, seeded)
+  tests/golden/texture_known_answers_wide.json  more of the same inside the range where the reference's casts are defined: checkers of
+                                         five square sizes and edges of three widths over [-2.5, 2.5]^2 with the cell boundaries
+                                         and their float neighbours, bitmaps tex_wide_1x1 / 1x9 / 9x1.ppm (written here) over
+                                         [-0.5, 1.5]^2; `make_golden.py --textures-wide` regenerates this file alone
   tests/golden/dragon.crtscene           the same scene DATA re-serialised from the reference's parsed
                                          values (float32 printed with 9 significant digits round-trips
                                          exactly) so the GPU box, which has no /root/reference, can load it.
@@ -28,9 +32,57 @@ def fmt(x):
     return repr(float(x)) if float(x) != int(x) else str(int(x))
 
 
+WIDE_BITMAPS = {"1x1": (1, 1), "1x9": (1, 9), "9x1": (9, 1)}  # name -> (width, height)
+
+
+def texture_wide(gold):
+    """tests/golden/texture_known_answers_wide.json and its three PPM fixtures.  Stored compactly: checker and edges rows are
+    [u, v, k], k = 0 for color_A (edges: the edge colour) and 1 for color_B, after checking that the reference returned exactly
+    that colour; bitmap rows are [u, v, R, G, B] with the colour = fl(R / 255.0f) etc. exactly (checked here)."""
+    import numpy as np
+    f32 = np.float32
+    paths = []
+    for name, (w, h) in WIDE_BITMAPS.items():
+        k = np.arange(w * h).reshape(h, w)
+        img = np.stack([(k * 29 + 7) % 256, (k * 53 + 101) % 256, 255 - k * 17], axis=-1).astype(np.uint8)
+        paths.append(os.path.join(gold, "tex_wide_%s.ppm" % name))
+        with open(paths[-1], "wb") as f:
+            f.write(b"P6\n%d %d\n255\n" % (w, h) + img.tobytes())
+    subprocess.check_call(["make", "-C", HERE, "_ref/ref_dump"])
+    tmp = os.path.join(HERE, "_ref", "textures_wide_ref.json")
+    subprocess.check_call([os.path.join(HERE, "_ref", "ref_dump"), "--textures-wide"] + paths + [tmp])
+    ref = json.load(open(tmp))
+    A, B = [f32(c) for c in ref["color_A"]], [f32(c) for c in ref["color_B"]]
+    out = {"color_A": ref["color_A"], "color_B": ref["color_B"], "checker": {}, "edges": {}, "bitmap": {}}
+    for kind in ("checker", "edges"):
+        for key, rows in ref[kind].items():
+            packed = []
+            for u, v, r, g, b in rows:
+                c = [f32(r), f32(g), f32(b)]
+                assert c == A or c == B, (kind, key, u, v, c)
+                if kind == "checker":
+                    assert abs(u * int(1.0 / float(key))) < 2.0 ** 31 and abs(v * int(1.0 / float(key))) < 2.0 ** 31
+                packed.append([u, v, 0 if c == A else 1])
+            out[kind][key] = packed
+    for key, rows in ref["bitmap"].items():
+        packed = []
+        for u, v, r, g, b in rows:
+            rgb = [int(round(c * 255.0)) for c in (r, g, b)]
+            assert all(f32(c) == f32(f32(q) / f32(255.0)) for c, q in zip((r, g, b), rgb)), (key, u, v)
+            packed.append([u, v] + rgb)
+        out["bitmap"][key] = packed
+    path = os.path.join(gold, "texture_known_answers_wide.json")
+    with open(path, "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+    assert os.path.getsize(path) < 100 * 1024, os.path.getsize(path)
+
+
 def main():
     if not os.path.exists(REF_SCENE):
         print("reference tree absent; nothing to do")
+        return 0
+    if "--textures-wide" in sys.argv[1:]:
+        texture_wide(os.path.join(ROOT, "tests", "golden"))
         return 0
     subprocess.check_call(["make", "-C", HERE, "_ref/ref_dump"])
     tmp = os.path.join(HERE, "_ref", "dragon_ref.json")
@@ -70,6 +122,7 @@ def main():
     subprocess.check_call([os.path.join(HERE, "_ref", "ref_dump"), "--textures", os.path.join(gold, "tex7x5.ppm"), ttmp])
     with open(os.path.join(gold, "texture_known_answers.json"), "w") as f:
         json.dump(json.load(open(ttmp)), f, separators=(",", ":"))
+    texture_wide(gold)
     # 4) bitmap textures in the other formats the reference's stb_image reads and this repo decodes itself (csrc/image_decode.cpp):
     #    seeded images written here (PNG: every colour type, 1 / 4 / 8 / 16 bits, all five filters, stored / fixed / dynamic deflate
     #    blocks, Adam7; BMP: 24 / 32 bit, palette, top-down; TGA: raw / run-length, colour / grey; JPEG: baseline / progressive,

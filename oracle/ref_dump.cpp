@@ -16,11 +16,13 @@
 #include "CRTTextureBitmap.h"
 #include "CRTTextureChecker.h"
 #include "CRTTextureEdges.h"
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
 #include <sstream>
 #include <string>
+#include <vector>
 
 static void putv(FILE* f, const CRTVector& v)
 {
@@ -93,6 +95,71 @@ int main(int argc, char** argv)
             fprintf(f, "]%s\n", t < 3 ? "," : "");
         }
         fprintf(f, "}\n");
+        fclose(f);
+        return 0;
+    }
+    if (argc >= 6 && std::string(argv[1]) == "--textures-wide") {
+        // more known answers of the reference's texture classes, inside the range where its float -> int casts are defined:
+        // checkers of several square sizes and edges of several widths over [-2.5, 2.5]^2, on a coarse grid plus the cell
+        // boundaries k * square_size and k / width with their float neighbours; bitmaps of 1x1, 1x9 and 9x1 texels over
+        // [-0.5, 1.5]^2 with the texel boundaries k / 8.  argv[2..4] = the three bitmaps, argv[5] = output json
+        FILE* f = fopen(argv[5], "w");
+        if (!f) return 3;
+        const CRTVector A(0.75f, 0.5f, 0.25f), B(0.125f, 0.375f, 0.625f);
+        const int ks[] = { -7, -3, -1, 0, 1, 2, 5 };
+        const float other[] = { -2.2f, -0.45f, 0.05f, 0.8f };
+        auto axis = [&](float lo, float hi, int n, float step, int cells) {
+            std::vector<float> X;
+            for (int i = 0; i <= n; i++) X.push_back(lo + (hi - lo) * (float)i / (float)n + (float)(i % 3) * 0.003f);
+            for (int k : ks)
+                for (int pass = 0; pass < 2; pass++) {
+                    if (pass == 1 && cells <= 0) continue;
+                    const float b = pass == 0 ? (float)k * step : (float)k / (float)cells;
+                    const float three[3] = { nextafterf(b, -INFINITY), b, nextafterf(b, INFINITY) };
+                    for (float x : three)
+                        if (x >= lo && x <= hi) X.push_back(x);
+                }
+            return X;
+        };
+        auto put = [&](const CRTTexture& t, const std::vector<float>& X, const float* fixed, int n_fixed, bool& first) {
+            for (float x : X)
+                for (int j = 0; j < n_fixed + 1; j++) {
+                    // the first n_fixed pairs vary u, the last one varies v
+                    const float u = j < n_fixed ? x : fixed[0], v = j < n_fixed ? fixed[j] : x;
+                    const CRTVector c = t.getColor(u, v);
+                    fprintf(f, "%s[%.9g,%.9g,%.9g,%.9g,%.9g]", first ? "" : ",", u, v, c.getX(), c.getY(), c.getZ());
+                    first = false;
+                }
+        };
+        fprintf(f, "{\n \"color_A\":[0.75,0.5,0.25],\"color_B\":[0.125,0.375,0.625],\n \"checker\":{");
+        const float squares[] = { 0.3f, 1.0f / 3.0f, 0.07f, 0.6f, 2.0f };
+        for (int i = 0; i < 5; i++) {
+            CRTTextureChecker chk(A, B, squares[i], "c");
+            fprintf(f, "%s\n  \"%.9g\":[", i ? "," : "", squares[i]);
+            bool first = true;
+            put(chk, axis(-2.5f, 2.5f, 11, squares[i], (int)(1.0f / squares[i])), other, 4, first);
+            fprintf(f, "]");
+        }
+        fprintf(f, "},\n \"edges\":{");
+        const float widths[] = { 0.0f, 0.04f, 0.5f };
+        for (int i = 0; i < 3; i++) {
+            CRTTextureEdges edg(A, B, widths[i], "e");
+            fprintf(f, "%s\n  \"%.9g\":[", i ? "," : "", widths[i]);
+            bool first = true;
+            put(edg, axis(-2.5f, 2.5f, 11, widths[i], 0), other, 4, first);
+            fprintf(f, "]");
+        }
+        fprintf(f, "},\n \"bitmap\":{");
+        const char* sizes[] = { "1x1", "1x9", "9x1" };
+        const float inside[] = { 0.3f, -0.5f, 1.5f };
+        for (int i = 0; i < 3; i++) {
+            CRTTextureBitmap bmp(argv[2 + i], "b");
+            fprintf(f, "%s\n  \"%s\":[", i ? "," : "", sizes[i]);
+            bool first = true;
+            put(bmp, axis(-0.5f, 1.5f, 15, 0.125f, 8), inside, 3, first);
+            fprintf(f, "]");
+        }
+        fprintf(f, "}\n}\n");
         fclose(f);
         return 0;
     }

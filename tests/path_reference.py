@@ -6,7 +6,25 @@ random numbers as the kernels, a 1-spp pixel is one path, traced here without st
 Near a discontinuity (a ray grazing a triangle edge, two surfaces at nearly the same t, a shadow ray ending on an occluder,
 a light at cos ~ 0, Snell's k ~ 0, a normal's z ~ 0 or a grazing hit) the float32 and float64 paths may legitimately take
 different branches.  trace_paths records the margin of every such decision and flags the path when one falls below the
-thresholds in MARGINS; the tests skip flagged paths and bound their share."""
+thresholds in MARGINS; the tests skip flagged paths and bound their share.
+
+Textures.  The albedo of a hit is the material's, or its texture's when 0 <= texture < number of textures (any material type;
+glass has no albedo term).  Kinds: albedo (colour a); edges (colour a where u, v or 1 - u - v of the hit's barycentrics is below
+the width, else b); checker (width = trunc(1 / square_size), cells floor(c * width), a when the cell numbers' sum is even);
+bitmap (c clamped to [0, 1], row trunc((1 - v) * (h - 1)), column trunc(u * (w - 1)), that texel / 255).  Checker and bitmap
+take c = uv0 * w + uv1 * u + uv2 * v from the mesh's per-vertex uvs; a mesh without uvs has c = (0, 0).
+Every lookup is a decision.  The float32 coordinate differs from c by the barycentrics' error, which MARGINS["bary"] bounds,
+times the uv span of the triangle, |uv1 - uv0| + |uv2 - uv0|, plus three roundings (one product, two fmas) of at most
+2^-24 max|uv| each: eps = 2e-5 * span + 3 * 2^-24 * max|uv| per axis.  A checker lookup is flagged when c * width lies within
+eps * |width| + 2^-24 |c * width| (the product's rounding) of an integer; a bitmap lookup when c is within eps of a clamp it has
+not clearly passed, or the texel coordinate within (eps + 2^-24) * (w - 1) + 2^-24 * coordinate of an integer (the extra 2^-24:
+the rounding of 1 - v); a coordinate clamped on both sides gives an exact integer and w - 1 = 0 or h - 1 = 0 leaves nothing to
+decide.  An edges lookup is flagged unless some barycentric is below width - MARGINS["bary"] or all are above width + it.
+Confirmed in numpy float32 (Moeller-Trumbore, then the interpolation in the order above, on the 6 863 textured camera-ray hits
+of the two textured scenes at pixel centres and with the jitter of the three seeds): the largest |float32 - float64| coordinate
+difference is 7.8e-7, at most 12.3 % of eps; the largest barycentric difference 2.7e-6 against the margin's 2e-5.
+Share of paths the reference alone flags, over max_bounces 0 / 1 / 2 / 5 and the three seeds: at most 0.49 % of a frame in
+textured_room and 0.10 % in textured_glass (cap: 3 %); at pixel centres at most 0.10 %."""
 import math
 from collections import Counter
 
@@ -70,11 +88,35 @@ def camera_dirs(rot, px, py, jx, jy, w, h):
     return _norm(dc @ R.T)
 
 
+_EPS32 = 2.0 ** -24
+_KINDS = ("albedo", "edges", "checker", "bitmap")
+
+
+def _parse_texture(t):
+    """a texture dict of the tests -> float64: kind, colours a / b, scalar (edge width / square size), pixels (H, W, C)"""
+    assert t["type"] in _KINDS
+    T = {"kind": t["type"], "a": np.float32(t.get("color_a", (0, 0, 0))).astype(np.float64),
+         "b": np.float32(t.get("color_b", (0, 0, 0))).astype(np.float64), "scalar": float(np.float32(t.get("scalar", 0.0)))}
+    if T["kind"] == "checker":
+        q = 1.0 / T["scalar"]
+        T["width"] = int(math.trunc(q))
+        # the number of squares is a decision too; the scenes keep 1 / square_size exact or well away from an integer
+        assert q == round(q) == float(np.float32(1.0) / np.float32(T["scalar"])) or abs(q - round(q)) > 1e-3
+    if T["kind"] == "bitmap":
+        T["pixels"] = np.asarray(t["pixels"], np.uint8)
+        assert T["pixels"].ndim == 3 and T["pixels"].shape[2] >= 3
+    return T
+
+
+def _from_integer(x):
+    return np.abs(x - np.rint(x))
+
+
 class Scene:
     """the scene dict of the tests (meshes / lights / materials), flattened to per-triangle float64 arrays"""
 
     def __init__(self, sc):
-        v0, e1, e2, inst, prim, mat, nrm = [], [], [], [], [], [], []
+        v0, e1, e2, inst, prim, mat, nrm, uv = [], [], [], [], [], [], [], []
         for mi, m in enumerate(sc["meshes"]):
             v = np.asarray(m["vertices"], np.float32).astype(np.float64).reshape(-1, 3)
             t = np.asarray(m["triangles"], np.int64).reshape(-1, 3)
@@ -87,8 +129,13 @@ class Scene:
             n = m.get("normals")
             n = np.zeros_like(v) if n is None else np.asarray(n, np.float32).astype(np.float64).reshape(-1, 3)
             nrm.append(np.stack([n[t[:, 0]], n[t[:, 1]], n[t[:, 2]]], axis=1))
+            c = m.get("uvs")  # (u, v, unused) per vertex; a mesh without them has the coordinate (0, 0) everywhere
+            c = np.zeros((len(v), 2)) if c is None else np.asarray(c, np.float32).astype(np.float64).reshape(-1, 3)[:, :2]
+            uv.append(np.stack([c[t[:, 0]], c[t[:, 1]], c[t[:, 2]]], axis=1))
         self.v0, self.e1, self.e2 = np.concatenate(v0), np.concatenate(e1), np.concatenate(e2)
         self.inst, self.prim, self.nrm = np.concatenate(inst), np.concatenate(prim), np.concatenate(nrm)
+        self.uv = np.concatenate(uv)
+        self.textures = [_parse_texture(t) for t in (sc.get("textures") or ())]
         mats = list(sc["materials"])
         matidx = np.concatenate(mat)
         known = matidx < len(mats)  # a triangle without a material is white DIFFUSE
@@ -96,6 +143,8 @@ class Scene:
         self.mtype = np.full(len(matidx), DIFFUSE)
         self.smooth = np.zeros(len(matidx), bool)
         self.ior = np.ones(len(matidx))
+        self.tex = np.full(len(matidx), -1)           # texture of the triangle's material, -1: its own albedo
+        self.tex_past = np.zeros(len(matidx), bool)   # a texture index at or past the end of the table: ignored
         for k in range(len(matidx)):
             if known[k]:
                 M = mats[matidx[k]]
@@ -103,6 +152,10 @@ class Scene:
                 self.mtype[k] = int(M.get("type", 1))
                 self.smooth[k] = bool(M.get("smooth_shading", False))
                 self.ior[k] = float(np.float32(M.get("ior", 1.0)))
+                ti = int(M.get("texture", -1))
+                if 0 <= ti < len(self.textures):
+                    self.tex[k] = ti
+                self.tex_past[k] = ti >= len(self.textures)
         self.lights = [(np.float32(p).astype(np.float64), float(np.float32(i))) for p, i in sc["lights"]]
 
     def intersect(self, o, d):
@@ -168,6 +221,68 @@ class Scene:
         entering = ~(nd > 0.0)
         N = np.where(entering[:, None], N, -N)
         return P, N, entering, np.abs(nd) >= MARGINS["cos"]
+
+    def albedo_at(self, tri, u, v, ev, all_diffuse=False, after_bounce=False):
+        """albedo of hits (tri, u, v): the material's, or its texture's when the material names one inside the table.  The edges
+        texture is a function of the hit's barycentrics, every other kind of uv0 * w + uv1 * u + uv2 * v.  Returns (rgb, robust):
+        robust is False where a float32 evaluation could pick another cell / texel / side (module docstring, "Textures").
+        Glass never uses its albedo, so its lookups decide nothing (unless all_diffuse: mode 100 shades every material alike)."""
+        rgb = self.albedo[tri].copy()
+        robust = np.ones(len(tri), bool)
+        ti, mt = self.tex[tri], self.mtype[tri]
+        w = 1.0 - u - v
+        ev["tex_index_past_table"] += int(np.sum(self.tex_past[tri]))
+        ev["tex_on_glass_or_mirror"] += int(np.sum((ti >= 0) & ((mt == REFLECTIVE) | (mt == REFRACTIVE))))
+        plain = (mt != REFLECTIVE) & (mt != REFRACTIVE) & (mt != CONSTANT)
+        if after_bounce:
+            ev["tex_after_bounce"] += int(np.sum((ti >= 0) & plain))
+        for k in np.unique(ti[ti >= 0]):
+            sel = np.nonzero(ti == k)[0]
+            T = self.textures[k]
+            ev["tex_" + T["kind"]] += len(sel)
+            ok = np.ones(len(sel), bool)
+            if T["kind"] == "albedo":
+                col = np.repeat(T["a"][None], len(sel), axis=0)
+            elif T["kind"] == "edges":
+                x = np.stack([u[sel], v[sel], w[sel]], axis=-1)
+                edge = np.any(x < T["scalar"], axis=-1)
+                m = MARGINS["bary"]
+                ok = np.any(x < T["scalar"] - m, axis=-1) | np.all(x >= T["scalar"] + m, axis=-1)
+                ev["edges_edge"] += int(edge.sum())
+                ev["edges_inner"] += int(np.sum(~edge))
+                col = np.where(edge[:, None], T["a"][None], T["b"][None])
+            else:
+                U = self.uv[tri[sel]]
+                c = U[:, 0] * w[sel, None] + U[:, 1] * u[sel, None] + U[:, 2] * v[sel, None]
+                # float32 coordinate - float64 coordinate: the barycentrics' error times the triangle's uv span + three roundings
+                eps = (MARGINS["bary"] * (np.abs(U[:, 1] - U[:, 0]) + np.abs(U[:, 2] - U[:, 0]))
+                       + 3.0 * _EPS32 * np.max(np.abs(U), axis=1))
+                if T["kind"] == "checker":
+                    x = c * T["width"]
+                    ok = np.all(_from_integer(x) >= eps * abs(T["width"]) + _EPS32 * np.abs(x), axis=-1)
+                    even = np.sum(np.floor(x), axis=-1) % 2.0 == 0.0
+                    ev["checker_negative"] += int(np.sum(np.any(c < 0.0, axis=-1)))
+                    ev["checker_above_1"] += int(np.sum(np.any(c > 1.0, axis=-1)))
+                    col = np.where(even[:, None], T["a"][None], T["b"][None])
+                else:
+                    px = T["pixels"]
+                    scale = np.array([px.shape[1] - 1.0, px.shape[0] - 1.0])
+                    for ax, name in ((0, "u"), (1, "v")):
+                        ev["bitmap_%s_low" % name] += int(np.sum(c[:, ax] < 0.0))
+                        ev["bitmap_%s_high" % name] += int(np.sum(c[:, ax] > 1.0))
+                    cc = np.clip(c, 0.0, 1.0)
+                    x = np.stack([cc[:, 0], 1.0 - cc[:, 1]], axis=-1) * scale
+                    clamped = (c <= -eps) | (c >= 1.0 + eps)  # 0 or 1 exactly on both sides: the texel index is an exact integer
+                    inside = (c >= eps) & (c <= 1.0 - eps)
+                    sure = inside & (_from_integer(x) >= (eps + _EPS32) * scale + _EPS32 * x)
+                    ok = np.all(clamped | sure | (scale == 0.0), axis=-1)
+                    at = np.trunc(x).astype(np.int64)
+                    col = px[at[:, 1], at[:, 0], :3].astype(np.float64) / 255.0
+            rgb[sel] = col
+            robust[sel] = ok
+        if not all_diffuse:
+            robust |= mt == REFRACTIVE
+        return rgb, robust
 
     def direct(self, Po, N, albedo, ev, view=None, ks=0.0, exponent=32):
         """sum over the lights of albedo * I / (4 pi r^2) * cos where the shadow ray (Po, L/r, 0, r) is clear; cos <= 0
@@ -238,7 +353,8 @@ def trace_paths(S, cam_pos, cam_rot, w, h, miss, max_bounces, seed, sample=0):
         P, N, entering, rb = S.surface(o[alive], d[alive], tri, t, u, v)
         robust[alive] &= rb
         mt = S.mtype[tri]
-        alb = S.albedo[tri]
+        alb, rb = S.albedo_at(tri, u, v, ev, after_bounce=bounce > 0)
+        robust[alive] &= rb
         nxt_o, nxt_d = np.zeros((len(alive), 3)), np.zeros((len(alive), 3))
         goes = np.zeros(len(alive), bool)
         cut = bounce == max_bounces
@@ -316,8 +432,9 @@ def trace_paths(S, cam_pos, cam_rot, w, h, miss, max_bounces, seed, sample=0):
             "segments": segs.reshape(h, w), "robust": robust.reshape(h, w), "ev": ev}
 
 
-def shade_centres(S, cam_pos, cam_rot, w, h, mode, miss, ks=0.0, exponent=32):
-    """modes 3 (barycentric), 5 (distance) and 100 (Lambert + Phong) at pixel centres, float64: (rgb, robust, inst, prim, t)"""
+def shade_centres(S, cam_pos, cam_rot, w, h, mode, miss, ks=0.0, exponent=32, ev=None):
+    """modes 3 (barycentric), 5 (distance) and 100 (Lambert + Phong) at pixel centres, float64: (rgb, robust, inst, prim, t);
+    ev: a Counter that receives the texture events of mode 100"""
     n = w * h
     pix = np.arange(n)
     o = np.repeat(np.float32(cam_pos).astype(np.float64)[None], n, axis=0)
@@ -331,7 +448,9 @@ def shade_centres(S, cam_pos, cam_rot, w, h, mode, miss, ks=0.0, exponent=32):
     else:
         P, N, _, rb = S.surface(o[hit], d[hit], tri[hit], t[hit], u[hit], v[hit])
         robust[hit] &= rb
-        c, rb = S.direct(P + N * BIAS, N, S.albedo[tri[hit]], Counter(), view=-d[hit], ks=ks, exponent=exponent)
+        alb, rb = S.albedo_at(tri[hit], u[hit], v[hit], Counter() if ev is None else ev, all_diffuse=True)
+        robust[hit] &= rb
+        c, rb = S.direct(P + N * BIAS, N, alb, Counter(), view=-d[hit], ks=ks, exponent=exponent)
         robust[hit] &= rb
         rgb[hit] = c
     inst = np.where(hit, S.inst[tri], MISS).astype(np.uint32)
@@ -473,5 +592,105 @@ def scene_sphere(scenes):
     return _sc(meshes, _GLASS_LIGHTS, mats, (0.0, 0.2, 0.4), scenes.camera_matrix(0.0, -4.0))
 
 
-SCENES = {"room": scene_room, "mirrors": scene_mirrors, "slab": scene_slab, "prism": scene_prism, "sphere": scene_sphere}
+
+# ---- textured scenes: every texture kind, uvs below 0 and above 1, several bitmaps in one table
+
+def _planar(m, pu, pv):
+    """per-vertex uvs (u, v, unused) as affine functions of the position: pu, pv = (cx, cy, cz, offset)"""
+    v = m["vertices"].astype(np.float64)
+    uv = np.stack([v @ np.array(pu[:3]) + pu[3], v @ np.array(pv[:3]) + pv[3], np.zeros(len(v))], axis=1)
+    m["uvs"] = uv.astype(np.float32)
+    return m
+
+
+def _bitmap(w, h, channels=3):
+    """a w x h image without two equal neighbours in any channel; the fourth channel, where there is one, holds values that no
+    colour channel takes at that texel"""
+    yy, xx = np.mgrid[0:h, 0:w]
+    ch = [(xx * 37 + yy * 11 + 20) % 256, (xx * 13 + yy * 53 + 90) % 256, (xx * 29 + yy * 31 + 160) % 256, (xx * 7 + yy * 3 + 5) % 256]
+    return np.stack(ch[:channels], axis=-1).astype(np.uint8)
+
+
+_CHK_A, _CHK_B = (0.85, 0.8, 0.7), (0.25, 0.3, 0.55)
+_TEXTURES = [
+    {"type": "checker", "color_a": _CHK_A, "color_b": _CHK_B, "scalar": 0.125},             # 0: 8 squares
+    {"type": "checker", "color_a": (0.7, 0.85, 0.6), "color_b": (0.35, 0.2, 0.3), "scalar": 0.3},    # 1: 3
+    {"type": "checker", "color_a": (0.6, 0.7, 0.9), "color_b": (0.5, 0.25, 0.2), "scalar": 0.07},    # 2: 14
+    {"type": "checker", "color_a": (0.9, 0.6, 0.5), "color_b": (0.2, 0.5, 0.4), "scalar": 0.6},      # 3: 1
+    {"type": "checker", "color_a": (0.55, 0.75, 0.65), "color_b": (0.9, 0.1, 0.1), "scalar": 2.0},   # 4: 0, all colour a
+    {"type": "edges", "color_a": (0.95, 0.85, 0.2), "color_b": (0.6, 0.15, 0.1), "scalar": 0.04},    # 5
+    {"type": "edges", "color_a": (0.1, 0.9, 0.9), "color_b": (0.5, 0.45, 0.8), "scalar": 0.0},       # 6: all inner
+    {"type": "edges", "color_a": (0.8, 0.4, 0.7), "color_b": (0.1, 0.1, 0.9), "scalar": 0.5},        # 7: all edge
+    {"type": "bitmap", "pixels": _bitmap(17, 13)},                                                  # 8
+    {"type": "bitmap", "pixels": _bitmap(5, 3, 4)},                                                 # 9: RGBA
+    {"type": "bitmap", "pixels": _bitmap(1, 9)},                                                    # 10: w - 1 = 0
+    {"type": "bitmap", "pixels": _bitmap(9, 1)},                                                    # 11: h - 1 = 0
+    {"type": "bitmap", "pixels": _bitmap(1, 1)[:, :, ::-1]},                                        # 12
+    {"type": "albedo", "color_a": (0.3, 0.8, 0.45)},                                                # 13
+]
+
+
+def scene_textured_room(scenes):
+    """scene_room's closed room with floor, ceiling and side walls cut into three strips along z, one texture per surface.
+    Material i < 14 has texture i (and an albedo that no texture yields).  Floor: checkers on uvs from -0.8 to 1.4 and -1.7 to
+    1.1.  Ceiling: bitmaps 17x13 and 9x1 with u from -0.3 to 1.3, and the albedo texture.  Left wall: the three edges textures,
+    on a mesh whose uvs are far from any barycentric.  Right wall: RGBA, 1x9 and 1x1 bitmaps on rotated uvs (u along y, v along
+    z, both leaving [0, 1]).  Back wall: the 14-square checker with u decreasing as x grows.  Behind the camera: the 1-square
+    checker.  A panel without uvs whose bitmap is therefore read at (0, 0), a box with planar uvs, and a second panel whose
+    material names texture 14 of 14: its own albedo."""
+    n = len(_TEXTURES)
+    own = [(0.31 + 0.04 * (i % 5), 0.62 - 0.05 * (i % 4), 0.43 + 0.06 * (i % 3)) for i in range(n)]
+    mats = [{"albedo": own[i], "type": DIFFUSE, "texture": i} for i in range(n)]
+    mats.append({"albedo": (0.75, 0.35, 0.55), "type": DIFFUSE, "texture": n})  # 14: index past the table
+    x0, x1, y0, y1 = -2.0, 2.0, -1.5, 1.5
+    zs = (2.0, -1.0, -3.5, -6.0)
+    meshes = []
+    for k, mat in enumerate((0, 1, 4)):  # floor, normal +y
+        za, zb = zs[k], zs[k + 1]
+        meshes.append(_planar(quad((x0, y0, za), (x1, y0, za), (x1, y0, zb), (x0, y0, zb), mat), (0.55, 0, 0, 0.3), (0, 0, 0.35, 0.4)))
+    for k, mat in enumerate((8, 11, 13)):  # ceiling
+        za, zb = zs[k], zs[k + 1]
+        meshes.append(_planar(quad((x0, y1, za), (x1, y1, za), (x1, y1, zb), (x0, y1, zb), mat), (0.4, 0, 0, 0.5), (0, 0, -0.3, 0.2)))
+    for k, mat in enumerate((5, 6, 7)):  # left wall
+        za, zb = zs[k], zs[k + 1]
+        meshes.append(_planar(quad((x0, y0, zb), (x0, y1, zb), (x0, y1, za), (x0, y0, za), mat), (0, 0.1, 0, 5.0), (0, 0, 0.1, 5.0)))
+    for k, mat in enumerate((9, 10, 12)):  # right wall: u along y, v along z
+        za, zb = zs[k], zs[k + 1]
+        meshes.append(_planar(quad((x1, y0, zb), (x1, y1, zb), (x1, y1, za), (x1, y0, za), mat),
+                              (0, 0.5, 0, 0.5), (0, 0, 1.5 / (zb - za), -0.25 - 1.5 * za / (zb - za))))
+    meshes.append(_planar(quad((x0, y0, zs[3]), (x1, y0, zs[3]), (x1, y1, zs[3]), (x0, y1, zs[3]), 2), (-0.4, 0, 0, 0.5), (0, 0.5, 0, 0.6)))
+    meshes.append(_planar(quad((x0, y0, zs[0]), (x0, y1, zs[0]), (x1, y1, zs[0]), (x1, y0, zs[0]), 3), (0.55, 0, 0, 0.3), (0, 0.5, 0, 0.4)))
+    c, r = np.array([0.9, -0.4, -3.6]), scenes.camera_matrix(35.0, 25.0).reshape(3, 3).astype(np.float64)
+    pts = [c + r @ np.array(p) for p in ((-0.6, -0.5, 0), (0.6, -0.5, 0), (0.6, 0.5, 0), (-0.6, 0.5, 0))]
+    meshes.append(quad(*pts, 8))  # no uvs: texel (row 12, column 0) of the 17x13 bitmap
+    meshes.append(_planar(box((-1.1, -1.5, -3.4), (-0.4, -0.8, -2.7), 8), (0.9, 0, 0.4, 2.3), (0, 1.1, 0.3, 2.4)))
+    c = np.array([-0.2, -0.9, -2.0])
+    pts = [c + r @ np.array(p) for p in ((-0.4, -0.3, 0), (0.4, -0.3, 0), (0.4, 0.3, 0), (-0.4, 0.3, 0))]
+    meshes.append(_planar(quad(*pts, 14), (0.5, 0, 0, 0.5), (0, 0.5, 0, 0.5)))
+    lights = [((-0.7, 1.2, -3.0), 40.0), ((1.6, 0.3, -4.8), 25.0)]
+    sc = _sc(meshes, lights, mats, (0.0, 0.0, 1.5), scenes.camera_matrix(0.0, -5.0))
+    sc["textures"] = [dict(t) for t in _TEXTURES]
+    return sc
+
+
+def scene_textured_glass(scenes):
+    """scene_sphere's smooth glass icosphere over a 3-square checker floor (uvs from -1 to 2) in front of a 17x13 bitmap wall
+    (u from -0.25 to 1.25, v up to 1.2), beside a mirror whose albedo is an albedo texture: textured surfaces are reached through
+    refraction and after mirror bounces.  The glass names a texture too; it decides nothing (glass has no albedo term)."""
+    floor, wall = _backdrop(0, 1)
+    _planar(floor, (0.25, 0, 0, 0.5), (0, 0, 0.2, 1.0))
+    _planar(wall, (0.125, 0, 0, 0.5), (0, 0.2, 0, 0.2))
+    mirror = _planar(quad((-2.4, -1, -1.0), (-1.6, -1, -4.0), (-1.6, 1.5, -4.0), (-2.4, 1.5, -1.0), 3), (0, 0, 0.3, 1), (0, 0.4, 0, 0.4))
+    meshes = [floor, wall, icosphere(scenes, (0.0, -0.1, -2.6), 0.8, 1, 2), mirror]
+    mats = [dict(m) for m in _GLASS_MATS]
+    mats[0]["texture"], mats[1]["texture"] = 0, 1
+    mats[2].update(smooth_shading=True, texture=0)
+    mats.append({"albedo": (0.5, 0.5, 0.5), "type": REFLECTIVE, "texture": 2})
+    sc = _sc(meshes, _GLASS_LIGHTS, mats, (0.0, 0.2, 0.4), scenes.camera_matrix(0.0, -4.0))
+    sc["textures"] = [dict(_TEXTURES[1]), dict(_TEXTURES[8]), {"type": "albedo", "color_a": (0.9, 0.7, 0.8)}]
+    return sc
+
+
+SCENES = {"room": scene_room, "mirrors": scene_mirrors, "slab": scene_slab, "prism": scene_prism, "sphere": scene_sphere,
+          "textured_room": scene_textured_room, "textured_glass": scene_textured_glass}
 MISS_RGB = (0.2, 0.35, 0.5)

@@ -8,6 +8,8 @@ internal reflection, origin biases, throughput products, the max_bounces cut per
 Tolerance per colour channel: 1e-4 x (closest-hit segments of the path) x |reference| + 1e-5.  A float32 segment carries
 relative errors of a few 1e-6 (measured: at most 4e-5 over a 6-segment path); any change of formula moves a pixel by far more.
 Paths with a decision margin below path_reference.MARGINS are skipped; at most 3 % may be, per frame."""
+from collections import Counter
+
 import numpy as np
 import pytest
 
@@ -27,6 +29,18 @@ COVERAGE = {
     "slab": ("enter", "exit", "tir", "refract_cut", "miss_after_bounce", "diffuse_bounce"),
     "prism": ("enter", "exit", "tir", "refract_cut"),
     "sphere": ("enter", "exit", "refract_cut", "miss_after_bounce"),
+    "textured_room": ("tex_albedo", "tex_edges", "tex_checker", "tex_bitmap", "checker_negative", "checker_above_1",
+                      "bitmap_u_low", "bitmap_u_high", "bitmap_v_low", "bitmap_v_high", "edges_edge", "edges_inner",
+                      "tex_index_past_table", "tex_after_bounce", "diffuse_bounce", "shadowed", "lit"),
+    "textured_glass": ("tex_albedo", "tex_checker", "tex_bitmap", "tex_on_glass_or_mirror", "tex_after_bounce", "checker_negative",
+                       "checker_above_1", "bitmap_u_low", "bitmap_u_high", "bitmap_v_high", "enter", "exit", "mirror", "refract_cut"),
+}
+TEXTURED = ("textured_room", "textured_glass")
+# texture events that mode 100 at pixel centres must see as well (every material shaded as diffuse)
+CENTRE_COVERAGE = {
+    "textured_room": ("tex_albedo", "tex_edges", "tex_checker", "tex_bitmap", "checker_negative", "checker_above_1", "bitmap_u_low",
+                      "bitmap_u_high", "bitmap_v_low", "bitmap_v_high", "edges_edge", "edges_inner", "tex_index_past_table"),
+    "textured_glass": ("tex_albedo", "tex_checker", "tex_bitmap", "tex_on_glass_or_mirror", "checker_negative", "checker_above_1"),
 }
 
 
@@ -48,8 +62,8 @@ def compare_path_frame(got, ref, what):
     return skipped
 
 
-def compare_centres(got, S, cam, mode, miss, ks=0.0, exponent=32):
-    rgb, rb, inst, prim, t = R.shade_centres(S, cam["position"], cam["matrix"], W, H, mode, miss, ks, exponent)
+def compare_centres(got, S, cam, mode, miss, ks=0.0, exponent=32, ev=None):
+    rgb, rb, inst, prim, t = R.shade_centres(S, cam["position"], cam["matrix"], W, H, mode, miss, ks, exponent, ev=ev)
     assert rb.mean() > 1.0 - MAX_SKIPPED
     np.testing.assert_array_equal(got["hit_inst"][rb], inst[rb])
     np.testing.assert_array_equal(got["hit_prim"][rb], prim[rb])
@@ -82,7 +96,7 @@ def _references(built, name):
 def test_oracle_paths_equal_float64_reference(oracle, built, name):
     sc, _ = built[name]
     cam = sc["camera"]
-    O = oracle.OracleScene(sc["meshes"], sc["lights"], sc["materials"])
+    O = oracle.OracleScene(sc["meshes"], sc["lights"], sc["materials"], textures=sc.get("textures", ()))
     ev = {}
     try:
         for mb, seed, ref in _references(built, name):
@@ -98,17 +112,20 @@ def test_oracle_paths_equal_float64_reference(oracle, built, name):
 
 
 def test_oracle_centre_modes_equal_float64_reference(oracle, built):
-    for name in ("room", "prism"):
+    for name in ("room", "prism") + TEXTURED:
         sc, S = built[name]
         cam = sc["camera"]
-        O = oracle.OracleScene(sc["meshes"], sc["lights"], sc["materials"])
+        ev = Counter()
+        O = oracle.OracleScene(sc["meshes"], sc["lights"], sc["materials"], textures=sc.get("textures", ()))
         try:
             for mode in (3, 5, 100):
                 oracle.set_phong(250 if mode == 100 else 0, 16)
                 got = O.render(cam["position"], cam["matrix"], mode, W, H, miss_rgb=R.MISS_RGB)
-                compare_centres(got, S, cam, mode, R.MISS_RGB, 0.25 if mode == 100 else 0.0, 16)
+                compare_centres(got, S, cam, mode, R.MISS_RGB, 0.25 if mode == 100 else 0.0, 16, ev=ev)
         finally:
             oracle.set_phong(0, 32)
+        missing = [k for k in CENTRE_COVERAGE.get(name, ()) if ev[k] == 0]
+        assert not missing, "scene %s: mode 100 never exercised %s" % (name, missing)
 
 
 def test_reference_rng_is_the_spec_hash():
@@ -136,7 +153,7 @@ def test_gpu_paths_equal_float64_reference(renderer, built, name, pipeline):
     cam = sc["camera"]
     r = renderer
     r.set_accumulation(0)
-    r.upload(sc["meshes"], sc["lights"], sc["materials"])
+    r.upload(sc["meshes"], sc["lights"], sc["materials"], sc.get("textures"))
     r.set_camera(cam["position"], cam["matrix"])
     r.set_miss_color(R.MISS_RGB)
     r.change_shading_mode(200)
@@ -153,14 +170,14 @@ def test_gpu_paths_equal_float64_reference(renderer, built, name, pipeline):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["room", "prism", "sphere"])
+@pytest.mark.parametrize("name", ["room", "prism", "sphere"] + list(TEXTURED))
 def test_gpu_centre_modes_equal_float64_reference(renderer, built, name):
     """modes 3 (barycentrics), 5 (distance) and 100 (Lambert + Phong, ks 0.25, exponent 16) at pixel centres"""
     sc, S = built[name]
     cam = sc["camera"]
     r = renderer
     r.set_accumulation(0)
-    r.upload(sc["meshes"], sc["lights"], sc["materials"])
+    r.upload(sc["meshes"], sc["lights"], sc["materials"], sc.get("textures"))
     r.set_camera(cam["position"], cam["matrix"])
     r.set_miss_color(R.MISS_RGB)
     try:

@@ -230,6 +230,36 @@ def test_texture_classes_match_the_reference(pkg, oracle, golden_dir):
             exp = np.float32([r, gg, b])
             np.testing.assert_array_equal(s.texture_color(i, u, v), exp, err_msg="%s host (%g,%g)" % (name, u, v))
             np.testing.assert_array_equal(oracle.texture_color(odesc[name], u, v), exp, err_msg="%s oracle (%g,%g)" % (name, u, v))
+    # the wide file: more square sizes and edge widths over [-2.5, 2.5]^2 with the cell boundaries and their float neighbours,
+    # bitmaps one texel wide or high over [-0.5, 1.5]^2 (oracle/make_golden.py texture_wide; rows [u, v, 0 = color_A | 1 = color_B]
+    # and [u, v, R, G, B]).  Inside the int range the conversion rule of include/crt_hip.h is the reference's plain cast.
+    wide = json.load(open(os.path.join(golden_dir, "texture_known_answers_wide.json")))
+    AB = (np.float32(wide["color_A"]), np.float32(wide["color_B"]))
+    assert sorted(wide["checker"], key=float) == ["0.0700000003", "0.300000012", "0.333333343", "0.600000024", "2"]
+    assert sorted(wide["edges"], key=float) == ["0", "0.0399999991", "0.5"] and sorted(wide["bitmap"]) == ["1x1", "1x9", "9x1"]
+    n_rows = 0
+    for kind in ("checker", "edges", "bitmap"):
+        for key, rows in wide[kind].items():
+            assert len(rows) > 100
+            s = pkg.Scene()
+            if kind == "bitmap":
+                path = os.path.join(golden_dir, "tex_wide_%s.ppm" % key)
+                s.add_texture("t", "bitmap", file_path=path)
+                w, h = (int(x) for x in key.split("x"))
+                raw = open(path, "rb").read()
+                desc = {"type": "bitmap", "pixels": np.frombuffer(raw[len(raw) - 3 * w * h:], np.uint8).reshape(h, w, 3)}
+            else:
+                s.add_texture("t", kind, AB[0], AB[1], float(key))
+                desc = {"type": kind, "color_a": AB[0], "color_b": AB[1], "scalar": float(key)}
+            if kind == "checker":
+                assert {r[2] for r in rows} == ({0} if float(key) > 1 else {0, 1})
+            for row in rows:
+                u, v = row[0], row[1]
+                exp = AB[row[2]] if kind != "bitmap" else np.float32(row[2:5]) / np.float32(255.0)
+                np.testing.assert_array_equal(s.texture_color(0, u, v), exp, err_msg="%s %s host (%r,%r)" % (kind, key, u, v))
+                np.testing.assert_array_equal(oracle.texture_color(desc, u, v), exp, err_msg="%s %s oracle (%r,%r)" % (kind, key, u, v))
+                n_rows += 1
+    assert n_rows > 2000
 
 
 def test_bitmap_formats_match_the_reference(pkg, golden_dir):
