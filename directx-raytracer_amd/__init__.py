@@ -51,7 +51,7 @@ ABI_SYMBOLS = [
     "crt_trace_rays_device", "crt_occluded_rays_device", "crt_trace_rays", "crt_occluded_rays",
     "crt_closest_points_device", "crt_closest_points", "crt_count_hits_device", "crt_count_hits", "crt_occupancy_device", "crt_occupancy",
     "crt_update_vertices", "crt_update_vertices_device", "crt_set_mesh_transform", "crt_refit", "crt_mesh_vertices",
-    "crt_rebuild",
+    "crt_rebuild", "crt_list_hits_device", "crt_list_hits", "crt_debug_list_phases",
 ]
 
 
@@ -216,6 +216,9 @@ def lib():
         "crt_refit": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "crt_mesh_vertices": (C.c_int, [vp, u32, vp, vp]),
         "crt_rebuild": (C.c_int, [vp, C.POINTER(C.c_double)]),
+        "crt_list_hits_device": (C.c_int, [vp, u32, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+        "crt_list_hits": (C.c_int, [vp, u32, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
+        "crt_debug_list_phases": (C.c_int, [vp, vp]),
     }
     assert set(sig) == set(ABI_SYMBOLS)
     for name, (res, args) in sig.items():
@@ -543,6 +546,25 @@ def quantize4(nodes4):
     return out
 
 
+def inside_length(offsets, t):
+    """Per ray of a hit list (Renderer.list_hits: offsets (N + 1,), t (total,) ascending inside a ray), the sum over k of
+    float64(t[2k+1]) - float64(t[2k]): the length between its 1st and 2nd, 3rd and 4th, ... hit; an odd last hit is ignored.
+    (N,) float64, pure numpy."""
+    off = np.asarray(offsets, dtype=np.int64)
+    t64 = np.asarray(t, dtype=np.float64)
+    n = len(off) - 1
+    cnt = np.diff(off)
+    ray = np.repeat(np.arange(n), cnt)
+    k = np.arange(len(t64)) - off[:-1][ray]  # position inside the ray's list
+    paired = k < (cnt[ray] & ~1)
+    out = np.zeros(n, dtype=np.float64)
+    # interval by interval (not a signed sum over all records): t[2k+1] - t[2k] first, then the sum in list order
+    hi = paired & ((k & 1) == 1)
+    seg = t64[hi] - t64[np.flatnonzero(hi) - 1]
+    np.add.at(out, ray[hi], seg)
+    return out
+
+
 class Renderer:
     """crt_ctx handle: the DXRTRenderer surface over HIP. Raises CrtError when no MI355X / HIP device is usable."""
 
@@ -828,6 +850,64 @@ class Renderer:
         st = FrameStats() if stats else None
         self._ok(lib().crt_occupancy_device(self.h, int(n), d_points, d_inside, C.byref(st) if stats else None), "crt_occupancy_device")
         return st.as_dict() if stats else None
+
+    # ---- all-hits ray queries (include/crt_hip.h): every crossing of a ray as a CSR list sorted by distance
+    def list_hits(self, rays, want=("t", "uv", "inst", "prim"), capacity=None):
+        """every triangle each ray crosses in (tmin, tmax), in ascending t (host buffers, synchronous).  Returns a dict:
+        offsets (N + 1,) int64 -- the hits of ray i are records offsets[i] .. offsets[i + 1] - 1 --, ray (total,) uint32 (the ray
+        of every record), the wanted arrays t (total,) float32, uv (total, 2) float32, inst / prim (total,) uint32, and 'stats'
+        of the last call.  Without `capacity` one offsets-only call learns the total first; with it that call is made only
+        when the guess was too small."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = len(r)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        tot = C.c_uint64(0)
+        st = FrameStats()
+        shapes = {"t": ((), np.float32), "uv": ((2,), np.float32), "inst": ((), np.uint32), "prim": ((), np.uint32)}
+        wanted = [k for k in shapes if k in want]
+
+        def call(cap, out):
+            def p(k):
+                return out[k].ctypes.data if k in out else None
+            self._ok(lib().crt_list_hits(self.h, n, r.ctypes.data, off.ctypes.data, cap, p("t"), p("uv"), p("inst"), p("prim"),
+                                         C.byref(tot), C.byref(st)), "crt_list_hits")
+        out = {}
+        if capacity is None or not wanted:
+            call(0, {})
+            capacity = tot.value
+        if wanted:
+            out = {k: np.zeros((int(capacity),) + shapes[k][0], dtype=shapes[k][1]) for k in wanted}
+            call(int(capacity), out)
+            if tot.value > capacity:  # the guess was too small
+                out = {k: np.zeros((tot.value,) + shapes[k][0], dtype=shapes[k][1]) for k in wanted}
+                call(tot.value, out)
+            out = {k: v[:tot.value] for k, v in out.items()}
+        out["offsets"] = off.astype(np.int64)
+        out["ray"] = np.repeat(np.arange(n, dtype=np.uint32), np.diff(out["offsets"]))
+        out["stats"] = st.as_dict()
+        return out
+
+    def list_hits_device(self, n, d_rays, d_offsets, capacity, d_t=None, d_uv=None, d_inst=None, d_prim=None, total=False, stats=False):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); d_offsets holds n + 1 int64.  Asynchronous on the
+        context's stream unless total or stats.  Returns None, the total, the stats, or (total, stats)."""
+        st = FrameStats() if stats else None
+        tot = C.c_uint64(0) if total else None
+        self._ok(lib().crt_list_hits_device(self.h, int(n), d_rays, d_offsets, int(capacity), d_t, d_uv, d_inst, d_prim,
+                                            C.byref(tot) if total else None, C.byref(st) if stats else None), "crt_list_hits_device")
+        if total and stats:
+            return tot.value, st.as_dict()
+        return tot.value if total else (st.as_dict() if stats else None)
+
+    def list_phases(self):
+        """HIP-event ms of count / scan / fill / sort of the last list_hits* call that was given stats"""
+        buf = np.zeros(4, dtype=np.float64)
+        self._ok(lib().crt_debug_list_phases(self.h, buf.ctypes.data), "crt_debug_list_phases")
+        return dict(zip(("count", "scan", "fill", "sort"), buf.tolist()))
+
+    def inside_length(self, rays):
+        """per ray, the length (in units of |d|) between its 1st and 2nd, 3rd and 4th, ... hit: the chord through closed meshes"""
+        got = self.list_hits(rays, want=("t",))
+        return inside_length(got["offsets"], got["t"])
 
     def read_counters(self):
         buf = np.zeros(32, dtype=np.uint64)

@@ -216,6 +216,17 @@ struct crt_ctx {
     uint32_t rayResidentEntries[5] = {}; // ... for this many LDS stack entries
     void* dRayStage = nullptr; // the host entry points' records and outputs, grown on demand
     size_t rayStageBytes = 0;
+    // crt_list_hits*: the fill kernel's resident workgroups, the host form's record arrays (grown on demand, apart from
+    // dRayStage, which holds its rays and offsets while the total is read back) and the sort's crossover ("list_short_max")
+    uint32_t listResident = 0, listResidentEntries = 0;
+    void* dListStage = nullptr;
+    size_t listStageBytes = 0;
+    // lists of up to this many hits are sorted by one lane, longer ones by a wavefront.  Measured (DESIGN.md section 5d,
+    // tools/list_hits_bench.py, lists of 0 .. 1024 hits): 2.89 ms from 4 to 24, 2.92 at 32, 2.93 at 64 (all within the 1 %
+    // spread of the rounds), 3.02 at 256, 3.93 with every list on one lane.  Any value up to ~64 would do.
+    uint32_t tuneListShortMax = 24;
+    hipEvent_t evList[5] = {};    // a listing with stats: before the count, after count / scan / fill / sort
+    double listPhaseMs[4] = {};   // count, scan, fill, sort + resolve of the last listing that was given stats (crt_debug_list_phases)
 };
 
 namespace {
@@ -831,6 +842,9 @@ void crt_destroy(crt_ctx* c)
         if (c->rayArena[i].lastUse) (void)hipEventDestroy(c->rayArena[i].lastUse);
     }
     if (c->dRayStage) (void)hipFree(c->dRayStage);
+    if (c->dListStage) (void)hipFree(c->dListStage);
+    for (hipEvent_t e : c->evList)
+        if (e) (void)hipEventDestroy(e);
     if (c->evStart) (void)hipEventDestroy(c->evStart);
     if (c->evStop) (void)hipEventDestroy(c->evStop);
     if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
@@ -1115,6 +1129,10 @@ int crt_set_option(crt_ctx* c, const char* name, int value)
         c->tuneInnerMinAny = static_cast<uint32_t>(value);
         return CRT_OK;
     }
+    if (std::strcmp(name, "list_short_max") == 0 && value >= 1 && value <= 1024) {
+        c->tuneListShortMax = static_cast<uint32_t>(value);
+        return CRT_OK;
+    }
     if (std::strcmp(name, "xcd_group") == 0 && (value == 1 || value == 2 || value == 4 || value == 8 || value == 16)) {
         c->tuneXcdGroup = static_cast<uint32_t>(value);
         return CRT_OK;
@@ -1191,6 +1209,13 @@ int crt_debug_read_counters(crt_ctx* c, unsigned long long out[32])
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(out, c->dCounters, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
+int crt_debug_list_phases(crt_ctx* c, double out_ms[4])
+{
+    if (!c || !out_ms) return CRT_EINVAL;
+    std::memcpy(out_ms, c->listPhaseMs, sizeof(c->listPhaseMs));
     return CRT_OK;
 }
 
@@ -1340,13 +1365,17 @@ struct QueryLaunch {
     uint32_t* cursor;
     unsigned long long* counters;
     int* spill;
+    unsigned char* extra; // extraBytes of the arena behind the spill area (256-byte aligned), or null
     crt_ctx::RayArena* arena;
 };
 
 // One query of n > 0 records on the context's stream, in two halves around the kernel launch.  beginQuery sizes the persistent
 // grid, takes an arena and (with stats) starts the timer; entryWords = ints per stack entry.  endQuery takes the launch's HIP
 // error code and, with stats, synchronises and fills them.
-int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t entryWords, crt_frame_stats* stats, QueryLaunch& ql)
+// extraBytes: scratch of the query's own with the arena's lifetime (an allocation failure is then CRT_ENOMEM); minGrid: the
+// spill area is sized for at least that many workgroups (a query that runs a second persistent kernel over the same arena).
+int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t entryWords, crt_frame_stats* stats, QueryLaunch& ql, size_t extraBytes = 0,
+               uint32_t minGrid = 0)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     ql.stack_entries = c->tuneStackEntries ? c->tuneStackEntries : 16u; // as fillParams
@@ -1372,17 +1401,25 @@ int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t entryWords, crt_
         arena->used = true;
     }
     constexpr size_t kHead = 256; // cursor at 0, counters at 64
-    const size_t need = kHead + static_cast<size_t>(ql.grid) * 64u * ql.spill_stride * sizeof(int);
+    const size_t spillBytes = (static_cast<size_t>(std::max(ql.grid, minGrid)) * 64u * ql.spill_stride * sizeof(int) + 255u) & ~static_cast<size_t>(255u);
+    const size_t need = kHead + spillBytes + extraBytes;
     if (arena->bytes < need) {
         HIP_TRY(c, hipDeviceSynchronize()); // (the arena may still be in use by a query on its stream)
         if (arena->mem) (void)hipFree(arena->mem);
         arena->mem = nullptr;
         arena->bytes = 0;
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&arena->mem), need));
+        if (extraBytes) {
+            if (hipMalloc(reinterpret_cast<void**>(&arena->mem), need) != hipSuccess) {
+                (void)hipGetLastError();
+                arena->mem = nullptr;
+                return fail(c, CRT_ENOMEM, "query scratch: %zu bytes of device memory not available", need);
+            }
+        } else HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&arena->mem), need));
         arena->bytes = need;
     }
     if (!arena->lastUse) HIP_TRY(c, hipEventCreateWithFlags(&arena->lastUse, hipEventDisableTiming));
     arena->serial = ++c->raySerial;
+    ql.extra = extraBytes ? arena->mem + kHead + spillBytes : nullptr;
     ql.cursor = reinterpret_cast<uint32_t*>(arena->mem);
     ql.counters = reinterpret_cast<unsigned long long*>(arena->mem + 64);
     ql.spill = reinterpret_cast<int*>(arena->mem + kHead);
@@ -1575,6 +1612,138 @@ QuerySpec closestPointSpec(const char* what, void* dist, void* point, void* uv, 
 QuerySpec countSpec(const char* what, void* count) { return QuerySpec{ what, kQueryCount, 32u, "count", { { count, 4u, 4u } } }; }
 QuerySpec occupancySpec(const char* what, void* inside) { return QuerySpec{ what, kQueryOccupancy, 16u, "inside", { { inside, 1u, 1u } } }; }
 
+// ---- all-hits listing (crt_list_hits*): count -> scan -> fill -> sort + resolve over one arena, between one beginQuery and
+// one endQuery.  The counts (reused as the sort's queue of long rays), the scan's tile sums and the key scratch live in the
+// arena, so that a second listing on another stream gets its own.
+inline size_t up256(size_t b) { return (b + 255u) & ~static_cast<size_t>(255u); }
+
+struct ListRun {
+    QueryLaunch ql;
+    crt::ListParams q;
+    uint32_t fillGrid = 0, fillChunk = 0;
+    unsigned char* keyScratch = nullptr;
+    bool timed = false; // stats were asked for: the phases are bracketed by the context's evList
+};
+
+int listMark(crt_ctx* c, const ListRun& lr, int i)
+{
+    return lr.timed ? static_cast<int>(hipEventRecord(c->evList[i], c->stream)) : 0;
+}
+
+// count + scan.  keyBytes: scratch wanted behind the counts and the tile sums (device form: work arrays the caller did not supply)
+int listBegin(crt_ctx* c, uint32_t n, const void* d_rays, void* d_offsets, size_t keyBytes, crt_frame_stats* stats, ListRun& lr)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t entries = c->tuneStackEntries ? c->tuneStackEntries : 16u; // as beginQuery
+    if (c->listResident == 0u || c->listResidentEntries != entries) {
+        c->listResident = crt::listFillResident(entries);
+        c->listResidentEntries = entries;
+        if (c->listResident == 0u) return fail(c, CRT_EHIP, "list fill kernel: occupancy query failed");
+    }
+    crt::rayQueryLayout(n, c->listResident, lr.fillChunk, lr.fillGrid);
+    lr.timed = stats != nullptr;
+    if (lr.timed)
+        for (hipEvent_t& e : c->evList)
+            if (!e) HIP_TRY(c, hipEventCreate(&e));
+    const size_t countBytes = up256(static_cast<size_t>(n) * sizeof(uint32_t)), scanBytes = up256(crt::listScanScratchBytes(n));
+    if (const int rc = beginQuery(c, kQueryCount, n, 1u, stats, lr.ql, countBytes + scanBytes + keyBytes, lr.fillGrid)) return rc;
+    const QueryLaunch& ql = lr.ql;
+    uint32_t* counts = reinterpret_cast<uint32_t*>(ql.extra);
+    unsigned long long* tileSums = reinterpret_cast<unsigned long long*>(ql.extra + countBytes);
+    lr.keyScratch = ql.extra + countBytes + scanBytes;
+
+    crt::PointQueryParams pq;
+    std::memset(&pq, 0, sizeof(pq));
+    pq.nodes = c->dNodes;
+    pq.tris = c->dTris;
+    pq.n_nodes = c->bvh.nNodes4;
+    pq.records = d_rays;
+    pq.n = n;
+    pq.count = counts;
+    pq.inner_min = c->tuneInnerMinAny;
+    pq.stack_entries = ql.stack_entries;
+    pq.spill_stride = ql.spill_stride;
+    pq.chunk = ql.chunk;
+    pq.cursor = ql.cursor;
+    pq.counters = ql.counters;
+    pq.spill = ql.spill;
+
+    crt::ListParams& q = lr.q;
+    std::memset(&q, 0, sizeof(q));
+    q.nodes = c->dNodes;
+    q.tris = c->dTris;
+    q.n_nodes = c->bvh.nNodes4;
+    q.rays = d_rays;
+    q.n = n;
+    q.offsets = static_cast<const unsigned long long*>(d_offsets);
+    q.longRays = counts;
+    q.longCount = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(ql.cursor) + 128); // in the arena's zeroed head
+    q.short_max = c->tuneListShortMax;
+    q.inner_min = c->tuneInnerMinAny;
+    q.stack_entries = ql.stack_entries;
+    q.spill_stride = ql.spill_stride;
+    q.chunk = lr.fillChunk;
+    q.cursor = ql.cursor;
+    q.counters = ql.counters;
+    q.spill = ql.spill;
+
+    int rc = listMark(c, lr, 0);
+    if (rc == 0) rc = crt::launchPointQuery(pq, crt::kPointCount, c->counting, ql.grid, c->stream);
+    if (rc == 0) rc = listMark(c, lr, 1);
+    if (rc == 0) rc = crt::launchListScan(counts, n, static_cast<unsigned long long*>(d_offsets), tileSums, c->stream);
+    if (rc == 0) rc = listMark(c, lr, 2);
+    return rc == 0 ? CRT_OK : endQuery(c, kQueryCount, n, ql, rc, nullptr);
+}
+
+// fill + sort + resolve into the record arrays: the cursor (not the counters) starts again for the second traversal
+int listFill(crt_ctx* c, ListRun& lr, unsigned long long capacity, float* tkey, uint32_t* idkey, void* const out[4])
+{
+    crt::ListParams& q = lr.q;
+    q.capacity = capacity;
+    q.tkey = tkey;
+    q.idkey = idkey;
+    q.t = static_cast<float*>(out[0]);
+    q.uv = static_cast<float*>(out[1]);
+    q.inst = static_cast<uint32_t*>(out[2]);
+    q.prim = static_cast<uint32_t*>(out[3]);
+    const hipError_t e = hipMemsetAsync(q.cursor, 0, sizeof(uint32_t), c->stream);
+    if (e != hipSuccess) return static_cast<int>(e);
+    int rc = crt::launchListFill(q, c->counting, lr.fillGrid, c->stream);
+    if (rc == 0) rc = listMark(c, lr, 3);
+    if (rc == 0) rc = crt::launchListSort(q, c->stream);
+    if (rc == 0) rc = listMark(c, lr, 4);
+    return rc;
+}
+
+// after endQuery has synchronised a timed listing: the phases' HIP-event times (fill and sort 0 when they did not run)
+int listPhases(crt_ctx* c, const ListRun& lr, bool filled)
+{
+    if (!lr.timed) return CRT_OK;
+    for (int i = 0; i < 4; i++) {
+        float ms = 0.f;
+        if (i < 2 || filled) HIP_TRY(c, hipEventElapsedTime(&ms, c->evList[i], c->evList[i + 1]));
+        c->listPhaseMs[i] = ms;
+    }
+    return CRT_OK;
+}
+
+int listCheck(crt_ctx* c, const char* what, uint32_t n, const void* rays, const void* offsets, std::chrono::steady_clock::time_point t0,
+              uint64_t* total, crt_frame_stats* stats, bool& done)
+{
+    done = false;
+    if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
+    if (!c->haveScene) return fail(c, CRT_ESTATE, "%s: no scene uploaded: call crt_upload_scene first", what);
+    if (n == 0u) {
+        zeroStats(stats, t0);
+        if (total) *total = 0u;
+        done = true;
+        return CRT_OK;
+    }
+    if (!rays) return fail(c, CRT_EINVAL, "%s: ray buffer is NULL", what);
+    if (!offsets) return fail(c, CRT_EINVAL, "%s: offsets is NULL", what);
+    return CRT_OK; // (the caller applies pending refits once its own argument checks are through: a failed call launches nothing)
+}
+
 } // namespace
 
 int crt_trace_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_t, void* d_uv, void* d_inst, void* d_prim, crt_frame_stats* stats)
@@ -1627,6 +1796,116 @@ int crt_occupancy_device(crt_ctx* c, uint32_t n, const void* d_points, void* d_i
 int crt_occupancy(crt_ctx* c, uint32_t n, const float* points, uint8_t* inside, crt_frame_stats* stats)
 {
     return queryHost(c, occupancySpec("crt_occupancy", inside), n, points, stats);
+}
+
+int crt_list_hits_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_offsets, uint64_t capacity, void* d_t, void* d_uv, void* d_inst,
+                         void* d_prim, uint64_t* total, crt_frame_stats* stats)
+{
+    const char* what = "crt_list_hits_device";
+    const auto t0 = std::chrono::steady_clock::now();
+    bool done;
+    int rc = listCheck(c, what, n, d_rays, d_offsets, t0, total, stats, done);
+    if (rc || done) return rc;
+    if (reinterpret_cast<uintptr_t>(d_rays) & 15u) return fail(c, CRT_EINVAL, "%s: ray buffer %p is not 16-byte aligned", what, d_rays);
+    if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return fail(c, CRT_EINVAL, "%s: offsets %p is not 8-byte aligned", what, d_offsets);
+    if ((reinterpret_cast<uintptr_t>(d_uv) & 7u) || ((reinterpret_cast<uintptr_t>(d_t) | reinterpret_cast<uintptr_t>(d_inst) | reinterpret_cast<uintptr_t>(d_prim)) & 3u))
+        return fail(c, CRT_EINVAL, "%s: a record array is misaligned (uv 8-byte, t / inst / prim 4-byte)", what);
+    const bool fill = d_t || d_uv || d_inst || d_prim;
+    // work arrays the caller's own t / prim arrays cannot stand in for, sized from the capacity
+    size_t keyBytes = 0;
+    if (fill && (!d_t || !d_prim)) {
+        if (capacity > (static_cast<uint64_t>(1) << 40)) return fail(c, CRT_ENOMEM, "%s: key scratch for a capacity of %llu records", what, static_cast<unsigned long long>(capacity));
+        keyBytes = (d_t ? 0u : up256(static_cast<size_t>(capacity) * 4u)) + (d_prim ? 0u : up256(static_cast<size_t>(capacity) * 4u));
+    }
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    ListRun lr;
+    if ((rc = listBegin(c, n, d_rays, d_offsets, keyBytes, stats, lr)) != CRT_OK) return rc;
+    int hrc = 0;
+    if (fill) {
+        unsigned char* scratch = lr.keyScratch;
+        float* tkey = static_cast<float*>(d_t);
+        if (!tkey) { tkey = reinterpret_cast<float*>(scratch); scratch += up256(static_cast<size_t>(capacity) * 4u); }
+        uint32_t* idkey = d_prim ? static_cast<uint32_t*>(d_prim) : reinterpret_cast<uint32_t*>(scratch);
+        void* const out[4] = { d_t, d_uv, d_inst, d_prim };
+        hrc = listFill(c, lr, capacity, tkey, idkey, out);
+    }
+    if ((rc = endQuery(c, kQueryCount, n, lr.ql, hrc, stats)) != CRT_OK) return rc;
+    if ((rc = listPhases(c, lr, fill)) != CRT_OK) return rc;
+    if (total) {
+        unsigned long long tot = 0;
+        HIP_TRY(c, hipMemcpyAsync(&tot, static_cast<const unsigned long long*>(d_offsets) + n, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        *total = tot;
+    }
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+int crt_list_hits(crt_ctx* c, uint32_t n, const float* rays, uint64_t* offsets, uint64_t capacity, float* t, float* uv, uint32_t* inst,
+                  uint32_t* prim, uint64_t* total, crt_frame_stats* stats)
+{
+    const char* what = "crt_list_hits";
+    const auto t0 = std::chrono::steady_clock::now();
+    bool done;
+    int rc = listCheck(c, what, n, rays, offsets, t0, total, stats, done);
+    if (done && offsets) offsets[0] = 0u;
+    if (rc || done) return rc;
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    const size_t nn = n, rayBytes = up256(nn * 32u), offBytes = up256((nn + 1u) * sizeof(uint64_t));
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->rayStageBytes < rayBytes + offBytes) {
+        HIP_TRY(c, hipDeviceSynchronize());
+        if (c->dRayStage) (void)hipFree(c->dRayStage);
+        c->dRayStage = nullptr;
+        c->rayStageBytes = 0;
+        HIP_TRY(c, hipMalloc(&c->dRayStage, rayBytes + offBytes));
+        c->rayStageBytes = rayBytes + offBytes;
+    }
+    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
+    unsigned long long* dOff = reinterpret_cast<unsigned long long*>(base + rayBytes);
+    HIP_TRY(c, hipMemcpyAsync(base, rays, nn * 32u, hipMemcpyHostToDevice, c->stream));
+    ListRun lr;
+    if ((rc = listBegin(c, n, base, dOff, 0u, stats, lr)) != CRT_OK) return rc;
+    // the one read-back: does the total fit the caller's arrays?
+    unsigned long long tot = 0;
+    hipError_t he = hipMemcpyAsync(&tot, dOff + n, sizeof(tot), hipMemcpyDeviceToHost, c->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    const bool fill = (t || uv || inst || prim) && he == hipSuccess && tot <= capacity && tot > 0u;
+    unsigned char* rec = nullptr;
+    const size_t cap4 = up256(static_cast<size_t>(tot) * 4u), cap8 = up256(static_cast<size_t>(tot) * 8u);
+    bool noMem = false;
+    if (fill) {
+        const size_t need = 3u * cap4 + cap8; // t, prim (the work arrays), inst, uv
+        if (c->listStageBytes < need) {
+            he = hipDeviceSynchronize();
+            if (c->dListStage) (void)hipFree(c->dListStage);
+            c->dListStage = nullptr;
+            c->listStageBytes = 0;
+            if (he == hipSuccess && hipMalloc(&c->dListStage, need) != hipSuccess) {
+                (void)hipGetLastError();
+                c->dListStage = nullptr;
+                noMem = true;
+            } else if (he == hipSuccess) c->listStageBytes = need;
+        }
+        rec = static_cast<unsigned char*>(c->dListStage);
+    }
+    int hrc = static_cast<int>(he);
+    void* const out[4] = { rec, uv ? rec + 3u * cap4 : nullptr, inst ? rec + 2u * cap4 : nullptr, rec ? rec + cap4 : nullptr };
+    if (fill && !noMem && hrc == 0) hrc = listFill(c, lr, tot, static_cast<float*>(out[0]), static_cast<uint32_t*>(out[3]), out);
+    if ((rc = endQuery(c, kQueryCount, n, lr.ql, hrc, stats)) != CRT_OK) return rc;
+    if ((rc = listPhases(c, lr, fill && !noMem)) != CRT_OK) return rc;
+    if (noMem) return fail(c, CRT_ENOMEM, "%s: staging for %llu records not available", what, tot);
+    HIP_TRY(c, hipMemcpyAsync(offsets, dOff, (nn + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (fill) {
+        if (t) HIP_TRY(c, hipMemcpyAsync(t, out[0], static_cast<size_t>(tot) * 4u, hipMemcpyDeviceToHost, c->stream));
+        if (uv) HIP_TRY(c, hipMemcpyAsync(uv, out[1], static_cast<size_t>(tot) * 8u, hipMemcpyDeviceToHost, c->stream));
+        if (inst) HIP_TRY(c, hipMemcpyAsync(inst, out[2], static_cast<size_t>(tot) * 4u, hipMemcpyDeviceToHost, c->stream));
+        if (prim) HIP_TRY(c, hipMemcpyAsync(prim, out[3], static_cast<size_t>(tot) * 4u, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (total) *total = tot;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
 }
 
 int crt_render_frame_device(crt_ctx* c, uint32_t w, uint32_t h, void* d_rgba8, void* d_hit_inst, void* d_hit_prim,

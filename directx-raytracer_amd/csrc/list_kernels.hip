@@ -1,0 +1,428 @@
+// HIP kernels for gfx950 (MI355X): all-hits ray queries (crt_list_hits*, include/crt_hip.h) -- every triangle a ray crosses
+// in (tmin, tmax), as a CSR list sorted by distance.
+//
+// A call is the hit count of point_kernels.hip (hitCountKernel, unchanged) followed by the kernels of this file, all on one
+// stream without a host round trip:
+//   scan   exclusive sum of the n uint32 counts into n + 1 uint64 offsets (tile sums, one-workgroup scan of the sums, rescan
+//          of each tile: the 64-bit sibling of gpu_sort.hip.h's prefix sum)
+//   fill   the count's traversal once more (same persistent shape, same triTest on the same records, so it accepts the same
+//          triangles), whose leaf step writes a hit's prescaled t' and its leaf-order triangle record at offsets[ray] + k++
+//   sort   every segment by (t', global id), then resolve: t' 2^-e, (u, v) by re-running triTest as the ray query's record
+//          re-read at retirement, inst and prim from the triangle record.  Segments of up to short_max records: one lane per
+//          ray, insertion sort.  Longer ones: one wavefront per ray, an all-ascending bitonic network, through LDS in tiles
+//          of kSortTile records and over global memory for the strides a tile cannot hold (any length, no scratch).
+// fill and sort read offsets[n] first and leave when it exceeds the capacity: the decision "does it fit" is the device's.
+//
+// The sort compares t' as floats and, only on equal t', the global ids, which it reads from the triangle records (the work
+// arrays hold the record index the resolve needs, not the id).  The order is total: a triangle sits in one leaf.
+#include "traversal.hip.h"
+#include "render_kernels.h"
+#include "../../include/crt_hip.h"
+
+namespace crt {
+namespace {
+
+#ifndef CRT_REFILL_MIN
+#define CRT_REFILL_MIN 16
+#endif
+
+constexpr int kListMaxWavesPerSimd = 7; // as kPointMaxWavesPerSimd
+
+// ---- scan: n uint32 counts -> n + 1 uint64 offsets.  Tiles of 2048 counts; tile n / 2048 holds offsets[n], so there are
+// n / 2048 + 1 tiles (up to 2^21 + 1 for n = 2^32 - 1: indices are 64-bit).
+constexpr uint32_t kScanThreads = 256, kScanItems = 8, kScanTile = kScanThreads * kScanItems, kScanWaves = kScanThreads / 64;
+constexpr uint32_t kSumThreads = 1024;
+
+inline uint32_t listTiles(uint32_t n) { return n / kScanTile + 1u; }
+
+__global__ __launch_bounds__(kScanThreads) void listTileSumKernel(const uint32_t* __restrict__ v, uint32_t n, unsigned long long* __restrict__ sums)
+{
+    __shared__ unsigned long long part[kScanWaves];
+    const unsigned long long base = static_cast<unsigned long long>(blockIdx.x) * kScanTile + threadIdx.x * kScanItems;
+    unsigned long long s = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kScanItems; j++) s += base + j < n ? v[base + j] : 0u;
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tot = 0;
+        for (uint32_t w = 0; w < kScanWaves; w++) tot += part[w];
+        sums[blockIdx.x] = tot;
+    }
+}
+
+// exclusive sum of v[0..m) in place, one workgroup
+__global__ __launch_bounds__(kSumThreads) void listScanSumsKernel(unsigned long long* __restrict__ v, uint32_t m)
+{
+    __shared__ unsigned long long part[kSumThreads];
+    const uint32_t t = threadIdx.x;
+    const uint32_t per = (m + kSumThreads - 1u) / kSumThreads;
+    const uint32_t lo = t * per < m ? t * per : m, hi = lo + per < m ? lo + per : m;
+    unsigned long long sum = 0;
+    for (uint32_t i = lo; i < hi; i++) sum += v[i];
+    part[t] = sum;
+    __syncthreads();
+    for (uint32_t d = 1; d < kSumThreads; d <<= 1) {
+        const unsigned long long add = t >= d ? part[t - d] : 0ull;
+        __syncthreads();
+        part[t] += add;
+        __syncthreads();
+    }
+    unsigned long long run = part[t] - sum;
+    for (uint32_t i = lo; i < hi; i++) {
+        const unsigned long long c = v[i];
+        v[i] = run;
+        run += c;
+    }
+}
+
+__global__ __launch_bounds__(kScanThreads) void listTileScanKernel(const uint32_t* __restrict__ v, uint32_t n, const unsigned long long* __restrict__ tileStarts,
+                                                                  unsigned long long* __restrict__ out /* n + 1 */)
+{
+    __shared__ unsigned long long part[kScanWaves];
+    const unsigned long long base = static_cast<unsigned long long>(blockIdx.x) * kScanTile + threadIdx.x * kScanItems;
+    uint32_t x[kScanItems];
+    unsigned long long s = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kScanItems; j++) {
+        x[j] = base + j < n ? v[base + j] : 0u;
+        s += x[j];
+    }
+    unsigned long long incl = s;
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long up = __shfl_up(incl, off, 64);
+        if ((threadIdx.x & 63u) >= static_cast<uint32_t>(off)) incl += up;
+    }
+    if ((threadIdx.x & 63u) == 63u) part[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    unsigned long long run = tileStarts[blockIdx.x] + incl - s;
+    for (uint32_t w = 0; w < (threadIdx.x >> 6); w++) run += part[w];
+#pragma unroll
+    for (uint32_t j = 0; j < kScanItems; j++) {
+        if (base + j <= n) out[base + j] = run; // entry n is the total
+        run += x[j];
+    }
+}
+
+// ---- fill
+
+// One scheduling decision of the listing traversal: countIteration (point_kernels.hip) whose leaf writes the accepted hit
+// into the ray's segment instead of counting it (its twin: keep the box cull and the triangle test of the two the same).  k counts every accepted hit; only the first `room` are stored, so that the
+// two traversals could never write outside the segment even if they disagreed.
+template <bool COUNT, class L, int OCT, bool DEC = false>
+__device__ __forceinline__ void listIteration(const float4* __restrict__ nodes, const float4* __restrict__ tris, const Ray& r, float tmin, float tmax,
+                                              float tcull, Stack& stack, int innerMin, float* tkey, uint32_t* idkey, unsigned long long base,
+                                              uint32_t room, uint32_t& k, int& cur, uint32_t& cntNodes, uint32_t& cntTris,
+                                              const float* __restrict__ planes = nullptr)
+{
+    const unsigned long long innerMask = __ballot(L::inner(cur));
+    const unsigned long long leafMask = __ballot(L::leaf(cur));
+    if ((innerMask | leafMask) == 0ull) return;
+    const int wantNode = innerMin > 0 ? innerMin : (static_cast<int>(__popcll(innerMask | leafMask)) * -innerMin + 7) / 8;
+    if (innerMask != 0ull && (leafMask == 0ull || static_cast<int>(__popcll(innerMask)) >= wantNode)) {
+        CRT_NODE_STEPS(anyStep)
+        return;
+    }
+    if (L::leaf(cur)) {
+        uint32_t first, cnt;
+        L::leafRange(cur, first, cnt);
+        for (uint32_t i = 0; i < cnt; i++) {
+            const uint32_t id = L::triId(first, i);
+            const float4* T = L::triPtr(tris, id);
+            const float4 a = T[0], b = T[1], c = T[2];
+            if (COUNT) cntTris++;
+            float t, u, v;
+            if (triTest<false>(r, a, b, c, tmin, t, u, v) & (t < tmax)) {
+                if (k < room) {
+                    tkey[base + k] = t;
+                    idkey[base + k] = id;
+                }
+                k++;
+            }
+        }
+        cur = stack.sp == 0 ? L::kDone : stack.pop();
+    }
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LayLegacy::kWavesPerEu, 8))) void listFillKernel(const ListParams q)
+{
+    using L = LayLegacy;
+    extern __shared__ int s_stack[]; // stack_entries x 64 dwords
+    if (q.offsets[q.n] > q.capacity) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const float4* nodes = reinterpret_cast<const float4*>(q.nodes);
+    const float4* tris = reinterpret_cast<const float4*>(q.tris);
+    const float4* recs = reinterpret_cast<const float4*>(q.rays);
+    Stack stack;
+    stack.lds = s_stack + lane;
+    stack.spill = q.spill + (static_cast<size_t>(blockIdx.x) * 64u + lane) * q.spill_stride;
+    stack.cap = static_cast<int>(q.stack_entries);
+    stack.sp = 0;
+    const int innerMin = static_cast<int>(q.inner_min);
+
+    Ray r = makeRay(f3(0.0f, 0.0f, 0.0f), f3(0.0f, 0.0f, 1.0f));
+    float tmin = 0.0f, tmax = 0.0f, tcull = 0.0f;
+    unsigned long long base = 0;
+    uint32_t room = 0, k = 0;
+    int cur = L::kDone;
+    bool have = false;
+    uint32_t cntNodes = 0, cntTris = 0;
+    RayTap tap;
+    tap.begin(q.n, q.chunk);
+    const unsigned long long all = __ballot(true);
+    for (;;) {
+        const bool idle = cur == L::kDone;
+        const unsigned long long idleMask = __ballot(idle);
+        if (idleMask == all || (tap.more() && static_cast<uint32_t>(__popcll(idleMask)) >= static_cast<uint32_t>(CRT_REFILL_MIN))) {
+            // a finished ray has nothing to retire: its records are in place
+            bool valid = false;
+            const uint32_t idx = tap.take(q.cursor, q.n, q.chunk, idleMask, valid);
+            if (idle) {
+                have = valid;
+                if (valid) {
+                    base = q.offsets[idx];
+                    room = static_cast<uint32_t>(q.offsets[static_cast<size_t>(idx) + 1u] - base);
+                    k = 0;
+                    stack.sp = 0;
+                    const float4 a = recs[2u * static_cast<size_t>(idx)], b = recs[2u * static_cast<size_t>(idx) + 1u];
+                    queryRay(a, b, r, tmin, tmax); // prescaled, as the ray queries
+                    tcull = cullBound(tmax);
+                    // a record with a NaN (or an empty interval) is not traced: no crossings
+                    const bool ok = (a.x == a.x) & (a.y == a.y) & (a.z == a.z) & (b.x == b.x) & (b.y == b.y) & (b.z == b.z) & (tmin < tmax) &
+                                    (q.n_nodes != 0u);
+                    cur = ok ? L::kRoot : L::kDone;
+                }
+            }
+            if (__ballot(have) == 0ull && !tap.more()) break;
+        }
+        listIteration<COUNT, L, 8>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, q.tkey, q.idkey, base, room, k, cur, cntNodes, cntTris);
+    }
+    if (COUNT) {
+        const uint32_t a = waveTotal(cntNodes), c = waveTotal(cntTris);
+        if (lane == 0) {
+            atomicAdd(&q.counters[0], static_cast<unsigned long long>(a));
+            atomicAdd(&q.counters[1], static_cast<unsigned long long>(c));
+        }
+    }
+}
+
+// ---- sort and resolve
+
+__device__ __forceinline__ uint32_t gidOf(const float4* tris, uint32_t id) { return __float_as_uint(LayLegacy::triPtr(tris, id)[2].w); }
+
+// (ta, ia) sorts before (tb, ib): t' as floats (-0 == +0), equal t' by global triangle id
+__device__ __forceinline__ bool listBefore(float ta, uint32_t ia, float tb, uint32_t ib, const float4* tris)
+{
+    return (ta < tb) || ((ta == tb) && (gidOf(tris, ia) < gidOf(tris, ib)));
+}
+
+// ascending compare-exchange of records lo < hi of a key array pair (LDS or global)
+__device__ __forceinline__ void listCmpSwap(float* tk, uint32_t* ik, size_t lo, size_t hi, const float4* tris)
+{
+    const float ta = tk[lo], tb = tk[hi];
+    const uint32_t ia = ik[lo], ib = ik[hi];
+    if (listBefore(tb, ib, ta, ia, tris)) {
+        tk[lo] = tb; tk[hi] = ta;
+        ik[lo] = ib; ik[hi] = ia;
+    }
+}
+
+struct ListRay {
+    Ray r;
+    float tmin;
+    int e;
+};
+
+__device__ __forceinline__ ListRay listRay(const ListParams& q, uint32_t ray)
+{
+    const float4* recs = reinterpret_cast<const float4*>(q.rays);
+    const float4 a = recs[2u * static_cast<size_t>(ray)], b = recs[2u * static_cast<size_t>(ray) + 1u];
+    ListRay lr;
+    float tmax;
+    lr.e = queryRay(a, b, lr.r, lr.tmin, tmax);
+    return lr;
+}
+
+// record j of the outputs from the sorted work arrays.  tkey / idkey may be the t / prim outputs themselves: a record is read
+// before it is written, by the one thread that resolves it.
+__device__ __forceinline__ void listResolve(const ListParams& q, const float4* tris, const ListRay& lr, unsigned long long j)
+{
+    const float tp = q.tkey[j];
+    const uint32_t id = q.idkey[j];
+    const float4* T = LayLegacy::triPtr(tris, id);
+    const float4 a = T[0], b = T[1], c = T[2];
+    if (q.t) q.t[j] = __builtin_amdgcn_ldexpf(tp, -lr.e);
+    if (q.uv) {
+        float t, u, v;
+        (void)triTest<false>(lr.r, a, b, c, lr.tmin, t, u, v);
+        reinterpret_cast<float2*>(q.uv)[j] = make_float2(u, v);
+    }
+    if (q.inst) q.inst[j] = __float_as_uint(a.w); // v0.w = mesh ordinal
+    if (q.prim) q.prim[j] = __float_as_uint(b.w); // e1.w = triangle of the mesh
+}
+
+// one lane per ray: segments of 1 .. short_max records; longer ones are queued for listSortLongKernel
+__global__ __launch_bounds__(256) void listSortShortKernel(const ListParams q)
+{
+    if (q.offsets[q.n] > q.capacity) return;
+    const unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= q.n) return;
+    const unsigned long long lo = q.offsets[i];
+    const unsigned long long len = q.offsets[i + 1u] - lo;
+    if (len == 0ull) return;
+    if (len > q.short_max) {
+        q.longRays[atomicAdd(q.longCount, 1u)] = static_cast<uint32_t>(i);
+        return;
+    }
+    const float4* tris = reinterpret_cast<const float4*>(q.tris);
+    float* tk = q.tkey + lo;
+    uint32_t* ik = q.idkey + lo;
+    const uint32_t cnt = static_cast<uint32_t>(len);
+    for (uint32_t j = 1; j < cnt; j++) {
+        const float tj = tk[j];
+        const uint32_t ij = ik[j];
+        uint32_t m = j;
+        while (m > 0u && listBefore(tj, ij, tk[m - 1u], ik[m - 1u], tris)) {
+            tk[m] = tk[m - 1u];
+            ik[m] = ik[m - 1u];
+            m--;
+        }
+        tk[m] = tj;
+        ik[m] = ij;
+    }
+    const ListRay lr = listRay(q, static_cast<uint32_t>(i));
+    for (uint32_t j = 0; j < cnt; j++) listResolve(q, tris, lr, lo + j);
+}
+
+// One wavefront per queued ray.  The network: for block sizes k = 2, 4, ... the "flip" step (record i of a block's lower half
+// against its mirror i ^ (k - 1)) and then the strides k / 4 .. 1 (i against i + j), every comparator ascending.  Such a
+// network sorts any length: a comparator whose upper record lies beyond the segment is skipped, which is what padding with
+// +inf records would do.  Blocks up to kSortTile sort inside LDS tile by tile; for larger blocks the flip and the strides
+// >= kSortTile run over global memory and the remaining strides again in LDS.
+constexpr uint32_t kSortTile = 1024;
+
+__device__ __forceinline__ void listTileSteps(float* tk, uint32_t* ik, uint32_t live, uint32_t jFirst, uint32_t lane, const float4* tris)
+{
+    for (uint32_t j = jFirst; j > 0u; j >>= 1) {
+        for (uint32_t p = lane; p < kSortTile / 2u; p += 64u) {
+            const uint32_t i = ((p & ~(j - 1u)) << 1) | (p & (j - 1u));
+            if (i + j < live) listCmpSwap(tk, ik, i, i + j, tris);
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(64) void listSortLongKernel(const ListParams q)
+{
+    __shared__ float s_t[kSortTile];
+    __shared__ uint32_t s_id[kSortTile];
+    if (q.offsets[q.n] > q.capacity) return;
+    const uint32_t lane = threadIdx.x;
+    const float4* tris = reinterpret_cast<const float4*>(q.tris);
+    const uint32_t nLong = *q.longCount;
+    for (uint32_t w = blockIdx.x; w < nLong; w += gridDim.x) {
+        const uint32_t ray = q.longRays[w];
+        const unsigned long long lo = q.offsets[ray];
+        const unsigned long long len = q.offsets[static_cast<size_t>(ray) + 1u] - lo; // a ray's count is a uint32
+        float* tk = q.tkey + lo;
+        uint32_t* ik = q.idkey + lo;
+        // blocks up to a tile: everything in LDS
+        for (unsigned long long tb = 0; tb < len; tb += kSortTile) {
+            const uint32_t live = static_cast<uint32_t>(len - tb < kSortTile ? len - tb : kSortTile);
+            for (uint32_t x = lane; x < live; x += 64u) { s_t[x] = tk[tb + x]; s_id[x] = ik[tb + x]; }
+            __syncthreads();
+            for (uint32_t k = 2; k <= kSortTile && (k >> 1) < live; k <<= 1) {
+                for (uint32_t p = lane; p < kSortTile / 2u; p += 64u) {
+                    const uint32_t h = k >> 1, i = ((p & ~(h - 1u)) << 1) | (p & (h - 1u)), m = i ^ (k - 1u);
+                    if (m < live) listCmpSwap(s_t, s_id, i, m, tris);
+                }
+                __syncthreads();
+                listTileSteps(s_t, s_id, live, k >> 2, lane, tris);
+            }
+            for (uint32_t x = lane; x < live; x += 64u) { tk[tb + x] = s_t[x]; ik[tb + x] = s_id[x]; }
+            __syncthreads();
+        }
+        // larger blocks
+        for (unsigned long long k = 2ull * kSortTile; (k >> 1) < len; k <<= 1) {
+            const unsigned long long h = k >> 1;
+            for (unsigned long long p = lane;; p += 64u) {
+                const unsigned long long i = ((p & ~(h - 1ull)) << 1) | (p & (h - 1ull)), m = i ^ (k - 1ull); // i grows with p
+                if (i >= len) break;
+                if (m < len) listCmpSwap(tk, ik, i, m, tris);
+            }
+            __syncthreads();
+            for (unsigned long long j = k >> 2; j >= kSortTile; j >>= 1) {
+                for (unsigned long long p = lane;; p += 64u) {
+                    const unsigned long long i = ((p & ~(j - 1ull)) << 1) | (p & (j - 1ull));
+                    if (i >= len) break;
+                    if (i + j < len) listCmpSwap(tk, ik, i, i + j, tris);
+                }
+                __syncthreads();
+            }
+            for (unsigned long long tb = 0; tb < len; tb += kSortTile) {
+                const uint32_t live = static_cast<uint32_t>(len - tb < kSortTile ? len - tb : kSortTile);
+                for (uint32_t x = lane; x < live; x += 64u) { s_t[x] = tk[tb + x]; s_id[x] = ik[tb + x]; }
+                __syncthreads();
+                listTileSteps(s_t, s_id, live, kSortTile >> 1, lane, tris);
+                for (uint32_t x = lane; x < live; x += 64u) { tk[tb + x] = s_t[x]; ik[tb + x] = s_id[x]; }
+                __syncthreads();
+            }
+        }
+        const ListRay lr = listRay(q, ray);
+        for (unsigned long long j = lane; j < len; j += 64u) listResolve(q, tris, lr, lo + j);
+        __syncthreads();
+    }
+}
+
+size_t listLds(uint32_t stack_entries) { return static_cast<size_t>(stack_entries) * 64u * sizeof(int); }
+
+} // namespace
+
+size_t listScanScratchBytes(uint32_t n) { return sizeof(unsigned long long) * listTiles(n); }
+
+int launchListScan(const uint32_t* counts, uint32_t n, unsigned long long* offsets, unsigned long long* tileSums, ihipStream_t* stream)
+{
+    const uint32_t nTiles = listTiles(n);
+    hipError_t e;
+    hipLaunchKernelGGL(listTileSumKernel, dim3(nTiles), dim3(kScanThreads), 0, stream, counts, n, tileSums);
+    if ((e = hipGetLastError()) != hipSuccess) return static_cast<int>(e);
+    hipLaunchKernelGGL(listScanSumsKernel, dim3(1), dim3(kSumThreads), 0, stream, tileSums, nTiles);
+    if ((e = hipGetLastError()) != hipSuccess) return static_cast<int>(e);
+    hipLaunchKernelGGL(listTileScanKernel, dim3(nTiles), dim3(kScanThreads), 0, stream, counts, n, tileSums, offsets);
+    return static_cast<int>(hipGetLastError());
+}
+
+// resident workgroups of the persistent fill kernel on the current device (as pointQueryResident); the caller caches it
+uint32_t listFillResident(uint32_t stack_entries)
+{
+    int dev = 0, cus = 0, perCu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, reinterpret_cast<const void*>(&listFillKernel<false>), 64, listLds(stack_entries)) != hipSuccess ||
+        perCu <= 0 || cus <= 0)
+        return 0u;
+    const int most = 4 * kListMaxWavesPerSimd;
+    return static_cast<uint32_t>(perCu > most ? most : perCu) * static_cast<uint32_t>(cus);
+}
+
+int launchListFill(const ListParams& q, bool counting, uint32_t grid, ihipStream_t* stream)
+{
+    if (q.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
+    if (counting) hipLaunchKernelGGL((listFillKernel<true>), dim3(grid), dim3(64), listLds(q.stack_entries), stream, q);
+    else hipLaunchKernelGGL((listFillKernel<false>), dim3(grid), dim3(64), listLds(q.stack_entries), stream, q);
+    return static_cast<int>(hipGetLastError());
+}
+
+int launchListSort(const ListParams& q, ihipStream_t* stream)
+{
+    if (q.n == 0u) return static_cast<int>(hipSuccess);
+    const uint32_t blocks = static_cast<uint32_t>((static_cast<unsigned long long>(q.n) + 255u) / 256u);
+    hipLaunchKernelGGL(listSortShortKernel, dim3(blocks), dim3(256), 0, stream, q);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return static_cast<int>(e);
+    hipLaunchKernelGGL(listSortLongKernel, dim3(2048), dim3(64), 0, stream, q);
+    return static_cast<int>(hipGetLastError());
+}
+
+} // namespace crt

@@ -287,7 +287,9 @@ __global__ __launch_bounds__(64) void closestPointKernel(const PointQueryParams 
 }
 
 // One scheduling decision of the counting traversal: anyIteration's node steps; a leaf counts every triangle the
-// Moeller-Trumbore test accepts in (tmin, tmax) and the lane goes on with its stack (no early exit)
+// Moeller-Trumbore test accepts in (tmin, tmax) and the lane goes on with its stack (no early exit).
+// listIteration (list_kernels.hip) is this function with a store in place of the increment, and crt_list_hits* relies on the
+// two accepting the same triangles: change them together.
 template <bool COUNT, class L, int OCT, bool DEC = false>
 __device__ __forceinline__ void countIteration(const float4* __restrict__ nodes, const float4* __restrict__ tris, const Ray& r, float tmin, float tmax,
                                                float tcull, Stack& stack, int innerMin, uint32_t& hits, int& cur, uint32_t& cntNodes,

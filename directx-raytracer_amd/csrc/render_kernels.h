@@ -180,6 +180,42 @@ struct PointQueryParams {
 inline uint32_t pointQueryEntryWords(PointQueryKind kind) { return kind == kPointClosest ? 2u : 1u; }
 uint32_t pointQueryResident(PointQueryKind kind, uint32_t stack_entries);
 int launchPointQuery(const PointQueryParams& q, PointQueryKind kind, bool counting, uint32_t grid, ihipStream_t* stream);
+// all-hits listing (list_kernels.hip; crt_list_hits*): after the hit counts of launchPointQuery(kPointCount), the exclusive
+// sum of the counts into 64-bit offsets, a second traversal that writes every accepted hit into its ray's segment, and the
+// sort + resolve of every segment.  The three later steps read offsets[n] on the device and leave when it exceeds capacity.
+struct ListParams {
+    const void* nodes;            // as RayQueryParams
+    const void* tris;
+    uint32_t n_nodes;
+    const void* rays;             // n x 32 bytes, 16-byte aligned
+    uint32_t n;
+    const unsigned long long* offsets; // n + 1, written by launchListScan
+    unsigned long long capacity;  // records every record array holds
+    float* tkey;                  // work arrays of `capacity` records: a hit's prescaled t' and its leaf-order triangle record.
+    uint32_t* idkey;              // They may be the caller's t and prim arrays (resolved in place) or scratch.
+    float* t;                     // outputs, each nullable
+    float* uv;
+    uint32_t* inst;
+    uint32_t* prim;
+    uint32_t* longRays;           // n entries (the count buffer, free once the offsets exist): rays left to the wavefront sort
+    uint32_t* longCount;          // their number, zeroed on the stream before the launches
+    uint32_t short_max;           // segments up to this length are sorted by one lane
+    uint32_t* cursor;             // as RayQueryParams
+    unsigned long long* counters;
+    int* spill;
+    uint32_t spill_stride;
+    uint32_t stack_entries;
+    uint32_t inner_min;
+    uint32_t chunk;
+};
+// bytes of the scan's scratch (64-bit tile sums) for n counts
+size_t listScanScratchBytes(uint32_t n);
+// counts[0..n) -> offsets[0..n], offsets[n] = the total
+int launchListScan(const uint32_t* counts, uint32_t n, unsigned long long* offsets, unsigned long long* tileSums, ihipStream_t* stream);
+uint32_t listFillResident(uint32_t stack_entries);
+int launchListFill(const ListParams& q, bool counting, uint32_t grid, ihipStream_t* stream);
+// sorts every segment by (t', global id) and resolves the records into the outputs
+int launchListSort(const ListParams& q, ihipStream_t* stream);
 // exhaustive check of the triangle test's reciprocal (ray_kernels.hip rcpCheckKernel) into out[0..6] (device memory, zeroed
 // except out[6] = ~0 by the caller)
 int launchRcpCheck(unsigned long long* out, ihipStream_t* stream);

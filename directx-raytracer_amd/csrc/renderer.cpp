@@ -152,6 +152,22 @@ void Renderer::traceRays(const float* rays, size_t n, RayHit* out)
     for (size_t i = 0; i < n; i++) out[i] = RayHit{ t[i], uv[2 * i], uv[2 * i + 1], inst[i], prim[i] };
 }
 
+void Renderer::listHits(const float* rays, size_t n, std::vector<uint64_t>& offsets, std::vector<RayHit>& hits)
+{
+    if (!ctx) throw std::runtime_error("listHits before prepareForRendering");
+    if (n > UINT32_MAX) throw std::runtime_error("listHits: more than 2^32 - 1 rays");
+    const uint32_t m = static_cast<uint32_t>(n);
+    offsets.assign(n + 1, 0);
+    uint64_t total = 0;
+    check(crt_list_hits(ctx, m, rays, offsets.data(), 0, nullptr, nullptr, nullptr, nullptr, &total, nullptr), "crt_list_hits");
+    hits.resize(total);
+    if (total == 0) return;
+    std::vector<float> t(total), uv(2 * total);
+    std::vector<uint32_t> inst(total), prim(total);
+    check(crt_list_hits(ctx, m, rays, offsets.data(), total, t.data(), uv.data(), inst.data(), prim.data(), &total, nullptr), "crt_list_hits");
+    for (size_t i = 0; i < hits.size(); i++) hits[i] = RayHit{ t[i], uv[2 * i], uv[2 * i + 1], inst[i], prim[i] };
+}
+
 void Renderer::occluded(const float* rays, size_t n, uint8_t* out)
 {
     if (!ctx) throw std::runtime_error("occluded before prepareForRendering");

@@ -56,6 +56,9 @@ public:
     };
     void traceRays(const float* rays, size_t n, RayHit* out);
     void occluded(const float* rays, size_t n, uint8_t* out); // 1 = some triangle lies in (tmin, tmax)
+    // every crossing of every ray, ascending in t (crt_list_hits, synchronous): the hits of ray i are hits[offsets[i]] ..
+    // hits[offsets[i + 1] - 1].  One offsets-only call learns the total, a second one fills the records.
+    void listHits(const float* rays, size_t n, std::vector<uint64_t>& offsets, std::vector<RayHit>& hits);
 
     // dynamic geometry (crt_update_vertices / crt_set_mesh_transform, include/crt_hip.h): enable before prepareForRendering, whose
     // upload then keeps what a refit needs.  Updates are applied before the next frame or ray query.

@@ -252,7 +252,7 @@ int crt_render_frame_distributed(crt_ctx* ctx, uint32_t width, uint32_t height, 
  * stages; its queues hold "path_pass_paths" paths per pass (65536..2^25, default 2^24 = 1.9 GB), a frame with more is rendered in
  * several passes), "path_ranges" (mode 200: 8 (default) = the
  * work items are cut into eight contiguous ranges and a wavefront works through the range of the XCD it runs on before taking from the others', 1 = one shared work counter), "stack_entries" (0 = default 16; deeper entries spill to a
- * global arena). The diagnostic options "timeline", "debug_skip_units" and "debug_force_measure" (which do change what a frame
+ * global arena), "list_short_max" (crt_list_hits*: 1..1024, default 24: lists up to this many hits are sorted by one lane, longer ones by a wavefront). The diagnostic options "timeline", "debug_skip_units" and "debug_force_measure" (which do change what a frame
  * does) exist only in the diagnostic build of the library (tools/diag_build.sh); the product returns CRT_EINVAL for them. */
 int crt_set_option(crt_ctx* ctx, const char* name, int value);
 
@@ -262,6 +262,9 @@ int crt_debug_read_timeline(crt_ctx* ctx, unsigned long long* out, size_t max_wo
 /* raw device counters of the last counting render: [0] nodes [1] triangles [2] shadow rays [3] closest-hit rays; [4..31]
  * are filled only by the CRT_PROF diagnostic build of the kernels (tools/prof_build.sh, meanings in tools/prof_run.py) */
 int crt_debug_read_counters(crt_ctx* ctx, unsigned long long out[32]);
+/* HIP-event times in ms of the phases of the last crt_list_hits* call that was given stats: [0] count, [1] scan, [2] fill,
+ * [3] sort + resolve (fill and sort 0 when the records were not written).  Their sum is that call's kernel_ms less the gaps. */
+int crt_debug_list_phases(crt_ctx* ctx, double out_ms[4]);
 /* self-check of the device arithmetic the triangle test relies on: its short reciprocal against the correctly rounded
  * 1.0f / d for all 2^32 inputs, on device device_id.  out[0] mismatches (0 expected), [1] inputs checked (2^32), [2..5]
  * mismatches of the unguarded Newton form by class (biased exponent 0 / 253..255 / all-ones significand / the rest), [6]
@@ -443,6 +446,57 @@ int crt_count_hits_device(crt_ctx* ctx, uint32_t n, const void* d_rays, void* d_
 int crt_count_hits(crt_ctx* ctx, uint32_t n, const float* rays, uint32_t* count, crt_frame_stats* stats);
 int crt_occupancy_device(crt_ctx* ctx, uint32_t n, const void* d_points, void* d_inside, crt_frame_stats* stats);
 int crt_occupancy(crt_ctx* ctx, uint32_t n, const float* points, uint8_t* inside, crt_frame_stats* stats);
+
+/* ---- all-hits ray queries: every crossing of a ray, sorted by distance (Open3D's list_intersections, Embree's rtcIntersect with
+ * an all-hits filter, the any-hit shader of DXR).  Wall thickness and chord lengths, layered depth images, inside / outside with
+ * the evidence attached, multi-return sensor casts.
+ * - Rays: the 8-float records of crt_trace_rays, with the same NaN / empty-interval / zero-direction rules and the same
+ *   direction-magnitude contract (traced prescaled by 2^e).
+ * - Which hits: exactly the triangles crt_count_hits counts for that record: every triangle the ray queries' Moeller-Trumbore
+ *   test accepts with tmin < t < tmax, no early exit, no culling against a best t.  offsets[i + 1] - offsets[i] is the count
+ *   crt_count_hits reports for record i, for every ray, always.
+ * - Layout (CSR): offsets[0] = 0, offsets[i] = number of hits of rays 0 .. i-1, offsets[n] = the total; uint64 values below
+ *   2^63 (a torch.int64 tensor can receive them).  The hits of ray i are records offsets[i] .. offsets[i+1]-1 of the four
+ *   record arrays: t (float, reported as t' 2^-e like crt_trace_rays), uv (2 floats, u = weight of v1, v = weight of v2),
+ *   inst, prim (uint32: mesh ordinal and triangle of that mesh).  Each may be NULL; all four NULL makes the call an
+ *   offsets-only call.
+ * - Order inside a ray: ascending prescaled t' compared as floats; records of equal t' (==, so -0 and +0 are equal) in
+ *   ascending global triangle id (upload ordinal), the frames' and the closest-hit query's tie rule.  A triangle sits in one
+ *   leaf, so the order is total.  For a ray with hits, record offsets[i] is bit for bit the closest hit crt_trace_rays
+ *   reports (t, u, v, inst, prim), boundary rays excepted.
+ * - Capacity: `capacity` is the number of records each non-NULL record array can hold (ignored when all four are NULL).  The
+ *   offsets are always written.  The records are written only if offsets[n] <= capacity; otherwise no byte of the four arrays
+ *   is touched.  The call returns CRT_OK in both cases (too small a buffer is an answer, not an error) and *total =
+ *   offsets[n] when total != NULL: the caller compares, allocates and calls again.  The decision is made on the device (the
+ *   fill and sort kernels read offsets[n] and leave when it exceeds the capacity they were given).
+ * - Asynchrony: the device form is asynchronous on the context's stream when total == NULL && stats == NULL; with either
+ *   given it synchronises.  The host form is synchronous and staged; it reads the total back once between the count and the
+ *   fill, traverses once when the records do not fit (or none are wanted) and copies no record array out then.
+ * - Independence: results do not depend on the tree (host SAH, gpu_build LBVH or PLOC, refitted, rebuilt), on the order of
+ *   the records, on scheduling, or on inner_min / inner_min_any / stack_entries / list_short_max.  The "boundary rays" limit
+ *   of the ray queries applies unchanged and is the only exception, as for crt_count_hits.
+ * - Common rules of the queries: pending refits are applied first; camera, mode, accumulation sums, launch orders and frame
+ *   outputs are untouched; n = 0 returns CRT_OK and launches nothing (the host form writes offsets[0] = 0 when offsets !=
+ *   NULL, the device form looks at no buffer; *total = 0); CRT_ESTATE without a scene; CRT_EINVAL for a NULL ctx, for NULL rays
+ *   or offsets with n > 0, and for misaligned device pointers (rays 16-byte, offsets 8-byte, uv 8-byte, t / inst / prim
+ *   4-byte).  A failed call launches nothing: these checks come before pending refits are applied.
+ * - How: two traversals.  The hit count into a context-owned buffer, an exclusive sum into the offsets, the same traversal
+ *   again writing each accepted hit (t', triangle record) into its ray's segment, a sort of every segment (one lane per ray
+ *   up to option "list_short_max" records, default 24, speed only; one wavefront per longer ray) and a resolve pass that
+ *   re-runs the triangle test for u, v as the closest-hit query does at retirement.
+ * - stats: kernel_ms = all kernels of the call (count, scan, fill, sort; the host form's figure spans its read-back too),
+ *   rays_primary = n.  With crt_set_counting(ctx, 1), nodes_visited / tris_tested are the records fetched by both traversals:
+ *   exactly twice what crt_count_hits reports for the same buffer when the records are written, exactly once when they are not
+ *   (offsets-only call, total above capacity, total = 0 in the host form).  The triangle records re-read by the sort's tie
+ *   rule and by the resolve pass are not counted.
+ * - Temporary memory is context-owned and grows on demand: n uint32 counts plus the scan's tile sums, per stream in use.  The
+ *   device form adds 4 B x capacity for each of t and prim the caller did not supply while asking for another array (the sort
+ *   keys live in those two arrays), allocated before anything is launched; CRT_ENOMEM if that fails, with nothing launched. */
+int crt_list_hits_device(crt_ctx* ctx, uint32_t n, const void* d_rays, void* d_offsets /* (n + 1) x uint64 */, uint64_t capacity,
+                         void* d_t, void* d_uv, void* d_inst, void* d_prim, uint64_t* total /* host, may be NULL */,
+                         crt_frame_stats* stats);
+int crt_list_hits(crt_ctx* ctx, uint32_t n, const float* rays, uint64_t* offsets, uint64_t capacity, float* t, float* uv,
+                  uint32_t* inst, uint32_t* prim, uint64_t* total, crt_frame_stats* stats);
 
 /* ---- dynamic geometry (DXR: acceleration-structure updates and D3D12_RAYTRACING_INSTANCE_DESC::Transform, which the reference
  * fills with the identity for every mesh, R/DXRTRenderer.cpp:690-704).  Opt-in: crt_set_option(ctx, "dynamic", 1) before
