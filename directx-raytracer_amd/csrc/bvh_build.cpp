@@ -318,6 +318,7 @@ void flattenMeshes(const crt_mesh_view* meshes, uint32_t n_meshes, std::vector<c
             const float* C = M.xyz + 3 * static_cast<size_t>(i2);
             crt_bvh_tri& T = inTri[g];
             float* bc = &boxCent[9 * static_cast<size_t>(g)];
+            bool finite = true;
             for (int k = 0; k < 3; k++) {
                 T.v0[k] = A[k];
                 T.e1[k] = B[k] - A[k];
@@ -325,6 +326,17 @@ void flattenMeshes(const crt_mesh_view* meshes, uint32_t n_meshes, std::vector<c
                 bc[k] = fmin_sel(fmin_sel(A[k], B[k]), C[k]);
                 bc[3 + k] = fmax_sel(fmax_sel(A[k], B[k]), C[k]);
                 bc[6 + k] = (bc[k] + bc[3 + k]) * 0.5f;
+                finite &= A[k] - A[k] == 0.0f && B[k] - B[k] == 0.0f && C[k] - C[k] == 0.0f; // x - x == 0: finite
+            }
+            // an inert triangle (crt_hip.h): box and centroid are the point (0, 0, 0), so the builders see finite numbers
+            // only; its record is nine quiet NaNs of one bit pattern (what B - A makes of a NaN's sign depends on the
+            // compiler), which no intersection routine accepts
+            if (!finite) {
+                const uint32_t qnanBits = 0x7FC00000u;
+                float qnan;
+                crt::copyBytes(&qnan, &qnanBits, 4);
+                for (int k = 0; k < 9; k++) bc[k] = 0.0f;
+                for (int k = 0; k < 3; k++) T.v0[k] = T.e1[k] = T.e2[k] = qnan;
             }
             T.inst = m;
             T.prim = t;

@@ -255,11 +255,15 @@ __global__ __launch_bounds__(256) void triBoxKernel(const MeshEntry* __restrict_
     const float* A = xyz + 3 * static_cast<size_t>(M.vertStart + i0);
     const float* B = xyz + 3 * static_cast<size_t>(M.vertStart + i1);
     const float* C = xyz + 3 * static_cast<size_t>(M.vertStart + i2);
+    bool finite = true;
     for (int k = 0; k < 3; k++) {
         b.mn[k] = minSel(minSel(A[k], B[k]), C[k]);
         b.mx[k] = maxSel(maxSel(A[k], B[k]), C[k]);
-        cent[3 * static_cast<size_t>(g) + k] = (b.mn[k] + b.mx[k]) * 0.5f;
+        finite &= A[k] - A[k] == 0.0f && B[k] - B[k] == 0.0f && C[k] - C[k] == 0.0f; // x - x == 0: finite
     }
+    if (!finite) // an inert triangle (crt_hip.h): the point (0, 0, 0), as flattenMeshes gives it
+        for (int k = 0; k < 3; k++) { b.mn[k] = 0.0f; b.mx[k] = 0.0f; }
+    for (int k = 0; k < 3; k++) cent[3 * static_cast<size_t>(g) + k] = (b.mn[k] + b.mx[k]) * 0.5f;
     box[g] = b;
 }
 
@@ -281,11 +285,15 @@ __global__ __launch_bounds__(256) void gatherKernel(const unsigned long long* __
     const float* B = xyz + 3 * static_cast<size_t>(v1);
     const float* C = xyz + 3 * static_cast<size_t>(v2);
     crt_bvh_tri T;
+    bool finite = true;
     for (int k = 0; k < 3; k++) {
         T.v0[k] = A[k];
         T.e1[k] = B[k] - A[k];
         T.e2[k] = C[k] - A[k];
+        finite &= A[k] - A[k] == 0.0f && B[k] - B[k] == 0.0f && C[k] - C[k] == 0.0f; // x - x == 0: finite
     }
+    if (!finite) // an inert triangle (crt_hip.h): nine quiet NaNs of one bit pattern, as flattenMeshes writes them
+        for (int k = 0; k < 3; k++) T.v0[k] = T.e1[k] = T.e2[k] = __uint_as_float(0x7FC00000u);
     T.inst = m;
     T.prim = g - M.triStart;
     T.gid = g;

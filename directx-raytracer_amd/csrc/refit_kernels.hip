@@ -63,10 +63,13 @@ __global__ __launch_bounds__(256) void recordsKernel(const MeshEntry* __restrict
     const float* A = xyz + 3 * static_cast<size_t>(v0);
     const float* B = xyz + 3 * static_cast<size_t>(v1);
     const float* C = xyz + 3 * static_cast<size_t>(v2);
+    bool finite = true;
+    for (int k = 0; k < 3; k++) finite &= A[k] - A[k] == 0.0f && B[k] - B[k] == 0.0f && C[k] - C[k] == 0.0f; // x - x == 0: finite
+    const float qnan = __uint_as_float(0x7FC00000u); // an inert triangle's record (crt_hip.h), as gatherKernel writes it
     for (int k = 0; k < 3; k++) {
-        tris[i].v0[k] = A[k];
-        tris[i].e1[k] = B[k] - A[k];
-        tris[i].e2[k] = C[k] - A[k];
+        tris[i].v0[k] = finite ? A[k] : qnan;
+        tris[i].e1[k] = finite ? B[k] - A[k] : qnan;
+        tris[i].e2[k] = finite ? C[k] - A[k] : qnan;
     }
     if (M.hasNormals)
         for (int k = 0; k < 3; k++) {
@@ -114,9 +117,13 @@ __global__ __launch_bounds__(256) void refitLevelKernel(const uint32_t* __restri
             const float* P = xyz + 3 * static_cast<size_t>(M.vertStart + idx[3 * static_cast<size_t>(g)]);
             const float* Q = xyz + 3 * static_cast<size_t>(M.vertStart + idx[3 * static_cast<size_t>(g) + 1]);
             const float* R = xyz + 3 * static_cast<size_t>(M.vertStart + idx[3 * static_cast<size_t>(g) + 2]);
-            for (int a = 0; a < 3; a++) {
-                B.mn[a] = minSel(B.mn[a], minSel(minSel(P[a], Q[a]), R[a]));
-                B.mx[a] = maxSel(B.mx[a], maxSel(maxSel(P[a], Q[a]), R[a]));
+            bool finite = true;
+            for (int a = 0; a < 3; a++) finite &= P[a] - P[a] == 0.0f && Q[a] - Q[a] == 0.0f && R[a] - R[a] == 0.0f; // x - x == 0: finite
+            for (int a = 0; a < 3; a++) { // an inert triangle (crt_hip.h) counts as the point (0, 0, 0), as in triBoxKernel
+                const float lo = finite ? minSel(minSel(P[a], Q[a]), R[a]) : 0.0f;
+                const float hi = finite ? maxSel(maxSel(P[a], Q[a]), R[a]) : 0.0f;
+                B.mn[a] = minSel(B.mn[a], lo);
+                B.mx[a] = maxSel(B.mx[a], hi);
             }
         }
     }

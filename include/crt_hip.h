@@ -339,6 +339,25 @@ int crt_set_accumulation(crt_ctx* ctx, uint32_t max_samples); /* 0 = off (defaul
 int crt_reset_accumulation(crt_ctx* ctx);                      /* drop the sums; the next frame starts at sample 0 */
 int crt_accumulated_samples(const crt_ctx* ctx, uint32_t* samples); /* samples per pixel in the current sums (0 when off or reset) */
 
+/* ---- non-finite vertices (inert triangles).  A triangle with a NaN or an infinity among its nine vertex coordinates, as traced
+ * (world space for a dynamic scene: a diverged solver's output handed to crt_update_vertices*, finite rest vertices that a
+ * crt_set_mesh_transform carries past FLT_MAX), is inert:
+ * - no frame, ray query, occlusion query, hit count, all-hits list, occupancy or closest-point query ever reports it;
+ * - every result equals the result for the same scene with the inert triangles absent; inst, prim and the global ids of all
+ *   other triangles are unchanged (an inert triangle keeps its place in the numbering and in the leaf-ordered records);
+ * - this holds over every tree -- host SAH, gpu_build LBVH or PLOC, after crt_refit, after crt_rebuild with either builder --
+ *   with the "boundary rays" limit of the ray queries as the only exception, as for finite scenes;
+ * - uploads, refits and rebuilds of such scenes succeed (PLOC included), and crt_mesh_vertices returns the non-finite values
+ *   as they are.
+ * How: where a triangle's box and centroid are taken (every builder, the refit), a triangle with a coordinate x that fails
+ * x - x == 0 is the point (0, 0, 0), so no box, Morton code, SAH bin or quantised plane is ever computed from a non-finite
+ * number and the boxes above a leaf always hold its finite triangles.  Its leaf-ordered record keeps inst / prim / gid and
+ * holds nine quiet NaNs (bits 0x7FC00000) as v0 / e1 / e2, whoever writes it (host build, GPU build, refit, rebuild): the sign
+ * that e = v1 - v0 gives a NaN differs between compilers and between host and device code, and the exported bytes must not
+ * depend on that.  The Moeller-Trumbore test and the closest-point routine reject such a record by themselves (every
+ * comparison with a NaN is false).  A scene of finite vertices gets the trees and records it got before, byte for byte.  Finite coordinates of huge
+ * magnitude (extents beyond 3e38) remain unsupported; non-finite normals or uvs are not covered. */
+
 /* ---- batched ray queries (DXR offers TraceRay on any ray; the reference only traces its own camera rays,
  * R/HLSL/ray_tracing_shaders.hlsl:21-69).  The caller hands over rays and asks what they hit: picking, visibility / ambient
  * occlusion rays, sensor casts.
@@ -372,6 +391,7 @@ int crt_accumulated_samples(const crt_ctx* ctx, uint32_t* samples); /* samples p
  *   is at t ~ tmin.  Such a ray may then report a miss, or a farther hit, although a triangle lies in (tmin, tmax).  The
  *   result is still the oracle's traversal of the same tree, but it can differ between the host SAH tree and the gpu_build
  *   tree.  Every other ray gives the same result over either tree, however far from the origin the scene lies.
+ *   Inert triangles (non-finite vertices, above) are never hit and hide nothing, over any tree.
  * - Layout: queries traverse the 64-byte 4-wide tree the frames traverse.
  * - A query needs an uploaded scene (CRT_ESTATE otherwise).  It reads the tree, the triangles and the options inner_min /
  *   inner_min_any, nothing else: camera, mode, accumulation sums, launch-order state and frame outputs are untouched, and a frame
@@ -429,6 +449,7 @@ int crt_occluded_rays(crt_ctx* ctx, uint32_t n, const float* rays, uint8_t* occl
  * - Results do not depend on the tree (host SAH, gpu_build LBVH or PLOC, refitted or rebuilt), on the order of the records
  *   or on scheduling: the closest-point search prunes a box only when no triangle in it can produce a computed d2 <= the
  *   best so far (the margin holds at any offset from the origin).
+ *   Inert triangles (non-finite vertices, above) are never the closest triangle and are never counted, over any tree.
  * - Common rules of the ray queries: pending refits are applied first; a query reads the tree and the triangle records,
  *   nothing else (camera, mode, accumulation sums, launch orders, frame outputs are untouched); n = 0 returns CRT_OK and
  *   launches nothing; CRT_ESTATE without a scene.  stats (may be NULL): kernel_ms, total_ms, rays_primary = records traced
@@ -475,6 +496,7 @@ int crt_occupancy(crt_ctx* ctx, uint32_t n, const float* points, uint8_t* inside
  * - Independence: results do not depend on the tree (host SAH, gpu_build LBVH or PLOC, refitted, rebuilt), on the order of
  *   the records, on scheduling, or on inner_min / inner_min_any / stack_entries / list_short_max.  The "boundary rays" limit
  *   of the ray queries applies unchanged and is the only exception, as for crt_count_hits.
+ *   Inert triangles (non-finite vertices, above) appear in no list, over any tree.
  * - Common rules of the queries: pending refits are applied first; camera, mode, accumulation sums, launch orders and frame
  *   outputs are untouched; n = 0 returns CRT_OK and launches nothing (the host form writes offsets[0] = 0 when offsets !=
  *   NULL, the device form looks at no buffer; *total = 0); CRT_ESTATE without a scene; CRT_EINVAL for a NULL ctx, for NULL rays

@@ -566,6 +566,7 @@ oracle_scene* oracle_scene_create_ex(const oracle_mesh* meshes, uint32_t n_meshe
             const float* b = &M->xyz[3 * i1];
             const float* c = &M->xyz[3 * i2];
             oracle_tri* T = &in_tri[g];
+            int finite = 1;
             for (int k = 0; k < 3; k++) {
                 T->v0[k] = a[k];
                 T->e1[k] = b[k] - a[k];
@@ -573,6 +574,19 @@ oracle_scene* oracle_scene_create_ex(const oracle_mesh* meshes, uint32_t n_meshe
                 pbox[g].mn[k] = minf_(minf_(a[k], b[k]), c[k]);
                 pbox[g].mx[k] = maxf_(maxf_(a[k], b[k]), c[k]);
                 pcent[3 * g + k] = (pbox[g].mn[k] + pbox[g].mx[k]) * 0.5f;
+                finite &= a[k] - a[k] == 0.0f && b[k] - b[k] == 0.0f && c[k] - c[k] == 0.0f;
+            }
+            /* an inert triangle (a NaN or inf among its nine coordinates): box and centroid are the point (0, 0, 0), so no
+               builder ever sees a non-finite number; its record is nine quiet NaNs, which no intersection routine accepts */
+            if (!finite) {
+                const uint32_t qnan_bits = 0x7FC00000u; /* what B - A makes of a NaN's sign differs between compilers and
+                                                           between host and device code: the record is pinned to these bits */
+                float qnan;
+                memcpy(&qnan, &qnan_bits, 4);
+                for (int k = 0; k < 3; k++) {
+                    pbox[g].mn[k] = pbox[g].mx[k] = pcent[3 * g + k] = 0.0f;
+                    T->v0[k] = T->e1[k] = T->e2[k] = qnan;
+                }
             }
             T->inst = m; T->prim = t; T->gid = g;
             oracle_shade* S = &in_sh[g];

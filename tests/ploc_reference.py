@@ -2,7 +2,8 @@
 independently of the kernels.  The initial cluster order is the LBVH's Morton order, which the callers take from the oracle's
 build_mode=1 records (OracleScene(..., build_mode=1).tris()["gid"]).
 
-  clusters   one per triangle, in that order; box = the triangle's vertex box (selects a < b ? a : b)
+  clusters   one per triangle, in that order; box = the triangle's vertex box (selects a < b ? a : b), or the point (0, 0, 0)
+             where one of its nine coordinates is not finite
   distance   d(i, j) = half area of union(box_i, box_j) in float32: (dx*dy + dy*dz) + dz*dx, no fused multiply-add
   neighbour  NN(i) = argmin of d over j in [i-16, i+16] \\ {i}, candidates in ascending j, the first one kept on ties
   merge      NN(i) = j, NN(j) = i, i < j: new node at position i (left = i, right = j); j dropped; order kept; new nodes of an
@@ -43,7 +44,8 @@ def union(a, b):
 
 
 def tri_boxes(meshes):
-    """(n, 6) float32 per gid: min / max of the three vertices as triBoxKernel takes them"""
+    """(n, 6) float32 per gid: min / max of the three vertices as triBoxKernel takes them; all zero for a triangle with a NaN or
+    an inf among its nine coordinates"""
     out = []
     for m in meshes:
         t = np.asarray(m["triangles"], dtype=np.int64).reshape(-1, 3)
@@ -51,7 +53,9 @@ def tri_boxes(meshes):
             continue
         v = np.asarray(m["vertices"], dtype=F32).reshape(-1, 3)
         A, B, C = v[t[:, 0]], v[t[:, 1]], v[t[:, 2]]
-        out.append(np.concatenate([_min(_min(A, B), C), _max(_max(A, B), C)], axis=1))
+        b = np.concatenate([_min(_min(A, B), C), _max(_max(A, B), C)], axis=1)
+        b[~np.isfinite(v[t]).all(axis=(1, 2))] = 0  # an inert triangle (crt_hip.h) is the point (0, 0, 0) to every builder
+        out.append(b)
     return np.concatenate(out).astype(F32) if out else np.zeros((0, 6), F32)
 
 
