@@ -212,13 +212,12 @@ struct crt_ctx {
         uint32_t serial = 0;
     } rayArena[kRing];
     uint32_t raySerial = 0;
-    uint32_t rayResident[5] = {};        // resident workgroups of each query kernel (QueryKind) on this device ...
-    uint32_t rayResidentEntries[5] = {}; // ... for this many LDS stack entries
+    uint32_t rayResident[6] = {};        // resident workgroups of each query kernel (QueryKind) on this device ...
+    uint32_t rayResidentEntries[6] = {}; // ... for this many LDS stack entries
     void* dRayStage = nullptr; // the host entry points' records and outputs, grown on demand
     size_t rayStageBytes = 0;
-    // crt_list_hits*: the fill kernel's resident workgroups, the host form's record arrays (grown on demand, apart from
-    // dRayStage, which holds its rays and offsets while the total is read back) and the sort's crossover ("list_short_max")
-    uint32_t listResident = 0, listResidentEntries = 0;
+    // crt_list_hits*: the host form's record arrays (grown on demand, apart from dRayStage, which holds its rays and offsets
+    // while the total is read back) and the sort's crossover ("list_short_max")
     void* dListStage = nullptr;
     size_t listStageBytes = 0;
     // lists of up to this many hits are sorted by one lane, longer ones by a wavefront.  Measured (DESIGN.md section 5d,
@@ -1295,7 +1294,8 @@ namespace {
 // Batched ray and point queries.  A query is n records of one kind (32-byte rays or 16-byte points) and up to five outputs
 // of a fixed size per record; every kind runs one persistent kernel (ray_kernels.hip, point_kernels.hip) over an arena of
 // the context.
-enum QueryKind { kQueryClosestHit = 0, kQueryOcclusion = 1, kQueryClosestPoint = 2, kQueryCount = 3, kQueryOccupancy = 4 };
+enum QueryKind { kQueryClosestHit = 0, kQueryOcclusion = 1, kQueryClosestPoint = 2, kQueryCount = 3, kQueryOccupancy = 4,
+                 kQueryListFill = 5 /* the second traversal of crt_list_hits*: a kernel of its own, not an entry point */ };
 struct QueryOutput {
     void* p = nullptr;
     uint32_t bytes = 0; // per record
@@ -1348,15 +1348,27 @@ int checkDeviceOutputs(crt_ctx* c, const QuerySpec& s, const void* records)
     return CRT_OK;
 }
 
-uint32_t queryResident(QueryKind kind, uint32_t stack_entries)
+// resident workgroups of the kind's kernel with the LDS stack the options ask for, from the context's cache; the persistent
+// grid and the chunking of n records follow from it
+int queryGrid(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t& stack_entries, uint32_t& chunk, uint32_t& grid)
 {
-    switch (kind) {
-    case kQueryClosestHit: return crt::rayQueryResident(false, stack_entries);
-    case kQueryOcclusion: return crt::rayQueryResident(true, stack_entries);
-    case kQueryClosestPoint: return crt::pointQueryResident(crt::kPointClosest, stack_entries);
-    case kQueryCount: return crt::pointQueryResident(crt::kPointCount, stack_entries);
-    default: return crt::pointQueryResident(crt::kPointOccupancy, stack_entries);
+    stack_entries = c->tuneStackEntries ? c->tuneStackEntries : 16u; // as fillParams
+    if (c->rayResident[kind] == 0u || c->rayResidentEntries[kind] != stack_entries) {
+        uint32_t r = 0u;
+        switch (kind) {
+        case kQueryClosestHit: r = crt::rayQueryResident(false, stack_entries); break;
+        case kQueryOcclusion: r = crt::rayQueryResident(true, stack_entries); break;
+        case kQueryClosestPoint: r = crt::pointQueryResident(crt::kPointClosest, stack_entries); break;
+        case kQueryCount: r = crt::pointQueryResident(crt::kPointCount, stack_entries); break;
+        case kQueryOccupancy: r = crt::pointQueryResident(crt::kPointOccupancy, stack_entries); break;
+        case kQueryListFill: r = crt::listFillResident(stack_entries); break;
+        }
+        c->rayResident[kind] = r;
+        c->rayResidentEntries[kind] = stack_entries;
+        if (r == 0u) return fail(c, CRT_EHIP, "query kernel: occupancy query failed");
     }
+    crt::rayQueryLayout(n, c->rayResident[kind], chunk, grid);
+    return CRT_OK;
 }
 
 // What a query kernel gets from its arena: grid, chunking, cursor, counters and the stack spill arena
@@ -1378,15 +1390,9 @@ int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t entryWords, crt_
                uint32_t minGrid = 0)
 {
     HIP_TRY(c, hipSetDevice(c->device));
-    ql.stack_entries = c->tuneStackEntries ? c->tuneStackEntries : 16u; // as fillParams
-    const uint32_t deepest = 3u * c->bvh.depth4 + 1u;                  // as runRender
+    if (const int rc = queryGrid(c, kind, n, ql.stack_entries, ql.chunk, ql.grid)) return rc;
+    const uint32_t deepest = 3u * c->bvh.depth4 + 1u; // as runRender
     ql.spill_stride = (deepest > ql.stack_entries ? deepest - ql.stack_entries : 1u) * entryWords;
-    if (c->rayResident[kind] == 0u || c->rayResidentEntries[kind] != ql.stack_entries) {
-        c->rayResident[kind] = queryResident(kind, ql.stack_entries);
-        c->rayResidentEntries[kind] = ql.stack_entries;
-        if (c->rayResident[kind] == 0u) return fail(c, CRT_EHIP, "query kernel: occupancy query failed");
-    }
-    crt::rayQueryLayout(n, c->rayResident[kind], ql.chunk, ql.grid);
 
     // the arena this stream used last; else an unused one; else the least recently used one of another stream, once the
     // query that used it last is done
@@ -1454,16 +1460,30 @@ int endQuery(crt_ctx* c, QueryKind kind, uint32_t n, const QueryLaunch& ql, int 
     return CRT_OK;
 }
 
+// the part of a query kernel's parameters every kind shares, from the context and the launch
+crt::QueryCommon queryCommon(const crt_ctx* c, const QueryLaunch& ql, const void* d_records, uint32_t n, uint32_t inner_min)
+{
+    crt::QueryCommon q;
+    q.nodes = c->dNodes;
+    q.tris = c->dTris;
+    q.n_nodes = c->bvh.nNodes4;
+    q.records = d_records;
+    q.n = n;
+    q.cursor = ql.cursor;
+    q.counters = ql.counters;
+    q.spill = ql.spill;
+    q.spill_stride = ql.spill_stride;
+    q.stack_entries = ql.stack_entries;
+    q.inner_min = inner_min;
+    q.chunk = ql.chunk;
+    return q;
+}
+
 int runRayQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_rays, void* const d[5], crt_frame_stats* stats)
 {
     const bool occlusion = s.kind == kQueryOcclusion;
     crt::RayQueryParams q;
     std::memset(&q, 0, sizeof(q));
-    q.nodes = c->dNodes;
-    q.tris = c->dTris;
-    q.n_nodes = c->bvh.nNodes4;
-    q.rays = d_rays;
-    q.n = n;
     if (occlusion) q.occluded = static_cast<unsigned char*>(d[0]);
     else {
         q.t = static_cast<float*>(d[0]);
@@ -1471,15 +1491,9 @@ int runRayQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_rays, 
         q.inst = static_cast<uint32_t*>(d[2]);
         q.prim = static_cast<uint32_t*>(d[3]);
     }
-    q.inner_min = occlusion ? c->tuneInnerMinAny : c->tuneInnerMin;
     QueryLaunch ql;
     if (const int rc = beginQuery(c, s.kind, n, 1u, stats, ql)) return rc;
-    q.stack_entries = ql.stack_entries;
-    q.spill_stride = ql.spill_stride;
-    q.chunk = ql.chunk;
-    q.cursor = ql.cursor;
-    q.counters = ql.counters;
-    q.spill = ql.spill;
+    q.c = queryCommon(c, ql, d_rays, n, occlusion ? c->tuneInnerMinAny : c->tuneInnerMin);
     return endQuery(c, s.kind, n, ql, crt::launchRayQuery(q, occlusion, c->counting, ql.grid, c->stream), stats);
 }
 
@@ -1499,11 +1513,6 @@ int runPointQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_reco
     const crt::PointQueryKind pk = s.kind == kQueryClosestPoint ? crt::kPointClosest : (s.kind == kQueryCount ? crt::kPointCount : crt::kPointOccupancy);
     crt::PointQueryParams q;
     std::memset(&q, 0, sizeof(q));
-    q.nodes = c->dNodes;
-    q.tris = c->dTris;
-    q.n_nodes = c->bvh.nNodes4;
-    q.records = d_records;
-    q.n = n;
     if (pk == crt::kPointClosest) {
         q.dist = static_cast<float*>(d[0]);
         q.point = static_cast<float*>(d[1]);
@@ -1516,15 +1525,9 @@ int runPointQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_reco
     } else {
         q.inside = static_cast<unsigned char*>(d[0]);
     }
-    q.inner_min = pk == crt::kPointClosest ? c->tuneInnerMin : c->tuneInnerMinAny;
     QueryLaunch ql;
     if (const int rc = beginQuery(c, s.kind, n, crt::pointQueryEntryWords(pk), stats, ql)) return rc;
-    q.stack_entries = ql.stack_entries;
-    q.spill_stride = ql.spill_stride;
-    q.chunk = ql.chunk;
-    q.cursor = ql.cursor;
-    q.counters = ql.counters;
-    q.spill = ql.spill;
+    q.c = queryCommon(c, ql, d_records, n, pk == crt::kPointClosest ? c->tuneInnerMin : c->tuneInnerMinAny);
     return endQuery(c, s.kind, n, ql, crt::launchPointQuery(q, pk, c->counting, ql.grid, c->stream), stats);
 }
 
@@ -1634,13 +1637,8 @@ int listMark(crt_ctx* c, const ListRun& lr, int i)
 int listBegin(crt_ctx* c, uint32_t n, const void* d_rays, void* d_offsets, size_t keyBytes, crt_frame_stats* stats, ListRun& lr)
 {
     HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t entries = c->tuneStackEntries ? c->tuneStackEntries : 16u; // as beginQuery
-    if (c->listResident == 0u || c->listResidentEntries != entries) {
-        c->listResident = crt::listFillResident(entries);
-        c->listResidentEntries = entries;
-        if (c->listResident == 0u) return fail(c, CRT_EHIP, "list fill kernel: occupancy query failed");
-    }
-    crt::rayQueryLayout(n, c->listResident, lr.fillChunk, lr.fillGrid);
+    uint32_t entries = 0;
+    if (const int rc = queryGrid(c, kQueryListFill, n, entries, lr.fillChunk, lr.fillGrid)) return rc;
     lr.timed = stats != nullptr;
     if (lr.timed)
         for (hipEvent_t& e : c->evList)
@@ -1654,38 +1652,17 @@ int listBegin(crt_ctx* c, uint32_t n, const void* d_rays, void* d_offsets, size_
 
     crt::PointQueryParams pq;
     std::memset(&pq, 0, sizeof(pq));
-    pq.nodes = c->dNodes;
-    pq.tris = c->dTris;
-    pq.n_nodes = c->bvh.nNodes4;
-    pq.records = d_rays;
-    pq.n = n;
+    pq.c = queryCommon(c, ql, d_rays, n, c->tuneInnerMinAny);
     pq.count = counts;
-    pq.inner_min = c->tuneInnerMinAny;
-    pq.stack_entries = ql.stack_entries;
-    pq.spill_stride = ql.spill_stride;
-    pq.chunk = ql.chunk;
-    pq.cursor = ql.cursor;
-    pq.counters = ql.counters;
-    pq.spill = ql.spill;
 
     crt::ListParams& q = lr.q;
     std::memset(&q, 0, sizeof(q));
-    q.nodes = c->dNodes;
-    q.tris = c->dTris;
-    q.n_nodes = c->bvh.nNodes4;
-    q.rays = d_rays;
-    q.n = n;
+    q.c = pq.c;
+    q.c.chunk = lr.fillChunk; // (the fill's own grid and chunking; everything else as the count)
     q.offsets = static_cast<const unsigned long long*>(d_offsets);
     q.longRays = counts;
     q.longCount = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(ql.cursor) + 128); // in the arena's zeroed head
     q.short_max = c->tuneListShortMax;
-    q.inner_min = c->tuneInnerMinAny;
-    q.stack_entries = ql.stack_entries;
-    q.spill_stride = ql.spill_stride;
-    q.chunk = lr.fillChunk;
-    q.cursor = ql.cursor;
-    q.counters = ql.counters;
-    q.spill = ql.spill;
 
     int rc = listMark(c, lr, 0);
     if (rc == 0) rc = crt::launchPointQuery(pq, crt::kPointCount, c->counting, ql.grid, c->stream);
@@ -1706,7 +1683,7 @@ int listFill(crt_ctx* c, ListRun& lr, unsigned long long capacity, float* tkey, 
     q.uv = static_cast<float*>(out[1]);
     q.inst = static_cast<uint32_t*>(out[2]);
     q.prim = static_cast<uint32_t*>(out[3]);
-    const hipError_t e = hipMemsetAsync(q.cursor, 0, sizeof(uint32_t), c->stream);
+    const hipError_t e = hipMemsetAsync(q.c.cursor, 0, sizeof(uint32_t), c->stream);
     if (e != hipSuccess) return static_cast<int>(e);
     int rc = crt::launchListFill(q, c->counting, lr.fillGrid, c->stream);
     if (rc == 0) rc = listMark(c, lr, 3);

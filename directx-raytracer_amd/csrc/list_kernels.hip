@@ -5,8 +5,8 @@
 // stream without a host round trip:
 //   scan   exclusive sum of the n uint32 counts into n + 1 uint64 offsets (tile sums, one-workgroup scan of the sums, rescan
 //          of each tile: the 64-bit sibling of gpu_sort.hip.h's prefix sum)
-//   fill   the count's traversal once more (same persistent shape, same triTest on the same records, so it accepts the same
-//          triangles), whose leaf step writes a hit's prescaled t' and its leaf-order triangle record at offsets[ray] + k++
+//   fill   the count's traversal once more (the same everyHitIteration of query.hip.h on the same records, so it accepts the
+//          same triangles), whose leaf step writes a hit's prescaled t' and its leaf-order triangle record at offsets[ray] + k++
 //   sort   every segment by (t', global id), then resolve: t' 2^-e, (u, v) by re-running triTest as the ray query's record
 //          re-read at retirement, inst and prim from the triangle record.  Segments of up to short_max records: one lane per
 //          ray, insertion sort.  Longer ones: one wavefront per ray, an all-ascending bitonic network, through LDS in tiles
@@ -15,18 +15,11 @@
 //
 // The sort compares t' as floats and, only on equal t', the global ids, which it reads from the triangle records (the work
 // arrays hold the record index the resolve needs, not the id).  The order is total: a triangle sits in one leaf.
-#include "traversal.hip.h"
-#include "render_kernels.h"
+#include "query.hip.h"
 #include "../../include/crt_hip.h"
 
 namespace crt {
 namespace {
-
-#ifndef CRT_REFILL_MIN
-#define CRT_REFILL_MIN 16
-#endif
-
-constexpr int kListMaxWavesPerSimd = 7; // as kPointMaxWavesPerSimd
 
 // ---- scan: n uint32 counts -> n + 1 uint64 offsets.  Tiles of 2048 counts; tile n / 2048 holds offsets[n], so there are
 // n / 2048 + 1 tiles (up to 2^21 + 1 for n = 2^32 - 1: indices are 64-bit).
@@ -107,105 +100,51 @@ __global__ __launch_bounds__(kScanThreads) void listTileScanKernel(const uint32_
 
 // ---- fill
 
-// One scheduling decision of the listing traversal: countIteration (point_kernels.hip) whose leaf writes the accepted hit
-// into the ray's segment instead of counting it (its twin: keep the box cull and the triangle test of the two the same).  k counts every accepted hit; only the first `room` are stored, so that the
-// two traversals could never write outside the segment even if they disagreed.
-template <bool COUNT, class L, int OCT, bool DEC = false>
-__device__ __forceinline__ void listIteration(const float4* __restrict__ nodes, const float4* __restrict__ tris, const Ray& r, float tmin, float tmax,
-                                              float tcull, Stack& stack, int innerMin, float* tkey, uint32_t* idkey, unsigned long long base,
-                                              uint32_t room, uint32_t& k, int& cur, uint32_t& cntNodes, uint32_t& cntTris,
-                                              const float* __restrict__ planes = nullptr)
-{
-    const unsigned long long innerMask = __ballot(L::inner(cur));
-    const unsigned long long leafMask = __ballot(L::leaf(cur));
-    if ((innerMask | leafMask) == 0ull) return;
-    const int wantNode = innerMin > 0 ? innerMin : (static_cast<int>(__popcll(innerMask | leafMask)) * -innerMin + 7) / 8;
-    if (innerMask != 0ull && (leafMask == 0ull || static_cast<int>(__popcll(innerMask)) >= wantNode)) {
-        CRT_NODE_STEPS(anyStep)
-        return;
+// The fill's job for runQuery (query.hip.h): the every-hit traversal whose accepted hits go into the ray's segment.  k counts
+// every accepted hit; only the first `room` are stored, so that the fill could never write outside the segment even if it
+// disagreed with the count.  A finished ray has nothing to retire: its records are in place.
+struct ListFillJob {
+    const ListParams& q;
+    Stack stack;
+    int cur;
+    Ray r;
+    float tmin = 0.0f, tmax = 0.0f, tcull = 0.0f;
+    unsigned long long base = 0;
+    uint32_t room = 0, k = 0;
+
+    __device__ __forceinline__ explicit ListFillJob(const ListParams& params) : q(params) { r = makeRay(f3(0.0f, 0.0f, 0.0f), f3(0.0f, 0.0f, 1.0f)); }
+    __device__ __forceinline__ void retire(uint32_t) {}
+    __device__ __forceinline__ void start(uint32_t idx)
+    {
+        const float4* recs = reinterpret_cast<const float4*>(q.c.records);
+        base = q.offsets[idx];
+        room = static_cast<uint32_t>(q.offsets[static_cast<size_t>(idx) + 1u] - base);
+        k = 0;
+        const float4 a = recs[2u * static_cast<size_t>(idx)], b = recs[2u * static_cast<size_t>(idx) + 1u];
+        queryRay(a, b, r, tmin, tmax); // prescaled, as the ray queries
+        tcull = cullBound(tmax);
+        // a record with a NaN (or an empty interval) is not traced: no crossings
+        cur = (queryRayOk(a, b, tmin, tmax) & (q.c.n_nodes != 0u)) ? LayLegacy::kRoot : LayLegacy::kDone;
     }
-    if (L::leaf(cur)) {
-        uint32_t first, cnt;
-        L::leafRange(cur, first, cnt);
-        for (uint32_t i = 0; i < cnt; i++) {
-            const uint32_t id = L::triId(first, i);
-            const float4* T = L::triPtr(tris, id);
-            const float4 a = T[0], b = T[1], c = T[2];
-            if (COUNT) cntTris++;
-            float t, u, v;
-            if (triTest<false>(r, a, b, c, tmin, t, u, v) & (t < tmax)) {
-                if (k < room) {
-                    tkey[base + k] = t;
-                    idkey[base + k] = id;
-                }
-                k++;
-            }
-        }
-        cur = stack.sp == 0 ? L::kDone : stack.pop();
+    template <bool COUNT>
+    __device__ __forceinline__ void step(uint32_t& cntNodes, uint32_t& cntTris)
+    {
+        everyHitIteration<COUNT>(reinterpret_cast<const float4*>(q.c.nodes), reinterpret_cast<const float4*>(q.c.tris), r, tmin, tmax, tcull, stack,
+                                 static_cast<int>(q.c.inner_min), cur, cntNodes, cntTris, [&](float t, uint32_t id) {
+                                     if (k < room) {
+                                         q.tkey[base + k] = t;
+                                         q.idkey[base + k] = id;
+                                     }
+                                     k++;
+                                 });
     }
-}
+};
 
 template <bool COUNT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LayLegacy::kWavesPerEu, 8))) void listFillKernel(const ListParams q)
 {
-    using L = LayLegacy;
-    extern __shared__ int s_stack[]; // stack_entries x 64 dwords
-    if (q.offsets[q.n] > q.capacity) return;
-    const uint32_t lane = threadIdx.x & 63u;
-    const float4* nodes = reinterpret_cast<const float4*>(q.nodes);
-    const float4* tris = reinterpret_cast<const float4*>(q.tris);
-    const float4* recs = reinterpret_cast<const float4*>(q.rays);
-    Stack stack;
-    stack.lds = s_stack + lane;
-    stack.spill = q.spill + (static_cast<size_t>(blockIdx.x) * 64u + lane) * q.spill_stride;
-    stack.cap = static_cast<int>(q.stack_entries);
-    stack.sp = 0;
-    const int innerMin = static_cast<int>(q.inner_min);
-
-    Ray r = makeRay(f3(0.0f, 0.0f, 0.0f), f3(0.0f, 0.0f, 1.0f));
-    float tmin = 0.0f, tmax = 0.0f, tcull = 0.0f;
-    unsigned long long base = 0;
-    uint32_t room = 0, k = 0;
-    int cur = L::kDone;
-    bool have = false;
-    uint32_t cntNodes = 0, cntTris = 0;
-    RayTap tap;
-    tap.begin(q.n, q.chunk);
-    const unsigned long long all = __ballot(true);
-    for (;;) {
-        const bool idle = cur == L::kDone;
-        const unsigned long long idleMask = __ballot(idle);
-        if (idleMask == all || (tap.more() && static_cast<uint32_t>(__popcll(idleMask)) >= static_cast<uint32_t>(CRT_REFILL_MIN))) {
-            // a finished ray has nothing to retire: its records are in place
-            bool valid = false;
-            const uint32_t idx = tap.take(q.cursor, q.n, q.chunk, idleMask, valid);
-            if (idle) {
-                have = valid;
-                if (valid) {
-                    base = q.offsets[idx];
-                    room = static_cast<uint32_t>(q.offsets[static_cast<size_t>(idx) + 1u] - base);
-                    k = 0;
-                    stack.sp = 0;
-                    const float4 a = recs[2u * static_cast<size_t>(idx)], b = recs[2u * static_cast<size_t>(idx) + 1u];
-                    queryRay(a, b, r, tmin, tmax); // prescaled, as the ray queries
-                    tcull = cullBound(tmax);
-                    // a record with a NaN (or an empty interval) is not traced: no crossings
-                    const bool ok = (a.x == a.x) & (a.y == a.y) & (a.z == a.z) & (b.x == b.x) & (b.y == b.y) & (b.z == b.z) & (tmin < tmax) &
-                                    (q.n_nodes != 0u);
-                    cur = ok ? L::kRoot : L::kDone;
-                }
-            }
-            if (__ballot(have) == 0ull && !tap.more()) break;
-        }
-        listIteration<COUNT, L, 8>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, q.tkey, q.idkey, base, room, k, cur, cntNodes, cntTris);
-    }
-    if (COUNT) {
-        const uint32_t a = waveTotal(cntNodes), c = waveTotal(cntTris);
-        if (lane == 0) {
-            atomicAdd(&q.counters[0], static_cast<unsigned long long>(a));
-            atomicAdd(&q.counters[1], static_cast<unsigned long long>(c));
-        }
-    }
+    if (q.offsets[q.c.n] > q.capacity) return;
+    runQuery<COUNT, ListFillJob>(q);
 }
 
 // ---- sort and resolve
@@ -237,7 +176,7 @@ struct ListRay {
 
 __device__ __forceinline__ ListRay listRay(const ListParams& q, uint32_t ray)
 {
-    const float4* recs = reinterpret_cast<const float4*>(q.rays);
+    const float4* recs = reinterpret_cast<const float4*>(q.c.records);
     const float4 a = recs[2u * static_cast<size_t>(ray)], b = recs[2u * static_cast<size_t>(ray) + 1u];
     ListRay lr;
     float tmax;
@@ -266,9 +205,9 @@ __device__ __forceinline__ void listResolve(const ListParams& q, const float4* t
 // one lane per ray: segments of 1 .. short_max records; longer ones are queued for listSortLongKernel
 __global__ __launch_bounds__(256) void listSortShortKernel(const ListParams q)
 {
-    if (q.offsets[q.n] > q.capacity) return;
+    if (q.offsets[q.c.n] > q.capacity) return;
     const unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256u + threadIdx.x;
-    if (i >= q.n) return;
+    if (i >= q.c.n) return;
     const unsigned long long lo = q.offsets[i];
     const unsigned long long len = q.offsets[i + 1u] - lo;
     if (len == 0ull) return;
@@ -276,7 +215,7 @@ __global__ __launch_bounds__(256) void listSortShortKernel(const ListParams q)
         q.longRays[atomicAdd(q.longCount, 1u)] = static_cast<uint32_t>(i);
         return;
     }
-    const float4* tris = reinterpret_cast<const float4*>(q.tris);
+    const float4* tris = reinterpret_cast<const float4*>(q.c.tris);
     float* tk = q.tkey + lo;
     uint32_t* ik = q.idkey + lo;
     const uint32_t cnt = static_cast<uint32_t>(len);
@@ -318,9 +257,9 @@ __global__ __launch_bounds__(64) void listSortLongKernel(const ListParams q)
 {
     __shared__ float s_t[kSortTile];
     __shared__ uint32_t s_id[kSortTile];
-    if (q.offsets[q.n] > q.capacity) return;
+    if (q.offsets[q.c.n] > q.capacity) return;
     const uint32_t lane = threadIdx.x;
-    const float4* tris = reinterpret_cast<const float4*>(q.tris);
+    const float4* tris = reinterpret_cast<const float4*>(q.c.tris);
     const uint32_t nLong = *q.longCount;
     for (uint32_t w = blockIdx.x; w < nLong; w += gridDim.x) {
         const uint32_t ray = q.longRays[w];
@@ -394,30 +333,23 @@ int launchListScan(const uint32_t* counts, uint32_t n, unsigned long long* offse
     return static_cast<int>(hipGetLastError());
 }
 
-// resident workgroups of the persistent fill kernel on the current device (as pointQueryResident); the caller caches it
 uint32_t listFillResident(uint32_t stack_entries)
 {
-    int dev = 0, cus = 0, perCu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, reinterpret_cast<const void*>(&listFillKernel<false>), 64, listLds(stack_entries)) != hipSuccess ||
-        perCu <= 0 || cus <= 0)
-        return 0u;
-    const int most = 4 * kListMaxWavesPerSimd;
-    return static_cast<uint32_t>(perCu > most ? most : perCu) * static_cast<uint32_t>(cus);
+    return queryResidentWorkgroups(reinterpret_cast<const void*>(&listFillKernel<false>), listLds(stack_entries));
 }
 
 int launchListFill(const ListParams& q, bool counting, uint32_t grid, ihipStream_t* stream)
 {
-    if (q.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
-    if (counting) hipLaunchKernelGGL((listFillKernel<true>), dim3(grid), dim3(64), listLds(q.stack_entries), stream, q);
-    else hipLaunchKernelGGL((listFillKernel<false>), dim3(grid), dim3(64), listLds(q.stack_entries), stream, q);
+    if (q.c.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
+    if (counting) hipLaunchKernelGGL((listFillKernel<true>), dim3(grid), dim3(64), listLds(q.c.stack_entries), stream, q);
+    else hipLaunchKernelGGL((listFillKernel<false>), dim3(grid), dim3(64), listLds(q.c.stack_entries), stream, q);
     return static_cast<int>(hipGetLastError());
 }
 
 int launchListSort(const ListParams& q, ihipStream_t* stream)
 {
-    if (q.n == 0u) return static_cast<int>(hipSuccess);
-    const uint32_t blocks = static_cast<uint32_t>((static_cast<unsigned long long>(q.n) + 255u) / 256u);
+    if (q.c.n == 0u) return static_cast<int>(hipSuccess);
+    const uint32_t blocks = static_cast<uint32_t>((static_cast<unsigned long long>(q.c.n) + 255u) / 256u);
     hipLaunchKernelGGL(listSortShortKernel, dim3(blocks), dim3(256), 0, stream, q);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return static_cast<int>(e);

@@ -145,9 +145,7 @@ struct GlobalTap {
 // retires its ray (miss -> radiance written, hit -> appended to the shade queue) and takes the next entry of the queue,
 // as soon as at least `refillMin` lanes are idle: the wavefront stays full until the queue runs dry.  Every ray is still
 // traced by one lane in its own fixed order, so results and fetch counts are those of the chunked loop.
-#ifndef CRT_REFILL_MIN
-#define CRT_REFILL_MIN 16
-#endif
+// (refillMin = CRT_REFILL_MIN, traversal.hip.h)
 // GLOBAL: the queues are shared by every wavefront of the launch (pathTraceKernel): entries are taken with one atomic on the
 // queue's cursor per refill and appended with one atomic on the other queue's length per retirement.
 template <bool COUNT, class L, bool GLOBAL>

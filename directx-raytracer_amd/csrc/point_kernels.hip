@@ -2,10 +2,8 @@
 // crt_occupancy*, include/crt_hip.h) -- the closest surface point of a point, the number of surfaces a ray crosses, and
 // whether a point lies inside the geometry.
 //
-// Both kernels are persistent like rayQueryKernel (ray_kernels.hip): one record per lane, a lane whose traversal has ended
-// retires its record and idle lanes are refilled from a chunked global cursor (RayTap) once CRT_REFILL_MIN of them wait.
-// Every record is still searched by one lane in its own fixed order, so results and fetch counts do not depend on the order
-// of the buffer, the refill timing or the wave scheduling.
+// Both kernels are persistent like rayQueryKernel (ray_kernels.hip): a job each for the driver they share (runQuery,
+// query.hip.h).
 //
 // Closest point: a best-first descent of the quantised 4-wide tree.  A node step decodes the four child boxes, takes the
 // squared distance from the point to each box as a lower bound, descends into the nearest child and pushes the others
@@ -19,19 +17,11 @@
 //
 // Arithmetic contract: operation for operation the order written in include/crt_hip.h (tests/point_reference.c restates it
 // on the host, compiled with -ffp-contract=off).
-#include "traversal.hip.h"
-#include "render_kernels.h"
+#include "query.hip.h"
 #include "../../include/crt_hip.h"
 
 namespace crt {
 namespace {
-
-#ifndef CRT_REFILL_MIN
-#define CRT_REFILL_MIN 16
-#endif
-
-// Resident wavefronts per SIMD the persistent grid is sized for (as kRayMaxWavesPerSimd)
-constexpr int kPointMaxWavesPerSimd = 7;
 
 // ---- closest point on one triangle (include/crt_hip.h gives the order in words)
 
@@ -104,14 +94,10 @@ __device__ __forceinline__ float dcullOf(float b, float pad)
     return (r * r) * kDistPad;
 }
 
-// Per-lane stack of (reference, key) pairs: entry e of lane l at dwords 2e*64+l and (2e+1)*64+l of LDS for e < cap, then in
-// the lane's slice of the spill arena.  key = the order key of the entry's box (its squared-distance bound with the two low
-// bits replaced by the child slot: a float <= the bound, so comparing it with the cull bound is conservative).
-struct PointStack {
-    int* lds;
-    int* spill;
-    int cap;
-    int sp;
+// Per-lane stack of (reference, key) pairs on the fields of Stack: entry e of lane l at dwords 2e*64+l and (2e+1)*64+l of LDS
+// for e < cap, then in the lane's slice of the spill arena.  key = the order key of the entry's box (its squared-distance bound
+// with the two low bits replaced by the child slot: a float <= the bound, so comparing it with the cull bound is conservative).
+struct PointStack : Stack {
     __device__ __forceinline__ void push(int ref, uint32_t key)
     {
         if (sp < cap) { lds[2 * sp * 64] = ref; lds[(2 * sp + 1) * 64] = static_cast<int>(key); }
@@ -196,125 +182,68 @@ __device__ __forceinline__ void pointLeafStep(const float4* __restrict__ tris, F
     cur = stack.popWithin(dcull);
 }
 
+// The closest-point job for runQuery (query.hip.h)
+struct ClosestPointJob {
+    const PointQueryParams& q;
+    PointStack stack;
+    int cur;
+    F3 p = { 0.0f, 0.0f, 0.0f };
+    float rmax = 0.0f, dcull = 0.0f;
+    PointBest b = { 0.0f, 0.0f, 0.0f, 0xFFFFFFFFu, 0u };
+
+    __device__ __forceinline__ explicit ClosestPointJob(const PointQueryParams& params) : q(params) {}
+    __device__ __forceinline__ void retire(uint32_t my)
+    {
+        const bool hit = b.gid != 0xFFFFFFFFu;
+        if (q.dist) q.dist[my] = hit ? sqrtf(b.d2) : rmax;
+        if (q.uv) reinterpret_cast<float2*>(q.uv)[my] = make_float2(b.u, b.v);
+        if (q.point || q.inst || q.prim) {
+            F3 x = p;
+            uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
+            if (hit) { // (an empty scene has no triangle record to read)
+                const float4* T = LayLegacy::triPtr(reinterpret_cast<const float4*>(q.c.tris), b.tri);
+                const float4 a = T[0], e1 = T[1], e2 = T[2];
+                x = f3(fmaf(b.v, e2.x, fmaf(b.u, e1.x, a.x)), fmaf(b.v, e2.y, fmaf(b.u, e1.y, a.y)), fmaf(b.v, e2.z, fmaf(b.u, e1.z, a.z)));
+                inst = __float_as_uint(a.w);  // v0.w = mesh ordinal
+                prim = __float_as_uint(e1.w); // e1.w = triangle of the mesh
+            }
+            if (q.point) { q.point[3u * static_cast<size_t>(my)] = x.x; q.point[3u * static_cast<size_t>(my) + 1u] = x.y; q.point[3u * static_cast<size_t>(my) + 2u] = x.z; }
+            if (q.inst) q.inst[my] = inst;
+            if (q.prim) q.prim[my] = prim;
+        }
+    }
+    __device__ __forceinline__ void start(uint32_t idx)
+    {
+        const float4 r = reinterpret_cast<const float4*>(q.c.records)[idx];
+        p = f3(r.x, r.y, r.z);
+        rmax = r.w;
+        b.d2 = rmax * rmax; b.u = 0.0f; b.v = 0.0f; b.gid = 0xFFFFFFFFu; b.tri = 0u;
+        dcull = dcullOf(b.d2, q.pad);
+        // a record with a NaN or a negative rmax is not searched: it reports a miss
+        const bool ok = (r.x == r.x) & (r.y == r.y) & (r.z == r.z) & (rmax >= 0.0f);
+        cur = (ok & (q.c.n_nodes != 0u)) ? LayLegacy::kRoot : LayLegacy::kDone;
+    }
+    // as closestIteration: node steps while enough lanes stand on inner nodes, else the leaves
+    template <bool COUNT>
+    __device__ __forceinline__ void step(uint32_t& cntNodes, uint32_t& cntTris)
+    {
+        const unsigned long long innerMask = __ballot(LayLegacy::inner(cur));
+        const unsigned long long leafMask = __ballot(LayLegacy::leaf(cur));
+        const int innerMin = static_cast<int>(q.c.inner_min);
+        if (CRT_NODE_STEPS_NEXT(innerMask, leafMask, innerMin)) {
+#pragma unroll
+            for (int rep = 0; rep < NODE_STEPS; rep++)
+                if (LayLegacy::inner(cur)) pointNodeStep<COUNT>(reinterpret_cast<const float4*>(q.c.nodes), p, dcull, stack, cur, cntNodes);
+        } else if (LayLegacy::leaf(cur)) {
+            pointLeafStep<COUNT>(reinterpret_cast<const float4*>(q.c.tris), p, q.pad, b, dcull, stack, cur, cntTris);
+        }
+    }
+};
+
 template <bool COUNT>
 __global__ __launch_bounds__(64) void closestPointKernel(const PointQueryParams q)
 {
-    extern __shared__ int s_stack[]; // stack_entries x 2 x 64 dwords
-    const uint32_t lane = threadIdx.x & 63u;
-    const float4* nodes = reinterpret_cast<const float4*>(q.nodes);
-    const float4* tris = reinterpret_cast<const float4*>(q.tris);
-    const float4* pts = reinterpret_cast<const float4*>(q.records);
-    PointStack stack;
-    stack.lds = s_stack + lane;
-    stack.spill = q.spill + (static_cast<size_t>(blockIdx.x) * 64u + lane) * q.spill_stride;
-    stack.cap = static_cast<int>(q.stack_entries);
-    stack.sp = 0;
-    const int innerMin = static_cast<int>(q.inner_min);
-
-    F3 p = f3(0.0f, 0.0f, 0.0f);
-    float rmax = 0.0f, dcull = 0.0f;
-    PointBest b;
-    b.d2 = 0.0f; b.u = 0.0f; b.v = 0.0f; b.gid = 0xFFFFFFFFu; b.tri = 0u;
-    int cur = LayLegacy::kDone;
-    bool have = false;
-    uint32_t my = 0, cntNodes = 0, cntTris = 0;
-    RayTap tap;
-    tap.begin(q.n, q.chunk);
-    const unsigned long long all = __ballot(true);
-    for (;;) {
-        const bool idle = cur == LayLegacy::kDone;
-        const unsigned long long idleMask = __ballot(idle);
-        if (idleMask == all || (tap.more() && static_cast<uint32_t>(__popcll(idleMask)) >= static_cast<uint32_t>(CRT_REFILL_MIN))) {
-            // retire the finished points ...
-            if (idle & have) {
-                const bool hit = b.gid != 0xFFFFFFFFu;
-                if (q.dist) q.dist[my] = hit ? sqrtf(b.d2) : rmax;
-                if (q.uv) reinterpret_cast<float2*>(q.uv)[my] = make_float2(b.u, b.v);
-                if (q.point || q.inst || q.prim) {
-                    F3 x = p;
-                    uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
-                    if (hit) { // (an empty scene has no triangle record to read)
-                        const float4* T = LayLegacy::triPtr(tris, b.tri);
-                        const float4 a = T[0], e1 = T[1], e2 = T[2];
-                        x = f3(fmaf(b.v, e2.x, fmaf(b.u, e1.x, a.x)), fmaf(b.v, e2.y, fmaf(b.u, e1.y, a.y)), fmaf(b.v, e2.z, fmaf(b.u, e1.z, a.z)));
-                        inst = __float_as_uint(a.w);  // v0.w = mesh ordinal
-                        prim = __float_as_uint(e1.w); // e1.w = triangle of the mesh
-                    }
-                    if (q.point) { q.point[3u * static_cast<size_t>(my)] = x.x; q.point[3u * static_cast<size_t>(my) + 1u] = x.y; q.point[3u * static_cast<size_t>(my) + 2u] = x.z; }
-                    if (q.inst) q.inst[my] = inst;
-                    if (q.prim) q.prim[my] = prim;
-                }
-            }
-            // ... and hand the next records to the idle lanes
-            bool valid = false;
-            const uint32_t idx = tap.take(q.cursor, q.n, q.chunk, idleMask, valid);
-            if (idle) {
-                have = valid;
-                if (valid) {
-                    my = idx;
-                    const float4 r = pts[idx];
-                    p = f3(r.x, r.y, r.z);
-                    rmax = r.w;
-                    b.d2 = rmax * rmax; b.u = 0.0f; b.v = 0.0f; b.gid = 0xFFFFFFFFu; b.tri = 0u;
-                    dcull = dcullOf(b.d2, q.pad);
-                    stack.sp = 0;
-                    // a record with a NaN or a negative rmax is not searched: it reports a miss
-                    const bool ok = (r.x == r.x) & (r.y == r.y) & (r.z == r.z) & (rmax >= 0.0f);
-                    cur = (ok & (q.n_nodes != 0u)) ? LayLegacy::kRoot : LayLegacy::kDone;
-                }
-            }
-            if (__ballot(have) == 0ull && !tap.more()) break; // buffer exhausted and every point retired
-        }
-        // one scheduling decision, as closestIteration: node steps while enough lanes stand on inner nodes, else the leaves
-        const unsigned long long innerMask = __ballot(LayLegacy::inner(cur));
-        const unsigned long long leafMask = __ballot(LayLegacy::leaf(cur));
-        const int wantNode = innerMin > 0 ? innerMin : (static_cast<int>(__popcll(innerMask | leafMask)) * -innerMin + 7) / 8;
-        if (innerMask != 0ull && (leafMask == 0ull || static_cast<int>(__popcll(innerMask)) >= wantNode)) {
-#pragma unroll
-            for (int rep = 0; rep < NODE_STEPS; rep++)
-                if (LayLegacy::inner(cur)) pointNodeStep<COUNT>(nodes, p, dcull, stack, cur, cntNodes);
-        } else if (LayLegacy::leaf(cur)) {
-            pointLeafStep<COUNT>(tris, p, q.pad, b, dcull, stack, cur, cntTris);
-        }
-    }
-    if (COUNT) {
-        const uint32_t a = waveTotal(cntNodes), c = waveTotal(cntTris);
-        if (lane == 0) {
-            atomicAdd(&q.counters[0], static_cast<unsigned long long>(a));
-            atomicAdd(&q.counters[1], static_cast<unsigned long long>(c));
-        }
-    }
-}
-
-// One scheduling decision of the counting traversal: anyIteration's node steps; a leaf counts every triangle the
-// Moeller-Trumbore test accepts in (tmin, tmax) and the lane goes on with its stack (no early exit).
-// listIteration (list_kernels.hip) is this function with a store in place of the increment, and crt_list_hits* relies on the
-// two accepting the same triangles: change them together.
-template <bool COUNT, class L, int OCT, bool DEC = false>
-__device__ __forceinline__ void countIteration(const float4* __restrict__ nodes, const float4* __restrict__ tris, const Ray& r, float tmin, float tmax,
-                                               float tcull, Stack& stack, int innerMin, uint32_t& hits, int& cur, uint32_t& cntNodes,
-                                               uint32_t& cntTris, const float* __restrict__ planes = nullptr)
-{
-    const unsigned long long innerMask = __ballot(L::inner(cur));
-    const unsigned long long leafMask = __ballot(L::leaf(cur));
-    if ((innerMask | leafMask) == 0ull) return;
-    const int wantNode = innerMin > 0 ? innerMin : (static_cast<int>(__popcll(innerMask | leafMask)) * -innerMin + 7) / 8;
-    if (innerMask != 0ull && (leafMask == 0ull || static_cast<int>(__popcll(innerMask)) >= wantNode)) {
-        CRT_NODE_STEPS(anyStep)
-        return;
-    }
-    if (L::leaf(cur)) {
-        uint32_t first, cnt;
-        L::leafRange(cur, first, cnt);
-        for (uint32_t i = 0; i < cnt; i++) {
-            const float4* T = L::triPtr(tris, L::triId(first, i));
-            const float4 a = T[0], b = T[1], c = T[2];
-            if (COUNT) cntTris++;
-            float t, u, v;
-            if (triTest<false>(r, a, b, c, tmin, t, u, v) & (t < tmax)) hits++;
-        }
-        cur = stack.sp == 0 ? L::kDone : stack.pop();
-    }
+    runQuery<COUNT, ClosestPointJob>(q);
 }
 
 __device__ __forceinline__ F3 occupancyDir(uint32_t k)
@@ -323,89 +252,68 @@ __device__ __forceinline__ F3 occupancyDir(uint32_t k)
     return f3(k == 0u ? d0[0] : (k == 1u ? d1[0] : d2[0]), k == 0u ? d0[1] : (k == 1u ? d1[1] : d2[1]), k == 0u ? d0[2] : (k == 1u ? d1[2] : d2[2]));
 }
 
+// The job of the hit counts and of occupancy for runQuery: the every-hit traversal (query.hip.h) with a per-lane counter.
 // OCC = false: hit count of every ray record (one uint32 each); true: occupancy of every point record (one byte each), its
 // three rays traced one after the other by the same lane
-template <bool COUNT, bool OCC>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LayLegacy::kWavesPerEu, 8))) void hitCountKernel(const PointQueryParams q)
-{
-    using L = LayLegacy;
-    extern __shared__ int s_stack[]; // stack_entries x 64 dwords
-    const uint32_t lane = threadIdx.x & 63u;
-    const float4* nodes = reinterpret_cast<const float4*>(q.nodes);
-    const float4* tris = reinterpret_cast<const float4*>(q.tris);
-    const float4* recs = reinterpret_cast<const float4*>(q.records);
+template <bool OCC>
+struct HitCountJob {
+    const PointQueryParams& q;
     Stack stack;
-    stack.lds = s_stack + lane;
-    stack.spill = q.spill + (static_cast<size_t>(blockIdx.x) * 64u + lane) * q.spill_stride;
-    stack.cap = static_cast<int>(q.stack_entries);
-    stack.sp = 0;
-    const int innerMin = static_cast<int>(q.inner_min);
-    const float tcullInf = cullBound(__builtin_inff());
-
-    Ray r = makeRay(f3(0.0f, 0.0f, 0.0f), f3(0.0f, 0.0f, 1.0f));
+    int cur;
+    Ray r;
     float tmin = 0.0f, tmax = 0.0f, tcull = 0.0f;
-    uint32_t hits = 0, odd = 0, dir = 0;
-    int cur = L::kDone;
-    bool have = false;
-    uint32_t my = 0, cntNodes = 0, cntTris = 0;
-    RayTap tap;
-    tap.begin(q.n, q.chunk);
-    const unsigned long long all = __ballot(true);
-    for (;;) {
-        if (OCC && have && (cur == L::kDone) && (dir < 2u)) { // next direction of the same point
+    uint32_t hits = 0, odd = 0;
+    uint32_t dir = 2; // occupancy: the direction being traced; 2 = the last one (also: no record), nothing to follow
+
+    __device__ __forceinline__ explicit HitCountJob(const PointQueryParams& params) : q(params) { r = makeRay(f3(0.0f, 0.0f, 0.0f), f3(0.0f, 0.0f, 1.0f)); }
+    __device__ __forceinline__ void retire(uint32_t my)
+    {
+        if (OCC) q.inside[my] = (odd + (hits & 1u)) >= 2u ? 1u : 0u;
+        else q.count[my] = hits;
+    }
+    __device__ __forceinline__ void start(uint32_t idx)
+    {
+        const float4* recs = reinterpret_cast<const float4*>(q.c.records);
+        hits = 0; odd = 0;
+        bool ok;
+        if (OCC) {
+            const float4 a = recs[idx];
+            r = makeRay(f3(a.x, a.y, a.z), occupancyDir(0u));
+            tmin = 0.0f;
+            tmax = __builtin_inff();
+            tcull = cullBound(__builtin_inff());
+            ok = (a.x == a.x) & (a.y == a.y) & (a.z == a.z);
+        } else {
+            const float4 a = recs[2u * static_cast<size_t>(idx)], b = recs[2u * static_cast<size_t>(idx) + 1u];
+            queryRay(a, b, r, tmin, tmax); // prescaled, as the ray queries
+            tcull = cullBound(tmax);
+            ok = queryRayOk(a, b, tmin, tmax);
+        }
+        // a record with a NaN (or an empty interval) is not traced: no crossings
+        ok = ok & (q.c.n_nodes != 0u);
+        dir = ok ? 0u : 2u;
+        cur = ok ? LayLegacy::kRoot : LayLegacy::kDone;
+    }
+    template <bool COUNT>
+    __device__ __forceinline__ void step(uint32_t& cntNodes, uint32_t& cntTris)
+    {
+        everyHitIteration<COUNT>(reinterpret_cast<const float4*>(q.c.nodes), reinterpret_cast<const float4*>(q.c.tris), r, tmin, tmax, tcull, stack,
+                                 static_cast<int>(q.c.inner_min), cur, cntNodes, cntTris, [&](float, uint32_t) { hits++; });
+        if (OCC && (cur == LayLegacy::kDone) && (dir < 2u)) { // this direction is done: the next one of the same point
             odd += hits & 1u;
             hits = 0;
             dir++;
             r = makeRay(r.o, occupancyDir(dir));
             stack.sp = 0;
-            cur = L::kRoot;
-        }
-        const bool idle = cur == L::kDone;
-        const unsigned long long idleMask = __ballot(idle);
-        if (idleMask == all || (tap.more() && static_cast<uint32_t>(__popcll(idleMask)) >= static_cast<uint32_t>(CRT_REFILL_MIN))) {
-            if (idle & have) {
-                if (OCC) q.inside[my] = (odd + (hits & 1u)) >= 2u ? 1u : 0u;
-                else q.count[my] = hits;
-            }
-            bool valid = false;
-            const uint32_t idx = tap.take(q.cursor, q.n, q.chunk, idleMask, valid);
-            if (idle) {
-                have = valid;
-                if (valid) {
-                    my = idx;
-                    hits = 0; odd = 0; dir = 0;
-                    stack.sp = 0;
-                    bool ok;
-                    if (OCC) {
-                        const float4 a = recs[idx];
-                        r = makeRay(f3(a.x, a.y, a.z), occupancyDir(0u));
-                        tmin = 0.0f;
-                        tmax = __builtin_inff();
-                        tcull = tcullInf;
-                        ok = (a.x == a.x) & (a.y == a.y) & (a.z == a.z);
-                    } else {
-                        const float4 a = recs[2u * static_cast<size_t>(idx)], b = recs[2u * static_cast<size_t>(idx) + 1u];
-                        queryRay(a, b, r, tmin, tmax); // prescaled, as the ray queries
-                        tcull = cullBound(tmax);
-                        ok = (a.x == a.x) & (a.y == a.y) & (a.z == a.z) & (b.x == b.x) & (b.y == b.y) & (b.z == b.z) & (tmin < tmax);
-                    }
-                    // a record with a NaN (or an empty interval) is not traced: no crossings
-                    ok = ok & (q.n_nodes != 0u);
-                    if (!ok) dir = 2u;
-                    cur = ok ? L::kRoot : L::kDone;
-                }
-            }
-            if (__ballot(have) == 0ull && !tap.more()) break;
-        }
-        countIteration<COUNT, L, 8>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, hits, cur, cntNodes, cntTris);
-    }
-    if (COUNT) {
-        const uint32_t a = waveTotal(cntNodes), c = waveTotal(cntTris);
-        if (lane == 0) {
-            atomicAdd(&q.counters[0], static_cast<unsigned long long>(a));
-            atomicAdd(&q.counters[1], static_cast<unsigned long long>(c));
+            cur = LayLegacy::kRoot;
         }
     }
+};
+
+template <bool COUNT, bool OCC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LayLegacy::kWavesPerEu, 8))) void hitCountKernel(const PointQueryParams q)
+{
+    runQuery<COUNT, HitCountJob<OCC>>(q);
 }
 
 const void* pointKernel(PointQueryKind kind, bool counting)
@@ -421,22 +329,15 @@ size_t pointLds(PointQueryKind kind, uint32_t stack_entries) { return static_cas
 
 } // namespace
 
-// resident workgroups of a persistent point query kernel on the current device (as rayQueryResident); the caller caches it
 uint32_t pointQueryResident(PointQueryKind kind, uint32_t stack_entries)
 {
-    int dev = 0, cus = 0, perCu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, pointKernel(kind, false), 64, pointLds(kind, stack_entries)) != hipSuccess ||
-        perCu <= 0 || cus <= 0)
-        return 0u;
-    const int most = 4 * kPointMaxWavesPerSimd;
-    return static_cast<uint32_t>(perCu > most ? most : perCu) * static_cast<uint32_t>(cus);
+    return queryResidentWorkgroups(pointKernel(kind, false), pointLds(kind, stack_entries));
 }
 
 int launchPointQuery(const PointQueryParams& q, PointQueryKind kind, bool counting, uint32_t grid, ihipStream_t* stream)
 {
-    if (q.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
-    const size_t lds = pointLds(kind, q.stack_entries);
+    if (q.c.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
+    const size_t lds = pointLds(kind, q.c.stack_entries);
     const dim3 g(grid), block(64);
     switch (kind) {
     case kPointClosest:

@@ -5,119 +5,94 @@
 // a node step long, its neighbour a grazing ray hundreds of steps long, so a wavefront that traced a fixed chunk of 64 would run
 // as long as its slowest ray.  Here the grid is persistent (what the chip holds at once) and every lane holds one ray: a lane
 // whose traversal has ended retires its ray (writes the requested outputs) and takes the next record as soon as CRT_REFILL_MIN
-// lanes are idle -- the streamClosest idea of path_kernels.hip applied to a user buffer.  Records are handed out from a global
+// lanes are idle -- the streamClosest idea of path_kernels.hip applied to a user buffer.  That loop is runQuery (query.hip.h),
+// shared with the point queries and the listing.  Records are handed out from a global
 // cursor in chunks of `chunk` rays per atomic.  Every ray is still traced by one lane in its own fixed order with the per-lane
 // tmin / tmax of its record, so results and fetch counts are those of the oracle's traversal of the same ray, whatever the
 // order of the buffer, the refill timing or the wave scheduling.
 //
-// A record is traced prescaled by a power of two (queryRay, traversal.hip.h): results do not depend on |d|.
+// A record is traced prescaled by a power of two (queryRay, query.hip.h): results do not depend on |d|.
 // Arithmetic contract: identical, operation for operation, to oracle/crt_oracle.c (compiled with -ffp-contract=off).
-#include "traversal.hip.h"
+#include "query.hip.h"
 
 namespace crt {
 namespace {
 
-#ifndef CRT_REFILL_MIN
-#define CRT_REFILL_MIN 16
-#endif
-
-// OCCL = false: closest hit (t, uv, inst, prim, each optional); true: any hit in (tmin, tmax), one byte per ray.  Output
-// pointers are kernel arguments, so their null tests are scalar branches.  The generic octant loop (OCT = 8): refilled lanes
-// mix direction octants.
 // Register budget: the closest-hit form is given 6 wavefronts per SIMD (76 VGPRs, nothing spilled); at the frames' 7 it spilled
 // 4 VGPRs inside the loop and ran 9 / 8 / 15 % slower on the camera / AO / random legs of tools/ray_query_bench.py.
 constexpr int kRayWavesClosest = 6;
-// Resident wavefronts per SIMD the persistent grid is sized for: at most 7.  The occlusion form fits 8 (60 VGPRs), but with
-// 8 its random leg took 0.56 ms against 0.46 with 7 (incoherent rays: more concurrent traversals, more cache misses).
-constexpr int kRayMaxWavesPerSimd = 7;
 
-template <bool COUNT, bool OCCL, class L>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCCL ? L::kWavesPerEu : kRayWavesClosest, 8))) void rayQueryKernel(const RayQueryParams q)
-{
-    extern __shared__ int s_stack[]; // stack_entries x 64 dwords
-    const uint32_t lane = threadIdx.x & 63u;
-    const float4* nodes = reinterpret_cast<const float4*>(q.nodes);
-    const float4* tris = reinterpret_cast<const float4*>(q.tris);
-    const float4* rays = reinterpret_cast<const float4*>(q.rays);
+// The ray query's job for runQuery (query.hip.h).  OCCL = false: closest hit (t, uv, inst, prim, each optional); true: any
+// hit in (tmin, tmax), one byte per ray.  Output pointers are kernel arguments, so their null tests are scalar branches.
+// The generic octant loop (OCT = 8): refilled lanes mix direction octants.
+template <bool OCCL>
+struct RayJob {
+    const RayQueryParams& q;
     Stack stack;
-    stack.lds = s_stack + lane;
-    stack.spill = q.spill + (static_cast<size_t>(blockIdx.x) * 64u + lane) * q.spill_stride;
-    stack.cap = static_cast<int>(q.stack_entries);
-    stack.sp = 0;
-    const int innerMin = static_cast<int>(q.inner_min);
-
-    Ray r = makeRay(f3(0.0f, 0.0f, 0.0f), f3(0.0f, 0.0f, 1.0f));
+    Ray r;
+    int cur;
     float tmin = 0.0f, tmax = 0.0f, tcull = 0.0f; // the prescaled interval (queryRay)
     float tmaxRec = 0.0f;                         // the record's own tmax: a miss reports it
     int e = 0;                                    // the record's scale exponent: a hit reports t * 2^-e
     Hit h;
-    h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.gid = 0;
     bool occluded = false;
-    int cur = L::kDone;
-    bool have = false; // this lane holds a record (being traced, or finished and not yet retired)
-    uint32_t my = 0;   // its index in the buffer
-    uint32_t iters = 0, cntNodes = 0, cntTris = 0;
-    RayTap tap;
-    tap.begin(q.n, q.chunk);
-    const unsigned long long all = __ballot(true);
-    for (;;) {
-        const bool idle = cur == L::kDone;
-        const unsigned long long idleMask = __ballot(idle);
-        if (idleMask == all || (tap.more() && static_cast<uint32_t>(__popcll(idleMask)) >= static_cast<uint32_t>(CRT_REFILL_MIN))) {
-            // retire the finished rays ...
-            if (idle & have) {
-                if (OCCL) {
-                    q.occluded[my] = occluded ? 1u : 0u;
-                } else {
-                    const bool hit = h.t < tmax;
-                    if (q.t) q.t[my] = hit ? __builtin_amdgcn_ldexpf(h.t, -e) : tmaxRec;
-                    if (q.uv) reinterpret_cast<float2*>(q.uv)[my] = make_float2(h.u, h.v);
-                    if (q.inst || q.prim) {
-                        uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
-                        if (hit) { // (an empty scene has no triangle record to read)
-                            const uint32_t* T = reinterpret_cast<const uint32_t*>(L::triPtr(tris, h.tri));
-                            inst = T[3]; // v0.w = mesh ordinal
-                            prim = T[7]; // e1.w = triangle of the mesh
-                        }
-                        if (q.inst) q.inst[my] = inst;
-                        if (q.prim) q.prim[my] = prim;
-                    }
-                }
-            }
-            // ... and hand the next records to the idle lanes
-            bool valid = false;
-            const uint32_t idx = tap.take(q.cursor, q.n, q.chunk, idleMask, valid);
-            if (idle) {
-                have = valid;
-                if (valid) {
-                    my = idx;
-                    const float4 a = rays[2u * static_cast<size_t>(idx)], b = rays[2u * static_cast<size_t>(idx) + 1u];
-                    e = queryRay(a, b, r, tmin, tmax);
-                    tmaxRec = b.w;
-                    h.t = tmax; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.gid = 0;
-                    occluded = false;
-                    tcull = cullBound(tmax);
-                    stack.sp = 0;
-                    // a record with a NaN or an empty interval is not traced: it reports a miss
-                    const bool ok = (a.x == a.x) & (a.y == a.y) & (a.z == a.z) & (b.x == b.x) & (b.y == b.y) & (b.z == b.z) & (tmin < tmax);
-                    cur = (ok & (q.n_nodes != 0u)) ? L::kRoot : L::kDone;
-                }
-            }
-            if (__ballot(have) == 0ull && !tap.more()) break; // buffer exhausted and every ray retired
+    uint32_t iters = 0;
+
+    __device__ __forceinline__ explicit RayJob(const RayQueryParams& params) : q(params)
+    {
+        r = makeRay(f3(0.0f, 0.0f, 0.0f), f3(0.0f, 0.0f, 1.0f));
+        h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.gid = 0;
+    }
+    __device__ __forceinline__ void retire(uint32_t my)
+    {
+        if (OCCL) {
+            q.occluded[my] = occluded ? 1u : 0u;
+            return;
         }
-        if (OCCL) anyIteration<COUNT, L, 8>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris);
+        const bool hit = h.t < tmax;
+        if (q.t) q.t[my] = hit ? __builtin_amdgcn_ldexpf(h.t, -e) : tmaxRec;
+        if (q.uv) reinterpret_cast<float2*>(q.uv)[my] = make_float2(h.u, h.v);
+        if (q.inst || q.prim) {
+            uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
+            if (hit) { // (an empty scene has no triangle record to read)
+                const uint32_t* T = reinterpret_cast<const uint32_t*>(LayLegacy::triPtr(reinterpret_cast<const float4*>(q.c.tris), h.tri));
+                inst = T[3]; // v0.w = mesh ordinal
+                prim = T[7]; // e1.w = triangle of the mesh
+            }
+            if (q.inst) q.inst[my] = inst;
+            if (q.prim) q.prim[my] = prim;
+        }
+    }
+    __device__ __forceinline__ void start(uint32_t idx)
+    {
+        const float4* rays = reinterpret_cast<const float4*>(q.c.records);
+        const float4 a = rays[2u * static_cast<size_t>(idx)], b = rays[2u * static_cast<size_t>(idx) + 1u];
+        e = queryRay(a, b, r, tmin, tmax);
+        tmaxRec = b.w;
+        h.t = tmax; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.gid = 0;
+        occluded = false;
+        tcull = cullBound(tmax);
+        // a record with a NaN or an empty interval is not traced: it reports a miss
+        cur = (queryRayOk(a, b, tmin, tmax) & (q.c.n_nodes != 0u)) ? LayLegacy::kRoot : LayLegacy::kDone;
+    }
+    template <bool COUNT>
+    __device__ __forceinline__ void step(uint32_t& cntNodes, uint32_t& cntTris)
+    {
+        const float4* nodes = reinterpret_cast<const float4*>(q.c.nodes);
+        const float4* tris = reinterpret_cast<const float4*>(q.c.tris);
+        const int innerMin = static_cast<int>(q.c.inner_min);
+        if (OCCL) anyIteration<COUNT, LayLegacy, 8>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris);
         else {
-            closestIteration<COUNT, L, 8>(nodes, tris, r, tmin, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris);
+            closestIteration<COUNT, LayLegacy, 8>(nodes, tris, r, tmin, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris);
             tcull = cullBound(h.t); // (closestIteration sets t * kCullPad on an accepted hit: the same value for t >= 0)
         }
     }
-    if (COUNT) {
-        const uint32_t a = waveTotal(cntNodes), c = waveTotal(cntTris);
-        if (lane == 0) {
-            atomicAdd(&q.counters[0], static_cast<unsigned long long>(a));
-            atomicAdd(&q.counters[1], static_cast<unsigned long long>(c));
-        }
-    }
+};
+
+template <bool COUNT, bool OCCL>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OCCL ? LayLegacy::kWavesPerEu : kRayWavesClosest, 8))) void rayQueryKernel(const RayQueryParams q)
+{
+    runQuery<COUNT, RayJob<OCCL>>(q);
 }
 
 // Exhaustive check of rcpExact (traversal.hip.h) against the compiled correctly rounded 1.0f / d: wavefront w takes the
@@ -150,19 +125,10 @@ __global__ void __launch_bounds__(256) rcpCheckKernel(unsigned long long* out)
 
 } // namespace
 
-// resident workgroups of a persistent query kernel: what the occupancy calculator allows per CU for this LDS stack x CUs of
-// the current device (the closest-hit and the occlusion kernel hold different numbers of wavefronts).  The caller caches it.
 uint32_t rayQueryResident(bool occlusion, uint32_t stack_entries)
 {
-    int dev = 0, cus = 0, perCu = 0;
-    const size_t lds = static_cast<size_t>(stack_entries) * 64u * sizeof(int);
-    const void* k = occlusion ? reinterpret_cast<const void*>(&rayQueryKernel<false, true, LayLegacy>)
-                              : reinterpret_cast<const void*>(&rayQueryKernel<false, false, LayLegacy>);
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k, 64, lds) != hipSuccess || perCu <= 0 || cus <= 0)
-        return 0u;
-    const int most = 4 * kRayMaxWavesPerSimd; // one wavefront per workgroup, four SIMDs per CU
-    return static_cast<uint32_t>(perCu > most ? most : perCu) * static_cast<uint32_t>(cus);
+    const void* k = occlusion ? reinterpret_cast<const void*>(&rayQueryKernel<false, true>) : reinterpret_cast<const void*>(&rayQueryKernel<false, false>);
+    return queryResidentWorkgroups(k, static_cast<size_t>(stack_entries) * 64u * sizeof(int));
 }
 
 void rayQueryLayout(uint32_t n, uint32_t resident, uint32_t& chunk, uint32_t& grid)
@@ -176,15 +142,15 @@ void rayQueryLayout(uint32_t n, uint32_t resident, uint32_t& chunk, uint32_t& gr
 
 int launchRayQuery(const RayQueryParams& q, bool occlusion, bool counting, uint32_t grid, ihipStream_t* stream)
 {
-    if (q.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
-    const size_t lds = static_cast<size_t>(q.stack_entries) * 64u * sizeof(int);
+    if (q.c.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
+    const size_t lds = static_cast<size_t>(q.c.stack_entries) * 64u * sizeof(int);
     const dim3 g(grid), block(64);
     if (occlusion) {
-        if (counting) hipLaunchKernelGGL((rayQueryKernel<true, true, LayLegacy>), g, block, lds, stream, q);
-        else hipLaunchKernelGGL((rayQueryKernel<false, true, LayLegacy>), g, block, lds, stream, q);
+        if (counting) hipLaunchKernelGGL((rayQueryKernel<true, true>), g, block, lds, stream, q);
+        else hipLaunchKernelGGL((rayQueryKernel<false, true>), g, block, lds, stream, q);
     } else {
-        if (counting) hipLaunchKernelGGL((rayQueryKernel<true, false, LayLegacy>), g, block, lds, stream, q);
-        else hipLaunchKernelGGL((rayQueryKernel<false, false, LayLegacy>), g, block, lds, stream, q);
+        if (counting) hipLaunchKernelGGL((rayQueryKernel<true, false>), g, block, lds, stream, q);
+        else hipLaunchKernelGGL((rayQueryKernel<false, false>), g, block, lds, stream, q);
     }
     return static_cast<int>(hipGetLastError());
 }

@@ -125,41 +125,43 @@ int launchSortUnits(const uint32_t* cost, uint32_t* order, uint32_t n, bool xcdA
 int launchUntile(const uint32_t* gathered, uint32_t* frame, uint32_t width, uint32_t height, uint32_t n_ranks,
                  uint32_t rank_stride, uint32_t first_slot, ihipStream_t* stream);
 
-// batched ray queries (ray_kernels.hip; crt_trace_rays* / crt_occluded_rays*): n caller-supplied records of 8 floats
-// {ox, oy, oz, tmin, dx, dy, dz, tmax}, closest hit or occlusion, over the 4-wide tree
-struct RayQueryParams {
+// What every persistent query kernel (query.hip.h runQuery) is given: the tree, the caller's records, and the launch's share of
+// its arena
+struct QueryCommon {
     const void* nodes;            // as RenderParams::nodes / tris
     const void* tris;
     uint32_t n_nodes;
-    const void* rays;             // n x 32 bytes, 16-byte aligned
+    const void* records;          // n records, 16-byte aligned: rays of 32 bytes {ox, oy, oz, tmin, dx, dy, dz, tmax} or points of 16
     uint32_t n;
-    float* t;                     // closest hit, each nullable: t, {u, v} (8-byte aligned), mesh ordinal, triangle of the mesh
-    float* uv;
-    uint32_t* inst;
-    uint32_t* prim;
-    unsigned char* occluded;      // occlusion: one byte per ray
     uint32_t* cursor;             // chunks handed out behind the grid's own (zeroed on the stream before the launch)
     unsigned long long* counters; // counting variant: [0] nodes fetched, [1] triangles fetched
     int* spill;                   // stack spill arena: grid x 64 lanes x spill_stride ints
     uint32_t spill_stride;
     uint32_t stack_entries;       // per-lane stack entries kept in LDS
-    uint32_t inner_min;           // tune_inner_min (closest hit) or tune_inner_min_any (occlusion)
+    uint32_t inner_min;           // tune_inner_min (closest hit, closest point) or tune_inner_min_any (the others)
     uint32_t chunk;               // records per cursor reservation (rayQueryLayout)
+};
+// records per reservation and grid (persistent: at most `resident` workgroups) of a query of n records
+void rayQueryLayout(uint32_t n, uint32_t resident, uint32_t& chunk, uint32_t& grid);
+
+// batched ray queries (ray_kernels.hip; crt_trace_rays* / crt_occluded_rays*): closest hit or occlusion of n ray records, over
+// the 4-wide tree
+struct RayQueryParams {
+    QueryCommon c;
+    float* t;                     // closest hit, each nullable: t, {u, v} (8-byte aligned), mesh ordinal, triangle of the mesh
+    float* uv;
+    uint32_t* inst;
+    uint32_t* prim;
+    unsigned char* occluded;      // occlusion: one byte per ray
 };
 // workgroups of the closest-hit / occlusion query kernel the current device holds at once (0: unknown)
 uint32_t rayQueryResident(bool occlusion, uint32_t stack_entries);
-// records per reservation and grid (persistent: at most `resident` workgroups) of a query of n rays
-void rayQueryLayout(uint32_t n, uint32_t resident, uint32_t& chunk, uint32_t& grid);
 int launchRayQuery(const RayQueryParams& q, bool occlusion, bool counting, uint32_t grid, ihipStream_t* stream);
 // point queries (point_kernels.hip; crt_closest_points* / crt_count_hits* / crt_occupancy*): n caller-supplied records, point
 // records of 4 floats {x, y, z, rmax} (closest point, occupancy) or ray records (hit counts), over the 4-wide tree
 enum PointQueryKind { kPointClosest = 0, kPointCount = 1, kPointOccupancy = 2 };
 struct PointQueryParams {
-    const void* nodes;            // as RayQueryParams
-    const void* tris;
-    uint32_t n_nodes;
-    const void* records;          // n x 16 bytes (points) or n x 32 bytes (rays), 16-byte aligned
-    uint32_t n;
+    QueryCommon c;
     float* dist;                  // closest point, each nullable: distance, point (3 floats), {u, v} (8-byte aligned), inst, prim
     float* point;
     float* uv;
@@ -168,13 +170,6 @@ struct PointQueryParams {
     uint32_t* count;              // hit counts: one uint32 per ray
     unsigned char* inside;        // occupancy: one byte per point
     float pad;                    // closest point: absolute pruning margin, 2^-18 x the root box's diagonal
-    uint32_t* cursor;             // as RayQueryParams
-    unsigned long long* counters;
-    int* spill;                   // stack spill arena: grid x 64 lanes x spill_stride ints
-    uint32_t spill_stride;
-    uint32_t stack_entries;
-    uint32_t inner_min;
-    uint32_t chunk;
 };
 // ints per stack entry of a point query kernel (the closest-point stack keeps each entry's box bound beside its reference)
 inline uint32_t pointQueryEntryWords(PointQueryKind kind) { return kind == kPointClosest ? 2u : 1u; }
@@ -184,11 +179,7 @@ int launchPointQuery(const PointQueryParams& q, PointQueryKind kind, bool counti
 // sum of the counts into 64-bit offsets, a second traversal that writes every accepted hit into its ray's segment, and the
 // sort + resolve of every segment.  The three later steps read offsets[n] on the device and leave when it exceeds capacity.
 struct ListParams {
-    const void* nodes;            // as RayQueryParams
-    const void* tris;
-    uint32_t n_nodes;
-    const void* rays;             // n x 32 bytes, 16-byte aligned
-    uint32_t n;
+    QueryCommon c;                // records: the rays
     const unsigned long long* offsets; // n + 1, written by launchListScan
     unsigned long long capacity;  // records every record array holds
     float* tkey;                  // work arrays of `capacity` records: a hit's prescaled t' and its leaf-order triangle record.
@@ -200,13 +191,6 @@ struct ListParams {
     uint32_t* longRays;           // n entries (the count buffer, free once the offsets exist): rays left to the wavefront sort
     uint32_t* longCount;          // their number, zeroed on the stream before the launches
     uint32_t short_max;           // segments up to this length are sorted by one lane
-    uint32_t* cursor;             // as RayQueryParams
-    unsigned long long* counters;
-    int* spill;
-    uint32_t spill_stride;
-    uint32_t stack_entries;
-    uint32_t inner_min;
-    uint32_t chunk;
 };
 // bytes of the scan's scratch (64-bit tile sums) for n counts
 size_t listScanScratchBytes(uint32_t n);

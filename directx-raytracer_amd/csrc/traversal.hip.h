@@ -66,6 +66,11 @@ constexpr uint32_t kBoostAfter = 300; // traversal-loop iterations after which a
 #ifndef OCTANT_SPECIALISE
 #define OCTANT_SPECIALISE 1
 #endif
+// idle lanes a wavefront of a streaming traversal (streamClosest of path_kernels.hip, runQuery of query.hip.h) collects before
+// it retires their rays and fetches new work for them, while there is any
+#ifndef CRT_REFILL_MIN
+#define CRT_REFILL_MIN 16
+#endif
 constexpr uint32_t kGroupMax = 16; // grid padding unit: tiles per XCD group never exceed this
 
 struct F3 { float x, y, z; };
@@ -826,86 +831,6 @@ __device__ __forceinline__ bool traceAny(const float4* __restrict__ nodes, const
 #endif
     return traceAnyOct<COUNT, L, 8, DEC>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
 }
-
-// =====================================================================================================================
-// Persistent query kernels (ray_kernels.hip, point_kernels.hip): every lane holds one caller record, a wavefront refills its
-// idle lanes from a chunked global cursor.
-// =====================================================================================================================
-
-__device__ __forceinline__ uint32_t lanesBelow(unsigned long long m)
-{
-    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
-}
-
-// The box-cull bound of a ray whose current bound (tmax, then the best hit) is b.  Slab distances and the Moeller-Trumbore t
-// round differently, so boxes are culled against b widened by 2^-18 of |b| (traversal.hip.h kCullPad): b * (1 + 2^-18) for
-// b >= 0, as the frames do, and b * (1 - 2^-18) for b < 0, where the frames' factor would narrow the bound instead and reject
-// boxes holding triangles strictly inside (tmin, tmax).  Frames never see a negative bound (tmin = 0.001).
-constexpr float kCullPadNeg = 0.999996185302734375f; // 1 - 2^-18
-__device__ __forceinline__ float cullBound(float b) { return b * (b >= 0.0f ? kCullPad : kCullPadNeg); }
-
-// The ray of a query record {ox, oy, oz, tmin} {dx, dy, dz, tmax} (crt_trace_rays*, crt_occluded_rays*, crt_count_hits*: any
-// direction magnitude), prescaled by a power of two as the oracle's query_setup does: (o, tmin 2^e, d 2^-e, tmax 2^e), e the
-// exponent of the largest |d_i|, which lands in [1, 2) (frexp's exponent is 0 for a zero or non-finite input: e = -1 there).
-// The scaling is exact, so every slab distance, pad, cull bound and Moeller-Trumbore value of the scaled ray is that of the
-// record scaled by 2^-e, the hit's t is t' 2^-e, and kDirEps clamps only components below 1e-20 of the largest instead of
-// every component below 1e-20.  The frames' rays have unit length and do not come through here.
-__device__ __forceinline__ int queryRay(const float4 a, const float4 b, Ray& r, float& tmin, float& tmax)
-{
-    const int e = __builtin_amdgcn_frexp_expf(fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fabsf(b.z))) - 1;
-    r = makeRay(f3(a.x, a.y, a.z), f3(__builtin_amdgcn_ldexpf(b.x, -e), __builtin_amdgcn_ldexpf(b.y, -e), __builtin_amdgcn_ldexpf(b.z, -e)));
-    tmin = __builtin_amdgcn_ldexpf(a.w, e);
-    tmax = __builtin_amdgcn_ldexpf(b.w, e);
-    return e;
-}
-
-__device__ __forceinline__ uint32_t waveTotal(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// A wavefront's window [next, end) on the ray buffer.  The first chunk is the wavefront's own (chunk number blockIdx.x, no
-// atomic); later ones come from the cursor, which counts the chunks behind the grid's own.  Everything here is wave-uniform.
-struct RayTap {
-    uint32_t next, end;
-    bool dry; // the cursor has passed the end of the buffer
-    __device__ __forceinline__ void begin(uint32_t n, uint32_t chunk)
-    {
-        const uint64_t first = static_cast<uint64_t>(blockIdx.x) * chunk;
-        next = static_cast<uint32_t>(first < n ? first : n);
-        end = static_cast<uint32_t>(first + chunk < n ? first + chunk : n);
-        dry = false;
-    }
-    __device__ __forceinline__ bool more() const { return (next < end) | !dry; }
-    // records for the lanes of `mask` (call in wave-uniform control flow); a lane's record is valid if `valid`
-    __device__ __forceinline__ uint32_t take(uint32_t* cursor, uint32_t n, uint32_t chunk, unsigned long long mask, bool& valid)
-    {
-        const uint32_t want = static_cast<uint32_t>(__popcll(mask)), avail = end - next;
-        uint32_t nb = 0u, nbEnd = 0u;
-        if ((want > avail) & !dry) {
-            uint32_t k = 0u;
-            if ((threadIdx.x & 63u) == 0u) k = atomicAdd(cursor, 1u);
-            const uint64_t start = (static_cast<uint64_t>(gridDim.x) + __builtin_amdgcn_readfirstlane(k)) * chunk;
-            if (start >= n) dry = true;
-            else {
-                nb = static_cast<uint32_t>(start);
-                nbEnd = static_cast<uint32_t>(start + chunk < n ? start + chunk : n);
-            }
-        }
-        const uint32_t pre = lanesBelow(mask);
-        const uint32_t idx = pre < avail ? next + pre : nb + (pre - avail);
-        valid = (pre < avail) | (idx < nbEnd);
-        if (want > avail) {
-            next = nbEnd ? min(nb + (want - avail), nbEnd) : end;
-            end = nbEnd ? nbEnd : end;
-        } else {
-            next += want;
-        }
-        return idx;
-    }
-};
 
 } // namespace
 } // namespace crt

@@ -555,6 +555,71 @@ def test_edge_cases_device_forms_and_streams(pkg, ref, dragon, renderer, trees):
         fresh.close()
 
 
+def _device_queries(renderer, pts, rays):
+    """the three point queries through the device forms, with stats: (results, {kind: stats})"""
+    import torch
+    n, m = len(pts), len(rays)
+    d_pts, d_rays = torch.from_numpy(pts).cuda(), torch.from_numpy(rays).cuda()
+    d = {"dist": torch.empty(n, dtype=torch.float32, device="cuda"), "point": torch.empty((n, 3), dtype=torch.float32, device="cuda"),
+         "uv": torch.empty((n, 2), dtype=torch.float32, device="cuda"), "inst": torch.empty(n, dtype=torch.int32, device="cuda"),
+         "prim": torch.empty(n, dtype=torch.int32, device="cuda"), "count": torch.empty(m, dtype=torch.int32, device="cuda"),
+         "inside": torch.empty(n, dtype=torch.bool, device="cuda")}
+    torch.cuda.synchronize()
+    st = {"closest": renderer.closest_points_device(n, d_pts.data_ptr(), *[d[k].data_ptr() for k in ("dist", "point", "uv", "inst", "prim")], stats=True),
+          "count": renderer.count_hits_device(m, d_rays.data_ptr(), d["count"].data_ptr(), stats=True),
+          "occupancy": renderer.occupancy_device(n, d_pts.data_ptr(), d["inside"].data_ptr(), stats=True)}
+    torch.cuda.synchronize()
+    res = {k: v.cpu().numpy() for k, v in d.items()}
+    for k in ("inst", "prim", "count"):
+        res[k] = res[k].view(np.uint32)
+    return res, st
+
+
+@pytest.mark.gpu
+def test_tuning_options_change_nothing(pkg, ref, dragon, renderer, trees):
+    """2^19 + 37 records per kind -- more than 64 per workgroup the device holds at once, so the cursor, the mid-flight refill
+    and the tail of the buffer all run -- with a one- and a three-entry LDS stack (nearly every push spills, the two-word
+    entries of the closest-point stack included) and other scheduling thresholds: every output and both fetch counters are
+    those of the default options.  A seeded sample of the default run is pinned to the reference."""
+    rng = np.random.default_rng(18)
+    _upload(renderer, dragon)
+    n = (1 << 19) + 37
+    k = 1 << 17
+    pts = np.ascontiguousarray(_dragon_points(pkg, dragon, rng, k)[-n:])  # (every kind of point; 27 near-surface ones left out)
+    rays = _generic_rays(pkg, dragon, rng, n)
+    assert len(pts) == n and len(rays) == n
+    defaults = (("inner_min", -6), ("inner_min_any", -6), ("stack_entries", 0))
+    counters = ("nodes_visited", "tris_tested")
+    renderer.set_counting(True)
+    try:
+        base, st = _device_queries(renderer, pts, rays)
+        assert all(st[kind][c] > 0 for kind in st for c in counters)
+        for name, value in (("stack_entries", 1), ("stack_entries", 3), ("inner_min", 3), ("inner_min_any", 40), ("inner_min_any", -2)):
+            renderer.set_option(name, value)
+            got, gs = _device_queries(renderer, pts, rays)
+            for o, v in defaults:
+                renderer.set_option(o, v)
+            what = "%s=%d" % (name, value)
+            _assert_closest_equal(got, base, what)
+            np.testing.assert_array_equal(got["count"], base["count"], err_msg=what + ": count")
+            np.testing.assert_array_equal(got["inside"], base["inside"], err_msg=what + ": occupancy")
+            for kind in st:
+                for c in counters:
+                    assert gs[kind][c] == st[kind][c], "%s: %s %s" % (what, kind, c)
+    finally:
+        for o, v in defaults:
+            renderer.set_option(o, v)
+        renderer.set_counting(False)
+    tris = _exported(renderer)
+    pick = np.sort(np.random.default_rng(19).choice(n, 2000, replace=False))
+    _assert_closest_equal({q: base[q][pick] for q in ("dist", "point", "uv", "inst", "prim")}, ref_closest(ref, tris, pts[pick]), "sample")
+    np.testing.assert_array_equal(base["count"][pick], ref_count(ref, tris, rays[pick]))
+    off = pick[pick < 3 * k - 27]  # (occupancy is undefined on a surface: the on-vertex / on-edge points are left out)
+    assert len(off) > 1000
+    np.testing.assert_array_equal(base["inside"][off], ref_occupancy(ref, tris, pts[off]))
+    assert (base["inst"] != MISS).sum() > n // 2 and (base["count"] > 1).sum() > n // 200  # (the shares the smaller dragon tests ask for)
+
+
 @pytest.mark.gpu
 def test_counting_is_not_brute_force(pkg, scenes, renderer, trees):
     """near-surface points on the 1M-triangle height field fetch few triangle records per query (measured on an MI355X:

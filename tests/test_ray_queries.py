@@ -441,6 +441,44 @@ def test_scale_tail_and_order(pkg, dragon, renderer):
 
 
 @pytest.mark.gpu
+def test_tuning_options_change_nothing(pkg, oracle, dragon, renderer):
+    """2^19 + 37 rays -- more than 64 per workgroup the device holds at once, so the cursor, the mid-flight refill and the tail
+    of the buffer all run -- with a one- and a three-entry LDS stack (nearly every push spills) and other scheduling
+    thresholds: every output and both fetch counters are those of the default options.  A seeded sample of the default run
+    is pinned to the oracle."""
+    _upload(renderer, dragon)
+    n = (1 << 19) + 37
+    rays = _mixed_rays(pkg, dragon, n, seed=41)
+    defaults = (("inner_min", -6), ("inner_min_any", -6), ("stack_entries", 0))
+    counters = ("nodes_visited", "tris_tested")
+    renderer.set_counting(True)
+    try:
+        base, st, so = _device_query(renderer, rays)
+        assert all(st[k] > 0 and so[k] > 0 for k in counters)
+        for name, value in (("stack_entries", 1), ("stack_entries", 3), ("inner_min", 3), ("inner_min_any", 40), ("inner_min_any", -2)):
+            renderer.set_option(name, value)
+            got, gt, go = _device_query(renderer, rays)
+            for k, v in defaults:
+                renderer.set_option(k, v)
+            what = "%s=%d" % (name, value)
+            _same(got, base, what)
+            for k in counters:
+                assert gt[k] == st[k], "%s: closest hit %s" % (what, k)
+                assert go[k] == so[k], "%s: occlusion %s" % (what, k)
+    finally:
+        for k, v in defaults:
+            renderer.set_option(k, v)
+        renderer.set_counting(False)
+    pick = np.sort(np.random.default_rng(42).choice(n, 2000, replace=False))
+    O = oracle.OracleScene(dragon["meshes"], dragon["lights"], dragon["materials"])
+    try:
+        hits = _check_against_oracle(oracle, O, dragon, rays[pick], {k: base[k][pick] for k in ("t", "uv", "inst", "prim")}, base["occ"][pick])
+    finally:
+        O.close()
+    assert 200 < hits < 1800, "the sample holds hits and misses (%d hits)" % hits
+
+
+@pytest.mark.gpu
 def test_tree_independence(pkg, scenes, dragon, renderer):
     """The same queries over the GPU-built LBVH give identical results, except for the boundary rays of include/crt_hip.h:
     a ray lying in a face of the boxes or starting on a surface can resolve differently where the two trees put their boxes
