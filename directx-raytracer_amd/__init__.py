@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "crt_closest_points_device", "crt_closest_points", "crt_count_hits_device", "crt_count_hits", "crt_occupancy_device", "crt_occupancy",
     "crt_update_vertices", "crt_update_vertices_device", "crt_set_mesh_transform", "crt_refit", "crt_mesh_vertices",
     "crt_rebuild", "crt_list_hits_device", "crt_list_hits", "crt_debug_list_phases",
+    "crt_shade_rays_device", "crt_shade_rays",
 ]
 
 
@@ -219,6 +220,8 @@ def lib():
         "crt_list_hits_device": (C.c_int, [vp, u32, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
         "crt_list_hits": (C.c_int, [vp, u32, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
         "crt_debug_list_phases": (C.c_int, [vp, vp]),
+        "crt_shade_rays_device": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "crt_shade_rays": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     assert set(sig) == set(ABI_SYMBOLS)
     for name, (res, args) in sig.items():
@@ -789,6 +792,33 @@ class Renderer:
         st = FrameStats() if stats else None
         self._ok(lib().crt_occluded_rays_device(self.h, int(n), d_rays, d_occluded, C.byref(st) if stats else None),
                  "crt_occluded_rays_device")
+        return st.as_dict() if stats else None
+
+    # ---- shaded ray queries (include/crt_hip.h): the closest hit of every record shaded in the current mode (0..100)
+    def shade_rays(self, rays, want=("rgb", "normal", "albedo", "t", "uv", "inst", "prim")):
+        """colour, shading normal and albedo at the closest hit of every ray (host buffers, synchronous).  Returns a dict of the
+        wanted arrays -- rgb / normal / albedo (N, 3) float32 (miss: the miss colour, zero, zero) and the arrays of trace_rays
+        -- plus 'stats'."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = len(r)
+        shapes = {"rgb": ((n, 3), np.float32), "normal": ((n, 3), np.float32), "albedo": ((n, 3), np.float32), "t": ((n,), np.float32),
+                  "uv": ((n, 2), np.float32), "inst": ((n,), np.uint32), "prim": ((n,), np.uint32)}
+        out = {k: np.zeros(*shapes[k]) for k in shapes if k in want}
+        st = FrameStats()
+
+        def p(k):
+            return out[k].ctypes.data if k in out else None
+        self._ok(lib().crt_shade_rays(self.h, n, r.ctypes.data, p("rgb"), p("normal"), p("albedo"), p("t"), p("uv"), p("inst"), p("prim"),
+                                      C.byref(st)), "crt_shade_rays")
+        out["stats"] = st.as_dict()
+        return out
+
+    def shade_rays_device(self, n, d_rays, d_rgb=None, d_normal=None, d_albedo=None, d_t=None, d_uv=None, d_inst=None, d_prim=None,
+                          stats=False):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_shade_rays_device(self.h, int(n), d_rays, d_rgb, d_normal, d_albedo, d_t, d_uv, d_inst, d_prim,
+                                             C.byref(st) if stats else None), "crt_shade_rays_device")
         return st.as_dict() if stats else None
 
     # ---- point queries (include/crt_hip.h): records of 4 floats {x, y, z, rmax}, see make_points

@@ -212,8 +212,8 @@ struct crt_ctx {
         uint32_t serial = 0;
     } rayArena[kRing];
     uint32_t raySerial = 0;
-    uint32_t rayResident[6] = {};        // resident workgroups of each query kernel (QueryKind) on this device ...
-    uint32_t rayResidentEntries[6] = {}; // ... for this many LDS stack entries
+    uint32_t rayResident[7] = {};        // resident workgroups of each query kernel (QueryKind) on this device ...
+    uint32_t rayResidentEntries[7] = {}; // ... for this many LDS stack entries
     void* dRayStage = nullptr; // the host entry points' records and outputs, grown on demand
     size_t rayStageBytes = 0;
     // crt_list_hits*: the host form's record arrays (grown on demand, apart from dRayStage, which holds its rays and offsets
@@ -1291,11 +1291,13 @@ int crt_accumulated_samples(const crt_ctx* c, uint32_t* samples)
 
 namespace {
 
-// Batched ray and point queries.  A query is n records of one kind (32-byte rays or 16-byte points) and up to five outputs
+// Batched ray and point queries.  A query is n records of one kind (32-byte rays or 16-byte points) and up to seven outputs
 // of a fixed size per record; every kind runs one persistent kernel (ray_kernels.hip, point_kernels.hip) over an arena of
 // the context.
 enum QueryKind { kQueryClosestHit = 0, kQueryOcclusion = 1, kQueryClosestPoint = 2, kQueryCount = 3, kQueryOccupancy = 4,
-                 kQueryListFill = 5 /* the second traversal of crt_list_hits*: a kernel of its own, not an entry point */ };
+                 kQueryListFill = 5 /* the second traversal of crt_list_hits*: a kernel of its own, not an entry point */,
+                 kQueryShade = 6 };
+constexpr int kQueryOutputs = 7; // the most any kind has (crt_shade_rays*)
 struct QueryOutput {
     void* p = nullptr;
     uint32_t bytes = 0; // per record
@@ -1306,7 +1308,7 @@ struct QuerySpec {
     QueryKind kind;
     uint32_t recordBytes;
     const char* outputNames; // for the alignment message
-    QueryOutput out[5];      // the kind's outputs, in a fixed order; NULL = not wanted
+    QueryOutput out[kQueryOutputs]; // the kind's outputs, in a fixed order; NULL = not wanted
 };
 
 QuerySpec rayQuerySpec(const char* what, bool occlusion, void* t, void* uv, void* inst, void* prim, void* occluded)
@@ -1322,11 +1324,18 @@ QuerySpec rayQuerySpec(const char* what, bool occlusion, void* t, void* uv, void
     return s;
 }
 
-// what every query entry point checks before anything is launched
-int checkQuery(crt_ctx* c, const char* what)
+// what every query entry point checks before anything is launched.  A shaded query (crt_shade_rays*) promises that a failed
+// call launches nothing: its refit follows its argument checks (queryDevice / queryHost) instead of coming here
+int checkQuery(crt_ctx* c, const QuerySpec& s)
 {
+    const char* what = s.what;
     if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
     if (!c->haveScene) return fail(c, CRT_ESTATE, "%s: no scene uploaded: call crt_upload_scene first", what);
+    if (s.kind == kQueryShade) {
+        if (c->mode >= 200u)
+            return fail(c, CRT_EINVAL, "%s: shading mode %u (path tracing) is not available for caller-supplied rays: set a mode below 200", what, c->mode);
+        return CRT_OK;
+    }
     return applyRefit(c, nullptr);
 }
 
@@ -1362,6 +1371,7 @@ int queryGrid(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t& stack_entries, u
         case kQueryCount: r = crt::pointQueryResident(crt::kPointCount, stack_entries); break;
         case kQueryOccupancy: r = crt::pointQueryResident(crt::kPointOccupancy, stack_entries); break;
         case kQueryListFill: r = crt::listFillResident(stack_entries); break;
+        case kQueryShade: r = crt::shadeQueryResident(stack_entries); break;
         }
         c->rayResident[kind] = r;
         c->rayResidentEntries[kind] = stack_entries;
@@ -1451,10 +1461,11 @@ int endQuery(crt_ctx* c, QueryKind kind, uint32_t n, const QueryLaunch& ql, int 
         if (kind == kQueryOcclusion) stats->rays_shadow = n;
         else stats->rays_primary = kind == kQueryOccupancy ? 3ull * n : n;
         if (c->counting) {
-            unsigned long long host[2] = { 0, 0 };
+            unsigned long long host[3] = { 0, 0, 0 };
             HIP_TRY(c, hipMemcpy(host, ql.counters, sizeof(host), hipMemcpyDeviceToHost));
             stats->nodes_visited = host[0];
             stats->tris_tested = host[1];
+            if (kind == kQueryShade) stats->rays_shadow = host[2]; // the shadow rays traced (mode 100)
         }
     }
     return CRT_OK;
@@ -1479,7 +1490,7 @@ crt::QueryCommon queryCommon(const crt_ctx* c, const QueryLaunch& ql, const void
     return q;
 }
 
-int runRayQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_rays, void* const d[5], crt_frame_stats* stats)
+int runRayQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_rays, void* const d[kQueryOutputs], crt_frame_stats* stats)
 {
     const bool occlusion = s.kind == kQueryOcclusion;
     crt::RayQueryParams q;
@@ -1508,7 +1519,7 @@ float pointPad(const crt_ctx* c)
     return static_cast<float>(std::sqrt(dd) * 0x1p-18 * (1.0 + 0x1p-20));
 }
 
-int runPointQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, void* const d[5], crt_frame_stats* stats)
+int runPointQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, void* const d[kQueryOutputs], crt_frame_stats* stats)
 {
     const crt::PointQueryKind pk = s.kind == kQueryClosestPoint ? crt::kPointClosest : (s.kind == kQueryCount ? crt::kPointCount : crt::kPointOccupancy);
     crt::PointQueryParams q;
@@ -1531,8 +1542,41 @@ int runPointQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_reco
     return endQuery(c, s.kind, n, ql, crt::launchPointQuery(q, pk, c->counting, ql.grid, c->stream), stats);
 }
 
-int runKind(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, void* const d[5], crt_frame_stats* stats)
+// crt_shade_rays*: the closest hit and the context's shading mode at it (shade_kernels.hip)
+int runShadeQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_rays, void* const d[kQueryOutputs], crt_frame_stats* stats)
 {
+    crt::ShadeQueryParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.rgb = static_cast<float*>(d[0]);
+    q.normal = static_cast<float*>(d[1]);
+    q.albedo = static_cast<float*>(d[2]);
+    q.t = static_cast<float*>(d[3]);
+    q.uv = static_cast<float*>(d[4]);
+    q.inst = static_cast<uint32_t*>(d[5]);
+    q.prim = static_cast<uint32_t*>(d[6]);
+    q.shade = c->dShade; // as fillParams
+    q.lights = c->dLights;
+    q.mats = c->dMats;
+    q.uvs = c->dUvs;
+    q.textures = c->dTextures;
+    q.texels = static_cast<const unsigned char*>(c->dTexels);
+    q.n_textures = c->nTextures;
+    q.n_lights = c->nLights;
+    q.n_mats = c->nMats;
+    crt::copyBytes(q.miss, c->miss, sizeof(q.miss));
+    q.mode = c->mode;
+    q.phong_ks = static_cast<float>(c->phongKsPermille) / 1000.0f;
+    q.phong_exp = c->phongExp;
+    q.inner_min_any = c->tuneInnerMinAny;
+    QueryLaunch ql;
+    if (const int rc = beginQuery(c, s.kind, n, 1u, stats, ql)) return rc;
+    q.c = queryCommon(c, ql, d_rays, n, c->tuneInnerMin);
+    return endQuery(c, s.kind, n, ql, crt::launchShadeQuery(q, c->counting, ql.grid, c->stream), stats);
+}
+
+int runKind(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, void* const d[kQueryOutputs], crt_frame_stats* stats)
+{
+    if (s.kind == kQueryShade) return runShadeQuery(c, s, n, d_records, d, stats);
     if (s.kind == kQueryClosestHit || s.kind == kQueryOcclusion) return runRayQuery(c, s, n, d_records, d, stats);
     return runPointQuery(c, s, n, d_records, d, stats);
 }
@@ -1546,7 +1590,7 @@ void zeroStats(crt_frame_stats* stats, std::chrono::steady_clock::time_point t0)
 
 int queryDevice(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, crt_frame_stats* stats)
 {
-    int rc = checkQuery(c, s.what);
+    int rc = checkQuery(c, s);
     if (rc) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     if (n == 0u) { // nothing to look at, nothing launched
@@ -1554,7 +1598,9 @@ int queryDevice(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_record
         return CRT_OK;
     }
     if ((rc = checkDeviceOutputs(c, s, d_records)) != CRT_OK) return rc;
-    void* const d[5] = { s.out[0].p, s.out[1].p, s.out[2].p, s.out[3].p, s.out[4].p };
+    if (s.kind == kQueryShade && (rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    void* d[kQueryOutputs];
+    for (int i = 0; i < kQueryOutputs; i++) d[i] = s.out[i].p;
     if ((rc = runKind(c, s, n, d_records, d, stats)) != CRT_OK) return rc;
     if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CRT_OK;
@@ -1563,7 +1609,7 @@ int queryDevice(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_record
 // host buffers: staged through the context's device buffer {records | outputs in order}; synchronous
 int queryHost(crt_ctx* c, const QuerySpec& s, uint32_t n, const float* records, crt_frame_stats* stats)
 {
-    int rc = checkQuery(c, s.what);
+    int rc = checkQuery(c, s);
     if (rc) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     if (n == 0u) {
@@ -1572,10 +1618,11 @@ int queryHost(crt_ctx* c, const QuerySpec& s, uint32_t n, const float* records, 
     }
     if (!records) return fail(c, CRT_EINVAL, "%s: record buffer is NULL", s.what);
     if ((rc = checkOutputs(c, s)) != CRT_OK) return rc;
+    if (s.kind == kQueryShade && (rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
     const size_t nn = n;
     auto up = [](size_t b) { return (b + 255u) & ~static_cast<size_t>(255u); };
-    size_t bytes[5], off[5], total = up(nn * s.recordBytes);
-    for (int i = 0; i < 5; i++) {
+    size_t bytes[kQueryOutputs], off[kQueryOutputs], total = up(nn * s.recordBytes);
+    for (int i = 0; i < kQueryOutputs; i++) {
         bytes[i] = s.out[i].p ? nn * s.out[i].bytes : 0u;
         off[i] = total;
         total += up(bytes[i]);
@@ -1590,12 +1637,12 @@ int queryHost(crt_ctx* c, const QuerySpec& s, uint32_t n, const float* records, 
         c->rayStageBytes = total;
     }
     unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
-    void* devPtr[5];
-    for (int i = 0; i < 5; i++) devPtr[i] = bytes[i] ? base + off[i] : nullptr;
+    void* devPtr[kQueryOutputs];
+    for (int i = 0; i < kQueryOutputs; i++) devPtr[i] = bytes[i] ? base + off[i] : nullptr;
     HIP_TRY(c, hipMemcpyAsync(base, records, nn * s.recordBytes, hipMemcpyHostToDevice, c->stream));
     crt_frame_stats local;
     if ((rc = runKind(c, s, n, base, devPtr, stats ? stats : &local)) != CRT_OK) return rc;
-    for (int i = 0; i < 5; i++)
+    for (int i = 0; i < kQueryOutputs; i++)
         if (bytes[i]) HIP_TRY(c, hipMemcpyAsync(s.out[i].p, devPtr[i], bytes[i], hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1610,6 +1657,18 @@ QuerySpec closestPointSpec(const char* what, void* dist, void* point, void* uv, 
     s.out[2] = { uv, 8u, 8u };
     s.out[3] = { inst, 4u, 4u };
     s.out[4] = { prim, 4u, 4u };
+    return s;
+}
+QuerySpec shadeSpec(const char* what, void* rgb, void* normal, void* albedo, void* t, void* uv, void* inst, void* prim)
+{
+    QuerySpec s{ what, kQueryShade, 32u, "rgb / normal / albedo / t / uv / inst / prim", {} };
+    s.out[0] = { rgb, 12u, 4u };
+    s.out[1] = { normal, 12u, 4u };
+    s.out[2] = { albedo, 12u, 4u };
+    s.out[3] = { t, 4u, 4u };
+    s.out[4] = { uv, 8u, 8u };
+    s.out[5] = { inst, 4u, 4u };
+    s.out[6] = { prim, 4u, 4u };
     return s;
 }
 QuerySpec countSpec(const char* what, void* count) { return QuerySpec{ what, kQueryCount, 32u, "count", { { count, 4u, 4u } } }; }
@@ -1741,6 +1800,18 @@ int crt_trace_rays(crt_ctx* c, uint32_t n, const float* rays, float* t, float* u
 int crt_occluded_rays(crt_ctx* c, uint32_t n, const float* rays, uint8_t* occluded, crt_frame_stats* stats)
 {
     return queryHost(c, rayQuerySpec("crt_occluded_rays", true, nullptr, nullptr, nullptr, nullptr, occluded), n, rays, stats);
+}
+
+int crt_shade_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_rgb, void* d_normal, void* d_albedo, void* d_t, void* d_uv,
+                          void* d_inst, void* d_prim, crt_frame_stats* stats)
+{
+    return queryDevice(c, shadeSpec("crt_shade_rays_device", d_rgb, d_normal, d_albedo, d_t, d_uv, d_inst, d_prim), n, d_rays, stats);
+}
+
+int crt_shade_rays(crt_ctx* c, uint32_t n, const float* rays, float* rgb, float* normal, float* albedo, float* t, float* uv, uint32_t* inst,
+                   uint32_t* prim, crt_frame_stats* stats)
+{
+    return queryHost(c, shadeSpec("crt_shade_rays", rgb, normal, albedo, t, uv, inst, prim), n, rays, stats);
 }
 
 int crt_closest_points_device(crt_ctx* c, uint32_t n, const void* d_points, void* d_dist, void* d_point, void* d_uv, void* d_inst,

@@ -157,6 +157,33 @@ struct RayQueryParams {
 // workgroups of the closest-hit / occlusion query kernel the current device holds at once (0: unknown)
 uint32_t rayQueryResident(bool occlusion, uint32_t stack_entries);
 int launchRayQuery(const RayQueryParams& q, bool occlusion, bool counting, uint32_t grid, ihipStream_t* stream);
+// shaded ray queries (shade_kernels.hip; crt_shade_rays*): closest hit of n ray records, then the context's shading mode at
+// the hit -- the frames' shading (shading.hip.h) for caller-supplied rays.  Every output is nullable
+struct ShadeQueryParams {
+    QueryCommon c;                // records: the rays; inner_min: tune_inner_min (the closest-hit phase)
+    uint32_t inner_min_any;       // tune_inner_min_any (the shadow-ray phases)
+    // the scene's shading tables and the shading state, as RenderParams'
+    const void* shade;
+    const void* lights;
+    const void* mats;
+    const void* uvs;
+    const void* textures;
+    const unsigned char* texels;
+    uint32_t n_textures, n_lights, n_mats;
+    float miss[3];
+    uint32_t mode;                // < 200
+    float phong_ks;
+    uint32_t phong_exp;
+    float* rgb;                   // 3 floats per ray: the mode's colour, the miss colour on a miss
+    float* normal;                // 3 floats per ray: Surface::N, zero on a miss
+    float* albedo;                // 3 floats per ray: Surface::albedo, zero on a miss
+    float* t;                     // as RayQueryParams'
+    float* uv;
+    uint32_t* inst;
+    uint32_t* prim;
+};
+uint32_t shadeQueryResident(uint32_t stack_entries);
+int launchShadeQuery(const ShadeQueryParams& q, bool counting, uint32_t grid, ihipStream_t* stream);
 // point queries (point_kernels.hip; crt_closest_points* / crt_count_hits* / crt_occupancy*): n caller-supplied records, point
 // records of 4 floats {x, y, z, rmax} (closest point, occupancy) or ray records (hit counts), over the 4-wide tree
 enum PointQueryKind { kPointClosest = 0, kPointCount = 1, kPointOccupancy = 2 };

@@ -152,6 +152,30 @@ void Renderer::traceRays(const float* rays, size_t n, RayHit* out)
     for (size_t i = 0; i < n; i++) out[i] = RayHit{ t[i], uv[2 * i], uv[2 * i + 1], inst[i], prim[i] };
 }
 
+void Renderer::shadeRays(const float* rays, size_t n, ShadedHit* out)
+{
+    if (!ctx) throw std::runtime_error("shadeRays before prepareForRendering");
+    if (n > UINT32_MAX) throw std::runtime_error("shadeRays: more than 2^32 - 1 rays");
+    if (isChangedShadingMode) { // a mode set since the last frame applies here as it would to the next frame
+        check(crt_set_shading_mode(ctx, currentShadingMode), "crt_set_shading_mode");
+        isChangedShadingMode = false;
+    }
+    if (n == 0) return;
+    const uint32_t m = static_cast<uint32_t>(n);
+    std::vector<float> rgb(3 * n), normal(3 * n), albedo(3 * n), t(n), uv(2 * n);
+    std::vector<uint32_t> inst(n), prim(n);
+    check(crt_shade_rays(ctx, m, rays, rgb.data(), normal.data(), albedo.data(), t.data(), uv.data(), inst.data(), prim.data(), nullptr), "crt_shade_rays");
+    for (size_t i = 0; i < n; i++) {
+        ShadedHit& o = out[i];
+        for (int k = 0; k < 3; k++) {
+            o.rgb[k] = rgb[3 * i + k];
+            o.normal[k] = normal[3 * i + k];
+            o.albedo[k] = albedo[3 * i + k];
+        }
+        o.hit = RayHit{ t[i], uv[2 * i], uv[2 * i + 1], inst[i], prim[i] };
+    }
+}
+
 void Renderer::listHits(const float* rays, size_t n, std::vector<uint64_t>& offsets, std::vector<RayHit>& hits)
 {
     if (!ctx) throw std::runtime_error("listHits before prepareForRendering");

@@ -56,6 +56,13 @@ public:
     };
     void traceRays(const float* rays, size_t n, RayHit* out);
     void occluded(const float* rays, size_t n, uint8_t* out); // 1 = some triangle lies in (tmin, tmax)
+    // the closest hit shaded in the current mode (crt_shade_rays, synchronous; modes 0..100): colour, shading normal and albedo
+    // beside the hit.  A miss reports the miss colour, a zero normal and a zero albedo.
+    struct ShadedHit {
+        float rgb[3], normal[3], albedo[3];
+        RayHit hit;
+    };
+    void shadeRays(const float* rays, size_t n, ShadedHit* out);
     // every crossing of every ray, ascending in t (crt_list_hits, synchronous): the hits of ray i are hits[offsets[i]] ..
     // hits[offsets[i + 1] - 1].  One offsets-only call learns the total, a second one fills the records.
     void listHits(const float* rays, size_t n, std::vector<uint64_t>& offsets, std::vector<RayHit>& hits);

@@ -110,8 +110,10 @@ struct Surface {
     float ior;
 };
 
-template <class L>
-__device__ __forceinline__ Surface surfaceAt(const RenderParams& p, const float4* tris, const Ray& r, const Hit& h)
+// P: the parameter block holding the scene's shading tables (RenderParams; ShadeQueryParams of the shaded ray queries).  Of r
+// only o and d are read.
+template <class L, class P>
+__device__ __forceinline__ Surface surfaceAt(const P& p, const float4* tris, const Ray& r, const Hit& h)
 {
     Surface sf;
     const float4* T = L::triPtr(tris, h.tri);
@@ -180,10 +182,45 @@ __device__ __forceinline__ float powUint(float x, uint32_t n)
     return result;
 }
 
-// direct light at Po: one any-hit shadow ray per light with a positive cosine (oracle: direct_light).  PHONG (mode 100
-// only): plus the specular term ks * I / (4 pi r^2) * max(0, R . view)^n, R = the light direction mirrored about N.
-// direct light at Po: one any-hit shadow ray per light with a positive cosine (oracle: direct_light).  PHONG (mode 100
-// only): plus the specular term ks * I / (4 pi r^2) * max(0, R . view)^n, R = the light direction mirrored about N.
+// One light seen from Po with normal N: squared distance, distance, unit direction, clamped cosine.  A shadow ray is traced
+// only for cosv > 0: origin Po, direction Ld, interval (0, dist).
+struct LightTerm {
+    F3 Ld;
+    float r2, dist, cosv;
+};
+__device__ __forceinline__ LightTerm lightTerm(const LightRec& Lt, F3 Po, F3 N)
+{
+    LightTerm lt;
+    const F3 Lv = sub3(f3(Lt.x, Lt.y, Lt.z), Po);
+    lt.r2 = dot3(Lv, Lv);
+    lt.dist = sqrtf(lt.r2);
+    const float invr = 1.0f / lt.dist;
+    lt.Ld = f3(Lv.x * invr, Lv.y * invr, Lv.z * invr);
+    lt.cosv = fmaxf(0.0f, dot3(N, lt.Ld));
+    return lt;
+}
+
+// An unoccluded light's contribution added to rgb: Lambert, and with PHONG (mode 100 only) the specular term
+// ks * I / (4 pi r^2) * max(0, R . view)^n, R = the light direction mirrored about N.  P: the parameter block (phong_ks,
+// phong_exp).  The one statement of the per-light arithmetic: directLight below and the shaded ray queries
+// (shade_kernels.hip) both add a light through here.
+template <bool PHONG, class P>
+__device__ __forceinline__ void addLight(const P& p, const LightRec& Lt, const LightTerm& lt, F3 N, F3 albedo, F3 view, F3& rgb)
+{
+    const float k = (Lt.intensity / (kFourPi * lt.r2)) * lt.cosv;
+    rgb.x = fmaf(albedo.x, k, rgb.x);
+    rgb.y = fmaf(albedo.y, k, rgb.y);
+    rgb.z = fmaf(albedo.z, k, rgb.z);
+    if (PHONG && p.phong_ks > 0.0f) {
+        const float nl2 = 2.0f * dot3(N, lt.Ld);
+        const F3 R = f3(fmaf(nl2, N.x, -lt.Ld.x), fmaf(nl2, N.y, -lt.Ld.y), fmaf(nl2, N.z, -lt.Ld.z));
+        const float rv = fmaxf(0.0f, dot3(R, view));
+        const float sp = (p.phong_ks * (Lt.intensity / (kFourPi * lt.r2))) * powUint(rv, p.phong_exp);
+        rgb.x += sp; rgb.y += sp; rgb.z += sp;
+    }
+}
+
+// direct light at Po: one any-hit shadow ray per light with a positive cosine (oracle: direct_light)
 template <bool COUNT, class L, bool PHONG>
 __device__ __forceinline__ F3 directLight(const RenderParams& p, const float4* nodes, const float4* tris, F3 Po, F3 N, F3 albedo, F3 view,
                                           Stack& stack, uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, uint32_t& cntShadow)
@@ -192,29 +229,12 @@ __device__ __forceinline__ F3 directLight(const RenderParams& p, const float4* n
     const LightRec* lights = reinterpret_cast<const LightRec*>(p.lights);
     for (uint32_t li = 0; li < p.n_lights; li++) {
         const LightRec Lt = lights[li];
-        const F3 Lv = sub3(f3(Lt.x, Lt.y, Lt.z), Po);
-        const float r2 = dot3(Lv, Lv);
-        const float dist = sqrtf(r2);
-        const float invr = 1.0f / dist;
-        const F3 Ld = f3(Lv.x * invr, Lv.y * invr, Lv.z * invr);
-        const float cosv = fmaxf(0.0f, dot3(N, Ld));
-        if (cosv > 0.0f) {
-            const Ray sr = makeRay(Po, Ld);
+        const LightTerm lt = lightTerm(Lt, Po, N);
+        if (lt.cosv > 0.0f) {
+            const Ray sr = makeRay(Po, lt.Ld);
             if (COUNT) cntShadow++;
-            const bool occluded = traceAny<COUNT, L, true>(nodes, tris, p.n_nodes, sr, 0.0f, dist, stack, static_cast<int>(p.tune_inner_min_any), iters, cntNodes, cntTris, p.planes);
-            if (!occluded) {
-                const float k = (Lt.intensity / (kFourPi * r2)) * cosv;
-                rgb.x = fmaf(albedo.x, k, rgb.x);
-                rgb.y = fmaf(albedo.y, k, rgb.y);
-                rgb.z = fmaf(albedo.z, k, rgb.z);
-                if (PHONG && p.phong_ks > 0.0f) {
-                    const float nl2 = 2.0f * dot3(N, Ld);
-                    const F3 R = f3(fmaf(nl2, N.x, -Ld.x), fmaf(nl2, N.y, -Ld.y), fmaf(nl2, N.z, -Ld.z));
-                    const float rv = fmaxf(0.0f, dot3(R, view));
-                    const float sp = (p.phong_ks * (Lt.intensity / (kFourPi * r2))) * powUint(rv, p.phong_exp);
-                    rgb.x += sp; rgb.y += sp; rgb.z += sp;
-                }
-            }
+            const bool occluded = traceAny<COUNT, L, true>(nodes, tris, p.n_nodes, sr, 0.0f, lt.dist, stack, static_cast<int>(p.tune_inner_min_any), iters, cntNodes, cntTris, p.planes);
+            if (!occluded) addLight<PHONG>(p, Lt, lt, N, albedo, view, rgb);
         }
     }
     return rgb;

@@ -193,30 +193,13 @@ __device__ __forceinline__ void renderSplitQuarter(const RenderParams& p, const 
         const LightRec* lights = reinterpret_cast<const LightRec*>(p.lights);
         for (uint32_t li = 0; li < p.n_lights; li++) {
             const LightRec Lt = lights[li];
-            const F3 Lv = sub3(f3(Lt.x, Lt.y, Lt.z), Po);
-            const float r2 = dot3(Lv, Lv);
-            const float dist = sqrtf(r2);
-            const float invr = 1.0f / dist;
-            const F3 Ld = f3(Lv.x * invr, Lv.y * invr, Lv.z * invr);
-            const float cosv = fmaxf(0.0f, dot3(sf.N, Ld));
-            const bool need = hit && cosv > 0.0f;
+            const LightTerm lt = lightTerm(Lt, Po, sf.N);
+            const bool need = hit && lt.cosv > 0.0f;
             if (COUNT && need) cntShadow++;
             Hit unusedHit;
             bool occluded;
-            splitStream<COUNT, L, false>(nodes, tris, p.n_nodes, Po, Ld, 0.0f, dist, need, 0.0f, dist, raysLog2, segsLog2, stack, static_cast<int>(p.tune_inner_min_any), unusedHit, occluded, iters, cntNodes, cntTris);
-            if (need && !occluded) {
-                const float k = (Lt.intensity / (kFourPi * r2)) * cosv;
-                rgb.x = fmaf(sf.albedo.x, k, rgb.x);
-                rgb.y = fmaf(sf.albedo.y, k, rgb.y);
-                rgb.z = fmaf(sf.albedo.z, k, rgb.z);
-                if (PHONG && p.phong_ks > 0.0f) {
-                    const float nl2 = 2.0f * dot3(sf.N, Ld);
-                    const F3 R = f3(fmaf(nl2, sf.N.x, -Ld.x), fmaf(nl2, sf.N.y, -Ld.y), fmaf(nl2, sf.N.z, -Ld.z));
-                    const float rv = fmaxf(0.0f, dot3(R, view));
-                    const float sp = (p.phong_ks * (Lt.intensity / (kFourPi * r2))) * powUint(rv, p.phong_exp);
-                    rgb.x += sp; rgb.y += sp; rgb.z += sp;
-                }
-            }
+            splitStream<COUNT, L, false>(nodes, tris, p.n_nodes, Po, lt.Ld, 0.0f, lt.dist, need, 0.0f, lt.dist, raysLog2, segsLog2, stack, static_cast<int>(p.tune_inner_min_any), unusedHit, occluded, iters, cntNodes, cntTris);
+            if (need && !occluded) addLight<PHONG>(p, Lt, lt, sf.N, sf.albedo, view, rgb);
         }
         if (hit) col = rgb;
     } else if (hit) {

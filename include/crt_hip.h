@@ -410,6 +410,51 @@ int crt_trace_rays(crt_ctx* ctx, uint32_t n, const float* rays, float* t, float*
                    crt_frame_stats* stats);
 int crt_occluded_rays(crt_ctx* ctx, uint32_t n, const float* rays, uint8_t* occluded, crt_frame_stats* stats);
 
+/* ---- shaded ray queries: colour, normal and albedo for caller-supplied rays (DXR lets any shader call TraceRay and shade
+ * the result; the reference only does so from its own rayGen, R/HLSL/ray_tracing_shaders.hlsl:21-169; Open3D's cast_rays
+ * returns primitive_normals).  A fisheye or equirectangular sensor, a calibrated lens, a lidar's return intensity, light
+ * fields, probes: the frames' shading without the frames' pinhole camera, in one launch.
+ * - Rays: the 8-float records of crt_trace_rays, with the same NaN / empty-interval / zero-direction rules and the same range
+ *   of direction magnitudes; they are traced prescaled by 2^e in the same way.  The hit is exactly the one crt_trace_rays
+ *   reports for that record: t / uv / inst / prim are its outputs bit for bit, each optional.  At least one of the seven
+ *   outputs must be non-NULL.
+ * - Mode: the context's current shading mode (crt_set_shading_mode) applies.  Modes 0..99 are the seven reference modes
+ *   (7..99 behave as 6, as in the frames); mode 100 is Lambert with optional Phong (options "phong_ks", "phong_exponent") and
+ *   one shadow ray per light.  Mode 200 returns CRT_EINVAL and launches nothing: path tracing of caller rays would need a
+ *   sample-indexing contract of its own.
+ * - What the shading sees: the record's own origin and direction and the unscaled t (t' 2^-e, the value reported) -- exactly
+ *   what the frame kernels hand the same functions for a camera ray.  Nothing is normalised: the hit point is o + d * t per
+ *   component, the entering test is the sign of dot(N, d), Phong's view vector is -d.  So a record that holds a frame's camera
+ *   ray (origin = the camera position, direction = the unit vector the frame's rayGen produces for the pixel, tmin = 0.001,
+ *   tmax = 10000) gives that pixel's rgb_f32 bit for bit.  Mode 5 (a function of t) and the Phong term (of -d) depend on
+ *   |d|: a caller who wants the frames' semantics passes unit directions.
+ * - Shadow rays of mode 100 are the frames': origin = the hit point moved 1e-3 along the shading normal, unit direction to the
+ *   light, interval (0, distance), boxes culled against distance (1 + 2^-18); traced only for a positive cosine, in light
+ *   order, and accumulated with the frames' fmaf sequence.  They are not prescaled (their direction is a unit vector).
+ * - rgb (3 floats per ray): on a hit the mode's colour before quantisation; on a miss or an untraced record the miss colour
+ *   (crt_set_miss_color).
+ * - normal (3 floats per ray): the shading normal of the frames' surface evaluation -- normalised, flipped to face the ray;
+ *   the geometric normal when the material is flat or the mesh has no usable vertex normals.  Miss: (0, 0, 0).
+ * - albedo (3 floats per ray): the material's colour, or its texture's colour where it has one; (1, 1, 1) for a material
+ *   index out of range, as in the frames.  Miss: (0, 0, 0).
+ * - normal and albedo are available in every mode 0..100; a debug mode evaluates the surface only when one of them is asked for.
+ * - Pending refits are applied first.  Camera, mode, accumulation sums, launch orders and frame outputs are untouched.
+ *   Results do not depend on the order of the records, on scheduling or on the options inner_min, inner_min_any and
+ *   stack_entries.  The boundary-ray limit of the ray queries applies unchanged; inert triangles are never hit and never
+ *   occlude.
+ * - n = 0 returns CRT_OK and launches nothing.  CRT_ESTATE without a scene.  CRT_EINVAL for a NULL ctx, NULL rays with n > 0,
+ *   all outputs NULL, mode 200, or a misaligned device pointer (rays 16-byte, uv 8-byte, everything else 4-byte).  These
+ *   checks come before the refit: a failed call launches nothing.
+ * - stats (may be NULL): kernel_ms, total_ms, rays_primary = n; with crt_set_counting(ctx, 1) rays_shadow = the shadow rays
+ *   traced and nodes_visited / tris_tested = the closest-hit and shadow traversals together, counted as the frames count
+ *   them: for a buffer of a frame's camera rays they are the oracle's statistics of that frame in that mode.
+ * *_device: device pointers, asynchronous on the context's stream (crt_set_stream) unless stats != NULL.  Host variant:
+ * synchronous, staged through the context's query staging buffer. */
+int crt_shade_rays_device(crt_ctx* ctx, uint32_t n, const void* d_rays, void* d_rgb, void* d_normal, void* d_albedo, void* d_t,
+                          void* d_uv, void* d_inst, void* d_prim, crt_frame_stats* stats);
+int crt_shade_rays(crt_ctx* ctx, uint32_t n, const float* rays, float* rgb, float* normal, float* albedo, float* t, float* uv,
+                   uint32_t* inst, uint32_t* prim, crt_frame_stats* stats);
+
 /* ---- point queries: closest surface point, hit counts, occupancy (no reference counterpart; the set of Open3D's
  * RaycastingScene: compute_closest_points / compute_distance / compute_signed_distance / compute_occupancy /
  * count_intersections).  SDF and occupancy training data, collision margins, snapping a point to the surface.
