@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "crt_update_vertices", "crt_update_vertices_device", "crt_set_mesh_transform", "crt_refit", "crt_mesh_vertices",
     "crt_rebuild", "crt_list_hits_device", "crt_list_hits", "crt_debug_list_phases",
     "crt_shade_rays_device", "crt_shade_rays",
+    "crt_path_rays_device", "crt_path_rays",
 ]
 
 
@@ -222,6 +223,8 @@ def lib():
         "crt_debug_list_phases": (C.c_int, [vp, vp]),
         "crt_shade_rays_device": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "crt_shade_rays": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "crt_path_rays_device": (C.c_int, [vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "crt_path_rays": (C.c_int, [vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
     }
     assert set(sig) == set(ABI_SYMBOLS)
     for name, (res, args) in sig.items():
@@ -254,6 +257,28 @@ def make_rays(origins, directions, tmin=0.0, tmax=np.inf):
     out[:, 4:7] = d
     out[:, 7] = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,))
     return out
+
+
+def _pcg_hash(v):
+    """the integer hash of the path tracer's RNG on uint32 arrays"""
+    state = v * np.uint32(747796405) + np.uint32(2891336453)
+    word = ((state >> ((state >> np.uint32(28)) + np.uint32(4))) ^ state) * np.uint32(277803737)
+    return (word >> np.uint32(22)) ^ word
+
+
+def path_jitter(ids, sample, seed):
+    """(jx, jy), float32 arrays in [0, 1): the two draws the path of (id, sample) takes before its first bounce draw -- in a
+    frame the jitter of pixel `id` inside its pixel; Renderer.path_rays leaves them unused (include/crt_hip.h, "sample
+    indexing").  ids: uint32 array (or scalar); sample and seed: integers.  Pure numpy."""
+    with np.errstate(over="ignore"):
+        ids = np.atleast_1d(np.asarray(ids, dtype=np.uint32))
+        seed_h = _pcg_hash(np.asarray([int(seed) & 0xFFFFFFFF], dtype=np.uint32))
+        st = _pcg_hash(ids ^ _pcg_hash(np.asarray([int(sample) & 0xFFFFFFFF], dtype=np.uint32) + seed_h))
+        st = _pcg_hash(st)
+        jx = (st >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+        st = _pcg_hash(st)
+        jy = (st >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return jx, jy
 
 
 def make_points(xyz, rmax=np.inf):
@@ -819,6 +844,44 @@ class Renderer:
         st = FrameStats() if stats else None
         self._ok(lib().crt_shade_rays_device(self.h, int(n), d_rays, d_rgb, d_normal, d_albedo, d_t, d_uv, d_inst, d_prim,
                                              C.byref(st) if stats else None), "crt_shade_rays_device")
+        return st.as_dict() if stats else None
+
+    # ---- path-traced ray queries (include/crt_hip.h): mode-200 radiance of every record, whatever the current mode
+    def path_rays(self, rays, ids=None, first_sample=0, n_samples=1, sums=None, want=("rgb", "t", "uv", "inst", "prim")):
+        """the frames' path tracing for caller-supplied rays (host buffers, synchronous): n_samples paths per record, samples
+        first_sample .. first_sample + n_samples - 1 of path id ids[i] (None: i).  sums: None, or an (N, 3) float64 array that
+        carries the per-record sample sums from call to call (read when first_sample > 0, always written; rgb is then the mean
+        over first_sample + n_samples samples).  Returns a dict of the wanted arrays -- rgb (N, 3) float32 and the arrays of
+        trace_rays -- plus 'stats'."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = len(r)
+        shapes = {"rgb": ((n, 3), np.float32), "t": ((n,), np.float32), "uv": ((n, 2), np.float32), "inst": ((n,), np.uint32),
+                  "prim": ((n,), np.uint32)}
+        out = {k: np.zeros(*shapes[k]) for k in shapes if k in want}
+        i = None
+        if ids is not None:
+            i = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            if len(i) != n:
+                raise ValueError("ids must hold one uint32 per ray")
+        if sums is not None and (not isinstance(sums, np.ndarray) or sums.dtype != np.float64 or sums.shape != (n, 3)
+                                 or not sums.flags.c_contiguous or not sums.flags.writeable):
+            raise ValueError("sums must be a writeable C-contiguous (N, 3) float64 array")
+        st = FrameStats()
+
+        def p(k):
+            return out[k].ctypes.data if k in out else None
+        self._ok(lib().crt_path_rays(self.h, n, r.ctypes.data, None if i is None else i.ctypes.data, int(first_sample), int(n_samples),
+                                     p("rgb"), None if sums is None else sums.ctypes.data, p("t"), p("uv"), p("inst"), p("prim"),
+                                     C.byref(st)), "crt_path_rays")
+        out["stats"] = st.as_dict()
+        return out
+
+    def path_rays_device(self, n, d_rays, d_ids=None, first_sample=0, n_samples=1, d_rgb=None, d_sums=None, d_t=None, d_uv=None,
+                         d_inst=None, d_prim=None, stats=False):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_path_rays_device(self.h, int(n), d_rays, d_ids, int(first_sample), int(n_samples), d_rgb, d_sums, d_t, d_uv,
+                                            d_inst, d_prim, C.byref(st) if stats else None), "crt_path_rays_device")
         return st.as_dict() if stats else None
 
     # ---- point queries (include/crt_hip.h): records of 4 floats {x, y, z, rmax}, see make_points

@@ -212,8 +212,8 @@ struct crt_ctx {
         uint32_t serial = 0;
     } rayArena[kRing];
     uint32_t raySerial = 0;
-    uint32_t rayResident[7] = {};        // resident workgroups of each query kernel (QueryKind) on this device ...
-    uint32_t rayResidentEntries[7] = {}; // ... for this many LDS stack entries
+    uint32_t rayResident[8] = {};        // resident workgroups of each query kernel (QueryKind) on this device ...
+    uint32_t rayResidentEntries[8] = {}; // ... for this many LDS stack entries
     void* dRayStage = nullptr; // the host entry points' records and outputs, grown on demand
     size_t rayStageBytes = 0;
     // crt_list_hits*: the host form's record arrays (grown on demand, apart from dRayStage, which holds its rays and offsets
@@ -1296,7 +1296,7 @@ namespace {
 // the context.
 enum QueryKind { kQueryClosestHit = 0, kQueryOcclusion = 1, kQueryClosestPoint = 2, kQueryCount = 3, kQueryOccupancy = 4,
                  kQueryListFill = 5 /* the second traversal of crt_list_hits*: a kernel of its own, not an entry point */,
-                 kQueryShade = 6 };
+                 kQueryShade = 6, kQueryPath = 7 /* crt_path_rays*: passes of (record, sample) items, not a QuerySpec */ };
 constexpr int kQueryOutputs = 7; // the most any kind has (crt_shade_rays*)
 struct QueryOutput {
     void* p = nullptr;
@@ -1372,6 +1372,7 @@ int queryGrid(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t& stack_entries, u
         case kQueryOccupancy: r = crt::pointQueryResident(crt::kPointOccupancy, stack_entries); break;
         case kQueryListFill: r = crt::listFillResident(stack_entries); break;
         case kQueryShade: r = crt::shadeQueryResident(stack_entries); break;
+        case kQueryPath: r = crt::pathQueryResident(stack_entries); break;
         }
         c->rayResident[kind] = r;
         c->rayResidentEntries[kind] = stack_entries;
@@ -1461,11 +1462,12 @@ int endQuery(crt_ctx* c, QueryKind kind, uint32_t n, const QueryLaunch& ql, int 
         if (kind == kQueryOcclusion) stats->rays_shadow = n;
         else stats->rays_primary = kind == kQueryOccupancy ? 3ull * n : n;
         if (c->counting) {
-            unsigned long long host[3] = { 0, 0, 0 };
+            unsigned long long host[4] = { 0, 0, 0, 0 };
             HIP_TRY(c, hipMemcpy(host, ql.counters, sizeof(host), hipMemcpyDeviceToHost));
             stats->nodes_visited = host[0];
             stats->tris_tested = host[1];
-            if (kind == kQueryShade) stats->rays_shadow = host[2]; // the shadow rays traced (mode 100)
+            if (kind == kQueryShade || kind == kQueryPath) stats->rays_shadow = host[2]; // the shadow rays traced (mode 100; paths)
+            if (kind == kQueryPath) stats->rays_primary += host[3];                       // the bounce rays of the paths
         }
     }
     return CRT_OK;
@@ -1671,6 +1673,106 @@ QuerySpec shadeSpec(const char* what, void* rgb, void* normal, void* albedo, voi
     s.out[6] = { prim, 4u, 4u };
     return s;
 }
+// ---- crt_path_rays*: the frames' mode-200 paths for caller records (path_query_kernels.hip).  Work items are (record, sample)
+// pairs; a launch covers at most "path_pass_paths" of them (all records x a range of samples; a buffer of more records than
+// that is also cut into blocks of records), each followed by the resolve that adds the pass's samples to the running sums.
+// Everything runs over one arena between one beginQuery and one endQuery: the radiance and throughput slots and, when the
+// caller gave no sums and there is more than one pass, the n x 3 float64 sums between the passes.
+struct PathCall {
+    const void* rays;
+    const uint32_t* ids;
+    uint32_t first, samples;
+    float* rgb;
+    double* sums;
+    float* t;
+    float* uv;
+    uint32_t* inst;
+    uint32_t* prim;
+    bool anyOutput() const { return rgb || sums || t || uv || inst || prim; }
+};
+
+inline size_t pathUp(size_t b) { return (b + 255u) & ~static_cast<size_t>(255u); }
+
+// the checks that need no buffer; n = 0 ends the call after them
+int checkPathCall(crt_ctx* c, const char* what, uint32_t first, uint32_t samples)
+{
+    if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
+    if (!c->haveScene) return fail(c, CRT_ESTATE, "%s: no scene uploaded: call crt_upload_scene first", what);
+    if (samples == 0u) return fail(c, CRT_EINVAL, "%s: n_samples is 0", what);
+    if (static_cast<uint64_t>(first) + samples > (1ull << 24))
+        return fail(c, CRT_EINVAL, "%s: first_sample + n_samples = %llu exceeds 2^24", what, static_cast<unsigned long long>(first) + samples);
+    return CRT_OK;
+}
+
+int runPathQuery(crt_ctx* c, uint32_t n, const PathCall& a, crt_frame_stats* stats)
+{
+    const uint32_t cap = c->tunePathPassPaths;
+    const uint32_t blockRecords = std::min(n, cap);
+    const uint32_t passSamples = std::max(1u, std::min(a.samples, cap / blockRecords));
+    const size_t slots = static_cast<size_t>(blockRecords) * passSamples; // <= cap <= 2^25
+    const bool keepSums = passSamples < a.samples && !a.sums && a.rgb;
+    const size_t slotBytes = pathUp(slots * 16u), sumBytes = keepSums ? pathUp(static_cast<size_t>(blockRecords) * 24u) : 0u;
+
+    crt::PathQueryParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.shade = c->dShade; // as fillParams
+    q.lights = c->dLights;
+    q.mats = c->dMats;
+    q.uvs = c->dUvs;
+    q.textures = c->dTextures;
+    q.texels = static_cast<const unsigned char*>(c->dTexels);
+    q.n_textures = c->nTextures;
+    q.n_lights = c->nLights;
+    q.n_mats = c->nMats;
+    crt::copyBytes(q.miss, c->miss, sizeof(q.miss));
+    q.max_bounces = c->pathBounces;
+    q.seed = c->pathSeed;
+    q.inner_min_any = c->tuneInnerMinAny;
+    QueryLaunch ql;
+    if (const int rc = beginQuery(c, kQueryPath, static_cast<uint32_t>(slots), 1u, stats, ql, 2u * slotBytes + sumBytes)) return rc;
+    q.rad = ql.extra;
+    q.thr = ql.extra + slotBytes;
+    double* kept = keepSums ? reinterpret_cast<double*>(ql.extra + 2u * slotBytes) : nullptr;
+
+    int hrc = 0;
+    bool launched = false;
+    for (uint64_t r0 = 0; r0 < n && hrc == 0; r0 += blockRecords) {
+        const uint32_t nr = static_cast<uint32_t>(std::min<uint64_t>(blockRecords, n - r0));
+        double* sums = a.sums ? a.sums + 3u * r0 : nullptr;
+        double* running = sums ? sums : kept;
+        for (uint32_t s0 = 0; s0 < a.samples && hrc == 0; s0 += passSamples) {
+            const uint32_t ns = std::min(passSamples, a.samples - s0);
+            const uint32_t items = nr * ns;
+            if (launched) HIP_TRY(c, hipMemsetAsync(ql.cursor, 0, sizeof(uint32_t), c->stream)); // (the counters go on counting)
+            launched = true;
+            uint32_t chunk = 0, grid = 0;
+            crt::rayQueryLayout(items, c->rayResident[kQueryPath], chunk, grid);
+            grid = std::min(grid, ql.grid); // (the spill area is sized for ql.grid workgroups, the largest pass's)
+            q.c = queryCommon(c, ql, static_cast<const unsigned char*>(a.rays) + 32u * r0, items, c->tuneInnerMin);
+            q.c.chunk = chunk;
+            q.ids = a.ids ? a.ids + r0 : nullptr;
+            q.id_base = static_cast<uint32_t>(r0);
+            q.n_records = nr;
+            q.sample0 = a.first + s0;
+            const bool firstPass = s0 == 0u, lastPass = s0 + ns == a.samples;
+            q.t = firstPass && a.t ? a.t + r0 : nullptr;
+            q.uv = firstPass && a.uv ? a.uv + 2u * r0 : nullptr;
+            q.inst = firstPass && a.inst ? a.inst + r0 : nullptr;
+            q.prim = firstPass && a.prim ? a.prim + r0 : nullptr;
+            hrc = crt::launchPathQuery(q, c->counting, grid, c->stream);
+            if (hrc == 0 && (a.rgb || a.sums)) {
+                const double* in = firstPass ? (sums && a.first > 0u ? sums : nullptr) : running;
+                double* out = lastPass ? sums : running;
+                float* rgb = lastPass && a.rgb ? a.rgb + 3u * r0 : nullptr;
+                hrc = crt::launchPathResolve(q.rad, nr, ns, in, out, rgb, a.sums ? a.first + a.samples : a.samples, c->stream);
+            }
+        }
+    }
+    if (const int rc = endQuery(c, kQueryPath, 0u, ql, hrc, stats)) return rc;
+    if (stats) stats->rays_primary += static_cast<uint64_t>(n) * a.samples; // (endQuery: the bounce rays, with counting)
+    return CRT_OK;
+}
+
 QuerySpec countSpec(const char* what, void* count) { return QuerySpec{ what, kQueryCount, 32u, "count", { { count, 4u, 4u } } }; }
 QuerySpec occupancySpec(const char* what, void* inside) { return QuerySpec{ what, kQueryOccupancy, 16u, "inside", { { inside, 1u, 1u } } }; }
 
@@ -1812,6 +1914,81 @@ int crt_shade_rays(crt_ctx* c, uint32_t n, const float* rays, float* rgb, float*
                    uint32_t* prim, crt_frame_stats* stats)
 {
     return queryHost(c, shadeSpec("crt_shade_rays", rgb, normal, albedo, t, uv, inst, prim), n, rays, stats);
+}
+
+int crt_path_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, const void* d_ids, uint32_t first_sample, uint32_t n_samples, void* d_rgb,
+                         void* d_sums, void* d_t, void* d_uv, void* d_inst, void* d_prim, crt_frame_stats* stats)
+{
+    const char* what = "crt_path_rays_device";
+    int rc = checkPathCall(c, what, first_sample, n_samples);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n == 0u) { // nothing to look at, nothing launched
+        zeroStats(stats, t0);
+        return CRT_OK;
+    }
+    const PathCall a{ d_rays, static_cast<const uint32_t*>(d_ids), first_sample, n_samples, static_cast<float*>(d_rgb), static_cast<double*>(d_sums),
+                      static_cast<float*>(d_t), static_cast<float*>(d_uv), static_cast<uint32_t*>(d_inst), static_cast<uint32_t*>(d_prim) };
+    if (!d_rays) return fail(c, CRT_EINVAL, "%s: record buffer is NULL", what);
+    if (!a.anyOutput()) return fail(c, CRT_EINVAL, "%s: every output is NULL", what);
+    const struct { const void* p; uintptr_t align; const char* name; } ptrs[] = { { d_rays, 16u, "rays" }, { d_ids, 4u, "ids" }, { d_rgb, 4u, "rgb" },
+        { d_sums, 8u, "sums" }, { d_t, 4u, "t" }, { d_uv, 8u, "uv" }, { d_inst, 4u, "inst" }, { d_prim, 4u, "prim" } };
+    for (const auto& p : ptrs)
+        if (reinterpret_cast<uintptr_t>(p.p) & (p.align - 1u))
+            return fail(c, CRT_EINVAL, "%s: %s buffer %p is not %u-byte aligned", what, p.name, p.p, static_cast<unsigned>(p.align));
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    if ((rc = runPathQuery(c, n, a, stats)) != CRT_OK) return rc;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+// host buffers: staged through the context's query staging buffer {rays | ids | sums | rgb | t | uv | inst | prim}; synchronous
+int crt_path_rays(crt_ctx* c, uint32_t n, const float* rays, const uint32_t* ids, uint32_t first_sample, uint32_t n_samples, float* rgb,
+                  double* sums, float* t, float* uv, uint32_t* inst, uint32_t* prim, crt_frame_stats* stats)
+{
+    const char* what = "crt_path_rays";
+    int rc = checkPathCall(c, what, first_sample, n_samples);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n == 0u) {
+        zeroStats(stats, t0);
+        return CRT_OK;
+    }
+    if (!rays) return fail(c, CRT_EINVAL, "%s: record buffer is NULL", what);
+    if (!(rgb || sums || t || uv || inst || prim)) return fail(c, CRT_EINVAL, "%s: every output is NULL", what);
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    const size_t nn = n;
+    void* const host[8] = { const_cast<float*>(rays), const_cast<uint32_t*>(ids), sums, rgb, t, uv, inst, prim };
+    const size_t per[8] = { 32u, 4u, 24u, 12u, 4u, 8u, 4u, 4u };
+    size_t off[8], total = 0;
+    for (int i = 0; i < 8; i++) {
+        off[i] = total;
+        total += host[i] ? pathUp(nn * per[i]) : 0u;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->rayStageBytes < total) {
+        HIP_TRY(c, hipDeviceSynchronize());
+        if (c->dRayStage) (void)hipFree(c->dRayStage);
+        c->dRayStage = nullptr;
+        c->rayStageBytes = 0;
+        HIP_TRY(c, hipMalloc(&c->dRayStage, total));
+        c->rayStageBytes = total;
+    }
+    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
+    void* dev[8];
+    for (int i = 0; i < 8; i++) dev[i] = host[i] ? base + off[i] : nullptr;
+    HIP_TRY(c, hipMemcpyAsync(dev[0], rays, nn * 32u, hipMemcpyHostToDevice, c->stream));
+    if (ids) HIP_TRY(c, hipMemcpyAsync(dev[1], ids, nn * 4u, hipMemcpyHostToDevice, c->stream));
+    if (sums && first_sample > 0u) HIP_TRY(c, hipMemcpyAsync(dev[2], sums, nn * 24u, hipMemcpyHostToDevice, c->stream));
+    const PathCall a{ dev[0], static_cast<const uint32_t*>(dev[1]), first_sample, n_samples, static_cast<float*>(dev[3]), static_cast<double*>(dev[2]),
+                      static_cast<float*>(dev[4]), static_cast<float*>(dev[5]), static_cast<uint32_t*>(dev[6]), static_cast<uint32_t*>(dev[7]) };
+    crt_frame_stats local;
+    if ((rc = runPathQuery(c, n, a, stats ? stats : &local)) != CRT_OK) return rc;
+    for (int i = 2; i < 8; i++)
+        if (host[i]) HIP_TRY(c, hipMemcpyAsync(host[i], dev[i], nn * per[i], hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
 }
 
 int crt_closest_points_device(crt_ctx* c, uint32_t n, const void* d_points, void* d_dist, void* d_point, void* d_uv, void* d_inst,

@@ -55,28 +55,8 @@ __device__ __forceinline__ uint32_t waveReserve(uint32_t* counter, uint32_t n)
     return __builtin_amdgcn_readfirstlane(base);
 }
 
-// Sample sums of one pixel: float64 {x, y}, {z, 0} (two 16-byte words per pixel, index i -> words 2i, 2i + 1), one sample
-// added at a time in sample order, resolved once as (float)(sum / total).  oracle_render sums and divides the same way.
-struct D3 { double x, y, z; };
-__device__ __forceinline__ D3 loadSum(const void* sums, size_t i)
-{
-    const double2 a = static_cast<const double2*>(sums)[2u * i], b = static_cast<const double2*>(sums)[2u * i + 1u];
-    return D3{ a.x, a.y, b.x };
-}
-__device__ __forceinline__ void storeSum(void* sums, size_t i, const D3& a)
-{
-    static_cast<double2*>(sums)[2u * i] = make_double2(a.x, a.y);
-    static_cast<double2*>(sums)[2u * i + 1u] = make_double2(a.z, 0.0);
-}
-__device__ __forceinline__ D3 addSample(const D3& a, const float4& s)
-{
-    return D3{ a.x + static_cast<double>(s.x), a.y + static_cast<double>(s.y), a.z + static_cast<double>(s.z) };
-}
-__device__ __forceinline__ F3 sumMean(const D3& a, uint32_t total)
-{
-    const double n = static_cast<double>(total);
-    return f3(static_cast<float>(a.x / n), static_cast<float>(a.y / n), static_cast<float>(a.z / n));
-}
+// (the per-pixel sample sums -- D3, loadSum / storeSum, addSample, sumMean -- are in shading.hip.h: the path-traced ray queries
+// add their samples with the same functions)
 
 __device__ __forceinline__ uint32_t lanePrefix(unsigned long long m)
 {
@@ -270,16 +250,7 @@ __device__ __forceinline__ void streamShade(const RenderParams& p, const float4*
                     Lr = f3(fmaf(thr.x, aux.x, Lr.x), fmaf(thr.y, aux.y, Lr.y), fmaf(thr.z, aux.z, Lr.z));
                     if ((idb >> PathId<GLOBAL>::kShift) != p.max_bounces) {
                         const float u1 = rngNext(rng), u2 = rngNext(rng);
-                        const float rr = sqrtf(u1), phi = 6.28318530717958648f * u2;
-                        const float lx = rr * sinContract(phi + 1.57079632679489662f), ly = rr * sinContract(phi), lz = sqrtf(fmaxf(0.0f, 1.0f - u1));
-                        const float sg = copysignf(1.0f, N.z);
-                        const float a = -1.0f / (sg + N.z);
-                        const float b = N.x * N.y * a;
-                        const F3 T = f3(1.0f + sg * N.x * N.x * a, sg * b, -sg * N.x);
-                        const F3 Bv = f3(b, sg + N.y * N.y * a, -N.y);
-                        const F3 d = f3(fmaf(lz, N.x, fmaf(ly, Bv.x, lx * T.x)), fmaf(lz, N.y, fmaf(ly, Bv.y, lx * T.y)),
-                                        fmaf(lz, N.z, fmaf(ly, Bv.z, lx * T.z)));
-                        nd = normalize3(d);
+                        nd = diffuseBounce(N, u1, u2);
                         thrMul = 1.0f;
                         goesOn = true;
                     }
@@ -327,26 +298,13 @@ __device__ __forceinline__ void streamShade(const RenderParams& p, const float4*
                     thrMul = -1.0f;
                 } else if (sf.mtype == 2u) { // REFLECTIVE
                     if (bounce != p.max_bounces) {
-                        const float k = 2.0f * dot3(r.d, sf.N);
-                        aux = normalize3(f3(fmaf(-k, sf.N.x, r.d.x), fmaf(-k, sf.N.y, r.d.y), fmaf(-k, sf.N.z, r.d.z)));
+                        aux = normalize3(mirrorDir(r.d, sf.N));
                         thrMul = 1.0f;
                         alive = true;
                     }
                 } else if (sf.mtype == 3u) { // REFRACTIVE
                     if (bounce != p.max_bounces) {
-                        const float eta = sf.entering ? 1.0f / sf.ior : sf.ior;
-                        const float cosi = -dot3(r.d, sf.N);
-                        const float k = 1.0f - eta * eta * (1.0f - cosi * cosi);
-                        F3 d;
-                        if (k < 0.0f) {
-                            const float m2 = 2.0f * dot3(r.d, sf.N);
-                            d = f3(fmaf(-m2, sf.N.x, r.d.x), fmaf(-m2, sf.N.y, r.d.y), fmaf(-m2, sf.N.z, r.d.z));
-                        } else {
-                            const float m2 = eta * cosi - sqrtf(k);
-                            d = f3(fmaf(m2, sf.N.x, eta * r.d.x), fmaf(m2, sf.N.y, eta * r.d.y), fmaf(m2, sf.N.z, eta * r.d.z));
-                            Po = biasPoint(sf.P, sf.N, -kShadowBias);
-                        }
-                        aux = normalize3(d);
+                        aux = normalize3(refractDir(r.d, sf, Po));
                         alive = true;
                     }
                 } else {

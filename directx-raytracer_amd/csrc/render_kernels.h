@@ -184,6 +184,39 @@ struct ShadeQueryParams {
 };
 uint32_t shadeQueryResident(uint32_t stack_entries);
 int launchShadeQuery(const ShadeQueryParams& q, bool counting, uint32_t grid, ihipStream_t* stream);
+// path-traced ray queries (path_query_kernels.hip; crt_path_rays*): one pass of (record, sample) work items, numbered
+// sample-major: item = sample-in-pass * n_records + record; c.n = the items of the pass.  Every path leaves its radiance in its
+// item's slot of `rad`; launchPathResolve then adds the pass's samples per record in sample order
+struct PathQueryParams {
+    QueryCommon c;                // records: the rays of the pass's records; inner_min: tune_inner_min (closest-hit phases)
+    uint32_t inner_min_any;       // tune_inner_min_any (the shadow-ray phases)
+    // the scene's shading tables, as RenderParams'
+    const void* shade;
+    const void* lights;
+    const void* mats;
+    const void* uvs;
+    const void* textures;
+    const unsigned char* texels;
+    uint32_t n_textures, n_lights, n_mats;
+    float miss[3];
+    uint32_t max_bounces, seed;
+    const uint32_t* ids;          // path id per record, or NULL: id_base + record
+    uint32_t id_base;
+    uint32_t n_records;
+    uint32_t sample0;             // the sample of the pass's items 0 .. n_records - 1
+    void* rad;                    // scratch, one float4 per item: the path's radiance so far, final when it ends
+    void* thr;                    // scratch, one float4 per item: its throughput
+    float* t;                     // hit outputs as RayQueryParams', written by the items of sample0 (NULL in a call's later passes)
+    float* uv;
+    uint32_t* inst;
+    uint32_t* prim;
+};
+uint32_t pathQueryResident(uint32_t stack_entries);
+int launchPathQuery(const PathQueryParams& q, bool counting, uint32_t grid, ihipStream_t* stream);
+// rad[sample * n_records + record] of n_samples samples added in sample order to `in` (3 float64 per record; NULL: zero);
+// the sums go to `out`, their mean over `total` samples to rgb (each nullable)
+int launchPathResolve(const void* rad, uint32_t n_records, uint32_t n_samples, const double* in, double* out, float* rgb, uint32_t total,
+                      ihipStream_t* stream);
 // point queries (point_kernels.hip; crt_closest_points* / crt_count_hits* / crt_occupancy*): n caller-supplied records, point
 // records of 4 floats {x, y, z, rmax} (closest point, occupancy) or ray records (hit counts), over the 4-wide tree
 enum PointQueryKind { kPointClosest = 0, kPointCount = 1, kPointOccupancy = 2 };

@@ -176,6 +176,21 @@ void Renderer::shadeRays(const float* rays, size_t n, ShadedHit* out)
     }
 }
 
+void Renderer::pathRays(const float* rays, size_t n, PathHit* out, const uint32_t* ids, uint32_t firstSample, uint32_t nSamples, double* sums)
+{
+    if (!ctx) throw std::runtime_error("pathRays before prepareForRendering");
+    if (n > UINT32_MAX) throw std::runtime_error("pathRays: more than 2^32 - 1 rays");
+    const uint32_t m = static_cast<uint32_t>(n);
+    std::vector<float> rgb(3 * n), t(n), uv(2 * n);
+    std::vector<uint32_t> inst(n), prim(n);
+    check(crt_path_rays(ctx, m, rays, ids, firstSample, nSamples, rgb.data(), sums, t.data(), uv.data(), inst.data(), prim.data(), nullptr), "crt_path_rays");
+    for (size_t i = 0; i < n; i++) {
+        PathHit& o = out[i];
+        for (int k = 0; k < 3; k++) o.rgb[k] = rgb[3 * i + k];
+        o.hit = RayHit{ t[i], uv[2 * i], uv[2 * i + 1], inst[i], prim[i] };
+    }
+}
+
 void Renderer::listHits(const float* rays, size_t n, std::vector<uint64_t>& offsets, std::vector<RayHit>& hits)
 {
     if (!ctx) throw std::runtime_error("listHits before prepareForRendering");

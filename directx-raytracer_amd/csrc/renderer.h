@@ -63,6 +63,15 @@ public:
         RayHit hit;
     };
     void shadeRays(const float* rays, size_t n, ShadedHit* out);
+    // mode-200 radiance of every ray (crt_path_rays, synchronous; any shading mode): n_samples paths per record, samples
+    // firstSample .. firstSample + nSamples - 1 of path id ids[i] (nullptr: i); sums (nullptr, or 3 doubles per ray, in / out)
+    // carries the sample sums from call to call.  The hit is the record's own closest hit.
+    struct PathHit {
+        float rgb[3];
+        RayHit hit;
+    };
+    void pathRays(const float* rays, size_t n, PathHit* out, const uint32_t* ids = nullptr, uint32_t firstSample = 0, uint32_t nSamples = 1,
+                  double* sums = nullptr);
     // every crossing of every ray, ascending in t (crt_list_hits, synchronous): the hits of ray i are hits[offsets[i]] ..
     // hits[offsets[i + 1] - 1].  One offsets-only call learns the total, a second one fills the records.
     void listHits(const float* rays, size_t n, std::vector<uint64_t>& offsets, std::vector<RayHit>& hits);

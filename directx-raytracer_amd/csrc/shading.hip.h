@@ -211,12 +211,14 @@ __device__ __forceinline__ void addLight(const P& p, const LightRec& Lt, const L
     rgb.x = fmaf(albedo.x, k, rgb.x);
     rgb.y = fmaf(albedo.y, k, rgb.y);
     rgb.z = fmaf(albedo.z, k, rgb.z);
-    if (PHONG && p.phong_ks > 0.0f) {
-        const float nl2 = 2.0f * dot3(N, lt.Ld);
-        const F3 R = f3(fmaf(nl2, N.x, -lt.Ld.x), fmaf(nl2, N.y, -lt.Ld.y), fmaf(nl2, N.z, -lt.Ld.z));
-        const float rv = fmaxf(0.0f, dot3(R, view));
-        const float sp = (p.phong_ks * (Lt.intensity / (kFourPi * lt.r2))) * powUint(rv, p.phong_exp);
-        rgb.x += sp; rgb.y += sp; rgb.z += sp;
+    if constexpr (PHONG) { // (a parameter block without the Phong options -- the path-traced ray queries' -- never gets here)
+        if (p.phong_ks > 0.0f) {
+            const float nl2 = 2.0f * dot3(N, lt.Ld);
+            const F3 R = f3(fmaf(nl2, N.x, -lt.Ld.x), fmaf(nl2, N.y, -lt.Ld.y), fmaf(nl2, N.z, -lt.Ld.z));
+            const float rv = fmaxf(0.0f, dot3(R, view));
+            const float sp = (p.phong_ks * (Lt.intensity / (kFourPi * lt.r2))) * powUint(rv, p.phong_exp);
+            rgb.x += sp; rgb.y += sp; rgb.z += sp;
+        }
     }
 }
 
@@ -260,6 +262,64 @@ __device__ __forceinline__ float rngNext(uint32_t& st)
 {
     st = pcgHash(st);
     return static_cast<float>(st >> 8) * 0x1p-24f;
+}
+
+// ---- The path's directions at a surface: the mirror direction, the Snell branch and the cosine-weighted bounce (oracle:
+// trace_path).  The one statement of each: streamShade (path_kernels.hip) and the path-traced ray queries
+// (path_query_kernels.hip) both go through here.
+__device__ __forceinline__ F3 mirrorDir(F3 d, F3 N) // not normalised
+{
+    const float k = 2.0f * dot3(d, N);
+    return f3(fmaf(-k, N.x, d.x), fmaf(-k, N.y, d.y), fmaf(-k, N.z, d.z));
+}
+// The direction behind a REFRACTIVE surface, not normalised: Snell's, with Po (the point the path goes on from) moved to the
+// far side of the surface; on total internal reflection the mirror direction, and Po stays
+__device__ __forceinline__ F3 refractDir(F3 d, const Surface& sf, F3& Po)
+{
+    const float eta = sf.entering ? 1.0f / sf.ior : sf.ior;
+    const float cosi = -dot3(d, sf.N);
+    const float k = 1.0f - eta * eta * (1.0f - cosi * cosi);
+    if (k < 0.0f) return mirrorDir(d, sf.N);
+    const float m2 = eta * cosi - sqrtf(k);
+    const F3 t = f3(fmaf(m2, sf.N.x, eta * d.x), fmaf(m2, sf.N.y, eta * d.y), fmaf(m2, sf.N.z, eta * d.z));
+    Po = biasPoint(sf.P, sf.N, -kShadowBias);
+    return t;
+}
+__device__ __forceinline__ F3 diffuseBounce(F3 N, float u1, float u2)
+{
+    const float rr = sqrtf(u1), phi = 6.28318530717958648f * u2;
+    const float lx = rr * sinContract(phi + 1.57079632679489662f), ly = rr * sinContract(phi), lz = sqrtf(fmaxf(0.0f, 1.0f - u1));
+    const float sg = copysignf(1.0f, N.z);
+    const float a = -1.0f / (sg + N.z);
+    const float b = N.x * N.y * a;
+    const F3 T = f3(1.0f + sg * N.x * N.x * a, sg * b, -sg * N.x);
+    const F3 Bv = f3(b, sg + N.y * N.y * a, -N.y);
+    const F3 d = f3(fmaf(lz, N.x, fmaf(ly, Bv.x, lx * T.x)), fmaf(lz, N.y, fmaf(ly, Bv.y, lx * T.y)), fmaf(lz, N.z, fmaf(ly, Bv.z, lx * T.z)));
+    return normalize3(d);
+}
+
+// Sample sums of one pixel (path_kernels.hip) or one record (path_query_kernels.hip): float64, one sample added at a time in
+// sample order, resolved once as (float)(sum / total).  oracle_render sums and divides the same way.  loadSum / storeSum: the
+// frames' layout, {x, y}, {z, 0} (two 16-byte words per pixel, index i -> words 2i, 2i + 1).
+struct D3 { double x, y, z; };
+__device__ __forceinline__ D3 loadSum(const void* sums, size_t i)
+{
+    const double2 a = static_cast<const double2*>(sums)[2u * i], b = static_cast<const double2*>(sums)[2u * i + 1u];
+    return D3{ a.x, a.y, b.x };
+}
+__device__ __forceinline__ void storeSum(void* sums, size_t i, const D3& a)
+{
+    static_cast<double2*>(sums)[2u * i] = make_double2(a.x, a.y);
+    static_cast<double2*>(sums)[2u * i + 1u] = make_double2(a.z, 0.0);
+}
+__device__ __forceinline__ D3 addSample(const D3& a, const float4& s)
+{
+    return D3{ a.x + static_cast<double>(s.x), a.y + static_cast<double>(s.y), a.z + static_cast<double>(s.z) };
+}
+__device__ __forceinline__ F3 sumMean(const D3& a, uint32_t total)
+{
+    const double n = static_cast<double>(total);
+    return f3(static_cast<float>(a.x / n), static_cast<float>(a.y / n), static_cast<float>(a.z / n));
 }
 
 __device__ __forceinline__ uint32_t waveSum(uint32_t v)

@@ -421,7 +421,7 @@ int crt_occluded_rays(crt_ctx* ctx, uint32_t n, const float* rays, uint8_t* occl
  * - Mode: the context's current shading mode (crt_set_shading_mode) applies.  Modes 0..99 are the seven reference modes
  *   (7..99 behave as 6, as in the frames); mode 100 is Lambert with optional Phong (options "phong_ks", "phong_exponent") and
  *   one shadow ray per light.  Mode 200 returns CRT_EINVAL and launches nothing: path tracing of caller rays would need a
- *   sample-indexing contract of its own.
+ *   sample-indexing contract of its own (crt_path_rays* below has it).
  * - What the shading sees: the record's own origin and direction and the unscaled t (t' 2^-e, the value reported) -- exactly
  *   what the frame kernels hand the same functions for a camera ray.  Nothing is normalised: the hit point is o + d * t per
  *   component, the entering test is the sign of dot(N, d), Phong's view vector is -d.  So a record that holds a frame's camera
@@ -454,6 +454,60 @@ int crt_shade_rays_device(crt_ctx* ctx, uint32_t n, const void* d_rays, void* d_
                           void* d_uv, void* d_inst, void* d_prim, crt_frame_stats* stats);
 int crt_shade_rays(crt_ctx* ctx, uint32_t n, const float* rays, float* rgb, float* normal, float* albedo, float* t, float* uv,
                    uint32_t* inst, uint32_t* prim, crt_frame_stats* stats);
+
+/* ---- path-traced ray queries: mode-200 radiance for caller-supplied rays (the sample-indexing contract crt_shade_rays'
+ * refusal of mode 200 asks for).  Global illumination for sensors that are not a pinhole -- fisheye and equirectangular
+ * cameras, calibrated lenses, light and irradiance probes, lidar returns with interreflection, light fields -- without
+ * rendering pinhole frames and resampling them.
+ * - Records: the 8-float records of crt_trace_rays, with the same NaN / empty-interval / zero-direction rules and the same
+ *   direction-magnitude contract.  The first segment is traced prescaled by 2^e, exactly as crt_trace_rays traces it, over the
+ *   record's own (tmin, tmax): t / uv / inst / prim are crt_trace_rays' outputs for that record bit for bit and do not depend
+ *   on the sample.  Each output is optional; at least one of rgb, sums, t, uv, inst, prim must be non-NULL.
+ * - What a path is: each record is traced as n_samples independent paths, samples first_sample .. first_sample + n_samples - 1.
+ *   Each is the frames' mode-200 path ("Path tracing") from its first segment on.  Per segment: a miss
+ *   adds throughput x miss colour; CONSTANT emits and stops; REFLECTIVE and REFRACTIVE continue as in the frames (total
+ *   internal reflection and the +-1e-3 bias included); DIFFUSE gathers direct light with one shadow ray per light that has a
+ *   positive cosine, in light order, then takes the cosine-weighted bounce; textures are honoured; every fmaf stays where the
+ *   frames have it.  Later segments run over (0, 10000) with the frames' cull bound.  max_bounces, seed, the miss colour and
+ *   the textures come from the context.  The option spp and the context's shading mode are not read: the call path-traces in
+ *   whatever mode the context is in and leaves the mode alone.
+ * - What the shading sees: the record's own origin and direction and the unscaled t; nothing is normalised, as in
+ *   crt_shade_rays.  Snell's cosine and the mirror formula assume unit directions: a caller who wants the frames' semantics
+ *   passes them.  A miss or an untraced record is one segment whose radiance is the miss colour.
+ * - Sample indexing: the path id of record i is ids[i], or i when ids is NULL.  The path of (id, sample s) starts its RNG at
+ *   hash(id ^ hash(s + hash(seed))), the frames' start for pixel `id`, then takes two draws it does not use (in a frame: the
+ *   pixel jitter), so that its first used draw is the frames' first bounce draw.  Hence:
+ *     . a record that holds a frame's jittered camera ray for pixel p and sample s (id = py * width + px, origin = the camera
+ *       position, tmin = 0.001, tmax = 10000) gives that path's radiance bit for bit;
+ *     . results do not depend on the order of the records when their ids travel with them; the same ray with another id is
+ *       another, equally valid, sample;
+ *     . a caller who wants jitter from the same stream computes it on the host (Python: path_jitter).
+ * - Sums and the mean: per record the samples' radiances are added in sample order into three float64 sums, as the frames add
+ *   theirs.  Without sums, rgb = (float)(S / n_samples).  With sums (n x 3 float64, in / out): the stored values are the
+ *   starting point when first_sample > 0, zero is when first_sample == 0 (the buffer is then not read); the new sums are
+ *   written back and rgb = (float)(S / (first_sample + n_samples)).  So K calls of S samples equal one call of K * S samples
+ *   bit for bit, and a caller may hand over different rays per call (its own jitter): the frames' accumulation with the sums
+ *   owned by the caller and the context stateless.
+ * - Passes: one launch covers at most the option "path_pass_paths" (record, sample) pairs; more run as several passes over
+ *   sample ranges, with no effect on any result.
+ * - Pending refits are applied first.  Camera, mode, accumulation sums, launch orders and frame outputs are untouched: a frame
+ *   rendered after any number of calls equals the frame rendered without them, accumulating mode-200 runs included.  Inert
+ *   triangles are never hit and never occlude; the boundary-ray limit of the ray queries applies unchanged.  Results do not
+ *   depend on scheduling, on the pass split or on the options inner_min, inner_min_any and stack_entries.
+ * - n = 0 returns CRT_OK and launches nothing.  CRT_ESTATE without a scene.  CRT_EINVAL for a NULL ctx, NULL rays with n > 0,
+ *   n_samples == 0, first_sample + n_samples > 2^24 (the frames' limit), all six outputs NULL, or a misaligned device pointer
+ *   (rays 16-byte; sums and uv 8-byte; everything else, ids included, 4-byte).  These checks come before the refit: a failed
+ *   call launches nothing.
+ * - stats (may be NULL): kernel_ms covers all kernels of the call; rays_primary = n * n_samples.  With crt_set_counting(ctx, 1)
+ *   rays_primary is the exact number of closest-hit rays, bounce rays included, and rays_shadow / nodes_visited / tris_tested
+ *   are counted as the frames count them: for a buffer of a frame's sample-0 camera rays they are the oracle's statistics of
+ *   that 1-spp frame.
+ * *_device: device pointers, asynchronous on the context's stream (crt_set_stream) unless stats != NULL.  Host variant:
+ * synchronous, staged through the context's query staging buffer. */
+int crt_path_rays_device(crt_ctx* ctx, uint32_t n, const void* d_rays, const void* d_ids, uint32_t first_sample, uint32_t n_samples,
+                         void* d_rgb, void* d_sums, void* d_t, void* d_uv, void* d_inst, void* d_prim, crt_frame_stats* stats);
+int crt_path_rays(crt_ctx* ctx, uint32_t n, const float* rays, const uint32_t* ids, uint32_t first_sample, uint32_t n_samples,
+                  float* rgb, double* sums, float* t, float* uv, uint32_t* inst, uint32_t* prim, crt_frame_stats* stats);
 
 /* ---- point queries: closest surface point, hit counts, occupancy (no reference counterpart; the set of Open3D's
  * RaycastingScene: compute_closest_points / compute_distance / compute_signed_distance / compute_occupancy /
