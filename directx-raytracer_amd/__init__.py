@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "crt_rebuild", "crt_list_hits_device", "crt_list_hits", "crt_debug_list_phases",
     "crt_shade_rays_device", "crt_shade_rays",
     "crt_path_rays_device", "crt_path_rays",
+    "crt_camera_rays_device", "crt_camera_rays", "crt_frame_guides_device", "crt_frame_guides", "crt_denoise_device", "crt_denoise",
 ]
 
 
@@ -89,6 +90,18 @@ class FrameStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+SAMPLE_CENTRE = 0xFFFFFFFF  # CRT_SAMPLE_CENTRE: the pixel-centre camera rays of modes 0..100
+
+
+class DenoiseParams(C.Structure):
+    """crt_denoise_params; the defaults are the header's"""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("demodulate", C.c_uint32)]
+
+    def __init__(self, iterations=5, sigma_color=4.0, sigma_normal=0.3, sigma_depth=0.05, demodulate=1):
+        super().__init__(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_depth), int(demodulate))
 
 
 def build(force=False):
@@ -225,6 +238,12 @@ def lib():
         "crt_shade_rays": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "crt_path_rays_device": (C.c_int, [vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
         "crt_path_rays": (C.c_int, [vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "crt_camera_rays_device": (C.c_int, [vp, u32, u32, u32, vp, vp]),
+        "crt_camera_rays": (C.c_int, [vp, u32, u32, u32, vp, vp]),
+        "crt_frame_guides_device": (C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
+        "crt_frame_guides": (C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
+        "crt_denoise_device": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "crt_denoise": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
     }
     assert set(sig) == set(ABI_SYMBOLS)
     for name, (res, args) in sig.items():
@@ -882,6 +901,72 @@ class Renderer:
         st = FrameStats() if stats else None
         self._ok(lib().crt_path_rays_device(self.h, int(n), d_rays, d_ids, int(first_sample), int(n_samples), d_rgb, d_sums, d_t, d_uv,
                                             d_inst, d_prim, C.byref(st) if stats else None), "crt_path_rays_device")
+        return st.as_dict() if stats else None
+
+    # ---- camera rays, guide buffers and the denoiser (include/crt_hip.h)
+    def camera_rays(self, w, h, sample=None):
+        """the frames' camera rays of a w x h frame as (w * h, 8) float32 records, record py * w + px (host buffer, synchronous).
+        sample None: the pixel-centre rays of modes 0..100; an integer below 2^24: the jittered rays a mode-200 frame traces for
+        that frame sample index with the context's seed."""
+        rays = np.zeros((int(w) * int(h), 8), dtype=np.float32)
+        self._ok(lib().crt_camera_rays(self.h, int(w), int(h), SAMPLE_CENTRE if sample is None else int(sample), rays.ctypes.data, None),
+                 "crt_camera_rays")
+        return rays
+
+    def camera_rays_device(self, w, h, d_rays, sample=None, stats=False):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_camera_rays_device(self.h, int(w), int(h), SAMPLE_CENTRE if sample is None else int(sample), d_rays,
+                                              C.byref(st) if stats else None), "crt_camera_rays_device")
+        return st.as_dict() if stats else None
+
+    def frame_guides(self, w, h, want=("normal", "albedo", "t")):
+        """the guide buffers of a w x h frame (host buffers, synchronous): per pixel the shading normal and the albedo, (h, w, 3)
+        float32, and t, (h, w) float32, of the pixel-centre camera ray (miss: zero, zero, 10000), in any shading mode.  Returns a
+        dict of the wanted arrays plus 'stats'."""
+        w, h = int(w), int(h)
+        shapes = {"normal": (h, w, 3), "albedo": (h, w, 3), "t": (h, w)}
+        out = {k: np.zeros(shapes[k], dtype=np.float32) for k in shapes if k in want}
+        st = FrameStats()
+
+        def p(k):
+            return out[k].ctypes.data if k in out else None
+        self._ok(lib().crt_frame_guides(self.h, w, h, p("normal"), p("albedo"), p("t"), C.byref(st)), "crt_frame_guides")
+        out["stats"] = st.as_dict()
+        return out
+
+    def frame_guides_device(self, w, h, d_normal=None, d_albedo=None, d_t=None, stats=False):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_frame_guides_device(self.h, int(w), int(h), d_normal, d_albedo, d_t, C.byref(st) if stats else None),
+                 "crt_frame_guides_device")
+        return st.as_dict() if stats else None
+
+    def denoise(self, rgb, normal, albedo, t, **params):
+        """the edge-avoiding a-trous filter (host buffers, synchronous): rgb, normal, albedo (h, w, 3) and t (h, w) float32, e.g. a
+        mode-200 frame's 'rgb' and frame_guides' arrays.  params: the fields of DenoiseParams (iterations, sigma_color,
+        sigma_normal, sigma_depth, demodulate).  Returns the filtered (h, w, 3) float32 image."""
+        t = np.ascontiguousarray(t, dtype=np.float32)
+        if t.ndim != 2:
+            raise ValueError("t must be (h, w)")
+        h, w = t.shape
+        bufs = [np.ascontiguousarray(a, dtype=np.float32) for a in (rgb, normal, albedo)]
+        for a in bufs:
+            if a.shape != (h, w, 3):
+                raise ValueError("rgb, normal and albedo must be (h, w, 3) where t is (h, w)")
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        prm = DenoiseParams(**params)
+        self._ok(lib().crt_denoise(self.h, w, h, bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data, t.ctypes.data, out.ctypes.data,
+                                   C.byref(prm), None), "crt_denoise")
+        return out
+
+    def denoise_device(self, w, h, d_rgb, d_normal, d_albedo, d_t, d_out, stats=False, **params):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); d_out may equal d_rgb; asynchronous on the context's
+        stream unless stats"""
+        st = FrameStats() if stats else None
+        prm = DenoiseParams(**params)
+        self._ok(lib().crt_denoise_device(self.h, int(w), int(h), d_rgb, d_normal, d_albedo, d_t, d_out, C.byref(prm),
+                                          C.byref(st) if stats else None), "crt_denoise_device")
         return st.as_dict() if stats else None
 
     # ---- point queries (include/crt_hip.h): records of 4 floats {x, y, z, rmax}, see make_points

@@ -22,11 +22,14 @@
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
+#include <initializer_list>
 #include <memory>
 #include <new>
 #include <stdexcept>
@@ -1392,6 +1395,41 @@ struct QueryLaunch {
     crt_ctx::RayArena* arena;
 };
 
+// The query arena of the context's stream, grown to `need` bytes: the arena this stream used last; else an unused one; else the
+// least recently used one of another stream, once the query that used it last is done.  ownScratch: the call keeps scratch of
+// its own in the arena, and an allocation failure is CRT_ENOMEM
+int takeArena(crt_ctx* c, size_t need, bool ownScratch, crt_ctx::RayArena*& out)
+{
+    crt_ctx::RayArena* arena = nullptr;
+    for (auto& a : c->rayArena)
+        if (a.used && a.stream == c->stream) arena = &a;
+    if (!arena) {
+        for (auto& a : c->rayArena)
+            if (!arena || (!a.used && arena->used) || (a.used == arena->used && a.serial < arena->serial)) arena = &a;
+        if (arena->pending && hipEventQuery(arena->lastUse) != hipSuccess) HIP_TRY(c, hipStreamWaitEvent(c->stream, arena->lastUse, 0));
+        arena->stream = c->stream;
+        arena->used = true;
+    }
+    if (arena->bytes < need) {
+        HIP_TRY(c, hipDeviceSynchronize()); // (the arena may still be in use by a query on its stream)
+        if (arena->mem) (void)hipFree(arena->mem);
+        arena->mem = nullptr;
+        arena->bytes = 0;
+        if (ownScratch) {
+            if (hipMalloc(reinterpret_cast<void**>(&arena->mem), need) != hipSuccess) {
+                (void)hipGetLastError();
+                arena->mem = nullptr;
+                return fail(c, CRT_ENOMEM, "query scratch: %zu bytes of device memory not available", need);
+            }
+        } else HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&arena->mem), need));
+        arena->bytes = need;
+    }
+    if (!arena->lastUse) HIP_TRY(c, hipEventCreateWithFlags(&arena->lastUse, hipEventDisableTiming));
+    arena->serial = ++c->raySerial;
+    out = arena;
+    return CRT_OK;
+}
+
 // One query of n > 0 records on the context's stream, in two halves around the kernel launch.  beginQuery sizes the persistent
 // grid, takes an arena and (with stats) starts the timer; entryWords = ints per stack entry.  endQuery takes the launch's HIP
 // error code and, with stats, synchronises and fills them.
@@ -1405,37 +1443,10 @@ int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t entryWords, crt_
     const uint32_t deepest = 3u * c->bvh.depth4 + 1u; // as runRender
     ql.spill_stride = (deepest > ql.stack_entries ? deepest - ql.stack_entries : 1u) * entryWords;
 
-    // the arena this stream used last; else an unused one; else the least recently used one of another stream, once the
-    // query that used it last is done
-    crt_ctx::RayArena* arena = nullptr;
-    for (auto& a : c->rayArena)
-        if (a.used && a.stream == c->stream) arena = &a;
-    if (!arena) {
-        for (auto& a : c->rayArena)
-            if (!arena || (!a.used && arena->used) || (a.used == arena->used && a.serial < arena->serial)) arena = &a;
-        if (arena->pending && hipEventQuery(arena->lastUse) != hipSuccess) HIP_TRY(c, hipStreamWaitEvent(c->stream, arena->lastUse, 0));
-        arena->stream = c->stream;
-        arena->used = true;
-    }
     constexpr size_t kHead = 256; // cursor at 0, counters at 64
     const size_t spillBytes = (static_cast<size_t>(std::max(ql.grid, minGrid)) * 64u * ql.spill_stride * sizeof(int) + 255u) & ~static_cast<size_t>(255u);
-    const size_t need = kHead + spillBytes + extraBytes;
-    if (arena->bytes < need) {
-        HIP_TRY(c, hipDeviceSynchronize()); // (the arena may still be in use by a query on its stream)
-        if (arena->mem) (void)hipFree(arena->mem);
-        arena->mem = nullptr;
-        arena->bytes = 0;
-        if (extraBytes) {
-            if (hipMalloc(reinterpret_cast<void**>(&arena->mem), need) != hipSuccess) {
-                (void)hipGetLastError();
-                arena->mem = nullptr;
-                return fail(c, CRT_ENOMEM, "query scratch: %zu bytes of device memory not available", need);
-            }
-        } else HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&arena->mem), need));
-        arena->bytes = need;
-    }
-    if (!arena->lastUse) HIP_TRY(c, hipEventCreateWithFlags(&arena->lastUse, hipEventDisableTiming));
-    arena->serial = ++c->raySerial;
+    crt_ctx::RayArena* arena = nullptr;
+    if (const int rc = takeArena(c, kHead + spillBytes + extraBytes, extraBytes != 0u, arena)) return rc;
     ql.extra = extraBytes ? arena->mem + kHead + spillBytes : nullptr;
     ql.cursor = reinterpret_cast<uint32_t*>(arena->mem);
     ql.counters = reinterpret_cast<unsigned long long*>(arena->mem + 64);
@@ -1544,18 +1555,9 @@ int runPointQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_reco
     return endQuery(c, s.kind, n, ql, crt::launchPointQuery(q, pk, c->counting, ql.grid, c->stream), stats);
 }
 
-// crt_shade_rays*: the closest hit and the context's shading mode at it (shade_kernels.hip)
-int runShadeQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_rays, void* const d[kQueryOutputs], crt_frame_stats* stats)
+// the scene's shading tables and the context's shading state of a shaded query
+void shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q)
 {
-    crt::ShadeQueryParams q;
-    std::memset(&q, 0, sizeof(q));
-    q.rgb = static_cast<float*>(d[0]);
-    q.normal = static_cast<float*>(d[1]);
-    q.albedo = static_cast<float*>(d[2]);
-    q.t = static_cast<float*>(d[3]);
-    q.uv = static_cast<float*>(d[4]);
-    q.inst = static_cast<uint32_t*>(d[5]);
-    q.prim = static_cast<uint32_t*>(d[6]);
     q.shade = c->dShade; // as fillParams
     q.lights = c->dLights;
     q.mats = c->dMats;
@@ -1570,6 +1572,21 @@ int runShadeQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_rays
     q.phong_ks = static_cast<float>(c->phongKsPermille) / 1000.0f;
     q.phong_exp = c->phongExp;
     q.inner_min_any = c->tuneInnerMinAny;
+}
+
+// crt_shade_rays*: the closest hit and the context's shading mode at it (shade_kernels.hip)
+int runShadeQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_rays, void* const d[kQueryOutputs], crt_frame_stats* stats)
+{
+    crt::ShadeQueryParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.rgb = static_cast<float*>(d[0]);
+    q.normal = static_cast<float*>(d[1]);
+    q.albedo = static_cast<float*>(d[2]);
+    q.t = static_cast<float*>(d[3]);
+    q.uv = static_cast<float*>(d[4]);
+    q.inst = static_cast<uint32_t*>(d[5]);
+    q.prim = static_cast<uint32_t*>(d[6]);
+    shadeTables(c, q);
     QueryLaunch ql;
     if (const int rc = beginQuery(c, s.kind, n, 1u, stats, ql)) return rc;
     q.c = queryCommon(c, ql, d_rays, n, c->tuneInnerMin);
@@ -1986,6 +2003,290 @@ int crt_path_rays(crt_ctx* c, uint32_t n, const float* rays, const uint32_t* ids
     if ((rc = runPathQuery(c, n, a, stats ? stats : &local)) != CRT_OK) return rc;
     for (int i = 2; i < 8; i++)
         if (host[i]) HIP_TRY(c, hipMemcpyAsync(host[i], dev[i], nn * per[i], hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+namespace {
+
+// ---- camera rays, frame guides and the denoiser (camera_kernels.hip, denoise_kernels.hip)
+constexpr uint64_t kMaxFramePixels = 1ull << 28;
+
+int checkFrameSize(crt_ctx* c, const char* what, uint32_t w, uint32_t h)
+{
+    if (w == 0u || h == 0u) return fail(c, CRT_EINVAL, "%s: frame size %u x %u", what, w, h);
+    if (static_cast<uint64_t>(w) * h > kMaxFramePixels) return fail(c, CRT_EINVAL, "%s: %u x %u exceeds 2^28 pixels", what, w, h);
+    return CRT_OK;
+}
+
+int checkDevicePointers(crt_ctx* c, const char* what, std::initializer_list<const void*> ptrs, uintptr_t align)
+{
+    for (const void* p : ptrs)
+        if (reinterpret_cast<uintptr_t>(p) & (align - 1u))
+            return fail(c, CRT_EINVAL, "%s: buffer %p is not %u-byte aligned", what, p, static_cast<unsigned>(align));
+    return CRT_OK;
+}
+
+// the query staging buffer of the host forms, grown to `total` bytes
+int reserveRayStage(crt_ctx* c, size_t total)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->rayStageBytes < total) {
+        HIP_TRY(c, hipDeviceSynchronize());
+        if (c->dRayStage) (void)hipFree(c->dRayStage);
+        c->dRayStage = nullptr;
+        c->rayStageBytes = 0;
+        HIP_TRY(c, hipMalloc(&c->dRayStage, total));
+        c->rayStageBytes = total;
+    }
+    return CRT_OK;
+}
+
+crt::CameraRayParams cameraRayParams(const crt_ctx* c, uint32_t w, uint32_t h, uint32_t sample, void* d_rays)
+{
+    crt::CameraRayParams p;
+    std::memset(&p, 0, sizeof(p));
+    crt::copyBytes(p.pos, c->pos, sizeof(p.pos));
+    crt::copyBytes(p.rot, c->rot, sizeof(p.rot));
+    p.width = w;
+    p.height = h;
+    p.sample = sample;
+    p.seed = c->pathSeed;
+    p.rays = d_rays;
+    return p;
+}
+
+int checkCameraRays(crt_ctx* c, const char* what, uint32_t w, uint32_t h, uint32_t sample, const void* rays)
+{
+    if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
+    if (const int rc = checkFrameSize(c, what, w, h)) return rc;
+    if (sample != CRT_SAMPLE_CENTRE && sample >= (1u << 24)) return fail(c, CRT_EINVAL, "%s: sample %u is neither below 2^24 nor CRT_SAMPLE_CENTRE", what, sample);
+    if (!rays) return fail(c, CRT_EINVAL, "%s: record buffer is NULL", what);
+    return CRT_OK;
+}
+
+// kernels that need no arena, timed when stats are wanted: `launch` returns a HIP error code.  With stats the call synchronises
+// and every count is zero
+int runTimed(crt_ctx* c, const char* what, crt_frame_stats* stats, const std::function<int()>& launch)
+{
+    if (stats) HIP_TRY(c, hipEventRecord(c->evStart, c->stream));
+    const int hrc = launch();
+    if (hrc != 0) return fail(c, CRT_EHIP, "%s: kernel launch failed: %s", what, hipGetErrorString(static_cast<hipError_t>(hrc)));
+    if (stats) {
+        HIP_TRY(c, hipEventRecord(c->evStop, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->evStart, c->evStop));
+        std::memset(stats, 0, sizeof(*stats));
+        stats->kernel_ms = ms;
+    }
+    return CRT_OK;
+}
+
+int runCameraRays(crt_ctx* c, const char* what, uint32_t w, uint32_t h, uint32_t sample, void* d_rays, crt_frame_stats* stats)
+{
+    const crt::CameraRayParams p = cameraRayParams(c, w, h, sample, d_rays);
+    if (const int rc = runTimed(c, what, stats, [&] { return crt::launchCameraRays(p, c->stream); })) return rc;
+    if (stats) stats->rays_primary = static_cast<uint64_t>(w) * h;
+    return CRT_OK;
+}
+
+// crt_frame_guides*: the camera-ray kernel into the query arena, then the shaded query over those records in a debug mode
+// (the surface is evaluated for normal / albedo in every mode; no colour is asked for)
+int runFrameGuides(crt_ctx* c, uint32_t w, uint32_t h, void* d_normal, void* d_albedo, void* d_t, crt_frame_stats* stats)
+{
+    const uint32_t n = w * h;
+    crt::ShadeQueryParams q;
+    std::memset(&q, 0, sizeof(q));
+    shadeTables(c, q);
+    q.mode = 3u;
+    q.normal = static_cast<float*>(d_normal);
+    q.albedo = static_cast<float*>(d_albedo);
+    q.t = static_cast<float*>(d_t);
+    QueryLaunch ql;
+    if (const int rc = beginQuery(c, kQueryShade, n, 1u, stats, ql, up256(static_cast<size_t>(n) * 32u))) return rc;
+    int hrc = crt::launchCameraRays(cameraRayParams(c, w, h, CRT_SAMPLE_CENTRE, ql.extra), c->stream);
+    if (hrc == 0) {
+        q.c = queryCommon(c, ql, ql.extra, n, c->tuneInnerMin);
+        hrc = crt::launchShadeQuery(q, c->counting, ql.grid, c->stream);
+    }
+    return endQuery(c, kQueryShade, n, ql, hrc, stats);
+}
+
+int checkFrameGuides(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* normal, const void* albedo, const void* t)
+{
+    if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
+    if (!c->haveScene) return fail(c, CRT_ESTATE, "%s: no scene uploaded: call crt_upload_scene first", what);
+    if (const int rc = checkFrameSize(c, what, w, h)) return rc;
+    if (!normal && !albedo && !t) return fail(c, CRT_EINVAL, "%s: every output is NULL", what);
+    return CRT_OK;
+}
+
+const crt_denoise_params kDenoiseDefaults = { 5u, 4.0f, 0.3f, 0.05f, 1u };
+
+int checkDenoise(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* rgb, const void* normal, const void* albedo, const void* t,
+                 const void* out, const crt_denoise_params& prm)
+{
+    if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
+    if (const int rc = checkFrameSize(c, what, w, h)) return rc;
+    if (prm.iterations < 1u || prm.iterations > 8u) return fail(c, CRT_EINVAL, "%s: iterations = %u is outside 1..8", what, prm.iterations);
+    const struct { const char* name; float v; } sig[] = { { "sigma_color", prm.sigma_color }, { "sigma_normal", prm.sigma_normal }, { "sigma_depth", prm.sigma_depth } };
+    for (const auto& s : sig)
+        if (!(s.v > 0.0f)) return fail(c, CRT_EINVAL, "%s: %s = %g must be > 0 (+inf switches the term off)", what, s.name, static_cast<double>(s.v));
+    if (prm.demodulate > 1u) return fail(c, CRT_EINVAL, "%s: demodulate = %u is neither 0 nor 1", what, prm.demodulate);
+    if (!rgb || !normal || !albedo || !t || !out) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
+    return CRT_OK;
+}
+
+// 1 / sigma^2 as the kernels take it: 0 for +inf, never infinite (0 x inf would poison a tap of equal value)
+float invSquare(float sigma)
+{
+    const double s = static_cast<double>(sigma);
+    return static_cast<float>(std::min(1.0 / (s * s), static_cast<double>(FLT_MAX)));
+}
+
+int runDenoise(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* d_rgb, const void* d_normal, const void* d_albedo, const void* d_t,
+               void* d_out, const crt_denoise_params& prm, crt_frame_stats* stats)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t plane = up256(static_cast<size_t>(w) * h * 16u);
+    static_assert(crt::kDenoiseScratchPerPixel == 48u, "three float4 planes");
+    crt_ctx::RayArena* arena = nullptr;
+    if (const int rc = takeArena(c, 3u * plane, true, arena)) return rc;
+    crt::DenoiseParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.width = w;
+    p.height = h;
+    p.iterations = prm.iterations;
+    p.demodulate = prm.demodulate;
+    p.inv_sigma_color2 = invSquare(prm.sigma_color);
+    p.inv_sigma_normal2 = invSquare(prm.sigma_normal);
+    p.sigma_depth = prm.sigma_depth;
+    p.rgb = static_cast<const float*>(d_rgb);
+    p.normal = static_cast<const float*>(d_normal);
+    p.albedo = static_cast<const float*>(d_albedo);
+    p.t = static_cast<const float*>(d_t);
+    p.out = static_cast<float*>(d_out);
+    p.guide = arena->mem;
+    p.colour[0] = arena->mem + plane;
+    p.colour[1] = arena->mem + 2u * plane;
+    // (the arena's last use is recorded before a timed call synchronises)
+    return runTimed(c, what, stats, [&] {
+        const int hrc = crt::launchDenoise(p, c->stream);
+        if (hrc != 0) return hrc;
+        arena->pending = true;
+        return static_cast<int>(hipEventRecord(arena->lastUse, c->stream));
+    });
+}
+
+} // namespace
+
+int crt_camera_rays_device(crt_ctx* c, uint32_t w, uint32_t h, uint32_t sample, void* d_rays, crt_frame_stats* stats)
+{
+    const char* what = "crt_camera_rays_device";
+    int rc = checkCameraRays(c, what, w, h, sample, d_rays);
+    if (rc) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_rays }, 16u)) != CRT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = runCameraRays(c, what, w, h, sample, d_rays, stats)) != CRT_OK) return rc;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+int crt_camera_rays(crt_ctx* c, uint32_t w, uint32_t h, uint32_t sample, float* rays, crt_frame_stats* stats)
+{
+    const char* what = "crt_camera_rays";
+    int rc = checkCameraRays(c, what, w, h, sample, rays);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t bytes = static_cast<size_t>(w) * h * 32u;
+    if ((rc = reserveRayStage(c, bytes)) != CRT_OK) return rc;
+    if ((rc = runCameraRays(c, what, w, h, sample, c->dRayStage, stats)) != CRT_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(rays, c->dRayStage, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+int crt_frame_guides_device(crt_ctx* c, uint32_t w, uint32_t h, void* d_normal, void* d_albedo, void* d_t, crt_frame_stats* stats)
+{
+    const char* what = "crt_frame_guides_device";
+    int rc = checkFrameGuides(c, what, w, h, d_normal, d_albedo, d_t);
+    if (rc) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_normal, d_albedo, d_t }, 4u)) != CRT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    if ((rc = runFrameGuides(c, w, h, d_normal, d_albedo, d_t, stats)) != CRT_OK) return rc;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+// host buffers: staged through the context's query staging buffer {normal | albedo | t}; synchronous
+int crt_frame_guides(crt_ctx* c, uint32_t w, uint32_t h, float* normal, float* albedo, float* t, crt_frame_stats* stats)
+{
+    const char* what = "crt_frame_guides";
+    int rc = checkFrameGuides(c, what, w, h, normal, albedo, t);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    const size_t nn = static_cast<size_t>(w) * h;
+    void* const host[3] = { normal, albedo, t };
+    const size_t per[3] = { 12u, 12u, 4u };
+    size_t off[3], total = 0;
+    for (int i = 0; i < 3; i++) {
+        off[i] = total;
+        total += host[i] ? up256(nn * per[i]) : 0u;
+    }
+    if ((rc = reserveRayStage(c, total)) != CRT_OK) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
+    void* dev[3];
+    for (int i = 0; i < 3; i++) dev[i] = host[i] ? base + off[i] : nullptr;
+    if ((rc = runFrameGuides(c, w, h, dev[0], dev[1], dev[2], stats)) != CRT_OK) return rc;
+    for (int i = 0; i < 3; i++)
+        if (host[i]) HIP_TRY(c, hipMemcpyAsync(host[i], dev[i], nn * per[i], hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+int crt_denoise_device(crt_ctx* c, uint32_t w, uint32_t h, const void* d_rgb, const void* d_normal, const void* d_albedo, const void* d_t,
+                       void* d_out, const crt_denoise_params* params, crt_frame_stats* stats)
+{
+    const char* what = "crt_denoise_device";
+    const crt_denoise_params prm = params ? *params : kDenoiseDefaults;
+    int rc = checkDenoise(c, what, w, h, d_rgb, d_normal, d_albedo, d_t, d_out, prm);
+    if (rc) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_out }, 4u)) != CRT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = runDenoise(c, what, w, h, d_rgb, d_normal, d_albedo, d_t, d_out, prm, stats)) != CRT_OK) return rc;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+// host buffers: staged through the context's query staging buffer {rgb | normal | albedo | t}, filtered in place; synchronous
+int crt_denoise(crt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const float* normal, const float* albedo, const float* t, float* out,
+                const crt_denoise_params* params, crt_frame_stats* stats)
+{
+    const char* what = "crt_denoise";
+    const crt_denoise_params prm = params ? *params : kDenoiseDefaults;
+    int rc = checkDenoise(c, what, w, h, rgb, normal, albedo, t, out, prm);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t nn = static_cast<size_t>(w) * h;
+    const void* const host[4] = { rgb, normal, albedo, t };
+    const size_t per[4] = { 12u, 12u, 12u, 4u };
+    size_t off[4], total = 0;
+    for (int i = 0; i < 4; i++) {
+        off[i] = total;
+        total += up256(nn * per[i]);
+    }
+    if ((rc = reserveRayStage(c, total)) != CRT_OK) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
+    for (int i = 0; i < 4; i++) HIP_TRY(c, hipMemcpyAsync(base + off[i], host[i], nn * per[i], hipMemcpyHostToDevice, c->stream));
+    if ((rc = runDenoise(c, what, w, h, base + off[0], base + off[1], base + off[2], base + off[3], base + off[0], prm, stats)) != CRT_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out, base + off[0], nn * 12u, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CRT_OK;

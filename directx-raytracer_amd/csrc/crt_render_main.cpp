@@ -42,6 +42,9 @@ static void usage()
                  "   [--phong KS_PERMILLE:EXPONENT]       mode 100 specular term\n"
                  "   [--gpu-build lbvh|ploc]              build the acceleration structure on the GPU with that builder (default: host SAH)\n"
                  "   [--out prefix] [--png] [--count]      frames as prefix_N.ppm, or prefix_N.png with --png\n"
+                 "   [--denoise [--denoise-iterations N]]  the last frame's float colour goes through the edge-avoiding a-trous filter with\n"
+                 "                                         its guide buffers (normal, albedo, t) before it is quantised and written; N = 1..8\n"
+                 "                                         passes (default 5); not with --ranks\n"
                  "   [--ranks N [--device-base D] [--id-file PATH]]   N processes / GPUs, RCCL gather per frame\n"
                  "   [--host-exchange [--same-device]]   with --ranks: tiles through shared host memory instead of RCCL; --same-device puts every\n"
                  "                                       rank on --device (a rehearsal of the multi-rank path on one GPU)\n");
@@ -55,7 +58,8 @@ struct Args {
     int spp = -1, bounces = -1, seed = -1, phongKs = -1, phongExp = -1, accumulate = -1;
     int gpuBuilder = -1; // --gpu-build: -1 = host SAH, 0 = LBVH, 1 = PLOC
     float orbit = 0.f, pitch = 0.f, forward = 0.f, right = 0.f, zoom = 0.f;
-    bool count = false, png = false, hostExchange = false, sameDevice = false;
+    bool count = false, png = false, hostExchange = false, sameDevice = false, denoise = false;
+    int denoiseIterations = 5;
     unsigned long long nonce = 0; // names the launch in the id file (set by the --ranks parent)
     std::map<int, uint32_t> modeAt;
 };
@@ -100,6 +104,7 @@ int runRank(const Args& a)
     if (a.accumulate >= 0) renderer.setAccumulation(static_cast<uint32_t>(a.accumulate));
     if (a.ranks > 0 && a.hostExchange) renderer.joinRanksThroughHostMemory(static_cast<uint32_t>(a.rank), static_cast<uint32_t>(a.ranks), a.nonce);
     else if (a.ranks > 0) renderer.joinRanks(static_cast<uint32_t>(a.rank), static_cast<uint32_t>(a.ranks), a.idFile, a.nonce);
+    renderer.setKeepFloatColour(a.denoise);
     const bool talk = a.ranks <= 0 || a.rank == 0;
     std::vector<std::string> script;
     if (!a.pathFile.empty()) {
@@ -134,6 +139,11 @@ int runRank(const Args& a)
         if (a.count) std::printf(", nodes %llu, tris %llu, shadow rays %llu", (unsigned long long)st.nodes_visited,
                                  (unsigned long long)st.tris_tested, (unsigned long long)st.rays_shadow);
         std::printf("\n");
+        if (a.denoise && f == a.frames - 1) {
+            crt_denoise_params prm = { static_cast<uint32_t>(a.denoiseIterations), 4.0f, 0.3f, 0.05f, 1u };
+            renderer.denoiseFrame(&prm);
+            std::printf("frame %d: denoised, %d passes\n", f, a.denoiseIterations);
+        }
         if (!a.out.empty()) {
             if (a.png) renderer.writePNG(a.out + "_" + std::to_string(f) + ".png");
             else renderer.writePPM(a.out + "_" + std::to_string(f) + ".ppm");
@@ -265,6 +275,8 @@ int main(int argc, char** argv)
             else { usage(); return 2; }
         }
         else if (s == "--png") a.png = true;
+        else if (s == "--denoise") a.denoise = true;
+        else if (s == "--denoise-iterations") a.denoiseIterations = std::atoi(next("--denoise-iterations"));
         else if (s == "--host-exchange") a.hostExchange = true;
         else if (s == "--same-device") a.sameDevice = true;
         else if (s == "--ranks") a.ranks = std::atoi(next("--ranks"));
@@ -275,6 +287,7 @@ int main(int argc, char** argv)
         else { usage(); return 2; }
     }
     if (a.frames < 1 || a.ranks < 0 || a.ranks > 64) { usage(); return 2; }
+    if (a.denoise && (a.ranks > 0 || a.denoiseIterations < 1 || a.denoiseIterations > 8)) { usage(); return 2; }
     try {
         if (a.ranks > 0 && a.rank < 0) return launchRanks(a, argc, argv);
         if (a.ranks > 0 && (a.rank >= a.ranks || a.idFile.empty())) { usage(); return 2; }

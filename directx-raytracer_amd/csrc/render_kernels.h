@@ -260,6 +260,38 @@ uint32_t listFillResident(uint32_t stack_entries);
 int launchListFill(const ListParams& q, bool counting, uint32_t grid, ihipStream_t* stream);
 // sorts every segment by (t', global id) and resolves the records into the outputs
 int launchListSort(const ListParams& q, ihipStream_t* stream);
+// camera rays (camera_kernels.hip; crt_camera_rays*, crt_frame_guides*): the frames' rayGen for a w x h frame as n = w * h ray
+// records {pos, kTMin, rayDirJ, kTMax}, record = py * width + px.  sample = kSampleCentre: the jitter (0.5, 0.5) of modes
+// 0..100; else the two draws a mode-200 frame takes for (pixel, sample, seed)
+constexpr uint32_t kSampleCentre = 0xFFFFFFFFu;
+struct CameraRayParams {
+    float pos[3];
+    float rot[9];
+    uint32_t width, height;
+    uint32_t sample, seed;
+    void* rays;                   // n records of 32 bytes, 16-byte aligned
+};
+int launchCameraRays(const CameraRayParams& p, ihipStream_t* stream);
+// the edge-avoiding a-trous filter (denoise_kernels.hip; crt_denoise*).  Scratch: three float4 planes of width * height --
+// the guide plane {n.xyz, t} and two colour planes {c.rgb, live} that the passes ping-pong between
+struct DenoiseParams {
+    uint32_t width, height;
+    uint32_t iterations;          // 1..8
+    uint32_t demodulate;          // 0 / 1
+    float inv_sigma_color2;       // 1 / sigma_color^2 of pass 0 (pass i: x 4^i); 0 switches the term off
+    float inv_sigma_normal2;      // 1 / sigma_normal^2
+    float sigma_depth;            // as given (+inf switches the term off)
+    const float* rgb;             // 3 floats per pixel
+    const float* normal;          // 3
+    const float* albedo;          // 3
+    const float* t;               // 1
+    float* out;                   // 3; may be rgb
+    void* guide;                  // scratch planes, 16 bytes per pixel each
+    void* colour[2];
+};
+constexpr size_t kDenoiseScratchPerPixel = 48;
+// pack, iterations - 1 passes, and the last pass fused with the multiply-back
+int launchDenoise(const DenoiseParams& p, ihipStream_t* stream);
 // exhaustive check of the triangle test's reciprocal (ray_kernels.hip rcpCheckKernel) into out[0..6] (device memory, zeroed
 // except out[6] = ~0 by the caller)
 int launchRcpCheck(unsigned long long* out, ihipStream_t* stream);

@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
@@ -96,8 +97,13 @@ void Renderer::renderFrame()
     // updateCameraCB every frame (R/DXRTRenderer.cpp:464)
     check(crt_set_camera(ctx, scene->getCamera().getPosition().data(), scene->getCamera().getRotationMatrix().data()), "crt_set_camera");
     frame.resize(static_cast<size_t>(width) * height * 4);
+    float* rgbF32 = nullptr;
+    if (keepFloatColour && !nRanks) {
+        floatColour.resize(static_cast<size_t>(width) * height * 3);
+        rgbF32 = floatColour.data();
+    }
     if (nRanks) check(crt_render_frame_distributed(ctx, width, height, nullptr, frame.data(), &stats), "crt_render_frame_distributed");
-    else check(crt_render_frame(ctx, width, height, frame.data(), nullptr, nullptr, nullptr, nullptr, &stats), "crt_render_frame");
+    else check(crt_render_frame(ctx, width, height, frame.data(), nullptr, nullptr, nullptr, rgbF32, &stats), "crt_render_frame");
 }
 
 double Renderer::rebuild()
@@ -188,6 +194,57 @@ void Renderer::pathRays(const float* rays, size_t n, PathHit* out, const uint32_
         PathHit& o = out[i];
         for (int k = 0; k < 3; k++) o.rgb[k] = rgb[3 * i + k];
         o.hit = RayHit{ t[i], uv[2 * i], uv[2 * i + 1], inst[i], prim[i] };
+    }
+}
+
+void Renderer::syncView()
+{
+    if (!ctx || !scene) throw std::runtime_error("no scene: call prepareForRendering first");
+    if (isChangedShadingMode) {
+        check(crt_set_shading_mode(ctx, currentShadingMode), "crt_set_shading_mode");
+        isChangedShadingMode = false;
+    }
+    check(crt_set_camera(ctx, scene->getCamera().getPosition().data(), scene->getCamera().getRotationMatrix().data()), "crt_set_camera");
+}
+
+void Renderer::cameraRays(std::vector<float>& rays, uint32_t sample)
+{
+    syncView();
+    rays.resize(static_cast<size_t>(width) * height * 8);
+    check(crt_camera_rays(ctx, width, height, sample, rays.data(), nullptr), "crt_camera_rays");
+}
+
+void Renderer::frameGuides(Guides& out)
+{
+    syncView();
+    const size_t n = static_cast<size_t>(width) * height;
+    out.normal.resize(3 * n);
+    out.albedo.resize(3 * n);
+    out.t.resize(n);
+    check(crt_frame_guides(ctx, width, height, out.normal.data(), out.albedo.data(), out.t.data(), nullptr), "crt_frame_guides");
+}
+
+void Renderer::denoise(const float* rgb, const Guides& guides, float* out, const crt_denoise_params* params)
+{
+    if (!ctx) throw std::runtime_error("denoise before prepareForRendering");
+    const size_t n = static_cast<size_t>(width) * height;
+    if (guides.normal.size() != 3 * n || guides.albedo.size() != 3 * n || guides.t.size() != n)
+        throw std::runtime_error("denoise: the guides are not of the current frame size");
+    check(crt_denoise(ctx, width, height, rgb, guides.normal.data(), guides.albedo.data(), guides.t.data(), out, params, nullptr), "crt_denoise");
+}
+
+void Renderer::denoiseFrame(const crt_denoise_params* params)
+{
+    const size_t n = static_cast<size_t>(width) * height;
+    if (floatColour.size() != 3 * n || frame.size() != 4 * n) throw std::runtime_error("denoiseFrame: no frame with float colour (setKeepFloatColour, renderFrame)");
+    Guides g;
+    frameGuides(g);
+    denoise(floatColour.data(), g, floatColour.data(), params);
+    // the kernels' unorm8 (traversal.hip.h): saturate (NaN -> 0), x 255, + 0.5, truncate
+    auto unorm8 = [](float c) { return static_cast<uint8_t>(std::fmin(std::fmax(c, 0.0f), 1.0f) * 255.0f + 0.5f); };
+    for (size_t i = 0; i < n; i++) {
+        for (int k = 0; k < 3; k++) frame[4 * i + k] = unorm8(floatColour[3 * i + k]);
+        frame[4 * i + 3] = 255;
     }
 }
 

@@ -72,6 +72,24 @@ public:
     };
     void pathRays(const float* rays, size_t n, PathHit* out, const uint32_t* ids = nullptr, uint32_t firstSample = 0, uint32_t nSamples = 1,
                   double* sums = nullptr);
+    // the frames' own camera rays for the current frame size and the scene's camera (crt_camera_rays, synchronous): width x
+    // height records of 8 floats, record py * width + px.  sample = CRT_SAMPLE_CENTRE: the rays of modes 0..100; a value
+    // below 2^24: the jittered rays of that mode-200 frame sample
+    void cameraRays(std::vector<float>& rays, uint32_t sample = CRT_SAMPLE_CENTRE);
+    // the guide buffers of the current frame size and camera (crt_frame_guides, synchronous; any shading mode): per pixel
+    // the shading normal and the albedo (3 floats) and t of the pixel-centre ray
+    struct Guides {
+        std::vector<float> normal, albedo, t;
+    };
+    void frameGuides(Guides& out);
+    // the edge-avoiding a-trous filter (crt_denoise, synchronous) on width x height buffers: rgb (3 floats per pixel) with its
+    // guides into out (may be rgb); params = nullptr: the defaults
+    void denoise(const float* rgb, const Guides& guides, float* out, const crt_denoise_params* params = nullptr);
+    // renderFrame() also keeps the frame's float colour (single-GPU path), for denoiseFrame()
+    void setKeepFloatColour(bool on) { keepFloatColour = on; }
+    const std::vector<float>& getFloatColour() const { return floatColour; }
+    // the last frame's float colour denoised with its guides and quantised into getFrame() with the frames' own UNORM rule
+    void denoiseFrame(const crt_denoise_params* params = nullptr);
     // every crossing of every ray, ascending in t (crt_list_hits, synchronous): the hits of ray i are hits[offsets[i]] ..
     // hits[offsets[i + 1] - 1].  One offsets-only call learns the total, a second one fills the records.
     void listHits(const float* rays, size_t n, std::vector<uint64_t>& offsets, std::vector<RayHit>& hits);
@@ -104,6 +122,9 @@ private:
     uint32_t currentShadingMode = 0; // R/DXRTRenderer.h:246
     bool isChangedShadingMode = true;
     std::vector<uint8_t> frame;
+    std::vector<float> floatColour; // rgb_f32 of the last frame when keepFloatColour
+    bool keepFloatColour = false;
+    void syncView(); // a pending mode change and the scene's camera, as renderFrame() applies them
     crt_frame_stats stats{};
     uint32_t rank = 0, nRanks = 0; // nRanks = 0: single-GPU path (crt_render_frame)
     bool dynamicGeometry = false;

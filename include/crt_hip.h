@@ -509,6 +509,83 @@ int crt_path_rays_device(crt_ctx* ctx, uint32_t n, const void* d_rays, const voi
 int crt_path_rays(crt_ctx* ctx, uint32_t n, const float* rays, const uint32_t* ids, uint32_t first_sample, uint32_t n_samples,
                   float* rgb, double* sums, float* t, float* uv, uint32_t* inst, uint32_t* prim, crt_frame_stats* stats);
 
+/* ---- camera rays: the frames' own camera rays as ray records (what a DXR rayGen shader computes from DispatchRaysIndex; the
+ * "record that holds a frame's camera ray" of crt_shade_rays* and crt_path_rays* without restating the ray generation).
+ * - Writes width * height records of 8 floats (the crt_trace_rays layout) in row-major pixel order, record py * width + px:
+ *   origin = the context's camera position (crt_set_camera), tmin = 0.001, direction = the frames' rayGen direction for that
+ *   pixel, tmax = 10000.
+ * - sample == CRT_SAMPLE_CENTRE: the jitter (0.5, 0.5), the rays of modes 0..100.  Otherwise (sample < 2^24): the two draws a
+ *   mode-200 frame takes for pixel id py * width + px and frame sample index `sample` with the context's seed (option "seed";
+ *   Python: path_jitter(ids, sample, seed)).  The mode is not read.
+ * - Bit for bit the ray the frame kernels trace: the kernel calls the frames' ray generation and hash chain, nothing is
+ *   restated.  So crt_shade_rays on the CRT_SAMPLE_CENTRE records gives a frame's rgb_f32 and hit_t in modes 0..100, and
+ *   crt_path_rays with first_sample = k, n_samples = 1 on the records of sample k, chained through one sums buffer for k = 0 ..
+ *   spp - 1, gives the mode-200 frame of spp samples.
+ * - Needs no scene.  Camera, mode, accumulation sums, launch orders and frame outputs are untouched.
+ * - CRT_EINVAL for a NULL ctx, a NULL buffer, width or height 0, width * height > 2^28, sample in [2^24, 0xFFFFFFFE], or a
+ *   device pointer that is not 16-byte aligned; nothing is launched then.
+ * - stats (may be NULL): kernel_ms, total_ms, rays_primary = width * height (rays generated; nothing is traced).
+ * *_device: asynchronous on the context's stream unless stats != NULL.  Host variant: synchronous, staged. */
+#define CRT_SAMPLE_CENTRE 0xFFFFFFFFu
+int crt_camera_rays_device(crt_ctx* ctx, uint32_t width, uint32_t height, uint32_t sample, void* d_rays, crt_frame_stats* stats);
+int crt_camera_rays(crt_ctx* ctx, uint32_t width, uint32_t height, uint32_t sample, float* rays, crt_frame_stats* stats);
+
+/* ---- frame guide buffers: per pixel the shading normal (3 floats), the albedo (3 floats) and t of the pixel-centre camera
+ * ray: the feature buffers an image-space denoiser is guided by (below), in the layout of rgb_f32 / hit_t.
+ * - Exactly what crt_shade_rays returns as normal, albedo and t for the CRT_SAMPLE_CENTRE records of crt_camera_rays, bit for
+ *   bit: a miss gives normal = albedo = (0, 0, 0) and t = 10000.  Each output is optional; not all three may be NULL.
+ * - Works in every shading mode, mode 200 included (the mode is not read: the surface evaluation does not depend on it).  A
+ *   separate pass over the camera rays: the frame kernels are not involved and a frame costs what it cost before.
+ * - The queries' common rules: pending refits are applied first; CRT_ESTATE without a scene; camera, mode, accumulation sums,
+ *   launch orders and frame outputs are untouched -- an accumulating mode-200 run goes on as if the call had not happened.
+ * - CRT_EINVAL for a NULL ctx, width or height 0, width * height > 2^28, all three outputs NULL, or a device pointer that is
+ *   not 4-byte aligned.  These checks come before the refit: a failed call launches nothing.
+ * - stats (may be NULL): kernel_ms = the camera-ray kernel and the shaded query together, rays_primary = width * height; with
+ *   crt_set_counting(ctx, 1) nodes_visited / tris_tested as crt_shade_rays counts them.
+ * - Temporary memory: 32 B per pixel (the records) in the context's query arena of the stream.
+ * *_device: asynchronous on the context's stream unless stats != NULL.  Host variant: synchronous, staged. */
+int crt_frame_guides_device(crt_ctx* ctx, uint32_t width, uint32_t height, void* d_normal, void* d_albedo, void* d_t,
+                            crt_frame_stats* stats);
+int crt_frame_guides(crt_ctx* ctx, uint32_t width, uint32_t height, float* normal, float* albedo, float* t, crt_frame_stats* stats);
+
+/* ---- denoiser: the edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010) on row-major width x height
+ * buffers: rgb, normal, albedo (3 floats per pixel) and t (1 float per pixel), the layouts of rgb_f32 and of crt_frame_guides.
+ * A pure image-space filter: no scene is needed and any colour / guide buffers of that layout will do.
+ * - Live pixels: a pixel is live when all 10 of its input values are finite, its normal has a non-zero component and t > 0.
+ *   A pixel that is not live (a miss, a NaN firefly, a hole the caller cut) is copied from rgb to out bit for bit and is never
+ *   a tap of another pixel.
+ * - Demodulation: a = demodulate ? max(albedo, 1e-3) per channel : 1, and c_0 = rgb / a (texture detail is divided out,
+ *   filtered irradiance is multiplied back).  rgb / a must stay finite.
+ * - Pass i = 0 .. iterations - 1: stride s = 2^i, sigma_c,i = sigma_color 2^-i.  For a live centre p the taps are q = p +
+ *   s (dx, dy), dx, dy in -2 .. 2; only taps inside the image and live are used.
+ *     e = |c_i(p) - c_i(q)|^2 / sigma_c,i^2 + |n_p - n_q|^2 / sigma_normal^2 + (t_p - t_q)^2 / (sigma_depth t_p)^2
+ *     w = h[dx + 2] h[dy + 2] exp(-e),  h = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *     c_{i+1}(p) = sum w c_i(q) / sum w      (the centre tap has e = 0, w = 9/64: the divisor is positive)
+ * - Output: out = c_N a.
+ * - Arithmetic: float32 throughout.  There is no bit-for-bit contract against a CPU form, because exp has none.  What holds:
+ *   the deviation from a float64 evaluation of the formulas above stays within 16 x that of a float32 evaluation on the host
+ *   (metric |x - ref| / max(|ref|, 1e-3); tests/test_denoise.py); determinism -- no atomics, the same input gives the same
+ *   bits; and the host form equals the device form bit for bit.
+ * - Aliasing: d_out may equal d_rgb (in place); no other two buffers may overlap.
+ * - params == NULL means the defaults.  CRT_EINVAL for iterations outside 1..8; a sigma that is <= 0 or NaN (+inf is allowed
+ *   and switches its term off); demodulate other than 0 / 1; width or height 0; width * height > 2^28; a NULL context or
+ *   buffer; a device pointer that is not 4-byte aligned.  A failed call launches nothing and leaves out untouched.
+ * - stats (may be NULL): kernel_ms = all kernels of the call, total_ms; every count is zero.
+ * - Scratch is context-owned (the query arena of the stream), grows on demand and is freed by crt_destroy: 48 B per pixel --
+ *   the guide plane {n, t} and two colour planes {c, live}, 16 B each.  CRT_ENOMEM when it cannot be had, nothing launched.
+ * *_device: asynchronous on the context's stream unless stats != NULL.  Host variant: synchronous, staged. */
+typedef struct crt_denoise_params {
+    uint32_t iterations;  /* 1..8, default 5: pass i samples at stride 2^i */
+    float sigma_color;    /* default 4.0; halved every pass */
+    float sigma_normal;   /* default 0.3 */
+    float sigma_depth;    /* default 0.05, relative to the centre pixel's t */
+    uint32_t demodulate;  /* default 1: filter rgb / albedo, multiply back at the end */
+} crt_denoise_params;
+int crt_denoise_device(crt_ctx* ctx, uint32_t width, uint32_t height, const void* d_rgb, const void* d_normal, const void* d_albedo,
+                       const void* d_t, void* d_out, const crt_denoise_params* params /* NULL = defaults */, crt_frame_stats* stats);
+int crt_denoise(crt_ctx* ctx, uint32_t width, uint32_t height, const float* rgb, const float* normal, const float* albedo,
+                const float* t, float* out, const crt_denoise_params* params, crt_frame_stats* stats);
+
 /* ---- point queries: closest surface point, hit counts, occupancy (no reference counterpart; the set of Open3D's
  * RaycastingScene: compute_closest_points / compute_distance / compute_signed_distance / compute_occupancy /
  * count_intersections).  SDF and occupancy training data, collision margins, snapping a point to the surface.
