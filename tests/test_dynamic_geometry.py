@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import shaded_query_checks as sq
+
 SYMBOLS = ("crt_update_vertices", "crt_update_vertices_device", "crt_set_mesh_transform", "crt_refit", "crt_mesh_vertices")
 METHODS = ("update_vertices", "set_mesh_transform", "refit", "mesh_vertices")
 EINVAL, ESTATE = 1, 5
@@ -288,6 +290,9 @@ def test_deformation_matches_the_oracle(pkg, scenes, oracle, renderer, gpu_build
             assert n4.tobytes() == S.nodes4().tobytes() and d4 == S.depth4
             assert renderer.bvh_export4q().tobytes() == S.nodes4q().tobytes()
             _check_frames_vs_oracle(renderer, S, cam, w, h, MODES)
+            # the same frames through camera_rays, shade_rays, path_rays and frame_guides
+            sq.frame_records_equal_frames(renderer, {m: S.render(cam["position"], cam["matrix"], m, w, h) for m in (3, 100, 200)}, w, h,
+                                          (2, 2, 99), "deformed scene %d, gpu_build %d" % (si, gpu_build), scene=dict(sc, meshes=moved))
             for mode in (3, 100):  # hits do not depend on the tree
                 renderer.change_shading_mode(mode)
                 got = _frame(renderer, w, h)[0]

@@ -11,6 +11,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ploc_reference as spec  # noqa: E402
+import shaded_query_checks as sq  # noqa: E402
 import test_list_hits as lh  # noqa: E402
 import test_point_queries as pq  # noqa: E402
 from test_dynamic_geometry import _numpy_refit  # noqa: E402
@@ -24,6 +25,7 @@ ALL_MODES = (0, 1, 2, 3, 4, 5, 6, 100, 200)
 LBVH, PLOC = 0, 1
 N_RAYS = 2000
 PATH_PARAMS = (2, 2, 99)
+N_SEEDED, MAX_AIMED = 64, 8  # poses per case: seeded ones, and one aimed at each of up to 8 inert triangles
 
 
 def _bits(a):
@@ -219,6 +221,45 @@ def _assert_none_inert(sc, inst, prim, what):
     assert not np.isin(key, _inert_ids(sc)).any(), "%s: an inert triangle was reported" % what
 
 
+def _aimed_poses(sc):
+    """one pose per inert triangle (at most MAX_AIMED, spread evenly over them): at C + 0.25 L n for the centroid C, the unit
+    normal n and the shortest edge L of the triangle's clean vertices, turned so that the pixel-centre ray of a 1 x 1 frame
+    (the camera's -z axis: the rotation's third column is n) runs along -n.  In the clean scene that ray's closest hit is the
+    triangle.  Returns positions, rotations and the (inst, prim) aimed at."""
+    clean = sc.get("clean", sc["meshes"])
+    ids = [(i, int(p)) for i, dead in enumerate(sc["inert"]) for p in np.flatnonzero(dead)]
+    if len(ids) > MAX_AIMED:
+        ids = [ids[k] for k in np.linspace(0, len(ids) - 1, MAX_AIMED).astype(int)]
+    pos, rot = np.zeros((len(ids), 3), np.float32), np.zeros((len(ids), 9), np.float32)
+    for k, (i, p) in enumerate(ids):
+        v = np.asarray(clean[i]["vertices"], dtype=np.float32).reshape(-1, 3).astype(np.float64)
+        a, b, c = v[np.asarray(clean[i]["triangles"], dtype=np.int64).reshape(-1, 3)[p]]
+        n = np.cross(b - a, c - a)
+        n /= np.linalg.norm(n)
+        L = min(np.linalg.norm(b - a), np.linalg.norm(c - b), np.linalg.norm(a - c))
+        x = np.cross(np.eye(3)[np.argmin(np.abs(n))], n)
+        x /= np.linalg.norm(x)
+        pos[k] = (a + b + c) / 3.0 + 0.25 * L * n
+        rot[k] = np.stack([x, np.cross(n, x), n], axis=1).astype(np.float32).reshape(9)
+    return pos, rot, ids
+
+
+def _pose_refs(oracle, sc):
+    """the case's poses with their brute-force 1 x 1 oracle frames in modes 100 and 200 (PATH_PARAMS), computed once and
+    shared: N_SEEDED seeded poses over the finite vertices' box, then the aimed ones"""
+    if "poses" not in sc:
+        pos, rot = sq.poses(sc, n=N_SEEDED)
+        apos, arot, aimed = _aimed_poses(sc)
+        P = sq.pose_set(oracle, sc, np.concatenate([pos, apos]), np.concatenate([rot, arot]), PATH_PARAMS, brute_force=True)
+        P["aimed"], P["n_seeded"] = aimed, len(pos)
+        for mode in (100, 200):
+            _assert_none_inert(sc, P[mode]["inst"], P[mode]["prim"], "poses mode %d" % mode)
+            for a in P[mode].values():
+                a.setflags(write=False)
+        sc["poses"] = P
+    return sc["poses"]
+
+
 def _assert_tree_equals_brute_force(oracle, O, sc, what, w=96, h=96):
     """the oracle's walk over the tree O holds against brute force over the same records: closest hits and occlusion of the
     case's generic rays, frames in modes 3, 100 and 200 -- every bit, no exemptions"""
@@ -372,6 +413,55 @@ def test_brute_force_results_equal_the_scene_without_the_inert_triangles(pkg, or
     np.testing.assert_array_equal(lp["inst"], ld["inst"], err_msg=what)
     np.testing.assert_array_equal(lp["prim"], _map_back(ld["inst"], ld["prim"], back), err_msg=what)
     assert np.array_equal(_bits(lp["t"]), _bits(ld["t"])) and np.array_equal(_bits(lp["uv"]), _bits(ld["uv"])), what
+    # the poses of the shaded and path-traced queries: colour and hit of the 1 x 1 frames (oracle, brute force)
+    poses = _pose_refs(oracle, sc)
+    for mode in (100, 200):
+        p = poses[mode]
+        d = sq.pose_reference(oracle, sc, poses["pos"], poses["rot"], mode, brute_force=True, path_params=PATH_PARAMS, meshes=meshes)
+        np.testing.assert_array_equal(p["inst"], d["inst"], err_msg="%s poses mode %d" % (what, mode))
+        np.testing.assert_array_equal(p["prim"], _map_back(d["inst"], d["prim"], back), err_msg="%s poses mode %d" % (what, mode))
+        assert np.array_equal(_bits(p["rgb"]), _bits(d["rgb"])) and np.array_equal(_bits(p["t"]), _bits(d["t"])), "%s poses mode %d" % (what, mode)
+
+
+# ---- CPU: the scenes of the GPU tests can show an inert triangle that is hit, that occludes or that is bounced onto
+
+def test_poses_and_frames_would_show_an_inert_triangle_that_is_hit_or_occludes(oracle, case):
+    """the oracle alone, over _GPU_PARAMS together: every aimed pose hits its triangle in the clean scene and not in the poisoned
+    one, and there are at least 20 of them; "never occlude": the camera frame of cornell_whole_mesh has at least 16 pixels whose
+    primary hit is the same with and without the short box and whose mode-100 colour differs (its shadow on the floor); "never
+    bounced onto": some pose or pixel in mode 200 has the same primary hit and another colour"""
+    def changed(a, b, inst="inst", prim="prim"):
+        same = (a[inst] == b[inst]) & (a[prim] == b[prim]) & (a[inst] != MISS)
+        return int((same & np.any(_bits(a["rgb"]) != _bits(b["rgb"]), axis=-1)).sum())
+
+    aimed, lit, bounced, shadow_pixels = 0, 0, 0, None
+    for name, kind in _GPU_PARAMS:
+        sc = case(name, kind)
+        clean = _clean_scene(sc)
+        P = _pose_refs(oracle, sc)
+        C = {m: sq.pose_reference(oracle, clean, P["pos"], P["rot"], m, brute_force=True, path_params=PATH_PARAMS) for m in (100, 200)}
+        for j, (inst, prim) in enumerate(P["aimed"]):
+            k = P["n_seeded"] + j
+            assert (C[100]["inst"][k], C[100]["prim"][k]) == (inst, prim), "%s %s: aimed pose %d misses its triangle in the clean scene" % (name, kind, j)
+            assert (P[100]["inst"][k], P[100]["prim"][k]) != (inst, prim), "%s %s: aimed pose %d" % (name, kind, j)
+        aimed += len(P["aimed"])
+        lit += changed(P[100], C[100])
+        bounced += changed(P[200], C[200])
+        if name == "cornell_whole_mesh":
+            cam = sc["camera"]
+            oracle.set_path_params(*PATH_PARAMS)
+            try:
+                f = {(which, m): _oracle_scene(oracle, s).render(cam["position"], cam["matrix"], m, W, H, brute_force=True)
+                     for which, s in (("poisoned", sc), ("clean", clean)) for m in (100, 200)}
+            finally:
+                oracle.set_path_params(4, 3, 1234)
+            shadow_pixels = changed(f[("poisoned", 100)], f[("clean", 100)], "hit_inst", "hit_prim")
+            bounced += changed(f[("poisoned", 200)], f[("clean", 200)], "hit_inst", "hit_prim")
+    print("aimed poses %d; same primary hit, other colour: %d mode-100 poses, %d cornell_whole_mesh mode-100 pixels, %d mode-200 poses and pixels"
+          % (aimed, lit, shadow_pixels, bounced))
+    assert aimed >= 20, aimed
+    assert shadow_pixels >= 16, shadow_pixels
+    assert bounced >= 1, bounced
 
 
 # ---- CPU: the host builder writes the oracle's bytes, and every ancestor's quantised box holds every finite triangle
@@ -489,8 +579,10 @@ def _references(pkg, oracle, sc, point_ref, list_ref):
         P = _oracle_scene(oracle, sc)
         recs, rays, cam = P.tris(), sc["rays"], sc["camera"]
         pts = _points(pkg, sc, 1000, 5)
+        poses = _pose_refs(oracle, sc)  # (leaves the oracle's default path parameters behind)
         oracle.set_path_params(*PATH_PARAMS)
         sc["refs"] = {
+            "poses": poses, "shaded_cache": {},
             "frames": {m: P.render(cam["position"], cam["matrix"], m, W, H, brute_force=True) for m in ALL_MODES},
             "trace": oracle.trace_rays(P, rays, brute_force=True), "occluded": oracle.occluded_rays(P, rays, brute_force=True)["occluded"],
             "count": pq.ref_count(point_ref, recs, rays), "lists": lh.ref_list(list_ref, recs, rays), "points": pts,
@@ -559,8 +651,10 @@ def _assert_frame(got, ref, what, rgb=True):
 def _check_gpu(pkg, oracle, r, sc, refs, what, same_tree=None):
     """the scene r holds is sc: its wide and quantised trees are the oracle's collapse of its binary tree, its frames in every
     mode (both path pipelines) equal the oracle's over that tree with the fetch counters, and the brute-force frames; the host
-    and device forms of the six queries equal their brute-force references.  same_tree: an oracle scene known to hold the same
-    tree (it keeps uvs, which OracleScene.set_bvh drops)."""
+    and device forms of the six queries equal their brute-force references; camera_rays through shade_rays and path_rays give
+    the brute-force frames, frame_guides the frames' surfaces, and shade_rays / path_rays on the generic rays and on the poses
+    their brute-force references (tests/shaded_query_checks.py).  same_tree: an oracle scene known to hold the same tree (it
+    keeps uvs, which OracleScene.set_bvh drops)."""
     nodes, tris, shade = r.bvh_export()
     S = same_tree
     if S is None:
@@ -593,6 +687,12 @@ def _check_gpu(pkg, oracle, r, sc, refs, what, same_tree=None):
             "closest": r.closest_points(pts), "occupancy": r.occupancy(pts)}
     _assert_queries(host, refs, what + " (host forms)")
     _assert_queries(_device_queries(r, rays, pts, int(refs["lists"]["offsets"][-1])), refs, what + " (device forms)")
+    # shade_rays, path_rays and frame_guides: the frame's camera_rays, the generic rays and the poses
+    scene = {"meshes": sc["meshes"], "materials": sc["materials"], "textures": sc.get("textures")}
+    sq.frame_records_equal_frames(r, refs["frames"], W, H, PATH_PARAMS, what, scene=scene, texture_color=oracle.texture_color,
+                                  cache=refs["shaded_cache"])
+    sq.arbitrary_records_equal_trace(r, rays, refs["trace"], what, meshes=sc["meshes"])
+    sq.pose_records_equal_oracle(r, refs["poses"], what, meshes=sc["meshes"])
     return nodes, tris, shade
 
 
@@ -668,7 +768,7 @@ def _dynamic_round_trip(pkg, oracle, point_ref, list_ref, r, builder, clean, sc,
 
 
 def _clean_scene(sc):
-    clean = {k: v for k, v in sc.items() if k not in ("meshes", "clean", "inert", "rays", "refs")}
+    clean = {k: v for k, v in sc.items() if k not in ("meshes", "clean", "inert", "rays", "refs", "poses")}
     clean["meshes"] = sc["clean"]
     clean["inert"] = [np.zeros(len(np.asarray(m["triangles"]).reshape(-1, 3)), bool) for m in sc["clean"]]
     clean["rays"] = sc["rays"]
@@ -712,7 +812,7 @@ def test_a_transform_that_overflows_makes_the_mesh_inert(pkg, scenes, oracle, po
         M = np.float32([[2e38, 0, 0, 0], [0, 1, 0, 0.5], [0, 0, 1, -0.25]])
         with np.errstate(over="ignore"):
             moved = [clean["meshes"][0], dict(probe, vertices=_apply(M, probe["vertices"]))]
-        sc = dict(clean, meshes=moved, inert=_inert_mask(moved))
+        sc = dict(clean, meshes=moved, inert=_inert_mask(moved), clean=clean["meshes"])
         assert sc["inert"][1].all() and np.isposinf(moved[1]["vertices"][:, 0]).all() and np.isfinite(moved[1]["vertices"][:, 1:]).all()
         _cache[key], _cache[("overflow", "moved")] = clean, (sc, M)
     clean, (sc, M) = _cache[key], _cache[("overflow", "moved")]

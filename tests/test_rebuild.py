@@ -10,6 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ploc_reference as spec  # noqa: E402
+import shaded_query_checks as sq  # noqa: E402
 
 EINVAL, ESTATE = 1, 5
 MODES = (0, 1, 2, 3, 4, 5, 6, 100, 200)
@@ -350,6 +351,41 @@ def test_rebuild_without_changes_reproduces_the_upload(pkg, scenes, renderer, bu
     r.set_option("gpu_build", 0)
 
 
+def _shaded_outputs(r, rays, w, h):
+    """every output of shade_rays (mode 100) and path_rays (2 samples) on `rays` and on the frame's camera rays, and the guides"""
+    r.change_shading_mode(100)
+    centre = r.camera_rays(w, h)
+    out = {"camera_rays": centre}
+    for tag, recs in (("rays", rays), ("camera rays", centre)):
+        shaded, paths = r.shade_rays(recs), r.path_rays(recs, n_samples=2)
+        out.update({"shade_rays %s, %s" % (k, tag): shaded[k] for k in sq.SHADE_OUTPUTS})
+        out.update({"path_rays %s, %s" % (k, tag): paths[k] for k in ("rgb",) + sq.HIT_OUTPUTS})
+    guides = r.frame_guides(w, h)
+    out.update({"frame_guides " + k: guides[k] for k in ("normal", "albedo", "t")})
+    return out
+
+
+def _guides_and_paths_hold(r, w, h, what):
+    """guides == shade_rays on the centre records; path_rays on the sample-0 records == the 1-spp mode-200 frame"""
+    r.set_path_params(1, 2, 99)
+    try:
+        r.change_shading_mode(200)
+        frame = r.render_frame(w, h)
+        got = r.path_rays(r.camera_rays(w, h, sample=0))
+        assert np.array_equal(_bits(got["rgb"]), _bits(frame["rgb"].reshape(-1, 3))), what + ": path_rays rgb"
+        assert np.array_equal(_bits(got["t"]), _bits(frame["hit_t"].reshape(-1))), what + ": path_rays t"
+        np.testing.assert_array_equal(got["inst"], frame["hit_inst"].reshape(-1), err_msg=what)
+        np.testing.assert_array_equal(got["prim"], frame["hit_prim"].reshape(-1), err_msg=what)
+        assert (got["inst"] != 0xFFFFFFFF).sum() > w * h // 10, what + ": the camera sees the scene"
+        r.change_shading_mode(100)
+        ref = r.shade_rays(r.camera_rays(w, h), want=("normal", "albedo", "t"))
+        guides = r.frame_guides(w, h)
+        for k in ("normal", "albedo", "t"):
+            assert np.array_equal(_bits(guides[k]).reshape(-1), _bits(ref[k]).reshape(-1)), "%s: frame_guides %s" % (what, k)
+    finally:
+        r.set_path_params(4, 3, 1234)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("builder", [LBVH, PLOC])
 def test_rebuild_of_moved_meshes_equals_a_fresh_build(pkg, scenes, oracle, dragon, renderer, builder):
@@ -408,6 +444,20 @@ def test_rebuild_of_moved_meshes_equals_a_fresh_build(pkg, scenes, oracle, drago
         for i in range(0, len(rays), 20):
             ray = rays[i]
             assert bool(occ[i]) == bool(oracle.occluded(S, ray[0:3], ray[4:7], ray[3], ray[7])), "ray %d" % i
+        # the shaded, path-traced and guide queries: the rebuilt context against a fresh upload of the moved meshes, every bit
+        r2 = pkg.Renderer(0)
+        try:
+            r2.set_option("gpu_build", 1)
+            r2.set_option("gpu_builder", builder)
+            r2.upload(moved, sc["lights"], sc["materials"])
+            r2.set_camera(cam["position"], cam["matrix"])
+            r2.set_path_params(2, 2, 99)
+            rebuilt, fresh = _shaded_outputs(r, rays, w, h), _shaded_outputs(r2, rays, w, h)
+        finally:
+            r2.close()
+        for key in rebuilt:
+            assert np.array_equal(rebuilt[key].view(np.uint32), fresh[key].view(np.uint32)), "%s: rebuilt and fresh differ" % key
+        assert (rebuilt["shade_rays inst, rays"] != 0xFFFFFFFF).sum() > 500 and (rebuilt["path_rays inst, camera rays"] != 0xFFFFFFFF).sum() > w * h // 10
         # a later deformation + refit refits the rebuilt shape
         v2 = (moved[0]["vertices"] + np.float32(0.02)).astype(np.float32)
         r.update_vertices(0, v2)
@@ -438,6 +488,7 @@ def test_rebuild_builders_in_turn_then_refit(pkg, scenes, oracle, renderer):
     r.set_option("gpu_build", 0)
     r.set_option("gpu_builder", LBVH)
     r.upload(sc["meshes"], sc["lights"], sc["materials"], dynamic=True)
+    r.set_camera(sc["camera"]["position"], sc["camera"]["matrix"])
     M = _rot(10.0, 1)
     r.set_mesh_transform(0, M)
     moved = [dict(m) for m in sc["meshes"]]
@@ -445,11 +496,14 @@ def test_rebuild_builders_in_turn_then_refit(pkg, scenes, oracle, renderer):
     try:
         r.rebuild()
         assert _export(r) == _fresh(pkg, sc, moved, LBVH)
+        _guides_and_paths_hold(r, 128, 96, "rebuilt with the LBVH")
         r.set_option("gpu_builder", PLOC)
         r.rebuild()
         assert _export(r) == _fresh(pkg, sc, moved, PLOC)
+        _guides_and_paths_hold(r, 128, 96, "rebuilt with PLOC")
         r.set_mesh_transform(0, None)
         r.refit()
+        _guides_and_paths_hold(r, 128, 96, "refitted to the rest pose")
         nodes, tris, shade = r.bvh_export()
         S = oracle.OracleScene(sc["meshes"], sc["lights"], sc["materials"])
         S.set_bvh(nodes, tris, shade)

@@ -7,6 +7,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from shaded_query_checks import bounds as _bounds, pose_rays as _pose_rays, pose_reference as _pose_reference, poses as _poses
+
 SYMBOLS = ("crt_shade_rays_device", "crt_shade_rays")
 MISS = 0xFFFFFFFF
 EINVAL, ESTATE = 1, 5
@@ -55,48 +57,6 @@ def _soup(scenes, n_lights=3):
     sc = scenes.icosphere_soup(n_spheres=400)
     sc["lights"] = list(SOUP_LIGHTS[:n_lights])
     return sc
-
-
-def _bounds(sc):
-    v = np.concatenate([np.asarray(m["vertices"], dtype=np.float32).reshape(-1, 3) for m in sc["meshes"]])
-    return v.min(axis=0), v.max(axis=0)
-
-
-def _poses(sc, n=N_POSES, seed=POSE_SEED):
-    """n seeded poses: positions in and around the scene's box (a tenth of its extent beyond it on every side), rotations
-    random orthonormal float32 matrices"""
-    rng = np.random.default_rng(seed)
-    lo, hi = _bounds(sc)
-    ext = hi - lo
-    pos = (lo - 0.1 * ext + rng.random((n, 3)) * 1.2 * ext).astype(np.float32)
-    rot = np.empty((n, 9), dtype=np.float32)
-    for k in range(n):
-        q, r = np.linalg.qr(rng.normal(size=(3, 3)))
-        rot[k] = (q * np.sign(np.diag(r))).astype(np.float32).reshape(9)
-    return pos, rot
-
-
-def _pose_rays(oracle, pos, rot):
-    rays = np.empty((len(pos), 8), dtype=np.float32)
-    for k in range(len(pos)):
-        rays[k, 0:3], rays[k, 3], rays[k, 4:7], rays[k, 7] = pos[k], TMIN, oracle.ray_dir(rot[k], 0, 0, 1, 1), TMAX
-    return rays
-
-
-def _pose_reference(oracle, sc, pos, rot, mode=100, build_mode=0):
-    """1 x 1 oracle frames: per pose the colour, the hit and the frame's statistics"""
-    O = oracle.OracleScene(sc["meshes"], sc["lights"], sc["materials"], build_mode=build_mode, textures=sc.get("textures") or ())
-    n = len(pos)
-    ref = {"rgb": np.zeros((n, 3), np.float32), "inst": np.zeros(n, np.uint32), "prim": np.zeros(n, np.uint32),
-           "t": np.zeros(n, np.float32), "shadow": np.zeros(n, np.uint64), "nodes": np.zeros(n, np.uint64), "tris": np.zeros(n, np.uint64)}
-    try:
-        for k in range(n):
-            f = O.render(pos[k], rot[k], mode, 1, 1, n_threads=1)
-            ref["rgb"][k], ref["inst"][k], ref["prim"][k], ref["t"][k] = f["rgb"][0, 0], f["hit_inst"][0, 0], f["hit_prim"][0, 0], f["hit_t"][0, 0]
-            ref["shadow"][k], ref["nodes"][k], ref["tris"][k] = f["stats"]["rays_shadow"], f["stats"]["nodes_visited"], f["stats"]["tris_tested"]
-    finally:
-        O.close()
-    return ref
 
 
 @pytest.fixture(scope="module")

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 import path_reference as R
+import shaded_query_checks as sq
 import test_path_reference as T
 
 f32 = np.float32
@@ -388,13 +389,30 @@ def _moved(name):
     return 1, f32([[c, 0, s, 0.0], [0, 1, 0, 0.0], [-s, 0, c, -0.3]])   # the bitmap wall, turned about y
 
 
+ROUTE_PATH_PARAMS = (1, 2, 1234)
+
+
+def _oracle_frames(oracle, sc, cam):
+    """the oracle's frames of the scene in modes 3, 100 and 200 (ROUTE_PATH_PARAMS) with the float64 reference's miss colour:
+    the bit-exact yardstick test_path_reference pins to the float64 reference on these scenes"""
+    O = oracle.OracleScene(sc["meshes"], sc["lights"], sc["materials"], textures=sc.get("textures", ()))
+    oracle.set_path_params(*ROUTE_PATH_PARAMS)
+    try:
+        return {m: O.render(cam["position"], cam["matrix"], m, T.W, T.H, miss_rgb=R.MISS_RGB) for m in (3, 100, 200)}
+    finally:
+        oracle.set_path_params(4, 3, 1234)
+        O.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("route", ROUTES)
 @pytest.mark.parametrize("name", T.TEXTURED)
-def test_gpu_uv_records_reach_leaf_order(pkg, scenes, name, route):
+def test_gpu_uv_records_reach_leaf_order(pkg, oracle, scenes, name, route):
     """mode 100 at pixel centres and one mode-200 frame per pipeline, against the float64 reference, after each kind of upload or
     tree change.  The reference knows per-vertex uvs only, so a uv record attached to the wrong triangle, or in the wrong
-    vertex order, moves the texture."""
+    vertex order, moves the texture.  Then the same frame through camera_rays, shade_rays, path_rays and frame_guides, which
+    read the uv records through their own parameter block, against the oracle's frames bit for bit; the guide albedo of a
+    textured hit is the oracle's texture_color at the hit's interpolated uv."""
     sc = R.SCENES[name](scenes)
     meshes = [dict(m) for m in sc["meshes"]]
     cam = sc["camera"]
@@ -432,5 +450,72 @@ def test_gpu_uv_records_reach_leaf_order(pkg, scenes, name, route):
             r.set_option("path_pipeline", pipeline)
             r.set_path_params(1, 2, 1234)
             T.compare_path_frame(r.render_frame(T.W, T.H), ref, "%s %s pipeline=%d" % (name, route, pipeline))
+        r.set_option("path_pipeline", 0)
+        now = dict(sc, meshes=meshes)
+        got = sq.frame_records_equal_frames(r, _oracle_frames(oracle, now, cam), T.W, T.H, ROUTE_PATH_PARAMS, "%s %s" % (name, route),
+                                            scene=now, texture_color=oracle.texture_color)
+        hit = got["guides"]["t"] != f32(sq.TMAX)
+        assert len(np.unique(got["guides"]["albedo"][hit], axis=0)) >= 4, "the textures show in the albedo guide"
     finally:
         r.close()
+
+
+def _upload_over_route(pkg, sc, name, route, moved=None):
+    """a context holding the scene with its textured mesh moved (_moved), reached over `route`: the three dynamic routes upload the
+    rest pose and move the mesh; the three static ones upload `moved`, the meshes as a dynamic route traced them"""
+    r = pkg.Renderer(0)
+    try:
+        r.set_accumulation(0)
+        r.set_option("gpu_build", 0 if route in ("host_sah", "transform_refit") else 1)
+        r.set_option("gpu_builder", PLOC if route.endswith("ploc") else LBVH)
+        dynamic = route.startswith("rebuild") or route == "transform_refit"
+        r.upload(sc["meshes"] if dynamic else moved, sc["lights"], sc["materials"], sc.get("textures"), dynamic=dynamic)
+        if dynamic:
+            mesh, M = _moved(name)
+            r.set_mesh_transform(mesh, M)
+            if route == "transform_refit":
+                r.refit()
+            else:
+                r.rebuild()
+        r.set_camera(sc["camera"]["position"], sc["camera"]["matrix"])
+        r.set_miss_color(R.MISS_RGB)
+        r.change_shading_mode(100)
+        return r
+    except Exception:
+        r.close()
+        raise
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", T.TEXTURED)
+def test_gpu_guide_albedo_is_the_same_over_every_route(pkg, scenes, name):
+    """One geometry (the scene with its textured mesh moved), one camera, the six routes: the albedo guide, and with it normal
+    and t, have the same bits over every route.  The frames read the uv records through fillParams and are compared route by
+    route above; the guides read them through the shaded queries' parameter block, so a stale uv pointer or an ungathered uv
+    record after crt_rebuild shows here."""
+    sc = R.SCENES[name](scenes)
+    mesh, _ = _moved(name)
+    guides, moved = {}, None
+    for route in ["transform_refit"] + [x for x in ROUTES if x != "transform_refit"]:
+        r = _upload_over_route(pkg, sc, name, route, moved)
+        try:
+            if route.startswith("rebuild") or route == "transform_refit":  # (crt_mesh_vertices reads dynamic scenes only)
+                xyz, nrm = r.mesh_vertices(mesh)
+                if moved is None:
+                    moved = [dict(m) for m in sc["meshes"]]
+                    moved[mesh]["vertices"] = np.asarray(xyz, np.float32).reshape(-1, 3).copy()
+                    if nrm is not None:
+                        moved[mesh]["normals"] = np.asarray(nrm, np.float32).reshape(-1, 3).copy()
+                assert np.array_equal(sq._bits(xyz).reshape(-1), sq._bits(moved[mesh]["vertices"]).reshape(-1)), "%s %s: the traced vertices" % (name, route)
+            guides[route] = r.frame_guides(T.W, T.H)
+            ref = r.shade_rays(r.camera_rays(T.W, T.H), want=("normal", "albedo", "t"))
+            for k in ("normal", "albedo", "t"):
+                assert np.array_equal(sq._bits(guides[route][k]).reshape(-1), sq._bits(ref[k]).reshape(-1)), "%s %s: guide %s against shade_rays" % (name, route, k)
+        finally:
+            r.close()
+    first = guides["transform_refit"]
+    hit = first["t"] != f32(sq.TMAX)
+    assert hit.sum() > T.W * T.H // 4 and len(np.unique(first["albedo"][hit], axis=0)) >= 4, "the camera sees the textures"
+    for route in ROUTES:
+        for k in ("albedo", "normal", "t"):
+            assert np.array_equal(sq._bits(guides[route][k]), sq._bits(first[k])), "%s: guide %s over %s differs from transform_refit" % (name, k, route)

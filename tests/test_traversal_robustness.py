@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import path_reference as R
+import shaded_query_checks as sq
 
 MISS = 0xFFFFFFFF
 OFFSETS = (0.0, 128.0, 1024.0, 8192.0, 131072.0)  # ~ 1e2, 1e3, 1e4, 1e5
@@ -336,9 +337,12 @@ def _gpu_frames_vs_brute(renderer, oracle, S, sc, what, pipelines=(0, 1), cache=
             renderer.set_option("path_pipeline", 0)
 
 
-def _gpu_rays_vs_brute(pkg, renderer, oracle, S, sc, rng, what):
-    """camera rays and rays from surfaces through trace_rays / occluded and their device forms"""
+def _gpu_rays_vs_brute(pkg, renderer, oracle, S, sc, rng, what, cache=None):
+    """camera rays and rays from surfaces through trace_rays / occluded and their device forms; the same rays through shade_rays
+    and path_rays, and the camera's 48 x 48 frame through camera_rays, shade_rays, path_rays and frame_guides (its brute-force
+    frames in modes 100 and 200 come from, and go to, the cache _gpu_frames_vs_brute fills)"""
     import torch
+    cache = {} if cache is None else cache
     for cname, cam in sc["cameras"].items():
         w, h = 48, 48
         ref = _render(oracle, S, cam, 3, w, h, brute=True)
@@ -367,6 +371,15 @@ def _gpu_rays_vs_brute(pkg, renderer, oracle, S, sc, rng, what):
             assert np.array_equal(_bits(res["t"]), _bits(bf["t"])), tag + ": trace_rays t"
             m = int(np.count_nonzero(o != occ))
             assert m == 0, "%s: occluded differs from brute force on %d of %d rays" % (tag, m, n)
+        frames = {3: ref}
+        for mode in (100, 200):
+            if (cname, mode) not in cache:
+                cache[(cname, mode)] = _render(oracle, S, cam, mode, w, h, brute=True)
+            frames[mode] = cache[(cname, mode)]
+        tag = "%s %s camera" % (what, cname)
+        renderer.set_camera(cam["position"], cam["matrix"])
+        sq.frame_records_equal_frames(renderer, frames, w, h, (1, 2, 77), tag, scene=sc)
+        sq.arbitrary_records_equal_trace(renderer, rays, bf, tag)
 
 
 def _upload(renderer, sc, tree, dynamic=False):
@@ -408,9 +421,10 @@ def test_gpu_ray_queries_equal_brute_force(pkg, oracle, scenes, renderer, gpu_st
     sc = _scene_of(scenes, kind, off, r)
     S = _oracle_scene(oracle, sc)
     rng = np.random.default_rng(int(off) + 11)
+    cache = {}
     for tree in TREES:
         _upload(renderer, sc, tree)
-        _gpu_rays_vs_brute(pkg, renderer, oracle, S, sc, rng, "%s-%g %s" % (kind, off, tree))
+        _gpu_rays_vs_brute(pkg, renderer, oracle, S, sc, rng, "%s-%g %s" % (kind, off, tree), cache=cache)
 
 
 @pytest.mark.gpu
@@ -436,4 +450,4 @@ def test_gpu_translated_dynamic_mesh_equals_brute_force(pkg, oracle, scenes, ren
         if step == "rebuild":
             renderer.rebuild()
         _gpu_frames_vs_brute(renderer, oracle, S, moved, "dynamic %s builder %d" % (step, builder), cache=cache)
-        _gpu_rays_vs_brute(pkg, renderer, oracle, S, moved, rng, "dynamic %s builder %d" % (step, builder))
+        _gpu_rays_vs_brute(pkg, renderer, oracle, S, moved, rng, "dynamic %s builder %d" % (step, builder), cache=cache)
