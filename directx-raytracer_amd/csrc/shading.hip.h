@@ -235,7 +235,7 @@ __device__ __forceinline__ F3 directLight(const RenderParams& p, const float4* n
         if (lt.cosv > 0.0f) {
             const Ray sr = makeRay(Po, lt.Ld);
             if (COUNT) cntShadow++;
-            const bool occluded = traceAny<COUNT, L, true>(nodes, tris, p.n_nodes, sr, 0.0f, lt.dist, stack, static_cast<int>(p.tune_inner_min_any), iters, cntNodes, cntTris, p.planes);
+            const bool occluded = traceAny<COUNT, L, true, true>(nodes, tris, p.n_nodes, sr, 0.0f, lt.dist, stack, static_cast<int>(p.tune_inner_min_any), iters, cntNodes, cntTris, p.planes);
             if (!occluded) addLight<PHONG>(p, Lt, lt, N, albedo, view, rgb);
         }
     }

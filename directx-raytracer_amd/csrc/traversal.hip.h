@@ -194,9 +194,16 @@ __device__ __forceinline__ bool triTest(const Ray& r, const float4 a, const floa
 }
 
 // Per-lane traversal stack.  The first `cap` entries live in LDS (entry e of lane l at dword e*64+l: conflict free); cap
-// is chosen so that the 28 wavefronts per CU the register budget allows fit its 160 KB (16 entries = 4 KB per wavefront).  No ray of the test scenes ever holds more than 15
-// entries while the trees are 24..26 deep, but the builder allows depth 32, so deeper entries spill to a per-lane slice
-// of a global arena that is never touched otherwise: any tree stays correct with the small LDS footprint.
+// is chosen so that the 28 wavefronts per CU the register budget allows fit its 160 KB (16 entries = 4 KB per wavefront).  No ray
+// of the bench scenes ever holds more than 15 entries while the trees are 24..26 deep, but the builder allows depth 32, so deeper
+// entries spill to a per-lane slice of a global arena that is never touched otherwise: any tree stays correct with the small LDS
+// footprint.  Every push and every pop decides per lane where its entry is.
+// pop() is `lds : spill` as one load: the compiler selects between the two 64-bit addresses (nine vector instructions, most
+// of them half rate) and loads through the flat path, so an entry in LDS still goes through the vector-memory address unit.
+// popLds() is the same pop as two loads under a branch, the LDS one through an LDS pointer: v_add, v_cmp, v_lshl_add_u32 and
+// ds_read_b32 plus four scalar instructions for the lanes in the LDS part, and the global load of the others is jumped over
+// when there are none.  Same entry, same order: only the instructions differ.  The render kernel's traversals take it
+// (LPOP of traceClosest / traceAny); what DESIGN section 5 measured for it and for the unchecked stack it replaced is there.
 struct Stack {
     int* lds;    // s_stack + lane
     int* spill;  // arena slice of this lane: kStackEntries - cap entries are ever needed, kStackEntries reserved
@@ -250,6 +257,19 @@ struct Stack {
     {
         sp--;
         return sp < cap ? lds[sp * 64] : spill[sp - cap];
+    }
+    __device__ __forceinline__ int popLds()
+    {
+        sp--;
+        int v;
+        if (sp < cap) v = ((const __attribute__((address_space(3))) int*)lds)[sp * 64]; // two address spaces: never merged into one flat load
+        else v = spill[sp - cap];
+        return v;
+    }
+    template <bool LPOP> __device__ __forceinline__ int popAs()
+    {
+        if constexpr (LPOP) return popLds();
+        else return pop();
     }
 };
 
@@ -425,7 +445,8 @@ struct LayLegacy {
     // 0.368 vs 0.361: the network runs under the early fetch, off the step's dependent chain, so removing it frees issue
     // slots nobody was waiting for.)
     // (N: Node, or NodeU on the scalar path with the plane table)
-    template <bool COUNT, int OCT, bool EARLY, class N>
+    // (LPOP: the pop is Stack::popLds)
+    template <bool COUNT, int OCT, bool EARLY, bool LPOP = false, class N>
     static __device__ __forceinline__ void closestStep(const N& nd, const Ray& r, float tmin, float tcull, Stack& stack,
                                                        int& cur, uint32_t& cntNodes, const float4* __restrict__ nodes, Node& ndNext)
     {
@@ -440,7 +461,7 @@ struct LayLegacy {
             key[k] = hit[k] ? ((__float_as_uint(tn[k]) & 0x7FFFFFFCu) | static_cast<uint32_t>(k)) : 0xFFFFFFFFu;
         const uint32_t nearest = min(min(key[0], key[1]), min(key[2], key[3])); // = key[0] after the network
         const bool any = nearest != 0xFFFFFFFFu;
-        cur = any ? pick4(refs, nearest & 3u) : (stack.sp == 0 ? kDone : stack.pop()); // a lane pops or pushes, never both
+        cur = any ? pick4(refs, nearest & 3u) : (stack.sp == 0 ? kDone : stack.template popAs<LPOP>()); // a lane pops or pushes, never both
         if (EARLY) {
             if (cur >= 0) ndNext = load(nodes, cur);
         }
@@ -455,7 +476,7 @@ struct LayLegacy {
     }
 
     // any hit: order independent, children taken in slot order
-    template <bool COUNT, int OCT, bool EARLY, class N>
+    template <bool COUNT, int OCT, bool EARLY, bool LPOP = false, class N>
     static __device__ __forceinline__ void anyStep(const N& nd, const Ray& r, float tmin, float tcull, Stack& stack,
                                                    int& cur, uint32_t& cntNodes, const float4* __restrict__ nodes, Node& ndNext)
     {
@@ -465,7 +486,7 @@ struct LayLegacy {
         bool hit[4];
         slab<OCT>(nd, r, tmin, tcull, tn, hit);
         const bool h0 = hit[0], h1 = hit[1], h2 = hit[2], h3 = hit[3];
-        cur = h0 ? refs.x : (h1 ? refs.y : (h2 ? refs.z : (h3 ? refs.w : (stack.sp == 0 ? kDone : stack.pop()))));
+        cur = h0 ? refs.x : (h1 ? refs.y : (h2 ? refs.z : (h3 ? refs.w : (stack.sp == 0 ? kDone : stack.template popAs<LPOP>()))));
         if (EARLY) {
             if (cur >= 0) ndNext = load(nodes, cur);
         }
@@ -491,16 +512,16 @@ __device__ __forceinline__ auto loadUniformStep(const float4* nodes, const float
 // wave-uniform, so the loads become s_load) instead of 64 identical per-lane vector fetches; each lane still runs its own
 // slab tests, ordering and pushes, so results and counters are exactly those of the per-lane loop that follows.
 #if UNIFORM_DESCENT
-#define CRT_UNIFORM_DESCENT(STEP)                                                                                              \
+#define CRT_UNIFORM_DESCENT(STEP, LPOP)                                                                                         \
     for (;;) {                                                                                                                 \
         const int c0 = __builtin_amdgcn_readfirstlane(cur);                                                                    \
         if (!L::inner(c0) || __ballot(cur != c0) != 0ull) break;                                                               \
         typename L::Node ndUnused;                                                                                             \
         CRT_UNIFORM_STEP_STAT(STEP)                                                                                            \
-        L::template STEP<COUNT, OCT, false>(loadUniformStep<L, OCT, DEC>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndUnused); \
+        L::template STEP<COUNT, OCT, false, LPOP>(loadUniformStep<L, OCT, DEC>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndUnused); \
     }
 #else
-#define CRT_UNIFORM_DESCENT(STEP)
+#define CRT_UNIFORM_DESCENT(STEP, LPOP)
 #endif
 #define CRT_STEP_KIND_closestStep 0
 #define CRT_STEP_KIND_anyStep 1
@@ -527,42 +548,43 @@ __device__ __forceinline__ auto loadUniformStep(const float4* nodes, const float
 // CRT_NODE_STEPS: the NODE_STEPS node steps of one scheduling decision.  The first fetches its record here; with
 // EARLY_FETCH every step but the last requests the next record itself (see closestStep), per lane.
 #if UNIFORM_STEP
-#define CRT_FIRST_NODE_STEP(STEP, EARLY)                                                                                       \
+#define CRT_FIRST_NODE_STEP(STEP, EARLY, LPOP)                                                                                  \
     {                                                                                                                          \
         const int c0 = __builtin_amdgcn_readfirstlane(cur);                                                                    \
         if (__ballot(cur != c0) == 0ull) {                                                                                     \
             CRT_UNIFORM_STEP_STAT(STEP)                                                                                        \
-            L::template STEP<COUNT, OCT, EARLY>(loadUniformStep<L, OCT, DEC>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
+            L::template STEP<COUNT, OCT, EARLY, LPOP>(loadUniformStep<L, OCT, DEC>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
         } else {                                                                                                               \
             CRT_DIV_STATS_NODE                                                                                                 \
             CRT_STEP_STAT(wsD, STEP)                                                                                           \
-            L::template STEP<COUNT, OCT, EARLY>(L::load(nodes, cur), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);      \
+            L::template STEP<COUNT, OCT, EARLY, LPOP>(L::load(nodes, cur), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);      \
         }                                                                                                                      \
     }
 #else
-#define CRT_FIRST_NODE_STEP(STEP, EARLY) L::template STEP<COUNT, OCT, EARLY>(L::load(nodes, cur), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);
+#define CRT_FIRST_NODE_STEP(STEP, EARLY, LPOP) L::template STEP<COUNT, OCT, EARLY, LPOP>(L::load(nodes, cur), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);
 #endif
 #if EARLY_FETCH
-#define CRT_NODE_STEPS(STEP)                                                                                                   \
+#define CRT_NODE_STEPS_AS(STEP, LPOP)                                                                                          \
     if (L::inner(cur)) {                                                                                                       \
         typename L::Node ndNext;                                                                                               \
-        CRT_FIRST_NODE_STEP(STEP, (NODE_STEPS > 1))                                                                            \
+        CRT_FIRST_NODE_STEP(STEP, (NODE_STEPS > 1), LPOP)                                                                      \
         _Pragma("unroll") for (int rep = 1; rep < NODE_STEPS; rep++) {                                                         \
             if (L::inner(cur)) {                                                                                               \
                 CRT_STEP_STAT(wsF, STEP)                                                                                       \
                 CRT_AGREE_STAT(STEP)                                                                                           \
                 const typename L::Node ndCur = ndNext;                                                                         \
-                if (rep + 1 < NODE_STEPS) L::template STEP<COUNT, OCT, true>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);   \
-                else L::template STEP<COUNT, OCT, false>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);           \
+                if (rep + 1 < NODE_STEPS) L::template STEP<COUNT, OCT, true, LPOP>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
+                else L::template STEP<COUNT, OCT, false, LPOP>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);     \
             }                                                                                                                  \
         }                                                                                                                      \
     }
 #else
-#define CRT_NODE_STEPS(STEP)                                                                                                   \
+#define CRT_NODE_STEPS_AS(STEP, LPOP)                                                                                          \
     _Pragma("unroll") for (int rep = 0; rep < NODE_STEPS; rep++) {                                                             \
-        if (L::inner(cur)) { typename L::Node ndNext; CRT_FIRST_NODE_STEP(STEP, false) }                                        \
+        if (L::inner(cur)) { typename L::Node ndNext; CRT_FIRST_NODE_STEP(STEP, false, LPOP) }                                  \
     }
 #endif
+#define CRT_NODE_STEPS(STEP) CRT_NODE_STEPS_AS(STEP, false)
 
 __device__ __forceinline__ void loadTriUniform(const float4* T, float4& a, float4& b, float4& c)
 {
@@ -584,8 +606,8 @@ __device__ __forceinline__ void loadTriUniform(const float4* T, float4& a, float
 // caller, so a caller may retire finished rays and start new ones between two calls (streamClosest).  Returns false when
 // no lane has anything left to do.
 // DEC / planes: scalar-path steps read the decoded plane table (kPlaneStride floats per node, render_kernels.h) -- the render kernel's
-// traversals; the others keep the default (no table).
-template <bool COUNT, class L, int OCT, bool DEC = false>
+// traversals; the others keep the default (no table).  LPOP: pops are Stack::popLds -- likewise.
+template <bool COUNT, class L, int OCT, bool DEC = false, bool LPOP = false>
 __device__ __forceinline__ bool closestIteration(const float4* __restrict__ nodes, const float4* __restrict__ tris, const Ray& r, float tmin,
                                                  float& tcull, Stack& stack, int innerMin, Hit& h, int& cur, uint32_t& iters,
                                                  uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
@@ -602,7 +624,7 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
 #if CRT_PROF
         const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
 #endif
-        CRT_NODE_STEPS(closestStep) // several node steps per scheduling decision: fewer ballots/branches
+        CRT_NODE_STEPS_AS(closestStep, LPOP) // several node steps per scheduling decision: fewer ballots/branches
 #if CRT_PROF
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         stack.tNode += __builtin_amdgcn_s_memtime() - ts0; stack.itNode++; stack.lanesNode += __popcll(innerMask);
@@ -683,7 +705,7 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
             }
 #endif
         }
-        cur = stack.sp == 0 ? L::kDone : stack.pop();
+        cur = stack.sp == 0 ? L::kDone : stack.template popAs<LPOP>();
     }
 #if CRT_PROF
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -692,7 +714,7 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
     return true;
 }
 
-template <bool COUNT, class L, int OCT, bool DEC>
+template <bool COUNT, class L, int OCT, bool DEC, bool LPOP>
 __device__ __forceinline__ void traceClosestOct(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                              uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
                                              Hit& h, uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes)
@@ -701,12 +723,12 @@ __device__ __forceinline__ void traceClosestOct(const float4* __restrict__ nodes
     int cur = n_nodes ? L::kRoot : L::kDone;
     stack.sp = 0;
     float tcull = tmax * kCullPad; // boxes are culled against best_t * pad; changes only when a hit is accepted
-    CRT_UNIFORM_DESCENT(closestStep)
-    while (closestIteration<COUNT, L, OCT, DEC>(nodes, tris, r, tmin, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris, planes)) {}
+    CRT_UNIFORM_DESCENT(closestStep, LPOP)
+    while (closestIteration<COUNT, L, OCT, DEC, LPOP>(nodes, tris, r, tmin, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris, planes)) {}
 }
 
 // One scheduling decision of the any-hit traversal (see closestIteration); tmax / tcull / occluded are per-lane state of the caller
-template <bool COUNT, class L, int OCT, bool DEC = false>
+template <bool COUNT, class L, int OCT, bool DEC = false, bool LPOP = false>
 __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, const float4* __restrict__ tris, const Ray& r, float tmin, float tmax,
                                              float tcull, Stack& stack, int innerMin, bool& occluded, int& cur, uint32_t& iters,
                                              uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
@@ -723,7 +745,7 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
 #if CRT_PROF
         const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
 #endif
-        CRT_NODE_STEPS(anyStep) // several node steps per scheduling decision: fewer ballots/branches
+        CRT_NODE_STEPS_AS(anyStep, LPOP) // several node steps per scheduling decision: fewer ballots/branches
 #if CRT_PROF
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         stack.tNode += __builtin_amdgcn_s_memtime() - ts0; stack.itNode++; stack.lanesNode += __popcll(innerMask);
@@ -764,7 +786,7 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
                 break;
             }
         }
-        cur = (occluded | (stack.sp == 0)) ? L::kDone : stack.pop();
+        cur = (occluded | (stack.sp == 0)) ? L::kDone : stack.template popAs<LPOP>();
     }
 #if CRT_PROF
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -773,7 +795,7 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
     return true;
 }
 
-template <bool COUNT, class L, int OCT, bool DEC>
+template <bool COUNT, class L, int OCT, bool DEC, bool LPOP>
 __device__ __forceinline__ bool traceAnyOct(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                          uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
                                          uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes)
@@ -782,8 +804,8 @@ __device__ __forceinline__ bool traceAnyOct(const float4* __restrict__ nodes, co
     int cur = n_nodes ? L::kRoot : L::kDone;
     stack.sp = 0;
     const float tcull = tmax * kCullPad;
-    CRT_UNIFORM_DESCENT(anyStep)
-    while (anyIteration<COUNT, L, OCT, DEC>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris, planes)) {}
+    CRT_UNIFORM_DESCENT(anyStep, LPOP)
+    while (anyIteration<COUNT, L, OCT, DEC, LPOP>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris, planes)) {}
     return occluded;
 }
 
@@ -794,7 +816,7 @@ __device__ __forceinline__ uint32_t octantOf(const Ray& r)
     return (__float_as_uint(r.d.x) >> 31) | ((__float_as_uint(r.d.y) >> 31) << 1) | ((__float_as_uint(r.d.z) >> 31) << 2);
 }
 
-template <bool COUNT, class L, bool DEC = false>
+template <bool COUNT, class L, bool DEC = false, bool LPOP = false>
 __device__ __forceinline__ void traceClosest(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                              uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
                                              Hit& h, uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
@@ -804,16 +826,16 @@ __device__ __forceinline__ void traceClosest(const float4* __restrict__ nodes, c
     const uint32_t o0 = __builtin_amdgcn_readfirstlane(oct);
     if (__ballot(oct != o0) == 0ull) {
         switch (o0) {
-#define CRT_CASE(k) case k: traceClosestOct<COUNT, L, k, DEC>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes); return;
+#define CRT_CASE(k) case k: traceClosestOct<COUNT, L, k, DEC, LPOP>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes); return;
             CRT_CASE(0) CRT_CASE(1) CRT_CASE(2) CRT_CASE(3) CRT_CASE(4) CRT_CASE(5) CRT_CASE(6) CRT_CASE(7)
 #undef CRT_CASE
         }
     }
 #endif
-    traceClosestOct<COUNT, L, 8, DEC>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes);
+    traceClosestOct<COUNT, L, 8, DEC, LPOP>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes);
 }
 
-template <bool COUNT, class L, bool DEC = false>
+template <bool COUNT, class L, bool DEC = false, bool LPOP = false>
 __device__ __forceinline__ bool traceAny(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                          uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
                                          uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
@@ -823,13 +845,13 @@ __device__ __forceinline__ bool traceAny(const float4* __restrict__ nodes, const
     const uint32_t o0 = __builtin_amdgcn_readfirstlane(oct);
     if (__ballot(oct != o0) == 0ull) {
         switch (o0) {
-#define CRT_CASE(k) case k: return traceAnyOct<COUNT, L, k, DEC>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
+#define CRT_CASE(k) case k: return traceAnyOct<COUNT, L, k, DEC, LPOP>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
             CRT_CASE(0) CRT_CASE(1) CRT_CASE(2) CRT_CASE(3) CRT_CASE(4) CRT_CASE(5) CRT_CASE(6) CRT_CASE(7)
 #undef CRT_CASE
         }
     }
 #endif
-    return traceAnyOct<COUNT, L, 8, DEC>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
+    return traceAnyOct<COUNT, L, 8, DEC, LPOP>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
 }
 
 } // namespace

@@ -38,7 +38,8 @@ def main():
                 ms = [r.render_frame_device(W, H, frame.data_ptr(), stats=True)["kernel_ms"] for _ in range(a.frames)]
                 if rnd: res[(path, v)].append(statistics.median(ms))
     for (path, v) in res:
-        print("%-32s %-18s median %.4f ms  min %.4f ms" % (os.path.basename(path), "" if v is None else "%s=%d" % (oname, v), statistics.median(res[(path, v)]), min(res[(path, v)])), flush=True)
+        # spread: largest minus smallest of the rounds' medians -- what a difference between two libraries has to exceed
+        print("%-32s %-18s median %.4f ms  min %.4f ms  spread %.4f ms over %d rounds" % (os.path.basename(path), "" if v is None else "%s=%d" % (oname, v), statistics.median(res[(path, v)]), min(res[(path, v)]), max(res[(path, v)]) - min(res[(path, v)]), len(res[(path, v)])), flush=True)
     # each context is destroyed by the library that made it (pkg._lib is global: left to __del__ at exit, every context would go
     # to the last library's crt_destroy, which reads another build's context layout)
     for path, L, r in rs:
