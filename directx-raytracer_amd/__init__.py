@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "crt_shade_rays_device", "crt_shade_rays",
     "crt_path_rays_device", "crt_path_rays",
     "crt_camera_rays_device", "crt_camera_rays", "crt_frame_guides_device", "crt_frame_guides", "crt_denoise_device", "crt_denoise",
+    "crt_temporal_accumulate_device", "crt_temporal_accumulate",
 ]
 
 
@@ -102,6 +103,15 @@ class DenoiseParams(C.Structure):
 
     def __init__(self, iterations=5, sigma_color=4.0, sigma_normal=0.3, sigma_depth=0.05, demodulate=1):
         super().__init__(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_depth), int(demodulate))
+
+
+class TemporalParams(C.Structure):
+    """crt_temporal_params; the defaults are the header's"""
+    _fields_ = [("alpha", C.c_float), ("depth_tolerance", C.c_float), ("normal_threshold", C.c_float), ("max_history", C.c_uint32),
+                ("demodulate", C.c_uint32)]
+
+    def __init__(self, alpha=0.1, depth_tolerance=0.01, normal_threshold=0.9, max_history=64, demodulate=1):
+        super().__init__(float(alpha), float(depth_tolerance), float(normal_threshold), int(max_history), int(demodulate))
 
 
 def build(force=False):
@@ -244,6 +254,8 @@ def lib():
         "crt_frame_guides": (C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
         "crt_denoise_device": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
         "crt_denoise": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "crt_temporal_accumulate_device": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "crt_temporal_accumulate": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     assert set(sig) == set(ABI_SYMBOLS)
     for name, (res, args) in sig.items():
@@ -525,6 +537,55 @@ class Scene:
         self._ok(lib().crt_scene_camera_pan_around_target(self.h, deg, t.ctypes.data), "panAroundTarget")
 
 
+class TemporalHistory:
+    """Frame-to-frame state of Renderer.temporal_accumulate_device: two torch CUDA history buffers of (h, w, 8) float32 that swap
+    every push, and the camera of the last push.  The renderer's context keeps none of it."""
+
+    def __init__(self, renderer, width, height, **params):
+        import torch
+        self.renderer, self.w, self.h, self.params = renderer, int(width), int(height), params
+        self.hist = [torch.zeros((self.h, self.w, 8), dtype=torch.float32, device="cuda") for _ in range(2)]
+        self.at = 0          # hist[at] holds the previous frame's records
+        self.camera = None   # the camera of the previous push; None = no history
+
+    def reset(self):
+        """drop the history (after geometry moved, or a cut): the next push starts over"""
+        self.camera = None
+
+    def push(self, rgb, normal, albedo, t, camera=None):
+        """rgb, normal, albedo (h, w, 3) and t (h, w): numpy arrays or torch CUDA tensors of this frame; camera: 12 floats
+        {pos, rot}, None = the one last given to the renderer's set_camera / set_camera_from.  Returns the accumulated image, of
+        the kind rgb is (numpy in, numpy out), and swaps the buffers."""
+        import torch
+        if camera is None:
+            camera = getattr(self.renderer, "camera", None)
+            if camera is None:
+                raise ValueError("no camera: pass camera= or call the renderer's set_camera first")
+        cam = _f32(camera, 12).copy()
+        shapes = ((self.h, self.w, 3), (self.h, self.w, 3), (self.h, self.w, 3), (self.h, self.w))
+        dev = []
+        for a, shape in zip((rgb, normal, albedo, t), shapes):
+            d = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+            if tuple(d.shape) != shape or d.dtype != torch.float32 or not d.is_cuda:
+                raise ValueError("expected float32 buffers of shape %r" % (shape,))
+            dev.append(d.contiguous())
+        out = torch.empty((self.h, self.w, 3), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()  # torch fills its tensors on its own stream
+        have = self.camera is not None
+        self.renderer.temporal_accumulate_device(self.w, self.h, cam, self.camera if have else cam, dev[0].data_ptr(), dev[1].data_ptr(),
+                                                 dev[2].data_ptr(), dev[3].data_ptr(), self.hist[self.at].data_ptr() if have else None,
+                                                 self.hist[self.at ^ 1].data_ptr(), out.data_ptr(), **self.params)
+        self.renderer.synchronize()
+        self.at ^= 1
+        self.camera = cam
+        return out if isinstance(rgb, torch.Tensor) else out.cpu().numpy()
+
+    @property
+    def records(self):
+        """the history records of the last push, (h, w, 8) torch CUDA tensor {c.rgb, len, n.xyz, t}"""
+        return self.hist[self.at]
+
+
 def _mesh_views(meshes, keep):
     arr = (MeshView * max(1, len(meshes)))()
     for i, m in enumerate(meshes):
@@ -758,9 +819,11 @@ class Renderer:
     def set_camera(self, pos, rot):
         p, r = _f32(pos, 3), _f32(rot, 9)
         self._ok(lib().crt_set_camera(self.h, p.ctypes.data, r.ctypes.data), "crt_set_camera")
+        self.camera = np.concatenate([p.reshape(3), r.reshape(9)])  # the 12 floats of the batch entry points (TemporalHistory.push)
 
     def set_camera_from(self, scene):
         self._ok(lib().crt_set_camera_from(self.h, scene.h), "crt_set_camera_from")
+        self.camera = np.concatenate(scene.camera())
 
     def change_shading_mode(self, mode):
         self._ok(lib().crt_set_shading_mode(self.h, int(mode)), "crt_set_shading_mode")
@@ -967,6 +1030,46 @@ class Renderer:
         prm = DenoiseParams(**params)
         self._ok(lib().crt_denoise_device(self.h, int(w), int(h), d_rgb, d_normal, d_albedo, d_t, d_out, C.byref(prm),
                                           C.byref(st) if stats else None), "crt_denoise_device")
+        return st.as_dict() if stats else None
+
+    # ---- temporal reprojection (include/crt_hip.h): cameras are 12 floats {pos[3], rot3x3 row-major[9]}
+    def temporal_accumulate(self, cam_cur, cam_prev, rgb, normal, albedo, t, hist_prev=None, want_out=True, **params):
+        """one frame blended with the reprojected history (host buffers, synchronous): rgb, normal, albedo (h, w, 3) and t (h, w)
+        float32 of this frame (albedo may be None with demodulate=0), hist_prev None or the (h, w, 8) float32 records an earlier
+        call returned, taken with camera cam_prev.  params: the fields of TemporalParams.  Returns (hist_next, out): the new
+        records and the accumulated (h, w, 3) image (None when not want_out)."""
+        t = np.ascontiguousarray(t, dtype=np.float32)
+        if t.ndim != 2:
+            raise ValueError("t must be (h, w)")
+        h, w = t.shape
+        bufs = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (rgb, normal, albedo)]
+        for a in bufs:
+            if a is not None and a.shape != (h, w, 3):
+                raise ValueError("rgb, normal and albedo must be (h, w, 3) where t is (h, w)")
+        hp = None if hist_prev is None else np.ascontiguousarray(hist_prev, dtype=np.float32)
+        if hp is not None and hp.shape != (h, w, 8):
+            raise ValueError("hist_prev must be (h, w, 8)")
+        cc, cp = _f32(cam_cur, 12), _f32(cam_prev, 12)
+        hist = np.zeros((h, w, 8), dtype=np.float32)
+        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+
+        def p(a):
+            return None if a is None else a.ctypes.data
+        prm = TemporalParams(**params)
+        self._ok(lib().crt_temporal_accumulate(self.h, w, h, cc.ctypes.data, cp.ctypes.data, p(bufs[0]), p(bufs[1]), p(bufs[2]), t.ctypes.data,
+                                               p(hp), hist.ctypes.data, p(out), C.byref(prm), None), "crt_temporal_accumulate")
+        return hist, out
+
+    def temporal_accumulate_device(self, w, h, cam_cur, cam_prev, d_rgb, d_normal, d_albedo, d_t, d_hist_prev, d_hist_next, d_out=None,
+                                   stats=False, **params):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); the cameras are host arrays of 12 floats; d_hist_prev None =
+        no history; d_out may equal d_rgb or be None; asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        cc, cp = _f32(cam_cur, 12), _f32(cam_prev, 12)
+        prm = TemporalParams(**params)
+        self._ok(lib().crt_temporal_accumulate_device(self.h, int(w), int(h), cc.ctypes.data, cp.ctypes.data, d_rgb, d_normal, d_albedo, d_t,
+                                                      d_hist_prev, d_hist_next, d_out, C.byref(prm), C.byref(st) if stats else None),
+                 "crt_temporal_accumulate_device")
         return st.as_dict() if stats else None
 
     # ---- point queries (include/crt_hip.h): records of 4 floats {x, y, z, rmax}, see make_points

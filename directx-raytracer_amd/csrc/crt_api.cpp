@@ -2292,6 +2292,111 @@ int crt_denoise(crt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const floa
     return CRT_OK;
 }
 
+namespace {
+
+// ---- temporal reprojection (temporal_kernels.hip)
+const crt_temporal_params kTemporalDefaults = { 0.1f, 0.01f, 0.9f, 64u, 1u };
+
+int checkTemporal(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const void* rgb,
+                  const void* normal, const void* albedo, const void* t, const void* histNext, const crt_temporal_params& prm)
+{
+    if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
+    if (const int rc = checkFrameSize(c, what, w, h)) return rc;
+    if (!camCur || !camPrev) return fail(c, CRT_EINVAL, "%s: NULL camera", what);
+    if (!(prm.alpha >= 0.0f && prm.alpha <= 1.0f)) return fail(c, CRT_EINVAL, "%s: alpha = %g is outside [0, 1]", what, static_cast<double>(prm.alpha));
+    if (!(prm.depth_tolerance > 0.0f))
+        return fail(c, CRT_EINVAL, "%s: depth_tolerance = %g must be > 0", what, static_cast<double>(prm.depth_tolerance));
+    if (prm.normal_threshold != prm.normal_threshold) return fail(c, CRT_EINVAL, "%s: normal_threshold is NaN", what);
+    if (prm.max_history < 1u || prm.max_history > (1u << 24))
+        return fail(c, CRT_EINVAL, "%s: max_history = %u is outside 1..2^24", what, prm.max_history);
+    if (prm.demodulate > 1u) return fail(c, CRT_EINVAL, "%s: demodulate = %u is neither 0 nor 1", what, prm.demodulate);
+    if (!rgb || !normal || !t || !histNext) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
+    if (prm.demodulate && !albedo) return fail(c, CRT_EINVAL, "%s: NULL albedo while demodulating", what);
+    return CRT_OK;
+}
+
+int runTemporal(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const void* d_rgb,
+                const void* d_normal, const void* d_albedo, const void* d_t, const void* d_histPrev, void* d_histNext, void* d_out,
+                const crt_temporal_params& prm, crt_frame_stats* stats)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    crt::TemporalParams p;
+    std::memset(&p, 0, sizeof(p));
+    crt::copyBytes(p.posCur, camCur, sizeof(p.posCur));
+    crt::copyBytes(p.rotCur, camCur + 3, sizeof(p.rotCur));
+    crt::copyBytes(p.posPrev, camPrev, sizeof(p.posPrev));
+    crt::copyBytes(p.rotPrev, camPrev + 3, sizeof(p.rotPrev));
+    p.width = w;
+    p.height = h;
+    p.demodulate = prm.demodulate;
+    p.staticCamera = std::memcmp(camCur, camPrev, 12u * sizeof(float)) == 0 ? 1u : 0u;
+    p.alpha = prm.alpha;
+    p.depthTolerance = prm.depth_tolerance;
+    p.normalThreshold = prm.normal_threshold;
+    p.maxHistory = static_cast<float>(prm.max_history);
+    p.rgb = static_cast<const float*>(d_rgb);
+    p.normal = static_cast<const float*>(d_normal);
+    p.albedo = static_cast<const float*>(d_albedo);
+    p.t = static_cast<const float*>(d_t);
+    p.histPrev = d_histPrev;
+    p.histNext = d_histNext;
+    p.out = static_cast<float*>(d_out);
+    return runTimed(c, what, stats, [&] { return crt::launchTemporal(p, c->stream); });
+}
+
+} // namespace
+
+int crt_temporal_accumulate_device(crt_ctx* c, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const void* d_rgb,
+                                   const void* d_normal, const void* d_albedo, const void* d_t, const void* d_histPrev, void* d_histNext,
+                                   void* d_out, const crt_temporal_params* params, crt_frame_stats* stats)
+{
+    const char* what = "crt_temporal_accumulate_device";
+    const crt_temporal_params prm = params ? *params : kTemporalDefaults;
+    int rc = checkTemporal(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histNext, prm);
+    if (rc) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_out }, 4u)) != CRT_OK) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_histPrev, d_histNext }, 16u)) != CRT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext, d_out, prm, stats)) != CRT_OK)
+        return rc;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+// host buffers: staged through the context's query staging buffer {rgb | normal | albedo | t | hist_prev | hist_next}, the
+// colour accumulated in place; synchronous
+int crt_temporal_accumulate(crt_ctx* c, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const float* rgb,
+                            const float* normal, const float* albedo, const float* t, const float* histPrev, float* histNext, float* out,
+                            const crt_temporal_params* params, crt_frame_stats* stats)
+{
+    const char* what = "crt_temporal_accumulate";
+    const crt_temporal_params prm = params ? *params : kTemporalDefaults;
+    int rc = checkTemporal(c, what, w, h, camCur, camPrev, rgb, normal, albedo, t, histNext, prm);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t nn = static_cast<size_t>(w) * h;
+    const void* const host[5] = { rgb, normal, albedo, t, histPrev };
+    const size_t per[6] = { 12u, 12u, 12u, 4u, 32u, 32u };
+    size_t off[6], total = 0;
+    for (int i = 0; i < 6; i++) {
+        off[i] = total;
+        total += (i == 5 || host[i]) ? up256(nn * per[i]) : 0u;
+    }
+    if ((rc = reserveRayStage(c, total)) != CRT_OK) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
+    unsigned char* dev[6];
+    for (int i = 0; i < 6; i++) dev[i] = (i == 5 || host[i]) ? base + off[i] : nullptr;
+    for (int i = 0; i < 5; i++)
+        if (host[i]) HIP_TRY(c, hipMemcpyAsync(dev[i], host[i], nn * per[i], hipMemcpyHostToDevice, c->stream));
+    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], out ? dev[0] : nullptr, prm, stats)) != CRT_OK)
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(histNext, dev[5], nn * 32u, hipMemcpyDeviceToHost, c->stream));
+    if (out) HIP_TRY(c, hipMemcpyAsync(out, dev[0], nn * 12u, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
 int crt_closest_points_device(crt_ctx* c, uint32_t n, const void* d_points, void* d_dist, void* d_point, void* d_uv, void* d_inst,
                               void* d_prim, crt_frame_stats* stats)
 {

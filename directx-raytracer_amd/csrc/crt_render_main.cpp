@@ -45,6 +45,13 @@ static void usage()
                  "   [--denoise [--denoise-iterations N]]  the last frame's float colour goes through the edge-avoiding a-trous filter with\n"
                  "                                         its guide buffers (normal, albedo, t) before it is quantised and written; N = 1..8\n"
                  "                                         passes (default 5); not with --ranks\n"
+                 "   [--temporal [--temporal-alpha A]]     mode 200 only: every frame's float colour is blended with the history of the frames\n"
+                 "                                         before it, reprojected through the camera move (temporal reprojection), and each\n"
+                 "                                         frame written is the accumulated one; A = least weight of the new frame, 0..1\n"
+                 "                                         (default 0.1).  Frame f renders with seed SEED + f (--seed, default 1234): with one\n"
+                 "                                         fixed seed every frame would draw the same per-pixel random numbers and there would\n"
+                 "                                         be nothing to average.  --denoise then filters the accumulated last frame; not with\n"
+                 "                                         --ranks\n"
                  "   [--ranks N [--device-base D] [--id-file PATH]]   N processes / GPUs, RCCL gather per frame\n"
                  "   [--host-exchange [--same-device]]   with --ranks: tiles through shared host memory instead of RCCL; --same-device puts every\n"
                  "                                       rank on --device (a rehearsal of the multi-rank path on one GPU)\n");
@@ -60,6 +67,8 @@ struct Args {
     float orbit = 0.f, pitch = 0.f, forward = 0.f, right = 0.f, zoom = 0.f;
     bool count = false, png = false, hostExchange = false, sameDevice = false, denoise = false;
     int denoiseIterations = 5;
+    bool temporal = false;
+    float temporalAlpha = 0.1f;
     unsigned long long nonce = 0; // names the launch in the id file (set by the --ranks parent)
     std::map<int, uint32_t> modeAt;
 };
@@ -104,7 +113,7 @@ int runRank(const Args& a)
     if (a.accumulate >= 0) renderer.setAccumulation(static_cast<uint32_t>(a.accumulate));
     if (a.ranks > 0 && a.hostExchange) renderer.joinRanksThroughHostMemory(static_cast<uint32_t>(a.rank), static_cast<uint32_t>(a.ranks), a.nonce);
     else if (a.ranks > 0) renderer.joinRanks(static_cast<uint32_t>(a.rank), static_cast<uint32_t>(a.ranks), a.idFile, a.nonce);
-    renderer.setKeepFloatColour(a.denoise);
+    renderer.setKeepFloatColour(a.denoise || a.temporal);
     const bool talk = a.ranks <= 0 || a.rank == 0;
     std::vector<std::string> script;
     if (!a.pathFile.empty()) {
@@ -128,6 +137,7 @@ int runRank(const Args& a)
             mode = sw->second;
             renderer.changeShadingMode(mode);
         }
+        if (a.temporal) renderer.setOption("seed", (a.seed >= 0 ? a.seed : 1234) + f); // fresh random numbers every frame
         renderer.renderFrame();
         const crt_frame_stats& st = renderer.getLastFrameStats();
         sumMs += st.kernel_ms;
@@ -139,6 +149,11 @@ int runRank(const Args& a)
         if (a.count) std::printf(", nodes %llu, tris %llu, shadow rays %llu", (unsigned long long)st.nodes_visited,
                                  (unsigned long long)st.tris_tested, (unsigned long long)st.rays_shadow);
         std::printf("\n");
+        if (a.temporal) {
+            const crt_temporal_params prm = { a.temporalAlpha, 0.01f, 0.9f, 64u, 1u };
+            renderer.temporalFrame(&prm);
+            std::printf("frame %d: accumulated over the camera move, alpha %g\n", f, static_cast<double>(a.temporalAlpha));
+        }
         if (a.denoise && f == a.frames - 1) {
             crt_denoise_params prm = { static_cast<uint32_t>(a.denoiseIterations), 4.0f, 0.3f, 0.05f, 1u };
             renderer.denoiseFrame(&prm);
@@ -277,6 +292,8 @@ int main(int argc, char** argv)
         else if (s == "--png") a.png = true;
         else if (s == "--denoise") a.denoise = true;
         else if (s == "--denoise-iterations") a.denoiseIterations = std::atoi(next("--denoise-iterations"));
+        else if (s == "--temporal") a.temporal = true;
+        else if (s == "--temporal-alpha") a.temporalAlpha = static_cast<float>(std::atof(next("--temporal-alpha")));
         else if (s == "--host-exchange") a.hostExchange = true;
         else if (s == "--same-device") a.sameDevice = true;
         else if (s == "--ranks") a.ranks = std::atoi(next("--ranks"));
@@ -288,6 +305,7 @@ int main(int argc, char** argv)
     }
     if (a.frames < 1 || a.ranks < 0 || a.ranks > 64) { usage(); return 2; }
     if (a.denoise && (a.ranks > 0 || a.denoiseIterations < 1 || a.denoiseIterations > 8)) { usage(); return 2; }
+    if (a.temporal && (a.ranks > 0 || a.mode != 200u || !a.modeAt.empty() || !(a.temporalAlpha >= 0.0f && a.temporalAlpha <= 1.0f))) { usage(); return 2; }
     try {
         if (a.ranks > 0 && a.rank < 0) return launchRanks(a, argc, argv);
         if (a.ranks > 0 && (a.rank >= a.ranks || a.idFile.empty())) { usage(); return 2; }

@@ -292,6 +292,25 @@ struct DenoiseParams {
 constexpr size_t kDenoiseScratchPerPixel = 48;
 // pack, iterations - 1 passes, and the last pass fused with the multiply-back
 int launchDenoise(const DenoiseParams& p, ihipStream_t* stream);
+// temporal reprojection (temporal_kernels.hip; crt_temporal_accumulate*): one kernel, no scratch.  A history record is two
+// float4 per pixel, {c.rgb, len} and {n.xyz, t}
+struct TemporalParams {
+    float posCur[3], rotCur[9];   // the camera of this frame
+    float posPrev[3], rotPrev[9]; // the camera the history was taken with
+    uint32_t width, height;
+    uint32_t demodulate;          // 0 / 1
+    uint32_t staticCamera;        // 1: the two cameras are equal bitwise, a pixel's history is its own record
+    float alpha, depthTolerance, normalThreshold;
+    float maxHistory;             // 1 .. 2^24, exact as a float
+    const float* rgb;             // 3 floats per pixel
+    const float* normal;          // 3
+    const float* albedo;          // 3; may be null when demodulate == 0
+    const float* t;               // 1
+    const void* histPrev;         // null: no history
+    void* histNext;
+    float* out;                   // 3; may be rgb; may be null
+};
+int launchTemporal(const TemporalParams& p, ihipStream_t* stream);
 // exhaustive check of the triangle test's reciprocal (ray_kernels.hip rcpCheckKernel) into out[0..6] (device memory, zeroed
 // except out[6] = ~0 by the caller)
 int launchRcpCheck(unsigned long long* out, ihipStream_t* stream);

@@ -240,12 +240,51 @@ void Renderer::denoiseFrame(const crt_denoise_params* params)
     Guides g;
     frameGuides(g);
     denoise(floatColour.data(), g, floatColour.data(), params);
+    quantiseFloatColour();
+}
+
+void Renderer::quantiseFloatColour()
+{
+    const size_t n = static_cast<size_t>(width) * height;
     // the kernels' unorm8 (traversal.hip.h): saturate (NaN -> 0), x 255, + 0.5, truncate
     auto unorm8 = [](float c) { return static_cast<uint8_t>(std::fmin(std::fmax(c, 0.0f), 1.0f) * 255.0f + 0.5f); };
     for (size_t i = 0; i < n; i++) {
         for (int k = 0; k < 3; k++) frame[4 * i + k] = unorm8(floatColour[3 * i + k]);
         frame[4 * i + 3] = 255;
     }
+}
+
+void Renderer::temporalAccumulate(const float camCur[12], const float camPrev[12], const float* rgb, const Guides& guides, const float* histPrev,
+                                  float* histNext, float* out, const crt_temporal_params* params)
+{
+    if (!ctx) throw std::runtime_error("temporalAccumulate before prepareForRendering");
+    const size_t n = static_cast<size_t>(width) * height;
+    if (guides.normal.size() != 3 * n || guides.albedo.size() != 3 * n || guides.t.size() != n)
+        throw std::runtime_error("temporalAccumulate: the guides are not of the current frame size");
+    check(crt_temporal_accumulate(ctx, width, height, camCur, camPrev, rgb, guides.normal.data(), guides.albedo.data(), guides.t.data(), histPrev,
+                                  histNext, out, params, nullptr),
+          "crt_temporal_accumulate");
+}
+
+void Renderer::temporalFrame(const crt_temporal_params* params)
+{
+    const size_t n = static_cast<size_t>(width) * height;
+    if (floatColour.size() != 3 * n || frame.size() != 4 * n) throw std::runtime_error("temporalFrame: no frame with float colour (setKeepFloatColour, renderFrame)");
+    Guides g;
+    frameGuides(g);
+    float cam[12];
+    const auto pos = scene->getCamera().getPosition();
+    const auto rot = scene->getCamera().getRotationMatrix();
+    for (int k = 0; k < 3; k++) cam[k] = pos.data()[k];
+    for (int k = 0; k < 9; k++) cam[3 + k] = rot.data()[k];
+    const bool have = haveHistory && history[historyAt].size() == 8 * n;
+    history[historyAt ^ 1].resize(8 * n);
+    temporalAccumulate(cam, have ? historyCamera : cam, floatColour.data(), g, have ? history[historyAt].data() : nullptr, history[historyAt ^ 1].data(),
+                       floatColour.data(), params);
+    historyAt ^= 1;
+    haveHistory = true;
+    for (int k = 0; k < 12; k++) historyCamera[k] = cam[k];
+    quantiseFloatColour();
 }
 
 void Renderer::listHits(const float* rays, size_t n, std::vector<uint64_t>& offsets, std::vector<RayHit>& hits)

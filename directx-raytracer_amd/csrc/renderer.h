@@ -90,6 +90,16 @@ public:
     const std::vector<float>& getFloatColour() const { return floatColour; }
     // the last frame's float colour denoised with its guides and quantised into getFrame() with the frames' own UNORM rule
     void denoiseFrame(const crt_denoise_params* params = nullptr);
+    // temporal reprojection (crt_temporal_accumulate, synchronous) on width x height buffers: rgb with its guides, blended with
+    // the history records histPrev (8 floats per pixel; nullptr = no history) that were taken with camera camPrev, into
+    // histNext and out (may be rgb or nullptr).  Cameras: {pos[3], rot3x3 row-major[9]}; params = nullptr: the defaults
+    void temporalAccumulate(const float camCur[12], const float camPrev[12], const float* rgb, const Guides& guides, const float* histPrev,
+                            float* histNext, float* out, const crt_temporal_params* params = nullptr);
+    // the last frame's float colour accumulated with the history of the frames before it and quantised into getFrame().  The
+    // renderer owns the two history buffers and the previous camera; a change of the frame size drops the history, and so
+    // does resetTemporal() (after geometry moved, for instance)
+    void temporalFrame(const crt_temporal_params* params = nullptr);
+    void resetTemporal() { haveHistory = false; }
     // every crossing of every ray, ascending in t (crt_list_hits, synchronous): the hits of ray i are hits[offsets[i]] ..
     // hits[offsets[i + 1] - 1].  One offsets-only call learns the total, a second one fills the records.
     void listHits(const float* rays, size_t n, std::vector<uint64_t>& offsets, std::vector<RayHit>& hits);
@@ -124,6 +134,11 @@ private:
     std::vector<uint8_t> frame;
     std::vector<float> floatColour; // rgb_f32 of the last frame when keepFloatColour
     bool keepFloatColour = false;
+    std::vector<float> history[2]; // temporalFrame(): history[historyAt] is the previous frame's
+    int historyAt = 0;
+    bool haveHistory = false;
+    float historyCamera[12] = {};
+    void quantiseFloatColour(); // floatColour into frame with the frames' own UNORM rule
     void syncView(); // a pending mode change and the scene's camera, as renderFrame() applies them
     crt_frame_stats stats{};
     uint32_t rank = 0, nRanks = 0; // nRanks = 0: single-GPU path (crt_render_frame)

@@ -586,6 +586,69 @@ int crt_denoise_device(crt_ctx* ctx, uint32_t width, uint32_t height, const void
 int crt_denoise(crt_ctx* ctx, uint32_t width, uint32_t height, const float* rgb, const float* normal, const float* albedo,
                 const float* t, float* out, const crt_denoise_params* params, crt_frame_stats* stats);
 
+/* ---- temporal reprojection: a path-traced frame blended with the history of earlier frames, carried across camera moves (the
+ * first half of a production denoiser; crt_denoise is the second).  Buffers are row-major width x height: rgb, normal, albedo
+ * (3 floats per pixel) and t (1 float per pixel) of the current frame, the layouts of rgb_f32 and of crt_frame_guides.
+ * - A history record is 8 floats (32 B, 16-byte aligned) per pixel, row-major: {c.r, c.g, c.b, len, n.x, n.y, n.z, t}.  The
+ *   caller owns two such buffers and swaps them every frame: hist_next of one call is hist_prev of the next, together with
+ *   that call's cam_cur as cam_prev.  The context keeps no state (the design of crt_path_rays' sums).
+ * - Cameras: 12 floats {pos[3], rot3x3_rowmajor[9]}, the layout of the batch entry points; host pointers in both forms.  The
+ *   rotation is taken as orthonormal.
+ * - Pure image space: no scene is needed; the context's camera and mode are not read; accumulation sums, launch orders and
+ *   frame outputs are untouched.
+ * - The contract, per pixel p = (px, py).  All arithmetic is float32; fmaf appears only where written; / is correctly rounded;
+ *   dot(x, y) = fmaf(x.z, y.z, fmaf(x.y, y.y, x.x * y.x)); w and h are the sizes as floats; dir(rot, x, y) is the direction of
+ *   the frames' pixel-centre camera ray of pixel (x, y) (crt_camera_rays with CRT_SAMPLE_CENTRE) for that rotation.
+ *    1. Live: rgb, normal and t are finite, the normal has a non-zero component and t > 0; when demodulating, albedo is finite
+ *       too (crt_denoise's rule).
+ *    2. a = demodulate ? max(albedo, 1e-3) per channel : 1;  c = rgb / a.  albedo may be NULL only when demodulate == 0.
+ *    3. A pixel that is not live: out = rgb bit for bit, hist_next = {rgb bits, 0, n, t}.  A record whose len is not > 0, or
+ *       that holds any non-finite value, is never a tap.
+ *    4. d = dir(rot_cur, px, py);  P = o_cur + d * t per component (a product, then a sum).
+ *    5. v = P - o_prev;  pc = (dot(col0(R_prev), v), dot(col1(R_prev), v), dot(col2(R_prev), v)).
+ *    6. s = -pc.z; no history unless s > 0.
+ *         fx = ((pc.x / s) / (w / h) + 1) * 0.5 * w - 0.5        fy = (1 - pc.y / s) * 0.5 * h - 0.5
+ *       (evaluated left to right); no history unless fx > -1 && fx < w && fy > -1 && fy < h (a NaN fails).
+ *    7. When the 12 floats of cam_prev equal those of cam_cur bitwise: fx = px, fy = py exactly, steps 5 and 6 are skipped.
+ *    8. x0 = floor(fx), wx = fx - x0, likewise y0, wy.  Taps k = 0..3: (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1)
+ *       with b_k = (1 - wx)(1 - wy), wx (1 - wy), (1 - wx) wy, wx wy.
+ *    9. A tap q is valid when it is inside the image, its record of hist_prev is usable (3),
+ *       |dot(n_p, Pq - P)| <= depth_tolerance * t_p with Pq = o_prev + dir(rot_prev, qx, qy) * t_q, and
+ *       dot(n_p, n_q) >= normal_threshold.
+ *   10. Over the valid taps in the order k = 0..3, each sum starting at 0:  W = sum b_k,  S = sum b_k * c_q (a product, then a
+ *       sum),  SL = sum b_k * len_q.  No history unless W >= 0.01.  hc = S / W,  L = SL / W.
+ *   11. With history: a_t = max(alpha, 1 / (L + 1)), c_out = fmaf(a_t, c - hc, hc), len_out = min(L + 1, max_history).
+ *       Without (also: hist_prev == NULL): c_out = c, len_out = 1.
+ *   12. hist_next = {c_out, len_out, n_p, t_p};  out = c_out * a.
+ *   alpha = 0 is the plain running mean of up to max_history frames; with alpha > 0 the mean turns into an exponential one
+ *   once 1 / (len + 1) falls below alpha.  tests/temporal_reference.c restates these steps in C; the kernel equals it bit for bit.
+ * - Not covered: object motion.  After crt_update_vertices, crt_set_mesh_transform, crt_refit or crt_rebuild a surface that slid
+ *   within its own plane keeps stale history (the plane-distance and normal tests cannot see it): drop the history by passing
+ *   d_hist_prev = NULL.  Variance estimation and second moments (SVGF) are out of scope.
+ * - Aliasing: d_out may equal d_rgb; d_hist_next must not overlap d_hist_prev; no other two buffers may overlap.  d_out may be
+ *   NULL (only the history is wanted).
+ * - params == NULL means the defaults.  CRT_EINVAL for a NULL context or camera; a NULL rgb, normal, t or hist_next; a NULL
+ *   albedo while demodulating; width or height 0; width * height > 2^28; alpha outside [0, 1] or NaN; depth_tolerance not > 0;
+ *   normal_threshold NaN; max_history outside 1..2^24; demodulate other than 0 / 1; a misaligned device pointer (history:
+ *   16-byte, the rest: 4-byte).  A failed call launches nothing and writes nothing.
+ * - stats (may be NULL): kernel_ms, total_ms; every count is zero.
+ * - No scratch memory: one kernel, one thread per pixel, no atomics -- the same input gives the same bits.
+ * *_device: asynchronous on the context's stream unless stats != NULL.  Host variant: synchronous, staged. */
+typedef struct crt_temporal_params {
+    float alpha;            /* default 0.1: least weight of the new frame; 0 = plain running mean up to max_history */
+    float depth_tolerance;  /* default 0.01: plane distance allowed, relative to the centre pixel's t */
+    float normal_threshold; /* default 0.9: least dot(n_p, n_q) */
+    uint32_t max_history;   /* default 64, 1..2^24: cap of the history length */
+    uint32_t demodulate;    /* default 1: history holds rgb / max(albedo, 1e-3) */
+} crt_temporal_params;
+int crt_temporal_accumulate_device(crt_ctx* ctx, uint32_t width, uint32_t height, const float cam_cur[12], const float cam_prev[12],
+                                   const void* d_rgb, const void* d_normal, const void* d_albedo, const void* d_t,
+                                   const void* d_hist_prev /* NULL = no history */, void* d_hist_next, void* d_out /* may be NULL */,
+                                   const crt_temporal_params* params /* NULL = defaults */, crt_frame_stats* stats);
+int crt_temporal_accumulate(crt_ctx* ctx, uint32_t width, uint32_t height, const float cam_cur[12], const float cam_prev[12],
+                            const float* rgb, const float* normal, const float* albedo, const float* t, const float* hist_prev,
+                            float* hist_next, float* out, const crt_temporal_params* params, crt_frame_stats* stats);
+
 /* ---- point queries: closest surface point, hit counts, occupancy (no reference counterpart; the set of Open3D's
  * RaycastingScene: compute_closest_points / compute_distance / compute_signed_distance / compute_occupancy /
  * count_intersections).  SDF and occupancy training data, collision margins, snapping a point to the surface.
