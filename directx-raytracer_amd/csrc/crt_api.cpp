@@ -427,7 +427,7 @@ void fillParams(const crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_
     p.debug_skip_units = c->debugSkipUnits;
     // LDS part of the per-lane stack: 16 entries x 64 lanes x 4 B = 4 KB per wavefront, so that LDS never limits the 7
     // wavefronts per SIMD the kernel's register budget allows (12 .. 20 entries measured alike, 24 costs 4 %); no ray of the
-    // test scenes holds more than 15 entries, deeper ones (possible up to the builder's depth 32) spill to the arena
+    // bench scenes holds more than 15 entries, deeper ones (up to 3 * depth4 + 1: tests/test_deep_stacks.py) spill to the arena
     p.stack_entries = c->tuneStackEntries ? c->tuneStackEntries : 16u;
     p.n_batch = 1;
     p.units_per_frame = crt::renderUnitCount(p);

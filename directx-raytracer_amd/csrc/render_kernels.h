@@ -9,7 +9,7 @@ namespace crt {
 
 constexpr int kMaxBatch = 4;       // frames per launch (crt_render_tiles_batch_device)
 constexpr int kTile = 16;          // macro tile edge: one 256-thread workgroup = 4 wavefronts of 8x8 pixels
-constexpr int kStackEntries = 32;  // upper bound of the per-lane LDS traversal stack = kMaxDepth of the builder
+constexpr int kStackEntries = 32;  // largest LDS part of the per-lane stack (option "stack_entries"); a lane can hold 3 * depth4 + 1 entries, the rest spills
 // Decoded plane table: row i = float(q) of the 24 plane bytes of node i (bytes 24..47 of its record, in
 // order: qlo_x qhi_x qlo_y qhi_y qlo_z qhi_z, child k in byte k of each word), 8 floats of zero padding: 128 bytes per
 // node, so that a row is one s_load_dwordx16 + one s_load_dwordx8 on 64-byte boundaries.  Read by scalar-path node steps only.

@@ -206,7 +206,7 @@ __device__ __forceinline__ bool triTest(const Ray& r, const float4 a, const floa
 // (LPOP of traceClosest / traceAny); what DESIGN section 5 measured for it and for the unchecked stack it replaced is there.
 struct Stack {
     int* lds;    // s_stack + lane
-    int* spill;  // arena slice of this lane: kStackEntries - cap entries are ever needed, kStackEntries reserved
+    int* spill;  // arena slice of this lane: spill_stride = 3 * depth4 + 1 - cap entries (the host's bound, reached to within one entry)
     int cap;     // wave-uniform
     int sp;
 #if CRT_PROF // diagnostic build (tools/prof_build.sh): where a wavefront's cycles go, never compiled into the product

@@ -50,6 +50,8 @@
  * small math (explicit FMA placement is part of the contract)
  * ---------------------------------------------------------------------------------------------- */
 static _Thread_local int t_max_sp; /* deepest stack of the rays traced by this thread since last reset (analysis only) */
+static _Thread_local int t_cam_sp; /* the part of it that camera rays reached, while a secondary stack output is set */
+static uint32_t* g_cost_sp2;       /* oracle_set_stack_output2 */
 typedef struct { float x, y, z; } v3;
 
 static inline v3 v3_make(float x, float y, float z) { v3 r = { x, y, z }; return r; }
@@ -1421,12 +1423,15 @@ static v3 trace_path(const oracle_scene* s, const float rot[9], v3 cam, uint32_t
     ray_setup(&r, cam, ray_dir_j(rot, px, py, jx, jy, width, height));
     v3 L = v3_make(0.0f, 0.0f, 0.0f), thr = v3_make(1.0f, 1.0f, 1.0f);
     float tmin = RAY_TMIN;
+    const int sec_sp = t_max_sp; /* the secondary rays of the pixel's earlier samples */
+    if (g_cost_sp2) t_max_sp = 0;
     for (uint32_t bounce = 0;; bounce++) {
         hit_rec h;
         (*n_closest)++;
         if (brute) brute_closest(s, &r, tmin, RAY_TMAX, &h, c);
         else trace_closest(s, &r, tmin, RAY_TMAX, &h, c);
         if (bounce == 0 && first_hit) *first_hit = h;
+        if (bounce == 0 && g_cost_sp2) { if (t_max_sp > t_cam_sp) t_cam_sp = t_max_sp; t_max_sp = sec_sp; } /* what follows is secondary */
         if (!h.hit) {
             L = v3_make(fmaf(thr.x, miss.x, L.x), fmaf(thr.y, miss.y, L.y), fmaf(thr.z, miss.z, L.z));
             break;
@@ -1494,6 +1499,8 @@ void oracle_set_cost_outputs(uint32_t* pn, uint32_t* pt, uint32_t* sn, uint32_t*
     g_cost_pn = pn; g_cost_pt = pt; g_cost_sn = sn; g_cost_st = st;
 }
 void oracle_set_stack_output(uint32_t* max_sp) { g_cost_sp = max_sp; }
+/* per pixel, the deepest stack of its rays other than the camera rays (shadow and bounce rays); set together with the above */
+void oracle_set_stack_output2(uint32_t* secondary_sp) { g_cost_sp2 = secondary_sp; }
 
 int oracle_max_threads(void)
 {
@@ -1538,11 +1545,14 @@ int oracle_render(const oracle_scene* s, const float pos[3], const float rot[9],
                 double ax = 0.0, ay = 0.0, az = 0.0;
                 hit_rec h0;
                 memset(&h0, 0, sizeof(h0));
+                if (g_cost_sp) t_max_sp = t_cam_sp = 0;
                 for (uint32_t sm = 0; sm < g_path_spp; sm++) {
                     v3 Ls = trace_path(s, rot, o, px, py, width, height, (uint32_t)pix, sm, miss, brute_force, &c, &n_closest, &n_shadow,
                                        sm == 0 ? &h0 : NULL);
                     ax += (double)Ls.x; ay += (double)Ls.y; az += (double)Ls.z;
                 }
+                if (g_cost_sp2) g_cost_sp2[pix] = (uint32_t)t_max_sp;
+                if (g_cost_sp) g_cost_sp[pix] = (uint32_t)(t_max_sp > t_cam_sp ? t_max_sp : t_cam_sp); /* deepest stack of any ray of the pixel's paths */
                 const double n = (double)g_path_spp;
                 v3 col = v3_make((float)(ax / n), (float)(ay / n), (float)(az / n));
                 if (rgba8) {
@@ -1558,9 +1568,10 @@ int oracle_render(const oracle_scene* s, const float pos[3], const float rot[9],
             n_closest++;
             ray_setup(&r, o, ray_dir(rot, px, py, width, height));
             const trav_count c0 = c;
-            if (g_cost_sp) t_max_sp = 0;
+            if (g_cost_sp) t_max_sp = t_cam_sp = 0;
             if (brute_force) brute_closest(s, &r, RAY_TMIN, RAY_TMAX, &hr, &c);
             else trace_closest(s, &r, RAY_TMIN, RAY_TMAX, &hr, &c);
+            if (g_cost_sp2) { t_cam_sp = t_max_sp; t_max_sp = 0; }
             const trav_count c1 = c;
             v3 col = miss;
             uint32_t inst = ORACLE_MISS, prim = ORACLE_MISS;
@@ -1570,7 +1581,8 @@ int oracle_render(const oracle_scene* s, const float pos[3], const float rot[9],
                 if (mode >= ORACLE_MODE_LAMBERT) col = shade_lambert(s, &r, &hr, brute_force, &c, &n_shadow);
                 else col = shade_debug(mode, inst, prim, hr.t, hr.u, hr.v, r.o, r.d);
             }
-            if (g_cost_sp) g_cost_sp[pix] = (uint32_t)t_max_sp;
+            if (g_cost_sp2) g_cost_sp2[pix] = (uint32_t)t_max_sp;
+            if (g_cost_sp) g_cost_sp[pix] = (uint32_t)(t_max_sp > t_cam_sp ? t_max_sp : t_cam_sp);
             if (g_cost_pn) {
                 g_cost_pn[pix] = (uint32_t)(c1.nodes - c0.nodes); g_cost_pt[pix] = (uint32_t)(c1.tris - c0.tris);
                 g_cost_sn[pix] = (uint32_t)(c.nodes - c1.nodes); g_cost_st[pix] = (uint32_t)(c.tris - c1.tris);

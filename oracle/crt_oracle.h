@@ -160,6 +160,7 @@ void oracle_set_path_params(uint32_t spp, uint32_t max_bounces, uint32_t seed);
 /* Phong specular term of mode 100 (extension, see crt_hip.h "phong_ks"): ks in thousandths (0 = off, the default), integer exponent */
 void oracle_set_phong(uint32_t ks_permille, uint32_t exponent);
 void oracle_set_stack_output(uint32_t* max_sp);
+void oracle_set_stack_output2(uint32_t* secondary_sp); /* with the above: the deepest stack of the pixel's shadow and bounce rays */
 
 /* Small pure functions exposed for known-answer tests. */
 void oracle_ray_dir(const float rot[9], uint32_t px, uint32_t py, uint32_t w, uint32_t h, float out_dir[3]);

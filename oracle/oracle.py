@@ -133,6 +133,7 @@ def lib():
         L.oracle_set_phong.restype = None
         L.oracle_set_cost_outputs.argtypes = [C.c_void_p] * 4
         L.oracle_set_stack_output.argtypes = [C.c_void_p]
+        L.oracle_set_stack_output2.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
