@@ -36,7 +36,7 @@ SHADE_DTYPE = np.dtype([("n0", "f4", 3), ("n1", "f4", 3), ("n2", "f4", 3), ("mat
 # every symbol include/crt_hip.h declares (tests/test_abi.py checks the library exports all of them)
 ABI_SYMBOLS = [
     "crt_abi_version", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_textures", "crt_bvh_export_uv", "crt_set_camera",
-    "crt_set_shading_mode", "crt_set_miss_color", "crt_set_counting", "crt_set_option", "crt_debug_read_timeline", "crt_debug_read_counters", "crt_debug_check_rcp", "crt_render_frame", "crt_render_frame_device",
+    "crt_set_shading_mode", "crt_set_miss_color", "crt_set_counting", "crt_set_option", "crt_debug_read_timeline", "crt_debug_read_counters", "crt_debug_check_rcp", "crt_debug_wide_offsets", "crt_render_frame", "crt_render_frame_device",
     "crt_tile_count", "crt_tile_slots", "crt_render_tiles_device", "crt_render_frames_batch_device", "crt_render_tiles_batch_device",
     "crt_untile_device", "crt_untile_batch_device", "crt_set_stream", "crt_reset_stream",
     "crt_synchronize", "crt_bvh_info", "crt_bvh_export", "crt_bvh_build_host", "crt_free", "crt_host_alloc", "crt_host_free", "crt_bvh_info4", "crt_bvh_export4", "crt_bvh_export4q", "crt_bvh_export_planes4q", "crt_bvh_quantize4", "crt_comm_unique_id", "crt_comm_init", "crt_comm_init_host", "crt_comm_destroy", "crt_comm_info", "crt_render_frame_distributed", "crt_bvh_build_host4", "crt_build_stats",
@@ -163,6 +163,7 @@ def lib():
         "crt_debug_read_timeline": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "crt_debug_read_counters": (C.c_int, [vp, vp]),
         "crt_debug_check_rcp": (C.c_int, [C.c_int, vp]),
+        "crt_debug_wide_offsets": (C.c_int, [C.c_ulonglong, C.c_ulonglong, C.c_int]),
         "crt_render_frame": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp]),
         "crt_render_frame_device": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp]),
         "crt_tile_count": (u32, [u32, u32]),

@@ -106,6 +106,7 @@ struct crt_ctx {
     uint32_t tuneInnerMin = static_cast<uint32_t>(-6);
     uint32_t tuneInnerMinAny = static_cast<uint32_t>(-6);
     uint32_t tuneStackEntries = 0; // 0 = from the BVH depth
+    uint32_t tuneWideOffsets = 0;  // 0 = by the scene's sizes (crt::wideOffsets), 1 = always the 64-bit form
     uint32_t tuneXcdGroup = 16;
     uint32_t tuneBoostUnits = 512;
     // Split packets (split_packet.hip.h): the n most expensive 8x8 packets are rendered by 64 / split_rays wavefronts each whose
@@ -429,6 +430,7 @@ void fillParams(const crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_
     // wavefronts per SIMD the kernel's register budget allows (12 .. 20 entries measured alike, 24 costs 4 %); no ray of the
     // bench scenes holds more than 15 entries, deeper ones (up to 3 * depth4 + 1: tests/test_deep_stacks.py) spill to the arena
     p.stack_entries = c->tuneStackEntries ? c->tuneStackEntries : 16u;
+    p.wide_offsets = crt::wideOffsets(p.n_nodes, p.n_tris, c->tuneWideOffsets) ? 1u : 0u;
     p.n_batch = 1;
     p.units_per_frame = crt::renderUnitCount(p);
 }
@@ -1191,6 +1193,10 @@ int crt_set_option(crt_ctx* c, const char* name, int value)
         c->tuneStackEntries = static_cast<uint32_t>(value);
         return CRT_OK;
     }
+    if (std::strcmp(name, "wide_offsets") == 0 && (value == 0 || value == 1)) {
+        c->tuneWideOffsets = static_cast<uint32_t>(value);
+        return CRT_OK;
+    }
     return fail(c, CRT_EINVAL, "unknown option '%s' or value %d out of range", name, value);
 }
 
@@ -1238,6 +1244,11 @@ int crt_debug_check_rcp(int device_id, unsigned long long out[8])
     (void)hipFree(d);
     if (e != hipSuccess) return fail(nullptr, CRT_EHIP, "crt_debug_check_rcp: %s", hipGetErrorString(e));
     return CRT_OK;
+}
+
+int crt_debug_wide_offsets(unsigned long long n_nodes, unsigned long long n_tris, int option)
+{
+    return crt::wideOffsets(n_nodes, n_tris, static_cast<uint32_t>(option)) ? 1 : 0;
 }
 
 int crt_set_stream(crt_ctx* c, void* hip_stream)

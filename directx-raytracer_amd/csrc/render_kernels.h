@@ -45,6 +45,7 @@ struct RenderParams {
     uint32_t tune_inner_min;     // wave scheduling knob of the closest-hit traversal, see closestIteration() (int: negative = adaptive)
     uint32_t tune_inner_min_any; // the same for the any-hit (shadow ray) traversal
     uint32_t stack_entries;      // per-lane stack entries kept in LDS; deeper ones go to the spill arena
+    uint32_t wide_offsets;       // wideOffsets() below: 1 = the render kernel's per-lane fetches keep 64-bit address arithmetic
     uint32_t debug_skip_units;   // diagnostics: with unit_order, the first N work units are not rendered
     uint32_t boost_units;        // with unit_order: the first boost_units (most expensive) work units run at raised priority
     uint32_t split_units;        // with unit_order: the first split_units work units are rendered by FOUR wavefronts, one per 4x4
@@ -98,6 +99,15 @@ struct RenderParams {
     uint32_t acc_base;            // global index of the call's first sample = samples already in the sums
     uint32_t acc_total;           // acc_base + spp: what the sums are divided by
 };
+
+// The form of the render kernel's per-lane node and triangle fetches.  The narrow form computes a record's byte offset in 32
+// bits, which holds while every record starts below 2^32: 64 * n_nodes <= 2^32 and 48 * n_tris <= 2^32 (the shading records
+// are 48 bytes too).  The builders admit 2^28 - 1 triangles, so the wide form stays reachable.  option: "wide_offsets", 0 =
+// by the sizes, 1 = always wide.
+inline bool wideOffsets(uint64_t n_nodes, uint64_t n_tris, uint32_t option)
+{
+    return option != 0u || 64u * n_nodes > (1ull << 32) || 48u * n_tris > (1ull << 32);
+}
 
 // Enqueue the fused rayGen -> traverse -> shade -> store kernel. counting selects the instrumented variant.
 int launchRender(const RenderParams& p, bool counting, ihipStream_t* stream);

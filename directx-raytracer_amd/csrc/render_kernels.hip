@@ -41,9 +41,13 @@ __device__ __forceinline__ uint32_t laneId() { return laneIndex(); }
 // slower and the kernel spilled 14 registers).
 // (The SPLIT variant is given 96 registers: the streams of a split quarter hold a ray in flight plus the hand-out state, and a
 // launch that splits packets is one whose chip is not full -- an N-rank tile share -- so five wavefronts per SIMD cost it nothing.)
-template <bool COUNT, bool PHONG, class L, bool SPLIT>
+// NARROW: per-lane node and triangle fetches take a 32-bit byte offset from the wave-uniform base (LayLegacy::load); launched
+// unless RenderParams::wide_offsets says the scene's arrays are too long for that (wideOffsets, render_kernels.h).  The streams of a
+// split packet keep the 64-bit form, so the SPLIT variant exists in that form only.
+template <bool COUNT, bool PHONG, class L, bool SPLIT, bool NARROW_ASKED = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SPLIT ? 5 : L::kWavesPerEu, 8))) void renderKernel(const RenderParams p)
 {
+    constexpr bool NARROW = NARROW_ASKED && NARROW_OFFSETS;
     extern __shared__ int s_stack[]; // stack_entries x 256 dwords, sized at launch from the BVH depth
     unsigned long long t_start = 0;
     if ((CRT_DIAG && p.timeline) || p.unit_cost) t_start = __builtin_amdgcn_s_memrealtime();
@@ -153,17 +157,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SPLIT ? 5 : 
             const F3 o = f3(camPos[0], camPos[1], camPos[2]);
             const Ray r = makeRay(o, rayDir(camRot, px, py, static_cast<float>(p.width), static_cast<float>(p.height)));
             if (COUNT) cntClosest++;
-            traceClosest<COUNT, L, true, true>(nodes, tris, p.n_nodes, r, kTMin, kTMax, stack, static_cast<int>(p.tune_inner_min), h, iters, cntNodes, cntTris, p.planes);
+            traceClosest<COUNT, L, true, true, true, NARROW>(nodes, tris, p.n_nodes, r, kTMin, kTMax, stack, static_cast<int>(p.tune_inner_min), h, iters, cntNodes, cntTris, p.planes);
             col = f3(p.miss[0], p.miss[1], p.miss[2]); // miss shader (hlsl:72-76)
             if (h.t < kTMax) {
-                const float4* T = L::triPtr(tris, h.tri);
-                if (p.mode >= 100u) col = shadeLambert<COUNT, L, PHONG>(p, nodes, tris, r, h, stack, iters, cntNodes, cntTris, cntShadow);
+                const float4* T = L::template triPtr<NARROW>(tris, h.tri);
+                if (p.mode >= 100u) col = shadeLambert<COUNT, L, PHONG, NARROW>(p, nodes, tris, r, h, stack, iters, cntNodes, cntTris, cntShadow);
                 else col = shadeDebug(p.mode, __float_as_uint(T[0].w), __float_as_uint(T[1].w), h.t, h.u, h.v, r.o, r.d);
             }
         }
         const bool hit = h.t < kTMax;
         if (hit) {
-            const float4* T = L::triPtr(tris, h.tri);
+            const float4* T = L::template triPtr<NARROW>(tris, h.tri);
             inst = __float_as_uint(T[0].w);
             prim = __float_as_uint(T[1].w);
         }
@@ -279,12 +283,12 @@ int launchRender(const RenderParams& p, bool counting, ihipStream_t* stream)
         const dim3 grid((n * 4u + extra) * (p.n_batch ? p.n_batch : 1u));
         const bool phong = p.mode >= 100u && p.phong_ks > 0.0f;
         const bool split = p.unit_order && p.split_units > 0u;
-#define CRT_LAUNCH(SPL)                                                                                                    \
-        if (counting && phong) hipLaunchKernelGGL((renderKernel<true, true, LayLegacy, SPL>), grid, block, lds, stream, p);  \
-        else if (counting) hipLaunchKernelGGL((renderKernel<true, false, LayLegacy, SPL>), grid, block, lds, stream, p);     \
-        else if (phong) hipLaunchKernelGGL((renderKernel<false, true, LayLegacy, SPL>), grid, block, lds, stream, p);        \
-        else hipLaunchKernelGGL((renderKernel<false, false, LayLegacy, SPL>), grid, block, lds, stream, p);
-        if (split) { CRT_LAUNCH(true) } else { CRT_LAUNCH(false) }
+#define CRT_LAUNCH(SPL, NAR)                                                                                                    \
+        if (counting && phong) hipLaunchKernelGGL((renderKernel<true, true, LayLegacy, SPL, NAR>), grid, block, lds, stream, p);  \
+        else if (counting) hipLaunchKernelGGL((renderKernel<true, false, LayLegacy, SPL, NAR>), grid, block, lds, stream, p);     \
+        else if (phong) hipLaunchKernelGGL((renderKernel<false, true, LayLegacy, SPL, NAR>), grid, block, lds, stream, p);        \
+        else hipLaunchKernelGGL((renderKernel<false, false, LayLegacy, SPL, NAR>), grid, block, lds, stream, p);
+        if (split) { CRT_LAUNCH(true, false) } else if (p.wide_offsets) { CRT_LAUNCH(false, false) } else { CRT_LAUNCH(false, true) }
 #undef CRT_LAUNCH
     }
     return static_cast<int>(hipGetLastError());

@@ -61,6 +61,14 @@ constexpr uint32_t kBoostAfter = 300; // traversal-loop iterations after which a
 #ifndef EARLY_FETCH
 #define EARLY_FETCH 1
 #endif
+// the render kernel's fetch forms: a closest-hit leaf pair's six loads pinned in front of their first wait (PAIR of
+// closestIteration), and per-lane record addresses as a 32-bit byte offset from the wave-uniform base (NARROW of both traversals)
+#ifndef LEAF_PAIR_PIN
+#define LEAF_PAIR_PIN 1
+#endif
+#ifndef NARROW_OFFSETS
+#define NARROW_OFFSETS 1
+#endif
 // the next node's record is requested before the current step's pushes (nodeStepClosestAt)
 // (EARLY_FETCH above); one copy of the traversal loops per direction octant for packets whose rays agree on it
 #ifndef OCTANT_SPECIALISE
@@ -359,9 +367,15 @@ struct LayLegacy {
     };
     static __device__ __forceinline__ bool inner(int c) { return c >= 0; }
     static __device__ __forceinline__ bool leaf(int c) { return (c < 0) & (c != kDone); }
+    // NARROW: the record's byte offset is computed in 32 bits and added to the wave-uniform base, so that the loads take the
+    // scalar-base form (one v_lshlrev_b32 instead of a 64-bit shift and add, and the reference needs no sign-extended upper
+    // half).  Valid while 64 * n_nodes <= 2^32 and 48 * n_tris <= 2^32: the host's choice, wideOffsets() of render_kernels.h.
+    template <bool NARROW = false>
     static __device__ __forceinline__ Node load(const float4* __restrict__ nodes, int ref)
     {
-        const float4* N = nodes + 4 * static_cast<size_t>(ref);
+        const float4* N;
+        if constexpr (NARROW) N = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(nodes) + (static_cast<uint32_t>(ref) << 6));
+        else N = nodes + 4 * static_cast<size_t>(ref);
         Node nd;
         nd.q0 = N[0]; nd.q1 = N[1]; nd.q2 = N[2];
         nd.refs = *reinterpret_cast<const int4*>(N + 3);
@@ -397,7 +411,20 @@ struct LayLegacy {
         cnt = code & 7u;
     }
     static __device__ __forceinline__ uint32_t triId(uint32_t first, uint32_t i) { return first + i; }
-    static __device__ __forceinline__ const float4* triPtr(const float4* __restrict__ tris, uint32_t id) { return tris + 3 * static_cast<size_t>(id); }
+    template <bool NARROW = false>
+    static __device__ __forceinline__ const float4* triPtr(const float4* __restrict__ tris, uint32_t id)
+    {
+        if constexpr (NARROW) return reinterpret_cast<const float4*>(reinterpret_cast<const char*>(tris) + id * 48u);
+        else return tris + 3 * static_cast<size_t>(id);
+    }
+    // the second record of a leaf pair, id1 = two ? id + 1 : id.  NARROW: the first record's offset plus 48 or 0, a select and an
+    // add where id1 * 48 is a full 32-bit multiply (the first offset is the loop's induction variable)
+    template <bool NARROW = false>
+    static __device__ __forceinline__ const float4* triPtrSecond(const float4* __restrict__ tris, uint32_t id, uint32_t id1, bool two)
+    {
+        if constexpr (NARROW) return reinterpret_cast<const float4*>(reinterpret_cast<const char*>(tris) + (id * 48u + (two ? 48u : 0u)));
+        else return triPtr(tris, id1);
+    }
 
     template <int OCT>
     static __device__ __forceinline__ void slab(const Node& nd, const Ray& r, float tmin, float tcull, float tn[4], bool hit[4])
@@ -445,8 +472,8 @@ struct LayLegacy {
     // 0.368 vs 0.361: the network runs under the early fetch, off the step's dependent chain, so removing it frees issue
     // slots nobody was waiting for.)
     // (N: Node, or NodeU on the scalar path with the plane table)
-    // (LPOP: the pop is Stack::popLds)
-    template <bool COUNT, int OCT, bool EARLY, bool LPOP = false, class N>
+    // (LPOP: the pop is Stack::popLds; NARROW: the early fetch is load<true>)
+    template <bool COUNT, int OCT, bool EARLY, bool LPOP = false, bool NARROW = false, class N>
     static __device__ __forceinline__ void closestStep(const N& nd, const Ray& r, float tmin, float tcull, Stack& stack,
                                                        int& cur, uint32_t& cntNodes, const float4* __restrict__ nodes, Node& ndNext)
     {
@@ -463,7 +490,7 @@ struct LayLegacy {
         const bool any = nearest != 0xFFFFFFFFu;
         cur = any ? pick4(refs, nearest & 3u) : (stack.sp == 0 ? kDone : stack.template popAs<LPOP>()); // a lane pops or pushes, never both
         if (EARLY) {
-            if (cur >= 0) ndNext = load(nodes, cur);
+            if (cur >= 0) ndNext = load<NARROW>(nodes, cur);
         }
 #define CRT_CSWAP(a, b) { const uint32_t lo = min(key[a], key[b]), hi = max(key[a], key[b]); key[a] = lo; key[b] = hi; }
         CRT_CSWAP(0, 1) CRT_CSWAP(2, 3) CRT_CSWAP(0, 2) CRT_CSWAP(1, 3) CRT_CSWAP(1, 2)
@@ -476,7 +503,7 @@ struct LayLegacy {
     }
 
     // any hit: order independent, children taken in slot order
-    template <bool COUNT, int OCT, bool EARLY, bool LPOP = false, class N>
+    template <bool COUNT, int OCT, bool EARLY, bool LPOP = false, bool NARROW = false, class N>
     static __device__ __forceinline__ void anyStep(const N& nd, const Ray& r, float tmin, float tcull, Stack& stack,
                                                    int& cur, uint32_t& cntNodes, const float4* __restrict__ nodes, Node& ndNext)
     {
@@ -488,7 +515,7 @@ struct LayLegacy {
         const bool h0 = hit[0], h1 = hit[1], h2 = hit[2], h3 = hit[3];
         cur = h0 ? refs.x : (h1 ? refs.y : (h2 ? refs.z : (h3 ? refs.w : (stack.sp == 0 ? kDone : stack.template popAs<LPOP>()))));
         if (EARLY) {
-            if (cur >= 0) ndNext = load(nodes, cur);
+            if (cur >= 0) ndNext = load<NARROW>(nodes, cur);
         }
         // first hit slot became current; later hit slots are pushed, last slot first
         if (h3 & (h0 | h1 | h2)) stack.push(refs.w);
@@ -512,16 +539,16 @@ __device__ __forceinline__ auto loadUniformStep(const float4* nodes, const float
 // wave-uniform, so the loads become s_load) instead of 64 identical per-lane vector fetches; each lane still runs its own
 // slab tests, ordering and pushes, so results and counters are exactly those of the per-lane loop that follows.
 #if UNIFORM_DESCENT
-#define CRT_UNIFORM_DESCENT(STEP, LPOP)                                                                                         \
+#define CRT_UNIFORM_DESCENT(STEP, LPOP, NARROW)                                                                                     \
     for (;;) {                                                                                                                 \
         const int c0 = __builtin_amdgcn_readfirstlane(cur);                                                                    \
         if (!L::inner(c0) || __ballot(cur != c0) != 0ull) break;                                                               \
         typename L::Node ndUnused;                                                                                             \
         CRT_UNIFORM_STEP_STAT(STEP)                                                                                            \
-        L::template STEP<COUNT, OCT, false, LPOP>(loadUniformStep<L, OCT, DEC>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndUnused); \
+        L::template STEP<COUNT, OCT, false, LPOP, NARROW>(loadUniformStep<L, OCT, DEC>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndUnused); \
     }
 #else
-#define CRT_UNIFORM_DESCENT(STEP, LPOP)
+#define CRT_UNIFORM_DESCENT(STEP, LPOP, NARROW)
 #endif
 #define CRT_STEP_KIND_closestStep 0
 #define CRT_STEP_KIND_anyStep 1
@@ -548,43 +575,43 @@ __device__ __forceinline__ auto loadUniformStep(const float4* nodes, const float
 // CRT_NODE_STEPS: the NODE_STEPS node steps of one scheduling decision.  The first fetches its record here; with
 // EARLY_FETCH every step but the last requests the next record itself (see closestStep), per lane.
 #if UNIFORM_STEP
-#define CRT_FIRST_NODE_STEP(STEP, EARLY, LPOP)                                                                                  \
+#define CRT_FIRST_NODE_STEP(STEP, EARLY, LPOP, NARROW)                                                                             \
     {                                                                                                                          \
         const int c0 = __builtin_amdgcn_readfirstlane(cur);                                                                    \
         if (__ballot(cur != c0) == 0ull) {                                                                                     \
             CRT_UNIFORM_STEP_STAT(STEP)                                                                                        \
-            L::template STEP<COUNT, OCT, EARLY, LPOP>(loadUniformStep<L, OCT, DEC>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
+            L::template STEP<COUNT, OCT, EARLY, LPOP, NARROW>(loadUniformStep<L, OCT, DEC>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
         } else {                                                                                                               \
             CRT_DIV_STATS_NODE                                                                                                 \
             CRT_STEP_STAT(wsD, STEP)                                                                                           \
-            L::template STEP<COUNT, OCT, EARLY, LPOP>(L::load(nodes, cur), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);      \
+            L::template STEP<COUNT, OCT, EARLY, LPOP, NARROW>(L::template load<NARROW>(nodes, cur), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
         }                                                                                                                      \
     }
 #else
-#define CRT_FIRST_NODE_STEP(STEP, EARLY, LPOP) L::template STEP<COUNT, OCT, EARLY, LPOP>(L::load(nodes, cur), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);
+#define CRT_FIRST_NODE_STEP(STEP, EARLY, LPOP, NARROW) L::template STEP<COUNT, OCT, EARLY, LPOP, NARROW>(L::template load<NARROW>(nodes, cur), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);
 #endif
 #if EARLY_FETCH
-#define CRT_NODE_STEPS_AS(STEP, LPOP)                                                                                          \
+#define CRT_NODE_STEPS_AS(STEP, LPOP, NARROW)                                                                                    \
     if (L::inner(cur)) {                                                                                                       \
         typename L::Node ndNext;                                                                                               \
-        CRT_FIRST_NODE_STEP(STEP, (NODE_STEPS > 1), LPOP)                                                                      \
+        CRT_FIRST_NODE_STEP(STEP, (NODE_STEPS > 1), LPOP, NARROW)                                                              \
         _Pragma("unroll") for (int rep = 1; rep < NODE_STEPS; rep++) {                                                         \
             if (L::inner(cur)) {                                                                                               \
                 CRT_STEP_STAT(wsF, STEP)                                                                                       \
                 CRT_AGREE_STAT(STEP)                                                                                           \
                 const typename L::Node ndCur = ndNext;                                                                         \
-                if (rep + 1 < NODE_STEPS) L::template STEP<COUNT, OCT, true, LPOP>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
-                else L::template STEP<COUNT, OCT, false, LPOP>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);     \
+                if (rep + 1 < NODE_STEPS) L::template STEP<COUNT, OCT, true, LPOP, NARROW>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
+                else L::template STEP<COUNT, OCT, false, LPOP, NARROW>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
             }                                                                                                                  \
         }                                                                                                                      \
     }
 #else
-#define CRT_NODE_STEPS_AS(STEP, LPOP)                                                                                          \
+#define CRT_NODE_STEPS_AS(STEP, LPOP, NARROW)                                                                                    \
     _Pragma("unroll") for (int rep = 0; rep < NODE_STEPS; rep++) {                                                             \
-        if (L::inner(cur)) { typename L::Node ndNext; CRT_FIRST_NODE_STEP(STEP, false, LPOP) }                                  \
+        if (L::inner(cur)) { typename L::Node ndNext; CRT_FIRST_NODE_STEP(STEP, false, LPOP, NARROW) }                          \
     }
 #endif
-#define CRT_NODE_STEPS(STEP) CRT_NODE_STEPS_AS(STEP, false)
+#define CRT_NODE_STEPS(STEP) CRT_NODE_STEPS_AS(STEP, false, false)
 
 __device__ __forceinline__ void loadTriUniform(const float4* T, float4& a, float4& b, float4& c)
 {
@@ -606,8 +633,10 @@ __device__ __forceinline__ void loadTriUniform(const float4* T, float4& a, float
 // caller, so a caller may retire finished rays and start new ones between two calls (streamClosest).  Returns false when
 // no lane has anything left to do.
 // DEC / planes: scalar-path steps read the decoded plane table (kPlaneStride floats per node, render_kernels.h) -- the render kernel's
-// traversals; the others keep the default (no table).  LPOP: pops are Stack::popLds -- likewise.
-template <bool COUNT, class L, int OCT, bool DEC = false, bool LPOP = false>
+// traversals; the others keep the default (no table).  LPOP: pops are Stack::popLds -- likewise.  PAIR: the six loads of a leaf
+// pair are issued in front of their first wait (LEAF_PAIRS below) -- likewise.  NARROW: per-lane node and triangle fetches take
+// a 32-bit byte offset from the wave-uniform base (LayLegacy::load) -- the render kernel's narrow variants.
+template <bool COUNT, class L, int OCT, bool DEC = false, bool LPOP = false, bool PAIR = false, bool NARROW = false>
 __device__ __forceinline__ bool closestIteration(const float4* __restrict__ nodes, const float4* __restrict__ tris, const Ray& r, float tmin,
                                                  float& tcull, Stack& stack, int innerMin, Hit& h, int& cur, uint32_t& iters,
                                                  uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
@@ -624,7 +653,7 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
 #if CRT_PROF
         const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
 #endif
-        CRT_NODE_STEPS_AS(closestStep, LPOP) // several node steps per scheduling decision: fewer ballots/branches
+        CRT_NODE_STEPS_AS(closestStep, LPOP, NARROW) // several node steps per scheduling decision: fewer ballots/branches
 #if CRT_PROF
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         stack.tNode += __builtin_amdgcn_s_memtime() - ts0; stack.itNode++; stack.lanesNode += __popcll(innerMask);
@@ -663,14 +692,22 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
         {
             CRT_DIV_STATS_LEAF
 #if LEAF_PAIRS
-            // two triangles per memory round trip (same test order): the second record's loads overlap the first's
+            // two triangles per trip, same test order, so that the second record's loads overlap the first's.  The source order
+            // alone does not get that: the compiler issues the first record's three loads, waits for the first of them, starts
+            // the triangle test and only then computes the second address and issues the second record's loads -- two memory
+            // latencies one after the other.  PAIR: a scheduling barrier behind the six loads keeps every instruction on its
+            // side, so both addresses are computed first, the six loads go out back to back and the first wait follows them:
+            // one round trip per pair (listings and times in DESIGN section 5).
             for (uint32_t i = 0; i < cnt; i += 2) {
                 const bool two = i + 1 < cnt;
                 const uint32_t id = L::triId(first, i), id1 = L::triId(first, two ? i + 1 : i);
-                const float4* T = L::triPtr(tris, id);
-                const float4* T1 = L::triPtr(tris, id1);
+                const float4* T = L::template triPtr<NARROW>(tris, id);
+                const float4* T1 = L::template triPtrSecond<NARROW>(tris, id, id1, two);
                 const float4 a = T[0], b = T[1], c = T[2];
                 const float4 a1 = T1[0], b1 = T1[1], c1 = T1[2];
+#if LEAF_PAIR_PIN
+                if constexpr (PAIR) __builtin_amdgcn_sched_barrier(0);
+#endif
                 if (COUNT) cntTris += two ? 2u : 1u;
                 float t, u, v;
                 if (triTest<DEC>(r, a, b, c, tmin, t, u, v)) {
@@ -691,7 +728,7 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
 #else
             for (uint32_t i = 0; i < cnt; i++) {
                 const uint32_t id = L::triId(first, i);
-                const float4* T = L::triPtr(tris, id);
+                const float4* T = L::template triPtr<NARROW>(tris, id);
                 const float4 a = T[0], b = T[1], c = T[2];
                 if (COUNT) cntTris++;
                 float t, u, v;
@@ -714,7 +751,7 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
     return true;
 }
 
-template <bool COUNT, class L, int OCT, bool DEC, bool LPOP>
+template <bool COUNT, class L, int OCT, bool DEC, bool LPOP, bool PAIR, bool NARROW>
 __device__ __forceinline__ void traceClosestOct(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                              uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
                                              Hit& h, uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes)
@@ -723,12 +760,12 @@ __device__ __forceinline__ void traceClosestOct(const float4* __restrict__ nodes
     int cur = n_nodes ? L::kRoot : L::kDone;
     stack.sp = 0;
     float tcull = tmax * kCullPad; // boxes are culled against best_t * pad; changes only when a hit is accepted
-    CRT_UNIFORM_DESCENT(closestStep, LPOP)
-    while (closestIteration<COUNT, L, OCT, DEC, LPOP>(nodes, tris, r, tmin, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris, planes)) {}
+    CRT_UNIFORM_DESCENT(closestStep, LPOP, NARROW)
+    while (closestIteration<COUNT, L, OCT, DEC, LPOP, PAIR, NARROW>(nodes, tris, r, tmin, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris, planes)) {}
 }
 
 // One scheduling decision of the any-hit traversal (see closestIteration); tmax / tcull / occluded are per-lane state of the caller
-template <bool COUNT, class L, int OCT, bool DEC = false, bool LPOP = false>
+template <bool COUNT, class L, int OCT, bool DEC = false, bool LPOP = false, bool NARROW = false>
 __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, const float4* __restrict__ tris, const Ray& r, float tmin, float tmax,
                                              float tcull, Stack& stack, int innerMin, bool& occluded, int& cur, uint32_t& iters,
                                              uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
@@ -745,7 +782,7 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
 #if CRT_PROF
         const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
 #endif
-        CRT_NODE_STEPS_AS(anyStep, LPOP) // several node steps per scheduling decision: fewer ballots/branches
+        CRT_NODE_STEPS_AS(anyStep, LPOP, NARROW) // several node steps per scheduling decision: fewer ballots/branches
 #if CRT_PROF
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         stack.tNode += __builtin_amdgcn_s_memtime() - ts0; stack.itNode++; stack.lanesNode += __popcll(innerMask);
@@ -777,7 +814,7 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
         } else
 #endif
         for (uint32_t i = 0; i < cnt; i++) {
-            const float4* T = L::triPtr(tris, L::triId(first, i));
+            const float4* T = L::template triPtr<NARROW>(tris, L::triId(first, i));
             const float4 a = T[0], b = T[1], c = T[2];
             if (COUNT) cntTris++;
             float t, u, v;
@@ -795,7 +832,7 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
     return true;
 }
 
-template <bool COUNT, class L, int OCT, bool DEC, bool LPOP>
+template <bool COUNT, class L, int OCT, bool DEC, bool LPOP, bool NARROW>
 __device__ __forceinline__ bool traceAnyOct(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                          uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
                                          uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes)
@@ -804,8 +841,8 @@ __device__ __forceinline__ bool traceAnyOct(const float4* __restrict__ nodes, co
     int cur = n_nodes ? L::kRoot : L::kDone;
     stack.sp = 0;
     const float tcull = tmax * kCullPad;
-    CRT_UNIFORM_DESCENT(anyStep, LPOP)
-    while (anyIteration<COUNT, L, OCT, DEC, LPOP>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris, planes)) {}
+    CRT_UNIFORM_DESCENT(anyStep, LPOP, NARROW)
+    while (anyIteration<COUNT, L, OCT, DEC, LPOP, NARROW>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris, planes)) {}
     return occluded;
 }
 
@@ -816,7 +853,7 @@ __device__ __forceinline__ uint32_t octantOf(const Ray& r)
     return (__float_as_uint(r.d.x) >> 31) | ((__float_as_uint(r.d.y) >> 31) << 1) | ((__float_as_uint(r.d.z) >> 31) << 2);
 }
 
-template <bool COUNT, class L, bool DEC = false, bool LPOP = false>
+template <bool COUNT, class L, bool DEC = false, bool LPOP = false, bool PAIR = false, bool NARROW = false>
 __device__ __forceinline__ void traceClosest(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                              uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
                                              Hit& h, uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
@@ -826,16 +863,16 @@ __device__ __forceinline__ void traceClosest(const float4* __restrict__ nodes, c
     const uint32_t o0 = __builtin_amdgcn_readfirstlane(oct);
     if (__ballot(oct != o0) == 0ull) {
         switch (o0) {
-#define CRT_CASE(k) case k: traceClosestOct<COUNT, L, k, DEC, LPOP>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes); return;
+#define CRT_CASE(k) case k: traceClosestOct<COUNT, L, k, DEC, LPOP, PAIR, NARROW>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes); return;
             CRT_CASE(0) CRT_CASE(1) CRT_CASE(2) CRT_CASE(3) CRT_CASE(4) CRT_CASE(5) CRT_CASE(6) CRT_CASE(7)
 #undef CRT_CASE
         }
     }
 #endif
-    traceClosestOct<COUNT, L, 8, DEC, LPOP>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes);
+    traceClosestOct<COUNT, L, 8, DEC, LPOP, PAIR, NARROW>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes);
 }
 
-template <bool COUNT, class L, bool DEC = false, bool LPOP = false>
+template <bool COUNT, class L, bool DEC = false, bool LPOP = false, bool NARROW = false>
 __device__ __forceinline__ bool traceAny(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                          uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
                                          uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
@@ -845,13 +882,13 @@ __device__ __forceinline__ bool traceAny(const float4* __restrict__ nodes, const
     const uint32_t o0 = __builtin_amdgcn_readfirstlane(oct);
     if (__ballot(oct != o0) == 0ull) {
         switch (o0) {
-#define CRT_CASE(k) case k: return traceAnyOct<COUNT, L, k, DEC, LPOP>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
+#define CRT_CASE(k) case k: return traceAnyOct<COUNT, L, k, DEC, LPOP, NARROW>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
             CRT_CASE(0) CRT_CASE(1) CRT_CASE(2) CRT_CASE(3) CRT_CASE(4) CRT_CASE(5) CRT_CASE(6) CRT_CASE(7)
 #undef CRT_CASE
         }
     }
 #endif
-    return traceAnyOct<COUNT, L, 8, DEC, LPOP>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
+    return traceAnyOct<COUNT, L, 8, DEC, LPOP, NARROW>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
 }
 
 } // namespace

@@ -252,7 +252,9 @@ int crt_render_frame_distributed(crt_ctx* ctx, uint32_t width, uint32_t height, 
  * stages; its queues hold "path_pass_paths" paths per pass (65536..2^25, default 2^24 = 1.9 GB), a frame with more is rendered in
  * several passes), "path_ranges" (mode 200: 8 (default) = the
  * work items are cut into eight contiguous ranges and a wavefront works through the range of the XCD it runs on before taking from the others', 1 = one shared work counter), "stack_entries" (0 = default 16; deeper entries spill to a
- * global arena), "list_short_max" (crt_list_hits*: 1..1024, default 24: lists up to this many hits are sorted by one lane, longer ones by a wavefront). The diagnostic options "timeline", "debug_skip_units" and "debug_force_measure" (which do change what a frame
+ * global arena), "wide_offsets" (frames of modes 0..100: 0 (default) = the render kernel computes the byte offset of a node or triangle
+ * record in 32 bits whenever 64 * nodes <= 2^32 and 48 * triangles <= 2^32, and in 64 bits otherwise; 1 = always in 64 bits.  Results
+ * are the same either way), "list_short_max" (crt_list_hits*: 1..1024, default 24: lists up to this many hits are sorted by one lane, longer ones by a wavefront). The diagnostic options "timeline", "debug_skip_units" and "debug_force_measure" (which do change what a frame
  * does) exist only in the diagnostic build of the library (tools/diag_build.sh); the product returns CRT_EINVAL for them. */
 int crt_set_option(crt_ctx* ctx, const char* name, int value);
 
@@ -270,6 +272,10 @@ int crt_debug_list_phases(crt_ctx* ctx, double out_ms[4]);
  * mismatches of the unguarded Newton form by class (biased exponent 0 / 253..255 / all-ones significand / the rest), [6]
  * smallest mismatching input or ~0.  Synchronous; a few milliseconds of GPU time. */
 int crt_debug_check_rcp(int device_id, unsigned long long out[8]);
+
+/* diagnostics: the render kernel's fetch form for a tree of n_nodes nodes and n_tris triangles under option "wide_offsets" =
+ * option: 1 = 64-bit offsets, 0 = 32-bit offsets.  Pure host arithmetic, no device needed. */
+int crt_debug_wide_offsets(unsigned long long n_nodes, unsigned long long n_tris, int option);
 
 /* stream plumbing: run on an external hipStream_t (e.g. torch's current stream; NULL = HIP's default stream);
  * crt_reset_stream goes back to the context's private non-blocking stream */
