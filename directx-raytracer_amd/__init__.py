@@ -56,6 +56,8 @@ ABI_SYMBOLS = [
     "crt_path_rays_device", "crt_path_rays",
     "crt_camera_rays_device", "crt_camera_rays", "crt_frame_guides_device", "crt_frame_guides", "crt_denoise_device", "crt_denoise",
     "crt_temporal_accumulate_device", "crt_temporal_accumulate",
+    "crt_motion_snapshot", "crt_previous_points_device", "crt_previous_points", "crt_frame_motion_device", "crt_frame_motion",
+    "crt_temporal_accumulate_motion_device", "crt_temporal_accumulate_motion",
 ]
 
 
@@ -257,6 +259,13 @@ def lib():
         "crt_denoise": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
         "crt_temporal_accumulate_device": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "crt_temporal_accumulate": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "crt_motion_snapshot": (C.c_int, [vp]),
+        "crt_previous_points_device": (C.c_int, [vp, u32, vp, vp, vp, vp, vp]),
+        "crt_previous_points": (C.c_int, [vp, u32, vp, vp, vp, vp, vp]),
+        "crt_frame_motion_device": (C.c_int, [vp, u32, u32, vp, vp]),
+        "crt_frame_motion": (C.c_int, [vp, u32, u32, vp, vp]),
+        "crt_temporal_accumulate_motion_device": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "crt_temporal_accumulate_motion": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     assert set(sig) == set(ABI_SYMBOLS)
     for name, (res, args) in sig.items():
@@ -550,22 +559,23 @@ class TemporalHistory:
         self.camera = None   # the camera of the previous push; None = no history
 
     def reset(self):
-        """drop the history (after geometry moved, or a cut): the next push starts over"""
+        """drop the history (after a cut, or after geometry moved when no prev_point is given): the next push starts over"""
         self.camera = None
 
-    def push(self, rgb, normal, albedo, t, camera=None):
+    def push(self, rgb, normal, albedo, t, camera=None, prev_point=None):
         """rgb, normal, albedo (h, w, 3) and t (h, w): numpy arrays or torch CUDA tensors of this frame; camera: 12 floats
-        {pos, rot}, None = the one last given to the renderer's set_camera / set_camera_from.  Returns the accumulated image, of
-        the kind rgb is (numpy in, numpy out), and swaps the buffers."""
+        {pos, rot}, None = the one last given to the renderer's set_camera / set_camera_from; prev_point: None, or the (h, w, 3)
+        previous points of this frame (Renderer.frame_motion) when meshes moved.  Returns the accumulated image, of the kind rgb
+        is (numpy in, numpy out), and swaps the buffers."""
         import torch
         if camera is None:
             camera = getattr(self.renderer, "camera", None)
             if camera is None:
                 raise ValueError("no camera: pass camera= or call the renderer's set_camera first")
         cam = _f32(camera, 12).copy()
-        shapes = ((self.h, self.w, 3), (self.h, self.w, 3), (self.h, self.w, 3), (self.h, self.w))
+        shapes = ((self.h, self.w, 3), (self.h, self.w, 3), (self.h, self.w, 3), (self.h, self.w), (self.h, self.w, 3))
         dev = []
-        for a, shape in zip((rgb, normal, albedo, t), shapes):
+        for a, shape in zip((rgb, normal, albedo, t) + (() if prev_point is None else (prev_point,)), shapes):
             d = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
             if tuple(d.shape) != shape or d.dtype != torch.float32 or not d.is_cuda:
                 raise ValueError("expected float32 buffers of shape %r" % (shape,))
@@ -575,7 +585,8 @@ class TemporalHistory:
         have = self.camera is not None
         self.renderer.temporal_accumulate_device(self.w, self.h, cam, self.camera if have else cam, dev[0].data_ptr(), dev[1].data_ptr(),
                                                  dev[2].data_ptr(), dev[3].data_ptr(), self.hist[self.at].data_ptr() if have else None,
-                                                 self.hist[self.at ^ 1].data_ptr(), out.data_ptr(), **self.params)
+                                                 self.hist[self.at ^ 1].data_ptr(), out.data_ptr(),
+                                                 d_prev_point=None if prev_point is None else dev[4].data_ptr(), **self.params)
         self.renderer.synchronize()
         self.at ^= 1
         self.camera = cam
@@ -1034,11 +1045,12 @@ class Renderer:
         return st.as_dict() if stats else None
 
     # ---- temporal reprojection (include/crt_hip.h): cameras are 12 floats {pos[3], rot3x3 row-major[9]}
-    def temporal_accumulate(self, cam_cur, cam_prev, rgb, normal, albedo, t, hist_prev=None, want_out=True, **params):
+    def temporal_accumulate(self, cam_cur, cam_prev, rgb, normal, albedo, t, hist_prev=None, want_out=True, prev_point=None, **params):
         """one frame blended with the reprojected history (host buffers, synchronous): rgb, normal, albedo (h, w, 3) and t (h, w)
         float32 of this frame (albedo may be None with demodulate=0), hist_prev None or the (h, w, 8) float32 records an earlier
-        call returned, taken with camera cam_prev.  params: the fields of TemporalParams.  Returns (hist_next, out): the new
-        records and the accumulated (h, w, 3) image (None when not want_out)."""
+        call returned, taken with camera cam_prev.  prev_point: None, or (h, w, 3) float32 previous points (frame_motion): the
+        call then goes to crt_temporal_accumulate_motion.  params: the fields of TemporalParams.  Returns (hist_next, out): the
+        new records and the accumulated (h, w, 3) image (None when not want_out)."""
         t = np.ascontiguousarray(t, dtype=np.float32)
         if t.ndim != 2:
             raise ValueError("t must be (h, w)")
@@ -1057,20 +1069,73 @@ class Renderer:
         def p(a):
             return None if a is None else a.ctypes.data
         prm = TemporalParams(**params)
+        if prev_point is not None:
+            pp = np.ascontiguousarray(prev_point, dtype=np.float32)
+            if pp.shape != (h, w, 3):
+                raise ValueError("prev_point must be (h, w, 3)")
+            self._ok(lib().crt_temporal_accumulate_motion(self.h, w, h, cc.ctypes.data, cp.ctypes.data, p(bufs[0]), p(bufs[1]), p(bufs[2]),
+                                                          t.ctypes.data, pp.ctypes.data, p(hp), hist.ctypes.data, p(out), C.byref(prm), None),
+                     "crt_temporal_accumulate_motion")
+            return hist, out
         self._ok(lib().crt_temporal_accumulate(self.h, w, h, cc.ctypes.data, cp.ctypes.data, p(bufs[0]), p(bufs[1]), p(bufs[2]), t.ctypes.data,
                                                p(hp), hist.ctypes.data, p(out), C.byref(prm), None), "crt_temporal_accumulate")
         return hist, out
 
     def temporal_accumulate_device(self, w, h, cam_cur, cam_prev, d_rgb, d_normal, d_albedo, d_t, d_hist_prev, d_hist_next, d_out=None,
-                                   stats=False, **params):
+                                   stats=False, d_prev_point=None, **params):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); the cameras are host arrays of 12 floats; d_hist_prev None =
-        no history; d_out may equal d_rgb or be None; asynchronous on the context's stream unless stats"""
+        no history; d_out may equal d_rgb or be None; d_prev_point: None, or the previous points of the frame
+        (frame_motion_device; the call then goes to crt_temporal_accumulate_motion_device); asynchronous on the context's stream
+        unless stats"""
         st = FrameStats() if stats else None
         cc, cp = _f32(cam_cur, 12), _f32(cam_prev, 12)
         prm = TemporalParams(**params)
+        if d_prev_point is not None:
+            self._ok(lib().crt_temporal_accumulate_motion_device(self.h, int(w), int(h), cc.ctypes.data, cp.ctypes.data, d_rgb, d_normal,
+                                                                 d_albedo, d_t, d_prev_point, d_hist_prev, d_hist_next, d_out, C.byref(prm),
+                                                                 C.byref(st) if stats else None), "crt_temporal_accumulate_motion_device")
+            return st.as_dict() if stats else None
         self._ok(lib().crt_temporal_accumulate_device(self.h, int(w), int(h), cc.ctypes.data, cp.ctypes.data, d_rgb, d_normal, d_albedo, d_t,
                                                       d_hist_prev, d_hist_next, d_out, C.byref(prm), C.byref(st) if stats else None),
                  "crt_temporal_accumulate_device")
+        return st.as_dict() if stats else None
+
+    # ---- motion (include/crt_hip.h): previous positions of hits on a dynamic scene whose meshes move
+    def motion_snapshot(self):
+        """remember the current world vertices as "previous" (after a frame is rendered, before the meshes are moved)"""
+        self._ok(lib().crt_motion_snapshot(self.h), "crt_motion_snapshot")
+
+    def previous_points(self, inst, prim, uv):
+        """where the hits (inst, prim, uv) of trace_rays / shade_rays / list_hits were at the last snapshot: (N, 3) float32, NaN
+        for a miss and for a triangle that did not move (host buffers, synchronous)"""
+        i = np.ascontiguousarray(inst, dtype=np.uint32).reshape(-1)
+        q = np.ascontiguousarray(prim, dtype=np.uint32).reshape(-1)
+        u = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+        if not len(i) == len(q) == len(u):
+            raise ValueError("inst, prim and uv must hold one record per hit")
+        out = np.zeros((len(i), 3), dtype=np.float32)
+        self._ok(lib().crt_previous_points(self.h, len(i), i.ctypes.data, q.ctypes.data, u.ctypes.data, out.ctypes.data, None),
+                 "crt_previous_points")
+        return out
+
+    def previous_points_device(self, n, d_inst, d_prim, d_uv, d_point, stats=False):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_previous_points_device(self.h, int(n), d_inst, d_prim, d_uv, d_point, C.byref(st) if stats else None),
+                 "crt_previous_points_device")
+        return st.as_dict() if stats else None
+
+    def frame_motion(self, w, h):
+        """the previous points of a w x h frame's pixel-centre camera rays, (h, w, 3) float32: what temporal_accumulate and
+        TemporalHistory.push take as prev_point (host buffer, synchronous)"""
+        out = np.zeros((int(h), int(w), 3), dtype=np.float32)
+        self._ok(lib().crt_frame_motion(self.h, int(w), int(h), out.ctypes.data, None), "crt_frame_motion")
+        return out
+
+    def frame_motion_device(self, w, h, d_prev_point, stats=False):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_frame_motion_device(self.h, int(w), int(h), d_prev_point, C.byref(st) if stats else None), "crt_frame_motion_device")
         return st.as_dict() if stats else None
 
     # ---- point queries (include/crt_hip.h): records of 4 floats {x, y, z, rmax}, see make_points

@@ -2328,7 +2328,7 @@ int checkTemporal(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const fl
 
 int runTemporal(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const void* d_rgb,
                 const void* d_normal, const void* d_albedo, const void* d_t, const void* d_histPrev, void* d_histNext, void* d_out,
-                const crt_temporal_params& prm, crt_frame_stats* stats)
+                const void* d_prevPoint, const crt_temporal_params& prm, crt_frame_stats* stats)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     crt::TemporalParams p;
@@ -2352,7 +2352,60 @@ int runTemporal(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const floa
     p.histPrev = d_histPrev;
     p.histNext = d_histNext;
     p.out = static_cast<float*>(d_out);
+    p.prevPoint = static_cast<const float*>(d_prevPoint);
     return runTimed(c, what, stats, [&] { return crt::launchTemporal(p, c->stream); });
+}
+
+// the device forms, plain (d_prevPoint == NULL) and with motion
+int temporalDevice(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const void* d_rgb,
+                   const void* d_normal, const void* d_albedo, const void* d_t, const void* d_histPrev, void* d_histNext, void* d_out,
+                   const void* d_prevPoint, const crt_temporal_params* params, crt_frame_stats* stats)
+{
+    const crt_temporal_params prm = params ? *params : kTemporalDefaults;
+    int rc = checkTemporal(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histNext, prm);
+    if (rc) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_out, d_prevPoint }, 4u)) != CRT_OK) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_histPrev, d_histNext }, 16u)) != CRT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext, d_out, d_prevPoint, prm, stats)) !=
+        CRT_OK)
+        return rc;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+// host buffers: staged through the context's query staging buffer {rgb | normal | albedo | t | hist_prev | hist_next | prev_point},
+// the colour accumulated in place; synchronous
+int temporalHost(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const float* rgb,
+                 const float* normal, const float* albedo, const float* t, const float* histPrev, float* histNext, float* out,
+                 const float* prevPoint, const crt_temporal_params* params, crt_frame_stats* stats)
+{
+    const crt_temporal_params prm = params ? *params : kTemporalDefaults;
+    int rc = checkTemporal(c, what, w, h, camCur, camPrev, rgb, normal, albedo, t, histNext, prm);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t nn = static_cast<size_t>(w) * h;
+    const void* const host[7] = { rgb, normal, albedo, t, histPrev, nullptr, prevPoint };
+    const size_t per[7] = { 12u, 12u, 12u, 4u, 32u, 32u, 12u };
+    size_t off[7], total = 0;
+    for (int i = 0; i < 7; i++) {
+        off[i] = total;
+        total += (i == 5 || host[i]) ? up256(nn * per[i]) : 0u;
+    }
+    if ((rc = reserveRayStage(c, total)) != CRT_OK) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
+    unsigned char* dev[7];
+    for (int i = 0; i < 7; i++) dev[i] = (i == 5 || host[i]) ? base + off[i] : nullptr;
+    for (int i = 0; i < 7; i++)
+        if (host[i]) HIP_TRY(c, hipMemcpyAsync(dev[i], host[i], nn * per[i], hipMemcpyHostToDevice, c->stream));
+    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], out ? dev[0] : nullptr, dev[6], prm, stats)) !=
+        CRT_OK)
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(histNext, dev[5], nn * 32u, hipMemcpyDeviceToHost, c->stream));
+    if (out) HIP_TRY(c, hipMemcpyAsync(out, dev[0], nn * 12u, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
 }
 
 } // namespace
@@ -2361,51 +2414,32 @@ int crt_temporal_accumulate_device(crt_ctx* c, uint32_t w, uint32_t h, const flo
                                    const void* d_normal, const void* d_albedo, const void* d_t, const void* d_histPrev, void* d_histNext,
                                    void* d_out, const crt_temporal_params* params, crt_frame_stats* stats)
 {
-    const char* what = "crt_temporal_accumulate_device";
-    const crt_temporal_params prm = params ? *params : kTemporalDefaults;
-    int rc = checkTemporal(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histNext, prm);
-    if (rc) return rc;
-    if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_out }, 4u)) != CRT_OK) return rc;
-    if ((rc = checkDevicePointers(c, what, { d_histPrev, d_histNext }, 16u)) != CRT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext, d_out, prm, stats)) != CRT_OK)
-        return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return CRT_OK;
+    return temporalDevice(c, "crt_temporal_accumulate_device", w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext, d_out,
+                          nullptr, params, stats);
 }
 
-// host buffers: staged through the context's query staging buffer {rgb | normal | albedo | t | hist_prev | hist_next}, the
-// colour accumulated in place; synchronous
 int crt_temporal_accumulate(crt_ctx* c, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const float* rgb,
                             const float* normal, const float* albedo, const float* t, const float* histPrev, float* histNext, float* out,
                             const crt_temporal_params* params, crt_frame_stats* stats)
 {
-    const char* what = "crt_temporal_accumulate";
-    const crt_temporal_params prm = params ? *params : kTemporalDefaults;
-    int rc = checkTemporal(c, what, w, h, camCur, camPrev, rgb, normal, albedo, t, histNext, prm);
-    if (rc) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t nn = static_cast<size_t>(w) * h;
-    const void* const host[5] = { rgb, normal, albedo, t, histPrev };
-    const size_t per[6] = { 12u, 12u, 12u, 4u, 32u, 32u };
-    size_t off[6], total = 0;
-    for (int i = 0; i < 6; i++) {
-        off[i] = total;
-        total += (i == 5 || host[i]) ? up256(nn * per[i]) : 0u;
-    }
-    if ((rc = reserveRayStage(c, total)) != CRT_OK) return rc;
-    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
-    unsigned char* dev[6];
-    for (int i = 0; i < 6; i++) dev[i] = (i == 5 || host[i]) ? base + off[i] : nullptr;
-    for (int i = 0; i < 5; i++)
-        if (host[i]) HIP_TRY(c, hipMemcpyAsync(dev[i], host[i], nn * per[i], hipMemcpyHostToDevice, c->stream));
-    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], out ? dev[0] : nullptr, prm, stats)) != CRT_OK)
-        return rc;
-    HIP_TRY(c, hipMemcpyAsync(histNext, dev[5], nn * 32u, hipMemcpyDeviceToHost, c->stream));
-    if (out) HIP_TRY(c, hipMemcpyAsync(out, dev[0], nn * 12u, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return CRT_OK;
+    return temporalHost(c, "crt_temporal_accumulate", w, h, camCur, camPrev, rgb, normal, albedo, t, histPrev, histNext, out, nullptr, params, stats);
+}
+
+int crt_temporal_accumulate_motion_device(crt_ctx* c, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const void* d_rgb,
+                                          const void* d_normal, const void* d_albedo, const void* d_t, const void* d_prevPoint,
+                                          const void* d_histPrev, void* d_histNext, void* d_out, const crt_temporal_params* params,
+                                          crt_frame_stats* stats)
+{
+    return temporalDevice(c, "crt_temporal_accumulate_motion_device", w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext,
+                          d_out, d_prevPoint, params, stats);
+}
+
+int crt_temporal_accumulate_motion(crt_ctx* c, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const float* rgb,
+                                   const float* normal, const float* albedo, const float* t, const float* prevPoint, const float* histPrev,
+                                   float* histNext, float* out, const crt_temporal_params* params, crt_frame_stats* stats)
+{
+    return temporalHost(c, "crt_temporal_accumulate_motion", w, h, camCur, camPrev, rgb, normal, albedo, t, histPrev, histNext, out, prevPoint, params,
+                        stats);
 }
 
 int crt_closest_points_device(crt_ctx* c, uint32_t n, const void* d_points, void* d_dist, void* d_point, void* d_uv, void* d_inst,
@@ -2964,6 +2998,166 @@ int crt_mesh_vertices(const crt_ctx* cc, uint32_t mesh, float* xyz, float* norma
         if (normals) HIP_TRY(c, hipMemcpyAsync(normals, c->dyn->dWorldNormals + off, bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
+    return CRT_OK;
+}
+
+// ------------------------------------------------------------------------------------------- motion (motion_kernels.hip)
+namespace {
+
+int checkMotionScene(crt_ctx* c, const char* what)
+{
+    if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
+    if (!c->haveScene || !c->dyn) return fail(c, CRT_ESTATE, "%s: no scene uploaded with option \"dynamic\" = 1", what);
+    return CRT_OK;
+}
+
+crt::PreviousPointsParams previousPointsParams(const crt_ctx* c, uint32_t n, const void* d_inst, const void* d_prim, const void* d_uv, void* d_point)
+{
+    crt::PreviousPointsParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.table = c->dyn->dTable;
+    p.nMeshes = static_cast<uint32_t>(c->dyn->meshes.size());
+    p.n = n;
+    p.world = c->dyn->dWorldXyz;
+    p.prev = c->dyn->dPrevXyz;
+    p.idx = c->dyn->dIdx;
+    p.inst = static_cast<const uint32_t*>(d_inst);
+    p.prim = static_cast<const uint32_t*>(d_prim);
+    p.uv = static_cast<const float*>(d_uv);
+    p.point = static_cast<float*>(d_point);
+    return p;
+}
+
+int runPreviousPoints(crt_ctx* c, const char* what, uint32_t n, const void* d_inst, const void* d_prim, const void* d_uv, void* d_point,
+                      crt_frame_stats* stats)
+{
+    const crt::PreviousPointsParams p = previousPointsParams(c, n, d_inst, d_prim, d_uv, d_point);
+    if (const int rc = runTimed(c, what, stats, [&] { return crt::launchPreviousPoints(p, c->stream); })) return rc;
+    if (stats) stats->rays_primary = n;
+    return CRT_OK;
+}
+
+// crt_frame_motion*: as runFrameGuides, the camera-ray kernel into the query arena, the closest-hit query over those records with
+// its uv / inst / prim beside them in the arena, then the previous points of those hits
+int runFrameMotion(crt_ctx* c, uint32_t w, uint32_t h, void* d_point, crt_frame_stats* stats)
+{
+    const uint32_t n = w * h;
+    const size_t nn = n;
+    crt::RayQueryParams q;
+    std::memset(&q, 0, sizeof(q));
+    QueryLaunch ql;
+    if (const int rc = beginQuery(c, kQueryClosestHit, n, 1u, stats, ql, up256(nn * 32u) + up256(nn * 8u) + 2u * up256(nn * 4u))) return rc;
+    unsigned char* rays = ql.extra;
+    q.uv = reinterpret_cast<float*>(rays + up256(nn * 32u));
+    q.inst = reinterpret_cast<uint32_t*>(rays + up256(nn * 32u) + up256(nn * 8u));
+    q.prim = q.inst + up256(nn * 4u) / 4u;
+    int hrc = crt::launchCameraRays(cameraRayParams(c, w, h, CRT_SAMPLE_CENTRE, rays), c->stream);
+    if (hrc == 0) {
+        q.c = queryCommon(c, ql, rays, n, c->tuneInnerMin);
+        hrc = crt::launchRayQuery(q, false, c->counting, ql.grid, c->stream);
+    }
+    if (hrc == 0) hrc = crt::launchPreviousPoints(previousPointsParams(c, n, q.inst, q.prim, q.uv, d_point), c->stream);
+    return endQuery(c, kQueryClosestHit, n, ql, hrc, stats);
+}
+
+int checkFrameMotion(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* point)
+{
+    if (const int rc = checkMotionScene(c, what)) return rc;
+    if (const int rc = checkFrameSize(c, what, w, h)) return rc;
+    if (!point) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
+    return CRT_OK;
+}
+
+} // namespace
+
+int crt_motion_snapshot(crt_ctx* c)
+{
+    const char* what = "crt_motion_snapshot";
+    int rc = checkMotionScene(c, what);
+    if (rc) return rc;
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    crt::DynamicScene& d = *c->dyn;
+    const size_t bytes = sizeof(float) * 3 * static_cast<size_t>(d.nVerts);
+    if (!d.dPrevXyz) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&d.dPrevXyz), bytes ? bytes : sizeof(float) * 3));
+    if (bytes) HIP_TRY(c, hipMemcpyAsync(d.dPrevXyz, d.dWorldXyz, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return CRT_OK;
+}
+
+int crt_previous_points_device(crt_ctx* c, uint32_t n, const void* d_inst, const void* d_prim, const void* d_uv, void* d_point, crt_frame_stats* stats)
+{
+    const char* what = "crt_previous_points_device";
+    int rc = checkMotionScene(c, what);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n == 0u) { // nothing to look at, nothing launched
+        zeroStats(stats, t0);
+        return CRT_OK;
+    }
+    if (!d_inst || !d_prim || !d_uv || !d_point) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
+    if ((rc = checkDevicePointers(c, what, { d_inst, d_prim, d_point }, 4u)) != CRT_OK) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_uv }, 8u)) != CRT_OK) return rc;
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = runPreviousPoints(c, what, n, d_inst, d_prim, d_uv, d_point, stats)) != CRT_OK) return rc;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+// host buffers: staged through the context's query staging buffer {inst | prim | uv | point}; synchronous
+int crt_previous_points(crt_ctx* c, uint32_t n, const uint32_t* inst, const uint32_t* prim, const float* uv, float* point, crt_frame_stats* stats)
+{
+    const char* what = "crt_previous_points";
+    int rc = checkMotionScene(c, what);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n == 0u) {
+        zeroStats(stats, t0);
+        return CRT_OK;
+    }
+    if (!inst || !prim || !uv || !point) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    const size_t nn = n;
+    const size_t off[4] = { 0u, up256(nn * 4u), 2u * up256(nn * 4u), 2u * up256(nn * 4u) + up256(nn * 8u) };
+    if ((rc = reserveRayStage(c, off[3] + up256(nn * 12u))) != CRT_OK) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
+    HIP_TRY(c, hipMemcpyAsync(base + off[0], inst, nn * 4u, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(base + off[1], prim, nn * 4u, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(base + off[2], uv, nn * 8u, hipMemcpyHostToDevice, c->stream));
+    if ((rc = runPreviousPoints(c, what, n, base + off[0], base + off[1], base + off[2], base + off[3], stats)) != CRT_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(point, base + off[3], nn * 12u, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+int crt_frame_motion_device(crt_ctx* c, uint32_t w, uint32_t h, void* d_prevPoint, crt_frame_stats* stats)
+{
+    const char* what = "crt_frame_motion_device";
+    int rc = checkFrameMotion(c, what, w, h, d_prevPoint);
+    if (rc) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_prevPoint }, 4u)) != CRT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    if ((rc = runFrameMotion(c, w, h, d_prevPoint, stats)) != CRT_OK) return rc;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+// host buffer: staged through the context's query staging buffer; synchronous
+int crt_frame_motion(crt_ctx* c, uint32_t w, uint32_t h, float* prevPoint, crt_frame_stats* stats)
+{
+    const char* what = "crt_frame_motion";
+    int rc = checkFrameMotion(c, what, w, h, prevPoint);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    const size_t bytes = static_cast<size_t>(w) * h * 12u;
+    if ((rc = reserveRayStage(c, bytes)) != CRT_OK) return rc;
+    if ((rc = runFrameMotion(c, w, h, c->dRayStage, stats)) != CRT_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(prevPoint, c->dRayStage, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CRT_OK;
 }
 

@@ -33,6 +33,7 @@ struct DynamicScene {
     float* dRestNormals = nullptr;    // idem (zeros for meshes without normals); NULL when no mesh has normals
     float* dWorldXyz = nullptr;
     float* dWorldNormals = nullptr;
+    float* dPrevXyz = nullptr;        // crt_motion_snapshot: dWorldXyz as it was at the last snapshot (by vertex); NULL before the first
     uint32_t* dIdx = nullptr;         // 3 per triangle, mesh-local vertex indices
     uint32_t* dLevelNodes = nullptr;  // binary inner nodes by depth: level k = dLevelNodes[levelStart[k] .. levelStart[k + 1])
     std::vector<uint32_t> levelStart;

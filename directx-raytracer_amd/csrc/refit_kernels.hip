@@ -217,7 +217,7 @@ static void applyTransforms(DynamicScene& d, ihipStream_t* stream)
 
 DynamicScene::~DynamicScene()
 {
-    void* ptrs[] = { dTable, dRestXyz, dRestNormals, dWorldXyz, dWorldNormals, dIdx, dLevelNodes, dScratch };
+    void* ptrs[] = { dTable, dRestXyz, dRestNormals, dWorldXyz, dWorldNormals, dPrevXyz, dIdx, dLevelNodes, dScratch };
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (ev0) (void)hipEventDestroy(ev0);

@@ -319,8 +319,25 @@ struct TemporalParams {
     const void* histPrev;         // null: no history
     void* histNext;
     float* out;                   // 3; may be rgb; may be null
+    const float* prevPoint;       // crt_temporal_accumulate_motion*: 3 floats per pixel, a pixel's world point in the previous frame
+                                  // (a non-finite component: not moved); null: the plain kernel
 };
 int launchTemporal(const TemporalParams& p, ihipStream_t* stream);
+// previous points of hits (motion_kernels.hip; crt_previous_points*, crt_frame_motion*): one lane per record, the triangle's
+// vertices of the last snapshot weighted by the hit's barycentrics
+struct PreviousPointsParams {
+    const void* table;            // MeshEntry per mesh + terminator (mesh_table.hip.h)
+    uint32_t nMeshes;
+    uint32_t n;                   // records
+    const float* world;           // 3 floats per vertex: the current world vertices
+    const float* prev;            // those of the last snapshot; null: none was taken, every record is "not moved"
+    const uint32_t* idx;          // 3 per triangle, mesh-local
+    const uint32_t* inst;         // per record, as the ray queries write them
+    const uint32_t* prim;
+    const float* uv;              // 2 floats per record, 8-byte aligned
+    float* point;                 // 3 floats per record
+};
+int launchPreviousPoints(const PreviousPointsParams& p, ihipStream_t* stream);
 // exhaustive check of the triangle test's reciprocal (ray_kernels.hip rcpCheckKernel) into out[0..6] (device memory, zeroed
 // except out[6] = ~0 by the caller)
 int launchRcpCheck(unsigned long long* out, ihipStream_t* stream);

@@ -266,7 +266,28 @@ void Renderer::temporalAccumulate(const float camCur[12], const float camPrev[12
           "crt_temporal_accumulate");
 }
 
-void Renderer::temporalFrame(const crt_temporal_params* params)
+void Renderer::motionSnapshot()
+{
+    if (!ctx) throw std::runtime_error("motionSnapshot before prepareForRendering");
+    check(crt_motion_snapshot(ctx), "crt_motion_snapshot");
+}
+
+void Renderer::previousPoints(const uint32_t* inst, const uint32_t* prim, const float* uv, size_t n, std::vector<float>& points)
+{
+    if (!ctx) throw std::runtime_error("previousPoints before prepareForRendering");
+    if (n > UINT32_MAX) throw std::runtime_error("previousPoints: more than 2^32 - 1 records");
+    points.resize(3 * n);
+    check(crt_previous_points(ctx, static_cast<uint32_t>(n), inst, prim, uv, points.data(), nullptr), "crt_previous_points");
+}
+
+void Renderer::frameMotion(std::vector<float>& prevPoint)
+{
+    syncView();
+    prevPoint.resize(static_cast<size_t>(width) * height * 3);
+    check(crt_frame_motion(ctx, width, height, prevPoint.data(), nullptr), "crt_frame_motion");
+}
+
+void Renderer::temporalFrame(const crt_temporal_params* params, bool motion)
 {
     const size_t n = static_cast<size_t>(width) * height;
     if (floatColour.size() != 3 * n || frame.size() != 4 * n) throw std::runtime_error("temporalFrame: no frame with float colour (setKeepFloatColour, renderFrame)");
@@ -279,8 +300,17 @@ void Renderer::temporalFrame(const crt_temporal_params* params)
     for (int k = 0; k < 9; k++) cam[3 + k] = rot.data()[k];
     const bool have = haveHistory && history[historyAt].size() == 8 * n;
     history[historyAt ^ 1].resize(8 * n);
-    temporalAccumulate(cam, have ? historyCamera : cam, floatColour.data(), g, have ? history[historyAt].data() : nullptr, history[historyAt ^ 1].data(),
-                       floatColour.data(), params);
+    if (motion) {
+        std::vector<float> prevPoint;
+        frameMotion(prevPoint);
+        check(crt_temporal_accumulate_motion(ctx, width, height, cam, have ? historyCamera : cam, floatColour.data(), g.normal.data(), g.albedo.data(),
+                                             g.t.data(), prevPoint.data(), have ? history[historyAt].data() : nullptr, history[historyAt ^ 1].data(),
+                                             floatColour.data(), params, nullptr),
+              "crt_temporal_accumulate_motion");
+    } else {
+        temporalAccumulate(cam, have ? historyCamera : cam, floatColour.data(), g, have ? history[historyAt].data() : nullptr,
+                           history[historyAt ^ 1].data(), floatColour.data(), params);
+    }
     historyAt ^= 1;
     haveHistory = true;
     for (int k = 0; k < 12; k++) historyCamera[k] = cam[k];

@@ -97,8 +97,17 @@ public:
                             float* histNext, float* out, const crt_temporal_params* params = nullptr);
     // the last frame's float colour accumulated with the history of the frames before it and quantised into getFrame().  The
     // renderer owns the two history buffers and the previous camera; a change of the frame size drops the history, and so
-    // does resetTemporal() (after geometry moved, for instance)
-    void temporalFrame(const crt_temporal_params* params = nullptr);
+    // does resetTemporal() (after a cut, or after geometry moved when temporalFrame runs without motion)
+    // motion: with the previous points of the frame (frameMotion) a moved mesh keeps its history; needs a dynamic scene and a
+    // motionSnapshot() after each frame, before the meshes are moved
+    void temporalFrame(const crt_temporal_params* params = nullptr, bool motion = false);
+    // crt_motion_snapshot: remember the current world vertices of a dynamic scene as "previous"
+    void motionSnapshot();
+    // crt_previous_points (synchronous): where the hits (inst, prim, {u, v}) were at the last snapshot, 3 floats per record, NaN for a
+    // miss and for a triangle that did not move
+    void previousPoints(const uint32_t* inst, const uint32_t* prim, const float* uv, size_t n, std::vector<float>& points);
+    // crt_frame_motion (synchronous): the previous points of the pixel-centre camera rays, width * height * 3 floats
+    void frameMotion(std::vector<float>& prevPoint);
     void resetTemporal() { haveHistory = false; }
     // every crossing of every ray, ascending in t (crt_list_hits, synchronous): the hits of ray i are hits[offsets[i]] ..
     // hits[offsets[i + 1] - 1].  One offsets-only call learns the total, a second one fills the records.

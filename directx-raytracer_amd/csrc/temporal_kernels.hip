@@ -14,6 +14,11 @@
 // Arithmetic: float32, -ffp-contract=off; fused multiply-adds only where fmaf is written (dot3, the blend); / and sqrtf are
 // correctly rounded.  Bit for bit tests/temporal_reference.c.  Nothing of the ray generation is restated: the directions are
 // rayDirJ (shading.hip.h), called as the frame kernels call it.
+//
+// The motion variant (crt_temporal_accumulate_motion*, steps 4', 5', 7' and 9') is the same kernel instantiated with MOTION:
+// a pixel whose prevPoint is finite projects that point instead of its own world point, always (the static-camera shortcut
+// becomes a per-lane select), and its plane test is taken at that point.  The choice is uniform over the launch, so the plain
+// entry point runs the instruction stream it ran before.
 #include "shading.hip.h"
 
 #include <algorithm>
@@ -27,6 +32,7 @@ constexpr uint32_t kTpMaxGrid = 1u << 20;       // workgroups of a launch; the k
 
 __device__ __forceinline__ bool finite1(float x) { return fabsf(x) <= FLT_MAX; } // false for NaN
 
+template <bool MOTION>
 __global__ __launch_bounds__(256) void temporalKernel(const TemporalParams p)
 {
     const float4* __restrict__ hist = reinterpret_cast<const float4*>(p.histPrev);
@@ -62,17 +68,32 @@ __global__ __launch_bounds__(256) void temporalKernel(const TemporalParams p)
             const F3 P = f3(oCur.x + d.x * t, oCur.y + d.y * t, oCur.z + d.z * t);
             float fx = static_cast<float>(x), fy = static_cast<float>(y);
             bool proj = live;
-            if (!p.staticCamera) {
-                const F3 v = sub3(P, oPrev);
+            F3 Pm = P;         // step 4': where the pixel's surface element was in the previous frame
+            bool moved = false;
+            if (MOTION) {
+                const F3 m = f3(p.prevPoint[3u * pi], p.prevPoint[3u * pi + 1u], p.prevPoint[3u * pi + 2u]);
+                moved = finite1(m.x) && finite1(m.y) && finite1(m.z);
+                Pm = moved ? m : P;
+            }
+            if (MOTION || !p.staticCamera) {
+                const F3 v = sub3(Pm, oPrev);
                 const float pcx = dot3(f3(p.rotPrev[0], p.rotPrev[3], p.rotPrev[6]), v);
                 const float pcy = dot3(f3(p.rotPrev[1], p.rotPrev[4], p.rotPrev[7]), v);
                 const float pcz = dot3(f3(p.rotPrev[2], p.rotPrev[5], p.rotPrev[8]), v);
                 const float s = -pcz;
                 const float sx = ((pcx / s) / (fw / fh) + 1.0f) * 0.5f * fw - 0.5f;
                 const float sy = (1.0f - pcy / s) * 0.5f * fh - 0.5f;
-                proj = proj && s > 0.0f && sx > -1.0f && sx < fw && sy > -1.0f && sy < fh; // (a NaN fails)
-                fx = proj ? sx : fx;
-                fy = proj ? sy : fy;
+                if (MOTION) { // step 7': a pixel that did not move under equal cameras keeps its own position
+                    const bool shortcut = p.staticCamera && !moved;
+                    const bool on = s > 0.0f && sx > -1.0f && sx < fw && sy > -1.0f && sy < fh; // (a NaN fails)
+                    proj = proj && (shortcut || on);
+                    fx = (proj && !shortcut) ? sx : fx;
+                    fy = (proj && !shortcut) ? sy : fy;
+                } else {
+                    proj = proj && s > 0.0f && sx > -1.0f && sx < fw && sy > -1.0f && sy < fh; // (a NaN fails)
+                    fx = proj ? sx : fx;
+                    fy = proj ? sy : fy;
+                }
             }
             // steps 8-10: the four taps
             const float x0 = floorf(fx), y0 = floorf(fy);
@@ -91,7 +112,7 @@ __global__ __launch_bounds__(256) void temporalKernel(const TemporalParams p)
                                     finite1(hg.z) && finite1(hg.w) && hc.w > 0.0f;
                 const F3 dq = rayDirJ(p.rotPrev, inside ? static_cast<uint32_t>(qx) : x, inside ? static_cast<uint32_t>(qy) : y, 0.5f, 0.5f, fw, fh);
                 const F3 Pq = f3(oPrev.x + dq.x * hg.w, oPrev.y + dq.y * hg.w, oPrev.z + dq.z * hg.w);
-                const float plane = fabsf(dot3(n, sub3(Pq, P)));
+                const float plane = fabsf(dot3(n, sub3(Pq, Pm)));
                 const float nn = dot3(n, f3(hg.x, hg.y, hg.z));
                 const bool ok = inside & usable & (plane <= limit) & (nn >= p.normalThreshold); // (a NaN fails either test)
                 const float wk = ok ? bk : 0.0f;
@@ -137,7 +158,8 @@ int launchTemporal(const TemporalParams& p, ihipStream_t* stream)
     const size_t tiles = static_cast<size_t>((p.width + kTpTileX - 1u) / kTpTileX) * ((p.height + kTpTileY - 1u) / kTpTileY);
     if (tiles == 0u) return static_cast<int>(hipSuccess);
     const dim3 g(static_cast<uint32_t>(std::min<size_t>(tiles, kTpMaxGrid))), block(256);
-    hipLaunchKernelGGL(temporalKernel, g, block, 0, stream, p);
+    if (p.prevPoint != nullptr) hipLaunchKernelGGL(temporalKernel<true>, g, block, 0, stream, p);
+    else hipLaunchKernelGGL(temporalKernel<false>, g, block, 0, stream, p);
     return static_cast<int>(hipGetLastError());
 }
 

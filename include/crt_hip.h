@@ -628,9 +628,11 @@ int crt_denoise(crt_ctx* ctx, uint32_t width, uint32_t height, const float* rgb,
  *   12. hist_next = {c_out, len_out, n_p, t_p};  out = c_out * a.
  *   alpha = 0 is the plain running mean of up to max_history frames; with alpha > 0 the mean turns into an exponential one
  *   once 1 / (len + 1) falls below alpha.  tests/temporal_reference.c restates these steps in C; the kernel equals it bit for bit.
- * - Not covered: object motion.  After crt_update_vertices, crt_set_mesh_transform, crt_refit or crt_rebuild a surface that slid
- *   within its own plane keeps stale history (the plane-distance and normal tests cannot see it): drop the history by passing
- *   d_hist_prev = NULL.  Variance estimation and second moments (SVGF) are out of scope.
+ * - Object motion is not seen by this call: after crt_update_vertices, crt_set_mesh_transform, crt_refit or crt_rebuild a surface
+ *   that slid within its own plane keeps stale history (the plane-distance and normal tests cannot see it) and one that moved
+ *   along its normal loses it.  Use crt_temporal_accumulate_motion* with the previous points of crt_frame_motion* /
+ *   crt_previous_points* (below, "motion"), or drop the history by passing d_hist_prev = NULL.  Variance estimation and second
+ *   moments (SVGF) are out of scope.
  * - Aliasing: d_out may equal d_rgb; d_hist_next must not overlap d_hist_prev; no other two buffers may overlap.  d_out may be
  *   NULL (only the history is wanted).
  * - params == NULL means the defaults.  CRT_EINVAL for a NULL context or camera; a NULL rgb, normal, t or hist_next; a NULL
@@ -804,6 +806,75 @@ int crt_refit(crt_ctx* ctx, double* device_ms /* may be NULL: HIP-event time of 
 int crt_rebuild(crt_ctx* ctx, double* device_ms /* may be NULL: HIP-event time from the first transform to the collapsed tree */);
 /* world-space vertices (and normals, may be NULL) of a mesh as they are traced, n_vertices * 3 floats each */
 int crt_mesh_vertices(const crt_ctx* ctx, uint32_t mesh, float* xyz, float* normals);
+
+/* ---- motion: where a pixel's surface element was in the previous frame, for scenes whose meshes move (DXR renderers compute
+ * motion vectors from the previous frame's instance transforms; here the previous world vertices themselves are kept, so
+ * crt_update_vertices deformations are covered too).  Dynamic scenes only (option "dynamic").  The per-frame loop:
+ *     1. render frame f;                       2. crt_motion_snapshot;
+ *     3. move the meshes (crt_update_vertices*, crt_set_mesh_transform);
+ *     4. render frame f + 1 and its guides;    5. crt_frame_motion (or crt_previous_points on ids the caller already has);
+ *     6. crt_temporal_accumulate_motion with those points.
+ * - crt_motion_snapshot applies pending refits, as the queries do, then copies the current world vertices of every mesh (12 B
+ *   per vertex) into a context-owned "previous" buffer, on the context's stream.  The buffer is allocated by the first call and
+ *   freed by the next upload or by crt_destroy; between an upload and the first snapshot there is none and every triangle counts
+ *   as "not moved".  It is indexed by vertex (topology and vertex numbering are fixed at upload), so it survives crt_refit and
+ *   crt_rebuild with either builder; crt_update_vertices* and crt_set_mesh_transform never touch it.  NULL ctx -> CRT_EINVAL; no
+ *   scene, or a scene uploaded without "dynamic" -> CRT_ESTATE.  A context that never calls it allocates nothing and behaves as
+ *   without it.
+ * - crt_previous_points*: n records of inst / prim (uint32) and uv (2 floats), exactly as crt_trace_rays*, crt_shade_rays* and
+ *   crt_list_hits* write them; point: 3 floats per record.  Let i0, i1, i2 be the triangle's mesh-local indices, q0, q1, q2 its
+ *   world vertices at the last snapshot and c0, c1, c2 its current ones (after pending refits).  The output is three quiet NaNs
+ *   (bits 0x7FC00000), "not moved / unknown", when inst == CRT_MISS, inst >= the number of meshes, prim >= that mesh's triangle
+ *   count, u or v is NaN, no snapshot exists, the nine floats of q equal the nine of c bitwise, or any component of the result is
+ *   not finite (an inert triangle).  Otherwise, per component,
+ *       point = fmaf(v, q2 - q0, fmaf(u, q1 - q0, q0))
+ *   with each difference rounded once and no other fused multiply-add: the form crt_closest_points uses for its point.
+ *   tests/motion_reference.c restates it in C; the kernel equals it bit for bit.
+ *   The results depend on the vertex buffers and the indices alone -- not on the tree, the builder, refit versus rebuild or the
+ *   order of the records.  n = 0 returns CRT_OK and launches nothing.  CRT_ESTATE without a dynamic scene.  CRT_EINVAL for a NULL
+ *   ctx or buffer or a misaligned device pointer (uv 8-byte, the rest 4-byte); these checks come before the refit.
+ *   stats (may be NULL): kernel_ms, total_ms, rays_primary = n; every other count is zero.
+ * - crt_frame_motion*: width * height * 3 floats, row-major: bit for bit crt_previous_points applied to the inst / prim / uv that
+ *   crt_trace_rays reports for the CRT_SAMPLE_CENTRE records of crt_camera_rays -- the ray whose t crt_frame_guides reports.  The
+ *   camera-ray kernel, the closest-hit query and the previous-points kernel run back to back; temporary memory: 48 B per pixel
+ *   (records, uv, inst, prim) in the context's query arena of the stream.  CRT_EINVAL as for crt_frame_guides (width or height
+ *   0, width * height > 2^28, a NULL buffer, a device pointer that is not 4-byte aligned), CRT_ESTATE without a dynamic scene;
+ *   these checks come before the refit.  Camera, mode, accumulation sums, launch orders and frame outputs are untouched.
+ *   stats: kernel_ms = the three kernels together, rays_primary = width * height; with crt_set_counting(ctx, 1) nodes_visited /
+ *   tris_tested as crt_trace_rays counts them.
+ *   The cheaper route: a caller who already has inst / prim / uv of the camera rays (crt_shade_rays on the crt_camera_rays
+ *   records gives guides and ids in one launch) calls crt_previous_points and pays no second trace.
+ * - crt_temporal_accumulate_motion*: crt_temporal_accumulate* with prev_point (3 floats per pixel, 4-byte aligned device
+ *   pointer; may be NULL).  With NULL, and with a buffer of NaNs, the result equals crt_temporal_accumulate* bit for bit.  The
+ *   contract is the twelve steps above with these changes:
+ *    4'. m = prev_point[p];  moved = all three components of m are finite;  P as in step 4;  Pm = moved ? m : P.
+ *    5'. v = Pm - o_prev.
+ *    7'. The static-camera shortcut (fx = px, fy = py, steps 5 and 6 skipped) applies to a pixel only when the cameras are equal
+ *        bitwise and the pixel is not moved.  A moved pixel always projects.
+ *    9'. The plane test is |dot(n_p, Pq - Pm)| <= depth_tolerance * t_p.  The normal test is unchanged.
+ *   Liveness, demodulation, taps, sums, blend and the history record stay as they are.
+ * - The remaining limit: history normals are the previous frame's, so a surface that rotates by more than
+ *   acos(normal_threshold) per frame drops its history (conservative).  Between two frames a surface either moved rigidly or did
+ *   not move; the plane test with n_p is exact for translations and approximate for rotations.  Previous normals and
+ *   rotation-aware tests are out of scope.
+ * *_device: asynchronous on the context's stream unless stats != NULL.  Host variants: synchronous, staged. */
+int crt_motion_snapshot(crt_ctx* ctx);
+int crt_previous_points_device(crt_ctx* ctx, uint32_t n, const void* d_inst, const void* d_prim, const void* d_uv, void* d_point,
+                               crt_frame_stats* stats);
+int crt_previous_points(crt_ctx* ctx, uint32_t n, const uint32_t* inst, const uint32_t* prim, const float* uv, float* point,
+                        crt_frame_stats* stats);
+int crt_frame_motion_device(crt_ctx* ctx, uint32_t width, uint32_t height, void* d_prev_point, crt_frame_stats* stats);
+int crt_frame_motion(crt_ctx* ctx, uint32_t width, uint32_t height, float* prev_point, crt_frame_stats* stats);
+int crt_temporal_accumulate_motion_device(crt_ctx* ctx, uint32_t width, uint32_t height, const float cam_cur[12],
+                                          const float cam_prev[12], const void* d_rgb, const void* d_normal, const void* d_albedo,
+                                          const void* d_t, const void* d_prev_point /* NULL = nothing moved */,
+                                          const void* d_hist_prev /* NULL = no history */, void* d_hist_next,
+                                          void* d_out /* may be NULL */, const crt_temporal_params* params /* NULL = defaults */,
+                                          crt_frame_stats* stats);
+int crt_temporal_accumulate_motion(crt_ctx* ctx, uint32_t width, uint32_t height, const float cam_cur[12], const float cam_prev[12],
+                                   const float* rgb, const float* normal, const float* albedo, const float* t, const float* prev_point,
+                                   const float* hist_prev, float* hist_next, float* out, const crt_temporal_params* params,
+                                   crt_frame_stats* stats);
 
 /* ---------------------------------------------------------------------------------------------------
  * Scene layer: stands in for CRTScene / CRTSceneParser / CRTCamera (kept API surface, host only, no GPU)
