@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "crt_temporal_accumulate_device", "crt_temporal_accumulate",
     "crt_motion_snapshot", "crt_previous_points_device", "crt_previous_points", "crt_frame_motion_device", "crt_frame_motion",
     "crt_temporal_accumulate_motion_device", "crt_temporal_accumulate_motion",
+    "crt_temporal_variance_device", "crt_temporal_variance", "crt_denoise_variance_device", "crt_denoise_variance",
 ]
 
 
@@ -114,6 +115,23 @@ class TemporalParams(C.Structure):
 
     def __init__(self, alpha=0.1, depth_tolerance=0.01, normal_threshold=0.9, max_history=64, demodulate=1):
         super().__init__(float(alpha), float(depth_tolerance), float(normal_threshold), int(max_history), int(demodulate))
+
+
+class TemporalVarianceParams(C.Structure):
+    """crt_temporal_variance_params: crt_temporal_params, then alpha_moments and min_history; the defaults are the header's"""
+    _fields_ = [("base", TemporalParams), ("alpha_moments", C.c_float), ("min_history", C.c_uint32)]
+
+    def __init__(self, alpha_moments=0.2, min_history=4, **base):
+        super().__init__(TemporalParams(**base), float(alpha_moments), int(min_history))
+
+
+class DenoiseVarianceParams(C.Structure):
+    """crt_denoise_variance_params; the defaults are the header's"""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("demodulate", C.c_uint32)]
+
+    def __init__(self, iterations=5, sigma_luminance=0.0625, sigma_normal=0.3, sigma_depth=0.05, demodulate=1):
+        super().__init__(int(iterations), float(sigma_luminance), float(sigma_normal), float(sigma_depth), int(demodulate))
 
 
 def build(force=False):
@@ -266,6 +284,10 @@ def lib():
         "crt_frame_motion": (C.c_int, [vp, u32, u32, vp, vp]),
         "crt_temporal_accumulate_motion_device": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "crt_temporal_accumulate_motion": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "crt_temporal_variance_device": (C.c_int, [vp, u32, u32] + [vp] * 15),
+        "crt_temporal_variance": (C.c_int, [vp, u32, u32] + [vp] * 15),
+        "crt_denoise_variance_device": (C.c_int, [vp, u32, u32] + [vp] * 9),
+        "crt_denoise_variance": (C.c_int, [vp, u32, u32] + [vp] * 9),
     }
     assert set(sig) == set(ABI_SYMBOLS)
     for name, (res, args) in sig.items():
@@ -549,12 +571,16 @@ class Scene:
 
 class TemporalHistory:
     """Frame-to-frame state of Renderer.temporal_accumulate_device: two torch CUDA history buffers of (h, w, 8) float32 that swap
-    every push, and the camera of the last push.  The renderer's context keeps none of it."""
+    every push, and the camera of the last push.  The renderer's context keeps none of it.  With variance=True the pushes go
+    through Renderer.temporal_variance_device: two (h, w, 2) moment buffers swap beside the history buffers, .variance is the
+    (h, w) variance of the last push, and params may hold alpha_moments and min_history too."""
 
-    def __init__(self, renderer, width, height, **params):
+    def __init__(self, renderer, width, height, variance=False, **params):
         import torch
         self.renderer, self.w, self.h, self.params = renderer, int(width), int(height), params
         self.hist = [torch.zeros((self.h, self.w, 8), dtype=torch.float32, device="cuda") for _ in range(2)]
+        self.mom = [torch.zeros((self.h, self.w, 2), dtype=torch.float32, device="cuda") for _ in range(2)] if variance else None
+        self.variance = torch.zeros((self.h, self.w), dtype=torch.float32, device="cuda") if variance else None
         self.at = 0          # hist[at] holds the previous frame's records
         self.camera = None   # the camera of the previous push; None = no history
 
@@ -583,10 +609,17 @@ class TemporalHistory:
         out = torch.empty((self.h, self.w, 3), dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()  # torch fills its tensors on its own stream
         have = self.camera is not None
-        self.renderer.temporal_accumulate_device(self.w, self.h, cam, self.camera if have else cam, dev[0].data_ptr(), dev[1].data_ptr(),
-                                                 dev[2].data_ptr(), dev[3].data_ptr(), self.hist[self.at].data_ptr() if have else None,
-                                                 self.hist[self.at ^ 1].data_ptr(), out.data_ptr(),
-                                                 d_prev_point=None if prev_point is None else dev[4].data_ptr(), **self.params)
+        if self.mom is not None:
+            self.renderer.temporal_variance_device(self.w, self.h, cam, self.camera if have else cam, dev[0].data_ptr(), dev[1].data_ptr(),
+                                                   dev[2].data_ptr(), dev[3].data_ptr(), self.hist[self.at].data_ptr() if have else None,
+                                                   self.hist[self.at ^ 1].data_ptr(), self.mom[self.at].data_ptr() if have else None,
+                                                   self.mom[self.at ^ 1].data_ptr(), self.variance.data_ptr(), out.data_ptr(),
+                                                   d_prev_point=None if prev_point is None else dev[4].data_ptr(), **self.params)
+        else:
+            self.renderer.temporal_accumulate_device(self.w, self.h, cam, self.camera if have else cam, dev[0].data_ptr(), dev[1].data_ptr(),
+                                                     dev[2].data_ptr(), dev[3].data_ptr(), self.hist[self.at].data_ptr() if have else None,
+                                                     self.hist[self.at ^ 1].data_ptr(), out.data_ptr(),
+                                                     d_prev_point=None if prev_point is None else dev[4].data_ptr(), **self.params)
         self.renderer.synchronize()
         self.at ^= 1
         self.camera = cam
@@ -596,6 +629,11 @@ class TemporalHistory:
     def records(self):
         """the history records of the last push, (h, w, 8) torch CUDA tensor {c.rgb, len, n.xyz, t}"""
         return self.hist[self.at]
+
+    @property
+    def moments(self):
+        """the luminance moments of the last push, (h, w, 2) torch CUDA tensor {m1, m2}; None without variance=True"""
+        return None if self.mom is None else self.mom[self.at]
 
 
 def _mesh_views(meshes, keep):
@@ -1098,6 +1136,86 @@ class Renderer:
         self._ok(lib().crt_temporal_accumulate_device(self.h, int(w), int(h), cc.ctypes.data, cp.ctypes.data, d_rgb, d_normal, d_albedo, d_t,
                                                       d_hist_prev, d_hist_next, d_out, C.byref(prm), C.byref(st) if stats else None),
                  "crt_temporal_accumulate_device")
+        return st.as_dict() if stats else None
+
+    # ---- variance (include/crt_hip.h): luminance moments beside the history, and the filter their variance steers
+    def temporal_variance(self, cam_cur, cam_prev, rgb, normal, albedo, t, hist_prev=None, mom_prev=None, want_out=True, prev_point=None,
+                          **params):
+        """temporal_accumulate with luminance moments (host buffers, synchronous): mom_prev None or the (h, w, 2) float32 moments
+        an earlier call returned, given exactly when hist_prev is.  params: the fields of TemporalVarianceParams (TemporalParams'
+        and alpha_moments, min_history).  Returns (hist_next, mom_next, variance, out): (h, w, 8), (h, w, 2), (h, w) and the
+        accumulated (h, w, 3) image (None when not want_out)."""
+        t = np.ascontiguousarray(t, dtype=np.float32)
+        if t.ndim != 2:
+            raise ValueError("t must be (h, w)")
+        h, w = t.shape
+        bufs = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (rgb, normal, albedo, prev_point)]
+        for a in bufs:
+            if a is not None and a.shape != (h, w, 3):
+                raise ValueError("rgb, normal, albedo and prev_point must be (h, w, 3) where t is (h, w)")
+        hp = None if hist_prev is None else np.ascontiguousarray(hist_prev, dtype=np.float32)
+        if hp is not None and hp.shape != (h, w, 8):
+            raise ValueError("hist_prev must be (h, w, 8)")
+        mp = None if mom_prev is None else np.ascontiguousarray(mom_prev, dtype=np.float32)
+        if mp is not None and mp.shape != (h, w, 2):
+            raise ValueError("mom_prev must be (h, w, 2)")
+        cc, cp = _f32(cam_cur, 12), _f32(cam_prev, 12)
+        hist = np.zeros((h, w, 8), dtype=np.float32)
+        mom = np.zeros((h, w, 2), dtype=np.float32)
+        var = np.zeros((h, w), dtype=np.float32)
+        out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
+
+        def p(a):
+            return None if a is None else a.ctypes.data
+        prm = TemporalVarianceParams(**params)
+        self._ok(lib().crt_temporal_variance(self.h, w, h, cc.ctypes.data, cp.ctypes.data, p(bufs[0]), p(bufs[1]), p(bufs[2]), t.ctypes.data,
+                                             p(bufs[3]), p(hp), hist.ctypes.data, p(mp), mom.ctypes.data, var.ctypes.data, p(out),
+                                             C.byref(prm), None), "crt_temporal_variance")
+        return hist, mom, var, out
+
+    def temporal_variance_device(self, w, h, cam_cur, cam_prev, d_rgb, d_normal, d_albedo, d_t, d_hist_prev, d_hist_next, d_mom_prev,
+                                 d_mom_next, d_variance, d_out=None, stats=False, d_prev_point=None, **params):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); the cameras are host arrays of 12 floats; d_hist_prev and
+        d_mom_prev None = no history; d_out may equal d_rgb or be None; d_prev_point: None, or the previous points of the frame;
+        asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        cc, cp = _f32(cam_cur, 12), _f32(cam_prev, 12)
+        prm = TemporalVarianceParams(**params)
+        self._ok(lib().crt_temporal_variance_device(self.h, int(w), int(h), cc.ctypes.data, cp.ctypes.data, d_rgb, d_normal, d_albedo, d_t,
+                                                    d_prev_point, d_hist_prev, d_hist_next, d_mom_prev, d_mom_next, d_variance, d_out,
+                                                    C.byref(prm), C.byref(st) if stats else None), "crt_temporal_variance_device")
+        return st.as_dict() if stats else None
+
+    def denoise_variance(self, rgb, normal, albedo, t, variance, want_variance=False, **params):
+        """the a-trous filter with a variance-driven luminance weight (host buffers, synchronous): denoise's buffers and the
+        (h, w) float32 variance of temporal_variance.  params: the fields of DenoiseVarianceParams; demodulate must be the
+        temporal call's.  Returns the filtered (h, w, 3) float32 image, with want_variance (image, filtered variance)."""
+        t = np.ascontiguousarray(t, dtype=np.float32)
+        if t.ndim != 2:
+            raise ValueError("t must be (h, w)")
+        h, w = t.shape
+        bufs = [np.ascontiguousarray(a, dtype=np.float32) for a in (rgb, normal, albedo)]
+        for a in bufs:
+            if a.shape != (h, w, 3):
+                raise ValueError("rgb, normal and albedo must be (h, w, 3) where t is (h, w)")
+        var = np.ascontiguousarray(variance, dtype=np.float32)
+        if var.shape != (h, w):
+            raise ValueError("variance must be (h, w)")
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        vout = np.zeros((h, w), dtype=np.float32) if want_variance else None
+        prm = DenoiseVarianceParams(**params)
+        self._ok(lib().crt_denoise_variance(self.h, w, h, bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data, t.ctypes.data,
+                                            var.ctypes.data, out.ctypes.data, None if vout is None else vout.ctypes.data, C.byref(prm), None),
+                 "crt_denoise_variance")
+        return (out, vout) if want_variance else out
+
+    def denoise_variance_device(self, w, h, d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, d_variance_out=None, stats=False, **params):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); d_out may equal d_rgb, d_variance_out may equal d_variance
+        or be None; asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        prm = DenoiseVarianceParams(**params)
+        self._ok(lib().crt_denoise_variance_device(self.h, int(w), int(h), d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, d_variance_out,
+                                                   C.byref(prm), C.byref(st) if stats else None), "crt_denoise_variance_device")
         return st.as_dict() if stats else None
 
     # ---- motion (include/crt_hip.h): previous positions of hits on a dynamic scene whose meshes move

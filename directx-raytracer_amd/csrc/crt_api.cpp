@@ -2326,9 +2326,18 @@ int checkTemporal(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const fl
     return CRT_OK;
 }
 
+// crt_temporal_variance*: the moment buffers and parameters beside the history's
+struct TemporalMoments {
+    const void* prev;
+    void* next;
+    void* variance;
+    float alphaMoments;
+    uint32_t minHistory;
+};
+
 int runTemporal(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const void* d_rgb,
                 const void* d_normal, const void* d_albedo, const void* d_t, const void* d_histPrev, void* d_histNext, void* d_out,
-                const void* d_prevPoint, const crt_temporal_params& prm, crt_frame_stats* stats)
+                const void* d_prevPoint, const crt_temporal_params& prm, crt_frame_stats* stats, const TemporalMoments* moments = nullptr)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     crt::TemporalParams p;
@@ -2353,6 +2362,13 @@ int runTemporal(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const floa
     p.histNext = d_histNext;
     p.out = static_cast<float*>(d_out);
     p.prevPoint = static_cast<const float*>(d_prevPoint);
+    if (moments) {
+        p.momPrev = moments->prev;
+        p.momNext = moments->next;
+        p.variance = static_cast<float*>(moments->variance);
+        p.alphaMoments = moments->alphaMoments;
+        p.minHistory = static_cast<float>(moments->minHistory);
+    }
     return runTimed(c, what, stats, [&] { return crt::launchTemporal(p, c->stream); });
 }
 
@@ -2440,6 +2456,184 @@ int crt_temporal_accumulate_motion(crt_ctx* c, uint32_t w, uint32_t h, const flo
 {
     return temporalHost(c, "crt_temporal_accumulate_motion", w, h, camCur, camPrev, rgb, normal, albedo, t, histPrev, histNext, out, prevPoint, params,
                         stats);
+}
+
+namespace {
+
+// ---- variance: luminance moments in the temporal pass, a variance-guided filter (temporal_kernels.hip, variance_kernels.hip)
+const crt_temporal_variance_params kTemporalVarianceDefaults = { { 0.1f, 0.01f, 0.9f, 64u, 1u }, 0.2f, 4u };
+const crt_denoise_variance_params kDenoiseVarianceDefaults = { 5u, 0.0625f, 0.3f, 0.05f, 1u };
+
+int checkTemporalVariance(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const void* rgb,
+                          const void* normal, const void* albedo, const void* t, const void* histPrev, const void* histNext, const void* momPrev,
+                          const void* momNext, const void* variance, const crt_temporal_variance_params& prm)
+{
+    if (const int rc = checkTemporal(c, what, w, h, camCur, camPrev, rgb, normal, albedo, t, histNext, prm.base)) return rc;
+    if (!(prm.alpha_moments >= 0.0f && prm.alpha_moments <= 1.0f))
+        return fail(c, CRT_EINVAL, "%s: alpha_moments = %g is outside [0, 1]", what, static_cast<double>(prm.alpha_moments));
+    if (prm.min_history < 1u || prm.min_history > (1u << 24))
+        return fail(c, CRT_EINVAL, "%s: min_history = %u is outside 1..2^24", what, prm.min_history);
+    if (!momNext || !variance) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
+    if ((histPrev == nullptr) != (momPrev == nullptr))
+        return fail(c, CRT_EINVAL, "%s: hist_prev and mom_prev must be given together or not at all", what);
+    return CRT_OK;
+}
+
+int checkDenoiseVariance(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* rgb, const void* normal, const void* albedo,
+                         const void* t, const void* variance, const void* out, const crt_denoise_variance_params& prm)
+{
+    const crt_denoise_params plain = { prm.iterations, prm.sigma_luminance, prm.sigma_normal, prm.sigma_depth, prm.demodulate };
+    if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
+    if (!(prm.sigma_luminance > 0.0f))
+        return fail(c, CRT_EINVAL, "%s: sigma_luminance = %g must be > 0 (+inf switches the term off)", what, static_cast<double>(prm.sigma_luminance));
+    if (const int rc = checkDenoise(c, what, w, h, rgb, normal, albedo, t, out, plain)) return rc;
+    if (!variance) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
+    return CRT_OK;
+}
+
+int runDenoiseVariance(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* d_rgb, const void* d_normal, const void* d_albedo,
+                       const void* d_t, const void* d_variance, void* d_out, void* d_varianceOut, const crt_denoise_variance_params& prm,
+                       crt_frame_stats* stats)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t plane = up256(static_cast<size_t>(w) * h * 16u);
+    crt_ctx::RayArena* arena = nullptr;
+    if (const int rc = takeArena(c, 3u * plane, true, arena)) return rc;
+    crt::DenoiseVarianceParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.width = w;
+    p.height = h;
+    p.iterations = prm.iterations;
+    p.demodulate = prm.demodulate;
+    p.sigma_luminance = prm.sigma_luminance;
+    p.inv_sigma_normal2 = invSquare(prm.sigma_normal);
+    p.sigma_depth = prm.sigma_depth;
+    p.rgb = static_cast<const float*>(d_rgb);
+    p.normal = static_cast<const float*>(d_normal);
+    p.albedo = static_cast<const float*>(d_albedo);
+    p.t = static_cast<const float*>(d_t);
+    p.variance = static_cast<const float*>(d_variance);
+    p.out = static_cast<float*>(d_out);
+    p.varianceOut = static_cast<float*>(d_varianceOut);
+    p.guide = arena->mem;
+    p.colour[0] = arena->mem + plane;
+    p.colour[1] = arena->mem + 2u * plane;
+    // (the arena's last use is recorded before a timed call synchronises)
+    return runTimed(c, what, stats, [&] {
+        const int hrc = crt::launchDenoiseVariance(p, c->stream);
+        if (hrc != 0) return hrc;
+        arena->pending = true;
+        return static_cast<int>(hipEventRecord(arena->lastUse, c->stream));
+    });
+}
+
+} // namespace
+
+int crt_temporal_variance_device(crt_ctx* c, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const void* d_rgb,
+                                 const void* d_normal, const void* d_albedo, const void* d_t, const void* d_prevPoint, const void* d_histPrev,
+                                 void* d_histNext, const void* d_momPrev, void* d_momNext, void* d_variance, void* d_out,
+                                 const crt_temporal_variance_params* params, crt_frame_stats* stats)
+{
+    const char* what = "crt_temporal_variance_device";
+    const crt_temporal_variance_params prm = params ? *params : kTemporalVarianceDefaults;
+    int rc = checkTemporalVariance(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext, d_momPrev, d_momNext,
+                                   d_variance, prm);
+    if (rc) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_out, d_prevPoint, d_variance }, 4u)) != CRT_OK) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_momPrev, d_momNext }, 8u)) != CRT_OK) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_histPrev, d_histNext }, 16u)) != CRT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const TemporalMoments moments = { d_momPrev, d_momNext, d_variance, prm.alpha_moments, prm.min_history };
+    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext, d_out, d_prevPoint, prm.base, stats,
+                          &moments)) != CRT_OK)
+        return rc;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+// host buffers: staged through the context's query staging buffer {rgb | normal | albedo | t | hist_prev | hist_next | prev_point |
+// mom_prev | mom_next | variance}, the colour accumulated in place; synchronous
+int crt_temporal_variance(crt_ctx* c, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const float* rgb, const float* normal,
+                          const float* albedo, const float* t, const float* prevPoint, const float* histPrev, float* histNext,
+                          const float* momPrev, float* momNext, float* variance, float* out, const crt_temporal_variance_params* params,
+                          crt_frame_stats* stats)
+{
+    const char* what = "crt_temporal_variance";
+    const crt_temporal_variance_params prm = params ? *params : kTemporalVarianceDefaults;
+    int rc = checkTemporalVariance(c, what, w, h, camCur, camPrev, rgb, normal, albedo, t, histPrev, histNext, momPrev, momNext, variance, prm);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t nn = static_cast<size_t>(w) * h;
+    constexpr int kBuffers = 10, kHistNext = 5, kMomNext = 8, kVariance = 9;
+    const void* const host[kBuffers] = { rgb, normal, albedo, t, histPrev, nullptr, prevPoint, momPrev, nullptr, nullptr };
+    const size_t per[kBuffers] = { 12u, 12u, 12u, 4u, 32u, 32u, 12u, 8u, 8u, 4u };
+    size_t off[kBuffers], total = 0;
+    unsigned char* dev[kBuffers];
+    for (int i = 0; i < kBuffers; i++) {
+        off[i] = total;
+        total += (i == kHistNext || i >= kMomNext || host[i]) ? up256(nn * per[i]) : 0u;
+    }
+    if ((rc = reserveRayStage(c, total)) != CRT_OK) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
+    for (int i = 0; i < kBuffers; i++) dev[i] = (i == kHistNext || i >= kMomNext || host[i]) ? base + off[i] : nullptr;
+    for (int i = 0; i < kBuffers; i++)
+        if (host[i]) HIP_TRY(c, hipMemcpyAsync(dev[i], host[i], nn * per[i], hipMemcpyHostToDevice, c->stream));
+    const TemporalMoments moments = { dev[7], dev[kMomNext], dev[kVariance], prm.alpha_moments, prm.min_history };
+    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, dev[0], dev[1], dev[2], dev[3], dev[4], dev[kHistNext], out ? dev[0] : nullptr, dev[6],
+                          prm.base, stats, &moments)) != CRT_OK)
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(histNext, dev[kHistNext], nn * 32u, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(momNext, dev[kMomNext], nn * 8u, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(variance, dev[kVariance], nn * 4u, hipMemcpyDeviceToHost, c->stream));
+    if (out) HIP_TRY(c, hipMemcpyAsync(out, dev[0], nn * 12u, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+int crt_denoise_variance_device(crt_ctx* c, uint32_t w, uint32_t h, const void* d_rgb, const void* d_normal, const void* d_albedo, const void* d_t,
+                                const void* d_variance, void* d_out, void* d_varianceOut, const crt_denoise_variance_params* params,
+                                crt_frame_stats* stats)
+{
+    const char* what = "crt_denoise_variance_device";
+    const crt_denoise_variance_params prm = params ? *params : kDenoiseVarianceDefaults;
+    int rc = checkDenoiseVariance(c, what, w, h, d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, prm);
+    if (rc) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, d_varianceOut }, 4u)) != CRT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = runDenoiseVariance(c, what, w, h, d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, d_varianceOut, prm, stats)) != CRT_OK) return rc;
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
+}
+
+// host buffers: staged through the context's query staging buffer {rgb | normal | albedo | t | variance}, filtered in place; synchronous
+int crt_denoise_variance(crt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const float* normal, const float* albedo, const float* t,
+                         const float* variance, float* out, float* varianceOut, const crt_denoise_variance_params* params, crt_frame_stats* stats)
+{
+    const char* what = "crt_denoise_variance";
+    const crt_denoise_variance_params prm = params ? *params : kDenoiseVarianceDefaults;
+    int rc = checkDenoiseVariance(c, what, w, h, rgb, normal, albedo, t, variance, out, prm);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t nn = static_cast<size_t>(w) * h;
+    const void* const host[5] = { rgb, normal, albedo, t, variance };
+    const size_t per[5] = { 12u, 12u, 12u, 4u, 4u };
+    size_t off[5], total = 0;
+    for (int i = 0; i < 5; i++) {
+        off[i] = total;
+        total += up256(nn * per[i]);
+    }
+    if ((rc = reserveRayStage(c, total)) != CRT_OK) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
+    for (int i = 0; i < 5; i++) HIP_TRY(c, hipMemcpyAsync(base + off[i], host[i], nn * per[i], hipMemcpyHostToDevice, c->stream));
+    if ((rc = runDenoiseVariance(c, what, w, h, base + off[0], base + off[1], base + off[2], base + off[3], base + off[4], base + off[0],
+                                 varianceOut ? base + off[4] : nullptr, prm, stats)) != CRT_OK)
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(out, base + off[0], nn * 12u, hipMemcpyDeviceToHost, c->stream));
+    if (varianceOut) HIP_TRY(c, hipMemcpyAsync(varianceOut, base + off[4], nn * 4u, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return CRT_OK;
 }
 
 int crt_closest_points_device(crt_ctx* c, uint32_t n, const void* d_points, void* d_dist, void* d_point, void* d_uv, void* d_inst,

@@ -52,6 +52,9 @@ static void usage()
                  "                                         fixed seed every frame would draw the same per-pixel random numbers and there would\n"
                  "                                         be nothing to average.  --denoise then filters the accumulated last frame; not with\n"
                  "                                         --ranks\n"
+                 "   [--variance]                          with --temporal: the frames carry luminance moments beside the history and give a\n"
+                 "                                         per-pixel variance (crt_temporal_variance); --denoise then filters the last frame\n"
+                 "                                         with a luminance weight that follows that variance (crt_denoise_variance)\n"
                  "   [--ranks N [--device-base D] [--id-file PATH]]   N processes / GPUs, RCCL gather per frame\n"
                  "   [--host-exchange [--same-device]]   with --ranks: tiles through shared host memory instead of RCCL; --same-device puts every\n"
                  "                                       rank on --device (a rehearsal of the multi-rank path on one GPU)\n");
@@ -67,7 +70,7 @@ struct Args {
     float orbit = 0.f, pitch = 0.f, forward = 0.f, right = 0.f, zoom = 0.f;
     bool count = false, png = false, hostExchange = false, sameDevice = false, denoise = false;
     int denoiseIterations = 5;
-    bool temporal = false;
+    bool temporal = false, variance = false;
     float temporalAlpha = 0.1f;
     unsigned long long nonce = 0; // names the launch in the id file (set by the --ranks parent)
     std::map<int, uint32_t> modeAt;
@@ -149,12 +152,21 @@ int runRank(const Args& a)
         if (a.count) std::printf(", nodes %llu, tris %llu, shadow rays %llu", (unsigned long long)st.nodes_visited,
                                  (unsigned long long)st.tris_tested, (unsigned long long)st.rays_shadow);
         std::printf("\n");
-        if (a.temporal) {
+        if (a.temporal && a.variance) {
+            const crt_temporal_variance_params prm = { { a.temporalAlpha, 0.01f, 0.9f, 64u, 1u }, 0.2f, 4u };
+            renderer.temporalVarianceFrame(&prm);
+            std::printf("frame %d: accumulated over the camera move with luminance moments, alpha %g\n", f, static_cast<double>(a.temporalAlpha));
+            if (a.denoise && f == a.frames - 1) {
+                const crt_denoise_variance_params dprm = { static_cast<uint32_t>(a.denoiseIterations), 0.0625f, 0.3f, 0.05f, 1u };
+                renderer.denoiseVarianceFrame(&dprm);
+                std::printf("frame %d: denoised with its variance, %d passes\n", f, a.denoiseIterations);
+            }
+        } else if (a.temporal) {
             const crt_temporal_params prm = { a.temporalAlpha, 0.01f, 0.9f, 64u, 1u };
             renderer.temporalFrame(&prm);
             std::printf("frame %d: accumulated over the camera move, alpha %g\n", f, static_cast<double>(a.temporalAlpha));
         }
-        if (a.denoise && f == a.frames - 1) {
+        if (a.denoise && !a.variance && f == a.frames - 1) {
             crt_denoise_params prm = { static_cast<uint32_t>(a.denoiseIterations), 4.0f, 0.3f, 0.05f, 1u };
             renderer.denoiseFrame(&prm);
             std::printf("frame %d: denoised, %d passes\n", f, a.denoiseIterations);
@@ -293,6 +305,7 @@ int main(int argc, char** argv)
         else if (s == "--denoise") a.denoise = true;
         else if (s == "--denoise-iterations") a.denoiseIterations = std::atoi(next("--denoise-iterations"));
         else if (s == "--temporal") a.temporal = true;
+        else if (s == "--variance") a.variance = true;
         else if (s == "--temporal-alpha") a.temporalAlpha = static_cast<float>(std::atof(next("--temporal-alpha")));
         else if (s == "--host-exchange") a.hostExchange = true;
         else if (s == "--same-device") a.sameDevice = true;
@@ -306,6 +319,7 @@ int main(int argc, char** argv)
     if (a.frames < 1 || a.ranks < 0 || a.ranks > 64) { usage(); return 2; }
     if (a.denoise && (a.ranks > 0 || a.denoiseIterations < 1 || a.denoiseIterations > 8)) { usage(); return 2; }
     if (a.temporal && (a.ranks > 0 || a.mode != 200u || !a.modeAt.empty() || !(a.temporalAlpha >= 0.0f && a.temporalAlpha <= 1.0f))) { usage(); return 2; }
+    if (a.variance && !a.temporal) { usage(); return 2; }
     try {
         if (a.ranks > 0 && a.rank < 0) return launchRanks(a, argc, argv);
         if (a.ranks > 0 && (a.rank >= a.ranks || a.idFile.empty())) { usage(); return 2; }

@@ -321,8 +321,37 @@ struct TemporalParams {
     float* out;                   // 3; may be rgb; may be null
     const float* prevPoint;       // crt_temporal_accumulate_motion*: 3 floats per pixel, a pixel's world point in the previous frame
                                   // (a non-finite component: not moved); null: the plain kernel
+    // crt_temporal_variance*: luminance moments {m1, m2}, 2 floats per pixel, beside the history; all null: the kernels above
+    const void* momPrev;          // null exactly when histPrev is
+    void* momNext;
+    float* variance;              // 1 float per pixel
+    float alphaMoments;
+    float minHistory;             // 1 .. 2^24, exact as a float
 };
 int launchTemporal(const TemporalParams& p, ihipStream_t* stream);
+// step V6 of crt_temporal_variance* (variance_kernels.hip): the variance from the records launchTemporal wrote; launchTemporal
+// calls it when momNext is set
+int launchTemporalVariance(const TemporalParams& p, ihipStream_t* stream);
+// the variance-guided a-trous filter (variance_kernels.hip; crt_denoise_variance*).  Scratch as for DenoiseParams: the guide
+// plane {n.xyz, t} and two colour planes {c.rgb, v}, v < 0: not live
+struct DenoiseVarianceParams {
+    uint32_t width, height;
+    uint32_t iterations;          // 1..8
+    uint32_t demodulate;          // 0 / 1
+    float sigma_luminance;        // as given (+inf switches the term off)
+    float inv_sigma_normal2;      // 1 / sigma_normal^2
+    float sigma_depth;            // as given (+inf switches the term off)
+    const float* rgb;             // 3 floats per pixel
+    const float* normal;          // 3
+    const float* albedo;          // 3
+    const float* t;               // 1
+    const float* variance;        // 1
+    float* out;                   // 3; may be rgb
+    float* varianceOut;           // 1; may be variance; may be null
+    void* guide;                  // scratch planes, 16 bytes per pixel each
+    void* colour[2];
+};
+int launchDenoiseVariance(const DenoiseVarianceParams& p, ihipStream_t* stream);
 // previous points of hits (motion_kernels.hip; crt_previous_points*, crt_frame_motion*): one lane per record, the triangle's
 // vertices of the last snapshot weighted by the hit's barycentrics
 struct PreviousPointsParams {

@@ -313,8 +313,79 @@ void Renderer::temporalFrame(const crt_temporal_params* params, bool motion)
     }
     historyAt ^= 1;
     haveHistory = true;
+    haveMoments = false;
     for (int k = 0; k < 12; k++) historyCamera[k] = cam[k];
     quantiseFloatColour();
+}
+
+void Renderer::temporalVariance(const float camCur[12], const float camPrev[12], const float* rgb, const Guides& guides, const float* prevPoint,
+                                const float* histPrev, float* histNext, const float* momPrev, float* momNext, float* varianceOut, float* out,
+                                const crt_temporal_variance_params* params)
+{
+    if (!ctx) throw std::runtime_error("temporalVariance before prepareForRendering");
+    const size_t n = static_cast<size_t>(width) * height;
+    if (guides.normal.size() != 3 * n || guides.albedo.size() != 3 * n || guides.t.size() != n)
+        throw std::runtime_error("temporalVariance: the guides are not of the current frame size");
+    check(crt_temporal_variance(ctx, width, height, camCur, camPrev, rgb, guides.normal.data(), guides.albedo.data(), guides.t.data(), prevPoint,
+                                histPrev, histNext, momPrev, momNext, varianceOut, out, params, nullptr),
+          "crt_temporal_variance");
+}
+
+void Renderer::denoiseVariance(const float* rgb, const Guides& guides, const float* varianceIn, float* out, float* varianceOut,
+                               const crt_denoise_variance_params* params)
+{
+    if (!ctx) throw std::runtime_error("denoiseVariance before prepareForRendering");
+    const size_t n = static_cast<size_t>(width) * height;
+    if (guides.normal.size() != 3 * n || guides.albedo.size() != 3 * n || guides.t.size() != n)
+        throw std::runtime_error("denoiseVariance: the guides are not of the current frame size");
+    check(crt_denoise_variance(ctx, width, height, rgb, guides.normal.data(), guides.albedo.data(), guides.t.data(), varianceIn, out, varianceOut,
+                               params, nullptr),
+          "crt_denoise_variance");
+}
+
+void Renderer::temporalVarianceFrame(const crt_temporal_variance_params* params, bool motion)
+{
+    const size_t n = static_cast<size_t>(width) * height;
+    if (floatColour.size() != 3 * n || frame.size() != 4 * n)
+        throw std::runtime_error("temporalVarianceFrame: no frame with float colour (setKeepFloatColour, renderFrame)");
+    Guides g;
+    frameGuides(g);
+    float cam[12];
+    const auto pos = scene->getCamera().getPosition();
+    const auto rot = scene->getCamera().getRotationMatrix();
+    for (int k = 0; k < 3; k++) cam[k] = pos.data()[k];
+    for (int k = 0; k < 9; k++) cam[3 + k] = rot.data()[k];
+    const bool have = haveHistory && haveMoments && history[historyAt].size() == 8 * n && moments[historyAt].size() == 2 * n;
+    history[historyAt ^ 1].resize(8 * n);
+    moments[historyAt ^ 1].resize(2 * n);
+    variance.resize(n);
+    std::vector<float> prevPoint;
+    if (motion) frameMotion(prevPoint);
+    temporalVariance(cam, have ? historyCamera : cam, floatColour.data(), g, motion ? prevPoint.data() : nullptr,
+                     have ? history[historyAt].data() : nullptr, history[historyAt ^ 1].data(), have ? moments[historyAt].data() : nullptr,
+                     moments[historyAt ^ 1].data(), variance.data(), floatColour.data(), params);
+    historyAt ^= 1;
+    haveHistory = true;
+    haveMoments = true;
+    for (int k = 0; k < 12; k++) historyCamera[k] = cam[k];
+    quantiseFloatColour();
+}
+
+void Renderer::denoiseVarianceFrame(const crt_denoise_variance_params* params)
+{
+    const size_t n = static_cast<size_t>(width) * height;
+    if (floatColour.size() != 3 * n || frame.size() != 4 * n || variance.size() != n)
+        throw std::runtime_error("denoiseVarianceFrame: no frame with a variance (temporalVarianceFrame)");
+    Guides g;
+    frameGuides(g);
+    denoiseVariance(floatColour.data(), g, variance.data(), floatColour.data(), nullptr, params);
+    quantiseFloatColour();
+}
+
+void Renderer::varianceFrame(const crt_temporal_variance_params* temporalParams, const crt_denoise_variance_params* denoiseParams, bool motion)
+{
+    temporalVarianceFrame(temporalParams, motion);
+    denoiseVarianceFrame(denoiseParams);
 }
 
 void Renderer::listHits(const float* rays, size_t n, std::vector<uint64_t>& offsets, std::vector<RayHit>& hits)

@@ -109,6 +109,27 @@ public:
     // crt_frame_motion (synchronous): the previous points of the pixel-centre camera rays, width * height * 3 floats
     void frameMotion(std::vector<float>& prevPoint);
     void resetTemporal() { haveHistory = false; }
+    // temporalAccumulate with luminance moments (crt_temporal_variance, synchronous): momPrev / momNext hold 2 floats per pixel
+    // beside the history records (momPrev is nullptr exactly when histPrev is), variance receives 1 float per pixel; prevPoint:
+    // nullptr, or the previous points of the frame (frameMotion)
+    void temporalVariance(const float camCur[12], const float camPrev[12], const float* rgb, const Guides& guides, const float* prevPoint,
+                          const float* histPrev, float* histNext, const float* momPrev, float* momNext, float* variance, float* out,
+                          const crt_temporal_variance_params* params = nullptr);
+    // denoise with a variance-driven luminance weight (crt_denoise_variance, synchronous): variance as temporalVariance wrote it,
+    // varianceOut (may be variance, may be nullptr) the filtered variance
+    void denoiseVariance(const float* rgb, const Guides& guides, const float* variance, float* out, float* varianceOut = nullptr,
+                         const crt_denoise_variance_params* params = nullptr);
+    // temporalFrame() through crt_temporal_variance: the renderer owns two moment buffers beside the history buffers and keeps
+    // the frame's variance (getVariance()) for denoiseVarianceFrame().  A temporalFrame() in between drops the moments, and the
+    // history with them
+    void temporalVarianceFrame(const crt_temporal_variance_params* params = nullptr, bool motion = false);
+    const std::vector<float>& getVariance() const { return variance; }
+    // the accumulated colour of the last temporalVarianceFrame() filtered with its variance and quantised into getFrame(); the
+    // history keeps the unfiltered colour
+    void denoiseVarianceFrame(const crt_denoise_variance_params* params = nullptr);
+    // both: the last frame accumulated with moments, then filtered with the variance into getFrame()
+    void varianceFrame(const crt_temporal_variance_params* temporalParams = nullptr, const crt_denoise_variance_params* denoiseParams = nullptr,
+                       bool motion = false);
     // every crossing of every ray, ascending in t (crt_list_hits, synchronous): the hits of ray i are hits[offsets[i]] ..
     // hits[offsets[i + 1] - 1].  One offsets-only call learns the total, a second one fills the records.
     void listHits(const float* rays, size_t n, std::vector<uint64_t>& offsets, std::vector<RayHit>& hits);
@@ -147,6 +168,9 @@ private:
     int historyAt = 0;
     bool haveHistory = false;
     float historyCamera[12] = {};
+    std::vector<float> moments[2]; // temporalVarianceFrame(): moments[historyAt] belongs to history[historyAt]
+    bool haveMoments = false;
+    std::vector<float> variance;   // of the last temporalVarianceFrame()
     void quantiseFloatColour(); // floatColour into frame with the frames' own UNORM rule
     void syncView(); // a pending mode change and the scene's camera, as renderFrame() applies them
     crt_frame_stats stats{};

@@ -19,6 +19,11 @@
 // a pixel whose prevPoint is finite projects that point instead of its own world point, always (the static-camera shortcut
 // becomes a per-lane select), and its plane test is taken at that point.  The choice is uniform over the launch, so the plain
 // entry point runs the instruction stream it ran before.
+//
+// The variance variant (crt_temporal_variance*, steps V1 to V5; section 5j) is the same kernel instantiated with MOMENTS: a tap
+// grows by one 8-byte load, the luminance moments {m1, m2} of its record, which ride on the tap's weight.  Again uniform over
+// the launch: the instantiations without MOMENTS compile to what they were.  Step V6, the variance itself, reads the records
+// this kernel wrote for a pixel's neighbours and is a kernel of its own (variance_kernels.hip), launched behind this one.
 #include "shading.hip.h"
 
 #include <algorithm>
@@ -32,11 +37,13 @@ constexpr uint32_t kTpMaxGrid = 1u << 20;       // workgroups of a launch; the k
 
 __device__ __forceinline__ bool finite1(float x) { return fabsf(x) <= FLT_MAX; } // false for NaN
 
-template <bool MOTION>
+template <bool MOTION, bool MOMENTS>
 __global__ __launch_bounds__(256) void temporalKernel(const TemporalParams p)
 {
     const float4* __restrict__ hist = reinterpret_cast<const float4*>(p.histPrev);
     float4* __restrict__ next = reinterpret_cast<float4*>(p.histNext);
+    const float2* __restrict__ mom = reinterpret_cast<const float2*>(p.momPrev); // null exactly when hist is
+    float2* __restrict__ momNext = reinterpret_cast<float2*>(p.momNext);
     const float fw = static_cast<float>(p.width), fh = static_cast<float>(p.height);
     const uint32_t tilesX = (p.width + kTpTileX - 1u) / kTpTileX, tilesY = (p.height + kTpTileY - 1u) / kTpTileY;
     const uint32_t nTiles = tilesX * tilesY; // < 2^28 for width * height <= 2^28
@@ -62,6 +69,13 @@ __global__ __launch_bounds__(256) void temporalKernel(const TemporalParams p)
         }
         const float cr = r / ar, cg = g / ag, cb = b / ab;
         float outR = cr, outG = cg, outB = cb, outLen = 1.0f; // a live pixel without history
+        float m1 = 0.0f, m2 = 0.0f, lum = 0.0f, lum2 = 0.0f;
+        if (MOMENTS) { // step V1
+            lum = fmaf(0.0722f, cb, fmaf(0.7152f, cg, 0.2126f * cr));
+            lum2 = lum * lum;
+            m1 = lum;
+            m2 = lum2;
+        }
         if (hist != nullptr) {
             // steps 4-7: where the pixel's world point was on the previous frame's screen
             const F3 d = rayDirJ(p.rotCur, x, y, 0.5f, 0.5f, fw, fh);
@@ -100,7 +114,7 @@ __global__ __launch_bounds__(256) void temporalKernel(const TemporalParams p)
             const float wx = fx - x0, wy = fy - y0;
             const int ix = static_cast<int>(x0), iy = static_cast<int>(y0); // -1 .. width - 1, -1 .. height - 1
             const float limit = p.depthTolerance * t;
-            float W = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sl = 0.0f;
+            float W = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sl = 0.0f, sm1 = 0.0f, sm2 = 0.0f;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const int qx = ix + (k & 1), qy = iy + (k >> 1);
@@ -108,8 +122,13 @@ __global__ __launch_bounds__(256) void temporalKernel(const TemporalParams p)
                 const bool inside = proj & (static_cast<uint32_t>(qx) < p.width) & (static_cast<uint32_t>(qy) < p.height);
                 const size_t qi = inside ? static_cast<size_t>(qy) * p.width + static_cast<size_t>(qx) : pi;
                 const float4 hc = hist[2u * qi], hg = hist[2u * qi + 1u];
-                const bool usable = finite1(hc.x) && finite1(hc.y) && finite1(hc.z) && finite1(hc.w) && finite1(hg.x) && finite1(hg.y) &&
-                                    finite1(hg.z) && finite1(hg.w) && hc.w > 0.0f;
+                bool usable = finite1(hc.x) && finite1(hc.y) && finite1(hc.z) && finite1(hc.w) && finite1(hg.x) && finite1(hg.y) &&
+                              finite1(hg.z) && finite1(hg.w) && hc.w > 0.0f;
+                float2 mq = make_float2(0.0f, 0.0f);
+                if (MOMENTS) { // step V3
+                    mq = mom[qi];
+                    usable = usable && finite1(mq.x) && finite1(mq.y);
+                }
                 const F3 dq = rayDirJ(p.rotPrev, inside ? static_cast<uint32_t>(qx) : x, inside ? static_cast<uint32_t>(qy) : y, 0.5f, 0.5f, fw, fh);
                 const F3 Pq = f3(oPrev.x + dq.x * hg.w, oPrev.y + dq.y * hg.w, oPrev.z + dq.z * hg.w);
                 const float plane = fabsf(dot3(n, sub3(Pq, Pm)));
@@ -121,6 +140,10 @@ __global__ __launch_bounds__(256) void temporalKernel(const TemporalParams p)
                 sg = sg + wk * (ok ? hc.y : 0.0f);
                 sb = sb + wk * (ok ? hc.z : 0.0f);
                 sl = sl + wk * (ok ? hc.w : 0.0f);
+                if (MOMENTS) { // step V4
+                    sm1 = sm1 + wk * (ok ? mq.x : 0.0f);
+                    sm2 = sm2 + wk * (ok ? mq.y : 0.0f);
+                }
             }
             if (W >= 0.01f) { // step 11
                 const float hr = sr / W, hgn = sg / W, hb = sb / W, L = sl / W;
@@ -129,6 +152,12 @@ __global__ __launch_bounds__(256) void temporalKernel(const TemporalParams p)
                 outG = fmaf(at, cg - hgn, hgn);
                 outB = fmaf(at, cb - hb, hb);
                 outLen = fminf(L + 1.0f, p.maxHistory);
+                if (MOMENTS) { // step V5
+                    const float am = fmaxf(p.alphaMoments, 1.0f / (L + 1.0f));
+                    const float h1 = sm1 / W, h2 = sm2 / W;
+                    m1 = fmaf(am, lum - h1, h1);
+                    m2 = fmaf(am, lum2 - h2, h2);
+                }
             }
         }
         if (live) {
@@ -143,6 +172,7 @@ __global__ __launch_bounds__(256) void temporalKernel(const TemporalParams p)
             outB = b;
         }
         next[2u * pi + 1u] = make_float4(n.x, n.y, n.z, t);
+        if (MOMENTS) momNext[pi] = live ? make_float2(m1, m2) : make_float2(0.0f, 0.0f); // step V2
         if (p.out != nullptr) {
             p.out[3u * pi] = outR;
             p.out[3u * pi + 1u] = outG;
@@ -158,8 +188,14 @@ int launchTemporal(const TemporalParams& p, ihipStream_t* stream)
     const size_t tiles = static_cast<size_t>((p.width + kTpTileX - 1u) / kTpTileX) * ((p.height + kTpTileY - 1u) / kTpTileY);
     if (tiles == 0u) return static_cast<int>(hipSuccess);
     const dim3 g(static_cast<uint32_t>(std::min<size_t>(tiles, kTpMaxGrid))), block(256);
-    if (p.prevPoint != nullptr) hipLaunchKernelGGL(temporalKernel<true>, g, block, 0, stream, p);
-    else hipLaunchKernelGGL(temporalKernel<false>, g, block, 0, stream, p);
+    if (p.momNext != nullptr) {
+        if (p.prevPoint != nullptr) hipLaunchKernelGGL((temporalKernel<true, true>), g, block, 0, stream, p);
+        else hipLaunchKernelGGL((temporalKernel<false, true>), g, block, 0, stream, p);
+        if (const hipError_t e = hipGetLastError()) return static_cast<int>(e);
+        return launchTemporalVariance(p, stream); // step V6, behind the records it reads
+    }
+    if (p.prevPoint != nullptr) hipLaunchKernelGGL((temporalKernel<true, false>), g, block, 0, stream, p);
+    else hipLaunchKernelGGL((temporalKernel<false, false>), g, block, 0, stream, p);
     return static_cast<int>(hipGetLastError());
 }
 

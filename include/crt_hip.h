@@ -632,7 +632,7 @@ int crt_denoise(crt_ctx* ctx, uint32_t width, uint32_t height, const float* rgb,
  *   that slid within its own plane keeps stale history (the plane-distance and normal tests cannot see it) and one that moved
  *   along its normal loses it.  Use crt_temporal_accumulate_motion* with the previous points of crt_frame_motion* /
  *   crt_previous_points* (below, "motion"), or drop the history by passing d_hist_prev = NULL.  Variance estimation and second
- *   moments (SVGF) are out of scope.
+ *   moments (SVGF) are crt_temporal_variance* (below, "variance").
  * - Aliasing: d_out may equal d_rgb; d_hist_next must not overlap d_hist_prev; no other two buffers may overlap.  d_out may be
  *   NULL (only the history is wanted).
  * - params == NULL means the defaults.  CRT_EINVAL for a NULL context or camera; a NULL rgb, normal, t or hist_next; a NULL
@@ -875,6 +875,91 @@ int crt_temporal_accumulate_motion(crt_ctx* ctx, uint32_t width, uint32_t height
                                    const float* rgb, const float* normal, const float* albedo, const float* t, const float* prev_point,
                                    const float* hist_prev, float* hist_next, float* out, const crt_temporal_params* params,
                                    crt_frame_stats* stats);
+
+/* ---- variance: luminance moments carried with the history, a per-pixel variance from them, and the a-trous filter with a colour
+ * weight that follows that variance (Schied et al. 2017, "Spatiotemporal Variance-Guided Filtering").  The filter's weight is wide
+ * where the estimate is noisy (short history, disocclusion, frame edges) and closes where the history has converged.
+ * - crt_temporal_variance*: crt_temporal_accumulate_motion* plus three buffers.  mom_prev / mom_next: 2 floats {m1, m2} per
+ *   pixel (8-byte aligned on the device), the running mean of the luminance and of its square; the caller owns two such buffers
+ *   and swaps them with the history buffers.  mom_prev is NULL exactly when hist_prev is.  variance: 1 float per pixel (4-byte
+ *   aligned).  prev_point may be NULL.  The context keeps no state.  The contract is the twelve steps of crt_temporal_accumulate,
+ *   with 4', 5', 7' and 9' when prev_point is given, and these; the arithmetic rules are the same:
+ *    V1. For a live pixel, with c of step 2:  l = fmaf(0.0722, c.b, fmaf(0.7152, c.g, 0.2126 * c.r));  q = l * l.
+ *    V2. A pixel that is not live: mom_next = {0, 0}, variance = 0.
+ *    V3. Step 9 gains a condition: a tap is valid only if m1 and m2 of its mom_prev record are finite.  When every moment
+ *        record is finite, hist_next and out equal crt_temporal_accumulate_motion* on the same inputs bit for bit.
+ *    V4. Step 10 gains SM1 = sum b_k * m1_q and SM2 = sum b_k * m2_q (a product, then a sum), over the same valid taps in the
+ *        same order, each starting at 0.
+ *    V5. With history (step 11's condition): a_m = max(alpha_moments, 1 / (L + 1));  h1 = SM1 / W, h2 = SM2 / W;
+ *        m1 = fmaf(a_m, l - h1, h1), m2 = fmaf(a_m, q - h2, h2).  Without: m1 = l, m2 = q.  mom_next = {m1, m2}.
+ *    V6. The variance, a second pass over the records V1 to V5 and step 12 wrote.  For a live pixel p with len = hist_next[p].len:
+ *        len >= min_history:  variance = fmaxf(m2 - m1 * m1, 0) (a product, then a difference).
+ *        Otherwise a spatial estimate over the 7 x 7 window around p, dy = -3..3 outer, dx = -3..3 inner, the centre included.
+ *        The centre always counts.  Another tap q counts when it is inside the image, hist_next[q].len > 0, the 8 floats of
+ *        hist_next[q] and the 2 of mom_next[q] are finite, |dot(n_p, Pq - P)| <= depth_tolerance * t_p with Pq = o_cur +
+ *        dir(rot_cur, qx, qy) * t_q and P of step 4, and dot(n_p, n_q) >= normal_threshold.  N = the number of counted taps as
+ *        a float, A1 = sum m1_q, A2 = sum m2_q in tap order from 0, M1 = A1 / N, M2 = A2 / N.
+ *        variance = fmaxf(M2 - M1 * M1, 0) * ((float)min_history / len).
+ *        The value is written as computed: a luminance that overflowed shows.
+ *   tests/variance_reference.c restates all of it in C; the kernels equal it bit for bit.
+ *   Aliasing: d_out may equal d_rgb; d_hist_next must not overlap d_hist_prev nor d_mom_next d_mom_prev; no other two buffers
+ *   may overlap.  CRT_EINVAL as for crt_temporal_accumulate_motion*, and for alpha_moments outside [0, 1] or NaN; min_history
+ *   outside 1..2^24; a NULL mom_next or variance; exactly one of hist_prev and mom_prev NULL; a misaligned device pointer
+ *   (history: 16-byte, moments: 8-byte, the rest: 4-byte).  A failed call launches nothing and writes nothing.
+ *   Two kernels, no scratch memory, no atomics: the same input gives the same bits.
+ * - crt_denoise_variance*: crt_denoise* with variance (1 float per pixel) as a further input and variance_out (1 float per
+ *   pixel; may be NULL) as a further output.  The variance is that of the luminance of the colour that is filtered: demodulate
+ *   must be what the crt_temporal_variance call that made it was given.
+ *     Live: crt_denoise's rule, and variance finite and >= 0.  A pixel that is not live is copied rgb -> out and variance ->
+ *       variance_out bit for bit and is never a tap.
+ *     Start: a and c_0 as in crt_denoise;  v_0 = variance;  lum(c) as l in V1.
+ *     Pass i = 0 .. iterations - 1, stride s = 2^i, for a live centre p:
+ *       g_p = the 3 x 3 mean of v_i at stride 1 whatever s, weights (1/4, 1/2, 1/4) x (1/4, 1/2, 1/4), over the taps inside the
+ *             image and live, divided by the sum of the weights used
+ *       d_p = sigma_luminance * sqrt(g_p) + 1e-4
+ *       for the 25 taps of crt_denoise (inside the image and live):
+ *         e = |lum(c_i(p)) - lum(c_i(q))| / d_p + |n_p - n_q|^2 / sigma_normal^2 + ((t_p - t_q) / (sigma_depth t_p))^2
+ *         w = h[dx + 2] h[dy + 2] exp(-e)
+ *       c_{i+1}(p) = sum w c_i(q) / sum w        v_{i+1}(p) = sum w^2 v_i(q) / (sum w)^2
+ *       sigma_luminance is not halved: the variance shrinks by itself every pass.
+ *     Output: out = c_N a;  variance_out = v_N.
+ *   Float32 throughout; no bit-for-bit contract against a CPU form (exp).  What holds: crt_denoise's deviation bound against a
+ *   float64 evaluation, for out and variance_out (tests/test_variance.py); determinism; host form = device form = in-place form
+ *   bit for bit.  Aliasing: d_out may equal d_rgb, d_variance_out may equal d_variance; no other two buffers may overlap.
+ *   CRT_EINVAL as for crt_denoise (sigma_luminance in sigma_color's place: > 0, +inf switches the term off) and for a NULL
+ *   variance.  Scratch as for crt_denoise: 48 B per pixel, the guide plane {n, t} and two colour planes {c, v}.
+ * Both: params == NULL means the defaults; stats (may be NULL): kernel_ms, total_ms, every count zero; no scene is needed; the
+ * context's camera, mode, accumulation sums, launch orders and frame outputs are untouched.
+ * *_device: asynchronous on the context's stream unless stats != NULL.  Host variants: synchronous, staged. */
+typedef struct crt_temporal_variance_params {
+    crt_temporal_params base;
+    float alpha_moments;   /* default 0.2: least weight of the new frame's luminance moments */
+    uint32_t min_history;  /* default 4, 1..2^24: below this history length the variance is the spatial estimate */
+} crt_temporal_variance_params;
+typedef struct crt_denoise_variance_params {
+    uint32_t iterations;    /* 1..8, default 5: pass i samples at stride 2^i */
+    float sigma_luminance;  /* default 0.0625: luminance differences are measured in this many standard deviations */
+    float sigma_normal;     /* default 0.3 */
+    float sigma_depth;      /* default 0.05, relative to the centre pixel's t */
+    uint32_t demodulate;    /* default 1; must match the crt_temporal_variance call's */
+} crt_denoise_variance_params;
+int crt_temporal_variance_device(crt_ctx* ctx, uint32_t width, uint32_t height, const float cam_cur[12], const float cam_prev[12],
+                                 const void* d_rgb, const void* d_normal, const void* d_albedo, const void* d_t,
+                                 const void* d_prev_point /* NULL = nothing moved */, const void* d_hist_prev /* NULL = no history */,
+                                 void* d_hist_next, const void* d_mom_prev /* NULL with d_hist_prev */, void* d_mom_next,
+                                 void* d_variance, void* d_out /* may be NULL */,
+                                 const crt_temporal_variance_params* params /* NULL = defaults */, crt_frame_stats* stats);
+int crt_temporal_variance(crt_ctx* ctx, uint32_t width, uint32_t height, const float cam_cur[12], const float cam_prev[12],
+                          const float* rgb, const float* normal, const float* albedo, const float* t, const float* prev_point,
+                          const float* hist_prev, float* hist_next, const float* mom_prev, float* mom_next, float* variance,
+                          float* out, const crt_temporal_variance_params* params, crt_frame_stats* stats);
+int crt_denoise_variance_device(crt_ctx* ctx, uint32_t width, uint32_t height, const void* d_rgb, const void* d_normal,
+                                const void* d_albedo, const void* d_t, const void* d_variance, void* d_out,
+                                void* d_variance_out /* may be NULL */, const crt_denoise_variance_params* params /* NULL = defaults */,
+                                crt_frame_stats* stats);
+int crt_denoise_variance(crt_ctx* ctx, uint32_t width, uint32_t height, const float* rgb, const float* normal, const float* albedo,
+                         const float* t, const float* variance, float* out, float* variance_out,
+                         const crt_denoise_variance_params* params, crt_frame_stats* stats);
 
 /* ---------------------------------------------------------------------------------------------------
  * Scene layer: stands in for CRTScene / CRTSceneParser / CRTCamera (kept API surface, host only, no GPU)
