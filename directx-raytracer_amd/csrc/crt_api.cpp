@@ -151,18 +151,20 @@ struct crt_ctx {
     unsigned long long* dCounters = nullptr;
     int* dSpill[kRing] = {};          // traversal-stack spill arenas (traversal.hip.h Stack), one per ring slot
     size_t spillBytes[kRing] = {};
-    // mode 200: scratch of the persistent path kernel (one region per RESIDENT workgroup + the launch's work counter).  An arena
-    // belongs to the stream that last used it: frames issued on one stream run one after the other and share ONE arena; only
-    // frames on different streams (up to kRing in flight) get arenas of their own.
-    struct PathArena {
+    // Scratch that belongs to the stream that last used it: calls issued on one stream run one after the other and share ONE
+    // arena; only calls on different streams (up to kRing in flight) get arenas of their own (takeArena).
+    struct Arena {
         unsigned char* mem = nullptr;
         size_t bytes = 0;
         hipStream_t stream = nullptr;
         bool used = false;       // `stream` is meaningful
         hipEvent_t lastUse = nullptr;
         bool pending = false;    // lastUse recorded
-        uint32_t serial = 0;     // frameSerial of the last use (least recently used arena is taken over by a new stream)
-    } pathArena[kRing];
+        uint32_t serial = 0;     // of the last use (the least recently used arena is taken over by a new stream)
+    };
+    // mode 200: scratch of the persistent path kernel (one region per RESIDENT workgroup + the launch's work counter); serial =
+    // frameSerial.  A pool of the frames' own: frames and queries never share an arena
+    Arena pathArena[kRing];
     unsigned long long* dTimeline = nullptr; // diagnostic: 3 words per workgroup, counting variant only
     size_t timelineWords = 0;
     bool wantTimeline = false;
@@ -203,18 +205,9 @@ struct crt_ctx {
     bool accumPending = false;
 
     // batched ray and point queries (crt_trace_rays* / crt_occluded_rays*, crt_closest_points* / crt_count_hits* /
-    // crt_occupancy*): per arena the launch's cursor, counters and the stack spill arena of the persistent query kernel.  Arenas belong to queries alone (never to a frame) and, like the path arenas, to the
-    // stream that last used one: queries on one stream run one after the other and share an arena, queries on different streams
-    // (up to kRing in flight) get arenas of their own.
-    struct RayArena {
-        unsigned char* mem = nullptr;
-        size_t bytes = 0;
-        hipStream_t stream = nullptr;
-        bool used = false;
-        hipEvent_t lastUse = nullptr;
-        bool pending = false;
-        uint32_t serial = 0;
-    } rayArena[kRing];
+    // crt_occupancy*): per arena the launch's cursor, counters and the stack spill arena of the persistent query kernel.  Arenas
+    // of this pool belong to queries alone (never to a frame); serial = ++raySerial.
+    Arena rayArena[kRing];
     uint32_t raySerial = 0;
     uint32_t rayResident[8] = {};        // resident workgroups of each query kernel (QueryKind) on this device ...
     uint32_t rayResidentEntries[8] = {}; // ... for this many LDS stack entries
@@ -295,6 +288,119 @@ int regrow(crt_ctx* c, void*& p, size_t used, size_t bytes)
     }
     if (p) (void)hipFree(p);
     p = q;
+    return CRT_OK;
+}
+
+// (ensureBuffer, reserveRayStage and takeArena keep C names: a helper defined below the header's extern "C" has one even in this
+// unnamed namespace and so stands in the library's dynamic symbol table, these three since they were written; new helpers down
+// there are static instead)
+extern "C" {
+
+// A device buffer of at least `need` bytes; one that grows keeps nothing of its contents.  Work in flight on any stream may still
+// use the old buffer, hence the device-wide wait.  ownScratch: the buffer is scratch the call keeps for itself; an allocation
+// failure is then CRT_ENOMEM (no HIP error left behind), and the caller words the message
+int ensureBuffer(crt_ctx* c, void** ptr, size_t* have, size_t need, bool ownScratch = false)
+{
+    if (*have >= need) return CRT_OK;
+    HIP_TRY(c, hipDeviceSynchronize());
+    if (*ptr) (void)hipFree(*ptr);
+    *ptr = nullptr;
+    *have = 0;
+    if (!ownScratch) HIP_TRY(c, hipMalloc(ptr, need));
+    else if (hipMalloc(ptr, need) != hipSuccess) {
+        (void)hipGetLastError();
+        *ptr = nullptr;
+        return CRT_ENOMEM;
+    }
+    *have = need;
+    return CRT_OK;
+}
+
+// The arena of `pool` for a call on the context's stream, grown to `need` bytes and stamped with `serial`: the arena this stream
+// used last; else an unused one; else the least recently used one of another stream, once the call that used it last is done.
+// ownScratch: as ensureBuffer
+int takeArena(crt_ctx* c, crt_ctx::Arena (&pool)[crt_ctx::kRing], size_t need, uint32_t serial, bool ownScratch, crt_ctx::Arena*& out)
+{
+    crt_ctx::Arena* arena = nullptr;
+    for (auto& a : pool)
+        if (a.used && a.stream == c->stream) arena = &a;
+    if (!arena) {
+        for (auto& a : pool)
+            if (!arena || (!a.used && arena->used) || (a.used == arena->used && a.serial < arena->serial)) arena = &a;
+        if (arena->pending && hipEventQuery(arena->lastUse) != hipSuccess) HIP_TRY(c, hipStreamWaitEvent(c->stream, arena->lastUse, 0));
+        arena->stream = c->stream;
+        arena->used = true;
+    }
+    const int rc = ensureBuffer(c, reinterpret_cast<void**>(&arena->mem), &arena->bytes, need, ownScratch);
+    if (rc == CRT_ENOMEM) return fail(c, CRT_ENOMEM, "query scratch: %zu bytes of device memory not available", need);
+    if (rc) return rc;
+    if (!arena->lastUse) HIP_TRY(c, hipEventCreateWithFlags(&arena->lastUse, hipEventDisableTiming));
+    arena->serial = serial;
+    out = arena;
+    return CRT_OK;
+}
+
+// the staging buffer of the host forms, grown to `total` bytes
+int reserveRayStage(crt_ctx* c, size_t total)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    return ensureBuffer(c, &c->dRayStage, &c->rayStageBytes, total);
+}
+
+} // extern "C"
+
+inline size_t up256(size_t b) { return (b + 255u) & ~static_cast<size_t>(255u); }
+
+void stampTotal(crt_frame_stats* stats, std::chrono::steady_clock::time_point t0)
+{
+    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// ---- Host staging.  A host form is its device form run over the context's staging buffer (dRayStage): the caller lists the
+// call's buffers as planes, stageBegin lays them out in list order, each on a 256-byte boundary, grows the buffer, hands back
+// the device pointers and enqueues the uploads; after the run stageEnd enqueues the downloads, in list order, and waits for
+// the stream.  The pointers hold until the next host form on the context plans its own layout, so a host form is synchronous
+// and none of them outlives the call.
+struct StagePlane {
+    const void* src; // host data the run reads, uploaded before it; NULL = none
+    void* dst;       // host buffer the plane is downloaded into after the run; NULL = none
+    size_t bytes;
+    int over = -1;   // >= 0: the room of that earlier plane, none of its own: a result written in place, downloaded at this place
+};
+
+// dev[i] = NULL for a plane that takes no room: one with neither src nor dst (an optional buffer the caller left out)
+int stageBegin(crt_ctx* c, const StagePlane* planes, int n, void** dev)
+{
+    size_t total = 0;
+    for (int i = 0; i < n; i++)
+        if (planes[i].over < 0 && (planes[i].src || planes[i].dst)) total += up256(planes[i].bytes);
+    if (const int rc = reserveRayStage(c, total)) return rc;
+    unsigned char* at = static_cast<unsigned char*>(c->dRayStage);
+    for (int i = 0; i < n; i++) {
+        const StagePlane& pl = planes[i];
+        dev[i] = nullptr;
+        if (pl.over >= 0) dev[i] = pl.dst ? dev[pl.over] : nullptr;
+        else if (pl.src || pl.dst) {
+            dev[i] = at;
+            at += up256(pl.bytes);
+        }
+    }
+    for (int i = 0; i < n; i++)
+        if (planes[i].src) HIP_TRY(c, hipMemcpyAsync(dev[i], planes[i].src, planes[i].bytes, hipMemcpyHostToDevice, c->stream));
+    return CRT_OK;
+}
+
+int stageDownload(crt_ctx* c, const StagePlane* planes, int n, void* const* dev)
+{
+    for (int i = 0; i < n; i++)
+        if (planes[i].dst) HIP_TRY(c, hipMemcpyAsync(planes[i].dst, dev[i], planes[i].bytes, hipMemcpyDeviceToHost, c->stream));
+    return CRT_OK;
+}
+
+int stageEnd(crt_ctx* c, const StagePlane* planes, int n, void* const* dev)
+{
+    if (const int rc = stageDownload(c, planes, n, dev)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return CRT_OK;
 }
 
@@ -435,6 +541,22 @@ void fillParams(const crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_
     p.units_per_frame = crt::renderUnitCount(p);
 }
 
+// the scene's shading tables as the shaded and the path-traced query take them (crt::ShadeQueryParams, crt::PathQueryParams)
+template <class Q> void sceneTables(const crt_ctx* c, Q& q)
+{
+    q.shade = c->dShade; // as fillParams
+    q.lights = c->dLights;
+    q.mats = c->dMats;
+    q.uvs = c->dUvs;
+    q.textures = c->dTextures;
+    q.texels = static_cast<const unsigned char*>(c->dTexels);
+    q.n_textures = c->nTextures;
+    q.n_lights = c->nLights;
+    q.n_mats = c->nMats;
+    crt::copyBytes(q.miss, c->miss, sizeof(q.miss));
+    q.inner_min_any = c->tuneInnerMinAny;
+}
+
 // a frame that uses the sums runs after the last one that did, even when issued on another stream (crt_set_stream)
 int orderAccum(crt_ctx* c)
 {
@@ -486,17 +608,10 @@ int runRender(crt_ctx* c, RenderParams& p, crt_frame_stats* stats)
         const size_t groups = p.mode >= 200u ? static_cast<size_t>(crt::pathGridSize(p))
                                              : (static_cast<size_t>(crt::renderUnitCount(p)) + 16u * std::min(c->tuneSplitUnits == crt_ctx::kSplitAuto ? 128u : c->tuneSplitUnits, crt::renderUnitCount(p) / 4u)) * p.n_batch;
         const size_t need = groups * 64u * p.spill_stride * sizeof(int);
-        if (c->spillBytes[slot] < need) {
-            HIP_TRY(c, hipDeviceSynchronize());
-            if (c->dSpill[slot]) (void)hipFree(c->dSpill[slot]);
-            c->dSpill[slot] = nullptr;
-            c->spillBytes[slot] = 0;
-            HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->dSpill[slot]), need));
-            c->spillBytes[slot] = need;
-        }
+        if (const int rc = ensureBuffer(c, reinterpret_cast<void**>(&c->dSpill[slot]), &c->spillBytes[slot], need)) return rc;
         p.spill = c->dSpill[slot];
     }
-    crt_ctx::PathArena* arena = nullptr;
+    crt_ctx::Arena* arena = nullptr;
     if (p.mode >= 200u) {
         // path tracing: resident wavefronts stream the paths of one pixel tile after the other through private queues in HBM.  One
         // 8x8 packet x up to 16 samples per work item (256 paths at 4 spp) measured best at every frame size -- 6.6 vs 10.1 ms on C3
@@ -514,26 +629,7 @@ int runRender(crt_ctx* c, RenderParams& p, crt_frame_stats* stats)
             crt::pathWavefrontLayout(p, wfItems, p.wf_chunk, p.wf_stride);
         }
         const size_t need = p.path_wavefront ? crt::pathWavefrontBytes(p, wfItems) : kHead + static_cast<size_t>(crt::pathGridSize(p)) * p.path_region_bytes;
-        // the arena this stream used last; else an unused one; else the least recently used one of another stream
-        for (auto& a : c->pathArena)
-            if (a.used && a.stream == c->stream) arena = &a;
-        if (!arena) {
-            for (auto& a : c->pathArena)
-                if (!arena || (!a.used && arena->used) || (a.used == arena->used && a.serial < arena->serial)) arena = &a;
-            if (arena->pending && hipEventQuery(arena->lastUse) != hipSuccess) HIP_TRY(c, hipStreamWaitEvent(c->stream, arena->lastUse, 0));
-            arena->stream = c->stream;
-            arena->used = true;
-        }
-        if (arena->bytes < need) {
-            HIP_TRY(c, hipDeviceSynchronize());
-            if (arena->mem) (void)hipFree(arena->mem);
-            arena->mem = nullptr;
-            arena->bytes = 0;
-            HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&arena->mem), need));
-            arena->bytes = need;
-        }
-        if (!arena->lastUse) HIP_TRY(c, hipEventCreateWithFlags(&arena->lastUse, hipEventDisableTiming));
-        arena->serial = c->frameSerial;
+        if (const int rc = takeArena(c, c->pathArena, need, c->frameSerial, false, arena)) return rc;
         if (p.path_wavefront) {
             const size_t plane = static_cast<size_t>(p.wf_paths) * 16u, qplane = static_cast<size_t>(p.wf_stride) * 16u; // one float4 per path / queue entry
             unsigned char* at = arena->mem;
@@ -700,12 +796,7 @@ int beginAccum(crt_ctx* c, RenderParams& p, uint32_t kind)
     const size_t need = outputs * 4u * sizeof(double); // float64 sums {x, y}, {z, 0} (path_kernels.hip loadSum)
     if (c->accumBytes < need) { // (a larger frame: the key has changed, nothing in the old sums is kept)
         HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipDeviceSynchronize()); // frames of other streams may still use the old buffer
-        if (c->dAccum) (void)hipFree(c->dAccum);
-        c->dAccum = nullptr;
-        c->accumBytes = 0;
-        HIP_TRY(c, hipMalloc(&c->dAccum, need));
-        c->accumBytes = need;
+        if (const int rc = ensureBuffer(c, &c->dAccum, &c->accumBytes, need)) return rc;
     }
     const uint32_t traced = std::min(p.spp, c->accMax - c->accSamples);
     p.acc_sum = c->dAccum;
@@ -827,8 +918,10 @@ void crt_destroy(crt_ctx* c)
     if (c->dTexels) (void)hipFree(c->dTexels);
     for (int i = 0; i < crt_ctx::kRing; i++) {
         if (c->dSpill[i]) (void)hipFree(c->dSpill[i]);
-        if (c->pathArena[i].mem) (void)hipFree(c->pathArena[i].mem);
-        if (c->pathArena[i].lastUse) (void)hipEventDestroy(c->pathArena[i].lastUse);
+        for (crt_ctx::Arena* a : { &c->pathArena[i], &c->rayArena[i] }) {
+            if (a->mem) (void)hipFree(a->mem);
+            if (a->lastUse) (void)hipEventDestroy(a->lastUse);
+        }
     }
     if (c->sideStream) (void)hipStreamSynchronize(c->sideStream);
     for (int i = 0; i < crt_ctx::kRing; i++) {
@@ -841,10 +934,6 @@ void crt_destroy(crt_ctx* c)
     if (c->dTimeline) (void)hipFree(c->dTimeline);
     if (c->dAccum) (void)hipFree(c->dAccum);
     if (c->evAccum) (void)hipEventDestroy(c->evAccum);
-    for (int i = 0; i < crt_ctx::kRing; i++) {
-        if (c->rayArena[i].mem) (void)hipFree(c->rayArena[i].mem);
-        if (c->rayArena[i].lastUse) (void)hipEventDestroy(c->rayArena[i].lastUse);
-    }
     if (c->dRayStage) (void)hipFree(c->dRayStage);
     if (c->dListStage) (void)hipFree(c->dListStage);
     for (hipEvent_t e : c->evList)
@@ -1403,43 +1492,8 @@ struct QueryLaunch {
     unsigned long long* counters;
     int* spill;
     unsigned char* extra; // extraBytes of the arena behind the spill area (256-byte aligned), or null
-    crt_ctx::RayArena* arena;
+    crt_ctx::Arena* arena;
 };
-
-// The query arena of the context's stream, grown to `need` bytes: the arena this stream used last; else an unused one; else the
-// least recently used one of another stream, once the query that used it last is done.  ownScratch: the call keeps scratch of
-// its own in the arena, and an allocation failure is CRT_ENOMEM
-int takeArena(crt_ctx* c, size_t need, bool ownScratch, crt_ctx::RayArena*& out)
-{
-    crt_ctx::RayArena* arena = nullptr;
-    for (auto& a : c->rayArena)
-        if (a.used && a.stream == c->stream) arena = &a;
-    if (!arena) {
-        for (auto& a : c->rayArena)
-            if (!arena || (!a.used && arena->used) || (a.used == arena->used && a.serial < arena->serial)) arena = &a;
-        if (arena->pending && hipEventQuery(arena->lastUse) != hipSuccess) HIP_TRY(c, hipStreamWaitEvent(c->stream, arena->lastUse, 0));
-        arena->stream = c->stream;
-        arena->used = true;
-    }
-    if (arena->bytes < need) {
-        HIP_TRY(c, hipDeviceSynchronize()); // (the arena may still be in use by a query on its stream)
-        if (arena->mem) (void)hipFree(arena->mem);
-        arena->mem = nullptr;
-        arena->bytes = 0;
-        if (ownScratch) {
-            if (hipMalloc(reinterpret_cast<void**>(&arena->mem), need) != hipSuccess) {
-                (void)hipGetLastError();
-                arena->mem = nullptr;
-                return fail(c, CRT_ENOMEM, "query scratch: %zu bytes of device memory not available", need);
-            }
-        } else HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&arena->mem), need));
-        arena->bytes = need;
-    }
-    if (!arena->lastUse) HIP_TRY(c, hipEventCreateWithFlags(&arena->lastUse, hipEventDisableTiming));
-    arena->serial = ++c->raySerial;
-    out = arena;
-    return CRT_OK;
-}
 
 // One query of n > 0 records on the context's stream, in two halves around the kernel launch.  beginQuery sizes the persistent
 // grid, takes an arena and (with stats) starts the timer; entryWords = ints per stack entry.  endQuery takes the launch's HIP
@@ -1455,9 +1509,9 @@ int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t entryWords, crt_
     ql.spill_stride = (deepest > ql.stack_entries ? deepest - ql.stack_entries : 1u) * entryWords;
 
     constexpr size_t kHead = 256; // cursor at 0, counters at 64
-    const size_t spillBytes = (static_cast<size_t>(std::max(ql.grid, minGrid)) * 64u * ql.spill_stride * sizeof(int) + 255u) & ~static_cast<size_t>(255u);
-    crt_ctx::RayArena* arena = nullptr;
-    if (const int rc = takeArena(c, kHead + spillBytes + extraBytes, extraBytes != 0u, arena)) return rc;
+    const size_t spillBytes = up256(static_cast<size_t>(std::max(ql.grid, minGrid)) * 64u * ql.spill_stride * sizeof(int));
+    crt_ctx::Arena* arena = nullptr;
+    if (const int rc = takeArena(c, c->rayArena, kHead + spillBytes + extraBytes, ++c->raySerial, extraBytes != 0u, arena)) return rc;
     ql.extra = extraBytes ? arena->mem + kHead + spillBytes : nullptr;
     ql.cursor = reinterpret_cast<uint32_t*>(arena->mem);
     ql.counters = reinterpret_cast<unsigned long long*>(arena->mem + 64);
@@ -1470,7 +1524,7 @@ int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t entryWords, crt_
 
 int endQuery(crt_ctx* c, QueryKind kind, uint32_t n, const QueryLaunch& ql, int rc, crt_frame_stats* stats)
 {
-    crt_ctx::RayArena* arena = ql.arena;
+    crt_ctx::Arena* arena = ql.arena;
     if (rc != 0) return fail(c, CRT_EHIP, "query kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
     if (stats) HIP_TRY(c, hipEventRecord(c->evStop, c->stream));
     HIP_TRY(c, hipEventRecord(arena->lastUse, c->stream));
@@ -1566,23 +1620,13 @@ int runPointQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_reco
     return endQuery(c, s.kind, n, ql, crt::launchPointQuery(q, pk, c->counting, ql.grid, c->stream), stats);
 }
 
-// the scene's shading tables and the context's shading state of a shaded query
+// the scene's shading tables (sceneTables) and the context's shading state of a shaded query
 void shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q)
 {
-    q.shade = c->dShade; // as fillParams
-    q.lights = c->dLights;
-    q.mats = c->dMats;
-    q.uvs = c->dUvs;
-    q.textures = c->dTextures;
-    q.texels = static_cast<const unsigned char*>(c->dTexels);
-    q.n_textures = c->nTextures;
-    q.n_lights = c->nLights;
-    q.n_mats = c->nMats;
-    crt::copyBytes(q.miss, c->miss, sizeof(q.miss));
+    sceneTables(c, q);
     q.mode = c->mode;
     q.phong_ks = static_cast<float>(c->phongKsPermille) / 1000.0f;
     q.phong_exp = c->phongExp;
-    q.inner_min_any = c->tuneInnerMinAny;
 }
 
 // crt_shade_rays*: the closest hit and the context's shading mode at it (shade_kernels.hip)
@@ -1615,7 +1659,7 @@ void zeroStats(crt_frame_stats* stats, std::chrono::steady_clock::time_point t0)
 {
     if (!stats) return;
     std::memset(stats, 0, sizeof(*stats));
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
 }
 
 int queryDevice(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, crt_frame_stats* stats)
@@ -1632,7 +1676,7 @@ int queryDevice(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_record
     void* d[kQueryOutputs];
     for (int i = 0; i < kQueryOutputs; i++) d[i] = s.out[i].p;
     if ((rc = runKind(c, s, n, d_records, d, stats)) != CRT_OK) return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -1649,33 +1693,15 @@ int queryHost(crt_ctx* c, const QuerySpec& s, uint32_t n, const float* records, 
     if (!records) return fail(c, CRT_EINVAL, "%s: record buffer is NULL", s.what);
     if ((rc = checkOutputs(c, s)) != CRT_OK) return rc;
     if (s.kind == kQueryShade && (rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
-    const size_t nn = n;
-    auto up = [](size_t b) { return (b + 255u) & ~static_cast<size_t>(255u); };
-    size_t bytes[kQueryOutputs], off[kQueryOutputs], total = up(nn * s.recordBytes);
-    for (int i = 0; i < kQueryOutputs; i++) {
-        bytes[i] = s.out[i].p ? nn * s.out[i].bytes : 0u;
-        off[i] = total;
-        total += up(bytes[i]);
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->rayStageBytes < total) {
-        HIP_TRY(c, hipDeviceSynchronize());
-        if (c->dRayStage) (void)hipFree(c->dRayStage);
-        c->dRayStage = nullptr;
-        c->rayStageBytes = 0;
-        HIP_TRY(c, hipMalloc(&c->dRayStage, total));
-        c->rayStageBytes = total;
-    }
-    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
-    void* devPtr[kQueryOutputs];
-    for (int i = 0; i < kQueryOutputs; i++) devPtr[i] = bytes[i] ? base + off[i] : nullptr;
-    HIP_TRY(c, hipMemcpyAsync(base, records, nn * s.recordBytes, hipMemcpyHostToDevice, c->stream));
+    constexpr int kPlanes = 1 + kQueryOutputs;
+    StagePlane planes[kPlanes] = { { records, nullptr, static_cast<size_t>(n) * s.recordBytes } };
+    for (int i = 0; i < kQueryOutputs; i++) planes[1 + i] = { nullptr, s.out[i].p, static_cast<size_t>(n) * s.out[i].bytes };
+    void* dev[kPlanes];
+    if ((rc = stageBegin(c, planes, kPlanes, dev)) != CRT_OK) return rc;
     crt_frame_stats local;
-    if ((rc = runKind(c, s, n, base, devPtr, stats ? stats : &local)) != CRT_OK) return rc;
-    for (int i = 0; i < kQueryOutputs; i++)
-        if (bytes[i]) HIP_TRY(c, hipMemcpyAsync(s.out[i].p, devPtr[i], bytes[i], hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if ((rc = runKind(c, s, n, dev[0], dev + 1, stats ? stats : &local)) != CRT_OK) return rc;
+    if ((rc = stageEnd(c, planes, kPlanes, dev)) != CRT_OK) return rc;
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -1719,8 +1745,6 @@ struct PathCall {
     bool anyOutput() const { return rgb || sums || t || uv || inst || prim; }
 };
 
-inline size_t pathUp(size_t b) { return (b + 255u) & ~static_cast<size_t>(255u); }
-
 // the checks that need no buffer; n = 0 ends the call after them
 int checkPathCall(crt_ctx* c, const char* what, uint32_t first, uint32_t samples)
 {
@@ -1739,23 +1763,13 @@ int runPathQuery(crt_ctx* c, uint32_t n, const PathCall& a, crt_frame_stats* sta
     const uint32_t passSamples = std::max(1u, std::min(a.samples, cap / blockRecords));
     const size_t slots = static_cast<size_t>(blockRecords) * passSamples; // <= cap <= 2^25
     const bool keepSums = passSamples < a.samples && !a.sums && a.rgb;
-    const size_t slotBytes = pathUp(slots * 16u), sumBytes = keepSums ? pathUp(static_cast<size_t>(blockRecords) * 24u) : 0u;
+    const size_t slotBytes = up256(slots * 16u), sumBytes = keepSums ? up256(static_cast<size_t>(blockRecords) * 24u) : 0u;
 
     crt::PathQueryParams q;
     std::memset(&q, 0, sizeof(q));
-    q.shade = c->dShade; // as fillParams
-    q.lights = c->dLights;
-    q.mats = c->dMats;
-    q.uvs = c->dUvs;
-    q.textures = c->dTextures;
-    q.texels = static_cast<const unsigned char*>(c->dTexels);
-    q.n_textures = c->nTextures;
-    q.n_lights = c->nLights;
-    q.n_mats = c->nMats;
-    crt::copyBytes(q.miss, c->miss, sizeof(q.miss));
+    sceneTables(c, q);
     q.max_bounces = c->pathBounces;
     q.seed = c->pathSeed;
-    q.inner_min_any = c->tuneInnerMinAny;
     QueryLaunch ql;
     if (const int rc = beginQuery(c, kQueryPath, static_cast<uint32_t>(slots), 1u, stats, ql, 2u * slotBytes + sumBytes)) return rc;
     q.rad = ql.extra;
@@ -1807,7 +1821,6 @@ QuerySpec occupancySpec(const char* what, void* inside) { return QuerySpec{ what
 // ---- all-hits listing (crt_list_hits*): count -> scan -> fill -> sort + resolve over one arena, between one beginQuery and
 // one endQuery.  The counts (reused as the sort's queue of long rays), the scan's tile sums and the key scratch live in the
 // arena, so that a second listing on another stream gets its own.
-inline size_t up256(size_t b) { return (b + 255u) & ~static_cast<size_t>(255u); }
 
 struct ListRun {
     QueryLaunch ql;
@@ -1966,7 +1979,7 @@ int crt_path_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, const void*
             return fail(c, CRT_EINVAL, "%s: %s buffer %p is not %u-byte aligned", what, p.name, p.p, static_cast<unsigned>(p.align));
     if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
     if ((rc = runPathQuery(c, n, a, stats)) != CRT_OK) return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -1986,36 +1999,18 @@ int crt_path_rays(crt_ctx* c, uint32_t n, const float* rays, const uint32_t* ids
     if (!(rgb || sums || t || uv || inst || prim)) return fail(c, CRT_EINVAL, "%s: every output is NULL", what);
     if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
     const size_t nn = n;
-    void* const host[8] = { const_cast<float*>(rays), const_cast<uint32_t*>(ids), sums, rgb, t, uv, inst, prim };
-    const size_t per[8] = { 32u, 4u, 24u, 12u, 4u, 8u, 4u, 4u };
-    size_t off[8], total = 0;
-    for (int i = 0; i < 8; i++) {
-        off[i] = total;
-        total += host[i] ? pathUp(nn * per[i]) : 0u;
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->rayStageBytes < total) {
-        HIP_TRY(c, hipDeviceSynchronize());
-        if (c->dRayStage) (void)hipFree(c->dRayStage);
-        c->dRayStage = nullptr;
-        c->rayStageBytes = 0;
-        HIP_TRY(c, hipMalloc(&c->dRayStage, total));
-        c->rayStageBytes = total;
-    }
-    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
+    // (the sums a first call starts are not read)
+    const StagePlane planes[8] = { { rays, nullptr, nn * 32u }, { ids, nullptr, nn * 4u }, { first_sample > 0u ? sums : nullptr, sums, nn * 24u },
+                                   { nullptr, rgb, nn * 12u }, { nullptr, t, nn * 4u }, { nullptr, uv, nn * 8u }, { nullptr, inst, nn * 4u },
+                                   { nullptr, prim, nn * 4u } };
     void* dev[8];
-    for (int i = 0; i < 8; i++) dev[i] = host[i] ? base + off[i] : nullptr;
-    HIP_TRY(c, hipMemcpyAsync(dev[0], rays, nn * 32u, hipMemcpyHostToDevice, c->stream));
-    if (ids) HIP_TRY(c, hipMemcpyAsync(dev[1], ids, nn * 4u, hipMemcpyHostToDevice, c->stream));
-    if (sums && first_sample > 0u) HIP_TRY(c, hipMemcpyAsync(dev[2], sums, nn * 24u, hipMemcpyHostToDevice, c->stream));
+    if ((rc = stageBegin(c, planes, 8, dev)) != CRT_OK) return rc;
     const PathCall a{ dev[0], static_cast<const uint32_t*>(dev[1]), first_sample, n_samples, static_cast<float*>(dev[3]), static_cast<double*>(dev[2]),
                       static_cast<float*>(dev[4]), static_cast<float*>(dev[5]), static_cast<uint32_t*>(dev[6]), static_cast<uint32_t*>(dev[7]) };
     crt_frame_stats local;
     if ((rc = runPathQuery(c, n, a, stats ? stats : &local)) != CRT_OK) return rc;
-    for (int i = 2; i < 8; i++)
-        if (host[i]) HIP_TRY(c, hipMemcpyAsync(host[i], dev[i], nn * per[i], hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if ((rc = stageEnd(c, planes, 8, dev)) != CRT_OK) return rc;
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2036,21 +2031,6 @@ int checkDevicePointers(crt_ctx* c, const char* what, std::initializer_list<cons
     for (const void* p : ptrs)
         if (reinterpret_cast<uintptr_t>(p) & (align - 1u))
             return fail(c, CRT_EINVAL, "%s: buffer %p is not %u-byte aligned", what, p, static_cast<unsigned>(align));
-    return CRT_OK;
-}
-
-// the query staging buffer of the host forms, grown to `total` bytes
-int reserveRayStage(crt_ctx* c, size_t total)
-{
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->rayStageBytes < total) {
-        HIP_TRY(c, hipDeviceSynchronize());
-        if (c->dRayStage) (void)hipFree(c->dRayStage);
-        c->dRayStage = nullptr;
-        c->rayStageBytes = 0;
-        HIP_TRY(c, hipMalloc(&c->dRayStage, total));
-        c->rayStageBytes = total;
-    }
     return CRT_OK;
 }
 
@@ -2157,14 +2137,30 @@ float invSquare(float sigma)
     return static_cast<float>(std::min(1.0 / (s * s), static_cast<double>(FLT_MAX)));
 }
 
-int runDenoise(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* d_rgb, const void* d_normal, const void* d_albedo, const void* d_t,
-               void* d_out, const crt_denoise_params& prm, crt_frame_stats* stats)
+// what both filters do around their kernel: the stream's query arena as three float4 planes {guide, colour[0], colour[1]}, the
+// launch (a HIP error code), and the arena's last use, recorded before a timed call synchronises
+static int runOverDenoiseArena(crt_ctx* c, const char* what, uint32_t w, uint32_t h, void*& guide, void* (&colour)[2], const std::function<int()>& launch,
+                               crt_frame_stats* stats)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t plane = up256(static_cast<size_t>(w) * h * 16u);
     static_assert(crt::kDenoiseScratchPerPixel == 48u, "three float4 planes");
-    crt_ctx::RayArena* arena = nullptr;
-    if (const int rc = takeArena(c, 3u * plane, true, arena)) return rc;
+    crt_ctx::Arena* arena = nullptr;
+    if (const int rc = takeArena(c, c->rayArena, 3u * plane, ++c->raySerial, true, arena)) return rc;
+    guide = arena->mem;
+    colour[0] = arena->mem + plane;
+    colour[1] = arena->mem + 2u * plane;
+    return runTimed(c, what, stats, [&] {
+        const int hrc = launch();
+        if (hrc != 0) return hrc;
+        arena->pending = true;
+        return static_cast<int>(hipEventRecord(arena->lastUse, c->stream));
+    });
+}
+
+int runDenoise(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* d_rgb, const void* d_normal, const void* d_albedo, const void* d_t,
+               void* d_out, const crt_denoise_params& prm, crt_frame_stats* stats)
+{
     crt::DenoiseParams p;
     std::memset(&p, 0, sizeof(p));
     p.width = w;
@@ -2179,16 +2175,7 @@ int runDenoise(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void*
     p.albedo = static_cast<const float*>(d_albedo);
     p.t = static_cast<const float*>(d_t);
     p.out = static_cast<float*>(d_out);
-    p.guide = arena->mem;
-    p.colour[0] = arena->mem + plane;
-    p.colour[1] = arena->mem + 2u * plane;
-    // (the arena's last use is recorded before a timed call synchronises)
-    return runTimed(c, what, stats, [&] {
-        const int hrc = crt::launchDenoise(p, c->stream);
-        if (hrc != 0) return hrc;
-        arena->pending = true;
-        return static_cast<int>(hipEventRecord(arena->lastUse, c->stream));
-    });
+    return runOverDenoiseArena(c, what, w, h, p.guide, p.colour, [&] { return crt::launchDenoise(p, c->stream); }, stats);
 }
 
 } // namespace
@@ -2202,7 +2189,7 @@ int crt_camera_rays_device(crt_ctx* c, uint32_t w, uint32_t h, uint32_t sample, 
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = runCameraRays(c, what, w, h, sample, d_rays, stats)) != CRT_OK) return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2217,7 +2204,7 @@ int crt_camera_rays(crt_ctx* c, uint32_t w, uint32_t h, uint32_t sample, float* 
     if ((rc = runCameraRays(c, what, w, h, sample, c->dRayStage, stats)) != CRT_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(rays, c->dRayStage, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2230,7 +2217,7 @@ int crt_frame_guides_device(crt_ctx* c, uint32_t w, uint32_t h, void* d_normal, 
     const auto t0 = std::chrono::steady_clock::now();
     if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
     if ((rc = runFrameGuides(c, w, h, d_normal, d_albedo, d_t, stats)) != CRT_OK) return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2243,22 +2230,12 @@ int crt_frame_guides(crt_ctx* c, uint32_t w, uint32_t h, float* normal, float* a
     const auto t0 = std::chrono::steady_clock::now();
     if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
     const size_t nn = static_cast<size_t>(w) * h;
-    void* const host[3] = { normal, albedo, t };
-    const size_t per[3] = { 12u, 12u, 4u };
-    size_t off[3], total = 0;
-    for (int i = 0; i < 3; i++) {
-        off[i] = total;
-        total += host[i] ? up256(nn * per[i]) : 0u;
-    }
-    if ((rc = reserveRayStage(c, total)) != CRT_OK) return rc;
-    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
+    const StagePlane planes[3] = { { nullptr, normal, nn * 12u }, { nullptr, albedo, nn * 12u }, { nullptr, t, nn * 4u } };
     void* dev[3];
-    for (int i = 0; i < 3; i++) dev[i] = host[i] ? base + off[i] : nullptr;
+    if ((rc = stageBegin(c, planes, 3, dev)) != CRT_OK) return rc;
     if ((rc = runFrameGuides(c, w, h, dev[0], dev[1], dev[2], stats)) != CRT_OK) return rc;
-    for (int i = 0; i < 3; i++)
-        if (host[i]) HIP_TRY(c, hipMemcpyAsync(host[i], dev[i], nn * per[i], hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if ((rc = stageEnd(c, planes, 3, dev)) != CRT_OK) return rc;
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2272,7 +2249,7 @@ int crt_denoise_device(crt_ctx* c, uint32_t w, uint32_t h, const void* d_rgb, co
     if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_out }, 4u)) != CRT_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     if ((rc = runDenoise(c, what, w, h, d_rgb, d_normal, d_albedo, d_t, d_out, prm, stats)) != CRT_OK) return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2286,20 +2263,13 @@ int crt_denoise(crt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const floa
     if (rc) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     const size_t nn = static_cast<size_t>(w) * h;
-    const void* const host[4] = { rgb, normal, albedo, t };
-    const size_t per[4] = { 12u, 12u, 12u, 4u };
-    size_t off[4], total = 0;
-    for (int i = 0; i < 4; i++) {
-        off[i] = total;
-        total += up256(nn * per[i]);
-    }
-    if ((rc = reserveRayStage(c, total)) != CRT_OK) return rc;
-    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
-    for (int i = 0; i < 4; i++) HIP_TRY(c, hipMemcpyAsync(base + off[i], host[i], nn * per[i], hipMemcpyHostToDevice, c->stream));
-    if ((rc = runDenoise(c, what, w, h, base + off[0], base + off[1], base + off[2], base + off[3], base + off[0], prm, stats)) != CRT_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out, base + off[0], nn * 12u, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const StagePlane planes[5] = { { rgb, nullptr, nn * 12u }, { normal, nullptr, nn * 12u }, { albedo, nullptr, nn * 12u }, { t, nullptr, nn * 4u },
+                                   { nullptr, out, nn * 12u, 0 } };
+    void* dev[5];
+    if ((rc = stageBegin(c, planes, 5, dev)) != CRT_OK) return rc;
+    if ((rc = runDenoise(c, what, w, h, dev[0], dev[1], dev[2], dev[3], dev[4], prm, stats)) != CRT_OK) return rc;
+    if ((rc = stageEnd(c, planes, 5, dev)) != CRT_OK) return rc;
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2372,55 +2342,65 @@ int runTemporal(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const floa
     return runTimed(c, what, stats, [&] { return crt::launchTemporal(p, c->stream); });
 }
 
-// the device forms, plain (d_prevPoint == NULL) and with motion
-int temporalDevice(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const void* d_rgb,
-                   const void* d_normal, const void* d_albedo, const void* d_t, const void* d_histPrev, void* d_histNext, void* d_out,
-                   const void* d_prevPoint, const crt_temporal_params* params, crt_frame_stats* stats)
+// what crt_temporal_variance* checks beyond checkTemporal
+int checkTemporalVariance(crt_ctx* c, const char* what, const void* histPrev, const TemporalMoments& m)
 {
-    const crt_temporal_params prm = params ? *params : kTemporalDefaults;
-    int rc = checkTemporal(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histNext, prm);
-    if (rc) return rc;
-    if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_out, d_prevPoint }, 4u)) != CRT_OK) return rc;
-    if ((rc = checkDevicePointers(c, what, { d_histPrev, d_histNext }, 16u)) != CRT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext, d_out, d_prevPoint, prm, stats)) !=
-        CRT_OK)
-        return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (!(m.alphaMoments >= 0.0f && m.alphaMoments <= 1.0f))
+        return fail(c, CRT_EINVAL, "%s: alpha_moments = %g is outside [0, 1]", what, static_cast<double>(m.alphaMoments));
+    if (m.minHistory < 1u || m.minHistory > (1u << 24)) return fail(c, CRT_EINVAL, "%s: min_history = %u is outside 1..2^24", what, m.minHistory);
+    if (!m.next || !m.variance) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
+    if ((histPrev == nullptr) != (m.prev == nullptr))
+        return fail(c, CRT_EINVAL, "%s: hist_prev and mom_prev must be given together or not at all", what);
     return CRT_OK;
 }
 
-// host buffers: staged through the context's query staging buffer {rgb | normal | albedo | t | hist_prev | hist_next | prev_point},
-// the colour accumulated in place; synchronous
+// The three temporal entry points are one call: plain (prevPoint == NULL), with motion, and with moments (moments != NULL).
+// The device forms ...
+int temporalDevice(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const void* d_rgb,
+                   const void* d_normal, const void* d_albedo, const void* d_t, const void* d_histPrev, void* d_histNext, void* d_out,
+                   const void* d_prevPoint, const crt_temporal_params* params, const TemporalMoments* moments, crt_frame_stats* stats)
+{
+    const crt_temporal_params prm = params ? *params : kTemporalDefaults;
+    int rc = checkTemporal(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histNext, prm);
+    if (rc == CRT_OK && moments) rc = checkTemporalVariance(c, what, d_histPrev, *moments);
+    if (rc) return rc;
+    const TemporalMoments m = moments ? *moments : TemporalMoments{};
+    if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_out, d_prevPoint, m.variance }, 4u)) != CRT_OK) return rc;
+    if ((rc = checkDevicePointers(c, what, { m.prev, m.next }, 8u)) != CRT_OK) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_histPrev, d_histNext }, 16u)) != CRT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext, d_out, d_prevPoint, prm, stats,
+                          moments)) != CRT_OK)
+        return rc;
+    stampTotal(stats, t0);
+    return CRT_OK;
+}
+
+// ... and the host forms: staged as {rgb | normal | albedo | t | hist_prev | hist_next | prev_point | mom_prev | mom_next | variance},
+// the colour accumulated in place and read back last; synchronous
 int temporalHost(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const float* rgb,
                  const float* normal, const float* albedo, const float* t, const float* histPrev, float* histNext, float* out,
-                 const float* prevPoint, const crt_temporal_params* params, crt_frame_stats* stats)
+                 const float* prevPoint, const crt_temporal_params* params, const TemporalMoments* moments, crt_frame_stats* stats)
 {
     const crt_temporal_params prm = params ? *params : kTemporalDefaults;
     int rc = checkTemporal(c, what, w, h, camCur, camPrev, rgb, normal, albedo, t, histNext, prm);
+    if (rc == CRT_OK && moments) rc = checkTemporalVariance(c, what, histPrev, *moments);
     if (rc) return rc;
     const auto t0 = std::chrono::steady_clock::now();
+    const TemporalMoments m = moments ? *moments : TemporalMoments{};
     const size_t nn = static_cast<size_t>(w) * h;
-    const void* const host[7] = { rgb, normal, albedo, t, histPrev, nullptr, prevPoint };
-    const size_t per[7] = { 12u, 12u, 12u, 4u, 32u, 32u, 12u };
-    size_t off[7], total = 0;
-    for (int i = 0; i < 7; i++) {
-        off[i] = total;
-        total += (i == 5 || host[i]) ? up256(nn * per[i]) : 0u;
-    }
-    if ((rc = reserveRayStage(c, total)) != CRT_OK) return rc;
-    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
-    unsigned char* dev[7];
-    for (int i = 0; i < 7; i++) dev[i] = (i == 5 || host[i]) ? base + off[i] : nullptr;
-    for (int i = 0; i < 7; i++)
-        if (host[i]) HIP_TRY(c, hipMemcpyAsync(dev[i], host[i], nn * per[i], hipMemcpyHostToDevice, c->stream));
-    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], out ? dev[0] : nullptr, dev[6], prm, stats)) !=
-        CRT_OK)
+    const StagePlane planes[11] = { { rgb, nullptr, nn * 12u }, { normal, nullptr, nn * 12u }, { albedo, nullptr, nn * 12u }, { t, nullptr, nn * 4u },
+                                    { histPrev, nullptr, nn * 32u }, { nullptr, histNext, nn * 32u }, { prevPoint, nullptr, nn * 12u },
+                                    { m.prev, nullptr, nn * 8u }, { nullptr, m.next, nn * 8u }, { nullptr, m.variance, nn * 4u },
+                                    { nullptr, out, nn * 12u, 0 } };
+    void* dev[11];
+    if ((rc = stageBegin(c, planes, 11, dev)) != CRT_OK) return rc;
+    const TemporalMoments staged = { dev[7], dev[8], dev[9], m.alphaMoments, m.minHistory };
+    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[10], dev[6], prm, stats,
+                          moments ? &staged : nullptr)) != CRT_OK)
         return rc;
-    HIP_TRY(c, hipMemcpyAsync(histNext, dev[5], nn * 32u, hipMemcpyDeviceToHost, c->stream));
-    if (out) HIP_TRY(c, hipMemcpyAsync(out, dev[0], nn * 12u, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if ((rc = stageEnd(c, planes, 11, dev)) != CRT_OK) return rc;
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2431,14 +2411,15 @@ int crt_temporal_accumulate_device(crt_ctx* c, uint32_t w, uint32_t h, const flo
                                    void* d_out, const crt_temporal_params* params, crt_frame_stats* stats)
 {
     return temporalDevice(c, "crt_temporal_accumulate_device", w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext, d_out,
-                          nullptr, params, stats);
+                          nullptr, params, nullptr, stats);
 }
 
 int crt_temporal_accumulate(crt_ctx* c, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const float* rgb,
                             const float* normal, const float* albedo, const float* t, const float* histPrev, float* histNext, float* out,
                             const crt_temporal_params* params, crt_frame_stats* stats)
 {
-    return temporalHost(c, "crt_temporal_accumulate", w, h, camCur, camPrev, rgb, normal, albedo, t, histPrev, histNext, out, nullptr, params, stats);
+    return temporalHost(c, "crt_temporal_accumulate", w, h, camCur, camPrev, rgb, normal, albedo, t, histPrev, histNext, out, nullptr,
+                        params, nullptr, stats);
 }
 
 int crt_temporal_accumulate_motion_device(crt_ctx* c, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const void* d_rgb,
@@ -2447,15 +2428,15 @@ int crt_temporal_accumulate_motion_device(crt_ctx* c, uint32_t w, uint32_t h, co
                                           crt_frame_stats* stats)
 {
     return temporalDevice(c, "crt_temporal_accumulate_motion_device", w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext,
-                          d_out, d_prevPoint, params, stats);
+                          d_out, d_prevPoint, params, nullptr, stats);
 }
 
 int crt_temporal_accumulate_motion(crt_ctx* c, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const float* rgb,
                                    const float* normal, const float* albedo, const float* t, const float* prevPoint, const float* histPrev,
                                    float* histNext, float* out, const crt_temporal_params* params, crt_frame_stats* stats)
 {
-    return temporalHost(c, "crt_temporal_accumulate_motion", w, h, camCur, camPrev, rgb, normal, albedo, t, histPrev, histNext, out, prevPoint, params,
-                        stats);
+    return temporalHost(c, "crt_temporal_accumulate_motion", w, h, camCur, camPrev, rgb, normal, albedo, t, histPrev, histNext, out, prevPoint,
+                        params, nullptr, stats);
 }
 
 namespace {
@@ -2463,21 +2444,6 @@ namespace {
 // ---- variance: luminance moments in the temporal pass, a variance-guided filter (temporal_kernels.hip, variance_kernels.hip)
 const crt_temporal_variance_params kTemporalVarianceDefaults = { { 0.1f, 0.01f, 0.9f, 64u, 1u }, 0.2f, 4u };
 const crt_denoise_variance_params kDenoiseVarianceDefaults = { 5u, 0.0625f, 0.3f, 0.05f, 1u };
-
-int checkTemporalVariance(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const void* rgb,
-                          const void* normal, const void* albedo, const void* t, const void* histPrev, const void* histNext, const void* momPrev,
-                          const void* momNext, const void* variance, const crt_temporal_variance_params& prm)
-{
-    if (const int rc = checkTemporal(c, what, w, h, camCur, camPrev, rgb, normal, albedo, t, histNext, prm.base)) return rc;
-    if (!(prm.alpha_moments >= 0.0f && prm.alpha_moments <= 1.0f))
-        return fail(c, CRT_EINVAL, "%s: alpha_moments = %g is outside [0, 1]", what, static_cast<double>(prm.alpha_moments));
-    if (prm.min_history < 1u || prm.min_history > (1u << 24))
-        return fail(c, CRT_EINVAL, "%s: min_history = %u is outside 1..2^24", what, prm.min_history);
-    if (!momNext || !variance) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
-    if ((histPrev == nullptr) != (momPrev == nullptr))
-        return fail(c, CRT_EINVAL, "%s: hist_prev and mom_prev must be given together or not at all", what);
-    return CRT_OK;
-}
 
 int checkDenoiseVariance(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* rgb, const void* normal, const void* albedo,
                          const void* t, const void* variance, const void* out, const crt_denoise_variance_params& prm)
@@ -2495,10 +2461,6 @@ int runDenoiseVariance(crt_ctx* c, const char* what, uint32_t w, uint32_t h, con
                        const void* d_t, const void* d_variance, void* d_out, void* d_varianceOut, const crt_denoise_variance_params& prm,
                        crt_frame_stats* stats)
 {
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t plane = up256(static_cast<size_t>(w) * h * 16u);
-    crt_ctx::RayArena* arena = nullptr;
-    if (const int rc = takeArena(c, 3u * plane, true, arena)) return rc;
     crt::DenoiseVarianceParams p;
     std::memset(&p, 0, sizeof(p));
     p.width = w;
@@ -2515,16 +2477,7 @@ int runDenoiseVariance(crt_ctx* c, const char* what, uint32_t w, uint32_t h, con
     p.variance = static_cast<const float*>(d_variance);
     p.out = static_cast<float*>(d_out);
     p.varianceOut = static_cast<float*>(d_varianceOut);
-    p.guide = arena->mem;
-    p.colour[0] = arena->mem + plane;
-    p.colour[1] = arena->mem + 2u * plane;
-    // (the arena's last use is recorded before a timed call synchronises)
-    return runTimed(c, what, stats, [&] {
-        const int hrc = crt::launchDenoiseVariance(p, c->stream);
-        if (hrc != 0) return hrc;
-        arena->pending = true;
-        return static_cast<int>(hipEventRecord(arena->lastUse, c->stream));
-    });
+    return runOverDenoiseArena(c, what, w, h, p.guide, p.colour, [&] { return crt::launchDenoiseVariance(p, c->stream); }, stats);
 }
 
 } // namespace
@@ -2534,61 +2487,21 @@ int crt_temporal_variance_device(crt_ctx* c, uint32_t w, uint32_t h, const float
                                  void* d_histNext, const void* d_momPrev, void* d_momNext, void* d_variance, void* d_out,
                                  const crt_temporal_variance_params* params, crt_frame_stats* stats)
 {
-    const char* what = "crt_temporal_variance_device";
     const crt_temporal_variance_params prm = params ? *params : kTemporalVarianceDefaults;
-    int rc = checkTemporalVariance(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext, d_momPrev, d_momNext,
-                                   d_variance, prm);
-    if (rc) return rc;
-    if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_out, d_prevPoint, d_variance }, 4u)) != CRT_OK) return rc;
-    if ((rc = checkDevicePointers(c, what, { d_momPrev, d_momNext }, 8u)) != CRT_OK) return rc;
-    if ((rc = checkDevicePointers(c, what, { d_histPrev, d_histNext }, 16u)) != CRT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
     const TemporalMoments moments = { d_momPrev, d_momNext, d_variance, prm.alpha_moments, prm.min_history };
-    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext, d_out, d_prevPoint, prm.base, stats,
-                          &moments)) != CRT_OK)
-        return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return CRT_OK;
+    return temporalDevice(c, "crt_temporal_variance_device", w, h, camCur, camPrev, d_rgb, d_normal, d_albedo, d_t, d_histPrev, d_histNext, d_out,
+                          d_prevPoint, &prm.base, &moments, stats);
 }
 
-// host buffers: staged through the context's query staging buffer {rgb | normal | albedo | t | hist_prev | hist_next | prev_point |
-// mom_prev | mom_next | variance}, the colour accumulated in place; synchronous
 int crt_temporal_variance(crt_ctx* c, uint32_t w, uint32_t h, const float* camCur, const float* camPrev, const float* rgb, const float* normal,
                           const float* albedo, const float* t, const float* prevPoint, const float* histPrev, float* histNext,
                           const float* momPrev, float* momNext, float* variance, float* out, const crt_temporal_variance_params* params,
                           crt_frame_stats* stats)
 {
-    const char* what = "crt_temporal_variance";
     const crt_temporal_variance_params prm = params ? *params : kTemporalVarianceDefaults;
-    int rc = checkTemporalVariance(c, what, w, h, camCur, camPrev, rgb, normal, albedo, t, histPrev, histNext, momPrev, momNext, variance, prm);
-    if (rc) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t nn = static_cast<size_t>(w) * h;
-    constexpr int kBuffers = 10, kHistNext = 5, kMomNext = 8, kVariance = 9;
-    const void* const host[kBuffers] = { rgb, normal, albedo, t, histPrev, nullptr, prevPoint, momPrev, nullptr, nullptr };
-    const size_t per[kBuffers] = { 12u, 12u, 12u, 4u, 32u, 32u, 12u, 8u, 8u, 4u };
-    size_t off[kBuffers], total = 0;
-    unsigned char* dev[kBuffers];
-    for (int i = 0; i < kBuffers; i++) {
-        off[i] = total;
-        total += (i == kHistNext || i >= kMomNext || host[i]) ? up256(nn * per[i]) : 0u;
-    }
-    if ((rc = reserveRayStage(c, total)) != CRT_OK) return rc;
-    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
-    for (int i = 0; i < kBuffers; i++) dev[i] = (i == kHistNext || i >= kMomNext || host[i]) ? base + off[i] : nullptr;
-    for (int i = 0; i < kBuffers; i++)
-        if (host[i]) HIP_TRY(c, hipMemcpyAsync(dev[i], host[i], nn * per[i], hipMemcpyHostToDevice, c->stream));
-    const TemporalMoments moments = { dev[7], dev[kMomNext], dev[kVariance], prm.alpha_moments, prm.min_history };
-    if ((rc = runTemporal(c, what, w, h, camCur, camPrev, dev[0], dev[1], dev[2], dev[3], dev[4], dev[kHistNext], out ? dev[0] : nullptr, dev[6],
-                          prm.base, stats, &moments)) != CRT_OK)
-        return rc;
-    HIP_TRY(c, hipMemcpyAsync(histNext, dev[kHistNext], nn * 32u, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(momNext, dev[kMomNext], nn * 8u, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(variance, dev[kVariance], nn * 4u, hipMemcpyDeviceToHost, c->stream));
-    if (out) HIP_TRY(c, hipMemcpyAsync(out, dev[0], nn * 12u, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return CRT_OK;
+    const TemporalMoments moments = { momPrev, momNext, variance, prm.alpha_moments, prm.min_history };
+    return temporalHost(c, "crt_temporal_variance", w, h, camCur, camPrev, rgb, normal, albedo, t, histPrev, histNext, out, prevPoint, &prm.base,
+                        &moments, stats);
 }
 
 int crt_denoise_variance_device(crt_ctx* c, uint32_t w, uint32_t h, const void* d_rgb, const void* d_normal, const void* d_albedo, const void* d_t,
@@ -2602,7 +2515,7 @@ int crt_denoise_variance_device(crt_ctx* c, uint32_t w, uint32_t h, const void* 
     if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, d_varianceOut }, 4u)) != CRT_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     if ((rc = runDenoiseVariance(c, what, w, h, d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, d_varianceOut, prm, stats)) != CRT_OK) return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2616,23 +2529,13 @@ int crt_denoise_variance(crt_ctx* c, uint32_t w, uint32_t h, const float* rgb, c
     if (rc) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     const size_t nn = static_cast<size_t>(w) * h;
-    const void* const host[5] = { rgb, normal, albedo, t, variance };
-    const size_t per[5] = { 12u, 12u, 12u, 4u, 4u };
-    size_t off[5], total = 0;
-    for (int i = 0; i < 5; i++) {
-        off[i] = total;
-        total += up256(nn * per[i]);
-    }
-    if ((rc = reserveRayStage(c, total)) != CRT_OK) return rc;
-    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
-    for (int i = 0; i < 5; i++) HIP_TRY(c, hipMemcpyAsync(base + off[i], host[i], nn * per[i], hipMemcpyHostToDevice, c->stream));
-    if ((rc = runDenoiseVariance(c, what, w, h, base + off[0], base + off[1], base + off[2], base + off[3], base + off[4], base + off[0],
-                                 varianceOut ? base + off[4] : nullptr, prm, stats)) != CRT_OK)
-        return rc;
-    HIP_TRY(c, hipMemcpyAsync(out, base + off[0], nn * 12u, hipMemcpyDeviceToHost, c->stream));
-    if (varianceOut) HIP_TRY(c, hipMemcpyAsync(varianceOut, base + off[4], nn * 4u, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const StagePlane planes[7] = { { rgb, nullptr, nn * 12u }, { normal, nullptr, nn * 12u }, { albedo, nullptr, nn * 12u }, { t, nullptr, nn * 4u },
+                                   { variance, nullptr, nn * 4u }, { nullptr, out, nn * 12u, 0 }, { nullptr, varianceOut, nn * 4u, 4 } };
+    void* dev[7];
+    if ((rc = stageBegin(c, planes, 7, dev)) != CRT_OK) return rc;
+    if ((rc = runDenoiseVariance(c, what, w, h, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], prm, stats)) != CRT_OK) return rc;
+    if ((rc = stageEnd(c, planes, 7, dev)) != CRT_OK) return rc;
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2707,7 +2610,7 @@ int crt_list_hits_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_off
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         *total = tot;
     }
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2721,21 +2624,12 @@ int crt_list_hits(crt_ctx* c, uint32_t n, const float* rays, uint64_t* offsets, 
     if (done && offsets) offsets[0] = 0u;
     if (rc || done) return rc;
     if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
-    const size_t nn = n, rayBytes = up256(nn * 32u), offBytes = up256((nn + 1u) * sizeof(uint64_t));
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->rayStageBytes < rayBytes + offBytes) {
-        HIP_TRY(c, hipDeviceSynchronize());
-        if (c->dRayStage) (void)hipFree(c->dRayStage);
-        c->dRayStage = nullptr;
-        c->rayStageBytes = 0;
-        HIP_TRY(c, hipMalloc(&c->dRayStage, rayBytes + offBytes));
-        c->rayStageBytes = rayBytes + offBytes;
-    }
-    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
-    unsigned long long* dOff = reinterpret_cast<unsigned long long*>(base + rayBytes);
-    HIP_TRY(c, hipMemcpyAsync(base, rays, nn * 32u, hipMemcpyHostToDevice, c->stream));
+    const StagePlane planes[2] = { { rays, nullptr, static_cast<size_t>(n) * 32u }, { nullptr, offsets, (static_cast<size_t>(n) + 1u) * sizeof(uint64_t) } };
+    void* dev[2];
+    if ((rc = stageBegin(c, planes, 2, dev)) != CRT_OK) return rc;
+    unsigned long long* dOff = static_cast<unsigned long long*>(dev[1]);
     ListRun lr;
-    if ((rc = listBegin(c, n, base, dOff, 0u, stats, lr)) != CRT_OK) return rc;
+    if ((rc = listBegin(c, n, dev[0], dOff, 0u, stats, lr)) != CRT_OK) return rc;
     // the one read-back: does the total fit the caller's arrays?
     unsigned long long tot = 0;
     hipError_t he = hipMemcpyAsync(&tot, dOff + n, sizeof(tot), hipMemcpyDeviceToHost, c->stream);
@@ -2744,19 +2638,10 @@ int crt_list_hits(crt_ctx* c, uint32_t n, const float* rays, uint64_t* offsets, 
     unsigned char* rec = nullptr;
     const size_t cap4 = up256(static_cast<size_t>(tot) * 4u), cap8 = up256(static_cast<size_t>(tot) * 8u);
     bool noMem = false;
-    if (fill) {
-        const size_t need = 3u * cap4 + cap8; // t, prim (the work arrays), inst, uv
-        if (c->listStageBytes < need) {
-            he = hipDeviceSynchronize();
-            if (c->dListStage) (void)hipFree(c->dListStage);
-            c->dListStage = nullptr;
-            c->listStageBytes = 0;
-            if (he == hipSuccess && hipMalloc(&c->dListStage, need) != hipSuccess) {
-                (void)hipGetLastError();
-                c->dListStage = nullptr;
-                noMem = true;
-            } else if (he == hipSuccess) c->listStageBytes = need;
-        }
+    if (fill) { // t, prim (the work arrays), inst, uv.  Without the memory the call still goes through endQuery: the count has used the arena
+        const int grown = ensureBuffer(c, &c->dListStage, &c->listStageBytes, 3u * cap4 + cap8, true);
+        if (grown == CRT_EHIP) return grown; // (the device-wide wait failed: endQuery would only return the same)
+        noMem = grown == CRT_ENOMEM;
         rec = static_cast<unsigned char*>(c->dListStage);
     }
     int hrc = static_cast<int>(he);
@@ -2765,7 +2650,7 @@ int crt_list_hits(crt_ctx* c, uint32_t n, const float* rays, uint64_t* offsets, 
     if ((rc = endQuery(c, kQueryCount, n, lr.ql, hrc, stats)) != CRT_OK) return rc;
     if ((rc = listPhases(c, lr, fill && !noMem)) != CRT_OK) return rc;
     if (noMem) return fail(c, CRT_ENOMEM, "%s: staging for %llu records not available", what, tot);
-    HIP_TRY(c, hipMemcpyAsync(offsets, dOff, (nn + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = stageDownload(c, planes, 2, dev)) != CRT_OK) return rc;
     if (fill) {
         if (t) HIP_TRY(c, hipMemcpyAsync(t, out[0], static_cast<size_t>(tot) * 4u, hipMemcpyDeviceToHost, c->stream));
         if (uv) HIP_TRY(c, hipMemcpyAsync(uv, out[1], static_cast<size_t>(tot) * 8u, hipMemcpyDeviceToHost, c->stream));
@@ -2774,7 +2659,7 @@ int crt_list_hits(crt_ctx* c, uint32_t n, const float* rays, uint64_t* offsets, 
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (total) *total = tot;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2794,7 +2679,7 @@ int crt_render_frame_device(crt_ctx* c, uint32_t w, uint32_t h, void* d_rgba8, v
     p.rgb_f32 = static_cast<float*>(d_rgb_f32);
     rc = runFrame(c, p, stats, kAccFrame);
     if (rc) return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2825,7 +2710,7 @@ int crt_render_frame(crt_ctx* c, uint32_t w, uint32_t h, uint8_t* rgba8, uint32_
     for (int i = 0; i < 5; i++)
         if (host[i] && (traced || i == 0 || i == 4)) HIP_TRY(c, hipMemcpyAsync(host[i], c->dFrame[i], bytes[i], hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2849,7 +2734,7 @@ int crt_render_tiles_device(crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, u
     p.rgba8 = static_cast<uint32_t*>(d_staging);
     rc = runFrame(c, p, stats, kAccTiles);
     if (rc) return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -2884,7 +2769,7 @@ int runBatch(crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_t n_ranks
     }
     rc = runRender(c, p, stats);
     if (rc) return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 } // namespace
@@ -3294,7 +3179,7 @@ int crt_previous_points_device(crt_ctx* c, uint32_t n, const void* d_inst, const
     if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = runPreviousPoints(c, what, n, d_inst, d_prim, d_uv, d_point, stats)) != CRT_OK) return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -3312,16 +3197,12 @@ int crt_previous_points(crt_ctx* c, uint32_t n, const uint32_t* inst, const uint
     if (!inst || !prim || !uv || !point) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
     if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
     const size_t nn = n;
-    const size_t off[4] = { 0u, up256(nn * 4u), 2u * up256(nn * 4u), 2u * up256(nn * 4u) + up256(nn * 8u) };
-    if ((rc = reserveRayStage(c, off[3] + up256(nn * 12u))) != CRT_OK) return rc;
-    unsigned char* base = static_cast<unsigned char*>(c->dRayStage);
-    HIP_TRY(c, hipMemcpyAsync(base + off[0], inst, nn * 4u, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(base + off[1], prim, nn * 4u, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(base + off[2], uv, nn * 8u, hipMemcpyHostToDevice, c->stream));
-    if ((rc = runPreviousPoints(c, what, n, base + off[0], base + off[1], base + off[2], base + off[3], stats)) != CRT_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(point, base + off[3], nn * 12u, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const StagePlane planes[4] = { { inst, nullptr, nn * 4u }, { prim, nullptr, nn * 4u }, { uv, nullptr, nn * 8u }, { nullptr, point, nn * 12u } };
+    void* dev[4];
+    if ((rc = stageBegin(c, planes, 4, dev)) != CRT_OK) return rc;
+    if ((rc = runPreviousPoints(c, what, n, dev[0], dev[1], dev[2], dev[3], stats)) != CRT_OK) return rc;
+    if ((rc = stageEnd(c, planes, 4, dev)) != CRT_OK) return rc;
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -3334,7 +3215,7 @@ int crt_frame_motion_device(crt_ctx* c, uint32_t w, uint32_t h, void* d_prevPoin
     const auto t0 = std::chrono::steady_clock::now();
     if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
     if ((rc = runFrameMotion(c, w, h, d_prevPoint, stats)) != CRT_OK) return rc;
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -3351,7 +3232,7 @@ int crt_frame_motion(crt_ctx* c, uint32_t w, uint32_t h, float* prevPoint, crt_f
     if ((rc = runFrameMotion(c, w, h, c->dRayStage, stats)) != CRT_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(prevPoint, c->dRayStage, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (stats) stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stampTotal(stats, t0);
     return CRT_OK;
 }
 
@@ -3403,17 +3284,6 @@ RcclApi& rccl()
     return api;
 }
 
-int ensureBuffer(crt_ctx* c, void** ptr, size_t* have, size_t need)
-{
-    if (*have >= need) return CRT_OK;
-    HIP_TRY(c, hipDeviceSynchronize());
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr;
-    *have = 0;
-    HIP_TRY(c, hipMalloc(ptr, need));
-    *have = need;
-    return CRT_OK;
-}
 } // namespace
 
 int crt_comm_unique_id(void* id_out)
