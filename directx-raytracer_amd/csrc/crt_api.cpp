@@ -2114,19 +2114,24 @@ int checkFrameGuides(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const
     return CRT_OK;
 }
 
+// ---- the a-trous filters (denoise_kernels.hip).  crt_denoise* and crt_denoise_variance* are one call: `guided` says which, and
+// the plain filter is the one without variance planes, its sigma_color where the guided one has sigma_luminance
 const crt_denoise_params kDenoiseDefaults = { 5u, 4.0f, 0.3f, 0.05f, 1u };
+const crt_denoise_variance_params kDenoiseVarianceDefaults = { 5u, 0.0625f, 0.3f, 0.05f, 1u };
 
-int checkDenoise(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* rgb, const void* normal, const void* albedo, const void* t,
-                 const void* out, const crt_denoise_params& prm)
+int checkDenoise(crt_ctx* c, const char* what, bool guided, uint32_t w, uint32_t h, const void* rgb, const void* normal, const void* albedo,
+                 const void* t, const void* variance, const void* out, const crt_denoise_params& prm)
 {
     if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
+    if (guided && !(prm.sigma_color > 0.0f))
+        return fail(c, CRT_EINVAL, "%s: sigma_luminance = %g must be > 0 (+inf switches the term off)", what, static_cast<double>(prm.sigma_color));
     if (const int rc = checkFrameSize(c, what, w, h)) return rc;
     if (prm.iterations < 1u || prm.iterations > 8u) return fail(c, CRT_EINVAL, "%s: iterations = %u is outside 1..8", what, prm.iterations);
     const struct { const char* name; float v; } sig[] = { { "sigma_color", prm.sigma_color }, { "sigma_normal", prm.sigma_normal }, { "sigma_depth", prm.sigma_depth } };
     for (const auto& s : sig)
         if (!(s.v > 0.0f)) return fail(c, CRT_EINVAL, "%s: %s = %g must be > 0 (+inf switches the term off)", what, s.name, static_cast<double>(s.v));
     if (prm.demodulate > 1u) return fail(c, CRT_EINVAL, "%s: demodulate = %u is neither 0 nor 1", what, prm.demodulate);
-    if (!rgb || !normal || !albedo || !t || !out) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
+    if (!rgb || !normal || !albedo || !t || !out || (guided && !variance)) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
     return CRT_OK;
 }
 
@@ -2137,45 +2142,82 @@ float invSquare(float sigma)
     return static_cast<float>(std::min(1.0 / (s * s), static_cast<double>(FLT_MAX)));
 }
 
-// what both filters do around their kernel: the stream's query arena as three float4 planes {guide, colour[0], colour[1]}, the
-// launch (a HIP error code), and the arena's last use, recorded before a timed call synchronises
-static int runOverDenoiseArena(crt_ctx* c, const char* what, uint32_t w, uint32_t h, void*& guide, void* (&colour)[2], const std::function<int()>& launch,
-                               crt_frame_stats* stats)
+// the stream's query arena as three float4 planes {guide, colour[0], colour[1]}, the launch, and the arena's last use, recorded
+// before a timed call synchronises
+int runDenoise(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* d_rgb, const void* d_normal, const void* d_albedo, const void* d_t,
+               const void* d_variance, void* d_out, void* d_varianceOut, const crt_denoise_params& prm, crt_frame_stats* stats)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t plane = up256(static_cast<size_t>(w) * h * 16u);
     static_assert(crt::kDenoiseScratchPerPixel == 48u, "three float4 planes");
     crt_ctx::Arena* arena = nullptr;
     if (const int rc = takeArena(c, c->rayArena, 3u * plane, ++c->raySerial, true, arena)) return rc;
-    guide = arena->mem;
-    colour[0] = arena->mem + plane;
-    colour[1] = arena->mem + 2u * plane;
-    return runTimed(c, what, stats, [&] {
-        const int hrc = launch();
-        if (hrc != 0) return hrc;
-        arena->pending = true;
-        return static_cast<int>(hipEventRecord(arena->lastUse, c->stream));
-    });
-}
-
-int runDenoise(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* d_rgb, const void* d_normal, const void* d_albedo, const void* d_t,
-               void* d_out, const crt_denoise_params& prm, crt_frame_stats* stats)
-{
     crt::DenoiseParams p;
     std::memset(&p, 0, sizeof(p));
     p.width = w;
     p.height = h;
     p.iterations = prm.iterations;
     p.demodulate = prm.demodulate;
-    p.inv_sigma_color2 = invSquare(prm.sigma_color);
+    p.sigma_first = d_variance ? prm.sigma_color : invSquare(prm.sigma_color);
     p.inv_sigma_normal2 = invSquare(prm.sigma_normal);
     p.sigma_depth = prm.sigma_depth;
     p.rgb = static_cast<const float*>(d_rgb);
     p.normal = static_cast<const float*>(d_normal);
     p.albedo = static_cast<const float*>(d_albedo);
     p.t = static_cast<const float*>(d_t);
+    p.variance = static_cast<const float*>(d_variance);
     p.out = static_cast<float*>(d_out);
-    return runOverDenoiseArena(c, what, w, h, p.guide, p.colour, [&] { return crt::launchDenoise(p, c->stream); }, stats);
+    p.varianceOut = static_cast<float*>(d_varianceOut);
+    p.guide = arena->mem;
+    p.colour[0] = arena->mem + plane;
+    p.colour[1] = arena->mem + 2u * plane;
+    return runTimed(c, what, stats, [&] {
+        const int hrc = crt::launchDenoise(p, c->stream);
+        if (hrc != 0) return hrc;
+        arena->pending = true;
+        return static_cast<int>(hipEventRecord(arena->lastUse, c->stream));
+    });
+}
+
+// The device forms ...
+static int denoiseDevice(crt_ctx* c, const char* what, bool guided, uint32_t w, uint32_t h, const void* d_rgb, const void* d_normal,
+                         const void* d_albedo, const void* d_t, const void* d_variance, void* d_out, void* d_varianceOut,
+                         const crt_denoise_params& prm, crt_frame_stats* stats)
+{
+    int rc = checkDenoise(c, what, guided, w, h, d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, prm);
+    if (rc) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, d_varianceOut }, 4u)) != CRT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = runDenoise(c, what, w, h, d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, d_varianceOut, prm, stats)) != CRT_OK) return rc;
+    stampTotal(stats, t0);
+    return CRT_OK;
+}
+
+// ... and the host forms: staged through the context's query staging buffer {rgb | normal | albedo | t | variance}, filtered in
+// place; synchronous
+static int denoiseHost(crt_ctx* c, const char* what, bool guided, uint32_t w, uint32_t h, const float* rgb, const float* normal,
+                       const float* albedo, const float* t, const float* variance, float* out, float* varianceOut,
+                       const crt_denoise_params& prm, crt_frame_stats* stats)
+{
+    int rc = checkDenoise(c, what, guided, w, h, rgb, normal, albedo, t, variance, out, prm);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t nn = static_cast<size_t>(w) * h;
+    const StagePlane planes[7] = { { rgb, nullptr, nn * 12u }, { normal, nullptr, nn * 12u }, { albedo, nullptr, nn * 12u }, { t, nullptr, nn * 4u },
+                                   { variance, nullptr, nn * 4u }, { nullptr, out, nn * 12u, 0 }, { nullptr, varianceOut, nn * 4u, 4 } };
+    void* dev[7];
+    if ((rc = stageBegin(c, planes, 7, dev)) != CRT_OK) return rc;
+    if ((rc = runDenoise(c, what, w, h, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], prm, stats)) != CRT_OK) return rc;
+    if ((rc = stageEnd(c, planes, 7, dev)) != CRT_OK) return rc;
+    stampTotal(stats, t0);
+    return CRT_OK;
+}
+
+// the guided filter's parameters in the plain filter's struct
+static crt_denoise_params guidedParams(const crt_denoise_variance_params* params)
+{
+    const crt_denoise_variance_params prm = params ? *params : kDenoiseVarianceDefaults;
+    return { prm.iterations, prm.sigma_luminance, prm.sigma_normal, prm.sigma_depth, prm.demodulate };
 }
 
 } // namespace
@@ -2242,35 +2284,14 @@ int crt_frame_guides(crt_ctx* c, uint32_t w, uint32_t h, float* normal, float* a
 int crt_denoise_device(crt_ctx* c, uint32_t w, uint32_t h, const void* d_rgb, const void* d_normal, const void* d_albedo, const void* d_t,
                        void* d_out, const crt_denoise_params* params, crt_frame_stats* stats)
 {
-    const char* what = "crt_denoise_device";
-    const crt_denoise_params prm = params ? *params : kDenoiseDefaults;
-    int rc = checkDenoise(c, what, w, h, d_rgb, d_normal, d_albedo, d_t, d_out, prm);
-    if (rc) return rc;
-    if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_out }, 4u)) != CRT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    if ((rc = runDenoise(c, what, w, h, d_rgb, d_normal, d_albedo, d_t, d_out, prm, stats)) != CRT_OK) return rc;
-    stampTotal(stats, t0);
-    return CRT_OK;
+    return denoiseDevice(c, "crt_denoise_device", false, w, h, d_rgb, d_normal, d_albedo, d_t, nullptr, d_out, nullptr,
+                         params ? *params : kDenoiseDefaults, stats);
 }
 
-// host buffers: staged through the context's query staging buffer {rgb | normal | albedo | t}, filtered in place; synchronous
 int crt_denoise(crt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const float* normal, const float* albedo, const float* t, float* out,
                 const crt_denoise_params* params, crt_frame_stats* stats)
 {
-    const char* what = "crt_denoise";
-    const crt_denoise_params prm = params ? *params : kDenoiseDefaults;
-    int rc = checkDenoise(c, what, w, h, rgb, normal, albedo, t, out, prm);
-    if (rc) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t nn = static_cast<size_t>(w) * h;
-    const StagePlane planes[5] = { { rgb, nullptr, nn * 12u }, { normal, nullptr, nn * 12u }, { albedo, nullptr, nn * 12u }, { t, nullptr, nn * 4u },
-                                   { nullptr, out, nn * 12u, 0 } };
-    void* dev[5];
-    if ((rc = stageBegin(c, planes, 5, dev)) != CRT_OK) return rc;
-    if ((rc = runDenoise(c, what, w, h, dev[0], dev[1], dev[2], dev[3], dev[4], prm, stats)) != CRT_OK) return rc;
-    if ((rc = stageEnd(c, planes, 5, dev)) != CRT_OK) return rc;
-    stampTotal(stats, t0);
-    return CRT_OK;
+    return denoiseHost(c, "crt_denoise", false, w, h, rgb, normal, albedo, t, nullptr, out, nullptr, params ? *params : kDenoiseDefaults, stats);
 }
 
 namespace {
@@ -2441,44 +2462,8 @@ int crt_temporal_accumulate_motion(crt_ctx* c, uint32_t w, uint32_t h, const flo
 
 namespace {
 
-// ---- variance: luminance moments in the temporal pass, a variance-guided filter (temporal_kernels.hip, variance_kernels.hip)
+// ---- variance: luminance moments in the temporal pass (temporal_kernels.hip); the variance-guided filter is denoiseDevice / denoiseHost
 const crt_temporal_variance_params kTemporalVarianceDefaults = { { 0.1f, 0.01f, 0.9f, 64u, 1u }, 0.2f, 4u };
-const crt_denoise_variance_params kDenoiseVarianceDefaults = { 5u, 0.0625f, 0.3f, 0.05f, 1u };
-
-int checkDenoiseVariance(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* rgb, const void* normal, const void* albedo,
-                         const void* t, const void* variance, const void* out, const crt_denoise_variance_params& prm)
-{
-    const crt_denoise_params plain = { prm.iterations, prm.sigma_luminance, prm.sigma_normal, prm.sigma_depth, prm.demodulate };
-    if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
-    if (!(prm.sigma_luminance > 0.0f))
-        return fail(c, CRT_EINVAL, "%s: sigma_luminance = %g must be > 0 (+inf switches the term off)", what, static_cast<double>(prm.sigma_luminance));
-    if (const int rc = checkDenoise(c, what, w, h, rgb, normal, albedo, t, out, plain)) return rc;
-    if (!variance) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
-    return CRT_OK;
-}
-
-int runDenoiseVariance(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* d_rgb, const void* d_normal, const void* d_albedo,
-                       const void* d_t, const void* d_variance, void* d_out, void* d_varianceOut, const crt_denoise_variance_params& prm,
-                       crt_frame_stats* stats)
-{
-    crt::DenoiseVarianceParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.width = w;
-    p.height = h;
-    p.iterations = prm.iterations;
-    p.demodulate = prm.demodulate;
-    p.sigma_luminance = prm.sigma_luminance;
-    p.inv_sigma_normal2 = invSquare(prm.sigma_normal);
-    p.sigma_depth = prm.sigma_depth;
-    p.rgb = static_cast<const float*>(d_rgb);
-    p.normal = static_cast<const float*>(d_normal);
-    p.albedo = static_cast<const float*>(d_albedo);
-    p.t = static_cast<const float*>(d_t);
-    p.variance = static_cast<const float*>(d_variance);
-    p.out = static_cast<float*>(d_out);
-    p.varianceOut = static_cast<float*>(d_varianceOut);
-    return runOverDenoiseArena(c, what, w, h, p.guide, p.colour, [&] { return crt::launchDenoiseVariance(p, c->stream); }, stats);
-}
 
 } // namespace
 
@@ -2508,35 +2493,14 @@ int crt_denoise_variance_device(crt_ctx* c, uint32_t w, uint32_t h, const void* 
                                 const void* d_variance, void* d_out, void* d_varianceOut, const crt_denoise_variance_params* params,
                                 crt_frame_stats* stats)
 {
-    const char* what = "crt_denoise_variance_device";
-    const crt_denoise_variance_params prm = params ? *params : kDenoiseVarianceDefaults;
-    int rc = checkDenoiseVariance(c, what, w, h, d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, prm);
-    if (rc) return rc;
-    if ((rc = checkDevicePointers(c, what, { d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, d_varianceOut }, 4u)) != CRT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    if ((rc = runDenoiseVariance(c, what, w, h, d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, d_varianceOut, prm, stats)) != CRT_OK) return rc;
-    stampTotal(stats, t0);
-    return CRT_OK;
+    return denoiseDevice(c, "crt_denoise_variance_device", true, w, h, d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, d_varianceOut,
+                         guidedParams(params), stats);
 }
 
-// host buffers: staged through the context's query staging buffer {rgb | normal | albedo | t | variance}, filtered in place; synchronous
 int crt_denoise_variance(crt_ctx* c, uint32_t w, uint32_t h, const float* rgb, const float* normal, const float* albedo, const float* t,
                          const float* variance, float* out, float* varianceOut, const crt_denoise_variance_params* params, crt_frame_stats* stats)
 {
-    const char* what = "crt_denoise_variance";
-    const crt_denoise_variance_params prm = params ? *params : kDenoiseVarianceDefaults;
-    int rc = checkDenoiseVariance(c, what, w, h, rgb, normal, albedo, t, variance, out, prm);
-    if (rc) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t nn = static_cast<size_t>(w) * h;
-    const StagePlane planes[7] = { { rgb, nullptr, nn * 12u }, { normal, nullptr, nn * 12u }, { albedo, nullptr, nn * 12u }, { t, nullptr, nn * 4u },
-                                   { variance, nullptr, nn * 4u }, { nullptr, out, nn * 12u, 0 }, { nullptr, varianceOut, nn * 4u, 4 } };
-    void* dev[7];
-    if ((rc = stageBegin(c, planes, 7, dev)) != CRT_OK) return rc;
-    if ((rc = runDenoiseVariance(c, what, w, h, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], prm, stats)) != CRT_OK) return rc;
-    if ((rc = stageEnd(c, planes, 7, dev)) != CRT_OK) return rc;
-    stampTotal(stats, t0);
-    return CRT_OK;
+    return denoiseHost(c, "crt_denoise_variance", true, w, h, rgb, normal, albedo, t, variance, out, varianceOut, guidedParams(params), stats);
 }
 
 int crt_closest_points_device(crt_ctx* c, uint32_t n, const void* d_points, void* d_dist, void* d_point, void* d_uv, void* d_inst,

@@ -282,28 +282,32 @@ struct CameraRayParams {
     void* rays;                   // n records of 32 bytes, 16-byte aligned
 };
 int launchCameraRays(const CameraRayParams& p, ihipStream_t* stream);
-// the edge-avoiding a-trous filter (denoise_kernels.hip; crt_denoise*).  Scratch: three float4 planes of width * height --
-// the guide plane {n.xyz, t} and two colour planes {c.rgb, live} that the passes ping-pong between
+// the edge-avoiding a-trous filter and its variance-guided form (denoise_kernels.hip; crt_denoise*, crt_denoise_variance*).
+// Scratch: three float4 planes of width * height -- the guide plane {n.xyz, t} and two colour planes {c.rgb, v} that the passes
+// ping-pong between; v >= 0: live (the variance; 0 for the plain filter), v = -1: not live
 struct DenoiseParams {
     uint32_t width, height;
     uint32_t iterations;          // 1..8
     uint32_t demodulate;          // 0 / 1
-    float inv_sigma_color2;       // 1 / sigma_color^2 of pass 0 (pass i: x 4^i); 0 switches the term off
+    float sigma_first;            // the first term's scale.  Plain: 1 / sigma_color^2 of pass 0 (pass i: x 4^i); 0 switches the term off.
+                                  // Variance: sigma_luminance as given (+inf switches the term off)
     float inv_sigma_normal2;      // 1 / sigma_normal^2
     float sigma_depth;            // as given (+inf switches the term off)
     const float* rgb;             // 3 floats per pixel
     const float* normal;          // 3
     const float* albedo;          // 3
     const float* t;               // 1
+    const float* variance;        // 1; null: the plain filter
     float* out;                   // 3; may be rgb
+    float* varianceOut;           // 1; may be variance; may be null
     void* guide;                  // scratch planes, 16 bytes per pixel each
     void* colour[2];
 };
 constexpr size_t kDenoiseScratchPerPixel = 48;
 // pack, iterations - 1 passes, and the last pass fused with the multiply-back
 int launchDenoise(const DenoiseParams& p, ihipStream_t* stream);
-// temporal reprojection (temporal_kernels.hip; crt_temporal_accumulate*): one kernel, no scratch.  A history record is two
-// float4 per pixel, {c.rgb, len} and {n.xyz, t}
+// temporal reprojection (temporal_kernels.hip; crt_temporal_accumulate*, crt_temporal_variance*): no scratch.  A history record
+// is two float4 per pixel, {c.rgb, len} and {n.xyz, t}
 struct TemporalParams {
     float posCur[3], rotCur[9];   // the camera of this frame
     float posPrev[3], rotPrev[9]; // the camera the history was taken with
@@ -328,30 +332,8 @@ struct TemporalParams {
     float alphaMoments;
     float minHistory;             // 1 .. 2^24, exact as a float
 };
+// the reprojection kernel and, when momNext is set, step V6 behind it: the variance from the records the first one wrote
 int launchTemporal(const TemporalParams& p, ihipStream_t* stream);
-// step V6 of crt_temporal_variance* (variance_kernels.hip): the variance from the records launchTemporal wrote; launchTemporal
-// calls it when momNext is set
-int launchTemporalVariance(const TemporalParams& p, ihipStream_t* stream);
-// the variance-guided a-trous filter (variance_kernels.hip; crt_denoise_variance*).  Scratch as for DenoiseParams: the guide
-// plane {n.xyz, t} and two colour planes {c.rgb, v}, v < 0: not live
-struct DenoiseVarianceParams {
-    uint32_t width, height;
-    uint32_t iterations;          // 1..8
-    uint32_t demodulate;          // 0 / 1
-    float sigma_luminance;        // as given (+inf switches the term off)
-    float inv_sigma_normal2;      // 1 / sigma_normal^2
-    float sigma_depth;            // as given (+inf switches the term off)
-    const float* rgb;             // 3 floats per pixel
-    const float* normal;          // 3
-    const float* albedo;          // 3
-    const float* t;               // 1
-    const float* variance;        // 1
-    float* out;                   // 3; may be rgb
-    float* varianceOut;           // 1; may be variance; may be null
-    void* guide;                  // scratch planes, 16 bytes per pixel each
-    void* colour[2];
-};
-int launchDenoiseVariance(const DenoiseVarianceParams& p, ihipStream_t* stream);
 // previous points of hits (motion_kernels.hip; crt_previous_points*, crt_frame_motion*): one lane per record, the triangle's
 // vertices of the last snapshot weighted by the hit's barycentrics
 struct PreviousPointsParams {

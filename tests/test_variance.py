@@ -694,6 +694,33 @@ def test_denoise_variance_equals_the_reference(pkg, renderer, size):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("size", [(1, 1), (1, 70), (130, 5), (37, 23)], ids=lambda s: "%dx%d" % s)
+def test_with_their_first_term_off_the_two_filters_are_one(pkg, renderer, size):
+    """denoise_device with sigma_color = +inf and denoise_variance_device with variance 0 and sigma_luminance = +inf give the same
+    bytes.  Both are one kernel (denoise_kernels.hip) that differs in the exponent's first term: |dc|^2 x 0 against |d lum| x 0,
+    both +0 on finite colours; the normal and depth terms, the weights, the sums and the multiply-back are the same expressions,
+    and with a variance of 0 the two liveness rules agree."""
+    import torch
+    w, h = size
+    s = R.synthetic(w, h, edge=20 if (w, h) == (37, 23) else None)
+    d = {g: _device(torch, s[g]) for g in GUIDES}
+    ptrs = [d[g].data_ptr() for g in GUIDES]
+    d_zero = torch.zeros((h, w), dtype=torch.float32, device="cuda")
+    for iterations in (1, 5):
+        for demodulate in (0, 1):
+            plain = torch.full((h, w, 3), -7.0, dtype=torch.float32, device="cuda")
+            guided = torch.full((h, w, 3), -9.0, dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()
+            renderer.denoise_device(w, h, *ptrs, plain.data_ptr(), iterations=iterations, demodulate=demodulate, sigma_color=float("inf"))
+            renderer.denoise_variance_device(w, h, *ptrs, d_zero.data_ptr(), guided.data_ptr(), None, iterations=iterations,
+                                             demodulate=demodulate, sigma_luminance=float("inf"))
+            renderer.synchronize()
+            assert torch.equal(plain.view(torch.int32), guided.view(torch.int32)), (size, iterations, demodulate)
+    if (w, h) == (37, 23):
+        assert s["miss"].sum() == 6 and np.array_equal(plain.cpu().numpy()[s["miss"]], s["rgb"][s["miss"]]), "the dead block"
+
+
+@pytest.mark.gpu
 def test_errors(pkg, scenes, vref, renderer):
     """every CRT_EINVAL case of both families launches nothing and leaves sentinel-filled outputs untouched; a context without a
     scene works; stats carry times and no counts"""
