@@ -128,7 +128,7 @@ struct GlobalTap {
 // (refillMin = CRT_REFILL_MIN, traversal.hip.h)
 // GLOBAL: the queues are shared by every wavefront of the launch (pathTraceKernel): entries are taken with one atomic on the
 // queue's cursor per refill and appended with one atomic on the other queue's length per retirement.
-template <bool COUNT, class L, bool GLOBAL>
+template <bool COUNT, bool GLOBAL>
 __device__ __forceinline__ void streamClosest(const float4* __restrict__ nodes, const float4* __restrict__ tris, uint32_t n_nodes,
                                               const PathScratch& q, uint32_t nTrace, uint32_t& nShade, F3 miss, Stack& stack, int innerMin,
                                               uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, uint32_t& cntClosest)
@@ -137,7 +137,7 @@ __device__ __forceinline__ void streamClosest(const float4* __restrict__ nodes, 
     Hit h;
     h.t = kTMax; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.gid = 0;
     float tcull = kTMax * kCullPad;
-    int cur = L::kDone;
+    int cur = LayLegacy::kDone;
     bool have = false;   // this lane holds a ray (being traced, or finished and not yet retired)
     uint32_t my = 0;     // its index in the trace queue
     uint32_t next = 0;   // wave-uniform: first queue entry not yet handed to a lane
@@ -145,7 +145,7 @@ __device__ __forceinline__ void streamClosest(const float4* __restrict__ nodes, 
     tap.begin(nTrace, q.chunk);
     const unsigned long long all = __ballot(true);
     for (;;) {
-        const bool idle = cur == L::kDone;
+        const bool idle = cur == LayLegacy::kDone;
         const unsigned long long idleMask = __ballot(idle);
         const bool more = GLOBAL ? tap.more() : next < nTrace;
         if (idleMask == all || (more && static_cast<uint32_t>(__popcll(idleMask)) >= static_cast<uint32_t>(CRT_REFILL_MIN))) {
@@ -185,14 +185,14 @@ __device__ __forceinline__ void streamClosest(const float4* __restrict__ nodes, 
                     h.t = kTMax; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.gid = 0;
                     tcull = kTMax * kCullPad;
                     stack.sp = 0;
-                    cur = n_nodes ? L::kRoot : L::kDone;
+                    cur = n_nodes ? LayLegacy::kRoot : LayLegacy::kDone;
                     if (COUNT) cntClosest++;
                 }
             }
             next += static_cast<uint32_t>(__popcll(idleMask));
             if (__ballot(have) == 0ull && !(GLOBAL && tap.more())) break; // queue empty and every ray retired
         }
-        closestIteration<COUNT, L, 8>(nodes, tris, r, 0.0f, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris);
+        closestIteration<COUNT, 8>(nodes, tris, r, 0.0f, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris);
     }
     if (GLOBAL) tap.flush(q.shade + q.B);
 }
@@ -202,7 +202,7 @@ __device__ __forceinline__ void streamClosest(const float4* __restrict__ nodes, 
 // positive cosine, in light order: one any-hit shadow ray, its contribution added when unoccluded (oracle: direct_light) ->
 // retire (radiance update, next direction drawn, appended to the trace queue or written out as finished).  Shadow rays end at
 // their first hit, so their traversals differ even more in length than the bounce rays': refilling keeps the wavefront full.
-template <bool COUNT, class L, bool GLOBAL>
+template <bool COUNT, bool GLOBAL>
 __device__ __forceinline__ void streamShade(const RenderParams& p, const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                             const PathScratch& q, uint32_t nShade, uint32_t& nTrace, Stack& stack, int innerMin,
                                             uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, uint32_t& cntShadow)
@@ -211,7 +211,7 @@ __device__ __forceinline__ void streamShade(const RenderParams& p, const float4*
     Ray sr = makeRay(f3(0.0f, 0.0f, 0.0f), f3(0.0f, 0.0f, 1.0f)); // the shadow ray in flight
     float dist = 0.0f, tcull = 0.0f, kcur = 0.0f;                  // its length, cull bound, and the light's weight if it arrives
     bool occluded = false;
-    int cur = L::kDone;
+    int cur = LayLegacy::kDone;
     bool have = false, diffuse = false, tracing = false, alive = false;
     float thrMul = 0.0f;  // 1: throughput *= albedo when the path goes on; -1: CONSTANT (radiance += throughput * albedo)
     uint32_t my = 0, li = 0;
@@ -222,7 +222,7 @@ __device__ __forceinline__ void streamShade(const RenderParams& p, const float4*
     tap.begin(nShade, q.chunk);
     const unsigned long long all = __ballot(true);
     for (;;) {
-        const bool idle = cur == L::kDone;
+        const bool idle = cur == LayLegacy::kDone;
         const unsigned long long idleMask = __ballot(idle);
         const bool more = GLOBAL ? tap.more() : next < nShade;
         if (idleMask == all || (more && static_cast<uint32_t>(__popcll(idleMask)) >= static_cast<uint32_t>(CRT_REFILL_MIN))) {
@@ -288,7 +288,7 @@ __device__ __forceinline__ void streamShade(const RenderParams& p, const float4*
                 Hit h;
                 const float4 a4 = q.shade[2u * q.B + idx];
                 h.t = a4.x; h.u = a4.y; h.v = a4.z; h.tri = __float_as_uint(a4.w); h.gid = 0;
-                const Surface sf = surfaceAt<L>(p, tris, r, h);
+                const Surface sf = surfaceAt(p, tris, r, h);
                 N = sf.N;
                 albedo = sf.albedo;
                 diffuse = false; alive = false; thrMul = 0.0f; li = 0;
@@ -313,7 +313,7 @@ __device__ __forceinline__ void streamShade(const RenderParams& p, const float4*
             }
             next += static_cast<uint32_t>(__popcll(mNew));
             // 4. the next light of every diffuse entry that is not waiting for a shadow ray
-            if ((cur == L::kDone) & have & diffuse & !tracing) {
+            if ((cur == LayLegacy::kDone) & have & diffuse & !tracing) {
                 while (li < p.n_lights) {
                     const LightRec Lt = lights[li];
                     const F3 Lv = sub3(f3(Lt.x, Lt.y, Lt.z), Po);
@@ -330,7 +330,7 @@ __device__ __forceinline__ void streamShade(const RenderParams& p, const float4*
                         occluded = false;
                         tracing = true;
                         stack.sp = 0;
-                        cur = p.n_nodes ? L::kRoot : L::kDone;
+                        cur = p.n_nodes ? LayLegacy::kRoot : LayLegacy::kDone;
                         if (COUNT) cntShadow++;
                         break;
                     }
@@ -339,7 +339,7 @@ __device__ __forceinline__ void streamShade(const RenderParams& p, const float4*
             }
             if (__ballot(have) == 0ull && !(GLOBAL && tap.more())) break;
         }
-        anyIteration<COUNT, L, 8>(nodes, tris, sr, 0.0f, dist, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris);
+        anyIteration<COUNT, 8>(nodes, tris, sr, 0.0f, dist, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris);
     }
     if (GLOBAL) tap.flush(q.trace + q.B);
 }
@@ -362,7 +362,7 @@ __device__ __forceinline__ size_t accIndex(const RenderParams& p, uint32_t tile_
                      : static_cast<size_t>(py) * p.width + px;
 }
 
-template <bool COUNT, class L, bool ACC>
+template <bool COUNT, bool ACC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_PATH_WAVES_PER_EU, 8))) void pathKernel(const RenderParams p)
 {
     extern __shared__ int s_stack[];
@@ -467,7 +467,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_PATH_WAV
                     const float jx = rngNext(rng), jy = rngNext(rng);
                     r = makeRay(f3(camPos[0], camPos[1], camPos[2]), rayDirJ(camRot, px, py, jx, jy, static_cast<float>(p.width), static_cast<float>(p.height)));
                     if (COUNT) cntClosest++;
-                    traceClosest<COUNT, L>(nodes, tris, p.n_nodes, r, kTMin, kTMax, stack, innerMin, h, iters, cntNodes, cntTris);
+                    traceClosest<COUNT>(nodes, tris, p.n_nodes, r, kTMin, kTMax, stack, innerMin, h, iters, cntNodes, cntTris);
                     isHit = h.t < kTMax;
                     // radiance so far: a miss ends the path with throughput (1) x miss colour; a hit starts from nothing, throughput 1
                     q.done[id] = isHit ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(fmaf(1.0f, miss.x, 0.0f), fmaf(1.0f, miss.y, 0.0f), fmaf(1.0f, miss.z, 0.0f), 0.0f);
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_PATH_WAV
                         const size_t pix = static_cast<size_t>(py) * p.width + px;
                         uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
                         if (isHit) {
-                            const float4* T = L::triPtr(tris, h.tri);
+                            const float4* T = LayLegacy::triPtr(tris, h.tri);
                             inst = __float_as_uint(T[0].w);
                             prim = __float_as_uint(T[1].w);
                         }
@@ -500,11 +500,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_PATH_WAV
         while (nShade != 0u) {
             uint32_t nTrace = 0;
             CRT_PATH_PROF_BEGIN()
-            streamShade<COUNT, L, false>(p, nodes, tris, q, nShade, nTrace, stack, static_cast<int>(p.tune_inner_min_any), iters, cntNodes, cntTris, cntShadow); // stage B
+            streamShade<COUNT, false>(p, nodes, tris, q, nShade, nTrace, stack, static_cast<int>(p.tune_inner_min_any), iters, cntNodes, cntTris, cntShadow); // stage B
             CRT_PATH_PROF_END(1)
             nShade = 0;
             CRT_PATH_PROF_BEGIN()
-            streamClosest<COUNT, L, false>(nodes, tris, p.n_nodes, q, nTrace, nShade, miss, stack, innerMin, iters, cntNodes, cntTris, cntClosest); // stage C
+            streamClosest<COUNT, false>(nodes, tris, p.n_nodes, q, nTrace, nShade, miss, stack, innerMin, iters, cntNodes, cntTris, cntClosest); // stage C
             CRT_PATH_PROF_END(2)
         }
         // ---- this pass's samples join the running sums in sample order; after the last pass: average, quantise, store
@@ -659,7 +659,7 @@ __device__ __forceinline__ void wfCount(const RenderParams& p, uint32_t cntNodes
 #define CRT_WF_TRACE_WAVES 7
 #endif
 
-template <bool COUNT, class L, bool ACC> // ACC: the call's samples start at acc_base (see pathKernel)
+template <bool COUNT, bool ACC> // ACC: the call's samples start at acc_base (see pathKernel)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WF_CAMERA_WAVES, 8))) void pathCameraKernel(const RenderParams p)
 {
     extern __shared__ int s_stack[];
@@ -708,7 +708,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WF_CAMER
                 const float jx = rngNext(rng), jy = rngNext(rng);
                 r = makeRay(f3(camPos[0], camPos[1], camPos[2]), rayDirJ(camRot, px, py, jx, jy, static_cast<float>(p.width), static_cast<float>(p.height)));
                 if (COUNT) cntClosest++;
-                traceClosest<COUNT, L>(nodes, tris, p.n_nodes, r, kTMin, kTMax, stack, innerMin, h, iters, cntNodes, cntTris);
+                traceClosest<COUNT>(nodes, tris, p.n_nodes, r, kTMin, kTMax, stack, innerMin, h, iters, cntNodes, cntTris);
                 isHit = h.t < kTMax;
                 // radiance so far: a miss ends the path with throughput (1) x miss colour; a hit starts from nothing, throughput 1
                 q.done[id] = isHit ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(fmaf(1.0f, miss.x, 0.0f), fmaf(1.0f, miss.y, 0.0f), fmaf(1.0f, miss.z, 0.0f), 0.0f);
@@ -717,7 +717,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WF_CAMER
                     const size_t pix = static_cast<size_t>(py) * p.width + px;
                     uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
                     if (isHit) {
-                        const float4* T = L::triPtr(tris, h.tri);
+                        const float4* T = LayLegacy::triPtr(tris, h.tri);
                         inst = __float_as_uint(T[0].w);
                         prim = __float_as_uint(T[1].w);
                     }
@@ -740,7 +740,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WF_CAMER
     wfCount<COUNT>(p, cntNodes, cntTris, 0u, cntClosest);
 }
 
-template <bool COUNT, class L>
+template <bool COUNT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WF_SHADE_WAVES, 8))) void pathShadeKernel(const RenderParams p)
 {
     extern __shared__ int s_stack[];
@@ -751,12 +751,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WF_SHADE
     q.take = wfQueueCursor(p, p.wf_queue);
     q.put = wfQueueLength(p, p.wf_queue + 1u);
     uint32_t cntNodes = 0, cntTris = 0, cntShadow = 0, iters = 0, nTrace = 0;
-    streamShade<COUNT, L, true>(p, reinterpret_cast<const float4*>(p.nodes), reinterpret_cast<const float4*>(p.tris), q, nShade, nTrace, stack,
+    streamShade<COUNT, true>(p, reinterpret_cast<const float4*>(p.nodes), reinterpret_cast<const float4*>(p.tris), q, nShade, nTrace, stack,
                                 static_cast<int>(p.tune_inner_min_any), iters, cntNodes, cntTris, cntShadow);
     wfCount<COUNT>(p, cntNodes, cntTris, cntShadow, 0u);
 }
 
-template <bool COUNT, class L>
+template <bool COUNT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WF_TRACE_WAVES, 8))) void pathTraceKernel(const RenderParams p)
 {
     extern __shared__ int s_stack[];
@@ -767,7 +767,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WF_TRACE
     q.take = wfQueueCursor(p, p.wf_queue);
     q.put = wfQueueLength(p, p.wf_queue + 1u);
     uint32_t cntNodes = 0, cntTris = 0, cntClosest = 0, iters = 0, nShade = 0;
-    streamClosest<COUNT, L, true>(reinterpret_cast<const float4*>(p.nodes), reinterpret_cast<const float4*>(p.tris), p.n_nodes, q, nTrace, nShade,
+    streamClosest<COUNT, true>(reinterpret_cast<const float4*>(p.nodes), reinterpret_cast<const float4*>(p.tris), p.n_nodes, q, nTrace, nShade,
                                   f3(p.miss[0], p.miss[1], p.miss[2]), stack, static_cast<int>(p.tune_inner_min), iters, cntNodes, cntTris, cntClosest);
     wfCount<COUNT>(p, cntNodes, cntTris, 0u, cntClosest);
 }
@@ -863,7 +863,7 @@ uint32_t pathGridSize(const RenderParams& p)
         hipDeviceProp_t prop;
         const size_t lds = static_cast<size_t>(kStackEntries) * 64u * sizeof(int); // worst case LDS: the grid must fit any stack_entries
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, reinterpret_cast<const void*>(&pathKernel<false, LayLegacy, false>), 64, lds) != hipSuccess || perCu <= 0) {
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, reinterpret_cast<const void*>(&pathKernel<false, false>), 64, lds) != hipSuccess || perCu <= 0) {
             perCu = 16;
             cus = 256;
         } else {
@@ -936,8 +936,8 @@ uint32_t residentGroups(const void* kernel, int& cache, uint32_t stackEntries)
 uint32_t wfResident(int which, uint32_t stackEntries) // 0 camera, 1 shade, 2 trace; the LDS part of the stacks decides with the registers
 {
     static int cache[3][kStackEntries + 1] = {};
-    const void* k[3] = { reinterpret_cast<const void*>(&pathCameraKernel<false, LayLegacy, false>), reinterpret_cast<const void*>(&pathShadeKernel<false, LayLegacy>),
-                         reinterpret_cast<const void*>(&pathTraceKernel<false, LayLegacy>) };
+    const void* k[3] = { reinterpret_cast<const void*>(&pathCameraKernel<false, false>), reinterpret_cast<const void*>(&pathShadeKernel<false>),
+                         reinterpret_cast<const void*>(&pathTraceKernel<false>) };
     const uint32_t e = stackEntries > kStackEntries ? kStackEntries : stackEntries;
     return residentGroups(k[which], cache[which][e], e);
 }
@@ -961,22 +961,22 @@ int launchPathWavefront(const RenderParams& p0, bool counting, ihipStream_t* str
             const uint32_t maxWaves = p.wf_items * perItem / 64u; // no stage has more entries than the pass has paths
             const uint32_t camGrid = p.wf_items < wfResident(0, p.stack_entries) ? p.wf_items : wfResident(0, p.stack_entries);
             if (p.acc_sum) {
-                if (counting) hipLaunchKernelGGL((pathCameraKernel<true, LayLegacy, true>), dim3(camGrid), block, lds, stream, p);
-                else hipLaunchKernelGGL((pathCameraKernel<false, LayLegacy, true>), dim3(camGrid), block, lds, stream, p);
+                if (counting) hipLaunchKernelGGL((pathCameraKernel<true, true>), dim3(camGrid), block, lds, stream, p);
+                else hipLaunchKernelGGL((pathCameraKernel<false, true>), dim3(camGrid), block, lds, stream, p);
             } else {
-                if (counting) hipLaunchKernelGGL((pathCameraKernel<true, LayLegacy, false>), dim3(camGrid), block, lds, stream, p);
-                else hipLaunchKernelGGL((pathCameraKernel<false, LayLegacy, false>), dim3(camGrid), block, lds, stream, p);
+                if (counting) hipLaunchKernelGGL((pathCameraKernel<true, false>), dim3(camGrid), block, lds, stream, p);
+                else hipLaunchKernelGGL((pathCameraKernel<false, false>), dim3(camGrid), block, lds, stream, p);
             }
             for (uint32_t b = 0; b <= p.max_bounces; b++) {
                 p.wf_queue = 2u * b;
                 const uint32_t sg = maxWaves < wfResident(1, p.stack_entries) ? maxWaves : wfResident(1, p.stack_entries);
-                if (counting) hipLaunchKernelGGL((pathShadeKernel<true, LayLegacy>), dim3(sg), block, lds, stream, p);
-                else hipLaunchKernelGGL((pathShadeKernel<false, LayLegacy>), dim3(sg), block, lds, stream, p);
+                if (counting) hipLaunchKernelGGL((pathShadeKernel<true>), dim3(sg), block, lds, stream, p);
+                else hipLaunchKernelGGL((pathShadeKernel<false>), dim3(sg), block, lds, stream, p);
                 if (b == p.max_bounces) break;
                 p.wf_queue = 2u * b + 1u;
                 const uint32_t tg = maxWaves < wfResident(2, p.stack_entries) ? maxWaves : wfResident(2, p.stack_entries);
-                if (counting) hipLaunchKernelGGL((pathTraceKernel<true, LayLegacy>), dim3(tg), block, lds, stream, p);
-                else hipLaunchKernelGGL((pathTraceKernel<false, LayLegacy>), dim3(tg), block, lds, stream, p);
+                if (counting) hipLaunchKernelGGL((pathTraceKernel<true>), dim3(tg), block, lds, stream, p);
+                else hipLaunchKernelGGL((pathTraceKernel<false>), dim3(tg), block, lds, stream, p);
             }
             if (p.acc_sum) hipLaunchKernelGGL(pathResolveKernel<true>, dim3(p.wf_items), block, 0, stream, p);
             else hipLaunchKernelGGL(pathResolveKernel<false>, dim3(p.wf_items), block, 0, stream, p);
@@ -996,11 +996,11 @@ int launchPath(const RenderParams& p, bool counting, ihipStream_t* stream)
     const dim3 grid(pathGridSize(p)), block(64);
     const size_t lds = static_cast<size_t>(p.stack_entries) * 64u * sizeof(int);
     if (p.acc_sum) {
-        if (counting) hipLaunchKernelGGL((pathKernel<true, LayLegacy, true>), grid, block, lds, stream, p);
-        else hipLaunchKernelGGL((pathKernel<false, LayLegacy, true>), grid, block, lds, stream, p);
+        if (counting) hipLaunchKernelGGL((pathKernel<true, true>), grid, block, lds, stream, p);
+        else hipLaunchKernelGGL((pathKernel<false, true>), grid, block, lds, stream, p);
     } else {
-        if (counting) hipLaunchKernelGGL((pathKernel<true, LayLegacy, false>), grid, block, lds, stream, p);
-        else hipLaunchKernelGGL((pathKernel<false, LayLegacy, false>), grid, block, lds, stream, p);
+        if (counting) hipLaunchKernelGGL((pathKernel<true, false>), grid, block, lds, stream, p);
+        else hipLaunchKernelGGL((pathKernel<false, false>), grid, block, lds, stream, p);
     }
     return static_cast<int>(hipGetLastError());
 }

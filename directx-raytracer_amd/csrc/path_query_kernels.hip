@@ -39,7 +39,6 @@ constexpr int kPathQueryWaves = CRT_PATH_QUERY_WAVES;
 
 template <bool CNT>
 struct PathJob {
-    using L = LayLegacy;
     static constexpr int kClosest = -1; // `light` while a closest-hit ray (the record's own, or a bounce ray) is walked
     static constexpr int kIdle = -2;    // no item, or a finished one
 
@@ -105,12 +104,12 @@ struct PathJob {
         store3(q.rad, f3(0.0f, 0.0f, 0.0f));
         store3(q.thr, f3(1.0f, 1.0f, 1.0f), pcgHash(pcgHash(rng)));
         // a record with a NaN or an empty interval is not traced: step() finishes it as a miss
-        cur = (queryRayOk(a, b, tlim, tmax) & (q.c.n_nodes != 0u)) ? L::kRoot : L::kDone;
+        cur = (queryRayOk(a, b, tlim, tmax) & (q.c.n_nodes != 0u)) ? LayLegacy::kRoot : LayLegacy::kDone;
     }
     __device__ __forceinline__ void finish()
     {
         light = kIdle;
-        cur = L::kDone;
+        cur = LayLegacy::kDone;
     }
     // the path goes on from Po in direction nd: the frames' bounce ray
     __device__ __forceinline__ void goOn(F3 Po, F3 nd)
@@ -120,7 +119,7 @@ struct PathJob {
         tlim = 0.0f;
         setHit(Hit{ kTMax, 0.0f, 0.0f, 0u, 0u });
         stack.sp = 0;
-        cur = L::kRoot; // (a path that goes on has hit a triangle: the tree is not empty)
+        cur = LayLegacy::kRoot; // (a path that goes on has hit a triangle: the tree is not empty)
         light = kClosest;
         if (CNT) cntBounce++;
     }
@@ -148,7 +147,7 @@ struct PathJob {
                 r = makeRay(Po, lt.Ld);
                 tlim = lt.dist;
                 stack.sp = 0;
-                cur = L::kRoot;
+                cur = LayLegacy::kRoot;
                 light = static_cast<int>(li);
                 if (CNT) cntShadow++;
                 return;
@@ -178,7 +177,7 @@ struct PathJob {
             if (sl == 0u) { // the hit outputs do not depend on the sample: the pass's first one writes them (NULL in later passes)
                 uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
                 if (isHit) {
-                    const float4* T = L::triPtr(tris, h.tri);
+                    const float4* T = LayLegacy::triPtr(tris, h.tri);
                     inst = __float_as_uint(T[0].w);
                     prim = __float_as_uint(T[1].w);
                 }
@@ -194,7 +193,7 @@ struct PathJob {
             finish();
             return;
         }
-        const Surface sf = surfaceAt<L>(q, tris, seg, h);
+        const Surface sf = surfaceAt(q, tris, seg, h);
         F3 Po = biasPoint(sf.P, sf.N, kShadowBias);
         if (sf.mtype == 4u) { // CONSTANT: emits and ends
             const F3 thr = load3(q.thr), Lr = load3(q.rad);
@@ -240,13 +239,13 @@ struct PathJob {
         if (light == kClosest) {
             Hit h = hit();
             float tcull = cullBound(h.t); // (closestIteration sets t * kCullPad on an accepted hit: the same value for t >= 0)
-            closestIteration<COUNT, L, 8>(nodes, tris, r, tlim, tcull, stack, static_cast<int>(q.c.inner_min), h, cur, iters, cntNodes, cntTris);
+            closestIteration<COUNT, 8>(nodes, tris, r, tlim, tcull, stack, static_cast<int>(q.c.inner_min), h, cur, iters, cntNodes, cntTris);
             setHit(h);
-            if (cur == L::kDone) endClosest();
+            if (cur == LayLegacy::kDone) endClosest();
         } else if (light >= 0) {
             bool occluded = false; // (set by the leaf step that also ends the traversal: nothing to carry)
-            anyIteration<COUNT, L, 8>(nodes, tris, r, 0.0f, tlim, tlim * kCullPad, stack, static_cast<int>(q.inner_min_any), occluded, cur, iters, cntNodes, cntTris);
-            if (cur == L::kDone) endShadow(occluded);
+            anyIteration<COUNT, 8>(nodes, tris, r, 0.0f, tlim, tlim * kCullPad, stack, static_cast<int>(q.inner_min_any), occluded, cur, iters, cntNodes, cntTris);
+            if (cur == LayLegacy::kDone) endShadow(occluded);
         }
     }
 };

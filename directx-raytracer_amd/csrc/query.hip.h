@@ -179,29 +179,27 @@ __device__ __forceinline__ void everyHitIteration(const float4* __restrict__ nod
                                                   float tmax, float tcull, Stack& stack, int innerMin, int& cur, uint32_t& cntNodes,
                                                   uint32_t& cntTris, OnHit onHit)
 {
-    using L = LayLegacy;
     constexpr int OCT = 8; // refilled lanes mix direction octants: the generic slab test, no plane table
-    constexpr bool DEC = false;
     const float* planes = nullptr;
-    const unsigned long long innerMask = __ballot(L::inner(cur));
-    const unsigned long long leafMask = __ballot(L::leaf(cur));
+    const unsigned long long innerMask = __ballot(LayLegacy::inner(cur));
+    const unsigned long long leafMask = __ballot(LayLegacy::leaf(cur));
     if ((innerMask | leafMask) == 0ull) return;
     if (CRT_NODE_STEPS_NEXT(innerMask, leafMask, innerMin)) {
         CRT_NODE_STEPS(anyStep)
         return;
     }
-    if (L::leaf(cur)) {
+    if (LayLegacy::leaf(cur)) {
         uint32_t first, cnt;
-        L::leafRange(cur, first, cnt);
+        LayLegacy::leafRange(cur, first, cnt);
         for (uint32_t i = 0; i < cnt; i++) {
-            const uint32_t id = L::triId(first, i);
-            const float4* T = L::triPtr(tris, id);
+            const uint32_t id = LayLegacy::triId(first, i);
+            const float4* T = LayLegacy::triPtr(tris, id);
             const float4 a = T[0], b = T[1], c = T[2];
             if (COUNT) cntTris++;
             float t, u, v;
             if (triTest<false>(r, a, b, c, tmin, t, u, v) & (t < tmax)) onHit(t, id);
         }
-        cur = stack.sp == 0 ? L::kDone : stack.pop();
+        cur = stack.sp == 0 ? LayLegacy::kDone : stack.pop();
     }
 }
 

@@ -81,9 +81,9 @@ struct RayJob {
         const float4* nodes = reinterpret_cast<const float4*>(q.c.nodes);
         const float4* tris = reinterpret_cast<const float4*>(q.c.tris);
         const int innerMin = static_cast<int>(q.c.inner_min);
-        if (OCCL) anyIteration<COUNT, LayLegacy, 8>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris);
+        if (OCCL) anyIteration<COUNT, 8>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris);
         else {
-            closestIteration<COUNT, LayLegacy, 8>(nodes, tris, r, tmin, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris);
+            closestIteration<COUNT, 8>(nodes, tris, r, tmin, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris);
             tcull = cullBound(h.t); // (closestIteration sets t * kCullPad on an accepted hit: the same value for t >= 0)
         }
     }

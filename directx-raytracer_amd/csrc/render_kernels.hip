@@ -44,10 +44,9 @@ __device__ __forceinline__ uint32_t laneId() { return laneIndex(); }
 // NARROW: per-lane node and triangle fetches take a 32-bit byte offset from the wave-uniform base (LayLegacy::load); launched
 // unless RenderParams::wide_offsets says the scene's arrays are too long for that (wideOffsets, render_kernels.h).  The streams of a
 // split packet keep the 64-bit form, so the SPLIT variant exists in that form only.
-template <bool COUNT, bool PHONG, class L, bool SPLIT, bool NARROW_ASKED = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SPLIT ? 5 : L::kWavesPerEu, 8))) void renderKernel(const RenderParams p)
+template <bool COUNT, bool PHONG, bool SPLIT, bool NARROW = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SPLIT ? 5 : LayLegacy::kWavesPerEu, 8))) void renderKernel(const RenderParams p)
 {
-    constexpr bool NARROW = NARROW_ASKED && NARROW_OFFSETS;
     extern __shared__ int s_stack[]; // stack_entries x 256 dwords, sized at launch from the BVH depth
     unsigned long long t_start = 0;
     if ((CRT_DIAG && p.timeline) || p.unit_cost) t_start = __builtin_amdgcn_s_memrealtime();
@@ -140,7 +139,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SPLIT ? 5 : 
         stack.spill = p.spill + ((static_cast<size_t>(p.units_per_frame) * p.n_batch + static_cast<size_t>(b) * p.n_batch + frame) * 64u + tid) * p.spill_stride;
         stack.cap = static_cast<int>(p.stack_entries);
         stack.sp = 0;
-        renderSplitQuarter<COUNT, PHONG, L>(p, camPos, camRot, outRgba8, frame, tile_x, tile_y, wave, quarter, p.split_rays_log2, p.split_segs_log2, stack, iters, cntNodes, cntTris, cntShadow, cntClosest);
+        renderSplitQuarter<COUNT, PHONG>(p, camPos, camRot, outRgba8, frame, tile_x, tile_y, wave, quarter, p.split_rays_log2, p.split_segs_log2, stack, iters, cntNodes, cntTris, cntShadow, cntClosest);
     } else if (active) {
         const float4* nodes = reinterpret_cast<const float4*>(p.nodes);
         const float4* tris = reinterpret_cast<const float4*>(p.tris);
@@ -157,17 +156,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SPLIT ? 5 : 
             const F3 o = f3(camPos[0], camPos[1], camPos[2]);
             const Ray r = makeRay(o, rayDir(camRot, px, py, static_cast<float>(p.width), static_cast<float>(p.height)));
             if (COUNT) cntClosest++;
-            traceClosest<COUNT, L, true, true, true, NARROW>(nodes, tris, p.n_nodes, r, kTMin, kTMax, stack, static_cast<int>(p.tune_inner_min), h, iters, cntNodes, cntTris, p.planes);
+            traceClosest<COUNT, true, NARROW>(nodes, tris, p.n_nodes, r, kTMin, kTMax, stack, static_cast<int>(p.tune_inner_min), h, iters, cntNodes, cntTris, p.planes);
             col = f3(p.miss[0], p.miss[1], p.miss[2]); // miss shader (hlsl:72-76)
             if (h.t < kTMax) {
-                const float4* T = L::template triPtr<NARROW>(tris, h.tri);
-                if (p.mode >= 100u) col = shadeLambert<COUNT, L, PHONG, NARROW>(p, nodes, tris, r, h, stack, iters, cntNodes, cntTris, cntShadow);
+                const float4* T = LayLegacy::triPtr<NARROW>(tris, h.tri);
+                if (p.mode >= 100u) col = shadeLambert<COUNT, PHONG, NARROW>(p, nodes, tris, r, h, stack, iters, cntNodes, cntTris, cntShadow);
                 else col = shadeDebug(p.mode, __float_as_uint(T[0].w), __float_as_uint(T[1].w), h.t, h.u, h.v, r.o, r.d);
             }
         }
         const bool hit = h.t < kTMax;
         if (hit) {
-            const float4* T = L::template triPtr<NARROW>(tris, h.tri);
+            const float4* T = LayLegacy::triPtr<NARROW>(tris, h.tri);
             inst = __float_as_uint(T[0].w);
             prim = __float_as_uint(T[1].w);
         }
@@ -283,11 +282,11 @@ int launchRender(const RenderParams& p, bool counting, ihipStream_t* stream)
         const dim3 grid((n * 4u + extra) * (p.n_batch ? p.n_batch : 1u));
         const bool phong = p.mode >= 100u && p.phong_ks > 0.0f;
         const bool split = p.unit_order && p.split_units > 0u;
-#define CRT_LAUNCH(SPL, NAR)                                                                                                    \
-        if (counting && phong) hipLaunchKernelGGL((renderKernel<true, true, LayLegacy, SPL, NAR>), grid, block, lds, stream, p);  \
-        else if (counting) hipLaunchKernelGGL((renderKernel<true, false, LayLegacy, SPL, NAR>), grid, block, lds, stream, p);     \
-        else if (phong) hipLaunchKernelGGL((renderKernel<false, true, LayLegacy, SPL, NAR>), grid, block, lds, stream, p);        \
-        else hipLaunchKernelGGL((renderKernel<false, false, LayLegacy, SPL, NAR>), grid, block, lds, stream, p);
+#define CRT_LAUNCH(SPL, NAR)                                                                                         \
+        if (counting && phong) hipLaunchKernelGGL((renderKernel<true, true, SPL, NAR>), grid, block, lds, stream, p); \
+        else if (counting) hipLaunchKernelGGL((renderKernel<true, false, SPL, NAR>), grid, block, lds, stream, p);    \
+        else if (phong) hipLaunchKernelGGL((renderKernel<false, true, SPL, NAR>), grid, block, lds, stream, p);       \
+        else hipLaunchKernelGGL((renderKernel<false, false, SPL, NAR>), grid, block, lds, stream, p);
         if (split) { CRT_LAUNCH(true, false) } else if (p.wide_offsets) { CRT_LAUNCH(false, false) } else { CRT_LAUNCH(false, true) }
 #undef CRT_LAUNCH
     }

@@ -33,7 +33,6 @@ constexpr int kShadeWaves = 5;
 
 template <bool CNT>
 struct ShadeJob {
-    using L = LayLegacy;
     static constexpr int kClosest = -1; // `light` while the record's own ray is walked
     static constexpr int kIdle = -2;    // no record, or a finished one
 
@@ -83,7 +82,7 @@ struct ShadeJob {
         tcull = cullBound(tmax);
         light = kClosest;
         // a record with a NaN or an empty interval is not traced: step() finishes it as a miss
-        cur = (queryRayOk(a, b, tmin, tmax) & (q.c.n_nodes != 0u)) ? L::kRoot : L::kDone;
+        cur = (queryRayOk(a, b, tmin, tmax) & (q.c.n_nodes != 0u)) ? LayLegacy::kRoot : LayLegacy::kDone;
     }
     static __device__ __forceinline__ void store3(float* out, uint32_t i, F3 v)
     {
@@ -94,7 +93,7 @@ struct ShadeJob {
     {
         if (q.rgb) store3(q.rgb, idx, colour);
         light = kIdle;
-        cur = L::kDone;
+        cur = LayLegacy::kDone;
     }
     // the shadow ray of the first light from `from` on that sees the surface from its front, or the end of the record
     __device__ __forceinline__ void nextLight(uint32_t from, F3 Po)
@@ -108,7 +107,7 @@ struct ShadeJob {
                 tmax = lt.dist;
                 tcull = lt.dist * kCullPad;
                 stack.sp = 0;
-                cur = L::kRoot;
+                cur = LayLegacy::kRoot;
                 light = static_cast<int>(li);
                 if (CNT) cntShadow++;
                 return;
@@ -133,7 +132,7 @@ struct ShadeJob {
         F3 colour = f3(q.miss[0], q.miss[1], q.miss[2]), nrm = f3(0.0f, 0.0f, 0.0f), alb = f3(0.0f, 0.0f, 0.0f), Po = nrm;
         const float t = isHit ? __builtin_amdgcn_ldexpf(h.t, -e) : b.w;
         if (isHit) { // (an empty scene has no triangle record to read)
-            const float4* T = L::triPtr(tris, h.tri);
+            const float4* T = LayLegacy::triPtr(tris, h.tri);
             inst = __float_as_uint(T[0].w); // v0.w = mesh ordinal
             prim = __float_as_uint(T[1].w); // e1.w = triangle of the mesh
             Ray rec; // the record as the caller wrote it
@@ -143,7 +142,7 @@ struct ShadeJob {
             Hit hr = h;
             hr.t = t;
             if (lambert || q.normal || q.albedo) {
-                const Surface sf = surfaceAt<L>(q, tris, rec, hr);
+                const Surface sf = surfaceAt(q, tris, rec, hr);
                 nrm = sf.N;
                 alb = sf.albedo;
                 Po = biasPoint(sf.P, sf.N, kShadowBias);
@@ -188,14 +187,14 @@ struct ShadeJob {
         const float4* tris = reinterpret_cast<const float4*>(q.c.tris);
         if (light == kClosest) {
             Hit h = hit();
-            closestIteration<COUNT, L, 8>(nodes, tris, r, tmin, tcull, stack, static_cast<int>(q.c.inner_min), h, cur, iters, cntNodes, cntTris);
+            closestIteration<COUNT, 8>(nodes, tris, r, tmin, tcull, stack, static_cast<int>(q.c.inner_min), h, cur, iters, cntNodes, cntTris);
             setHit(h);
             tcull = cullBound(h.t); // (closestIteration sets t * kCullPad on an accepted hit: the same value for t >= 0)
-            if (cur == L::kDone) endClosest();
+            if (cur == LayLegacy::kDone) endClosest();
         } else if (light >= 0) {
             bool occluded = false; // (set by the leaf step that also ends the traversal: nothing to carry)
-            anyIteration<COUNT, L, 8>(nodes, tris, r, tmin, tmax, tcull, stack, static_cast<int>(q.inner_min_any), occluded, cur, iters, cntNodes, cntTris);
-            if (cur == L::kDone) endShadow(occluded);
+            anyIteration<COUNT, 8>(nodes, tris, r, tmin, tmax, tcull, stack, static_cast<int>(q.inner_min_any), occluded, cur, iters, cntNodes, cntTris);
+            if (cur == LayLegacy::kDone) endShadow(occluded);
         }
     }
 };

@@ -113,13 +113,13 @@ struct Surface {
 // P: the parameter block holding the scene's shading tables (RenderParams; ShadeQueryParams of the shaded ray queries).  Of r
 // only o and d are read.
 // NARROW: the triangle and shading records (48 bytes each) at a 32-bit byte offset from their bases (LayLegacy::triPtr)
-template <class L, bool NARROW = false, class P>
+template <bool NARROW = false, class P>
 __device__ __forceinline__ Surface surfaceAt(const P& p, const float4* tris, const Ray& r, const Hit& h)
 {
     Surface sf;
-    const float4* T = L::template triPtr<NARROW>(tris, h.tri);
+    const float4* T = LayLegacy::triPtr<NARROW>(tris, h.tri);
     const float4 tb = T[1], tc = T[2];
-    const float* S = reinterpret_cast<const float*>(L::template triPtr<NARROW>(reinterpret_cast<const float4*>(p.shade), h.tri)); // shading / uv record: leaf order, 48 bytes as well
+    const float* S = reinterpret_cast<const float*>(LayLegacy::triPtr<NARROW>(reinterpret_cast<const float4*>(p.shade), h.tri)); // shading / uv record: leaf order, 48 bytes as well
     const uint32_t material = __float_as_uint(S[9]);
     sf.P = f3(r.o.x + r.d.x * h.t, r.o.y + r.d.y * h.t, r.o.z + r.d.z * h.t);
     sf.albedo = f3(1.0f, 1.0f, 1.0f);
@@ -224,7 +224,7 @@ __device__ __forceinline__ void addLight(const P& p, const LightRec& Lt, const L
 }
 
 // direct light at Po: one any-hit shadow ray per light with a positive cosine (oracle: direct_light)
-template <bool COUNT, class L, bool PHONG, bool NARROW = false>
+template <bool COUNT, bool PHONG, bool NARROW = false>
 __device__ __forceinline__ F3 directLight(const RenderParams& p, const float4* nodes, const float4* tris, F3 Po, F3 N, F3 albedo, F3 view,
                                           Stack& stack, uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, uint32_t& cntShadow)
 {
@@ -236,7 +236,7 @@ __device__ __forceinline__ F3 directLight(const RenderParams& p, const float4* n
         if (lt.cosv > 0.0f) {
             const Ray sr = makeRay(Po, lt.Ld);
             if (COUNT) cntShadow++;
-            const bool occluded = traceAny<COUNT, L, true, true, NARROW>(nodes, tris, p.n_nodes, sr, 0.0f, lt.dist, stack, static_cast<int>(p.tune_inner_min_any), iters, cntNodes, cntTris, p.planes);
+            const bool occluded = traceAny<COUNT, true, NARROW>(nodes, tris, p.n_nodes, sr, 0.0f, lt.dist, stack, static_cast<int>(p.tune_inner_min_any), iters, cntNodes, cntTris, p.planes);
             if (!occluded) addLight<PHONG>(p, Lt, lt, N, albedo, view, rgb);
         }
     }
@@ -244,12 +244,12 @@ __device__ __forceinline__ F3 directLight(const RenderParams& p, const float4* n
 }
 
 // mode 100: Lambert (+ optional Phong highlight) + one shadow ray per light, every material treated as diffuse (oracle: shade_lambert)
-template <bool COUNT, class L, bool PHONG, bool NARROW = false>
+template <bool COUNT, bool PHONG, bool NARROW = false>
 __device__ __forceinline__ F3 shadeLambert(const RenderParams& p, const float4* nodes, const float4* tris, const Ray& r,
                                            const Hit& h, Stack& stack, uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, uint32_t& cntShadow)
 {
-    const Surface sf = surfaceAt<L, NARROW>(p, tris, r, h);
-    return directLight<COUNT, L, PHONG, NARROW>(p, nodes, tris, biasPoint(sf.P, sf.N, kShadowBias), sf.N, sf.albedo, f3(-r.d.x, -r.d.y, -r.d.z), stack, iters, cntNodes, cntTris, cntShadow);
+    const Surface sf = surfaceAt<NARROW>(p, tris, r, h);
+    return directLight<COUNT, PHONG, NARROW>(p, nodes, tris, biasPoint(sf.P, sf.N, kShadowBias), sf.N, sf.albedo, f3(-r.d.x, -r.d.y, -r.d.z), stack, iters, cntNodes, cntTris, cntShadow);
 }
 
 // ---- mode 200: path tracing (oracle: trace_path). Counter-based RNG keyed by (pixel, sample, seed).

@@ -59,7 +59,7 @@ __device__ __forceinline__ void sceneInterval(const Ray& r, const float* lo, con
 // hit in best (best.t = tmaxAll on a miss); else `occluded` of lane q says whether anything lies in (t0, t1).
 // The first segment starts at tminAll (wave-uniform) and, for closest hits, the last one ends at tmaxAll (wave-uniform), so that
 // the union of the segments is the whole open interval whatever the box test's rounding did; an any-hit ray ends at its own t1.
-template <bool COUNT, class L, bool CLOSEST>
+template <bool COUNT, bool CLOSEST>
 __device__ __forceinline__ void splitStream(const float4* __restrict__ nodes, const float4* __restrict__ tris, uint32_t n_nodes, F3 o, F3 d, float t0, float t1,
                                             bool want, float tminAll, float tmaxAll, uint32_t raysLog2, uint32_t segsLog2, Stack& stack, int innerMin, Hit& best, bool& occluded,
                                             uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris)
@@ -75,13 +75,13 @@ __device__ __forceinline__ void splitStream(const float4* __restrict__ nodes, co
     h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.tri = 0u; h.gid = 0u;
     float tlo = 0.0f, thi = 0.0f, tcull = 0.0f;
     bool occ = false;
-    int cur = L::kDone;
+    int cur = LayLegacy::kDone;
     bool have = false;
     uint32_t myRay = 0u, mySeg = 0u;
     uint32_t next = 0u; // wave-uniform: first item not yet handed out
     const unsigned long long all = __ballot(true);
     for (;;) {
-        const bool idle = cur == L::kDone;
+        const bool idle = cur == LayLegacy::kDone;
         const unsigned long long idleMask = __ballot(idle);
         if (idleMask == all || (next < kSplitItems && static_cast<uint32_t>(__popcll(idleMask)) >= kSplitRefillMin)) {
             // 1. retire: a finished item that found something reports to the lane that owns its ray
@@ -110,7 +110,7 @@ __device__ __forceinline__ void splitStream(const float4* __restrict__ nodes, co
             {
                 const uint32_t done = shflU(bestSeg, myRay);
                 if (have && done <= mySeg && !(CLOSEST && done == mySeg)) {
-                    cur = L::kDone;
+                    cur = LayLegacy::kDone;
                     have = false;
                 }
             }
@@ -138,14 +138,14 @@ __device__ __forceinline__ void splitStream(const float4* __restrict__ nodes, co
                 tcull = thi * kCullPad;
                 occ = false;
                 stack.sp = 0;
-                cur = n_nodes ? L::kRoot : L::kDone;
+                cur = n_nodes ? LayLegacy::kRoot : LayLegacy::kDone;
             }
             next += static_cast<uint32_t>(__popcll(mf));
             if (next >= kSplitItems && __ballot(have) == 0ull) break;
-            if (__ballot(cur != L::kDone) == 0ull) continue; // everything handed out was dead: hand out again
+            if (__ballot(cur != LayLegacy::kDone) == 0ull) continue; // everything handed out was dead: hand out again
         }
-        if (CLOSEST) closestIteration<COUNT, L, 8>(nodes, tris, r, tlo, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris);
-        else anyIteration<COUNT, L, 8>(nodes, tris, r, tlo, thi, tcull, stack, innerMin, occ, cur, iters, cntNodes, cntTris);
+        if (CLOSEST) closestIteration<COUNT, 8>(nodes, tris, r, tlo, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris);
+        else anyIteration<COUNT, 8>(nodes, tris, r, tlo, thi, tcull, stack, innerMin, occ, cur, iters, cntNodes, cntTris);
     }
 }
 
@@ -154,7 +154,7 @@ __device__ __forceinline__ void splitStream(const float4* __restrict__ nodes, co
 // streams.  Pixel i = part * R + q of the packet sits at the Z-order position of i: x from its even bits, y from its odd bits.
 __device__ __forceinline__ uint32_t evenBits3(uint32_t i) { return (i & 1u) | ((i >> 1) & 2u) | ((i >> 2) & 4u); }
 
-template <bool COUNT, bool PHONG, class L>
+template <bool COUNT, bool PHONG>
 __device__ __forceinline__ void renderSplitQuarter(const RenderParams& p, const float* camPos, const float* camRot, uint32_t* outRgba8, uint32_t frame,
                                                    uint32_t tile_x, uint32_t tile_y, uint32_t wave, uint32_t part, uint32_t raysLog2, uint32_t segsLog2, Stack& stack, uint32_t& iters,
                                                    uint32_t& cntNodes, uint32_t& cntTris, uint32_t& cntShadow, uint32_t& cntClosest)
@@ -174,12 +174,12 @@ __device__ __forceinline__ void renderSplitQuarter(const RenderParams& p, const 
     if (COUNT && owner) cntClosest++;
     Hit h;
     bool unusedOcc;
-    splitStream<COUNT, L, true>(nodes, tris, p.n_nodes, r.o, r.d, t0, t1, owner, kTMin, kTMax, raysLog2, segsLog2, stack, innerMin, h, unusedOcc, iters, cntNodes, cntTris);
+    splitStream<COUNT, true>(nodes, tris, p.n_nodes, r.o, r.d, t0, t1, owner, kTMin, kTMax, raysLog2, segsLog2, stack, innerMin, h, unusedOcc, iters, cntNodes, cntTris);
     const bool hit = owner && h.t < kTMax;
     F3 col = f3(p.miss[0], p.miss[1], p.miss[2]); // miss shader (hlsl:72-76)
     uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
     if (hit) {
-        const float4* T = L::triPtr(tris, h.tri);
+        const float4* T = LayLegacy::triPtr(tris, h.tri);
         inst = __float_as_uint(T[0].w);
         prim = __float_as_uint(T[1].w);
     }
@@ -187,7 +187,7 @@ __device__ __forceinline__ void renderSplitQuarter(const RenderParams& p, const 
         // shadeLambert / directLight (shading.hip.h), with every shadow ray traced as a stream of segments by all 64 lanes
         Surface sf;
         sf.P = f3(0.f, 0.f, 0.f); sf.N = f3(0.f, 0.f, 1.f); sf.albedo = f3(0.f, 0.f, 0.f); sf.mtype = 1u; sf.entering = true; sf.ior = 1.0f;
-        if (hit) sf = surfaceAt<L>(p, tris, r, h);
+        if (hit) sf = surfaceAt(p, tris, r, h);
         const F3 Po = biasPoint(sf.P, sf.N, kShadowBias), view = f3(-r.d.x, -r.d.y, -r.d.z);
         F3 rgb = f3(0.0f, 0.0f, 0.0f);
         const LightRec* lights = reinterpret_cast<const LightRec*>(p.lights);
@@ -198,7 +198,7 @@ __device__ __forceinline__ void renderSplitQuarter(const RenderParams& p, const 
             if (COUNT && need) cntShadow++;
             Hit unusedHit;
             bool occluded;
-            splitStream<COUNT, L, false>(nodes, tris, p.n_nodes, Po, lt.Ld, 0.0f, lt.dist, need, 0.0f, lt.dist, raysLog2, segsLog2, stack, static_cast<int>(p.tune_inner_min_any), unusedHit, occluded, iters, cntNodes, cntTris);
+            splitStream<COUNT, false>(nodes, tris, p.n_nodes, Po, lt.Ld, 0.0f, lt.dist, need, 0.0f, lt.dist, raysLog2, segsLog2, stack, static_cast<int>(p.tune_inner_min_any), unusedHit, occluded, iters, cntNodes, cntTris);
             if (need && !occluded) addLight<PHONG>(p, Lt, lt, sf.N, sf.albedo, view, rgb);
         }
         if (hit) col = rgb;

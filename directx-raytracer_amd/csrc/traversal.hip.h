@@ -44,36 +44,12 @@ constexpr uint32_t kBoostAfter = 300; // traversal-loop iterations after which a
 #define CRT_WAVES_PER_EU 7
 #endif
 #define CRT_OCCUPANCY_ATTR __attribute__((amdgpu_waves_per_eu(CRT_WAVES_PER_EU, 8)))
-// scalar-cache fetches of records a whole wavefront shares (see loadNodeUniform): in the descent from the root, in any
-// node step whose lanes agree, and in leaves
-#ifndef UNIFORM_DESCENT
-#define UNIFORM_DESCENT 1
-#endif
-#ifndef UNIFORM_STEP
-#define UNIFORM_STEP 1
-#endif
-#ifndef UNIFORM_LEAF
-#define UNIFORM_LEAF 1
-#endif
-#ifndef LEAF_PAIRS
-#define LEAF_PAIRS 1
-#endif
-#ifndef EARLY_FETCH
-#define EARLY_FETCH 1
-#endif
-// the render kernel's fetch forms: a closest-hit leaf pair's six loads pinned in front of their first wait (PAIR of
-// closestIteration), and per-lane record addresses as a 32-bit byte offset from the wave-uniform base (NARROW of both traversals)
-#ifndef LEAF_PAIR_PIN
-#define LEAF_PAIR_PIN 1
-#endif
-#ifndef NARROW_OFFSETS
-#define NARROW_OFFSETS 1
-#endif
-// the next node's record is requested before the current step's pushes (nodeStepClosestAt)
-// (EARLY_FETCH above); one copy of the traversal loops per direction octant for packets whose rays agree on it
-#ifndef OCTANT_SPECIALISE
-#define OCTANT_SPECIALISE 1
-#endif
+// The forms every traversal is built with, each settled by a measurement and no longer a build switch: records a whole
+// wavefront shares come through the scalar cache (LayLegacy::loadUniform) -- in the descent from the root, in any node step
+// whose lanes agree, and in leaves; closest-hit leaves take their triangles two per trip; the next node's record is requested
+// before the current step's pushes (closestStep); one copy of the traversal loops per direction octant for packets whose rays
+// agree on it.  The render kernel's own forms are template parameters (RENDER and NARROW of closestIteration).
+
 // idle lanes a wavefront of a streaming traversal (streamClosest of path_kernels.hip, runQuery of query.hip.h) collects before
 // it retires their rays and fetches new work for them, while there is any
 #ifndef CRT_REFILL_MIN
@@ -182,7 +158,7 @@ __device__ __forceinline__ float rcpExact(float d)
 }
 
 // Moeller-Trumbore, two sided; u = weight of v1, v = weight of v2.  NaN/inf from det == 0 fail the compares.
-// SHORT: 1 / det by rcpExact or by the division.  Only the render kernel's closest-hit leaves (DEC) take the short form;
+// SHORT: 1 / det by rcpExact or by the division.  Only the render kernel's closest-hit leaves (RENDER) take the short form;
 // any-hit leaves, the path kernel and the ray queries keep the division (measured, DESIGN section 5: the short form gained
 // nothing there -- shadow rays: 5M-triangle frame +3 %, path tracing +0.9 %).
 template <bool SHORT>
@@ -211,7 +187,7 @@ __device__ __forceinline__ bool triTest(const Ray& r, const float4 a, const floa
 // popLds() is the same pop as two loads under a branch, the LDS one through an LDS pointer: v_add, v_cmp, v_lshl_add_u32 and
 // ds_read_b32 plus four scalar instructions for the lanes in the LDS part, and the global load of the others is jumped over
 // when there are none.  Same entry, same order: only the instructions differ.  The render kernel's traversals take it
-// (LPOP of traceClosest / traceAny); what DESIGN section 5 measured for it and for the unchecked stack it replaced is there.
+// (RENDER of traceClosest / traceAny); what DESIGN section 5 measured for it and for the unchecked stack it replaced is there.
 struct Stack {
     int* lds;    // s_stack + lane
     int* spill;  // arena slice of this lane: spill_stride = 3 * depth4 + 1 - cap entries (the host's bound, reached to within one entry)
@@ -274,9 +250,9 @@ struct Stack {
         else v = spill[sp - cap];
         return v;
     }
-    template <bool LPOP> __device__ __forceinline__ int popAs()
+    template <bool RENDER> __device__ __forceinline__ int popAs()
     {
-        if constexpr (LPOP) return popLds();
+        if constexpr (RENDER) return popLds();
         else return pop();
     }
 };
@@ -472,8 +448,8 @@ struct LayLegacy {
     // 0.368 vs 0.361: the network runs under the early fetch, off the step's dependent chain, so removing it frees issue
     // slots nobody was waiting for.)
     // (N: Node, or NodeU on the scalar path with the plane table)
-    // (LPOP: the pop is Stack::popLds; NARROW: the early fetch is load<true>)
-    template <bool COUNT, int OCT, bool EARLY, bool LPOP = false, bool NARROW = false, class N>
+    // (RENDER: the pop is Stack::popLds; NARROW: the early fetch is load<true>)
+    template <bool COUNT, int OCT, bool EARLY, bool RENDER = false, bool NARROW = false, class N>
     static __device__ __forceinline__ void closestStep(const N& nd, const Ray& r, float tmin, float tcull, Stack& stack,
                                                        int& cur, uint32_t& cntNodes, const float4* __restrict__ nodes, Node& ndNext)
     {
@@ -488,7 +464,7 @@ struct LayLegacy {
             key[k] = hit[k] ? ((__float_as_uint(tn[k]) & 0x7FFFFFFCu) | static_cast<uint32_t>(k)) : 0xFFFFFFFFu;
         const uint32_t nearest = min(min(key[0], key[1]), min(key[2], key[3])); // = key[0] after the network
         const bool any = nearest != 0xFFFFFFFFu;
-        cur = any ? pick4(refs, nearest & 3u) : (stack.sp == 0 ? kDone : stack.template popAs<LPOP>()); // a lane pops or pushes, never both
+        cur = any ? pick4(refs, nearest & 3u) : (stack.sp == 0 ? kDone : stack.popAs<RENDER>()); // a lane pops or pushes, never both
         if (EARLY) {
             if (cur >= 0) ndNext = load<NARROW>(nodes, cur);
         }
@@ -503,7 +479,7 @@ struct LayLegacy {
     }
 
     // any hit: order independent, children taken in slot order
-    template <bool COUNT, int OCT, bool EARLY, bool LPOP = false, bool NARROW = false, class N>
+    template <bool COUNT, int OCT, bool EARLY, bool RENDER = false, bool NARROW = false, class N>
     static __device__ __forceinline__ void anyStep(const N& nd, const Ray& r, float tmin, float tcull, Stack& stack,
                                                    int& cur, uint32_t& cntNodes, const float4* __restrict__ nodes, Node& ndNext)
     {
@@ -513,7 +489,7 @@ struct LayLegacy {
         bool hit[4];
         slab<OCT>(nd, r, tmin, tcull, tn, hit);
         const bool h0 = hit[0], h1 = hit[1], h2 = hit[2], h3 = hit[3];
-        cur = h0 ? refs.x : (h1 ? refs.y : (h2 ? refs.z : (h3 ? refs.w : (stack.sp == 0 ? kDone : stack.template popAs<LPOP>()))));
+        cur = h0 ? refs.x : (h1 ? refs.y : (h2 ? refs.z : (h3 ? refs.w : (stack.sp == 0 ? kDone : stack.popAs<RENDER>()))));
         if (EARLY) {
             if (cur >= 0) ndNext = load<NARROW>(nodes, cur);
         }
@@ -524,32 +500,30 @@ struct LayLegacy {
     }
 };
 
-// The record of a scalar-path step: with the plane table (DEC) and a known octant its planes come
+// The record of a scalar-path step: with the plane table (RENDER) and a known octant its planes come
 // decoded (LayLegacy::NodeU), otherwise it is the plain record.  Per-lane steps always fetch the plain 64-byte record: a
 // second fetch per lane costs more than the conversions it would save (section 5 of DESIGN.md).
-template <class L, int OCT, bool DEC>
+template <int OCT, bool RENDER>
 __device__ __forceinline__ auto loadUniformStep(const float4* nodes, const float* planes, int ref)
 {
-    if constexpr (DEC && OCT < 8) return L::loadUniformDecoded(nodes, planes, ref);
-    else return L::loadUniform(nodes, ref);
+    if constexpr (RENDER && OCT < 8) return LayLegacy::loadUniformDecoded(nodes, planes, ref);
+    else return LayLegacy::loadUniform(nodes, ref);
 }
 
+// The step macros below expand inside a traversal function and read its names: COUNT, OCT, nodes, planes, r, tmin, tcull,
+// stack, cur, cntNodes.  Their RENDER and NARROW arguments are the traversal's (see closestIteration).
 // Uniform descent: the rays of an 8x8 packet start at the root and usually agree on the first few nodes.  While every
 // active lane stands on the SAME inner node its record is fetched once through the scalar cache (the node address is
 // wave-uniform, so the loads become s_load) instead of 64 identical per-lane vector fetches; each lane still runs its own
 // slab tests, ordering and pushes, so results and counters are exactly those of the per-lane loop that follows.
-#if UNIFORM_DESCENT
-#define CRT_UNIFORM_DESCENT(STEP, LPOP, NARROW)                                                                                     \
+#define CRT_UNIFORM_DESCENT(STEP, RENDER, NARROW)                                                                              \
     for (;;) {                                                                                                                 \
         const int c0 = __builtin_amdgcn_readfirstlane(cur);                                                                    \
-        if (!L::inner(c0) || __ballot(cur != c0) != 0ull) break;                                                               \
-        typename L::Node ndUnused;                                                                                             \
+        if (!LayLegacy::inner(c0) || __ballot(cur != c0) != 0ull) break;                                                       \
+        LayLegacy::Node ndUnused;                                                                                              \
         CRT_UNIFORM_STEP_STAT(STEP)                                                                                            \
-        L::template STEP<COUNT, OCT, false, LPOP, NARROW>(loadUniformStep<L, OCT, DEC>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndUnused); \
+        LayLegacy::STEP<COUNT, OCT, false, RENDER, NARROW>(loadUniformStep<OCT, RENDER>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndUnused); \
     }
-#else
-#define CRT_UNIFORM_DESCENT(STEP, LPOP, NARROW)
-#endif
 #define CRT_STEP_KIND_closestStep 0
 #define CRT_STEP_KIND_anyStep 1
 #if CRT_PROF
@@ -572,51 +546,50 @@ __device__ __forceinline__ auto loadUniformStep(const float4* nodes, const float
 // peels the distinct values, fetchers load and ds_write, every lane ds_reads its slot.  Bit-exact, a seventh of the
 // per-lane requests, and 0.49 ms instead of 0.31: the peeling loop and two LDS round trips per step cost far more than
 // the requests they save.)
-// CRT_NODE_STEPS: the NODE_STEPS node steps of one scheduling decision.  The first fetches its record here; with
-// EARLY_FETCH every step but the last requests the next record itself (see closestStep), per lane.
-#if UNIFORM_STEP
-#define CRT_FIRST_NODE_STEP(STEP, EARLY, LPOP, NARROW)                                                                             \
+// CRT_NODE_STEPS: the NODE_STEPS node steps of one scheduling decision.  The first fetches its record here; every step
+// but the last requests the next record itself (see closestStep), per lane.
+#define CRT_FIRST_NODE_STEP(STEP, EARLY, RENDER, NARROW)                                                                       \
     {                                                                                                                          \
         const int c0 = __builtin_amdgcn_readfirstlane(cur);                                                                    \
         if (__ballot(cur != c0) == 0ull) {                                                                                     \
             CRT_UNIFORM_STEP_STAT(STEP)                                                                                        \
-            L::template STEP<COUNT, OCT, EARLY, LPOP, NARROW>(loadUniformStep<L, OCT, DEC>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
+            LayLegacy::STEP<COUNT, OCT, EARLY, RENDER, NARROW>(loadUniformStep<OCT, RENDER>(nodes, planes, c0), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
         } else {                                                                                                               \
             CRT_DIV_STATS_NODE                                                                                                 \
             CRT_STEP_STAT(wsD, STEP)                                                                                           \
-            L::template STEP<COUNT, OCT, EARLY, LPOP, NARROW>(L::template load<NARROW>(nodes, cur), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
+            LayLegacy::STEP<COUNT, OCT, EARLY, RENDER, NARROW>(LayLegacy::load<NARROW>(nodes, cur), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
         }                                                                                                                      \
     }
-#else
-#define CRT_FIRST_NODE_STEP(STEP, EARLY, LPOP, NARROW) L::template STEP<COUNT, OCT, EARLY, LPOP, NARROW>(L::template load<NARROW>(nodes, cur), r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext);
-#endif
-#if EARLY_FETCH
-#define CRT_NODE_STEPS_AS(STEP, LPOP, NARROW)                                                                                    \
-    if (L::inner(cur)) {                                                                                                       \
-        typename L::Node ndNext;                                                                                               \
-        CRT_FIRST_NODE_STEP(STEP, (NODE_STEPS > 1), LPOP, NARROW)                                                              \
+#define CRT_NODE_STEPS_AS(STEP, RENDER, NARROW)                                                                                \
+    if (LayLegacy::inner(cur)) {                                                                                               \
+        LayLegacy::Node ndNext;                                                                                                \
+        CRT_FIRST_NODE_STEP(STEP, (NODE_STEPS > 1), RENDER, NARROW)                                                            \
         _Pragma("unroll") for (int rep = 1; rep < NODE_STEPS; rep++) {                                                         \
-            if (L::inner(cur)) {                                                                                               \
+            if (LayLegacy::inner(cur)) {                                                                                       \
                 CRT_STEP_STAT(wsF, STEP)                                                                                       \
                 CRT_AGREE_STAT(STEP)                                                                                           \
-                const typename L::Node ndCur = ndNext;                                                                         \
-                if (rep + 1 < NODE_STEPS) L::template STEP<COUNT, OCT, true, LPOP, NARROW>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
-                else L::template STEP<COUNT, OCT, false, LPOP, NARROW>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
+                const LayLegacy::Node ndCur = ndNext;                                                                          \
+                if (rep + 1 < NODE_STEPS) LayLegacy::STEP<COUNT, OCT, true, RENDER, NARROW>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
+                else LayLegacy::STEP<COUNT, OCT, false, RENDER, NARROW>(ndCur, r, tmin, tcull, stack, cur, cntNodes, nodes, ndNext); \
             }                                                                                                                  \
         }                                                                                                                      \
     }
-#else
-#define CRT_NODE_STEPS_AS(STEP, LPOP, NARROW)                                                                                    \
-    _Pragma("unroll") for (int rep = 0; rep < NODE_STEPS; rep++) {                                                             \
-        if (L::inner(cur)) { typename L::Node ndNext; CRT_FIRST_NODE_STEP(STEP, false, LPOP, NARROW) }                          \
-    }
-#endif
 #define CRT_NODE_STEPS(STEP) CRT_NODE_STEPS_AS(STEP, false, false)
 
 __device__ __forceinline__ void loadTriUniform(const float4* T, float4& a, float4& b, float4& c)
 {
     ConstQuadPtr C = (ConstQuadPtr)(reinterpret_cast<uintptr_t>(T));
     a = quadOf(C[0]); b = quadOf(C[1]); c = quadOf(C[2]);
+}
+
+// A candidate hit replaces the lane's closest one if it is nearer, or as near with the smaller triangle gid (the tie-break
+// that makes the result independent of the visiting order); boxes are culled against the new distance from then on.
+__device__ __forceinline__ void acceptHit(Hit& h, float& tcull, float t, float u, float v, uint32_t id, uint32_t gid)
+{
+    if ((t < h.t) | ((t == h.t) & (gid < h.gid))) {
+        h.t = t; h.u = u; h.v = v; h.tri = id; h.gid = gid;
+        tcull = t * kCullPad;
+    }
 }
 
 // Wave-level scheduling shared by both traversals.  Every lane walks its own ray in its own fixed order (so results
@@ -632,17 +605,18 @@ __device__ __forceinline__ void loadTriUniform(const float4* T, float4& a, float
 // on inner nodes, or the leaf step of the lanes waiting at leaves.  Per-lane state (cur, stack, h, tcull) lives in the
 // caller, so a caller may retire finished rays and start new ones between two calls (streamClosest).  Returns false when
 // no lane has anything left to do.
-// DEC / planes: scalar-path steps read the decoded plane table (kPlaneStride floats per node, render_kernels.h) -- the render kernel's
-// traversals; the others keep the default (no table).  LPOP: pops are Stack::popLds -- likewise.  PAIR: the six loads of a leaf
-// pair are issued in front of their first wait (LEAF_PAIRS below) -- likewise.  NARROW: per-lane node and triangle fetches take
-// a 32-bit byte offset from the wave-uniform base (LayLegacy::load) -- the render kernel's narrow variants.
-template <bool COUNT, class L, int OCT, bool DEC = false, bool LPOP = false, bool PAIR = false, bool NARROW = false>
+// RENDER: the render kernel's forms, which its two traversals take together and the others leave off.  Scalar-path steps read
+// the decoded plane table (planes: kPlaneStride floats per node, render_kernels.h; without RENDER there is no table), pops
+// are Stack::popLds, closest-hit leaves take the short reciprocal (triTest) and the six loads of a leaf pair are issued in
+// front of their first wait (see the leaf loop below).  NARROW: per-lane node and triangle fetches take a 32-bit byte
+// offset from the wave-uniform base (LayLegacy::load) -- the render kernel's narrow variants, the host's choice per scene.
+template <bool COUNT, int OCT, bool RENDER = false, bool NARROW = false>
 __device__ __forceinline__ bool closestIteration(const float4* __restrict__ nodes, const float4* __restrict__ tris, const Ray& r, float tmin,
                                                  float& tcull, Stack& stack, int innerMin, Hit& h, int& cur, uint32_t& iters,
                                                  uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
 {
-    const unsigned long long innerMask = __ballot(L::inner(cur));
-    const unsigned long long leafMask = __ballot(L::leaf(cur));
+    const unsigned long long innerMask = __ballot(LayLegacy::inner(cur));
+    const unsigned long long leafMask = __ballot(LayLegacy::leaf(cur));
     if ((innerMask | leafMask) == 0ull) return false;
     if (++iters == kBoostAfter) __builtin_amdgcn_s_setprio(3); // a wavefront on a long critical path stops queueing behind the others
     // innerMin > 0: node steps while at least that many lanes stand on inner nodes; innerMin <= 0 (adaptive): while at least
@@ -653,7 +627,7 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
 #if CRT_PROF
         const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
 #endif
-        CRT_NODE_STEPS_AS(closestStep, LPOP, NARROW) // several node steps per scheduling decision: fewer ballots/branches
+        CRT_NODE_STEPS_AS(closestStep, RENDER, NARROW) // several node steps per scheduling decision: fewer ballots/branches
 #if CRT_PROF
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         stack.tNode += __builtin_amdgcn_s_memtime() - ts0; stack.itNode++; stack.lanesNode += __popcll(innerMask);
@@ -664,85 +638,45 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
     const unsigned long long tl0 = __builtin_amdgcn_s_memtime();
     stack.itLeaf++; stack.lanesLeaf += __popcll(leafMask);
 #endif
-    if (L::leaf(cur)) {
+    if (LayLegacy::leaf(cur)) {
         uint32_t first, cnt;
-        L::leafRange(cur, first, cnt);
-#if UNIFORM_LEAF
+        LayLegacy::leafRange(cur, first, cnt);
         const int lc0 = __builtin_amdgcn_readfirstlane(cur);
         if (__ballot(cur != lc0) == 0ull) {
             // every waiting lane stands on the same leaf: its triangles come through the scalar cache, once per wavefront
             uint32_t ufirst, ucnt;
-            L::leafRange(lc0, ufirst, ucnt);
+            LayLegacy::leafRange(lc0, ufirst, ucnt);
             for (uint32_t i = 0; i < ucnt; i++) {
-                const uint32_t id = L::triId(ufirst, i);
+                const uint32_t id = LayLegacy::triId(ufirst, i);
                 float4 a, b, c;
-                loadTriUniform(L::triPtr(tris, id), a, b, c);
+                loadTriUniform(LayLegacy::triPtr(tris, id), a, b, c);
                 if (COUNT) cntTris++;
                 float t, u, v;
-                if (triTest<DEC>(r, a, b, c, tmin, t, u, v)) {
-                    const uint32_t gid = __float_as_uint(c.w);
-                    if ((t < h.t) | ((t == h.t) & (gid < h.gid))) {
-                        h.t = t; h.u = u; h.v = v; h.tri = id; h.gid = gid;
-                        tcull = t * kCullPad;
-                    }
-                }
+                if (triTest<RENDER>(r, a, b, c, tmin, t, u, v)) acceptHit(h, tcull, t, u, v, id, __float_as_uint(c.w));
             }
-        } else
-#endif
-        {
+        } else {
             CRT_DIV_STATS_LEAF
-#if LEAF_PAIRS
             // two triangles per trip, same test order, so that the second record's loads overlap the first's.  The source order
             // alone does not get that: the compiler issues the first record's three loads, waits for the first of them, starts
             // the triangle test and only then computes the second address and issues the second record's loads -- two memory
-            // latencies one after the other.  PAIR: a scheduling barrier behind the six loads keeps every instruction on its
+            // latencies one after the other.  RENDER: a scheduling barrier behind the six loads keeps every instruction on its
             // side, so both addresses are computed first, the six loads go out back to back and the first wait follows them:
             // one round trip per pair (listings and times in DESIGN section 5).
             for (uint32_t i = 0; i < cnt; i += 2) {
                 const bool two = i + 1 < cnt;
-                const uint32_t id = L::triId(first, i), id1 = L::triId(first, two ? i + 1 : i);
-                const float4* T = L::template triPtr<NARROW>(tris, id);
-                const float4* T1 = L::template triPtrSecond<NARROW>(tris, id, id1, two);
+                const uint32_t id = LayLegacy::triId(first, i), id1 = LayLegacy::triId(first, two ? i + 1 : i);
+                const float4* T = LayLegacy::triPtr<NARROW>(tris, id);
+                const float4* T1 = LayLegacy::triPtrSecond<NARROW>(tris, id, id1, two);
                 const float4 a = T[0], b = T[1], c = T[2];
                 const float4 a1 = T1[0], b1 = T1[1], c1 = T1[2];
-#if LEAF_PAIR_PIN
-                if constexpr (PAIR) __builtin_amdgcn_sched_barrier(0);
-#endif
+                if constexpr (RENDER) __builtin_amdgcn_sched_barrier(0);
                 if (COUNT) cntTris += two ? 2u : 1u;
                 float t, u, v;
-                if (triTest<DEC>(r, a, b, c, tmin, t, u, v)) {
-                    const uint32_t gid = __float_as_uint(c.w);
-                    if ((t < h.t) | ((t == h.t) & (gid < h.gid))) {
-                        h.t = t; h.u = u; h.v = v; h.tri = id; h.gid = gid;
-                        tcull = t * kCullPad;
-                    }
-                }
-                if (two & triTest<DEC>(r, a1, b1, c1, tmin, t, u, v)) {
-                    const uint32_t gid = __float_as_uint(c1.w);
-                    if ((t < h.t) | ((t == h.t) & (gid < h.gid))) {
-                        h.t = t; h.u = u; h.v = v; h.tri = id1; h.gid = gid;
-                        tcull = t * kCullPad;
-                    }
-                }
+                if (triTest<RENDER>(r, a, b, c, tmin, t, u, v)) acceptHit(h, tcull, t, u, v, id, __float_as_uint(c.w));
+                if (two & triTest<RENDER>(r, a1, b1, c1, tmin, t, u, v)) acceptHit(h, tcull, t, u, v, id1, __float_as_uint(c1.w));
             }
-#else
-            for (uint32_t i = 0; i < cnt; i++) {
-                const uint32_t id = L::triId(first, i);
-                const float4* T = L::template triPtr<NARROW>(tris, id);
-                const float4 a = T[0], b = T[1], c = T[2];
-                if (COUNT) cntTris++;
-                float t, u, v;
-                if (triTest<DEC>(r, a, b, c, tmin, t, u, v)) {
-                    const uint32_t gid = __float_as_uint(c.w);
-                    if ((t < h.t) | ((t == h.t) & (gid < h.gid))) {
-                        h.t = t; h.u = u; h.v = v; h.tri = id; h.gid = gid;
-                        tcull = t * kCullPad;
-                    }
-                }
-            }
-#endif
         }
-        cur = stack.sp == 0 ? L::kDone : stack.template popAs<LPOP>();
+        cur = stack.sp == 0 ? LayLegacy::kDone : stack.popAs<RENDER>();
     }
 #if CRT_PROF
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -751,27 +685,27 @@ __device__ __forceinline__ bool closestIteration(const float4* __restrict__ node
     return true;
 }
 
-template <bool COUNT, class L, int OCT, bool DEC, bool LPOP, bool PAIR, bool NARROW>
+template <bool COUNT, int OCT, bool RENDER, bool NARROW>
 __device__ __forceinline__ void traceClosestOct(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                              uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
                                              Hit& h, uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes)
 {
     h.t = tmax; h.u = 0.0f; h.v = 0.0f; h.tri = 0; h.gid = 0;
-    int cur = n_nodes ? L::kRoot : L::kDone;
+    int cur = n_nodes ? LayLegacy::kRoot : LayLegacy::kDone;
     stack.sp = 0;
     float tcull = tmax * kCullPad; // boxes are culled against best_t * pad; changes only when a hit is accepted
-    CRT_UNIFORM_DESCENT(closestStep, LPOP, NARROW)
-    while (closestIteration<COUNT, L, OCT, DEC, LPOP, PAIR, NARROW>(nodes, tris, r, tmin, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris, planes)) {}
+    CRT_UNIFORM_DESCENT(closestStep, RENDER, NARROW)
+    while (closestIteration<COUNT, OCT, RENDER, NARROW>(nodes, tris, r, tmin, tcull, stack, innerMin, h, cur, iters, cntNodes, cntTris, planes)) {}
 }
 
 // One scheduling decision of the any-hit traversal (see closestIteration); tmax / tcull / occluded are per-lane state of the caller
-template <bool COUNT, class L, int OCT, bool DEC = false, bool LPOP = false, bool NARROW = false>
+template <bool COUNT, int OCT, bool RENDER = false, bool NARROW = false>
 __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, const float4* __restrict__ tris, const Ray& r, float tmin, float tmax,
                                              float tcull, Stack& stack, int innerMin, bool& occluded, int& cur, uint32_t& iters,
                                              uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
 {
-    const unsigned long long innerMask = __ballot(L::inner(cur));
-    const unsigned long long leafMask = __ballot(L::leaf(cur));
+    const unsigned long long innerMask = __ballot(LayLegacy::inner(cur));
+    const unsigned long long leafMask = __ballot(LayLegacy::leaf(cur));
     if ((innerMask | leafMask) == 0ull) return false;
     if (++iters == kBoostAfter) __builtin_amdgcn_s_setprio(3);
     // innerMin > 0: node steps while at least that many lanes stand on inner nodes; innerMin <= 0 (adaptive): while at least
@@ -782,7 +716,7 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
 #if CRT_PROF
         const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
 #endif
-        CRT_NODE_STEPS_AS(anyStep, LPOP, NARROW) // several node steps per scheduling decision: fewer ballots/branches
+        CRT_NODE_STEPS_AS(anyStep, RENDER, NARROW) // several node steps per scheduling decision: fewer ballots/branches
 #if CRT_PROF
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         stack.tNode += __builtin_amdgcn_s_memtime() - ts0; stack.itNode++; stack.lanesNode += __popcll(innerMask);
@@ -793,17 +727,16 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
     const unsigned long long tl0 = __builtin_amdgcn_s_memtime();
     stack.itLeaf++; stack.lanesLeaf += __popcll(leafMask);
 #endif
-    if (L::leaf(cur)) {
+    if (LayLegacy::leaf(cur)) {
         uint32_t first, cnt;
-        L::leafRange(cur, first, cnt);
-#if UNIFORM_LEAF
+        LayLegacy::leafRange(cur, first, cnt);
         const int lc0 = __builtin_amdgcn_readfirstlane(cur);
         if (__ballot(cur != lc0) == 0ull) {
             uint32_t ufirst, ucnt;
-            L::leafRange(lc0, ufirst, ucnt);
+            LayLegacy::leafRange(lc0, ufirst, ucnt);
             for (uint32_t i = 0; i < ucnt; i++) {
                 float4 a, b, c;
-                loadTriUniform(L::triPtr(tris, L::triId(ufirst, i)), a, b, c);
+                loadTriUniform(LayLegacy::triPtr(tris, LayLegacy::triId(ufirst, i)), a, b, c);
                 if (COUNT) cntTris++;
                 float t, u, v;
                 if (triTest<false>(r, a, b, c, tmin, t, u, v) & (t < tmax)) {
@@ -811,19 +744,19 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
                     break;
                 }
             }
-        } else
-#endif
-        for (uint32_t i = 0; i < cnt; i++) {
-            const float4* T = L::template triPtr<NARROW>(tris, L::triId(first, i));
-            const float4 a = T[0], b = T[1], c = T[2];
-            if (COUNT) cntTris++;
-            float t, u, v;
-            if (triTest<false>(r, a, b, c, tmin, t, u, v) & (t < tmax)) {
-                occluded = true;
-                break;
+        } else {
+            for (uint32_t i = 0; i < cnt; i++) {
+                const float4* T = LayLegacy::triPtr<NARROW>(tris, LayLegacy::triId(first, i));
+                const float4 a = T[0], b = T[1], c = T[2];
+                if (COUNT) cntTris++;
+                float t, u, v;
+                if (triTest<false>(r, a, b, c, tmin, t, u, v) & (t < tmax)) {
+                    occluded = true;
+                    break;
+                }
             }
         }
-        cur = (occluded | (stack.sp == 0)) ? L::kDone : stack.template popAs<LPOP>();
+        cur = (occluded | (stack.sp == 0)) ? LayLegacy::kDone : stack.popAs<RENDER>();
     }
 #if CRT_PROF
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -832,17 +765,17 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
     return true;
 }
 
-template <bool COUNT, class L, int OCT, bool DEC, bool LPOP, bool NARROW>
+template <bool COUNT, int OCT, bool RENDER, bool NARROW>
 __device__ __forceinline__ bool traceAnyOct(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                          uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
                                          uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes)
 {
     bool occluded = false;
-    int cur = n_nodes ? L::kRoot : L::kDone;
+    int cur = n_nodes ? LayLegacy::kRoot : LayLegacy::kDone;
     stack.sp = 0;
     const float tcull = tmax * kCullPad;
-    CRT_UNIFORM_DESCENT(anyStep, LPOP, NARROW)
-    while (anyIteration<COUNT, L, OCT, DEC, LPOP, NARROW>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris, planes)) {}
+    CRT_UNIFORM_DESCENT(anyStep, RENDER, NARROW)
+    while (anyIteration<COUNT, OCT, RENDER, NARROW>(nodes, tris, r, tmin, tmax, tcull, stack, innerMin, occluded, cur, iters, cntNodes, cntTris, planes)) {}
     return occluded;
 }
 
@@ -853,42 +786,38 @@ __device__ __forceinline__ uint32_t octantOf(const Ray& r)
     return (__float_as_uint(r.d.x) >> 31) | ((__float_as_uint(r.d.y) >> 31) << 1) | ((__float_as_uint(r.d.z) >> 31) << 2);
 }
 
-template <bool COUNT, class L, bool DEC = false, bool LPOP = false, bool PAIR = false, bool NARROW = false>
+template <bool COUNT, bool RENDER = false, bool NARROW = false>
 __device__ __forceinline__ void traceClosest(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                              uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
                                              Hit& h, uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
 {
-#if OCTANT_SPECIALISE
     const uint32_t oct = octantOf(r);
     const uint32_t o0 = __builtin_amdgcn_readfirstlane(oct);
     if (__ballot(oct != o0) == 0ull) {
         switch (o0) {
-#define CRT_CASE(k) case k: traceClosestOct<COUNT, L, k, DEC, LPOP, PAIR, NARROW>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes); return;
+#define CRT_CASE(k) case k: traceClosestOct<COUNT, k, RENDER, NARROW>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes); return;
             CRT_CASE(0) CRT_CASE(1) CRT_CASE(2) CRT_CASE(3) CRT_CASE(4) CRT_CASE(5) CRT_CASE(6) CRT_CASE(7)
 #undef CRT_CASE
         }
     }
-#endif
-    traceClosestOct<COUNT, L, 8, DEC, LPOP, PAIR, NARROW>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes);
+    traceClosestOct<COUNT, 8, RENDER, NARROW>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, h, iters, cntNodes, cntTris, planes);
 }
 
-template <bool COUNT, class L, bool DEC = false, bool LPOP = false, bool NARROW = false>
+template <bool COUNT, bool RENDER = false, bool NARROW = false>
 __device__ __forceinline__ bool traceAny(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                          uint32_t n_nodes, const Ray& r, float tmin, float tmax, Stack& stack, int innerMin,
                                          uint32_t& iters, uint32_t& cntNodes, uint32_t& cntTris, const float* __restrict__ planes = nullptr)
 {
-#if OCTANT_SPECIALISE
     const uint32_t oct = octantOf(r);
     const uint32_t o0 = __builtin_amdgcn_readfirstlane(oct);
     if (__ballot(oct != o0) == 0ull) {
         switch (o0) {
-#define CRT_CASE(k) case k: return traceAnyOct<COUNT, L, k, DEC, LPOP, NARROW>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
+#define CRT_CASE(k) case k: return traceAnyOct<COUNT, k, RENDER, NARROW>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
             CRT_CASE(0) CRT_CASE(1) CRT_CASE(2) CRT_CASE(3) CRT_CASE(4) CRT_CASE(5) CRT_CASE(6) CRT_CASE(7)
 #undef CRT_CASE
         }
     }
-#endif
-    return traceAnyOct<COUNT, L, 8, DEC, LPOP, NARROW>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
+    return traceAnyOct<COUNT, 8, RENDER, NARROW>(nodes, tris, n_nodes, r, tmin, tmax, stack, innerMin, iters, cntNodes, cntTris, planes);
 }
 
 } // namespace
