@@ -24,6 +24,7 @@
 #include <cerrno>
 #include <cfloat>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -54,6 +55,39 @@ struct crt_scene {
     // uint32 copies of the int index vectors are not needed: std::vector<int> is reinterpreted like the
     // reference does for its index buffers (R/DXRTRenderer.cpp:314-315)
 };
+
+// "The work enqueued on a stream up to here": an event, the stream it was last recorded on, and whether it was recorded at all.
+// Everything on the context that one call leaves behind for a later call, possibly on another stream, is guarded by one.
+namespace {
+struct Fence {
+    hipEvent_t event = nullptr; // created at the first record (the frame slots': by crt_create)
+    hipStream_t stream = nullptr;
+    bool pending = false;
+
+    hipError_t record(hipStream_t s)
+    {
+        if (!event)
+            if (const hipError_t e = hipEventCreateWithFlags(&event, hipEventDisableTiming)) return e;
+        stream = s;
+        pending = true;
+        return hipEventRecord(event, s);
+    }
+    // `s` runs behind the recorded work.  A wait is only enqueued when it can matter: not for an event that has already completed
+    // (a host-side poll), and -- unless sameStreamToo -- not for work recorded on `s` itself, which runs in order anyway: every
+    // barrier packet costs the stream a few microseconds
+    hipError_t wait(hipStream_t s, bool sameStreamToo) const
+    {
+        if (!pending || (!sameStreamToo && stream == s) || hipEventQuery(event) == hipSuccess) return hipSuccess;
+        return hipStreamWaitEvent(s, event, 0);
+    }
+    void destroy()
+    {
+        if (event) (void)hipEventDestroy(event);
+        event = nullptr;
+        pending = false;
+    }
+};
+} // namespace
 
 struct crt_ctx {
     int device = 0;
@@ -132,34 +166,34 @@ struct crt_ctx {
     // the host) for the frame that used the slot before it, so up to kRing frames issued on different streams run
     // concurrently without sharing a spill arena or a cost/order buffer.
     static constexpr int kRing = 4;
-    uint32_t* dUnitCost[kRing] = {};
-    uint32_t* dUnitOrder[kRing] = {};
-    uint32_t unitCapacity = 0;
-    uint64_t orderKey[kRing] = {};   // frame geometry each stored order belongs to; 0 = none
-    bool sortPending[kRing] = {};    // evSort[slot] recorded (a sort of this slot's costs was issued)
-    uint32_t orderView[kRing] = {};  // viewSerial the stored order was measured under
-    uint32_t orderGen[kRing] = {};   // consecutive measurements of this frame geometry
-    uint32_t orderFrame[kRing] = {}; // frameSerial of the last measurement
+    struct FrameSlot {
+        int* spill = nullptr;          // traversal-stack spill arena (traversal.hip.h Stack)
+        size_t spillBytes = 0;
+        uint32_t* unitCost = nullptr;  // unitCapacity entries each: what the frame's wavefronts report, ...
+        uint32_t* unitOrder = nullptr; // ... and the launch order sorted from it
+        uint64_t orderKey = 0;         // frame geometry the stored order belongs to; 0 = none
+        uint32_t orderView = 0;        // viewSerial the stored order was measured under
+        uint32_t orderGen = 0;         // consecutive measurements of this frame geometry
+        uint32_t orderFrame = 0;       // frameSerial of the last measurement
+        Fence rendered;                // the slot's last frame, on the stream it ran on
+        Fence sorted;                  // the sort of that frame's costs, on the side stream
+    };
+    FrameSlot slot[kRing];
+    uint32_t unitCapacity = 0;       // of every slot's cost and order buffer: the four grow together
     bool debugForceMeasure = false;  // diagnostics: measure and sort at every frame even for an unchanged view
     uint32_t tuneRemeasureEvery = 1; // a changing view re-measures at every use of a slot: stale orders cost more than the measuring (tools/moving_camera.py)
     uint32_t viewSerial = 1;         // bumped when camera, mode or path settings change: costs must be measured again
-    bool renderPending[kRing] = {};  // evRender[slot] recorded
-    hipStream_t slotStream[kRing] = {}; // stream the slot's last frame ran on
     uint32_t frameSerial = 0;
     hipStream_t sideStream = nullptr; // sorts the costs of frame f while later frames render
-    hipEvent_t evRender[kRing] = {}, evSort[kRing] = {};
     unsigned long long* dCounters = nullptr;
-    int* dSpill[kRing] = {};          // traversal-stack spill arenas (traversal.hip.h Stack), one per ring slot
-    size_t spillBytes[kRing] = {};
     // Scratch that belongs to the stream that last used it: calls issued on one stream run one after the other and share ONE
     // arena; only calls on different streams (up to kRing in flight) get arenas of their own (takeArena).
     struct Arena {
         unsigned char* mem = nullptr;
         size_t bytes = 0;
-        hipStream_t stream = nullptr;
-        bool used = false;       // `stream` is meaningful
-        hipEvent_t lastUse = nullptr;
-        bool pending = false;    // lastUse recorded
+        bool used = false;       // lastUse.stream is meaningful
+        Fence lastUse;           // of the last call that used the arena; its stream is the arena's OWNER, set when a stream takes
+                                 // the arena (before anything is recorded) and the only stream that ever records it
         uint32_t serial = 0;     // of the last use (the least recently used arena is taken over by a new stream)
     };
     // mode 200: scratch of the persistent path kernel (one region per RESIDENT workgroup + the launch's work counter); serial =
@@ -173,14 +207,15 @@ struct crt_ctx {
     ncclComm_t comm = nullptr;
     struct HostExchange* hostComm = nullptr; // crt_comm_init_host: the tiles travel through shared host memory instead of RCCL
     uint32_t commRank = 0, commRanks = 0;
-    void* dStage[kRing] = {};
-    void* dGather[kRing] = {};
-    void* dDistFrame[kRing] = {};
-    size_t stageBytes[kRing] = {}, gatherBytes[kRing] = {}, distFrameBytes[kRing] = {};
+    struct DistSlot {
+        void* stage = nullptr;    // this rank's tiles
+        void* gathered = nullptr; // every rank's
+        void* frame = nullptr;    // the assembled frame of a call that gave no device buffer
+        size_t stageBytes = 0, gatheredBytes = 0, frameBytes = 0;
+        Fence done;               // end of the frame that last used the three, on the stream it ran on
+    };
+    DistSlot dist[kRing];
     uint32_t distSerial = 0;
-    hipEvent_t evDist[kRing] = {};       // end of the frame that last used a slot's staging / gathered / frame buffers
-    hipStream_t distStream[kRing] = {};  // and the stream it ran on
-    bool distPending[kRing] = {};
 
     // scratch frame buffers for the host-output path, grown on demand
     void* dFrame[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
@@ -200,9 +235,7 @@ struct crt_ctx {
     void* dAccum = nullptr;         // 4 doubles per output index of the RGBA8 store (pixel, or staging index of a tile share)
     size_t accumBytes = 0;
     // consecutive accumulating frames depend on each other through the sums: the next one waits (on the GPU) for the last one
-    hipEvent_t evAccum = nullptr;
-    hipStream_t accumStream = nullptr;
-    bool accumPending = false;
+    Fence accumUsed;
 
     // batched ray and point queries (crt_trace_rays* / crt_occluded_rays*, crt_closest_points* / crt_count_hits* /
     // crt_occupancy*): per arena the launch's cursor, counters and the stack spill arena of the persistent query kernel.  Arenas
@@ -257,6 +290,12 @@ void freeScene(crt_ctx* c)
     delete c->dyn;
     c->dyn = nullptr;
     c->haveScene = false;
+}
+
+// forget the stored launch orders: the scene changed, or how orders are made or used did
+void dropOrders(crt_ctx* c)
+{
+    for (crt_ctx::FrameSlot& s : c->slot) s.orderKey = 0;
 }
 
 // the root record as it sits in HBM: where split rays are cut into segments
@@ -323,18 +362,17 @@ int takeArena(crt_ctx* c, crt_ctx::Arena (&pool)[crt_ctx::kRing], size_t need, u
 {
     crt_ctx::Arena* arena = nullptr;
     for (auto& a : pool)
-        if (a.used && a.stream == c->stream) arena = &a;
+        if (a.used && a.lastUse.stream == c->stream) arena = &a;
     if (!arena) {
         for (auto& a : pool)
             if (!arena || (!a.used && arena->used) || (a.used == arena->used && a.serial < arena->serial)) arena = &a;
-        if (arena->pending && hipEventQuery(arena->lastUse) != hipSuccess) HIP_TRY(c, hipStreamWaitEvent(c->stream, arena->lastUse, 0));
-        arena->stream = c->stream;
+        HIP_TRY(c, arena->lastUse.wait(c->stream, true)); // (whichever stream it was: the arena changes hands)
+        arena->lastUse.stream = c->stream;
         arena->used = true;
     }
     const int rc = ensureBuffer(c, reinterpret_cast<void**>(&arena->mem), &arena->bytes, need, ownScratch);
     if (rc == CRT_ENOMEM) return fail(c, CRT_ENOMEM, "query scratch: %zu bytes of device memory not available", need);
     if (rc) return rc;
-    if (!arena->lastUse) HIP_TRY(c, hipEventCreateWithFlags(&arena->lastUse, hipEventDisableTiming));
     arena->serial = serial;
     out = arena;
     return CRT_OK;
@@ -466,7 +504,7 @@ int applyRefit(crt_ctx* c, double* device_ms)
     c->bvh.depth4 = depth4;
     if (int rc = readSceneBox(c)) return rc;
     c->sceneSerial++;
-    for (uint64_t& k : c->orderKey) k = 0;
+    dropOrders(c);
     return CRT_OK;
 }
 
@@ -528,7 +566,7 @@ void fillParams(const crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_
     p.tune_inner_min_any = c->tuneInnerMinAny;
     p.xcd_group = c->tuneXcdGroup;
     p.boost_units = c->tuneBoostUnits;
-    p.split_units = 0; // set in runRender once a launch order is in use
+    p.split_units = 0; // set in frameLaunchOrder once a launch order is in use
     p.split_rays_log2 = c->tuneSplitRaysLog2;
     p.split_segs_log2 = c->tuneSplitSegsLog2;
     p.debug_skip_units = c->debugSkipUnits;
@@ -560,208 +598,264 @@ template <class Q> void sceneTables(const crt_ctx* c, Q& q)
 // a frame that uses the sums runs after the last one that did, even when issued on another stream (crt_set_stream)
 int orderAccum(crt_ctx* c)
 {
-    if (!c->evAccum) HIP_TRY(c, hipEventCreateWithFlags(&c->evAccum, hipEventDisableTiming));
-    if (c->accumPending && c->accumStream != c->stream && hipEventQuery(c->evAccum) != hipSuccess)
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evAccum, 0));
+    HIP_TRY(c, c->accumUsed.wait(c->stream, false));
     return CRT_OK;
 }
 
 // after the launch: the sums now hold acc_total samples
 int commitAccum(crt_ctx* c, const RenderParams& p)
 {
-    HIP_TRY(c, hipEventRecord(c->evAccum, c->stream));
-    c->accumStream = c->stream;
-    c->accumPending = true;
+    HIP_TRY(c, c->accumUsed.record(c->stream));
     c->accSamples = p.acc_total;
+    return CRT_OK;
+}
+
+// What a call with stats reports after its launch: waits for the stream, then kernel_ms = evStart .. evStop and every count zero.
+// A launch that counts gives dCounters and four words: with counting on its four counter words are read into them (else zeros),
+// of which the fetches mean the same for every kind of call; the ray counts are the caller's to fill in
+int readStats(crt_ctx* c, crt_frame_stats* stats, const unsigned long long* dCounters = nullptr, unsigned long long* words = nullptr)
+{
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->evStart, c->evStop));
+    std::memset(stats, 0, sizeof(*stats));
+    stats->kernel_ms = ms;
+    if (!dCounters) return CRT_OK;
+    std::memset(words, 0, 4 * sizeof(*words));
+    if (c->counting) {
+        HIP_TRY(c, hipMemcpy(words, dCounters, 4 * sizeof(*words), hipMemcpyDeviceToHost));
+        stats->nodes_visited = words[0];
+        stats->tris_tested = words[1];
+    }
+    return CRT_OK;
+}
+
+// ---- One frame (runRender), step by step.  Each step enqueues on the context's stream only what its comment says.
+
+// diagnostic builds, option "timeline": 3 words per workgroup, zeroed before the frame
+int frameTimeline(crt_ctx* c, RenderParams& p)
+{
+    if (!c->wantTimeline || p.n_batch != 1) return CRT_OK;
+    const size_t words = 3 * (static_cast<size_t>(p.tiles_x + 4) * (p.tiles_y + 4) * 4 + 1024);
+    if (c->timelineWords < words) {
+        if (c->dTimeline) (void)hipFree(c->dTimeline);
+        c->dTimeline = nullptr;
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->dTimeline), words * sizeof(unsigned long long)));
+        c->timelineWords = words;
+    }
+    HIP_TRY(c, hipMemsetAsync(c->dTimeline, 0, c->timelineWords * sizeof(unsigned long long), c->stream));
+    p.timeline = c->dTimeline;
+    return CRT_OK;
+}
+
+// Mode 200: how the frame is cut into work items, and the scratch of the persistent path kernel from the stream's arena
+// (enqueues: a wait when the arena changes hands, and the zeroing of the work counters)
+int framePathScratch(crt_ctx* c, RenderParams& p, crt_ctx::Arena*& arena)
+{
+    // path tracing: resident wavefronts stream the paths of one pixel tile after the other through private queues in HBM.  One
+    // 8x8 packet x up to 16 samples per work item (256 paths at 4 spp) measured best at every frame size -- 6.6 vs 10.1 ms on C3
+    // at 1080p, 27.3 vs 29.2 ms on C5 at 4K against one 16x16 macro tile x 4 samples
+    p.path_tile = c->tunePathTile ? c->tunePathTile : 8u;
+    // the stages as separate launches over global queues (8x8 work items, 64-byte nodes), or one persistent kernel
+    p.path_wavefront = (c->tunePathPipeline == 1u && p.path_tile == 8u) ? 1u : 0u;
+    p.path_samples = std::min<uint32_t>(p.path_tile == 16u ? 4u : 16u, std::max<uint32_t>(1u, p.spp));
+    p.path_region_bytes = crt::pathRegionBytes(p.path_tile, p.path_samples);
+    p.path_work_items = crt::pathWorkgroupCount(p);
+    const size_t kHead = 512; // the work counters (one 64-byte line per range) live in front of the regions
+    p.path_ranges = c->tunePathRanges;
+    uint32_t wfItems = 0;
+    if (p.path_wavefront) {
+        wfItems = crt::pathWavefrontPassItems(p, c->tunePathPassPaths);
+        p.wf_paths = wfItems * 64u * p.path_samples;
+        crt::pathWavefrontLayout(p, wfItems, p.wf_chunk, p.wf_stride);
+    }
+    const size_t need = p.path_wavefront ? crt::pathWavefrontBytes(p, wfItems) : kHead + static_cast<size_t>(crt::pathGridSize(p)) * p.path_region_bytes;
+    if (const int rc = takeArena(c, c->pathArena, need, c->frameSerial, false, arena)) return rc;
+    if (p.path_wavefront) {
+        const size_t plane = static_cast<size_t>(p.wf_paths) * 16u, qplane = static_cast<size_t>(p.wf_stride) * 16u; // one float4 per path / queue entry
+        unsigned char* at = arena->mem;
+        p.wf_counts = reinterpret_cast<uint32_t*>(at); at += crt::kWfHeadBytes;
+        p.wf_shade_q = at; at += 3u * qplane;
+        p.wf_trace_q = at; at += 2u * qplane;
+        p.wf_done = at; at += plane;
+        p.wf_thr = at; at += plane;
+        p.wf_accum = p.spp > p.path_samples ? at : nullptr;
+    } else {
+        p.path_counter = reinterpret_cast<uint32_t*>(arena->mem);
+        p.path_scratch = arena->mem + kHead;
+        HIP_TRY(c, hipMemsetAsync(p.path_counter, 0, kHead, c->stream));
+    }
+    return CRT_OK;
+}
+
+// How many packets are split, at most a quarter of them.  Option "split_units", whose default kSplitAuto stands for two numbers:
+// 128 when the spill arena is sized (sizing: the most the rule below can ask for), and for the launch none / 64 / 128 by the
+// number of ranks (the measurements stand at kSplitAuto)
+uint32_t splitUnits(const crt_ctx* c, const RenderParams& p, bool sizing)
+{
+    uint32_t want = c->tuneSplitUnits;
+    if (want == crt_ctx::kSplitAuto) want = sizing || p.n_ranks >= 4u ? 128u : (p.n_ranks >= 2u ? 64u : 0u);
+    return std::min(want, crt::renderUnitCount(p) / 4u);
+}
+
+// the slot's stack spill arena (enqueues nothing; after framePathScratch, whose work split sizes it in mode 200)
+int frameSpill(crt_ctx* c, crt_ctx::FrameSlot& slot, RenderParams& p)
+{
+    // deepest stack a ray can build: three pending siblings per wide level; what does not fit the LDS part spills
+    const uint32_t deepest = 3u * c->bvh.depth4 + 1u;
+    p.spill_stride = deepest > p.stack_entries ? deepest - p.stack_entries : 1u;
+    // (mode 200: one slice per resident workgroup of the persistent kernel)
+    // (+ 64 slices for each of the four wavefronts of a split packet)
+    const size_t groups = p.mode >= 200u ? static_cast<size_t>(crt::pathGridSize(p))
+                                         : (static_cast<size_t>(crt::renderUnitCount(p)) + 16u * splitUnits(c, p, true)) * p.n_batch;
+    const size_t need = groups * 64u * p.spill_stride * sizeof(int);
+    if (const int rc = ensureBuffer(c, reinterpret_cast<void**>(&slot.spill), &slot.spillBytes, need)) return rc;
+    p.spill = slot.spill;
+    return CRT_OK;
+}
+
+// every slot's cost and order buffer made to hold nUnits entries, after one device-wide wait; the stored orders are lost
+int growUnitBuffers(crt_ctx* c, uint32_t nUnits)
+{
+    HIP_TRY(c, hipDeviceSynchronize()); // (frames of other streams may still use the buffers about to be replaced)
+    for (crt_ctx::FrameSlot& s : c->slot) {
+        if (s.unitCost) (void)hipFree(s.unitCost);
+        if (s.unitOrder) (void)hipFree(s.unitOrder);
+        s.unitCost = s.unitOrder = nullptr;
+        s.sorted.pending = false;
+    }
+    dropOrders(c);
+    c->unitCapacity = 0;
+    for (crt_ctx::FrameSlot& s : c->slot) {
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s.unitCost), sizeof(uint32_t) * nUnits));
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&s.unitOrder), sizeof(uint32_t) * nUnits));
+    }
+    c->unitCapacity = nUnits;
+    return CRT_OK;
+}
+
+// Cost feedback: the lifetimes frame f's wavefronts report are sorted on a side stream while the next frames render and
+// order the launch of frame f + kRing (same ring slot), so neither the sort nor the dependency on an earlier frame
+// sits on a frame's critical path and kRing frames can be in flight.  Hint only: a stale or missing order changes
+// speed, never results.
+struct LaunchOrder {
+    uint32_t nUnits = 0;
+    uint64_t key = 0;     // the frame geometry an order measured by this frame belongs to
+    bool measure = false; // this frame reports its costs, and they are sorted behind it
+};
+
+// Whether the frame is launched in the slot's stored order (p.unit_order), how many packets it splits (p.split_units) and whether
+// it measures (p.unit_cost, lo.measure).  Enqueues nothing
+int frameLaunchOrder(crt_ctx* c, crt_ctx::FrameSlot& slot, RenderParams& p, LaunchOrder& lo)
+{
+    lo.nUnits = crt::renderUnitCount(p);
+    lo.key = (static_cast<uint64_t>(p.width) << 40) ^ (static_cast<uint64_t>(p.height) << 20) ^ (static_cast<uint64_t>(p.n_ranks) << 8) ^ p.rank ^
+             (static_cast<uint64_t>(c->sceneSerial) << 52) ^ 1ull;
+    const bool sameStream = c->haveLastRenderStream && c->lastRenderStream == c->stream;
+    c->lastRenderStream = c->stream;
+    c->haveLastRenderStream = true;
+    if (!(c->adaptiveOrder == 1 || (c->adaptiveOrder == 2 && sameStream)) || !lo.nUnits || p.mode >= 200u) return CRT_OK; // (the path pipeline has its own work split)
+    if (c->unitCapacity < lo.nUnits)
+        if (const int rc = growUnitBuffers(c, lo.nUnits)) return rc;
+    const bool usable = slot.orderKey == lo.key;
+    p.unit_order = usable ? slot.unitOrder : nullptr;
+    p.split_units = usable ? splitUnits(c, p, false) : 0u; // (at most a quarter of the packets: the spill arena is sized for that)
+    // Costs are measured (and sorted) twice in a row -- the first measurement ran under an unordered launch -- and then:
+    // an unchanged view keeps its order for good; a view that keeps changing (a moving camera) measures again every
+    // remeasure_every-th use of the slot.  Default 1: the order ages fast -- with a camera turning 0.01 degrees per frame
+    // an order 32 frames old cost 0.367 ms per frame, 128 frames old 0.423, against 0.347 when measured every frame.
+    // (The feedback itself -- cost stores, the sort beside the next frame -- is 1.4 % of a frame: tools/moving_camera.py --wobble;
+    //  the rest of that run's difference to a static view was the frame's own cost changing along the orbit.)
+    const bool twice = usable && slot.orderGen >= 2;
+    const bool sameView = slot.orderView == c->viewSerial;
+    const bool recent = (c->frameSerial - slot.orderFrame) < static_cast<uint32_t>(crt_ctx::kRing) * c->tuneRemeasureEvery;
+    if (c->debugForceMeasure || !(twice && (sameView || recent))) {
+        p.unit_cost = slot.unitCost;
+        lo.measure = true;
+        slot.orderGen = usable ? slot.orderGen + 1 : 1;
+        slot.orderView = c->viewSerial;
+        slot.orderFrame = c->frameSerial;
+    }
+    return CRT_OK;
+}
+
+// The previous user of this slot (frame f - kRing, possibly on another stream) and the sort of its costs must be done before this
+// frame touches the slot's spill arena, cost or order buffer; a frame that uses the sums runs after the last one that did.
+// Enqueues up to three waits (Fence::wait: only where one can matter); the sort ran on the side stream, so it always can
+int frameWaits(crt_ctx* c, crt_ctx::FrameSlot& slot, const RenderParams& p)
+{
+    HIP_TRY(c, slot.sorted.wait(c->stream, true));
+    if (p.acc_sum)
+        if (const int rc = orderAccum(c)) return rc;
+    HIP_TRY(c, slot.rendered.wait(c->stream, false));
+    slot.sorted.pending = false;
+    return CRT_OK;
+}
+
+// the launch, between the timer's events when stats are wanted, and the records of everything it used
+int frameLaunch(crt_ctx* c, crt_ctx::FrameSlot& slot, crt_ctx::Arena* arena, const RenderParams& p, const LaunchOrder& lo, bool timed)
+{
+    // split packets add their quarters' lifetimes into their cost slot: start from zero
+    if (p.unit_cost && p.split_units) HIP_TRY(c, hipMemsetAsync(p.unit_cost, 0, sizeof(uint32_t) * lo.nUnits, c->stream));
+    if (timed) HIP_TRY(c, hipEventRecord(c->evStart, c->stream));
+    const int rc = crt::launchRender(p, c->counting, c->stream);
+    if (rc != 0) return fail(c, CRT_EHIP, "render kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+    if (timed) HIP_TRY(c, hipEventRecord(c->evStop, c->stream)); // kernel_ms = the render kernel alone
+    HIP_TRY(c, slot.rendered.record(c->stream));
+    if (arena) HIP_TRY(c, arena->lastUse.record(c->stream));
+    if (p.acc_sum) return commitAccum(c, p);
+    return CRT_OK;
+}
+
+// the frame's costs sorted into the slot's launch order, on the side stream behind the frame
+int frameSortCosts(crt_ctx* c, crt_ctx::FrameSlot& slot, const LaunchOrder& lo)
+{
+    hipStream_t ss = c->sideStream;
+    HIP_TRY(c, hipStreamWaitEvent(ss, slot.rendered.event, 0));
+    const int rs = crt::launchSortUnits(slot.unitCost, slot.unitOrder, lo.nUnits, c->tuneXcdAffine, ss);
+    if (rs != 0) return fail(c, CRT_EHIP, "sort kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rs)));
+    HIP_TRY(c, slot.sorted.record(ss));
+    slot.orderKey = lo.key;
+    return CRT_OK;
+}
+
+// synchronises; rays_primary = the pixels this launch rendered, or with counting what the kernel counted
+int frameStats(crt_ctx* c, const RenderParams& p, crt_frame_stats* stats)
+{
+    unsigned long long words[4];
+    if (const int rc = readStats(c, stats, c->dCounters, words)) return rc;
+    const uint32_t nTiles = p.tiles_x * p.tiles_y;
+    for (uint32_t k = p.rank; k < nTiles; k += p.n_ranks) {
+        const uint32_t tx = k % p.tiles_x, ty = k / p.tiles_x;
+        const uint32_t w = std::min<uint32_t>(crt::kTile, p.width - tx * crt::kTile);
+        const uint32_t h = std::min<uint32_t>(crt::kTile, p.height - ty * crt::kTile);
+        stats->rays_primary += static_cast<uint64_t>(w) * h;
+    }
+    if (c->counting) {
+        stats->rays_shadow = words[2];
+        stats->rays_primary = words[3]; // closest-hit rays: camera rays, plus bounce rays in mode 200
+    }
     return CRT_OK;
 }
 
 // enqueue one frame; when stats != nullptr, bracket with events, synchronise and fill the timers/counters
 int runRender(crt_ctx* c, RenderParams& p, crt_frame_stats* stats)
 {
-    const bool counting = c->counting;
     HIP_TRY(c, hipSetDevice(c->device)); // the calling thread's current device may be another one (scratch hipMallocs below)
-    if (counting) HIP_TRY(c, hipMemsetAsync(c->dCounters, 0, 32 * sizeof(unsigned long long), c->stream));
-    if (c->wantTimeline && p.n_batch == 1) {
-        const size_t words = 3 * (static_cast<size_t>(p.tiles_x + 4) * (p.tiles_y + 4) * 4 + 1024);
-        if (c->timelineWords < words) {
-            if (c->dTimeline) (void)hipFree(c->dTimeline);
-            c->dTimeline = nullptr;
-            HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->dTimeline), words * sizeof(unsigned long long)));
-            c->timelineWords = words;
-        }
-        HIP_TRY(c, hipMemsetAsync(c->dTimeline, 0, c->timelineWords * sizeof(unsigned long long), c->stream));
-        p.timeline = c->dTimeline;
-    }
-    const uint32_t slot = c->frameSerial++ % crt_ctx::kRing;
-    {
-        // deepest stack a ray can build: three pending siblings per wide level; what does not fit the LDS part spills
-        const uint32_t deepest = 3u * c->bvh.depth4 + 1u;
-        p.spill_stride = deepest > p.stack_entries ? deepest - p.stack_entries : 1u;
-        // (mode 200: one slice per resident workgroup of the persistent kernel)
-        if (p.mode >= 200u) {
-            p.path_tile = c->tunePathTile ? c->tunePathTile : 8u;
-            // the stages as separate launches over global queues (8x8 work items, 64-byte nodes), or one persistent kernel
-            p.path_wavefront = (c->tunePathPipeline == 1u && p.path_tile == 8u) ? 1u : 0u;
-        }
-        // (+ 64 slices for each of the four wavefronts of a split packet)
-        const size_t groups = p.mode >= 200u ? static_cast<size_t>(crt::pathGridSize(p))
-                                             : (static_cast<size_t>(crt::renderUnitCount(p)) + 16u * std::min(c->tuneSplitUnits == crt_ctx::kSplitAuto ? 128u : c->tuneSplitUnits, crt::renderUnitCount(p) / 4u)) * p.n_batch;
-        const size_t need = groups * 64u * p.spill_stride * sizeof(int);
-        if (const int rc = ensureBuffer(c, reinterpret_cast<void**>(&c->dSpill[slot]), &c->spillBytes[slot], need)) return rc;
-        p.spill = c->dSpill[slot];
-    }
-    crt_ctx::Arena* arena = nullptr;
-    if (p.mode >= 200u) {
-        // path tracing: resident wavefronts stream the paths of one pixel tile after the other through private queues in HBM.  One
-        // 8x8 packet x up to 16 samples per work item (256 paths at 4 spp) measured best at every frame size -- 6.6 vs 10.1 ms on C3
-        // at 1080p, 27.3 vs 29.2 ms on C5 at 4K against one 16x16 macro tile x 4 samples
-        p.path_tile = c->tunePathTile ? c->tunePathTile : 8u;
-        p.path_samples = std::min<uint32_t>(p.path_tile == 16u ? 4u : 16u, std::max<uint32_t>(1u, p.spp));
-        p.path_region_bytes = crt::pathRegionBytes(p.path_tile, p.path_samples);
-        p.path_work_items = crt::pathWorkgroupCount(p);
-        const size_t kHead = 512; // the work counters (one 64-byte line per range) live in front of the regions
-        p.path_ranges = c->tunePathRanges;
-        uint32_t wfItems = 0;
-        if (p.path_wavefront) {
-            wfItems = crt::pathWavefrontPassItems(p, c->tunePathPassPaths);
-            p.wf_paths = wfItems * 64u * p.path_samples;
-            crt::pathWavefrontLayout(p, wfItems, p.wf_chunk, p.wf_stride);
-        }
-        const size_t need = p.path_wavefront ? crt::pathWavefrontBytes(p, wfItems) : kHead + static_cast<size_t>(crt::pathGridSize(p)) * p.path_region_bytes;
-        if (const int rc = takeArena(c, c->pathArena, need, c->frameSerial, false, arena)) return rc;
-        if (p.path_wavefront) {
-            const size_t plane = static_cast<size_t>(p.wf_paths) * 16u, qplane = static_cast<size_t>(p.wf_stride) * 16u; // one float4 per path / queue entry
-            unsigned char* at = arena->mem;
-            p.wf_counts = reinterpret_cast<uint32_t*>(at); at += crt::kWfHeadBytes;
-            p.wf_shade_q = at; at += 3u * qplane;
-            p.wf_trace_q = at; at += 2u * qplane;
-            p.wf_done = at; at += plane;
-            p.wf_thr = at; at += plane;
-            p.wf_accum = p.spp > p.path_samples ? at : nullptr;
-        } else {
-            p.path_counter = reinterpret_cast<uint32_t*>(arena->mem);
-            p.path_scratch = arena->mem + kHead;
-            HIP_TRY(c, hipMemsetAsync(p.path_counter, 0, kHead, c->stream));
-        }
-    }
-    // Cost feedback: the lifetimes frame f's wavefronts report are sorted on a side stream while the next frames render and
-    // order the launch of frame f + kRing (same ring slot), so neither the sort nor the dependency on an earlier frame
-    // sits on a frame's critical path and kRing frames can be in flight.  Hint only: a stale or missing order changes
-    // speed, never results.
-    const uint32_t nUnits = crt::renderUnitCount(p);
-    const uint64_t key = (static_cast<uint64_t>(p.width) << 40) ^ (static_cast<uint64_t>(p.height) << 20) ^
-                         (static_cast<uint64_t>(p.n_ranks) << 8) ^ p.rank ^ (static_cast<uint64_t>(c->sceneSerial) << 52) ^ 1ull;
-    bool feedback = false;
-    const bool sameStream = c->haveLastRenderStream && c->lastRenderStream == c->stream;
-    c->lastRenderStream = c->stream;
-    c->haveLastRenderStream = true;
-    if ((c->adaptiveOrder == 1 || (c->adaptiveOrder == 2 && sameStream)) && nUnits && p.mode < 200u) { // (the path pipeline has its own work split)
-        if (c->unitCapacity < nUnits) {
-            HIP_TRY(c, hipDeviceSynchronize()); // (frames of other streams may still use the buffers about to be replaced)
-            for (int i = 0; i < crt_ctx::kRing; i++) {
-                if (c->dUnitCost[i]) (void)hipFree(c->dUnitCost[i]);
-                if (c->dUnitOrder[i]) (void)hipFree(c->dUnitOrder[i]);
-                c->dUnitCost[i] = c->dUnitOrder[i] = nullptr;
-                c->orderKey[i] = 0;
-                c->sortPending[i] = false;
-            }
-            c->unitCapacity = 0;
-            for (int i = 0; i < crt_ctx::kRing; i++) {
-                HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->dUnitCost[i]), sizeof(uint32_t) * nUnits));
-                HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->dUnitOrder[i]), sizeof(uint32_t) * nUnits));
-            }
-            c->unitCapacity = nUnits;
-        }
-        const bool usable = c->orderKey[slot] == key;
-        p.unit_order = usable ? c->dUnitOrder[slot] : nullptr;
-        {
-            uint32_t want = c->tuneSplitUnits;
-            if (want == crt_ctx::kSplitAuto) want = p.n_ranks >= 4u ? 128u : (p.n_ranks >= 2u ? 64u : 0u);
-            p.split_units = usable ? std::min(want, nUnits / 4u) : 0u; // (at most a quarter of the packets: the spill arena below is sized for that)
-        }
-        // Costs are measured (and sorted) twice in a row -- the first measurement ran under an unordered launch -- and then:
-        // an unchanged view keeps its order for good; a view that keeps changing (a moving camera) measures again every
-        // remeasure_every-th use of the slot.  Default 1: the order ages fast -- with a camera turning 0.01 degrees per frame
-        // an order 32 frames old cost 0.367 ms per frame, 128 frames old 0.423, against 0.347 when measured every frame.
-        // (The feedback itself -- cost stores, the sort beside the next frame -- is 1.4 % of a frame: tools/moving_camera.py --wobble;
-        //  the rest of that run's difference to a static view was the frame's own cost changing along the orbit.)
-        const bool twice = usable && c->orderGen[slot] >= 2;
-        const bool sameView = c->orderView[slot] == c->viewSerial;
-        const bool recent = (c->frameSerial - c->orderFrame[slot]) < static_cast<uint32_t>(crt_ctx::kRing) * c->tuneRemeasureEvery;
-        if (c->debugForceMeasure || !(twice && (sameView || recent))) {
-            p.unit_cost = c->dUnitCost[slot];
-            feedback = true;
-            c->orderGen[slot] = usable ? c->orderGen[slot] + 1 : 1;
-            c->orderView[slot] = c->viewSerial;
-            c->orderFrame[slot] = c->frameSerial;
-        }
-    }
-    // the previous user of this slot (frame f - kRing, possibly on another stream) and the sort of its costs must be done
-    // before this frame touches the slot's spill arena, cost or order buffer
-    // (a wait is only enqueued when it can matter: not for an event that has already completed, not for a frame that ran on
-    // this same stream -- every barrier packet costs the stream a few microseconds)
-    if (c->sortPending[slot] && hipEventQuery(c->evSort[slot]) != hipSuccess) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evSort[slot], 0));
-    if (p.acc_sum) {
-        const int ro = orderAccum(c);
-        if (ro) return ro;
-    }
-    if (c->renderPending[slot] && c->slotStream[slot] != c->stream && hipEventQuery(c->evRender[slot]) != hipSuccess)
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evRender[slot], 0));
-    c->sortPending[slot] = false;
-    c->slotStream[slot] = c->stream;
-    // split packets add their quarters' lifetimes into their cost slot: start from zero
-    if (p.unit_cost && p.split_units) HIP_TRY(c, hipMemsetAsync(p.unit_cost, 0, sizeof(uint32_t) * nUnits, c->stream));
-    if (stats) HIP_TRY(c, hipEventRecord(c->evStart, c->stream));
-    const int rc = crt::launchRender(p, counting, c->stream);
-    if (rc != 0) return fail(c, CRT_EHIP, "render kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
-    if (stats) HIP_TRY(c, hipEventRecord(c->evStop, c->stream)); // kernel_ms = the render kernel alone
-    HIP_TRY(c, hipEventRecord(c->evRender[slot], c->stream));
-    c->renderPending[slot] = true;
-    if (arena) {
-        HIP_TRY(c, hipEventRecord(arena->lastUse, c->stream));
-        arena->pending = true;
-    }
-    if (p.acc_sum) {
-        const int ra = commitAccum(c, p);
-        if (ra) return ra;
-    }
-    if (feedback) {
-        hipStream_t ss = c->sideStream;
-        HIP_TRY(c, hipStreamWaitEvent(ss, c->evRender[slot], 0));
-        const int rs = crt::launchSortUnits(c->dUnitCost[slot], c->dUnitOrder[slot], nUnits, c->tuneXcdAffine, ss);
-        if (rs != 0) return fail(c, CRT_EHIP, "sort kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rs)));
-        HIP_TRY(c, hipEventRecord(c->evSort[slot], ss));
-        c->sortPending[slot] = true;
-        c->orderKey[slot] = key;
-    }
-    if (stats) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->evStart, c->evStop));
-        std::memset(stats, 0, sizeof(*stats));
-        stats->kernel_ms = ms;
-        stats->rays_primary = 0;
-        // pixels rendered by this launch
-        uint64_t pix = 0;
-        const uint32_t nTiles = p.tiles_x * p.tiles_y;
-        for (uint32_t k = p.rank; k < nTiles; k += p.n_ranks) {
-            const uint32_t tx = k % p.tiles_x, ty = k / p.tiles_x;
-            const uint32_t w = std::min<uint32_t>(crt::kTile, p.width - tx * crt::kTile);
-            const uint32_t h = std::min<uint32_t>(crt::kTile, p.height - ty * crt::kTile);
-            pix += static_cast<uint64_t>(w) * h;
-        }
-        stats->rays_primary = pix;
-        if (counting) {
-            unsigned long long host[4] = { 0, 0, 0, 0 };
-            HIP_TRY(c, hipMemcpy(host, c->dCounters, sizeof(host), hipMemcpyDeviceToHost));
-            stats->nodes_visited = host[0];
-            stats->tris_tested = host[1];
-            stats->rays_shadow = host[2];
-            stats->rays_primary = host[3]; // closest-hit rays: camera rays, plus bounce rays in mode 200
-        }
-    }
-    return CRT_OK;
+    if (c->counting) HIP_TRY(c, hipMemsetAsync(c->dCounters, 0, 32 * sizeof(unsigned long long), c->stream));
+    int rc = frameTimeline(c, p);
+    if (rc) return rc;
+    // Per-frame scratch lives in a ring: see crt_ctx::kRing
+    crt_ctx::FrameSlot& slot = c->slot[c->frameSerial++ % crt_ctx::kRing];
+    crt_ctx::Arena* arena = nullptr; // mode 200 only
+    if (p.mode >= 200u && (rc = framePathScratch(c, p, arena)) != CRT_OK) return rc;
+    if ((rc = frameSpill(c, slot, p)) != CRT_OK) return rc;
+    LaunchOrder lo;
+    if ((rc = frameLaunchOrder(c, slot, p, lo)) != CRT_OK) return rc;
+    if ((rc = frameWaits(c, slot, p)) != CRT_OK) return rc;
+    if ((rc = frameLaunch(c, slot, arena, p, lo, stats != nullptr)) != CRT_OK) return rc;
+    if (lo.measure && (rc = frameSortCosts(c, slot, lo)) != CRT_OK) return rc;
+    return stats ? frameStats(c, p, stats) : CRT_OK;
 }
 
 enum { kAccFrame = 1u, kAccTiles = 2u }; // the entry-point kinds whose frames accumulate (part of the key)
@@ -818,14 +912,7 @@ int runAccumResolve(crt_ctx* c, const RenderParams& p, crt_frame_stats* stats)
     if (rc != 0) return fail(c, CRT_EHIP, "resolve kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
     if (stats) HIP_TRY(c, hipEventRecord(c->evStop, c->stream));
     if ((rc = commitAccum(c, p)) != CRT_OK) return rc;
-    if (stats) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->evStart, c->evStop));
-        std::memset(stats, 0, sizeof(*stats));
-        stats->kernel_ms = ms;
-    }
-    return CRT_OK;
+    return stats ? readStats(c, stats) : CRT_OK;
 }
 
 // one frame of an entry point that accumulates (kind: kAccFrame / kAccTiles)
@@ -844,6 +931,60 @@ int checkRenderable(crt_ctx* c, uint32_t w, uint32_t h)
     return applyRefit(c, nullptr);
 }
 
+// ---- crt_set_option: one row per option.  What an option means and why it has its default stands at the field it is stored in.
+template <int lo, int hi> bool within(int v) { return v >= lo && v <= hi; }
+template <int... values> bool oneOf(int v) { return ((v == values) || ...); }
+bool any(int) { return true; }
+bool innerMin(int v) { return v >= -8 && v <= 65 && v != 0; } // negative: adaptive, eighths of the live lanes
+uint32_t log2Of(int v) { return v == 4 ? 2u : (v == 8 ? 3u : 4u); }
+
+enum OptionEffect { kNoEffect, kNewView /* viewSerial++, even for the value it had: costs are measured again */, kDropOrders };
+struct Option {
+    const char* name;
+    bool (*accepts)(int);
+    void (*store)(crt_ctx& c, int v);
+    OptionEffect effect = kNoEffect;
+    const char* refusal = nullptr; // the option's own message for a value it does not accept; NULL = the common one
+};
+#define U32(field) [](crt_ctx& c, int v) { c.field = static_cast<uint32_t>(v); }
+#define FLAG(field) [](crt_ctx& c, int v) { c.field = v != 0; }
+const Option kOptions[] = {
+    { "gpu_build", any, FLAG(gpuBuild) },
+    { "dynamic", any, FLAG(dynamicOpt) },
+    { "gpu_builder", oneOf<crt::kGpuBuilderLbvh, crt::kGpuBuilderPloc>, [](crt_ctx& c, int v) { c.gpuBuilder = v; } },
+    // the 64-byte 4-wide tree is the only layout: 0 names it, any other width is rejected
+    { "bvh_width", oneOf<0>, [](crt_ctx&, int) {} },
+    { "spp", within<1, 65536>, U32(pathSpp), kNewView },
+    { "max_bounces", within<0, 64>, U32(pathBounces), kNewView },
+    { "phong_ks", within<0, 100000>, U32(phongKsPermille), kNewView },
+    { "phong_exponent", within<1, 65536>, U32(phongExp), kNewView },
+    { "seed", any, U32(pathSeed) },
+    { "path_pipeline", oneOf<0, 1>, U32(tunePathPipeline) },
+    { "path_pass_paths", within<(1 << 16), (1 << 25)>, U32(tunePathPassPaths) },
+    { "path_ranges", oneOf<1, 8>, U32(tunePathRanges) },
+    { "path_tile", oneOf<0, 8, 16>, U32(tunePathTile) },
+    { "inner_min", innerMin, U32(tuneInnerMin) },
+    { "inner_min_any", innerMin, U32(tuneInnerMinAny) },
+    { "list_short_max", within<1, 1024>, U32(tuneListShortMax) },
+    { "xcd_group", oneOf<1, 2, 4, 8, 16>, U32(tuneXcdGroup) },
+    { "xcd_affine_order", oneOf<0, 1>, FLAG(tuneXcdAffine), kDropOrders }, // orders sorted the other way are stale
+    { "split_units", within<-1, 65536>, [](crt_ctx& c, int v) { c.tuneSplitUnits = v < 0 ? crt_ctx::kSplitAuto : static_cast<uint32_t>(v); } },
+    { "split_rays", oneOf<4, 8, 16>, [](crt_ctx& c, int v) { c.tuneSplitRaysLog2 = log2Of(v); } },
+    { "split_segments", oneOf<4, 8, 16>, [](crt_ctx& c, int v) { c.tuneSplitSegsLog2 = log2Of(v); } },
+    { "boost_units", within<0, INT_MAX>, U32(tuneBoostUnits) },
+#if CRT_DIAG
+    { "debug_skip_units", within<0, INT_MAX>, U32(debugSkipUnits) },
+    { "timeline", any, FLAG(wantTimeline) },
+    { "debug_force_measure", any, FLAG(debugForceMeasure) },
+#endif
+    { "remeasure_every", within<1, 1024>, U32(tuneRemeasureEvery) },
+    { "adaptive_order", within<0, 2>, [](crt_ctx& c, int v) { c.adaptiveOrder = v; }, kDropOrders, "adaptive_order takes 0 (off), 1 (on) or 2 (auto)" },
+    { "stack_entries", within<0, crt::kStackEntries>, U32(tuneStackEntries) },
+    { "wide_offsets", oneOf<0, 1>, U32(tuneWideOffsets) },
+};
+#undef U32
+#undef FLAG
+
 } // namespace
 
 extern "C" {
@@ -860,13 +1001,12 @@ hipError_t createSideStream(crt_ctx* c)
     if (e != hipSuccess) return e;
     return hipStreamCreateWithPriority(&c->sideStream, hipStreamNonBlocking, greatest);
 }
+// the frame slots' events up front: without them crt_create fails, not the first frame
 hipError_t createRingEvents(crt_ctx* c)
 {
-    for (int i = 0; i < crt_ctx::kRing; i++) {
-        hipError_t e = hipEventCreateWithFlags(&c->evRender[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->evSort[i], hipEventDisableTiming);
-        if (e != hipSuccess) return e;
-    }
+    for (crt_ctx::FrameSlot& s : c->slot)
+        for (Fence* f : { &s.rendered, &s.sorted })
+            if (const hipError_t e = hipEventCreateWithFlags(&f->event, hipEventDisableTiming)) return e;
     return hipSuccess;
 }
 } // namespace
@@ -907,33 +1047,21 @@ void crt_destroy(crt_ctx* c)
     for (int i = 0; i < 5; i++)
         if (c->dFrame[i]) (void)hipFree(c->dFrame[i]);
     (void)crt_comm_destroy(c);
+    if (c->sideStream) (void)hipStreamSynchronize(c->sideStream);
     for (int i = 0; i < crt_ctx::kRing; i++) {
-        if (c->dStage[i]) (void)hipFree(c->dStage[i]);
-        if (c->dGather[i]) (void)hipFree(c->dGather[i]);
-        if (c->dDistFrame[i]) (void)hipFree(c->dDistFrame[i]);
-        if (c->evDist[i]) (void)hipEventDestroy(c->evDist[i]);
+        crt_ctx::FrameSlot& s = c->slot[i];
+        crt_ctx::DistSlot& d = c->dist[i];
+        for (void* p : std::initializer_list<void*>{ s.spill, s.unitCost, s.unitOrder, d.stage, d.gathered, d.frame, c->pathArena[i].mem, c->rayArena[i].mem })
+            if (p) (void)hipFree(p);
+        for (Fence* f : { &s.rendered, &s.sorted, &d.done, &c->pathArena[i].lastUse, &c->rayArena[i].lastUse }) f->destroy();
     }
     if (c->dCounters) (void)hipFree(c->dCounters);
     if (c->dTextures) (void)hipFree(c->dTextures);
     if (c->dTexels) (void)hipFree(c->dTexels);
-    for (int i = 0; i < crt_ctx::kRing; i++) {
-        if (c->dSpill[i]) (void)hipFree(c->dSpill[i]);
-        for (crt_ctx::Arena* a : { &c->pathArena[i], &c->rayArena[i] }) {
-            if (a->mem) (void)hipFree(a->mem);
-            if (a->lastUse) (void)hipEventDestroy(a->lastUse);
-        }
-    }
-    if (c->sideStream) (void)hipStreamSynchronize(c->sideStream);
-    for (int i = 0; i < crt_ctx::kRing; i++) {
-        if (c->dUnitCost[i]) (void)hipFree(c->dUnitCost[i]);
-        if (c->dUnitOrder[i]) (void)hipFree(c->dUnitOrder[i]);
-        if (c->evRender[i]) (void)hipEventDestroy(c->evRender[i]);
-        if (c->evSort[i]) (void)hipEventDestroy(c->evSort[i]);
-    }
     if (c->sideStream) (void)hipStreamDestroy(c->sideStream);
     if (c->dTimeline) (void)hipFree(c->dTimeline);
     if (c->dAccum) (void)hipFree(c->dAccum);
-    if (c->evAccum) (void)hipEventDestroy(c->evAccum);
+    c->accumUsed.destroy();
     if (c->dRayStage) (void)hipFree(c->dRayStage);
     if (c->dListStage) (void)hipFree(c->dListStage);
     for (hipEvent_t e : c->evList)
@@ -1069,7 +1197,7 @@ int crt_upload_scene(crt_ctx* c, const crt_mesh_view* meshes, uint32_t n_meshes,
     c->buildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count();
     c->haveScene = true;
     c->sceneSerial++;
-    for (uint64_t& k : c->orderKey) k = 0;
+    dropOrders(c);
     return CRT_OK;
 }
 
@@ -1160,132 +1288,21 @@ int crt_set_counting(crt_ctx* c, int enabled)
 int crt_set_option(crt_ctx* c, const char* name, int value)
 {
     if (!c || !name) return CRT_EINVAL;
-    if (std::strcmp(name, "gpu_build") == 0) {
-        c->gpuBuild = value != 0;
+    for (const Option& o : kOptions) {
+        if (std::strcmp(name, o.name) != 0) continue;
+        if (!o.accepts(value)) {
+            if (o.refusal) return fail(c, CRT_EINVAL, "%s", o.refusal);
+            break;
+        }
+        o.store(*c, value);
+        if (o.effect == kNewView) c->viewSerial++;
+        if (o.effect == kDropOrders) dropOrders(c);
         return CRT_OK;
     }
-    if (std::strcmp(name, "dynamic") == 0) {
-        c->dynamicOpt = value != 0;
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "gpu_builder") == 0 && (value == crt::kGpuBuilderLbvh || value == crt::kGpuBuilderPloc)) {
-        c->gpuBuilder = value;
-        return CRT_OK;
-    }
-    // the 64-byte 4-wide tree is the only layout: 0 names it, any other width is rejected below
-    if (std::strcmp(name, "bvh_width") == 0 && value == 0) return CRT_OK;
-    if (std::strcmp(name, "spp") == 0 && value >= 1 && value <= 65536) {
-        c->pathSpp = static_cast<uint32_t>(value);
-        c->viewSerial++;
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "max_bounces") == 0 && value >= 0 && value <= 64) {
-        c->pathBounces = static_cast<uint32_t>(value);
-        c->viewSerial++;
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "phong_ks") == 0 && value >= 0 && value <= 100000) {
-        c->phongKsPermille = static_cast<uint32_t>(value);
-        c->viewSerial++;
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "phong_exponent") == 0 && value >= 1 && value <= 65536) {
-        c->phongExp = static_cast<uint32_t>(value);
-        c->viewSerial++;
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "seed") == 0) {
-        c->pathSeed = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "path_pipeline") == 0 && (value == 0 || value == 1)) {
-        c->tunePathPipeline = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "path_pass_paths") == 0 && value >= (1 << 16) && value <= (1 << 25)) {
-        c->tunePathPassPaths = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "path_ranges") == 0 && (value == 1 || value == 8)) {
-        c->tunePathRanges = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "path_tile") == 0 && (value == 0 || value == 8 || value == 16)) {
-        c->tunePathTile = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "inner_min") == 0 && value >= -8 && value <= 65 && value != 0) { // negative: adaptive, eighths of the live lanes
-        c->tuneInnerMin = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "inner_min_any") == 0 && value >= -8 && value <= 65 && value != 0) {
-        c->tuneInnerMinAny = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "list_short_max") == 0 && value >= 1 && value <= 1024) {
-        c->tuneListShortMax = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "xcd_group") == 0 && (value == 1 || value == 2 || value == 4 || value == 8 || value == 16)) {
-        c->tuneXcdGroup = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "xcd_affine_order") == 0 && (value == 0 || value == 1)) {
-        c->tuneXcdAffine = value != 0;
-        for (int i = 0; i < crt_ctx::kRing; i++) c->orderKey[i] = 0; // orders sorted the other way are stale
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "split_units") == 0 && value >= -1 && value <= 65536) {
-        c->tuneSplitUnits = value < 0 ? crt_ctx::kSplitAuto : static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "split_rays") == 0 && (value == 4 || value == 8 || value == 16)) {
-        c->tuneSplitRaysLog2 = value == 4 ? 2u : (value == 8 ? 3u : 4u);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "split_segments") == 0 && (value == 4 || value == 8 || value == 16)) {
-        c->tuneSplitSegsLog2 = value == 4 ? 2u : (value == 8 ? 3u : 4u);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "boost_units") == 0 && value >= 0) {
-        c->tuneBoostUnits = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-#if CRT_DIAG
-    if (std::strcmp(name, "debug_skip_units") == 0 && value >= 0) {
-        c->debugSkipUnits = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "timeline") == 0) {
-        c->wantTimeline = value != 0;
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "debug_force_measure") == 0) {
-        c->debugForceMeasure = value != 0;
-        return CRT_OK;
-    }
-#else
-    if (std::strcmp(name, "debug_skip_units") == 0 || std::strcmp(name, "timeline") == 0 || std::strcmp(name, "debug_force_measure") == 0)
-        return fail(c, CRT_EINVAL, "option '%s' exists only in the diagnostic build (tools/diag_build.sh)", name);
+#if !CRT_DIAG
+    for (const char* diagnostic : { "debug_skip_units", "timeline", "debug_force_measure" })
+        if (std::strcmp(name, diagnostic) == 0) return fail(c, CRT_EINVAL, "option '%s' exists only in the diagnostic build (tools/diag_build.sh)", name);
 #endif
-    if (std::strcmp(name, "remeasure_every") == 0 && value >= 1 && value <= 1024) {
-        c->tuneRemeasureEvery = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "adaptive_order") == 0) {
-        if (value < 0 || value > 2) return fail(c, CRT_EINVAL, "adaptive_order takes 0 (off), 1 (on) or 2 (auto)");
-        c->adaptiveOrder = static_cast<int>(value);
-        for (uint64_t& k : c->orderKey) k = 0;
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "stack_entries") == 0 && (value == 0 || (value >= 1 && value <= crt::kStackEntries))) {
-        c->tuneStackEntries = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
-    if (std::strcmp(name, "wide_offsets") == 0 && (value == 0 || value == 1)) {
-        c->tuneWideOffsets = static_cast<uint32_t>(value);
-        return CRT_OK;
-    }
     return fail(c, CRT_EINVAL, "unknown option '%s' or value %d out of range", name, value);
 }
 
@@ -1505,7 +1522,7 @@ int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t entryWords, crt_
 {
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = queryGrid(c, kind, n, ql.stack_entries, ql.chunk, ql.grid)) return rc;
-    const uint32_t deepest = 3u * c->bvh.depth4 + 1u; // as runRender
+    const uint32_t deepest = 3u * c->bvh.depth4 + 1u; // as frameSpill
     ql.spill_stride = (deepest > ql.stack_entries ? deepest - ql.stack_entries : 1u) * entryWords;
 
     constexpr size_t kHead = 256; // cursor at 0, counters at 64
@@ -1524,28 +1541,16 @@ int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t entryWords, crt_
 
 int endQuery(crt_ctx* c, QueryKind kind, uint32_t n, const QueryLaunch& ql, int rc, crt_frame_stats* stats)
 {
-    crt_ctx::Arena* arena = ql.arena;
     if (rc != 0) return fail(c, CRT_EHIP, "query kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
     if (stats) HIP_TRY(c, hipEventRecord(c->evStop, c->stream));
-    HIP_TRY(c, hipEventRecord(arena->lastUse, c->stream));
-    arena->pending = true;
-    if (stats) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->evStart, c->evStop));
-        std::memset(stats, 0, sizeof(*stats));
-        stats->kernel_ms = ms;
-        if (kind == kQueryOcclusion) stats->rays_shadow = n;
-        else stats->rays_primary = kind == kQueryOccupancy ? 3ull * n : n;
-        if (c->counting) {
-            unsigned long long host[4] = { 0, 0, 0, 0 };
-            HIP_TRY(c, hipMemcpy(host, ql.counters, sizeof(host), hipMemcpyDeviceToHost));
-            stats->nodes_visited = host[0];
-            stats->tris_tested = host[1];
-            if (kind == kQueryShade || kind == kQueryPath) stats->rays_shadow = host[2]; // the shadow rays traced (mode 100; paths)
-            if (kind == kQueryPath) stats->rays_primary += host[3];                       // the bounce rays of the paths
-        }
-    }
+    HIP_TRY(c, ql.arena->lastUse.record(c->stream));
+    if (!stats) return CRT_OK;
+    unsigned long long words[4]; // (zeros unless counting is on)
+    if (const int rs = readStats(c, stats, ql.counters, words)) return rs;
+    if (kind == kQueryOcclusion) stats->rays_shadow = n;
+    else stats->rays_primary = kind == kQueryOccupancy ? 3ull * n : n;
+    if (c->counting && (kind == kQueryShade || kind == kQueryPath)) stats->rays_shadow = words[2]; // the shadow rays traced (mode 100; paths)
+    if (kind == kQueryPath) stats->rays_primary += words[3];                                      // the bounce rays of the paths
     return CRT_OK;
 }
 
@@ -2064,15 +2069,9 @@ int runTimed(crt_ctx* c, const char* what, crt_frame_stats* stats, const std::fu
     if (stats) HIP_TRY(c, hipEventRecord(c->evStart, c->stream));
     const int hrc = launch();
     if (hrc != 0) return fail(c, CRT_EHIP, "%s: kernel launch failed: %s", what, hipGetErrorString(static_cast<hipError_t>(hrc)));
-    if (stats) {
-        HIP_TRY(c, hipEventRecord(c->evStop, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->evStart, c->evStop));
-        std::memset(stats, 0, sizeof(*stats));
-        stats->kernel_ms = ms;
-    }
-    return CRT_OK;
+    if (!stats) return CRT_OK;
+    HIP_TRY(c, hipEventRecord(c->evStop, c->stream));
+    return readStats(c, stats);
 }
 
 int runCameraRays(crt_ctx* c, const char* what, uint32_t w, uint32_t h, uint32_t sample, void* d_rays, crt_frame_stats* stats)
@@ -2174,8 +2173,7 @@ int runDenoise(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void*
     return runTimed(c, what, stats, [&] {
         const int hrc = crt::launchDenoise(p, c->stream);
         if (hrc != 0) return hrc;
-        arena->pending = true;
-        return static_cast<int>(hipEventRecord(arena->lastUse, c->stream));
+        return static_cast<int>(arena->lastUse.record(c->stream));
     });
 }
 
@@ -3022,7 +3020,7 @@ int crt_rebuild(crt_ctx* c, double* device_ms)
     }
     c->sceneSerial++;
     c->accSamples = 0u;
-    for (uint64_t& k : c->orderKey) k = 0;
+    dropOrders(c);
     return CRT_OK;
 }
 
@@ -3427,39 +3425,36 @@ int crt_render_frame_distributed(crt_ctx* c, uint32_t w, uint32_t h, void* d_rgb
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t n = c->commRanks, slots = crt_tile_slots(w, h, n);
     const size_t per = static_cast<size_t>(slots) * crt::kTile * crt::kTile * 4; // bytes each rank contributes
-    const uint32_t k = c->distSerial++ % crt_ctx::kRing;
-    if ((rc = ensureBuffer(c, &c->dStage[k], &c->stageBytes[k], per)) != CRT_OK) return rc;
-    if ((rc = ensureBuffer(c, &c->dGather[k], &c->gatherBytes[k], per * n)) != CRT_OK) return rc;
+    crt_ctx::DistSlot& d = c->dist[c->distSerial++ % crt_ctx::kRing];
+    if ((rc = ensureBuffer(c, &d.stage, &d.stageBytes, per)) != CRT_OK) return rc;
+    if ((rc = ensureBuffer(c, &d.gathered, &d.gatheredBytes, per * n)) != CRT_OK) return rc;
     void* frame = d_rgba8;
     if (!frame) {
-        if ((rc = ensureBuffer(c, &c->dDistFrame[k], &c->distFrameBytes[k], static_cast<size_t>(w) * h * 4)) != CRT_OK) return rc;
-        frame = c->dDistFrame[k];
+        if ((rc = ensureBuffer(c, &d.frame, &d.frameBytes, static_cast<size_t>(w) * h * 4)) != CRT_OK) return rc;
+        frame = d.frame;
     }
     // the slot's previous frame (4 frames ago) may have been issued on another stream: order behind it on the GPU
-    if (c->distPending[k] && c->distStream[k] != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evDist[k], 0));
+    HIP_TRY(c, d.done.wait(c->stream, false));
     crt_frame_stats local;
-    rc = crt_render_tiles_device(c, w, h, c->commRank, n, c->dStage[k], stats ? &local : nullptr);
+    rc = crt_render_tiles_device(c, w, h, c->commRank, n, d.stage, stats ? &local : nullptr);
     if (rc) return rc;
     if (c->comm) {
-        const ncclResult_t r = rccl().allGather(c->dStage[k], c->dGather[k], per, ncclUint8, c->comm, c->stream);
+        const ncclResult_t r = rccl().allGather(d.stage, d.gathered, per, ncclUint8, c->comm, c->stream);
         if (r != ncclSuccess) return fail(c, CRT_EHIP, "ncclAllGather failed: %s", rccl().getErrorString(r));
     } else { // through shared host memory: own slice in, everybody waits, all slices out, everybody waits again before the next frame's writes
         HostExchange* x = c->hostComm;
         if (per * n > x->header()->capacity) return fail(c, CRT_EINVAL, "crt_render_frame_distributed: frame too large for the host exchange");
-        HIP_TRY(c, hipMemcpyAsync(x->data() + per * c->commRank, c->dStage[k], per, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(x->data() + per * c->commRank, d.stage, per, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (!x->barrier(n)) return fail(c, CRT_EIO, "crt_render_frame_distributed: a rank did not deliver its tiles within a minute");
-        HIP_TRY(c, hipMemcpyAsync(c->dGather[k], x->data(), per * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d.gathered, x->data(), per * n, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (!x->barrier(n)) return fail(c, CRT_EIO, "crt_render_frame_distributed: a rank did not collect the tiles within a minute");
     }
-    rc = crt_untile_device(c, w, h, n, c->dGather[k], frame);
+    rc = crt_untile_device(c, w, h, n, d.gathered, frame);
     if (rc) return rc;
     if (host_rgba8) HIP_TRY(c, hipMemcpyAsync(host_rgba8, frame, static_cast<size_t>(w) * h * 4, hipMemcpyDeviceToHost, c->stream));
-    if (!c->evDist[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->evDist[k], hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->evDist[k], c->stream));
-    c->distStream[k] = c->stream;
-    c->distPending[k] = true;
+    HIP_TRY(c, d.done.record(c->stream));
     if (stats || host_rgba8) HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (stats) {
         *stats = local; // kernel_ms and the counters describe this rank's tile launch
