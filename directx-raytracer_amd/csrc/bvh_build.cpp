@@ -52,8 +52,6 @@ struct TempNode {
     int32_t left, right; // >= 0: pool index, < 0: final leaf reference
 };
 
-inline int32_t leafRef(uint32_t first, uint32_t count) { return ~static_cast<int32_t>((first << 3) | count); }
-
 struct Builder {
     const Box* primBox;
     const float* cent; // 3 per triangle
@@ -411,9 +409,7 @@ void buildBvh(const crt_mesh_view* meshes, uint32_t n_meshes, Bvh& out)
     out.maxDepth = 0;
     out.uvs.clear();
     out.nTris = 0;
-    out.devTris = out.devShade = out.devUvs = nullptr;
-    out.devNodes = out.devNodes4 = out.devNodes4q = nullptr;
-    out.nNodes = out.nNodes4 = 0;
+    out.dev = DeviceTree();
     if (n == 0) return;
 
     std::vector<Box> primBox(n);
@@ -520,8 +516,6 @@ void collapseBvh4(Bvh& bvh)
         for (int i = n - 1; i >= 0; i--)
             if (sl[i].ref >= 0) work.push_back({ sl[i].ref, me, i, w.depth + 1 });
     }
-    bvh.nNodes = static_cast<uint32_t>(bvh.nodes.size());
-    bvh.nNodes4 = static_cast<uint32_t>(bvh.nodes4.size());
     bvh.nodes4q.resize(bvh.nodes4.size());
     const int64_t nq = static_cast<int64_t>(bvh.nodes4.size());
 #pragma omp parallel for schedule(static) if (nq > 65536)

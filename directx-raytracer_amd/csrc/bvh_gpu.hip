@@ -14,8 +14,9 @@
 // both and starts from meshes already in HBM, so the rebuild of a dynamic scene (crt_rebuild) runs the same code as an upload.
 #include "bvh_build.h"
 #include "bvh_wide.h"
-#include "mesh_table.hip.h"
+#include "hip_own.h"
 #include "render_kernels.h"
+#include "tri_geometry.hip.h"
 
 #include <hip/hip_runtime.h>
 #include "gpu_sort.hip.h"
@@ -30,12 +31,6 @@
 
 namespace crt {
 namespace {
-
-#define GPU_TRY(expr)                                                                                          \
-    do {                                                                                                       \
-        hipError_t e_ = (expr);                                                                                \
-        if (e_ != hipSuccess) throw std::runtime_error(std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-    } while (0)
 
 struct KNode { // Karras internal node
     int left, right;   // >= 0 internal index, < 0: ~sorted leaf position
@@ -80,16 +75,6 @@ __global__ __launch_bounds__(256) void boundsKernel(const float* __restrict__ ce
         }
 }
 
-__device__ __forceinline__ uint32_t expandBits10(uint32_t v)
-{
-    v = (v * 0x00010001u) & 0xFF0000FFu;
-    v = (v * 0x00000101u) & 0x0F00F00Fu;
-    v = (v * 0x00000011u) & 0xC30C30C3u;
-    v = (v * 0x00000005u) & 0x49249249u;
-    return v;
-}
-__device__ __forceinline__ uint32_t quant10(float f) { return f >= 0.0f ? (f < 1024.0f ? static_cast<uint32_t>(f) : 1023u) : 0u; }
-
 __global__ __launch_bounds__(256) void mortonKernel(const float* __restrict__ cent, uint32_t n, const int* __restrict__ bounds,
                                                     unsigned long long* __restrict__ keys)
 {
@@ -101,7 +86,7 @@ __global__ __launch_bounds__(256) void mortonKernel(const float* __restrict__ ce
         const float ext = fromOrderedInt(bounds[3 + a]) - fromOrderedInt(bounds[a]);
         if (ext > extm) extm = ext;
     }
-    const float scale = extm > 0.0f ? 1024.0f / extm : 0.0f;
+    const float scale = mortonScale(extm);
     for (int a = 0; a < 3; a++) q[a] = quant10((cent[3 * static_cast<size_t>(i) + a] - fromOrderedInt(bounds[a])) * scale);
     const uint32_t code = (expandBits10(q[0]) << 2) | (expandBits10(q[1]) << 1) | expandBits10(q[2]);
     keys[i] = (static_cast<unsigned long long>(code) << 32) | i;
@@ -147,8 +132,6 @@ __global__ __launch_bounds__(256) void hierarchyKernel(const unsigned long long*
     if (i == 0) parentOfInternal[0] = -1;
 }
 
-struct Box6 { float mn[3], mx[3]; };
-
 // bottom-up exact boxes: the second thread to arrive at a node unions its children and moves on.  A node whose triangle
 // range lies inside the 256 leaves of one workgroup is only ever touched by that workgroup: arrival counter and fences at
 // workgroup scope, which cost nothing.  A node spanning workgroups hands boxes between XCDs through memory, so those hops
@@ -182,11 +165,7 @@ __global__ __launch_bounds__(256) void fitKernel(const KNode* __restrict__ K, co
                 for (int a = 0; a < 3; a++) { cb.mn[a] = src->mn[a]; cb.mx[a] = src->mx[a]; }
             }
             if (c == 0) b = cb;
-            else
-                for (int a = 0; a < 3; a++) {
-                    b.mn[a] = b.mn[a] < cb.mn[a] ? b.mn[a] : cb.mn[a]; // same selects as the oracle's aabb_grow(l, r)
-                    b.mx[a] = b.mx[a] > cb.mx[a] ? b.mx[a] : cb.mx[a];
-                }
+            else b = unionBox(b, cb); // same selects as the oracle's aabb_grow(l, r)
         }
         // write-through stores: an agent-scope release writes this XCD's dirty L2 lines back, and it is far cheaper when
         // the 24 MB of boxes this kernel produces are not sitting there dirty
@@ -204,8 +183,6 @@ __global__ __launch_bounds__(256) void keptKernel(const KNode* __restrict__ K, u
     if (i < nInternal) kept[i] = (K[i].hi - K[i].lo + 1u > static_cast<uint32_t>(kLbvhLeafMax)) ? 1u : 0u;
 }
 
-__device__ __forceinline__ int leafRefDev(uint32_t first, uint32_t count) { return ~static_cast<int>((first << 3) | count); }
-
 __global__ __launch_bounds__(256) void emitKernel(const KNode* __restrict__ K, const uint32_t* __restrict__ kept, const uint32_t* __restrict__ rank,
                                                   const Box6* __restrict__ nodeBox, const Box6* __restrict__ pbox,
                                                   const unsigned long long* __restrict__ keys, uint32_t nInternal, crt_bvh_node* __restrict__ out)
@@ -219,11 +196,11 @@ __global__ __launch_bounds__(256) void emitKernel(const KNode* __restrict__ K, c
         const int ch = c == 0 ? k.left : k.right;
         if (ch < 0) {
             b[c] = pbox[static_cast<uint32_t>(keys[~ch] & 0xFFFFFFFFull)];
-            ref[c] = leafRefDev(static_cast<uint32_t>(~ch), 1u);
+            ref[c] = leafRef(static_cast<uint32_t>(~ch), 1u);
         } else {
             b[c] = nodeBox[ch];
             const uint32_t cnt = K[ch].hi - K[ch].lo + 1u;
-            ref[c] = cnt <= static_cast<uint32_t>(kLbvhLeafMax) ? leafRefDev(K[ch].lo, cnt) : static_cast<int>(rank[ch]);
+            ref[c] = cnt <= static_cast<uint32_t>(kLbvhLeafMax) ? leafRef(K[ch].lo, cnt) : static_cast<int>(rank[ch]);
         }
     }
     crt_bvh_node N;
@@ -233,9 +210,6 @@ __global__ __launch_bounds__(256) void emitKernel(const KNode* __restrict__ K, c
     out[rank[i]] = N;
 }
 
-__device__ __forceinline__ float minSel(float a, float b) { return a < b ? a : b; }
-__device__ __forceinline__ float maxSel(float a, float b) { return a > b ? a : b; }
-
 // per input triangle (global ordinal g): bounds and centroid, exactly as flattenMeshes computes them on the host
 __global__ __launch_bounds__(256) void triBoxKernel(const MeshEntry* __restrict__ table, uint32_t n_meshes, const float* __restrict__ xyz,
                                                     const uint32_t* __restrict__ idx, uint32_t n, Box6* __restrict__ box, float* __restrict__ cent,
@@ -243,26 +217,9 @@ __global__ __launch_bounds__(256) void triBoxKernel(const MeshEntry* __restrict_
 {
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
     if (g >= n) return;
-    const MeshEntry M = table[meshOf(table, n_meshes, g)];
-    const uint32_t i0 = idx[3 * static_cast<size_t>(g)], i1 = idx[3 * static_cast<size_t>(g) + 1], i2 = idx[3 * static_cast<size_t>(g) + 2];
-    Box6 b;
-    if (i0 >= M.nVerts || i1 >= M.nVerts || i2 >= M.nVerts) {
-        *badIndex = 1;
-        for (int k = 0; k < 3; k++) { b.mn[k] = 0.0f; b.mx[k] = 0.0f; cent[3 * static_cast<size_t>(g) + k] = 0.0f; }
-        box[g] = b;
-        return;
-    }
-    const float* A = xyz + 3 * static_cast<size_t>(M.vertStart + i0);
-    const float* B = xyz + 3 * static_cast<size_t>(M.vertStart + i1);
-    const float* C = xyz + 3 * static_cast<size_t>(M.vertStart + i2);
-    bool finite = true;
-    for (int k = 0; k < 3; k++) {
-        b.mn[k] = minSel(minSel(A[k], B[k]), C[k]);
-        b.mx[k] = maxSel(maxSel(A[k], B[k]), C[k]);
-        finite &= A[k] - A[k] == 0.0f && B[k] - B[k] == 0.0f && C[k] - C[k] == 0.0f; // x - x == 0: finite
-    }
-    if (!finite) // an inert triangle (crt_hip.h): the point (0, 0, 0), as flattenMeshes gives it
-        for (int k = 0; k < 3; k++) { b.mn[k] = 0.0f; b.mx[k] = 0.0f; }
+    const TriFetch t = fetchTri<true>(table, n_meshes, xyz, idx, g);
+    if (!t.inRange) *badIndex = 1; // (the build throws; the triangle counts as inert until then)
+    const Box6 b = triBox(t);
     for (int k = 0; k < 3; k++) cent[3 * static_cast<size_t>(g) + k] = (b.mn[k] + b.mx[k]) * 0.5f;
     box[g] = b;
 }
@@ -277,46 +234,26 @@ __global__ __launch_bounds__(256) void gatherKernel(const unsigned long long* __
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const uint32_t g = static_cast<uint32_t>(keys[i] & 0xFFFFFFFFull);
-    const uint32_t m = meshOf(table, n_meshes, g);
-    const MeshEntry M = table[m];
-    const uint32_t v0 = M.vertStart + idx[3 * static_cast<size_t>(g)], v1 = M.vertStart + idx[3 * static_cast<size_t>(g) + 1],
-                   v2 = M.vertStart + idx[3 * static_cast<size_t>(g) + 2];
-    const float* A = xyz + 3 * static_cast<size_t>(v0);
-    const float* B = xyz + 3 * static_cast<size_t>(v1);
-    const float* C = xyz + 3 * static_cast<size_t>(v2);
+    const TriFetch t = fetchTri(table, n_meshes, xyz, idx, g);
     crt_bvh_tri T;
-    bool finite = true;
-    for (int k = 0; k < 3; k++) {
-        T.v0[k] = A[k];
-        T.e1[k] = B[k] - A[k];
-        T.e2[k] = C[k] - A[k];
-        finite &= A[k] - A[k] == 0.0f && B[k] - B[k] == 0.0f && C[k] - C[k] == 0.0f; // x - x == 0: finite
-    }
-    if (!finite) // an inert triangle (crt_hip.h): nine quiet NaNs of one bit pattern, as flattenMeshes writes them
-        for (int k = 0; k < 3; k++) T.v0[k] = T.e1[k] = T.e2[k] = __uint_as_float(0x7FC00000u);
-    T.inst = m;
-    T.prim = g - M.triStart;
+    triRecord(t, T.v0, T.e1, T.e2);
+    T.inst = t.mesh;
+    T.prim = g - t.M.triStart;
     T.gid = g;
     tris[i] = T;
     crt_bvh_shade S;
     for (int k = 0; k < 3; k++) { S.n0[k] = 0.0f; S.n1[k] = 0.0f; S.n2[k] = 0.0f; }
-    S.material = M.material;
+    S.material = t.M.material;
     S.pad[0] = 0; S.pad[1] = 0;
-    if (M.hasNormals) {
-        for (int k = 0; k < 3; k++) {
-            S.n0[k] = normals[3 * static_cast<size_t>(v0) + k];
-            S.n1[k] = normals[3 * static_cast<size_t>(v1) + k];
-            S.n2[k] = normals[3 * static_cast<size_t>(v2) + k];
-        }
-    }
+    triNormals(t, normals, S.n0, S.n1, S.n2);
     shade[i] = S;
     if (uvs) {
         crt_bvh_uv U;
         U.uv0[0] = U.uv0[1] = U.uv1[0] = U.uv1[1] = U.uv2[0] = U.uv2[1] = 0.0f;
-        if (M.hasUvs) {
-            U.uv0[0] = uvsIn[3 * static_cast<size_t>(v0)]; U.uv0[1] = uvsIn[3 * static_cast<size_t>(v0) + 1];
-            U.uv1[0] = uvsIn[3 * static_cast<size_t>(v1)]; U.uv1[1] = uvsIn[3 * static_cast<size_t>(v1) + 1];
-            U.uv2[0] = uvsIn[3 * static_cast<size_t>(v2)]; U.uv2[1] = uvsIn[3 * static_cast<size_t>(v2) + 1];
+        if (t.M.hasUvs) {
+            U.uv0[0] = uvsIn[3 * static_cast<size_t>(t.v[0])]; U.uv0[1] = uvsIn[3 * static_cast<size_t>(t.v[0]) + 1];
+            U.uv1[0] = uvsIn[3 * static_cast<size_t>(t.v[1])]; U.uv1[1] = uvsIn[3 * static_cast<size_t>(t.v[1]) + 1];
+            U.uv2[0] = uvsIn[3 * static_cast<size_t>(t.v[2])]; U.uv2[1] = uvsIn[3 * static_cast<size_t>(t.v[2]) + 1];
         }
         uvs[i] = U;
     }
@@ -427,16 +364,6 @@ __global__ __launch_bounds__(256) void decodePlanesKernel(const unsigned char* _
     planes[t] = k < 24u ? static_cast<float>(nodes[node * sizeof(crt_bvh_node4q) + offsetof(crt_bvh_node4q, qlo_x) + k]) : 0.0f;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    explicit DevBuf(size_t bytes) { GPU_TRY(hipMalloc(&p, bytes ? bytes : 16)); }
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    template <class T> T* as() const { return static_cast<T*>(p); }
-    void* release() { void* q = p; p = nullptr; return q; } // ownership leaves (the context adopts the buffer)
-};
-
 } // namespace
 
 size_t collapseScratchBytes(uint32_t nBinary)
@@ -446,11 +373,11 @@ size_t collapseScratchBytes(uint32_t nBinary)
 }
 
 // Binary -> 4-wide collapse + quantisation of the nBinary nodes at `nodes` (the rules: bvh_wide.h).  Scratch: collapseScratchBytes.
-// *nodes4 / *nodes4q: buffers of at least nBinary records (a wide node absorbs one binary node at least), or NULL: then buffers of
-// exactly the wide node count (+128 bytes of slack behind the quantised ones) are allocated here and handed to the caller.
+// nodes4 / nodes4q: buffers of at least nBinary records (a wide node absorbs one binary node at least); or, with `fresh` set, they
+// are ignored and fresh->nodes4 / nodes4q are allocated here for exactly the wide node count and written instead.
 // Synchronises the stream once per wide level (the next level's count decides the next launch).
-void collapseWideGpu(const crt_bvh_node* nodes, uint32_t nBinary, void* scratch, void** nodes4, void** nodes4q, ihipStream_t* stream,
-                     uint32_t* nWideOut, uint32_t* depth4Out, uint32_t* maxDepthOut)
+void collapseWideGpu(const crt_bvh_node* nodes, uint32_t nBinary, void* scratch, void* nodes4, void* nodes4q, DeviceTree* fresh,
+                     ihipStream_t* stream, uint32_t* nWideOut, uint32_t* depth4Out, uint32_t* maxDepthOut)
 {
     const size_t n = nBinary ? nBinary : 1u;
     WideTmp* dTmp = static_cast<WideTmp*>(scratch);
@@ -463,21 +390,21 @@ void collapseWideGpu(const crt_bvh_node* nodes, uint32_t nBinary, void* scratch,
     std::vector<std::pair<uint32_t, uint32_t>> levels; // {first temporary index, count}
     {
         const uint32_t rootEntry[2] = { 0u, 0u };
-        GPU_TRY(hipMemcpyAsync(dFrontA, rootEntry, sizeof(rootEntry), hipMemcpyHostToDevice, stream));
-        GPU_TRY(hipMemsetAsync(dScalars, 0, sizeof(uint32_t) * 2, stream));
+        HIP_THROW(hipMemcpyAsync(dFrontA, rootEntry, sizeof(rootEntry), hipMemcpyHostToDevice, stream));
+        HIP_THROW(hipMemsetAsync(dScalars, 0, sizeof(uint32_t) * 2, stream));
         uint32_t base = 0, count = 1;
         uint32_t* cur = dFrontA;
         uint32_t* nxt = dFrontB;
         while (count) {
             if (static_cast<uint64_t>(base) + count > nBinary) throw std::runtime_error("wide collapse: more wide nodes than binary nodes");
             levels.emplace_back(base, count);
-            GPU_TRY(hipMemsetAsync(dScalars, 0, sizeof(uint32_t), stream));
+            HIP_THROW(hipMemsetAsync(dScalars, 0, sizeof(uint32_t), stream));
             hipLaunchKernelGGL(wideExpandKernel, dim3((count + 255) / 256), blk, 0, stream, nodes, cur, count, base, base + count, dTmp, nxt,
                                dScalars, dScalars + 1);
-            GPU_TRY(hipGetLastError());
+            HIP_THROW(hipGetLastError());
             uint32_t nextCount = 0;
-            GPU_TRY(hipMemcpyAsync(&nextCount, dScalars, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            GPU_TRY(hipStreamSynchronize(stream));
+            HIP_THROW(hipMemcpyAsync(&nextCount, dScalars, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIP_THROW(hipStreamSynchronize(stream));
             base += count;
             count = nextCount;
             std::swap(cur, nxt);
@@ -486,21 +413,22 @@ void collapseWideGpu(const crt_bvh_node* nodes, uint32_t nBinary, void* scratch,
     const uint32_t nWide = levels.back().first + levels.back().second;
     for (size_t L = levels.size(); L-- > 0;)
         hipLaunchKernelGGL(wideSizeKernel, dim3((levels[L].second + 255) / 256), blk, 0, stream, dTmp, levels[L].first, levels[L].second, dSize);
-    GPU_TRY(hipMemsetAsync(dId, 0, sizeof(uint32_t), stream)); // the root's id
+    HIP_THROW(hipMemsetAsync(dId, 0, sizeof(uint32_t), stream)); // the root's id
     for (size_t L = 0; L < levels.size(); L++)
         hipLaunchKernelGGL(wideIdKernel, dim3((levels[L].second + 255) / 256), blk, 0, stream, dTmp, levels[L].first, levels[L].second, dSize, dId);
-    GPU_TRY(hipGetLastError());
-    if (!*nodes4) {
-        DevBuf a(sizeof(crt_bvh_node4) * nWide), b(sizeof(crt_bvh_node4q) * nWide + 128);
-        *nodes4 = a.release();
-        *nodes4q = b.release();
+    HIP_THROW(hipGetLastError());
+    if (fresh) {
+        fresh->nodes4 = DeviceBuffer(sizeof(crt_bvh_node4) * nWide);
+        fresh->nodes4q = DeviceBuffer(quantisedBytes(nWide));
+        nodes4 = fresh->nodes4.as<>();
+        nodes4q = fresh->nodes4q.as<>();
     }
-    hipLaunchKernelGGL(wideEmitKernel, dim3((nWide + 255) / 256), blk, 0, stream, dTmp, nWide, dId, static_cast<crt_bvh_node4*>(*nodes4),
-                       static_cast<crt_bvh_node4q*>(*nodes4q));
-    GPU_TRY(hipGetLastError());
+    hipLaunchKernelGGL(wideEmitKernel, dim3((nWide + 255) / 256), blk, 0, stream, dTmp, nWide, dId, static_cast<crt_bvh_node4*>(nodes4),
+                       static_cast<crt_bvh_node4q*>(nodes4q));
+    HIP_THROW(hipGetLastError());
     uint32_t maxDepth = 0;
-    GPU_TRY(hipMemcpyAsync(&maxDepth, dScalars + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    GPU_TRY(hipStreamSynchronize(stream));
+    HIP_THROW(hipMemcpyAsync(&maxDepth, dScalars + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_THROW(hipStreamSynchronize(stream));
     *nWideOut = nWide;
     *depth4Out = static_cast<uint32_t>(levels.size());
     if (maxDepthOut) *maxDepthOut = maxDepth;
@@ -509,32 +437,25 @@ void collapseWideGpu(const crt_bvh_node* nodes, uint32_t nBinary, void* scratch,
 namespace {
 
 // Morton order, the builder's binary tree, the leaf-ordered records and the wide tree, from meshes already in HBM (n > kLeafMax)
-void buildFromDevice(const GpuMeshes& in, int builder, Bvh& out, ihipStream_t* stream, double* device_ms, const std::function<void(const char*)>& lap)
+DeviceTree buildFromDevice(const GpuMeshes& in, int builder, ihipStream_t* stream, double* device_ms, const std::function<void(const char*)>& lap)
 {
     const bool timing = std::getenv("CRT_BUILD_TIMING") != nullptr;
     const uint32_t n = in.n, n_meshes = in.nMeshes, nInternal = n - 1;
     const MeshEntry* table = static_cast<const MeshEntry*>(in.table);
-    DevBuf dBad(sizeof(int));
-    DevBuf dBox(sizeof(Box6) * n), dCent(sizeof(float) * 3 * n), dBounds(sizeof(int) * 6);
-    DevBuf dKeysIn(sizeof(unsigned long long) * n), dKeys(sizeof(unsigned long long) * n);
-    // the records the kernels will traverse (+64 bytes of slack for speculative wide loads of the last record)
-    DevBuf dTris(sizeof(crt_bvh_tri) * n + 64), dShade(sizeof(crt_bvh_shade) * n + 64), dUvs(in.uvsIn ? sizeof(crt_bvh_uv) * n + 64 : 0);
+    DeviceTree out;
+    DeviceBuffer dBad(sizeof(int));
+    DeviceBuffer dBox(sizeof(Box6) * n), dCent(sizeof(float) * 3 * n), dBounds(sizeof(int) * 6);
+    DeviceBuffer dKeysIn(sizeof(unsigned long long) * n), dKeys(sizeof(unsigned long long) * n);
+    // the leaf-ordered records stay in HBM: whoever takes the tree copies them out only if someone asks
+    out.tris = DeviceBuffer(recordBytes(sizeof(crt_bvh_tri), n));
+    out.shade = DeviceBuffer(recordBytes(sizeof(crt_bvh_shade), n));
+    if (in.uvsIn) out.uvs = DeviceBuffer(recordBytes(sizeof(crt_bvh_uv), n));
     // scratch of the sort (digit counts per tile) and of the scan (tile sums); both written by this file's own kernels (gpu_sort.hip.h)
-    DevBuf dSortCounts(sizeof(uint32_t) * gpusort::sortScratchWords(n)), dScanSums(gpusort::scanScratchBytes(nInternal));
-    GPU_TRY(hipMemsetAsync(dBad.p, 0, sizeof(int), stream));
+    DeviceBuffer dSortCounts(sizeof(uint32_t) * gpusort::sortScratchWords(n)), dScanSums(gpusort::scanScratchBytes(nInternal));
+    HIP_THROW(hipMemsetAsync(dBad.as<>(), 0, sizeof(int), stream));
 
-    struct Events { // destroyed on every way out, exceptions included
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events()
-        {
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-        }
-    } ev;
-    GPU_TRY(hipEventCreate(&ev.e0));
-    GPU_TRY(hipEventCreate(&ev.e1));
-    hipEvent_t e0 = ev.e0, e1 = ev.e1;
-    GPU_TRY(hipEventRecord(e0, stream));
+    EventPair timer;
+    timer.start(stream);
     const dim3 blk(256), grdN((n + 255) / 256), grdI((nInternal + 255) / 256);
     hipLaunchKernelGGL(triBoxKernel, grdN, blk, 0, stream, table, n_meshes, in.xyz, in.idx, n, dBox.as<Box6>(), dCent.as<float>(), dBad.as<int>());
     hipLaunchKernelGGL(initBoundsKernel, dim3(1), dim3(64), 0, stream, dBounds.as<int>());
@@ -542,78 +463,118 @@ void buildFromDevice(const GpuMeshes& in, int builder, Bvh& out, ihipStream_t* s
     // keys = Morton code << 32 | ordinal, written in ordinal order: a stable sort on the four bytes of the high dword orders the full keys;
     // four passes ping-pong dKeys -> dKeysIn -> ... and end in dKeys
     hipLaunchKernelGGL(mortonKernel, grdN, blk, 0, stream, dCent.as<float>(), n, dBounds.as<int>(), dKeys.as<unsigned long long>());
-    GPU_TRY(hipGetLastError()); // triBox / bounds / Morton launches
+    HIP_THROW(hipGetLastError()); // triBox / bounds / Morton launches
     hipError_t sortStatus = hipSuccess;
     unsigned long long* sorted = gpusort::sortKeysHigh(dKeys.as<unsigned long long>(), dKeysIn.as<unsigned long long>(), n, 4, dSortCounts.as<uint32_t>(), stream, &sortStatus);
-    GPU_TRY(sortStatus);
+    HIP_THROW(sortStatus);
     if (sorted != dKeys.as<unsigned long long>()) throw std::logic_error("sorted keys expected in the first buffer");
-    void* binNodes = nullptr; // the binary tree in DFS pre-order, handed to `out` at the end
-    struct OwnedNodes { void*& p; ~OwnedNodes() { if (p) (void)hipFree(p); } } ownedNodes{ binNodes };
-    uint32_t nKept = 0;
+    uint32_t nKept = 0; // binary nodes, in DFS pre-order in out.nodes
     const unsigned long long* leafKeys = dKeys.as<unsigned long long>(); // leaf position -> key (gid in the low dword)
     if (builder == kGpuBuilderPloc) {
         int bad = 0;
-        GPU_TRY(hipMemcpyAsync(&bad, dBad.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-        GPU_TRY(hipStreamSynchronize(stream));
+        HIP_THROW(hipMemcpyAsync(&bad, dBad.as<>(), sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_THROW(hipStreamSynchronize(stream));
         if (bad) throw std::runtime_error("triangle index out of range");
-        nKept = plocBuildGpu(dKeys.as<unsigned long long>(), dBox.as<float>(), n, dKeysIn.as<unsigned long long>(), &binNodes, stream);
+        nKept = plocBuildGpu(dKeys.as<unsigned long long>(), dBox.as<float>(), n, dKeysIn.as<unsigned long long>(), out.nodes, stream);
         leafKeys = dKeysIn.as<unsigned long long>();
     } else {
-        DevBuf dK(sizeof(KNode) * nInternal), dParI(sizeof(int) * nInternal), dParL(sizeof(int) * n);
-        DevBuf dNodeBox(sizeof(Box6) * nInternal), dFlags(sizeof(unsigned int) * nInternal);
-        DevBuf dKept(sizeof(uint32_t) * nInternal), dRank(sizeof(uint32_t) * nInternal);
+        DeviceBuffer dK(sizeof(KNode) * nInternal), dParI(sizeof(int) * nInternal), dParL(sizeof(int) * n);
+        DeviceBuffer dNodeBox(sizeof(Box6) * nInternal), dFlags(sizeof(unsigned int) * nInternal);
+        DeviceBuffer dKept(sizeof(uint32_t) * nInternal), dRank(sizeof(uint32_t) * nInternal);
         hipLaunchKernelGGL(hierarchyKernel, grdI, blk, 0, stream, dKeys.as<unsigned long long>(), n, dK.as<KNode>(), dParI.as<int>(), dParL.as<int>());
-        GPU_TRY(hipMemsetAsync(dFlags.p, 0, sizeof(unsigned int) * nInternal, stream));
+        HIP_THROW(hipMemsetAsync(dFlags.as<>(), 0, sizeof(unsigned int) * nInternal, stream));
         hipLaunchKernelGGL(fitKernel, grdN, blk, 0, stream, dK.as<KNode>(), dBox.as<Box6>(), dKeys.as<unsigned long long>(), n, dParI.as<int>(),
                            dParL.as<int>(), dNodeBox.as<Box6>(), dFlags.as<unsigned int>());
         hipLaunchKernelGGL(keptKernel, grdI, blk, 0, stream, dK.as<KNode>(), nInternal, dKept.as<uint32_t>());
-        GPU_TRY(hipGetLastError()); // hierarchy / fit / kept launches
-        GPU_TRY(gpusort::exclusiveSum(dKept.as<uint32_t>(), dRank.as<uint32_t>(), nInternal, dScanSums.as<uint32_t>(), stream));
+        HIP_THROW(hipGetLastError()); // hierarchy / fit / kept launches
+        HIP_THROW(gpusort::exclusiveSum(dKept.as<uint32_t>(), dRank.as<uint32_t>(), nInternal, dScanSums.as<uint32_t>(), stream));
         uint32_t lastKept = 0, lastRank = 0;
         int bad = 0;
-        GPU_TRY(hipMemcpyAsync(&lastKept, dKept.as<uint32_t>() + (nInternal - 1), 4, hipMemcpyDeviceToHost, stream));
-        GPU_TRY(hipMemcpyAsync(&lastRank, dRank.as<uint32_t>() + (nInternal - 1), 4, hipMemcpyDeviceToHost, stream));
-        GPU_TRY(hipMemcpyAsync(&bad, dBad.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-        GPU_TRY(hipStreamSynchronize(stream));
+        HIP_THROW(hipMemcpyAsync(&lastKept, dKept.as<uint32_t>() + (nInternal - 1), 4, hipMemcpyDeviceToHost, stream));
+        HIP_THROW(hipMemcpyAsync(&lastRank, dRank.as<uint32_t>() + (nInternal - 1), 4, hipMemcpyDeviceToHost, stream));
+        HIP_THROW(hipMemcpyAsync(&bad, dBad.as<>(), sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_THROW(hipStreamSynchronize(stream));
         if (bad) throw std::runtime_error("triangle index out of range");
         nKept = lastKept + lastRank;
-        GPU_TRY(hipMalloc(&binNodes, sizeof(crt_bvh_node) * nKept));
+        out.nodes = DeviceBuffer(sizeof(crt_bvh_node) * nKept);
         hipLaunchKernelGGL(emitKernel, grdI, blk, 0, stream, dK.as<KNode>(), dKept.as<uint32_t>(), dRank.as<uint32_t>(), dNodeBox.as<Box6>(), dBox.as<Box6>(),
-                           dKeys.as<unsigned long long>(), nInternal, static_cast<crt_bvh_node*>(binNodes));
-        GPU_TRY(hipGetLastError());
-        GPU_TRY(hipStreamSynchronize(stream)); // the Karras scratch dies with this scope
+                           dKeys.as<unsigned long long>(), nInternal, out.nodes.as<crt_bvh_node>());
+        HIP_THROW(hipGetLastError());
+        HIP_THROW(hipStreamSynchronize(stream)); // the Karras scratch dies with this scope
     }
-    hipLaunchKernelGGL(gatherKernel, grdN, blk, 0, stream, leafKeys, n, table, n_meshes, in.xyz, in.idx, in.normals, in.uvsIn, dTris.as<crt_bvh_tri>(),
-                       dShade.as<crt_bvh_shade>(), in.uvsIn ? dUvs.as<crt_bvh_uv>() : nullptr);
-    GPU_TRY(hipGetLastError());
-    if (timing) { GPU_TRY(hipStreamSynchronize(stream)); }
+    hipLaunchKernelGGL(gatherKernel, grdN, blk, 0, stream, leafKeys, n, table, n_meshes, in.xyz, in.idx, in.normals, in.uvsIn, out.tris.as<crt_bvh_tri>(),
+                       out.shade.as<crt_bvh_shade>(), out.uvs.as<crt_bvh_uv>());
+    HIP_THROW(hipGetLastError());
+    if (timing) { HIP_THROW(hipStreamSynchronize(stream)); }
     lap("device build");
     // ---- collapse to the 4-wide tree and quantise, still on the device
-    DevBuf dScratch(collapseScratchBytes(nKept));
-    uint32_t nWide = 0, depth4 = 0, maxDepth = 0;
-    void* wide[2] = { nullptr, nullptr }; // allocated by the collapse at their exact size
-    struct Owned { void** p; ~Owned() { for (int i = 0; i < 2; i++) if (p[i]) (void)hipFree(p[i]); } } owned{ wide };
-    collapseWideGpu(static_cast<const crt_bvh_node*>(binNodes), nKept, dScratch.p, &wide[0], &wide[1], stream, &nWide, &depth4, &maxDepth);
-    GPU_TRY(hipEventRecord(e1, stream));
-    GPU_TRY(hipStreamSynchronize(stream));
-    float ms = 0.f;
-    GPU_TRY(hipEventElapsedTime(&ms, e0, e1));
+    DeviceBuffer dScratch(collapseScratchBytes(nKept));
+    out.nNodes = nKept;
+    out.nTris = n;
+    collapseWideGpu(out.nodes.as<crt_bvh_node>(), nKept, dScratch.as<>(), nullptr, nullptr, &out, stream, &out.nNodes4, &out.depth4, &out.maxDepth);
+    const double ms = timer.stopAndWait(stream);
     if (device_ms) *device_ms = ms;
     lap("device collapse + quantise");
-    out.maxDepth = maxDepth;
-    out.depth4 = depth4;
-    out.nNodes = nKept;
-    out.nNodes4 = nWide;
-    out.devNodes = binNodes;
-    binNodes = nullptr;
-    out.devNodes4 = wide[0];
-    out.devNodes4q = wide[1];
-    wide[0] = wide[1] = nullptr;
-    // the leaf-ordered records stay in HBM: the caller adopts the buffers (and copies them out only if someone asks)
+    return out;
+}
+
+// A handful of triangles (n <= kLeafMax): one leaf, wrapped in a node whose right child is an empty leaf with the same box (as the
+// SAH path does); nothing worth a kernel launch -- the host does it with the same rules, in the leaf order the device path would
+// give: by Morton key.  The tree stays on the host (out.dev empty); whoever needs it in HBM uploads it (uploadTree).
+void buildOneLeaf(const crt_mesh_view* meshes, uint32_t n_meshes, uint32_t n, Bvh& out)
+{
+    std::vector<crt_bvh_tri> inTri;
+    std::vector<crt_bvh_shade> inShade;
+    std::vector<float> pboxCent; // per triangle: 6 floats box + 3 floats centroid
+    flattenMeshes(meshes, n_meshes, inTri, inShade, pboxCent);
+    std::vector<crt_bvh_uv> inUv;
+    flattenUvs(meshes, n_meshes, inUv);
+    auto boxOf = [&](uint32_t i) {
+        Box6 b;
+        std::memcpy(&b, &pboxCent[9 * static_cast<size_t>(i)], sizeof(Box6));
+        return b;
+    };
+    auto centOf = [&](uint32_t i, int a) { return pboxCent[9 * static_cast<size_t>(i) + 6 + a]; };
+    Box6 root = boxOf(0), cb; // cb: the centroids' bounds
+    for (int a = 0; a < 3; a++) cb.mn[a] = cb.mx[a] = centOf(0, a);
+    for (uint32_t i = 1; i < n; i++) {
+        root = unionBox(root, boxOf(i));
+        for (int a = 0; a < 3; a++) {
+            cb.mn[a] = minSel(cb.mn[a], centOf(i, a));
+            cb.mx[a] = maxSel(cb.mx[a], centOf(i, a));
+        }
+    }
+    crt_bvh_node N;
+    N.lx0 = N.rx0 = root.mn[0]; N.lx1 = N.rx1 = root.mx[0]; N.ly0 = N.ry0 = root.mn[1]; N.ly1 = N.ry1 = root.mx[1];
+    N.lz0 = N.rz0 = root.mn[2]; N.lz1 = N.rz1 = root.mx[2];
+    N.left = leafRef(0u, n);
+    N.right = leafRef(0u, 0u);
+    N.pad0 = N.pad1 = 0;
+    out.nodes.push_back(N);
+    float extm = 0.0f;
+    for (int a = 0; a < 3; a++) {
+        const float ext = cb.mx[a] - cb.mn[a];
+        if (ext > extm) extm = ext;
+    }
+    const float scale = mortonScale(extm);
+    std::vector<unsigned long long> keys(n);
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t q[3];
+        for (int a = 0; a < 3; a++) q[a] = quant10((centOf(i, a) - cb.mn[a]) * scale);
+        const uint32_t code = (expandBits10(q[0]) << 2) | (expandBits10(q[1]) << 1) | expandBits10(q[2]); // as mortonKernel
+        keys[i] = (static_cast<unsigned long long>(code) << 32) | i;
+    }
+    std::sort(keys.begin(), keys.end());
+    out.tris.resize(n);
+    out.shade.resize(n);
+    for (uint32_t i = 0; i < n; i++) {
+        out.tris[i] = inTri[keys[i] & 0xFFFFFFFFull];
+        out.shade[i] = inShade[keys[i] & 0xFFFFFFFFull];
+    }
     out.nTris = n;
-    out.devTris = dTris.release();
-    out.devShade = dShade.release();
-    out.devUvs = in.uvsIn ? dUvs.release() : nullptr;
+    out.maxDepth = 1;
+    collapseBvh4(out);
+    reorderUvs(inUv, out);
 }
 
 } // namespace
@@ -646,124 +607,76 @@ void buildBvhGpu(const crt_mesh_view* meshes, uint32_t n_meshes, Bvh& out, ihipS
     const uint32_t n = static_cast<uint32_t>(total);
     if (n == 0) return;
 
-    if (n <= static_cast<uint32_t>(kLeafMax)) {
-        // a handful of triangles: one leaf, wrapped in a node whose right child is an empty leaf with the same box (as the SAH
-        // path does); nothing worth a kernel launch -- the host does it with the same rules
-        std::vector<crt_bvh_tri> inTri;
-        std::vector<crt_bvh_shade> inShade;
-        std::vector<float> pboxCent; // per triangle: 6 floats box + 3 floats centroid
-        flattenMeshes(meshes, n_meshes, inTri, inShade, pboxCent);
-        std::vector<crt_bvh_uv> inUv;
-        flattenUvs(meshes, n_meshes, inUv);
-        std::vector<Box6> hBox(n);
-        std::vector<float> hCent(3 * static_cast<size_t>(n));
-        for (uint32_t i = 0; i < n; i++) {
-            std::memcpy(&hBox[i], &pboxCent[9 * static_cast<size_t>(i)], sizeof(Box6));
-            std::memcpy(&hCent[3 * static_cast<size_t>(i)], &pboxCent[9 * static_cast<size_t>(i) + 6], 3 * sizeof(float));
-        }
-        out.tris.resize(n);
-        out.shade.resize(n);
-        Box6 root = hBox[0];
-        for (uint32_t i = 1; i < n; i++)
-            for (int a = 0; a < 3; a++) {
-                root.mn[a] = root.mn[a] < hBox[i].mn[a] ? root.mn[a] : hBox[i].mn[a];
-                root.mx[a] = root.mx[a] > hBox[i].mx[a] ? root.mx[a] : hBox[i].mx[a];
-            }
-        crt_bvh_node N;
-        N.lx0 = N.rx0 = root.mn[0]; N.lx1 = N.rx1 = root.mx[0]; N.ly0 = N.ry0 = root.mn[1]; N.ly1 = N.ry1 = root.mx[1];
-        N.lz0 = N.rz0 = root.mn[2]; N.lz1 = N.rz1 = root.mx[2];
-        N.left = ~static_cast<int32_t>((0u << 3) | n);
-        N.right = ~static_cast<int32_t>(0);
-        N.pad0 = N.pad1 = 0;
-        out.nodes.push_back(N);
-        std::vector<unsigned long long> keys(n);
-        float lo[3], hi[3];
-        for (int a = 0; a < 3; a++) { lo[a] = hCent[a]; hi[a] = hCent[a]; }
-        for (uint32_t i = 1; i < n; i++)
-            for (int a = 0; a < 3; a++) {
-                const float c = hCent[3 * i + a];
-                lo[a] = lo[a] < c ? lo[a] : c;
-                hi[a] = hi[a] > c ? hi[a] : c;
-            }
-        auto expand = [](uint32_t v) { v = (v * 0x00010001u) & 0xFF0000FFu; v = (v * 0x00000101u) & 0x0F00F00Fu; v = (v * 0x00000011u) & 0xC30C30C3u; v = (v * 0x00000005u) & 0x49249249u; return v; };
-        for (uint32_t i = 0; i < n; i++) {
-            uint32_t q[3];
-            float extm = 0.0f;
-            for (int a = 0; a < 3; a++) {
-                const float ext = hi[a] - lo[a];
-                if (ext > extm) extm = ext;
-            }
-            const float scale = extm > 0.0f ? 1024.0f / extm : 0.0f;
-            for (int a = 0; a < 3; a++) {
-                const float f = (hCent[3 * i + a] - lo[a]) * scale;
-                q[a] = f >= 0.0f ? (f < 1024.0f ? static_cast<uint32_t>(f) : 1023u) : 0u;
-            }
-            keys[i] = (static_cast<unsigned long long>((expand(q[0]) << 2) | (expand(q[1]) << 1) | expand(q[2])) << 32) | i;
-        }
-        std::sort(keys.begin(), keys.end());
-        for (uint32_t i = 0; i < n; i++) {
-            out.tris[i] = inTri[keys[i] & 0xFFFFFFFFull];
-            out.shade[i] = inShade[keys[i] & 0xFFFFFFFFull];
-        }
-        out.nTris = n;
-        out.maxDepth = 1;
-        collapseBvh4(out);
-        reorderUvs(inUv, out);
-        return;
-    }
+    if (n <= static_cast<uint32_t>(kLeafMax)) return buildOneLeaf(meshes, n_meshes, n, out);
 
     // ---- the meshes as they are, back to back
-    std::vector<MeshEntry> table(n_meshes + 1u);
+    const std::vector<MeshEntry> table = makeMeshTable(meshes, n_meshes);
     std::vector<float> hXyz(3 * static_cast<size_t>(totalVerts)), hNormals, hUvs;
     std::vector<uint32_t> hIdx(3 * static_cast<size_t>(n));
     if (anyNormals) hNormals.assign(3 * static_cast<size_t>(totalVerts), 0.0f);
     if (anyUvs) hUvs.assign(3 * static_cast<size_t>(totalVerts), 0.0f);
-    {
-        uint32_t t0 = 0, v0 = 0;
-        for (uint32_t m = 0; m < n_meshes; m++) {
-            const crt_mesh_view& M = meshes[m];
-            MeshEntry& E = table[m];
-            E.triStart = t0; E.vertStart = v0; E.nVerts = M.n_vertices; E.material = static_cast<uint32_t>(M.material_index);
-            E.hasNormals = M.normals ? 1u : 0u; E.hasUvs = M.uvs ? 1u : 0u; E.pad0 = E.pad1 = 0;
-            if (M.n_vertices && M.xyz) std::memcpy(&hXyz[3 * static_cast<size_t>(v0)], M.xyz, sizeof(float) * 3 * M.n_vertices); // (a mesh without triangles may come without arrays)
-            if (M.n_triangles && M.idx) std::memcpy(&hIdx[3 * static_cast<size_t>(t0)], M.idx, sizeof(uint32_t) * 3 * static_cast<size_t>(M.n_triangles));
-            if (M.normals && M.n_vertices) std::memcpy(&hNormals[3 * static_cast<size_t>(v0)], M.normals, sizeof(float) * 3 * M.n_vertices);
-            if (M.uvs && M.n_vertices) std::memcpy(&hUvs[3 * static_cast<size_t>(v0)], M.uvs, sizeof(float) * 3 * M.n_vertices);
-            t0 += M.n_triangles;
-            v0 += M.n_vertices;
-        }
-        MeshEntry& E = table[n_meshes];
-        E.triStart = t0; E.vertStart = v0; E.nVerts = 0; E.material = 0; E.hasNormals = E.hasUvs = E.pad0 = E.pad1 = 0;
+    for (uint32_t m = 0; m < n_meshes; m++) {
+        const crt_mesh_view& M = meshes[m];
+        const size_t t0 = table[m].triStart, v0 = table[m].vertStart;
+        if (M.n_vertices && M.xyz) std::memcpy(&hXyz[3 * v0], M.xyz, sizeof(float) * 3 * M.n_vertices); // (a mesh without triangles may come without arrays)
+        if (M.n_triangles && M.idx) std::memcpy(&hIdx[3 * t0], M.idx, sizeof(uint32_t) * 3 * static_cast<size_t>(M.n_triangles));
+        if (M.normals && M.n_vertices) std::memcpy(&hNormals[3 * v0], M.normals, sizeof(float) * 3 * M.n_vertices);
+        if (M.uvs && M.n_vertices) std::memcpy(&hUvs[3 * v0], M.uvs, sizeof(float) * 3 * M.n_vertices);
     }
     lap("host concatenate");
 
-    DevBuf dTable(sizeof(MeshEntry) * table.size()), dXyz(sizeof(float) * hXyz.size()), dIdx(sizeof(uint32_t) * hIdx.size());
-    DevBuf dNormals(sizeof(float) * hNormals.size()), dUvsIn(sizeof(float) * hUvs.size());
-    GPU_TRY(hipMemcpyAsync(dTable.p, table.data(), sizeof(MeshEntry) * table.size(), hipMemcpyHostToDevice, stream));
-    GPU_TRY(hipMemcpyAsync(dXyz.p, hXyz.data(), sizeof(float) * hXyz.size(), hipMemcpyHostToDevice, stream));
-    GPU_TRY(hipMemcpyAsync(dIdx.p, hIdx.data(), sizeof(uint32_t) * hIdx.size(), hipMemcpyHostToDevice, stream));
-    if (anyNormals) GPU_TRY(hipMemcpyAsync(dNormals.p, hNormals.data(), sizeof(float) * hNormals.size(), hipMemcpyHostToDevice, stream));
-    if (anyUvs) GPU_TRY(hipMemcpyAsync(dUvsIn.p, hUvs.data(), sizeof(float) * hUvs.size(), hipMemcpyHostToDevice, stream));
-    if (timing) { GPU_TRY(hipStreamSynchronize(stream)); }
+    DeviceBuffer dTable(sizeof(MeshEntry) * table.size()), dXyz(sizeof(float) * hXyz.size()), dIdx(sizeof(uint32_t) * hIdx.size());
+    DeviceBuffer dNormals(sizeof(float) * hNormals.size()), dUvsIn(sizeof(float) * hUvs.size());
+    HIP_THROW(hipMemcpyAsync(dTable.as<>(), table.data(), sizeof(MeshEntry) * table.size(), hipMemcpyHostToDevice, stream));
+    HIP_THROW(hipMemcpyAsync(dXyz.as<>(), hXyz.data(), sizeof(float) * hXyz.size(), hipMemcpyHostToDevice, stream));
+    HIP_THROW(hipMemcpyAsync(dIdx.as<>(), hIdx.data(), sizeof(uint32_t) * hIdx.size(), hipMemcpyHostToDevice, stream));
+    if (anyNormals) HIP_THROW(hipMemcpyAsync(dNormals.as<>(), hNormals.data(), sizeof(float) * hNormals.size(), hipMemcpyHostToDevice, stream));
+    if (anyUvs) HIP_THROW(hipMemcpyAsync(dUvsIn.as<>(), hUvs.data(), sizeof(float) * hUvs.size(), hipMemcpyHostToDevice, stream));
+    if (timing) { HIP_THROW(hipStreamSynchronize(stream)); }
     lap("alloc + H2D meshes");
     GpuMeshes in;
-    in.table = dTable.p;
+    in.table = dTable.as<>();
     in.nMeshes = n_meshes;
     in.n = n;
     in.xyz = dXyz.as<float>();
     in.idx = dIdx.as<uint32_t>();
     in.normals = dNormals.as<float>();
     in.uvsIn = anyUvs ? dUvsIn.as<float>() : nullptr;
-    buildFromDevice(in, builder, out, stream, device_ms, lap);
+    out.dev = buildFromDevice(in, builder, stream, device_ms, lap);
+    out.nTris = out.dev.nTris;
+    out.depth4 = out.dev.depth4;
+    out.maxDepth = out.dev.maxDepth;
 }
 
-void rebuildBvhGpu(const GpuMeshes& in, int builder, Bvh& out, ihipStream_t* stream, double* device_ms)
+DeviceTree rebuildBvhGpu(const GpuMeshes& in, int builder, ihipStream_t* stream, double* device_ms)
 {
     if (builder != kGpuBuilderLbvh && builder != kGpuBuilderPloc) throw std::runtime_error("unknown GPU builder");
     if (in.n <= static_cast<uint32_t>(kLeafMax)) throw std::logic_error("rebuildBvhGpu: more than kLeafMax triangles expected");
-    out = Bvh();
     if (device_ms) *device_ms = 0.0;
-    buildFromDevice(in, builder, out, stream, device_ms, [](const char*) {});
+    return buildFromDevice(in, builder, stream, device_ms, [](const char*) {});
+}
+
+DeviceTree uploadTree(const Bvh& host, bool withBinaryAndWide)
+{
+    DeviceTree t;
+    auto put = [](DeviceBuffer& b, const auto& v, size_t room) { // (synchronous copies: the host arrays may die after this call)
+        b = DeviceBuffer(room);
+        if (!v.empty()) HIP_THROW(hipMemcpy(b.as<>(), v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice));
+    };
+    if (withBinaryAndWide) {
+        put(t.nodes, host.nodes, sizeof(crt_bvh_node) * host.nodes.size());
+        put(t.nodes4, host.nodes4, sizeof(crt_bvh_node4) * host.nodes4.size());
+    }
+    put(t.nodes4q, host.nodes4q, quantisedBytes(host.nodes4q.size()));
+    put(t.tris, host.tris, recordBytes(sizeof(crt_bvh_tri), host.tris.size()));
+    put(t.shade, host.shade, recordBytes(sizeof(crt_bvh_shade), host.shade.size()));
+    if (!host.uvs.empty()) put(t.uvs, host.uvs, recordBytes(sizeof(crt_bvh_uv), host.uvs.size()));
+    t.nNodes = static_cast<uint32_t>(host.nodes.size());
+    t.nNodes4 = static_cast<uint32_t>(host.nodes4.size());
+    t.nTris = host.nTris;
+    t.depth4 = host.depth4;
+    t.maxDepth = host.maxDepth;
+    return t;
 }
 
 int deviceExclusiveSum(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* tileSums, ihipStream_t* stream)

@@ -20,29 +20,24 @@
 //              give at most 26 levels, so every leaf sits at depth <= 32.  Only a tree whose root is taller than kMaxDepth
 //              takes this path (two more passes over the iterations and one launch for the balanced subtrees).
 #include "bvh_build.h"
+#include "hip_own.h"
+#include "tri_geometry.hip.h"
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace crt {
 namespace {
 
-#define PLOC_TRY(expr)                                                                                         \
-    do {                                                                                                       \
-        hipError_t e_ = (expr);                                                                                \
-        if (e_ != hipSuccess) throw std::runtime_error(std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-    } while (0)
-
 constexpr int kRadius = 16;            // neighbour search window: [i - kRadius, i + kRadius]
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kRuleDepth = 6;     // where the depth rule cuts
 constexpr uint32_t kRuleHeight = static_cast<uint32_t>(kMaxDepth) - kRuleDepth;
-
-struct Box6 { float mn[3], mx[3]; };
 
 struct PNode {           // a cluster: ids < n are the triangles (by sorted position), n.. the merged nodes in creation order
     Box6 box;
@@ -59,26 +54,11 @@ struct TopDown { uint32_t first, depth, id, state; }; // state 0: inside a leaf 
 
 struct Balanced { uint32_t id, first, count, pad; };
 
-__device__ __forceinline__ float minSel(float a, float b) { return a < b ? a : b; }
-__device__ __forceinline__ float maxSel(float a, float b) { return a > b ? a : b; }
-
-__device__ __forceinline__ Box6 unionBox(const Box6& a, const Box6& b)
-{
-    Box6 u;
-    for (int k = 0; k < 3; k++) {
-        u.mn[k] = minSel(a.mn[k], b.mn[k]);
-        u.mx[k] = maxSel(a.mx[k], b.mx[k]);
-    }
-    return u;
-}
-
 __device__ __forceinline__ float halfArea(const Box6& b)
 {
     const float dx = b.mx[0] - b.mn[0], dy = b.mx[1] - b.mn[1], dz = b.mx[2] - b.mn[2];
     return (dx * dy + dy * dz) + dz * dx;
 }
-
-__device__ __forceinline__ int32_t leafRef(uint32_t first, uint32_t count) { return ~static_cast<int32_t>((first << 3) | count); }
 
 // inner nodes of the balanced tree over c triangles: level k holds 2^k ranges of floor(c / 2^k) or ceil(c / 2^k) triangles,
 // c mod 2^k of them the larger; a range of more than kLeafMax is an inner node (and so are all its ancestors)
@@ -317,31 +297,22 @@ __global__ __launch_bounds__(kBlock) void plocBalancedKernel(const Balanced* __r
     }
 }
 
-struct Buf {
-    void* p = nullptr;
-    explicit Buf(size_t bytes) { PLOC_TRY(hipMalloc(&p, bytes ? bytes : 16)); }
-    ~Buf() { if (p) (void)hipFree(p); }
-    Buf(const Buf&) = delete;
-    Buf& operator=(const Buf&) = delete;
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
 inline dim3 grid(uint32_t count) { return dim3((count + kBlock - 1u) / kBlock); }
 
 } // namespace
 
-uint32_t plocBuildGpu(const unsigned long long* sortedKeys, const float* triBoxes, uint32_t n, unsigned long long* leafKeys, void** nodesOut,
+uint32_t plocBuildGpu(const unsigned long long* sortedKeys, const float* triBoxes, uint32_t n, unsigned long long* leafKeys, DeviceBuffer& nodesOut,
                       ihipStream_t* stream)
 {
     static_assert(sizeof(Box6) == 24 && sizeof(PNode) == 56 && sizeof(TopDown) == 16, "record layout");
     if (n < 2u) throw std::logic_error("plocBuildGpu: at least two triangles");
     const Box6* triBox = reinterpret_cast<const Box6*>(triBoxes);
     const uint32_t nAll = 2u * n - 1u;
-    Buf dNodes(sizeof(PNode) * nAll), dTd(sizeof(TopDown) * nAll), dBal(sizeof(uint32_t) * nAll);
-    Buf dIdsA(sizeof(uint32_t) * n), dIdsB(sizeof(uint32_t) * n), dBoxA(sizeof(Box6) * n), dBoxB(sizeof(Box6) * n);
-    Buf dNn(sizeof(uint32_t) * n), dKeep(sizeof(uint32_t) * n), dKeepRank(sizeof(uint32_t) * n), dMerge(sizeof(uint32_t) * n),
-        dMergeRank(sizeof(uint32_t) * n);
-    Buf dScan(deviceScanScratchBytes(n)), dTotals(sizeof(uint32_t) * 4), dTriPos(sizeof(uint32_t) * n);
+    DeviceBuffer dNodes(sizeof(PNode) * nAll), dTd(sizeof(TopDown) * nAll), dBal(sizeof(uint32_t) * nAll);
+    DeviceBuffer dIdsA(sizeof(uint32_t) * n), dIdsB(sizeof(uint32_t) * n), dBoxA(sizeof(Box6) * n), dBoxB(sizeof(Box6) * n);
+    DeviceBuffer dNn(sizeof(uint32_t) * n), dKeep(sizeof(uint32_t) * n), dKeepRank(sizeof(uint32_t) * n), dMerge(sizeof(uint32_t) * n),
+                 dMergeRank(sizeof(uint32_t) * n);
+    DeviceBuffer dScan(deviceScanScratchBytes(n)), dTotals(sizeof(uint32_t) * 4), dTriPos(sizeof(uint32_t) * n);
     PNode* nodes = dNodes.as<PNode>();
     uint32_t* ids = dIdsA.as<uint32_t>();
     uint32_t* idsNext = dIdsB.as<uint32_t>();
@@ -350,25 +321,25 @@ uint32_t plocBuildGpu(const unsigned long long* sortedKeys, const float* triBoxe
     uint32_t* totals = dTotals.as<uint32_t>();
 
     hipLaunchKernelGGL(plocInitKernel, grid(n), dim3(kBlock), 0, stream, sortedKeys, triBox, n, nodes, ids, cbox);
-    PLOC_TRY(hipGetLastError());
+    HIP_THROW(hipGetLastError());
     // clustering: one pass per iteration; the next iteration's size comes back to the host
     std::vector<std::pair<uint32_t, uint32_t>> iters; // {first node id, nodes created}
     uint32_t m = n, created = 0;
     while (m > 1u) {
         hipLaunchKernelGGL(plocNeighbourKernel, grid(m), dim3(kBlock), 0, stream, cbox, m, dNn.as<uint32_t>());
         hipLaunchKernelGGL(plocFlagsKernel, grid(m), dim3(kBlock), 0, stream, dNn.as<uint32_t>(), m, dKeep.as<uint32_t>(), dMerge.as<uint32_t>());
-        PLOC_TRY(hipGetLastError());
-        PLOC_TRY(static_cast<hipError_t>(deviceExclusiveSum(dKeep.as<uint32_t>(), dKeepRank.as<uint32_t>(), m, dScan.as<uint32_t>(), stream)));
-        PLOC_TRY(static_cast<hipError_t>(deviceExclusiveSum(dMerge.as<uint32_t>(), dMergeRank.as<uint32_t>(), m, dScan.as<uint32_t>(), stream)));
+        HIP_THROW(hipGetLastError());
+        HIP_THROW(static_cast<hipError_t>(deviceExclusiveSum(dKeep.as<uint32_t>(), dKeepRank.as<uint32_t>(), m, dScan.as<uint32_t>(), stream)));
+        HIP_THROW(static_cast<hipError_t>(deviceExclusiveSum(dMerge.as<uint32_t>(), dMergeRank.as<uint32_t>(), m, dScan.as<uint32_t>(), stream)));
         const uint32_t nodeBase = n + created;
         hipLaunchKernelGGL(plocMergeKernel, grid(m), dim3(kBlock), 0, stream, ids, cbox, dNn.as<uint32_t>(), dKeep.as<uint32_t>(),
                            dKeepRank.as<uint32_t>(), dMerge.as<uint32_t>(), dMergeRank.as<uint32_t>(), m, nodeBase, nodes, idsNext, cboxNext);
         hipLaunchKernelGGL(plocTotalsKernel, dim3(1), dim3(64), 0, stream, dKeep.as<uint32_t>(), dKeepRank.as<uint32_t>(), dMerge.as<uint32_t>(),
                            dMergeRank.as<uint32_t>(), m, totals);
-        PLOC_TRY(hipGetLastError());
+        HIP_THROW(hipGetLastError());
         uint32_t h[2] = { 0, 0 };
-        PLOC_TRY(hipMemcpyAsync(h, totals, sizeof(h), hipMemcpyDeviceToHost, stream));
-        PLOC_TRY(hipStreamSynchronize(stream));
+        HIP_THROW(hipMemcpyAsync(h, totals, sizeof(h), hipMemcpyDeviceToHost, stream));
+        HIP_THROW(hipStreamSynchronize(stream));
         if (h[1] == 0u || h[0] + h[1] != m || created + h[1] > n - 1u) throw std::runtime_error("PLOC: no mutual neighbours (non-finite triangle boxes?)");
         iters.emplace_back(nodeBase, h[1]);
         created += h[1];
@@ -378,51 +349,48 @@ uint32_t plocBuildGpu(const unsigned long long* sortedKeys, const float* triBoxe
     }
     const uint32_t root = n + created - 1u; // = 2n - 2
     PNode rootNode;
-    PLOC_TRY(hipMemcpyAsync(&rootNode, nodes + root, sizeof(PNode), hipMemcpyDeviceToHost, stream));
-    PLOC_TRY(hipMemsetAsync(dBal.p, 0, sizeof(uint32_t) * nAll, stream));
+    HIP_THROW(hipMemcpyAsync(&rootNode, nodes + root, sizeof(PNode), hipMemcpyDeviceToHost, stream));
+    HIP_THROW(hipMemsetAsync(dBal.as<>(), 0, sizeof(uint32_t) * nAll, stream));
     const TopDown rootTd = { 0u, 0u, 0u, 1u };
-    PLOC_TRY(hipMemcpyAsync(dTd.as<TopDown>() + root, &rootTd, sizeof(rootTd), hipMemcpyHostToDevice, stream));
-    PLOC_TRY(hipStreamSynchronize(stream)); // (rootTd, rootNode)
+    HIP_THROW(hipMemcpyAsync(dTd.as<TopDown>() + root, &rootTd, sizeof(rootTd), hipMemcpyHostToDevice, stream));
+    HIP_THROW(hipStreamSynchronize(stream)); // (rootTd, rootNode)
     const bool tooDeep = rootNode.height > static_cast<uint32_t>(kMaxDepth);
-    Buf dBalList(tooDeep ? sizeof(Balanced) * (1u << kRuleDepth) : 0), dBalCount(sizeof(uint32_t));
-    PLOC_TRY(hipMemsetAsync(dBalCount.p, 0, sizeof(uint32_t), stream));
+    DeviceBuffer dBalList(tooDeep ? sizeof(Balanced) * (1u << kRuleDepth) : 0), dBalCount(sizeof(uint32_t));
+    HIP_THROW(hipMemsetAsync(dBalCount.as<>(), 0, sizeof(uint32_t), stream));
     if (tooDeep) {
         for (size_t k = iters.size(); k-- > 0;)
             hipLaunchKernelGGL(plocTopDownKernel, grid(iters[k].second), dim3(kBlock), 0, stream, nodes, n, iters[k].first, iters[k].second,
                                dTd.as<TopDown>(), dBal.as<uint32_t>(), 0, nullptr, dTriPos.as<uint32_t>(), nullptr, nullptr);
         for (size_t k = 0; k < iters.size(); k++)
             hipLaunchKernelGGL(plocSizeKernel, grid(iters[k].second), dim3(kBlock), 0, stream, nodes, iters[k].first, iters[k].second, dBal.as<uint32_t>());
-        PLOC_TRY(hipGetLastError());
-        PLOC_TRY(hipMemcpyAsync(&rootNode, nodes + root, sizeof(PNode), hipMemcpyDeviceToHost, stream));
-        PLOC_TRY(hipStreamSynchronize(stream));
+        HIP_THROW(hipGetLastError());
+        HIP_THROW(hipMemcpyAsync(&rootNode, nodes + root, sizeof(PNode), hipMemcpyDeviceToHost, stream));
+        HIP_THROW(hipStreamSynchronize(stream));
     }
     const uint32_t nBinary = rootNode.size;
-    void* out = nullptr;
-    PLOC_TRY(hipMalloc(&out, sizeof(crt_bvh_node) * nBinary));
-    struct Owned { void*& p; ~Owned() { if (p) (void)hipFree(p); } } owned{ out }; // handed over at the end
+    DeviceBuffer dOut(sizeof(crt_bvh_node) * nBinary); // handed over at the end
+    crt_bvh_node* out = dOut.as<crt_bvh_node>();
     for (size_t k = iters.size(); k-- > 0;)
         hipLaunchKernelGGL(plocTopDownKernel, grid(iters[k].second), dim3(kBlock), 0, stream, nodes, n, iters[k].first, iters[k].second,
-                           dTd.as<TopDown>(), dBal.as<uint32_t>(), 1, static_cast<crt_bvh_node*>(out), dTriPos.as<uint32_t>(),
+                           dTd.as<TopDown>(), dBal.as<uint32_t>(), 1, out, dTriPos.as<uint32_t>(),
                            dBalList.as<Balanced>(), dBalCount.as<uint32_t>());
-    PLOC_TRY(hipGetLastError());
-    Buf dLeafBox(tooDeep ? sizeof(Box6) * n : 0);
+    HIP_THROW(hipGetLastError());
+    DeviceBuffer dLeafBox(tooDeep ? sizeof(Box6) * n : 0);
     hipLaunchKernelGGL(plocPermuteKernel, grid(n), dim3(kBlock), 0, stream, sortedKeys, dTriPos.as<uint32_t>(), n, leafKeys, triBox,
                        tooDeep ? dLeafBox.as<Box6>() : nullptr);
-    PLOC_TRY(hipGetLastError());
+    HIP_THROW(hipGetLastError());
     if (tooDeep) {
         uint32_t nBal = 0;
-        PLOC_TRY(hipMemcpyAsync(&nBal, dBalCount.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        PLOC_TRY(hipStreamSynchronize(stream));
+        HIP_THROW(hipMemcpyAsync(&nBal, dBalCount.as<>(), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_THROW(hipStreamSynchronize(stream));
         if (nBal > (1u << kRuleDepth)) throw std::logic_error("PLOC: more balanced subtrees than nodes at the rule's depth");
         if (nBal) {
-            hipLaunchKernelGGL(plocBalancedKernel, dim3(nBal), dim3(kBlock), 0, stream, dBalList.as<Balanced>(), dLeafBox.as<Box6>(),
-                               static_cast<crt_bvh_node*>(out));
-            PLOC_TRY(hipGetLastError());
+            hipLaunchKernelGGL(plocBalancedKernel, dim3(nBal), dim3(kBlock), 0, stream, dBalList.as<Balanced>(), dLeafBox.as<Box6>(), out);
+            HIP_THROW(hipGetLastError());
         }
     }
-    PLOC_TRY(hipStreamSynchronize(stream)); // the scratch above dies with this call
-    *nodesOut = out;
-    out = nullptr;
+    HIP_THROW(hipStreamSynchronize(stream)); // the scratch above dies with this call
+    nodesOut = std::move(dOut);
     return nBinary;
 }
 

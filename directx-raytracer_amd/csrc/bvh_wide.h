@@ -17,6 +17,9 @@
 
 namespace crt {
 
+// the reference a node holds for a leaf of `count` triangles (<= 7) starting at leaf position `first`
+CRT_HD inline int32_t leafRef(uint32_t first, uint32_t count) { return ~static_cast<int32_t>((first << 3) | count); }
+
 struct WideSlot {
     int32_t ref;      // binary node index (>= 0) or leaf reference (< 0)
     float mn[3], mx[3];

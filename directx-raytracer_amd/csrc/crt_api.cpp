@@ -302,7 +302,7 @@ void dropOrders(crt_ctx* c)
 int readSceneBox(crt_ctx* c)
 {
     for (int a = 0; a < 3; a++) c->sceneLo[a] = c->sceneHi[a] = 0.0f;
-    if (c->bvh.nNodes4 > 0) {
+    if (c->bvh.dev.nNodes4 > 0) {
         crt_bvh_node4q root;
         HIP_TRY(c, hipMemcpy(&root, c->dNodes, sizeof(root), hipMemcpyDeviceToHost));
         for (int a = 0; a < 3; a++) {
@@ -442,29 +442,47 @@ int stageEnd(crt_ctx* c, const StagePlane* planes, int n, void* const* dev)
     return CRT_OK;
 }
 
-// Upload with option "dynamic": the binary tree goes to (or stays in) HBM, the wide tree, its quantised form and the plane table get
-// room for one node per binary inner node (a refit may collapse to more wide nodes than the build did), and the meshes are kept.
+// The context takes a tree in HBM over: its buffers replace the context's (c->bvh.dev keeps the counts and no buffer), the plane
+// table of the old tree goes.
+static void adoptTree(crt_ctx* c, crt::DeviceTree&& t)
+{
+    void** olds[] = { &c->dBinNodes, &c->dWideNodes, &c->dNodes, &c->dPlanes, &c->dTris, &c->dShade, &c->dUvs };
+    for (void** q : olds) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    c->dBinNodes = t.nodes.release();
+    c->dWideNodes = t.nodes4.release();
+    c->dNodes = t.nodes4q.release();
+    c->dTris = t.tris.release();
+    c->dShade = t.shade.release();
+    c->dUvs = t.uvs.release();
+    c->bvh.depth4 = t.depth4;
+    c->bvh.maxDepth = t.maxDepth;
+    c->bvh.nTris = t.nTris;
+    c->bvh.dev = std::move(t);
+}
+
+// The wide tree, its quantised form and the plane table get room for one node per binary inner node: a refit may collapse to more
+// wide nodes than the build did.  What they hold stays (a plane table that does not exist yet is only allocated).
+static int reserveRefitCapacity(crt_ctx* c)
+{
+    const uint32_t cap = c->bvh.dev.nNodes ? c->bvh.dev.nNodes : 1u, n4 = c->bvh.dev.nNodes4;
+    if (int rc = regrow(c, c->dWideNodes, sizeof(crt_bvh_node4) * n4, sizeof(crt_bvh_node4) * cap)) return rc;
+    if (int rc = regrow(c, c->dNodes, sizeof(crt_bvh_node4q) * n4, crt::quantisedBytes(cap))) return rc;
+    return regrow(c, c->dPlanes, c->dPlanes ? sizeof(float) * crt::kPlaneStride * n4 : 0, sizeof(float) * crt::kPlaneStride * cap);
+}
+
+// Upload with option "dynamic": the binary and the wide tree are in HBM by now (built there, or uploaded with the rest); they get
+// their refit capacity and the meshes are kept.
 int setupDynamic(crt_ctx* c, const crt_mesh_view* meshes, uint32_t n_meshes)
 {
-    const uint32_t nBin = c->bvh.nNodes, cap = nBin ? nBin : 1u, n4 = c->bvh.nNodes4;
-    const bool hostTree = !c->dBinNodes;
-    if (hostTree) {
-        HIP_TRY(c, hipMalloc(&c->dBinNodes, sizeof(crt_bvh_node) * cap));
-        if (nBin) HIP_TRY(c, hipMemcpy(c->dBinNodes, c->bvh.nodes.data(), sizeof(crt_bvh_node) * nBin, hipMemcpyHostToDevice));
-    }
-    if (!c->dWideNodes) {
-        HIP_TRY(c, hipMalloc(&c->dWideNodes, sizeof(crt_bvh_node4) * cap));
-        if (n4) HIP_TRY(c, hipMemcpy(c->dWideNodes, c->bvh.nodes4.data(), sizeof(crt_bvh_node4) * n4, hipMemcpyHostToDevice));
-    } else if (int rc = regrow(c, c->dWideNodes, sizeof(crt_bvh_node4) * n4, sizeof(crt_bvh_node4) * cap)) {
-        return rc;
-    }
-    if (int rc = regrow(c, c->dNodes, sizeof(crt_bvh_node4q) * n4, sizeof(crt_bvh_node4q) * cap + 128)) return rc;
-    if (int rc = regrow(c, c->dPlanes, sizeof(float) * crt::kPlaneStride * n4, sizeof(float) * crt::kPlaneStride * cap)) return rc;
+    if (int rc = reserveRefitCapacity(c)) return rc;
     c->dyn = new (std::nothrow) crt::DynamicScene();
     if (!c->dyn) return fail(c, CRT_ENOMEM, "out of host memory");
     try {
-        crt::dynamicInit(*c->dyn, meshes, n_meshes, hostTree ? c->bvh.nodes.data() : nullptr, static_cast<const crt_bvh_node*>(c->dBinNodes), nBin,
-                         c->stream);
+        crt::dynamicInit(*c->dyn, meshes, n_meshes, c->bvh.nodes.empty() ? nullptr : c->bvh.nodes.data(),
+                         static_cast<const crt_bvh_node*>(c->dBinNodes), c->bvh.dev.nNodes, c->stream);
     } catch (const std::bad_alloc&) {
         return fail(c, CRT_ENOMEM, "out of host memory while keeping the dynamic scene");
     } catch (const std::exception& ex) {
@@ -500,7 +518,7 @@ int applyRefit(crt_ctx* c, double* device_ms)
     } catch (const std::exception& ex) {
         return fail(c, CRT_EHIP, "refit failed: %s", ex.what());
     }
-    c->bvh.nNodes4 = nWide;
+    c->bvh.dev.nNodes4 = nWide;
     c->bvh.depth4 = depth4;
     if (int rc = readSceneBox(c)) return rc;
     c->sceneSerial++;
@@ -534,7 +552,7 @@ void fillParams(const crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_
     p.textures = c->dTextures;
     p.texels = static_cast<const unsigned char*>(c->dTexels);
     p.n_textures = c->nTextures;
-    p.n_nodes = c->bvh.nNodes4;
+    p.n_nodes = c->bvh.dev.nNodes4;
     p.n_tris = c->bvh.nTris;
     p.n_lights = c->nLights;
     p.n_mats = c->nMats;
@@ -1131,55 +1149,25 @@ int crt_upload_scene(crt_ctx* c, const crt_mesh_view* meshes, uint32_t n_meshes,
     } catch (const std::exception& ex) {
         return fail(c, CRT_EINVAL, "BVH build failed: %s", ex.what());
     }
-    // records the GPU builder left in HBM: adopted below, or released here if anything fails before that
-    struct DevRecords {
-        crt::Bvh& b;
-        ~DevRecords()
-        {
-            for (void** q : { &b.devTris, &b.devShade, &b.devUvs, &b.devNodes, &b.devNodes4, &b.devNodes4q }) {
-                if (*q) (void)hipFree(*q);
-                *q = nullptr;
-            }
-        }
-    } pending{ built };
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipDeviceSynchronize()); // frames in flight on any stream the caller used still read the old scene's buffers
     freeScene(c); // from here on a failure leaves NO scene (haveScene = false): never the new host tree over old device buffers
-    std::swap(c->bvh, built); // (pending now guards whatever the OLD tree still pointed at: nothing)
+    crt::DeviceTree tree = std::move(built.dev); // (a failure before the context adopts it frees it with this call)
+    const bool builtOnDevice = static_cast<bool>(tree.tris);
+    std::swap(c->bvh, built);
     c->buildDeviceMs = deviceMs;
-    const bool recordsOnDevice = c->bvh.devTris != nullptr;
-    if (recordsOnDevice) { // built on the GPU: the leaf-ordered records are already in HBM; adopted before anything else can fail
-        c->dTris = c->bvh.devTris;
-        c->dShade = c->bvh.devShade;
-        c->dUvs = c->bvh.devUvs;
-        c->dNodes = c->bvh.devNodes4q;
-        c->dBinNodes = c->bvh.devNodes;
-        c->dWideNodes = c->bvh.devNodes4;
-        c->bvh.devTris = c->bvh.devShade = c->bvh.devUvs = c->bvh.devNodes = c->bvh.devNodes4 = c->bvh.devNodes4q = nullptr;
-    }
-    const size_t nb = sizeof(crt_bvh_node4q) * c->bvh.nodes4q.size(); // the quantised wide tree is what the kernels traverse
-    const size_t tb = sizeof(crt_bvh_tri) * c->bvh.nTris;
-    const size_t sb = sizeof(crt_bvh_shade) * c->bvh.nTris;
-    // +64 bytes of slack so that a speculative wide load of the last record stays inside the allocation
-    if (!c->dNodes) { // (a tree collapsed on the device is already there)
-        HIP_TRY(c, hipMalloc(&c->dNodes, nb + 128));
-        if (nb) HIP_TRY(c, hipMemcpy(c->dNodes, c->bvh.nodes4q.data(), nb, hipMemcpyHostToDevice));
-    }
-    if (c->bvh.nNodes4 > 0) { // from the records in HBM, so a tree built on the device gets its table the same way
-        HIP_TRY(c, hipMalloc(&c->dPlanes, sizeof(float) * crt::kPlaneStride * c->bvh.nNodes4));
-        HIP_TRY(c, static_cast<hipError_t>(crt::launchDecodePlanes(c->dNodes, c->bvh.nNodes4, static_cast<float*>(c->dPlanes), nullptr)));
-        HIP_TRY(c, hipDeviceSynchronize());
-    }
-    if (!recordsOnDevice) {
-        HIP_TRY(c, hipMalloc(&c->dTris, tb + 64));
-        HIP_TRY(c, hipMalloc(&c->dShade, sb + 64));
-        if (tb) HIP_TRY(c, hipMemcpy(c->dTris, c->bvh.tris.data(), tb, hipMemcpyHostToDevice));
-        if (sb) HIP_TRY(c, hipMemcpy(c->dShade, c->bvh.shade.data(), sb, hipMemcpyHostToDevice));
-        if (!c->bvh.uvs.empty()) {
-            const size_t ub = sizeof(crt_bvh_uv) * c->bvh.uvs.size();
-            HIP_TRY(c, hipMalloc(&c->dUvs, ub));
-            HIP_TRY(c, hipMemcpy(c->dUvs, c->bvh.uvs.data(), ub, hipMemcpyHostToDevice));
+    if (!builtOnDevice) { // a host tree: what the kernels traverse goes to HBM, for a dynamic scene also what a refit starts from
+        try {
+            tree = crt::uploadTree(c->bvh, c->dynamicOpt);
+        } catch (const std::exception& ex) {
+            return fail(c, CRT_EHIP, "%s", ex.what());
         }
+    }
+    adoptTree(c, std::move(tree));
+    if (c->bvh.dev.nNodes4 > 0) { // from the records in HBM, so a tree built on the device gets its table the same way
+        HIP_TRY(c, hipMalloc(&c->dPlanes, sizeof(float) * crt::kPlaneStride * c->bvh.dev.nNodes4));
+        HIP_TRY(c, static_cast<hipError_t>(crt::launchDecodePlanes(c->dNodes, c->bvh.dev.nNodes4, static_cast<float*>(c->dPlanes), nullptr)));
+        HIP_TRY(c, hipDeviceSynchronize());
     }
     HIP_TRY(c, hipMalloc(&c->dLights, sizeof(crt_light) * (n_lights + 1)));
     HIP_TRY(c, hipMalloc(&c->dMats, sizeof(crt_material) * (n_materials + 1)));
@@ -1560,7 +1548,7 @@ crt::QueryCommon queryCommon(const crt_ctx* c, const QueryLaunch& ql, const void
     crt::QueryCommon q;
     q.nodes = c->dNodes;
     q.tris = c->dTris;
-    q.n_nodes = c->bvh.nNodes4;
+    q.n_nodes = c->bvh.dev.nNodes4;
     q.records = d_records;
     q.n = n;
     q.cursor = ql.cursor;
@@ -2771,7 +2759,7 @@ int crt_bvh_info(const crt_ctx* c, uint32_t* n_nodes, uint32_t* n_tris, uint32_t
 {
     if (!c || !c->haveScene) return CRT_ESTATE;
     if (int rc = applyRefit(const_cast<crt_ctx*>(c), nullptr)) return rc; // (pending updates of a dynamic scene)
-    if (n_nodes) *n_nodes = c->bvh.nNodes;
+    if (n_nodes) *n_nodes = c->bvh.dev.nNodes;
     if (n_tris) *n_tris = c->bvh.nTris;
     if (max_depth) *max_depth = c->bvh.maxDepth;
     return CRT_OK;
@@ -2789,7 +2777,7 @@ int crt_bvh_info4(const crt_ctx* c, uint32_t* n_nodes4, uint32_t* depth4)
 {
     if (!c || !c->haveScene) return CRT_ESTATE;
     if (int rc = applyRefit(const_cast<crt_ctx*>(c), nullptr)) return rc; // (pending updates of a dynamic scene)
-    if (n_nodes4) *n_nodes4 = c->bvh.nNodes4;
+    if (n_nodes4) *n_nodes4 = c->bvh.dev.nNodes4;
     if (depth4) *depth4 = c->bvh.depth4;
     return CRT_OK;
 }
@@ -2800,7 +2788,7 @@ int crt_bvh_export4(const crt_ctx* c, crt_bvh_node4* nodes4)
     if (int rc = applyRefit(const_cast<crt_ctx*>(c), nullptr)) return rc; // (pending updates of a dynamic scene)
     if (nodes4) {
         if (!c->dWideNodes) crt::copyBytes(nodes4, c->bvh.nodes4.data(), sizeof(crt_bvh_node4) * c->bvh.nodes4.size());
-        else if (hipMemcpy(nodes4, c->dWideNodes, sizeof(crt_bvh_node4) * c->bvh.nNodes4, hipMemcpyDeviceToHost) != hipSuccess) return CRT_EHIP;
+        else if (hipMemcpy(nodes4, c->dWideNodes, sizeof(crt_bvh_node4) * c->bvh.dev.nNodes4, hipMemcpyDeviceToHost) != hipSuccess) return CRT_EHIP;
     }
     return CRT_OK;
 }
@@ -2811,7 +2799,7 @@ int crt_bvh_export4q(const crt_ctx* c, crt_bvh_node4q* nodes4q)
     if (int rc = applyRefit(const_cast<crt_ctx*>(c), nullptr)) return rc; // (pending updates of a dynamic scene)
     if (nodes4q) {
         if (!c->dWideNodes) crt::copyBytes(nodes4q, c->bvh.nodes4q.data(), sizeof(crt_bvh_node4q) * c->bvh.nodes4q.size());
-        else if (hipMemcpy(nodes4q, c->dNodes, sizeof(crt_bvh_node4q) * c->bvh.nNodes4, hipMemcpyDeviceToHost) != hipSuccess) return CRT_EHIP;
+        else if (hipMemcpy(nodes4q, c->dNodes, sizeof(crt_bvh_node4q) * c->bvh.dev.nNodes4, hipMemcpyDeviceToHost) != hipSuccess) return CRT_EHIP;
     }
     return CRT_OK;
 }
@@ -2820,8 +2808,8 @@ int crt_bvh_export_planes4q(const crt_ctx* c, float* planes)
 {
     if (!c || !c->haveScene) return CRT_ESTATE;
     if (int rc = applyRefit(const_cast<crt_ctx*>(c), nullptr)) return rc; // (pending updates of a dynamic scene)
-    if (planes && c->bvh.nNodes4 > 0 &&
-        hipMemcpy(planes, c->dPlanes, sizeof(float) * crt::kPlaneStride * c->bvh.nNodes4, hipMemcpyDeviceToHost) != hipSuccess)
+    if (planes && c->bvh.dev.nNodes4 > 0 &&
+        hipMemcpy(planes, c->dPlanes, sizeof(float) * crt::kPlaneStride * c->bvh.dev.nNodes4, hipMemcpyDeviceToHost) != hipSuccess)
         return CRT_EHIP;
     return CRT_OK;
 }
@@ -2856,7 +2844,7 @@ int crt_bvh_export(const crt_ctx* c, crt_bvh_node* nodes, crt_bvh_tri* tris, crt
     if (int rc = applyRefit(const_cast<crt_ctx*>(c), nullptr)) return rc; // (pending updates of a dynamic scene)
     if (nodes) {
         if (!c->dBinNodes) crt::copyBytes(nodes, c->bvh.nodes.data(), sizeof(crt_bvh_node) * c->bvh.nodes.size());
-        else if (hipMemcpy(nodes, c->dBinNodes, sizeof(crt_bvh_node) * c->bvh.nNodes, hipMemcpyDeviceToHost) != hipSuccess) return CRT_EHIP;
+        else if (hipMemcpy(nodes, c->dBinNodes, sizeof(crt_bvh_node) * c->bvh.dev.nNodes, hipMemcpyDeviceToHost) != hipSuccess) return CRT_EHIP;
     }
     // a tree built on the GPU keeps its leaf-ordered records in HBM only: copy them out of there
     const bool onDevice = c->bvh.tris.empty() && c->bvh.nTris != 0;
@@ -2962,19 +2950,9 @@ int crt_rebuild(crt_ctx* c, double* device_ms)
     if (c->dyn->nTris == 0) return applyRefit(c, device_ms); // no tree to build: the pending updates are all there is
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipDeviceSynchronize()); // frames in flight on any stream the caller used still read the records and the tree
-    crt::Bvh built;
-    struct DevRecords { // the new tree's buffers until the context adopts them
-        crt::Bvh& b;
-        ~DevRecords()
-        {
-            for (void** q : { &b.devTris, &b.devShade, &b.devUvs, &b.devNodes, &b.devNodes4, &b.devNodes4q }) {
-                if (*q) (void)hipFree(*q);
-                *q = nullptr;
-            }
-        }
-    } pending{ built };
+    crt::DeviceTree built;
     try {
-        crt::dynamicRebuild(*c->dyn, c->gpuBuilder, static_cast<const crt_bvh_tri*>(c->dTris), c->dUvs, built, c->stream, device_ms);
+        built = crt::dynamicRebuild(*c->dyn, c->gpuBuilder, static_cast<const crt_bvh_tri*>(c->dTris), c->dUvs, c->stream, device_ms);
     } catch (const std::bad_alloc&) {
         freeScene(c); // the world vertices may already be moved and the level lists half rewritten: as a failed upload, no scene
         return fail(c, CRT_ENOMEM, "crt_rebuild: out of host memory");
@@ -2982,34 +2960,11 @@ int crt_rebuild(crt_ctx* c, double* device_ms)
         freeScene(c);
         return fail(c, CRT_EHIP, "crt_rebuild failed: %s", ex.what());
     }
-    // adopt the new tree and records; the wide tree, its quantised form and the plane table get room for one node per binary inner
-    // node, as at a dynamic upload (a refit may collapse to more wide nodes than the build did)
-    void** olds[] = { &c->dBinNodes, &c->dWideNodes, &c->dNodes, &c->dPlanes, &c->dTris, &c->dShade, &c->dUvs };
-    for (void** q : olds) {
-        if (*q) (void)hipFree(*q);
-        *q = nullptr;
-    }
-    c->dBinNodes = built.devNodes;
-    c->dWideNodes = built.devNodes4;
-    c->dNodes = built.devNodes4q;
-    c->dTris = built.devTris;
-    c->dShade = built.devShade;
-    c->dUvs = built.devUvs;
-    built.devNodes = built.devNodes4 = built.devNodes4q = built.devTris = built.devShade = built.devUvs = nullptr;
-    c->bvh.nNodes = built.nNodes;
-    c->bvh.nNodes4 = built.nNodes4;
-    c->bvh.depth4 = built.depth4;
-    c->bvh.maxDepth = built.maxDepth;
-    c->bvh.nTris = built.nTris;
-    const uint32_t cap = built.nNodes ? built.nNodes : 1u, n4 = built.nNodes4;
-    int rc = regrow(c, c->dWideNodes, sizeof(crt_bvh_node4) * n4, sizeof(crt_bvh_node4) * cap);
-    if (!rc) rc = regrow(c, c->dNodes, sizeof(crt_bvh_node4q) * n4, sizeof(crt_bvh_node4q) * cap + 128);
+    // adopt the new tree and records, with the refit capacity of a dynamic upload
+    adoptTree(c, std::move(built));
+    int rc = reserveRefitCapacity(c);
     if (!rc) {
-        const hipError_t e = hipMalloc(&c->dPlanes, sizeof(float) * crt::kPlaneStride * cap);
-        if (e != hipSuccess) rc = fail(c, CRT_EHIP, "hipMalloc failed: %s", hipGetErrorString(e));
-    }
-    if (!rc) {
-        hipError_t e = static_cast<hipError_t>(crt::launchDecodePlanes(c->dNodes, n4, static_cast<float*>(c->dPlanes), c->stream));
+        hipError_t e = static_cast<hipError_t>(crt::launchDecodePlanes(c->dNodes, c->bvh.dev.nNodes4, static_cast<float*>(c->dPlanes), c->stream));
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(c, CRT_EHIP, "plane table: %s", hipGetErrorString(e));
     }

@@ -12,7 +12,6 @@
 #include <vector>
 
 struct ihipStream_t;
-struct ihipEvent_t;
 
 namespace crt {
 
@@ -38,8 +37,7 @@ struct DynamicScene {
     uint32_t* dLevelNodes = nullptr;  // binary inner nodes by depth: level k = dLevelNodes[levelStart[k] .. levelStart[k + 1])
     std::vector<uint32_t> levelStart;
     void* dScratch = nullptr;         // collapseWideGpu scratch
-    ihipEvent_t* ev0 = nullptr;
-    ihipEvent_t* ev1 = nullptr;
+    EventPair timer;                  // device_ms of a refit or a rebuild
     bool pending = false;             // some mesh is dirty
 
     DynamicScene() = default;
@@ -67,11 +65,10 @@ void dynamicInit(DynamicScene& d, const crt_mesh_view* meshes, uint32_t n_meshes
 void dynamicRefit(DynamicScene& d, const RefitTargets& t, ihipStream_t* stream, uint32_t* nWide, uint32_t* depth4, double* device_ms);
 
 // The rebuild (crt_rebuild; d.nTris > 0): the pending updates applied, then a new tree from the world vertices in HBM with the GPU
-// builder `builder` (bvh_build.h kGpuBuilder*).  out: the tree, its wide and quantised forms and the leaf-ordered records, all in HBM
-// (for <= kLeafMax triangles the builders' one-leaf tree is made on the host and uploaded here); whatever out holds belongs to the
-// caller, on success and on failure.  oldTris / oldUvs: the current leaf-ordered records; when oldUvs is set, out.devUvs holds the uv
-// records permuted to the new leaf order by gid.  The level lists and the collapse scratch follow the new tree.  Throws
-// std::runtime_error on HIP errors.
-void dynamicRebuild(DynamicScene& d, int builder, const crt_bvh_tri* oldTris, const void* oldUvs, Bvh& out, ihipStream_t* stream, double* device_ms);
+// builder `builder` (bvh_build.h kGpuBuilder*).  Returns the tree, its wide and quantised forms and the leaf-ordered records, all in
+// HBM (for <= kLeafMax triangles the builders' one-leaf tree is made on the host and uploaded: uploadTree).  oldTris / oldUvs: the
+// current leaf-ordered records; when oldUvs is set, the tree's uvs hold the uv records permuted to the new leaf order by gid.  The
+// level lists and the collapse scratch follow the new tree.  Throws std::runtime_error on HIP errors.
+DeviceTree dynamicRebuild(DynamicScene& d, int builder, const crt_bvh_tri* oldTris, const void* oldUvs, ihipStream_t* stream, double* device_ms);
 
 } // namespace crt

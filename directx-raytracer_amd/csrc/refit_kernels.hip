@@ -2,16 +2,18 @@
 // same bytes a fresh build of the moved meshes writes for every record whose place in the tree did not change.
 //   1. transformKernel: world = transform . rest, one thread per vertex, for meshes whose transform is not the identity
 //      (an identity mesh's world data is a copy of its rest data: no arithmetic, -0.0 stays -0.0)
-//   2. recordsKernel: the leaf-ordered triangle / shading records from the world vertices, as gatherKernel / flattenMeshes
+//   2. recordsKernel: the leaf-ordered triangle / shading records from the world vertices, by triRecord / triNormals
+//      (tri_geometry.hip.h), which the GPU build's gatherKernel calls too
 //   3. refitLevelKernel: the binary boxes bottom-up, one launch per depth level, deepest first -- the kernel boundary is the
-//      only synchronisation (no atomics, no hand-off between XCDs); a leaf's box from its triangles' vertices as triBoxKernel
-//      takes them, an inner node's from grow(left, right) with the selects of fitKernel / the oracle's aabb_grow
+//      only synchronisation (no atomics, no hand-off between XCDs); a leaf's box from its triangles' triBox, as the GPU build's
+//      triBoxKernel, an inner node's from grow(left, right) with minSel / maxSel, the selects of the oracle's aabb_grow
 //   4. collapseWideGpu (bvh_gpu.hip, shared with the GPU build) and the plane table (launchDecodePlanes)
 #include "refit.h"
 
 #include "bvh_build.h"
-#include "mesh_table.hip.h"
+#include "hip_own.h"
 #include "render_kernels.h"
+#include "tri_geometry.hip.h"
 
 #include <hip/hip_runtime.h>
 
@@ -22,12 +24,6 @@
 
 namespace crt {
 namespace {
-
-#define REFIT_TRY(expr)                                                                                        \
-    do {                                                                                                       \
-        hipError_t e_ = (expr);                                                                                \
-        if (e_ != hipSuccess) throw std::runtime_error(std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-    } while (0)
 
 struct Xform {
     float m[12];
@@ -49,40 +45,18 @@ __global__ __launch_bounds__(256) void transformKernel(const float* __restrict__
     }
 }
 
-// leaf position i: the record's gid names the triangle; v0 / e1 / e2 and the vertex normals as gatherKernel writes them
+// leaf position i: the record's gid names the triangle; v0 / e1 / e2 and the vertex normals rewritten in place (inst, prim, gid,
+// the material and a mesh without normals' zeros stay)
 __global__ __launch_bounds__(256) void recordsKernel(const MeshEntry* __restrict__ table, uint32_t n_meshes, const float* __restrict__ xyz,
                                                      const float* __restrict__ normals, const uint32_t* __restrict__ idx, uint32_t n,
                                                      crt_bvh_tri* __restrict__ tris, crt_bvh_shade* __restrict__ shade)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const uint32_t g = tris[i].gid;
-    const MeshEntry M = table[meshOf(table, n_meshes, g)];
-    const uint32_t v0 = M.vertStart + idx[3 * static_cast<size_t>(g)], v1 = M.vertStart + idx[3 * static_cast<size_t>(g) + 1],
-                   v2 = M.vertStart + idx[3 * static_cast<size_t>(g) + 2];
-    const float* A = xyz + 3 * static_cast<size_t>(v0);
-    const float* B = xyz + 3 * static_cast<size_t>(v1);
-    const float* C = xyz + 3 * static_cast<size_t>(v2);
-    bool finite = true;
-    for (int k = 0; k < 3; k++) finite &= A[k] - A[k] == 0.0f && B[k] - B[k] == 0.0f && C[k] - C[k] == 0.0f; // x - x == 0: finite
-    const float qnan = __uint_as_float(0x7FC00000u); // an inert triangle's record (crt_hip.h), as gatherKernel writes it
-    for (int k = 0; k < 3; k++) {
-        tris[i].v0[k] = finite ? A[k] : qnan;
-        tris[i].e1[k] = finite ? B[k] - A[k] : qnan;
-        tris[i].e2[k] = finite ? C[k] - A[k] : qnan;
-    }
-    if (M.hasNormals)
-        for (int k = 0; k < 3; k++) {
-            shade[i].n0[k] = normals[3 * static_cast<size_t>(v0) + k];
-            shade[i].n1[k] = normals[3 * static_cast<size_t>(v1) + k];
-            shade[i].n2[k] = normals[3 * static_cast<size_t>(v2) + k];
-        }
+    const TriFetch t = fetchTri(table, n_meshes, xyz, idx, tris[i].gid);
+    triRecord(t, tris[i].v0, tris[i].e1, tris[i].e2);
+    triNormals(t, normals, shade[i].n0, shade[i].n1, shade[i].n2);
 }
-
-__device__ __forceinline__ float minSel(float a, float b) { return a < b ? a : b; }
-__device__ __forceinline__ float maxSel(float a, float b) { return a > b ? a : b; }
-
-struct Box6 { float mn[3], mx[3]; };
 
 // Every node of one depth level: both child boxes.  An inner child's box is the union of ITS two child boxes (written by the
 // launch of the level below); a leaf's the union of its triangles' boxes in leaf order.  Both builders fold boxes with the same
@@ -111,21 +85,7 @@ __global__ __launch_bounds__(256) void refitLevelKernel(const uint32_t* __restri
         const uint32_t leaf = static_cast<uint32_t>(~ref), first = leaf >> 3, cnt = leaf & 7u;
         empty[c] = cnt == 0u;
         for (int a = 0; a < 3; a++) { B.mn[a] = INFINITY; B.mx[a] = -INFINITY; }
-        for (uint32_t k = 0; k < cnt; k++) {
-            const uint32_t g = tris[first + k].gid;
-            const MeshEntry M = table[meshOf(table, n_meshes, g)];
-            const float* P = xyz + 3 * static_cast<size_t>(M.vertStart + idx[3 * static_cast<size_t>(g)]);
-            const float* Q = xyz + 3 * static_cast<size_t>(M.vertStart + idx[3 * static_cast<size_t>(g) + 1]);
-            const float* R = xyz + 3 * static_cast<size_t>(M.vertStart + idx[3 * static_cast<size_t>(g) + 2]);
-            bool finite = true;
-            for (int a = 0; a < 3; a++) finite &= P[a] - P[a] == 0.0f && Q[a] - Q[a] == 0.0f && R[a] - R[a] == 0.0f; // x - x == 0: finite
-            for (int a = 0; a < 3; a++) { // an inert triangle (crt_hip.h) counts as the point (0, 0, 0), as in triBoxKernel
-                const float lo = finite ? minSel(minSel(P[a], Q[a]), R[a]) : 0.0f;
-                const float hi = finite ? maxSel(maxSel(P[a], Q[a]), R[a]) : 0.0f;
-                B.mn[a] = minSel(B.mn[a], lo);
-                B.mx[a] = maxSel(B.mx[a], hi);
-            }
-        }
+        for (uint32_t k = 0; k < cnt; k++) B = unionBox(B, triBox(fetchTri(table, n_meshes, xyz, idx, tris[first + k].gid)));
     }
     if (empty[1]) box[1] = box[0];
     else if (empty[0]) box[0] = box[1];
@@ -158,8 +118,8 @@ static void setLevels(DynamicScene& d, const crt_bvh_node* hostNodes, const crt_
     std::vector<crt_bvh_node> readBack;
     if (!hostNodes && nBinary) {
         readBack.resize(nBinary);
-        REFIT_TRY(hipMemcpyAsync(readBack.data(), binNodes, sizeof(crt_bvh_node) * nBinary, hipMemcpyDeviceToHost, stream));
-        REFIT_TRY(hipStreamSynchronize(stream));
+        HIP_THROW(hipMemcpyAsync(readBack.data(), binNodes, sizeof(crt_bvh_node) * nBinary, hipMemcpyDeviceToHost, stream));
+        HIP_THROW(hipStreamSynchronize(stream));
         hostNodes = readBack.data();
     }
     std::vector<uint32_t> order;
@@ -188,11 +148,11 @@ static void setLevels(DynamicScene& d, const crt_bvh_node* hostNodes, const crt_
     if (d.dScratch) (void)hipFree(d.dScratch);
     d.dScratch = nullptr;
     d.nBinary = nBinary;
-    REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dLevelNodes), sizeof(uint32_t) * (order.empty() ? 1 : order.size())));
+    HIP_THROW(hipMalloc(reinterpret_cast<void**>(&d.dLevelNodes), sizeof(uint32_t) * (order.empty() ? 1 : order.size())));
     if (!order.empty())
-        REFIT_TRY(hipMemcpyAsync(d.dLevelNodes, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, stream));
-    REFIT_TRY(hipMalloc(&d.dScratch, collapseScratchBytes(nBinary)));
-    REFIT_TRY(hipStreamSynchronize(stream)); // the host arrays above die with this call
+        HIP_THROW(hipMemcpyAsync(d.dLevelNodes, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice, stream));
+    HIP_THROW(hipMalloc(&d.dScratch, collapseScratchBytes(nBinary)));
+    HIP_THROW(hipStreamSynchronize(stream)); // the host arrays above die with this call
 }
 
 // world = transform . rest for every dirty mesh (step 1 of the refit and of the rebuild)
@@ -203,8 +163,8 @@ static void applyTransforms(DynamicScene& d, ihipStream_t* stream)
         if (!D.dirty || D.nVerts == 0) continue;
         const size_t off = 3 * static_cast<size_t>(D.vertStart), bytes = sizeof(float) * 3 * D.nVerts;
         if (D.identity) {
-            REFIT_TRY(hipMemcpyAsync(d.dWorldXyz + off, d.dRestXyz + off, bytes, hipMemcpyDeviceToDevice, stream));
-            if (D.hasNormals) REFIT_TRY(hipMemcpyAsync(d.dWorldNormals + off, d.dRestNormals + off, bytes, hipMemcpyDeviceToDevice, stream));
+            HIP_THROW(hipMemcpyAsync(d.dWorldXyz + off, d.dRestXyz + off, bytes, hipMemcpyDeviceToDevice, stream));
+            if (D.hasNormals) HIP_THROW(hipMemcpyAsync(d.dWorldNormals + off, d.dRestNormals + off, bytes, hipMemcpyDeviceToDevice, stream));
         } else {
             Xform X;
             std::memcpy(X.m, D.m, sizeof(X.m));
@@ -220,8 +180,6 @@ DynamicScene::~DynamicScene()
     void* ptrs[] = { dTable, dRestXyz, dRestNormals, dWorldXyz, dWorldNormals, dPrevXyz, dIdx, dLevelNodes, dScratch };
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
 }
 
 void dynamicInit(DynamicScene& d, const crt_mesh_view* meshes, uint32_t n_meshes, const crt_bvh_node* hostNodes, const crt_bvh_node* binNodes,
@@ -230,59 +188,51 @@ void dynamicInit(DynamicScene& d, const crt_mesh_view* meshes, uint32_t n_meshes
     uint64_t nv = 0, nt = 0;
     bool anyNormals = false;
     d.meshes.resize(n_meshes);
-    std::vector<MeshEntry> table(n_meshes + 1u);
+    const std::vector<MeshEntry> table = makeMeshTable(meshes, n_meshes);
     for (uint32_t m = 0; m < n_meshes; m++) {
         DynamicMesh& D = d.meshes[m];
-        D.vertStart = static_cast<uint32_t>(nv);
+        D.vertStart = table[m].vertStart;
         D.nVerts = meshes[m].n_vertices;
         D.hasNormals = meshes[m].normals != nullptr;
         anyNormals |= D.hasNormals && D.nVerts > 0;
-        MeshEntry& E = table[m];
-        E.triStart = static_cast<uint32_t>(nt); E.vertStart = static_cast<uint32_t>(nv); E.nVerts = D.nVerts;
-        E.material = static_cast<uint32_t>(meshes[m].material_index);
-        E.hasNormals = D.hasNormals ? 1u : 0u; E.hasUvs = meshes[m].uvs ? 1u : 0u; E.pad0 = E.pad1 = 0;
         nv += meshes[m].n_vertices;
         nt += meshes[m].n_triangles;
     }
     if (nv >= (1ull << 32)) throw std::runtime_error("too many vertices");
-    MeshEntry& E = table[n_meshes];
-    E.triStart = static_cast<uint32_t>(nt); E.vertStart = static_cast<uint32_t>(nv); E.nVerts = 0; E.material = 0; E.hasNormals = E.hasUvs = E.pad0 = E.pad1 = 0;
     d.nVerts = static_cast<uint32_t>(nv);
     d.nTris = static_cast<uint32_t>(nt);
     const size_t vb = sizeof(float) * 3 * (nv ? nv : 1);
-    REFIT_TRY(hipMalloc(&d.dTable, sizeof(MeshEntry) * table.size()));
-    REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dRestXyz), vb));
-    REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dWorldXyz), vb));
+    HIP_THROW(hipMalloc(&d.dTable, sizeof(MeshEntry) * table.size()));
+    HIP_THROW(hipMalloc(reinterpret_cast<void**>(&d.dRestXyz), vb));
+    HIP_THROW(hipMalloc(reinterpret_cast<void**>(&d.dWorldXyz), vb));
     if (anyNormals) {
-        REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dRestNormals), vb));
-        REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dWorldNormals), vb));
-        REFIT_TRY(hipMemsetAsync(d.dRestNormals, 0, vb, stream));
+        HIP_THROW(hipMalloc(reinterpret_cast<void**>(&d.dRestNormals), vb));
+        HIP_THROW(hipMalloc(reinterpret_cast<void**>(&d.dWorldNormals), vb));
+        HIP_THROW(hipMemsetAsync(d.dRestNormals, 0, vb, stream));
     }
-    REFIT_TRY(hipMalloc(reinterpret_cast<void**>(&d.dIdx), sizeof(uint32_t) * 3 * (nt ? nt : 1)));
-    REFIT_TRY(hipMemcpyAsync(d.dTable, table.data(), sizeof(MeshEntry) * table.size(), hipMemcpyHostToDevice, stream));
+    HIP_THROW(hipMalloc(reinterpret_cast<void**>(&d.dIdx), sizeof(uint32_t) * 3 * (nt ? nt : 1)));
+    HIP_THROW(hipMemcpyAsync(d.dTable, table.data(), sizeof(MeshEntry) * table.size(), hipMemcpyHostToDevice, stream));
     for (uint32_t m = 0; m < n_meshes; m++) {
         const crt_mesh_view& M = meshes[m];
         const size_t off = 3 * static_cast<size_t>(table[m].vertStart);
-        if (M.n_vertices && M.xyz) REFIT_TRY(hipMemcpyAsync(d.dRestXyz + off, M.xyz, sizeof(float) * 3 * M.n_vertices, hipMemcpyHostToDevice, stream));
+        if (M.n_vertices && M.xyz) HIP_THROW(hipMemcpyAsync(d.dRestXyz + off, M.xyz, sizeof(float) * 3 * M.n_vertices, hipMemcpyHostToDevice, stream));
         if (M.n_vertices && M.normals)
-            REFIT_TRY(hipMemcpyAsync(d.dRestNormals + off, M.normals, sizeof(float) * 3 * M.n_vertices, hipMemcpyHostToDevice, stream));
+            HIP_THROW(hipMemcpyAsync(d.dRestNormals + off, M.normals, sizeof(float) * 3 * M.n_vertices, hipMemcpyHostToDevice, stream));
         if (M.n_triangles)
-            REFIT_TRY(hipMemcpyAsync(d.dIdx + 3 * static_cast<size_t>(table[m].triStart), M.idx, sizeof(uint32_t) * 3 * static_cast<size_t>(M.n_triangles),
+            HIP_THROW(hipMemcpyAsync(d.dIdx + 3 * static_cast<size_t>(table[m].triStart), M.idx, sizeof(uint32_t) * 3 * static_cast<size_t>(M.n_triangles),
                                      hipMemcpyHostToDevice, stream));
     }
-    REFIT_TRY(hipMemcpyAsync(d.dWorldXyz, d.dRestXyz, vb, hipMemcpyDeviceToDevice, stream));
-    if (anyNormals) REFIT_TRY(hipMemcpyAsync(d.dWorldNormals, d.dRestNormals, vb, hipMemcpyDeviceToDevice, stream));
+    HIP_THROW(hipMemcpyAsync(d.dWorldXyz, d.dRestXyz, vb, hipMemcpyDeviceToDevice, stream));
+    if (anyNormals) HIP_THROW(hipMemcpyAsync(d.dWorldNormals, d.dRestNormals, vb, hipMemcpyDeviceToDevice, stream));
 
     setLevels(d, hostNodes, binNodes, nBinary, stream);
-    REFIT_TRY(hipEventCreate(&d.ev0));
-    REFIT_TRY(hipEventCreate(&d.ev1));
-    REFIT_TRY(hipStreamSynchronize(stream)); // the host arrays above die with this call
+    HIP_THROW(hipStreamSynchronize(stream)); // the host arrays above die with this call
 }
 
 void dynamicRefit(DynamicScene& d, const RefitTargets& t, ihipStream_t* stream, uint32_t* nWide, uint32_t* depth4, double* device_ms)
 {
     const dim3 blk(256);
-    REFIT_TRY(hipEventRecord(d.ev0, stream));
+    d.timer.start(stream);
     applyTransforms(d, stream);
     const uint32_t nMeshes = static_cast<uint32_t>(d.meshes.size());
     const MeshEntry* table = static_cast<const MeshEntry*>(d.dTable);
@@ -294,19 +244,14 @@ void dynamicRefit(DynamicScene& d, const RefitTargets& t, ihipStream_t* stream, 
         hipLaunchKernelGGL(refitLevelKernel, dim3((count + 255) / 256), blk, 0, stream, d.dLevelNodes + first, count, t.binNodes, t.tris, table,
                            nMeshes, d.dWorldXyz, d.dIdx);
     }
-    REFIT_TRY(hipGetLastError());
+    HIP_THROW(hipGetLastError());
     *nWide = 0;
     *depth4 = 0;
     if (d.nBinary) {
-        void* n4 = t.nodes4;
-        void* n4q = t.nodes4q;
-        collapseWideGpu(t.binNodes, d.nBinary, d.dScratch, &n4, &n4q, stream, nWide, depth4, nullptr);
-        REFIT_TRY(static_cast<hipError_t>(launchDecodePlanes(t.nodes4q, *nWide, t.planes, stream)));
+        collapseWideGpu(t.binNodes, d.nBinary, d.dScratch, t.nodes4, t.nodes4q, nullptr, stream, nWide, depth4, nullptr);
+        HIP_THROW(static_cast<hipError_t>(launchDecodePlanes(t.nodes4q, *nWide, t.planes, stream)));
     }
-    REFIT_TRY(hipEventRecord(d.ev1, stream));
-    REFIT_TRY(hipStreamSynchronize(stream));
-    float ms = 0.f;
-    REFIT_TRY(hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    const double ms = d.timer.stopAndWait(stream);
     if (device_ms) *device_ms = ms;
     for (DynamicMesh& D : d.meshes) D.dirty = false;
     d.pending = false;
@@ -316,12 +261,12 @@ void dynamicRefit(DynamicScene& d, const RefitTargets& t, ihipStream_t* stream, 
 
 namespace crt {
 
-void dynamicRebuild(DynamicScene& d, int builder, const crt_bvh_tri* oldTris, const void* oldUvs, Bvh& out, ihipStream_t* stream, double* device_ms)
+DeviceTree dynamicRebuild(DynamicScene& d, int builder, const crt_bvh_tri* oldTris, const void* oldUvs, ihipStream_t* stream, double* device_ms)
 {
-    out = Bvh();
+    DeviceTree out;
     if (device_ms) *device_ms = 0.0;
     if (d.nTris == 0) throw std::logic_error("dynamicRebuild: a scene without triangles");
-    REFIT_TRY(hipEventRecord(d.ev0, stream));
+    d.timer.start(stream);
     applyTransforms(d, stream);
     const uint32_t nMeshes = static_cast<uint32_t>(d.meshes.size());
     if (d.nTris > static_cast<uint32_t>(kLeafMax)) {
@@ -332,17 +277,17 @@ void dynamicRebuild(DynamicScene& d, int builder, const crt_bvh_tri* oldTris, co
         in.xyz = d.dWorldXyz;
         in.idx = d.dIdx;
         in.normals = d.dWorldNormals;
-        rebuildBvhGpu(in, builder, out, stream, nullptr);
+        out = rebuildBvhGpu(in, builder, stream, nullptr);
     } else {
         // a handful of triangles: the builders' one-leaf tree is made on the host (bvh_gpu.hip), from the world vertices read back
         std::vector<MeshEntry> table(nMeshes + 1u);
         std::vector<float> xyz(3 * static_cast<size_t>(d.nVerts)), nrm(d.dWorldNormals ? 3 * static_cast<size_t>(d.nVerts) : 0);
         std::vector<uint32_t> idx(3 * static_cast<size_t>(d.nTris));
-        REFIT_TRY(hipMemcpyAsync(table.data(), d.dTable, sizeof(MeshEntry) * table.size(), hipMemcpyDeviceToHost, stream));
-        if (!xyz.empty()) REFIT_TRY(hipMemcpyAsync(xyz.data(), d.dWorldXyz, sizeof(float) * xyz.size(), hipMemcpyDeviceToHost, stream));
-        if (!nrm.empty()) REFIT_TRY(hipMemcpyAsync(nrm.data(), d.dWorldNormals, sizeof(float) * nrm.size(), hipMemcpyDeviceToHost, stream));
-        REFIT_TRY(hipMemcpyAsync(idx.data(), d.dIdx, sizeof(uint32_t) * idx.size(), hipMemcpyDeviceToHost, stream));
-        REFIT_TRY(hipStreamSynchronize(stream));
+        HIP_THROW(hipMemcpyAsync(table.data(), d.dTable, sizeof(MeshEntry) * table.size(), hipMemcpyDeviceToHost, stream));
+        if (!xyz.empty()) HIP_THROW(hipMemcpyAsync(xyz.data(), d.dWorldXyz, sizeof(float) * xyz.size(), hipMemcpyDeviceToHost, stream));
+        if (!nrm.empty()) HIP_THROW(hipMemcpyAsync(nrm.data(), d.dWorldNormals, sizeof(float) * nrm.size(), hipMemcpyDeviceToHost, stream));
+        HIP_THROW(hipMemcpyAsync(idx.data(), d.dIdx, sizeof(uint32_t) * idx.size(), hipMemcpyDeviceToHost, stream));
+        HIP_THROW(hipStreamSynchronize(stream));
         std::vector<crt_mesh_view> views(nMeshes);
         for (uint32_t m = 0; m < nMeshes; m++) {
             const MeshEntry& E = table[m];
@@ -357,43 +302,24 @@ void dynamicRebuild(DynamicScene& d, int builder, const crt_bvh_tri* oldTris, co
         }
         Bvh host;
         buildBvhGpu(views.data(), nMeshes, host, stream, nullptr, builder);
-        REFIT_TRY(hipMalloc(&out.devNodes, sizeof(crt_bvh_node) * host.nodes.size()));
-        REFIT_TRY(hipMalloc(&out.devNodes4, sizeof(crt_bvh_node4) * host.nodes4.size()));
-        REFIT_TRY(hipMalloc(&out.devNodes4q, sizeof(crt_bvh_node4q) * host.nodes4q.size() + 128));
-        REFIT_TRY(hipMalloc(&out.devTris, sizeof(crt_bvh_tri) * host.tris.size() + 64));
-        REFIT_TRY(hipMalloc(&out.devShade, sizeof(crt_bvh_shade) * host.shade.size() + 64));
-        REFIT_TRY(hipMemcpyAsync(out.devNodes, host.nodes.data(), sizeof(crt_bvh_node) * host.nodes.size(), hipMemcpyHostToDevice, stream));
-        REFIT_TRY(hipMemcpyAsync(out.devNodes4, host.nodes4.data(), sizeof(crt_bvh_node4) * host.nodes4.size(), hipMemcpyHostToDevice, stream));
-        REFIT_TRY(hipMemcpyAsync(out.devNodes4q, host.nodes4q.data(), sizeof(crt_bvh_node4q) * host.nodes4q.size(), hipMemcpyHostToDevice, stream));
-        REFIT_TRY(hipMemcpyAsync(out.devTris, host.tris.data(), sizeof(crt_bvh_tri) * host.tris.size(), hipMemcpyHostToDevice, stream));
-        REFIT_TRY(hipMemcpyAsync(out.devShade, host.shade.data(), sizeof(crt_bvh_shade) * host.shade.size(), hipMemcpyHostToDevice, stream));
-        REFIT_TRY(hipStreamSynchronize(stream)); // (the host arrays die with this scope)
-        out.nNodes = static_cast<uint32_t>(host.nodes.size());
-        out.nNodes4 = static_cast<uint32_t>(host.nodes4.size());
-        out.depth4 = host.depth4;
-        out.maxDepth = host.maxDepth;
-        out.nTris = host.nTris;
+        out = uploadTree(host, true);
     }
     if (oldUvs) {
         const dim3 blk(256), grd((d.nTris + 255) / 256);
-        void* byGid = nullptr;
-        REFIT_TRY(hipMalloc(&byGid, sizeof(crt_bvh_uv) * d.nTris));
-        struct Owned { void*& p; ~Owned() { if (p) (void)hipFree(p); } } owned{ byGid };
-        REFIT_TRY(hipMalloc(&out.devUvs, sizeof(crt_bvh_uv) * d.nTris + 64));
-        hipLaunchKernelGGL(uvScatterKernel, grd, blk, 0, stream, oldTris, static_cast<const crt_bvh_uv*>(oldUvs), d.nTris, static_cast<crt_bvh_uv*>(byGid));
-        hipLaunchKernelGGL(uvGatherKernel, grd, blk, 0, stream, static_cast<const crt_bvh_tri*>(out.devTris), static_cast<const crt_bvh_uv*>(byGid), d.nTris,
-                           static_cast<crt_bvh_uv*>(out.devUvs));
-        REFIT_TRY(hipGetLastError());
-        REFIT_TRY(hipStreamSynchronize(stream)); // byGid dies with this scope
+        DeviceBuffer byGid(sizeof(crt_bvh_uv) * d.nTris);
+        out.uvs = DeviceBuffer(recordBytes(sizeof(crt_bvh_uv), d.nTris));
+        hipLaunchKernelGGL(uvScatterKernel, grd, blk, 0, stream, oldTris, static_cast<const crt_bvh_uv*>(oldUvs), d.nTris, byGid.as<crt_bvh_uv>());
+        hipLaunchKernelGGL(uvGatherKernel, grd, blk, 0, stream, out.tris.as<const crt_bvh_tri>(), byGid.as<const crt_bvh_uv>(), d.nTris,
+                           out.uvs.as<crt_bvh_uv>());
+        HIP_THROW(hipGetLastError());
+        HIP_THROW(hipStreamSynchronize(stream)); // byGid dies with this scope
     }
-    REFIT_TRY(hipEventRecord(d.ev1, stream));
-    REFIT_TRY(hipStreamSynchronize(stream));
-    float ms = 0.f;
-    REFIT_TRY(hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    const double ms = d.timer.stopAndWait(stream);
     if (device_ms) *device_ms = ms;
-    setLevels(d, nullptr, static_cast<const crt_bvh_node*>(out.devNodes), out.nNodes, stream);
+    setLevels(d, nullptr, out.nodes.as<const crt_bvh_node>(), out.nNodes, stream);
     for (DynamicMesh& D : d.meshes) D.dirty = false;
     d.pending = false;
+    return out;
 }
 
 } // namespace crt

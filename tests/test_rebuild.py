@@ -335,11 +335,33 @@ def _fresh(pkg, sc, meshes, builder, textures=None):
         r2.close()
 
 
+def _road_scenes():
+    """Where the one-leaf host path, the hand-over between it and the device path and the slack behind the records can go wrong:
+    1, 4 (= kLeafMax), 5 (the smallest device build) and 9 triangles over two meshes, the first with normals and uvs, the second
+    with neither (and, for one triangle, with nothing at all); and the 9 triangles again with a NaN corner in one of them."""
+    f = np.float32
+    rng = np.random.default_rng(11)
+
+    def mesh(n, full):
+        v = (rng.uniform(-3, 3, (n, 1, 3)) + rng.uniform(-0.5, 0.5, (n, 3, 3))).astype(f).reshape(-1, 3)
+        m = {"vertices": v, "triangles": np.arange(3 * n, dtype=np.uint32).reshape(-1, 3)}
+        if full:
+            m["normals"] = rng.normal(size=(3 * n, 3)).astype(f)
+            m["uvs"] = rng.random((3 * n, 3)).astype(f)
+        return m
+
+    out = [{"meshes": [mesh((n + 1) // 2, True), mesh(n // 2, False)], "lights": [], "materials": []} for n in (1, 4, 5, 9)]
+    inert = [dict(m) for m in out[-1]["meshes"]]
+    inert[0]["vertices"] = inert[0]["vertices"].copy()
+    inert[0]["vertices"][7, 1] = np.nan  # triangle 2 of the first mesh
+    return out + [{"meshes": inert, "lights": [], "materials": []}]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("builder", [LBVH, PLOC])
 def test_rebuild_without_changes_reproduces_the_upload(pkg, scenes, renderer, builder):
     r = renderer
-    for sc in (scenes.textured_cornell(), _with_normals(scenes, scenes.displaced_sphere(n_lat=40, n_lon=40)), _chain()):
+    for sc in [scenes.textured_cornell(), _with_normals(scenes, scenes.displaced_sphere(n_lat=40, n_lon=40)), _chain()] + _road_scenes():
         r.set_option("gpu_build", 1)
         r.set_option("gpu_builder", builder)
         r.upload(sc["meshes"], sc["lights"], sc["materials"], sc.get("textures"), dynamic=True)
@@ -349,6 +371,34 @@ def test_rebuild_without_changes_reproduces_the_upload(pkg, scenes, renderer, bu
         assert _export(r) == before
     r.set_option("gpu_builder", LBVH)
     r.set_option("gpu_build", 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("gpu_build,builder", [(1, LBVH), (1, PLOC), (0, LBVH)], ids=["lbvh", "ploc", "host-sah"])
+def test_every_road_to_hbm_gives_the_same_bytes(pkg, renderer, gpu_build, builder):
+    """A static upload, a dynamic upload and a dynamic upload followed by an identity update_vertices + refit leave the same binary,
+    wide and quantised nodes, plane table, records and uvs in HBM, for both GPU builders and the host SAH tree.  (The rebuild with
+    nothing pending is held to the dynamic upload by test_rebuild_without_changes_reproduces_the_upload, on the same scenes.)"""
+    r = renderer
+    r.set_option("gpu_build", gpu_build)
+    r.set_option("gpu_builder", builder)
+    try:
+        for sc in _road_scenes():
+            meshes = sc["meshes"]
+            what = "%d triangles" % sum(len(m["triangles"]) for m in meshes)
+            r.upload(meshes, sc["lights"], sc["materials"])
+            static = _export(r)
+            assert static[3] is not None, what + ": uv records"
+            r.upload(meshes, sc["lights"], sc["materials"], dynamic=True)
+            assert _export(r) == static, what + ": dynamic upload"
+            for i, m in enumerate(meshes):
+                if len(m["vertices"]):
+                    r.update_vertices(i, m["vertices"], m.get("normals"))
+            r.refit()
+            assert _export(r) == static, what + ": identity refit"
+    finally:
+        r.set_option("gpu_builder", LBVH)
+        r.set_option("gpu_build", 0)
 
 
 def _shaded_outputs(r, rays, w, h):
