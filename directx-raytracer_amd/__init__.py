@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "crt_motion_snapshot", "crt_previous_points_device", "crt_previous_points", "crt_frame_motion_device", "crt_frame_motion",
     "crt_temporal_accumulate_motion_device", "crt_temporal_accumulate_motion",
     "crt_temporal_variance_device", "crt_temporal_variance", "crt_denoise_variance_device", "crt_denoise_variance",
+    "crt_trace_rays_backward_device", "crt_trace_rays_backward", "crt_closest_points_backward_device", "crt_closest_points_backward",
 ]
 
 
@@ -288,6 +289,10 @@ def lib():
         "crt_temporal_variance": (C.c_int, [vp, u32, u32] + [vp] * 15),
         "crt_denoise_variance_device": (C.c_int, [vp, u32, u32] + [vp] * 9),
         "crt_denoise_variance": (C.c_int, [vp, u32, u32] + [vp] * 9),
+        "crt_trace_rays_backward_device": (C.c_int, [vp, u32] + [vp] * 10),
+        "crt_trace_rays_backward": (C.c_int, [vp, u32] + [vp] * 10),
+        "crt_closest_points_backward_device": (C.c_int, [vp, u32] + [vp] * 8),
+        "crt_closest_points_backward": (C.c_int, [vp, u32] + [vp] * 8),
     }
     assert set(sig) == set(ABI_SYMBOLS)
     for name, (res, args) in sig.items():
@@ -723,6 +728,135 @@ def inside_length(offsets, t):
     return out
 
 
+_torch_fns = None
+
+
+def _torch_functions():
+    """(ray function, point function): the torch.autograd.Functions behind Renderer.trace_rays_torch / closest_points_torch, made at
+    the first call -- torch is not needed to import this package"""
+    global _torch_fns
+    if _torch_fns is not None:
+        return _torch_fns
+    import torch
+
+    def records(a, width, what):
+        if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.float32 and a.dim() == 2 and a.shape[1] == width):
+            raise ValueError("%s must be an (N, %d) float32 CUDA tensor" % (what, width))
+        return a.detach().contiguous()
+
+    def forward_setup(ctx, renderer, meshes, verts):
+        shapes = getattr(renderer, "_mesh_shapes", [])
+        if len(set(meshes)) != len(meshes) or any(not 0 <= m < len(shapes) for m in meshes):
+            raise ValueError("vertices: the keys must be distinct mesh ordinals of the uploaded scene")
+        for m, v in zip(meshes, verts):
+            if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 and tuple(v.shape) == (shapes[m][0], 3)):
+                raise ValueError("vertices[%d] must be a (%d, 3) float32 CUDA tensor" % (m, shapes[m][0]))
+        torch.cuda.current_stream().synchronize()  # the inputs are ready
+        for m, v in zip(meshes, verts):
+            renderer.update_vertices(m, v.detach().contiguous())
+        ctx.renderer, ctx.meshes = renderer, meshes
+        ctx.set_materialize_grads(False)
+
+    def ptr(a):
+        return None if a is None else a.data_ptr()
+
+    def grad_in(g, like):
+        return None if g is None else g.to(torch.float32).expand_as(like).contiguous()
+
+    def vertex_grads(ctx, grad_xyz):
+        """per mesh of the forward call the rest-vertex gradient: its rows of grad_xyz times the transposed 3x3 of its transform"""
+        r = ctx.renderer
+        starts = np.cumsum([0] + [nv for nv, _ in r._mesh_shapes])
+        out = []
+        for k, m in enumerate(ctx.meshes):
+            if grad_xyz is None or not ctx.needs_input_grad[3 + k]:
+                out.append(None)
+                continue
+            g = grad_xyz[starts[m]:starts[m + 1]]
+            tr = r._mesh_transforms[m]
+            if tr is not None:  # world = M rest + t: dL/drest = M^T dL/dworld, row by row g M
+                g = g @ torch.from_numpy(np.ascontiguousarray(tr[:, :3])).to(g.device)
+            out.append(g)
+        return out
+
+    def check_serial(ctx):
+        if ctx.serial != ctx.renderer._geom_serial:
+            raise CrtError("backward: the scene's vertices or transforms changed since the forward pass")
+
+    class RayFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, renderer, rays, meshes, *verts):
+            r = records(rays, 8, "rays")
+            forward_setup(ctx, renderer, meshes, verts)
+            n = r.shape[0]
+            t = torch.empty(n, dtype=torch.float32, device=r.device)
+            uv = torch.empty((n, 2), dtype=torch.float32, device=r.device)
+            inst = torch.empty(n, dtype=torch.int32, device=r.device)
+            prim = torch.empty(n, dtype=torch.int32, device=r.device)
+            renderer.trace_rays_device(n, ptr(r), ptr(t), ptr(uv), ptr(inst), ptr(prim))
+            renderer.synchronize()
+            ctx.serial = renderer._geom_serial
+            ctx.save_for_backward(r, t, uv, inst, prim)
+            ctx.mark_non_differentiable(inst, prim)
+            return t, uv, inst, prim
+
+        @staticmethod
+        def backward(ctx, g_t, g_uv, _g_inst, _g_prim):
+            r, t, uv, inst, prim = ctx.saved_tensors
+            n = r.shape[0]
+            none = (None, None, None) + (None,) * len(ctx.meshes)
+            want_rays, want_xyz = ctx.needs_input_grad[1], any(ctx.needs_input_grad[3:])
+            if (g_t is None and g_uv is None) or not (want_rays or want_xyz):
+                return none
+            check_serial(ctx)
+            g_t, g_uv = grad_in(g_t, t), grad_in(g_uv, uv)
+            grad_rays = torch.zeros((n, 8), dtype=torch.float32, device=r.device) if want_rays else None
+            grad_xyz = torch.zeros((ctx.renderer._total_vertices(), 3), dtype=torch.float32, device=r.device) if want_xyz else None
+            torch.cuda.current_stream().synchronize()  # the incoming gradients are ready
+            ctx.renderer.trace_rays_backward_device(n, ptr(r), ptr(inst), ptr(prim), ptr(t), ptr(uv), ptr(g_t), ptr(g_uv), ptr(grad_rays),
+                                                    ptr(grad_xyz))
+            ctx.renderer.synchronize()
+            return (None, grad_rays, None) + tuple(vertex_grads(ctx, grad_xyz))
+
+    class PointFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, renderer, points, meshes, *verts):
+            p = records(points, 4, "points")
+            forward_setup(ctx, renderer, meshes, verts)
+            n = p.shape[0]
+            dist = torch.empty(n, dtype=torch.float32, device=p.device)
+            point = torch.empty((n, 3), dtype=torch.float32, device=p.device)
+            uv = torch.empty((n, 2), dtype=torch.float32, device=p.device)
+            inst = torch.empty(n, dtype=torch.int32, device=p.device)
+            prim = torch.empty(n, dtype=torch.int32, device=p.device)
+            renderer.closest_points_device(n, ptr(p), ptr(dist), ptr(point), ptr(uv), ptr(inst), ptr(prim))
+            renderer.synchronize()
+            ctx.serial = renderer._geom_serial
+            ctx.save_for_backward(p, uv, inst, prim)
+            ctx.mark_non_differentiable(point, uv, inst, prim)
+            return dist, point, uv, inst, prim
+
+        @staticmethod
+        def backward(ctx, g_dist, *_rest):
+            p, uv, inst, prim = ctx.saved_tensors
+            n = p.shape[0]
+            none = (None, None, None) + (None,) * len(ctx.meshes)
+            want_points, want_xyz = ctx.needs_input_grad[1], any(ctx.needs_input_grad[3:])
+            if g_dist is None or not (want_points or want_xyz):
+                return none
+            check_serial(ctx)
+            g_dist = grad_in(g_dist, p[:, 0])
+            grad_points = torch.zeros((n, 4), dtype=torch.float32, device=p.device) if want_points else None
+            grad_xyz = torch.zeros((ctx.renderer._total_vertices(), 3), dtype=torch.float32, device=p.device) if want_xyz else None
+            torch.cuda.current_stream().synchronize()
+            ctx.renderer.closest_points_backward_device(n, ptr(p), ptr(inst), ptr(prim), ptr(uv), ptr(g_dist), ptr(grad_points), ptr(grad_xyz))
+            ctx.renderer.synchronize()
+            return (None, grad_points, None) + tuple(vertex_grads(ctx, grad_xyz))
+
+    _torch_fns = (RayFunction, PointFunction)
+    return _torch_fns
+
+
 class Renderer:
     """crt_ctx handle: the DXRTRenderer surface over HIP. Raises CrtError when no MI355X / HIP device is usable."""
 
@@ -734,6 +868,7 @@ class Renderer:
             raise CrtError("crt_create rc=%d: %s" % (rc, L.crt_last_error(None).decode()))
         self.h = h
         self._keep = []
+        self._geom_serial = 0  # bumped whenever vertices or transforms may have changed (the torch layer's backward checks it)
 
     def close(self):
         if getattr(self, "h", None):
@@ -793,6 +928,8 @@ class Renderer:
             marr[i].texture = int(m.get("texture", -1))
         self._ok(lib().crt_upload_scene(self.h, mv, len(meshes), larr, len(lights), marr, len(materials)), "crt_upload_scene")
         self._mesh_shapes = [(int(mv[i].n_vertices), bool(mv[i].normals)) for i in range(len(meshes))]
+        self._geom_serial += 1
+        self._mesh_transforms = [None] * len(meshes)  # per mesh the 3x4 of set_mesh_transform (None = identity), for the torch layer
         self.set_textures(list(textures) if textures else [])
 
     def upload_scene(self, scene, dynamic=False):
@@ -804,11 +941,14 @@ class Renderer:
             self._ok(lib().crt_scene_mesh(scene.h, i, C.byref(mv)), "crt_scene_mesh")
             shapes.append((int(mv.n_vertices), bool(mv.normals)))
         self._mesh_shapes = shapes
+        self._mesh_transforms = [None] * len(shapes)
+        self._geom_serial += 1
 
     # ---- dynamic geometry (include/crt_hip.h): scenes uploaded with dynamic=True
     def update_vertices(self, mesh, xyz, normals=None):
         """new rest vertices (and normals) of a mesh: numpy arrays (host), or contiguous float32 torch tensors on the GPU (device
         form; made ready on the current stream first).  Applied by the next refit."""
+        self._geom_serial += 1
         try:
             import torch
             on_device = isinstance(xyz, torch.Tensor) and xyz.is_cuda
@@ -831,6 +971,7 @@ class Renderer:
         """m: 3x4 row-major, or 4x4 whose last row is 0 0 0 1; None = identity"""
         if m is None:
             self._ok(lib().crt_set_mesh_transform(self.h, int(mesh), None), "crt_set_mesh_transform")
+            self._remember_transform(mesh, None)
             return
         a = np.asarray(m, dtype=np.float32)
         if a.shape == (4, 4):
@@ -841,6 +982,15 @@ class Renderer:
             raise ValueError("set_mesh_transform: 3x4 or 4x4 matrix expected, got %s" % (a.shape,))
         a = np.ascontiguousarray(a)
         self._ok(lib().crt_set_mesh_transform(self.h, int(mesh), a.ctypes.data), "crt_set_mesh_transform")
+        self._remember_transform(mesh, None if np.array_equal(a, np.eye(3, 4, dtype=np.float32)) else a.copy())
+
+    def _remember_transform(self, mesh, m):
+        """the Python side's copy of a mesh's 3x4 (None = identity): trace_rays_torch / closest_points_torch turn world-vertex
+        gradients into rest-vertex gradients with it"""
+        self._geom_serial += 1
+        kept = getattr(self, "_mesh_transforms", None)
+        if kept is not None and 0 <= int(mesh) < len(kept):
+            kept[int(mesh)] = m
 
     def refit(self):
         """apply pending updates now; returns the refit's device time in ms (0 when nothing was pending)"""
@@ -1305,6 +1455,93 @@ class Renderer:
         self._ok(lib().crt_closest_points_device(self.h, int(n), d_points, d_dist, d_point, d_uv, d_inst, d_prim,
                                                  C.byref(st) if stats else None), "crt_closest_points_device")
         return st.as_dict() if stats else None
+
+    # ---- gradients (include/crt_hip.h, "gradients"): the backward pass of trace_rays and closest_points; dynamic scenes only
+    def _total_vertices(self):
+        return sum(nv for nv, _ in getattr(self, "_mesh_shapes", []))
+
+    def trace_rays_backward(self, rays, inst, prim, t, uv, grad_t=None, grad_uv=None, want=("grad_rays", "grad_xyz")):
+        """gradients of a loss on the hits (inst, prim, t, uv) of `rays` (host buffers, synchronous).  grad_t (N,) and grad_uv
+        (N, 2) are dL/dt and dL/d(u, v); one of them may be None (zeros).  Returns a dict of the wanted arrays: grad_rays (N, 8)
+        float32 {dL/do, 0, dL/dd, 0} and grad_xyz (total vertices, 3) float32, the gradient with respect to the world vertices of
+        all meshes back to back in upload order."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = len(r)
+        i = np.ascontiguousarray(inst, dtype=np.uint32).reshape(-1)
+        q = np.ascontiguousarray(prim, dtype=np.uint32).reshape(-1)
+        tt = np.ascontiguousarray(t, dtype=np.float32).reshape(-1)
+        u = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+        gt = None if grad_t is None else np.ascontiguousarray(grad_t, dtype=np.float32).reshape(-1)
+        gu = None if grad_uv is None else np.ascontiguousarray(grad_uv, dtype=np.float32).reshape(-1, 2)
+        if not all(len(a) == n for a in (i, q, tt, u, gt, gu) if a is not None):
+            raise ValueError("rays, inst, prim, t, uv and the gradients must hold one record per ray")
+        out = {}
+        if "grad_rays" in want:
+            out["grad_rays"] = np.zeros((n, 8), dtype=np.float32)
+        if "grad_xyz" in want:
+            out["grad_xyz"] = np.zeros((self._total_vertices(), 3), dtype=np.float32)
+
+        def p(a):
+            return None if a is None else a.ctypes.data
+        self._ok(lib().crt_trace_rays_backward(self.h, n, p(r), p(i), p(q), p(tt), p(u), p(gt), p(gu), p(out.get("grad_rays")),
+                                               p(out.get("grad_xyz")), None), "crt_trace_rays_backward")
+        return out
+
+    def trace_rays_backward_device(self, n, d_rays, d_inst, d_prim, d_t, d_uv, d_grad_t=None, d_grad_uv=None, d_grad_rays=None, d_grad_xyz=None,
+                                   stats=False):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_trace_rays_backward_device(self.h, int(n), d_rays, d_inst, d_prim, d_t, d_uv, d_grad_t, d_grad_uv, d_grad_rays, d_grad_xyz,
+                                                      C.byref(st) if stats else None), "crt_trace_rays_backward_device")
+        return st.as_dict() if stats else None
+
+    def closest_points_backward(self, points, inst, prim, uv, grad_dist, want=("grad_points", "grad_xyz")):
+        """gradients of a loss on the distances of `points` to their closest surface points (inst, prim, uv) (host buffers,
+        synchronous).  grad_dist (N,) is dL/ddist.  Returns a dict of the wanted arrays: grad_points (N, 4) float32 {dL/dp, 0} and
+        grad_xyz as trace_rays_backward."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
+        n = len(pts)
+        i = np.ascontiguousarray(inst, dtype=np.uint32).reshape(-1)
+        q = np.ascontiguousarray(prim, dtype=np.uint32).reshape(-1)
+        u = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+        g = np.ascontiguousarray(grad_dist, dtype=np.float32).reshape(-1)
+        if not all(len(a) == n for a in (i, q, u, g)):
+            raise ValueError("points, inst, prim, uv and grad_dist must hold one record per point")
+        out = {}
+        if "grad_points" in want:
+            out["grad_points"] = np.zeros((n, 4), dtype=np.float32)
+        if "grad_xyz" in want:
+            out["grad_xyz"] = np.zeros((self._total_vertices(), 3), dtype=np.float32)
+
+        def p(a):
+            return None if a is None else a.ctypes.data
+        self._ok(lib().crt_closest_points_backward(self.h, n, p(pts), p(i), p(q), p(u), p(g), p(out.get("grad_points")), p(out.get("grad_xyz")), None),
+                 "crt_closest_points_backward")
+        return out
+
+    def closest_points_backward_device(self, n, d_points, d_inst, d_prim, d_uv, d_grad_dist, d_grad_points=None, d_grad_xyz=None, stats=False):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_closest_points_backward_device(self.h, int(n), d_points, d_inst, d_prim, d_uv, d_grad_dist, d_grad_points, d_grad_xyz,
+                                                          C.byref(st) if stats else None), "crt_closest_points_backward_device")
+        return st.as_dict() if stats else None
+
+    def trace_rays_torch(self, rays, vertices):
+        """trace_rays with a torch.autograd graph behind it.  rays: (N, 8) float32 CUDA tensor (may require grad); vertices: dict
+        {mesh: (nv, 3) float32 CUDA tensor} of REST vertices (may require grad); the scene was uploaded with dynamic=True.  The
+        forward pass hands every entry to update_vertices and traces; it returns (t, uv, inst, prim): t (N,) and uv (N, 2) carry
+        the graph, inst / prim are int32 (a miss reads -1, t = the ray's tmax) and do not.  backward() gives the rays' gradient
+        (tmin / tmax columns zero) and, per mesh named in `vertices`, the gradient with respect to its rest vertices (the world
+        gradient times the transposed 3x3 of the mesh's transform).  Misses get zero gradient.  Call backward() before the
+        vertices or transforms change again: it reads the scene as it stands."""
+        return _torch_functions()[0].apply(self, rays, tuple(int(m) for m in vertices), *vertices.values())
+
+    def closest_points_torch(self, points, vertices):
+        """closest_points with a torch.autograd graph behind it.  points: (N, 4) float32 CUDA tensor {x, y, z, rmax} (may require
+        grad); vertices as trace_rays_torch.  Returns (dist, point, uv, inst, prim); only dist carries the graph (multiply it by a
+        constant sign for a signed distance).  backward() gives the points' gradient (rmax column zero) and the rest-vertex
+        gradients as trace_rays_torch."""
+        return _torch_functions()[1].apply(self, points, tuple(int(m) for m in vertices), *vertices.values())
 
     def count_hits_device(self, n, d_rays, d_count, stats=False):
         st = FrameStats() if stats else None

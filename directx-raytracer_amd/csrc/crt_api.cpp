@@ -254,6 +254,10 @@ struct crt_ctx {
     // tools/list_hits_bench.py, lists of 0 .. 1024 hits): 2.89 ms from 4 to 24, 2.92 at 32, 2.93 at 64 (all within the 1 %
     // spread of the rounds), 3.02 at 256, 3.93 with every list on one lane.  Any value up to ~64 would do.
     uint32_t tuneListShortMax = 24;
+    // crt_trace_rays_backward* / crt_closest_points_backward*: the float64 vertex sums of a dynamic scene, 3 doubles per vertex.
+    // Allocated by the first call that wants vertex gradients, freed with the scene (freeScene); calls share it in stream order
+    double* dGradSum = nullptr;
+    Fence gradUsed; // the last call that used the sums, on the stream it ran on
     hipEvent_t evList[5] = {};    // a listing with stats: before the count, after count / scan / fill / sort
     double listPhaseMs[4] = {};   // count, scan, fill, sort + resolve of the last listing that was given stats (crt_debug_list_phases)
 };
@@ -287,6 +291,8 @@ void freeScene(crt_ctx* c)
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
+    if (c->dGradSum) (void)hipFree(c->dGradSum);
+    c->dGradSum = nullptr;
     delete c->dyn;
     c->dyn = nullptr;
     c->haveScene = false;
@@ -1080,6 +1086,7 @@ void crt_destroy(crt_ctx* c)
     if (c->dTimeline) (void)hipFree(c->dTimeline);
     if (c->dAccum) (void)hipFree(c->dAccum);
     c->accumUsed.destroy();
+    c->gradUsed.destroy();
     if (c->dRayStage) (void)hipFree(c->dRayStage);
     if (c->dListStage) (void)hipFree(c->dListStage);
     for (hipEvent_t e : c->evList)
@@ -3149,6 +3156,217 @@ int crt_frame_motion(crt_ctx* c, uint32_t w, uint32_t h, float* prevPoint, crt_f
     if ((rc = runFrameMotion(c, w, h, c->dRayStage, stats)) != CRT_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(prevPoint, c->dRayStage, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    stampTotal(stats, t0);
+    return CRT_OK;
+}
+
+// ------------------------------------------------------------------------------------------- gradients (grad_kernels.hip)
+namespace {
+
+// The vertex gradient of a backward call: the float64 sums (allocated on first use), zeroed in front of the record kernel and
+// rounded into d_grad_xyz behind it.  A call on another stream than the last one's waits for it on the GPU: the sums are the
+// context's, not the stream's.  gradSumsZero and gradSumsEnd return HIP error codes, as the launches between them
+int gradSumsReserve(crt_ctx* c, void* d_grad_xyz, double*& sums)
+{
+    sums = nullptr;
+    const size_t bytes = sizeof(double) * 3 * static_cast<size_t>(c->dyn->nVerts);
+    if (!d_grad_xyz || bytes == 0u) return CRT_OK;
+    if (!c->dGradSum) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->dGradSum), bytes));
+    sums = c->dGradSum;
+    return CRT_OK;
+}
+
+int gradSumsZero(crt_ctx* c, double* sums)
+{
+    if (!sums) return static_cast<int>(hipSuccess);
+    if (const hipError_t e = c->gradUsed.wait(c->stream, false)) return static_cast<int>(e);
+    return static_cast<int>(hipMemsetAsync(sums, 0, sizeof(double) * 3 * static_cast<size_t>(c->dyn->nVerts), c->stream));
+}
+
+int gradSumsEnd(crt_ctx* c, const double* sums, void* d_grad_xyz)
+{
+    if (!sums) return static_cast<int>(hipSuccess);
+    const int hrc = crt::launchGradFinalize(sums, static_cast<float*>(d_grad_xyz), 3 * static_cast<size_t>(c->dyn->nVerts), c->stream);
+    return hrc != 0 ? hrc : static_cast<int>(c->gradUsed.record(c->stream));
+}
+
+struct RayGradCall {
+    const void *rays, *inst, *prim, *t, *uv, *gradT, *gradUv;
+    void *gradRays, *gradXyz;
+};
+struct PointGradCall {
+    const void *points, *inst, *prim, *uv, *gradDist;
+    void *gradPoints, *gradXyz;
+};
+
+int runRayGrad(crt_ctx* c, const char* what, uint32_t n, const RayGradCall& a, crt_frame_stats* stats)
+{
+    crt::RayGradParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.table = c->dyn->dTable;
+    p.nMeshes = static_cast<uint32_t>(c->dyn->meshes.size());
+    p.n = n;
+    p.world = c->dyn->dWorldXyz;
+    p.idx = c->dyn->dIdx;
+    p.rays = static_cast<const float*>(a.rays);
+    p.inst = static_cast<const uint32_t*>(a.inst);
+    p.prim = static_cast<const uint32_t*>(a.prim);
+    p.t = static_cast<const float*>(a.t);
+    p.uv = static_cast<const float*>(a.uv);
+    p.gradT = static_cast<const float*>(a.gradT);
+    p.gradUv = static_cast<const float*>(a.gradUv);
+    p.gradRays = static_cast<float*>(a.gradRays);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = gradSumsReserve(c, a.gradXyz, p.sums)) return rc;
+    const auto launch = [&] {
+        int hrc = gradSumsZero(c, p.sums);
+        if (hrc == 0) hrc = crt::launchRayGrad(p, c->stream);
+        return hrc != 0 ? hrc : gradSumsEnd(c, p.sums, a.gradXyz);
+    };
+    if (const int rc = runTimed(c, what, stats, launch)) return rc;
+    if (stats) stats->rays_primary = n;
+    return CRT_OK;
+}
+
+int runPointGrad(crt_ctx* c, const char* what, uint32_t n, const PointGradCall& a, crt_frame_stats* stats)
+{
+    crt::PointGradParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.table = c->dyn->dTable;
+    p.nMeshes = static_cast<uint32_t>(c->dyn->meshes.size());
+    p.n = n;
+    p.world = c->dyn->dWorldXyz;
+    p.idx = c->dyn->dIdx;
+    p.points = static_cast<const float*>(a.points);
+    p.inst = static_cast<const uint32_t*>(a.inst);
+    p.prim = static_cast<const uint32_t*>(a.prim);
+    p.uv = static_cast<const float*>(a.uv);
+    p.gradDist = static_cast<const float*>(a.gradDist);
+    p.gradPoints = static_cast<float*>(a.gradPoints);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = gradSumsReserve(c, a.gradXyz, p.sums)) return rc;
+    const auto launch = [&] {
+        int hrc = gradSumsZero(c, p.sums);
+        if (hrc == 0) hrc = crt::launchPointGrad(p, c->stream);
+        return hrc != 0 ? hrc : gradSumsEnd(c, p.sums, a.gradXyz);
+    };
+    if (const int rc = runTimed(c, what, stats, launch)) return rc;
+    if (stats) stats->rays_primary = n;
+    return CRT_OK;
+}
+
+int checkRayGrad(crt_ctx* c, const char* what, const RayGradCall& a)
+{
+    if (!a.rays || !a.inst || !a.prim || !a.t || !a.uv) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
+    if (!a.gradT && !a.gradUv) return fail(c, CRT_EINVAL, "%s: grad_t and grad_uv are both NULL", what);
+    if (!a.gradRays && !a.gradXyz) return fail(c, CRT_EINVAL, "%s: every output is NULL", what);
+    return CRT_OK;
+}
+
+int checkPointGrad(crt_ctx* c, const char* what, const PointGradCall& a)
+{
+    if (!a.points || !a.inst || !a.prim || !a.uv || !a.gradDist) return fail(c, CRT_EINVAL, "%s: NULL buffer", what);
+    if (!a.gradPoints && !a.gradXyz) return fail(c, CRT_EINVAL, "%s: every output is NULL", what);
+    return CRT_OK;
+}
+
+size_t gradXyzBytes(const crt_ctx* c) { return sizeof(float) * 3 * static_cast<size_t>(c->dyn->nVerts); }
+
+} // namespace
+
+int crt_trace_rays_backward_device(crt_ctx* c, uint32_t n, const void* d_rays, const void* d_inst, const void* d_prim, const void* d_t,
+                                   const void* d_uv, const void* d_grad_t, const void* d_grad_uv, void* d_grad_rays, void* d_grad_xyz,
+                                   crt_frame_stats* stats)
+{
+    const char* what = "crt_trace_rays_backward_device";
+    int rc = checkMotionScene(c, what);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n == 0u) { // nothing to look at, nothing launched
+        zeroStats(stats, t0);
+        return CRT_OK;
+    }
+    const RayGradCall a{ d_rays, d_inst, d_prim, d_t, d_uv, d_grad_t, d_grad_uv, d_grad_rays, d_grad_xyz };
+    if ((rc = checkRayGrad(c, what, a)) != CRT_OK) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_rays, d_grad_rays }, 16u)) != CRT_OK) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_uv, d_grad_uv }, 8u)) != CRT_OK) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_inst, d_prim, d_t, d_grad_t, d_grad_xyz }, 4u)) != CRT_OK) return rc;
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    if ((rc = runRayGrad(c, what, n, a, stats)) != CRT_OK) return rc;
+    stampTotal(stats, t0);
+    return CRT_OK;
+}
+
+// host buffers: staged through the context's query staging buffer {rays | inst | prim | t | uv | grad_t | grad_uv | grad_rays |
+// grad_xyz}; synchronous
+int crt_trace_rays_backward(crt_ctx* c, uint32_t n, const float* rays, const uint32_t* inst, const uint32_t* prim, const float* t, const float* uv,
+                            const float* grad_t, const float* grad_uv, float* grad_rays, float* grad_xyz, crt_frame_stats* stats)
+{
+    const char* what = "crt_trace_rays_backward";
+    int rc = checkMotionScene(c, what);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n == 0u) {
+        zeroStats(stats, t0);
+        return CRT_OK;
+    }
+    if ((rc = checkRayGrad(c, what, { rays, inst, prim, t, uv, grad_t, grad_uv, grad_rays, grad_xyz })) != CRT_OK) return rc;
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    const size_t nn = n;
+    const StagePlane planes[9] = { { rays, nullptr, nn * 32u }, { inst, nullptr, nn * 4u }, { prim, nullptr, nn * 4u }, { t, nullptr, nn * 4u },
+                                   { uv, nullptr, nn * 8u }, { grad_t, nullptr, nn * 4u }, { grad_uv, nullptr, nn * 8u },
+                                   { nullptr, grad_rays, nn * 32u }, { nullptr, grad_xyz, gradXyzBytes(c) } };
+    void* dev[9];
+    if ((rc = stageBegin(c, planes, 9, dev)) != CRT_OK) return rc;
+    if ((rc = runRayGrad(c, what, n, { dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], dev[8] }, stats)) != CRT_OK) return rc;
+    if ((rc = stageEnd(c, planes, 9, dev)) != CRT_OK) return rc;
+    stampTotal(stats, t0);
+    return CRT_OK;
+}
+
+int crt_closest_points_backward_device(crt_ctx* c, uint32_t n, const void* d_points, const void* d_inst, const void* d_prim, const void* d_uv,
+                                       const void* d_grad_dist, void* d_grad_points, void* d_grad_xyz, crt_frame_stats* stats)
+{
+    const char* what = "crt_closest_points_backward_device";
+    int rc = checkMotionScene(c, what);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n == 0u) {
+        zeroStats(stats, t0);
+        return CRT_OK;
+    }
+    const PointGradCall a{ d_points, d_inst, d_prim, d_uv, d_grad_dist, d_grad_points, d_grad_xyz };
+    if ((rc = checkPointGrad(c, what, a)) != CRT_OK) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_points, d_grad_points }, 16u)) != CRT_OK) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_uv }, 8u)) != CRT_OK) return rc;
+    if ((rc = checkDevicePointers(c, what, { d_inst, d_prim, d_grad_dist, d_grad_xyz }, 4u)) != CRT_OK) return rc;
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    if ((rc = runPointGrad(c, what, n, a, stats)) != CRT_OK) return rc;
+    stampTotal(stats, t0);
+    return CRT_OK;
+}
+
+// host buffers: staged {points | inst | prim | uv | grad_dist | grad_points | grad_xyz}; synchronous
+int crt_closest_points_backward(crt_ctx* c, uint32_t n, const float* points, const uint32_t* inst, const uint32_t* prim, const float* uv,
+                                const float* grad_dist, float* grad_points, float* grad_xyz, crt_frame_stats* stats)
+{
+    const char* what = "crt_closest_points_backward";
+    int rc = checkMotionScene(c, what);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (n == 0u) {
+        zeroStats(stats, t0);
+        return CRT_OK;
+    }
+    if ((rc = checkPointGrad(c, what, { points, inst, prim, uv, grad_dist, grad_points, grad_xyz })) != CRT_OK) return rc;
+    if ((rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    const size_t nn = n;
+    const StagePlane planes[7] = { { points, nullptr, nn * 16u }, { inst, nullptr, nn * 4u }, { prim, nullptr, nn * 4u }, { uv, nullptr, nn * 8u },
+                                   { grad_dist, nullptr, nn * 4u }, { nullptr, grad_points, nn * 16u }, { nullptr, grad_xyz, gradXyzBytes(c) } };
+    void* dev[7];
+    if ((rc = stageBegin(c, planes, 7, dev)) != CRT_OK) return rc;
+    if ((rc = runPointGrad(c, what, n, { dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6] }, stats)) != CRT_OK) return rc;
+    if ((rc = stageEnd(c, planes, 7, dev)) != CRT_OK) return rc;
     stampTotal(stats, t0);
     return CRT_OK;
 }

@@ -349,6 +349,42 @@ struct PreviousPointsParams {
     float* point;                 // 3 floats per record
 };
 int launchPreviousPoints(const PreviousPointsParams& p, ihipStream_t* stream);
+// gradients of the closest-hit and closest-point queries (grad_kernels.hip; crt_trace_rays_backward*, crt_closest_points_backward*):
+// one lane per record, the triangle's current world vertices gathered as above, the vertex contributions added to `sums`
+struct RayGradParams {
+    const void* table;            // MeshEntry per mesh + terminator (mesh_table.hip.h)
+    uint32_t nMeshes;
+    uint32_t n;                   // records
+    const float* world;           // 3 floats per vertex: the current world vertices
+    const uint32_t* idx;          // 3 per triangle, mesh-local
+    const float* rays;            // 8 floats per record, 16-byte aligned
+    const uint32_t* inst;         // per record, as crt_trace_rays* writes them
+    const uint32_t* prim;
+    const float* t;
+    const float* uv;              // 2 floats per record, 8-byte aligned
+    const float* gradT;           // dL/dt per record; null: zeros
+    const float* gradUv;          // dL/du, dL/dv per record, 8-byte aligned; null: zeros
+    float* gradRays;              // 8 floats per record {dL/do, 0, dL/dd, 0}, 16-byte aligned; may be null
+    double* sums;                 // 3 doubles per vertex, zeroed by the caller; null: no vertex gradient, no atomics
+};
+struct PointGradParams {
+    const void* table;
+    uint32_t nMeshes;
+    uint32_t n;
+    const float* world;
+    const uint32_t* idx;
+    const float* points;          // 4 floats per record, 16-byte aligned
+    const uint32_t* inst;         // per record, as crt_closest_points* writes them
+    const uint32_t* prim;
+    const float* uv;
+    const float* gradDist;        // dL/ddist per record
+    float* gradPoints;            // 4 floats per record {dL/dp, 0}, 16-byte aligned; may be null
+    double* sums;
+};
+int launchRayGrad(const RayGradParams& p, ihipStream_t* stream);
+int launchPointGrad(const PointGradParams& p, ihipStream_t* stream);
+// out[i] = float(sums[i]), n values: each float64 sum rounded once
+int launchGradFinalize(const double* sums, float* out, size_t n, ihipStream_t* stream);
 // exhaustive check of the triangle test's reciprocal (ray_kernels.hip rcpCheckKernel) into out[0..6] (device memory, zeroed
 // except out[6] = ~0 by the caller)
 int launchRcpCheck(unsigned long long* out, ihipStream_t* stream);

@@ -287,6 +287,46 @@ void Renderer::frameMotion(std::vector<float>& prevPoint)
     check(crt_frame_motion(ctx, width, height, prevPoint.data(), nullptr), "crt_frame_motion");
 }
 
+static size_t sceneVertexFloats(const Scene& scene)
+{
+    size_t n = 0;
+    for (const Mesh& m : scene.getObjects()) n += m.getVertices().size();
+    return 3 * n;
+}
+
+void Renderer::traceRaysBackward(const float* rays, const RayHit* hits, const float* gradT, const float* gradUv, size_t n, std::vector<float>* gradRays,
+                                 std::vector<float>* gradXyz)
+{
+    if (!ctx || !scene) throw std::runtime_error("traceRaysBackward before prepareForRendering");
+    if (n > UINT32_MAX) throw std::runtime_error("traceRaysBackward: more than 2^32 - 1 records");
+    std::vector<uint32_t> inst(n), prim(n);
+    std::vector<float> t(n), uv(2 * n);
+    for (size_t i = 0; i < n; i++) {
+        inst[i] = hits[i].inst;
+        prim[i] = hits[i].prim;
+        t[i] = hits[i].t;
+        uv[2 * i] = hits[i].u;
+        uv[2 * i + 1] = hits[i].v;
+    }
+    if (gradRays) gradRays->assign(8 * n, 0.0f);
+    if (gradXyz) gradXyz->assign(sceneVertexFloats(*scene), 0.0f);
+    check(crt_trace_rays_backward(ctx, static_cast<uint32_t>(n), rays, inst.data(), prim.data(), t.data(), uv.data(), gradT, gradUv,
+                                  gradRays ? gradRays->data() : nullptr, gradXyz ? gradXyz->data() : nullptr, nullptr),
+          "crt_trace_rays_backward");
+}
+
+void Renderer::closestPointsBackward(const float* points, const uint32_t* inst, const uint32_t* prim, const float* uv, const float* gradDist, size_t n,
+                                     std::vector<float>* gradPoints, std::vector<float>* gradXyz)
+{
+    if (!ctx || !scene) throw std::runtime_error("closestPointsBackward before prepareForRendering");
+    if (n > UINT32_MAX) throw std::runtime_error("closestPointsBackward: more than 2^32 - 1 records");
+    if (gradPoints) gradPoints->assign(4 * n, 0.0f);
+    if (gradXyz) gradXyz->assign(sceneVertexFloats(*scene), 0.0f);
+    check(crt_closest_points_backward(ctx, static_cast<uint32_t>(n), points, inst, prim, uv, gradDist, gradPoints ? gradPoints->data() : nullptr,
+                                      gradXyz ? gradXyz->data() : nullptr, nullptr),
+          "crt_closest_points_backward");
+}
+
 void Renderer::temporalFrame(const crt_temporal_params* params, bool motion)
 {
     const size_t n = static_cast<size_t>(width) * height;

@@ -108,6 +108,17 @@ public:
     void previousPoints(const uint32_t* inst, const uint32_t* prim, const float* uv, size_t n, std::vector<float>& points);
     // crt_frame_motion (synchronous): the previous points of the pixel-centre camera rays, width * height * 3 floats
     void frameMotion(std::vector<float>& prevPoint);
+    // crt_trace_rays_backward (synchronous; needs a dynamic scene): the gradients of a loss on the hits traceRays reported for
+    // `rays` -- gradT: dL/dt per record, gradUv: dL/du, dL/dv per record, either may be nullptr (zeros), not both -- with respect
+    // to the rays (gradRays: 8 floats per record {dL/do, 0, dL/dd, 0}) and to the world vertices (gradXyz: 3 floats per vertex,
+    // the scene's meshes back to back).  Either output may be nullptr, not both
+    void traceRaysBackward(const float* rays, const RayHit* hits, const float* gradT, const float* gradUv, size_t n, std::vector<float>* gradRays,
+                           std::vector<float>* gradXyz);
+    // crt_closest_points_backward (synchronous; needs a dynamic scene): the gradients of a loss on the distances crt_closest_points
+    // reported for `points` (4 floats per record) at the surface points (inst, prim, {u, v}) -- gradDist: dL/ddist per record --
+    // with respect to the points (gradPoints: 4 floats per record {dL/dp, 0}) and to the world vertices (gradXyz, as above)
+    void closestPointsBackward(const float* points, const uint32_t* inst, const uint32_t* prim, const float* uv, const float* gradDist, size_t n,
+                               std::vector<float>* gradPoints, std::vector<float>* gradXyz);
     void resetTemporal() { haveHistory = false; }
     // temporalAccumulate with luminance moments (crt_temporal_variance, synchronous): momPrev / momNext hold 2 floats per pixel
     // beside the history records (momPrev is nullptr exactly when histPrev is), variance receives 1 float per pixel; prevPoint:

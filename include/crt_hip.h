@@ -876,6 +876,71 @@ int crt_temporal_accumulate_motion(crt_ctx* ctx, uint32_t width, uint32_t height
                                    const float* hist_prev, float* hist_next, float* out, const crt_temporal_params* params,
                                    crt_frame_stats* stats);
 
+/* ---- gradients: the backward pass of crt_trace_rays* and crt_closest_points* (no reference counterpart; what a differentiable
+ * renderer's ray cast gives a fitting loop).  A caller moves the vertices (crt_update_vertices*), queries, forms a loss on t / uv
+ * or on dist and gets dL/d(record) and dL/d(vertex) back: fitting a mesh to depth or lidar returns, pose estimation, training
+ * against a distance field.  Dynamic scenes only (option "dynamic"): the world vertices by vertex, the mesh-local indices and the
+ * mesh table are what such a scene keeps in HBM.
+ * - Inputs, n records each: the ray or point records of the forward call, and inst / prim / t / uv (points: inst / prim / uv)
+ *   exactly as the forward call wrote them -- or edited: nothing is traced again, a record names its triangle by (inst, prim).
+ *   grad_t (n floats) and grad_uv (n x 2 floats) are dL/dt and dL/d(u, v); either may be NULL (= zeros), not both.  grad_dist
+ *   (n floats) is dL/ddist.
+ * - Ray hit.  The hit satisfies o + t d = a + u (b - a) + v (c - a) with a, b, c the triangle's current world vertices (after
+ *   pending refits), d not normalised and t parametric, as crt_trace_rays defines them.  With e1 = b - a, e2 = c - a,
+ *   n = e1 x e2, w = 1 - u - v and g = (g_t, g_u, g_v), implicit differentiation gives
+ *       det = -(d . n),   lambda = (g_t n + g_u (d x e2) + g_v (e1 x d)) / det,
+ *       dL/do = lambda,  dL/dd = t lambda,  dL/da = -w lambda,  dL/db = -u lambda,  dL/dc = -v lambda.
+ *   grad_rays: 8 floats per record {dL/do, 0, dL/dd, 0}, the layout of the ray record (tmin and tmax get no gradient).
+ * - Closest point.  dist = |p - q| with q = w a + u b + v c the minimiser over the triangle; by the envelope theorem, with
+ *   nhat = (p - q) / dist and s = g nhat:  dL/dp = s,  dL/da = -w s,  dL/db = -u s,  dL/dc = -v s.  Only dist is differentiable
+ *   this way; point, uv, inst and prim have no gradient.  grad_points: 4 floats per record {dL/dp, 0} (rmax gets none).
+ * - Operation order (float32, no fused multiply-add except where fmaf is written, / and sqrtf correctly rounded), per record:
+ *     e1_k = b_k - a_k, e2_k = c_k - a_k, each rounded once;
+ *     a cross product x x y = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0): two products and one subtraction per component;
+ *     n = e1 x e2, P = d x e2, Q = e1 x d;  det = -((d0 n0 + d1 n1) + d2 n2);
+ *     num_k = (g_t n_k + g_u P_k) + g_v Q_k;  lambda_k = num_k / det;  dL/dd_k = t lambda_k;
+ *     w = (1 - u) - v;  the vertex contributions are -(w lambda_k), -(u lambda_k), -(v lambda_k).
+ *   Points:  q_k = fmaf(v, c_k - a_k, fmaf(u, b_k - a_k, a_k)), the form crt_closest_points uses for its point;  r_k = p_k - q_k;
+ *     len = sqrtf((r0 r0 + r1 r1) + r2 r2);  nhat_k = r_k / len;  s_k = g nhat_k;  contributions -(w s_k), -(u s_k), -(v s_k).
+ *   tests/grad_reference.c restates this in C; grad_rays and grad_points equal it bit for bit.
+ * - A record is inert -- its grad_rays / grad_points entry is all +0.0 and it adds nothing to any vertex -- when
+ *   inst == CRT_MISS or inst >= the number of meshes; prim >= that mesh's triangle count; any of t, u, v, g_t, g_u, g_v (points: u,
+ *   v, g), lambda_k, t lambda_k (points: s_k) is not finite; or, for points, len is 0 or not finite.  A miss of crt_trace_rays
+ *   with tmax = +inf is inert by its t; a ray parallel to its triangle's plane (det = 0) by its lambda; a triangle with a
+ *   non-finite vertex by its lambda.  len is computed here from p, u, v and the current vertices, not read from the forward call's
+ *   dist: a point that lies on the surface only up to rounding has a tiny len and gets a unit vector of rounding noise times g --
+ *   the derivative of a distance has no direction at zero.
+ * - grad_xyz: 3 floats per vertex, all meshes back to back in upload order -- the order of the concatenated crt_mesh_vertices
+ *   results; mesh m starts at the sum of the vertex counts of the meshes before it.  It is the gradient with respect to the WORLD
+ *   vertices (a caller who moves rest vertices under a transform multiplies by the transposed 3x3).  It is overwritten, not
+ *   accumulated: a vertex no live record touches reads exactly +0.0.
+ *   Each float32 contribution is widened to float64 and added with the hardware float64 atomic add to a context-owned array of 3
+ *   doubles per vertex (allocated by the first call that asks for grad_xyz, freed by the next upload or by crt_destroy, zeroed per
+ *   call; a context that never asks allocates nothing); a second kernel rounds each sum to float32 once.  The result is the
+ *   correctly rounded float32 of the exact sum of the contributions unless that sum lies within m * 2^-52 * sum|c_i| of a
+ *   rounding boundary, for m contributions: independent of the order of the records and of scheduling up to that rare last bit,
+ *   not promised bit-reproducible.  Calls of one context share the array: a call waits (on the GPU) for the one before it.
+ * - Nothing depends on the tree, the builder or refit versus rebuild: only the vertex buffer and the indices are read.
+ * - Pending refits are applied first.  n = 0 returns CRT_OK and launches nothing (no buffer is looked at, grad_xyz is not
+ *   written); n up to 2^32 - 1.  CRT_ESTATE without a dynamic scene.  CRT_EINVAL for a NULL ctx, a NULL input buffer, grad_t and
+ *   grad_uv both NULL, grad_rays (grad_points) and grad_xyz both NULL, or a misaligned device pointer: rays, points, grad_rays and
+ *   grad_points 16-byte, uv and grad_uv 8-byte, the rest 4-byte.  These checks come before the refit.
+ * - stats (may be NULL): kernel_ms (the zeroing, the record kernel and the rounding kernel), total_ms, rays_primary = n; every
+ *   other count is zero.
+ * *_device: asynchronous on the context's stream unless stats != NULL.  Host variants: synchronous, staged. */
+int crt_trace_rays_backward_device(crt_ctx* ctx, uint32_t n, const void* d_rays, const void* d_inst, const void* d_prim,
+                                   const void* d_t, const void* d_uv, const void* d_grad_t /* may be NULL = zeros */,
+                                   const void* d_grad_uv /* may be NULL = zeros */, void* d_grad_rays /* may be NULL */,
+                                   void* d_grad_xyz /* may be NULL */, crt_frame_stats* stats);
+int crt_trace_rays_backward(crt_ctx* ctx, uint32_t n, const float* rays, const uint32_t* inst, const uint32_t* prim, const float* t,
+                            const float* uv, const float* grad_t, const float* grad_uv, float* grad_rays, float* grad_xyz,
+                            crt_frame_stats* stats);
+int crt_closest_points_backward_device(crt_ctx* ctx, uint32_t n, const void* d_points, const void* d_inst, const void* d_prim,
+                                       const void* d_uv, const void* d_grad_dist, void* d_grad_points /* may be NULL */,
+                                       void* d_grad_xyz /* may be NULL */, crt_frame_stats* stats);
+int crt_closest_points_backward(crt_ctx* ctx, uint32_t n, const float* points, const uint32_t* inst, const uint32_t* prim,
+                                const float* uv, const float* grad_dist, float* grad_points, float* grad_xyz, crt_frame_stats* stats);
+
 /* ---- variance: luminance moments carried with the history, a per-pixel variance from them, and the a-trous filter with a colour
  * weight that follows that variance (Schied et al. 2017, "Spatiotemporal Variance-Guided Filtering").  The filter's weight is wide
  * where the estimate is noisy (short history, disocclusion, frame edges) and closes where the history has converged.
