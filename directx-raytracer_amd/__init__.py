@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "crt_set_accumulation", "crt_reset_accumulation", "crt_accumulated_samples",
     "crt_trace_rays_device", "crt_occluded_rays_device", "crt_trace_rays", "crt_occluded_rays",
     "crt_closest_points_device", "crt_closest_points", "crt_count_hits_device", "crt_count_hits", "crt_occupancy_device", "crt_occupancy",
+    "crt_winding_numbers_device", "crt_winding_numbers", "crt_winding_moments_export",
     "crt_update_vertices", "crt_update_vertices_device", "crt_set_mesh_transform", "crt_refit", "crt_mesh_vertices",
     "crt_rebuild", "crt_list_hits_device", "crt_list_hits", "crt_debug_list_phases",
     "crt_shade_rays_device", "crt_shade_rays",
@@ -257,6 +258,9 @@ def lib():
         "crt_count_hits": (C.c_int, [vp, u32, vp, vp, vp]),
         "crt_occupancy_device": (C.c_int, [vp, u32, vp, vp, vp]),
         "crt_occupancy": (C.c_int, [vp, u32, vp, vp, vp]),
+        "crt_winding_numbers_device": (C.c_int, [vp, u32, vp, f32, vp, vp]),
+        "crt_winding_numbers": (C.c_int, [vp, u32, vp, f32, vp, vp]),
+        "crt_winding_moments_export": (C.c_int, [vp, vp]),
         "crt_update_vertices": (C.c_int, [vp, u32, u32, vp, vp]),
         "crt_update_vertices_device": (C.c_int, [vp, u32, u32, vp, vp]),
         "crt_set_mesh_transform": (C.c_int, [vp, u32, vp]),
@@ -1441,13 +1445,48 @@ class Renderer:
         self._ok(lib().crt_occupancy(self.h, len(pts), pts.ctypes.data, out.ctypes.data, None), "crt_occupancy")
         return out
 
-    def signed_distance(self, points):
-        """distance to the closest surface point, negated where the point is inside (occupancy): (N,) float32.
+    def signed_distance(self, points, sign="parity", beta=2.0, threshold=0.5):
+        """distance to the closest surface point, negated where the point is inside: (N,) float32.  sign = "parity": inside by
+        occupancy (closed meshes); "winding": inside by inside_winding(points, beta, threshold) (open meshes and soups too).
         points: (N, 4) records (make_points; rmax bounds the search) or (N, 3) coordinates (rmax = inf)."""
+        if sign not in ("parity", "winding"):
+            raise ValueError("sign must be 'parity' or 'winding'")
         pts = np.asarray(points, dtype=np.float32)
         pts = make_points(pts) if pts.shape[-1:] == (3,) else np.ascontiguousarray(pts).reshape(-1, 4)
         d = self.closest_points(pts, want=("dist",))["dist"]
-        return np.where(self.occupancy(pts), -d, d).astype(np.float32)
+        inside = self.occupancy(pts) if sign == "parity" else self.inside_winding(pts, beta, threshold)
+        return np.where(inside, -d, d).astype(np.float32)
+
+    # ---- winding numbers (include/crt_hip.h): the inside test for open meshes and triangle soups
+    def winding_numbers(self, points, beta=2.0):
+        """generalised winding number of every point: (N,) float32 (host buffers, synchronous).  beta > 0: clusters farther than
+        beta x their radius are taken by their dipole; beta <= 0: exact, the sum over every triangle.
+        points: (N, 4) records (make_points; rmax is ignored) or (N, 3) coordinates."""
+        pts = np.asarray(points, dtype=np.float32)
+        pts = make_points(pts) if pts.shape[-1:] == (3,) else np.ascontiguousarray(pts).reshape(-1, 4)
+        out = np.zeros(len(pts), dtype=np.float32)
+        self._ok(lib().crt_winding_numbers(self.h, len(pts), pts.ctypes.data, float(beta), out.ctypes.data, None), "crt_winding_numbers")
+        return out
+
+    def winding_numbers_device(self, n, d_points, d_w, beta=2.0, stats=False):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
+        st = FrameStats() if stats else None
+        self._ok(lib().crt_winding_numbers_device(self.h, int(n), d_points, float(beta), d_w, C.byref(st) if stats else None),
+                 "crt_winding_numbers_device")
+        return st.as_dict() if stats else None
+
+    def winding_moments(self):
+        """the moment table the winding walk reads: (n_nodes4, 32) float32, {p~, r} of child slots 0..3, then {N~, 0} of slots 0..3"""
+        n4 = C.c_uint32(0)
+        self._ok(lib().crt_bvh_info4(self.h, C.byref(n4), None), "crt_bvh_info4")
+        out = np.zeros((n4.value, 32), dtype=np.float32)
+        if n4.value:
+            self._ok(lib().crt_winding_moments_export(self.h, out.ctypes.data), "crt_winding_moments_export")
+        return out
+
+    def inside_winding(self, points, beta=2.0, threshold=0.5):
+        """inside / outside of every point by its winding number: (N,) bool, winding_numbers(points, beta) > threshold"""
+        return self.winding_numbers(points, beta) > np.float32(threshold)
 
     def closest_points_device(self, n, d_points, d_dist=None, d_point=None, d_uv=None, d_inst=None, d_prim=None, stats=False):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""

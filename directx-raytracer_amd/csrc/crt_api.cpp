@@ -99,6 +99,12 @@ struct crt_ctx {
     crt::Bvh bvh; // host copy of what sits in HBM
     void* dNodes = nullptr;     // quantised wide nodes: what the kernels traverse
     void* dPlanes = nullptr;    // their decoded plane table (render_kernels.h kPlaneStride), rebuilt at every upload
+    // crt_winding_numbers*: the moment table beside the nodes (render_kernels.h kMomentStride), made by the first call that wants
+    // it and again once the tree or the records have changed: valid while momentsSerial == sceneSerial, which every upload, refit
+    // and rebuild bumps.  Freed with the tree (freeScene, adoptTree)
+    void* dMoments = nullptr;
+    uint32_t momentsNodes = 0;  // nodes the buffer has room for
+    uint32_t momentsSerial = 0;
     void* dBinNodes = nullptr;  // gpu_build only: the binary tree and the full-precision wide tree as the builder left them in
     void* dWideNodes = nullptr; // HBM (no host copy exists; crt_bvh_export* read them back)
     void* dTris = nullptr;
@@ -242,8 +248,8 @@ struct crt_ctx {
     // of this pool belong to queries alone (never to a frame); serial = ++raySerial.
     Arena rayArena[kRing];
     uint32_t raySerial = 0;
-    uint32_t rayResident[8] = {};        // resident workgroups of each query kernel (QueryKind) on this device ...
-    uint32_t rayResidentEntries[8] = {}; // ... for this many LDS stack entries
+    uint32_t rayResident[9] = {};        // resident workgroups of each query kernel (QueryKind) on this device ...
+    uint32_t rayResidentEntries[9] = {}; // ... for this many LDS stack entries
     void* dRayStage = nullptr; // the host entry points' records and outputs, grown on demand
     size_t rayStageBytes = 0;
     // crt_list_hits*: the host form's record arrays (grown on demand, apart from dRayStage, which holds its rays and offsets
@@ -286,11 +292,12 @@ int fail(crt_ctx* ctx, int code, const char* fmt, ...)
 
 void freeScene(crt_ctx* c)
 {
-    void** ptrs[] = { &c->dNodes, &c->dPlanes, &c->dBinNodes, &c->dWideNodes, &c->dTris, &c->dShade, &c->dLights, &c->dMats, &c->dUvs };
+    void** ptrs[] = { &c->dNodes, &c->dPlanes, &c->dMoments, &c->dBinNodes, &c->dWideNodes, &c->dTris, &c->dShade, &c->dLights, &c->dMats, &c->dUvs };
     for (void** p : ptrs) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
+    c->momentsNodes = 0;
     if (c->dGradSum) (void)hipFree(c->dGradSum);
     c->dGradSum = nullptr;
     delete c->dyn;
@@ -452,11 +459,12 @@ int stageEnd(crt_ctx* c, const StagePlane* planes, int n, void* const* dev)
 // table of the old tree goes.
 static void adoptTree(crt_ctx* c, crt::DeviceTree&& t)
 {
-    void** olds[] = { &c->dBinNodes, &c->dWideNodes, &c->dNodes, &c->dPlanes, &c->dTris, &c->dShade, &c->dUvs };
+    void** olds[] = { &c->dBinNodes, &c->dWideNodes, &c->dNodes, &c->dPlanes, &c->dMoments, &c->dTris, &c->dShade, &c->dUvs };
     for (void** q : olds) {
         if (*q) (void)hipFree(*q);
         *q = nullptr;
     }
+    c->momentsNodes = 0;
     c->dBinNodes = t.nodes.release();
     c->dWideNodes = t.nodes4.release();
     c->dNodes = t.nodes4q.release();
@@ -1411,7 +1419,8 @@ namespace {
 // the context.
 enum QueryKind { kQueryClosestHit = 0, kQueryOcclusion = 1, kQueryClosestPoint = 2, kQueryCount = 3, kQueryOccupancy = 4,
                  kQueryListFill = 5 /* the second traversal of crt_list_hits*: a kernel of its own, not an entry point */,
-                 kQueryShade = 6, kQueryPath = 7 /* crt_path_rays*: passes of (record, sample) items, not a QuerySpec */ };
+                 kQueryShade = 6, kQueryPath = 7 /* crt_path_rays*: passes of (record, sample) items, not a QuerySpec */,
+                 kQueryWinding = 8 };
 constexpr int kQueryOutputs = 7; // the most any kind has (crt_shade_rays*)
 struct QueryOutput {
     void* p = nullptr;
@@ -1424,6 +1433,7 @@ struct QuerySpec {
     uint32_t recordBytes;
     const char* outputNames; // for the alignment message
     QueryOutput out[kQueryOutputs]; // the kind's outputs, in a fixed order; NULL = not wanted
+    float beta = 0.0f;              // crt_winding_numbers*: travels with the call
 };
 
 QuerySpec rayQuerySpec(const char* what, bool occlusion, void* t, void* uv, void* inst, void* prim, void* occluded)
@@ -1488,6 +1498,7 @@ int queryGrid(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t& stack_entries, u
         case kQueryListFill: r = crt::listFillResident(stack_entries); break;
         case kQueryShade: r = crt::shadeQueryResident(stack_entries); break;
         case kQueryPath: r = crt::pathQueryResident(stack_entries); break;
+        case kQueryWinding: r = crt::windingQueryResident(stack_entries); break;
         }
         c->rayResident[kind] = r;
         c->rayResidentEntries[kind] = stack_entries;
@@ -1620,6 +1631,47 @@ int runPointQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_reco
     return endQuery(c, s.kind, n, ql, crt::launchPointQuery(q, pk, c->counting, ql.grid, c->stream), stats);
 }
 
+// The moment table of the tree as it stands (crt_winding_numbers*, crt_winding_moments_export), built on the context's stream
+// when there is none or the scene has changed since.  The scratch dies with the call, hence the wait.
+int ensureMoments(crt_ctx* c)
+{
+    const uint32_t n4 = c->bvh.dev.nNodes4;
+    if (c->dMoments && c->momentsNodes >= n4 && c->momentsSerial == c->sceneSerial) return CRT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->dMoments || c->momentsNodes < n4) {
+        HIP_TRY(c, hipDeviceSynchronize()); // a query in flight on another stream may still read the old table
+        if (c->dMoments) (void)hipFree(c->dMoments);
+        c->dMoments = nullptr;
+        c->momentsNodes = 0;
+        HIP_TRY(c, hipMalloc(&c->dMoments, sizeof(float) * crt::kMomentStride * (n4 ? n4 : 1u)));
+        c->momentsNodes = n4;
+    }
+    void* scratch = nullptr;
+    HIP_TRY(c, hipMalloc(&scratch, crt::windingScratchBytes(n4)));
+    hipError_t e = hipMemsetAsync(c->dMoments, 0, sizeof(float) * crt::kMomentStride * (n4 ? n4 : 1u), c->stream); // (nodes the root does not reach)
+    if (e == hipSuccess) e = static_cast<hipError_t>(crt::launchWindingMoments(c->dNodes, c->dTris, n4, c->bvh.depth4, static_cast<float*>(c->dMoments), scratch, c->stream));
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(scratch);
+    if (e != hipSuccess) return fail(c, CRT_EHIP, "winding moments: %s", hipGetErrorString(e));
+    c->momentsSerial = c->sceneSerial;
+    return CRT_OK;
+}
+
+// crt_winding_numbers*: the walk over the tree and its moment table (winding_kernels.hip)
+int runWindingQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, void* const d[kQueryOutputs], crt_frame_stats* stats)
+{
+    if (const int rc = ensureMoments(c)) return rc;
+    crt::WindingQueryParams q;
+    std::memset(&q, 0, sizeof(q));
+    q.moments = static_cast<const float*>(c->dMoments);
+    q.beta = s.beta > 0.0f ? s.beta : 0.0f; // (a NaN too)
+    q.w = static_cast<float*>(d[0]);
+    QueryLaunch ql;
+    if (const int rc = beginQuery(c, s.kind, n, 1u, stats, ql)) return rc;
+    q.c = queryCommon(c, ql, d_records, n, c->tuneInnerMinAny);
+    return endQuery(c, s.kind, n, ql, crt::launchWindingQuery(q, c->counting, ql.grid, c->stream), stats);
+}
+
 // the scene's shading tables (sceneTables) and the context's shading state of a shaded query
 void shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q)
 {
@@ -1652,6 +1704,7 @@ int runKind(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, v
 {
     if (s.kind == kQueryShade) return runShadeQuery(c, s, n, d_records, d, stats);
     if (s.kind == kQueryClosestHit || s.kind == kQueryOcclusion) return runRayQuery(c, s, n, d_records, d, stats);
+    if (s.kind == kQueryWinding) return runWindingQuery(c, s, n, d_records, d, stats);
     return runPointQuery(c, s, n, d_records, d, stats);
 }
 
@@ -1817,6 +1870,7 @@ int runPathQuery(crt_ctx* c, uint32_t n, const PathCall& a, crt_frame_stats* sta
 
 QuerySpec countSpec(const char* what, void* count) { return QuerySpec{ what, kQueryCount, 32u, "count", { { count, 4u, 4u } } }; }
 QuerySpec occupancySpec(const char* what, void* inside) { return QuerySpec{ what, kQueryOccupancy, 16u, "inside", { { inside, 1u, 1u } } }; }
+QuerySpec windingSpec(const char* what, void* w, float beta) { return QuerySpec{ what, kQueryWinding, 16u, "w", { { w, 4u, 4u } }, beta }; }
 
 // ---- all-hits listing (crt_list_hits*): count -> scan -> fill -> sort + resolve over one arena, between one beginQuery and
 // one endQuery.  The counts (reused as the sort's queue of long rays), the scan's tile sums and the key scratch live in the
@@ -2526,6 +2580,29 @@ int crt_occupancy_device(crt_ctx* c, uint32_t n, const void* d_points, void* d_i
 int crt_occupancy(crt_ctx* c, uint32_t n, const float* points, uint8_t* inside, crt_frame_stats* stats)
 {
     return queryHost(c, occupancySpec("crt_occupancy", inside), n, points, stats);
+}
+
+int crt_winding_numbers_device(crt_ctx* c, uint32_t n, const void* d_points, float beta, void* d_w, crt_frame_stats* stats)
+{
+    return queryDevice(c, windingSpec("crt_winding_numbers_device", d_w, beta), n, d_points, stats);
+}
+
+int crt_winding_numbers(crt_ctx* c, uint32_t n, const float* points, float beta, float* w, crt_frame_stats* stats)
+{
+    return queryHost(c, windingSpec("crt_winding_numbers", w, beta), n, points, stats);
+}
+
+int crt_winding_moments_export(const crt_ctx* cc, float* moments)
+{
+    if (!cc) return CRT_EINVAL;
+    crt_ctx* c = const_cast<crt_ctx*>(cc); // a pending refit runs first, as for the tree's exports
+    if (!c->haveScene) return fail(c, CRT_ESTATE, "crt_winding_moments_export: no scene uploaded: call crt_upload_scene first");
+    if (!moments) return fail(c, CRT_EINVAL, "crt_winding_moments_export: moments is NULL");
+    if (const int rc = applyRefit(c, nullptr)) return rc;
+    if (const int rc = ensureMoments(c)) return rc;
+    if (c->bvh.dev.nNodes4 > 0)
+        HIP_TRY(c, hipMemcpy(moments, c->dMoments, sizeof(float) * crt::kMomentStride * c->bvh.dev.nNodes4, hipMemcpyDeviceToHost));
+    return CRT_OK;
 }
 
 int crt_list_hits_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_offsets, uint64_t capacity, void* d_t, void* d_uv, void* d_inst,

@@ -245,6 +245,22 @@ struct PointQueryParams {
 inline uint32_t pointQueryEntryWords(PointQueryKind kind) { return kind == kPointClosest ? 2u : 1u; }
 uint32_t pointQueryResident(PointQueryKind kind, uint32_t stack_entries);
 int launchPointQuery(const PointQueryParams& q, PointQueryKind kind, bool counting, uint32_t grid, ihipStream_t* stream);
+// winding numbers (winding_kernels.hip; crt_winding_numbers*): n point records over the 4-wide tree and its moment table,
+// kMomentStride floats per node: {p~.xyz, r} of child slots 0..3 (one 64-byte line), then {N~.xyz, 0} of slots 0..3
+constexpr uint32_t kMomentStride = 32;
+struct WindingQueryParams {
+    QueryCommon c;
+    const float* moments;         // kMomentStride floats per wide node
+    float beta;                   // > 0: a child farther than beta x its radius is taken by its dipole; else every triangle
+    float* w;                     // one float per point
+};
+uint32_t windingQueryResident(uint32_t stack_entries);
+int launchWindingQuery(const WindingQueryParams& q, bool counting, uint32_t grid, ihipStream_t* stream);
+// the moment table of n_nodes4 quantised nodes, bottom-up over `levels` depth levels (any number >= the wide tree's depth).
+// scratch: windingScratchBytes(n_nodes4), the nodes' depths and their float64 sums
+size_t windingScratchBytes(uint32_t n_nodes4);
+int launchWindingMoments(const void* nodes4q, const void* tris, uint32_t n_nodes4, uint32_t levels, float* moments, void* scratch,
+                         ihipStream_t* stream);
 // all-hits listing (list_kernels.hip; crt_list_hits*): after the hit counts of launchPointQuery(kPointCount), the exclusive
 // sum of the counts into 64-bit offsets, a second traversal that writes every accepted hit into its ray's segment, and the
 // sort + resolve of every segment.  The three later steps read offsets[n] on the device and leave when it exceeds capacity.

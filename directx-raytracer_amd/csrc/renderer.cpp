@@ -327,6 +327,23 @@ void Renderer::closestPointsBackward(const float* points, const uint32_t* inst, 
           "crt_closest_points_backward");
 }
 
+void Renderer::windingNumbers(const float* points, size_t n, std::vector<float>& w, float beta)
+{
+    if (!ctx || !scene) throw std::runtime_error("windingNumbers before prepareForRendering");
+    if (n > UINT32_MAX) throw std::runtime_error("windingNumbers: more than 2^32 - 1 records");
+    w.assign(n, 0.0f);
+    check(crt_winding_numbers(ctx, static_cast<uint32_t>(n), points, beta, w.data(), nullptr), "crt_winding_numbers");
+}
+
+void Renderer::windingMoments(std::vector<float>& moments)
+{
+    if (!ctx || !scene) throw std::runtime_error("windingMoments before prepareForRendering");
+    uint32_t n4 = 0, depth4 = 0;
+    check(crt_bvh_info4(ctx, &n4, &depth4), "crt_bvh_info4");
+    moments.assign(32 * static_cast<size_t>(n4), 0.0f);
+    if (n4) check(crt_winding_moments_export(ctx, moments.data()), "crt_winding_moments_export");
+}
+
 void Renderer::temporalFrame(const crt_temporal_params* params, bool motion)
 {
     const size_t n = static_cast<size_t>(width) * height;

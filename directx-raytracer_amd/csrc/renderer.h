@@ -119,6 +119,11 @@ public:
     // with respect to the points (gradPoints: 4 floats per record {dL/dp, 0}) and to the world vertices (gradXyz, as above)
     void closestPointsBackward(const float* points, const uint32_t* inst, const uint32_t* prim, const float* uv, const float* gradDist, size_t n,
                                std::vector<float>* gradPoints, std::vector<float>* gradXyz);
+    // crt_winding_numbers (synchronous): the generalised winding number of n points (4 floats per record {x, y, z, unused}), one
+    // float each; beta > 0: clusters farther than beta x their radius are taken by their dipole, beta <= 0: every triangle
+    void windingNumbers(const float* points, size_t n, std::vector<float>& w, float beta = 2.0f);
+    // crt_winding_moments_export: 32 floats per wide node of the tree as it stands
+    void windingMoments(std::vector<float>& moments);
     void resetTemporal() { haveHistory = false; }
     // temporalAccumulate with luminance moments (crt_temporal_variance, synchronous): momPrev / momNext hold 2 floats per pixel
     // beside the history records (momPrev is nullptr exactly when histPrev is), variance receives 1 float per pixel; prevPoint:

@@ -715,6 +715,68 @@ int crt_count_hits(crt_ctx* ctx, uint32_t n, const float* rays, uint32_t* count,
 int crt_occupancy_device(crt_ctx* ctx, uint32_t n, const void* d_points, void* d_inside, crt_frame_stats* stats);
 int crt_occupancy(crt_ctx* ctx, uint32_t n, const float* points, uint8_t* inside, crt_frame_stats* stats);
 
+/* ---- winding numbers: the inside test for open meshes and triangle soups (no reference counterpart; Jacobson, Kavan,
+ * Sorkine-Hornung 2013, "Robust inside-outside segmentation using generalized winding numbers", evaluated over the tree as in
+ * Barill, Dickson, Schmidt, Levin, Jacobson 2018, "Fast winding numbers for soups and clouds", first order).  The generalised
+ * winding number w of a point is the sum of the signed solid angles of all triangles over 4 pi: 1 inside and 0 outside a closed
+ * outward-oriented mesh, -1 inside a reversed one, 2 inside two nested shells, a smooth fraction near a hole.  w > 0.5 is the
+ * inside test crt_occupancy cannot give for open geometry.
+ * - Records: the point records of crt_closest_points, 4 floats {x, y, z, rmax}; rmax is ignored.  Output: one float per point.
+ * - Per-triangle term h (half the signed solid angle; float, fused multiply-adds only where fmaf is written, / and sqrtf
+ *   correctly rounded, dot as in the point queries), from the leaf-ordered record {v0, e1, e2} as traced and the point q:
+ *     a = v0 - q; b = a + e1; c = a + e2  (per component)
+ *     n = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x);  det = dot(a, n)
+ *       (the edge form of a . (b x c): its rounding error grows with the triangle's size, not with the cube of its distance)
+ *     la = sqrtf(dot(a, a)), lb = sqrtf(dot(b, b)), lc = sqrtf(dot(c, c));  m = (la * lb) * lc
+ *     den = ((m + dot(a, b) * lc) + dot(b, c) * la) + dot(c, a) * lb
+ *     h = m == 0 ? 0 : crtAtan2(det, den)        (m == 0: the point is a vertex of the triangle)
+ * - crtAtan2(y, x), the project's own arctangent (neither the device library's atan2f nor libm's: they differ):
+ *     ay = |y|, ax = |x|; swap = ay > ax; mx = swap ? ay : ax; mn = swap ? ax : ay
+ *     t = mn / mx; s = t * t; p = C6; p = fmaf(p, s, Ck) for k = 5 .. 0; r = fmaf(t, s * p, t)
+ *     swap -> r = PI_2 - r;  x < 0 -> r = PI - r  (PI = 0x1.921fb6p+1f, PI_2 = 0x1.921fb6p+0f);  result y < 0 ? -r : r
+ *     and r = 0 when y or x is a NaN, when both are zero, or when either is infinite.
+ *   So y = +-0 gives +0 for x > 0 (a point in the triangle's plane outside the triangle) and +PI for x < 0 whichever the sign of
+ *   the zero (in the plane inside the triangle: undefined on the surface, but the same bits from both sides); x = +-0 gives
+ *   +-PI_2.  Absolute error against atan2 in float64: at most 2.95e-7 measured over the grid of tests/test_winding.py (the test
+ *   asserts that figure plus one float32 ulp of pi, under the 2^-20 the error budget below needs).
+ *   Triangles that contribute exactly zero: inert ones (a non-finite vertex makes det or den a NaN or an infinity, as does
+ *   any overflow of the products above) and those with the point at a vertex.  A record with a NaN coordinate gives w = 0.
+ * - Sum: every contribution h, a triangle's or a cluster's, is added to a 64-bit integer as llrint((double)h * 2^36); the
+ *   result is w = (float)((double)sum * 2^-36 / (2 pi)), 2 pi = 6.283185307179586.  Integer addition is associative: w does not
+ *   depend on the order of the walk, of the records or on scheduling.  |h| <= pi < 2^38 / 2^36, so the sum cannot wrap below
+ *   2^25 triangles; a cluster's h is clamped to +-4096 before the conversion (a NaN counts as 0).
+ * - Moments (crt_winding_moments_export: n_nodes4 x 32 floats): per wide node, words 4k .. 4k+3 = {p~.x, p~.y, p~.z, r} and
+ *   words 16+4k .. 16+4k+3 = {N~.x, N~.y, N~.z, 0} of child slot k.  For the triangles below the child, in float64 from the
+ *   float32 records, without fused multiply-add, with n_i = 0.5 * (e1 x e2) (component order as n above) and
+ *   A_i = sqrt((n.x*n.x + n.y*n.y) + n.z*n.z):  N~ = sum n_i,  A = sum A_i,  P = sum A_i * (v0 + (e1 + e2) / 3.0),  p~ = P / A
+ *   (the child's box centre 0.5f * (lo + hi) when A = 0), each rounded to float32 once.  A leaf's sums start at 0 and take its
+ *   triangles in leaf order; a node's total starts at 0 and takes its four slots in order 0..3; an inner child's sums are its
+ *   node's total.  Inert triangles are left out; CRT_BVH_EMPTY slots hold zeros.  r (float) over the child's decoded
+ *   quantised box [lo, hi]: r = sqrtf((mx + my) + mz), m_a = max((p~_a - lo_a)^2, (hi_a - p~_a)^2): no triangle of the child
+ *   is farther from p~.
+ * - Walk: from the root, per non-empty child slot with d = p~ - q, d2 = dot(d, d): when beta > 0 and d2 > (beta * r)^2 the child
+ *   contributes h = (0.5f * dot(N~, d)) / (d2 * sqrtf(d2)) and is not entered; else it is entered; a leaf adds every triangle's
+ *   term.  beta <= 0 or NaN: exact -- no cluster is approximated and w is the sum over all triangles, the same bits over every
+ *   tree (host SAH, LBVH, PLOC, refitted, rebuilt).  beta = +inf is exact through the same comparison.  With a finite beta > 0
+ *   the result depends on the tree (other clusters exist), not on any order.  beta = 2 keeps the error near 1e-2 at worst
+ *   close to a cluster and far below it elsewhere (DESIGN.md section 5q has the measured figures).
+ * - Common rules of the point queries: pending refits are applied first; n = 0 returns CRT_OK and launches nothing;
+ *   CRT_ESTATE without a scene; CRT_EINVAL for a NULL context, a NULL or misaligned pointer (points 16-byte, w 4-byte).  The
+ *   moment table (n_nodes4 x 128 bytes) is built by the first winding query or export after an upload, a refit or a rebuild;
+ *   that build waits for the stream.  Otherwise the device form is asynchronous on the context's stream unless stats != NULL.
+ *   stats: rays_primary = n; nodes_visited / tris_tested with crt_set_counting(ctx, 1): node records (each with its moment
+ *   line) and triangle records fetched.  Frames, accumulation and launch orders are untouched. */
+#define CRT_ATAN_C0 -0x1.5550f2p-2f   /* -0.33331659 */
+#define CRT_ATAN_C1 0x1.98d61p-3f     /*  0.19962704 */
+#define CRT_ATAN_C2 -0x1.1e3d8ap-3f   /* -0.13976581 */
+#define CRT_ATAN_C3 0x1.912bfap-4f    /*  0.09794233 */
+#define CRT_ATAN_C4 -0x1.d947fp-5f    /* -0.05777356 */
+#define CRT_ATAN_C5 0x1.797d4p-6f     /*  0.02304012 */
+#define CRT_ATAN_C6 -0x1.1d6f7ap-8f   /* -0.00435540 */
+int crt_winding_numbers_device(crt_ctx* ctx, uint32_t n, const void* d_points, float beta, void* d_w, crt_frame_stats* stats);
+int crt_winding_numbers(crt_ctx* ctx, uint32_t n, const float* points, float beta, float* w, crt_frame_stats* stats);
+int crt_winding_moments_export(const crt_ctx* ctx, float* moments /* n_nodes4 (crt_bvh_info4) x 32 floats */);
+
 /* ---- all-hits ray queries: every crossing of a ray, sorted by distance (Open3D's list_intersections, Embree's rtcIntersect with
  * an all-hits filter, the any-hit shader of DXR).  Wall thickness and chord lengths, layered depth images, inside / outside with
  * the evidence attached, multi-return sensor casts.
