@@ -33,36 +33,6 @@ TRI_DTYPE = np.dtype([("v0", "f4", 3), ("inst", "u4"), ("e1", "f4", 3), ("prim",
                       ("e2", "f4", 3), ("gid", "u4")])
 SHADE_DTYPE = np.dtype([("n0", "f4", 3), ("n1", "f4", 3), ("n2", "f4", 3), ("material", "u4"), ("pad", "u4", 2)])
 
-# every symbol include/crt_hip.h declares (tests/test_abi.py checks the library exports all of them)
-ABI_SYMBOLS = [
-    "crt_abi_version", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_textures", "crt_bvh_export_uv", "crt_set_camera",
-    "crt_set_shading_mode", "crt_set_miss_color", "crt_set_counting", "crt_set_option", "crt_debug_read_timeline", "crt_debug_read_counters", "crt_debug_check_rcp", "crt_debug_wide_offsets", "crt_render_frame", "crt_render_frame_device",
-    "crt_tile_count", "crt_tile_slots", "crt_render_tiles_device", "crt_render_frames_batch_device", "crt_render_tiles_batch_device",
-    "crt_untile_device", "crt_untile_batch_device", "crt_set_stream", "crt_reset_stream",
-    "crt_synchronize", "crt_bvh_info", "crt_bvh_export", "crt_bvh_build_host", "crt_free", "crt_host_alloc", "crt_host_free", "crt_bvh_info4", "crt_bvh_export4", "crt_bvh_export4q", "crt_bvh_export_planes4q", "crt_bvh_quantize4", "crt_comm_unique_id", "crt_comm_init", "crt_comm_init_host", "crt_comm_destroy", "crt_comm_info", "crt_render_frame_distributed", "crt_bvh_build_host4", "crt_build_stats",
-    "crt_scene_load", "crt_scene_save", "crt_scene_new", "crt_scene_free", "crt_scene_add_mesh", "crt_scene_add_light",
-    "crt_scene_add_material", "crt_scene_mesh_count", "crt_scene_mesh", "crt_scene_light_count", "crt_scene_light",
-    "crt_scene_material_count", "crt_scene_material", "crt_scene_texture_count", "crt_scene_texture_color", "crt_scene_add_texture",
-    "crt_scene_set_material_texture", "crt_scene_set_mesh_uvs", "crt_scene_settings",
-    "crt_scene_camera_get", "crt_scene_camera_set", "crt_scene_camera_rotate", "crt_scene_camera_zoom",
-    "crt_scene_camera_move_forward", "crt_scene_camera_move_right", "crt_scene_camera_pan", "crt_scene_camera_tilt",
-    "crt_scene_camera_roll", "crt_scene_camera_pan_around_target", "crt_upload_scene_from", "crt_set_camera_from",
-    "crt_set_accumulation", "crt_reset_accumulation", "crt_accumulated_samples",
-    "crt_trace_rays_device", "crt_occluded_rays_device", "crt_trace_rays", "crt_occluded_rays",
-    "crt_closest_points_device", "crt_closest_points", "crt_count_hits_device", "crt_count_hits", "crt_occupancy_device", "crt_occupancy",
-    "crt_winding_numbers_device", "crt_winding_numbers", "crt_winding_moments_export",
-    "crt_update_vertices", "crt_update_vertices_device", "crt_set_mesh_transform", "crt_refit", "crt_mesh_vertices",
-    "crt_rebuild", "crt_list_hits_device", "crt_list_hits", "crt_debug_list_phases",
-    "crt_shade_rays_device", "crt_shade_rays",
-    "crt_path_rays_device", "crt_path_rays",
-    "crt_camera_rays_device", "crt_camera_rays", "crt_frame_guides_device", "crt_frame_guides", "crt_denoise_device", "crt_denoise",
-    "crt_temporal_accumulate_device", "crt_temporal_accumulate",
-    "crt_motion_snapshot", "crt_previous_points_device", "crt_previous_points", "crt_frame_motion_device", "crt_frame_motion",
-    "crt_temporal_accumulate_motion_device", "crt_temporal_accumulate_motion",
-    "crt_temporal_variance_device", "crt_temporal_variance", "crt_denoise_variance_device", "crt_denoise_variance",
-    "crt_trace_rays_backward_device", "crt_trace_rays_backward", "crt_closest_points_backward_device", "crt_closest_points_backward",
-]
-
 
 class CrtError(RuntimeError):
     pass
@@ -145,6 +115,131 @@ def build(force=False):
     return LIB_PATH
 
 
+# ---- the C ABI: every symbol include/crt_hip.h declares -> (restype, argtypes), stated once (tests/test_abi.py checks the table
+# against the header and the library); lib() applies it, ABI_SYMBOLS lists it
+_vp, _u32, _i32, _flt, _int = C.c_void_p, C.c_uint32, C.c_int32, C.c_float, C.c_int
+_ABI = {
+    "crt_abi_version": (_u32, []),
+    "crt_create": (_int, [C.POINTER(_vp), _int]),
+    "crt_destroy": (None, [_vp]),
+    "crt_last_error": (C.c_char_p, [_vp]),
+    "crt_upload_scene": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32]),
+    "crt_set_camera": (_int, [_vp, _vp, _vp]),
+    "crt_set_textures": (_int, [_vp, _vp, _u32]),
+    "crt_bvh_export_uv": (_int, [_vp, _vp, C.POINTER(_int)]),
+    "crt_scene_texture_color": (_int, [_vp, _u32, _flt, _flt, _vp]),
+    "crt_scene_add_texture": (_int, [_vp, C.c_char_p, C.c_char_p, _vp, _vp, _flt, C.c_char_p]),
+    "crt_scene_set_material_texture": (_int, [_vp, _u32, C.c_char_p]),
+    "crt_scene_set_mesh_uvs": (_int, [_vp, _u32, _vp]),
+    "crt_set_shading_mode": (_int, [_vp, _u32]),
+    "crt_set_miss_color": (_int, [_vp, _vp]),
+    "crt_set_counting": (_int, [_vp, _int]),
+    "crt_set_option": (_int, [_vp, C.c_char_p, _int]),
+    "crt_debug_read_timeline": (_int, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "crt_debug_read_counters": (_int, [_vp, _vp]),
+    "crt_debug_check_rcp": (_int, [_int, _vp]),
+    "crt_debug_wide_offsets": (_int, [C.c_ulonglong, C.c_ulonglong, _int]),
+    "crt_tile_count": (_u32, [_u32, _u32]),
+    "crt_tile_slots": (_u32, [_u32, _u32, _u32]),
+    "crt_render_tiles_device": (_int, [_vp, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "crt_untile_batch_device": (_int, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "crt_render_frames_batch_device": (_int, [_vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "crt_render_tiles_batch_device": (_int, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "crt_untile_device": (_int, [_vp, _u32, _u32, _u32, _vp, _vp]),
+    "crt_set_stream": (_int, [_vp, _vp]),
+    "crt_reset_stream": (_int, [_vp]),
+    "crt_synchronize": (_int, [_vp]),
+    "crt_bvh_info": (_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "crt_bvh_export": (_int, [_vp, _vp, _vp, _vp]),
+    "crt_bvh_build_host": (_int, [_vp, _u32, C.POINTER(_vp), C.POINTER(_u32), C.POINTER(_vp), C.POINTER(_vp),
+                                  C.POINTER(_u32), C.POINTER(_u32)]),
+    "crt_free": (None, [_vp]),
+    "crt_host_alloc": (_vp, [C.c_size_t]),
+    "crt_host_free": (None, [_vp]),
+    "crt_bvh_info4": (_int, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
+    "crt_build_stats": (_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "crt_bvh_export4": (_int, [_vp, _vp]),
+    "crt_bvh_export4q": (_int, [_vp, _vp]),
+    "crt_bvh_export_planes4q": (_int, [_vp, _vp]),
+    "crt_comm_unique_id": (_int, [_vp]),
+    "crt_comm_init": (_int, [_vp, _u32, _u32, _vp]),
+    "crt_comm_init_host": (_int, [_vp, _u32, _u32, C.c_char_p]),
+    "crt_comm_destroy": (_int, [_vp]),
+    "crt_comm_info": (_int, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
+    "crt_render_frame_distributed": (_int, [_vp, _u32, _u32, _vp, _vp, C.POINTER(FrameStats)]),
+    "crt_bvh_quantize4": (_int, [_vp, _u32, _vp]),
+    "crt_bvh_build_host4": (_int, [_vp, _u32, C.POINTER(_vp), C.POINTER(_u32), C.POINTER(_u32)]),
+    "crt_scene_load": (_int, [C.c_char_p, C.POINTER(_vp), C.c_char_p, C.c_size_t]),
+    "crt_scene_new": (_int, [C.POINTER(_vp)]),
+    "crt_scene_save": (_int, [_vp, C.c_char_p, C.c_char_p, C.c_size_t]),
+    "crt_scene_free": (None, [_vp]),
+    "crt_scene_add_mesh": (_int, [_vp, _vp, _u32, _vp, _u32, _i32]),
+    "crt_scene_add_light": (_int, [_vp, _vp, _flt]),
+    "crt_scene_add_material": (_int, [_vp, _vp]),
+    "crt_scene_mesh_count": (_u32, [_vp]),
+    "crt_scene_mesh": (_int, [_vp, _u32, _vp]),
+    "crt_scene_light_count": (_u32, [_vp]),
+    "crt_scene_light": (_int, [_vp, _u32, _vp]),
+    "crt_scene_material_count": (_u32, [_vp]),
+    "crt_scene_material": (_int, [_vp, _u32, _vp]),
+    "crt_scene_texture_count": (_u32, [_vp]),
+    "crt_scene_settings": (_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), _vp]),
+    "crt_scene_camera_get": (_int, [_vp, _vp, _vp]),
+    "crt_scene_camera_set": (_int, [_vp, _vp, _vp]),
+    "crt_scene_camera_rotate": (_int, [_vp, _flt, _flt]),
+    "crt_scene_camera_zoom": (_int, [_vp, _flt]),
+    "crt_scene_camera_move_forward": (_int, [_vp, _flt]),
+    "crt_scene_camera_move_right": (_int, [_vp, _flt]),
+    "crt_scene_camera_pan": (_int, [_vp, _flt]),
+    "crt_scene_camera_tilt": (_int, [_vp, _flt]),
+    "crt_scene_camera_roll": (_int, [_vp, _flt]),
+    "crt_scene_camera_pan_around_target": (_int, [_vp, _flt, _vp]),
+    "crt_upload_scene_from": (_int, [_vp, _vp]),
+    "crt_set_camera_from": (_int, [_vp, _vp]),
+    "crt_set_accumulation": (_int, [_vp, _u32]),
+    "crt_reset_accumulation": (_int, [_vp]),
+    "crt_accumulated_samples": (_int, [_vp, C.POINTER(_u32)]),
+    "crt_winding_moments_export": (_int, [_vp, _vp]),
+    "crt_set_mesh_transform": (_int, [_vp, _u32, _vp]),
+    "crt_refit": (_int, [_vp, C.POINTER(C.c_double)]),
+    "crt_mesh_vertices": (_int, [_vp, _u32, _vp, _vp]),
+    "crt_rebuild": (_int, [_vp, C.POINTER(C.c_double)]),
+    "crt_debug_list_phases": (_int, [_vp, _vp]),
+    "crt_motion_snapshot": (_int, [_vp]),
+}
+
+
+def _host_and_device(rows):
+    """the entry points that come as crt_x (host buffers) and crt_x_device (device pointers) with one argument list"""
+    return {name + suffix: sig for name, sig in rows.items() for suffix in ("", "_device")}
+
+
+_ABI.update(_host_and_device({
+    "crt_render_frame": (_int, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "crt_trace_rays": (_int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "crt_occluded_rays": (_int, [_vp, _u32, _vp, _vp, _vp]),
+    "crt_closest_points": (_int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "crt_count_hits": (_int, [_vp, _u32, _vp, _vp, _vp]),
+    "crt_occupancy": (_int, [_vp, _u32, _vp, _vp, _vp]),
+    "crt_winding_numbers": (_int, [_vp, _u32, _vp, _flt, _vp, _vp]),
+    "crt_update_vertices": (_int, [_vp, _u32, _u32, _vp, _vp]),
+    "crt_list_hits": (_int, [_vp, _u32, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "crt_shade_rays": (_int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "crt_path_rays": (_int, [_vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "crt_camera_rays": (_int, [_vp, _u32, _u32, _u32, _vp, _vp]),
+    "crt_frame_guides": (_int, [_vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "crt_denoise": (_int, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "crt_temporal_accumulate": (_int, [_vp, _u32, _u32] + [_vp] * 11),
+    "crt_previous_points": (_int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "crt_frame_motion": (_int, [_vp, _u32, _u32, _vp, _vp]),
+    "crt_temporal_accumulate_motion": (_int, [_vp, _u32, _u32] + [_vp] * 12),
+    "crt_temporal_variance": (_int, [_vp, _u32, _u32] + [_vp] * 15),
+    "crt_denoise_variance": (_int, [_vp, _u32, _u32] + [_vp] * 9),
+    "crt_trace_rays_backward": (_int, [_vp, _u32] + [_vp] * 10),
+    "crt_closest_points_backward": (_int, [_vp, _u32] + [_vp] * 8),
+}))
+ABI_SYMBOLS = list(_ABI)
+
 _lib = None
 
 
@@ -164,142 +259,7 @@ def lib():
     except ImportError:
         pass
     L = C.CDLL(LIB_PATH)
-    vp, u32, i32, f32 = C.c_void_p, C.c_uint32, C.c_int32, C.c_float
-    sig = {
-        "crt_abi_version": (u32, []),
-        "crt_create": (C.c_int, [C.POINTER(vp), C.c_int]),
-        "crt_destroy": (None, [vp]),
-        "crt_last_error": (C.c_char_p, [vp]),
-        "crt_upload_scene": (C.c_int, [vp, vp, u32, vp, u32, vp, u32]),
-        "crt_set_camera": (C.c_int, [vp, vp, vp]),
-        "crt_set_textures": (C.c_int, [vp, vp, u32]),
-        "crt_bvh_export_uv": (C.c_int, [vp, vp, C.POINTER(C.c_int)]),
-        "crt_scene_texture_color": (C.c_int, [vp, u32, f32, f32, vp]),
-        "crt_scene_add_texture": (C.c_int, [vp, C.c_char_p, C.c_char_p, vp, vp, f32, C.c_char_p]),
-        "crt_scene_set_material_texture": (C.c_int, [vp, u32, C.c_char_p]),
-        "crt_scene_set_mesh_uvs": (C.c_int, [vp, u32, vp]),
-        "crt_set_shading_mode": (C.c_int, [vp, u32]),
-        "crt_set_miss_color": (C.c_int, [vp, vp]),
-        "crt_set_counting": (C.c_int, [vp, C.c_int]),
-        "crt_set_option": (C.c_int, [vp, C.c_char_p, C.c_int]),
-        "crt_debug_read_timeline": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
-        "crt_debug_read_counters": (C.c_int, [vp, vp]),
-        "crt_debug_check_rcp": (C.c_int, [C.c_int, vp]),
-        "crt_debug_wide_offsets": (C.c_int, [C.c_ulonglong, C.c_ulonglong, C.c_int]),
-        "crt_render_frame": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp]),
-        "crt_render_frame_device": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp]),
-        "crt_tile_count": (u32, [u32, u32]),
-        "crt_tile_slots": (u32, [u32, u32, u32]),
-        "crt_render_tiles_device": (C.c_int, [vp, u32, u32, u32, u32, vp, vp]),
-        "crt_untile_batch_device": (C.c_int, [vp, u32, u32, u32, u32, u32, vp, vp]),
-        "crt_render_frames_batch_device": (C.c_int, [vp, u32, u32, u32, vp, vp, vp]),
-        "crt_render_tiles_batch_device": (C.c_int, [vp, u32, u32, u32, u32, u32, vp, vp, vp]),
-        "crt_untile_device": (C.c_int, [vp, u32, u32, u32, vp, vp]),
-        "crt_set_stream": (C.c_int, [vp, vp]),
-        "crt_reset_stream": (C.c_int, [vp]),
-        "crt_synchronize": (C.c_int, [vp]),
-        "crt_bvh_info": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
-        "crt_bvh_export": (C.c_int, [vp, vp, vp, vp]),
-        "crt_bvh_build_host": (C.c_int, [vp, u32, C.POINTER(vp), C.POINTER(u32), C.POINTER(vp), C.POINTER(vp),
-                                         C.POINTER(u32), C.POINTER(u32)]),
-        "crt_free": (None, [vp]),
-        "crt_host_alloc": (vp, [C.c_size_t]),
-        "crt_host_free": (None, [vp]),
-        "crt_bvh_info4": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32)]),
-        "crt_build_stats": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-        "crt_bvh_export4": (C.c_int, [vp, vp]),
-        "crt_bvh_export4q": (C.c_int, [vp, vp]),
-        "crt_bvh_export_planes4q": (C.c_int, [vp, vp]),
-        "crt_comm_unique_id": (C.c_int, [vp]),
-        "crt_comm_init": (C.c_int, [vp, u32, u32, vp]),
-        "crt_comm_init_host": (C.c_int, [vp, u32, u32, C.c_char_p]),
-        "crt_comm_destroy": (C.c_int, [vp]),
-        "crt_comm_info": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32)]),
-        "crt_render_frame_distributed": (C.c_int, [vp, u32, u32, vp, vp, C.POINTER(FrameStats)]),
-        "crt_bvh_quantize4": (C.c_int, [vp, u32, vp]),
-        "crt_bvh_build_host4": (C.c_int, [vp, u32, C.POINTER(vp), C.POINTER(u32), C.POINTER(u32)]),
-        "crt_scene_load": (C.c_int, [C.c_char_p, C.POINTER(vp), C.c_char_p, C.c_size_t]),
-        "crt_scene_new": (C.c_int, [C.POINTER(vp)]),
-        "crt_scene_save": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_size_t]),
-        "crt_scene_free": (None, [vp]),
-        "crt_scene_add_mesh": (C.c_int, [vp, vp, u32, vp, u32, i32]),
-        "crt_scene_add_light": (C.c_int, [vp, vp, f32]),
-        "crt_scene_add_material": (C.c_int, [vp, vp]),
-        "crt_scene_mesh_count": (u32, [vp]),
-        "crt_scene_mesh": (C.c_int, [vp, u32, vp]),
-        "crt_scene_light_count": (u32, [vp]),
-        "crt_scene_light": (C.c_int, [vp, u32, vp]),
-        "crt_scene_material_count": (u32, [vp]),
-        "crt_scene_material": (C.c_int, [vp, u32, vp]),
-        "crt_scene_texture_count": (u32, [vp]),
-        "crt_scene_settings": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32), vp]),
-        "crt_scene_camera_get": (C.c_int, [vp, vp, vp]),
-        "crt_scene_camera_set": (C.c_int, [vp, vp, vp]),
-        "crt_scene_camera_rotate": (C.c_int, [vp, f32, f32]),
-        "crt_scene_camera_zoom": (C.c_int, [vp, f32]),
-        "crt_scene_camera_move_forward": (C.c_int, [vp, f32]),
-        "crt_scene_camera_move_right": (C.c_int, [vp, f32]),
-        "crt_scene_camera_pan": (C.c_int, [vp, f32]),
-        "crt_scene_camera_tilt": (C.c_int, [vp, f32]),
-        "crt_scene_camera_roll": (C.c_int, [vp, f32]),
-        "crt_scene_camera_pan_around_target": (C.c_int, [vp, f32, vp]),
-        "crt_upload_scene_from": (C.c_int, [vp, vp]),
-        "crt_set_camera_from": (C.c_int, [vp, vp]),
-        "crt_set_accumulation": (C.c_int, [vp, u32]),
-        "crt_reset_accumulation": (C.c_int, [vp]),
-        "crt_accumulated_samples": (C.c_int, [vp, C.POINTER(u32)]),
-        "crt_trace_rays_device": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp]),
-        "crt_occluded_rays_device": (C.c_int, [vp, u32, vp, vp, vp]),
-        "crt_trace_rays": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp]),
-        "crt_occluded_rays": (C.c_int, [vp, u32, vp, vp, vp]),
-        "crt_closest_points_device": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp]),
-        "crt_closest_points": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp]),
-        "crt_count_hits_device": (C.c_int, [vp, u32, vp, vp, vp]),
-        "crt_count_hits": (C.c_int, [vp, u32, vp, vp, vp]),
-        "crt_occupancy_device": (C.c_int, [vp, u32, vp, vp, vp]),
-        "crt_occupancy": (C.c_int, [vp, u32, vp, vp, vp]),
-        "crt_winding_numbers_device": (C.c_int, [vp, u32, vp, f32, vp, vp]),
-        "crt_winding_numbers": (C.c_int, [vp, u32, vp, f32, vp, vp]),
-        "crt_winding_moments_export": (C.c_int, [vp, vp]),
-        "crt_update_vertices": (C.c_int, [vp, u32, u32, vp, vp]),
-        "crt_update_vertices_device": (C.c_int, [vp, u32, u32, vp, vp]),
-        "crt_set_mesh_transform": (C.c_int, [vp, u32, vp]),
-        "crt_refit": (C.c_int, [vp, C.POINTER(C.c_double)]),
-        "crt_mesh_vertices": (C.c_int, [vp, u32, vp, vp]),
-        "crt_rebuild": (C.c_int, [vp, C.POINTER(C.c_double)]),
-        "crt_list_hits_device": (C.c_int, [vp, u32, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
-        "crt_list_hits": (C.c_int, [vp, u32, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp]),
-        "crt_debug_list_phases": (C.c_int, [vp, vp]),
-        "crt_shade_rays_device": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "crt_shade_rays": (C.c_int, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "crt_path_rays_device": (C.c_int, [vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
-        "crt_path_rays": (C.c_int, [vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
-        "crt_camera_rays_device": (C.c_int, [vp, u32, u32, u32, vp, vp]),
-        "crt_camera_rays": (C.c_int, [vp, u32, u32, u32, vp, vp]),
-        "crt_frame_guides_device": (C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
-        "crt_frame_guides": (C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
-        "crt_denoise_device": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
-        "crt_denoise": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
-        "crt_temporal_accumulate_device": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "crt_temporal_accumulate": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "crt_motion_snapshot": (C.c_int, [vp]),
-        "crt_previous_points_device": (C.c_int, [vp, u32, vp, vp, vp, vp, vp]),
-        "crt_previous_points": (C.c_int, [vp, u32, vp, vp, vp, vp, vp]),
-        "crt_frame_motion_device": (C.c_int, [vp, u32, u32, vp, vp]),
-        "crt_frame_motion": (C.c_int, [vp, u32, u32, vp, vp]),
-        "crt_temporal_accumulate_motion_device": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "crt_temporal_accumulate_motion": (C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "crt_temporal_variance_device": (C.c_int, [vp, u32, u32] + [vp] * 15),
-        "crt_temporal_variance": (C.c_int, [vp, u32, u32] + [vp] * 15),
-        "crt_denoise_variance_device": (C.c_int, [vp, u32, u32] + [vp] * 9),
-        "crt_denoise_variance": (C.c_int, [vp, u32, u32] + [vp] * 9),
-        "crt_trace_rays_backward_device": (C.c_int, [vp, u32] + [vp] * 10),
-        "crt_trace_rays_backward": (C.c_int, [vp, u32] + [vp] * 10),
-        "crt_closest_points_backward_device": (C.c_int, [vp, u32] + [vp] * 8),
-        "crt_closest_points_backward": (C.c_int, [vp, u32] + [vp] * 8),
-    }
-    assert set(sig) == set(ABI_SYMBOLS)
-    for name, (res, args) in sig.items():
+    for name, (res, args) in _ABI.items():
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
@@ -451,6 +411,11 @@ class Scene:
         if rc:
             raise CrtError("%s rc=%d" % (what, rc))
 
+    def _call(self, name, *args):
+        """the entry point `name` with the scene's handle in front, reported under its own name (the camera methods below report
+        under the reference's method names, so they call _ok themselves)"""
+        self._ok(getattr(lib(), name)(self.h, *args), name)
+
     def save(self, path):
         """binary cache (.crtbin)"""
         err = C.create_string_buffer(512)
@@ -461,31 +426,31 @@ class Scene:
     def add_mesh(self, vertices, triangles, material_index=0):
         v = _f32(vertices).reshape(-1, 3)
         t = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
-        self._ok(lib().crt_scene_add_mesh(self.h, v.ctypes.data, len(v), t.ctypes.data, len(t), int(material_index)), "crt_scene_add_mesh")
+        self._call("crt_scene_add_mesh", v.ctypes.data, len(v), t.ctypes.data, len(t), int(material_index))
 
     def add_light(self, pos, intensity):
         p = _f32(pos, 3)
-        self._ok(lib().crt_scene_add_light(self.h, p.ctypes.data, float(intensity)), "crt_scene_add_light")
+        self._call("crt_scene_add_light", p.ctypes.data, float(intensity))
 
     def add_material(self, albedo=(1, 1, 1), type=1, smooth_shading=False, ior=1.0):
         m = Material((C.c_float * 3)(*[float(x) for x in albedo]), int(type), int(bool(smooth_shading)), float(ior), -1)
-        self._ok(lib().crt_scene_add_material(self.h, C.byref(m)), "crt_scene_add_material")
+        self._call("crt_scene_add_material", C.byref(m))
 
     def add_texture(self, name, type, color_a=(0, 0, 0), color_b=(0, 0, 0), scalar=0.0, file_path=None):
         a, b = _f32(color_a, 3), _f32(color_b, 3)
-        self._ok(lib().crt_scene_add_texture(self.h, name.encode(), type.encode(), a.ctypes.data, b.ctypes.data, float(scalar),
-                                             os.fsencode(file_path) if file_path else None), "crt_scene_add_texture")
+        self._call("crt_scene_add_texture", name.encode(), type.encode(), a.ctypes.data, b.ctypes.data, float(scalar),
+                   os.fsencode(file_path) if file_path else None)
 
     def set_material_texture(self, material, texture_name):
-        self._ok(lib().crt_scene_set_material_texture(self.h, int(material), texture_name.encode()), "crt_scene_set_material_texture")
+        self._call("crt_scene_set_material_texture", int(material), texture_name.encode())
 
     def set_mesh_uvs(self, mesh, uvs):
         u = _f32(uvs).reshape(-1, 3)
-        self._ok(lib().crt_scene_set_mesh_uvs(self.h, int(mesh), u.ctypes.data), "crt_scene_set_mesh_uvs")
+        self._call("crt_scene_set_mesh_uvs", int(mesh), u.ctypes.data)
 
     def texture_color(self, i, u, v):
         out = np.zeros(3, dtype=np.float32)
-        self._ok(lib().crt_scene_texture_color(self.h, int(i), float(np.float32(u)), float(np.float32(v)), out.ctypes.data), "crt_scene_texture_color")
+        self._call("crt_scene_texture_color", int(i), float(np.float32(u)), float(np.float32(v)), out.ctypes.data)
         return out
 
     # ---- getters (CRTScene::getObjects / getLights / getMaterials / getTextures / getSettings)
@@ -495,7 +460,7 @@ class Scene:
 
     def mesh(self, i):
         mv = MeshView()
-        self._ok(lib().crt_scene_mesh(self.h, i, C.byref(mv)), "crt_scene_mesh")
+        self._call("crt_scene_mesh", i, C.byref(mv))
 
         def arr(ptr, n, dt):
             if not ptr or n == 0:
@@ -517,7 +482,7 @@ class Scene:
         out = []
         for i in range(lib().crt_scene_light_count(self.h)):
             l = Light()
-            self._ok(lib().crt_scene_light(self.h, i, C.byref(l)), "crt_scene_light")
+            self._call("crt_scene_light", i, C.byref(l))
             out.append((tuple(l.pos), l.intensity))
         return out
 
@@ -525,7 +490,7 @@ class Scene:
         out = []
         for i in range(lib().crt_scene_material_count(self.h)):
             m = Material()
-            self._ok(lib().crt_scene_material(self.h, i, C.byref(m)), "crt_scene_material")
+            self._call("crt_scene_material", i, C.byref(m))
             out.append({"albedo": tuple(m.albedo), "type": m.type, "smooth_shading": bool(m.smooth), "ior": m.ior, "texture": m.texture})
         return out
 
@@ -536,21 +501,20 @@ class Scene:
     def settings(self):
         w, h = C.c_uint32(), C.c_uint32()
         bg = np.zeros(3, dtype=np.float32)
-        self._ok(lib().crt_scene_settings(self.h, C.byref(w), C.byref(h), bg.ctypes.data), "crt_scene_settings")
+        self._call("crt_scene_settings", C.byref(w), C.byref(h), bg.ctypes.data)
         return {"width": w.value, "height": h.value, "background_color": tuple(bg)}
 
     # ---- camera (CRTCamera)
     def camera(self):
         pos = np.zeros(3, dtype=np.float32)
         rot = np.zeros(9, dtype=np.float32)
-        self._ok(lib().crt_scene_camera_get(self.h, pos.ctypes.data, rot.ctypes.data), "crt_scene_camera_get")
+        self._call("crt_scene_camera_get", pos.ctypes.data, rot.ctypes.data)
         return pos, rot
 
     def set_camera(self, pos=None, rot=None):
         p = _f32(pos, 3) if pos is not None else None
         r = _f32(rot, 9) if rot is not None else None
-        self._ok(lib().crt_scene_camera_set(self.h, p.ctypes.data if p is not None else None,
-                                            r.ctypes.data if r is not None else None), "crt_scene_camera_set")
+        self._call("crt_scene_camera_set", p.ctypes.data if p is not None else None, r.ctypes.data if r is not None else None)
 
     def rotate(self, dyaw, dpitch):
         self._ok(lib().crt_scene_camera_rotate(self.h, dyaw, dpitch), "rotate")
@@ -861,6 +825,76 @@ def _torch_functions():
     return _torch_fns
 
 
+# ---- what Renderer's wrappers share: the layout of every output field, and the coercion of every kind of input
+# per record of a query (n records) or per pixel of a frame (h x w pixels): the field's trailing shape and its dtype
+_FIELDS = {
+    "t": ((), np.float32), "uv": ((2,), np.float32), "inst": ((), np.uint32), "prim": ((), np.uint32),
+    "rgb": ((3,), np.float32), "normal": ((3,), np.float32), "albedo": ((3,), np.float32),
+    "dist": ((), np.float32), "point": ((3,), np.float32),
+    "grad_rays": ((8,), np.float32), "grad_points": ((4,), np.float32), "grad_xyz": ((3,), np.float32),
+    "hit_inst": ((), np.uint32), "hit_prim": ((), np.uint32), "hit_t": ((), np.float32),
+}
+
+
+def _outputs(keys, want, lead):
+    """(out, pointers): out holds a zeroed array of shape lead + the field's for every key of `keys` that is in `want`, in the order of
+    `keys`; pointers has one entry per key in that order, the array's address or None (NULL: not wanted)"""
+    out = {k: np.zeros(tuple(lead) + _FIELDS[k][0], dtype=_FIELDS[k][1]) for k in keys if k in want}
+    return out, [out[k].ctypes.data if k in out else None for k in keys]
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _ray_records(rays):
+    return np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+
+
+def _point_records(points):
+    return np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
+
+
+def _points_or_records(points):
+    """(N, 4) records as they are, (N, 3) coordinates as records with rmax = inf"""
+    pts = np.asarray(points, dtype=np.float32)
+    return make_points(pts) if pts.shape[-1:] == (3,) else _point_records(pts)
+
+
+def _ids(a):
+    return np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+
+
+def _sample_index(sample):
+    return SAMPLE_CENTRE if sample is None else int(sample)
+
+
+def _one_per_record(n, what, *arrays):
+    """the shared check of the *_backward host forms: every array that is given holds n records"""
+    if not all(len(a) == n for a in arrays if a is not None):
+        raise ValueError("%s must hold one record per %s" % what)
+
+
+_FRAME_TRAIL = {"hist_prev": (8,), "mom_prev": (2,), "variance": ()}  # floats per pixel of a frame buffer; every other one has 3
+
+
+def _frame_buffers(t, optional=(), **buffers):
+    """(h, w, t, buffers): t as a contiguous float32 (h, w) plane and every named buffer as contiguous float32 of (h, w) + its
+    trailing shape (_FRAME_TRAIL), in the order given; one named in `optional` may be None and stays None"""
+    t = np.ascontiguousarray(t, dtype=np.float32)
+    if t.ndim != 2:
+        raise ValueError("t must be (h, w)")
+    got = []
+    for name, a in buffers.items():
+        if a is not None or name not in optional:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            trail = _FRAME_TRAIL.get(name, (3,))
+            if a.shape != t.shape + trail:
+                raise ValueError("%s must be (h, w%s) where t is (h, w)" % (name, "".join(", %d" % k for k in trail)))
+        got.append(a)
+    return t.shape[0], t.shape[1], t, got
+
+
 class Renderer:
     """crt_ctx handle: the DXRTRenderer surface over HIP. Raises CrtError when no MI355X / HIP device is usable."""
 
@@ -886,9 +920,18 @@ class Renderer:
         except Exception:
             pass
 
-    def _ok(self, rc, what):
+    def _call(self, name, *args, on=None):
+        """the entry point `name` with the context's handle in front (on: another handle, a scene's); a return code other than
+        zero raises CrtError with the context's last error"""
+        rc = getattr(lib(), name)(self.h if on is None else on, *args)
         if rc:
-            raise CrtError("%s rc=%d: %s" % (what, rc, lib().crt_last_error(self.h).decode()))
+            raise CrtError("%s rc=%d: %s" % (name, rc, lib().crt_last_error(self.h).decode()))
+
+    def _call_stats(self, name, *args, stats=True):
+        """_call for an entry point whose last argument is a crt_frame_stats*: NULL unless stats; returns the dict, or None"""
+        st = FrameStats() if stats else None
+        self._call(name, *args, C.byref(st) if stats else None)
+        return st.as_dict() if stats else None
 
     def set_textures(self, textures):
         """textures: list of dicts {type: albedo|edges|checker|bitmap, color_a, color_b, scalar, pixels (H,W,C uint8)}"""
@@ -905,13 +948,13 @@ class Renderer:
                 keep.append(px)
                 arr[i].pixels = px.ctypes.data
                 arr[i].height, arr[i].width, arr[i].channels = px.shape
-        self._ok(lib().crt_set_textures(self.h, arr, len(textures)), "crt_set_textures")
+        self._call("crt_set_textures", arr, len(textures))
 
     def bvh_export_uv(self):
         info = self.bvh_info()
         uv = np.zeros(info["n_tris"], dtype=UV_DTYPE)
         has = C.c_int()
-        self._ok(lib().crt_bvh_export_uv(self.h, uv.ctypes.data, C.byref(has)), "crt_bvh_export_uv")
+        self._call("crt_bvh_export_uv", uv.ctypes.data, C.byref(has))
         return uv if has.value else None
 
     def upload(self, meshes, lights=(), materials=(), textures=None, dynamic=False):
@@ -930,7 +973,7 @@ class Renderer:
             marr[i].smooth = int(bool(m.get("smooth_shading", False)))
             marr[i].ior = float(m.get("ior", 1.0))
             marr[i].texture = int(m.get("texture", -1))
-        self._ok(lib().crt_upload_scene(self.h, mv, len(meshes), larr, len(lights), marr, len(materials)), "crt_upload_scene")
+        self._call("crt_upload_scene", mv, len(meshes), larr, len(lights), marr, len(materials))
         self._mesh_shapes = [(int(mv[i].n_vertices), bool(mv[i].normals)) for i in range(len(meshes))]
         self._geom_serial += 1
         self._mesh_transforms = [None] * len(meshes)  # per mesh the 3x4 of set_mesh_transform (None = identity), for the torch layer
@@ -938,11 +981,11 @@ class Renderer:
 
     def upload_scene(self, scene, dynamic=False):
         self.set_option("dynamic", int(bool(dynamic)))
-        self._ok(lib().crt_upload_scene_from(self.h, scene.h), "crt_upload_scene_from")
+        self._call("crt_upload_scene_from", scene.h)
         shapes = []
         for i in range(scene.mesh_count):
             mv = MeshView()
-            self._ok(lib().crt_scene_mesh(scene.h, i, C.byref(mv)), "crt_scene_mesh")
+            self._call("crt_scene_mesh", i, C.byref(mv), on=scene.h)
             shapes.append((int(mv.n_vertices), bool(mv.normals)))
         self._mesh_shapes = shapes
         self._mesh_transforms = [None] * len(shapes)
@@ -963,18 +1006,17 @@ class Renderer:
                 if a is not None and (a.dtype != torch.float32 or not a.is_contiguous() or not a.is_cuda or a.numel() % 3):
                     raise ValueError("update_vertices: device arrays must be contiguous float32 CUDA tensors of n x 3 floats")
             torch.cuda.current_stream().synchronize()
-            self._ok(lib().crt_update_vertices_device(self.h, int(mesh), xyz.numel() // 3, xyz.data_ptr(),
-                                                      normals.data_ptr() if normals is not None else None), "crt_update_vertices_device")
+            self._call("crt_update_vertices_device", int(mesh), xyz.numel() // 3, xyz.data_ptr(),
+                       normals.data_ptr() if normals is not None else None)
             return
         v = _f32(xyz).reshape(-1, 3)
         n = _f32(normals).reshape(-1, 3) if normals is not None else None
-        self._ok(lib().crt_update_vertices(self.h, int(mesh), len(v), v.ctypes.data, n.ctypes.data if n is not None else None),
-                 "crt_update_vertices")
+        self._call("crt_update_vertices", int(mesh), len(v), v.ctypes.data, _ptr(n))
 
     def set_mesh_transform(self, mesh, m):
         """m: 3x4 row-major, or 4x4 whose last row is 0 0 0 1; None = identity"""
         if m is None:
-            self._ok(lib().crt_set_mesh_transform(self.h, int(mesh), None), "crt_set_mesh_transform")
+            self._call("crt_set_mesh_transform", int(mesh), None)
             self._remember_transform(mesh, None)
             return
         a = np.asarray(m, dtype=np.float32)
@@ -985,7 +1027,7 @@ class Renderer:
         if a.shape != (3, 4):
             raise ValueError("set_mesh_transform: 3x4 or 4x4 matrix expected, got %s" % (a.shape,))
         a = np.ascontiguousarray(a)
-        self._ok(lib().crt_set_mesh_transform(self.h, int(mesh), a.ctypes.data), "crt_set_mesh_transform")
+        self._call("crt_set_mesh_transform", int(mesh), a.ctypes.data)
         self._remember_transform(mesh, None if np.array_equal(a, np.eye(3, 4, dtype=np.float32)) else a.copy())
 
     def _remember_transform(self, mesh, m):
@@ -999,14 +1041,14 @@ class Renderer:
     def refit(self):
         """apply pending updates now; returns the refit's device time in ms (0 when nothing was pending)"""
         ms = C.c_double()
-        self._ok(lib().crt_refit(self.h, C.byref(ms)), "crt_refit")
+        self._call("crt_refit", C.byref(ms))
         return ms.value
 
     def rebuild(self):
         """apply pending updates and build a new tree on the GPU from the world vertices (builder: option "gpu_builder", 0 = LBVH,
         1 = PLOC); returns the rebuild's device time in ms"""
         ms = C.c_double()
-        self._ok(lib().crt_rebuild(self.h, C.byref(ms)), "crt_rebuild")
+        self._call("crt_rebuild", C.byref(ms))
         return ms.value
 
     def mesh_vertices(self, mesh):
@@ -1017,27 +1059,27 @@ class Renderer:
         nv, has_n = shapes[int(mesh)]
         xyz = np.zeros((nv, 3), dtype=np.float32)
         nrm = np.zeros((nv, 3), dtype=np.float32) if has_n else None
-        self._ok(lib().crt_mesh_vertices(self.h, int(mesh), xyz.ctypes.data, nrm.ctypes.data if has_n else None), "crt_mesh_vertices")
+        self._call("crt_mesh_vertices", int(mesh), xyz.ctypes.data, _ptr(nrm))
         return xyz, nrm
 
     def set_camera(self, pos, rot):
         p, r = _f32(pos, 3), _f32(rot, 9)
-        self._ok(lib().crt_set_camera(self.h, p.ctypes.data, r.ctypes.data), "crt_set_camera")
+        self._call("crt_set_camera", p.ctypes.data, r.ctypes.data)
         self.camera = np.concatenate([p.reshape(3), r.reshape(9)])  # the 12 floats of the batch entry points (TemporalHistory.push)
 
     def set_camera_from(self, scene):
-        self._ok(lib().crt_set_camera_from(self.h, scene.h), "crt_set_camera_from")
+        self._call("crt_set_camera_from", scene.h)
         self.camera = np.concatenate(scene.camera())
 
     def change_shading_mode(self, mode):
-        self._ok(lib().crt_set_shading_mode(self.h, int(mode)), "crt_set_shading_mode")
+        self._call("crt_set_shading_mode", int(mode))
 
     def set_miss_color(self, rgb):
         c = _f32(rgb, 3)
-        self._ok(lib().crt_set_miss_color(self.h, c.ctypes.data), "crt_set_miss_color")
+        self._call("crt_set_miss_color", c.ctypes.data)
 
     def set_counting(self, on):
-        self._ok(lib().crt_set_counting(self.h, int(bool(on))), "crt_set_counting")
+        self._call("crt_set_counting", int(bool(on)))
 
     def set_path_params(self, spp=4, max_bounces=3, seed=1234):
         """mode 200 (path tracing) parameters"""
@@ -1046,91 +1088,69 @@ class Renderer:
         self.set_option("seed", seed)
 
     def set_option(self, name, value):
-        self._ok(lib().crt_set_option(self.h, name.encode(), int(value)), "crt_set_option")
+        self._call("crt_set_option", name.encode(), int(value))
 
     def set_accumulation(self, max_samples):
         """mode 200: frames add their samples to per-pixel sums while the view holds still, up to max_samples per pixel
         (0 = off); always starts over (include/crt_hip.h)"""
-        self._ok(lib().crt_set_accumulation(self.h, int(max_samples)), "crt_set_accumulation")
+        self._call("crt_set_accumulation", int(max_samples))
 
     def reset_accumulation(self):
-        self._ok(lib().crt_reset_accumulation(self.h), "crt_reset_accumulation")
+        self._call("crt_reset_accumulation")
 
     def accumulated_samples(self):
         """samples per pixel in the current sums (0 when accumulation is off or was reset)"""
         n = C.c_uint32()
-        self._ok(lib().crt_accumulated_samples(self.h, C.byref(n)), "crt_accumulated_samples")
+        self._call("crt_accumulated_samples", C.byref(n))
         return n.value
 
     # ---- batched ray queries (include/crt_hip.h): records of 8 floats {ox, oy, oz, tmin, dx, dy, dz, tmax}, see make_rays
     def trace_rays(self, rays, want=("t", "uv", "inst", "prim")):
         """closest hit of every ray (host buffers, synchronous).  Returns a dict of the wanted arrays -- t (N,) float32, uv (N, 2)
         float32, inst / prim (N,) uint32 (MISS on a miss, t = the ray's tmax) -- plus 'stats'."""
-        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
-        n = len(r)
-        out = {}
-        if "t" in want:
-            out["t"] = np.zeros(n, dtype=np.float32)
-        if "uv" in want:
-            out["uv"] = np.zeros((n, 2), dtype=np.float32)
-        if "inst" in want:
-            out["inst"] = np.zeros(n, dtype=np.uint32)
-        if "prim" in want:
-            out["prim"] = np.zeros(n, dtype=np.uint32)
-        st = FrameStats()
-
-        def p(k):
-            return out[k].ctypes.data if k in out else None
-        self._ok(lib().crt_trace_rays(self.h, n, r.ctypes.data, p("t"), p("uv"), p("inst"), p("prim"), C.byref(st)), "crt_trace_rays")
-        out["stats"] = st.as_dict()
-        return out
-
-    def occluded(self, rays):
-        """occlusion of every ray on (tmin, tmax): bool array (host buffers, synchronous)"""
-        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
-        out = np.zeros(len(r), dtype=np.bool_)
-        self._ok(lib().crt_occluded_rays(self.h, len(r), r.ctypes.data, out.ctypes.data, None), "crt_occluded_rays")
+        r = _ray_records(rays)
+        out, ptrs = _outputs(("t", "uv", "inst", "prim"), want, (len(r),))
+        out["stats"] = self._call_stats("crt_trace_rays", len(r), r.ctypes.data, *ptrs)
         return out
 
     def trace_rays_device(self, n, d_rays, d_t=None, d_uv=None, d_inst=None, d_prim=None, stats=False):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_trace_rays_device(self.h, int(n), d_rays, d_t, d_uv, d_inst, d_prim, C.byref(st) if stats else None),
-                 "crt_trace_rays_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_trace_rays_device", int(n), d_rays, d_t, d_uv, d_inst, d_prim, stats=stats)
+
+    def occluded(self, rays):
+        """occlusion of every ray on (tmin, tmax): bool array (host buffers, synchronous)"""
+        r = _ray_records(rays)
+        out = np.zeros(len(r), dtype=np.bool_)
+        self._call("crt_occluded_rays", len(r), r.ctypes.data, out.ctypes.data, None)
+        return out
 
     def occluded_device(self, n, d_rays, d_occluded, stats=False):
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_occluded_rays_device(self.h, int(n), d_rays, d_occluded, C.byref(st) if stats else None),
-                 "crt_occluded_rays_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_occluded_rays_device", int(n), d_rays, d_occluded, stats=stats)
+
+    def count_hits(self, rays):
+        """number of triangles every ray crosses in (tmin, tmax): (N,) uint32 (host buffers, synchronous; rays as make_rays)"""
+        r = _ray_records(rays)
+        out = np.zeros(len(r), dtype=np.uint32)
+        self._call("crt_count_hits", len(r), r.ctypes.data, out.ctypes.data, None)
+        return out
+
+    def count_hits_device(self, n, d_rays, d_count, stats=False):
+        return self._call_stats("crt_count_hits_device", int(n), d_rays, d_count, stats=stats)
 
     # ---- shaded ray queries (include/crt_hip.h): the closest hit of every record shaded in the current mode (0..100)
     def shade_rays(self, rays, want=("rgb", "normal", "albedo", "t", "uv", "inst", "prim")):
         """colour, shading normal and albedo at the closest hit of every ray (host buffers, synchronous).  Returns a dict of the
         wanted arrays -- rgb / normal / albedo (N, 3) float32 (miss: the miss colour, zero, zero) and the arrays of trace_rays
         -- plus 'stats'."""
-        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
-        n = len(r)
-        shapes = {"rgb": ((n, 3), np.float32), "normal": ((n, 3), np.float32), "albedo": ((n, 3), np.float32), "t": ((n,), np.float32),
-                  "uv": ((n, 2), np.float32), "inst": ((n,), np.uint32), "prim": ((n,), np.uint32)}
-        out = {k: np.zeros(*shapes[k]) for k in shapes if k in want}
-        st = FrameStats()
-
-        def p(k):
-            return out[k].ctypes.data if k in out else None
-        self._ok(lib().crt_shade_rays(self.h, n, r.ctypes.data, p("rgb"), p("normal"), p("albedo"), p("t"), p("uv"), p("inst"), p("prim"),
-                                      C.byref(st)), "crt_shade_rays")
-        out["stats"] = st.as_dict()
+        r = _ray_records(rays)
+        out, ptrs = _outputs(("rgb", "normal", "albedo", "t", "uv", "inst", "prim"), want, (len(r),))
+        out["stats"] = self._call_stats("crt_shade_rays", len(r), r.ctypes.data, *ptrs)
         return out
 
     def shade_rays_device(self, n, d_rays, d_rgb=None, d_normal=None, d_albedo=None, d_t=None, d_uv=None, d_inst=None, d_prim=None,
                           stats=False):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_shade_rays_device(self.h, int(n), d_rays, d_rgb, d_normal, d_albedo, d_t, d_uv, d_inst, d_prim,
-                                             C.byref(st) if stats else None), "crt_shade_rays_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_shade_rays_device", int(n), d_rays, d_rgb, d_normal, d_albedo, d_t, d_uv, d_inst, d_prim, stats=stats)
 
     # ---- path-traced ray queries (include/crt_hip.h): mode-200 radiance of every record, whatever the current mode
     def path_rays(self, rays, ids=None, first_sample=0, n_samples=1, sums=None, want=("rgb", "t", "uv", "inst", "prim")):
@@ -1139,36 +1159,25 @@ class Renderer:
         carries the per-record sample sums from call to call (read when first_sample > 0, always written; rgb is then the mean
         over first_sample + n_samples samples).  Returns a dict of the wanted arrays -- rgb (N, 3) float32 and the arrays of
         trace_rays -- plus 'stats'."""
-        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        r = _ray_records(rays)
         n = len(r)
-        shapes = {"rgb": ((n, 3), np.float32), "t": ((n,), np.float32), "uv": ((n, 2), np.float32), "inst": ((n,), np.uint32),
-                  "prim": ((n,), np.uint32)}
-        out = {k: np.zeros(*shapes[k]) for k in shapes if k in want}
+        out, (rgb, *hit) = _outputs(("rgb", "t", "uv", "inst", "prim"), want, (n,))
         i = None
         if ids is not None:
-            i = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            i = _ids(ids)
             if len(i) != n:
                 raise ValueError("ids must hold one uint32 per ray")
         if sums is not None and (not isinstance(sums, np.ndarray) or sums.dtype != np.float64 or sums.shape != (n, 3)
                                  or not sums.flags.c_contiguous or not sums.flags.writeable):
             raise ValueError("sums must be a writeable C-contiguous (N, 3) float64 array")
-        st = FrameStats()
-
-        def p(k):
-            return out[k].ctypes.data if k in out else None
-        self._ok(lib().crt_path_rays(self.h, n, r.ctypes.data, None if i is None else i.ctypes.data, int(first_sample), int(n_samples),
-                                     p("rgb"), None if sums is None else sums.ctypes.data, p("t"), p("uv"), p("inst"), p("prim"),
-                                     C.byref(st)), "crt_path_rays")
-        out["stats"] = st.as_dict()
+        out["stats"] = self._call_stats("crt_path_rays", n, r.ctypes.data, _ptr(i), int(first_sample), int(n_samples), rgb, _ptr(sums), *hit)
         return out
 
     def path_rays_device(self, n, d_rays, d_ids=None, first_sample=0, n_samples=1, d_rgb=None, d_sums=None, d_t=None, d_uv=None,
                          d_inst=None, d_prim=None, stats=False):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_path_rays_device(self.h, int(n), d_rays, d_ids, int(first_sample), int(n_samples), d_rgb, d_sums, d_t, d_uv,
-                                            d_inst, d_prim, C.byref(st) if stats else None), "crt_path_rays_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_path_rays_device", int(n), d_rays, d_ids, int(first_sample), int(n_samples), d_rgb, d_sums, d_t, d_uv,
+                                d_inst, d_prim, stats=stats)
 
     # ---- camera rays, guide buffers and the denoiser (include/crt_hip.h)
     def camera_rays(self, w, h, sample=None):
@@ -1176,101 +1185,69 @@ class Renderer:
         sample None: the pixel-centre rays of modes 0..100; an integer below 2^24: the jittered rays a mode-200 frame traces for
         that frame sample index with the context's seed."""
         rays = np.zeros((int(w) * int(h), 8), dtype=np.float32)
-        self._ok(lib().crt_camera_rays(self.h, int(w), int(h), SAMPLE_CENTRE if sample is None else int(sample), rays.ctypes.data, None),
-                 "crt_camera_rays")
+        self._call("crt_camera_rays", int(w), int(h), _sample_index(sample), rays.ctypes.data, None)
         return rays
 
     def camera_rays_device(self, w, h, d_rays, sample=None, stats=False):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_camera_rays_device(self.h, int(w), int(h), SAMPLE_CENTRE if sample is None else int(sample), d_rays,
-                                              C.byref(st) if stats else None), "crt_camera_rays_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_camera_rays_device", int(w), int(h), _sample_index(sample), d_rays, stats=stats)
 
     def frame_guides(self, w, h, want=("normal", "albedo", "t")):
         """the guide buffers of a w x h frame (host buffers, synchronous): per pixel the shading normal and the albedo, (h, w, 3)
         float32, and t, (h, w) float32, of the pixel-centre camera ray (miss: zero, zero, 10000), in any shading mode.  Returns a
         dict of the wanted arrays plus 'stats'."""
         w, h = int(w), int(h)
-        shapes = {"normal": (h, w, 3), "albedo": (h, w, 3), "t": (h, w)}
-        out = {k: np.zeros(shapes[k], dtype=np.float32) for k in shapes if k in want}
-        st = FrameStats()
-
-        def p(k):
-            return out[k].ctypes.data if k in out else None
-        self._ok(lib().crt_frame_guides(self.h, w, h, p("normal"), p("albedo"), p("t"), C.byref(st)), "crt_frame_guides")
-        out["stats"] = st.as_dict()
+        out, ptrs = _outputs(("normal", "albedo", "t"), want, (h, w))
+        out["stats"] = self._call_stats("crt_frame_guides", w, h, *ptrs)
         return out
 
     def frame_guides_device(self, w, h, d_normal=None, d_albedo=None, d_t=None, stats=False):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_frame_guides_device(self.h, int(w), int(h), d_normal, d_albedo, d_t, C.byref(st) if stats else None),
-                 "crt_frame_guides_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_frame_guides_device", int(w), int(h), d_normal, d_albedo, d_t, stats=stats)
 
     def denoise(self, rgb, normal, albedo, t, **params):
         """the edge-avoiding a-trous filter (host buffers, synchronous): rgb, normal, albedo (h, w, 3) and t (h, w) float32, e.g. a
         mode-200 frame's 'rgb' and frame_guides' arrays.  params: the fields of DenoiseParams (iterations, sigma_color,
         sigma_normal, sigma_depth, demodulate).  Returns the filtered (h, w, 3) float32 image."""
-        t = np.ascontiguousarray(t, dtype=np.float32)
-        if t.ndim != 2:
-            raise ValueError("t must be (h, w)")
-        h, w = t.shape
-        bufs = [np.ascontiguousarray(a, dtype=np.float32) for a in (rgb, normal, albedo)]
-        for a in bufs:
-            if a.shape != (h, w, 3):
-                raise ValueError("rgb, normal and albedo must be (h, w, 3) where t is (h, w)")
+        h, w, t, (rgb, normal, albedo) = _frame_buffers(t, rgb=rgb, normal=normal, albedo=albedo)
         out = np.zeros((h, w, 3), dtype=np.float32)
         prm = DenoiseParams(**params)
-        self._ok(lib().crt_denoise(self.h, w, h, bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data, t.ctypes.data, out.ctypes.data,
-                                   C.byref(prm), None), "crt_denoise")
+        self._call("crt_denoise", w, h, rgb.ctypes.data, normal.ctypes.data, albedo.ctypes.data, t.ctypes.data, out.ctypes.data,
+                   C.byref(prm), None)
         return out
 
     def denoise_device(self, w, h, d_rgb, d_normal, d_albedo, d_t, d_out, stats=False, **params):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); d_out may equal d_rgb; asynchronous on the context's
         stream unless stats"""
-        st = FrameStats() if stats else None
         prm = DenoiseParams(**params)
-        self._ok(lib().crt_denoise_device(self.h, int(w), int(h), d_rgb, d_normal, d_albedo, d_t, d_out, C.byref(prm),
-                                          C.byref(st) if stats else None), "crt_denoise_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_denoise_device", int(w), int(h), d_rgb, d_normal, d_albedo, d_t, d_out, C.byref(prm), stats=stats)
 
     # ---- temporal reprojection (include/crt_hip.h): cameras are 12 floats {pos[3], rot3x3 row-major[9]}
+    def _temporal(self, name, w, h, cam_cur, cam_prev, pointers, prm, stats):
+        """what the temporal entry points share: w, h, the two cameras as 12 floats each, the pointers, the parameter struct, stats"""
+        cc, cp = _f32(cam_cur, 12), _f32(cam_prev, 12)
+        return self._call_stats(name, int(w), int(h), cc.ctypes.data, cp.ctypes.data, *pointers, C.byref(prm), stats=stats)
+
+    def _temporal_accumulate(self, form, w, h, cam_cur, cam_prev, frame, prev_point, history, stats, params):
+        """crt_temporal_accumulate + form ("" or "_device"), or its _motion twin when prev_point is given: frame = the pointers
+        rgb, normal, albedo, t; history = hist_prev, hist_next, out; prev_point goes between the two"""
+        motion = [] if prev_point is None else [prev_point]
+        return self._temporal("crt_temporal_accumulate" + ("_motion" if motion else "") + form, w, h, cam_cur, cam_prev,
+                              (*frame, *motion, *history), TemporalParams(**params), stats)
+
     def temporal_accumulate(self, cam_cur, cam_prev, rgb, normal, albedo, t, hist_prev=None, want_out=True, prev_point=None, **params):
         """one frame blended with the reprojected history (host buffers, synchronous): rgb, normal, albedo (h, w, 3) and t (h, w)
         float32 of this frame (albedo may be None with demodulate=0), hist_prev None or the (h, w, 8) float32 records an earlier
         call returned, taken with camera cam_prev.  prev_point: None, or (h, w, 3) float32 previous points (frame_motion): the
         call then goes to crt_temporal_accumulate_motion.  params: the fields of TemporalParams.  Returns (hist_next, out): the
         new records and the accumulated (h, w, 3) image (None when not want_out)."""
-        t = np.ascontiguousarray(t, dtype=np.float32)
-        if t.ndim != 2:
-            raise ValueError("t must be (h, w)")
-        h, w = t.shape
-        bufs = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (rgb, normal, albedo)]
-        for a in bufs:
-            if a is not None and a.shape != (h, w, 3):
-                raise ValueError("rgb, normal and albedo must be (h, w, 3) where t is (h, w)")
-        hp = None if hist_prev is None else np.ascontiguousarray(hist_prev, dtype=np.float32)
-        if hp is not None and hp.shape != (h, w, 8):
-            raise ValueError("hist_prev must be (h, w, 8)")
-        cc, cp = _f32(cam_cur, 12), _f32(cam_prev, 12)
+        h, w, t, bufs = _frame_buffers(t, optional=("rgb", "normal", "albedo", "hist_prev", "prev_point"), rgb=rgb, normal=normal,
+                                       albedo=albedo, hist_prev=hist_prev, prev_point=prev_point)
+        rgb, normal, albedo, hp, pp = map(_ptr, bufs)
         hist = np.zeros((h, w, 8), dtype=np.float32)
         out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
-
-        def p(a):
-            return None if a is None else a.ctypes.data
-        prm = TemporalParams(**params)
-        if prev_point is not None:
-            pp = np.ascontiguousarray(prev_point, dtype=np.float32)
-            if pp.shape != (h, w, 3):
-                raise ValueError("prev_point must be (h, w, 3)")
-            self._ok(lib().crt_temporal_accumulate_motion(self.h, w, h, cc.ctypes.data, cp.ctypes.data, p(bufs[0]), p(bufs[1]), p(bufs[2]),
-                                                          t.ctypes.data, pp.ctypes.data, p(hp), hist.ctypes.data, p(out), C.byref(prm), None),
-                     "crt_temporal_accumulate_motion")
-            return hist, out
-        self._ok(lib().crt_temporal_accumulate(self.h, w, h, cc.ctypes.data, cp.ctypes.data, p(bufs[0]), p(bufs[1]), p(bufs[2]), t.ctypes.data,
-                                               p(hp), hist.ctypes.data, p(out), C.byref(prm), None), "crt_temporal_accumulate")
+        self._temporal_accumulate("", w, h, cam_cur, cam_prev, (rgb, normal, albedo, t.ctypes.data), pp, (hp, hist.ctypes.data, _ptr(out)),
+                                  False, params)
         return hist, out
 
     def temporal_accumulate_device(self, w, h, cam_cur, cam_prev, d_rgb, d_normal, d_albedo, d_t, d_hist_prev, d_hist_next, d_out=None,
@@ -1279,18 +1256,8 @@ class Renderer:
         no history; d_out may equal d_rgb or be None; d_prev_point: None, or the previous points of the frame
         (frame_motion_device; the call then goes to crt_temporal_accumulate_motion_device); asynchronous on the context's stream
         unless stats"""
-        st = FrameStats() if stats else None
-        cc, cp = _f32(cam_cur, 12), _f32(cam_prev, 12)
-        prm = TemporalParams(**params)
-        if d_prev_point is not None:
-            self._ok(lib().crt_temporal_accumulate_motion_device(self.h, int(w), int(h), cc.ctypes.data, cp.ctypes.data, d_rgb, d_normal,
-                                                                 d_albedo, d_t, d_prev_point, d_hist_prev, d_hist_next, d_out, C.byref(prm),
-                                                                 C.byref(st) if stats else None), "crt_temporal_accumulate_motion_device")
-            return st.as_dict() if stats else None
-        self._ok(lib().crt_temporal_accumulate_device(self.h, int(w), int(h), cc.ctypes.data, cp.ctypes.data, d_rgb, d_normal, d_albedo, d_t,
-                                                      d_hist_prev, d_hist_next, d_out, C.byref(prm), C.byref(st) if stats else None),
-                 "crt_temporal_accumulate_device")
-        return st.as_dict() if stats else None
+        return self._temporal_accumulate("_device", w, h, cam_cur, cam_prev, (d_rgb, d_normal, d_albedo, d_t), d_prev_point,
+                                         (d_hist_prev, d_hist_next, d_out), stats, params)
 
     # ---- variance (include/crt_hip.h): luminance moments beside the history, and the filter their variance steers
     def temporal_variance(self, cam_cur, cam_prev, rgb, normal, albedo, t, hist_prev=None, mom_prev=None, want_out=True, prev_point=None,
@@ -1299,32 +1266,16 @@ class Renderer:
         an earlier call returned, given exactly when hist_prev is.  params: the fields of TemporalVarianceParams (TemporalParams'
         and alpha_moments, min_history).  Returns (hist_next, mom_next, variance, out): (h, w, 8), (h, w, 2), (h, w) and the
         accumulated (h, w, 3) image (None when not want_out)."""
-        t = np.ascontiguousarray(t, dtype=np.float32)
-        if t.ndim != 2:
-            raise ValueError("t must be (h, w)")
-        h, w = t.shape
-        bufs = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (rgb, normal, albedo, prev_point)]
-        for a in bufs:
-            if a is not None and a.shape != (h, w, 3):
-                raise ValueError("rgb, normal, albedo and prev_point must be (h, w, 3) where t is (h, w)")
-        hp = None if hist_prev is None else np.ascontiguousarray(hist_prev, dtype=np.float32)
-        if hp is not None and hp.shape != (h, w, 8):
-            raise ValueError("hist_prev must be (h, w, 8)")
-        mp = None if mom_prev is None else np.ascontiguousarray(mom_prev, dtype=np.float32)
-        if mp is not None and mp.shape != (h, w, 2):
-            raise ValueError("mom_prev must be (h, w, 2)")
-        cc, cp = _f32(cam_cur, 12), _f32(cam_prev, 12)
+        h, w, t, bufs = _frame_buffers(t, optional=("rgb", "normal", "albedo", "prev_point", "hist_prev", "mom_prev"), rgb=rgb, normal=normal,
+                                       albedo=albedo, prev_point=prev_point, hist_prev=hist_prev, mom_prev=mom_prev)
+        rgb, normal, albedo, pp, hp, mp = map(_ptr, bufs)
         hist = np.zeros((h, w, 8), dtype=np.float32)
         mom = np.zeros((h, w, 2), dtype=np.float32)
         var = np.zeros((h, w), dtype=np.float32)
         out = np.zeros((h, w, 3), dtype=np.float32) if want_out else None
-
-        def p(a):
-            return None if a is None else a.ctypes.data
-        prm = TemporalVarianceParams(**params)
-        self._ok(lib().crt_temporal_variance(self.h, w, h, cc.ctypes.data, cp.ctypes.data, p(bufs[0]), p(bufs[1]), p(bufs[2]), t.ctypes.data,
-                                             p(bufs[3]), p(hp), hist.ctypes.data, p(mp), mom.ctypes.data, var.ctypes.data, p(out),
-                                             C.byref(prm), None), "crt_temporal_variance")
+        self._temporal("crt_temporal_variance", w, h, cam_cur, cam_prev, (rgb, normal, albedo, t.ctypes.data, pp, hp, hist.ctypes.data, mp,
+                                                                          mom.ctypes.data, var.ctypes.data, _ptr(out)),
+                       TemporalVarianceParams(**params), False)
         return hist, mom, var, out
 
     def temporal_variance_device(self, w, h, cam_cur, cam_prev, d_rgb, d_normal, d_albedo, d_t, d_hist_prev, d_hist_next, d_mom_prev,
@@ -1332,118 +1283,84 @@ class Renderer:
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); the cameras are host arrays of 12 floats; d_hist_prev and
         d_mom_prev None = no history; d_out may equal d_rgb or be None; d_prev_point: None, or the previous points of the frame;
         asynchronous on the context's stream unless stats"""
-        st = FrameStats() if stats else None
-        cc, cp = _f32(cam_cur, 12), _f32(cam_prev, 12)
-        prm = TemporalVarianceParams(**params)
-        self._ok(lib().crt_temporal_variance_device(self.h, int(w), int(h), cc.ctypes.data, cp.ctypes.data, d_rgb, d_normal, d_albedo, d_t,
-                                                    d_prev_point, d_hist_prev, d_hist_next, d_mom_prev, d_mom_next, d_variance, d_out,
-                                                    C.byref(prm), C.byref(st) if stats else None), "crt_temporal_variance_device")
-        return st.as_dict() if stats else None
+        return self._temporal("crt_temporal_variance_device", w, h, cam_cur, cam_prev, (d_rgb, d_normal, d_albedo, d_t, d_prev_point, d_hist_prev,
+                                                                                        d_hist_next, d_mom_prev, d_mom_next, d_variance, d_out),
+                              TemporalVarianceParams(**params), stats)
 
     def denoise_variance(self, rgb, normal, albedo, t, variance, want_variance=False, **params):
         """the a-trous filter with a variance-driven luminance weight (host buffers, synchronous): denoise's buffers and the
         (h, w) float32 variance of temporal_variance.  params: the fields of DenoiseVarianceParams; demodulate must be the
         temporal call's.  Returns the filtered (h, w, 3) float32 image, with want_variance (image, filtered variance)."""
-        t = np.ascontiguousarray(t, dtype=np.float32)
-        if t.ndim != 2:
-            raise ValueError("t must be (h, w)")
-        h, w = t.shape
-        bufs = [np.ascontiguousarray(a, dtype=np.float32) for a in (rgb, normal, albedo)]
-        for a in bufs:
-            if a.shape != (h, w, 3):
-                raise ValueError("rgb, normal and albedo must be (h, w, 3) where t is (h, w)")
-        var = np.ascontiguousarray(variance, dtype=np.float32)
-        if var.shape != (h, w):
-            raise ValueError("variance must be (h, w)")
+        h, w, t, (rgb, normal, albedo, var) = _frame_buffers(t, rgb=rgb, normal=normal, albedo=albedo, variance=variance)
         out = np.zeros((h, w, 3), dtype=np.float32)
         vout = np.zeros((h, w), dtype=np.float32) if want_variance else None
         prm = DenoiseVarianceParams(**params)
-        self._ok(lib().crt_denoise_variance(self.h, w, h, bufs[0].ctypes.data, bufs[1].ctypes.data, bufs[2].ctypes.data, t.ctypes.data,
-                                            var.ctypes.data, out.ctypes.data, None if vout is None else vout.ctypes.data, C.byref(prm), None),
-                 "crt_denoise_variance")
+        self._call("crt_denoise_variance", w, h, rgb.ctypes.data, normal.ctypes.data, albedo.ctypes.data, t.ctypes.data, var.ctypes.data,
+                   out.ctypes.data, _ptr(vout), C.byref(prm), None)
         return (out, vout) if want_variance else out
 
     def denoise_variance_device(self, w, h, d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, d_variance_out=None, stats=False, **params):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); d_out may equal d_rgb, d_variance_out may equal d_variance
         or be None; asynchronous on the context's stream unless stats"""
-        st = FrameStats() if stats else None
         prm = DenoiseVarianceParams(**params)
-        self._ok(lib().crt_denoise_variance_device(self.h, int(w), int(h), d_rgb, d_normal, d_albedo, d_t, d_variance, d_out, d_variance_out,
-                                                   C.byref(prm), C.byref(st) if stats else None), "crt_denoise_variance_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_denoise_variance_device", int(w), int(h), d_rgb, d_normal, d_albedo, d_t, d_variance, d_out,
+                                d_variance_out, C.byref(prm), stats=stats)
 
     # ---- motion (include/crt_hip.h): previous positions of hits on a dynamic scene whose meshes move
     def motion_snapshot(self):
         """remember the current world vertices as "previous" (after a frame is rendered, before the meshes are moved)"""
-        self._ok(lib().crt_motion_snapshot(self.h), "crt_motion_snapshot")
+        self._call("crt_motion_snapshot")
 
     def previous_points(self, inst, prim, uv):
         """where the hits (inst, prim, uv) of trace_rays / shade_rays / list_hits were at the last snapshot: (N, 3) float32, NaN
         for a miss and for a triangle that did not move (host buffers, synchronous)"""
-        i = np.ascontiguousarray(inst, dtype=np.uint32).reshape(-1)
-        q = np.ascontiguousarray(prim, dtype=np.uint32).reshape(-1)
+        i, q = _ids(inst), _ids(prim)
         u = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
         if not len(i) == len(q) == len(u):
             raise ValueError("inst, prim and uv must hold one record per hit")
         out = np.zeros((len(i), 3), dtype=np.float32)
-        self._ok(lib().crt_previous_points(self.h, len(i), i.ctypes.data, q.ctypes.data, u.ctypes.data, out.ctypes.data, None),
-                 "crt_previous_points")
+        self._call("crt_previous_points", len(i), i.ctypes.data, q.ctypes.data, u.ctypes.data, out.ctypes.data, None)
         return out
 
     def previous_points_device(self, n, d_inst, d_prim, d_uv, d_point, stats=False):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_previous_points_device(self.h, int(n), d_inst, d_prim, d_uv, d_point, C.byref(st) if stats else None),
-                 "crt_previous_points_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_previous_points_device", int(n), d_inst, d_prim, d_uv, d_point, stats=stats)
 
     def frame_motion(self, w, h):
         """the previous points of a w x h frame's pixel-centre camera rays, (h, w, 3) float32: what temporal_accumulate and
         TemporalHistory.push take as prev_point (host buffer, synchronous)"""
         out = np.zeros((int(h), int(w), 3), dtype=np.float32)
-        self._ok(lib().crt_frame_motion(self.h, int(w), int(h), out.ctypes.data, None), "crt_frame_motion")
+        self._call("crt_frame_motion", int(w), int(h), out.ctypes.data, None)
         return out
 
     def frame_motion_device(self, w, h, d_prev_point, stats=False):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_frame_motion_device(self.h, int(w), int(h), d_prev_point, C.byref(st) if stats else None), "crt_frame_motion_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_frame_motion_device", int(w), int(h), d_prev_point, stats=stats)
 
     # ---- point queries (include/crt_hip.h): records of 4 floats {x, y, z, rmax}, see make_points
     def closest_points(self, points, want=("dist", "point", "uv", "inst", "prim")):
         """closest surface point of every point within its rmax (host buffers, synchronous).  Returns a dict of the wanted
         arrays -- dist (N,) float32, point (N, 3) float32, uv (N, 2) float32, inst / prim (N,) uint32 (MISS on a miss, dist =
         the record's rmax, point = the query point) -- plus 'stats'."""
-        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
-        n = len(pts)
-        shapes = {"dist": ((n,), np.float32), "point": ((n, 3), np.float32), "uv": ((n, 2), np.float32),
-                  "inst": ((n,), np.uint32), "prim": ((n,), np.uint32)}
-        out = {k: np.zeros(*shapes[k]) for k in shapes if k in want}
-        st = FrameStats()
-
-        def p(k):
-            return out[k].ctypes.data if k in out else None
-        self._ok(lib().crt_closest_points(self.h, n, pts.ctypes.data, p("dist"), p("point"), p("uv"), p("inst"), p("prim"), C.byref(st)),
-                 "crt_closest_points")
-        out["stats"] = st.as_dict()
+        pts = _point_records(points)
+        out, ptrs = _outputs(("dist", "point", "uv", "inst", "prim"), want, (len(pts),))
+        out["stats"] = self._call_stats("crt_closest_points", len(pts), pts.ctypes.data, *ptrs)
         return out
 
-    def count_hits(self, rays):
-        """number of triangles every ray crosses in (tmin, tmax): (N,) uint32 (host buffers, synchronous; rays as make_rays)"""
-        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
-        out = np.zeros(len(r), dtype=np.uint32)
-        self._ok(lib().crt_count_hits(self.h, len(r), r.ctypes.data, out.ctypes.data, None), "crt_count_hits")
-        return out
+    def closest_points_device(self, n, d_points, d_dist=None, d_point=None, d_uv=None, d_inst=None, d_prim=None, stats=False):
+        """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
+        return self._call_stats("crt_closest_points_device", int(n), d_points, d_dist, d_point, d_uv, d_inst, d_prim, stats=stats)
 
     def occupancy(self, points):
         """inside / outside of every point (majority of three crossing parities): (N,) bool (host buffers, synchronous).
         points: (N, 4) records (make_points) or (N, 3) coordinates."""
-        pts = np.asarray(points, dtype=np.float32)
-        pts = make_points(pts) if pts.shape[-1:] == (3,) else np.ascontiguousarray(pts).reshape(-1, 4)
+        pts = _points_or_records(points)
         out = np.zeros(len(pts), dtype=np.bool_)
-        self._ok(lib().crt_occupancy(self.h, len(pts), pts.ctypes.data, out.ctypes.data, None), "crt_occupancy")
+        self._call("crt_occupancy", len(pts), pts.ctypes.data, out.ctypes.data, None)
         return out
+
+    def occupancy_device(self, n, d_points, d_inside, stats=False):
+        return self._call_stats("crt_occupancy_device", int(n), d_points, d_inside, stats=stats)
 
     def signed_distance(self, points, sign="parity", beta=2.0, threshold=0.5):
         """distance to the closest surface point, negated where the point is inside: (N,) float32.  sign = "parity": inside by
@@ -1451,8 +1368,7 @@ class Renderer:
         points: (N, 4) records (make_points; rmax bounds the search) or (N, 3) coordinates (rmax = inf)."""
         if sign not in ("parity", "winding"):
             raise ValueError("sign must be 'parity' or 'winding'")
-        pts = np.asarray(points, dtype=np.float32)
-        pts = make_points(pts) if pts.shape[-1:] == (3,) else np.ascontiguousarray(pts).reshape(-1, 4)
+        pts = _points_or_records(points)
         d = self.closest_points(pts, want=("dist",))["dist"]
         inside = self.occupancy(pts) if sign == "parity" else self.inside_winding(pts, beta, threshold)
         return np.where(inside, -d, d).astype(np.float32)
@@ -1462,108 +1378,80 @@ class Renderer:
         """generalised winding number of every point: (N,) float32 (host buffers, synchronous).  beta > 0: clusters farther than
         beta x their radius are taken by their dipole; beta <= 0: exact, the sum over every triangle.
         points: (N, 4) records (make_points; rmax is ignored) or (N, 3) coordinates."""
-        pts = np.asarray(points, dtype=np.float32)
-        pts = make_points(pts) if pts.shape[-1:] == (3,) else np.ascontiguousarray(pts).reshape(-1, 4)
+        pts = _points_or_records(points)
         out = np.zeros(len(pts), dtype=np.float32)
-        self._ok(lib().crt_winding_numbers(self.h, len(pts), pts.ctypes.data, float(beta), out.ctypes.data, None), "crt_winding_numbers")
+        self._call("crt_winding_numbers", len(pts), pts.ctypes.data, float(beta), out.ctypes.data, None)
         return out
 
     def winding_numbers_device(self, n, d_points, d_w, beta=2.0, stats=False):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_winding_numbers_device(self.h, int(n), d_points, float(beta), d_w, C.byref(st) if stats else None),
-                 "crt_winding_numbers_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_winding_numbers_device", int(n), d_points, float(beta), d_w, stats=stats)
 
     def winding_moments(self):
         """the moment table the winding walk reads: (n_nodes4, 32) float32, {p~, r} of child slots 0..3, then {N~, 0} of slots 0..3"""
         n4 = C.c_uint32(0)
-        self._ok(lib().crt_bvh_info4(self.h, C.byref(n4), None), "crt_bvh_info4")
+        self._call("crt_bvh_info4", C.byref(n4), None)
         out = np.zeros((n4.value, 32), dtype=np.float32)
         if n4.value:
-            self._ok(lib().crt_winding_moments_export(self.h, out.ctypes.data), "crt_winding_moments_export")
+            self._call("crt_winding_moments_export", out.ctypes.data)
         return out
 
     def inside_winding(self, points, beta=2.0, threshold=0.5):
         """inside / outside of every point by its winding number: (N,) bool, winding_numbers(points, beta) > threshold"""
         return self.winding_numbers(points, beta) > np.float32(threshold)
 
-    def closest_points_device(self, n, d_points, d_dist=None, d_point=None, d_uv=None, d_inst=None, d_prim=None, stats=False):
-        """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_closest_points_device(self.h, int(n), d_points, d_dist, d_point, d_uv, d_inst, d_prim,
-                                                 C.byref(st) if stats else None), "crt_closest_points_device")
-        return st.as_dict() if stats else None
-
     # ---- gradients (include/crt_hip.h, "gradients"): the backward pass of trace_rays and closest_points; dynamic scenes only
     def _total_vertices(self):
         return sum(nv for nv, _ in getattr(self, "_mesh_shapes", []))
+
+    def _grad_outputs(self, per_record, n, want):
+        """_outputs of the two gradients of a *_backward host form: `per_record` over n records, grad_xyz over all vertices"""
+        out, ptrs = _outputs((per_record,), want, (n,))
+        xyz, xyz_ptrs = _outputs(("grad_xyz",), want, (self._total_vertices(),))
+        return {**out, **xyz}, ptrs + xyz_ptrs
 
     def trace_rays_backward(self, rays, inst, prim, t, uv, grad_t=None, grad_uv=None, want=("grad_rays", "grad_xyz")):
         """gradients of a loss on the hits (inst, prim, t, uv) of `rays` (host buffers, synchronous).  grad_t (N,) and grad_uv
         (N, 2) are dL/dt and dL/d(u, v); one of them may be None (zeros).  Returns a dict of the wanted arrays: grad_rays (N, 8)
         float32 {dL/do, 0, dL/dd, 0} and grad_xyz (total vertices, 3) float32, the gradient with respect to the world vertices of
         all meshes back to back in upload order."""
-        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        r = _ray_records(rays)
         n = len(r)
-        i = np.ascontiguousarray(inst, dtype=np.uint32).reshape(-1)
-        q = np.ascontiguousarray(prim, dtype=np.uint32).reshape(-1)
+        i, q = _ids(inst), _ids(prim)
         tt = np.ascontiguousarray(t, dtype=np.float32).reshape(-1)
         u = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
         gt = None if grad_t is None else np.ascontiguousarray(grad_t, dtype=np.float32).reshape(-1)
         gu = None if grad_uv is None else np.ascontiguousarray(grad_uv, dtype=np.float32).reshape(-1, 2)
-        if not all(len(a) == n for a in (i, q, tt, u, gt, gu) if a is not None):
-            raise ValueError("rays, inst, prim, t, uv and the gradients must hold one record per ray")
-        out = {}
-        if "grad_rays" in want:
-            out["grad_rays"] = np.zeros((n, 8), dtype=np.float32)
-        if "grad_xyz" in want:
-            out["grad_xyz"] = np.zeros((self._total_vertices(), 3), dtype=np.float32)
-
-        def p(a):
-            return None if a is None else a.ctypes.data
-        self._ok(lib().crt_trace_rays_backward(self.h, n, p(r), p(i), p(q), p(tt), p(u), p(gt), p(gu), p(out.get("grad_rays")),
-                                               p(out.get("grad_xyz")), None), "crt_trace_rays_backward")
+        _one_per_record(n, ("rays, inst, prim, t, uv and the gradients", "ray"), i, q, tt, u, gt, gu)
+        out, ptrs = self._grad_outputs("grad_rays", n, want)
+        self._call("crt_trace_rays_backward", n, r.ctypes.data, i.ctypes.data, q.ctypes.data, tt.ctypes.data, u.ctypes.data, _ptr(gt), _ptr(gu),
+                   *ptrs, None)
         return out
 
     def trace_rays_backward_device(self, n, d_rays, d_inst, d_prim, d_t, d_uv, d_grad_t=None, d_grad_uv=None, d_grad_rays=None, d_grad_xyz=None,
                                    stats=False):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_trace_rays_backward_device(self.h, int(n), d_rays, d_inst, d_prim, d_t, d_uv, d_grad_t, d_grad_uv, d_grad_rays, d_grad_xyz,
-                                                      C.byref(st) if stats else None), "crt_trace_rays_backward_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_trace_rays_backward_device", int(n), d_rays, d_inst, d_prim, d_t, d_uv, d_grad_t, d_grad_uv, d_grad_rays,
+                                d_grad_xyz, stats=stats)
 
     def closest_points_backward(self, points, inst, prim, uv, grad_dist, want=("grad_points", "grad_xyz")):
         """gradients of a loss on the distances of `points` to their closest surface points (inst, prim, uv) (host buffers,
         synchronous).  grad_dist (N,) is dL/ddist.  Returns a dict of the wanted arrays: grad_points (N, 4) float32 {dL/dp, 0} and
         grad_xyz as trace_rays_backward."""
-        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 4)
+        pts = _point_records(points)
         n = len(pts)
-        i = np.ascontiguousarray(inst, dtype=np.uint32).reshape(-1)
-        q = np.ascontiguousarray(prim, dtype=np.uint32).reshape(-1)
+        i, q = _ids(inst), _ids(prim)
         u = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
         g = np.ascontiguousarray(grad_dist, dtype=np.float32).reshape(-1)
-        if not all(len(a) == n for a in (i, q, u, g)):
-            raise ValueError("points, inst, prim, uv and grad_dist must hold one record per point")
-        out = {}
-        if "grad_points" in want:
-            out["grad_points"] = np.zeros((n, 4), dtype=np.float32)
-        if "grad_xyz" in want:
-            out["grad_xyz"] = np.zeros((self._total_vertices(), 3), dtype=np.float32)
-
-        def p(a):
-            return None if a is None else a.ctypes.data
-        self._ok(lib().crt_closest_points_backward(self.h, n, p(pts), p(i), p(q), p(u), p(g), p(out.get("grad_points")), p(out.get("grad_xyz")), None),
-                 "crt_closest_points_backward")
+        _one_per_record(n, ("points, inst, prim, uv and grad_dist", "point"), i, q, u, g)
+        out, ptrs = self._grad_outputs("grad_points", n, want)
+        self._call("crt_closest_points_backward", n, pts.ctypes.data, i.ctypes.data, q.ctypes.data, u.ctypes.data, g.ctypes.data, *ptrs, None)
         return out
 
     def closest_points_backward_device(self, n, d_points, d_inst, d_prim, d_uv, d_grad_dist, d_grad_points=None, d_grad_xyz=None, stats=False):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); asynchronous on the context's stream unless stats"""
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_closest_points_backward_device(self.h, int(n), d_points, d_inst, d_prim, d_uv, d_grad_dist, d_grad_points, d_grad_xyz,
-                                                          C.byref(st) if stats else None), "crt_closest_points_backward_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_closest_points_backward_device", int(n), d_points, d_inst, d_prim, d_uv, d_grad_dist, d_grad_points,
+                                d_grad_xyz, stats=stats)
 
     def trace_rays_torch(self, rays, vertices):
         """trace_rays with a torch.autograd graph behind it.  rays: (N, 8) float32 CUDA tensor (may require grad); vertices: dict
@@ -1582,16 +1470,6 @@ class Renderer:
         gradients as trace_rays_torch."""
         return _torch_functions()[1].apply(self, points, tuple(int(m) for m in vertices), *vertices.values())
 
-    def count_hits_device(self, n, d_rays, d_count, stats=False):
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_count_hits_device(self.h, int(n), d_rays, d_count, C.byref(st) if stats else None), "crt_count_hits_device")
-        return st.as_dict() if stats else None
-
-    def occupancy_device(self, n, d_points, d_inside, stats=False):
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_occupancy_device(self.h, int(n), d_points, d_inside, C.byref(st) if stats else None), "crt_occupancy_device")
-        return st.as_dict() if stats else None
-
     # ---- all-hits ray queries (include/crt_hip.h): every crossing of a ray as a CSR list sorted by distance
     def list_hits(self, rays, want=("t", "uv", "inst", "prim"), capacity=None):
         """every triangle each ray crosses in (tmin, tmax), in ascending t (host buffers, synchronous).  Returns a dict:
@@ -1599,29 +1477,26 @@ class Renderer:
         of every record), the wanted arrays t (total,) float32, uv (total, 2) float32, inst / prim (total,) uint32, and 'stats'
         of the last call.  Without `capacity` one offsets-only call learns the total first; with it that call is made only
         when the guess was too small."""
-        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        r = _ray_records(rays)
         n = len(r)
         off = np.zeros(n + 1, dtype=np.uint64)
         tot = C.c_uint64(0)
         st = FrameStats()
-        shapes = {"t": ((), np.float32), "uv": ((2,), np.float32), "inst": ((), np.uint32), "prim": ((), np.uint32)}
-        wanted = [k for k in shapes if k in want]
+        keys = ("t", "uv", "inst", "prim")
+        wanted = [k for k in keys if k in want]
 
-        def call(cap, out):
-            def p(k):
-                return out[k].ctypes.data if k in out else None
-            self._ok(lib().crt_list_hits(self.h, n, r.ctypes.data, off.ctypes.data, cap, p("t"), p("uv"), p("inst"), p("prim"),
-                                         C.byref(tot), C.byref(st)), "crt_list_hits")
+        def call(cap, want):
+            out, ptrs = _outputs(keys, want, (cap,))
+            self._call("crt_list_hits", n, r.ctypes.data, off.ctypes.data, cap, *ptrs, C.byref(tot), C.byref(st))
+            return out
         out = {}
         if capacity is None or not wanted:
-            call(0, {})
+            call(0, ())
             capacity = tot.value
         if wanted:
-            out = {k: np.zeros((int(capacity),) + shapes[k][0], dtype=shapes[k][1]) for k in wanted}
-            call(int(capacity), out)
+            out = call(int(capacity), wanted)
             if tot.value > capacity:  # the guess was too small
-                out = {k: np.zeros((tot.value,) + shapes[k][0], dtype=shapes[k][1]) for k in wanted}
-                call(tot.value, out)
+                out = call(tot.value, wanted)
             out = {k: v[:tot.value] for k, v in out.items()}
         out["offsets"] = off.astype(np.int64)
         out["ray"] = np.repeat(np.arange(n, dtype=np.uint32), np.diff(out["offsets"]))
@@ -1631,18 +1506,17 @@ class Renderer:
     def list_hits_device(self, n, d_rays, d_offsets, capacity, d_t=None, d_uv=None, d_inst=None, d_prim=None, total=False, stats=False):
         """device pointers are integers (e.g. torch.Tensor.data_ptr()); d_offsets holds n + 1 int64.  Asynchronous on the
         context's stream unless total or stats.  Returns None, the total, the stats, or (total, stats)."""
-        st = FrameStats() if stats else None
         tot = C.c_uint64(0) if total else None
-        self._ok(lib().crt_list_hits_device(self.h, int(n), d_rays, d_offsets, int(capacity), d_t, d_uv, d_inst, d_prim,
-                                            C.byref(tot) if total else None, C.byref(st) if stats else None), "crt_list_hits_device")
+        st = self._call_stats("crt_list_hits_device", int(n), d_rays, d_offsets, int(capacity), d_t, d_uv, d_inst, d_prim,
+                              C.byref(tot) if total else None, stats=stats)
         if total and stats:
-            return tot.value, st.as_dict()
-        return tot.value if total else (st.as_dict() if stats else None)
+            return tot.value, st
+        return tot.value if total else st
 
     def list_phases(self):
         """HIP-event ms of count / scan / fill / sort of the last list_hits* call that was given stats"""
         buf = np.zeros(4, dtype=np.float64)
-        self._ok(lib().crt_debug_list_phases(self.h, buf.ctypes.data), "crt_debug_list_phases")
+        self._call("crt_debug_list_phases", buf.ctypes.data)
         return dict(zip(("count", "scan", "fill", "sort"), buf.tolist()))
 
     def inside_length(self, rays):
@@ -1652,28 +1526,28 @@ class Renderer:
 
     def read_counters(self):
         buf = np.zeros(32, dtype=np.uint64)
-        self._ok(lib().crt_debug_read_counters(self.h, buf.ctypes.data), "crt_debug_read_counters")
+        self._call("crt_debug_read_counters", buf.ctypes.data)
         return buf
 
     def read_timeline(self, max_words=1 << 22):
         buf = np.zeros(max_words, dtype=np.uint64)
         n = C.c_size_t()
-        self._ok(lib().crt_debug_read_timeline(self.h, buf.ctypes.data, max_words, C.byref(n)), "crt_debug_read_timeline")
+        self._call("crt_debug_read_timeline", buf.ctypes.data, max_words, C.byref(n))
         return buf[:n.value].reshape(-1, 3)
 
     def set_stream(self, stream_ptr):
         """run on an external hipStream_t handle (0 / None = HIP's default stream, which is torch's default)"""
-        self._ok(lib().crt_set_stream(self.h, stream_ptr), "crt_set_stream")
+        self._call("crt_set_stream", stream_ptr)
 
     def reset_stream(self):
-        self._ok(lib().crt_reset_stream(self.h), "crt_reset_stream")
+        self._call("crt_reset_stream")
 
     def synchronize(self):
-        self._ok(lib().crt_synchronize(self.h), "crt_synchronize")
+        self._call("crt_synchronize")
 
     def bvh_info(self):
         a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
-        self._ok(lib().crt_bvh_info(self.h, C.byref(a), C.byref(b), C.byref(c)), "crt_bvh_info")
+        self._call("crt_bvh_info", C.byref(a), C.byref(b), C.byref(c))
         return {"n_nodes": a.value, "n_tris": b.value, "max_depth": c.value}
 
     def bvh_export(self):
@@ -1681,19 +1555,19 @@ class Renderer:
         nodes = np.zeros(info["n_nodes"], dtype=NODE_DTYPE)
         tris = np.zeros(info["n_tris"], dtype=TRI_DTYPE)
         shade = np.zeros(info["n_tris"], dtype=SHADE_DTYPE)
-        self._ok(lib().crt_bvh_export(self.h, nodes.ctypes.data, tris.ctypes.data, shade.ctypes.data), "crt_bvh_export")
+        self._call("crt_bvh_export", nodes.ctypes.data, tris.ctypes.data, shade.ctypes.data)
         return nodes, tris, shade
 
     def build_stats(self):
         a, b = C.c_double(), C.c_double()
-        self._ok(lib().crt_build_stats(self.h, C.byref(a), C.byref(b)), "crt_build_stats")
+        self._call("crt_build_stats", C.byref(a), C.byref(b))
         return {"upload_ms": a.value, "device_build_ms": b.value}
 
     def bvh_export4(self):
         a, b = C.c_uint32(), C.c_uint32()
-        self._ok(lib().crt_bvh_info4(self.h, C.byref(a), C.byref(b)), "crt_bvh_info4")
+        self._call("crt_bvh_info4", C.byref(a), C.byref(b))
         nodes4 = np.zeros(a.value, dtype=NODE4_DTYPE)
-        self._ok(lib().crt_bvh_export4(self.h, nodes4.ctypes.data), "crt_bvh_export4")
+        self._call("crt_bvh_export4", nodes4.ctypes.data)
         return nodes4, b.value
 
     # native RCCL frame assembly (crt_comm_*): no torch involved
@@ -1705,21 +1579,20 @@ class Renderer:
             if rc != 0:
                 raise CrtError("crt_comm_unique_id failed rc=%d: %s" % (rc, lib().crt_last_error(None).decode()))
             unique_id = buf.raw
-        self._ok(lib().crt_comm_init(self.h, rank, n_ranks, C.create_string_buffer(unique_id, 128)), "crt_comm_init")
+        self._call("crt_comm_init", rank, n_ranks, C.create_string_buffer(unique_id, 128))
         return unique_id
 
     def comm_init_host(self, rank, n_ranks, name):
         """the same frame assembly with a POSIX shared-memory object ("/name") as the transport: ranks that share one GPU (rehearsal)"""
-        self._ok(lib().crt_comm_init_host(self.h, rank, n_ranks, name.encode()), "crt_comm_init_host")
+        self._call("crt_comm_init_host", rank, n_ranks, name.encode())
 
     def comm_destroy(self):
-        self._ok(lib().crt_comm_destroy(self.h), "crt_comm_destroy")
+        self._call("crt_comm_destroy")
 
     def render_frame_distributed(self, w, h, d_rgba8=None, host=False, stats=False):
         out = np.zeros((h, w, 4), dtype=np.uint8) if host else None
         st = FrameStats()
-        self._ok(lib().crt_render_frame_distributed(self.h, w, h, d_rgba8, out.ctypes.data if host else None, C.byref(st) if stats else None),
-                 "crt_render_frame_distributed")
+        self._call("crt_render_frame_distributed", w, h, d_rgba8, _ptr(out), C.byref(st) if stats else None)
         res = {"stats": st.as_dict()} if stats else {}
         if host:
             res["rgba8"] = out
@@ -1728,17 +1601,17 @@ class Renderer:
     def bvh_export4q(self):
         """the quantised 64-byte nodes as they sit in HBM"""
         a = C.c_uint32()
-        self._ok(lib().crt_bvh_info4(self.h, C.byref(a), None), "crt_bvh_info4")
+        self._call("crt_bvh_info4", C.byref(a), None)
         q = np.zeros(a.value, dtype=NODE4Q_DTYPE)
-        self._ok(lib().crt_bvh_export4q(self.h, q.ctypes.data), "crt_bvh_export4q")
+        self._call("crt_bvh_export4q", q.ctypes.data)
         return q
 
     def bvh_export_planes4q(self):
         """the decoded plane table: one row of 32 floats per quantised node, float(q) of its 24 plane bytes + 8 zeros"""
         a = C.c_uint32()
-        self._ok(lib().crt_bvh_info4(self.h, C.byref(a), None), "crt_bvh_info4")
+        self._call("crt_bvh_info4", C.byref(a), None)
         p = np.zeros((a.value, 32), dtype=np.float32)
-        self._ok(lib().crt_bvh_export_planes4q(self.h, p.ctypes.data), "crt_bvh_export_planes4q")
+        self._call("crt_bvh_export_planes4q", p.ctypes.data)
         return p
 
     def pinned_frame(self, w, h):
@@ -1762,36 +1635,18 @@ class Renderer:
     def render_frame(self, w, h, want=("rgba8", "hit_inst", "hit_prim", "hit_t", "rgb"), pinned=False):
         """renderFrame with host outputs. Returns dict of arrays + 'stats'. pinned=True: rgba8 lands in a reused page-locked
         buffer (valid until the next such call)."""
-        out = {"rgba8": self.pinned_frame(w, h) if pinned else np.zeros((h, w, 4), dtype=np.uint8)}
-        if "hit_inst" in want:
-            out["hit_inst"] = np.zeros((h, w), dtype=np.uint32)
-        if "hit_prim" in want:
-            out["hit_prim"] = np.zeros((h, w), dtype=np.uint32)
-        if "hit_t" in want:
-            out["hit_t"] = np.zeros((h, w), dtype=np.float32)
-        if "rgb" in want:
-            out["rgb"] = np.zeros((h, w, 3), dtype=np.float32)
-        st = FrameStats()
-
-        def p(k):
-            return out[k].ctypes.data if k in out else None
-        self._ok(lib().crt_render_frame(self.h, w, h, p("rgba8"), p("hit_inst"), p("hit_prim"), p("hit_t"), p("rgb"),
-                                        C.byref(st)), "crt_render_frame")
-        out["stats"] = st.as_dict()
+        rgba8 = self.pinned_frame(w, h) if pinned else np.zeros((h, w, 4), dtype=np.uint8)  # always filled, wanted or not
+        out, ptrs = _outputs(("hit_inst", "hit_prim", "hit_t", "rgb"), want, (h, w))
+        out = {"rgba8": rgba8, **out}
+        out["stats"] = self._call_stats("crt_render_frame", w, h, rgba8.ctypes.data, *ptrs)
         return out
 
     def render_frame_device(self, w, h, d_rgba8, d_hit_inst=None, d_hit_prim=None, d_hit_t=None, d_rgb=None, stats=False):
         """device pointers are integers (e.g. torch.Tensor.data_ptr())."""
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_render_frame_device(self.h, w, h, d_rgba8, d_hit_inst, d_hit_prim, d_hit_t, d_rgb,
-                                               C.byref(st) if stats else None), "crt_render_frame_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_render_frame_device", w, h, d_rgba8, d_hit_inst, d_hit_prim, d_hit_t, d_rgb, stats=stats)
 
     def render_tiles_device(self, w, h, rank, n_ranks, d_staging, stats=False):
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_render_tiles_device(self.h, w, h, rank, n_ranks, d_staging, C.byref(st) if stats else None),
-                 "crt_render_tiles_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_render_tiles_device", w, h, rank, n_ranks, d_staging, stats=stats)
 
     @staticmethod
     def _batch_args(cameras, d_out):
@@ -1806,20 +1661,14 @@ class Renderer:
     def render_frames_batch_device(self, w, h, d_rgba8_list, cameras=None, stats=False):
         """several frames in ONE launch; cameras = [(pos, rot3x3), ...] per frame or None (current camera for all)."""
         n, cams, outs = self._batch_args(cameras, d_rgba8_list)
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_render_frames_batch_device(self.h, w, h, n, cams.ctypes.data if cams is not None else None, outs,
-                                                      C.byref(st) if stats else None), "crt_render_frames_batch_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_render_frames_batch_device", w, h, n, _ptr(cams), outs, stats=stats)
 
     def render_tiles_batch_device(self, w, h, rank, n_ranks, d_staging_list, cameras=None, stats=False):
         n, cams, outs = self._batch_args(cameras, d_staging_list)
-        st = FrameStats() if stats else None
-        self._ok(lib().crt_render_tiles_batch_device(self.h, w, h, rank, n_ranks, n, cams.ctypes.data if cams is not None else None, outs,
-                                                     C.byref(st) if stats else None), "crt_render_tiles_batch_device")
-        return st.as_dict() if stats else None
+        return self._call_stats("crt_render_tiles_batch_device", w, h, rank, n_ranks, n, _ptr(cams), outs, stats=stats)
 
     def untile_batch_device(self, w, h, n_ranks, n_frames, frame, d_gathered, d_frame):
-        self._ok(lib().crt_untile_batch_device(self.h, w, h, n_ranks, n_frames, frame, d_gathered, d_frame), "crt_untile_batch_device")
+        self._call("crt_untile_batch_device", w, h, n_ranks, n_frames, frame, d_gathered, d_frame)
 
     def untile_device(self, w, h, n_ranks, d_gathered, d_frame):
-        self._ok(lib().crt_untile_device(self.h, w, h, n_ranks, d_gathered, d_frame), "crt_untile_device")
+        self._call("crt_untile_device", w, h, n_ranks, d_gathered, d_frame)
