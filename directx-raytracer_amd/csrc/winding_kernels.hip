@@ -48,10 +48,32 @@ __device__ __forceinline__ float crtAtan2(float y, float x)
     return y < 0.0f ? -r : r;
 }
 
+// the contract's expo(m): the frexp exponent of m, 0 when m is zero or not finite (a NaN is never the largest: m is none)
+__device__ __forceinline__ int expo(float m)
+{
+    int e;
+    (void)frexpf(m, &e);
+    return ((m > 0.0f) & (m < __builtin_inff())) ? e : 0;
+}
+
+__device__ __forceinline__ float maxAbs(float m, float x)
+{
+    const float ax = fabsf(x);
+    return ax > m ? ax : m;
+}
+__device__ __forceinline__ float maxAbs3(float m, F3 v) { return maxAbs(maxAbs(maxAbs(m, v.x), v.y), v.z); }
+__device__ __forceinline__ F3 scale3(F3 v, int s) { return f3(ldexpf(v.x, s), ldexpf(v.y, s), ldexpf(v.z, s)); }
+
 // half the signed solid angle of the record {v0, e1, e2} seen from q
 __device__ __forceinline__ float halfAngle(F3 q, F3 v0, F3 e1, F3 e2)
 {
-    const F3 a = sub3(v0, q);
+    const F3 a0 = sub3(v0, q);
+    const F3 b0 = f3(a0.x + e1.x, a0.y + e1.y, a0.z + e1.z), c0 = f3(a0.x + e2.x, a0.y + e2.y, a0.z + e2.z);
+    // everything below is dimensionless: the triangle as seen from q, brought to unit size by an exact power of two
+    const int s = -expo(maxAbs3(maxAbs3(maxAbs3(0.0f, a0), b0), c0));
+    const F3 a = scale3(a0, s);
+    e1 = scale3(e1, s);
+    e2 = scale3(e2, s);
     const F3 b = f3(a.x + e1.x, a.y + e1.y, a.z + e1.z), c = f3(a.x + e2.x, a.y + e2.y, a.z + e2.z);
     const F3 n = f3(e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z, e1.x * e2.y - e1.y * e2.x);
     const float det = dot3(a, n);
@@ -97,11 +119,13 @@ struct WindingJob {
             const int ref = k == 0 ? refs.x : (k == 1 ? refs.y : (k == 2 ? refs.z : refs.w));
             if (ref == CRT_BVH_EMPTY) continue;
             const float4 c = M[k];
-            const F3 d = sub3(f3(c.x, c.y, c.z), p);
-            const float d2 = dot3(d, d), br = beta * c.w;
+            const F3 d0 = sub3(f3(c.x, c.y, c.z), p);
+            const int s = -expo(maxAbs3(0.0f, d0)); // the dipole in units of 2^-s, so that |d| is of order 1
+            const F3 d = scale3(d0, s);
+            const float d2 = dot3(d, d), br = beta * ldexpf(c.w, s);
             if (approx & (d2 > br * br)) {
                 const float4 N = M[4 + k]; // only an accepted child's second line is touched
-                float h = (0.5f * dot3(f3(N.x, N.y, N.z), d)) / (d2 * sqrtf(d2));
+                float h = ldexpf((0.5f * dot3(f3(N.x, N.y, N.z), d)) / (d2 * sqrtf(d2)), 2 * s);
                 h = h == h ? h : 0.0f;
                 h = h > kClusterMax ? kClusterMax : (h < -kClusterMax ? -kClusterMax : h);
                 sum += toFixed(h);

@@ -378,6 +378,12 @@ int crt_accumulated_samples(const crt_ctx* ctx, uint32_t* samples); /* samples p
  *   rounded; a t that leaves the float range is reported as +inf (still a hit) or as a subnormal; a component below 1e-20 of
  *   the largest counts as +-1e-20 of it in the slab test (a boundary ray, below).  A zero direction, just outside the
  *   range, hits nothing.
+ * - Scene scale: the vertices, the origins and tmin / tmax times 2^k (directions as they are) give the same inst, prim, u, v
+ *   and occlusion, and t 2^k, bit for bit, while every intermediate stays a normal float.  The Moeller-Trumbore products are
+ *   cubic in a length, so that range is about a third of float32's: measured on a scene of extent 4 with edges of 0.1 .. 2 and
+ *   257 records (tests/test_scale_similarity.py), k = -34 .. 41 for the closest hit and for all hits,
+ *   -43 .. 41 for occlusion, -41 .. 41 for hit counts.  Outside it products go subnormal or overflow and results change
+ *   without an error being reported; kernel and oracle still agree bit for bit there (checked at the first k outside).  A scene much smaller than 2^-30 or larger than 2^40 units should be rescaled by the caller.
  * - Closest hit (crt_trace_rays*), per ray, each output optional: t (float), uv (2 floats: u = weight of v1, v = weight of
  *   v2, the frames' barycentrics), inst (uint32 mesh ordinal in upload order), prim (uint32 triangle of that mesh).  Equal t
  *   goes to the lower global triangle id, as in the frames.  Miss: inst = prim = CRT_MISS, t = the ray's tmax, u = v = 0.
@@ -697,6 +703,11 @@ int crt_temporal_accumulate(crt_ctx* ctx, uint32_t width, uint32_t height, const
  *   or on scheduling: the closest-point search prunes a box only when no triangle in it can produce a computed d2 <= the
  *   best so far (the margin holds at any offset from the origin).
  *   Inert triangles (non-finite vertices, above) are never the closest triangle and are never counted, over any tree.
+ * - Scene scale: vertices, points and rmax times 2^k give the same inst, prim, uv and occupancy, and dist and point times 2^k,
+ *   bit for bit, while every intermediate stays a normal float.  The region tests multiply two dot products (vc = d1*d4 -
+ *   d3*d2: fourth order in a length), so the closest point has the narrowest range of all queries: measured as for the ray
+ *   queries (scene of extent 4, tests/test_scale_similarity.py) k = -28 .. 30; occupancy, three hit
+ *   counts, -45 .. 42.  Outside it results change without an error; kernel and reference still agree bit for bit there.
  * - Common rules of the ray queries: pending refits are applied first; a query reads the tree and the triangle records,
  *   nothing else (camera, mode, accumulation sums, launch orders, frame outputs are untouched); n = 0 returns CRT_OK and
  *   launches nothing; CRT_ESTATE without a scene.  stats (may be NULL): kernel_ms, total_ms, rays_primary = records traced
@@ -725,11 +736,18 @@ int crt_occupancy(crt_ctx* ctx, uint32_t n, const float* points, uint8_t* inside
  * - Per-triangle term h (half the signed solid angle; float, fused multiply-adds only where fmaf is written, / and sqrtf
  *   correctly rounded, dot as in the point queries), from the leaf-ordered record {v0, e1, e2} as traced and the point q:
  *     a = v0 - q; b = a + e1; c = a + e2  (per component)
+ *     E = expo(the largest of the nine |components| of a, b, c), where expo(m) is the exponent frexpf gives (m = f 2^E, f in
+ *       [0.5, 1)) and 0 when m is zero or not finite; a NaN component is never the largest
+ *     a = ldexpf(a, -E), e1 = ldexpf(e1, -E), e2 = ldexpf(e2, -E) per component (exact: the triangle as seen from q, brought to
+ *       unit size; the solid angle has no dimension);  b = a + e1; c = a + e2 again, from the scaled values
  *     n = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x);  det = dot(a, n)
  *       (the edge form of a . (b x c): its rounding error grows with the triangle's size, not with the cube of its distance)
  *     la = sqrtf(dot(a, a)), lb = sqrtf(dot(b, b)), lc = sqrtf(dot(c, c));  m = (la * lb) * lc
  *     den = ((m + dot(a, b) * lc) + dot(b, c) * la) + dot(c, a) * lb
- *     h = m == 0 ? 0 : crtAtan2(det, den)        (m == 0: the point is a vertex of the triangle)
+ *     h = m == 0 ? 0 : crtAtan2(det, den)        (m == 0: the point is a vertex of the triangle -- after the scaling the largest
+ *       of la, lb, lc is at least 0.5 and a length is zero only when its vector is below 2^-75 of that: the product of three
+ *       lengths no longer underflows because the scene is small)
+ *   Where a, b, c, e1, e2 and every product were normal floats without the scaling, h has the bits it would have without it.
  * - crtAtan2(y, x), the project's own arctangent (neither the device library's atan2f nor libm's: they differ):
  *     ay = |y|, ax = |x|; swap = ay > ax; mx = swap ? ay : ax; mn = swap ? ax : ay
  *     t = mn / mx; s = t * t; p = C6; p = fmaf(p, s, Ck) for k = 5 .. 0; r = fmaf(t, s * p, t)
@@ -739,8 +757,11 @@ int crt_occupancy(crt_ctx* ctx, uint32_t n, const float* points, uint8_t* inside
  *   the zero (in the plane inside the triangle: undefined on the surface, but the same bits from both sides); x = +-0 gives
  *   +-PI_2.  Absolute error against atan2 in float64: at most 2.95e-7 measured over the grid of tests/test_winding.py (the test
  *   asserts that figure plus one float32 ulp of pi, under the 2^-20 the error budget below needs).
- *   Triangles that contribute exactly zero: inert ones (a non-finite vertex makes det or den a NaN or an infinity, as does
- *   any overflow of the products above) and those with the point at a vertex.  A record with a NaN coordinate gives w = 0.
+ *   Triangles that contribute exactly zero: inert ones (a non-finite vertex makes det or den a NaN or an infinity) and those
+ *   with the point at a vertex.  The scaled products cannot overflow: every component is below 2 in magnitude.  What is left
+ *   of the float range is the subtraction v0 - q and the sums a + e1, a + e2 themselves, which overflow only within a factor 2
+ *   of FLT_MAX (E = 0 then, and the triangle contributes zero), and components 2^-126 and more below the largest, which the
+ *   scaling rounds.  A record with a NaN coordinate gives w = 0.
  * - Sum: every contribution h, a triangle's or a cluster's, is added to a 64-bit integer as llrint((double)h * 2^36); the
  *   result is w = (float)((double)sum * 2^-36 / (2 pi)), 2 pi = 6.283185307179586.  Integer addition is associative: w does not
  *   depend on the order of the walk, of the records or on scheduling.  |h| <= pi < 2^38 / 2^36, so the sum cannot wrap below
@@ -754,12 +775,23 @@ int crt_occupancy(crt_ctx* ctx, uint32_t n, const float* points, uint8_t* inside
  *   node's total.  Inert triangles are left out; CRT_BVH_EMPTY slots hold zeros.  r (float) over the child's decoded
  *   quantised box [lo, hi]: r = sqrtf((mx + my) + mz), m_a = max((p~_a - lo_a)^2, (hi_a - p~_a)^2): no triangle of the child
  *   is farther from p~.
- * - Walk: from the root, per non-empty child slot with d = p~ - q, d2 = dot(d, d): when beta > 0 and d2 > (beta * r)^2 the child
- *   contributes h = (0.5f * dot(N~, d)) / (d2 * sqrtf(d2)) and is not entered; else it is entered; a leaf adds every triangle's
- *   term.  beta <= 0 or NaN: exact -- no cluster is approximated and w is the sum over all triangles, the same bits over every
+ * - Walk: from the root, per non-empty child slot with d0 = p~ - q: E = expo(the largest |component| of d0), d = ldexpf(d0, -E)
+ *   per component, d2 = dot(d, d) (in [0.25, 3) for a finite non-zero d0), br = beta * ldexpf(r, -E): when beta > 0 and
+ *   d2 > br * br the child contributes h = ldexpf((0.5f * dot(N~, d)) / (d2 * sqrtf(d2)), -2 * E) and is not entered; else it is
+ *   entered; a leaf adds every triangle's term.  The comparison is d0 . d0 > (beta r)^2 with both sides divided by 2^2E: it
+ *   cannot overflow on the left, and where neither side left the normal range before it decides as before.  The dipole is
+ *   0.5 N~ . d0 / |d0|^3 with the length taken out; h itself has no dimension.  beta <= 0 or NaN: exact -- no cluster is approximated and w is the sum over all triangles, the same bits over every
  *   tree (host SAH, LBVH, PLOC, refitted, rebuilt).  beta = +inf is exact through the same comparison.  With a finite beta > 0
  *   the result depends on the tree (other clusters exist), not on any order.  beta = 2 keeps the error near 1e-2 at worst
  *   close to a cluster and far below it elsewhere (DESIGN.md section 5q has the measured figures).
+ * - Unit of length: w does not depend on it.  Vertices and points times 2^k give the same bits of w in exact mode wherever the
+ *   scaled vertices and points are themselves normal floats (asserted for k = -118 .. 120 on a scene of extent 4, all that scene
+ *   can express; tests/test_scale_similarity.py).  With beta > 0 the moment table is the bound: N~ is an
+ *   area in squared units, rounded to float32, and r a length.  The same bits hold while every non-zero component of N~ and
+ *   each product N~_i d_i is a normal float (d_i is below 1 in magnitude) and while the builder forms the
+ *   same tree; measured k = -57 .. 58 at beta = 2 and -58 .. 58 at beta = 8 over the host SAH tree of that scene, whose
+ *   smallest leaf clusters have an area near 2^-9 (the host builder's tree itself changes above k = 58 and below k = -70).
+ *   Outside that range clusters whose N~ has underflowed contribute too little: use exact mode or rescale.
  * - Common rules of the point queries: pending refits are applied first; n = 0 returns CRT_OK and launches nothing;
  *   CRT_ESTATE without a scene; CRT_EINVAL for a NULL context, a NULL or misaligned pointer (points 16-byte, w 4-byte).  The
  *   moment table (n_nodes4 x 128 bytes) is built by the first winding query or export after an upload, a refit or a rebuild;
@@ -983,6 +1015,11 @@ int crt_temporal_accumulate_motion(crt_ctx* ctx, uint32_t width, uint32_t height
  *   rounding boundary, for m contributions: independent of the order of the records and of scheduling up to that rare last bit,
  *   not promised bit-reproducible.  Calls of one context share the array: a call waits (on the GPU) for the one before it.
  * - Nothing depends on the tree, the builder or refit versus rebuild: only the vertex buffer and the indices are read.
+ * - Scene scale: with vertices, origins, t, points times 2^k and a fixed loss -- g_t and grad_dist times 2^-k, g_u and g_v as they
+ *   are -- the formulas above give dL/do, dL/dp and the vertex contributions times 2^-k and dL/dd unchanged, bit for bit while
+ *   every intermediate stays a normal float (n and det are quadratic in a length).  Measured with the forward query's outputs
+ *   at that scale as inputs (tests/test_scale_similarity.py): the forward query's own range, k = -34 .. 41
+ *   for rays and -28 .. 30 for points.  Outside it kernel and reference still agree bit for bit.
  * - Pending refits are applied first.  n = 0 returns CRT_OK and launches nothing (no buffer is looked at, grad_xyz is not
  *   written); n up to 2^32 - 1.  CRT_ESTATE without a dynamic scene.  CRT_EINVAL for a NULL ctx, a NULL input buffer, grad_t and
  *   grad_uv both NULL, grad_rays (grad_points) and grad_xyz both NULL, or a misaligned device pointer: rays, points, grad_rays and

@@ -17,6 +17,16 @@
 
 static float dot3(const float* a, const float* b) { return fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0])); }
 
+/* the contract's expo(m): the frexp exponent of m, 0 when m is zero or not finite (a NaN is never the largest: m is none) */
+static int ref_expo(float m)
+{
+    int e = 0;
+    if (m > 0.0f && m < INFINITY) (void)frexpf(m, &e);
+    return e;
+}
+
+static float max_abs(float m, float x) { const float ax = fabsf(x); return ax > m ? ax : m; }
+
 float ref_atan2(float y, float x)
 {
     const float ay = fabsf(y), ax = fabsf(x);
@@ -45,12 +55,24 @@ void ref_atan2_array(uint32_t n, const float* y, const float* x, float* out)
 
 float ref_half_angle(const float* q, const float* v0, const float* e1, const float* e2)
 {
-    float a[3], b[3], c[3];
+    float a[3], b[3], c[3], f1[3], f2[3], mx = 0.0f;
     for (int k = 0; k < 3; k++) {
         a[k] = v0[k] - q[k];
         b[k] = a[k] + e1[k];
         c[k] = a[k] + e2[k];
+        mx = max_abs(max_abs(max_abs(mx, a[k]), b[k]), c[k]);
     }
+    /* everything below is dimensionless: the triangle as seen from q, brought to unit size by an exact power of two */
+    const int E = ref_expo(mx);
+    for (int k = 0; k < 3; k++) {
+        a[k] = ldexpf(a[k], -E);
+        f1[k] = ldexpf(e1[k], -E);
+        f2[k] = ldexpf(e2[k], -E);
+        b[k] = a[k] + f1[k];
+        c[k] = a[k] + f2[k];
+    }
+    e1 = f1;
+    e2 = f2;
     const float n[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
     const float det = dot3(a, n);
     const float la = sqrtf(dot3(a, a)), lb = sqrtf(dot3(b, b)), lc = sqrtf(dot3(c, c));
@@ -162,10 +184,12 @@ void ref_winding_tree(const crt_bvh_node4q* nodes, uint32_t n4, const crt_bvh_tr
                 for (int k = 0; k < 4; k++) {
                     const int32_t ref = nodes[cur].ref[k];
                     if (ref == CRT_BVH_EMPTY) continue;
-                    const float d[3] = { M[4 * k] - q[0], M[4 * k + 1] - q[1], M[4 * k + 2] - q[2] };
-                    const float d2 = dot3(d, d), br = beta * M[4 * k + 3];
+                    const float d0[3] = { M[4 * k] - q[0], M[4 * k + 1] - q[1], M[4 * k + 2] - q[2] };
+                    const int E = ref_expo(max_abs(max_abs(max_abs(0.0f, d0[0]), d0[1]), d0[2]));
+                    const float d[3] = { ldexpf(d0[0], -E), ldexpf(d0[1], -E), ldexpf(d0[2], -E) };
+                    const float d2 = dot3(d, d), br = beta * ldexpf(M[4 * k + 3], -E);
                     if (approx && d2 > br * br) {
-                        float h = (0.5f * dot3(M + 16 + 4 * k, d)) / (d2 * sqrtf(d2));
+                        float h = ldexpf((0.5f * dot3(M + 16 + 4 * k, d)) / (d2 * sqrtf(d2)), -2 * E);
                         h = h == h ? h : 0.0f;
                         h = h > REF_CLUSTER_MAX ? REF_CLUSTER_MAX : (h < -REF_CLUSTER_MAX ? -REF_CLUSTER_MAX : h);
                         sum += to_fixed(h);
