@@ -479,6 +479,14 @@ struct LayLegacy {
     }
 
     // any hit: order independent, children taken in slot order
+    // RENDER: the same step with its conditions formed on lane masks.  `bool & bool` is integer arithmetic, and the compiler
+    // takes it literally: each compare mask becomes a 0/1 register (v_cndmask_b32 0, 1), the or / and run in vector registers,
+    // a v_cmp turns each result back into a mask, and the "nothing hit" branch gets second, negated compares -- 13 vector
+    // instructions per step, most of them half rate, for four scalar instructions' worth of work.  (`&&` / `||` fare no
+    // better: two of the three conditions come out widened all the same.)  A ballot of a compare IS its mask, in an SGPR
+    // pair; the masks are combined as 64-bit integers on the scalar unit and handed back as branch masks by the inverse
+    // ballot.  One compare per child; same selects, same pop, the same three push blocks in the same order, so every
+    // stack operation, result and counter is what the form below gives.  DESIGN section 5 has the listings and the timing.
     template <bool COUNT, int OCT, bool EARLY, bool RENDER = false, bool NARROW = false, class N>
     static __device__ __forceinline__ void anyStep(const N& nd, const Ray& r, float tmin, float tcull, Stack& stack,
                                                    int& cur, uint32_t& cntNodes, const float4* __restrict__ nodes, Node& ndNext)
@@ -489,14 +497,34 @@ struct LayLegacy {
         bool hit[4];
         slab<OCT>(nd, r, tmin, tcull, tn, hit);
         const bool h0 = hit[0], h1 = hit[1], h2 = hit[2], h3 = hit[3];
-        cur = h0 ? refs.x : (h1 ? refs.y : (h2 ? refs.z : (h3 ? refs.w : (stack.sp == 0 ? kDone : stack.popAs<RENDER>()))));
-        if (EARLY) {
-            if (cur >= 0) ndNext = load<NARROW>(nodes, cur);
+        if constexpr (RENDER) {
+            const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1), m2 = __ballot(h2), m3 = __ballot(h3);
+            const unsigned long long m01 = m0 | m1, m012 = m01 | m2;
+            if constexpr (COUNT) {
+                // the counting variants keep the last select behind the pop: with three selects in front of it the chain's value
+                // lives across the pop's branches, and the counting Phong variant with wide offsets -- four counters more
+                // to hold -- then reloads its arena pointer inside the loops (22 spilled registers instead of 11)
+                cur = h0 ? refs.x : (h1 ? refs.y : (h2 ? refs.z : (__builtin_amdgcn_inverse_ballot_w64(m012 | m3) ? refs.w : (stack.sp == 0 ? kDone : stack.popLds()))));
+            } else {
+                cur = h0 ? refs.x : (h1 ? refs.y : (h2 ? refs.z : refs.w));
+                if (__builtin_amdgcn_inverse_ballot_w64(~(m012 | m3))) cur = stack.sp == 0 ? kDone : stack.popLds(); // a lane pops or pushes, never both
+            }
+            if (EARLY) {
+                if (cur >= 0) ndNext = load<NARROW>(nodes, cur);
+            }
+            if (__builtin_amdgcn_inverse_ballot_w64(m3 & m012)) stack.push(refs.w);
+            if (__builtin_amdgcn_inverse_ballot_w64(m2 & m01)) stack.push(refs.z);
+            if (__builtin_amdgcn_inverse_ballot_w64(m1 & m0)) stack.push(refs.y);
+        } else {
+            cur = h0 ? refs.x : (h1 ? refs.y : (h2 ? refs.z : (h3 ? refs.w : (stack.sp == 0 ? kDone : stack.popAs<RENDER>()))));
+            if (EARLY) {
+                if (cur >= 0) ndNext = load<NARROW>(nodes, cur);
+            }
+            // first hit slot became current; later hit slots are pushed, last slot first
+            if (h3 & (h0 | h1 | h2)) stack.push(refs.w);
+            if (h2 & (h0 | h1)) stack.push(refs.z);
+            if (h1 & h0) stack.push(refs.y);
         }
-        // first hit slot became current; later hit slots are pushed, last slot first
-        if (h3 & (h0 | h1 | h2)) stack.push(refs.w);
-        if (h2 & (h0 | h1)) stack.push(refs.z);
-        if (h1 & h0) stack.push(refs.y);
     }
 };
 
@@ -756,7 +784,12 @@ __device__ __forceinline__ bool anyIteration(const float4* __restrict__ nodes, c
                 }
             }
         }
-        cur = (occluded | (stack.sp == 0)) ? LayLegacy::kDone : stack.popAs<RENDER>();
+        if constexpr (RENDER) { // the pop condition on lane masks, as in anyStep: no 0/1 register and no 16-bit or
+            cur = LayLegacy::kDone;
+            if (__builtin_amdgcn_inverse_ballot_w64(~(__ballot(occluded) | __ballot(stack.sp == 0)))) cur = stack.popLds();
+        } else {
+            cur = (occluded | (stack.sp == 0)) ? LayLegacy::kDone : stack.popAs<RENDER>();
+        }
     }
 #if CRT_PROF
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
