@@ -248,8 +248,8 @@ struct crt_ctx {
     // of this pool belong to queries alone (never to a frame); serial = ++raySerial.
     Arena rayArena[kRing];
     uint32_t raySerial = 0;
-    uint32_t rayResident[9] = {};        // resident workgroups of each query kernel (QueryKind) on this device ...
-    uint32_t rayResidentEntries[9] = {}; // ... for this many LDS stack entries
+    uint32_t queryResident[crt::kQueryKinds] = {};        // resident workgroups of each query kernel on this device ...
+    uint32_t queryResidentEntries[crt::kQueryKinds] = {}; // ... for this many LDS stack entries
     void* dRayStage = nullptr; // the host entry points' records and outputs, grown on demand
     size_t rayStageBytes = 0;
     // crt_list_hits*: the host form's record arrays (grown on demand, apart from dRayStage, which holds its rays and offsets
@@ -1415,187 +1415,27 @@ int crt_accumulated_samples(const crt_ctx* c, uint32_t* samples)
 namespace {
 
 // Batched ray and point queries.  A query is n records of one kind (32-byte rays or 16-byte points) and up to seven outputs
-// of a fixed size per record; every kind runs one persistent kernel (ray_kernels.hip, point_kernels.hip) over an arena of
-// the context.
-enum QueryKind { kQueryClosestHit = 0, kQueryOcclusion = 1, kQueryClosestPoint = 2, kQueryCount = 3, kQueryOccupancy = 4,
-                 kQueryListFill = 5 /* the second traversal of crt_list_hits*: a kernel of its own, not an entry point */,
-                 kQueryShade = 6, kQueryPath = 7 /* crt_path_rays*: passes of (record, sample) items, not a QuerySpec */,
-                 kQueryWinding = 8 };
+// of a fixed size per record; every kind (crt::QueryKind) runs one persistent kernel over an arena of the context.
+using crt::QueryKind;
 constexpr int kQueryOutputs = 7; // the most any kind has (crt_shade_rays*)
-struct QueryOutput {
-    void* p = nullptr;
-    uint32_t bytes = 0; // per record
-    uint32_t align = 1; // of a device pointer
-};
+// what an entry point asks for
 struct QuerySpec {
     const char* what;
     QueryKind kind;
-    uint32_t recordBytes;
-    const char* outputNames; // for the alignment message
-    QueryOutput out[kQueryOutputs]; // the kind's outputs, in a fixed order; NULL = not wanted
-    float beta = 0.0f;              // crt_winding_numbers*: travels with the call
+    void* out[kQueryOutputs]; // the kind's outputs in the order of its QueryShape; NULL = not wanted
+    float beta = 0.0f;        // crt_winding_numbers*: travels with the call
 };
 
-QuerySpec rayQuerySpec(const char* what, bool occlusion, void* t, void* uv, void* inst, void* prim, void* occluded)
-{
-    QuerySpec s{ what, occlusion ? kQueryOcclusion : kQueryClosestHit, 32u, occlusion ? "occlusion" : "t / uv / inst / prim", {} };
-    if (occlusion) s.out[0] = { occluded, 1u, 1u };
-    else {
-        s.out[0] = { t, 4u, 4u };
-        s.out[1] = { uv, 8u, 8u };
-        s.out[2] = { inst, 4u, 4u };
-        s.out[3] = { prim, 4u, 4u };
-    }
-    return s;
-}
-
-// what every query entry point checks before anything is launched.  A shaded query (crt_shade_rays*) promises that a failed
-// call launches nothing: its refit follows its argument checks (queryDevice / queryHost) instead of coming here
-int checkQuery(crt_ctx* c, const QuerySpec& s)
-{
-    const char* what = s.what;
-    if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
-    if (!c->haveScene) return fail(c, CRT_ESTATE, "%s: no scene uploaded: call crt_upload_scene first", what);
-    if (s.kind == kQueryShade) {
-        if (c->mode >= 200u)
-            return fail(c, CRT_EINVAL, "%s: shading mode %u (path tracing) is not available for caller-supplied rays: set a mode below 200", what, c->mode);
-        return CRT_OK;
-    }
-    return applyRefit(c, nullptr);
-}
-
-int checkOutputs(crt_ctx* c, const QuerySpec& s)
-{
-    for (const QueryOutput& o : s.out)
-        if (o.p) return CRT_OK;
-    return fail(c, CRT_EINVAL, "%s: every output is NULL", s.what);
-}
-
-int checkDeviceOutputs(crt_ctx* c, const QuerySpec& s, const void* records)
-{
-    if (!records) return fail(c, CRT_EINVAL, "%s: record buffer is NULL", s.what);
-    if (reinterpret_cast<uintptr_t>(records) & 15u) return fail(c, CRT_EINVAL, "%s: record buffer %p is not 16-byte aligned", s.what, records);
-    if (const int rc = checkOutputs(c, s)) return rc;
-    for (const QueryOutput& o : s.out)
-        if (reinterpret_cast<uintptr_t>(o.p) & (o.align - 1u))
-            return fail(c, CRT_EINVAL, "%s: output %p (%s) is not %u-byte aligned", s.what, o.p, s.outputNames, o.align);
-    return CRT_OK;
-}
-
-// resident workgroups of the kind's kernel with the LDS stack the options ask for, from the context's cache; the persistent
-// grid and the chunking of n records follow from it
-int queryGrid(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t& stack_entries, uint32_t& chunk, uint32_t& grid)
-{
-    stack_entries = c->tuneStackEntries ? c->tuneStackEntries : 16u; // as fillParams
-    if (c->rayResident[kind] == 0u || c->rayResidentEntries[kind] != stack_entries) {
-        uint32_t r = 0u;
-        switch (kind) {
-        case kQueryClosestHit: r = crt::rayQueryResident(false, stack_entries); break;
-        case kQueryOcclusion: r = crt::rayQueryResident(true, stack_entries); break;
-        case kQueryClosestPoint: r = crt::pointQueryResident(crt::kPointClosest, stack_entries); break;
-        case kQueryCount: r = crt::pointQueryResident(crt::kPointCount, stack_entries); break;
-        case kQueryOccupancy: r = crt::pointQueryResident(crt::kPointOccupancy, stack_entries); break;
-        case kQueryListFill: r = crt::listFillResident(stack_entries); break;
-        case kQueryShade: r = crt::shadeQueryResident(stack_entries); break;
-        case kQueryPath: r = crt::pathQueryResident(stack_entries); break;
-        case kQueryWinding: r = crt::windingQueryResident(stack_entries); break;
-        }
-        c->rayResident[kind] = r;
-        c->rayResidentEntries[kind] = stack_entries;
-        if (r == 0u) return fail(c, CRT_EHIP, "query kernel: occupancy query failed");
-    }
-    crt::rayQueryLayout(n, c->rayResident[kind], chunk, grid);
-    return CRT_OK;
-}
-
-// What a query kernel gets from its arena: grid, chunking, cursor, counters and the stack spill arena
-struct QueryLaunch {
-    uint32_t stack_entries, spill_stride, chunk, grid;
-    uint32_t* cursor;
-    unsigned long long* counters;
-    int* spill;
-    unsigned char* extra; // extraBytes of the arena behind the spill area (256-byte aligned), or null
-    crt_ctx::Arena* arena;
+// The parameter struct of a kind with an entry point of its own, each beginning with its QueryCommon (c), and what fills it
+// from the call: d = the outputs as device pointers; innerMin = the scheduling knob the kind's traversal reads
+union QueryParams {
+    crt::QueryCommon c;
+    crt::RayQueryParams ray;
+    crt::PointQueryParams point;
+    crt::WindingQueryParams winding;
+    crt::ShadeQueryParams shade;
 };
-
-// One query of n > 0 records on the context's stream, in two halves around the kernel launch.  beginQuery sizes the persistent
-// grid, takes an arena and (with stats) starts the timer; entryWords = ints per stack entry.  endQuery takes the launch's HIP
-// error code and, with stats, synchronises and fills them.
-// extraBytes: scratch of the query's own with the arena's lifetime (an allocation failure is then CRT_ENOMEM); minGrid: the
-// spill area is sized for at least that many workgroups (a query that runs a second persistent kernel over the same arena).
-int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t entryWords, crt_frame_stats* stats, QueryLaunch& ql, size_t extraBytes = 0,
-               uint32_t minGrid = 0)
-{
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (const int rc = queryGrid(c, kind, n, ql.stack_entries, ql.chunk, ql.grid)) return rc;
-    const uint32_t deepest = 3u * c->bvh.depth4 + 1u; // as frameSpill
-    ql.spill_stride = (deepest > ql.stack_entries ? deepest - ql.stack_entries : 1u) * entryWords;
-
-    constexpr size_t kHead = 256; // cursor at 0, counters at 64
-    const size_t spillBytes = up256(static_cast<size_t>(std::max(ql.grid, minGrid)) * 64u * ql.spill_stride * sizeof(int));
-    crt_ctx::Arena* arena = nullptr;
-    if (const int rc = takeArena(c, c->rayArena, kHead + spillBytes + extraBytes, ++c->raySerial, extraBytes != 0u, arena)) return rc;
-    ql.extra = extraBytes ? arena->mem + kHead + spillBytes : nullptr;
-    ql.cursor = reinterpret_cast<uint32_t*>(arena->mem);
-    ql.counters = reinterpret_cast<unsigned long long*>(arena->mem + 64);
-    ql.spill = reinterpret_cast<int*>(arena->mem + kHead);
-    HIP_TRY(c, hipMemsetAsync(arena->mem, 0, kHead, c->stream));
-    ql.arena = arena;
-    if (stats) HIP_TRY(c, hipEventRecord(c->evStart, c->stream));
-    return CRT_OK;
-}
-
-int endQuery(crt_ctx* c, QueryKind kind, uint32_t n, const QueryLaunch& ql, int rc, crt_frame_stats* stats)
-{
-    if (rc != 0) return fail(c, CRT_EHIP, "query kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
-    if (stats) HIP_TRY(c, hipEventRecord(c->evStop, c->stream));
-    HIP_TRY(c, ql.arena->lastUse.record(c->stream));
-    if (!stats) return CRT_OK;
-    unsigned long long words[4]; // (zeros unless counting is on)
-    if (const int rs = readStats(c, stats, ql.counters, words)) return rs;
-    if (kind == kQueryOcclusion) stats->rays_shadow = n;
-    else stats->rays_primary = kind == kQueryOccupancy ? 3ull * n : n;
-    if (c->counting && (kind == kQueryShade || kind == kQueryPath)) stats->rays_shadow = words[2]; // the shadow rays traced (mode 100; paths)
-    if (kind == kQueryPath) stats->rays_primary += words[3];                                      // the bounce rays of the paths
-    return CRT_OK;
-}
-
-// the part of a query kernel's parameters every kind shares, from the context and the launch
-crt::QueryCommon queryCommon(const crt_ctx* c, const QueryLaunch& ql, const void* d_records, uint32_t n, uint32_t inner_min)
-{
-    crt::QueryCommon q;
-    q.nodes = c->dNodes;
-    q.tris = c->dTris;
-    q.n_nodes = c->bvh.dev.nNodes4;
-    q.records = d_records;
-    q.n = n;
-    q.cursor = ql.cursor;
-    q.counters = ql.counters;
-    q.spill = ql.spill;
-    q.spill_stride = ql.spill_stride;
-    q.stack_entries = ql.stack_entries;
-    q.inner_min = inner_min;
-    q.chunk = ql.chunk;
-    return q;
-}
-
-int runRayQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_rays, void* const d[kQueryOutputs], crt_frame_stats* stats)
-{
-    const bool occlusion = s.kind == kQueryOcclusion;
-    crt::RayQueryParams q;
-    std::memset(&q, 0, sizeof(q));
-    if (occlusion) q.occluded = static_cast<unsigned char*>(d[0]);
-    else {
-        q.t = static_cast<float*>(d[0]);
-        q.uv = static_cast<float*>(d[1]);
-        q.inst = static_cast<uint32_t*>(d[2]);
-        q.prim = static_cast<uint32_t*>(d[3]);
-    }
-    QueryLaunch ql;
-    if (const int rc = beginQuery(c, s.kind, n, 1u, stats, ql)) return rc;
-    q.c = queryCommon(c, ql, d_rays, n, occlusion ? c->tuneInnerMinAny : c->tuneInnerMin);
-    return endQuery(c, s.kind, n, ql, crt::launchRayQuery(q, occlusion, c->counting, ql.grid, c->stream), stats);
-}
+using QueryFill = int (*)(crt_ctx* c, const QuerySpec& s, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin);
 
 // the closest-point search's absolute pruning margin: 2^-18 x the diagonal of the root box, rounded up
 float pointPad(const crt_ctx* c)
@@ -1606,29 +1446,6 @@ float pointPad(const crt_ctx* c)
         dd += e * e;
     }
     return static_cast<float>(std::sqrt(dd) * 0x1p-18 * (1.0 + 0x1p-20));
-}
-
-int runPointQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, void* const d[kQueryOutputs], crt_frame_stats* stats)
-{
-    const crt::PointQueryKind pk = s.kind == kQueryClosestPoint ? crt::kPointClosest : (s.kind == kQueryCount ? crt::kPointCount : crt::kPointOccupancy);
-    crt::PointQueryParams q;
-    std::memset(&q, 0, sizeof(q));
-    if (pk == crt::kPointClosest) {
-        q.dist = static_cast<float*>(d[0]);
-        q.point = static_cast<float*>(d[1]);
-        q.uv = static_cast<float*>(d[2]);
-        q.inst = static_cast<uint32_t*>(d[3]);
-        q.prim = static_cast<uint32_t*>(d[4]);
-        q.pad = pointPad(c);
-    } else if (pk == crt::kPointCount) {
-        q.count = static_cast<uint32_t*>(d[0]);
-    } else {
-        q.inside = static_cast<unsigned char*>(d[0]);
-    }
-    QueryLaunch ql;
-    if (const int rc = beginQuery(c, s.kind, n, crt::pointQueryEntryWords(pk), stats, ql)) return rc;
-    q.c = queryCommon(c, ql, d_records, n, pk == crt::kPointClosest ? c->tuneInnerMin : c->tuneInnerMinAny);
-    return endQuery(c, s.kind, n, ql, crt::launchPointQuery(q, pk, c->counting, ql.grid, c->stream), stats);
 }
 
 // The moment table of the tree as it stands (crt_winding_numbers*, crt_winding_moments_export), built on the context's stream
@@ -1657,21 +1474,6 @@ int ensureMoments(crt_ctx* c)
     return CRT_OK;
 }
 
-// crt_winding_numbers*: the walk over the tree and its moment table (winding_kernels.hip)
-int runWindingQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, void* const d[kQueryOutputs], crt_frame_stats* stats)
-{
-    if (const int rc = ensureMoments(c)) return rc;
-    crt::WindingQueryParams q;
-    std::memset(&q, 0, sizeof(q));
-    q.moments = static_cast<const float*>(c->dMoments);
-    q.beta = s.beta > 0.0f ? s.beta : 0.0f; // (a NaN too)
-    q.w = static_cast<float*>(d[0]);
-    QueryLaunch ql;
-    if (const int rc = beginQuery(c, s.kind, n, 1u, stats, ql)) return rc;
-    q.c = queryCommon(c, ql, d_records, n, c->tuneInnerMinAny);
-    return endQuery(c, s.kind, n, ql, crt::launchWindingQuery(q, c->counting, ql.grid, c->stream), stats);
-}
-
 // the scene's shading tables (sceneTables) and the context's shading state of a shaded query
 void shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q)
 {
@@ -1681,31 +1483,223 @@ void shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q)
     q.phong_exp = c->phongExp;
 }
 
-// crt_shade_rays*: the closest hit and the context's shading mode at it (shade_kernels.hip)
-int runShadeQuery(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_rays, void* const d[kQueryOutputs], crt_frame_stats* stats)
+int fillClosestHit(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
 {
-    crt::ShadeQueryParams q;
-    std::memset(&q, 0, sizeof(q));
-    q.rgb = static_cast<float*>(d[0]);
-    q.normal = static_cast<float*>(d[1]);
-    q.albedo = static_cast<float*>(d[2]);
-    q.t = static_cast<float*>(d[3]);
-    q.uv = static_cast<float*>(d[4]);
-    q.inst = static_cast<uint32_t*>(d[5]);
-    q.prim = static_cast<uint32_t*>(d[6]);
-    shadeTables(c, q);
-    QueryLaunch ql;
-    if (const int rc = beginQuery(c, s.kind, n, 1u, stats, ql)) return rc;
-    q.c = queryCommon(c, ql, d_rays, n, c->tuneInnerMin);
-    return endQuery(c, s.kind, n, ql, crt::launchShadeQuery(q, c->counting, ql.grid, c->stream), stats);
+    p.ray.t = static_cast<float*>(d[0]);
+    p.ray.uv = static_cast<float*>(d[1]);
+    p.ray.inst = static_cast<uint32_t*>(d[2]);
+    p.ray.prim = static_cast<uint32_t*>(d[3]);
+    innerMin = c->tuneInnerMin;
+    return CRT_OK;
+}
+int fillOcclusion(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
+{
+    p.ray.occluded = static_cast<unsigned char*>(d[0]);
+    innerMin = c->tuneInnerMinAny;
+    return CRT_OK;
+}
+int fillClosestPoint(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
+{
+    p.point.dist = static_cast<float*>(d[0]);
+    p.point.point = static_cast<float*>(d[1]);
+    p.point.uv = static_cast<float*>(d[2]);
+    p.point.inst = static_cast<uint32_t*>(d[3]);
+    p.point.prim = static_cast<uint32_t*>(d[4]);
+    p.point.pad = pointPad(c);
+    innerMin = c->tuneInnerMin;
+    return CRT_OK;
+}
+int fillCount(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
+{
+    p.point.count = static_cast<uint32_t*>(d[0]);
+    innerMin = c->tuneInnerMinAny;
+    return CRT_OK;
+}
+int fillOccupancy(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
+{
+    p.point.inside = static_cast<unsigned char*>(d[0]);
+    innerMin = c->tuneInnerMinAny;
+    return CRT_OK;
+}
+// crt_shade_rays*: the closest hit and the context's shading mode at it (shade_kernels.hip)
+int fillShade(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
+{
+    p.shade.rgb = static_cast<float*>(d[0]);
+    p.shade.normal = static_cast<float*>(d[1]);
+    p.shade.albedo = static_cast<float*>(d[2]);
+    p.shade.t = static_cast<float*>(d[3]);
+    p.shade.uv = static_cast<float*>(d[4]);
+    p.shade.inst = static_cast<uint32_t*>(d[5]);
+    p.shade.prim = static_cast<uint32_t*>(d[6]);
+    shadeTables(c, p.shade);
+    innerMin = c->tuneInnerMin;
+    return CRT_OK;
+}
+// crt_winding_numbers*: the walk over the tree and its moment table (winding_kernels.hip)
+int fillWinding(crt_ctx* c, const QuerySpec& s, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
+{
+    if (const int rc = ensureMoments(c)) return rc;
+    p.winding.moments = static_cast<const float*>(c->dMoments);
+    p.winding.beta = s.beta > 0.0f ? s.beta : 0.0f; // (a NaN too)
+    p.winding.w = static_cast<float*>(d[0]);
+    innerMin = c->tuneInnerMinAny;
+    return CRT_OK;
 }
 
+// The static shape of a kind, by QueryKind: its records, its outputs in a fixed order and its fill.  (The listing's fill and
+// the path-traced queries have no entry point that comes through a QuerySpec.)
+struct QueryShape {
+    uint32_t recordBytes;
+    const char* outputNames; // for the alignment message
+    struct {
+        uint32_t bytes; // per record
+        uint32_t align; // of a device pointer
+    } out[kQueryOutputs];
+    QueryFill fill;
+};
+const QueryShape kQueryShapes[crt::kQueryKinds] = {
+    /* kQueryClosestHit */ { 32u, "t / uv / inst / prim", { { 4u, 4u }, { 8u, 8u }, { 4u, 4u }, { 4u, 4u } }, fillClosestHit },
+    /* kQueryOcclusion */ { 32u, "occlusion", { { 1u, 1u } }, fillOcclusion },
+    /* kQueryClosestPoint */
+    { 16u, "dist / point / uv / inst / prim", { { 4u, 4u }, { 12u, 4u }, { 8u, 8u }, { 4u, 4u }, { 4u, 4u } }, fillClosestPoint },
+    /* kQueryCount */ { 32u, "count", { { 4u, 4u } }, fillCount },
+    /* kQueryOccupancy */ { 16u, "inside", { { 1u, 1u } }, fillOccupancy },
+    /* kQueryListFill */ {},
+    /* kQueryShade */
+    { 32u, "rgb / normal / albedo / t / uv / inst / prim", { { 12u, 4u }, { 12u, 4u }, { 12u, 4u }, { 4u, 4u }, { 8u, 8u }, { 4u, 4u }, { 4u, 4u } }, fillShade },
+    /* kQueryPath */ {},
+    /* kQueryWinding */ { 16u, "w", { { 4u, 4u } }, fillWinding },
+};
+
+// what every query entry point checks before anything is launched.  A shaded query (crt_shade_rays*) promises that a failed
+// call launches nothing: its refit follows its argument checks (queryDevice / queryHost) instead of coming here
+int checkQuery(crt_ctx* c, const QuerySpec& s)
+{
+    const char* what = s.what;
+    if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
+    if (!c->haveScene) return fail(c, CRT_ESTATE, "%s: no scene uploaded: call crt_upload_scene first", what);
+    if (s.kind == crt::kQueryShade) {
+        if (c->mode >= 200u)
+            return fail(c, CRT_EINVAL, "%s: shading mode %u (path tracing) is not available for caller-supplied rays: set a mode below 200", what, c->mode);
+        return CRT_OK;
+    }
+    return applyRefit(c, nullptr);
+}
+
+int checkOutputs(crt_ctx* c, const QuerySpec& s)
+{
+    for (const void* p : s.out)
+        if (p) return CRT_OK;
+    return fail(c, CRT_EINVAL, "%s: every output is NULL", s.what);
+}
+
+int checkDeviceOutputs(crt_ctx* c, const QuerySpec& s, const void* records)
+{
+    if (!records) return fail(c, CRT_EINVAL, "%s: record buffer is NULL", s.what);
+    if (reinterpret_cast<uintptr_t>(records) & 15u) return fail(c, CRT_EINVAL, "%s: record buffer %p is not 16-byte aligned", s.what, records);
+    if (const int rc = checkOutputs(c, s)) return rc;
+    const QueryShape& shape = kQueryShapes[s.kind];
+    for (int i = 0; i < kQueryOutputs; i++)
+        if (s.out[i] && (reinterpret_cast<uintptr_t>(s.out[i]) & (shape.out[i].align - 1u)))
+            return fail(c, CRT_EINVAL, "%s: output %p (%s) is not %u-byte aligned", s.what, s.out[i], shape.outputNames, shape.out[i].align);
+    return CRT_OK;
+}
+
+// resident workgroups of the kind's kernel with the LDS stack the options ask for, from the context's cache; the persistent
+// grid and the chunking of n records follow from it
+int queryGrid(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t& stack_entries, uint32_t& chunk, uint32_t& grid)
+{
+    stack_entries = c->tuneStackEntries ? c->tuneStackEntries : 16u; // as fillParams
+    if (c->queryResident[kind] == 0u || c->queryResidentEntries[kind] != stack_entries) {
+        c->queryResident[kind] = crt::queryResident(kind, stack_entries);
+        c->queryResidentEntries[kind] = stack_entries;
+        if (c->queryResident[kind] == 0u) return fail(c, CRT_EHIP, "query kernel: occupancy query failed");
+    }
+    crt::queryLayout(n, c->queryResident[kind], chunk, grid);
+    return CRT_OK;
+}
+
+// What a query kernel gets from its arena: grid, chunking, cursor, counters and the stack spill arena
+struct QueryLaunch {
+    uint32_t stack_entries, spill_stride, chunk, grid;
+    uint32_t* cursor;
+    unsigned long long* counters;
+    int* spill;
+    unsigned char* extra; // extraBytes of the arena behind the spill area (256-byte aligned), or null
+    crt_ctx::Arena* arena;
+};
+
+// One query of n > 0 records on the context's stream, in two halves around the kernel launch.  beginQuery sizes the persistent
+// grid, takes an arena and (with stats) starts the timer.  endQuery takes the launch's HIP error code and, with stats,
+// synchronises and fills them.
+// extraBytes: scratch of the query's own with the arena's lifetime (an allocation failure is then CRT_ENOMEM); minGrid: the
+// spill area is sized for at least that many workgroups (a query that runs a second persistent kernel over the same arena).
+int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, crt_frame_stats* stats, QueryLaunch& ql, size_t extraBytes = 0, uint32_t minGrid = 0)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const int rc = queryGrid(c, kind, n, ql.stack_entries, ql.chunk, ql.grid)) return rc;
+    const uint32_t deepest = 3u * c->bvh.depth4 + 1u; // as frameSpill
+    ql.spill_stride = (deepest > ql.stack_entries ? deepest - ql.stack_entries : 1u) * crt::queryKernel(kind).entryWords;
+
+    constexpr size_t kHead = 256; // cursor at 0, counters at 64
+    const size_t spillBytes = up256(static_cast<size_t>(std::max(ql.grid, minGrid)) * 64u * ql.spill_stride * sizeof(int));
+    crt_ctx::Arena* arena = nullptr;
+    if (const int rc = takeArena(c, c->rayArena, kHead + spillBytes + extraBytes, ++c->raySerial, extraBytes != 0u, arena)) return rc;
+    ql.extra = extraBytes ? arena->mem + kHead + spillBytes : nullptr;
+    ql.cursor = reinterpret_cast<uint32_t*>(arena->mem);
+    ql.counters = reinterpret_cast<unsigned long long*>(arena->mem + 64);
+    ql.spill = reinterpret_cast<int*>(arena->mem + kHead);
+    HIP_TRY(c, hipMemsetAsync(arena->mem, 0, kHead, c->stream));
+    ql.arena = arena;
+    if (stats) HIP_TRY(c, hipEventRecord(c->evStart, c->stream));
+    return CRT_OK;
+}
+
+int endQuery(crt_ctx* c, QueryKind kind, uint32_t n, const QueryLaunch& ql, int rc, crt_frame_stats* stats)
+{
+    if (rc != 0) return fail(c, CRT_EHIP, "query kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
+    if (stats) HIP_TRY(c, hipEventRecord(c->evStop, c->stream));
+    HIP_TRY(c, ql.arena->lastUse.record(c->stream));
+    if (!stats) return CRT_OK;
+    unsigned long long words[4]; // (zeros unless counting is on)
+    if (const int rs = readStats(c, stats, ql.counters, words)) return rs;
+    if (kind == crt::kQueryOcclusion) stats->rays_shadow = n;
+    else stats->rays_primary = kind == crt::kQueryOccupancy ? 3ull * n : n;
+    if (c->counting && (kind == crt::kQueryShade || kind == crt::kQueryPath)) stats->rays_shadow = words[2]; // the shadow rays traced (mode 100; paths)
+    if (kind == crt::kQueryPath) stats->rays_primary += words[3];                                      // the bounce rays of the paths
+    return CRT_OK;
+}
+
+// the part of a query kernel's parameters every kind shares, from the context and the launch
+crt::QueryCommon queryCommon(const crt_ctx* c, const QueryLaunch& ql, const void* d_records, uint32_t n, uint32_t inner_min)
+{
+    crt::QueryCommon q;
+    q.nodes = c->dNodes;
+    q.tris = c->dTris;
+    q.n_nodes = c->bvh.dev.nNodes4;
+    q.records = d_records;
+    q.n = n;
+    q.cursor = ql.cursor;
+    q.counters = ql.counters;
+    q.spill = ql.spill;
+    q.spill_stride = ql.spill_stride;
+    q.stack_entries = ql.stack_entries;
+    q.inner_min = inner_min;
+    q.chunk = ql.chunk;
+    return q;
+}
+
+// a query of any kind with an entry point: its fill, then one launch between beginQuery and endQuery
 int runKind(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, void* const d[kQueryOutputs], crt_frame_stats* stats)
 {
-    if (s.kind == kQueryShade) return runShadeQuery(c, s, n, d_records, d, stats);
-    if (s.kind == kQueryClosestHit || s.kind == kQueryOcclusion) return runRayQuery(c, s, n, d_records, d, stats);
-    if (s.kind == kQueryWinding) return runWindingQuery(c, s, n, d_records, d, stats);
-    return runPointQuery(c, s, n, d_records, d, stats);
+    QueryParams p;
+    std::memset(&p, 0, sizeof(p));
+    uint32_t innerMin = 0;
+    if (const int rc = kQueryShapes[s.kind].fill(c, s, d, p, innerMin)) return rc;
+    QueryLaunch ql;
+    if (const int rc = beginQuery(c, s.kind, n, stats, ql)) return rc;
+    p.c = queryCommon(c, ql, d_records, n, innerMin);
+    return endQuery(c, s.kind, n, ql, crt::launchQuery(s.kind, &p, c->counting, ql.grid, c->stream), stats);
 }
 
 void zeroStats(crt_frame_stats* stats, std::chrono::steady_clock::time_point t0)
@@ -1725,10 +1719,8 @@ int queryDevice(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_record
         return CRT_OK;
     }
     if ((rc = checkDeviceOutputs(c, s, d_records)) != CRT_OK) return rc;
-    if (s.kind == kQueryShade && (rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
-    void* d[kQueryOutputs];
-    for (int i = 0; i < kQueryOutputs; i++) d[i] = s.out[i].p;
-    if ((rc = runKind(c, s, n, d_records, d, stats)) != CRT_OK) return rc;
+    if (s.kind == crt::kQueryShade && (rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    if ((rc = runKind(c, s, n, d_records, s.out, stats)) != CRT_OK) return rc;
     stampTotal(stats, t0);
     return CRT_OK;
 }
@@ -1745,10 +1737,11 @@ int queryHost(crt_ctx* c, const QuerySpec& s, uint32_t n, const float* records, 
     }
     if (!records) return fail(c, CRT_EINVAL, "%s: record buffer is NULL", s.what);
     if ((rc = checkOutputs(c, s)) != CRT_OK) return rc;
-    if (s.kind == kQueryShade && (rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    if (s.kind == crt::kQueryShade && (rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
     constexpr int kPlanes = 1 + kQueryOutputs;
-    StagePlane planes[kPlanes] = { { records, nullptr, static_cast<size_t>(n) * s.recordBytes } };
-    for (int i = 0; i < kQueryOutputs; i++) planes[1 + i] = { nullptr, s.out[i].p, static_cast<size_t>(n) * s.out[i].bytes };
+    const QueryShape& shape = kQueryShapes[s.kind];
+    StagePlane planes[kPlanes] = { { records, nullptr, static_cast<size_t>(n) * shape.recordBytes } };
+    for (int i = 0; i < kQueryOutputs; i++) planes[1 + i] = { nullptr, s.out[i], static_cast<size_t>(n) * shape.out[i].bytes };
     void* dev[kPlanes];
     if ((rc = stageBegin(c, planes, kPlanes, dev)) != CRT_OK) return rc;
     crt_frame_stats local;
@@ -1758,28 +1751,6 @@ int queryHost(crt_ctx* c, const QuerySpec& s, uint32_t n, const float* records, 
     return CRT_OK;
 }
 
-QuerySpec closestPointSpec(const char* what, void* dist, void* point, void* uv, void* inst, void* prim)
-{
-    QuerySpec s{ what, kQueryClosestPoint, 16u, "dist / point / uv / inst / prim", {} };
-    s.out[0] = { dist, 4u, 4u };
-    s.out[1] = { point, 12u, 4u };
-    s.out[2] = { uv, 8u, 8u };
-    s.out[3] = { inst, 4u, 4u };
-    s.out[4] = { prim, 4u, 4u };
-    return s;
-}
-QuerySpec shadeSpec(const char* what, void* rgb, void* normal, void* albedo, void* t, void* uv, void* inst, void* prim)
-{
-    QuerySpec s{ what, kQueryShade, 32u, "rgb / normal / albedo / t / uv / inst / prim", {} };
-    s.out[0] = { rgb, 12u, 4u };
-    s.out[1] = { normal, 12u, 4u };
-    s.out[2] = { albedo, 12u, 4u };
-    s.out[3] = { t, 4u, 4u };
-    s.out[4] = { uv, 8u, 8u };
-    s.out[5] = { inst, 4u, 4u };
-    s.out[6] = { prim, 4u, 4u };
-    return s;
-}
 // ---- crt_path_rays*: the frames' mode-200 paths for caller records (path_query_kernels.hip).  Work items are (record, sample)
 // pairs; a launch covers at most "path_pass_paths" of them (all records x a range of samples; a buffer of more records than
 // that is also cut into blocks of records), each followed by the resolve that adds the pass's samples to the running sums.
@@ -1824,7 +1795,7 @@ int runPathQuery(crt_ctx* c, uint32_t n, const PathCall& a, crt_frame_stats* sta
     q.max_bounces = c->pathBounces;
     q.seed = c->pathSeed;
     QueryLaunch ql;
-    if (const int rc = beginQuery(c, kQueryPath, static_cast<uint32_t>(slots), 1u, stats, ql, 2u * slotBytes + sumBytes)) return rc;
+    if (const int rc = beginQuery(c, crt::kQueryPath, static_cast<uint32_t>(slots), stats, ql, 2u * slotBytes + sumBytes)) return rc;
     q.rad = ql.extra;
     q.thr = ql.extra + slotBytes;
     double* kept = keepSums ? reinterpret_cast<double*>(ql.extra + 2u * slotBytes) : nullptr;
@@ -1841,7 +1812,7 @@ int runPathQuery(crt_ctx* c, uint32_t n, const PathCall& a, crt_frame_stats* sta
             if (launched) HIP_TRY(c, hipMemsetAsync(ql.cursor, 0, sizeof(uint32_t), c->stream)); // (the counters go on counting)
             launched = true;
             uint32_t chunk = 0, grid = 0;
-            crt::rayQueryLayout(items, c->rayResident[kQueryPath], chunk, grid);
+            crt::queryLayout(items, c->queryResident[crt::kQueryPath], chunk, grid);
             grid = std::min(grid, ql.grid); // (the spill area is sized for ql.grid workgroups, the largest pass's)
             q.c = queryCommon(c, ql, static_cast<const unsigned char*>(a.rays) + 32u * r0, items, c->tuneInnerMin);
             q.c.chunk = chunk;
@@ -1854,7 +1825,7 @@ int runPathQuery(crt_ctx* c, uint32_t n, const PathCall& a, crt_frame_stats* sta
             q.uv = firstPass && a.uv ? a.uv + 2u * r0 : nullptr;
             q.inst = firstPass && a.inst ? a.inst + r0 : nullptr;
             q.prim = firstPass && a.prim ? a.prim + r0 : nullptr;
-            hrc = crt::launchPathQuery(q, c->counting, grid, c->stream);
+            hrc = crt::launchQuery(crt::kQueryPath, &q, c->counting, grid, c->stream);
             if (hrc == 0 && (a.rgb || a.sums)) {
                 const double* in = firstPass ? (sums && a.first > 0u ? sums : nullptr) : running;
                 double* out = lastPass ? sums : running;
@@ -1863,14 +1834,10 @@ int runPathQuery(crt_ctx* c, uint32_t n, const PathCall& a, crt_frame_stats* sta
             }
         }
     }
-    if (const int rc = endQuery(c, kQueryPath, 0u, ql, hrc, stats)) return rc;
+    if (const int rc = endQuery(c, crt::kQueryPath, 0u, ql, hrc, stats)) return rc;
     if (stats) stats->rays_primary += static_cast<uint64_t>(n) * a.samples; // (endQuery: the bounce rays, with counting)
     return CRT_OK;
 }
-
-QuerySpec countSpec(const char* what, void* count) { return QuerySpec{ what, kQueryCount, 32u, "count", { { count, 4u, 4u } } }; }
-QuerySpec occupancySpec(const char* what, void* inside) { return QuerySpec{ what, kQueryOccupancy, 16u, "inside", { { inside, 1u, 1u } } }; }
-QuerySpec windingSpec(const char* what, void* w, float beta) { return QuerySpec{ what, kQueryWinding, 16u, "w", { { w, 4u, 4u } }, beta }; }
 
 // ---- all-hits listing (crt_list_hits*): count -> scan -> fill -> sort + resolve over one arena, between one beginQuery and
 // one endQuery.  The counts (reused as the sort's queue of long rays), the scan's tile sums and the key scratch live in the
@@ -1894,13 +1861,13 @@ int listBegin(crt_ctx* c, uint32_t n, const void* d_rays, void* d_offsets, size_
 {
     HIP_TRY(c, hipSetDevice(c->device));
     uint32_t entries = 0;
-    if (const int rc = queryGrid(c, kQueryListFill, n, entries, lr.fillChunk, lr.fillGrid)) return rc;
+    if (const int rc = queryGrid(c, crt::kQueryListFill, n, entries, lr.fillChunk, lr.fillGrid)) return rc;
     lr.timed = stats != nullptr;
     if (lr.timed)
         for (hipEvent_t& e : c->evList)
             if (!e) HIP_TRY(c, hipEventCreate(&e));
     const size_t countBytes = up256(static_cast<size_t>(n) * sizeof(uint32_t)), scanBytes = up256(crt::listScanScratchBytes(n));
-    if (const int rc = beginQuery(c, kQueryCount, n, 1u, stats, lr.ql, countBytes + scanBytes + keyBytes, lr.fillGrid)) return rc;
+    if (const int rc = beginQuery(c, crt::kQueryCount, n, stats, lr.ql, countBytes + scanBytes + keyBytes, lr.fillGrid)) return rc;
     const QueryLaunch& ql = lr.ql;
     uint32_t* counts = reinterpret_cast<uint32_t*>(ql.extra);
     unsigned long long* tileSums = reinterpret_cast<unsigned long long*>(ql.extra + countBytes);
@@ -1921,11 +1888,11 @@ int listBegin(crt_ctx* c, uint32_t n, const void* d_rays, void* d_offsets, size_
     q.short_max = c->tuneListShortMax;
 
     int rc = listMark(c, lr, 0);
-    if (rc == 0) rc = crt::launchPointQuery(pq, crt::kPointCount, c->counting, ql.grid, c->stream);
+    if (rc == 0) rc = crt::launchQuery(crt::kQueryCount, &pq, c->counting, ql.grid, c->stream);
     if (rc == 0) rc = listMark(c, lr, 1);
     if (rc == 0) rc = crt::launchListScan(counts, n, static_cast<unsigned long long*>(d_offsets), tileSums, c->stream);
     if (rc == 0) rc = listMark(c, lr, 2);
-    return rc == 0 ? CRT_OK : endQuery(c, kQueryCount, n, ql, rc, nullptr);
+    return rc == 0 ? CRT_OK : endQuery(c, crt::kQueryCount, n, ql, rc, nullptr);
 }
 
 // fill + sort + resolve into the record arrays: the cursor (not the counters) starts again for the second traversal
@@ -1941,7 +1908,7 @@ int listFill(crt_ctx* c, ListRun& lr, unsigned long long capacity, float* tkey, 
     q.prim = static_cast<uint32_t*>(out[3]);
     const hipError_t e = hipMemsetAsync(q.c.cursor, 0, sizeof(uint32_t), c->stream);
     if (e != hipSuccess) return static_cast<int>(e);
-    int rc = crt::launchListFill(q, c->counting, lr.fillGrid, c->stream);
+    int rc = crt::launchQuery(crt::kQueryListFill, &q, c->counting, lr.fillGrid, c->stream);
     if (rc == 0) rc = listMark(c, lr, 3);
     if (rc == 0) rc = crt::launchListSort(q, c->stream);
     if (rc == 0) rc = listMark(c, lr, 4);
@@ -1981,34 +1948,34 @@ int listCheck(crt_ctx* c, const char* what, uint32_t n, const void* rays, const 
 
 int crt_trace_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_t, void* d_uv, void* d_inst, void* d_prim, crt_frame_stats* stats)
 {
-    return queryDevice(c, rayQuerySpec("crt_trace_rays_device", false, d_t, d_uv, d_inst, d_prim, nullptr), n, d_rays, stats);
+    return queryDevice(c, { "crt_trace_rays_device", crt::kQueryClosestHit, { d_t, d_uv, d_inst, d_prim } }, n, d_rays, stats);
 }
 
 int crt_occluded_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_occluded, crt_frame_stats* stats)
 {
-    return queryDevice(c, rayQuerySpec("crt_occluded_rays_device", true, nullptr, nullptr, nullptr, nullptr, d_occluded), n, d_rays, stats);
+    return queryDevice(c, { "crt_occluded_rays_device", crt::kQueryOcclusion, { d_occluded } }, n, d_rays, stats);
 }
 
 int crt_trace_rays(crt_ctx* c, uint32_t n, const float* rays, float* t, float* uv, uint32_t* inst, uint32_t* prim, crt_frame_stats* stats)
 {
-    return queryHost(c, rayQuerySpec("crt_trace_rays", false, t, uv, inst, prim, nullptr), n, rays, stats);
+    return queryHost(c, { "crt_trace_rays", crt::kQueryClosestHit, { t, uv, inst, prim } }, n, rays, stats);
 }
 
 int crt_occluded_rays(crt_ctx* c, uint32_t n, const float* rays, uint8_t* occluded, crt_frame_stats* stats)
 {
-    return queryHost(c, rayQuerySpec("crt_occluded_rays", true, nullptr, nullptr, nullptr, nullptr, occluded), n, rays, stats);
+    return queryHost(c, { "crt_occluded_rays", crt::kQueryOcclusion, { occluded } }, n, rays, stats);
 }
 
 int crt_shade_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_rgb, void* d_normal, void* d_albedo, void* d_t, void* d_uv,
                           void* d_inst, void* d_prim, crt_frame_stats* stats)
 {
-    return queryDevice(c, shadeSpec("crt_shade_rays_device", d_rgb, d_normal, d_albedo, d_t, d_uv, d_inst, d_prim), n, d_rays, stats);
+    return queryDevice(c, { "crt_shade_rays_device", crt::kQueryShade, { d_rgb, d_normal, d_albedo, d_t, d_uv, d_inst, d_prim } }, n, d_rays, stats);
 }
 
 int crt_shade_rays(crt_ctx* c, uint32_t n, const float* rays, float* rgb, float* normal, float* albedo, float* t, float* uv, uint32_t* inst,
                    uint32_t* prim, crt_frame_stats* stats)
 {
-    return queryHost(c, shadeSpec("crt_shade_rays", rgb, normal, albedo, t, uv, inst, prim), n, rays, stats);
+    return queryHost(c, { "crt_shade_rays", crt::kQueryShade, { rgb, normal, albedo, t, uv, inst, prim } }, n, rays, stats);
 }
 
 int crt_path_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, const void* d_ids, uint32_t first_sample, uint32_t n_samples, void* d_rgb,
@@ -2144,13 +2111,13 @@ int runFrameGuides(crt_ctx* c, uint32_t w, uint32_t h, void* d_normal, void* d_a
     q.albedo = static_cast<float*>(d_albedo);
     q.t = static_cast<float*>(d_t);
     QueryLaunch ql;
-    if (const int rc = beginQuery(c, kQueryShade, n, 1u, stats, ql, up256(static_cast<size_t>(n) * 32u))) return rc;
+    if (const int rc = beginQuery(c, crt::kQueryShade, n, stats, ql, up256(static_cast<size_t>(n) * 32u))) return rc;
     int hrc = crt::launchCameraRays(cameraRayParams(c, w, h, CRT_SAMPLE_CENTRE, ql.extra), c->stream);
     if (hrc == 0) {
         q.c = queryCommon(c, ql, ql.extra, n, c->tuneInnerMin);
-        hrc = crt::launchShadeQuery(q, c->counting, ql.grid, c->stream);
+        hrc = crt::launchQuery(crt::kQueryShade, &q, c->counting, ql.grid, c->stream);
     }
-    return endQuery(c, kQueryShade, n, ql, hrc, stats);
+    return endQuery(c, crt::kQueryShade, n, ql, hrc, stats);
 }
 
 int checkFrameGuides(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* normal, const void* albedo, const void* t)
@@ -2553,43 +2520,43 @@ int crt_denoise_variance(crt_ctx* c, uint32_t w, uint32_t h, const float* rgb, c
 int crt_closest_points_device(crt_ctx* c, uint32_t n, const void* d_points, void* d_dist, void* d_point, void* d_uv, void* d_inst,
                               void* d_prim, crt_frame_stats* stats)
 {
-    return queryDevice(c, closestPointSpec("crt_closest_points_device", d_dist, d_point, d_uv, d_inst, d_prim), n, d_points, stats);
+    return queryDevice(c, { "crt_closest_points_device", crt::kQueryClosestPoint, { d_dist, d_point, d_uv, d_inst, d_prim } }, n, d_points, stats);
 }
 
 int crt_closest_points(crt_ctx* c, uint32_t n, const float* points, float* dist, float* point, float* uv, uint32_t* inst, uint32_t* prim,
                        crt_frame_stats* stats)
 {
-    return queryHost(c, closestPointSpec("crt_closest_points", dist, point, uv, inst, prim), n, points, stats);
+    return queryHost(c, { "crt_closest_points", crt::kQueryClosestPoint, { dist, point, uv, inst, prim } }, n, points, stats);
 }
 
 int crt_count_hits_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_count, crt_frame_stats* stats)
 {
-    return queryDevice(c, countSpec("crt_count_hits_device", d_count), n, d_rays, stats);
+    return queryDevice(c, { "crt_count_hits_device", crt::kQueryCount, { d_count } }, n, d_rays, stats);
 }
 
 int crt_count_hits(crt_ctx* c, uint32_t n, const float* rays, uint32_t* count, crt_frame_stats* stats)
 {
-    return queryHost(c, countSpec("crt_count_hits", count), n, rays, stats);
+    return queryHost(c, { "crt_count_hits", crt::kQueryCount, { count } }, n, rays, stats);
 }
 
 int crt_occupancy_device(crt_ctx* c, uint32_t n, const void* d_points, void* d_inside, crt_frame_stats* stats)
 {
-    return queryDevice(c, occupancySpec("crt_occupancy_device", d_inside), n, d_points, stats);
+    return queryDevice(c, { "crt_occupancy_device", crt::kQueryOccupancy, { d_inside } }, n, d_points, stats);
 }
 
 int crt_occupancy(crt_ctx* c, uint32_t n, const float* points, uint8_t* inside, crt_frame_stats* stats)
 {
-    return queryHost(c, occupancySpec("crt_occupancy", inside), n, points, stats);
+    return queryHost(c, { "crt_occupancy", crt::kQueryOccupancy, { inside } }, n, points, stats);
 }
 
 int crt_winding_numbers_device(crt_ctx* c, uint32_t n, const void* d_points, float beta, void* d_w, crt_frame_stats* stats)
 {
-    return queryDevice(c, windingSpec("crt_winding_numbers_device", d_w, beta), n, d_points, stats);
+    return queryDevice(c, { "crt_winding_numbers_device", crt::kQueryWinding, { d_w }, beta }, n, d_points, stats);
 }
 
 int crt_winding_numbers(crt_ctx* c, uint32_t n, const float* points, float beta, float* w, crt_frame_stats* stats)
 {
-    return queryHost(c, windingSpec("crt_winding_numbers", w, beta), n, points, stats);
+    return queryHost(c, { "crt_winding_numbers", crt::kQueryWinding, { w }, beta }, n, points, stats);
 }
 
 int crt_winding_moments_export(const crt_ctx* cc, float* moments)
@@ -2636,7 +2603,7 @@ int crt_list_hits_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_off
         void* const out[4] = { d_t, d_uv, d_inst, d_prim };
         hrc = listFill(c, lr, capacity, tkey, idkey, out);
     }
-    if ((rc = endQuery(c, kQueryCount, n, lr.ql, hrc, stats)) != CRT_OK) return rc;
+    if ((rc = endQuery(c, crt::kQueryCount, n, lr.ql, hrc, stats)) != CRT_OK) return rc;
     if ((rc = listPhases(c, lr, fill)) != CRT_OK) return rc;
     if (total) {
         unsigned long long tot = 0;
@@ -2681,7 +2648,7 @@ int crt_list_hits(crt_ctx* c, uint32_t n, const float* rays, uint64_t* offsets, 
     int hrc = static_cast<int>(he);
     void* const out[4] = { rec, uv ? rec + 3u * cap4 : nullptr, inst ? rec + 2u * cap4 : nullptr, rec ? rec + cap4 : nullptr };
     if (fill && !noMem && hrc == 0) hrc = listFill(c, lr, tot, static_cast<float*>(out[0]), static_cast<uint32_t*>(out[3]), out);
-    if ((rc = endQuery(c, kQueryCount, n, lr.ql, hrc, stats)) != CRT_OK) return rc;
+    if ((rc = endQuery(c, crt::kQueryCount, n, lr.ql, hrc, stats)) != CRT_OK) return rc;
     if ((rc = listPhases(c, lr, fill && !noMem)) != CRT_OK) return rc;
     if (noMem) return fail(c, CRT_ENOMEM, "%s: staging for %llu records not available", what, tot);
     if ((rc = stageDownload(c, planes, 2, dev)) != CRT_OK) return rc;
@@ -3126,7 +3093,7 @@ int runFrameMotion(crt_ctx* c, uint32_t w, uint32_t h, void* d_point, crt_frame_
     crt::RayQueryParams q;
     std::memset(&q, 0, sizeof(q));
     QueryLaunch ql;
-    if (const int rc = beginQuery(c, kQueryClosestHit, n, 1u, stats, ql, up256(nn * 32u) + up256(nn * 8u) + 2u * up256(nn * 4u))) return rc;
+    if (const int rc = beginQuery(c, crt::kQueryClosestHit, n, stats, ql, up256(nn * 32u) + up256(nn * 8u) + 2u * up256(nn * 4u))) return rc;
     unsigned char* rays = ql.extra;
     q.uv = reinterpret_cast<float*>(rays + up256(nn * 32u));
     q.inst = reinterpret_cast<uint32_t*>(rays + up256(nn * 32u) + up256(nn * 8u));
@@ -3134,10 +3101,10 @@ int runFrameMotion(crt_ctx* c, uint32_t w, uint32_t h, void* d_point, crt_frame_
     int hrc = crt::launchCameraRays(cameraRayParams(c, w, h, CRT_SAMPLE_CENTRE, rays), c->stream);
     if (hrc == 0) {
         q.c = queryCommon(c, ql, rays, n, c->tuneInnerMin);
-        hrc = crt::launchRayQuery(q, false, c->counting, ql.grid, c->stream);
+        hrc = crt::launchQuery(crt::kQueryClosestHit, &q, c->counting, ql.grid, c->stream);
     }
     if (hrc == 0) hrc = crt::launchPreviousPoints(previousPointsParams(c, n, q.inst, q.prim, q.uv, d_point), c->stream);
-    return endQuery(c, kQueryClosestHit, n, ql, hrc, stats);
+    return endQuery(c, crt::kQueryClosestHit, n, ql, hrc, stats);
 }
 
 int checkFrameMotion(crt_ctx* c, const char* what, uint32_t w, uint32_t h, const void* point)

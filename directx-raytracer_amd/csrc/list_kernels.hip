@@ -315,9 +315,10 @@ __global__ __launch_bounds__(64) void listSortLongKernel(const ListParams q)
     }
 }
 
-size_t listLds(uint32_t stack_entries) { return static_cast<size_t>(stack_entries) * 64u * sizeof(int); }
-
 } // namespace
+
+// the kind of this file for launchQuery (render_kernels.h)
+QueryKernel kKernelListFill = { reinterpret_cast<const void*>(&listFillKernel<false>), reinterpret_cast<const void*>(&listFillKernel<true>), 1u };
 
 size_t listScanScratchBytes(uint32_t n) { return sizeof(unsigned long long) * listTiles(n); }
 
@@ -330,19 +331,6 @@ int launchListScan(const uint32_t* counts, uint32_t n, unsigned long long* offse
     hipLaunchKernelGGL(listScanSumsKernel, dim3(1), dim3(kSumThreads), 0, stream, tileSums, nTiles);
     if ((e = hipGetLastError()) != hipSuccess) return static_cast<int>(e);
     hipLaunchKernelGGL(listTileScanKernel, dim3(nTiles), dim3(kScanThreads), 0, stream, counts, n, tileSums, offsets);
-    return static_cast<int>(hipGetLastError());
-}
-
-uint32_t listFillResident(uint32_t stack_entries)
-{
-    return queryResidentWorkgroups(reinterpret_cast<const void*>(&listFillKernel<false>), listLds(stack_entries));
-}
-
-int launchListFill(const ListParams& q, bool counting, uint32_t grid, ihipStream_t* stream)
-{
-    if (q.c.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
-    if (counting) hipLaunchKernelGGL((listFillKernel<true>), dim3(grid), dim3(64), listLds(q.c.stack_entries), stream, q);
-    else hipLaunchKernelGGL((listFillKernel<false>), dim3(grid), dim3(64), listLds(q.c.stack_entries), stream, q);
     return static_cast<int>(hipGetLastError());
 }
 

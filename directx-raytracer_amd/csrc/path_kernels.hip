@@ -58,11 +58,6 @@ __device__ __forceinline__ uint32_t waveReserve(uint32_t* counter, uint32_t n)
 // (the per-pixel sample sums -- D3, loadSum / storeSum, addSample, sumMean -- are in shading.hip.h: the path-traced ray queries
 // add their samples with the same functions)
 
-__device__ __forceinline__ uint32_t lanePrefix(unsigned long long m)
-{
-    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
-}
-
 // A wavefront's window on two GLOBAL queues (the stages as separate launches): entries are reserved a chunk at a time -- one atomic
 // per `chunk` entries on the consumed queue's cursor and on the filled queue's length (an atomic on one address takes about 6 ns of
 // the whole device's time: one per refill, 3.4 M per frame, made the pipeline five times slower than the traversal it feeds).  The
@@ -93,7 +88,7 @@ struct GlobalTap {
             if (nb >= n) { dry = true; nb = 0u; }
             else nbEnd = min(nb + chunk, n);
         }
-        const uint32_t pre = lanePrefix(mask);
+        const uint32_t pre = lanesBelow(mask);
         const uint32_t idx = pre < avail ? inNext + pre : nb + (pre - avail);
         valid = (pre < avail) | (idx < nbEnd);
         if (want > avail) { inNext = min(nb + (want - avail), nbEnd); inEnd = nbEnd; }
@@ -106,7 +101,7 @@ struct GlobalTap {
         const uint32_t need = static_cast<uint32_t>(__popcll(mask)), room = outEnd - outNext;
         uint32_t nb = 0u;
         if (need > room) nb = waveReserve(length, chunk);
-        const uint32_t pre = lanePrefix(mask);
+        const uint32_t pre = lanesBelow(mask);
         const uint32_t idx = pre < room ? outNext + pre : nb + (pre - room);
         if (need > room) { outNext = nb + (need - room); outEnd = nb + chunk; }
         else outNext += need;
@@ -152,7 +147,7 @@ __device__ __forceinline__ void streamClosest(const float4* __restrict__ nodes, 
             // retire the finished rays ...
             const bool retire = idle & have, isHit = retire & (h.t < kTMax);
             const unsigned long long mh = __ballot(isHit);
-            uint32_t slot = nShade + lanePrefix(mh);
+            uint32_t slot = nShade + lanesBelow(mh);
             if (GLOBAL) slot = tap.put(q.put, mh);
             if (retire) {
                 const float4 a0 = q.trace[my], a1 = q.trace[q.B + my];
@@ -170,7 +165,7 @@ __device__ __forceinline__ void streamClosest(const float4* __restrict__ nodes, 
             nShade += static_cast<uint32_t>(__popcll(mh));
             // ... and hand the next queue entries to the idle lanes
             bool valid = true;
-            uint32_t idx = next + lanePrefix(idleMask);
+            uint32_t idx = next + lanesBelow(idleMask);
             if (GLOBAL) idx = tap.take(q.take, idleMask, valid);
             else valid = idx < nTrace;
             if (idle) {
@@ -263,7 +258,7 @@ __device__ __forceinline__ void streamShade(const RenderParams& p, const float4*
                 have = false;
             }
             const unsigned long long mOn = __ballot(goesOn);
-            uint32_t slot = nTrace + lanePrefix(mOn);
+            uint32_t slot = nTrace + lanesBelow(mOn);
             if (GLOBAL) slot = tap.put(q.put, mOn);
             if (goesOn) {
                 const uint32_t k = slot;
@@ -275,7 +270,7 @@ __device__ __forceinline__ void streamShade(const RenderParams& p, const float4*
             const bool wantNew = idle & !have;
             const unsigned long long mNew = __ballot(wantNew);
             bool valid = true;
-            uint32_t idx = next + lanePrefix(mNew);
+            uint32_t idx = next + lanesBelow(mNew);
             if (GLOBAL) idx = tap.take(q.take, mNew, valid);
             else valid = idx < nShade;
             if (GLOBAL && wantNew && valid && __float_as_uint(q.shade[q.B + idx].w) == kNullPath) valid = false; // reserved by a producer and never filled
@@ -487,7 +482,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_PATH_WAV
                 }
                 const unsigned long long m = __ballot(isHit);
                 if (isHit) {
-                    const uint32_t i = nShade + lanePrefix(m);
+                    const uint32_t i = nShade + lanesBelow(m);
                     q.shade[i] = make_float4(r.o.x, r.o.y, r.o.z, __uint_as_float(rng));
                     q.shade[q.B + i] = make_float4(r.d.x, r.d.y, r.d.z, __uint_as_float(id)); // bounce 0 in the upper half
                     q.shade[2u * q.B + i] = make_float4(h.t, h.u, h.v, __uint_as_float(h.tri));

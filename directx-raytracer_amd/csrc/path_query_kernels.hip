@@ -281,20 +281,8 @@ __global__ __launch_bounds__(256) void pathResolveKernel(const float4* __restric
 
 } // namespace
 
-uint32_t pathQueryResident(uint32_t stack_entries)
-{
-    return queryResidentWorkgroups(reinterpret_cast<const void*>(&pathQueryKernel<false>), static_cast<size_t>(stack_entries) * 64u * sizeof(int));
-}
-
-int launchPathQuery(const PathQueryParams& q, bool counting, uint32_t grid, ihipStream_t* stream)
-{
-    if (q.c.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
-    const size_t lds = static_cast<size_t>(q.c.stack_entries) * 64u * sizeof(int);
-    const dim3 g(grid), block(64);
-    if (counting) hipLaunchKernelGGL((pathQueryKernel<true>), g, block, lds, stream, q);
-    else hipLaunchKernelGGL((pathQueryKernel<false>), g, block, lds, stream, q);
-    return static_cast<int>(hipGetLastError());
-}
+// the kind of this file for launchQuery (render_kernels.h)
+QueryKernel kKernelPath = { reinterpret_cast<const void*>(&pathQueryKernel<false>), reinterpret_cast<const void*>(&pathQueryKernel<true>), 1u };
 
 int launchPathResolve(const void* rad, uint32_t n_records, uint32_t n_samples, const double* in, double* out, float* rgb, uint32_t total,
                       ihipStream_t* stream)

@@ -316,44 +316,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LayLegacy::k
     runQuery<COUNT, HitCountJob<OCC>>(q);
 }
 
-const void* pointKernel(PointQueryKind kind, bool counting)
-{
-    switch (kind) {
-    case kPointClosest: return counting ? reinterpret_cast<const void*>(&closestPointKernel<true>) : reinterpret_cast<const void*>(&closestPointKernel<false>);
-    case kPointCount: return counting ? reinterpret_cast<const void*>(&hitCountKernel<true, false>) : reinterpret_cast<const void*>(&hitCountKernel<false, false>);
-    default: return counting ? reinterpret_cast<const void*>(&hitCountKernel<true, true>) : reinterpret_cast<const void*>(&hitCountKernel<false, true>);
-    }
-}
-
-size_t pointLds(PointQueryKind kind, uint32_t stack_entries) { return static_cast<size_t>(stack_entries) * pointQueryEntryWords(kind) * 64u * sizeof(int); }
-
 } // namespace
 
-uint32_t pointQueryResident(PointQueryKind kind, uint32_t stack_entries)
-{
-    return queryResidentWorkgroups(pointKernel(kind, false), pointLds(kind, stack_entries));
-}
-
-int launchPointQuery(const PointQueryParams& q, PointQueryKind kind, bool counting, uint32_t grid, ihipStream_t* stream)
-{
-    if (q.c.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
-    const size_t lds = pointLds(kind, q.c.stack_entries);
-    const dim3 g(grid), block(64);
-    switch (kind) {
-    case kPointClosest:
-        if (counting) hipLaunchKernelGGL((closestPointKernel<true>), g, block, lds, stream, q);
-        else hipLaunchKernelGGL((closestPointKernel<false>), g, block, lds, stream, q);
-        break;
-    case kPointCount:
-        if (counting) hipLaunchKernelGGL((hitCountKernel<true, false>), g, block, lds, stream, q);
-        else hipLaunchKernelGGL((hitCountKernel<false, false>), g, block, lds, stream, q);
-        break;
-    default:
-        if (counting) hipLaunchKernelGGL((hitCountKernel<true, true>), g, block, lds, stream, q);
-        else hipLaunchKernelGGL((hitCountKernel<false, true>), g, block, lds, stream, q);
-        break;
-    }
-    return static_cast<int>(hipGetLastError());
-}
+// the kinds of this file for launchQuery (render_kernels.h); the closest-point stack keeps each entry's box bound beside its reference
+QueryKernel kKernelClosestPoint = { reinterpret_cast<const void*>(&closestPointKernel<false>), reinterpret_cast<const void*>(&closestPointKernel<true>), 2u };
+QueryKernel kKernelCount = { reinterpret_cast<const void*>(&hitCountKernel<false, false>), reinterpret_cast<const void*>(&hitCountKernel<true, false>), 1u };
+QueryKernel kKernelOccupancy = { reinterpret_cast<const void*>(&hitCountKernel<false, true>), reinterpret_cast<const void*>(&hitCountKernel<true, true>), 1u };
 
 } // namespace crt
+
+// The query kernels are instantiated here, in the order the code object has listed them since each had a launcher of its own
+// (tools/kernel_diff.sh compares listings line by line)
+template __global__ void crt::closestPointKernel<true>(const crt::PointQueryParams);
+template __global__ void crt::closestPointKernel<false>(const crt::PointQueryParams);
+template __global__ void crt::hitCountKernel<true, false>(const crt::PointQueryParams);
+template __global__ void crt::hitCountKernel<false, false>(const crt::PointQueryParams);
+template __global__ void crt::hitCountKernel<true, true>(const crt::PointQueryParams);
+template __global__ void crt::hitCountKernel<false, true>(const crt::PointQueryParams);

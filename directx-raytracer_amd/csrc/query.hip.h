@@ -1,24 +1,15 @@
-// Device-side skeleton of the persistent query kernels (ray_kernels.hip, point_kernels.hip, list_kernels.hip): every lane
-// holds one caller record, a wavefront refills its idle lanes from a chunked global cursor.  The record window (RayTap), the
-// driver loop every query kernel runs (runQuery), the every-hit traversal of the hit counts and the listing, and the sizing
-// of the persistent grid.  No frame kernel includes this.  (The refill threshold CRT_REFILL_MIN is in traversal.hip.h: the path
-// pipeline's streamClosest refills by the same rule.)
+// Device-side skeleton of the persistent query kernels (ray_kernels.hip, point_kernels.hip, list_kernels.hip, shade_kernels.hip,
+// path_query_kernels.hip, winding_kernels.hip): every lane holds one caller record, a wavefront refills its idle lanes from a
+// chunked global cursor.  The record window (RayTap), the driver loop every query kernel runs (runQuery) and the every-hit
+// traversal of the hit counts and the listing.  Device code only: the sizing of the persistent grid and the launch are
+// query_launch.cpp.  No frame kernel includes this.  (The refill threshold CRT_REFILL_MIN and lanesBelow are in
+// traversal.hip.h: the path pipeline's streamClosest refills by the same rule.)
 #pragma once
 
 #include "traversal.hip.h"
 
 namespace crt {
 namespace {
-
-// Resident wavefronts per SIMD the persistent grids are sized for: at most 7, whatever the kernel's registers allow.  The
-// occlusion form of the ray query fits 8 (60 VGPRs), but with 8 its random leg took 0.56 ms against 0.46 with 7 (incoherent
-// rays: more concurrent traversals, more cache misses).
-constexpr int kQueryMaxWavesPerSimd = 7;
-
-__device__ __forceinline__ uint32_t lanesBelow(unsigned long long m)
-{
-    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
-}
 
 // The box-cull bound of a ray whose current bound (tmax, then the best hit) is b.  Slab distances and the Moeller-Trumbore t
 // round differently, so boxes are culled against b widened by 2^-18 of |b| (traversal.hip.h kCullPad): b * (1 + 2^-18) for
@@ -201,19 +192,6 @@ __device__ __forceinline__ void everyHitIteration(const float4* __restrict__ nod
         }
         cur = stack.sp == 0 ? LayLegacy::kDone : stack.pop();
     }
-}
-
-// Resident workgroups of a persistent query kernel (one wavefront each, four SIMDs per CU): what the occupancy calculator
-// allows per CU for `ldsBytes` of stack, at most kQueryMaxWavesPerSimd per SIMD, x the CUs of the current device.  0: unknown.
-// The caller caches it.
-inline uint32_t queryResidentWorkgroups(const void* kernel, size_t ldsBytes)
-{
-    int dev = 0, cus = 0, perCu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, kernel, 64, ldsBytes) != hipSuccess || perCu <= 0 || cus <= 0)
-        return 0u;
-    const int most = 4 * kQueryMaxWavesPerSimd;
-    return static_cast<uint32_t>(perCu > most ? most : perCu) * static_cast<uint32_t>(cus);
 }
 
 } // namespace

@@ -125,35 +125,9 @@ __global__ void __launch_bounds__(256) rcpCheckKernel(unsigned long long* out)
 
 } // namespace
 
-uint32_t rayQueryResident(bool occlusion, uint32_t stack_entries)
-{
-    const void* k = occlusion ? reinterpret_cast<const void*>(&rayQueryKernel<false, true>) : reinterpret_cast<const void*>(&rayQueryKernel<false, false>);
-    return queryResidentWorkgroups(k, static_cast<size_t>(stack_entries) * 64u * sizeof(int));
-}
-
-void rayQueryLayout(uint32_t n, uint32_t resident, uint32_t& chunk, uint32_t& grid)
-{
-    // about four reservations per wavefront, of 64 to 1024 records: one atomic on one address costs the whole device a few ns
-    uint64_t c = (static_cast<uint64_t>(n) / (4u * static_cast<uint64_t>(resident)) + 63u) & ~static_cast<uint64_t>(63u);
-    chunk = static_cast<uint32_t>(c < 64u ? 64u : (c > 1024u ? 1024u : c));
-    const uint64_t chunks = (static_cast<uint64_t>(n) + chunk - 1u) / chunk;
-    grid = static_cast<uint32_t>(chunks < resident ? chunks : resident);
-}
-
-int launchRayQuery(const RayQueryParams& q, bool occlusion, bool counting, uint32_t grid, ihipStream_t* stream)
-{
-    if (q.c.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
-    const size_t lds = static_cast<size_t>(q.c.stack_entries) * 64u * sizeof(int);
-    const dim3 g(grid), block(64);
-    if (occlusion) {
-        if (counting) hipLaunchKernelGGL((rayQueryKernel<true, true>), g, block, lds, stream, q);
-        else hipLaunchKernelGGL((rayQueryKernel<false, true>), g, block, lds, stream, q);
-    } else {
-        if (counting) hipLaunchKernelGGL((rayQueryKernel<true, false>), g, block, lds, stream, q);
-        else hipLaunchKernelGGL((rayQueryKernel<false, false>), g, block, lds, stream, q);
-    }
-    return static_cast<int>(hipGetLastError());
-}
+// the kinds of this file for launchQuery (render_kernels.h)
+QueryKernel kKernelClosestHit = { reinterpret_cast<const void*>(&rayQueryKernel<false, false>), reinterpret_cast<const void*>(&rayQueryKernel<true, false>), 1u };
+QueryKernel kKernelOcclusion = { reinterpret_cast<const void*>(&rayQueryKernel<false, true>), reinterpret_cast<const void*>(&rayQueryKernel<true, true>), 1u };
 
 int launchRcpCheck(unsigned long long* out, ihipStream_t* stream)
 {
@@ -164,3 +138,10 @@ int launchRcpCheck(unsigned long long* out, ihipStream_t* stream)
 }
 
 } // namespace crt
+
+// The query kernels are instantiated here, in the order the code object has listed them since each had a launcher of its own
+// (tools/kernel_diff.sh compares listings line by line)
+template __global__ void crt::rayQueryKernel<false, true>(const crt::RayQueryParams);
+template __global__ void crt::rayQueryKernel<false, false>(const crt::RayQueryParams);
+template __global__ void crt::rayQueryKernel<true, true>(const crt::RayQueryParams);
+template __global__ void crt::rayQueryKernel<true, false>(const crt::RayQueryParams);

@@ -1,6 +1,9 @@
 // Launch interface between the C-ABI layer (crt_api.cpp, host C++) and the HIP kernels (render_kernels.hip, path_kernels.hip; device code shared through traversal.hip.h / shading.hip.h).
+// The frame kernels and the image-space kernels have one launch function each; the persistent query kernels share one
+// (launchQuery, query_launch.cpp) over a table of their host stubs (QueryKind, QueryKernel): a kernel file states its rows.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 struct ihipStream_t;
@@ -149,10 +152,37 @@ struct QueryCommon {
     uint32_t spill_stride;
     uint32_t stack_entries;       // per-lane stack entries kept in LDS
     uint32_t inner_min;           // tune_inner_min (closest hit, closest point) or tune_inner_min_any (the others)
-    uint32_t chunk;               // records per cursor reservation (rayQueryLayout)
+    uint32_t chunk;               // records per cursor reservation (queryLayout)
 };
+// The kinds of query: one persistent kernel each, in a plain and a counting instantiation.  Every kind's parameter struct
+// (below) begins with its QueryCommon
+enum QueryKind { kQueryClosestHit = 0, kQueryOcclusion = 1, kQueryClosestPoint = 2, kQueryCount = 3, kQueryOccupancy = 4,
+                 kQueryListFill = 5 /* the second traversal of crt_list_hits*: a kernel of its own, not an entry point */,
+                 kQueryShade = 6, kQueryPath = 7 /* crt_path_rays*: passes of (record, sample) items */, kQueryWinding = 8,
+                 kQueryKinds };
+// What the host knows of a kind's kernel: the host stubs of its two instantiations and the ints per stack entry (the
+// closest-point stack keeps each entry's box bound beside its reference: 2; every other kind: 1).  Stated by the file that
+// defines the kernel and never written again.  (Not const: hipcc would emit a const row into the device code object too.)
+struct QueryKernel {
+    const void* plain;
+    const void* counted;
+    uint32_t entryWords;
+};
+extern QueryKernel kKernelClosestHit, kKernelOcclusion;                 // ray_kernels.hip
+extern QueryKernel kKernelClosestPoint, kKernelCount, kKernelOccupancy; // point_kernels.hip
+extern QueryKernel kKernelListFill;                                     // list_kernels.hip
+extern QueryKernel kKernelShade;                                        // shade_kernels.hip
+extern QueryKernel kKernelPath;                                         // path_query_kernels.hip
+extern QueryKernel kKernelWinding;                                      // winding_kernels.hip
+// The rest is query_launch.cpp.  The kind's row
+const QueryKernel& queryKernel(QueryKind kind);
+// workgroups of the kind's kernel the current device holds at once with `stack_entries` of LDS stack per lane (0: unknown)
+uint32_t queryResident(QueryKind kind, uint32_t stack_entries);
 // records per reservation and grid (persistent: at most `resident` workgroups) of a query of n records
-void rayQueryLayout(uint32_t n, uint32_t resident, uint32_t& chunk, uint32_t& grid);
+void queryLayout(uint32_t n, uint32_t resident, uint32_t& chunk, uint32_t& grid);
+// The launch of `grid` workgroups of one wavefront.  params: the kind's parameter struct.  Nothing is launched for no records
+// or no grid.  Returns the HIP error code
+int launchQuery(QueryKind kind, const void* params, bool counting, uint32_t grid, ihipStream_t* stream);
 
 // batched ray queries (ray_kernels.hip; crt_trace_rays* / crt_occluded_rays*): closest hit or occlusion of n ray records, over
 // the 4-wide tree
@@ -164,9 +194,6 @@ struct RayQueryParams {
     uint32_t* prim;
     unsigned char* occluded;      // occlusion: one byte per ray
 };
-// workgroups of the closest-hit / occlusion query kernel the current device holds at once (0: unknown)
-uint32_t rayQueryResident(bool occlusion, uint32_t stack_entries);
-int launchRayQuery(const RayQueryParams& q, bool occlusion, bool counting, uint32_t grid, ihipStream_t* stream);
 // shaded ray queries (shade_kernels.hip; crt_shade_rays*): closest hit of n ray records, then the context's shading mode at
 // the hit -- the frames' shading (shading.hip.h) for caller-supplied rays.  Every output is nullable
 struct ShadeQueryParams {
@@ -192,8 +219,6 @@ struct ShadeQueryParams {
     uint32_t* inst;
     uint32_t* prim;
 };
-uint32_t shadeQueryResident(uint32_t stack_entries);
-int launchShadeQuery(const ShadeQueryParams& q, bool counting, uint32_t grid, ihipStream_t* stream);
 // path-traced ray queries (path_query_kernels.hip; crt_path_rays*): one pass of (record, sample) work items, numbered
 // sample-major: item = sample-in-pass * n_records + record; c.n = the items of the pass.  Every path leaves its radiance in its
 // item's slot of `rad`; launchPathResolve then adds the pass's samples per record in sample order
@@ -221,15 +246,12 @@ struct PathQueryParams {
     uint32_t* inst;
     uint32_t* prim;
 };
-uint32_t pathQueryResident(uint32_t stack_entries);
-int launchPathQuery(const PathQueryParams& q, bool counting, uint32_t grid, ihipStream_t* stream);
 // rad[sample * n_records + record] of n_samples samples added in sample order to `in` (3 float64 per record; NULL: zero);
 // the sums go to `out`, their mean over `total` samples to rgb (each nullable)
 int launchPathResolve(const void* rad, uint32_t n_records, uint32_t n_samples, const double* in, double* out, float* rgb, uint32_t total,
                       ihipStream_t* stream);
 // point queries (point_kernels.hip; crt_closest_points* / crt_count_hits* / crt_occupancy*): n caller-supplied records, point
 // records of 4 floats {x, y, z, rmax} (closest point, occupancy) or ray records (hit counts), over the 4-wide tree
-enum PointQueryKind { kPointClosest = 0, kPointCount = 1, kPointOccupancy = 2 };
 struct PointQueryParams {
     QueryCommon c;
     float* dist;                  // closest point, each nullable: distance, point (3 floats), {u, v} (8-byte aligned), inst, prim
@@ -241,10 +263,6 @@ struct PointQueryParams {
     unsigned char* inside;        // occupancy: one byte per point
     float pad;                    // closest point: absolute pruning margin, 2^-18 x the root box's diagonal
 };
-// ints per stack entry of a point query kernel (the closest-point stack keeps each entry's box bound beside its reference)
-inline uint32_t pointQueryEntryWords(PointQueryKind kind) { return kind == kPointClosest ? 2u : 1u; }
-uint32_t pointQueryResident(PointQueryKind kind, uint32_t stack_entries);
-int launchPointQuery(const PointQueryParams& q, PointQueryKind kind, bool counting, uint32_t grid, ihipStream_t* stream);
 // winding numbers (winding_kernels.hip; crt_winding_numbers*): n point records over the 4-wide tree and its moment table,
 // kMomentStride floats per node: {p~.xyz, r} of child slots 0..3 (one 64-byte line), then {N~.xyz, 0} of slots 0..3
 constexpr uint32_t kMomentStride = 32;
@@ -254,15 +272,13 @@ struct WindingQueryParams {
     float beta;                   // > 0: a child farther than beta x its radius is taken by its dipole; else every triangle
     float* w;                     // one float per point
 };
-uint32_t windingQueryResident(uint32_t stack_entries);
-int launchWindingQuery(const WindingQueryParams& q, bool counting, uint32_t grid, ihipStream_t* stream);
 // the moment table of n_nodes4 quantised nodes, bottom-up over `levels` depth levels (any number >= the wide tree's depth).
 // scratch: windingScratchBytes(n_nodes4), the nodes' depths and their float64 sums
 size_t windingScratchBytes(uint32_t n_nodes4);
 int launchWindingMoments(const void* nodes4q, const void* tris, uint32_t n_nodes4, uint32_t levels, float* moments, void* scratch,
                          ihipStream_t* stream);
-// all-hits listing (list_kernels.hip; crt_list_hits*): after the hit counts of launchPointQuery(kPointCount), the exclusive
-// sum of the counts into 64-bit offsets, a second traversal that writes every accepted hit into its ray's segment, and the
+// all-hits listing (list_kernels.hip; crt_list_hits*): after the hit counts (kQueryCount), the exclusive
+// sum of the counts into 64-bit offsets, a second traversal (kQueryListFill) that writes every accepted hit into its ray's segment, and the
 // sort + resolve of every segment.  The three later steps read offsets[n] on the device and leave when it exceeds capacity.
 struct ListParams {
     QueryCommon c;                // records: the rays
@@ -282,8 +298,6 @@ struct ListParams {
 size_t listScanScratchBytes(uint32_t n);
 // counts[0..n) -> offsets[0..n], offsets[n] = the total
 int launchListScan(const uint32_t* counts, uint32_t n, unsigned long long* offsets, unsigned long long* tileSums, ihipStream_t* stream);
-uint32_t listFillResident(uint32_t stack_entries);
-int launchListFill(const ListParams& q, bool counting, uint32_t grid, ihipStream_t* stream);
 // sorts every segment by (t', global id) and resolves the records into the outputs
 int launchListSort(const ListParams& q, ihipStream_t* stream);
 // camera rays (camera_kernels.hip; crt_camera_rays*, crt_frame_guides*): the frames' rayGen for a w x h frame as n = w * h ray

@@ -207,19 +207,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kShadeWaves,
 
 } // namespace
 
-uint32_t shadeQueryResident(uint32_t stack_entries)
-{
-    return queryResidentWorkgroups(reinterpret_cast<const void*>(&shadeQueryKernel<false>), static_cast<size_t>(stack_entries) * 64u * sizeof(int));
-}
-
-int launchShadeQuery(const ShadeQueryParams& q, bool counting, uint32_t grid, ihipStream_t* stream)
-{
-    if (q.c.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
-    const size_t lds = static_cast<size_t>(q.c.stack_entries) * 64u * sizeof(int);
-    const dim3 g(grid), block(64);
-    if (counting) hipLaunchKernelGGL((shadeQueryKernel<true>), g, block, lds, stream, q);
-    else hipLaunchKernelGGL((shadeQueryKernel<false>), g, block, lds, stream, q);
-    return static_cast<int>(hipGetLastError());
-}
+// the kind of this file for launchQuery (render_kernels.h)
+QueryKernel kKernelShade = { reinterpret_cast<const void*>(&shadeQueryKernel<false>), reinterpret_cast<const void*>(&shadeQueryKernel<true>), 1u };
 
 } // namespace crt

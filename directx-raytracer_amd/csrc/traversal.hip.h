@@ -57,6 +57,12 @@ constexpr uint32_t kBoostAfter = 300; // traversal-loop iterations after which a
 #endif
 constexpr uint32_t kGroupMax = 16; // grid padding unit: tiles per XCD group never exceed this
 
+// the lanes of mask m below the calling lane: its place among them when work is handed out to the lanes of m
+__device__ __forceinline__ uint32_t lanesBelow(unsigned long long m)
+{
+    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
+}
+
 struct F3 { float x, y, z; };
 
 __device__ __forceinline__ F3 f3(float x, float y, float z) { return F3{ x, y, z }; }

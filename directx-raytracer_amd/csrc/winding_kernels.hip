@@ -260,26 +260,10 @@ __global__ __launch_bounds__(256) void windingMomentsKernel(const crt_bvh_node4q
 
 size_t depthBytes(uint32_t n) { return (sizeof(uint32_t) * static_cast<size_t>(n) + 255u) & ~static_cast<size_t>(255u); }
 
-const void* windingKernelPtr(bool counting)
-{
-    return counting ? reinterpret_cast<const void*>(&windingKernel<true>) : reinterpret_cast<const void*>(&windingKernel<false>);
-}
-
 } // namespace
 
-uint32_t windingQueryResident(uint32_t stack_entries)
-{
-    return queryResidentWorkgroups(windingKernelPtr(false), static_cast<size_t>(stack_entries) * 64u * sizeof(int));
-}
-
-int launchWindingQuery(const WindingQueryParams& q, bool counting, uint32_t grid, ihipStream_t* stream)
-{
-    if (q.c.n == 0u || grid == 0u) return static_cast<int>(hipSuccess);
-    const size_t lds = static_cast<size_t>(q.c.stack_entries) * 64u * sizeof(int);
-    if (counting) hipLaunchKernelGGL((windingKernel<true>), dim3(grid), dim3(64), lds, stream, q);
-    else hipLaunchKernelGGL((windingKernel<false>), dim3(grid), dim3(64), lds, stream, q);
-    return static_cast<int>(hipGetLastError());
-}
+// the kind of this file for launchQuery (render_kernels.h)
+QueryKernel kKernelWinding = { reinterpret_cast<const void*>(&windingKernel<false>), reinterpret_cast<const void*>(&windingKernel<true>), 1u };
 
 size_t windingScratchBytes(uint32_t n_nodes4) { return depthBytes(n_nodes4) + sizeof(MomentSum) * static_cast<size_t>(n_nodes4 ? n_nodes4 : 1u); }
 
@@ -298,3 +282,8 @@ int launchWindingMoments(const void* nodes4q, const void* tris, uint32_t n, uint
 }
 
 } // namespace crt
+
+// The query kernels are instantiated here, in the order the code object has listed them since each had a launcher of its own
+// (tools/kernel_diff.sh compares listings line by line)
+template __global__ void crt::windingKernel<true>(const crt::WindingQueryParams);
+template __global__ void crt::windingKernel<false>(const crt::WindingQueryParams);
