@@ -758,7 +758,8 @@ int crt_occupancy(crt_ctx* ctx, uint32_t n, const float* points, uint8_t* inside
  *   +-PI_2.  Absolute error against atan2 in float64: at most 2.95e-7 measured over the grid of tests/test_winding.py (the test
  *   asserts that figure plus one float32 ulp of pi, under the 2^-20 the error budget below needs).
  *   Triangles that contribute exactly zero: inert ones (a non-finite vertex makes det or den a NaN or an infinity) and those
- *   with the point at a vertex.  The scaled products cannot overflow: every component is below 2 in magnitude.  What is left
+ *   with the point at a vertex (held on every poisoned upload, refit, rebuild and heal by tests/test_nonfinite_vertices.py
+ *   through tests/winding_checks.py: exact mode equals brute force over the records with the inert ones deleted).  The scaled products cannot overflow: every component is below 2 in magnitude.  What is left
  *   of the float range is the subtraction v0 - q and the sums a + e1, a + e2 themselves, which overflow only within a factor 2
  *   of FLT_MAX (E = 0 then, and the triangle contributes zero), and components 2^-126 and more below the largest, which the
  *   scaling rounds.  A record with a NaN coordinate gives w = 0.
@@ -774,14 +775,18 @@ int crt_occupancy(crt_ctx* ctx, uint32_t n, const float* points, uint8_t* inside
  *   triangles in leaf order; a node's total starts at 0 and takes its four slots in order 0..3; an inner child's sums are its
  *   node's total.  Inert triangles are left out; CRT_BVH_EMPTY slots hold zeros.  r (float) over the child's decoded
  *   quantised box [lo, hi]: r = sqrtf((mx + my) + mz), m_a = max((p~_a - lo_a)^2, (hi_a - p~_a)^2): no triangle of the child
- *   is farther from p~.
+ *   is farther from p~.  (tests/winding_checks.py moments_f64 restates this paragraph in float64, per child slot straight over
+ *   the triangles below it, and holds every exported table to it: N~ and p~ to one float32 rounding plus the summation error,
+ *   r against the vertices; tests/test_winding_checks.py shows that it rejects a table that counts an inert triangle.)
  * - Walk: from the root, per non-empty child slot with d0 = p~ - q: E = expo(the largest |component| of d0), d = ldexpf(d0, -E)
  *   per component, d2 = dot(d, d) (in [0.25, 3) for a finite non-zero d0), br = beta * ldexpf(r, -E): when beta > 0 and
  *   d2 > br * br the child contributes h = ldexpf((0.5f * dot(N~, d)) / (d2 * sqrtf(d2)), -2 * E) and is not entered; else it is
  *   entered; a leaf adds every triangle's term.  The comparison is d0 . d0 > (beta r)^2 with both sides divided by 2^2E: it
  *   cannot overflow on the left, and where neither side left the normal range before it decides as before.  The dipole is
  *   0.5 N~ . d0 / |d0|^3 with the length taken out; h itself has no dimension.  beta <= 0 or NaN: exact -- no cluster is approximated and w is the sum over all triangles, the same bits over every
- *   tree (host SAH, LBVH, PLOC, refitted, rebuilt).  beta = +inf is exact through the same comparison.  With a finite beta > 0
+ *   tree (host SAH, LBVH, PLOC, refitted, rebuilt; tests/test_winding.py test_exact_mode_is_the_same_over_every_tree and
+ *   test_far_from_origin, tests/test_deep_stacks.py on trees whose exact-mode walk holds up to 57 stack entries and through
+ *   every move of depth4, tests/test_nonfinite_vertices.py on poisoned scenes).  beta = +inf is exact through the same comparison.  With a finite beta > 0
  *   the result depends on the tree (other clusters exist), not on any order.  beta = 2 keeps the error near 1e-2 at worst
  *   close to a cluster and far below it elsewhere (DESIGN.md section 5q has the measured figures).
  * - Unit of length: w does not depend on it.  Vertices and points times 2^k give the same bits of w in exact mode wherever the

@@ -8,7 +8,12 @@ wrong slice index makes lanes overwrite each other's pending nodes and the compa
 The CPU tests prove that the GPU tests cannot pass vacuously: the depths come from the oracle's own walk (oracle_set_stack_output,
 oracle_debug_max_sp) or from plain float64 models of the walks the oracle does not have, never from the product kernels.  The GPU
 tests then hold frames, queries, split packets, batches, tile shares and contexts whose depth4 moves to the existing references, at
-LDS parts of 0 (= 16), 1, 5 and 32 entries, counting off and on."""
+LDS parts of 0 (= 16), 1, 5 and 32 entries, counting off and on.
+
+Winding numbers in exact mode enter or push every non-empty child, whatever the geometry: over chain A a lane holds 36 (SAH),
+50 (LBVH) and 28 (PLOC) entries, over the plate and chain B 27, 57 and 30 (tests/test_winding_checks.py measures them from the
+trees alone).  tests/winding_checks.py's assert_winding holds them to brute force, to the reference's walk and to the moment
+table in float64 here, and after every move of depth4, where the level launches of the moment table take their count from it."""
 import ctypes as C
 import os
 import sys
@@ -23,8 +28,10 @@ import shaded_query_checks as sq  # noqa: E402
 import test_list_hits as tl  # noqa: E402
 import test_point_queries as tp  # noqa: E402
 import test_ray_queries as tr  # noqa: E402
+import winding_checks as wc  # noqa: E402
 from test_list_hits import ref as list_ref  # noqa: E402,F401  (fixture: tests/list_hits_reference.c)
 from test_point_queries import ref as point_ref  # noqa: E402,F401  (fixture: tests/point_reference.c)
+from winding_checks import wref  # noqa: E402,F401  (fixture: tests/winding_reference.c)
 
 MISS = 0xFFFFFFFF
 TREES = tp.TREES  # sah / lbvh / ploc -> the upload options
@@ -540,10 +547,34 @@ def _some_points(pkg, sc, n, seed):
                                                 pkg.make_points(xyz, rmax=rng.choice([np.inf, 50.0], size=n))]))
 
 
+def winding_points(pkg, sc, seed):
+    """192 points: 64 at chain A's apex, 120 of _some_points, 8 a hundred sizes away, the last of them with a NaN"""
+    lo, hi = sq.bounds(sc)
+    far = np.random.default_rng(seed).normal(size=(8, 3))
+    far = pkg.make_points(np.float32(0.5 * (lo + hi) + far / np.linalg.norm(far, axis=1, keepdims=True) * 100.0 * np.linalg.norm(hi - lo)))
+    far[-1, 2] = np.nan
+    pts = np.ascontiguousarray(np.concatenate([apex_points(pkg, 64, seed), _some_points(pkg, sc, 40, seed + 1), far]))
+    assert len(pts) == 192
+    return pts
+
+
+_winding_seen = {}  # (scene, builder) -> what assert_winding returned at the first LDS part that ran
+
+
+def _check_winding(pkg, wref, renderer, name, sc, builder, tag):
+    """winding numbers over the deep tree: every check of winding_checks.assert_winding; the bits and the fetch counters are the
+    same at every LDS part"""
+    out = wc.assert_winding(pkg, wref, renderer, sc, tp._tri_records(pkg, sc["meshes"]), winding_points(pkg, sc, seed=9), "%s, %s" % (name, tag))
+    first = _winding_seen.setdefault((name, builder), out)
+    for beta, bits in out["w"].items():
+        np.testing.assert_array_equal(bits, first["w"][beta], err_msg="%s, %s: beta %r depends on stack_entries" % (name, tag, beta))
+    assert out["counters"] == first["counters"], "%s, %s: the fetch counters depend on stack_entries" % (name, tag)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("entries", STACK_ENTRIES)
 @pytest.mark.parametrize("builder", BUILDERS)
-def test_queries_match_their_references(pkg, oracle, refs, list_ref, point_ref, renderer, builder, entries):
+def test_queries_match_their_references(pkg, oracle, refs, list_ref, point_ref, wref, renderer, builder, entries):
     """every query kernel on the camera rays and the apex rays: chain A for the closest-hit and closest-point walks, the plate
     and chain B for the any-hit and no-cull walks and, its shadow and bounce rays being deep, for the shaded, path-traced and
     guide queries"""
@@ -559,6 +590,7 @@ def test_queries_match_their_references(pkg, oracle, refs, list_ref, point_ref, 
         pick = np.arange(0, len(e["rays"]), 16)  # the plain-Python brute force of tests/test_ray_queries.py on every 16th ray
         tr._check_brute(oracle, tr._scene_triangles(sc), e["rays"][pick], {k: got[k][pick] for k in sq.HIT_OUTPUTS})
         _check_closest_points(pkg, point_ref, renderer, sc, _some_points(pkg, sc, 192, seed=5), "chain A, " + tag)
+        _check_winding(pkg, wref, renderer, "chain A", sc, builder, tag)
         # the plate and chain B
         e = refs["shadow"]
         t, sc = e["trees"][builder], e["scene"]
@@ -581,6 +613,7 @@ def test_queries_match_their_references(pkg, oracle, refs, list_ref, point_ref, 
         for counting, occ in enumerate(_counting_forms(renderer, lambda: renderer.occupancy(pts))):
             np.testing.assert_array_equal(occ, inside, err_msg="%s: occupancy counting=%d" % (tag, counting))
         _check_closest_points(pkg, point_ref, renderer, sc, pts, "plate and chain B, " + tag)
+        _check_winding(pkg, wref, renderer, "plate and chain B", sc, builder, tag)
         # shade_rays (modes 3 and 100; host, counting and device forms), path_rays and frame_guides against the frames
         w, h = SIZES["shadow"]
         sq.frame_records_equal_frames(renderer, t["frames"], w, h, PATH, "plate and chain B, " + tag, scene=sc)
@@ -674,11 +707,12 @@ def test_split_packets_batches_and_tile_shares_render_the_same_frame(pkg, oracle
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("entries", STACK_ENTRIES)
-def test_slices_follow_a_depth4_that_moves(pkg, oracle, point_ref, renderer, entries):
+def test_slices_follow_a_depth4_that_moves(pkg, oracle, point_ref, wref, renderer, entries):
     """One context through the states of test_depth4_moves_on_every_route: uploads, a vertex update with a refit, rebuilds with
     both builders, refits back and forth.  After every step crt_bvh_info4 reports the predicted tree's depth4, and more frames than
     the context has ring slots, the ray queries and the closest-point query (arenas of their own) equal the oracle over the
-    exported tree."""
+    exported tree.  So do the winding numbers and their moment table (winding_checks.assert_winding): the table a winding query
+    built just before the move is stale after it, and is built again with the new tree's level count and node count."""
     w, h = ROUTE_SIZE
     states = route_states(pkg, oracle)
     r = renderer
@@ -694,8 +728,11 @@ def test_slices_follow_a_depth4_that_moves(pkg, oracle, point_ref, renderer, ent
             r.rebuild()
     try:
         r.set_option("stack_entries", entries)
+        held = None  # the points and the beta = 2 bits of the state the context holds
         for name, sc, O, route in states:
             what = "%s, stack_entries=%d" % (name, entries)
+            if held is not None:  # the moment table is this state's when the move comes
+                np.testing.assert_array_equal(_bits(r.winding_numbers(held[0], 2.0)), held[1], err_msg=what + ": before the move")
             move(route, sc)
             # the oracle over the tree the context now holds; it has the predicted state's depth4 and deepest lane
             nodes, tris, shade = r.bvh_export()
@@ -715,6 +752,8 @@ def test_slices_follow_a_depth4_that_moves(pkg, oracle, point_ref, renderer, ent
                         r.render_frame(w, h, want=("rgba8",))
                 _check_ray_queries(oracle, r, S, query_rays(pkg, oracle, sc, w, h), what, frame=ref)
                 _check_closest_points(pkg, point_ref, r, sc, apex_points(pkg, 128, seed=7), what)
+                wpts = winding_points(pkg, sc, seed=11)
+                held = (wpts, wc.assert_winding(pkg, wref, r, sc, tp._tri_records(pkg, sc["meshes"]), wpts, what)["w"][2.0])
             finally:
                 S.close()
     finally:

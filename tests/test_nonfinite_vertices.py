@@ -2,7 +2,10 @@
 never reported, and every result equals the result for the scene without it -- over every tree.  The rule that makes it so sits
 where a triangle's box and centroid are taken (such a triangle is the point (0, 0, 0) to every builder and to the refit, and its
 record is nine quiet NaNs); these tests pin it by comparing every tree walk with brute force over the same records, bit for bit, on scenes poisoned with NaN,
-+inf, -inf and a mix of them at the places listed in _CASES."""
++inf, -inf and a mix of them at the places listed in _CASES.  Winding numbers, whose walk enters every cluster and whose moment table sums over every
+triangle below a node, are held by tests/winding_checks.py's assert_winding: exact mode to brute force over the records with the
+inert ones deleted, the moment table to a float64 statement that drops them (tests/test_winding_checks.py shows on the CPU that
+the points of every case would see an inert triangle that was counted)."""
 import os
 import sys
 
@@ -14,9 +17,11 @@ import ploc_reference as spec  # noqa: E402
 import shaded_query_checks as sq  # noqa: E402
 import test_list_hits as lh  # noqa: E402
 import test_point_queries as pq  # noqa: E402
+import winding_checks as wc  # noqa: E402
 from test_dynamic_geometry import _numpy_refit  # noqa: E402
 from test_list_hits import ref as list_ref  # noqa: E402,F401  (fixture: tests/list_hits_reference.c)
 from test_point_queries import ref as point_ref  # noqa: E402,F401  (fixture: tests/point_reference.c)
+from winding_checks import wref  # noqa: E402,F401  (fixture: tests/winding_reference.c)
 
 MISS = 0xFFFFFFFF
 KINDS = {"nan": (np.nan,), "+inf": (np.inf,), "-inf": (-np.inf,), "mix": (np.nan, np.inf, -np.inf)}
@@ -574,7 +579,8 @@ def _export(r):
 
 def _references(pkg, oracle, sc, point_ref, list_ref):
     """brute force over the scene, computed once and shared: frames in every mode, closest hits, occlusion, hit counts, lists,
-    closest points and occupancy"""
+    closest points and occupancy; the winding points and the records by gid (winding_checks.assert_winding computes its own
+    expectations from them and from the exported tree)"""
     if "refs" not in sc:
         P = _oracle_scene(oracle, sc)
         recs, rays, cam = P.tris(), sc["rays"], sc["camera"]
@@ -586,7 +592,8 @@ def _references(pkg, oracle, sc, point_ref, list_ref):
             "frames": {m: P.render(cam["position"], cam["matrix"], m, W, H, brute_force=True) for m in ALL_MODES},
             "trace": oracle.trace_rays(P, rays, brute_force=True), "occluded": oracle.occluded_rays(P, rays, brute_force=True)["occluded"],
             "count": pq.ref_count(point_ref, recs, rays), "lists": lh.ref_list(list_ref, recs, rays), "points": pts,
-            "closest": pq.ref_closest(point_ref, recs, pts), "occupancy": pq.ref_occupancy(point_ref, recs, pts)}
+            "closest": pq.ref_closest(point_ref, recs, pts), "occupancy": pq.ref_occupancy(point_ref, recs, pts),
+            "winding_points": wc.points_for(sc, seed=7), "records": _records(pkg, sc["meshes"])}
         for k in ("trace", "lists", "closest"):
             _assert_none_inert(sc, sc["refs"][k]["inst"], sc["refs"][k]["prim"], k)
     return sc["refs"]
@@ -648,12 +655,13 @@ def _assert_frame(got, ref, what, rgb=True):
         assert np.array_equal(got["rgb"], ref["rgb"], equal_nan=True), what + " rgb"
 
 
-def _check_gpu(pkg, oracle, r, sc, refs, what, same_tree=None):
+def _check_gpu(pkg, oracle, wref, r, sc, refs, what, same_tree=None):
     """the scene r holds is sc: its wide and quantised trees are the oracle's collapse of its binary tree, its frames in every
     mode (both path pipelines) equal the oracle's over that tree with the fetch counters, and the brute-force frames; the host
     and device forms of the six queries equal their brute-force references; camera_rays through shade_rays and path_rays give
     the brute-force frames, frame_guides the frames' surfaces, and shade_rays / path_rays on the generic rays and on the poses
-    their brute-force references (tests/shaded_query_checks.py).  same_tree: an oracle scene known to hold the same tree (it
+    their brute-force references (tests/shaded_query_checks.py); the winding numbers and the moment table pass
+    winding_checks.assert_winding.  same_tree: an oracle scene known to hold the same tree (it
     keeps uvs, which OracleScene.set_bvh drops)."""
     nodes, tris, shade = r.bvh_export()
     S = same_tree
@@ -693,6 +701,7 @@ def _check_gpu(pkg, oracle, r, sc, refs, what, same_tree=None):
                                   cache=refs["shaded_cache"])
     sq.arbitrary_records_equal_trace(r, rays, refs["trace"], what, meshes=sc["meshes"])
     sq.pose_records_equal_oracle(r, refs["poses"], what, meshes=sc["meshes"])
+    wc.assert_winding(pkg, wref, r, sc, refs["records"], refs["winding_points"], what)
     return nodes, tris, shade
 
 
@@ -707,7 +716,7 @@ def _expected_tree(pkg, oracle, sc, tree):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,kind", _GPU_PARAMS, ids=_GPU_IDS)
-def test_uploads_of_poisoned_scenes(pkg, oracle, point_ref, list_ref, renderer, defaults, case, name, kind):
+def test_uploads_of_poisoned_scenes(pkg, oracle, point_ref, list_ref, wref, renderer, defaults, case, name, kind):
     r, sc = renderer, case(name, kind)
     refs = _references(pkg, oracle, sc, point_ref, list_ref)
     for tree in TREES:
@@ -717,7 +726,7 @@ def test_uploads_of_poisoned_scenes(pkg, oracle, point_ref, list_ref, renderer, 
         want = _expected_tree(pkg, oracle, sc, tree)
         assert nodes.tobytes() == want[0].tobytes(), what + ": binary nodes"
         assert tris.tobytes() == want[1].tobytes() and shade.tobytes() == want[2].tobytes(), what + ": records"
-        _check_gpu(pkg, oracle, r, sc, refs, what, same_tree=want[3])
+        _check_gpu(pkg, oracle, wref, r, sc, refs, what, same_tree=want[3])
 
 
 def _assert_vertices(r, meshes, what):
@@ -737,34 +746,40 @@ def _assert_refitted(pkg, r, shape, sc, what):
     assert tris[np.argsort(tris["gid"], kind="stable")].tobytes() == _records(pkg, sc["meshes"]).tobytes(), what + ": records"
 
 
-def _dynamic_round_trip(pkg, oracle, point_ref, list_ref, r, builder, clean, sc, poison, heal, what):
+def _dynamic_round_trip(pkg, oracle, wref, point_ref, list_ref, r, builder, clean, sc, poison, heal, what):
     """upload clean; poison() + refit; heal() + refit; poison() + rebuild; heal() + rebuild.  After every step the checks of
-    _check_gpu hold and crt_mesh_vertices returns the traced values bit for bit; the healed scene equals the upload."""
+    _check_gpu hold and crt_mesh_vertices returns the traced values bit for bit; the healed scene equals the upload, its
+    exact-mode winding numbers included."""
     tree = "lbvh" if builder == LBVH else "ploc"
     refs, clean_refs = _references(pkg, oracle, sc, point_ref, list_ref), _references(pkg, oracle, clean, point_ref, list_ref)
     _upload(r, clean, tree, dynamic=True)
     fresh = _export(r)
     shape = r.bvh_export()[0]
+    wpts = clean_refs["winding_points"]
+    w_fresh = _bits(r.winding_numbers(wpts, 0.0))
     poison()
     r.refit()
     _assert_vertices(r, sc["meshes"], what + " refit")
     _assert_refitted(pkg, r, shape, sc, what + " refit")
-    _check_gpu(pkg, oracle, r, sc, refs, what + " refit")
+    _check_gpu(pkg, oracle, wref, r, sc, refs, what + " refit")
     heal()
     r.refit()
     _assert_vertices(r, clean["meshes"], what + " healed by a refit")
     assert _export(r) == fresh, what + ": healed by a refit"
+    wc.assert_winding(pkg, wref, r, clean, clean_refs["records"], wpts, what + " healed by a refit")
+    np.testing.assert_array_equal(_bits(r.winding_numbers(wpts, 0.0)), w_fresh, err_msg=what + ": exact-mode winding numbers healed by a refit")
     poison()
     r.rebuild()  # (PLOC included: the rebuild returns CRT_OK -- the binding raises otherwise -- and the scene is kept)
     _assert_vertices(r, sc["meshes"], what + " rebuild")
     nodes, tris, shade = r.bvh_export()
     want = _expected_tree(pkg, oracle, sc, tree)
     assert nodes.tobytes() == want[0].tobytes() and tris.tobytes() == want[1].tobytes() and shade.tobytes() == want[2].tobytes(), what + " rebuild"
-    _check_gpu(pkg, oracle, r, sc, refs, what + " rebuild")
+    _check_gpu(pkg, oracle, wref, r, sc, refs, what + " rebuild")
     heal()
     r.rebuild()
     assert _export(r) == fresh, what + ": healed by a rebuild"
-    _check_gpu(pkg, oracle, r, clean, clean_refs, what + " healed")
+    _check_gpu(pkg, oracle, wref, r, clean, clean_refs, what + " healed")
+    np.testing.assert_array_equal(_bits(r.winding_numbers(wpts, 0.0)), w_fresh, err_msg=what + ": exact-mode winding numbers healed by a rebuild")
 
 
 def _clean_scene(sc):
@@ -782,7 +797,7 @@ _DYNAMIC = [("probe100", "nan"), ("heightfield_leaf", "mix"), ("icosphere_pole",
 @pytest.mark.gpu
 @pytest.mark.parametrize("builder", [LBVH, PLOC], ids=["lbvh", "ploc"])
 @pytest.mark.parametrize("name,kind", _DYNAMIC, ids=["%s-%s" % p for p in _DYNAMIC])
-def test_vertex_updates_poison_and_heal_a_dynamic_scene(pkg, oracle, point_ref, list_ref, renderer, defaults, case, name, kind, builder):
+def test_vertex_updates_poison_and_heal_a_dynamic_scene(pkg, oracle, point_ref, list_ref, wref, renderer, defaults, case, name, kind, builder):
     import torch
     r, sc = renderer, case(name, kind)
     clean = _cache.setdefault((name, "clean"), _clean_scene(sc))
@@ -793,13 +808,13 @@ def test_vertex_updates_poison_and_heal_a_dynamic_scene(pkg, oracle, point_ref, 
             v = np.ascontiguousarray(meshes[i]["vertices"], dtype=np.float32)
             r.update_vertices(i, v if (k + builder) % 2 == 0 else torch.from_numpy(v).cuda())
 
-    _dynamic_round_trip(pkg, oracle, point_ref, list_ref, r, builder, clean, sc, lambda: send(sc["meshes"]), lambda: send(clean["meshes"]),
+    _dynamic_round_trip(pkg, oracle, wref, point_ref, list_ref, r, builder, clean, sc, lambda: send(sc["meshes"]), lambda: send(clean["meshes"]),
                         "%s %s builder %d" % (name, kind, builder))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("builder", [LBVH, PLOC], ids=["lbvh", "ploc"])
-def test_a_transform_that_overflows_makes_the_mesh_inert(pkg, scenes, oracle, point_ref, list_ref, renderer, defaults, builder):
+def test_a_transform_that_overflows_makes_the_mesh_inert(pkg, scenes, oracle, point_ref, list_ref, wref, renderer, defaults, builder):
     """finite rest vertices, a finite non-singular transform, products beyond FLT_MAX: every world x of the mesh is +inf"""
     from test_dynamic_geometry import _apply
     probe = _probe_mesh(60, 21)
@@ -816,7 +831,7 @@ def test_a_transform_that_overflows_makes_the_mesh_inert(pkg, scenes, oracle, po
         assert sc["inert"][1].all() and np.isposinf(moved[1]["vertices"][:, 0]).all() and np.isfinite(moved[1]["vertices"][:, 1:]).all()
         _cache[key], _cache[("overflow", "moved")] = clean, (sc, M)
     clean, (sc, M) = _cache[key], _cache[("overflow", "moved")]
-    _dynamic_round_trip(pkg, oracle, point_ref, list_ref, renderer, builder, clean, sc, lambda: renderer.set_mesh_transform(1, M),
+    _dynamic_round_trip(pkg, oracle, wref, point_ref, list_ref, renderer, builder, clean, sc, lambda: renderer.set_mesh_transform(1, M),
                         lambda: renderer.set_mesh_transform(1, None), "overflowing transform, builder %d" % builder)
 
 

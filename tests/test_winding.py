@@ -10,7 +10,11 @@ Measured on the CPU (host SAH tree; 257 points per scene no nearer to a triangle
     reversed              1.23e-7   1.40e-1   2.43e-2   3.44e-3   9.5e-5
     two nested            2.23e-7   1.92e-1   4.17e-2   6.77e-3   1.36e-4
     one octant removed    9.4e-8    1.38e-1   2.00e-2   3.27e-3   8.7e-5
-"""
+
+
+test_far_from_origin and test_tiny_scenes go through tests/winding_checks.py's assert_winding, the hub that also holds winding
+numbers on poisoned scenes (tests/test_nonfinite_vertices.py) and on deep trees and a moving depth4 (tests/test_deep_stacks.py);
+tests/test_winding_checks.py has the figures measured on those inputs."""
 import ctypes as C
 import math
 import os
@@ -156,6 +160,20 @@ def shell_points(rng, n, holes):
 
 
 BANDS = {"sphere": [(0.95, 1.03)], "reversed": [(0.95, 1.03)], "open": [(0.95, 1.03)], "nested": [(0.95, 1.03), (0.47, 0.52)]}
+FAR_OFFSETS = (0.0, 1024.0, 8192.0, 131072.0)
+FAR_SCENES = ("sphere", "open")
+
+
+def far_case(scenes, kind, off):
+    """a sphere scene and 257 shell points, both moved by (off, -off, 0.5 off) in float32 (a translation rounds the vertices,
+    p~ and p~ - q otherwise than a power-of-two scale does), and every point's float64 distance from the moved centre"""
+    shift = np.float32([off, -off, 0.5 * off])
+    sc = sphere_scene(scenes, kind)
+    for m in sc["meshes"]:
+        m["vertices"] = (m["vertices"] + shift).astype(np.float32)
+    pts = _records((shell_points(np.random.default_rng(200 + int(off)), 257, BANDS[kind]) + shift).astype(np.float32))
+    radius = np.linalg.norm(pts[:, 0:3].astype(np.float64) - (np.float32(CENTRE).astype(np.float64) + shift.astype(np.float64)), axis=1)
+    return sc, pts, radius
 
 
 def _min_distance(tris, p, nearest=12):
@@ -448,6 +466,45 @@ def test_exact_mode_is_the_same_over_every_tree(pkg, wref, scenes, dragon, rende
                 renderer.set_option("gpu_builder", builder)
                 renderer.rebuild()
                 np.testing.assert_array_equal(_bits(renderer.winding_numbers(pts, 0.0)), _bits(want), err_msg="%s %s rebuild %d" % (name, tree, builder))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("off", FAR_OFFSETS)
+def test_far_from_origin(pkg, wref, scenes, renderer, trees, off):
+    """the closed and the open sphere at (off, -off, 0.5 off) over all three trees: every check of winding_checks.assert_winding,
+    and at beta 2 the inside test of the closed sphere on every point outside the band [0.9, 1.1] around its surface"""
+    import winding_checks as wc
+    for kind in FAR_SCENES:
+        sc, pts, radius = far_case(scenes, kind, off)
+        records = tp._tri_records(pkg, sc["meshes"])
+        judged = (radius < 0.9) | (radius > 1.1)
+        # the band [0.9, 1.1] of the radii drawn from [0, 2.5] less (0.95, 1.03) is 4.8 % of them
+        assert 1.0 - judged.mean() <= 0.2, "%s at %g: %.1f %% of the points left out" % (kind, off, 100.0 * (1.0 - judged.mean()))
+        assert (radius[judged] < 0.9).sum() >= 20 and (radius[judged] > 1.1).sum() >= 20
+        exact = None
+        for tree in TREES:
+            _upload(renderer, sc, tree)
+            out = wc.assert_winding(pkg, wref, renderer, sc, records, pts, "%s at %g, %s" % (kind, off, tree))
+            exact = out["w"][0.0] if exact is None else exact
+            np.testing.assert_array_equal(out["w"][0.0], exact, err_msg="%s at %g: exact mode over %s" % (kind, off, tree))
+            if kind == "sphere":
+                inside = out["w"][2.0].view(np.float32) > 0.5
+                bad = np.flatnonzero((inside != (radius < 0.9)) & judged)
+                assert len(bad) == 0, "%s at %g, %s: %d points on the wrong side at beta 2, first %d at radius %r" % (kind, off, tree, len(bad), bad[0], radius[bad[0]])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5])
+def test_tiny_scenes(pkg, wref, renderer, trees, n):
+    """1 to 5 triangles over all three trees: the one-leaf root and a two-node tree"""
+    import test_nonfinite_vertices as nf
+    import winding_checks as wc
+    sc = nf._tiny(n)
+    pts = wc.points_for(sc, seed=n)
+    records = tp._tri_records(pkg, sc["meshes"])
+    for tree in TREES:
+        _upload(renderer, sc, tree)
+        wc.assert_winding(pkg, wref, renderer, sc, records, pts, "tiny%d %s" % (n, tree))
 
 
 @pytest.mark.gpu
