@@ -12,7 +12,7 @@ namespace {
 
 __global__ __launch_bounds__(256) void cameraRayKernel(const CameraRayParams p)
 {
-    const uint32_t n = p.width * p.height; // <= 2^28 (crt_api.cpp)
+    const uint32_t n = p.width * p.height; // <= 2^28 (crt_api.cpp checkFrameSize)
     const uint32_t pixId = blockIdx.x * 256u + threadIdx.x;
     if (pixId >= n) return;
     const uint32_t px = pixId % p.width, py = pixId / p.width;

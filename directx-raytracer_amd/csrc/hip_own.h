@@ -1,5 +1,5 @@
 // Ownership of HIP resources for the host side of the geometry code (bvh_gpu.hip, bvh_ploc.hip, refit_kernels.hip and what
-// crt_api.cpp takes over from them): one way to turn a hipError_t into an exception, one buffer in HBM that frees itself, one
+// the C-ABI layer takes over from them): one way to turn a hipError_t into an exception, one buffer in HBM that frees itself, one
 // pair of timing events.
 #pragma once
 

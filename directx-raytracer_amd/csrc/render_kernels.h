@@ -1,4 +1,4 @@
-// Launch interface between the C-ABI layer (crt_api.cpp, host C++) and the HIP kernels (render_kernels.hip, path_kernels.hip; device code shared through traversal.hip.h / shading.hip.h).
+// Launch interface between the C-ABI layer (crt_api.cpp and the api_*.cpp units, host C++: crt_ctx.h maps them) and the HIP kernels (render_kernels.hip, path_kernels.hip; device code shared through traversal.hip.h / shading.hip.h).
 // The frame kernels and the image-space kernels have one launch function each; the persistent query kernels share one
 // (launchQuery, query_launch.cpp) over a table of their host stubs (QueryKind, QueryKernel): a kernel file states its rows.
 #pragma once

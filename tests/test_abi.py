@@ -67,6 +67,15 @@ def test_comm_entry_points_reject_bad_arguments_without_a_gpu(pkg):
     assert "rccl" not in out.lower(), "RCCL must stay a run-time (dlopen) dependency"
 
 
+def test_shared_helpers_of_the_abi_layer_are_not_exported(pkg):
+    """what the units of the C-ABI layer share (csrc/crt_ctx.h, namespace crtapi) is hidden: none of it in the dynamic symbol table"""
+    out = os.popen("nm -D --defined-only %s" % pkg.LIB_PATH).read()
+    names = [line.split()[-1] for line in out.splitlines() if line.strip()]
+    assert "crt_create" in names, "nm listed no symbols of the library"
+    leaked = [n for n in names if "crtapi" in n]
+    assert not leaked, "internal helpers in the dynamic symbol table: %s" % leaked
+
+
 def test_product_does_not_reference_the_oracle():
     """The product path must not import, link or call anything under oracle/."""
     pkg_dir = os.path.join(ROOT, "directx-raytracer_amd")

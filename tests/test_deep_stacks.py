@@ -1,6 +1,6 @@
 """Stacks past the LDS part.  Every traversal kernel keeps the first `stack_entries` entries (default 16) of a lane's stack in LDS
 and the deeper ones in the lane's slice of a global spill arena, which the host sizes as 3 * depth4 + 1 - stack_entries entries
-(crt_api.cpp: runRender and the query launch setup; twice as many ints for the closest-point kernel's pairs).  The scenes of
+(api_frames.cpp runRender and api_queries.cpp beginQuery; twice as many ints for the closest-point kernel's pairs).  The scenes of
 tests/deep_stack_scenes.py put lanes up to 60 entries deep -- one entry short of that bound -- in every walk class (closest hit, any
 hit, the no-cull walks of the counts and lists, closest point) over every builder's tree, so a wrong stride, a stale depth4 or a
 wrong slice index makes lanes overwrite each other's pending nodes and the comparisons below fail.
@@ -408,7 +408,7 @@ def test_depth4_moves_on_every_route(pkg, oracle):
 
 # ---- GPU
 
-RING = 4  # frames a context keeps in flight (crt_api.cpp kRing): one spill arena each
+RING = 4  # frames a context keeps in flight (crt_ctx.h kRing): one spill arena each
 DEFAULTS = (("gpu_build", 0), ("gpu_builder", 0), ("stack_entries", 0), ("path_pipeline", 0), ("path_tile", 0), ("split_units", -1),
             ("split_rays", 4), ("split_segments", 16), ("list_short_max", 24))
 PATH_FORMS = ((0, 0), (1, 0), (0, 16))  # (path_pipeline, path_tile): path_tile = 16 runs with path_pipeline = 0

@@ -773,7 +773,7 @@ def test_headless_driver_full_camera_controls_and_mode_switch(pkg, oracle, scene
 
 
 def test_native_rccl_gather_behind_the_c_abi(pkg, oracle, scenes, dragon, renderer, tmp_path, golden_dir):
-    """crt_comm_init + crt_render_frame_distributed (csrc/crt_api.cpp): tiles -> ncclAllGather on the context's stream ->
+    """crt_comm_init + crt_render_frame_distributed (csrc/api_comm.cpp): tiles -> ncclAllGather on the context's stream ->
     untile, no torch involved.  With the one rank this box has: the distributed frame equals crt_render_frame_device's and the
     oracle's; crt_render --ranks 1 (the C++-only launcher: parent forks the rank processes before touching the GPU) writes
     the same images as the single-process run; and so do three rank processes sharing this GPU through the host-memory exchange."""
