@@ -19,8 +19,6 @@
 
 using namespace crtapi;
 
-extern "C" {
-
 // ------------------------------------------------------------------------------------------- native RCCL gather
 // One process per GPU; every rank renders its macro tiles into a tile-major staging buffer, ONE ncclAllGather per frame moves
 // them over xGMI (1 044 480 bytes per rank at 1080p / 8 GPUs, each rank's 7 inbound messages on 7 different links), the
@@ -285,5 +283,3 @@ int crt_render_frame_distributed(crt_ctx* c, uint32_t w, uint32_t h, void* d_rgb
     }
     return CRT_OK;
 }
-
-} // extern "C"

@@ -11,8 +11,6 @@
 
 using namespace crtapi;
 
-extern "C" {
-
 // ------------------------------------------------------------------------------------------- dynamic geometry (refit.h)
 namespace {
 
@@ -516,5 +514,3 @@ int crt_closest_points_backward(crt_ctx* c, uint32_t n, const float* points, con
     stampTotal(stats, t0);
     return CRT_OK;
 }
-
-} // extern "C"

@@ -405,8 +405,6 @@ int runFrame(crt_ctx* c, RenderParams& p, crt_frame_stats* stats, uint32_t kind)
 
 } // namespace
 
-extern "C" {
-
 int crt_set_accumulation(crt_ctx* c, uint32_t max_samples)
 {
     if (!c) return CRT_EINVAL;
@@ -589,5 +587,3 @@ int crt_debug_read_timeline(crt_ctx* c, unsigned long long* out, size_t max_word
     *n_words = n;
     return CRT_OK;
 }
-
-} // extern "C"

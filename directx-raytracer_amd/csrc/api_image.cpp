@@ -11,10 +11,8 @@
 
 using namespace crtapi;
 
-extern "C" {
-
 // ---- camera rays, frame guides and the denoiser (camera_kernels.hip, denoise_kernels.hip)
-crt::CameraRayParams cameraRayParams(const crt_ctx* c, uint32_t w, uint32_t h, uint32_t sample, void* d_rays)
+crt::CameraRayParams crtapi::cameraRayParams(const crt_ctx* c, uint32_t w, uint32_t h, uint32_t sample, void* d_rays)
 {
     crt::CameraRayParams p;
     std::memset(&p, 0, sizeof(p));
@@ -465,5 +463,3 @@ int crt_denoise_variance(crt_ctx* c, uint32_t w, uint32_t h, const float* rgb, c
 {
     return denoiseHost(c, "crt_denoise_variance", true, w, h, rgb, normal, albedo, t, variance, out, varianceOut, guidedParams(params), stats);
 }
-
-} // extern "C"

@@ -29,12 +29,6 @@ template <class Q> void sceneTables(const crt_ctx* c, Q& q)
     q.inner_min_any = c->tuneInnerMinAny;
 }
 
-} // namespace
-
-extern "C" {
-
-namespace {
-
 // Batched ray and point queries.  A query is n records of one kind (32-byte rays or 16-byte points) and up to seven outputs
 // of a fixed size per record; every kind (crt::QueryKind) runs one persistent kernel over an arena of the context.
 using crt::QueryKind;
@@ -98,7 +92,7 @@ int ensureMoments(crt_ctx* c)
 } // namespace
 
 // the scene's shading tables (sceneTables) and the context's shading state of a shaded query
-void shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q)
+void crtapi::shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q)
 {
     sceneTables(c, q);
     q.mode = c->mode;
@@ -251,7 +245,7 @@ int queryGrid(crt_ctx* c, QueryKind kind, uint32_t n, uint32_t& stack_entries, u
 // synchronises and fills them.
 // extraBytes: scratch of the query's own with the arena's lifetime (an allocation failure is then CRT_ENOMEM); minGrid: the
 // spill area is sized for at least that many workgroups (a query that runs a second persistent kernel over the same arena).
-int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, crt_frame_stats* stats, QueryLaunch& ql, size_t extraBytes, uint32_t minGrid)
+int crtapi::beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, crt_frame_stats* stats, QueryLaunch& ql, size_t extraBytes, uint32_t minGrid)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int rc = queryGrid(c, kind, n, ql.stack_entries, ql.chunk, ql.grid)) return rc;
@@ -272,7 +266,7 @@ int beginQuery(crt_ctx* c, QueryKind kind, uint32_t n, crt_frame_stats* stats, Q
     return CRT_OK;
 }
 
-int endQuery(crt_ctx* c, QueryKind kind, uint32_t n, const QueryLaunch& ql, int rc, crt_frame_stats* stats)
+int crtapi::endQuery(crt_ctx* c, QueryKind kind, uint32_t n, const QueryLaunch& ql, int rc, crt_frame_stats* stats)
 {
     if (rc != 0) return fail(c, CRT_EHIP, "query kernel launch failed: %s", hipGetErrorString(static_cast<hipError_t>(rc)));
     if (stats) HIP_TRY(c, hipEventRecord(c->evStop, c->stream));
@@ -288,7 +282,7 @@ int endQuery(crt_ctx* c, QueryKind kind, uint32_t n, const QueryLaunch& ql, int 
 }
 
 // the part of a query kernel's parameters every kind shares, from the context and the launch
-crt::QueryCommon queryCommon(const crt_ctx* c, const QueryLaunch& ql, const void* d_records, uint32_t n, uint32_t inner_min)
+crt::QueryCommon crtapi::queryCommon(const crt_ctx* c, const QueryLaunch& ql, const void* d_records, uint32_t n, uint32_t inner_min)
 {
     crt::QueryCommon q;
     q.nodes = c->dNodes;
@@ -800,5 +794,3 @@ int crt_debug_list_phases(crt_ctx* c, double out_ms[4])
     std::memcpy(out_ms, c->queries.listPhaseMs, sizeof(c->queries.listPhaseMs));
     return CRT_OK;
 }
-
-} // extern "C"

@@ -14,9 +14,7 @@
 
 // (crt_ctx.h's, which this unit leaves out: it would bring the HIP runtime's header)
 namespace crtapi {
-#pragma GCC visibility push(hidden)
 int fail(crt_ctx* ctx, int code, const char* fmt, ...);
-#pragma GCC visibility pop
 } // namespace crtapi
 using crtapi::fail;
 
@@ -25,8 +23,6 @@ struct crt_scene {
     // uint32 copies of the int index vectors are not needed: std::vector<int> is reinterpreted like the
     // reference does for its index buffers (R/DXRTRenderer.cpp:314-315)
 };
-
-extern "C" {
 
 // ------------------------------------------------------------------------------------------- scene layer
 int crt_scene_load(const char* path, crt_scene** out, char* err, size_t err_len)
@@ -278,5 +274,3 @@ int crt_set_camera_from(crt_ctx* c, const crt_scene* s)
     if (!s) return fail(c, CRT_EINVAL, "scene is NULL");
     return crt_set_camera(c, s->scene.getCamera().getPosition().data(), s->scene.getCamera().getRotationMatrix().data());
 }
-
-} // extern "C"

@@ -52,10 +52,7 @@ int regrow(crt_ctx* c, void*& p, size_t used, size_t bytes)
 
 } // namespace
 
-// (ensureBuffer, reserveRayStage and takeArena keep C names: a helper defined inside an extern "C" block has one even in an
-// unnamed namespace and so stands in the library's dynamic symbol table, these three since they were written and, in every unit of
-// the layer, each helper that is not static; the table is kept as it is)
-extern "C" {
+namespace crtapi {
 
 // A device buffer of at least `need` bytes; one that grows keeps nothing of its contents.  Work in flight on any stream may still
 // use the old buffer, hence the device-wide wait.  ownScratch: the buffer is scratch the call keeps for itself; an allocation
@@ -106,10 +103,6 @@ int reserveRayStage(crt_ctx* c, size_t total)
     HIP_TRY(c, hipSetDevice(c->device));
     return ensureBuffer(c, &c->dRayStage, &c->rayStageBytes, total);
 }
-
-} // extern "C"
-
-namespace crtapi {
 
 int fail(crt_ctx* ctx, int code, const char* fmt, ...)
 {
@@ -366,8 +359,6 @@ const Option kOptions[] = {
 #undef FLAG
 
 } // namespace
-
-extern "C" {
 
 uint32_t crt_abi_version(void) { return CRT_ABI_VERSION; }
 
@@ -816,7 +807,9 @@ int crt_bvh_export(const crt_ctx* c, crt_bvh_node* nodes, crt_bvh_tri* tris, crt
     return CRT_OK;
 }
 
-// ---- shared with the other units under their C names (crt_ctx.h)
+// ---- shared with the other units (crt_ctx.h)
+namespace crtapi {
+
 void zeroStats(crt_frame_stats* stats, std::chrono::steady_clock::time_point t0)
 {
     if (!stats) return;
@@ -853,4 +846,4 @@ int runTimed(crt_ctx* c, const char* what, crt_frame_stats* stats, const std::fu
     return readStats(c, stats);
 }
 
-} // extern "C"
+} // namespace crtapi

@@ -6,8 +6,9 @@
 //   api_dynamic.cpp  vertex updates, transforms, refit / rebuild, motion, gradients
 //   api_comm.cpp     RCCL gather and the host-memory exchange
 //   api_scene.cpp    the crt_scene_* layer (no context, no HIP: it does not include this header)
-// Helpers the units share live in namespace crtapi with hidden visibility, so none of them reaches the library's dynamic symbol
-// table.  The exception stands at the end: the helpers that have always carried C names there.
+// Helpers the units share live in namespace crtapi; what a unit keeps to itself stands in its unnamed namespace.  Only the crt_*
+// functions carry C names (from their declarations in the public header), and exports.map keeps all the rest out of the library's
+// dynamic symbol table.
 #pragma once
 
 #include "../../include/crt_hip.h"
@@ -31,16 +32,13 @@ struct HostExchange; // api_comm.cpp
 
 // "The work enqueued on a stream up to here": an event, the stream it was last recorded on, and whether it was recorded at all.
 // Everything on the context that one call leaves behind for a later call, possibly on another stream, is guarded by one.
-// (CRTAPI_HIDDEN: a member emitted out of line stays out of the dynamic symbol table; the type itself cannot be hidden, the public
-// crt_ctx holds it)
-#define CRTAPI_HIDDEN __attribute__((visibility("hidden")))
 namespace crtapi {
 struct Fence {
     hipEvent_t event = nullptr; // created at the first record (the frame slots': by crt_create)
     hipStream_t stream = nullptr;
     bool pending = false;
 
-    CRTAPI_HIDDEN hipError_t record(hipStream_t s)
+    hipError_t record(hipStream_t s)
     {
         if (!event)
             if (const hipError_t e = hipEventCreateWithFlags(&event, hipEventDisableTiming)) return e;
@@ -51,12 +49,12 @@ struct Fence {
     // `s` runs behind the recorded work.  A wait is only enqueued when it can matter: not for an event that has already completed
     // (a host-side poll), and -- unless sameStreamToo -- not for work recorded on `s` itself, which runs in order anyway: every
     // barrier packet costs the stream a few microseconds
-    CRTAPI_HIDDEN hipError_t wait(hipStream_t s, bool sameStreamToo) const
+    hipError_t wait(hipStream_t s, bool sameStreamToo) const
     {
         if (!pending || (!sameStreamToo && stream == s) || hipEventQuery(event) == hipSuccess) return hipSuccess;
         return hipStreamWaitEvent(s, event, 0);
     }
-    CRTAPI_HIDDEN void destroy()
+    void destroy()
     {
         if (event) (void)hipEventDestroy(event);
         event = nullptr;
@@ -288,9 +286,6 @@ struct StagePlane {
     int over = -1;   // >= 0: the room of that earlier plane, none of its own: a result written in place, downloaded at this place
 };
 
-// The functions below are hidden, so that none of what the cut into units made external reaches the dynamic symbol table
-#pragma GCC visibility push(hidden)
-
 // sets the context's error string (ctx == NULL: the thread's create error, crt_last_error(NULL)) and returns `code`
 int fail(crt_ctx* ctx, int code, const char* fmt, ...);
 
@@ -318,12 +313,7 @@ int reserveRefitCapacity(crt_ctx* c);
 int applyRefit(crt_ctx* c, double* device_ms);
 int checkRenderable(crt_ctx* c, uint32_t w, uint32_t h);
 
-#pragma GCC visibility pop
-} // namespace crtapi
-
-// Shared helpers that stand in the library's dynamic symbol table under C names and keep doing so: the three of crt_api.cpp that
-// were written that way, and those that were defined below the public header's extern "C" before the layer was cut into units
-extern "C" {
+// buffers, arenas, stats and argument checks (crt_api.cpp)
 int ensureBuffer(crt_ctx* c, void** ptr, size_t* have, size_t need, bool ownScratch = false);
 int takeArena(crt_ctx* c, crt_ctx::Arena (&pool)[crt_ctx::kRing], size_t need, uint32_t serial, bool ownScratch, crt_ctx::Arena*& out);
 int reserveRayStage(crt_ctx* c, size_t total);
@@ -333,10 +323,11 @@ int checkFrameSize(crt_ctx* c, const char* what, uint32_t w, uint32_t h);
 int checkDevicePointers(crt_ctx* c, const char* what, std::initializer_list<const void*> ptrs, uintptr_t align);
 // api_queries.cpp
 void shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q);
-int beginQuery(crt_ctx* c, crt::QueryKind kind, uint32_t n, crt_frame_stats* stats, crtapi::QueryLaunch& ql, size_t extraBytes = 0,
+int beginQuery(crt_ctx* c, crt::QueryKind kind, uint32_t n, crt_frame_stats* stats, QueryLaunch& ql, size_t extraBytes = 0,
                uint32_t minGrid = 0);
-int endQuery(crt_ctx* c, crt::QueryKind kind, uint32_t n, const crtapi::QueryLaunch& ql, int rc, crt_frame_stats* stats);
-crt::QueryCommon queryCommon(const crt_ctx* c, const crtapi::QueryLaunch& ql, const void* d_records, uint32_t n, uint32_t inner_min);
+int endQuery(crt_ctx* c, crt::QueryKind kind, uint32_t n, const QueryLaunch& ql, int rc, crt_frame_stats* stats);
+crt::QueryCommon queryCommon(const crt_ctx* c, const QueryLaunch& ql, const void* d_records, uint32_t n, uint32_t inner_min);
 // api_image.cpp
 crt::CameraRayParams cameraRayParams(const crt_ctx* c, uint32_t w, uint32_t h, uint32_t sample, void* d_rays);
-}
+
+} // namespace crtapi

@@ -76,6 +76,44 @@ def test_shared_helpers_of_the_abi_layer_are_not_exported(pkg):
     assert not leaked, "internal helpers in the dynamic symbol table: %s" % leaked
 
 
+# the host C++ classes of csrc/scene.h and csrc/renderer.h: with the C ABI, all that csrc/exports.map lets out of the library
+EXPORTED_CLASSES = ["Renderer", "Scene", "SceneParser", "Camera", "Mesh", "Matrix", "Vector", "Triangle", "Light", "Material", "TextureDesc"]
+
+
+def test_library_exports_exactly_its_interface(pkg):
+    """the dynamic symbol table is the interface and nothing else: the crt_* names are the header's, no more and no fewer (a
+    definition whose signature drifted from its declaration would be a mangled overload and its C name missing), every other
+    name is a member of a class the export map lists, and no other unmangled name appears"""
+    text = open(os.path.join(os.path.dirname(pkg.LIB_PATH), "csrc", "exports.map")).read()
+    assert sorted(re.findall(r"^\s*crt::(\w+)::\*;", text, flags=re.M)) == sorted(EXPORTED_CLASSES)
+    raw = [line.split()[-1] for line in os.popen("nm -D --defined-only %s" % pkg.LIB_PATH).read().splitlines() if line.strip()]
+    assert sorted(n for n in raw if n.startswith("crt_")) == _declared_symbols()
+    unmangled = [n for n in raw if not n.startswith("crt_") and not n.startswith("_Z")]
+    assert not unmangled, "unmangled names besides the C ABI: %s" % unmangled
+    demangled = [line.split(None, 2)[2] for line in os.popen("nm -DC --defined-only %s" % pkg.LIB_PATH).read().splitlines() if line.strip()]
+    assert len(demangled) == len(raw)
+    prefixes = tuple("crt::%s::" % c for c in EXPORTED_CLASSES)
+    stray = [n for n in demangled if not n.startswith("crt_") and not n.startswith(prefixes)]
+    assert not stray, "exported, but neither the C ABI nor a class of the export map: %s" % stray
+
+
+def test_cpp_consumers_link(pkg, tmp_path):
+    """every C++ driver of the suite (tests/*_cpp.cpp) compiles and links against the library with the flags of the GPU test that
+    runs it (-O0 here): what they use of crt::Renderer and crt::Camera is exported"""
+    import glob
+    import subprocess
+    lib_dir = os.path.dirname(pkg.LIB_PATH)
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    sources = sorted(glob.glob(os.path.join(ROOT, "tests", "*_cpp.cpp")))
+    assert len(sources) >= 10
+    jobs = [(src, subprocess.Popen(["g++", "-std=c++17", "-O0", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
+                                    "-I" + os.path.join(lib_dir, "csrc"), "-o", str(tmp_path / os.path.basename(src)[:-4]), src,
+                                    "-L" + lib_dir, "-lcrt_hip", "-Wl,-rpath," + lib_dir, "-L" + os.path.join(rocm, "lib"), "-lamdhip64",
+                                    "-Wl,-rpath," + os.path.join(rocm, "lib")], stderr=subprocess.PIPE, text=True)) for src in sources]
+    failed = ["%s:\n%s" % (os.path.basename(src), err) for src, job in jobs for err in [job.communicate(timeout=300)[1]] if job.returncode != 0]
+    assert not failed, "\n".join(failed)
+
+
 def test_product_does_not_reference_the_oracle():
     """The product path must not import, link or call anything under oracle/."""
     pkg_dir = os.path.join(ROOT, "directx-raytracer_amd")

@@ -20,6 +20,6 @@ wait
 # the Makefile's object list, with the recompiled units in place of the product's
 OBJ=$(make -pn | sed -n 's/^OBJ = //p' | head -1)
 for u in $UNITS $HOST; do OBJ=${OBJ/build\/$u.o/build\/${u}_$NAME.o}; done
-g++ -shared -o ../libcrt_hip_$NAME.so $OBJ -L/opt/rocm/lib -lamdhip64 -ldl -fopenmp -Wl,-rpath,/opt/rocm/lib
+g++ -shared -o ../libcrt_hip_$NAME.so $OBJ -Wl,--version-script=exports.map -L/opt/rocm/lib -lamdhip64 -ldl -fopenmp -Wl,-rpath,/opt/rocm/lib
 for u in $UNITS $HOST; do rm -f build/${u}_$NAME.o; done
 echo "built directx-raytracer_amd/libcrt_hip_$NAME.so"
