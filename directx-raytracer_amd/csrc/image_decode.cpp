@@ -15,6 +15,15 @@ namespace {
 
 constexpr long long kMaxTexels = 1ll << 28;
 
+constexpr size_t kMaxGifTexelsPerByte = 65536;
+
+// width x height within the texel cap; each factor is held to the cap first, so the product cannot wrap whatever a header says
+bool texelsFit(unsigned long long w, unsigned long long h)
+{
+    const unsigned long long cap = static_cast<unsigned long long>(kMaxTexels);
+    return w <= cap && h <= cap && w * h <= cap;
+}
+
 // ---------------------------------------------------------------------------------------------- inflate (RFC 1951)
 struct BitReader {
     const unsigned char* p;
@@ -110,6 +119,9 @@ void inflateBlock(BitReader& br, const Huffman& lit, const Huffman& dist, std::v
     }
 }
 
+// deflate's ceiling: a length / distance pair of one bit each yields 258 bytes, 1032 bytes for every byte of coded data
+constexpr size_t kMaxDeflateRatio = 1032;
+
 } // namespace
 
 std::vector<unsigned char> zlibInflate(const unsigned char* data, size_t size, size_t expectedSize, const std::string& what)
@@ -117,7 +129,7 @@ std::vector<unsigned char> zlibInflate(const unsigned char* data, size_t size, s
     if (size < 2 || (data[0] & 0x0F) != 8 || ((data[0] << 8) | data[1]) % 31 != 0 || (data[1] & 0x20)) bad(what, "bad zlib header");
     BitReader br{ data + 2, size - 2, 0, 0, 0, what };
     std::vector<unsigned char> out;
-    out.reserve(expectedSize);
+    out.reserve(std::min(expectedSize, size * kMaxDeflateRatio)); // (never on the caller's word alone)
     Huffman lit, dist;
     for (;;) {
         const uint32_t last = br.take(1), type = br.take(2);
@@ -242,7 +254,7 @@ DecodedImage decodePng(const std::vector<unsigned char>& f, const std::string& w
         if (std::memcmp(type, "IHDR", 4) == 0) {
             if (len != 13 || haveHeader) bad(what, "bad IHDR");
             w = be32(d); h = be32(d + 4); depth = d[8]; color = d[9]; interlace = d[12];
-            if (w == 0 || h == 0 || static_cast<long long>(w) * h > kMaxTexels) bad(what, "bad PNG size");
+            if (w == 0 || h == 0 || !texelsFit(w, h)) bad(what, "bad PNG size");
             if (d[10] != 0 || d[11] != 0 || interlace > 1) bad(what, "unknown PNG compression / filter / interlace method");
             const bool ok = (color == 0 && (depth == 1 || depth == 2 || depth == 4 || depth == 8 || depth == 16)) ||
                             ((color == 2 || color == 4 || color == 6) && (depth == 8 || depth == 16)) ||
@@ -264,9 +276,10 @@ DecodedImage decodePng(const std::vector<unsigned char>& f, const std::string& w
                 if (len != 2 * n) bad(what, "bad tRNS");
                 for (uint32_t i = 0; i < n; i++) {
                     trns16[i] = static_cast<uint32_t>(d[2 * i] << 8) | d[2 * i + 1];
-                    // samples are compared after their reduction to 8 bits, as stb_image does
+                    // below 16 bits the samples are compared after their scaling to 8 bits; 16-bit samples are compared in full, before
+                    // their reduction to the high byte (as stb_image does in both cases)
                     static const int scale[9] = { 0, 255, 85, 0, 17, 0, 0, 0, 1 };
-                    trnsKey[i] = depth == 16 ? static_cast<unsigned char>(trns16[i] >> 8) : static_cast<unsigned char>((trns16[i] & 255u) * scale[depth]);
+                    if (depth != 16) trnsKey[i] = static_cast<unsigned char>((trns16[i] & 255u) * scale[depth]);
                 }
                 haveTrns = true;
             } else {
@@ -297,10 +310,15 @@ DecodedImage decodePng(const std::vector<unsigned char>& f, const std::string& w
         if (interlace && (static_cast<uint32_t>(x0[p]) >= w || static_cast<uint32_t>(y0[p]) >= h)) pw[p] = ph[p] = 0;
         if (pw[p] && ph[p]) rawSize += ph[p] * (1 + (pw[p] * bitsPerPixel + 7) / 8);
     }
+    // nothing is allocated for the image before the coded data is known to be able to fill it
+    if (rawSize / kMaxDeflateRatio > idat.size()) bad(what, "PNG image data too short for the image's size");
     std::vector<unsigned char> raw = zlibInflate(idat.data(), idat.size(), rawSize, what);
     if (raw.size() != rawSize) bad(what, "PNG image data has the wrong size");
-    // samples as 8-bit values, file channel count
+    std::vector<unsigned char>().swap(idat);
+    // samples as 8-bit values, file channel count; a 16-bit colour key is looked up here, where the full samples still are
     std::vector<unsigned char> samples(static_cast<size_t>(w) * h * fileCh);
+    const bool key16 = haveTrns && depth == 16 && color != 3;
+    std::vector<unsigned char> keyed(key16 ? static_cast<size_t>(w) * h : 0);
     size_t at = 0;
     for (int p = 0; p < passes; p++) {
         if (!pw[p] || !ph[p]) continue;
@@ -315,7 +333,13 @@ DecodedImage decodePng(const std::vector<unsigned char>& f, const std::string& w
                 if (depth == 8) {
                     std::memcpy(dst, line + x * fileCh, static_cast<size_t>(fileCh));
                 } else if (depth == 16) {
-                    for (int c = 0; c < fileCh; c++) dst[c] = line[(x * fileCh + c) * 2]; // the high byte
+                    bool isKey = key16;
+                    for (int c = 0; c < fileCh; c++) {
+                        const unsigned char* s16 = line + (x * fileCh + c) * 2;
+                        dst[c] = s16[0]; // the high byte
+                        if (key16) isKey = isKey && ((static_cast<uint32_t>(s16[0]) << 8) | s16[1]) == trns16[c];
+                    }
+                    if (key16) keyed[oy * w + ox] = isKey ? 1 : 0;
                 } else { // 1, 2, 4 bits, one channel
                     const size_t bit = x * depth;
                     const unsigned v = (line[bit >> 3] >> (8 - depth - (bit & 7))) & ((1u << depth) - 1u);
@@ -326,6 +350,7 @@ DecodedImage decodePng(const std::vector<unsigned char>& f, const std::string& w
         }
         at += ph[p] * (stride + 1);
     }
+    std::vector<unsigned char>().swap(raw);
     DecodedImage img;
     img.width = static_cast<int>(w);
     img.height = static_cast<int>(h);
@@ -347,6 +372,7 @@ DecodedImage decodePng(const std::vector<unsigned char>& f, const std::string& w
                 img.pixels[i * img.channels + c] = samples[i * fileCh + c];
                 key = key && samples[i * fileCh + c] == trnsKey[c];
             }
+            if (key16) key = keyed[i] != 0;
             img.pixels[i * img.channels + fileCh] = key ? 0 : 255;
         }
     } else {
@@ -377,7 +403,7 @@ DecodedImage decodeBmp(const std::vector<unsigned char>& f, const std::string& w
     }
     const bool flip = h > 0; // rows bottom-up unless the height is negative
     if (h < 0) h = -h;
-    if (w <= 0 || h <= 0 || w * h > kMaxTexels) bad(what, "bad BMP size");
+    if (w <= 0 || h <= 0 || !texelsFit(static_cast<unsigned long long>(w), static_cast<unsigned long long>(h))) bad(what, "bad BMP size");
     if (compression == 1 || compression == 2) bad(what, "run-length coded BMP files are not supported (the reference's decoder rejects them too)");
     if (compression >= 4) bad(what, "BMP files that wrap a JPEG or PNG are not supported (the reference's decoder rejects them too)");
     if (compression == 3 && bpp != 16 && bpp != 32) bad(what, "BMP channel masks need 16 or 32 bits per pixel");
@@ -502,7 +528,7 @@ DecodedImage decodeTga(const std::vector<unsigned char>& f, const std::string& w
     if (mapped > 1) bad(what, "TGA colour-map type that is not 0 or 1");
     if (mapped ? type != 1 : (type != 2 && type != 3)) bad(what, "TGA image type that is not colour-mapped, true colour or grey");
     if (mapped && bpp != 8 && bpp != 16) bad(what, "colour-mapped TGA whose indices are not 8 or 16 bits");
-    if (w == 0 || h == 0) bad(what, "bad TGA size");
+    if (w == 0 || h == 0 || !texelsFit(w, h)) bad(what, "bad TGA size");
     auto layout = [&](unsigned bits, bool grey, bool& packed555) -> unsigned { // bytes per texel of the result
         packed555 = false;
         if (bits == 8) return 1;
@@ -529,6 +555,7 @@ DecodedImage decodeTga(const std::vector<unsigned char>& f, const std::string& w
         if (palLen == 0) bad(what, "colour-mapped TGA without a palette");
         need(palStart);
         pos += palStart;
+        need(static_cast<size_t>(palLen) * (packed ? 2 : comp));
         palette.resize(static_cast<size_t>(palLen) * comp);
         if (packed) {
             for (unsigned i = 0; i < palLen; i++) rgb555(&palette[static_cast<size_t>(i) * comp]);
@@ -542,6 +569,10 @@ DecodedImage decodeTga(const std::vector<unsigned char>& f, const std::string& w
     img.width = static_cast<int>(w);
     img.height = static_cast<int>(h);
     img.channels = static_cast<int>(comp);
+    // the file must be able to hold the image: raw, every texel's bytes; run-length coded, a packet of a count and one texel for
+    // every 128 texels
+    const size_t texelBytes = mapped ? bpp / 8 : (packed ? 2 : comp);
+    need(rle ? (n + 127) / 128 * (1 + texelBytes) : n * texelBytes);
     img.pixels.resize(n * comp);
     unsigned char texel[4] = { 0, 0, 0, 0 };
     unsigned left = 0;       // texels left in the current packet
@@ -609,7 +640,7 @@ DecodedImage decodePnm(const std::vector<unsigned char>& f, const std::string& w
     };
     const long long w = nextInt(), h = nextInt(), maxv = nextInt();
     pos++; // the single whitespace byte after maxval
-    if (w <= 0 || h <= 0 || maxv > 65535 || w * h > kMaxTexels) bad(what, "bad PNM header");
+    if (w <= 0 || h <= 0 || maxv > 65535 || !texelsFit(static_cast<unsigned long long>(w), static_cast<unsigned long long>(h))) bad(what, "bad PNM header");
     DecodedImage img;
     img.width = static_cast<int>(w);
     img.height = static_cast<int>(h);
@@ -642,7 +673,11 @@ DecodedImage decodeGif(const std::vector<unsigned char>& f, const std::string& w
     const unsigned flags = u8(), background = u8();
     u8(); // aspect ratio
     if (img.width == 0 || img.height == 0) bad(what, "GIF canvas without an extent");
-    if (static_cast<uint64_t>(img.width) * static_cast<uint64_t>(img.height) > (1ull << 28)) bad(what, "more than 2^28 texels");
+    if (!texelsFit(static_cast<unsigned>(img.width), static_cast<unsigned>(img.height))) bad(what, "more than 2^28 texels");
+    // A canvas is in no byte of the file beyond these four, so no coding bounds it.  It is held to what the file's image data could
+    // at best draw -- an LZW code of one bit stands for at most the 8192 texels of the longest table entry, 65536 texels a byte --
+    // which refuses a well-formed file only where a few bytes name a canvas thousands of times their image (see image_decode.h).
+    if (static_cast<size_t>(img.width) * static_cast<size_t>(img.height) / kMaxGifTexelsPerByte > f.size()) bad(what, "GIF canvas too large for its file");
     struct Entry { unsigned char r, g, b, a; };
     Entry global[256] = {}, local[256] = {};
     auto readTable = [&](Entry* t, unsigned n, int transparent) {
@@ -828,7 +863,14 @@ DecodedImage decodeHdr(const std::vector<unsigned char>& f, const std::string& w
     while (*rest == ' ') rest++;
     if (std::strncmp(rest, "+X ", 3) != 0) bad(what, "HDR file with an unsupported scanline order");
     const long w = std::strtol(rest + 3, nullptr, 10);
-    if (w <= 0 || h <= 0 || static_cast<uint64_t>(w) * static_cast<uint64_t>(h) > (1ull << 28)) bad(what, "HDR size missing or above 2^28 texels");
+    if (w <= 0 || h <= 0 || !texelsFit(static_cast<unsigned long long>(w), static_cast<unsigned long long>(h))) bad(what, "HDR size missing or above 2^28 texels");
+    // the file must be able to hold the image: flat, four bytes a texel; run-length coded, per scanline its four-byte head and, in
+    // each of the four channels, a run of a count and a value for every 127 texels
+    const size_t texels = static_cast<size_t>(w) * static_cast<size_t>(h);
+    const bool flat = w < 8 || w >= 32768;
+    auto needFlat = [&](size_t n) { if (at > f.size() || n > (f.size() - at) / 4) bad(what, "HDR file too short for its size"); };
+    if (flat) needFlat(texels);
+    else if (static_cast<size_t>(h) > (f.size() - std::min(at, f.size())) / (4 + 8 * ((static_cast<size_t>(w) + 126) / 127))) bad(what, "HDR file too short for its size");
     DecodedImage img;
     img.width = static_cast<int>(w);
     img.height = static_cast<int>(h);
@@ -849,7 +891,7 @@ DecodedImage decodeHdr(const std::vector<unsigned char>& f, const std::string& w
             convert(lin.data() + 3 * t, q);
         }
     };
-    if (w < 8 || w >= 32768) {
+    if (flat) {
         flatFrom(0);
     } else {
         std::vector<unsigned char> scan(static_cast<size_t>(w) * 4);
@@ -860,6 +902,7 @@ DecodedImage decodeHdr(const std::vector<unsigned char>& f, const std::string& w
                 // the frame's SECOND texel whatever row it was in (so only a file that is flat from its first row decodes sensibly)
                 const unsigned char q[4] = { static_cast<unsigned char>(c1), static_cast<unsigned char>(c2), static_cast<unsigned char>(hi), static_cast<unsigned char>(u8()) };
                 convert(lin.data(), q);
+                needFlat(texels - 1);
                 flatFrom(1);
                 break;
             }
@@ -915,14 +958,21 @@ DecodedImage decodePsd(const std::vector<unsigned char>& f, const std::string& w
     skip(u32()); // layers and masks
     const unsigned compression = u16();
     if (compression > 1) bad(what, "PSD with an unknown compression");
-    if (w == 0 || h == 0 || static_cast<uint64_t>(w) * h > (1ull << 28)) bad(what, "PSD size missing or above 2^28 texels");
+    if (w == 0 || h == 0 || !texelsFit(w, h)) bad(what, "PSD size missing or above 2^28 texels");
+    if (channels == 0) bad(what, "PSD without channels");
     DecodedImage img;
     img.width = static_cast<int>(w);
     img.height = static_cast<int>(h);
     img.channels = 4;
     const size_t texels = static_cast<size_t>(w) * h;
-    img.pixels.assign(texels * 4, 0);
     if (compression) skip(static_cast<uint64_t>(h) * channels * 2); // the byte counts of the coded rows: not needed, the planes are decoded as one stream
+    // the file must be able to hold the planes that are read: raw, every sample; PackBits, two bytes for every 128 samples
+    {
+        const size_t planes = channels < 4 ? channels : 4, left = at < f.size() ? f.size() - at : 0;
+        const size_t perPlane = compression ? (texels + 127) / 128 * 2 : texels * (depth / 8);
+        if (perPlane > left / planes) bad(what, "PSD file too short for its size");
+    }
+    img.pixels.assign(texels * 4, 0);
     for (unsigned c = 0; c < 4; c++) {
         unsigned char* p = img.pixels.data() + c;
         if (c >= channels) {
@@ -987,6 +1037,20 @@ DecodedImage decodePic(const std::vector<unsigned char>& f, const std::string& w
         need();
         if (bits != 8) bad(what, "PIC packet that is not 8 bits per channel");
     } while (chained);
+    // the file must be able to hold the image: the fewest bytes a scanline can take is, per packet, every texel's channels (raw), a
+    // count and a value for every 255 texels (runs only), or a three-byte head and a value for every 65535 texels (mixed)
+    {
+        size_t rowBytes = 0;
+        for (int k = 0; k < nPackets; k++) {
+            size_t chans = 0;
+            for (int i = 0; i < 4; i++) chans += (packets[k].mask >> (7 - i)) & 1u;
+            if (packets[k].type == 0) rowBytes += static_cast<size_t>(w) * chans;
+            else if (packets[k].type == 1) rowBytes += (static_cast<size_t>(w) + 254) / 255 * (1 + chans);
+            else rowBytes += (static_cast<size_t>(w) + 65534) / 65535 * (3 + chans);
+        }
+        if (rowBytes == 0) bad(what, "PIC file whose packets carry no channel");
+        if (h > (f.size() - std::min(at, f.size())) / rowBytes) bad(what, "PIC file too short for its size");
+    }
     std::vector<unsigned char> rgba(static_cast<size_t>(w) * h * 4, 0xFF);
     auto read = [&](unsigned mask, unsigned char* dest) {
         for (int i = 0; i < 4; i++)
@@ -1066,19 +1130,60 @@ bool endsWith(const std::string& s, const char* suffix)
 
 } // namespace
 
-DecodedImage decodeImage(const std::vector<unsigned char>& f, const std::string& what)
+namespace {
+
+enum class Kind { Png, Jpeg, Gif, Psd, Pic, Hdr, Bmp, Pnm, Tga, Unknown };
+
+Kind kindOf(const std::vector<unsigned char>& f, const std::string& what)
 {
     static const unsigned char pngMagic[8] = { 0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A };
-    if (f.size() >= 8 && std::memcmp(f.data(), pngMagic, 8) == 0) return decodePng(f, what);
-    if (f.size() >= 3 && f[0] == 0xFF && f[1] == 0xD8 && f[2] == 0xFF) return decodeJpeg(f, what);
-    if (f.size() >= 6 && std::memcmp(f.data(), "GIF8", 4) == 0) return decodeGif(f, what);
-    if (f.size() >= 4 && std::memcmp(f.data(), "8BPS", 4) == 0) return decodePsd(f, what);
-    if (f.size() >= 4 && std::memcmp(f.data(), "\x53\x80\xF6\x34", 4) == 0) return decodePic(f, what);
-    if ((f.size() >= 11 && std::memcmp(f.data(), "#?RADIANCE\n", 11) == 0) || (f.size() >= 7 && std::memcmp(f.data(), "#?RGBE\n", 7) == 0)) return decodeHdr(f, what);
-    if (f.size() >= 2 && f[0] == 'B' && f[1] == 'M') return decodeBmp(f, what);
-    if (f.size() >= 2 && f[0] == 'P' && (f[1] == '5' || f[1] == '6')) return decodePnm(f, what);
-    if (endsWith(what, ".tga")) return decodeTga(f, what); // TGA has no magic number: by its name
+    if (f.size() >= 8 && std::memcmp(f.data(), pngMagic, 8) == 0) return Kind::Png;
+    if (f.size() >= 3 && f[0] == 0xFF && f[1] == 0xD8 && f[2] == 0xFF) return Kind::Jpeg;
+    if (f.size() >= 6 && std::memcmp(f.data(), "GIF8", 4) == 0) return Kind::Gif;
+    if (f.size() >= 4 && std::memcmp(f.data(), "8BPS", 4) == 0) return Kind::Psd;
+    if (f.size() >= 4 && std::memcmp(f.data(), "\x53\x80\xF6\x34", 4) == 0) return Kind::Pic;
+    if ((f.size() >= 11 && std::memcmp(f.data(), "#?RADIANCE\n", 11) == 0) || (f.size() >= 7 && std::memcmp(f.data(), "#?RGBE\n", 7) == 0)) return Kind::Hdr;
+    if (f.size() >= 2 && f[0] == 'B' && f[1] == 'M') return Kind::Bmp;
+    if (f.size() >= 2 && f[0] == 'P' && (f[1] == '5' || f[1] == '6')) return Kind::Pnm;
+    if (endsWith(what, ".tga")) return Kind::Tga; // TGA has no magic number: by its name
+    return Kind::Unknown;
+}
+
+} // namespace
+
+DecodedImage decodeImage(const std::vector<unsigned char>& f, const std::string& what)
+{
+    switch (kindOf(f, what)) {
+    case Kind::Png: return decodePng(f, what);
+    case Kind::Jpeg: return decodeJpeg(f, what);
+    case Kind::Gif: return decodeGif(f, what);
+    case Kind::Psd: return decodePsd(f, what);
+    case Kind::Pic: return decodePic(f, what);
+    case Kind::Hdr: return decodeHdr(f, what);
+    case Kind::Bmp: return decodeBmp(f, what);
+    case Kind::Pnm: return decodePnm(f, what);
+    case Kind::Tga: return decodeTga(f, what);
+    case Kind::Unknown: break;
+    }
     bad(what, "not a PNG, JPEG, GIF, BMP, TGA, PSD, Radiance HDR, Softimage PIC or binary PPM / PGM file");
+}
+
+size_t decodeHeapBound(const std::vector<unsigned char>& f, const std::string& what)
+{
+    size_t factor = 0;
+    switch (kindOf(f, what)) {
+    case Kind::Pnm: factor = 1; break;
+    case Kind::Bmp: factor = 24; break;
+    case Kind::Tga: factor = 258; break;
+    case Kind::Hdr: factor = 241; break;
+    case Kind::Psd: factor = 256; break;
+    case Kind::Pic: factor = 153000; break;
+    case Kind::Png: factor = 42400; break;
+    case Kind::Jpeg: factor = 26700; break;
+    case Kind::Gif: factor = 5 * kMaxGifTexelsPerByte; break;
+    case Kind::Unknown: break;
+    }
+    return kDecodeFixedBytes + factor * f.size();
 }
 
 } // namespace crt

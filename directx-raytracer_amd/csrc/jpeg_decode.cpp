@@ -310,10 +310,18 @@ struct Decoder {
             if (hMax % comp[i].h != 0 || vMax % comp[i].v != 0) bad(what, "sampling factors that are not whole ratios");
         mcusX = (width + 8 * hMax - 1) / (8 * hMax);
         mcusY = (height + 8 * vMax - 1) / (8 * vMax);
+        // nothing is allocated before the file is known to be able to hold the frame: every 8 x 8 block of every component costs at
+        // least the one bit of its DC code, in a sequential file and in the first DC scan of a progressive one
+        size_t blocks = 0;
         for (int i = 0; i < nComp; i++) {
             Component& c = comp[i];
             c.x = (width * c.h + hMax - 1) / hMax;
             c.y = (height * c.v + vMax - 1) / vMax;
+            blocks += static_cast<size_t>((c.x + 7) / 8) * static_cast<size_t>((c.y + 7) / 8);
+        }
+        if (blocks / 8 > f.size() - (at < f.size() ? at : f.size())) bad(what, "file too short for its frame size");
+        for (int i = 0; i < nComp; i++) {
+            Component& c = comp[i];
             c.blocksW = mcusX * c.h;
             c.blocksH = mcusY * c.v;
             c.coef.assign(static_cast<size_t>(c.blocksW) * c.blocksH * 64, 0);

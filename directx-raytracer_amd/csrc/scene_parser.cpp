@@ -35,14 +35,24 @@ Matrix matrixFrom(const Value& arr)
 
 float numberOr(const Value* v, float fallback) { return (v && v->isNumber()) ? static_cast<float>(v->num) : fallback; }
 
+// an integer key: truncated towards zero, held to the int range (a plain cast is undefined outside it), 0 when absent or no number
+int intOr0(const Value* v)
+{
+    const double d = (v && v->isNumber()) ? v->num : 0.0;
+    if (!(d == d)) return 0;
+    if (d >= 2147483647.0) return 2147483647;
+    if (d <= -2147483648.0) return -2147483647 - 1;
+    return static_cast<int>(d);
+}
+
 void readSettings(const Value& doc, Settings& st)
 {
     const Value* s = doc.find("settings");
     if (!s || !s->isObject()) return;
     if (const Value* bg = s->find("background_color")) st.backgroundColor = vectorAt(*bg, 0);
     if (const Value* img = s->find("image_settings")) {
-        if (const Value* w = img->find("width")) st.imageWidth = static_cast<int>(numberOr(w, 0.f));
-        if (const Value* h = img->find("height")) st.imageHeight = static_cast<int>(numberOr(h, 0.f));
+        if (const Value* w = img->find("width")) st.imageWidth = intOr0(w);
+        if (const Value* h = img->find("height")) st.imageHeight = intOr0(h);
     }
 }
 
@@ -72,7 +82,9 @@ void readMesh(const Value& o, Mesh& mesh)
         mesh.addIndex(static_cast<int>(d));
     }
     if (ni % 3 != 0) throw std::runtime_error("crtscene: 'triangles' length is not a multiple of 3");
-    mesh.setMaterialIndex(static_cast<int>(numberOr(o.find("material_index"), 0.f)));
+    // uvs go to the device one per vertex: any other count is a damaged file, not a mesh without uvs
+    if (!mesh.getUV().empty() && mesh.getUV().size() != nv) throw std::runtime_error("crtscene: 'uvs' does not hold one entry per vertex");
+    mesh.setMaterialIndex(intOr0(o.find("material_index")));
     mesh.calculateVertexNormals(); // R/CRTSceneParser.cpp:131
 }
 
@@ -356,7 +368,7 @@ void SceneParser::parseBinary(const std::string& bytes, Scene& scene)
         mesh.setMaterialIndex(r.pod<int32_t>());
         const uint64_t nv = r.pod<uint64_t>(), ni = r.pod<uint64_t>(), nn = r.pod<uint64_t>(), nu = r.pod<uint64_t>();
         const uint64_t remaining = static_cast<uint64_t>(r.end - r.p);
-        if (nv > remaining / 12 || ni > remaining / 4 || nn > remaining / 12 || nu > remaining / 12 || ni % 3 != 0 || (nn != 0 && nn != nv))
+        if (nv > remaining / 12 || ni > remaining / 4 || nn > remaining / 12 || nu > remaining / 12 || ni % 3 != 0 || (nn != 0 && nn != nv) || (nu != 0 && nu != nv))
             throw std::runtime_error("crtbin: inconsistent mesh header");
         std::vector<Vector> v(nv), nrm(nn), uv(nu);
         std::vector<int> idx(ni);

@@ -159,8 +159,12 @@ def main():
                 assert all(f32(c) == f32(f32(q) / f32(255.0)) for c, q in zip((r, g, b), rgb)), (name, iu, iv, r, g, b)
                 rows.append([iu, iv] + rgb)
         answers[name] = rows
+    # bitmap_known_answers.json is one line, so a fixture added to it would rewrite the whole file in a diff: it keeps the fixtures it
+    # has, and LATER_FIXTURES go to bitmap_known_answers_more.json, one fixture per line (a new one there is an added line)
     with open(os.path.join(gold, "bitmap_known_answers.json"), "w") as f:
-        json.dump(answers, f, separators=(",", ":"))
+        json.dump({n: r for n, r in answers.items() if n not in LATER_FIXTURES}, f, separators=(",", ":"))
+    with open(os.path.join(gold, "bitmap_known_answers_more.json"), "w") as f:
+        f.write("{\n" + ",\n".join(json.dumps(n) + ":" + json.dumps(answers[n], separators=(",", ":")) for n in LATER_FIXTURES) + "\n}\n")
     print("wrote", gold)
     return 0
 
@@ -233,6 +237,9 @@ def _png(w, h, depth, color, rows, level=9, strategy=None, interlace=False, pale
 ONE_CHANNEL = {"tex_grey8_stored.png": (9, 6), "tex_grey1.png": (13, 6), "tex_grey8.tga": (9, 6), "tex_grey.jpg": (21, 19),
                "tex_proggrey.jpg": (20, 21), "tex_max65535.pgm": (9, 6), "tex_grey2.png": (13, 6), "tex_grey4.png": (13, 6), "tex_grey16.png": (9, 6),
                "tex_grey4_adam7.png": (23, 19)}  # name -> (width, height)
+
+
+LATER_FIXTURES = ("tex_grey16_key_low_byte.png", "tex_rgb16_key_low_byte.png")  # answers in bitmap_known_answers_more.json
 
 
 def bitmap_fixtures():
@@ -606,6 +613,15 @@ def bitmap_fixtures():
     fx["tex_grey8_key.png"] = _png(w, h, 8, 0, [gk[y].astype(np.uint8).tobytes() for y in range(h)], trns=[0, 170])
     g16k = rng.integers(0, 3, (h, w)) * 30000
     fx["tex_grey16_key.png"] = _png(w, h, 16, 0, [g16k[y].astype(">u2").tobytes() for y in range(h)], trns=[0x75, 0x30])
+    # 16-bit colour keys are compared on the full samples: texels that ARE the key beside texels that share its high bytes and differ
+    # in a low byte (opaque, though their 8-bit reduction equals the key's) and texels of other high bytes
+    near_grey = np.array([0x7530, 0x7531, 0x75FF, 0x7500, 0x7430, 0xC000])
+    g16n = near_grey[rng.integers(0, len(near_grey), (h, w))]
+    fx["tex_grey16_key_low_byte.png"] = _png(w, h, 16, 0, [g16n[y].astype(">u2").tobytes() for y in range(h)], trns=[0x75, 0x30])
+    near_rgb = np.array([[0x1234, 0x5678, 0x9ABC], [0x1234, 0x5678, 0x9ABD], [0x1235, 0x5678, 0x9ABC], [0x1234, 0x56FF, 0x9ABC], [0x1334, 0x5678, 0x9ABC],
+                         [0xF000, 0x0F00, 0x00F0]])
+    c16n = near_rgb[rng.integers(0, len(near_rgb), (h, w))]
+    fx["tex_rgb16_key_low_byte.png"] = _png(w, h, 16, 2, [c16n[y].astype(">u2").tobytes() for y in range(h)], trns=[0x12, 0x34, 0x56, 0x78, 0x9A, 0xBC])
     return fx
 
 

@@ -267,7 +267,8 @@ def test_bitmap_formats_match_the_reference(pkg, golden_dir):
     (R/CRTTextureBitmap.cpp:10); this repo with its own decoders (csrc/image_decode.cpp: PNG with its own inflate, BMP, TGA;
     csrc/jpeg_decode.cpp).  Known answers: the reference's CRTTextureBitmap::getColor over the same seeded files
     (oracle/make_golden.py), bit for bit -- PNG in every colour type (grey, grey + alpha, RGB, RGBA, palette with and without
-    tRNS; colour-key tRNS on grey and RGB files, which adds an alpha channel) at every bit depth each allows (1 / 2 / 4 / 8 / 16,
+    tRNS; colour-key tRNS on grey and RGB files, which adds an alpha channel -- 16-bit keys also beside texels that differ from
+    the key in a low byte only and stay opaque) at every bit depth each allows (1 / 2 / 4 / 8 / 16,
     Adam7 also below 8 bits), all five scanline filters, stored / fixed / dynamic deflate blocks, several IDAT chunks, Adam7;
     BMP 24 / 32 bit / palette / top-down; TGA raw and run-length coded, colour and grey; JPEG baseline and progressive (also
     with optimised Huffman tables), 4:4:4 / 4:2:2 / 4:2:0 / 4:1:1, grey, Adobe CMYK, restart intervals, quality 10, and images one
@@ -281,7 +282,12 @@ def test_bitmap_formats_match_the_reference(pkg, golden_dir):
     colour, grey + alpha, the ignored right-to-left bit; PNM with maxima of 100, 1000 and 65535.
     With these every format (and every variant of it) the reference's loader accepts is read here."""
     answers = json.load(open(os.path.join(golden_dir, "bitmap_known_answers.json")))
-    assert len(answers) >= 72 and all(sum(n.endswith(e) for n in answers) >= k for e, k in ((".jpg", 14), (".gif", 6), (".hdr", 3), (".psd", 3), (".pic", 3), (".bmp", 10), (".tga", 8), (".png", 22)))
+    later = json.load(open(os.path.join(golden_dir, "bitmap_known_answers_more.json")))  # fixtures added since, one per line
+    assert len(answers) >= 72 and not set(answers) & set(later)
+    answers.update(later)
+    assert len(answers) >= 74 and all(sum(n.endswith(e) for n in answers) >= k for e, k in ((".jpg", 14), (".gif", 6), (".hdr", 3), (".psd", 3), (".pic", 3), (".bmp", 10), (".tga", 8), (".png", 24)))
+    # a 16-bit colour key is compared on the full samples: these two hold texels that share the key's high bytes alone
+    assert "tex_grey16_key_low_byte.png" in answers and "tex_rgb16_key_low_byte.png" in answers
     f32 = np.float32
     for name, rows in sorted(answers.items()):
         s = pkg.Scene()
@@ -352,6 +358,30 @@ def test_damaged_bitmap_files_are_errors_not_crashes(pkg, golden_dir, tmp_path):
     arith.write_bytes(b"\xff\xd8\xff\xc9\x00\x0b\x08\x00\x04\x00\x04\x01\x01\x11\x00\xff\xd9")
     with pytest.raises(pkg.CrtError):
         pkg.Scene().add_texture("b", "bitmap", file_path=str(arith))
+    # headers that name more than their file holds (tests/fuzz_readers.cpp runs the same under sanitizers and a heap bound): sizes past
+    # the texel cap, products that wrap 64 bits, images of gigabytes on files of a few bytes -- errors, not allocations or nonsense
+    import struct
+    import zlib
+
+    def png(w, h, depth, color, idat):
+        def chunk(t, d):
+            return struct.pack(">I", len(d)) + t + d + struct.pack(">I", zlib.crc32(t + d) & 0xFFFFFFFF)
+        return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, depth, color, 0, 0, 0)) + chunk(b"IDAT", idat) + chunk(b"IEND", b"")
+
+    tga_head = lambda w, h, bpp: struct.pack("<BBBHHBHHHHBB", 0, 0, 2, 0, 0, 0, 0, 0, w, h, bpp, 0)
+    oversized = (("huge.tga", tga_head(65535, 65535, 32)),
+                 ("nodata.tga", tga_head(4096, 4096, 24)),
+                 ("wrap.pgm", b"P5 8589934592 2147483648 255\n"),
+                 ("cap.ppm", b"P6 65536 65536 255\n"),
+                 ("wrap.png", png(3688618971, 3688562688, 8, 2, zlib.compress(b""))),
+                 ("empty_idat.png", png(16384, 16384, 16, 6, b"")),
+                 ("empty_stream.png", png(16384, 16384, 16, 6, zlib.compress(b""))))
+    assert len(tga_head(1, 1, 8)) == 18
+    for name, blob in oversized:
+        path = tmp_path / name
+        path.write_bytes(blob)
+        with pytest.raises(pkg.CrtError):
+            pkg.Scene().add_texture("b", "bitmap", file_path=str(path))
 
 
 def test_textured_scene_file(pkg, tmp_path, golden_dir):
