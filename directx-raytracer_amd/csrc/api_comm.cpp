@@ -239,7 +239,8 @@ int crt_comm_info(const crt_ctx* c, uint32_t* rank, uint32_t* n_ranks)
 
 int crt_render_frame_distributed(crt_ctx* c, uint32_t w, uint32_t h, void* d_rgba8, uint8_t* host_rgba8, crt_frame_stats* stats)
 {
-    int rc = checkRenderable(c, w, h);
+    int rc = refuseWhitted(c, "crt_render_frame_distributed");
+    if (rc == CRT_OK) rc = checkRenderable(c, w, h);
     if (rc) return rc;
     if (!c->dist.comm && !c->dist.hostComm) return fail(c, CRT_ESTATE, "crt_render_frame_distributed: no communicator (crt_comm_init first)");
     const auto t0 = std::chrono::steady_clock::now();

@@ -20,6 +20,14 @@ void dropOrders(crt_ctx* c)
     for (crt_ctx::FrameSlot& s : c->frames.slot) s.orderKey = 0;
 }
 
+// the tile, batch and distributed entry points render shares of the render kernel's work: the Whitted query kind has none.
+// Checked before anything else of the call (a NULL context is the caller's next check)
+int refuseWhitted(crt_ctx* c, const char* what)
+{
+    if (!c || !whittedMode(c)) return CRT_OK;
+    return fail(c, CRT_EINVAL, "%s: shading mode %u (Whitted) renders whole frames only (crt_render_frame*): set another mode", what, c->mode);
+}
+
 } // namespace crtapi
 
 namespace {
@@ -395,9 +403,21 @@ int runAccumResolve(crt_ctx* c, const RenderParams& p, crt_frame_stats* stats)
     return stats ? readStats(c, stats) : CRT_OK;
 }
 
+// A frame in mode 150 (CRT_MODE_WHITTED) is a query, not a launch of the render kernel: the pixel-centre camera rays, the Whitted
+// query kind over them and the quantisation of its float colour (runWhitted, api_queries.cpp), on the stream's query arena.
+// Nothing of runRender runs: the frame ring, the launch orders and their cost state stay as they are.
+int runWhittedFrame(crt_ctx* c, const RenderParams& p, crt_frame_stats* stats)
+{
+    if (const int rc = checkFrameSize(c, "a frame in shading mode 150", p.width, p.height)) return rc; // (the camera-ray kernel's limit)
+    void* const out[7] = { p.rgb_f32, nullptr, nullptr, p.hit_t, nullptr, p.hit_inst, p.hit_prim };
+    const WhittedFrame frame = { p.width, p.height, p.rgba8 };
+    return runWhitted(c, p.width * p.height, nullptr, out, &frame, stats);
+}
+
 // one frame of an entry point that accumulates (kind: kAccFrame / kAccTiles)
 int runFrame(crt_ctx* c, RenderParams& p, crt_frame_stats* stats, uint32_t kind)
 {
+    if (p.mode == CRT_MODE_WHITTED) return runWhittedFrame(c, p, stats);
     const int rc = beginAccum(c, p, kind);
     if (rc) return rc;
     return p.acc_sum && p.spp == 0u ? runAccumResolve(c, p, stats) : runRender(c, p, stats);
@@ -496,7 +516,8 @@ uint32_t crt_tile_slots(uint32_t w, uint32_t h, uint32_t n_ranks)
 
 int crt_render_tiles_device(crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_t n_ranks, void* d_staging, crt_frame_stats* stats)
 {
-    int rc = checkRenderable(c, w, h);
+    int rc = refuseWhitted(c, "crt_render_tiles_device");
+    if (rc == CRT_OK) rc = checkRenderable(c, w, h);
     if (rc) return rc;
     if (!d_staging || n_ranks == 0 || rank >= n_ranks) return fail(c, CRT_EINVAL, "bad tile arguments (rank %u of %u)", rank, n_ranks);
     const auto t0 = std::chrono::steady_clock::now();
@@ -515,7 +536,8 @@ namespace {
 int runBatch(crt_ctx* c, uint32_t w, uint32_t h, uint32_t rank, uint32_t n_ranks, bool staging, uint32_t n_frames, const float* cameras,
              void* const* d_out, crt_frame_stats* stats)
 {
-    int rc = checkRenderable(c, w, h);
+    int rc = refuseWhitted(c, staging ? "crt_render_tiles_batch_device" : "crt_render_frames_batch_device");
+    if (rc == CRT_OK) rc = checkRenderable(c, w, h);
     if (rc) return rc;
     if (n_frames == 0 || n_frames > static_cast<uint32_t>(crt::kMaxBatch)) return fail(c, CRT_EINVAL, "n_frames %u outside [1,%d]", n_frames, crt::kMaxBatch);
     if (!d_out || n_ranks == 0 || rank >= n_ranks) return fail(c, CRT_EINVAL, "bad batch arguments (rank %u of %u)", rank, n_ranks);

@@ -13,7 +13,8 @@ using namespace crtapi;
 
 namespace {
 
-// the scene's shading tables as the shaded and the path-traced query take them (crt::ShadeQueryParams, crt::PathQueryParams)
+// the scene's shading tables as the shaded, the path-traced and the Whitted query take them (crt::ShadeQueryParams,
+// crt::PathQueryParams, crt::WhittedQueryParams)
 template <class Q> void sceneTables(const crt_ctx* c, Q& q)
 {
     q.shade = c->dShade; // as fillParams
@@ -49,6 +50,7 @@ union QueryParams {
     crt::PointQueryParams point;
     crt::WindingQueryParams winding;
     crt::ShadeQueryParams shade;
+    crt::WhittedQueryParams whitted;
 };
 using QueryFill = int (*)(crt_ctx* c, const QuerySpec& s, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin);
 
@@ -100,7 +102,13 @@ void crtapi::shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q)
     q.phong_exp = c->phongExp;
 }
 
+// crt_shade_rays* and the frames in mode 150: whether the context's mode asks for the Whitted kind (101..149 and 151..199 are mode 100)
+bool crtapi::whittedMode(const crt_ctx* c) { return c->mode == CRT_MODE_WHITTED; }
+
 namespace {
+
+// the kinds of crt_shade_rays*: the context's mode is checked, and the refit follows the argument checks
+bool shadedKind(QueryKind kind) { return kind == crt::kQueryShade || kind == crt::kQueryWhitted; }
 
 int fillClosestHit(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
 {
@@ -154,6 +162,24 @@ int fillShade(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryP
     innerMin = c->tuneInnerMin;
     return CRT_OK;
 }
+// crt_shade_rays* in mode 150 (whitted_kernels.hip): the outputs of fillShade; the record state comes from the launch's arena (runWhitted)
+int fillWhitted(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
+{
+    crt::WhittedQueryParams& q = p.whitted;
+    q.rgb = static_cast<float*>(d[0]);
+    q.normal = static_cast<float*>(d[1]);
+    q.albedo = static_cast<float*>(d[2]);
+    q.t = static_cast<float*>(d[3]);
+    q.uv = static_cast<float*>(d[4]);
+    q.inst = static_cast<uint32_t*>(d[5]);
+    q.prim = static_cast<uint32_t*>(d[6]);
+    sceneTables(c, q);
+    q.max_bounces = c->pathBounces;
+    q.phong_ks = static_cast<float>(c->phongKsPermille) / 1000.0f;
+    q.phong_exp = c->phongExp;
+    innerMin = c->tuneInnerMin;
+    return CRT_OK;
+}
 // crt_winding_numbers*: the walk over the tree and its moment table (winding_kernels.hip)
 int fillWinding(crt_ctx* c, const QuerySpec& s, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
 {
@@ -188,6 +214,8 @@ const QueryShape kQueryShapes[crt::kQueryKinds] = {
     { 32u, "rgb / normal / albedo / t / uv / inst / prim", { { 12u, 4u }, { 12u, 4u }, { 12u, 4u }, { 4u, 4u }, { 8u, 8u }, { 4u, 4u }, { 4u, 4u } }, fillShade },
     /* kQueryPath */ {},
     /* kQueryWinding */ { 16u, "w", { { 4u, 4u } }, fillWinding },
+    /* kQueryWhitted */
+    { 32u, "rgb / normal / albedo / t / uv / inst / prim", { { 12u, 4u }, { 12u, 4u }, { 12u, 4u }, { 4u, 4u }, { 8u, 8u }, { 4u, 4u }, { 4u, 4u } }, fillWhitted },
 };
 
 // what every query entry point checks before anything is launched.  A shaded query (crt_shade_rays*) promises that a failed
@@ -197,7 +225,7 @@ int checkQuery(crt_ctx* c, const QuerySpec& s)
     const char* what = s.what;
     if (!c) return fail(nullptr, CRT_EINVAL, "%s: NULL context", what);
     if (!c->haveScene) return fail(c, CRT_ESTATE, "%s: no scene uploaded: call crt_upload_scene first", what);
-    if (s.kind == crt::kQueryShade) {
+    if (shadedKind(s.kind)) {
         if (c->mode >= 200u)
             return fail(c, CRT_EINVAL, "%s: shading mode %u (path tracing) is not available for caller-supplied rays: set a mode below 200", what, c->mode);
         return CRT_OK;
@@ -276,8 +304,8 @@ int crtapi::endQuery(crt_ctx* c, QueryKind kind, uint32_t n, const QueryLaunch& 
     if (const int rs = readStats(c, stats, ql.counters, words)) return rs;
     if (kind == crt::kQueryOcclusion) stats->rays_shadow = n;
     else stats->rays_primary = kind == crt::kQueryOccupancy ? 3ull * n : n;
-    if (c->counting && (kind == crt::kQueryShade || kind == crt::kQueryPath)) stats->rays_shadow = words[2]; // the shadow rays traced (mode 100; paths)
-    if (kind == crt::kQueryPath) stats->rays_primary += words[3];                                      // the bounce rays of the paths
+    if (c->counting && (shadedKind(kind) || kind == crt::kQueryPath)) stats->rays_shadow = words[2];   // the shadow rays traced (modes 100, 150; paths)
+    if (kind == crt::kQueryPath || kind == crt::kQueryWhitted) stats->rays_primary += words[3];        // the bounce rays of the paths, the turns of mode 150
     return CRT_OK;
 }
 
@@ -300,11 +328,61 @@ crt::QueryCommon crtapi::queryCommon(const crt_ctx* c, const QueryLaunch& ql, co
     return q;
 }
 
+// A Whitted query of n records into the outputs d (fillWhitted's order), over one arena between one beginQuery and one endQuery.
+// The arena holds the records' state (kWhittedStateBytes each), so a launch covers at most "path_pass_paths" records, as a pass of
+// crt_path_rays* does; a larger buffer runs as several launches over blocks of records.
+// frame (crt_render_frame* in mode 150): d_records is NULL and the records are the frame's pixel-centre camera rays, made in
+// the arena by the camera-ray kernel, all in one launch; behind the query the float colour (d[0], or scratch of the arena when
+// the caller wants none) is quantised into frame->rgba8.  The other frame outputs are the query's own, bit for bit: hit_t is
+// t (on a miss the record's tmax, which is the frames' 10000), hit_inst / hit_prim are inst / prim.
+int crtapi::runWhitted(crt_ctx* c, uint32_t n, const void* d_records, void* const d[7], const WhittedFrame* frame, crt_frame_stats* stats)
+{
+    static_assert(kQueryOutputs == 7, "the outputs of crt_shade_rays*");
+    QueryParams p;
+    std::memset(&p, 0, sizeof(p));
+    uint32_t innerMin = 0;
+    if (const int rc = fillWhitted(c, QuerySpec{}, d, p, innerMin)) return rc;
+    crt::WhittedQueryParams& q = p.whitted;
+    const uint32_t block = frame ? n : std::min(n, c->tunePathPassPaths);
+    const size_t stateBytes = up256(static_cast<size_t>(block) * crt::kWhittedStateBytes);
+    const size_t rayBytes = frame ? up256(static_cast<size_t>(n) * 32u) : 0u, rgbBytes = frame && !q.rgb ? up256(static_cast<size_t>(n) * 12u) : 0u;
+    QueryLaunch ql;
+    if (const int rc = beginQuery(c, crt::kQueryWhitted, block, stats, ql, stateBytes + rayBytes + rgbBytes)) return rc;
+    q.state = ql.extra;
+    int hrc = 0;
+    if (frame) {
+        d_records = ql.extra + stateBytes;
+        if (!q.rgb) q.rgb = reinterpret_cast<float*>(ql.extra + stateBytes + rayBytes);
+        hrc = crt::launchCameraRays(cameraRayParams(c, frame->width, frame->height, CRT_SAMPLE_CENTRE, ql.extra + stateBytes), c->stream);
+    }
+    const crt::WhittedQueryParams all = q; // the outputs of record 0
+    for (uint64_t r0 = 0; r0 < n && hrc == 0; r0 += block) {
+        const uint32_t nr = static_cast<uint32_t>(std::min<uint64_t>(block, n - r0));
+        if (r0 != 0u) HIP_TRY(c, hipMemsetAsync(ql.cursor, 0, sizeof(uint32_t), c->stream)); // (the counters go on counting)
+        uint32_t chunk = 0, grid = 0;
+        crt::queryLayout(nr, c->queries.resident[crt::kQueryWhitted], chunk, grid);
+        grid = std::min(grid, ql.grid); // (the spill area is sized for ql.grid workgroups, the largest block's)
+        q.c = queryCommon(c, ql, static_cast<const unsigned char*>(d_records) + 32u * r0, nr, innerMin);
+        q.c.chunk = chunk;
+        q.rgb = all.rgb ? all.rgb + 3u * r0 : nullptr;
+        q.normal = all.normal ? all.normal + 3u * r0 : nullptr;
+        q.albedo = all.albedo ? all.albedo + 3u * r0 : nullptr;
+        q.t = all.t ? all.t + r0 : nullptr;
+        q.uv = all.uv ? all.uv + 2u * r0 : nullptr;
+        q.inst = all.inst ? all.inst + r0 : nullptr;
+        q.prim = all.prim ? all.prim + r0 : nullptr;
+        hrc = crt::launchQuery(crt::kQueryWhitted, &q, c->counting, grid, c->stream);
+    }
+    if (frame && hrc == 0) hrc = crt::launchWhittedPack(all.rgb, frame->rgba8, n, c->stream);
+    return endQuery(c, crt::kQueryWhitted, n, ql, hrc, stats);
+}
+
 namespace {
 
 // a query of any kind with an entry point: its fill, then one launch between beginQuery and endQuery
 int runKind(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, void* const d[kQueryOutputs], crt_frame_stats* stats)
 {
+    if (s.kind == crt::kQueryWhitted) return runWhitted(c, n, d_records, d, nullptr, stats);
     QueryParams p;
     std::memset(&p, 0, sizeof(p));
     uint32_t innerMin = 0;
@@ -325,7 +403,7 @@ int queryDevice(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_record
         return CRT_OK;
     }
     if ((rc = checkDeviceOutputs(c, s, d_records)) != CRT_OK) return rc;
-    if (s.kind == crt::kQueryShade && (rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    if (shadedKind(s.kind) && (rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
     if ((rc = runKind(c, s, n, d_records, s.out, stats)) != CRT_OK) return rc;
     stampTotal(stats, t0);
     return CRT_OK;
@@ -343,7 +421,7 @@ int queryHost(crt_ctx* c, const QuerySpec& s, uint32_t n, const float* records, 
     }
     if (!records) return fail(c, CRT_EINVAL, "%s: record buffer is NULL", s.what);
     if ((rc = checkOutputs(c, s)) != CRT_OK) return rc;
-    if (s.kind == crt::kQueryShade && (rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
+    if (shadedKind(s.kind) && (rc = applyRefit(c, nullptr)) != CRT_OK) return rc;
     constexpr int kPlanes = 1 + kQueryOutputs;
     const QueryShape& shape = kQueryShapes[s.kind];
     StagePlane planes[kPlanes] = { { records, nullptr, static_cast<size_t>(n) * shape.recordBytes } };
@@ -575,13 +653,13 @@ int crt_occluded_rays(crt_ctx* c, uint32_t n, const float* rays, uint8_t* occlud
 int crt_shade_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_rgb, void* d_normal, void* d_albedo, void* d_t, void* d_uv,
                           void* d_inst, void* d_prim, crt_frame_stats* stats)
 {
-    return queryDevice(c, { "crt_shade_rays_device", crt::kQueryShade, { d_rgb, d_normal, d_albedo, d_t, d_uv, d_inst, d_prim } }, n, d_rays, stats);
+    return queryDevice(c, { "crt_shade_rays_device", c && whittedMode(c) ? crt::kQueryWhitted : crt::kQueryShade, { d_rgb, d_normal, d_albedo, d_t, d_uv, d_inst, d_prim } }, n, d_rays, stats);
 }
 
 int crt_shade_rays(crt_ctx* c, uint32_t n, const float* rays, float* rgb, float* normal, float* albedo, float* t, float* uv, uint32_t* inst,
                    uint32_t* prim, crt_frame_stats* stats)
 {
-    return queryHost(c, { "crt_shade_rays", crt::kQueryShade, { rgb, normal, albedo, t, uv, inst, prim } }, n, rays, stats);
+    return queryHost(c, { "crt_shade_rays", c && whittedMode(c) ? crt::kQueryWhitted : crt::kQueryShade, { rgb, normal, albedo, t, uv, inst, prim } }, n, rays, stats);
 }
 
 int crt_path_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, const void* d_ids, uint32_t first_sample, uint32_t n_samples, void* d_rgb,

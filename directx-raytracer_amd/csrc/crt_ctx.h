@@ -1,7 +1,7 @@
 // Internal to the C-ABI layer (host C++ only): the renderer context and what more than one of the layer's units uses.
 //   crt_api.cpp      context, streams, options, scene upload, tree exports; defines the shared helpers declared here
 //   api_frames.cpp   the per-frame path: runRender, launch-order feedback, accumulation, frame / tile / batch entry points
-//   api_queries.cpp  ray, point, shaded, path and listing queries
+//   api_queries.cpp  ray, point, shaded, Whitted, path and listing queries
 //   api_image.cpp    camera rays, frame guides, the a-trous filters, temporal reprojection and variance
 //   api_dynamic.cpp  vertex updates, transforms, refit / rebuild, motion, gradients
 //   api_comm.cpp     RCCL gather and the host-memory exchange
@@ -218,8 +218,8 @@ struct crt_ctx {
 
     // batched ray and point queries (crt_trace_rays* / crt_occluded_rays*, crt_closest_points* / crt_count_hits* /
     // crt_occupancy*): per arena the launch's cursor, counters and the stack spill arena of the persistent query kernel.  Arenas
-    // of this pool belong to queries alone (never to a frame); serial = ++raySerial.  (Flat: the a-trous filter of api_image.cpp
-    // takes its planes from this pool too)
+    // of this pool belong to queries alone (never to a frame of runRender; a mode-150 frame is a query); serial = ++raySerial.
+    // (Flat: the a-trous filter of api_image.cpp takes its planes from this pool too)
     Arena rayArena[kRing];
     uint32_t raySerial = 0;
     void* dRayStage = nullptr; // the host entry points' records and outputs, grown on demand
@@ -304,9 +304,10 @@ int stageBegin(crt_ctx* c, const StagePlane* planes, int n, void** dev);
 int stageDownload(crt_ctx* c, const StagePlane* planes, int n, void* const* dev);
 int stageEnd(crt_ctx* c, const StagePlane* planes, int n, void* const* dev);
 
-// the scene and its tree (crt_api.cpp; dropOrders: api_frames.cpp)
+// the scene and its tree (crt_api.cpp; dropOrders and refuseWhitted: api_frames.cpp)
 void freeScene(crt_ctx* c);
 void dropOrders(crt_ctx* c);
+int refuseWhitted(crt_ctx* c, const char* what);
 int readSceneBox(crt_ctx* c);
 void adoptTree(crt_ctx* c, crt::DeviceTree&& t);
 int reserveRefitCapacity(crt_ctx* c);
@@ -323,6 +324,12 @@ int checkFrameSize(crt_ctx* c, const char* what, uint32_t w, uint32_t h);
 int checkDevicePointers(crt_ctx* c, const char* what, std::initializer_list<const void*> ptrs, uintptr_t align);
 // api_queries.cpp
 void shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q);
+bool whittedMode(const crt_ctx* c);
+struct WhittedFrame {
+    uint32_t width, height;
+    uint32_t* rgba8;
+};
+int runWhitted(crt_ctx* c, uint32_t n, const void* d_records, void* const d[7], const WhittedFrame* frame, crt_frame_stats* stats);
 int beginQuery(crt_ctx* c, crt::QueryKind kind, uint32_t n, crt_frame_stats* stats, QueryLaunch& ql, size_t extraBytes = 0,
                uint32_t minGrid = 0);
 int endQuery(crt_ctx* c, crt::QueryKind kind, uint32_t n, const QueryLaunch& ql, int rc, crt_frame_stats* stats);

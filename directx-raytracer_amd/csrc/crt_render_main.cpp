@@ -35,7 +35,9 @@ static void usage()
                  "       [--path FILE]   one line per frame, commands separated by ';':\n"
                  "                       rotate YAW PITCH | forward D | right D | zoom A | pan DEG | tilt DEG | roll DEG | mode M\n"
                  "   [--mode-at FRAME:MODE]...  switch the shading mode from that frame on\n"
-                 "   [--spp N] [--bounces N] [--seed N]   mode 200 (path tracing)\n"
+                 "       modes: 0..6 the reference's, 100 Lambert / Phong with shadow rays, 150 Whitted (mode 100 seen through mirrors and\n"
+                 "       glass, at most --bounces turns; one rank only: not with --ranks / --rank), 200 path tracing\n"
+                 "   [--spp N] [--bounces N] [--seed N]   mode 200 (path tracing); --bounces also limits the turns of mode 150\n"
                  "   [--accumulate MAX]   mode 200: frames add their samples to running per-pixel sums (up to MAX samples) while the\n"
                  "                        camera holds still and start over when it moves; each frame written is the running mean;\n"
                  "                        with --ranks every rank accumulates its own tiles\n"
@@ -320,6 +322,14 @@ int main(int argc, char** argv)
     if (a.denoise && (a.ranks > 0 || a.denoiseIterations < 1 || a.denoiseIterations > 8)) { usage(); return 2; }
     if (a.temporal && (a.ranks > 0 || a.mode != 200u || !a.modeAt.empty() || !(a.temporalAlpha >= 0.0f && a.temporalAlpha <= 1.0f))) { usage(); return 2; }
     if (a.variance && !a.temporal) { usage(); return 2; }
+    if (a.ranks > 0 || a.rank >= 0) { // the Whitted mode renders whole frames only: the tile entry points refuse it
+        bool whitted = a.mode == CRT_MODE_WHITTED;
+        for (const auto& sw : a.modeAt) whitted = whitted || sw.second == CRT_MODE_WHITTED;
+        if (whitted) {
+            std::fprintf(stderr, "crt_render: shading mode %u (Whitted) is not available with --ranks / --rank: it renders on one rank only\n", CRT_MODE_WHITTED);
+            return 2;
+        }
+    }
     try {
         if (a.ranks > 0 && a.rank < 0) return launchRanks(a, argc, argv);
         if (a.ranks > 0 && (a.rank >= a.ranks || a.idFile.empty())) { usage(); return 2; }

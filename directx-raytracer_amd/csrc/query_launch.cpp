@@ -37,7 +37,8 @@ const QueryKernel& queryKernel(QueryKind kind)
 {
     static const QueryKernel* const kernels[kQueryKinds] = { &kKernelClosestHit, &kKernelOcclusion, &kKernelClosestPoint,
                                                              &kKernelCount,      &kKernelOccupancy, &kKernelListFill,
-                                                             &kKernelShade,      &kKernelPath,      &kKernelWinding };
+                                                             &kKernelShade,      &kKernelPath,      &kKernelWinding,
+                                                             &kKernelWhitted };
     return *kernels[kind];
 }
 

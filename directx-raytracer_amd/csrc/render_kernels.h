@@ -159,7 +159,7 @@ struct QueryCommon {
 enum QueryKind { kQueryClosestHit = 0, kQueryOcclusion = 1, kQueryClosestPoint = 2, kQueryCount = 3, kQueryOccupancy = 4,
                  kQueryListFill = 5 /* the second traversal of crt_list_hits*: a kernel of its own, not an entry point */,
                  kQueryShade = 6, kQueryPath = 7 /* crt_path_rays*: passes of (record, sample) items */, kQueryWinding = 8,
-                 kQueryKinds };
+                 kQueryWhitted = 9 /* crt_shade_rays* and the frames in mode 150 */, kQueryKinds };
 // What the host knows of a kind's kernel: the host stubs of its two instantiations and the ints per stack entry (the
 // closest-point stack keeps each entry's box bound beside its reference: 2; every other kind: 1).  Stated by the file that
 // defines the kernel and never written again.  (Not const: hipcc would emit a const row into the device code object too.)
@@ -174,6 +174,7 @@ extern QueryKernel kKernelListFill;                                     // list_
 extern QueryKernel kKernelShade;                                        // shade_kernels.hip
 extern QueryKernel kKernelPath;                                         // path_query_kernels.hip
 extern QueryKernel kKernelWinding;                                      // winding_kernels.hip
+extern QueryKernel kKernelWhitted;                                      // whitted_kernels.hip
 // The rest is query_launch.cpp.  The kind's row
 const QueryKernel& queryKernel(QueryKind kind);
 // workgroups of the kind's kernel the current device holds at once with `stack_entries` of LDS stack per lane (0: unknown)
@@ -246,6 +247,37 @@ struct PathQueryParams {
     uint32_t* inst;
     uint32_t* prim;
 };
+// Whitted ray queries (whitted_kernels.hip; crt_shade_rays* and the frames in mode 150): the closest hit of n ray records
+// followed through mirrors and glass (the specular chain of PathQueryParams' paths, at most max_bounces turns), then mode 100's
+// shading at the first surface that is neither.  The outputs are ShadeQueryParams'; every one is nullable
+struct WhittedQueryParams {
+    QueryCommon c;                // records: the rays; inner_min: tune_inner_min (the closest-hit phases)
+    uint32_t inner_min_any;       // tune_inner_min_any (the shadow-ray phases)
+    // the scene's shading tables, as RenderParams'
+    const void* shade;
+    const void* lights;
+    const void* mats;
+    const void* uvs;
+    const void* textures;
+    const unsigned char* texels;
+    uint32_t n_textures, n_lights, n_mats;
+    float miss[3];
+    uint32_t max_bounces;         // turns a record may take
+    float phong_ks;
+    uint32_t phong_exp;
+    void* state;                  // scratch, kWhittedStateBytes per record: what is touched once per surface -- {T.rgb, k} and
+                                  // Phong's view vector
+    float* rgb;                   // as ShadeQueryParams'
+    float* normal;
+    float* albedo;
+    float* t;
+    float* uv;
+    uint32_t* inst;
+    uint32_t* prim;
+};
+constexpr size_t kWhittedStateBytes = 32; // two float4
+// a mode-150 frame's RGBA8 from its float colour (3 floats per pixel), the frames' unorm8 rule: n pixels
+int launchWhittedPack(const float* rgb, uint32_t* rgba8, uint32_t n, ihipStream_t* stream);
 // rad[sample * n_records + record] of n_samples samples added in sample order to `in` (3 float64 per record; NULL: zero);
 // the sums go to `out`, their mean over `total` samples to rgb (each nullable)
 int launchPathResolve(const void* rad, uint32_t n_records, uint32_t n_samples, const double* in, double* out, float* rgb, uint32_t total,

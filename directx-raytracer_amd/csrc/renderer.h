@@ -56,8 +56,9 @@ public:
     };
     void traceRays(const float* rays, size_t n, RayHit* out);
     void occluded(const float* rays, size_t n, uint8_t* out); // 1 = some triangle lies in (tmin, tmax)
-    // the closest hit shaded in the current mode (crt_shade_rays, synchronous; modes 0..100): colour, shading normal and albedo
-    // beside the hit.  A miss reports the miss colour, a zero normal and a zero albedo.
+    // the closest hit shaded in the current mode (crt_shade_rays, synchronous; modes 0..100, and 150: the colour seen through
+    // mirrors and glass, CRT_MODE_WHITTED): colour, shading normal and albedo beside the hit.  A miss reports the miss colour, a
+    // zero normal and a zero albedo.
     struct ShadedHit {
         float rgb[3], normal[3], albedo[3];
         RayHit hit;

@@ -49,6 +49,10 @@ enum {
 #define CRT_MODE_CHECKER 6u
 #define CRT_MODE_LAMBERT 100u /* Lambert (+ optional Phong highlight, options "phong_ks" / "phong_exponent") + one shadow ray per light
                                  (BASELINE.json north_star: "Lambert/Phong shading") */
+#define CRT_MODE_WHITTED 150u /* mode 100 seen through mirrors and glass: REFLECTIVE and REFRACTIVE surfaces are followed as mode 200
+                                 follows them (no Fresnel split, no random numbers, no samples), at most option "max_bounces" turns,
+                                 and mode 100 shades the first surface that is neither; the contract is below ("Whitted shading").
+                                 101..149 and 151..199 behave as 100, every mode >= 200 as 200 */
 #define CRT_MODE_PATH 200u    /* path tracing: options "spp" (default 4), "max_bounces" (3), "seed" (1234); BASELINE.json configs[4] */
 
 /* ---- geometry handed over at upload: exactly what createVertexBuffers / createIndexBuffers memcpy ----
@@ -233,7 +237,7 @@ int crt_render_frame_distributed(crt_ctx* ctx, uint32_t width, uint32_t height, 
  * "gpu_build" 0/1: acceleration structure built on the GPU at the next crt_upload_scene.  "gpu_builder" picks the GPU builder for
  * those uploads and for crt_rebuild: 0 = LBVH (the default), 1 = PLOC (closer to the SAH tree in quality, slower to build); other
  * values -> CRT_EINVAL.  It has no effect on host SAH uploads.
- * Rendering parameters of mode 200: "spp", "max_bounces", "seed". Tuning knobs (speed only, results never
+ * Rendering parameters of mode 200: "spp", "max_bounces", "seed" ("max_bounces" also limits the turns of mode 150). Tuning knobs (speed only, results never
  * change): "inner_min" / "inner_min_any" wave scheduling of the closest-hit / any-hit traversal loops (1..65: node steps while that
  * many lanes stand on inner nodes; -1..-8: while that many eighths of the wavefront's live lanes do; default -6), "xcd_group", "adaptive_order" (launch the most expensive 8x8
  * packets of the previous frame first: 0 never, 1 always, 2 = default: only for a frame issued on the same stream as the frame
@@ -432,7 +436,7 @@ int crt_occluded_rays(crt_ctx* ctx, uint32_t n, const float* rays, uint8_t* occl
  *   outputs must be non-NULL.
  * - Mode: the context's current shading mode (crt_set_shading_mode) applies.  Modes 0..99 are the seven reference modes
  *   (7..99 behave as 6, as in the frames); mode 100 is Lambert with optional Phong (options "phong_ks", "phong_exponent") and
- *   one shadow ray per light.  Mode 200 returns CRT_EINVAL and launches nothing: path tracing of caller rays would need a
+ *   one shadow ray per light (101..199 behave as 100, except 150: "Whitted shading" below).  Mode 200 returns CRT_EINVAL and launches nothing: path tracing of caller rays would need a
  *   sample-indexing contract of its own (crt_path_rays* below has it).
  * - What the shading sees: the record's own origin and direction and the unscaled t (t' 2^-e, the value reported) -- exactly
  *   what the frame kernels hand the same functions for a camera ray.  Nothing is normalised: the hit point is o + d * t per
@@ -466,6 +470,50 @@ int crt_shade_rays_device(crt_ctx* ctx, uint32_t n, const void* d_rays, void* d_
                           void* d_uv, void* d_inst, void* d_prim, crt_frame_stats* stats);
 int crt_shade_rays(crt_ctx* ctx, uint32_t n, const float* rays, float* rgb, float* normal, float* albedo, float* t, float* uv,
                    uint32_t* inst, uint32_t* prim, crt_frame_stats* stats);
+
+/* ---- Whitted shading (CRT_MODE_WHITTED, 150): mirrors and glass without path noise.  No function of its own: in mode 150
+ * crt_shade_rays* and crt_render_frame* (the pinned-host form included) do what follows, with the same arguments and the same
+ * argument checks as in mode 100; a failed call launches nothing.  The scene format's REFLECTIVE and REFRACTIVE materials,
+ * which mode 100 shades as diffuse, are honoured deterministically: a camera looking at a mirror, a lidar's intensity behind a
+ * window, a probe inside glass, a still of a .crtscene with its reflections and refraction.
+ * - Segment 0 is the record (crt_shade_rays*) or the pixel-centre camera ray (frames).  It is traced exactly as crt_shade_rays
+ *   traces it in mode 100 -- prescaled by 2^e, the same NaN / empty-interval rules, the same closest-hit traversal -- and the
+ *   outputs t, uv, inst, prim, normal and albedo are those of its hit, as in mode 100.
+ * - A record carries a throughput T = (1, 1, 1) and a turn count k = 0.  At the end of a segment:
+ *     . miss: the colour is the miss colour if k == 0, else fmaf(T.c, miss.c, 0) per channel; the record ends;
+ *     . REFLECTIVE (type 2): if k == max_bounces the colour is (0, 0, 0) and the record ends -- mode 200 cuts a chain the same
+ *       way.  Otherwise T *= albedo (the texture's where the material has one), the next segment starts at the hit point moved
+ *       1e-3 along the shading normal, in the normalised mirror direction, over (0, 10000), and k += 1;
+ *     . REFRACTIVE (type 3): the same cut.  Otherwise Snell's direction with eta = 1 / ior entering and ior leaving, from the
+ *       point moved 1e-3 to the far side; on total internal reflection the mirror direction from the near side.  T is unchanged,
+ *       k += 1.  There is no Fresnel split and no branching: glass refracts or, past the critical angle, mirrors;
+ *     . CONSTANT (type 4): the colour is fmaf(T.c, albedo.c, 0), also at k == 0, as in mode 200; the record ends;
+ *     . anything else (DIFFUSE, an invalid type, a triangle without a material): mode 100's shading at this surface -- one
+ *       any-hit shadow ray per light with a positive cosine, in light order, from the point moved 1e-3 along the normal over
+ *       (0, distance), the frames' fmaf sequence, the options "phong_ks" and "phong_exponent".  Phong's view vector is minus this
+ *       segment's direction: the record's direction as written for segment 0, the unit turn direction afterwards.  With L
+ *       the sum, the colour is L itself if k == 0, else fmaf(T.c, L.c, 0); the record ends.
+ *   These are the functions and the fmaf placement of the mode-200 path (crt_path_rays*) along the specular chain and of mode
+ *   100 at its end.  So a record that meets no mirror and no glass gives mode 100's bits in every output, and with phong_ks =
+ *   0 a record whose chain has k turns gives, at max_bounces = B, the rgb of crt_path_rays at one sample with max_bounces =
+ *   min(B, k), bit for bit (tests/test_whitted.py).
+ * - Options: "max_bounces" (0..64, default 3) also limits the turns of mode 150.  "spp" and "seed" are not read: there are no
+ *   samples and no random numbers.
+ * - Scale: segment 0 is scale-free as in mode 100 (any direction magnitude, the interval the record gives).  The bias 1e-3 and
+ *   the interval (0, 10000) of later segments are absolute lengths, as in mode 200: mode 150 is not scale-free.  Snell's cosine
+ *   and the mirror formula assume a unit direction on segment 0: a caller who wants the frames' semantics passes one.
+ * - Frames: crt_render_frame* in mode 150 is the pixel-centre camera rays (crt_camera_rays, CRT_SAMPLE_CENTRE), this query over
+ *   them and the frames' quantisation.  rgb_f32 is bit for bit crt_shade_rays of crt_camera_rays; rgba8 is its UNORM8; hit_t
+ *   (10000 on a miss), hit_inst and hit_prim are those of the camera ray's own hit.  Such a frame leaves the launch orders
+ *   and their cost state as it found them, and needs width x height <= 2^28 (CRT_EINVAL otherwise).  Accumulation ignores the
+ *   mode, as it ignores mode 100; crt_frame_guides, the denoiser and the temporal passes work on such a frame as on any other.
+ * - Not available (CRT_EINVAL, the message names the mode, nothing is launched): the tile entries (crt_render_tiles_device),
+ *   the batch entries (crt_render_frames_batch_device, crt_render_tiles_batch_device) and crt_render_frame_distributed.
+ * - stats: rays_primary = n (frames: the pixels); with crt_set_counting(ctx, 1) rays_primary is the exact number of closest-hit
+ *   rays, records plus turns, rays_shadow the shadow rays, nodes_visited / tris_tested all traversals together.
+ * - Pending refits are applied first.  Results do not depend on the order of the records, on scheduling, on the option
+ *   "path_pass_paths" (a launch covers at most that many records: a larger buffer runs as several) or on inner_min,
+ *   inner_min_any and stack_entries. */
 
 /* ---- path-traced ray queries: mode-200 radiance for caller-supplied rays (the sample-indexing contract crt_shade_rays'
  * refusal of mode 200 asks for).  Global illumination for sensors that are not a pinhole -- fisheye and equirectangular
