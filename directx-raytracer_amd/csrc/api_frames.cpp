@@ -20,12 +20,13 @@ void dropOrders(crt_ctx* c)
     for (crt_ctx::FrameSlot& s : c->frames.slot) s.orderKey = 0;
 }
 
-// the tile, batch and distributed entry points render shares of the render kernel's work: the Whitted query kind has none.
-// Checked before anything else of the call (a NULL context is the caller's next check)
+// the tile, batch and distributed entry points render shares of the render kernel's work: the Whitted and the ambient-occlusion
+// query kinds (modes 150 and 120) have none.  Checked before anything else of the call (a NULL context is the caller's next check)
 int refuseWhitted(crt_ctx* c, const char* what)
 {
-    if (!c || !whittedMode(c)) return CRT_OK;
-    return fail(c, CRT_EINVAL, "%s: shading mode %u (Whitted) renders whole frames only (crt_render_frame*): set another mode", what, c->mode);
+    if (!c || !(whittedMode(c) || ambientMode(c))) return CRT_OK;
+    return fail(c, CRT_EINVAL, "%s: shading mode %u (%s) renders whole frames only (crt_render_frame*): set another mode", what, c->mode,
+                whittedMode(c) ? "Whitted" : "ambient occlusion");
 }
 
 } // namespace crtapi
@@ -413,11 +414,20 @@ int runWhittedFrame(crt_ctx* c, const RenderParams& p, crt_frame_stats* stats)
     const WhittedFrame frame = { p.width, p.height, p.rgba8 };
     return runWhitted(c, p.width * p.height, nullptr, out, &frame, stats);
 }
+// A frame in mode 120 (CRT_MODE_AMBIENT), the same way: the camera rays, the ambient-occlusion query kind and the quantisation
+// (runAmbientFrame, api_queries.cpp)
+int runAmbientModeFrame(crt_ctx* c, const RenderParams& p, crt_frame_stats* stats)
+{
+    if (const int rc = checkFrameSize(c, "a frame in shading mode 120", p.width, p.height)) return rc; // (the camera-ray kernel's limit)
+    void* const out[7] = { p.rgb_f32, nullptr, nullptr, p.hit_t, nullptr, p.hit_inst, p.hit_prim };
+    return runAmbientFrame(c, out, WhittedFrame{ p.width, p.height, p.rgba8 }, stats);
+}
 
 // one frame of an entry point that accumulates (kind: kAccFrame / kAccTiles)
 int runFrame(crt_ctx* c, RenderParams& p, crt_frame_stats* stats, uint32_t kind)
 {
     if (p.mode == CRT_MODE_WHITTED) return runWhittedFrame(c, p, stats);
+    if (p.mode == CRT_MODE_AMBIENT) return runAmbientModeFrame(c, p, stats);
     const int rc = beginAccum(c, p, kind);
     if (rc) return rc;
     return p.acc_sum && p.spp == 0u ? runAccumResolve(c, p, stats) : runRender(c, p, stats);

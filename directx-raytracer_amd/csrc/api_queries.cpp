@@ -1,4 +1,4 @@
-// C ABI, batched queries (crt_ctx.h maps the units): ray, point, shaded, winding, path-traced and all-hits listing queries,
+// C ABI, batched queries (crt_ctx.h maps the units): ray, point, shaded (modes 120 and 150 among them), winding, path-traced and all-hits listing queries,
 // each entry point next to the run path it calls.
 #include "crt_ctx.h"
 
@@ -13,8 +13,8 @@ using namespace crtapi;
 
 namespace {
 
-// the scene's shading tables as the shaded, the path-traced and the Whitted query take them (crt::ShadeQueryParams,
-// crt::PathQueryParams, crt::WhittedQueryParams)
+// the scene's shading tables as the shaded, the path-traced, the Whitted and the ambient-occlusion query take them
+// (crt::ShadeQueryParams, crt::PathQueryParams, crt::WhittedQueryParams, crt::AmbientQueryParams)
 template <class Q> void sceneTables(const crt_ctx* c, Q& q)
 {
     q.shade = c->dShade; // as fillParams
@@ -51,6 +51,7 @@ union QueryParams {
     crt::WindingQueryParams winding;
     crt::ShadeQueryParams shade;
     crt::WhittedQueryParams whitted;
+    crt::AmbientQueryParams ambient;
 };
 using QueryFill = int (*)(crt_ctx* c, const QuerySpec& s, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin);
 
@@ -104,11 +105,30 @@ void crtapi::shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q)
 
 // crt_shade_rays* and the frames in mode 150: whether the context's mode asks for the Whitted kind (101..149 and 151..199 are mode 100)
 bool crtapi::whittedMode(const crt_ctx* c) { return c->mode == CRT_MODE_WHITTED; }
+// the same for mode 120 and the ambient-occlusion kind
+bool crtapi::ambientMode(const crt_ctx* c) { return c->mode == CRT_MODE_AMBIENT; }
 
 namespace {
 
 // the kinds of crt_shade_rays*: the context's mode is checked, and the refit follows the argument checks
-bool shadedKind(QueryKind kind) { return kind == crt::kQueryShade || kind == crt::kQueryWhitted; }
+bool shadedKind(QueryKind kind) { return kind == crt::kQueryShade || kind == crt::kQueryWhitted || kind == crt::kQueryAmbient; }
+// the kind crt_shade_rays* runs in the context's mode
+QueryKind shadedKindOf(const crt_ctx* c)
+{
+    if (c && whittedMode(c)) return crt::kQueryWhitted;
+    return c && ambientMode(c) ? crt::kQueryAmbient : crt::kQueryShade;
+}
+
+// The reach of mode 120's occlusion rays (include/crt_hip.h "ambient occlusion"): option "ao_radius" in thousandths of the
+// diagonal of the root box as crt_bvh_export reports it (readSceneBox), every operation rounded to float32 on its own
+// (-ffp-contract=off); 0 = the interval of a mode-200 bounce ray
+float ambientRadius(const crt_ctx* c)
+{
+    if (c->aoRadiusPermille == 0u) return 10000.0f; // traversal.hip.h kTMax
+    const float dx = c->binHi[0] - c->binLo[0], dy = c->binHi[1] - c->binLo[1], dz = c->binHi[2] - c->binLo[2];
+    const float D = std::sqrt((dx * dx + dy * dy) + dz * dz);
+    return (static_cast<float>(c->aoRadiusPermille) / 1000.0f) * D;
+}
 
 int fillClosestHit(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
 {
@@ -180,6 +200,27 @@ int fillWhitted(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], Quer
     innerMin = c->tuneInnerMin;
     return CRT_OK;
 }
+// crt_shade_rays* and the frames in mode 120 (ao_kernels.hip): the outputs of fillShade
+int fillAmbient(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
+{
+    crt::AmbientQueryParams& q = p.ambient;
+    q.rgb = static_cast<float*>(d[0]);
+    q.normal = static_cast<float*>(d[1]);
+    q.albedo = static_cast<float*>(d[2]);
+    q.t = static_cast<float*>(d[3]);
+    q.uv = static_cast<float*>(d[4]);
+    q.inst = static_cast<uint32_t*>(d[5]);
+    q.prim = static_cast<uint32_t*>(d[6]);
+    sceneTables(c, q);
+    q.phong_ks = static_cast<float>(c->phongKsPermille) / 1000.0f;
+    q.phong_exp = c->phongExp;
+    q.samples = c->aoSamples;
+    q.radius = ambientRadius(c);
+    q.sky = c->aoSky;
+    q.seed = c->pathSeed;
+    innerMin = c->tuneInnerMin;
+    return CRT_OK;
+}
 // crt_winding_numbers*: the walk over the tree and its moment table (winding_kernels.hip)
 int fillWinding(crt_ctx* c, const QuerySpec& s, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
 {
@@ -216,6 +257,8 @@ const QueryShape kQueryShapes[crt::kQueryKinds] = {
     /* kQueryWinding */ { 16u, "w", { { 4u, 4u } }, fillWinding },
     /* kQueryWhitted */
     { 32u, "rgb / normal / albedo / t / uv / inst / prim", { { 12u, 4u }, { 12u, 4u }, { 12u, 4u }, { 4u, 4u }, { 8u, 8u }, { 4u, 4u }, { 4u, 4u } }, fillWhitted },
+    /* kQueryAmbient */
+    { 32u, "rgb / normal / albedo / t / uv / inst / prim", { { 12u, 4u }, { 12u, 4u }, { 12u, 4u }, { 4u, 4u }, { 8u, 8u }, { 4u, 4u }, { 4u, 4u } }, fillAmbient },
 };
 
 // what every query entry point checks before anything is launched.  A shaded query (crt_shade_rays*) promises that a failed
@@ -304,7 +347,7 @@ int crtapi::endQuery(crt_ctx* c, QueryKind kind, uint32_t n, const QueryLaunch& 
     if (const int rs = readStats(c, stats, ql.counters, words)) return rs;
     if (kind == crt::kQueryOcclusion) stats->rays_shadow = n;
     else stats->rays_primary = kind == crt::kQueryOccupancy ? 3ull * n : n;
-    if (c->counting && (shadedKind(kind) || kind == crt::kQueryPath)) stats->rays_shadow = words[2];   // the shadow rays traced (modes 100, 150; paths)
+    if (c->counting && (shadedKind(kind) || kind == crt::kQueryPath)) stats->rays_shadow = words[2];   // the shadow rays traced (modes 100, 120 with its occlusion rays, 150; paths)
     if (kind == crt::kQueryPath || kind == crt::kQueryWhitted) stats->rays_primary += words[3];        // the bounce rays of the paths, the turns of mode 150
     return CRT_OK;
 }
@@ -375,6 +418,29 @@ int crtapi::runWhitted(crt_ctx* c, uint32_t n, const void* d_records, void* cons
     }
     if (frame && hrc == 0) hrc = crt::launchWhittedPack(all.rgb, frame->rgba8, n, c->stream);
     return endQuery(c, crt::kQueryWhitted, n, ql, hrc, stats);
+}
+
+// A frame in mode 120 (crt_render_frame*), as runWhitted's: the records are the frame's pixel-centre camera rays, made in the
+// arena by the camera-ray kernel; the ambient-occlusion kind runs over them in one launch into the outputs d (fillAmbient's
+// order), and the float colour (d[0], or scratch of the arena when the caller wants none) is quantised into frame.rgba8.
+// (crt_shade_rays* in mode 120 needs nothing of this: the kind keeps no record state, so runKind launches it as any other.)
+int crtapi::runAmbientFrame(crt_ctx* c, void* const d[7], const WhittedFrame& frame, crt_frame_stats* stats)
+{
+    QueryParams p;
+    std::memset(&p, 0, sizeof(p));
+    uint32_t innerMin = 0;
+    if (const int rc = fillAmbient(c, QuerySpec{}, d, p, innerMin)) return rc;
+    crt::AmbientQueryParams& q = p.ambient;
+    const uint32_t n = frame.width * frame.height;
+    const size_t rayBytes = up256(static_cast<size_t>(n) * 32u), rgbBytes = q.rgb ? 0u : up256(static_cast<size_t>(n) * 12u);
+    QueryLaunch ql;
+    if (const int rc = beginQuery(c, crt::kQueryAmbient, n, stats, ql, rayBytes + rgbBytes)) return rc;
+    if (!q.rgb) q.rgb = reinterpret_cast<float*>(ql.extra + rayBytes);
+    int hrc = crt::launchCameraRays(cameraRayParams(c, frame.width, frame.height, CRT_SAMPLE_CENTRE, ql.extra), c->stream);
+    q.c = queryCommon(c, ql, ql.extra, n, innerMin);
+    if (hrc == 0) hrc = crt::launchQuery(crt::kQueryAmbient, &q, c->counting, ql.grid, c->stream);
+    if (hrc == 0) hrc = crt::launchWhittedPack(q.rgb, frame.rgba8, n, c->stream);
+    return endQuery(c, crt::kQueryAmbient, n, ql, hrc, stats);
 }
 
 namespace {
@@ -653,13 +719,13 @@ int crt_occluded_rays(crt_ctx* c, uint32_t n, const float* rays, uint8_t* occlud
 int crt_shade_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, void* d_rgb, void* d_normal, void* d_albedo, void* d_t, void* d_uv,
                           void* d_inst, void* d_prim, crt_frame_stats* stats)
 {
-    return queryDevice(c, { "crt_shade_rays_device", c && whittedMode(c) ? crt::kQueryWhitted : crt::kQueryShade, { d_rgb, d_normal, d_albedo, d_t, d_uv, d_inst, d_prim } }, n, d_rays, stats);
+    return queryDevice(c, { "crt_shade_rays_device", shadedKindOf(c), { d_rgb, d_normal, d_albedo, d_t, d_uv, d_inst, d_prim } }, n, d_rays, stats);
 }
 
 int crt_shade_rays(crt_ctx* c, uint32_t n, const float* rays, float* rgb, float* normal, float* albedo, float* t, float* uv, uint32_t* inst,
                    uint32_t* prim, crt_frame_stats* stats)
 {
-    return queryHost(c, { "crt_shade_rays", c && whittedMode(c) ? crt::kQueryWhitted : crt::kQueryShade, { rgb, normal, albedo, t, uv, inst, prim } }, n, rays, stats);
+    return queryHost(c, { "crt_shade_rays", shadedKindOf(c), { rgb, normal, albedo, t, uv, inst, prim } }, n, rays, stats);
 }
 
 int crt_path_rays_device(crt_ctx* c, uint32_t n, const void* d_rays, const void* d_ids, uint32_t first_sample, uint32_t n_samples, void* d_rgb,

@@ -8,6 +8,7 @@
 #include "mem_util.h"
 
 #include <climits>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -131,10 +132,22 @@ void freeScene(crt_ctx* c)
     c->haveScene = false;
 }
 
-// the root record as it sits in HBM: where split rays are cut into segments
+// the root record as it sits in HBM: where split rays are cut into segments; and the union of the two child boxes of the
+// binary tree's node 0, from where crt_bvh_export reads it (the quantised root's far planes are rounded outwards)
 int readSceneBox(crt_ctx* c)
 {
-    for (int a = 0; a < 3; a++) c->sceneLo[a] = c->sceneHi[a] = 0.0f;
+    for (int a = 0; a < 3; a++) c->sceneLo[a] = c->sceneHi[a] = c->binLo[a] = c->binHi[a] = 0.0f;
+    if (c->bvh.dev.nNodes > 0 && (c->dBinNodes || !c->bvh.nodes.empty())) {
+        crt_bvh_node root;
+        if (c->dBinNodes) HIP_TRY(c, hipMemcpy(&root, c->dBinNodes, sizeof(root), hipMemcpyDeviceToHost));
+        else root = c->bvh.nodes[0];
+        const float lo[3][2] = { { root.lx0, root.rx0 }, { root.ly0, root.ry0 }, { root.lz0, root.rz0 } };
+        const float hi[3][2] = { { root.lx1, root.rx1 }, { root.ly1, root.ry1 }, { root.lz1, root.rz1 } };
+        for (int a = 0; a < 3; a++) {
+            c->binLo[a] = std::fmin(lo[a][0], lo[a][1]);
+            c->binHi[a] = std::fmax(hi[a][0], hi[a][1]);
+        }
+    }
     if (c->bvh.dev.nNodes4 > 0) {
         crt_bvh_node4q root;
         HIP_TRY(c, hipMemcpy(&root, c->dNodes, sizeof(root), hipMemcpyDeviceToHost));
@@ -332,6 +345,10 @@ const Option kOptions[] = {
     { "phong_ks", within<0, 100000>, U32(phongKsPermille), kNewView },
     { "phong_exponent", within<1, 65536>, U32(phongExp), kNewView },
     { "seed", any, U32(pathSeed) },
+    // mode 120 runs outside the frame ring and the accumulation: nothing of theirs follows these
+    { "ao_samples", within<1, 4096>, U32(aoSamples) },
+    { "ao_radius", within<0, 1000000>, U32(aoRadiusPermille) },
+    { "ao_sky", oneOf<0, 1>, U32(aoSky) },
     { "path_pipeline", oneOf<0, 1>, U32(tunePathPipeline) },
     { "path_pass_paths", within<(1 << 16), (1 << 25)>, U32(tunePathPassPaths) },
     { "path_ranges", oneOf<1, 8>, U32(tunePathRanges) },

@@ -1,7 +1,7 @@
 // Internal to the C-ABI layer (host C++ only): the renderer context and what more than one of the layer's units uses.
 //   crt_api.cpp      context, streams, options, scene upload, tree exports; defines the shared helpers declared here
 //   api_frames.cpp   the per-frame path: runRender, launch-order feedback, accumulation, frame / tile / batch entry points
-//   api_queries.cpp  ray, point, shaded, Whitted, path and listing queries
+//   api_queries.cpp  ray, point, shaded, Whitted, ambient-occlusion, path and listing queries
 //   api_image.cpp    camera rays, frame guides, the a-trous filters, temporal reprojection and variance
 //   api_dynamic.cpp  vertex updates, transforms, refit / rebuild, motion, gradients
 //   api_comm.cpp     RCCL gather and the host-memory exchange
@@ -101,6 +101,8 @@ struct crt_ctx {
     bool dynamicOpt = false;
     crt::DynamicScene* dyn = nullptr;
     float sceneLo[3] = { 0.f, 0.f, 0.f }, sceneHi[3] = { 0.f, 0.f, 0.f }; // box of the tree's root: where split rays are cut into segments
+    float binLo[3] = { 0.f, 0.f, 0.f }, binHi[3] = { 0.f, 0.f, 0.f };     // the same box in full precision, from node 0 of the binary tree
+                                                                          // (crt_bvh_export): what "ao_radius" is a fraction of
 
     float pos[3] = { 0.f, 0.f, 0.f };
     float rot[9] = { 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f };
@@ -109,6 +111,7 @@ struct crt_ctx {
     bool counting = false;
     uint32_t pathSpp = 4, pathBounces = 3, pathSeed = 1234; // mode 200 (BASELINE.json configs[4]: 4 spp, 3 bounces)
     uint32_t phongKsPermille = 0, phongExp = 32;            // mode 100: specular term, off by default
+    uint32_t aoSamples = 16, aoRadiusPermille = 0, aoSky = 0; // mode 120: occlusion rays per hit, their reach (0: unbounded), sky colour
     uint32_t tunePathTile = 0;     // mode 200 work split: 0 = default (8), 8 / 16 = pixel tile edge per workgroup
     uint32_t tunePathPipeline = 0; // mode 200: 0 = one persistent kernel with wavefront-private queues (default: 21.2 vs 23.4 ms on C5), 1 = the stages as separate launches over global queues
     uint32_t tunePathPassPaths = 1u << 24; // wavefront pipeline: paths one pass may carry (112 bytes of queue / radiance memory each)
@@ -218,7 +221,7 @@ struct crt_ctx {
 
     // batched ray and point queries (crt_trace_rays* / crt_occluded_rays*, crt_closest_points* / crt_count_hits* /
     // crt_occupancy*): per arena the launch's cursor, counters and the stack spill arena of the persistent query kernel.  Arenas
-    // of this pool belong to queries alone (never to a frame of runRender; a mode-150 frame is a query); serial = ++raySerial.
+    // of this pool belong to queries alone (never to a frame of runRender; a mode-150 or mode-120 frame is a query); serial = ++raySerial.
     // (Flat: the a-trous filter of api_image.cpp takes its planes from this pool too)
     Arena rayArena[kRing];
     uint32_t raySerial = 0;
@@ -325,11 +328,13 @@ int checkDevicePointers(crt_ctx* c, const char* what, std::initializer_list<cons
 // api_queries.cpp
 void shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q);
 bool whittedMode(const crt_ctx* c);
+bool ambientMode(const crt_ctx* c);
 struct WhittedFrame {
     uint32_t width, height;
     uint32_t* rgba8;
 };
 int runWhitted(crt_ctx* c, uint32_t n, const void* d_records, void* const d[7], const WhittedFrame* frame, crt_frame_stats* stats);
+int runAmbientFrame(crt_ctx* c, void* const d[7], const WhittedFrame& frame, crt_frame_stats* stats);
 int beginQuery(crt_ctx* c, crt::QueryKind kind, uint32_t n, crt_frame_stats* stats, QueryLaunch& ql, size_t extraBytes = 0,
                uint32_t minGrid = 0);
 int endQuery(crt_ctx* c, crt::QueryKind kind, uint32_t n, const QueryLaunch& ql, int rc, crt_frame_stats* stats);

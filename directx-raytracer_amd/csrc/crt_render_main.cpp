@@ -35,9 +35,13 @@ static void usage()
                  "       [--path FILE]   one line per frame, commands separated by ';':\n"
                  "                       rotate YAW PITCH | forward D | right D | zoom A | pan DEG | tilt DEG | roll DEG | mode M\n"
                  "   [--mode-at FRAME:MODE]...  switch the shading mode from that frame on\n"
-                 "       modes: 0..6 the reference's, 100 Lambert / Phong with shadow rays, 150 Whitted (mode 100 seen through mirrors and\n"
-                 "       glass, at most --bounces turns; one rank only: not with --ranks / --rank), 200 path tracing\n"
+                 "       modes: 0..6 the reference's, 100 Lambert / Phong with shadow rays, 120 ambient occlusion (the share of the sky a\n"
+                 "       surface sees; one rank only), 150 Whitted (mode 100 seen through mirrors and glass, at most --bounces turns; one\n"
+                 "       rank only: not with --ranks / --rank), 200 path tracing\n"
                  "   [--spp N] [--bounces N] [--seed N]   mode 200 (path tracing); --bounces also limits the turns of mode 150\n"
+                 "   [--ao-samples N] [--ao-radius M] [--ao-sky]   mode 120: N occlusion rays per pixel (1..4096, default 16; --seed picks\n"
+                 "                        their directions), reaching M thousandths of the scene box's diagonal (default 0: unbounded);\n"
+                 "                        --ao-sky: mode 100's point lights plus a sky of the miss colour instead of the grey visibility\n"
                  "   [--accumulate MAX]   mode 200: frames add their samples to running per-pixel sums (up to MAX samples) while the\n"
                  "                        camera holds still and start over when it moves; each frame written is the running mean;\n"
                  "                        with --ranks every rank accumulates its own tiles\n"
@@ -68,6 +72,8 @@ struct Args {
     uint32_t mode = 0, w = 1920, h = 1080;
     int frames = 1, device = 0, deviceBase = 0, ranks = 0, rank = -1;
     int spp = -1, bounces = -1, seed = -1, phongKs = -1, phongExp = -1, accumulate = -1;
+    int aoSamples = -1, aoRadius = -1; // mode 120
+    bool aoSky = false;
     int gpuBuilder = -1; // --gpu-build: -1 = host SAH, 0 = LBVH, 1 = PLOC
     float orbit = 0.f, pitch = 0.f, forward = 0.f, right = 0.f, zoom = 0.f;
     bool count = false, png = false, hostExchange = false, sameDevice = false, denoise = false;
@@ -115,6 +121,9 @@ int runRank(const Args& a)
     if (a.seed >= 0) renderer.setOption("seed", a.seed);
     if (a.phongKs >= 0) renderer.setOption("phong_ks", a.phongKs);
     if (a.phongExp >= 0) renderer.setOption("phong_exponent", a.phongExp);
+    if (a.aoSamples >= 0) renderer.setOption("ao_samples", a.aoSamples);
+    if (a.aoRadius >= 0) renderer.setOption("ao_radius", a.aoRadius);
+    if (a.aoSky) renderer.setOption("ao_sky", 1);
     if (a.accumulate >= 0) renderer.setAccumulation(static_cast<uint32_t>(a.accumulate));
     if (a.ranks > 0 && a.hostExchange) renderer.joinRanksThroughHostMemory(static_cast<uint32_t>(a.rank), static_cast<uint32_t>(a.ranks), a.nonce);
     else if (a.ranks > 0) renderer.joinRanks(static_cast<uint32_t>(a.rank), static_cast<uint32_t>(a.ranks), a.idFile, a.nonce);
@@ -293,6 +302,9 @@ int main(int argc, char** argv)
         else if (s == "--spp") a.spp = std::atoi(next("--spp"));
         else if (s == "--bounces") a.bounces = std::atoi(next("--bounces"));
         else if (s == "--seed") a.seed = std::atoi(next("--seed"));
+        else if (s == "--ao-samples") a.aoSamples = std::atoi(next("--ao-samples"));
+        else if (s == "--ao-radius") a.aoRadius = std::atoi(next("--ao-radius"));
+        else if (s == "--ao-sky") a.aoSky = true;
         else if (s == "--accumulate") { if ((a.accumulate = std::atoi(next("--accumulate"))) < 0) { usage(); return 2; } }
         else if (s == "--phong") { if (std::sscanf(next("--phong"), "%d:%d", &a.phongKs, &a.phongExp) != 2) { usage(); return 2; } }
         else if (s == "--out") a.out = next("--out");
@@ -322,12 +334,15 @@ int main(int argc, char** argv)
     if (a.denoise && (a.ranks > 0 || a.denoiseIterations < 1 || a.denoiseIterations > 8)) { usage(); return 2; }
     if (a.temporal && (a.ranks > 0 || a.mode != 200u || !a.modeAt.empty() || !(a.temporalAlpha >= 0.0f && a.temporalAlpha <= 1.0f))) { usage(); return 2; }
     if (a.variance && !a.temporal) { usage(); return 2; }
-    if (a.ranks > 0 || a.rank >= 0) { // the Whitted mode renders whole frames only: the tile entry points refuse it
-        bool whitted = a.mode == CRT_MODE_WHITTED;
-        for (const auto& sw : a.modeAt) whitted = whitted || sw.second == CRT_MODE_WHITTED;
-        if (whitted) {
-            std::fprintf(stderr, "crt_render: shading mode %u (Whitted) is not available with --ranks / --rank: it renders on one rank only\n", CRT_MODE_WHITTED);
-            return 2;
+    if (a.ranks > 0 || a.rank >= 0) { // the Whitted and ambient-occlusion modes render whole frames only: the tile entry points refuse them
+        for (const uint32_t whole : { CRT_MODE_WHITTED, CRT_MODE_AMBIENT }) {
+            bool asked = a.mode == whole;
+            for (const auto& sw : a.modeAt) asked = asked || sw.second == whole;
+            if (asked) {
+                std::fprintf(stderr, "crt_render: shading mode %u (%s) is not available with --ranks / --rank: it renders on one rank only\n", whole,
+                             whole == CRT_MODE_WHITTED ? "Whitted" : "ambient occlusion");
+                return 2;
+            }
         }
     }
     try {

@@ -38,7 +38,7 @@ const QueryKernel& queryKernel(QueryKind kind)
     static const QueryKernel* const kernels[kQueryKinds] = { &kKernelClosestHit, &kKernelOcclusion, &kKernelClosestPoint,
                                                              &kKernelCount,      &kKernelOccupancy, &kKernelListFill,
                                                              &kKernelShade,      &kKernelPath,      &kKernelWinding,
-                                                             &kKernelWhitted };
+                                                             &kKernelWhitted,    &kKernelAmbient };
     return *kernels[kind];
 }
 

@@ -159,7 +159,8 @@ struct QueryCommon {
 enum QueryKind { kQueryClosestHit = 0, kQueryOcclusion = 1, kQueryClosestPoint = 2, kQueryCount = 3, kQueryOccupancy = 4,
                  kQueryListFill = 5 /* the second traversal of crt_list_hits*: a kernel of its own, not an entry point */,
                  kQueryShade = 6, kQueryPath = 7 /* crt_path_rays*: passes of (record, sample) items */, kQueryWinding = 8,
-                 kQueryWhitted = 9 /* crt_shade_rays* and the frames in mode 150 */, kQueryKinds };
+                 kQueryWhitted = 9 /* crt_shade_rays* and the frames in mode 150 */,
+                 kQueryAmbient = 10 /* crt_shade_rays* and the frames in mode 120 */, kQueryKinds };
 // What the host knows of a kind's kernel: the host stubs of its two instantiations and the ints per stack entry (the
 // closest-point stack keeps each entry's box bound beside its reference: 2; every other kind: 1).  Stated by the file that
 // defines the kernel and never written again.  (Not const: hipcc would emit a const row into the device code object too.)
@@ -175,6 +176,7 @@ extern QueryKernel kKernelShade;                                        // shade
 extern QueryKernel kKernelPath;                                         // path_query_kernels.hip
 extern QueryKernel kKernelWinding;                                      // winding_kernels.hip
 extern QueryKernel kKernelWhitted;                                      // whitted_kernels.hip
+extern QueryKernel kKernelAmbient;                                      // ao_kernels.hip
 // The rest is query_launch.cpp.  The kind's row
 const QueryKernel& queryKernel(QueryKind kind);
 // workgroups of the kind's kernel the current device holds at once with `stack_entries` of LDS stack per lane (0: unknown)
@@ -276,8 +278,38 @@ struct WhittedQueryParams {
     uint32_t* prim;
 };
 constexpr size_t kWhittedStateBytes = 32; // two float4
-// a mode-150 frame's RGBA8 from its float colour (3 floats per pixel), the frames' unorm8 rule: n pixels
+// a mode-150 or mode-120 frame's RGBA8 from its float colour (3 floats per pixel), the frames' unorm8 rule: n pixels
 int launchWhittedPack(const float* rgb, uint32_t* rgba8, uint32_t n, ihipStream_t* stream);
+// Ambient-occlusion ray queries (ao_kernels.hip; crt_shade_rays* and the frames in mode 120): the closest hit of n ray records,
+// then `samples` any-hit rays from the hit point over (0, radius) in the first-bounce directions of the mode-200 paths of
+// (record, sample, seed); the colour is the share that escapes, or with `sky` mode 100's light plus albedo x miss x that share.
+// The outputs are ShadeQueryParams'; every one is nullable.  No record state outside the registers
+struct AmbientQueryParams {
+    QueryCommon c;                // records: the rays; inner_min: tune_inner_min (the closest-hit phase)
+    uint32_t inner_min_any;       // tune_inner_min_any (the shadow-ray and occlusion phases)
+    // the scene's shading tables, as RenderParams'
+    const void* shade;
+    const void* lights;
+    const void* mats;
+    const void* uvs;
+    const void* textures;
+    const unsigned char* texels;
+    uint32_t n_textures, n_lights, n_mats;
+    float miss[3];
+    float phong_ks;               // sky only: mode 100's specular term
+    uint32_t phong_exp;
+    uint32_t samples;             // option "ao_samples": 1..4096
+    float radius;                 // the occlusion rays' tmax: option "ao_radius" of the root box's diagonal, or 10000
+    uint32_t sky;                 // option "ao_sky"
+    uint32_t seed;                // option "seed"
+    float* rgb;                   // as ShadeQueryParams'
+    float* normal;
+    float* albedo;
+    float* t;
+    float* uv;
+    uint32_t* inst;
+    uint32_t* prim;
+};
 // rad[sample * n_records + record] of n_samples samples added in sample order to `in` (3 float64 per record; NULL: zero);
 // the sums go to `out`, their mean over `total` samples to rgb (each nullable)
 int launchPathResolve(const void* rad, uint32_t n_records, uint32_t n_samples, const double* in, double* out, float* rgb, uint32_t total,

@@ -133,6 +133,14 @@ void Renderer::setOption(const char* name, int value)
     check(crt_set_option(ctx, name, value), name);
 }
 
+void Renderer::setAmbientOcclusion(uint32_t samples, uint32_t radiusThousandths, bool sky)
+{
+    if (samples > INT32_MAX || radiusThousandths > INT32_MAX) throw std::runtime_error("setAmbientOcclusion: value out of range");
+    setOption("ao_samples", static_cast<int>(samples));
+    setOption("ao_radius", static_cast<int>(radiusThousandths));
+    setOption("ao_sky", sky ? 1 : 0);
+}
+
 void Renderer::setAccumulation(uint32_t maxSamples)
 {
     if (!ctx) throw std::runtime_error("setAccumulation before prepareForRendering");

@@ -44,6 +44,9 @@ public:
     const crt_frame_stats& getLastFrameStats() const { return stats; }
     void setCounting(bool on);
     void setOption(const char* name, int value); // crt_set_option: "spp", "max_bounces", "seed", "phong_ks", "phong_exponent", ...
+    // mode 120 (CRT_MODE_AMBIENT): the options "ao_samples" (1..4096), "ao_radius" (thousandths of the scene box's diagonal,
+    // 0 = unbounded) and "ao_sky" (point lights plus a sky of the miss colour instead of the grey visibility)
+    void setAmbientOcclusion(uint32_t samples, uint32_t radiusThousandths, bool sky);
     // crt_set_accumulation: mode-200 frames add their samples to running sums while the camera holds still (0 = off)
     void setAccumulation(uint32_t maxSamples);
     uint32_t getAccumulatedSamples() const; // crt_accumulated_samples
@@ -56,9 +59,9 @@ public:
     };
     void traceRays(const float* rays, size_t n, RayHit* out);
     void occluded(const float* rays, size_t n, uint8_t* out); // 1 = some triangle lies in (tmin, tmax)
-    // the closest hit shaded in the current mode (crt_shade_rays, synchronous; modes 0..100, and 150: the colour seen through
-    // mirrors and glass, CRT_MODE_WHITTED): colour, shading normal and albedo beside the hit.  A miss reports the miss colour, a
-    // zero normal and a zero albedo.
+    // the closest hit shaded in the current mode (crt_shade_rays, synchronous; modes 0..100, 120: the share of the sky the hit
+    // point sees, CRT_MODE_AMBIENT, and 150: the colour seen through mirrors and glass, CRT_MODE_WHITTED): colour, shading normal
+    // and albedo beside the hit.  A miss reports the miss colour, a zero normal and a zero albedo.
     struct ShadedHit {
         float rgb[3], normal[3], albedo[3];
         RayHit hit;

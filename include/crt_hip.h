@@ -49,10 +49,13 @@ enum {
 #define CRT_MODE_CHECKER 6u
 #define CRT_MODE_LAMBERT 100u /* Lambert (+ optional Phong highlight, options "phong_ks" / "phong_exponent") + one shadow ray per light
                                  (BASELINE.json north_star: "Lambert/Phong shading") */
+#define CRT_MODE_AMBIENT 120u /* ambient occlusion: the cosine-weighted share of the hemisphere over the hit point that option "ao_samples"
+                                 any-hit rays see free within option "ao_radius", as a grey value or (option "ao_sky") as a sky of the
+                                 miss colour on top of mode 100's point lights; the contract is below ("ambient occlusion") */
 #define CRT_MODE_WHITTED 150u /* mode 100 seen through mirrors and glass: REFLECTIVE and REFRACTIVE surfaces are followed as mode 200
                                  follows them (no Fresnel split, no random numbers, no samples), at most option "max_bounces" turns,
                                  and mode 100 shades the first surface that is neither; the contract is below ("Whitted shading").
-                                 101..149 and 151..199 behave as 100, every mode >= 200 as 200 */
+                                 101..119, 121..149 and 151..199 behave as 100, every mode >= 200 as 200 */
 #define CRT_MODE_PATH 200u    /* path tracing: options "spp" (default 4), "max_bounces" (3), "seed" (1234); BASELINE.json configs[4] */
 
 /* ---- geometry handed over at upload: exactly what createVertexBuffers / createIndexBuffers memcpy ----
@@ -237,7 +240,9 @@ int crt_render_frame_distributed(crt_ctx* ctx, uint32_t width, uint32_t height, 
  * "gpu_build" 0/1: acceleration structure built on the GPU at the next crt_upload_scene.  "gpu_builder" picks the GPU builder for
  * those uploads and for crt_rebuild: 0 = LBVH (the default), 1 = PLOC (closer to the SAH tree in quality, slower to build); other
  * values -> CRT_EINVAL.  It has no effect on host SAH uploads.
- * Rendering parameters of mode 200: "spp", "max_bounces", "seed" ("max_bounces" also limits the turns of mode 150). Tuning knobs (speed only, results never
+ * Rendering parameters of mode 200: "spp", "max_bounces", "seed" ("max_bounces" also limits the turns of mode 150).
+ * Rendering parameters of mode 120: "ao_samples" (1..4096, default 16), "ao_radius" (0..1000000 thousandths of the scene box's
+ * diagonal, default 0 = unbounded), "ao_sky" (0/1, default 0) and "seed"; other values -> CRT_EINVAL ("ambient occlusion" below). Tuning knobs (speed only, results never
  * change): "inner_min" / "inner_min_any" wave scheduling of the closest-hit / any-hit traversal loops (1..65: node steps while that
  * many lanes stand on inner nodes; -1..-8: while that many eighths of the wavefront's live lanes do; default -6), "xcd_group", "adaptive_order" (launch the most expensive 8x8
  * packets of the previous frame first: 0 never, 1 always, 2 = default: only for a frame issued on the same stream as the frame
@@ -436,7 +441,7 @@ int crt_occluded_rays(crt_ctx* ctx, uint32_t n, const float* rays, uint8_t* occl
  *   outputs must be non-NULL.
  * - Mode: the context's current shading mode (crt_set_shading_mode) applies.  Modes 0..99 are the seven reference modes
  *   (7..99 behave as 6, as in the frames); mode 100 is Lambert with optional Phong (options "phong_ks", "phong_exponent") and
- *   one shadow ray per light (101..199 behave as 100, except 150: "Whitted shading" below).  Mode 200 returns CRT_EINVAL and launches nothing: path tracing of caller rays would need a
+ *   one shadow ray per light (101..199 behave as 100, except 120: "ambient occlusion", and 150: "Whitted shading", both below).  Mode 200 returns CRT_EINVAL and launches nothing: path tracing of caller rays would need a
  *   sample-indexing contract of its own (crt_path_rays* below has it).
  * - What the shading sees: the record's own origin and direction and the unscaled t (t' 2^-e, the value reported) -- exactly
  *   what the frame kernels hand the same functions for a camera ray.  Nothing is normalised: the hit point is o + d * t per
@@ -514,6 +519,55 @@ int crt_shade_rays(crt_ctx* ctx, uint32_t n, const float* rays, float* rgb, floa
  * - Pending refits are applied first.  Results do not depend on the order of the records, on scheduling, on the option
  *   "path_pass_paths" (a launch covers at most that many records: a larger buffer runs as several) or on inner_min,
  *   inner_min_any and stack_entries. */
+
+/* ---- ambient occlusion (CRT_MODE_AMBIENT, 120): sky visibility per hit.  No function of its own: in mode 120 crt_shade_rays*
+ * and crt_render_frame* (the pinned-host form included) do what follows, with the same arguments and the same argument checks
+ * as in mode 100; a failed call launches nothing.  The result is the cosine-weighted share v of the hemisphere over a surface
+ * point that is free of geometry within a radius -- ambient occlusion, the sky-view factor, accessibility: the contact shadows
+ * of a still, a training target beside signed distance and occupancy, the visibility term of a sky-lit lidar return or probe --
+ * estimated with K any-hit rays whose directions are drawn in registers: no ray buffer is written and no byte per ray read.
+ * Options (crt_set_option; a value out of range -> CRT_EINVAL):
+ *     "ao_samples"  K, 1..4096, default 16;
+ *     "ao_radius"   0..1000000: the reach R of the occlusion rays in thousandths of the diagonal of the scene's bounding box,
+ *                   so that it does not depend on the unit of length; default 0 = unbounded, R = 10000 (the interval of a
+ *                   mode-200 bounce ray).  For a value v > 0, R = ((float)v / 1000.0f) * D with D = sqrtf((dx*dx + dy*dy) +
+ *                   dz*dz), every operation rounded to float32 on its own (no fused multiply-add), where the box is that of node
+ *                   0 of the binary tree as crt_bvh_export reports it at the time of the call (after a refit or a rebuild: the
+ *                   new one): dx = fmaxf(nodes[0].lx1, nodes[0].rx1) - fminf(nodes[0].lx0, nodes[0].rx0), dy and dz likewise
+ *                   from ly0 / ly1 / ry0 / ry1 and lz0 / lz1 / rz0 / rz1; a scene without triangles has D = 0;
+ *     "ao_sky"      0/1, default 0: which colour step 5 gives;
+ *     "seed"        the seed of mode 200 is read.  "spp" and "max_bounces" are not.
+ * One record `id` (crt_shade_rays*: the index in the buffer; frames: the pixel-centre camera ray of pixel id = py * width + px):
+ * 1. Closest hit: exactly that of crt_trace_rays.  t, uv, inst, prim, normal and albedo are mode 100's, bit for bit.  A miss,
+ *    and a record that is not traced (NaN, empty interval), gives the miss colour, as in every mode, and ends.
+ * 2. Surface: position P, shading normal N flipped to face the ray, and albedo as in mode 100; every material is treated as
+ *    diffuse, as mode 100 treats it.  Po = P moved 1e-3 along N (fmaf(N.c, 1e-3f, P.c)).
+ * 3. Occlusion samples s = 0 .. K - 1: with the hash h() and the generator next() of mode 200 (a PCG permutation of 32 bits;
+ *    next(st): st = h(st), the value (st >> 8) * 2^-24),
+ *        st = h(h(h(id ^ h(s + h(seed))))),  u1 = next(st),  u2 = next(st),  d = the cosine-weighted direction about N for
+ *    (u1, u2) -- the two numbers the mode-200 path of (id, s, seed) draws for its first bounce, right after the two its pixel
+ *    jitter takes, and the direction that path takes at a diffuse first hit with this normal.  One any-hit traversal from Po
+ *    along d over (0, R), as crt_occluded_rays answers the record {Po, 0, d, R}.  `visible` counts the samples not occluded.
+ * 4. Visibility: v = (float)((double)visible / (double)K).  `visible` is an integer: nothing depends on the order of the samples.
+ * 5. Colour.  "ao_sky" = 0: rgb = (v, v, v).  "ao_sky" = 1: with `direct` mode 100's rgb at this hit (one shadow ray per light
+ *    with a positive cosine, in light order, the options "phong_ks" / "phong_exponent" included), rgb.c = fmaf(albedo.c *
+ *    miss.c, v, direct.c): point lights plus a sky of the miss colour.  With a black miss colour that is mode 100 bit for bit.
+ * So with no lights, every material DIFFUSE and white, a white miss colour and "ao_radius" = 0, rgb is bit for bit that of
+ * crt_path_rays with n_samples = K, max_bounces = 1 and the same seed: each of its samples is 1 or 0 as its first bounce ray
+ * escapes or not (tests/test_occlusion_mode.py).
+ * - Scale: the closest hit is scale-free as in mode 100.  The bias 1e-3 is an absolute length, as in modes 100 and 200, and so
+ *   is the unbounded reach of 10000; a radius given by "ao_radius" follows the scene.
+ * - Frames: crt_render_frame* in mode 120 is the pixel-centre camera rays (crt_camera_rays, CRT_SAMPLE_CENTRE), this query over
+ *   them and the frames' quantisation, exactly as in mode 150: rgb_f32 is bit for bit crt_shade_rays of crt_camera_rays, rgba8
+ *   its UNORM8, hit_t (10000 on a miss), hit_inst and hit_prim those of the camera ray's hit.  Such a frame leaves the launch
+ *   orders and their cost state as it found them, needs width x height <= 2^28 (CRT_EINVAL otherwise), and neither reads nor
+ *   changes the accumulation.
+ * - Not available (CRT_EINVAL, the message names the mode, nothing is launched): the tile entries (crt_render_tiles_device),
+ *   the batch entries (crt_render_frames_batch_device, crt_render_tiles_batch_device) and crt_render_frame_distributed.
+ * - stats: rays_primary = n (frames: the pixels); with crt_set_counting(ctx, 1) rays_shadow is the exact number of any-hit rays,
+ *   occlusion samples (K per hit) plus, with "ao_sky", the shadow rays; nodes_visited / tris_tested all traversals together.
+ * - Pending refits are applied first.  Results do not depend on the order in which records are scheduled, on inner_min,
+ *   inner_min_any or stack_entries; they do depend on a record's index, which is its id. */
 
 /* ---- path-traced ray queries: mode-200 radiance for caller-supplied rays (the sample-indexing contract crt_shade_rays'
  * refusal of mode 200 asks for).  Global illumination for sensors that are not a pinhole -- fisheye and equirectangular
