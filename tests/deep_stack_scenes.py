@@ -49,6 +49,31 @@ def plate_and_chain_b(n=30, dup=4):
     return _scene([plates(1, 1.5, 0.01, 1, -1.0), plates(n, 1.5, 0.02, dup, 1.0)], [LIGHT])
 
 
+MIRROR = {"albedo": (0.9, 0.9, 0.9), "type": 2}  # REFLECTIVE
+BACKDROP_Z = 3000.0  # behind the largest plate of chain B (s = 2557), within the frames' ray interval along every mirrored ray
+APEX_LIGHT = ((0.0005, 0.001, 0.005), 3.0e8)  # between the mirror and chain B, next to the apex
+
+
+def _quad(lo, hi, z, material):
+    v = np.float32([[lo, lo, z], [hi, lo, z], [hi, hi, z], [lo, hi, z]])
+    return {"vertices": v, "triangles": np.uint32([[0, 1, 3], [1, 2, 3]]), "material_index": material, "normals": None}
+
+
+def mirror_and_chain_b(n=30, dup=4):
+    """plate_and_chain_b with a mirror for its front plate (a second material; chain B stays diffuse), a diffuse backdrop behind
+    chain B and a second light next to the apex.  The mirror is the whole square the front plate is half of, so the camera
+    rays, which hold nothing, are mirrored into chain B in two kinds: those inside the plates' triangle end on the first plate,
+    those in the other half of the square (x + y > 1.2 z) cross every box of the chain, miss every plate and end on the
+    backdrop.  Both walk the chain nearest child first.  The backdrop faces the apex light through the whole chain, so the
+    shadow ray that follows such a turn walks the chain in slot order, and its light depends on where the mirrored ray arrived"""
+    sc = plate_and_chain_b(n, dup)
+    a = 0.6 * 0.01
+    sc["materials"] = sc["materials"] + [dict(MIRROR)]
+    sc["meshes"] = [_quad(-a, 3 * a, -0.01, 1), sc["meshes"][1], _quad(-0.7 * BACKDROP_Z, 2.0 * BACKDROP_Z, BACKDROP_Z, 0)]
+    sc["lights"] = sc["lights"] + [APEX_LIGHT]
+    return sc
+
+
 def shallow_like(sc):
     """per mesh of sc, evenly spaced plates of the same triangle count (same buffers' sizes, a shallow tree)"""
     meshes = []

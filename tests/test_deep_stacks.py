@@ -1,9 +1,14 @@
-"""Stacks past the LDS part.  Every traversal kernel keeps the first `stack_entries` entries (default 16) of a lane's stack in LDS
+"""Stacks past the LDS part.  Every traversal kernel -- the frame kernels, the query kinds, and among them the two with phase
+machines of their own, mode 120 (ao_kernels.hip: closest hit, shadow rays, K any-hit probes) and mode 150 (whitted_kernels.hip:
+closest hit, turn, closest hit, shadow rays), which reset the stack by hand between phases -- keeps the first `stack_entries`
+entries (default 16) of a lane's stack in LDS
 and the deeper ones in the lane's slice of a global spill arena, which the host sizes as 3 * depth4 + 1 - stack_entries entries
 (api_frames.cpp runRender and api_queries.cpp beginQuery; twice as many ints for the closest-point kernel's pairs).  The scenes of
 tests/deep_stack_scenes.py put lanes up to 60 entries deep -- one entry short of that bound -- in every walk class (closest hit, any
 hit, the no-cull walks of the counts and lists, closest point) over every builder's tree, so a wrong stride, a stale depth4 or a
-wrong slice index makes lanes overwrite each other's pending nodes and the comparisons below fail.
+wrong slice index makes lanes overwrite each other's pending nodes and the comparisons below fail.  A mirror in front of chain B
+sends mode 150's mirrored rays 27 to 35 entries deep into it and the shadow rays behind that turn as deep back through it; the
+occlusion probes mode 120 draws on the plate hold 26 to 57.
 
 The CPU tests prove that the GPU tests cannot pass vacuously: the depths come from the oracle's own walk (oracle_set_stack_output,
 oracle_debug_max_sp) or from plain float64 models of the walks the oracle does not have, never from the product kernels.  The GPU
@@ -22,7 +27,10 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ambient_checks as A  # noqa: E402
 import deep_stack_scenes as D  # noqa: E402
+import path_rays_helpers as PH  # noqa: E402
+import path_reference as PR  # noqa: E402
 import ploc_reference as spec  # noqa: E402
 import shaded_query_checks as sq  # noqa: E402
 import test_list_hits as tl  # noqa: E402
@@ -42,6 +50,9 @@ PATH = (2, 2, 77)  # spp, bounces, seed of the mode-200 frames
 SIZES = {"chain": (48, 32), "shadow": (48, 32)}
 MODES = {"chain": (3,), "shadow": (3, 100, 200)}  # chain A: deep camera rays; the plate and chain B: deep shadow and bounce rays
 N_APEX = 512
+DEEP_AO = ((5, 0, 1), (64, 0, 0), (64, 50, 1))  # (ao_samples, ao_radius, ao_sky): at K = 64 lanes wait and start in groups while others are deep
+ROUTE_AO = ((5, 0, 0), (5, 50, 1))
+LAUNCH_COPIES = 129  # copies of a 48 x 32 frame's records: 198144, which "path_pass_paths" = 65536 splits into four launches
 
 
 def _bits(a):
@@ -66,14 +77,22 @@ def oracle_tree(pkg, oracle, sc, builder):
     return L
 
 
-def _frame(oracle, O, cam, mode, w, h, brute_force=False, depth=False):
+def _world(oracle, sc, O=None):
+    """what tests/shaded_query_checks.py needs for the references of modes 120 and 150; O: the oracle over the tree the context holds"""
+    out = {"oracle": oracle, "camera": (sc["camera"]["position"], sc["camera"]["matrix"]), "lights": sc["lights"]}
+    if O is not None:
+        out["O"] = O
+    return out
+
+
+def _frame(oracle, O, cam, mode, w, h, brute_force=False, depth=False, path=PATH):
     """an oracle frame (mode 200: PATH) and, with depth, the deepest stack of every pixel's rays; the frame then also holds
     "secondary_depth", that of the pixel's shadow and bounce rays alone"""
     d, d2 = np.zeros((h, w), dtype=np.uint32), np.zeros((h, w), dtype=np.uint32)
     if depth:
         oracle.lib().oracle_set_stack_output(d.ctypes.data_as(C.c_void_p))
         oracle.lib().oracle_set_stack_output2(d2.ctypes.data_as(C.c_void_p))
-    oracle.set_path_params(*PATH)
+    oracle.set_path_params(*path)
     try:
         f = O.render(cam["position"], cam["matrix"], mode, w, h, brute_force=brute_force)
     finally:
@@ -203,7 +222,7 @@ def refs(pkg, oracle):
     out = {}
     for name, sc in _scenes().items():
         w, h = SIZES[name]
-        entry = {"scene": sc, "rays": query_rays(pkg, oracle, sc, w, h), "trees": {}}
+        entry = {"scene": sc, "rays": query_rays(pkg, oracle, sc, w, h), "trees": {}, "cache": {}}
         for b in BUILDERS:
             O = oracle_tree(pkg, oracle, sc, b)
             t = {"oracle": O, "depth4": O.depth4, "frames": {}, "depth": {}, "brute": {}}
@@ -216,6 +235,16 @@ def refs(pkg, oracle):
     for entry in out.values():
         for t in entry["trees"].values():
             t["oracle"].close()
+
+
+@pytest.fixture(scope="module")
+def mirror_refs(pkg, oracle):
+    """the plate as a mirror in front of chain B: the oracle over every builder's tree"""
+    sc = D.mirror_and_chain_b()
+    out = {"scene": sc, "trees": {b: oracle_tree(pkg, oracle, sc, b) for b in BUILDERS}, "cache": {}}
+    yield out
+    for O in out["trees"].values():
+        O.close()
 
 
 def _walk_equals_brute_force(got, brute, what):
@@ -329,6 +358,72 @@ def test_closest_point_walks_leave_the_lds_part(pkg, refs):
     assert max(deepest.values()) > LDS_MOST
 
 
+def test_mirrored_rays_and_occlusion_probes_leave_the_lds_part(pkg, oracle, refs, mirror_refs):
+    """What the phase machines of modes 150 and 120 send after their camera rays.  Mode 150 over the mirror, chain B and the
+    backdrop (deep_stack_scenes.mirror_and_chain_b): the rays mirrored off the front square (closest hit, nearest child first),
+    the shadow rays to the apex light from where they end on the backdrop (any hit, slot order, through the whole chain), and
+    both as the oracle's mode-200 frame at one bounce sends them: a deep closest hit, then a deep any-hit walk behind one turn.
+    Mode 120 over the plate and chain B: the K = 5 probes of the composed reference (tests/ambient_checks.py) of every pixel
+    that sees the plate.  On every builder's tree some ray of each walk holds more than 16 entries, over the LBVH tree more
+    than 32.
+
+    Measured (depth4 of the mirror scene: deepest mirrored record / deepest shadow ray behind a turn / deepest bounce or shadow
+    ray of the frame; depth4 of the plate scene: deepest probe): SAH 10: 27 / 27 / 27; 9: 26, LBVH 12: 35 / 35 / 35; 19: 57,
+    PLOC 11: 30 / 30 / 30; 10: 29.  All 865 mirrored records, all 215 shadow rays from the backdrop (61 % of them lit) and 1734 of
+    the 3370 probes hold more than 16 entries; 43 % of the probes are occluded."""
+    w, h = SIZES["shadow"]
+    seed = PATH[2]
+    L = A.reference()
+    msc = mirror_refs["scene"]
+    recs = PH.frame_records(PR, msc["camera"], w, h, 0, seed)  # the jittered records of sample 0
+    centre = camera_records(pkg, oracle, refs["shadow"]["scene"], w, h)
+    deepest = {}
+    for b in BUILDERS:
+        # mode 150
+        O = mirror_refs["trees"][b]
+        first = oracle.trace_rays(O, recs)
+        on = np.flatnonzero(first["inst"] == 0)
+        assert len(on) > 100, "the camera sees the mirror"
+        P = recs[on, 0:3] + recs[on, 4:7] * first["t"][on, None]
+        mirrored = pkg.make_rays(np.float32(P + np.float32([0, 0, 1e-3])), np.float32(recs[on, 4:7] * np.float32([1, 1, -1])), tmin=0.0, tmax=D.TMAX)
+        d_mirror = query_depths(oracle, O, mirrored, any_hit=False)
+        second = oracle.trace_rays(O, mirrored)
+        lit = np.flatnonzero(second["inst"] == 2)
+        assert (second["inst"] == 1).sum() > 100 and len(lit) > 100, "mirrored rays end on chain B, and behind it on the backdrop"
+        assert int(d_mirror[lit].max()) > LDS_DEFAULT, "the rays that reach the backdrop crossed the chain deep"
+        P2 = mirrored[lit, 0:3] + mirrored[lit, 4:7] * second["t"][lit, None] - np.float32([0, 0, 1e-3])
+        shadow = pkg.make_rays(np.float32(P2), np.float32(np.float64(D.APEX_LIGHT[0]) - P2), tmin=0.0, tmax=1.0)
+        d_shadow = query_depths(oracle, O, shadow, any_hit=True)
+        lit_share = 1.0 - float(oracle.occluded_rays(O, shadow)["occluded"].mean())
+        assert 0.2 < lit_share < 0.8, "lit and shadowed points behind a turn"
+        f, d_cam = _frame(oracle, O, msc["camera"], 200, w, h, depth=True, path=(1, 1, seed))
+        _walk_equals_brute_force(f, _frame(oracle, O, msc["camera"], 200, w, h, brute_force=True, path=(1, 1, seed)), "the mirror and chain B, " + b)
+        assert f["stats"]["rays_primary"] == w * h + len(on) and 100 < f["stats"]["rays_shadow"] <= len(on), "a mirrored ray per pixel on the mirror, a shadow ray behind it"
+        lit_rgb = f["rgb"].reshape(-1, 3)[first["inst"] == 0]
+        assert len(np.unique(lit_rgb, axis=0)) > len(on) // 4, "the light of a mirrored pixel depends on where its ray arrived"
+        d_frame = int(f["secondary_depth"].max())
+        # mode 120
+        t = refs["shadow"]["trees"][b]
+        f3 = {k: t["frames"][3][k].reshape(-1) for k in ("hit_inst", "hit_prim", "hit_t")}
+        hit = np.flatnonzero(f3["hit_inst"] != MISS)
+        N = sq.geometric_normals(refs["shadow"]["scene"]["meshes"], f3["hit_inst"][hit], f3["hit_prim"][hit], centre[hit, 4:7])[0].astype(np.float32)
+        probes = A.probe_records(L, centre[hit], f3["hit_t"][hit], N, hit, 5, seed, A.UNBOUNDED)
+        d_probe = query_depths(oracle, t["oracle"], probes, any_hit=True)
+        occ = oracle.occluded_rays(t["oracle"], probes)["occluded"]
+        np.testing.assert_array_equal(occ, oracle.occluded_rays(t["oracle"], probes, brute_force=True)["occluded"])
+        print("%s: depth4 %d; mode 150: deepest mirrored record %d (deeper than 16: %d of %d), deepest shadow ray behind a turn %d (deeper than 16: %d of "
+              "%d, lit %.0f %%), deepest bounce or shadow ray of the mode-200 frame at one bounce %d (of all its rays %d); depth4 %d; mode 120: deepest probe %d (deeper than 16: %d of %d, occluded %.0f %%)" % (
+                  b, O.depth4, int(d_mirror.max()), int((d_mirror > LDS_DEFAULT).sum()), len(d_mirror), int(d_shadow.max()), int((d_shadow > LDS_DEFAULT).sum()),
+                  len(d_shadow), 100.0 * lit_share, d_frame, int(d_cam.max()), t["depth4"],
+                  int(d_probe.max()), int((d_probe > LDS_DEFAULT).sum()), len(d_probe), 100.0 * occ.mean()))
+        assert int(d_cam.max()) == d_frame
+        walks = (int(d_mirror.max()), int(d_shadow.max()), d_frame, int(d_probe.max()))
+        assert min(walks) > LDS_DEFAULT and max(walks[:3]) <= 3 * O.depth4 + 1 and walks[3] <= 3 * t["depth4"] + 1, (b, walks)
+        assert 0.2 < occ.mean() < 0.8, "occluded and escaping probes"
+        deepest[b] = min(walks)
+    assert deepest["lbvh"] > LDS_MOST
+
+
 # ---- a depth4 that moves under a live context: the states the GPU test walks through, predicted on the CPU
 
 def refitted_tree(oracle, topology, sc):
@@ -410,7 +505,8 @@ def test_depth4_moves_on_every_route(pkg, oracle):
 
 RING = 4  # frames a context keeps in flight (crt_ctx.h kRing): one spill arena each
 DEFAULTS = (("gpu_build", 0), ("gpu_builder", 0), ("stack_entries", 0), ("path_pipeline", 0), ("path_tile", 0), ("split_units", -1),
-            ("split_rays", 4), ("split_segments", 16), ("list_short_max", 24))
+            ("split_rays", 4), ("split_segments", 16), ("list_short_max", 24), ("path_pass_paths", 1 << 24), ("ao_samples", 16), ("ao_radius", 0),
+            ("ao_sky", 0))
 PATH_FORMS = ((0, 0), (1, 0), (0, 16))  # (path_pipeline, path_tile): path_tile = 16 runs with path_pipeline = 0
 
 
@@ -576,8 +672,9 @@ def _check_winding(pkg, wref, renderer, name, sc, builder, tag):
 @pytest.mark.parametrize("builder", BUILDERS)
 def test_queries_match_their_references(pkg, oracle, refs, list_ref, point_ref, wref, renderer, builder, entries):
     """every query kernel on the camera rays and the apex rays: chain A for the closest-hit and closest-point walks, the plate
-    and chain B for the any-hit and no-cull walks and, its shadow and bounce rays being deep, for the shaded, path-traced and
-    guide queries"""
+    and chain B for the any-hit and no-cull walks and, its shadow and bounce rays being deep, for the shaded (modes 3, 100,
+    120 and 150), path-traced and guide queries; test_whitted_and_ambient_queries_match_the_oracle adds the mirror for mode 150
+    and K = 64 for mode 120"""
     try:
         renderer.set_option("stack_entries", entries)
         tag = "%s, stack_entries=%d" % (builder, entries)
@@ -616,9 +713,59 @@ def test_queries_match_their_references(pkg, oracle, refs, list_ref, point_ref, 
         _check_winding(pkg, wref, renderer, "plate and chain B", sc, builder, tag)
         # shade_rays (modes 3 and 100; host, counting and device forms), path_rays and frame_guides against the frames
         w, h = SIZES["shadow"]
-        sq.frame_records_equal_frames(renderer, t["frames"], w, h, PATH, "plate and chain B, " + tag, scene=sc)
+        sq.frame_records_equal_frames(renderer, t["frames"], w, h, PATH, "plate and chain B, " + tag, scene=sc, cache=e["cache"],
+                                      world=_world(oracle, sc, t["oracle"]))
         apex = e["rays"][w * h:]
         sq.arbitrary_records_equal_trace(renderer, apex, oracle.trace_rays(t["oracle"], apex, brute_force=True), "apex rays, " + tag)
+    finally:
+        _restore(renderer)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entries", STACK_ENTRIES)
+@pytest.mark.parametrize("builder", BUILDERS)
+def test_whitted_and_ambient_queries_match_the_oracle(pkg, oracle, refs, mirror_refs, renderer, builder, entries):
+    """Mode 150 over the mirror and chain B: the three forms and the frame against the oracle's mode-200 frames along the
+    specular chain (shaded_query_checks.whitted_reference), and 129 copies of the frame's records in four launches
+    ("path_pass_paths" = 65536) against one launch, every output bit for bit.  Mode 120 over the plate and chain B at K = 5
+    and K = 64 against the contract composed on the CPU (shaded_query_checks.ambient_reference).
+    test_mirrored_rays_and_occlusion_probes_leave_the_lds_part measures how deep these rays go."""
+    try:
+        renderer.set_option("stack_entries", entries)
+        tag = "%s, stack_entries=%d" % (builder, entries)
+        w, h = SIZES["shadow"]
+        _, bounces, seed = PATH
+        sc, O = mirror_refs["scene"], mirror_refs["trees"][builder]
+        _upload(renderer, sc, builder)
+        _same_tree(renderer, O, "the mirror and chain B, " + tag)
+        renderer.set_path_params(1, bounces, seed)
+        centre, recs = renderer.camera_rays(w, h), renderer.camera_rays(w, h, sample=0)
+        got = sq.collect_whitted_records(renderer, recs, bounces, True, frame=(w, h, centre))
+        ref = sq.whitted_reference(_world(oracle, sc, O), sc, w, h, bounces, seed, tag, mirror_refs["cache"].setdefault(builder, {}))
+        assert (ref["turns"] == 1).sum() > 500 and (ref["turns"] == 0).sum() > 500, "pixels on the mirror, and beside it"
+        sq.assert_whitted_records(got, ref, "the mirror and chain B, " + tag, sc["meshes"])
+        many = np.ascontiguousarray(np.tile(recs, (LAUNCH_COPIES, 1)))
+        assert len(many) > 3 * (1 << 16)
+        renderer.change_shading_mode(150)
+        one = renderer.shade_rays(many)
+        sq._same_bits(one["rgb"].reshape(LAUNCH_COPIES, -1), np.tile(ref["rgb"][bounces].reshape(1, -1), (LAUNCH_COPIES, 1)), tag + ": every copy of the records, rgb")
+        renderer.set_option("path_pass_paths", 1 << 16)
+        for counting, several in enumerate(_counting_forms(renderer, lambda: renderer.shade_rays(many))):
+            for k in sq.SHADE_OUTPUTS:
+                (sq._same_ids if k in ("inst", "prim") else sq._same_bits)(several[k], one[k], "%s: four launches against one, counting=%d, %s" % (tag, counting, k))
+        assert several["stats"]["rays_primary"] == len(many) + LAUNCH_COPIES * int((ref["turns"] >= 1).sum()), tag + ": the counters go on over the launches"
+        renderer.set_option("path_pass_paths", 1 << 24)
+
+        e = refs["shadow"]
+        t, sc = e["trees"][builder], e["scene"]
+        _upload(renderer, sc, builder)
+        centre = renderer.camera_rays(w, h)
+        got = sq.collect_ambient_records(renderer, centre, seed, DEEP_AO, frame=(w, h, centre))
+        ref = sq.ambient_reference(got, sq.frame_hits(t["frames"]), _world(oracle, sc, t["oracle"]), sc, e["cache"])
+        sq.assert_surface(got["surface"], centre, sc, "plate and chain B, " + tag)
+        sq.assert_ambient_records(got, ref, "plate and chain B, " + tag, sc["meshes"])
+        occ = ref["occluded"][0]
+        assert len(ref["hit"]) > 500 and 0.2 < occ.mean() < 0.8 and (occ.sum(axis=1) % 64 != 0).any(), "occluded and escaping probes within one record"
     finally:
         _restore(renderer)
 
@@ -751,6 +898,9 @@ def test_slices_follow_a_depth4_that_moves(pkg, oracle, point_ref, wref, rendere
                     else:
                         r.render_frame(w, h, want=("rgba8",))
                 _check_ray_queries(oracle, r, S, query_rays(pkg, oracle, sc, w, h), what, frame=ref)
+                # a query and a frame of modes 120 and 150: arenas of beginQuery with phase machines of their own over them
+                sq.new_modes_equal_references(r, {3: ref, 100: _frame(oracle, S, sc["camera"], 100, w, h)}, w, h, PATH[1], PATH[2], what, sc,
+                                              _world(oracle, sc, S), settings=ROUTE_AO)
                 _check_closest_points(pkg, point_ref, r, sc, apex_points(pkg, 128, seed=7), what)
                 wpts = winding_points(pkg, sc, seed=11)
                 held = (wpts, wc.assert_winding(pkg, wref, r, sc, tp._tri_records(pkg, sc["meshes"]), wpts, what)["w"][2.0])

@@ -292,7 +292,9 @@ def test_deformation_matches_the_oracle(pkg, scenes, oracle, renderer, gpu_build
             _check_frames_vs_oracle(renderer, S, cam, w, h, MODES)
             # the same frames through camera_rays, shade_rays, path_rays and frame_guides
             sq.frame_records_equal_frames(renderer, {m: S.render(cam["position"], cam["matrix"], m, w, h) for m in (3, 100, 200)}, w, h,
-                                          (2, 2, 99), "deformed scene %d, gpu_build %d" % (si, gpu_build), scene=dict(sc, meshes=moved))
+                                          (2, 2, 99), "deformed scene %d, gpu_build %d" % (si, gpu_build), scene=dict(sc, meshes=moved),
+                                          world={"oracle": oracle, "camera": (cam["position"], cam["matrix"]), "lights": sc["lights"], "O": S,
+                                                 "path_held": (2, 2, 99)})
             for mode in (3, 100):  # hits do not depend on the tree
                 renderer.change_shading_mode(mode)
                 got = _frame(renderer, w, h)[0]
@@ -322,6 +324,20 @@ def test_deformation_matches_the_oracle(pkg, scenes, oracle, renderer, gpu_build
         oracle.set_path_params(4, 3, 1234)
 
 
+def _shaded_records_vs_oracle(renderer, oracle, S, sc, moved, what, w=48, h=32):
+    """a small frame of the moved scene through camera_rays, shade_rays (modes 3, 100, 120 and 150), path_rays and frame_guides
+    against the oracle over the exported tree S (tests/shaded_query_checks.py); mode 120's bounded reach follows the root box
+    as exported now"""
+    cam = sc["camera"]
+    oracle.set_path_params(2, 2, 99)
+    try:
+        frames = {m: S.render(cam["position"], cam["matrix"], m, w, h) for m in (3, 100, 200)}
+    finally:
+        oracle.set_path_params(4, 3, 1234)
+    sq.frame_records_equal_frames(renderer, frames, w, h, (2, 2, 99), what, scene=dict(sc, meshes=moved),
+                                  world={"oracle": oracle, "camera": (cam["position"], cam["matrix"]), "lights": sc["lights"], "O": S})
+
+
 @pytest.mark.gpu
 def test_transforms_on_the_dragon(pkg, scenes, oracle, renderer, dragon):
     sc = _with_normals(scenes, dragon)
@@ -346,6 +362,7 @@ def test_transforms_on_the_dragon(pkg, scenes, oracle, renderer, dragon):
     S = oracle.OracleScene(moved, sc["lights"], sc["materials"])
     S.set_bvh(nodes, tris, shade)
     _check_frames_vs_oracle(renderer, S, cam, w, h, (3, 100))
+    _shaded_records_vs_oracle(renderer, oracle, S, sc, moved, "the dragon turned, the ground scaled")
     fresh = oracle.OracleScene(moved, sc["lights"], sc["materials"])
     renderer.change_shading_mode(100)
     got = _frame(renderer, w, h)[0]
@@ -364,6 +381,9 @@ def test_transforms_on_the_dragon(pkg, scenes, oracle, renderer, dragon):
     xyz, _ = renderer.mesh_vertices(dragon_mesh)
     assert np.array_equal(_bits(xyz), _bits(moved[dragon_mesh]["vertices"]))
     assert not np.array_equal(renderer.bvh_export4q()[0]["lo"], lo0)
+    S = oracle.OracleScene(moved, sc["lights"], sc["materials"])
+    S.set_bvh(*renderer.bvh_export())
+    _shaded_records_vs_oracle(renderer, oracle, S, sc, moved, "the dragon moved out of the root box")
     import torch
     W, H, n_ranks = 320, 180, 4
     cam_far = cam

@@ -698,7 +698,7 @@ def _check_gpu(pkg, oracle, wref, r, sc, refs, what, same_tree=None):
     # shade_rays, path_rays and frame_guides: the frame's camera_rays, the generic rays and the poses
     scene = {"meshes": sc["meshes"], "materials": sc["materials"], "textures": sc.get("textures")}
     sq.frame_records_equal_frames(r, refs["frames"], W, H, PATH_PARAMS, what, scene=scene, texture_color=oracle.texture_color,
-                                  cache=refs["shaded_cache"])
+                                  cache=refs["shaded_cache"], world={"oracle": oracle, "camera": (cam["position"], cam["matrix"]), "lights": sc["lights"], "path_held": PATH_PARAMS})
     sq.arbitrary_records_equal_trace(r, rays, refs["trace"], what, meshes=sc["meshes"])
     sq.pose_records_equal_oracle(r, refs["poses"], what, meshes=sc["meshes"])
     wc.assert_winding(pkg, wref, r, sc, refs["records"], refs["winding_points"], what)

@@ -9,15 +9,15 @@ tests/ao_reference.c, their occlusion over (0, R) from occluded(), R restated fr
 sees everything, the inside of a closed box nothing, the foot of a wall half.
 
 The scene (y up): a floor, a closed box floating above it, a tall wall and a seeded triangle soup: 216 triangles."""
-import ctypes as C
 import os
-import shutil
 import struct
 import subprocess
 import zlib
 
 import numpy as np
 import pytest
+
+from ambient_checks import ref  # noqa: F401  (fixture: tests/ao_reference.c)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MISS = 0xFFFFFFFF
@@ -88,28 +88,7 @@ def make_rays():
     return rays
 
 
-# ---- the restatement (tests/ao_reference.c)
-
-@pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if cc is None:
-        pytest.fail("no C compiler for tests/ao_reference.c")
-    out = str(tmp_path_factory.mktemp("ao_reference") / "libao_reference.so")
-    subprocess.check_call([cc, "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", os.path.join(ROOT, "tests", "ao_reference.c"),
-                           "-o", out, "-lm"])
-    L = C.CDLL(out)
-    vp, u32 = C.c_void_p, C.c_uint32
-    L.ao_ref_bounce.argtypes = [u32, vp, vp, vp, vp]
-    L.ao_ref_origins.argtypes = [u32, vp, vp, vp, vp]
-    L.ao_ref_directions.argtypes = [u32, vp, u32, u32, vp, vp]
-    L.ao_ref_radius.argtypes = [u32, vp]
-    L.ao_ref_radius.restype = C.c_float
-    L.ao_ref_colour.argtypes = [u32, vp, u32, C.c_int, vp, vp, vp, vp]
-    for f in (L.ao_ref_bounce, L.ao_ref_origins, L.ao_ref_directions, L.ao_ref_colour):
-        f.restype = None
-    return L
-
+# ---- the restatement (tests/ao_reference.c, loaded by tests/ambient_checks.py)
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)

@@ -412,6 +412,20 @@ def _shaded_outputs(r, rays, w, h):
         out.update({"path_rays %s, %s" % (k, tag): paths[k] for k in ("rgb",) + sq.HIT_OUTPUTS})
     guides = r.frame_guides(w, h)
     out.update({"frame_guides " + k: guides[k] for k in ("normal", "albedo", "t")})
+    # the kernels with phase machines of their own: ambient occlusion (bounded by the root box) and Whitted
+    r.set_option("ao_samples", 5)
+    r.set_option("ao_radius", 50)
+    r.set_option("ao_sky", 1)
+    for mode in (120, 150):
+        r.change_shading_mode(mode)
+        for tag, recs in (("rays", rays), ("camera rays", centre)):
+            shaded = r.shade_rays(recs)
+            out.update({"shade_rays mode %d %s, %s" % (mode, k, tag): shaded[k] for k in sq.SHADE_OUTPUTS})
+        frame = r.render_frame(w, h)
+        out.update({"render_frame mode %d %s" % (mode, k): frame[k] for k in ("rgb", "hit_t", "hit_inst", "hit_prim")})
+    for name, v in sq.AO_DEFAULTS:
+        r.set_option(name, v)
+    r.change_shading_mode(100)
     return out
 
 
@@ -508,6 +522,11 @@ def test_rebuild_of_moved_meshes_equals_a_fresh_build(pkg, scenes, oracle, drago
         for key in rebuilt:
             assert np.array_equal(rebuilt[key].view(np.uint32), fresh[key].view(np.uint32)), "%s: rebuilt and fresh differ" % key
         assert (rebuilt["shade_rays inst, rays"] != 0xFFFFFFFF).sum() > 500 and (rebuilt["path_rays inst, camera rays"] != 0xFFFFFFFF).sum() > w * h // 10
+        # modes 120 and 150 of the rebuilt context against the oracle over its tree and brute-force probes (a small frame)
+        small = {m: S.render(cam["position"], cam["matrix"], m, 48, 32) for m in (3, 100)}
+        sq.new_modes_equal_references(r, small, 48, 32, 2, 99, "rebuilt, builder %d" % builder, dict(sc, meshes=moved),
+                                      {"oracle": oracle, "camera": (cam["position"], cam["matrix"]), "lights": sc["lights"], "O": S, "path_held": (2, 2, 99)},
+                                      held=(2, 99, 100))
         # a later deformation + refit refits the rebuilt shape
         v2 = (moved[0]["vertices"] + np.float32(0.02)).astype(np.float32)
         r.update_vertices(0, v2)

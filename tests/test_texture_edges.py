@@ -453,7 +453,8 @@ def test_gpu_uv_records_reach_leaf_order(pkg, oracle, scenes, name, route):
         r.set_option("path_pipeline", 0)
         now = dict(sc, meshes=meshes)
         got = sq.frame_records_equal_frames(r, _oracle_frames(oracle, now, cam), T.W, T.H, ROUTE_PATH_PARAMS, "%s %s" % (name, route),
-                                            scene=now, texture_color=oracle.texture_color)
+                                            scene=now, texture_color=oracle.texture_color,
+                                            world={"oracle": oracle, "camera": (cam["position"], cam["matrix"]), "lights": sc["lights"], "miss": R.MISS_RGB})
         hit = got["guides"]["t"] != f32(sq.TMAX)
         assert len(np.unique(got["guides"]["albedo"][hit], axis=0)) >= 4, "the textures show in the albedo guide"
     finally:

@@ -378,7 +378,8 @@ def _gpu_rays_vs_brute(pkg, renderer, oracle, S, sc, rng, what, cache=None):
             frames[mode] = cache[(cname, mode)]
         tag = "%s %s camera" % (what, cname)
         renderer.set_camera(cam["position"], cam["matrix"])
-        sq.frame_records_equal_frames(renderer, frames, w, h, (1, 2, 77), tag, scene=sc)
+        world = {"oracle": oracle, "camera": (cam["position"], cam["matrix"]), "lights": sc["lights"], "O": S, "brute_force": True, "path_held": (1, 2, 77)}
+        sq.frame_records_equal_frames(renderer, frames, w, h, (1, 2, 77), tag, scene=sc, cache=cache.setdefault(("shaded", cname), {}), world=world)
         sq.arbitrary_records_equal_trace(renderer, rays, bf, tag)
 
 
