@@ -404,30 +404,24 @@ int runAccumResolve(crt_ctx* c, const RenderParams& p, crt_frame_stats* stats)
     return stats ? readStats(c, stats) : CRT_OK;
 }
 
-// A frame in mode 150 (CRT_MODE_WHITTED) is a query, not a launch of the render kernel: the pixel-centre camera rays, the Whitted
-// query kind over them and the quantisation of its float colour (runWhitted, api_queries.cpp), on the stream's query arena.
-// Nothing of runRender runs: the frame ring, the launch orders and their cost state stay as they are.
-int runWhittedFrame(crt_ctx* c, const RenderParams& p, crt_frame_stats* stats)
+// A frame in mode 150 (CRT_MODE_WHITTED) or 120 (CRT_MODE_AMBIENT) is a query, not a launch of the render kernel: the
+// pixel-centre camera rays, the mode's query kind over them and the quantisation of its float colour (runShaded,
+// api_queries.cpp), on the stream's query arena.  Nothing of runRender runs: the frame ring, the launch orders and their cost
+// state stay as they are.
+int runQueryFrame(crt_ctx* c, const RenderParams& p, crt_frame_stats* stats)
 {
-    if (const int rc = checkFrameSize(c, "a frame in shading mode 150", p.width, p.height)) return rc; // (the camera-ray kernel's limit)
+    const bool whitted = p.mode == CRT_MODE_WHITTED;
+    const char* what = whitted ? "a frame in shading mode 150" : "a frame in shading mode 120";
+    if (const int rc = checkFrameSize(c, what, p.width, p.height)) return rc; // (the camera-ray kernel's limit)
     void* const out[7] = { p.rgb_f32, nullptr, nullptr, p.hit_t, nullptr, p.hit_inst, p.hit_prim };
-    const WhittedFrame frame = { p.width, p.height, p.rgba8 };
-    return runWhitted(c, p.width * p.height, nullptr, out, &frame, stats);
-}
-// A frame in mode 120 (CRT_MODE_AMBIENT), the same way: the camera rays, the ambient-occlusion query kind and the quantisation
-// (runAmbientFrame, api_queries.cpp)
-int runAmbientModeFrame(crt_ctx* c, const RenderParams& p, crt_frame_stats* stats)
-{
-    if (const int rc = checkFrameSize(c, "a frame in shading mode 120", p.width, p.height)) return rc; // (the camera-ray kernel's limit)
-    void* const out[7] = { p.rgb_f32, nullptr, nullptr, p.hit_t, nullptr, p.hit_inst, p.hit_prim };
-    return runAmbientFrame(c, out, WhittedFrame{ p.width, p.height, p.rgba8 }, stats);
+    const ShadedFrame frame = { p.width, p.height, p.rgba8 };
+    return runShaded(c, whitted ? crt::kQueryWhitted : crt::kQueryAmbient, p.width * p.height, nullptr, out, &frame, stats);
 }
 
 // one frame of an entry point that accumulates (kind: kAccFrame / kAccTiles)
 int runFrame(crt_ctx* c, RenderParams& p, crt_frame_stats* stats, uint32_t kind)
 {
-    if (p.mode == CRT_MODE_WHITTED) return runWhittedFrame(c, p, stats);
-    if (p.mode == CRT_MODE_AMBIENT) return runAmbientModeFrame(c, p, stats);
+    if (p.mode == CRT_MODE_WHITTED || p.mode == CRT_MODE_AMBIENT) return runQueryFrame(c, p, stats);
     const int rc = beginAccum(c, p, kind);
     if (rc) return rc;
     return p.acc_sum && p.spp == 0u ? runAccumResolve(c, p, stats) : runRender(c, p, stats);

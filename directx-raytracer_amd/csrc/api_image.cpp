@@ -54,9 +54,9 @@ int runFrameGuides(crt_ctx* c, uint32_t w, uint32_t h, void* d_normal, void* d_a
     std::memset(&q, 0, sizeof(q));
     shadeTables(c, q);
     q.mode = 3u;
-    q.normal = static_cast<float*>(d_normal);
-    q.albedo = static_cast<float*>(d_albedo);
-    q.t = static_cast<float*>(d_t);
+    q.out.normal = static_cast<float*>(d_normal);
+    q.out.albedo = static_cast<float*>(d_albedo);
+    q.out.t = static_cast<float*>(d_t);
     QueryLaunch ql;
     if (const int rc = beginQuery(c, crt::kQueryShade, n, stats, ql, up256(static_cast<size_t>(n) * 32u))) return rc;
     int hrc = crt::launchCameraRays(cameraRayParams(c, w, h, CRT_SAMPLE_CENTRE, ql.extra), c->stream);

@@ -92,6 +92,26 @@ int ensureMoments(crt_ctx* c)
     return CRT_OK;
 }
 
+// the specular term of mode 100's light sum, from the options
+template <class Q> void phongState(const crt_ctx* c, Q& q)
+{
+    q.phong_ks = static_cast<float>(c->phongKsPermille) / 1000.0f;
+    q.phong_exp = c->phongExp;
+}
+// the outputs of crt_shade_rays* from the device pointers d[0..6]
+crt::ShadedOutputs shadedOutputs(void* const d[kQueryOutputs])
+{
+    static_assert(kQueryOutputs == 7, "the outputs of crt_shade_rays*");
+    return { static_cast<float*>(d[0]), static_cast<float*>(d[1]), static_cast<float*>(d[2]), static_cast<float*>(d[3]),
+             static_cast<float*>(d[4]), static_cast<uint32_t*>(d[5]), static_cast<uint32_t*>(d[6]) };
+}
+// the same outputs from record r0 on (a NULL stays NULL)
+crt::ShadedOutputs offsetOutputs(const crt::ShadedOutputs& o, uint64_t r0)
+{
+    const auto at = [r0](auto* p, uint32_t per) { return p ? p + per * r0 : nullptr; };
+    return { at(o.rgb, 3u), at(o.normal, 3u), at(o.albedo, 3u), at(o.t, 1u), at(o.uv, 2u), at(o.inst, 1u), at(o.prim, 1u) };
+}
+
 } // namespace
 
 // the scene's shading tables (sceneTables) and the context's shading state of a shaded query
@@ -99,8 +119,7 @@ void crtapi::shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q)
 {
     sceneTables(c, q);
     q.mode = c->mode;
-    q.phong_ks = static_cast<float>(c->phongKsPermille) / 1000.0f;
-    q.phong_exp = c->phongExp;
+    phongState(c, q);
 }
 
 // crt_shade_rays* and the frames in mode 150: whether the context's mode asks for the Whitted kind (101..149 and 151..199 are mode 100)
@@ -171,32 +190,19 @@ int fillOccupancy(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], Qu
 // crt_shade_rays*: the closest hit and the context's shading mode at it (shade_kernels.hip)
 int fillShade(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
 {
-    p.shade.rgb = static_cast<float*>(d[0]);
-    p.shade.normal = static_cast<float*>(d[1]);
-    p.shade.albedo = static_cast<float*>(d[2]);
-    p.shade.t = static_cast<float*>(d[3]);
-    p.shade.uv = static_cast<float*>(d[4]);
-    p.shade.inst = static_cast<uint32_t*>(d[5]);
-    p.shade.prim = static_cast<uint32_t*>(d[6]);
+    p.shade.out = shadedOutputs(d);
     shadeTables(c, p.shade);
     innerMin = c->tuneInnerMin;
     return CRT_OK;
 }
-// crt_shade_rays* in mode 150 (whitted_kernels.hip): the outputs of fillShade; the record state comes from the launch's arena (runWhitted)
+// crt_shade_rays* in mode 150 (whitted_kernels.hip): the outputs of fillShade; the record state comes from the launch's arena (runShaded)
 int fillWhitted(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
 {
     crt::WhittedQueryParams& q = p.whitted;
-    q.rgb = static_cast<float*>(d[0]);
-    q.normal = static_cast<float*>(d[1]);
-    q.albedo = static_cast<float*>(d[2]);
-    q.t = static_cast<float*>(d[3]);
-    q.uv = static_cast<float*>(d[4]);
-    q.inst = static_cast<uint32_t*>(d[5]);
-    q.prim = static_cast<uint32_t*>(d[6]);
+    q.out = shadedOutputs(d);
     sceneTables(c, q);
     q.max_bounces = c->pathBounces;
-    q.phong_ks = static_cast<float>(c->phongKsPermille) / 1000.0f;
-    q.phong_exp = c->phongExp;
+    phongState(c, q);
     innerMin = c->tuneInnerMin;
     return CRT_OK;
 }
@@ -204,16 +210,9 @@ int fillWhitted(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], Quer
 int fillAmbient(crt_ctx* c, const QuerySpec&, void* const d[kQueryOutputs], QueryParams& p, uint32_t& innerMin)
 {
     crt::AmbientQueryParams& q = p.ambient;
-    q.rgb = static_cast<float*>(d[0]);
-    q.normal = static_cast<float*>(d[1]);
-    q.albedo = static_cast<float*>(d[2]);
-    q.t = static_cast<float*>(d[3]);
-    q.uv = static_cast<float*>(d[4]);
-    q.inst = static_cast<uint32_t*>(d[5]);
-    q.prim = static_cast<uint32_t*>(d[6]);
+    q.out = shadedOutputs(d);
     sceneTables(c, q);
-    q.phong_ks = static_cast<float>(c->phongKsPermille) / 1000.0f;
-    q.phong_exp = c->phongExp;
+    phongState(c, q);
     q.samples = c->aoSamples;
     q.radius = ambientRadius(c);
     q.sky = c->aoSky;
@@ -371,76 +370,50 @@ crt::QueryCommon crtapi::queryCommon(const crt_ctx* c, const QueryLaunch& ql, co
     return q;
 }
 
-// A Whitted query of n records into the outputs d (fillWhitted's order), over one arena between one beginQuery and one endQuery.
-// The arena holds the records' state (kWhittedStateBytes each), so a launch covers at most "path_pass_paths" records, as a pass of
-// crt_path_rays* does; a larger buffer runs as several launches over blocks of records.
-// frame (crt_render_frame* in mode 150): d_records is NULL and the records are the frame's pixel-centre camera rays, made in
-// the arena by the camera-ray kernel, all in one launch; behind the query the float colour (d[0], or scratch of the arena when
-// the caller wants none) is quantised into frame->rgba8.  The other frame outputs are the query's own, bit for bit: hit_t is
-// t (on a miss the record's tmax, which is the frames' 10000), hit_inst / hit_prim are inst / prim.
-int crtapi::runWhitted(crt_ctx* c, uint32_t n, const void* d_records, void* const d[7], const WhittedFrame* frame, crt_frame_stats* stats)
+// A query of the Whitted or the ambient-occlusion kind of n records into the outputs d (shadedOutputs' order), over one arena
+// between one beginQuery and one endQuery.
+// The Whitted kind keeps the records' state (kWhittedStateBytes each) in the arena, so a launch covers at most "path_pass_paths"
+// records, as a pass of crt_path_rays* does; a larger buffer runs as several launches over blocks of records.  (The ambient
+// kind keeps none: crt_shade_rays* in mode 120 goes through runKind as any other kind, and only its frames come here.)
+// frame (crt_render_frame* in modes 150 and 120): d_records is NULL and the records are the frame's pixel-centre camera rays,
+// made in the arena by the camera-ray kernel, all in one launch; behind the query the float colour (d[0], or scratch of the
+// arena when the caller wants none) is quantised into frame->rgba8.  The other frame outputs are the query's own, bit for bit:
+// hit_t is t (on a miss the record's tmax, which is the frames' 10000), hit_inst / hit_prim are inst / prim.
+int crtapi::runShaded(crt_ctx* c, QueryKind kind, uint32_t n, const void* d_records, void* const d[7], const ShadedFrame* frame,
+                      crt_frame_stats* stats)
 {
-    static_assert(kQueryOutputs == 7, "the outputs of crt_shade_rays*");
+    const bool whitted = kind == crt::kQueryWhitted;
     QueryParams p;
     std::memset(&p, 0, sizeof(p));
     uint32_t innerMin = 0;
-    if (const int rc = fillWhitted(c, QuerySpec{}, d, p, innerMin)) return rc;
-    crt::WhittedQueryParams& q = p.whitted;
+    if (const int rc = kQueryShapes[kind].fill(c, QuerySpec{}, d, p, innerMin)) return rc;
+    crt::ShadedOutputs& out = whitted ? p.whitted.out : p.ambient.out;
     const uint32_t block = frame ? n : std::min(n, c->tunePathPassPaths);
-    const size_t stateBytes = up256(static_cast<size_t>(block) * crt::kWhittedStateBytes);
-    const size_t rayBytes = frame ? up256(static_cast<size_t>(n) * 32u) : 0u, rgbBytes = frame && !q.rgb ? up256(static_cast<size_t>(n) * 12u) : 0u;
+    const size_t stateBytes = whitted ? up256(static_cast<size_t>(block) * crt::kWhittedStateBytes) : 0u;
+    const size_t rayBytes = frame ? up256(static_cast<size_t>(n) * 32u) : 0u, rgbBytes = frame && !out.rgb ? up256(static_cast<size_t>(n) * 12u) : 0u;
     QueryLaunch ql;
-    if (const int rc = beginQuery(c, crt::kQueryWhitted, block, stats, ql, stateBytes + rayBytes + rgbBytes)) return rc;
-    q.state = ql.extra;
+    if (const int rc = beginQuery(c, kind, block, stats, ql, stateBytes + rayBytes + rgbBytes)) return rc;
+    if (whitted) p.whitted.state = ql.extra;
     int hrc = 0;
     if (frame) {
         d_records = ql.extra + stateBytes;
-        if (!q.rgb) q.rgb = reinterpret_cast<float*>(ql.extra + stateBytes + rayBytes);
+        if (!out.rgb) out.rgb = reinterpret_cast<float*>(ql.extra + stateBytes + rayBytes);
         hrc = crt::launchCameraRays(cameraRayParams(c, frame->width, frame->height, CRT_SAMPLE_CENTRE, ql.extra + stateBytes), c->stream);
     }
-    const crt::WhittedQueryParams all = q; // the outputs of record 0
+    const crt::ShadedOutputs all = out; // the outputs of record 0
     for (uint64_t r0 = 0; r0 < n && hrc == 0; r0 += block) {
         const uint32_t nr = static_cast<uint32_t>(std::min<uint64_t>(block, n - r0));
         if (r0 != 0u) HIP_TRY(c, hipMemsetAsync(ql.cursor, 0, sizeof(uint32_t), c->stream)); // (the counters go on counting)
         uint32_t chunk = 0, grid = 0;
-        crt::queryLayout(nr, c->queries.resident[crt::kQueryWhitted], chunk, grid);
+        crt::queryLayout(nr, c->queries.resident[kind], chunk, grid);
         grid = std::min(grid, ql.grid); // (the spill area is sized for ql.grid workgroups, the largest block's)
-        q.c = queryCommon(c, ql, static_cast<const unsigned char*>(d_records) + 32u * r0, nr, innerMin);
-        q.c.chunk = chunk;
-        q.rgb = all.rgb ? all.rgb + 3u * r0 : nullptr;
-        q.normal = all.normal ? all.normal + 3u * r0 : nullptr;
-        q.albedo = all.albedo ? all.albedo + 3u * r0 : nullptr;
-        q.t = all.t ? all.t + r0 : nullptr;
-        q.uv = all.uv ? all.uv + 2u * r0 : nullptr;
-        q.inst = all.inst ? all.inst + r0 : nullptr;
-        q.prim = all.prim ? all.prim + r0 : nullptr;
-        hrc = crt::launchQuery(crt::kQueryWhitted, &q, c->counting, grid, c->stream);
+        p.c = queryCommon(c, ql, static_cast<const unsigned char*>(d_records) + 32u * r0, nr, innerMin);
+        p.c.chunk = chunk;
+        out = offsetOutputs(all, r0);
+        hrc = crt::launchQuery(kind, &p, c->counting, grid, c->stream);
     }
-    if (frame && hrc == 0) hrc = crt::launchWhittedPack(all.rgb, frame->rgba8, n, c->stream);
-    return endQuery(c, crt::kQueryWhitted, n, ql, hrc, stats);
-}
-
-// A frame in mode 120 (crt_render_frame*), as runWhitted's: the records are the frame's pixel-centre camera rays, made in the
-// arena by the camera-ray kernel; the ambient-occlusion kind runs over them in one launch into the outputs d (fillAmbient's
-// order), and the float colour (d[0], or scratch of the arena when the caller wants none) is quantised into frame.rgba8.
-// (crt_shade_rays* in mode 120 needs nothing of this: the kind keeps no record state, so runKind launches it as any other.)
-int crtapi::runAmbientFrame(crt_ctx* c, void* const d[7], const WhittedFrame& frame, crt_frame_stats* stats)
-{
-    QueryParams p;
-    std::memset(&p, 0, sizeof(p));
-    uint32_t innerMin = 0;
-    if (const int rc = fillAmbient(c, QuerySpec{}, d, p, innerMin)) return rc;
-    crt::AmbientQueryParams& q = p.ambient;
-    const uint32_t n = frame.width * frame.height;
-    const size_t rayBytes = up256(static_cast<size_t>(n) * 32u), rgbBytes = q.rgb ? 0u : up256(static_cast<size_t>(n) * 12u);
-    QueryLaunch ql;
-    if (const int rc = beginQuery(c, crt::kQueryAmbient, n, stats, ql, rayBytes + rgbBytes)) return rc;
-    if (!q.rgb) q.rgb = reinterpret_cast<float*>(ql.extra + rayBytes);
-    int hrc = crt::launchCameraRays(cameraRayParams(c, frame.width, frame.height, CRT_SAMPLE_CENTRE, ql.extra), c->stream);
-    q.c = queryCommon(c, ql, ql.extra, n, innerMin);
-    if (hrc == 0) hrc = crt::launchQuery(crt::kQueryAmbient, &q, c->counting, ql.grid, c->stream);
-    if (hrc == 0) hrc = crt::launchWhittedPack(q.rgb, frame.rgba8, n, c->stream);
-    return endQuery(c, crt::kQueryAmbient, n, ql, hrc, stats);
+    if (frame && hrc == 0) hrc = crt::launchRgbToRgba8(all.rgb, frame->rgba8, n, c->stream);
+    return endQuery(c, kind, n, ql, hrc, stats);
 }
 
 namespace {
@@ -448,7 +421,7 @@ namespace {
 // a query of any kind with an entry point: its fill, then one launch between beginQuery and endQuery
 int runKind(crt_ctx* c, const QuerySpec& s, uint32_t n, const void* d_records, void* const d[kQueryOutputs], crt_frame_stats* stats)
 {
-    if (s.kind == crt::kQueryWhitted) return runWhitted(c, n, d_records, d, nullptr, stats);
+    if (s.kind == crt::kQueryWhitted) return runShaded(c, s.kind, n, d_records, d, nullptr, stats);
     QueryParams p;
     std::memset(&p, 0, sizeof(p));
     uint32_t innerMin = 0;

@@ -329,12 +329,12 @@ int checkDevicePointers(crt_ctx* c, const char* what, std::initializer_list<cons
 void shadeTables(const crt_ctx* c, crt::ShadeQueryParams& q);
 bool whittedMode(const crt_ctx* c);
 bool ambientMode(const crt_ctx* c);
-struct WhittedFrame {
+struct ShadedFrame { // a frame in mode 150 or 120: a query over its camera rays
     uint32_t width, height;
     uint32_t* rgba8;
 };
-int runWhitted(crt_ctx* c, uint32_t n, const void* d_records, void* const d[7], const WhittedFrame* frame, crt_frame_stats* stats);
-int runAmbientFrame(crt_ctx* c, void* const d[7], const WhittedFrame& frame, crt_frame_stats* stats);
+int runShaded(crt_ctx* c, crt::QueryKind kind, uint32_t n, const void* d_records, void* const d[7], const ShadedFrame* frame,
+              crt_frame_stats* stats);
 int beginQuery(crt_ctx* c, crt::QueryKind kind, uint32_t n, crt_frame_stats* stats, QueryLaunch& ql, size_t extraBytes = 0,
                uint32_t minGrid = 0);
 int endQuery(crt_ctx* c, crt::QueryKind kind, uint32_t n, const QueryLaunch& ql, int rc, crt_frame_stats* stats);

@@ -1,17 +1,13 @@
 // HIP kernels for gfx950 (MI355X): path-traced ray queries on caller-supplied rays (crt_path_rays*) -- the frames' mode-200
 // path (path_kernels.hip; specification: oracle trace_path) from its first segment on, for records instead of pixels.
 //
-// One job of runQuery (query.hip.h), beside ShadeJob (shade_kernels.hip).  A work item is a (record, sample) pair, numbered
+// One job of runQuery (query.hip.h) on the phase machine of lit_job.hip.h.  A work item is a (record, sample) pair, numbered
 // sample-major inside a pass (item = sample-in-pass * records + record), so neighbouring lanes hold neighbouring records of
-// the same sample and one record at thousands of samples still fills the machine.  A lane's item goes through phases inside
-// step():
-//   closest hit   bounce 0: the record prescaled by 2^e (queryRay), exactly the traversal of crt_trace_rays; later bounces:
-//                 the plain unit-direction ray over (0, 10000), the frames' bounce ray
+// the same sample and one record at thousands of samples still fills the machine.  What it adds:
+//   closest hit   later bounces: the plain unit-direction ray over (0, 10000), the frames' bounce ray (goOn)
 //   end of it     bounce 0 of the call's first sample writes the hit outputs.  A miss adds throughput x miss colour and ends
 //                 the path; CONSTANT emits and ends it; REFLECTIVE / REFRACTIVE turn the lane into the next closest-hit
-//                 traversal at once; DIFFUSE goes on to its lights:
-//   shadow ray    for each light with a positive cosine, in light order, an any-hit traversal from the root (lightTerm,
-//                 addLight<false>: the code ShadeJob and the frames' directLight add a light with)
+//                 traversal at once; DIFFUSE goes on to its lights (addLight<false>)
 //   after the last light the gathered light joins the radiance, the cosine-weighted bounce is drawn and the lane becomes a
 //   closest-hit traversal again -- where ShadeJob ends the record.  A path that ends leaves its radiance in the item's slot
 //   of the scratch array; `cur` becomes kDone only then, so that runQuery refills the lane.
@@ -24,8 +20,7 @@
 // shading.hip.h that the frames' streamShade and pathKernel go through.
 //
 // Arithmetic contract: identical, operation for operation, to oracle/crt_oracle.c (compiled with -ffp-contract=off).
-#include "query.hip.h"
-#include "shading.hip.h"
+#include "lit_job.hip.h"
 
 namespace crt {
 namespace {
@@ -38,52 +33,22 @@ namespace {
 constexpr int kPathQueryWaves = CRT_PATH_QUERY_WAVES;
 
 template <bool CNT>
-struct PathJob {
-    static constexpr int kClosest = -1; // `light` while a closest-hit ray (the record's own, or a bounce ray) is walked
-    static constexpr int kIdle = -2;    // no item, or a finished one
-
-    const PathQueryParams& q;
-    Stack stack;
-    Ray r;    // closest phase: bounce 0 the prescaled record, later the bounce ray; shadow phase: the shadow ray (r.o = the biased hit point)
-    int cur;
-    int light = kIdle;  // >= 0: the light whose shadow ray is being walked
-    // Registers are what limits this kernel, so nothing is held that can be had again:
-    uint32_t ib = 0;    // the work item of the pass = its scratch slot (<= 2^25 items a pass), the bounce count above it
-    float tlim = 0.0f;  // closest phase: tmin (bounce 0: the record's, prescaled; later 0); shadow phase: tmax = the light's distance
-    // (tmax of a closest phase: the record's again at its end, kTMax later; the cull bound follows from the best hit or from
-    // the distance; the RNG state travels in the w of the item's throughput slot: only a diffuse bounce draws)
+struct PathJob : LitJob<PathJob<CNT>, PathQueryParams, CNT> {
+    using Base = LitJob<PathJob<CNT>, PathQueryParams, CNT>;
+    using Base::q; using Base::stack; using Base::r; using Base::cur; using Base::light; using Base::tlim;
+    using Base::kClosest; using Base::kIdle; using Base::kN; using Base::kAlbedo; using Base::hit; using Base::setHit;
+    using Base::vec; using Base::setVec; using Base::nextLight;
+    // Registers are what limits this kernel, so nothing is held that can be had again.  The base's
+    // record word is the work item of the pass = its scratch slot (<= 2^25 items a pass), the bounce count above it; the RNG
+    // state travels in the w of the item's throughput slot: only a diffuse bounce draws
     static constexpr uint32_t kItemBits = 25u, kItemMask = (1u << kItemBits) - 1u;
-    __device__ __forceinline__ uint32_t item() const { return ib & kItemMask; }
-    __device__ __forceinline__ uint32_t bounce() const { return ib >> kItemBits; }
-    // One set of registers for the two phases, as ShadeJob's: closest phase the best hit {t, u, v, tri, gid} (w[0..4]), shadow
-    // phases the normal, the albedo and the direct light gathered so far (w[0..2], [3..5], [6..8])
-    float w[9];
-    __device__ __forceinline__ Hit hit() const { return Hit{ w[0], w[1], w[2], __float_as_uint(w[3]), __float_as_uint(w[4]) }; }
-    __device__ __forceinline__ void setHit(const Hit& h) { w[0] = h.t; w[1] = h.u; w[2] = h.v; w[3] = __uint_as_float(h.tri); w[4] = __uint_as_float(h.gid); }
-    __device__ __forceinline__ F3 vec(int k) const { return f3(w[3 * k], w[3 * k + 1], w[3 * k + 2]); }
-    __device__ __forceinline__ void setVec(int k, F3 v) { w[3 * k] = v.x; w[3 * k + 1] = v.y; w[3 * k + 2] = v.z; }
-    static constexpr int kN = 0, kAlbedo = 1, kAux = 2;
-    uint32_t iters = 0;
-    uint32_t cntShadow = 0, cntBounce = 0;
+    __device__ __forceinline__ uint32_t item() const { return Base::idx & kItemMask; }
+    __device__ __forceinline__ uint32_t bounce() const { return Base::idx >> kItemBits; }
+    static constexpr int kAux = Base::kRgb; // the direct light gathered so far
+    uint32_t cntBounce = 0;
 
-    __device__ __forceinline__ explicit PathJob(const PathQueryParams& params) : q(params)
-    {
-        r = makeRay(f3(0.0f, 0.0f, 0.0f), f3(0.0f, 0.0f, 1.0f));
-        for (float& x : w) x = 0.0f;
-    }
-    // (counting) the wavefront's shadow and bounce rays: runQuery adds the fetch counts itself.  Runs when runQuery's loop has
-    // ended, every lane active
-    __device__ __forceinline__ ~PathJob()
-    {
-        if (CNT) {
-            const uint32_t s = waveTotal(cntShadow), b = waveTotal(cntBounce);
-            if ((threadIdx.x & 63u) == 0u) {
-                atomicAdd(&q.c.counters[2], static_cast<unsigned long long>(s));
-                atomicAdd(&q.c.counters[3], static_cast<unsigned long long>(b));
-            }
-        }
-    }
-    __device__ __forceinline__ void retire(uint32_t) {}
+    __device__ __forceinline__ explicit PathJob(const PathQueryParams& params) : Base(params) {}
+    __device__ __forceinline__ ~PathJob() { this->template addCounts<true>(cntBounce); } // the shadow and the bounce rays
     // the item's slot of a scratch array (q.rad, q.thr)
     __device__ __forceinline__ float4 load4(const void* a) const { return static_cast<const float4*>(a)[item()]; }
     __device__ __forceinline__ F3 load3(const void* a) const { const float4 v = load4(a); return f3(v.x, v.y, v.z); }
@@ -93,7 +58,7 @@ struct PathJob {
         const float4* rays = reinterpret_cast<const float4*>(q.c.records);
         const uint32_t sl = i / q.n_records, rec = i - sl * q.n_records;
         const float4 a = rays[2u * static_cast<size_t>(rec)], b = rays[2u * static_cast<size_t>(rec) + 1u];
-        ib = i; // bounce 0
+        Base::idx = i; // bounce 0
         float tmax;
         queryRay(a, b, r, tlim, tmax);
         setHit(Hit{ tmax, 0.0f, 0.0f, 0u, 0u });
@@ -114,7 +79,7 @@ struct PathJob {
     // the path goes on from Po in direction nd: the frames' bounce ray
     __device__ __forceinline__ void goOn(F3 Po, F3 nd)
     {
-        ib += 1u << kItemBits;
+        Base::idx += 1u << kItemBits;
         r = makeRay(Po, nd);
         tlim = 0.0f;
         setHit(Hit{ kTMax, 0.0f, 0.0f, 0u, 0u });
@@ -137,24 +102,7 @@ struct PathJob {
             goOn(Po, nd);
         } else finish();
     }
-    // the shadow ray of the first light from `from` on that sees the surface from its front, or the end of the lights
-    __device__ __forceinline__ void nextLight(uint32_t from, F3 Po)
-    {
-        const LightRec* lights = reinterpret_cast<const LightRec*>(q.lights);
-        for (uint32_t li = from; li < q.n_lights; li++) {
-            const LightTerm lt = lightTerm(lights[li], Po, vec(kN));
-            if (lt.cosv > 0.0f) {
-                r = makeRay(Po, lt.Ld);
-                tlim = lt.dist;
-                stack.sp = 0;
-                cur = LayLegacy::kRoot;
-                light = static_cast<int>(li);
-                if (CNT) cntShadow++;
-                return;
-            }
-        }
-        afterLights(Po);
-    }
+    static constexpr bool kPhong = false; // addLight<false>: no view vector
     // a closest-hit traversal has ended (or, for an untraced record, never began)
     __device__ __forceinline__ void endClosest()
     {
@@ -163,28 +111,17 @@ struct PathJob {
         bool isHit = h.t < kTMax;
         Ray seg = r; // what the shading sees: origin, direction (of seg only o and d are read) and h.t
         if (bounce() == 0u) {
-            // the record as the caller wrote it and the unscaled t (ShadeJob::endClosest)
-            const float4* rays = reinterpret_cast<const float4*>(q.c.records);
+            // the record as the caller wrote it and the unscaled t.  The hit outputs do not depend on the sample: the pass's
+            // first one writes them (NULL in later passes)
             const uint32_t sl = item() / q.n_records, rec = item() - sl * q.n_records;
-            const float4 a = rays[2u * static_cast<size_t>(rec)], b = rays[2u * static_cast<size_t>(rec) + 1u];
-            Ray scaled;
-            float tminRec, tmaxRec;
-            const int e = queryRay(a, b, scaled, tminRec, tmaxRec);
-            isHit = h.t < tmaxRec;
-            seg.o = f3(a.x, a.y, a.z);
-            seg.d = f3(b.x, b.y, b.z);
-            h.t = isHit ? __builtin_amdgcn_ldexpf(h.t, -e) : b.w;
-            if (sl == 0u) { // the hit outputs do not depend on the sample: the pass's first one writes them (NULL in later passes)
+            isHit = this->segment0(rec, h, seg);
+            if (sl == 0u) {
                 uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
                 if (isHit) {
-                    const float4* T = LayLegacy::triPtr(tris, h.tri);
-                    inst = __float_as_uint(T[0].w);
-                    prim = __float_as_uint(T[1].w);
-                }
-                if (q.t) q.t[rec] = h.t;
-                if (q.uv) reinterpret_cast<float2*>(q.uv)[rec] = make_float2(h.u, h.v);
-                if (q.inst) q.inst[rec] = inst;
-                if (q.prim) q.prim[rec] = prim;
+    inst = this->hitId(h, 0);
+    prim = this->hitId(h, 1);
+}
+                Base::storeHit(q, rec, h, inst, prim);
             }
         }
         if (!isHit) { // throughput x miss colour, and the path ends
@@ -216,36 +153,6 @@ struct PathJob {
             setVec(kAlbedo, sf.albedo);
             setVec(kAux, f3(0.0f, 0.0f, 0.0f));
             nextLight(0u, Po);
-        }
-    }
-    // a shadow ray has ended: its light's contribution, then the next light
-    __device__ __forceinline__ void endShadow(bool occluded)
-    {
-        if (!occluded) {
-            const LightRec Lt = reinterpret_cast<const LightRec*>(q.lights)[light];
-            const LightTerm lt = lightTerm(Lt, r.o, vec(kN)); // (again rather than carried: the same inputs, the same bits)
-            F3 aux = vec(kAux);
-            addLight<false>(q, Lt, lt, vec(kN), vec(kAlbedo), f3(0.0f, 0.0f, 0.0f), aux);
-            setVec(kAux, aux);
-        }
-        nextLight(static_cast<uint32_t>(light) + 1u, r.o);
-    }
-    template <bool COUNT>
-    __device__ __forceinline__ void step(uint32_t& cntNodes, uint32_t& cntTris)
-    {
-        static_assert(COUNT == CNT, "PathJob<COUNT> runs under runQuery<COUNT>");
-        const float4* nodes = reinterpret_cast<const float4*>(q.c.nodes);
-        const float4* tris = reinterpret_cast<const float4*>(q.c.tris);
-        if (light == kClosest) {
-            Hit h = hit();
-            float tcull = cullBound(h.t); // (closestIteration sets t * kCullPad on an accepted hit: the same value for t >= 0)
-            closestIteration<COUNT, 8>(nodes, tris, r, tlim, tcull, stack, static_cast<int>(q.c.inner_min), h, cur, iters, cntNodes, cntTris);
-            setHit(h);
-            if (cur == LayLegacy::kDone) endClosest();
-        } else if (light >= 0) {
-            bool occluded = false; // (set by the leaf step that also ends the traversal: nothing to carry)
-            anyIteration<COUNT, 8>(nodes, tris, r, 0.0f, tlim, tlim * kCullPad, stack, static_cast<int>(q.inner_min_any), occluded, cur, iters, cntNodes, cntTris);
-            if (cur == LayLegacy::kDone) endShadow(occluded);
         }
     }
 };

@@ -1,5 +1,6 @@
-// Device-side skeleton of the persistent query kernels (ray_kernels.hip, point_kernels.hip, list_kernels.hip, shade_kernels.hip,
-// path_query_kernels.hip, whitted_kernels.hip, ao_kernels.hip, winding_kernels.hip): every lane holds one caller record, a wavefront refills its idle lanes from a
+// Device-side skeleton of the persistent query kernels (ray_kernels.hip, point_kernels.hip, list_kernels.hip, winding_kernels.hip
+// and, through the phase machine of lit_job.hip.h, shade_kernels.hip, ao_kernels.hip, whitted_kernels.hip, path_query_kernels.hip):
+// every lane holds one caller record, a wavefront refills its idle lanes from a
 // chunked global cursor.  The record window (RayTap), the driver loop every query kernel runs (runQuery) and the every-hit
 // traversal of the hit counts and the listing.  Device code only: the sizing of the persistent grid and the launch are
 // query_launch.cpp.  No frame kernel includes this.  (The refill threshold CRT_REFILL_MIN and lanesBelow are in

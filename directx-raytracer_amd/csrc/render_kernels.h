@@ -197,6 +197,16 @@ struct RayQueryParams {
     uint32_t* prim;
     unsigned char* occluded;      // occlusion: one byte per ray
 };
+// The outputs of crt_shade_rays* in every mode (ShadeQueryParams, WhittedQueryParams, AmbientQueryParams): each nullable
+struct ShadedOutputs {
+    float* rgb;                   // 3 floats per ray: the mode's colour, the miss colour on a miss
+    float* normal;                // 3 floats per ray: Surface::N, zero on a miss
+    float* albedo;                // 3 floats per ray: Surface::albedo, zero on a miss
+    float* t;                     // as RayQueryParams'
+    float* uv;
+    uint32_t* inst;
+    uint32_t* prim;
+};
 // shaded ray queries (shade_kernels.hip; crt_shade_rays*): closest hit of n ray records, then the context's shading mode at
 // the hit -- the frames' shading (shading.hip.h) for caller-supplied rays.  Every output is nullable
 struct ShadeQueryParams {
@@ -214,13 +224,7 @@ struct ShadeQueryParams {
     uint32_t mode;                // < 200
     float phong_ks;
     uint32_t phong_exp;
-    float* rgb;                   // 3 floats per ray: the mode's colour, the miss colour on a miss
-    float* normal;                // 3 floats per ray: Surface::N, zero on a miss
-    float* albedo;                // 3 floats per ray: Surface::albedo, zero on a miss
-    float* t;                     // as RayQueryParams'
-    float* uv;
-    uint32_t* inst;
-    uint32_t* prim;
+    ShadedOutputs out;
 };
 // path-traced ray queries (path_query_kernels.hip; crt_path_rays*): one pass of (record, sample) work items, numbered
 // sample-major: item = sample-in-pass * n_records + record; c.n = the items of the pass.  Every path leaves its radiance in its
@@ -251,7 +255,7 @@ struct PathQueryParams {
 };
 // Whitted ray queries (whitted_kernels.hip; crt_shade_rays* and the frames in mode 150): the closest hit of n ray records
 // followed through mirrors and glass (the specular chain of PathQueryParams' paths, at most max_bounces turns), then mode 100's
-// shading at the first surface that is neither.  The outputs are ShadeQueryParams'; every one is nullable
+// shading at the first surface that is neither.  The outputs are ShadeQueryParams'
 struct WhittedQueryParams {
     QueryCommon c;                // records: the rays; inner_min: tune_inner_min (the closest-hit phases)
     uint32_t inner_min_any;       // tune_inner_min_any (the shadow-ray phases)
@@ -269,21 +273,16 @@ struct WhittedQueryParams {
     uint32_t phong_exp;
     void* state;                  // scratch, kWhittedStateBytes per record: what is touched once per surface -- {T.rgb, k} and
                                   // Phong's view vector
-    float* rgb;                   // as ShadeQueryParams'
-    float* normal;
-    float* albedo;
-    float* t;
-    float* uv;
-    uint32_t* inst;
-    uint32_t* prim;
+    ShadedOutputs out;
 };
 constexpr size_t kWhittedStateBytes = 32; // two float4
 // a mode-150 or mode-120 frame's RGBA8 from its float colour (3 floats per pixel), the frames' unorm8 rule: n pixels
-int launchWhittedPack(const float* rgb, uint32_t* rgba8, uint32_t n, ihipStream_t* stream);
+// (whitted_kernels.hip)
+int launchRgbToRgba8(const float* rgb, uint32_t* rgba8, uint32_t n, ihipStream_t* stream);
 // Ambient-occlusion ray queries (ao_kernels.hip; crt_shade_rays* and the frames in mode 120): the closest hit of n ray records,
 // then `samples` any-hit rays from the hit point over (0, radius) in the first-bounce directions of the mode-200 paths of
 // (record, sample, seed); the colour is the share that escapes, or with `sky` mode 100's light plus albedo x miss x that share.
-// The outputs are ShadeQueryParams'; every one is nullable.  No record state outside the registers
+// The outputs are ShadeQueryParams'.  No record state outside the registers
 struct AmbientQueryParams {
     QueryCommon c;                // records: the rays; inner_min: tune_inner_min (the closest-hit phase)
     uint32_t inner_min_any;       // tune_inner_min_any (the shadow-ray and occlusion phases)
@@ -302,14 +301,13 @@ struct AmbientQueryParams {
     float radius;                 // the occlusion rays' tmax: option "ao_radius" of the root box's diagonal, or 10000
     uint32_t sky;                 // option "ao_sky"
     uint32_t seed;                // option "seed"
-    float* rgb;                   // as ShadeQueryParams'
-    float* normal;
-    float* albedo;
-    float* t;
-    float* uv;
-    uint32_t* inst;
-    uint32_t* prim;
+    ShadedOutputs out;
 };
+// The kernels take these structs by value: a member that moves changes their arguments, and with them the device code
+static_assert(offsetof(ShadeQueryParams, out) == 176 && sizeof(ShadeQueryParams) == 232, "ShadeQueryParams: layout");
+static_assert(offsetof(WhittedQueryParams, out) == 184 && sizeof(WhittedQueryParams) == 240, "WhittedQueryParams: layout");
+static_assert(offsetof(AmbientQueryParams, out) == 184 && sizeof(AmbientQueryParams) == 240, "AmbientQueryParams: layout");
+static_assert(offsetof(ShadedOutputs, prim) == 48 && sizeof(ShadedOutputs) == 56, "ShadedOutputs: seven pointers");
 // rad[sample * n_records + record] of n_samples samples added in sample order to `in` (3 float64 per record; NULL: zero);
 // the sums go to `out`, their mean over `total` samples to rgb (each nullable)
 int launchPathResolve(const void* rad, uint32_t n_records, uint32_t n_samples, const double* in, double* out, float* rgb, uint32_t total,

@@ -4,15 +4,12 @@
 // Fresnel split, no random numbers) and is shaded as ShadeJob (shade_kernels.hip) shades in mode 100 at the first surface that
 // is neither: one any-hit shadow ray per light with a positive cosine, addLight<true>.
 //
-// One job of runQuery (query.hip.h), joined from the phases of those two.  A lane's record goes through phases inside step():
-//   closest hit   segment 0: the record prescaled by 2^e (queryRay), exactly the traversal of crt_trace_rays; after a turn: the
-//                 plain unit-direction ray over (0, 10000), PathJob's bounce ray (goOn)
+// One job of runQuery (query.hip.h) on the phase machine of lit_job.hip.h.  What it adds:
+//   closest hit   after a turn: the plain unit-direction ray over (0, 10000), PathJob's bounce ray (goOn)
 //   end of it     segment 0 writes the hit outputs (t, uv, inst, prim, normal, albedo).  A miss gives T x miss colour and
 //                 CONSTANT T x albedo, and the record ends; REFLECTIVE / REFRACTIVE turn the lane into the next closest-hit
-//                 traversal at once, or end the record black after max_bounces turns; anything else goes on to its lights:
-//   shadow ray    for each light with a positive cosine, in light order, an any-hit traversal from the root (lightTerm,
-//                 addLight<true>: the code ShadeJob adds a light with)
-//   after the last light T x the gathered light is written and only then `cur` becomes kDone, so that runQuery refills the lane.
+//                 traversal at once, or end the record black after max_bounces turns; anything else goes on to its lights
+//   after the last light T x the gathered light is written and the record ends.
 // T is the product of the mirrors' albedos so far and k the number of turns.  With k = 0 every colour is written as it stands,
 // without the product: a record that meets no mirror and no glass gives ShadeJob's mode-100 bits.
 //
@@ -23,8 +20,7 @@
 // compiler computes once in front of the loop and then holds: tried, 95 VGPRs, and 4 spilled in the counting variant.)
 //
 // Arithmetic contract: every function called here is the one the frames, ShadeJob and PathJob call (shading.hip.h).
-#include "query.hip.h"
-#include "shading.hip.h"
+#include "lit_job.hip.h"
 
 namespace crt {
 namespace {
@@ -37,47 +33,16 @@ namespace {
 constexpr int kWhittedWaves = CRT_WHITTED_WAVES;
 
 template <bool CNT>
-struct WhittedJob {
-    static constexpr int kClosest = -1; // `light` while a closest-hit ray (the record's own, or a turn's) is walked
-    static constexpr int kIdle = -2;    // no record, or a finished one
-
-    const WhittedQueryParams& q;
-    Stack stack;
-    Ray r;    // closest phase: segment 0 the prescaled record, later the turn's ray; shadow phase: the shadow ray (r.o = the biased hit point)
-    int cur;
-    int light = kIdle;  // >= 0: the light whose shadow ray is being walked
+struct WhittedJob : LitJob<WhittedJob<CNT>, WhittedQueryParams, CNT> {
+    using Base = LitJob<WhittedJob<CNT>, WhittedQueryParams, CNT>;
+    using Base::q; using Base::stack; using Base::r; using Base::cur; using Base::light; using Base::idx; using Base::tlim;
+    using Base::kClosest; using Base::kIdle; using Base::kN; using Base::kAlbedo; using Base::kRgb; using Base::hit;
+    using Base::setHit; using Base::vec; using Base::setVec; using Base::store3; using Base::nextLight;
     // Registers are what limits this kernel, as PathJob: nothing is held that can be had again
-    uint32_t idx = 0;   // the record
-    float tlim = 0.0f;  // closest phase: tmin (segment 0: the record's, prescaled; later 0); shadow phase: tmax = the light's distance
-    // One set of registers for the two phases, as ShadeJob's: closest phase the best hit {t, u, v, tri, gid} (w[0..4]), shadow
-    // phases the normal, the albedo and the light gathered so far (w[0..2], [3..5], [6..8])
-    float w[9];
-    __device__ __forceinline__ Hit hit() const { return Hit{ w[0], w[1], w[2], __float_as_uint(w[3]), __float_as_uint(w[4]) }; }
-    __device__ __forceinline__ void setHit(const Hit& h) { w[0] = h.t; w[1] = h.u; w[2] = h.v; w[3] = __uint_as_float(h.tri); w[4] = __uint_as_float(h.gid); }
-    __device__ __forceinline__ F3 vec(int k) const { return f3(w[3 * k], w[3 * k + 1], w[3 * k + 2]); }
-    __device__ __forceinline__ void setVec(int k, F3 v) { w[3 * k] = v.x; w[3 * k + 1] = v.y; w[3 * k + 2] = v.z; }
-    static constexpr int kN = 0, kAlbedo = 1, kRgb = 2;
-    uint32_t iters = 0;
-    uint32_t cntShadow = 0, cntTurn = 0;
+    uint32_t cntTurn = 0;
 
-    __device__ __forceinline__ explicit WhittedJob(const WhittedQueryParams& params) : q(params)
-    {
-        r = makeRay(f3(0.0f, 0.0f, 0.0f), f3(0.0f, 0.0f, 1.0f));
-        for (float& x : w) x = 0.0f;
-    }
-    // (counting) the wavefront's shadow and turn rays: runQuery adds the fetch counts itself.  Runs when runQuery's loop has
-    // ended, every lane active
-    __device__ __forceinline__ ~WhittedJob()
-    {
-        if (CNT) {
-            const uint32_t s = waveTotal(cntShadow), b = waveTotal(cntTurn);
-            if ((threadIdx.x & 63u) == 0u) {
-                atomicAdd(&q.c.counters[2], static_cast<unsigned long long>(s));
-                atomicAdd(&q.c.counters[3], static_cast<unsigned long long>(b));
-            }
-        }
-    }
-    __device__ __forceinline__ void retire(uint32_t) {}
+    __device__ __forceinline__ explicit WhittedJob(const WhittedQueryParams& params) : Base(params) {}
+    __device__ __forceinline__ ~WhittedJob() { this->template addCounts<true>(cntTurn); } // the shadow and the turn rays
     // The record's scratch slot: [0] = {T.rgb, k | kHasT}, [1] = {view.xyz, 0}.  T is stored by the first mirror and stands for
     // (1, 1, 1) until then (kHasT clear): start() writes the one word.  (Written as the constant {1, 1, 1, 0} there, the four
     // registers of that constant stayed allocated through the traversal loops and the kernel spilled.)
@@ -90,21 +55,8 @@ struct WhittedJob {
     __device__ __forceinline__ float4* slot() const { return static_cast<float4*>(q.state) + 2u * static_cast<size_t>(idx); }
     __device__ __forceinline__ void start(uint32_t i)
     {
-        const float4* rays = reinterpret_cast<const float4*>(q.c.records);
-        const float4 a = rays[2u * static_cast<size_t>(i)], b = rays[2u * static_cast<size_t>(i) + 1u];
-        idx = i;
-        float tmax;
-        queryRay(a, b, r, tlim, tmax);
-        setHit(Hit{ tmax, 0.0f, 0.0f, 0u, 0u });
-        light = kClosest;
+        Base::start(i);
         reinterpret_cast<uint32_t*>(slot())[3] = 0u; // k = 0, T = (1, 1, 1)
-        // a record with a NaN or an empty interval is not traced: step() finishes it as a miss
-        cur = (queryRayOk(a, b, tlim, tmax) & (q.c.n_nodes != 0u)) ? LayLegacy::kRoot : LayLegacy::kDone;
-    }
-    static __device__ __forceinline__ void store3(float* out, uint32_t i, F3 v)
-    {
-        float* o = out + 3u * static_cast<size_t>(i);
-        o[0] = v.x; o[1] = v.y; o[2] = v.z;
     }
     // the record ends with light L reaching its last surface (or the miss colour, or an emitter's albedo): L itself before the
     // first turn, T x L after it
@@ -115,7 +67,7 @@ struct WhittedJob {
             const F3 T = throughput(Tk);
             L = f3(fmaf(T.x, L.x, 0.0f), fmaf(T.y, L.y, 0.0f), fmaf(T.z, L.z, 0.0f));
         }
-        if (q.rgb) store3(q.rgb, idx, L);
+        if (q.out.rgb) store3(q.out.rgb, idx, L);
         light = kIdle;
         cur = LayLegacy::kDone;
     }
@@ -130,23 +82,13 @@ struct WhittedJob {
         light = kClosest;
         if (CNT) cntTurn++;
     }
-    // the shadow ray of the first light from `from` on that sees the surface from its front, or the end of the record
-    __device__ __forceinline__ void nextLight(uint32_t from, F3 Po)
+    __device__ __forceinline__ void afterLights(F3) { finish(vec(kRgb)); }
+    // Phong's view vector: minus the direction of the segment that reached the lit surface, from the scratch slot
+    static constexpr bool kPhong = true;
+    __device__ __forceinline__ F3 viewVector() const
     {
-        const LightRec* lights = reinterpret_cast<const LightRec*>(q.lights);
-        for (uint32_t li = from; li < q.n_lights; li++) {
-            const LightTerm lt = lightTerm(lights[li], Po, vec(kN));
-            if (lt.cosv > 0.0f) {
-                r = makeRay(Po, lt.Ld);
-                tlim = lt.dist;
-                stack.sp = 0;
-                cur = LayLegacy::kRoot;
-                light = static_cast<int>(li);
-                if (CNT) cntShadow++;
-                return;
-            }
-        }
-        finish(vec(kRgb));
+        const float4 v = slot()[1];
+        return f3(v.x, v.y, v.z);
     }
     // a closest-hit traversal has ended (or, for an untraced record, never began)
     __device__ __forceinline__ void endClosest()
@@ -157,29 +99,16 @@ struct WhittedJob {
         bool isHit = h.t < kTMax;
         Ray seg = r; // what the shading sees: origin, direction (of seg only o and d are read) and h.t
         if (first) {
-            // the record as the caller wrote it and the unscaled t (ShadeJob::endClosest), and the hit outputs
-            const float4* rays = reinterpret_cast<const float4*>(q.c.records);
-            const float4 a = rays[2u * static_cast<size_t>(idx)], b = rays[2u * static_cast<size_t>(idx) + 1u];
-            Ray scaled;
-            float tminRec, tmaxRec;
-            const int e = queryRay(a, b, scaled, tminRec, tmaxRec);
-            isHit = h.t < tmaxRec;
-            seg.o = f3(a.x, a.y, a.z);
-            seg.d = f3(b.x, b.y, b.z);
-            h.t = isHit ? __builtin_amdgcn_ldexpf(h.t, -e) : b.w;
+            isHit = this->segment0(idx, h, seg);
             uint32_t inst = 0xFFFFFFFFu, prim = 0xFFFFFFFFu;
-            if (isHit) { // (an empty scene has no triangle record to read)
-                const float4* T = LayLegacy::triPtr(tris, h.tri);
-                inst = __float_as_uint(T[0].w); // v0.w = mesh ordinal
-                prim = __float_as_uint(T[1].w); // e1.w = triangle of the mesh
-            }
-            if (q.t) q.t[idx] = h.t;
-            if (q.uv) reinterpret_cast<float2*>(q.uv)[idx] = make_float2(h.u, h.v);
-            if (q.inst) q.inst[idx] = inst;
-            if (q.prim) q.prim[idx] = prim;
+            if (isHit) {
+    inst = this->hitId(h, 0);
+    prim = this->hitId(h, 1);
+}
+            Base::storeHit(q.out, idx, h, inst, prim); // the record as the caller wrote it, the unscaled t; the hit outputs
             if (!isHit) {
-                if (q.normal) store3(q.normal, idx, f3(0.0f, 0.0f, 0.0f));
-                if (q.albedo) store3(q.albedo, idx, f3(0.0f, 0.0f, 0.0f));
+                if (q.out.normal) store3(q.out.normal, idx, f3(0.0f, 0.0f, 0.0f));
+                if (q.out.albedo) store3(q.out.albedo, idx, f3(0.0f, 0.0f, 0.0f));
             }
         }
         if (!isHit) {
@@ -191,17 +120,17 @@ struct WhittedJob {
         const uint32_t k = __float_as_uint(Tk.w) & kTurns;
         const F3 T = throughput(Tk);
         if (k == 0u) {
-            if (q.normal) store3(q.normal, idx, sf.N);
-            if (q.albedo) store3(q.albedo, idx, sf.albedo);
+            if (q.out.normal) store3(q.out.normal, idx, sf.N);
+            if (q.out.albedo) store3(q.out.albedo, idx, sf.albedo);
         }
         F3 Po = biasPoint(sf.P, sf.N, kShadowBias);
         if (sf.mtype == 4u) { // CONSTANT: emits and ends.  T x albedo before the first turn too, as a path's first segment
-            if (q.rgb) store3(q.rgb, idx, f3(fmaf(T.x, sf.albedo.x, 0.0f), fmaf(T.y, sf.albedo.y, 0.0f), fmaf(T.z, sf.albedo.z, 0.0f)));
+            if (q.out.rgb) store3(q.out.rgb, idx, f3(fmaf(T.x, sf.albedo.x, 0.0f), fmaf(T.y, sf.albedo.y, 0.0f), fmaf(T.z, sf.albedo.z, 0.0f)));
             light = kIdle;
             cur = LayLegacy::kDone;
         } else if (sf.mtype == 2u || sf.mtype == 3u) {
             if (k == q.max_bounces) { // the chain is cut: black, as a path's
-                if (q.rgb) store3(q.rgb, idx, f3(0.0f, 0.0f, 0.0f));
+                if (q.out.rgb) store3(q.out.rgb, idx, f3(0.0f, 0.0f, 0.0f));
                 light = kIdle;
                 cur = LayLegacy::kDone;
             } else if (sf.mtype == 2u) { // REFLECTIVE
@@ -221,41 +150,6 @@ struct WhittedJob {
             nextLight(0u, Po);
         }
     }
-    // a shadow ray has ended: its light's contribution, then the next light
-    __device__ __forceinline__ void endShadow(bool occluded)
-    {
-        if (!occluded) {
-            const LightRec Lt = reinterpret_cast<const LightRec*>(q.lights)[light];
-            const LightTerm lt = lightTerm(Lt, r.o, vec(kN)); // (again rather than carried: the same inputs, the same bits)
-            F3 view = f3(0.0f, 0.0f, 0.0f);
-            if (q.phong_ks > 0.0f) {
-                const float4 v = slot()[1];
-                view = f3(v.x, v.y, v.z);
-            }
-            F3 rgb = vec(kRgb);
-            addLight<true>(q, Lt, lt, vec(kN), vec(kAlbedo), view, rgb);
-            setVec(kRgb, rgb);
-        }
-        nextLight(static_cast<uint32_t>(light) + 1u, r.o);
-    }
-    template <bool COUNT>
-    __device__ __forceinline__ void step(uint32_t& cntNodes, uint32_t& cntTris)
-    {
-        static_assert(COUNT == CNT, "WhittedJob<COUNT> runs under runQuery<COUNT>");
-        const float4* nodes = reinterpret_cast<const float4*>(q.c.nodes);
-        const float4* tris = reinterpret_cast<const float4*>(q.c.tris);
-        if (light == kClosest) {
-            Hit h = hit();
-            float tcull = cullBound(h.t); // (closestIteration sets t * kCullPad on an accepted hit: the same value for t >= 0)
-            closestIteration<COUNT, 8>(nodes, tris, r, tlim, tcull, stack, static_cast<int>(q.c.inner_min), h, cur, iters, cntNodes, cntTris);
-            setHit(h);
-            if (cur == LayLegacy::kDone) endClosest();
-        } else if (light >= 0) {
-            bool occluded = false; // (set by the leaf step that also ends the traversal: nothing to carry)
-            anyIteration<COUNT, 8>(nodes, tris, r, 0.0f, tlim, tlim * kCullPad, stack, static_cast<int>(q.inner_min_any), occluded, cur, iters, cntNodes, cntTris);
-            if (cur == LayLegacy::kDone) endShadow(occluded);
-        }
-    }
 };
 
 template <bool COUNT>
@@ -264,8 +158,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kWhittedWave
     runQuery<COUNT, WhittedJob<COUNT>>(q);
 }
 
-// One thread per pixel of a mode-150 frame: the float colour the query wrote, quantised as every frame kernel quantises its own
-__global__ __launch_bounds__(256) void whittedPackKernel(const float* __restrict__ rgb, uint32_t* __restrict__ rgba8, uint32_t n)
+// One thread per pixel of a mode-150 or mode-120 frame: the float colour the query wrote, quantised as every frame kernel quantises its own
+__global__ __launch_bounds__(256) void rgbToRgba8Kernel(const float* __restrict__ rgb, uint32_t* __restrict__ rgba8, uint32_t n)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x; // n <= 2^28
     if (i >= n) return;
@@ -278,11 +172,11 @@ __global__ __launch_bounds__(256) void whittedPackKernel(const float* __restrict
 // the kind of this file for launchQuery (render_kernels.h)
 QueryKernel kKernelWhitted = { reinterpret_cast<const void*>(&whittedQueryKernel<false>), reinterpret_cast<const void*>(&whittedQueryKernel<true>), 1u };
 
-int launchWhittedPack(const float* rgb, uint32_t* rgba8, uint32_t n, ihipStream_t* stream)
+int launchRgbToRgba8(const float* rgb, uint32_t* rgba8, uint32_t n, ihipStream_t* stream)
 {
     if (n == 0u) return static_cast<int>(hipSuccess);
     const dim3 g((n + 255u) / 256u), block(256);
-    hipLaunchKernelGGL(whittedPackKernel, g, block, 0, stream, rgb, rgba8, n);
+    hipLaunchKernelGGL(rgbToRgba8Kernel, g, block, 0, stream, rgb, rgba8, n);
     return static_cast<int>(hipGetLastError());
 }
 

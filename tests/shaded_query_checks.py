@@ -2,7 +2,7 @@
 crt_frame_guides*, include/crt_hip.h) on scenes other test files build: poisoned, rebuilt, refitted, textured or far from the origin.
 Every shaded kernel is meant: modes 3 and 100 of shade_kernels.hip, and the two kinds with phase machines of their own over
 the shared traversal, mode 120 (ambient occlusion, ao_kernels.hip) and mode 150 (Whitted, whitted_kernels.hip), as queries in
-their three forms and as frames (runAmbientFrame, runWhitted).  Mode 120 has a reference made on the CPU alone
+their three forms and as frames (runShaded).  Mode 120 has a reference made on the CPU alone
 (ambient_reference: the oracle's hits and direct light, tests/ao_reference.c, brute-force occlusion of the probes); mode 150 is
 mode 100 where every material is mode 100's and the oracle's mode-200 frames along its chain elsewhere (whitted_reference).
 
